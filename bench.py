@@ -12,11 +12,19 @@ describes.  value = sentences all ranks processed / max-over-ranks wall time.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N --inproc          # ONE process, N GPUs inside libbert.so (BERT_HIP_DEVICES, RCCL gather)
+    python bench.py --full                     # + everything below (roofline, host APIs, CPU baselines, `also`)
+    python bench.py --dump-outputs DIR         # + DIR/embeddings.npy: what the last timed step computed
 
-Prints ONE JSON line on rank 0 (contract in the task description).  The timed region of K steps is
-repeated (--repeat, default 5): `value` / `ms_per_step` are the MEDIAN region, `regions` lists them all
-(the boxes of the pool and the chip's power management spread single regions by several percent).
-Extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better,
+scaling, vs_baseline, dtype, data, config, regions.  A plain run sets up, runs W warm-up steps, times
+exactly K steps (one region), optionally writes its outputs and prints the line; nothing else.
+--dump-outputs DIR: after the timed steps, the [B, H] float32 embeddings of the last step as the caller
+of the timed path receives them (at N > 1 the gathered [N * B, H] matrix), DIR/embeddings.npy; an
+output above 64 MB is replaced by a fixed seeded sample of rows (embeddings_sample.npy, row indices in
+embeddings_sample_rows.npy).  Inputs are seeded: the same arguments give the same inputs every run.
+--full adds what takes runs of its own.  Its timed region of K steps is repeated (--repeat, default 5
+with --full, 1 without): `value` / `ms_per_step` are the MEDIAN region, `regions` lists them all (the
+chip's power management spreads single regions by several percent).  Extra objects:
   roofline     — dominant kernel, algorithmic FLOPs per launch / HIP-event launch duration vs the
                  dense f16 MFMA peak (2.5 PFLOP/s); traffic = HBM bytes per launch from the committed
                  rocprofv3 PMC pass (profiles/traffic.json);
@@ -149,6 +157,34 @@ def timed_regions(step, steps, warmup, repeat, sync, barrier=None, reduce_max=No
     return out
 
 
+def device_rows_to_host(ptr, B, H):
+    """A [B, H] f32 matrix that lives in a context's device buffer (the gather entry point's result): a host copy (hipMemcpy D2H)."""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    host = np.empty((B, H), dtype=np.float32)
+    assert hip.hipDeviceSynchronize() == 0
+    assert hip.hipMemcpy(ctypes.c_void_p(host.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(host.nbytes), 2) == 0
+    return host
+
+
+DUMP_LIMIT = 64 * 10**6          # bytes written by --dump-outputs, all files together
+DUMP_SAMPLE_ROWS = 4096
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: array} -> out_dir/<name>.npy in float32 (float64 stays float64).  An array above the limit is
+    replaced by a fixed seeded sample of its rows (<name>_sample.npy, the row indices in <name>_sample_rows.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > DUMP_LIMIT // len(arrays):
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(DUMP_SAMPLE_ROWS, a.shape[0]), replace=False))
+            np.save(os.path.join(out_dir, f"{name}_sample_rows.npy"), rows.astype(np.float64))
+            name, a = f"{name}_sample", a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def run_config(cfg_id, args, rank, world, device, dist, torch, tmpdir, steps=None, warmup=None, repeat=None):
     cfg = CONFIGS[cfg_id]
     hp = gf.MODEL_DIMS[cfg["dims"]]
@@ -228,14 +264,11 @@ def run_config(cfg_id, args, rank, world, device, dist, torch, tmpdir, steps=Non
             w.wait()
     out = torch.from_numpy(h_out) if h_out is not None else d_outs[(turn[0] - 1) & 1 if world > 1 and turn[0] else 0]
     if cfg.get("gather_step"):
-        # the gathered matrix lives in the context's device buffer: fetch a copy through torch (hipMemcpy D2H)
-        import ctypes
-        hip = ctypes.CDLL("libamdhip64.so")
-        host = np.empty((B, H), dtype=np.float32)
         torch.cuda.synchronize(device)
-        assert hip.hipMemcpy(ctypes.c_void_p(host.ctypes.data), ctypes.c_void_p(gathered["ptr"]), ctypes.c_size_t(host.nbytes), 2) == 0
-        out = torch.from_numpy(host)
-    res = dict(cfg=cfg, cfg_id=cfg_id, hp=hp, model=model, path=path, flat=flat, cu=cu, out=out, steps=steps, regions=regions, world=world,
+        out = torch.from_numpy(device_rows_to_host(gathered["ptr"], B, H))
+    # what a caller of the timed path receives from its last step: at N > 1 the gathered [N * B, H] matrix
+    result = d_alls[(turn[0] - 1) & 1] if d_alls is not None and turn[0] else out
+    res = dict(cfg=cfg, cfg_id=cfg_id, hp=hp, model=model, path=path, flat=flat, cu=cu, out=out, result=result, steps=steps, regions=regions, world=world,
                value=world * B * steps / dt, ms_per_step=1e3 * dt / steps, step=step, tokens=T, max_len=max_len)
     return res
 
@@ -727,15 +760,16 @@ def run_inproc(args):
         m = load_model(cfg, path)
         ids, cu, _ = config_inputs(dict(cfg, batch=cfg["batch"] * n), args.config, hp, 0)
         B = len(cu) - 1
-        step = lambda: m.eval_packed_gather(ids, cu)
+        last = {}
+
+        def step():
+            last["ptrs"] = m.eval_packed_gather(ids, cu)
         regions = timed_regions(step, args.steps, args.warmup, args.repeat, lambda: None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"embeddings": device_rows_to_host(last["ptrs"][0], B, hp.n_embd)})
         dt = float(np.median(regions))
         r = sorted(B * args.steps / np.asarray(regions))
         fps = flops_per_sentence(hp, cfg["seq_len"] or 25)
-        # per-kernel HIP-event times of device 0 (every device runs the same launches on its shard)
-        res = dict(cfg=dict(cfg, host_step=True), cfg_id=args.config, hp=hp, model=m, path=path, flat=ids, cu=cu, step=step, tokens=int(cu[-1]),
-                   value=B * args.steps / dt, ms_per_step=1e3 * dt / args.steps, steps=args.steps, regions=regions)
-        roof, bd = kernel_roofline(res, None, None, steps=3, sync=lambda: None)
         contract = {
             "metric": "sentences/sec (seq_len=%s)" % cfg["seq_len"], "value": B * args.steps / dt, "unit": "sentences/s", "n_gpus": m.n_devices(),
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -743,8 +777,16 @@ def run_inproc(args):
             "config": {"workload": cfg["name"], "per_gpu_batch": cfg["batch"], "global_batch": B, "seq_len": cfg["seq_len"],
                        "weights": cfg["ftype"], "parallelism": f"dp{n} in one process (libbert.so: engine + thread + stream per device, "
                                                                 "RCCL all-gather per step; ids start in HOST memory)"}}
-        e = {"regions": {"n": len(r), "steps_each": args.steps, "median": float(np.median(r)), "min": float(r[0]), "max": float(r[-1])},
-             "path_gflop_per_sentence": fps / 1e9, "path_mfma_frac": B * args.steps / dt * fps / (n * MFMA_PEAK_F16),
+        regions_e = {"n": len(r), "steps_each": args.steps, "median": float(np.median(r)), "min": float(r[0]), "max": float(r[-1])}
+        if not args.full:
+            emit_line(dict(contract, regions={k: sig(v) for k, v in regions_e.items()}))
+            m.close()
+            return
+        # per-kernel HIP-event times of device 0 (every device runs the same launches on its shard)
+        res = dict(cfg=dict(cfg, host_step=True), cfg_id=args.config, hp=hp, model=m, path=path, flat=ids, cu=cu, step=step, tokens=int(cu[-1]),
+                   value=B * args.steps / dt, ms_per_step=1e3 * dt / args.steps, steps=args.steps, regions=regions)
+        roof, bd = kernel_roofline(res, None, None, steps=3, sync=lambda: None)
+        e = {"regions": regions_e, "path_gflop_per_sentence": fps / 1e9, "path_mfma_frac": B * args.steps / dt * fps / (n * MFMA_PEAK_F16),
              "roofline": roof, "kernel_ms_per_step_timed_alone_upper_bound": bd}
         if not args.no_cpu_baseline:
             host = m.eval_packed(ids[:int(cu[min(B, 64)])], cu[:min(B, 64) + 1])
@@ -774,13 +816,20 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeat", type=int, default=5, help="timed regions of --steps steps each; value = the median region")
+    ap.add_argument("--repeat", type=int, default=None,
+                    help="timed regions of --steps steps each; value = the median region (default 1; 5 with --full)")
     ap.add_argument("--config", type=int, default=1, choices=sorted(CONFIGS))
     ap.add_argument("--also", type=int, nargs="*", default=None,
                     help="extra configs reported under 'also' (default at N=1 with config 1: 2, 22, 3, 33, 4, 42, 44, 45, 5, 55, 58)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--inproc", action="store_true", help="one process, --gpus N devices inside libbert.so")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline, per-kernel times, host APIs, CPU baselines, the `also` configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's embeddings to DIR/embeddings.npy (float32; a seeded row sample above 64 MB)")
     args = ap.parse_args()
+    if args.repeat is None:
+        args.repeat = 5 if args.full else 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -820,13 +869,8 @@ def main():
         contract = e = None
         if rank == 0:
             cfg = res["cfg"]
-            prof_steps = int(min(20, max(2, 0.4 / (res["ms_per_step"] * 1e-3))))        # (about 0.4 s of profiled steps)
-            e = report(res, world, torch, device, args, prof_steps=prof_steps, cpu_budget=10.0, replay_groups=3, headline=True)
-            if world == 1 and not args.no_cpu_baseline and cfg["seq_len"]:
-                try:
-                    e["cpu_torch_fp32"] = cpu_torch_fp32(res["hp"], cfg["seq_len"], budget_s=4.0)
-                except Exception as ex:
-                    e["cpu_torch_fp32"] = {"error": f"{type(ex).__name__}: {ex}"}
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"embeddings": res["result"].cpu().numpy()})
             contract = {
                 "metric": "sentences/sec (seq_len=%s)" % cfg["seq_len"], "value": res["value"], "unit": "sentences/s",
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
@@ -839,6 +883,24 @@ def main():
             }
             if shared:
                 contract["validation_only"] = "BERT_BENCH_SHARED_GPU: the ranks share the box's GPU(s) and exchange over gloo — not a scaling measurement"
+        if not args.full:
+            # a plain run: set-up, warm-up, the timed steps, the outputs, the line — nothing else
+            if rank == 0:
+                r = sorted(world * res["cfg"]["batch"] * res["steps"] / np.asarray(res["regions"]))
+                emit_line(dict(contract, regions={"n": len(r), "steps_each": res["steps"], "median": sig(float(np.median(r))),
+                                                  "min": sig(float(r[0])), "max": sig(float(r[-1]))}))
+            res["model"].close()
+            if world > 1:
+                dist.destroy_process_group()
+            return
+        if rank == 0:
+            prof_steps = int(min(20, max(2, 0.4 / (res["ms_per_step"] * 1e-3))))        # (about 0.4 s of profiled steps)
+            e = report(res, world, torch, device, args, prof_steps=prof_steps, cpu_budget=10.0, replay_groups=3, headline=True)
+            if world == 1 and not args.no_cpu_baseline and cfg["seq_len"]:
+                try:
+                    e["cpu_torch_fp32"] = cpu_torch_fp32(res["hp"], cfg["seq_len"], budget_s=4.0)
+                except Exception as ex:
+                    e["cpu_torch_fp32"] = {"error": f"{type(ex).__name__}: {ex}"}
             if "host_api" in e:
                 # SURVEY.md §8(d) quotes the metric host to host; the bench contract keeps `value` on HBM-resident inputs
                 # ("the PCIe-inclusive rate ... is never `value`"), so the host-to-host rate travels beside it, in `config` too

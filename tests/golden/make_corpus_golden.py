@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Writes tests/golden/sample_texts_golden.json: the first 200 lines of the reference's sample texts (a DATA file of the reference,
-examples/sample_client_texts.txt — what its sample client and server embed) with the token ids the ORACLE's line-for-line restatement
-of bert_tokenize (oracle/bert_oracle.cpp, reference bert.cpp:199-325) gives them on a small English vocabulary written here.  Run in
-the container that has /root/reference; the fixture travels to the GPU box, where the reference tree does not exist.  The product's
+examples/sample_client_texts.txt — what its sample client and server embed; its first 600 lines are committed as
+tests/golden/sample_client_texts_600.txt) with the token ids the ORACLE's line-for-line restatement of bert_tokenize
+(oracle/bert_oracle.cpp, reference bert.cpp:199-325) gives them on a small English vocabulary written here.  The product's
 tokenizer is tested against these ids (tests/test_host.py, tests/test_gpu_exactness.py); nothing in the product reads the fixture."""
 import json
 import os
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from conftest import write_vocab_only_model  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 
-SRC = "/root/reference/examples/sample_client_texts.txt"
+SRC = os.path.join(ROOT, "tests", "golden", "sample_client_texts_600.txt")
 N_LINES = 200
 N_MAX_TOKENS = 64
 

@@ -31,7 +31,7 @@ def test_tokenizer_fuzz_matches_oracle_on_the_gpu_box(fuzz_vocab_model):  # noqa
 
 
 def test_tokenizer_on_committed_reference_texts_on_the_gpu_box(corpus_golden):  # noqa: F811
-    """(the reference's sample texts: tests/test_host.py skips the mounted-tree form of this test on the GPU box)"""
+    """(the reference's sample texts, from the committed fixture)"""
     test_host.test_tokenizer_on_committed_reference_texts(corpus_golden)
 
 

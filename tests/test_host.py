@@ -151,10 +151,8 @@ def test_tokenize_batch_on_threads_equals_one_by_one(fuzz_vocab_model):
 
 
 def test_tokenizer_on_reference_corpus_if_present(sparse_vocab_model):
-    """Real text (reference examples/sample_client_texts.txt) when the reference tree is mounted."""
-    path = "/root/reference/examples/sample_client_texts.txt"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not mounted")
+    """Real text: the first 600 lines of the reference's examples/sample_client_texts.txt (tests/golden/sample_client_texts_600.txt)."""
+    path = os.path.join(ROOT, "tests", "golden", "sample_client_texts_600.txt")
     m = libbert.BertModel(sparse_vocab_model, tokenizer_only=True)
     o = orc.Oracle(sparse_vocab_model, vocab_only=True)
     with silenced_stderr():
@@ -175,10 +173,10 @@ def corpus_golden(tmp_path_factory):
 
 
 def test_tokenizer_on_committed_reference_texts(corpus_golden):
-    """The first 200 of the reference's own sample texts (tests/golden/sample_texts_golden.json, written by make_corpus_golden.py where the
-    reference tree is mounted): the product's bert_tokenize gives the ids the oracle's restatement of bert.cpp:199-325 gave — whole words,
+    """The first 200 of the reference's own sample texts (tests/golden/sample_texts_golden.json, written by make_corpus_golden.py from
+    tests/golden/sample_client_texts_600.txt): the product's bert_tokenize gives the ids the oracle's restatement of bert.cpp:199-325 gave — whole words,
     multi-piece splits, punctuation, unmatched bytes, truncation at n_max_tokens — and the oracle still gives them too.  Runs on the GPU
-    box as well (tests/test_gpu_exactness.py), where /root/reference does not exist."""
+    box as well (tests/test_gpu_exactness.py)."""
     g, path = corpus_golden
     m = libbert.BertModel(path, tokenizer_only=True)
     o = orc.Oracle(path, vocab_only=True)

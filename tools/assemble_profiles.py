@@ -48,7 +48,7 @@ bench_text = [l for l in read(f"bench_{tag}.log").splitlines() if l.startswith("
 line = json.loads(bench_text)                  # the ONE compact line (what the driver parses)
 assert len(bench_text) < 6144, len(bench_text)
 bench = json.loads(read(f"bench_detail_{tag}.json"))      # the full detail the same run wrote beside it (bench_detail.json)
-hdr = (f"# rocprofv3 --kernel-trace --stats -- python bench.py --steps 100 --warmup 10 --repeat 2 --no-cpu-baseline --also   (MI355X, round {tag[1:]}, commit {commit}; tools/gpu_round_check.sh)\n"
+hdr = (f"# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 100 --warmup 10 --repeat 2 --no-cpu-baseline --also   (MI355X, round {tag[1:]}, commit {commit}; tools/gpu_round_check.sh)\n"
        f"# config: all-MiniLM-L6-v2 dims f16, 256 x 128 tokens per step, 6 layers: ONE launch for all layers (model_kernel: a workgroup per window, qkv_attention2 + layer_tail as phases)\n"
        f"# same box, un-profiled default bench line: {bench['value'] / 1e3:.1f} k sentences/s (device-resident; host to host {bench['host_api']['value'] / 1e3:.1f} k; bert_eval_batch {bench['eval_batch_api']['value'] / 1e3:.1f} k), its own time of {bench['roofline']['kernel']} ({bench['roofline']['timing']}): {bench['roofline']['avg_launch_us']:.1f} us per launch\n"
        "# MFMA busy share = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs): " +
@@ -56,13 +56,13 @@ hdr = (f"# rocprofv3 --kernel-trace --stats -- python bench.py --steps 100 --war
 c3 = bench["also"]["config3"]
 with open(os.path.join(P, f"{tag}_kernel_stats.txt"), "w") as f:
     f.write(hdr + read(f"stats_{tag}.txt") +
-            f"\n# --config 3 (bert-base dims q4_1 expanded to f16 at load, 512 x 512 tokens per step, 12 layers): rocprofv3 --kernel-trace --stats -- python bench.py --config 3 --steps 3 --warmup 1 --repeat 1 --no-cpu-baseline --also\n"
+            f"\n# --config 3 (bert-base dims q4_1 expanded to f16 at load, 512 x 512 tokens per step, 12 layers): rocprofv3 --kernel-trace --stats -- python bench.py --full --config 3 --steps 3 --warmup 1 --repeat 1 --no-cpu-baseline --also\n"
             f"# gemm256_kernel<EPI, WT, LN>: EPI 0 = QKV (bias), 1 = FFN up (bias + GELU), 2 = attention output and FFN down (bias + residual); WT 0 = f16 image, 2 = q4_1 planes (layer 0's QKV); LN = the LayerNorm fold: 1 the input rows' statistics ride in (QKV of layers >= 1, FFN up), 4 / 6 = 4 the rows' partial sums go out + 2 the residual is rebuilt from the un-normalised rows (attention output, FFN down; 4 alone = layer 0's attention output); same box un-profiled: {c3['value']:.0f} sentences/s = {c3['path_mfma_frac']:.3f} of the MFMA peak\n" +
             read(f"stats_config3_{tag}.txt") +
             (f"\n# --config 33: the same model and batch with BERT_HIP_Q4=fused — the matrices stay 4-bit in HBM, gemm256_kernel<EPI, 2> (q4_1 planes) dequantises the blocks in its tile load; same box un-profiled: "
              f"{bench['also']['config3_fused']['value']:.0f} sentences/s\n" + read(f"stats_config33_{tag}.txt") if os.path.exists(os.path.join(g, f"stats_config33_{tag}.txt")) and "config3_fused" in bench["also"] else ""))
 with open(os.path.join(P, f"{tag}_pmc.txt"), "w") as f:
-    f.write(f"# rocprofv3 --pmc <set> --kernel-trace -- python bench.py --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also   (separate runs per counter set; mean per dispatch; commit {commit})\n"
+    f.write(f"# rocprofv3 --pmc <set> --kernel-trace -- python bench.py --full --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also   (separate runs per counter set; mean per dispatch; commit {commit})\n"
             "# SQ_* in quad-cycles except SQ_VALU_MFMA_BUSY_CYCLES (cycles); FETCH_SIZE / WRITE_SIZE in KiB, FETCH_SIZE must be doubled on gfx950 (MI355X_MICROARCH.md, HBM section)\n" +
             pmc1 + "\n" + pmc2 + "\n" + pmc3 + "\n# --config 3 (bert-base dims q4_1, 512 x 512 tokens): FETCH_SIZE / GRBM_GUI_ACTIVE / WRITE_SIZE\n" + pmc3c3)
 with open(os.path.join(P, "traffic.json"), "w") as f:

@@ -14,7 +14,7 @@ export TMPDIR=/tmp BERT_HIP_QUIET=1
 timeout 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_$TAG.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed" $OUT/pytest_$TAG.log | tail -1
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke_$TAG.log 2>&1; echo "smoke rc=$?"
 t0=$(date +%s)
-timeout 900 python bench.py > $OUT/bench_$TAG.log 2> $OUT/bench_$TAG.err; echo "bench rc=$? [$(( $(date +%s) - t0 )) s] line bytes $(tail -1 $OUT/bench_$TAG.log | wc -c)"; cut -c1-600 $OUT/bench_$TAG.log
+timeout 900 python bench.py --full > $OUT/bench_$TAG.log 2> $OUT/bench_$TAG.err; echo "bench rc=$? [$(( $(date +%s) - t0 )) s] line bytes $(tail -1 $OUT/bench_$TAG.log | wc -c)"; cut -c1-600 $OUT/bench_$TAG.log
 cp bench_detail.json $OUT/bench_detail_$TAG.json
 # the driver's own invocation (its clock around the run is what BENCH_rNN.json records)
 t0=$(date +%s)
@@ -23,13 +23,13 @@ timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_$
 cd /tmp
 # (100-step regions like the un-profiled line: a region's fixed costs — first launch, final synchronisation, the profiler's flush —
 # spread over 10 steps would inflate ms_per_step, which the in-place kernel's roofline time is derived from)
-B1="python $OUT/../bench.py --steps 100 --warmup 10 --repeat 2 --no-cpu-baseline --also"
+B1="python $OUT/../bench.py --full --steps 100 --warmup 10 --repeat 2 --no-cpu-baseline --also"
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_stats_$TAG -o stats -- $B1 > $OUT/bench_prof_$TAG.log 2>&1; echo "stats rc=$?"
-B3="python $OUT/../bench.py --config 3 --steps 3 --warmup 1 --repeat 1 --no-cpu-baseline --also"
+B3="python $OUT/../bench.py --full --config 3 --steps 3 --warmup 1 --repeat 1 --no-cpu-baseline --also"
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_stats3_$TAG -o stats -- $B3 > $OUT/bench_prof3_$TAG.log 2>&1; echo "stats3 rc=$?"
-B33="python $OUT/../bench.py --config 33 --steps 3 --warmup 1 --repeat 1 --no-cpu-baseline --also"
+B33="python $OUT/../bench.py --full --config 33 --steps 3 --warmup 1 --repeat 1 --no-cpu-baseline --also"
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_stats33_$TAG -o stats -- $B33 > $OUT/bench_prof33_$TAG.log 2>&1; echo "stats33 rc=$?"
-P1="python $OUT/../bench.py --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also"
+P1="python $OUT/../bench.py --full --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also"
 i=0
 for set in \
   "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY" \
@@ -40,7 +40,7 @@ done
 TR=""
 for cfg in 1 2 22 3 33 4 42 5; do
   key=config$cfg; [ $cfg = 22 ] && key=config2_expanded; [ $cfg = 5 ] && key=mixed_len; [ $cfg = 33 ] && key=config3_fused; [ $cfg = 42 ] && key=config4_fused
-  Pc="python $OUT/../bench.py --config $cfg --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also"
+  Pc="python $OUT/../bench.py --full --config $cfg --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also"
   timeout 400 rocprofv3 --pmc FETCH_SIZE GRBM_GUI_ACTIVE --kernel-trace -d $OUT/prof_fetch${cfg}_$TAG -o pmc -- $Pc > $OUT/bench_fetch${cfg}_$TAG.log 2>&1; echo "fetch$cfg rc=$?"
   timeout 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/prof_write${cfg}_$TAG -o pmc -- $Pc > $OUT/bench_write${cfg}_$TAG.log 2>&1; echo "write$cfg rc=$?"
   TR="$TR $key=$(find $OUT/prof_fetch${cfg}_$TAG -name '*_results.db' | head -1),$(find $OUT/prof_write${cfg}_$TAG -name '*_results.db' | head -1)"

@@ -4,7 +4,7 @@ set -u
 CFG=${1:-3}; TAG=${2:-c$CFG}
 export TMPDIR=/tmp BERT_HIP_QUIET=1
 OUT=$PWD/gpurun_out; mkdir -p $OUT
-P="python $OUT/../bench.py --config $CFG --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also"
+P="python $OUT/../bench.py --full --config $CFG --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also"
 cd /tmp
 i=0
 for set in \

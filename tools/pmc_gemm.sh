@@ -7,7 +7,7 @@ TAG=${TAG:-x}
 export TMPDIR=/tmp BERT_HIP_QUIET=1
 ROOT=$PWD
 cd /tmp
-P="python $ROOT/bench.py --config 3 --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also"
+P="python $ROOT/bench.py --full --config 3 --steps 2 --warmup 1 --repeat 1 --no-cpu-baseline --also"
 for set in "FETCH_SIZE GRBM_GUI_ACTIVE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"; do
   n=$(echo $set | tr ' ' '_')
   timeout 400 rocprofv3 --pmc $set --kernel-trace -d $OUT/prof_${TAG}_$n -o pmc -- $P > $OUT/pmc_run_$TAG.log 2>&1 || echo "rc=$? for $set"

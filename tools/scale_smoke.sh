@@ -35,10 +35,10 @@ done
 for n in 1 2 4 8; do
   [ $n -gt $MAX ] && break
   if [ $n -le $HAVE ]; then
-    timeout 900 python bench.py --gpus $n --inproc --steps $STEPS --warmup 3 --repeat 3 --no-cpu-baseline | cut -c1-400 || rc=1
+    timeout 900 python bench.py --full --gpus $n --inproc --steps $STEPS --warmup 3 --repeat 3 --no-cpu-baseline | cut -c1-400 || rc=1
   fi
   if [ $n -gt 1 ]; then
-    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n)) bench.py --gpus $n --steps $STEPS --warmup 3 --no-cpu-baseline --also | cut -c1-2500 || rc=1
+    timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n)) bench.py --full --gpus $n --steps $STEPS --warmup 3 --no-cpu-baseline --also | cut -c1-2500 || rc=1
   fi
 done
 exit $rc
