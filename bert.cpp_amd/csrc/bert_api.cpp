@@ -29,9 +29,16 @@
 #include "engine.h"
 #include "model_file.h"
 #include "multi_device.h"
+#include "search.h"
 #include "tokenizer.h"
 
 using namespace bert_hip;
+
+// an embedding index (search.h) and the context it was made from
+struct bert_hip_index {
+    bert_ctx *ctx = nullptr;
+    std::unique_ptr<Index> ix;
+};
 
 struct bert_ctx {
     HParams hp;
@@ -67,7 +74,10 @@ struct bert_ctx {
     std::vector<hipEvent_t> xdone;
     int gather_super_tokens = 0;        // option "gather_super_tokens": tokens per device and super-batch (0: four device chunks)
     RcclGather rccl;
+    // the caller's embedding indexes (bert_hip_index_create), freed with the context before its engines
+    std::vector<bert_hip_index *> indexes;
     ~bert_ctx() {
+        for (bert_hip_index *ix : indexes) delete ix;
         for (size_t d = 0; d < xstream.size(); ++d) {
             if (d < engines.size()) (void)hipSetDevice(engines[d]->device());
             if (xstream[d]) { (void)hipStreamSynchronize(xstream[d]); (void)hipStreamDestroy(xstream[d]); }
@@ -726,6 +736,205 @@ void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const char *valu
         else if (strcmp(key, "gather_super_tokens") == 0) ctx->gather_super_tokens = std::max(0, atoi(value));
         else
             for (auto &e : ctx->engines) e->set_option(key, value);
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// embedding index (search.h)
+// ------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+// Tokenizes and evaluates texts in groups on the context's first device; each group's embeddings [c][n_embd] land in the
+// index's device scratch buffer and are handed to use(i0, c, d_rows).  No host copy of the embeddings.
+template <class F>
+bool encode_groups_device(bert_ctx *ctx, Index &ix, int32_t n_threads, int32_t n, const char **texts, F &&use, std::string &err) {
+    const int32_t N = ctx->hp.n_max_tokens, H = ctx->hp.n_embd, G = 16384;
+    std::vector<bert_vocab_id> ids, packed;
+    std::vector<int32_t> ntok, cu;
+    for (int32_t i0 = 0; i0 < n; i0 += G) {
+        const int32_t c = std::min(G, n - i0);
+        ids.resize((size_t)c * N);
+        ntok.resize(c);
+        tokenize_many(ctx, n_threads, c, texts + i0, ids.data(), ntok.data());
+        cu.assign((size_t)c + 1, 0);
+        for (int32_t i = 0; i < c; ++i) {
+            if (ntok[i] <= 0 || ntok[i] > N) { err = "input " + std::to_string(i0 + i) + " cannot be evaluated"; return false; }
+            cu[i + 1] = cu[i] + ntok[i];
+        }
+        packed.resize((size_t)cu[c]);
+        for (int32_t i = 0; i < c; ++i) memcpy(packed.data() + cu[i], ids.data() + (size_t)i * N, sizeof(bert_vocab_id) * ntok[i]);
+        float *d = ix.scratch((size_t)c * H, err);
+        if (!d) return false;
+        // (blocking: the rows are in d when it returns)
+        if (ctx->engine()->eval_packed_host(packed.data(), cu.data(), c, nullptr, err, d) != 0) return false;
+        if (!use(i0, c, d)) return false;
+    }
+    return true;
+}
+
+// the multi-device route of the text entry points: bert_hip_encode_batch into host rows
+bool encode_host(bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts, std::vector<float> &emb, std::string &err) {
+    const size_t H = ctx->hp.n_embd;
+    emb.assign((size_t)n * H, 0.f);
+    std::vector<float *> rows((size_t)n);
+    for (int32_t i = 0; i < n; ++i) rows[i] = emb.data() + i * H;
+    const int32_t done = encode_batch_impl(ctx, n_threads, n, texts, rows.data());
+    if (done != n) { err = "input " + std::to_string(std::max(done, 0)) + " could not be encoded"; return false; }
+    return true;
+}
+
+bool index_ok(const bert_hip_index *ix, const char *me) {
+    if (!ix || !ix->ix) { fprintf(stderr, "%s: no index\n", me); return false; }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+struct bert_hip_index *bert_hip_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype) {
+    return guarded("bert_hip_index_create", (bert_hip_index *)nullptr, [&]() -> bert_hip_index * {
+        const char *me = "bert_hip_index_create";
+        if (!ctx) { fprintf(stderr, "%s: no context\n", me); return nullptr; }
+        if (!ctx->engine()) { fprintf(stderr, "%s: this context has no device (tokenizer-only): an index lives on the context's device\n", me); return nullptr; }
+        if (dim == 0) dim = ctx->hp.n_embd;
+        std::string err;
+        std::unique_ptr<Index> ix(Index::create(ctx->engine(), dim, dtype, err));
+        if (!ix) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return nullptr; }
+        std::unique_ptr<bert_hip_index> h(new bert_hip_index);
+        h->ctx = ctx;
+        h->ix = std::move(ix);
+        ctx->indexes.push_back(h.get());
+        return h.release();
+    });
+}
+
+void bert_hip_index_free(struct bert_hip_index *ix) {
+    guarded_void("bert_hip_index_free", [&] {
+        if (!ix) return;
+        auto &v = ix->ctx->indexes;
+        v.erase(std::remove(v.begin(), v.end(), ix), v.end());
+        delete ix;
+    });
+}
+
+int32_t bert_hip_index_size(struct bert_hip_index *ix) { return ix && ix->ix ? ix->ix->size() : -1; }
+
+int32_t bert_hip_index_reserve(struct bert_hip_index *ix, int32_t n_rows, int32_t n_queries, int32_t k) {
+    return guarded("bert_hip_index_reserve", (int32_t)-4, [&]() -> int32_t {
+        const char *me = "bert_hip_index_reserve";
+        if (!index_ok(ix, me)) return -1;
+        std::string err;
+        if (!ix->ix->reserve(n_rows, n_queries, k, err)) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return -3; }
+        return 0;
+    });
+}
+
+int32_t bert_hip_index_add(struct bert_hip_index *ix, int32_t n, const float *rows) {
+    return guarded("bert_hip_index_add", (int32_t)-4, [&]() -> int32_t {
+        const char *me = "bert_hip_index_add";
+        if (!index_ok(ix, me)) return -1;
+        std::string err;
+        const int first = ix->ix->add_host(n, rows, err);
+        if (first < 0) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return -3; }
+        return first;
+    });
+}
+
+int32_t bert_hip_index_add_device(struct bert_hip_index *ix, int32_t n, const float *d_rows, void *stream) {
+    return guarded("bert_hip_index_add_device", (int32_t)-4, [&]() -> int32_t {
+        const char *me = "bert_hip_index_add_device";
+        if (!index_ok(ix, me)) return -1;
+        std::string err;
+        const int first = ix->ix->add_device(n, d_rows, (hipStream_t)stream, err);
+        if (first < 0) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return -3; }
+        return first;
+    });
+}
+
+int32_t bert_hip_index_add_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n, const char **texts) {
+    return guarded("bert_hip_index_add_texts", (int32_t)-4, [&]() -> int32_t {
+        const char *me = "bert_hip_index_add_texts";
+        if (!index_ok(ix, me)) return -1;
+        bert_ctx *ctx = ix->ctx;
+        Index &x = *ix->ix;
+        if (x.dim() != ctx->hp.n_embd) { fprintf(stderr, "%s: the index has dim %d, the model's embeddings %d\n", me, x.dim(), ctx->hp.n_embd); return -2; }
+        if (n < 0 || (n > 0 && !texts)) { fprintf(stderr, "%s: n >= 0 and texts required\n", me); return -2; }
+        const int first = x.size();
+        if (n == 0) return first;
+        std::string err;
+        bool ok;
+        if (ctx->engines.size() > 1) {
+            std::vector<float> emb;
+            ok = encode_host(ctx, n_threads, n, texts, emb, err) && x.add_host(n, emb.data(), err) >= 0;
+        } else {
+            ok = encode_groups_device(ctx, x, n_threads, n, texts, [&](int32_t, int32_t c, const float *d) {
+                return x.add_device(c, d, x.stream(), err) >= 0 && hipStreamSynchronize(x.stream()) == hipSuccess;
+            }, err);
+        }
+        if (!ok) {
+            x.truncate(first);
+            fprintf(stderr, "%s: %s\n", me, err.empty() ? "device error" : err.c_str());
+            return -3;
+        }
+        return first;
+    });
+}
+
+int32_t bert_hip_index_search(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t k, int32_t *ids, float *scores) {
+    return guarded("bert_hip_index_search", (int32_t)-4, [&]() -> int32_t {
+        const char *me = "bert_hip_index_search";
+        if (!index_ok(ix, me)) return -1;
+        std::string err;
+        if (ix->ix->search_to_host(n_queries, queries, false, k, ids, scores, err) != 0) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return -3; }
+        return 0;
+    });
+}
+
+int32_t bert_hip_index_search_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t k, int32_t *d_ids,
+                                     float *d_scores, void *stream) {
+    return guarded("bert_hip_index_search_device", (int32_t)-4, [&]() -> int32_t {
+        const char *me = "bert_hip_index_search_device";
+        if (!index_ok(ix, me)) return -1;
+        std::string err;
+        if (ix->ix->search_device(n_queries, d_queries, k, d_ids, d_scores, (hipStream_t)stream, err) != 0) {
+            fprintf(stderr, "%s: %s\n", me, err.c_str());
+            return -3;
+        }
+        return 0;
+    });
+}
+
+int32_t bert_hip_index_search_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n_queries, const char **texts, int32_t k,
+                                    int32_t *ids, float *scores) {
+    return guarded("bert_hip_index_search_texts", (int32_t)-4, [&]() -> int32_t {
+        const char *me = "bert_hip_index_search_texts";
+        if (!index_ok(ix, me)) return -1;
+        bert_ctx *ctx = ix->ctx;
+        Index &x = *ix->ix;
+        if (x.dim() != ctx->hp.n_embd) { fprintf(stderr, "%s: the index has dim %d, the model's embeddings %d\n", me, x.dim(), ctx->hp.n_embd); return -2; }
+        if (k < 1 || k > Index::MAX_K) { fprintf(stderr, "%s: k must be 1 .. 256\n", me); return -2; }
+        if (n_queries < 0 || (n_queries > 0 && (!texts || !ids || !scores))) { fprintf(stderr, "%s: n_queries >= 0 and texts / outputs required\n", me); return -2; }
+        if (n_queries == 0) return 0;
+        std::string err;
+        bool ok;
+        // (results land in a buffer of our own: the caller's outputs stay untouched on an error)
+        std::vector<int32_t> hid((size_t)n_queries * k);
+        std::vector<float> hsc((size_t)n_queries * k);
+        if (ctx->engines.size() > 1) {
+            std::vector<float> emb;
+            ok = encode_host(ctx, n_threads, n_queries, texts, emb, err) && x.search_to_host(n_queries, emb.data(), false, k, hid.data(), hsc.data(), err) == 0;
+        } else {
+            ok = encode_groups_device(ctx, x, n_threads, n_queries, texts, [&](int32_t i0, int32_t c, const float *d) {
+                return x.search_to_host(c, d, true, k, hid.data() + (size_t)i0 * k, hsc.data() + (size_t)i0 * k, err) == 0;
+            }, err);
+        }
+        if (!ok) { fprintf(stderr, "%s: %s\n", me, err.empty() ? "device error" : err.c_str()); return -3; }
+        memcpy(ids, hid.data(), hid.size() * 4);
+        memcpy(scores, hsc.data(), hsc.size() * 4);
+        return 0;
     });
 }
 

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -94,6 +95,9 @@ public:
     void set_option(const std::string &key, const std::string &value);
     void profile_enable(bool on);
     std::string profile_report();
+    // a launch of another part of the library (the index kernels of search.hip) under this engine's profiling: listed by
+    // profile_report as `name`
+    void timed_launch(const char *name, double flops, hipStream_t s, const std::function<void()> &f);
 
     const HParams &hparams() const { return hp_; }
     int device() const { return device_; }

@@ -500,6 +500,8 @@ void Engine::timed(const char *name, double flops, hipStream_t s, F &&f) {
     else { ev_pool_.push_back(p.a); ev_pool_.push_back(p.b); }
 }
 
+void Engine::timed_launch(const char *name, double flops, hipStream_t s, const std::function<void()> &f) { timed(name, flops, s, f); }
+
 void Engine::profile_enable(bool on) { profiling_ = on; }
 
 std::string Engine::profile_report() {

@@ -1,0 +1,64 @@
+// search.h — an embedding index in HBM and its exact top-k inner-product search (search.hip; C ABI: bert_hip_index_* in
+// include/bert_hip.h).  Rows live on the device of the engine the index was made from, as f32 or as f16 (RNE), each row
+// zero-padded to the k-step of the score kernel's MFMA.  A search is a GEMM (queries x rows x dim) whose epilogue selects
+// instead of storing: index_topk_kernel keeps a top-k per (query, slice of rows) in LDS, topk_merge_kernel merges the
+// slices' lists per query.  The score matrix never reaches HBM.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "engine.h"
+
+namespace bert_hip {
+
+class Index {
+public:
+    static constexpr int MAX_K = 256, MAX_DIM = 2048;
+    static constexpr int QCHUNK = 4096;                  // queries per internal pass (workspace bound)
+
+    // dtype 0: f32 rows, 1: f16 rows (queries rounded to f16 as well)
+    static Index *create(Engine *eng, int dim, int dtype, std::string &err);
+    ~Index();
+
+    int size() const { return n_; }
+    int dim() const { return dim_; }
+    int dtype() const { return dtype_; }
+    hipStream_t stream() const { return stream_; }
+
+    // storage for n_rows rows and the workspace of searches of up to n_queries queries with any k' <= k, now
+    bool reserve(int n_rows, int n_queries, int k, std::string &err);
+    // append f32 rows [n][dim]: the first new id, -1 on error (index unchanged)
+    int add_device(int n, const float *d_rows, hipStream_t s, std::string &err);     // asynchronous on s
+    int add_host(int n, const float *rows, std::string &err);                        // blocking
+    // ids / scores [nq][k], best first; 0 or -1
+    int search_device(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err);
+    // host results (written only on success), queries in host (q_on_device = false) or device memory; blocking
+    int search_to_host(int nq, const float *q, bool q_on_device, int k, int32_t *ids, float *scores, std::string &err);
+    // a device f32 buffer of at least n floats for the text routes (the index's operations that read it are finished)
+    float *scratch(size_t n, std::string &err);
+    // forget the rows behind the first n (an add of several parts that failed part way)
+    void truncate(int n) { if (n >= 0 && n < n_) n_ = n; }
+
+private:
+    Index() = default;
+    struct Plan { int nqt, slices, slice_rows, L; size_t lds; };
+    static Plan plan(int n_rows, int nq, int k);
+    static size_t ws_entries_bound(int n_rows, int nq, int k);
+    bool grow_rows(int n_rows, std::string &err);
+    bool grow(DevBuf &b, size_t bytes, std::string &err);
+    void enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s);
+
+    Engine *eng_ = nullptr;
+    int dim_ = 0, dtype_ = 0, dpad_ = 0, es_ = 4;       // dpad_: elements per stored row, es_: bytes per element
+    int n_ = 0, cap_ = 0;
+    void *rows_ = nullptr;                              // [cap_][dpad_]
+    DevBuf ws_s_, ws_i_, qbuf_;                         // per-(query, slice) lists; the current chunk's queries as stored
+    DevBuf stage_, out_ids_, out_scores_, scratch_;     // host routes: f32 rows / queries, results; the text routes' embeddings
+    hipStream_t stream_ = nullptr;                      // the host routes' stream
+    // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
+    hipEvent_t busy_ = nullptr;
+};
+
+}  // namespace bert_hip

@@ -1,0 +1,502 @@
+// search.hip — exact top-k inner-product search over an HBM-resident embedding index (search.h).
+//
+// A search of nq queries over N rows of dim elements is a GEMM (M = queries, N = rows, K = dim) whose epilogue selects:
+//   index_topk_kernel<T>  one workgroup per (query tile of 32, slice of rows).  Each wave scores a 32 x 32 block
+//                         (queries x rows) per step on the matrix cores — f16 rows: v_mfma_f32_32x32x16_f16, f32 rows:
+//                         v_mfma_f32_32x32x2_f32 — and a lane ends the step with one row's scores for 16 queries.  Every score
+//                         is compared with its query's threshold (the k-th best of this workgroup so far, kept in registers);
+//                         only the ones that beat it go into the query's candidate queue in LDS (an LDS atomic hands out the
+//                         slot).  When a queue might not take another step's rows, the lists are bitonic-sorted in LDS by
+//                         (score, id) keys, the first k kept and the thresholds raised.  At the end of its slice the
+//                         workgroup writes one sorted top-k list per query to the workspace.
+//   topk_merge_kernel     one workgroup per query: the same threshold / queue / sort over the slices' lists, then the
+//                         final ids and scores.
+//   index_convert_kernel  f32 rows (added rows, queries) -> the stored form: f32 or f16 (RNE), zero-padded to dpad.
+//
+// Order of a result: larger score first, equal scores (==, so +0 equals -0) by smaller id; NaN scores never pass a compare
+// and are never returned; missing entries are id -1, score -inf (inside the kernels: id INT_MAX, which ranks below every row).
+// Determinism: a (query, row) score is one MFMA accumulation chain in a fixed k order that depends on nothing but dpad, and
+// the key order is total over distinct rows, so the set and order of a result do not depend on the slicing, the chunking of
+// the queries, the neighbours in a batch, or k (top-10 is the first 10 of top-100).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "kernels.h"
+#include "search.h"
+
+#define HIP_OK(expr, errvar, ret)                                                                       \
+    do {                                                                                                \
+        hipError_t e__ = (expr);                                                                        \
+        if (e__ != hipSuccess) {                                                                        \
+            errvar = std::string(#expr) + ": " + hipGetErrorString(e__);                                \
+            return ret;                                                                                 \
+        }                                                                                               \
+    } while (0)
+
+namespace bert_hip {
+
+namespace {
+
+constexpr int QT = 32;                  // queries per workgroup tile: the M side of one 32 x 32 MFMA block
+constexpr int NWAVE = 4;
+constexpr int NT = 64 * NWAVE;
+constexpr int STEP_ROWS = 32 * NWAVE;   // rows a workgroup scores per step (each wave one 32-row block)
+constexpr int SENT_ID = INT_MAX;        // id of an empty list entry (score -inf): ranks below every row
+constexpr int TARGET_BLOCKS = 2048;     // score workgroups a search aims for (8 per CU)
+constexpr int MERGE_U = 16;             // candidates per thread and round of the merge
+
+typedef float f32x16_t __attribute__((ext_vector_type(16)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+
+// (s, i) ranks before (ts, ti)
+__device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
+
+// Sorts nl lists of L (pow2) keys each, best first, with all NT threads of the workgroup.  Enter after a barrier; ends
+// with one.
+__device__ void bitonic_sort_lists(float *ls, int *li, int nl, int L, int tid) {
+    const int lg_half = __builtin_ctz((unsigned)L) - 1, total = nl << lg_half;
+    for (int size = 2; size <= L; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            const int lg_s = __builtin_ctz((unsigned)stride);
+            for (int p = tid; p < total; p += NT) {
+                const int list = p >> lg_half, i = p & ((1 << lg_half) - 1);
+                const int lo = ((i >> lg_s) << (lg_s + 1)) + (i & (stride - 1)), hi = lo + stride;
+                float *s = ls + list * L;
+                int *d = li + list * L;
+                const float sl = s[lo], sh = s[hi];
+                const int il = d[lo], ih = d[hi];
+                const bool swap = (lo & size) == 0 ? better(sh, ih, sl, il) : better(sl, il, sh, ih);
+                if (swap) { s[lo] = sh; s[hi] = sl; d[lo] = ih; d[hi] = il; }
+            }
+            __syncthreads();
+        }
+}
+
+// One 32 x 32 block of scores: acc[r] = query (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the tile against row (lane & 31).
+// qp / rp: this lane's query / row (rows of dpad elements); qok / rok false: that operand is zero.  The k order of the
+// accumulation is fixed by dpad alone.
+template <class T> struct ScoreBlock;
+
+template <> struct ScoreBlock<half_t> {
+    // v_mfma_f32_32x32x16_f16: lane l holds A[l & 31][16 s + 8 (l >> 5) + j] and B[..][l & 31] in element j of step s
+    static __device__ __forceinline__ void run(const half_t *qp, const half_t *rp, bool qok, bool rok, int dpad, int h, f32x16_t &acc) {
+        constexpr int U = 8;
+        const f16x8_t z = {};
+        for (int k0 = 0; k0 < dpad; k0 += 16 * U) {
+            f16x8_t a[U], b[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k0 + 16 * u < dpad;
+                const int kk = k0 + 16 * u + 8 * h;
+                a[u] = qok && in ? *(const f16x8_t *)(qp + kk) : z;
+                b[u] = rok && in ? *(const f16x8_t *)(rp + kk) : z;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (k0 + 16 * u < dpad) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[u], b[u], acc, 0, 0, 0);
+        }
+    }
+};
+
+template <> struct ScoreBlock<float> {
+    // v_mfma_f32_32x32x2_f32 (an exact f32 fma chain): lane l loads the float4 at k = 8 g + 4 (l >> 5) and feeds element e
+    // to step (g, e), which covers k = 8 g + e and 8 g + 4 + e
+    static __device__ __forceinline__ void run(const float *qp, const float *rp, bool qok, bool rok, int dpad, int h, f32x16_t &acc) {
+        constexpr int U = 8;
+        const f32x4_t z = {};
+        for (int k0 = 0; k0 < dpad; k0 += 8 * U) {
+            f32x4_t a[U], b[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k0 + 8 * u < dpad;
+                const int kk = k0 + 8 * u + 4 * h;
+                a[u] = qok && in ? *(const f32x4_t *)(qp + kk) : z;
+                b[u] = rok && in ? *(const f32x4_t *)(rp + kk) : z;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (k0 + 8 * u < dpad) {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][0], b[u][0], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][1], b[u][1], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][2], b[u][2], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u][3], b[u][3], acc, 0, 0, 0);
+                }
+        }
+    }
+};
+
+struct TopkArgs {
+    const void *rows, *queries;          // [n_rows][dpad], [nq][dpad] of T
+    float *ws_s;                         // [nq][n_slices][k] per-(query, slice) lists, best first
+    int *ws_i;
+    int n_rows, dpad, nq, n_qtiles, n_slices, slice_rows, k, L, n_items;
+};
+
+// LDS: float scores [nqv][L], int ids [nqv][L], int count [nqv] — per query the current top-k in [0, k), the queue behind
+template <class T>
+__global__ __launch_bounds__(NT) void index_topk_kernel(TopkArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    // workgroup b runs on XCD b % 8: consecutive items — the query tiles of one slice of rows — go to one XCD, so that
+    // they find the slice in that XCD's L2 (the grid is a multiple of 8; items beyond n_items do nothing)
+    const int item = (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8);
+    if (item >= a.n_items) return;
+    const int slice = item / a.n_qtiles, qt = item - slice * a.n_qtiles;
+    const int q0 = qt * QT, nqv = min(QT, a.nq - q0);
+    const int r0 = slice * a.slice_rows, r1 = min(a.n_rows, r0 + a.slice_rows);
+    const int L = a.L, k = a.k;
+    float *ls = (float *)smem;
+    int *li = (int *)(ls + nqv * L);
+    int *cnt = li + nqv * L;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
+
+    for (int i = tid; i < nqv * L; i += NT) { ls[i] = -INFINITY; li[i] = SENT_ID; }
+    if (tid < nqv) cnt[tid] = 0;
+    float ts[16];
+    int ti[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { ts[r] = -INFINITY; ti[r] = SENT_ID; }
+    __syncthreads();
+
+    const bool qok = col < nqv;
+    const T *qp = (const T *)a.queries + (size_t)(q0 + (qok ? col : 0)) * a.dpad;
+    // a step pushes at most STEP_ROWS entries per query: sort before a queue could hold fewer free slots
+    const int room = L - k - STEP_ROWS;
+    for (int base = r0; base < r1; base += STEP_ROWS) {
+        const int row = base + wave * 32 + col;
+        const bool rok = row < r1;
+        const T *rp = (const T *)a.rows + (size_t)(rok ? row : r0) * a.dpad;
+        f32x16_t acc = {};
+        ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, acc);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int q = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const float s = acc[r];
+            if (rok && q < nqv && better(s, row, ts[r], ti[r])) {
+                const int p = atomicAdd(&cnt[q], 1);
+                ls[q * L + k + p] = s;
+                li[q * L + k + p] = row;
+            }
+        }
+        __syncthreads();
+        if (__syncthreads_or(tid < nqv && cnt[tid] > room)) {
+            bitonic_sort_lists(ls, li, nqv, L, tid);
+            if (tid < nqv) cnt[tid] = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int q = (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (q < nqv) { ts[r] = ls[q * L + k - 1]; ti[r] = li[q * L + k - 1]; }
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (__syncthreads_or(tid < nqv && cnt[tid] > 0)) bitonic_sort_lists(ls, li, nqv, L, tid);
+    for (int i = tid; i < nqv * k; i += NT) {
+        const int q = i / k, j = i - q * k;
+        const size_t o = ((size_t)(q0 + q) * a.n_slices + slice) * k + j;
+        a.ws_s[o] = ls[q * L + j];
+        a.ws_i[o] = li[q * L + j];
+    }
+}
+
+struct MergeArgs {
+    const float *ws_s;                   // [nq][n_cand]
+    const int *ws_i;
+    int n_cand, k, L;
+    int32_t *ids;                        // [nq][k]
+    float *scores;
+};
+
+// LDS: float scores [L], int ids [L], int count
+__global__ __launch_bounds__(NT) void topk_merge_kernel(MergeArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int L = a.L, k = a.k, tid = threadIdx.x;
+    float *ls = (float *)smem;
+    int *li = (int *)(ls + L);
+    int *cnt = li + L;
+    const float *cs = a.ws_s + (size_t)blockIdx.x * a.n_cand;
+    const int *ci = a.ws_i + (size_t)blockIdx.x * a.n_cand;
+    for (int i = tid; i < L; i += NT) { ls[i] = -INFINITY; li[i] = SENT_ID; }
+    if (tid == 0) *cnt = 0;
+    float ts = -INFINITY;
+    int ti = SENT_ID;
+    __syncthreads();
+    const int room = L - k - NT;                 // a round pushes at most NT entries
+    for (int base = 0; base < a.n_cand; base += NT * MERGE_U) {
+        float s[MERGE_U];
+        int id[MERGE_U];
+#pragma unroll
+        for (int u = 0; u < MERGE_U; ++u) {
+            const int c = base + u * NT + tid;
+            s[u] = c < a.n_cand ? cs[c] : -INFINITY;
+            id[u] = c < a.n_cand ? ci[c] : SENT_ID;
+        }
+#pragma unroll
+        for (int u = 0; u < MERGE_U; ++u) {
+            if (better(s[u], id[u], ts, ti)) {
+                const int p = atomicAdd(cnt, 1);
+                ls[k + p] = s[u];
+                li[k + p] = id[u];
+            }
+            __syncthreads();
+            // (one thread reads the count between the two barriers: the next round's pushes come after the second)
+            if (__syncthreads_or(tid == 0 && *cnt > room)) {
+                bitonic_sort_lists(ls, li, 1, L, tid);
+                ts = ls[k - 1];
+                ti = li[k - 1];
+                if (tid == 0) *cnt = 0;
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
+    if (__syncthreads_or(tid == 0 && *cnt > 0)) bitonic_sort_lists(ls, li, 1, L, tid);
+    for (int j = tid; j < k; j += NT) {
+        const int id = li[j];
+        a.ids[(size_t)blockIdx.x * k + j] = id == SENT_ID ? -1 : id;
+        a.scores[(size_t)blockIdx.x * k + j] = ls[j];
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void index_convert_kernel(const float *__restrict__ src, T *__restrict__ dst, int n, int dim, int dpad) {
+    const size_t total = (size_t)n * dpad;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / dpad;
+        const int c = (int)(i - r * dpad);
+        dst[i] = c < dim ? (T)src[r * dim + c] : (T)0;        // (float -> _Float16: round to nearest even)
+    }
+}
+
+template <class T>
+void launch_convert(const float *src, void *dst, int n, int dim, int dpad, hipStream_t s) {
+    const size_t total = (size_t)n * dpad;
+    const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+    BERT_LAUNCH(index_convert_kernel<T>, dim3(blocks), dim3(256), 0, s, src, (T *)dst, n, dim, dpad);
+}
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int d) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        (void)hipSetDevice(d);
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+int merge_L(int k) { return k + NT <= 256 ? 256 : 512; }
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+Index::Plan Index::plan(int n_rows, int nq, int k) {
+    Plan p;
+    p.nqt = (nq + QT - 1) / QT;
+    // slices: enough workgroups to fill the chip, but each slice long against k (the first k rows of a slice all enter its
+    // list, and the merge reads slices x k candidates per query)
+    const int min_rows = std::max(2048, 16 * k);
+    const int s = std::max(1, std::min((TARGET_BLOCKS + p.nqt - 1) / p.nqt, n_rows / min_rows));
+    const int per = (int)(((long long)n_rows + s - 1) / s);
+    p.slice_rows = std::max(STEP_ROWS, (per + STEP_ROWS - 1) / STEP_ROWS * STEP_ROWS);
+    p.slices = std::max(1, (int)(((long long)n_rows + p.slice_rows - 1) / p.slice_rows));
+    p.L = k + STEP_ROWS <= 256 ? 256 : 512;
+    p.lds = (size_t)std::min(QT, nq) * p.L * 8 + QT * 4;
+    return p;
+}
+
+size_t Index::ws_entries_bound(int n_rows, int nq, int k) {
+    // (plan's slice count is at most this s, which grows with n_rows; taken over every tile count and k' <= k by reserve)
+    const int nqt = (nq + QT - 1) / QT, min_rows = std::max(2048, 16 * k);
+    const int s = std::max(1, std::min((TARGET_BLOCKS + nqt - 1) / nqt, n_rows / min_rows));
+    return (size_t)nq * s * k;
+}
+
+Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
+    if (!eng) { err = "no device engine"; return nullptr; }
+    if (dim < 1 || dim > MAX_DIM) { err = "dim must be 1 .. 2048"; return nullptr; }
+    if (dtype != 0 && dtype != 1) { err = "dtype must be 0 (f32) or 1 (f16)"; return nullptr; }
+    DeviceGuard g(eng->device());
+    Index *ix = new Index;
+    ix->eng_ = eng;
+    ix->dim_ = dim;
+    ix->dtype_ = dtype;
+    ix->es_ = dtype == 1 ? 2 : 4;
+    ix->dpad_ = dtype == 1 ? (dim + 15) / 16 * 16 : (dim + 7) / 8 * 8;      // the score kernel's k-step (a 16-byte load per lane)
+    const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
+    if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
+    // (32 queries x 512-entry lists: 128 KiB of LDS, beyond the 64 KiB a launch gets unasked; a launch that still cannot
+    // have it fails, and the search reports the launch error)
+    const int lds_max = QT * 512 * 8 + QT * 4;
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<half_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    return ix;
+}
+
+Index::~Index() {
+    DeviceGuard g(eng_ ? eng_->device() : 0);
+    if (busy_) { (void)hipEventSynchronize(busy_); (void)hipEventDestroy(busy_); }
+    if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
+    if (rows_) (void)hipFree(rows_);
+}
+
+bool Index::grow(DevBuf &b, size_t bytes, std::string &err) {
+    if (bytes <= b.bytes) return true;
+    HIP_OK(hipEventSynchronize(busy_), err, false);          // (what is queued may still read the old buffer)
+    return b.ensure(bytes, err);
+}
+
+bool Index::grow_rows(int n_rows, std::string &err) {
+    if (n_rows <= cap_) return true;
+    const int cap = (int)std::min<long long>(INT_MAX, std::max<long long>({(long long)n_rows, (long long)cap_ * 3 / 2, 1024}));
+    const size_t row_bytes = (size_t)dpad_ * es_;
+    void *p = nullptr;
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    HIP_OK(hipMalloc(&p, (size_t)cap * row_bytes), err, false);
+    if (n_ > 0 && hipMemcpy(p, rows_, (size_t)n_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+        (void)hipFree(p);
+        err = "hipMemcpy (index rows) failed";
+        return false;
+    }
+    if (rows_) (void)hipFree(rows_);
+    rows_ = p;
+    cap_ = cap;
+    return true;
+}
+
+bool Index::reserve(int n_rows, int n_queries, int k, std::string &err) {
+    if (n_rows < 0 || n_queries < 0 || k < 1 || k > MAX_K) { err = "reserve: n_rows, n_queries >= 0 and 1 <= k <= 256 required"; return false; }
+    DeviceGuard g(eng_->device());
+    if (!grow_rows(n_rows, err)) return false;
+    const int nqc = std::min(n_queries, QCHUNK);
+    if (nqc == 0) return true;
+    size_t ent = 0;
+    const int rows = std::max(n_rows, n_);
+    for (int kk = 1; kk <= k; ++kk)
+        for (int t = 1; t <= (nqc + QT - 1) / QT; ++t) ent = std::max(ent, ws_entries_bound(rows, std::min(nqc, t * QT), kk));
+    return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err) && grow(qbuf_, (size_t)nqc * dpad_ * es_, err);
+}
+
+int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &err) {
+    if (n < 0 || (n > 0 && !d_rows)) { err = "add: n >= 0 and a row pointer required"; return -1; }
+    if ((long long)n_ + n > INT_MAX) { err = "add: an index holds at most 2^31 - 1 rows"; return -1; }
+    if (n == 0) return n_;
+    DeviceGuard g(eng_->device());
+    if (!grow_rows(n_ + n, err)) return -1;
+    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
+    char *dst = (char *)rows_ + (size_t)n_ * dpad_ * es_;
+    eng_->timed_launch(dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
+        if (dtype_ == 1) launch_convert<half_t>(d_rows, dst, n, dim_, dpad_, s);
+        else launch_convert<float>(d_rows, dst, n, dim_, dpad_, s);
+    });
+    HIP_OK(hipGetLastError(), err, -1);
+    HIP_OK(hipEventRecord(busy_, s), err, -1);
+    const int first = n_;
+    n_ += n;
+    return first;
+}
+
+int Index::add_host(int n, const float *rows, std::string &err) {
+    if (n < 0 || (n > 0 && !rows)) { err = "add: n >= 0 and a row pointer required"; return -1; }
+    if ((long long)n_ + n > INT_MAX) { err = "add: an index holds at most 2^31 - 1 rows"; return -1; }
+    if (n == 0) return n_;
+    DeviceGuard g(eng_->device());
+    const int first = n_;
+    if (!grow_rows(n_ + n, err)) return -1;
+    // through a staging buffer of at most 64 MiB (a row's stored form does not depend on the parts it came in)
+    const int per = (int)std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)dim_ * 4));
+    for (int i0 = 0; i0 < n; i0 += per) {
+        const int c = std::min(per, n - i0);
+        if (!grow(stage_, (size_t)c * dim_ * 4, err) ||
+            hipMemcpyAsync(stage_.p, rows + (size_t)i0 * dim_, (size_t)c * dim_ * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+            add_device(c, stage_.as<float>(), stream_, err) < 0 || hipStreamSynchronize(stream_) != hipSuccess) {
+            (void)hipStreamSynchronize(stream_);
+            if (err.empty()) err = "add: copy to the device failed";
+            n_ = first;
+            return -1;
+        }
+    }
+    return first;
+}
+
+void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s) {
+    const Plan p = plan(n_, nq, k);
+    eng_->timed_launch(dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
+        if (dtype_ == 1) launch_convert<half_t>(d_q, qbuf_.p, nq, dim_, dpad_, s);
+        else launch_convert<float>(d_q, qbuf_.p, nq, dim_, dpad_, s);
+    });
+    TopkArgs a;
+    a.rows = rows_; a.queries = qbuf_.p; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+    a.n_rows = n_; a.dpad = dpad_; a.nq = nq; a.n_qtiles = p.nqt; a.n_slices = p.slices; a.slice_rows = p.slice_rows;
+    a.k = k; a.L = p.L; a.n_items = p.nqt * p.slices;
+    const int grid = (a.n_items + 7) / 8 * 8;
+    const double flops = 2.0 * nq * (double)n_ * dim_;
+    eng_->timed_launch(dtype_ == 1 ? "index_topk_f16" : "index_topk_f32", flops, s, [&] {
+        if (dtype_ == 1) BERT_LAUNCH(index_topk_kernel<half_t>, dim3(grid), dim3(NT), p.lds, s, a);
+        else BERT_LAUNCH(index_topk_kernel<float>, dim3(grid), dim3(NT), p.lds, s, a);
+    });
+    MergeArgs m;
+    m.ws_s = a.ws_s; m.ws_i = a.ws_i; m.n_cand = p.slices * k; m.k = k; m.L = merge_L(k); m.ids = d_ids; m.scores = d_scores;
+    const size_t lds = (size_t)m.L * 8 + 16;
+    eng_->timed_launch("topk_merge", 0.0, s, [&] { BERT_LAUNCH(topk_merge_kernel, dim3(nq), dim3(NT), lds, s, m); });
+}
+
+int Index::search_device(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err) {
+    if (k < 1 || k > MAX_K) { err = "search: k must be 1 .. 256"; return -1; }
+    if (nq < 0 || (nq > 0 && (!d_q || !d_ids || !d_scores))) { err = "search: n_queries >= 0 and query / result pointers required"; return -1; }
+    if (nq == 0) return 0;
+    DeviceGuard g(eng_->device());
+    const int nqc = std::min(nq, QCHUNK);
+    // (the last, shorter chunk may be cut into more slices than a full one)
+    const size_t ent = std::max(ws_entries_bound(n_, nqc, k), nq % QCHUNK ? ws_entries_bound(n_, nq % QCHUNK, k) : 0);
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(qbuf_, (size_t)nqc * dpad_ * es_, err)) return -1;
+    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        enqueue_chunk(c, d_q + (size_t)c0 * dim_, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
+    }
+    HIP_OK(hipGetLastError(), err, -1);
+    HIP_OK(hipEventRecord(busy_, s), err, -1);
+    return 0;
+}
+
+int Index::search_to_host(int nq, const float *q, bool q_on_device, int k, int32_t *ids, float *scores, std::string &err) {
+    if (k < 1 || k > MAX_K) { err = "search: k must be 1 .. 256"; return -1; }
+    if (nq < 0 || (nq > 0 && (!q || !ids || !scores))) { err = "search: n_queries >= 0 and query / result pointers required"; return -1; }
+    if (nq == 0) return 0;
+    DeviceGuard g(eng_->device());
+    std::vector<int32_t> hid((size_t)nq * k);
+    std::vector<float> hsc((size_t)nq * k);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        const float *dq = q + (size_t)c0 * dim_;
+        if (!q_on_device) {
+            if (!grow(stage_, (size_t)c * dim_ * 4, err)) return -1;
+            HIP_OK(hipMemcpyAsync(stage_.p, dq, (size_t)c * dim_ * 4, hipMemcpyHostToDevice, stream_), err, -1);
+            dq = stage_.as<float>();
+        }
+        if (!grow(out_ids_, (size_t)c * k * 4, err) || !grow(out_scores_, (size_t)c * k * 4, err)) return -1;
+        if (search_device(c, dq, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err) != 0) { (void)hipStreamSynchronize(stream_); return -1; }
+        HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
+        HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
+        HIP_OK(hipStreamSynchronize(stream_), err, -1);
+    }
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+float *Index::scratch(size_t n, std::string &err) {
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipEventSynchronize(busy_), err, nullptr);
+    return scratch_.ensure(n * 4, err) ? scratch_.as<float>() : nullptr;
+}
+
+}  // namespace bert_hip

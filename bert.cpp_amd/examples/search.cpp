@@ -1,0 +1,91 @@
+// bert-search — the reference's "find similar texts" demo (its README; examples/sample_dylib.py and sample_client.py) in one
+// process on the GPU: every line of a text file is embedded straight into an HBM-resident index (bert_hip_index_add_texts),
+// then each line read from stdin is a query whose k closest texts are printed in the reference's format.  'q' or the end
+// of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
+//
+//   bert-search -m MODEL -f TEXTS [-k 3] [--f32] [-t THREADS]
+//   (--f32: an f32 index; the default stores the rows as f16)
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "bert.h"
+#include "bert_hip.h"
+
+namespace {
+void usage(const char *argv0) {
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32] [-t THREADS]\n", argv0);
+}
+
+std::string chomp(std::string s) {
+    while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back();
+    return s;
+}
+}  // namespace
+
+int main(int argc, char **argv) {
+    const char *model = nullptr, *file = nullptr;
+    int k = 3, n_threads = 6, dtype = 1;
+    for (int i = 1; i < argc; ++i) {
+        const bool has_value = i + 1 < argc;
+        if ((!strcmp(argv[i], "-m") || !strcmp(argv[i], "--model")) && has_value) model = argv[++i];
+        else if ((!strcmp(argv[i], "-f") || !strcmp(argv[i], "--file")) && has_value) file = argv[++i];
+        else if (!strcmp(argv[i], "-k") && has_value) k = atoi(argv[++i]);
+        else if ((!strcmp(argv[i], "-t") || !strcmp(argv[i], "--threads")) && has_value) n_threads = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--f32")) dtype = 0;
+        else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
+    }
+    if (!model || !file) { usage(argv[0]); return 2; }
+    if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
+
+    bert_ctx *ctx = bert_load_from_file(model);
+    if (!ctx) {
+        fprintf(stderr, "search: failed to load model from '%s'\n", model);
+        return 1;
+    }
+    printf("Loading texts from %s...\n", file);
+    std::ifstream in(file);
+    if (!in) {
+        fprintf(stderr, "search: cannot read '%s'\n", file);
+        bert_free(ctx);
+        return 1;
+    }
+    std::vector<std::string> texts;
+    for (std::string line; std::getline(in, line);) texts.push_back(chomp(line));
+    std::vector<const char *> ptrs;
+    for (auto &t : texts) ptrs.push_back(t.c_str());
+
+    bert_hip_index *ix = bert_hip_index_create(ctx, 0, dtype);
+    if (!ix || bert_hip_index_add_texts(ix, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+        fprintf(stderr, "search: could not build the index\n");
+        bert_free(ctx);
+        return 1;
+    }
+    printf("Loaded %zu lines.\n", texts.size());
+
+    std::vector<int32_t> ids((size_t)k);
+    std::vector<float> scores((size_t)k);
+    for (;;) {
+        printf("Enter a text to find similar texts (enter 'q' to quit): ");
+        fflush(stdout);
+        std::string q;
+        if (!std::getline(std::cin, q)) break;
+        q = chomp(q);
+        if (q == "q") break;
+        const char *qp = q.c_str();
+        if (bert_hip_index_search_texts(ix, n_threads, 1, &qp, k, ids.data(), scores.data()) != 0) {
+            fprintf(stderr, "search: the search failed\n");
+            bert_free(ctx);
+            return 1;
+        }
+        printf("\nClosest texts:\n");
+        for (int i = 0; i < k && ids[i] >= 0; ++i) printf("%d. %s\n (similarity score: %.4f)\n", i + 1, texts[ids[i]].c_str(), scores[i]);
+    }
+    printf("\n");
+    bert_free(ctx);                                           // (frees the index as well)
+    return 0;
+}

@@ -25,6 +25,9 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_ftype", "bert_hip_device", "bert_hip_n_devices", "bert_hip_encode_batch", "bert_hip_eval_packed", "bert_hip_eval_packed_gather",
     "bert_hip_eval_packed_device", "bert_hip_reserve", "bert_hip_check", "bert_hip_eval_hidden",
     "bert_hip_profile_enable", "bert_hip_profile_report", "bert_hip_set_option", "bert_hip_version",
+    "bert_hip_index_create", "bert_hip_index_free", "bert_hip_index_size", "bert_hip_index_reserve", "bert_hip_index_add",
+    "bert_hip_index_add_device", "bert_hip_index_add_texts", "bert_hip_index_search", "bert_hip_index_search_device",
+    "bert_hip_index_search_texts",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -83,6 +86,17 @@ def _declare_product_abi(L):
     L.bert_hip_tokenize_batch.restype = i32
     L.bert_hip_tokenize_batch.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32p, i32p]
     L.bert_hip_version.restype = C.c_char_p
+    L.bert_hip_index_create.restype = vp; L.bert_hip_index_create.argtypes = [vp, i32, i32]
+    L.bert_hip_index_free.restype = None; L.bert_hip_index_free.argtypes = [vp]
+    L.bert_hip_index_size.restype = i32; L.bert_hip_index_size.argtypes = [vp]
+    L.bert_hip_index_reserve.restype = i32; L.bert_hip_index_reserve.argtypes = [vp, i32, i32, i32]
+    L.bert_hip_index_add.restype = i32; L.bert_hip_index_add.argtypes = [vp, i32, f32p]
+    L.bert_hip_index_add_device.restype = i32; L.bert_hip_index_add_device.argtypes = [vp, i32, vp, vp]
+    L.bert_hip_index_add_texts.restype = i32; L.bert_hip_index_add_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p)]
+    L.bert_hip_index_search.restype = i32; L.bert_hip_index_search.argtypes = [vp, i32, f32p, i32, i32p, f32p]
+    L.bert_hip_index_search_device.restype = i32; L.bert_hip_index_search_device.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_index_search_texts.restype = i32
+    L.bert_hip_index_search_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32p, f32p]
 
 
 def lib() -> C.CDLL:
@@ -383,6 +397,91 @@ class BertModel:
 
     def set_option(self, key: str, value: str) -> None:
         self.lib.bert_hip_set_option(self.ctx, key.encode(), value.encode())
+
+    def index(self, dim: Optional[int] = None, dtype: str = "f16") -> "BertIndex":
+        """An embedding index on the context's first device (bert_hip_index_create): dim None = n_embd, dtype "f16" | "f32"."""
+        return BertIndex(self, dim, dtype)
+
+
+class BertIndex:
+    """bert_hip_index_*: rows in HBM, exact top-k inner-product search.  search* return (ids [n, k] int32, scores [n, k] f32),
+    best first; missing entries are id -1, score -inf.  The *_device forms take device pointers (ints, e.g. torch's
+    data_ptr()) and a stream handle, and return at once."""
+
+    def __init__(self, model: BertModel, dim: Optional[int] = None, dtype: str = "f16"):
+        if dtype not in ("f16", "f32"):
+            raise ValueError("dtype must be 'f16' or 'f32'")
+        self.model, self.lib = model, model.lib
+        self.ix = self.lib.bert_hip_index_create(model.ctx, 0 if dim is None else int(dim), 1 if dtype == "f16" else 0)
+        if not self.ix:
+            raise RuntimeError("bert_hip_index_create failed (see stderr)")
+        self.dim = model.n_embd if dim is None else int(dim)
+        self.dtype = dtype
+
+    def close(self):
+        # (an index the context freed already — bert_free frees its indexes — must not be freed again)
+        if getattr(self, "ix", None) and getattr(self.model, "ctx", None):
+            self.lib.bert_hip_index_free(self.ix)
+        self.ix = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(self.lib.bert_hip_index_size(self.ix))
+
+    def reserve(self, n_rows: int, n_queries: int = 0, k: int = 1) -> None:
+        if self.lib.bert_hip_index_reserve(self.ix, n_rows, n_queries, k) != 0:
+            raise RuntimeError("bert_hip_index_reserve failed")
+
+    def add(self, rows) -> int:
+        """rows [n, dim] (converted to f32); returns the first new id."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, self.dim)
+        r = self.lib.bert_hip_index_add(self.ix, rows.shape[0], _f32p(rows))
+        if r < 0:
+            raise RuntimeError(f"bert_hip_index_add failed: {r}")
+        return r
+
+    def add_device(self, n: int, d_rows_ptr: int, stream: int = 0) -> int:
+        r = self.lib.bert_hip_index_add_device(self.ix, n, d_rows_ptr, stream)
+        if r < 0:
+            raise RuntimeError(f"bert_hip_index_add_device failed: {r}")
+        return r
+
+    def add_texts(self, texts: Sequence[str], n_threads: int = 6) -> int:
+        n = len(texts)
+        txt = (C.c_char_p * n)(*[t.encode("utf-8") for t in texts])
+        r = self.lib.bert_hip_index_add_texts(self.ix, n_threads, n, txt)
+        if r < 0:
+            raise RuntimeError(f"bert_hip_index_add_texts failed: {r}")
+        return r
+
+    def search(self, queries, k: int = 10):
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), dtype=np.int32)
+        scores = np.empty((q.shape[0], k), dtype=np.float32)
+        r = self.lib.bert_hip_index_search(self.ix, q.shape[0], _f32p(q), k, _i32p(ids), _f32p(scores))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search failed: {r}")
+        return ids, scores
+
+    def search_device(self, n_queries: int, d_queries_ptr: int, k: int, d_ids_ptr: int, d_scores_ptr: int, stream: int = 0) -> None:
+        r = self.lib.bert_hip_index_search_device(self.ix, n_queries, d_queries_ptr, k, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search_device failed: {r}")
+
+    def search_texts(self, texts: Sequence[str], k: int = 10, n_threads: int = 6):
+        n = len(texts)
+        txt = (C.c_char_p * max(n, 1))(*[t.encode("utf-8") for t in texts])
+        ids = np.empty((n, k), dtype=np.int32)
+        scores = np.empty((n, k), dtype=np.float32)
+        r = self.lib.bert_hip_index_search_texts(self.ix, n_threads, n, txt, k, _i32p(ids), _f32p(scores))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search_texts failed: {r}")
+        return ids, scores
 
 
 def test_gemm(A: np.ndarray, W_bytes: np.ndarray, wtype: int, N: int, bias: np.ndarray,

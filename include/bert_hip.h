@@ -136,6 +136,48 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  * pinned memory instead of the copy engine), "profile_replay" (above).                                                                 */
 BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const char *value);
 
+/* Embedding index: rows in HBM on the context's FIRST device (bert_hip_device), exact top-k search by inner product.
+ * An index belongs to the context it was made from: bert_free frees any index the caller left alive.  Like every
+ * entry point of a context, the index functions are not re-entrant on one context.
+ *   create   dim: 0 = bert_n_embd(ctx), else 1 .. 2048.  dtype: 0 = f32 rows, 1 = f16 rows (rounded to nearest even; the
+ *            queries are rounded to f16 the same way).  NULL + a message on stderr on error (tokenizer-only context, no
+ *            device, bad arguments).
+ *   add      appends rows [n][dim] (f32); they get ids size, size + 1, ...; returns the first new id, negative on error
+ *            (index unchanged).  add_device: the rows in device memory of the index's device, enqueued on `stream`.
+ *            add_texts: encodes the texts (dim must equal n_embd) on the context's devices as bert_hip_encode_batch does; on a
+ *            single-device context the embeddings go from the forward pass's device output straight into the index.
+ *   search   ids[n_queries][k] and scores[n_queries][k], best first; 0 on success, negative on error (outputs untouched).
+ *            search_device: queries and results in device memory, enqueued on `stream`.  search_texts: the queries are texts,
+ *            encoded like add_texts's (single device: into a device buffer, no host round trip).
+ *   reserve  sizes the storage for n_rows rows and the search workspace for up to n_queries queries with any k' <= k now,
+ *            so that the *_device calls within those bounds never allocate (allocation synchronises the device: illegal under
+ *            stream capture).  Without it storage and workspace grow on demand.
+ * Semantics:
+ *   - score = sum_i q[i] * row[i], accumulated in f32: f32 rows on v_mfma_f32_32x32x2_f32 (an f32 fma chain), f16 rows and
+ *     f16-rounded queries on v_mfma_f32_32x32x16_f16 (rows zero-padded to its k-step, which changes no sum).  The engine's
+ *     embeddings are L2-normalised: for them the score is the cosine.
+ *   - order: larger score first; equal scores (==, so +0 equals -0) smaller id first.  Rows with a NaN score are never
+ *     returned.  Slots beyond the rows that can be returned are id -1, score -INFINITY.  An empty index is valid.
+ *   - 1 <= k <= 256, anything else is an error; n_queries == 0 is a successful no-op; large n_queries run in internal chunks.
+ *   - a row's score for a query has the same bits whatever the other queries of the call, the number of add calls that built
+ *     the index, reserved or grown storage, k (top-10 is the first 10 entries of top-100), and host or device entry point.
+ *   - *_device calls are asynchronous on the caller's stream; an index has ONE event, so its operations never overlap,
+ *     whatever streams they were enqueued on.                                                                            */
+struct bert_hip_index;
+BERT_API struct bert_hip_index *bert_hip_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype);
+BERT_API void    bert_hip_index_free(struct bert_hip_index *ix);
+BERT_API int32_t bert_hip_index_size(struct bert_hip_index *ix);
+BERT_API int32_t bert_hip_index_reserve(struct bert_hip_index *ix, int32_t n_rows, int32_t n_queries, int32_t k);
+BERT_API int32_t bert_hip_index_add(struct bert_hip_index *ix, int32_t n, const float *rows);
+BERT_API int32_t bert_hip_index_add_device(struct bert_hip_index *ix, int32_t n, const float *d_rows, void *stream);
+BERT_API int32_t bert_hip_index_add_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n, const char **texts);
+BERT_API int32_t bert_hip_index_search(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t k,
+                                       int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_index_search_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t k,
+                                              int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_index_search_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n_queries, const char **texts,
+                                             int32_t k, int32_t *ids, float *scores);
+
 BERT_API const char *bert_hip_version(void);
 
 #ifdef __cplusplus

@@ -1,0 +1,152 @@
+"""Rate of the embedding index's search (bert_hip_index_search_device) on one GPU, with torch's matmul + topk on the same
+device and data beside every line as the yardstick, and the rate of bert_hip_index_add_texts against bert_encode_batch +
+bert_hip_index_add.  GPU only: there is no CPU fallback.
+
+    python tools/search_rate.py [--rows 1000000] [--iters 10] [--out profiles/search_rate.txt]
+
+Per line: ms per call (device events, after warm-up), queries/s, the algorithmic bytes (the rows once, the queries, the
+results) and FLOPs (2 Q N dim), the share of the binding roofline (HBM 6.3 TB/s achievable; matrix cores 2.5 PF/s f16,
+155 TF/s f32) and its name, torch's ms, and whether the two agree (per query: the same ids up to ties within tolerance).
+"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM = 6.3e12
+PEAK = {"f16": 2.5e15, "f32": 155e12}
+
+
+def agree(ids, scores, t_ids, t_vals, k, tol):
+    """set equality up to ties: every id that only one side returned scores within tol of that side's k-th score"""
+    for q in range(ids.shape[0]):
+        a, b = set(ids[q].tolist()), set(t_ids[q].tolist())
+        if a == b:
+            continue
+        if not (abs(float(scores[q, k - 1]) - float(t_vals[q, k - 1])) <= tol and
+                all(float(scores[q, list(ids[q]).index(i)]) <= float(scores[q, k - 1]) + tol for i in a - b) and
+                all(float(t_vals[q, list(t_ids[q]).index(i)]) <= float(t_vals[q, k - 1]) + tol for i in b - a)):
+            return False
+    return True
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("search_rate.py needs a GPU")
+    os.environ.setdefault("BERT_HIP_QUIET", "1")
+    from bert_cpp_amd import ggml_file as gf
+    from bert_cpp_amd import pybert
+
+    lines = []
+
+    def out(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    dev = torch.device("cuda:0")
+    tmp = tempfile.mkdtemp()
+    path = os.path.join(tmp, "minilm.bin")
+    gf.make_synthetic_model(path, "minilm-l6", "f16", seed=1)
+    m = pybert.BertModel(path)
+    st = torch.cuda.current_stream()
+    sp = st.cuda_stream
+    N = a.rows
+    out(f"# search_device, N = {N} rows, {torch.cuda.get_device_name(0)}; ms per call = median of {a.iters} after 3 warm-up calls")
+    out("# dim dtype     Q    k |      ms    queries/s  bytes      FLOPs   | bound  share | torch ms  agree")
+    for dim in (384, 768):
+        g = torch.Generator(device=dev).manual_seed(dim)
+        C = torch.randn(N, dim, device=dev, generator=g)
+        C /= C.norm(dim=1, keepdim=True)
+        Qall = torch.randn(4096, dim, device=dev, generator=g)
+        Qall /= Qall.norm(dim=1, keepdim=True)
+        for dtype in ("f16", "f32"):
+            ix = m.index(dim=dim, dtype=dtype)
+            ix.reserve(N, 4096, 100)
+            ix.add_device(N, C.data_ptr(), sp)
+            Ct = C.half() if dtype == "f16" else C
+            for Q in (1, 16, 256, 4096):
+                q = Qall[:Q].contiguous()
+                for k in (10, 100):
+                    ids = torch.empty(Q, k, dtype=torch.int32, device=dev)
+                    sc = torch.empty(Q, k, dtype=torch.float32, device=dev)
+
+                    def call():
+                        ix.search_device(Q, q.data_ptr(), k, ids.data_ptr(), sc.data_ptr(), sp)
+
+                    def yard():
+                        qt = q.half() if dtype == "f16" else q
+                        res = []
+                        for c0 in range(0, Q, 256):          # (a [256, N] f32 score block at a time: 1 GB)
+                            s = (qt[c0:c0 + 256] @ Ct.T).float()
+                            res.append(torch.topk(s, k, dim=1))
+                        return torch.cat([r.values for r in res]), torch.cat([r.indices for r in res])
+
+                    def timed(f):
+                        for _ in range(3):
+                            f()
+                        ms = []
+                        for _ in range(a.iters):
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(st)
+                            f()
+                            e1.record(st)
+                            e1.synchronize()
+                            ms.append(e0.elapsed_time(e1))
+                        return float(np.median(ms))
+
+                    t = timed(call)
+                    ty = timed(yard)
+                    tv, ti = yard()
+                    torch.cuda.synchronize()
+                    nq = min(Q, 64)
+                    ok = agree(ids[:nq].cpu().numpy(), sc[:nq].cpu().numpy(), ti[:nq].cpu().numpy(), tv[:nq].cpu().numpy(), k, 1e-3)
+                    es = 2 if dtype == "f16" else 4
+                    dpad = (dim + 15) // 16 * 16 if dtype == "f16" else (dim + 7) // 8 * 8
+                    nbytes = N * dpad * es + Q * dim * 4 + Q * k * 8
+                    flops = 2.0 * Q * N * dim
+                    tb, tf = nbytes / HBM, flops / PEAK[dtype]
+                    bound, share = ("HBM", tb / (t * 1e-3)) if tb >= tf else ("MFMA", tf / (t * 1e-3))
+                    out(f"{dim:5d} {dtype:5s} {Q:5d} {k:4d} | {t:8.3f} {Q / (t * 1e-3):11.0f}  {nbytes:.2e} {flops:.2e} | "
+                        f"{bound:5s} {share:6.3f} | {ty:8.3f}  {'yes' if ok else 'NO'}")
+            ix.close()
+        del C, Qall
+        torch.cuda.empty_cache()
+
+    # strings in, index rows out: add_texts against encode_batch + add
+    base = [l.rstrip("\n") for l in open(os.path.join(ROOT, "tests", "golden", "sample_client_texts_600.txt"), encoding="utf-8")]
+    texts = [f"{base[i % len(base)]} {i}" for i in range(32768)]
+    rates = {}
+    for name in ("add_texts", "encode_batch+add"):
+        best = 1e9
+        for _ in range(3):
+            ix = m.index(dtype="f16")
+            t0 = time.perf_counter()
+            if name == "add_texts":
+                ix.add_texts(texts, n_threads=16)
+            else:
+                ix.add(m.encode_batch(texts, n_threads=16))
+            best = min(best, time.perf_counter() - t0)
+            ix.close()
+        rates[name] = len(texts) / best
+    out(f"# texts into the index (minilm-l6 synthetic f16, 32768 texts, best of 3): add_texts {rates['add_texts']:.0f} texts/s, "
+        f"encode_batch + add {rates['encode_batch+add']:.0f} texts/s")
+    m.close()
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
