@@ -106,9 +106,42 @@ public:
 private:
     Engine() = default;
     bool ensure_workspace(int t_pad, int n_sentences, std::string &err);
-    // f32 files in f32 arithmetic (f32_route.hip): the whole pass, one launch per operation
-    int forward_f32(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s, float *d_hidden,
-                    std::string &err);
+
+    // The forward pass: plan() decides everything once, before the first launch; a forward_* method per route only launches.
+    enum class Route { F32, LATENCY, ONE_LAUNCH, FOLDED, LAYERED };
+    enum class Family { GEMM256, MFMA, NAIVE, F32 };         // the kernel that serves a weight mat-mul
+    struct LayerPlan {                                       // (LAYERED; FOLDED reads layer 0's planes)
+        bool qkv2 = false;            // qkv_attention2, else the Q|K|V mat-mul + attention
+        bool tail = false;            // layer_tail, else the mat-muls + LayerNorms
+        bool planes = false;          // the Q|K|V mat-mul reads the 4-bit planes (LayerWeights::qkv_q4), else the f16 image
+        Family qkv = Family::NAIVE, o = Family::NAIVE, ffi = Family::NAIVE, ffo = Family::NAIVE;
+    };
+    struct Plan {
+        // the call (windows, n_windows: the caller's list, or the one the pass builds on the device)
+        const int32_t *tokens, *cu;
+        int B, T, max_len, t_pad, slots;
+        float *out, *hidden;
+        hipStream_t s;
+        const int2 *windows;
+        int n_windows;
+        // the decisions
+        Route route = Route::LAYERED;
+        bool build_windows = false;   // launch_build_windows ahead of the route, its count in n_windows_dev (n_windows: a bound)
+        const int *n_windows_dev = nullptr;
+        std::vector<LayerPlan> layers;
+    };
+    Plan plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s, float *d_hidden,
+              const int2 *d_windows, int n_windows, int slots) const;
+    bool forward_f32(const Plan &p, std::string &err);        // f32 files in f32 arithmetic (f32_route.hip), one launch per operation
+    void forward_latency(const Plan &p);
+    void forward_one_launch(const Plan &p);
+    bool forward_folded(const Plan &p, std::string &err);
+    bool forward_layers(const Plan &p, std::string &err);
+    // A, resid, C: f32 for Family::F32, else f16
+    bool gemm(const Plan &p, const char *name, Family f, const GemmWeightStore &W, const void *A, const float *bias, const void *resid, void *C,
+              int epi, std::string &err, const GemmLnFold *ln = nullptr);
+    void attention(const Plan &p);
+    void tap(const Plan &p, int idx);
     template <class F> void timed(const char *name, double flops, hipStream_t s, F &&f);
 
     HParams hp_;
@@ -138,6 +171,7 @@ private:
 
     // options
     bool gemm_naive_ = false, attn_naive_ = false, qkv2_ = true, gemm256_ = true, ln_fold_ = true, tail_ = true, latency_ = true, q4_expand_ = true;
+    bool fold_images_ = false;        // the LayerNorm-folding images were built at load (ln_fold_ was set then)
     bool f32_file_ = false;           // every matrix and table of the file is f32: the f32 route can take it
     bool f32_exact_ = true;           // ... and takes it unless BERT_HIP_F32=f16 / set_option("f32", "f16")
     int one_launch_ = 1;              // all layers in one launch: 0 never, 1 when it pays (well-filled windows), 2 whenever the kernel takes the batch

@@ -348,30 +348,30 @@ Engine *Engine::create(const ModelFile &mf, int device, std::string &err) {
         ok = ok && upload_f32(L->ln_out_b, T(p + "output.LayerNorm.bias"), err);
     }
     // LayerNorm folding (kernels.h GemmLnFold; the route of models the fused H <= 384 kernels do not take): images for every layer
-    // whose four matrices run on gemm256's f16 form
-    for (int i = 0; ok && i < mf.hp.n_layer; ++i) {
+    // whose four matrices run on gemm256's f16 form; only when folding is on at load (set_option cannot turn it on without them)
+    e->fold_images_ = e->ln_fold_;
+    auto f16_256 = [](const GemmWeightStore &s) { return s.mfma_ok && s.w.type == GW_F16 && s.w.N % 256 == 0 && s.w.K % 64 == 0 && s.w.K >= 128; };
+    // (1-D f32 tensors, copied out: their bytes in the file buffer have no alignment guarantee; empty: no such tensor)
+    auto F = [&](const std::string &n) { std::vector<float> v(T(n) ? T(n)->nbytes / 4 : 0); if (!v.empty()) memcpy(v.data(), T(n)->data, v.size() * 4); return v; };
+    for (int i = 0; ok && e->fold_images_ && i < mf.hp.n_layer; ++i) {
         LayerWeights &L = *e->layers_[i];
         const std::string p = "encoder.layer." + std::to_string(i) + ".";
         const int H = mf.hp.n_embd;
-        auto f16_256 = [](const GemmWeightStore &s) { return s.mfma_ok && s.w.type == GW_F16 && s.w.N % 256 == 0 && s.w.K % 64 == 0 && s.w.K >= 128; };
         if (!(H > 384 && H % 256 == 0 && f16_256(L.qkv) && f16_256(L.o) && f16_256(L.ffi) && f16_256(L.ffo)) || e->f32_file_) continue;
-        auto F = [&](const std::string &n) { const HostTensor *t = T(n); return t ? (const float *)t->data : nullptr; };
-        const float *g1 = F(p + "attention.output.LayerNorm.weight"), *b1 = F(p + "attention.output.LayerNorm.bias");
-        const float *bi = F(p + "intermediate.dense.bias"), *bo2 = F(p + "output.dense.bias"), *bo = F(p + "attention.output.dense.bias");
-        if (!g1 || !b1 || !bi || !bo2 || !bo) continue;
-        ok = L.ffi_fold.build_ln_fold({T(p + "intermediate.dense.weight")}, g1, b1, bi, L.ffi_waug, err) &&
-             upload_gamma_beta_bias(L.ffo_gb, g1, b1, bo2, H, err);
+        const std::vector<float> g1 = F(p + "attention.output.LayerNorm.weight"), b1 = F(p + "attention.output.LayerNorm.bias"),
+                                 bi = F(p + "intermediate.dense.bias"), bo2 = F(p + "output.dense.bias"), bo = F(p + "attention.output.dense.bias");
+        if (g1.empty() || b1.empty() || bi.empty() || bo2.empty() || bo.empty()) continue;
+        ok = L.ffi_fold.build_ln_fold({T(p + "intermediate.dense.weight")}, g1.data(), b1.data(), bi.data(), L.ffi_waug, err) &&
+             upload_gamma_beta_bias(L.ffo_gb, g1.data(), b1.data(), bo2.data(), H, err);
         if (ok && i >= 1) {
             const std::string q = "encoder.layer." + std::to_string(i - 1) + ".";
-            const float *g2 = F(q + "output.LayerNorm.weight"), *b2 = F(q + "output.LayerNorm.bias");
-            std::vector<float> qb((size_t)3 * H);
-            const char *names[3] = {"attention.self.query.bias", "attention.self.key.bias", "attention.self.value.bias"};
-            bool have = g2 && b2;
-            for (int k = 0; have && k < 3; ++k) { const float *b = F(p + names[k]); have = b != nullptr; if (have) memcpy(qb.data() + (size_t)k * H, b, (size_t)H * 4); }
-            if (!have) continue;
+            const std::vector<float> g2 = F(q + "output.LayerNorm.weight"), b2 = F(q + "output.LayerNorm.bias");
+            std::vector<float> qb;
+            for (const char *n : {"attention.self.query.bias", "attention.self.key.bias", "attention.self.value.bias"}) { const auto b = F(p + n); qb.insert(qb.end(), b.begin(), b.end()); }
+            if (g2.empty() || b2.empty() || qb.size() != (size_t)3 * H) continue;
             ok = L.qkv_fold.build_ln_fold({T(p + "attention.self.query.weight"), T(p + "attention.self.key.weight"), T(p + "attention.self.value.weight")},
-                                          g2, b2, qb.data(), L.qkv_waug, err) &&
-                 upload_gamma_beta_bias(L.o_gb, g2, b2, bo, H, err);
+                                          g2.data(), b2.data(), qb.data(), L.qkv_waug, err) &&
+                 upload_gamma_beta_bias(L.o_gb, g2.data(), b2.data(), bo.data(), H, err);
         }
         L.fold_ok = ok && L.ffi_fold.mfma_ok && (i == 0 || L.qkv_fold.mfma_ok);
     }
@@ -431,6 +431,8 @@ void Engine::set_option(const std::string &key, const std::string &value) {
     } else if (key == "attn") attn_naive_ = value == "naive";
     else if (key == "qkv2") qkv2_ = value != "0";
     else if (key == "gemm256") gemm256_ = value != "0";
+    else if (key == "ln_fold" && value != "0" && !fold_images_)
+        fprintf(stderr, "bert_hip_set_option: ln_fold=1 needs BERT_HIP_LN_FOLD=1 at load time (the folded images were not built); ignored\n");
     else if (key == "ln_fold") ln_fold_ = value != "0";
     else if (key == "tail") tail_ = value != "0";
     else if (key == "latency") latency_ = value != "0";
@@ -553,246 +555,275 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     // grid bound and the kernels' place rule must agree whatever another thread or context sets meanwhile
     const int slots = slots_in ? slots_in : window_slots();
     HIP_OK(hipSetDevice(device_), err, -1);
-    const int H = hp_.n_embd, I = hp_.n_intermediate, nh = hp_.n_head, dh = H / nh;
-    const int t_pad = (T + 255) / 256 * 256;                 // whole tiles of every kernel family (128- and 256-token tiles)
-    if (!ensure_workspace(t_pad, B, err)) return -1;
+    if (!ensure_workspace((T + 255) / 256 * 256, B, err)) return -1;
     replay_done_ = false;
     // one forward pass at a time on the shared workspace: wait (on the caller's stream) for the previous pass
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
-    if (f32_file_ && f32_exact_) return forward_f32(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, err);
-    half_t *x = x_.as<half_t>(), *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>(), *y = y_.as<half_t>(),
-           *ff = ff_.as<half_t>();
-    const double Td = (double)T;
-
-    auto gemm = [&](const char *name, GemmWeightStore &W, const half_t *A, const float *bias, const half_t *resid,
-                    half_t *C, int epi, const GemmLnFold *ln = nullptr) {
-        const bool big = W.mfma_ok && gemm256_ && !gemm_naive_ && gemm256_supported(W.w, t_pad);
-        const bool tiled = !big && W.mfma_ok && (!gemm_naive_ || !W.w.naive16);
-        // (which kernel family served the mat-mul: reported as "family:<kernel>_<weights>" lines of the profile)
-        if (profiling_ && replay_name_.empty())
-            families_[std::string("family:") + (big ? "gemm256" : tiled ? "gemm_mfma" : "gemm_naive") + (big || tiled ? (W.w.type == GW_F16 ? "_f16" : "_q4") : "")] += 1;
-        timed(name, 2.0 * Td * W.w.N * W.w.K, s, [&] {
-            if (big) launch_gemm256(W.w, A, bias, resid, C, t_pad, epi, s, ln);
-            else if (tiled) launch_gemm_mfma(W.w, A, bias, resid, C, t_pad, epi, s);
-            else launch_gemm_naive(W.w, A, bias, resid, C, T, epi, s);
-        });
-    };
-    auto tap = [&](int idx) {
-        if (d_hidden) launch_f16_to_f32(x, d_hidden + (size_t)idx * T * H, (size_t)T * H, s);
-    };
-
-    timed("embed_ln", 0.0, s, [&] {
-        launch_embed_ln(word_emb_.p, type_emb_.p, pos_emb_.p, table_type_, ln_e_w_.as<float>(), ln_e_b_.as<float>(),
-                        d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, x, s);
-    });
-    tap(0);
-    // attention FLOPs: 4 * sum_b N_b^2 * H; only T and max_len are known here -> upper bound T * max_len
-    const double att_flops = 4.0 * Td * max_len * H;
-    // sentence windows of the fused projection+attention kernel: the caller's (host path), or built here on the device from
-    // cu_seqlens when packing can pay — sentences on average clearly shorter than max_len; for full-length batches the
-    // uniform rule (max_len-sized places) gives the same windows without the extra launch
-    const int *d_n_windows = nullptr;
-    const bool fused_windows = qkv2_ && !gemm_naive_ && !attn_naive_ && layers_[0]->qkv.mfma_ok && qkv_attention2_supported(layers_[0]->qkv.w, nh, dh, max_len);
-    // all layers in one launch (model_kernel.hip): a workgroup carries its window through every layer
-    // (every layer's matrices are checked: a file may mix types or shapes from layer to layer, and the kernel takes all layers' pointers)
-    bool one_launch_ok = fused_windows && one_launch_ && tail_ && !d_hidden && !(latency_ && T <= latency_tokens_);
-    for (int il = 0; one_launch_ok && il < hp_.n_layer; ++il) {
-        LayerWeights &L = *layers_[il];
-        one_launch_ok = L.qkv.mfma_ok && L.o.mfma_ok && L.ffi.mfma_ok && L.ffo.mfma_ok && L.ffi.w.w16p && L.ffo.w.w16p &&
-                        model_kernel_supported(L.qkv.w, L.o.w, L.ffi.w, L.ffo.w, hp_.n_layer, nh, dh, max_len);
-    }
-    const bool full_windows = (long long)B * 128 == T;
-    if (!d_windows && fused_windows) {
-        const int spw = qkv_attention2_sentences_per_window(max_len, slots), uniform = (B + spw - 1) / spw;
-        // (forced one-launch: the kernel takes a window list or one sentence per window — its layer-tail phase needs a window's
-        // tokens to be at most 128 whatever the sentences' lengths turn out to be)
-        if (4ll * uniform * 128 > 5 * ((long long)T + (long long)(slots / 2) * B) || (one_launch_ok && one_launch_ == 2 && spw > 1 && !full_windows)) {
-            int *count = status_.as<int>() + 1;
-            timed("build_windows", 0.0, s, [&] { launch_build_windows(d_cu, B, windows_.as<int2>(), count, slots, s); });
-            d_windows = windows_.as<int2>();
-            d_n_windows = count;
-            // upper bound from T and B alone (the extra workgroups return at once): "never more than the uniform rule" only
-            // holds for batches that keep their max_len promise, and a broken promise must cost the offender its row, not
-            // a neighbour its window
-            n_windows = qkv_attention2_max_windows(B, T, slots);
+    const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots);
+    bool ok = true;
+    if (p.route == Route::F32) ok = forward_f32(p, err);
+    else {
+        const int H = hp_.n_embd;
+        timed("embed_ln", 0.0, s, [&] { launch_embed_ln(word_emb_.p, type_emb_.p, pos_emb_.p, table_type_, ln_e_w_.as<float>(), ln_e_b_.as<float>(),
+                                                        d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, x_.as<half_t>(), s); });
+        tap(p, 0);
+        if (p.build_windows)
+            timed("build_windows", 0.0, s, [&] { launch_build_windows(d_cu, B, windows_.as<int2>(), status_.as<int>() + 1, slots, s); });
+        switch (p.route) {
+            case Route::LATENCY: forward_latency(p); break;
+            case Route::ONE_LAUNCH: forward_one_launch(p); break;
+            case Route::FOLDED: ok = forward_folded(p, err); break;
+            default: ok = forward_layers(p, err); break;
         }
+        // (the one-launch kernel's workgroups pool their sentences themselves)
+        if (ok && p.route != Route::ONE_LAUNCH)
+            timed("pool_normalize", 2.0 * T * H, s, [&] { launch_pool_normalize(x_.as<half_t>(), d_cu, B, H, max_len, status_.as<int>(), d_out, s); });
     }
-    // When it pays: the layer-tail phase costs a window 128 rows' time however few tokens it holds, the layer-tail KERNEL runs
-    // on the packed tokens — 0.32 + 0.68 fill against 0.94 (full windows: +6.7 %): from a fill of 0.91.  The window count is
-    // known for the caller's list and for one sentence per window, not for a list built on the device.
-    bool one_launch_pays = full_windows || one_launch_ == 2;
-    if (!one_launch_pays && !d_n_windows) {
-        const long long n_win = d_windows ? n_windows : B;
-        one_launch_pays = (d_windows || qkv_attention2_sentences_per_window(max_len, slots) == 1) && 100ll * T >= 95ll * 128 * n_win;
-    }
-    // The latency route (skinny.hip): at most 128 tokens = one window of the fused kernels, which would keep one CU of 256 busy
-    // per launch.  Same bits per sentence (the route must not show in the results), seven short launches per layer.
-    const bool skinny = latency_ && tail_ && qkv2_ && !gemm_naive_ && !attn_naive_ && T <= latency_tokens_ && max_len <= 128 && (dh == 32 || dh == 64) &&
-                        skinny_layer_supported(layers_[0]->qkv.w, layers_[0]->o.w, layers_[0]->ffi.w, layers_[0]->ffo.w) &&
-                        qkv_attention2_supported(layers_[0]->qkv.w, nh, dh, max_len);
-    if (skinny) {
-        const int tb = (T + 31) / 32, Lz = hp_.n_layer;
-        float *v32 = v32_.as<float>();
-        for (int il = 0; il < Lz; ++il) {
-            LayerWeights &L = *layers_[il];
-            // (from the second layer on the QKV kernel LayerNorms the previous layer's output itself and writes x)
-            LayerWeights *P = il ? layers_[il - 1] : nullptr;
-            timed("skinny_qkv", 2.0 * Td * 3 * H * H, s, [&] {
-                launch_skinny_gemm(0, L.qkv.w, x, P ? v32 : nullptr, P ? P->ln_out_w.as<float>() : nullptr, P ? P->ln_out_b.as<float>() : nullptr,
-                                   x, L.qkv_b.as<float>(), nullptr, qkv, nullptr, tb, s);
-            });
-            timed("attention", att_flops, s, [&] { (void)launch_attention_mfma(qkv, d_cu, B, nh, dh, max_len, ctx, s); });
-            timed("skinny_proj", 2.0 * Td * H * H, s, [&] {
-                launch_skinny_gemm(1, L.o.w, ctx, nullptr, nullptr, nullptr, nullptr, L.o_b.as<float>(), x, nullptr, v32, tb, s);
-            });
-            timed("skinny_ffn_up", 2.0 * Td * H * I, s, [&] {
-                launch_skinny_gemm(2, L.ffi.w, nullptr, v32, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), y, L.ffi_b.as<float>(), nullptr, ff, nullptr, tb, s);
-            });
-            timed("skinny_ffn_down", 2.0 * Td * H * I, s, [&] {
-                launch_skinny_gemm(3, L.ffo.w, ff, nullptr, nullptr, nullptr, nullptr, L.ffo_b.as<float>(), y, nullptr, v32, tb, s);
-            });
-            if (il + 1 == Lz || d_hidden) {
-                // (the last layer, or a hidden-state tap: somebody has to materialise x now; the next QKV kernel writes the same bits again)
-                timed("skinny_layernorm", 0.0, s, [&] { launch_skinny_layernorm(v32, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), x, tb, H, s); });
-            }
-            tap(il + 1);
-        }
-    }
-    // All layers in one launch, a workgroup per window (model_kernel.hip) — the two fused kernels' bodies as phases, no kernel
-    // boundary to put the workgroups back in step.  Batches of FULL windows (every sentence exactly 128 tokens: T = 128 B) take the
-    // specialised form (every window is one whole sentence, whatever list the caller built).
-    const bool one_launch = !skinny && one_launch_ok && one_launch_pays;
-    if (one_launch) {
-        ModelLayerWeights mw[16];
-        for (int il = 0; il < hp_.n_layer; ++il) {
-            LayerWeights &L = *layers_[il];
-            mw[il] = {&L.qkv.w, &L.o.w, &L.ffi.w, &L.ffo.w, L.qkv_b.as<float>(), L.o_b.as<float>(), L.ln_att_w.as<float>(), L.ln_att_b.as<float>(),
-                      L.ffi_b.as<float>(), L.ffo_b.as<float>(), L.ln_out_w.as<float>(), L.ln_out_b.as<float>()};
-        }
-        timed("model_kernel", hp_.n_layer * (2.0 * Td * 3 * H * H + att_flops + 2.0 * Td * H * H + 4.0 * Td * H * I), s, [&] {
-            launch_model_kernel(mw, hp_.n_layer, x, ctx, d_cu, B, T, d_windows, n_windows, d_n_windows, nh, d_out, max_len, status_.as<int>(), slots, s);
-        });
-    }
-    // LayerNorm folding (kernels.h GemmLnFold): models whose layers run as gemm256 mat-muls on f16 images (H = 768) keep the
-    // UN-normalised sums u1 (in y) and u2 (in x) and never launch a LayerNorm of their own but the last one; a hidden-state tap
-    // wants the normalised states and takes the plain sequence
-    bool fold = ln_fold_ && gemm256_ && !gemm_naive_ && !skinny && !one_launch && !d_hidden && H > 384 && H % 256 == 0 && ln_rows2_.p;
-    for (int il = 0; fold && il < hp_.n_layer; ++il) {
-        LayerWeights &L = *layers_[il];
-        fold = L.fold_ok && gemm256_supported(L.o.w, t_pad) && gemm256_supported(L.ffo.w, t_pad) && gemm256_supported(L.ffi_fold.w, t_pad) &&
-               gemm256_supported(L.qkv.w, t_pad) && !(qkv2_ && qkv_attention2_supported(L.qkv.w, nh, dh, max_len)) &&
-               !(tail_ && layer_tail_supported(L.o.w, L.ffi.w, L.ffo.w));
-    }
-    for (int il = 0; fold && il < hp_.n_layer; ++il) {
-        LayerWeights &L = *layers_[il];
-        const int P = 2 * H / 256;
-        float2 *st1 = ln_stats1_.as<float2>(), *st2 = ln_stats2_.as<float2>();
-        float4 *rows1 = ln_rows1_.as<float4>(), *rows2 = ln_rows2_.as<float4>();
-        GemmLnFold ln;
-        if (il == 0) {
-            // x = LayerNorm(embeddings), materialised by the embedding kernel: the plain projection (4-bit planes where the file has them)
-            const bool planes = L.qkv_q4.w.qs && L.qkv_q4.mfma_ok && gemm256_supported(L.qkv_q4.w, t_pad);
-            gemm("gemm_qkv", planes ? L.qkv_q4 : L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS);
-        } else {
-            // x holds u2 of the layer before: its output LayerNorm rides in the folded weights, the statistics k-step and the row scale
-            ln = GemmLnFold(); ln.flags = GemmLnFold::IN; ln.rows_in = rows2; ln.waug = L.qkv_waug.as<half_t>();
-            gemm("gemm_qkv", L.qkv_fold, x, nullptr, nullptr, qkv, EPI_BIAS, &ln);
-        }
-        timed("attention", att_flops, s, [&] {
-            if (attn_naive_ || !launch_attention_mfma(qkv, d_cu, B, nh, dh, max_len, ctx, s))
-                launch_attention_naive(qkv, d_cu, B, nh, dh, max_len, ctx, s);
-        });
-        // u1 = ctx Wo^T + bo + (x | LayerNorm(u2 of the layer before)) -> y, with its rows' partial statistics
-        ln = GemmLnFold(); ln.flags = GemmLnFold::STATS | (il ? GemmLnFold::RES : 0); ln.stats = st1;
-        ln.rows_res = rows2; ln.gb = L.o_gb.as<unsigned>();
-        gemm("gemm_attn_out", L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, &ln);
-        timed("ln_rows_finalize", 0.0, s, [&] { launch_ln_rows_finalize(st1, P, t_pad, H, rows1, s); });
-        ln = GemmLnFold(); ln.flags = GemmLnFold::IN; ln.rows_in = rows1; ln.waug = L.ffi_waug.as<half_t>();
-        gemm("gemm_ffn_up", L.ffi_fold, y, nullptr, nullptr, ff, EPI_BIAS_GELU, &ln);
-        // u2 = ff W2^T + b2 + LayerNorm(u1) -> x
-        ln = GemmLnFold(); ln.flags = GemmLnFold::STATS | GemmLnFold::RES; ln.stats = st2; ln.rows_res = rows1; ln.gb = L.ffo_gb.as<unsigned>();
-        gemm("gemm_ffn_down", L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID, &ln);
-        timed("ln_rows_finalize", 0.0, s, [&] { launch_ln_rows_finalize(st2, P, t_pad, H, rows2, s); });
-        if (il + 1 == hp_.n_layer)     // (the pooling reads normalised rows: the one LayerNorm launch of the pass)
-            timed("layernorm", 0.0, s, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), T, H, s); });
-    }
-    for (int il = 0; !fold && !skinny && !one_launch && il < hp_.n_layer; ++il) {
-        LayerWeights &L = *layers_[il];
-        if (qkv2_ && !gemm_naive_ && !attn_naive_ && L.qkv.mfma_ok && qkv_attention2_supported(L.qkv.w, nh, dh, max_len)) {
-            // windows of 128 token slots holding whole sentences: Q|K|V never reach HBM whatever the sentence lengths
-            timed("qkv_attention2", 2.0 * Td * L.qkv.w.N * L.qkv.w.K + att_flops, s, [&] {
-                launch_qkv_attention2(L.qkv.w, x, L.qkv_b.as<float>(), d_cu, B, d_windows, n_windows, d_n_windows, max_len, nh, slots, ctx, s);
-            });
-        } else {
-            // (q4 files: the 4-bit planes of the stacked matrix where its f16 image overflows an XCD's L2 and gemm256 takes the launch)
-            const bool planes = L.qkv_q4.w.qs && L.qkv_q4.mfma_ok && gemm256_ && !gemm_naive_ && gemm256_supported(L.qkv_q4.w, t_pad);
-            gemm("gemm_qkv", planes ? L.qkv_q4 : L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS);
-            timed("attention", att_flops, s, [&] {
-                if (attn_naive_ || !launch_attention_mfma(qkv, d_cu, B, nh, dh, max_len, ctx, s))
-                    launch_attention_naive(qkv, d_cu, B, nh, dh, max_len, ctx, s);
-            });
-        }
-        if (tail_ && !gemm_naive_ && L.o.mfma_ok && L.ffi.mfma_ok && L.ffo.mfma_ok && layer_tail_supported(L.o.w, L.ffi.w, L.ffo.w)) {
-            // out-projection + LN + FFN + LN in one launch, a pair of specialist waves per 32 tokens: y and the intermediate
-            // never leave the chip
-            timed("layer_tail", 2.0 * Td * H * H + 4.0 * Td * H * I, s, [&] {
-                launch_layer_tail(L.o.w, L.ffi.w, L.ffo.w, ctx, x, L.o_b.as<float>(), L.ln_att_w.as<float>(),
-                                  L.ln_att_b.as<float>(), L.ffi_b.as<float>(), L.ffo_b.as<float>(),
-                                  L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), x, t_pad, s);
-            });
-        } else {
-            gemm("gemm_attn_out", L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID);
-            timed("layernorm", 0.0, s, [&] { launch_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), T, H, s); });
-            gemm("gemm_ffn_up", L.ffi, y, L.ffi_b.as<float>(), nullptr, ff, EPI_BIAS_GELU);
-            gemm("gemm_ffn_down", L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID);
-            timed("layernorm", 0.0, s, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), T, H, s); });
-        }
-        tap(il + 1);
-    }
-    // (the one-launch kernel's workgroups pool their sentences themselves)
-    if (!one_launch) timed("pool_normalize", 2.0 * Td * H, s, [&] { launch_pool_normalize(x, d_cu, B, H, max_len, status_.as<int>(), d_out, s); });
-    (void)I;
+    if (!ok) return -1;
     HIP_OK(hipGetLastError(), err, -1);
     HIP_OK(hipEventRecord(busy_, s), err, -1);
     return 0;
 }
 
-// f32 files at the reference's precision (f32_route.hip; reference bert.cpp:784-913 with GGML_TYPE_F32 tensors): the same
-// sequence of operations as the tiled family, every one in f32.  Called from eval_packed_device behind its workspace sizing
-// and its wait for the previous pass.
-int Engine::forward_f32(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s, float *d_hidden,
-                        std::string &err) {
-    const int H = hp_.n_embd, I = hp_.n_intermediate, nh = hp_.n_head, dh = H / nh;
-    float *x = x_.as<float>(), *qkv = qkv_.as<float>(), *ctx = ctx_.as<float>(), *y = y_.as<float>(), *ff = ff_.as<float>();
-    const double Td = (double)T;
-    auto gemm = [&](const char *name, GemmWeightStore &W, const float *A, const float *bias, const float *resid, float *C, int epi) {
-        if (profiling_ && replay_name_.empty()) families_["family:gemm_f32"] += 1;
-        timed(name, 2.0 * Td * W.w.N * W.w.K, s, [&] { launch_f32_gemm(A, W.w.w32, bias, resid, C, T, W.w.N, W.w.K, epi, s); });
+// The route of a pass and, per layer, its kernels: every eligibility test of the forward pass, each made here once.  Launches nothing.
+Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s,
+                          float *d_hidden, const int2 *d_windows, int n_windows, int slots) const {
+    // (t_pad: whole tiles of every kernel family, 128- and 256-token tiles)
+    Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, d_out, d_hidden, s, d_windows, n_windows};
+    if (f32_file_ && f32_exact_) { p.route = Route::F32; return p; }
+    const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh, Lz = hp_.n_layer;
+    auto family = [&](const GemmWeightStore &W) {
+        if (W.mfma_ok && gemm256_ && !gemm_naive_ && gemm256_supported(W.w, p.t_pad)) return Family::GEMM256;
+        return W.mfma_ok && (!gemm_naive_ || !W.w.naive16) ? Family::MFMA : Family::NAIVE;
     };
-    auto tap = [&](int idx) {
-        if (d_hidden) (void)hipMemcpyAsync(d_hidden + (size_t)idx * T * H, x, (size_t)T * H * 4, hipMemcpyDeviceToDevice, s);
-    };
-    timed("embed_ln", 0.0, s, [&] {
-        launch_f32_embed_ln(word_emb_.as<float>(), type_emb_.as<float>(), pos_emb_.as<float>(), ln_e_w_.as<float>(), ln_e_b_.as<float>(), d_tokens,
-                            d_cu, B, T, H, hp_.n_vocab, x, s);
-    });
-    tap(0);
-    for (int il = 0; il < hp_.n_layer; ++il) {
-        LayerWeights &L = *layers_[il];
-        gemm("gemm_qkv", L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS);
-        timed("attention", 4.0 * Td * max_len * H, s, [&] { launch_f32_attention(qkv, d_cu, B, nh, dh, max_len, ctx, s); });
-        gemm("gemm_attn_out", L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID);
-        timed("layernorm", 0.0, s, [&] { launch_f32_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), T, H, s); });
-        gemm("gemm_ffn_up", L.ffi, y, L.ffi_b.as<float>(), nullptr, ff, EPI_BIAS_GELU);
-        gemm("gemm_ffn_down", L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID);
-        timed("layernorm", 0.0, s, [&] { launch_f32_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), T, H, s); });
-        tap(il + 1);
+    // per layer (a file may mix types or shapes from layer to layer): its stages and mat-mul kernels, and whether it can run in the
+    // one-launch kernel (which takes all layers' pointers) or with its LayerNorms folded (only models the fused kernels do not take)
+    p.layers.resize(Lz);
+    bool qkv2_shape0 = false, one_launch = true, fold = ln_fold_ && H > 384 && H % 256 == 0 && ln_rows2_.p;
+    for (int il = 0; il < Lz; ++il) {
+        const LayerWeights &L = *layers_[il];
+        LayerPlan &lp = p.layers[il];
+        const bool qkv2_shape = qkv_attention2_supported(L.qkv.w, nh, dh, max_len), tail_shape = layer_tail_supported(L.o.w, L.ffi.w, L.ffo.w);
+        if (il == 0) qkv2_shape0 = qkv2_shape;
+        lp.qkv2 = qkv2_ && !gemm_naive_ && !attn_naive_ && L.qkv.mfma_ok && qkv2_shape;
+        lp.tail = tail_ && !gemm_naive_ && L.o.mfma_ok && L.ffi.mfma_ok && L.ffo.mfma_ok && tail_shape;
+        // (q4 files: the 4-bit planes of the stacked matrix where its f16 image overflows an XCD's L2 and gemm256 takes the launch)
+        lp.planes = L.qkv_q4.w.qs && family(L.qkv_q4) == Family::GEMM256;
+        lp.qkv = family(lp.planes ? L.qkv_q4 : L.qkv), lp.o = family(L.o), lp.ffi = family(L.ffi), lp.ffo = family(L.ffo);
+        one_launch = one_launch && L.qkv.mfma_ok && L.o.mfma_ok && L.ffi.mfma_ok && L.ffo.mfma_ok && L.ffi.w.w16p && L.ffo.w.w16p &&
+                     model_kernel_supported(L.qkv.w, L.o.w, L.ffi.w, L.ffo.w, Lz, nh, dh, max_len);
+        fold = fold && L.fold_ok && (il ? family(L.qkv_fold) : lp.qkv) == Family::GEMM256 && lp.o == Family::GEMM256 &&
+               family(L.ffi_fold) == Family::GEMM256 && lp.ffo == Family::GEMM256 && !(qkv2_ && qkv2_shape) && !(tail_ && tail_shape);
     }
-    timed("pool_normalize", 2.0 * Td * H, s, [&] { launch_f32_pool_normalize(x, d_cu, B, H, max_len, status_.as<int>(), d_out, s); });
-    (void)I;
-    HIP_OK(hipGetLastError(), err, -1);
-    HIP_OK(hipEventRecord(busy_, s), err, -1);
-    return 0;
+    // a hidden-state tap wants every layer's normalised states: it takes neither the one-launch kernel nor the folded LayerNorms
+    if (d_hidden) one_launch = fold = false;
+    const bool fused_windows = p.layers[0].qkv2, latency_call = latency_ && T <= latency_tokens_;
+    one_launch = one_launch && fused_windows && one_launch_ && tail_ && !latency_call;
+    // sentence windows of the fused projection+attention kernel: the caller's (host path), or built on the device from cu_seqlens
+    // when packing can pay — sentences on average clearly shorter than max_len; for full-length batches the uniform rule
+    // (max_len-sized places) gives the same windows without the extra launch.  (Forced one-launch: the kernel takes a window list
+    // or one sentence per window — its layer-tail phase needs a window's tokens to be at most 128 whatever the sentences' lengths.)
+    const bool full_windows = (long long)B * 128 == T;
+    const int spw = qkv_attention2_sentences_per_window(max_len, slots);
+    if (!d_windows && fused_windows &&
+        (4ll * ((B + spw - 1) / spw) * 128 > 5 * ((long long)T + (long long)(slots / 2) * B) || (one_launch && one_launch_ == 2 && spw > 1 && !full_windows))) {
+        p.build_windows = true;
+        p.windows = windows_.as<int2>();
+        p.n_windows_dev = status_.as<int>() + 1;
+        // upper bound from T and B alone (the extra workgroups return at once): "never more than the uniform rule" only holds for
+        // batches that keep their max_len promise, and a broken promise must cost the offender its row, not a neighbour its window
+        p.n_windows = qkv_attention2_max_windows(B, T, slots);
+    }
+    // When the one-launch kernel pays: its layer-tail phase costs a window 128 rows' time however few tokens it holds, the layer-tail
+    // KERNEL runs on the packed tokens — 0.32 + 0.68 fill against 0.94 (full windows: +6.7 %): from a fill of 0.91.  The window
+    // count is known for the caller's list and for one sentence per window, not for a list built on the device.
+    bool one_launch_pays = full_windows || one_launch_ == 2;
+    if (!one_launch_pays && !p.build_windows) one_launch_pays = (d_windows || spw == 1) && 100ll * T >= 95ll * 128 * (d_windows ? n_windows : B);
+    const LayerWeights &L0 = *layers_[0];
+    const bool skinny = latency_call && tail_ && qkv2_ && !gemm_naive_ && !attn_naive_ && max_len <= 128 && (dh == 32 || dh == 64) &&
+                        skinny_layer_supported(L0.qkv.w, L0.o.w, L0.ffi.w, L0.ffo.w) && qkv2_shape0;
+    p.route = skinny ? Route::LATENCY : one_launch && one_launch_pays ? Route::ONE_LAUNCH : fold ? Route::FOLDED : Route::LAYERED;
+    return p;
+}
+
+// one weight mat-mul on the kernel family the plan chose: counted for the profile ("family:<kernel>_<weights>"), timed, launched.  A
+// LayerNorm-folding form that no kernel runs fails the pass (it must not run as the plain mat-mul).
+bool Engine::gemm(const Plan &p, const char *name, Family f, const GemmWeightStore &W, const void *A, const float *bias, const void *resid,
+                  void *C, int epi, std::string &err, const GemmLnFold *ln) {
+    static const char *const kernel[] = {"gemm256", "gemm_mfma", "gemm_naive", "gemm_f32"};
+    if (profiling_ && replay_name_.empty())
+        families_[std::string("family:") + kernel[(int)f] + (f == Family::GEMM256 || f == Family::MFMA ? (W.w.type == GW_F16 ? "_f16" : "_q4") : "")] += 1;
+    const half_t *a = (const half_t *)A, *r = (const half_t *)resid;
+    bool ok = !(ln && ln->flags) || f == Family::GEMM256;
+    if (ok)
+        timed(name, 2.0 * p.T * W.w.N * W.w.K, p.s, [&] {
+            if (f == Family::F32) launch_f32_gemm((const float *)A, W.w.w32, bias, (const float *)resid, (float *)C, p.T, W.w.N, W.w.K, epi, p.s);
+            else if (f == Family::GEMM256) ok = launch_gemm256(W.w, a, bias, r, (half_t *)C, p.t_pad, epi, p.s, ln);
+            else if (f == Family::MFMA) launch_gemm_mfma(W.w, a, bias, r, (half_t *)C, p.t_pad, epi, p.s);
+            else launch_gemm_naive(W.w, a, bias, r, (half_t *)C, p.T, epi, p.s);
+        });
+    if (!ok) err = std::string(name) + ": no " + kernel[(int)f] + " kernel for LayerNorm-folding flags " + std::to_string(ln->flags) + ", epilogue " + std::to_string(epi);
+    return ok;
+}
+
+// (attention FLOPs: 4 * sum_b N_b^2 * H; only T and max_len are known here -> upper bound T * max_len)
+void Engine::attention(const Plan &p) {
+    const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh;
+    half_t *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>();
+    timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] {
+        if (attn_naive_ || !launch_attention_mfma(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s)) launch_attention_naive(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s);
+    });
+}
+
+// the layer states of eval_hidden as f32: x after the embedding LayerNorm (idx 0) and after every layer
+void Engine::tap(const Plan &p, int idx) {
+    const size_t n = (size_t)p.T * hp_.n_embd;
+    if (p.hidden && p.route == Route::F32) (void)hipMemcpyAsync(p.hidden + idx * n, x_.p, n * 4, hipMemcpyDeviceToDevice, p.s);
+    else if (p.hidden) launch_f16_to_f32(x_.as<half_t>(), p.hidden + idx * n, n, p.s);
+}
+
+// The latency route (skinny.hip): a call of a few windows would keep as many CUs of 256 busy on the fused kernels.  Same bits per
+// sentence (the route must not show in the results), seven short launches per layer.
+void Engine::forward_latency(const Plan &p) {
+    const int H = hp_.n_embd, I = hp_.n_intermediate, tb = (p.T + 31) / 32, Lz = hp_.n_layer;
+    half_t *x = x_.as<half_t>(), *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>(), *y = y_.as<half_t>(), *ff = ff_.as<half_t>();
+    float *v32 = v32_.as<float>();
+    for (int il = 0; il < Lz; ++il) {
+        const LayerWeights &L = *layers_[il];
+        // (from the second layer on the QKV kernel LayerNorms the previous layer's output itself and writes x)
+        const LayerWeights *P = il ? layers_[il - 1] : nullptr;
+        timed("skinny_qkv", 2.0 * p.T * 3 * H * H, p.s, [&] {
+            launch_skinny_gemm(0, L.qkv.w, x, P ? v32 : nullptr, P ? P->ln_out_w.as<float>() : nullptr, P ? P->ln_out_b.as<float>() : nullptr,
+                               x, L.qkv_b.as<float>(), nullptr, qkv, nullptr, tb, p.s);
+        });
+        attention(p);
+        timed("skinny_proj", 2.0 * p.T * H * H, p.s, [&] {
+            launch_skinny_gemm(1, L.o.w, ctx, nullptr, nullptr, nullptr, nullptr, L.o_b.as<float>(), x, nullptr, v32, tb, p.s);
+        });
+        timed("skinny_ffn_up", 2.0 * p.T * H * I, p.s, [&] {
+            launch_skinny_gemm(2, L.ffi.w, nullptr, v32, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), y, L.ffi_b.as<float>(), nullptr, ff, nullptr, tb, p.s);
+        });
+        timed("skinny_ffn_down", 2.0 * p.T * H * I, p.s, [&] {
+            launch_skinny_gemm(3, L.ffo.w, ff, nullptr, nullptr, nullptr, nullptr, L.ffo_b.as<float>(), y, nullptr, v32, tb, p.s);
+        });
+        // (the last layer, or a hidden-state tap: somebody has to materialise x now; the next QKV kernel writes the same bits again)
+        if (il + 1 == Lz || p.hidden)
+            timed("skinny_layernorm", 0.0, p.s, [&] { launch_skinny_layernorm(v32, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), x, tb, H, p.s); });
+        tap(p, il + 1);
+    }
+}
+
+// All layers in one launch, a workgroup per window (model_kernel.hip) — the two fused kernels' bodies as phases, no kernel boundary
+// to put the workgroups back in step.  Batches of FULL windows (every sentence exactly 128 tokens: T = 128 B) take the specialised
+// form (every window is one whole sentence, whatever list the caller built).
+void Engine::forward_one_launch(const Plan &p) {
+    const int H = hp_.n_embd, I = hp_.n_intermediate;
+    ModelLayerWeights mw[16];
+    for (int il = 0; il < hp_.n_layer; ++il) {
+        const LayerWeights &L = *layers_[il];
+        mw[il] = {&L.qkv.w, &L.o.w, &L.ffi.w, &L.ffo.w, L.qkv_b.as<float>(), L.o_b.as<float>(), L.ln_att_w.as<float>(), L.ln_att_b.as<float>(),
+                  L.ffi_b.as<float>(), L.ffo_b.as<float>(), L.ln_out_w.as<float>(), L.ln_out_b.as<float>()};
+    }
+    timed("model_kernel", hp_.n_layer * (2.0 * p.T * 3 * H * H + 4.0 * p.T * p.max_len * H + 2.0 * p.T * H * H + 4.0 * p.T * H * I), p.s, [&] {
+        launch_model_kernel(mw, hp_.n_layer, x_.as<half_t>(), ctx_.as<half_t>(), p.cu, p.B, p.T, p.windows, p.n_windows, p.n_windows_dev, hp_.n_head,
+                            p.out, p.max_len, status_.as<int>(), p.slots, p.s);
+    });
+}
+
+// LayerNorm folding (kernels.h GemmLnFold; the plan put every mat-mul on gemm256's f16 form): the layers keep the UN-normalised sums
+// u1 (in y) and u2 (in x) and never launch a LayerNorm of their own but the last one
+bool Engine::forward_folded(const Plan &p, std::string &err) {
+    const int H = hp_.n_embd, P = 2 * H / 256;
+    const Family G = Family::GEMM256;
+    half_t *x = x_.as<half_t>(), *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>(), *y = y_.as<half_t>(), *ff = ff_.as<half_t>();
+    float2 *st1 = ln_stats1_.as<float2>(), *st2 = ln_stats2_.as<float2>();
+    float4 *rows1 = ln_rows1_.as<float4>(), *rows2 = ln_rows2_.as<float4>();
+    for (int il = 0; il < hp_.n_layer; ++il) {
+        const LayerWeights &L = *layers_[il];
+        GemmLnFold ln;
+        if (il == 0) {
+            // x = LayerNorm(embeddings), materialised by the embedding kernel: the plain projection (4-bit planes where the file has them)
+            if (!gemm(p, "gemm_qkv", G, p.layers[0].planes ? L.qkv_q4 : L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS, err)) return false;
+        } else {
+            // x holds u2 of the layer before: its output LayerNorm rides in the folded weights, the statistics k-step and the row scale
+            ln.flags = GemmLnFold::IN; ln.rows_in = rows2; ln.waug = L.qkv_waug.as<half_t>();
+            if (!gemm(p, "gemm_qkv", G, L.qkv_fold, x, nullptr, nullptr, qkv, EPI_BIAS, err, &ln)) return false;
+        }
+        attention(p);
+        // u1 = ctx Wo^T + bo + (x | LayerNorm(u2 of the layer before)) -> y, with its rows' partial statistics
+        ln = GemmLnFold(); ln.flags = GemmLnFold::STATS | (il ? GemmLnFold::RES : 0); ln.stats = st1; ln.rows_res = rows2; ln.gb = L.o_gb.as<unsigned>();
+        if (!gemm(p, "gemm_attn_out", G, L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, err, &ln)) return false;
+        timed("ln_rows_finalize", 0.0, p.s, [&] { launch_ln_rows_finalize(st1, P, p.t_pad, H, rows1, p.s); });
+        ln = GemmLnFold(); ln.flags = GemmLnFold::IN; ln.rows_in = rows1; ln.waug = L.ffi_waug.as<half_t>();
+        if (!gemm(p, "gemm_ffn_up", G, L.ffi_fold, y, nullptr, nullptr, ff, EPI_BIAS_GELU, err, &ln)) return false;
+        // u2 = ff W2^T + b2 + LayerNorm(u1) -> x
+        ln = GemmLnFold(); ln.flags = GemmLnFold::STATS | GemmLnFold::RES; ln.stats = st2; ln.rows_res = rows1; ln.gb = L.ffo_gb.as<unsigned>();
+        if (!gemm(p, "gemm_ffn_down", G, L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID, err, &ln)) return false;
+        timed("ln_rows_finalize", 0.0, p.s, [&] { launch_ln_rows_finalize(st2, P, p.t_pad, H, rows2, p.s); });
+        if (il + 1 == hp_.n_layer)     // (the pooling reads normalised rows: the one LayerNorm launch of the pass)
+            timed("layernorm", 0.0, p.s, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.T, H, p.s); });
+    }
+    return true;
+}
+
+// A layer at a time, each with the stages and mat-mul kernels the plan chose for it
+bool Engine::forward_layers(const Plan &p, std::string &err) {
+    const int H = hp_.n_embd, I = hp_.n_intermediate;
+    half_t *x = x_.as<half_t>(), *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>(), *y = y_.as<half_t>(), *ff = ff_.as<half_t>();
+    for (int il = 0; il < hp_.n_layer; ++il) {
+        const LayerWeights &L = *layers_[il];
+        const LayerPlan &lp = p.layers[il];
+        if (lp.qkv2) {
+            // windows of 128 token slots holding whole sentences: Q|K|V never reach HBM whatever the sentence lengths
+            timed("qkv_attention2", 2.0 * p.T * L.qkv.w.N * L.qkv.w.K + 4.0 * p.T * p.max_len * H, p.s, [&] {
+                launch_qkv_attention2(L.qkv.w, x, L.qkv_b.as<float>(), p.cu, p.B, p.windows, p.n_windows, p.n_windows_dev, p.max_len, hp_.n_head, p.slots, ctx, p.s);
+            });
+        } else {
+            if (!gemm(p, "gemm_qkv", lp.qkv, lp.planes ? L.qkv_q4 : L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS, err)) return false;
+            attention(p);
+        }
+        if (lp.tail) {
+            // out-projection + LN + FFN + LN in one launch, a pair of specialist waves per 32 tokens: y and the intermediate never leave the chip
+            timed("layer_tail", 2.0 * p.T * H * H + 4.0 * p.T * H * I, p.s, [&] {
+                launch_layer_tail(L.o.w, L.ffi.w, L.ffo.w, ctx, x, L.o_b.as<float>(), L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), L.ffi_b.as<float>(),
+                                  L.ffo_b.as<float>(), L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), x, p.t_pad, p.s);
+            });
+        } else {
+            if (!gemm(p, "gemm_attn_out", lp.o, L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, err)) return false;
+            timed("layernorm", 0.0, p.s, [&] { launch_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), p.T, H, p.s); });
+            if (!gemm(p, "gemm_ffn_up", lp.ffi, L.ffi, y, L.ffi_b.as<float>(), nullptr, ff, EPI_BIAS_GELU, err) ||
+                !gemm(p, "gemm_ffn_down", lp.ffo, L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID, err)) return false;
+            timed("layernorm", 0.0, p.s, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.T, H, p.s); });
+        }
+        tap(p, il + 1);
+    }
+    return true;
+}
+
+// f32 files at the reference's precision (f32_route.hip; reference bert.cpp:784-913 with GGML_TYPE_F32 tensors): the same
+// sequence of operations as the tiled family, every one in f32, with embedding and pooling kernels of its own.
+bool Engine::forward_f32(const Plan &p, std::string &err) {
+    const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh;
+    const Family F = Family::F32;
+    float *x = x_.as<float>(), *qkv = qkv_.as<float>(), *ctx = ctx_.as<float>(), *y = y_.as<float>(), *ff = ff_.as<float>();
+    timed("embed_ln", 0.0, p.s, [&] {
+        launch_f32_embed_ln(word_emb_.as<float>(), type_emb_.as<float>(), pos_emb_.as<float>(), ln_e_w_.as<float>(), ln_e_b_.as<float>(), p.tokens,
+                            p.cu, p.B, p.T, H, hp_.n_vocab, x, p.s);
+    });
+    tap(p, 0);
+    for (int il = 0; il < hp_.n_layer; ++il) {
+        const LayerWeights &L = *layers_[il];
+        if (!gemm(p, "gemm_qkv", F, L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS, err)) return false;
+        timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] { launch_f32_attention(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s); });
+        if (!gemm(p, "gemm_attn_out", F, L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, err)) return false;
+        timed("layernorm", 0.0, p.s, [&] { launch_f32_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), p.T, H, p.s); });
+        if (!gemm(p, "gemm_ffn_up", F, L.ffi, y, L.ffi_b.as<float>(), nullptr, ff, EPI_BIAS_GELU, err) ||
+            !gemm(p, "gemm_ffn_down", F, L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID, err)) return false;
+        timed("layernorm", 0.0, p.s, [&] { launch_f32_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.T, H, p.s); });
+        tap(p, il + 1);
+    }
+    timed("pool_normalize", 2.0 * p.T * H, p.s, [&] { launch_f32_pool_normalize(x, p.cu, p.B, H, p.max_len, status_.as<int>(), p.out, p.s); });
+    return true;
 }
 
 static bool ensure_pinned(void **p, size_t *cap, size_t need, std::string &err) {

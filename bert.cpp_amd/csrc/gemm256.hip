@@ -604,7 +604,7 @@ bool gemm256_supported(const GemmWeight &W, int M_pad) {
     return (W.type == GW_F16 ? W.w16 != nullptr : W.qs != nullptr && W.sc != nullptr) && W.N % G2_BN == 0 && W.K % G2_BK == 0 && W.K >= 2 * G2_BK && M_pad % G2_BM == 0 && M_pad > 0;
 }
 
-void launch_gemm256(const GemmWeight &W, const half_t *A, const float *bias, const half_t *resid, half_t *C, int M_pad,
+bool launch_gemm256(const GemmWeight &W, const half_t *A, const float *bias, const half_t *resid, half_t *C, int M_pad,
                     int epilogue, hipStream_t stream, const GemmLnFold *ln) {
     Gemm256Args a;
     a.A = A; a.w16 = W.w16; a.bias = bias; a.resid = resid; a.C = C; a.qs = W.qs; a.sc = W.sc;
@@ -642,20 +642,22 @@ void launch_gemm256(const GemmWeight &W, const half_t *A, const float *bias, con
             default: go(gemm256_kernel<E, GW_Q4_1>, 6 + E); break;
         }
     };
-    if (ln && ln->flags && W.type == GW_F16) {
+    if (ln && ln->flags) {
         // (the folded-LayerNorm forms: f16 images only — the engine does not fold where a matrix stays on 4-bit planes)
+        if (W.type != GW_F16) return false;
         if (epilogue == EPI_BIAS && ln->flags == GemmLnFold::IN) go(gemm256_kernel<EPI_BIAS, GW_F16, LN_IN>, 9);
         else if (epilogue == EPI_BIAS_GELU && ln->flags == GemmLnFold::IN) go(gemm256_kernel<EPI_BIAS_GELU, GW_F16, LN_IN>, 10);
         else if (epilogue == EPI_BIAS_RESID && ln->flags == GemmLnFold::STATS) go(gemm256_kernel<EPI_BIAS_RESID, GW_F16, LN_STATS>, 11);
         else if (epilogue == EPI_BIAS_RESID && ln->flags == (GemmLnFold::RES | GemmLnFold::STATS)) go(gemm256_kernel<EPI_BIAS_RESID, GW_F16, LN_RES | LN_STATS>, 12);
-        else fprintf(stderr, "launch_gemm256: unsupported LayerNorm-folding form (epilogue %d, flags %d): nothing launched\n", epilogue, ln->flags);
-        return;
+        else return false;
+        return true;
     }
     switch (epilogue) {
         case EPI_BIAS: by_type(std::integral_constant<int, EPI_BIAS>{}); break;
         case EPI_BIAS_GELU: by_type(std::integral_constant<int, EPI_BIAS_GELU>{}); break;
         default: by_type(std::integral_constant<int, EPI_BIAS_RESID>{}); break;
     }
+    return true;
 }
 
 }  // namespace bert_hip

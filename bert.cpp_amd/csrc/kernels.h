@@ -222,7 +222,9 @@ struct GemmLnFold {
     const unsigned *gb = nullptr;         // RES: [N] f16 gamma | f16 (beta + bias) << 16
     float2 *stats = nullptr;              // STATS: [M_pad][2 N / 256] (sum, sum of squares)
 };
-void launch_gemm256(const GemmWeight &W, const half_t *A, const float *bias, const half_t *resid, half_t *C, int M_pad,
+// false, launching nothing: a LayerNorm-folding form (ln->flags set) that no kernel runs — a matrix that is not an f16 image, or
+// an (epilogue, flags) pair other than (EPI_BIAS | EPI_BIAS_GELU, IN), (EPI_BIAS_RESID, STATS), (EPI_BIAS_RESID, RES | STATS)
+bool launch_gemm256(const GemmWeight &W, const half_t *A, const float *bias, const half_t *resid, half_t *C, int M_pad,
                     int epilogue, hipStream_t stream, const GemmLnFold *ln = nullptr);
 // per-row partial statistics [T][P] -> {rstd, -mean rstd, -mean, std} (eps 1e-5, H features per row)
 void launch_ln_rows_finalize(const float2 *stats, int P, int T, int H, float4 *rows, hipStream_t stream);

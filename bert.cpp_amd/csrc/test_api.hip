@@ -45,7 +45,7 @@ int32_t bert_hip_test_gemm(int32_t M, int32_t N, int32_t K, const uint16_t *A, c
     }
     if (impl == 3) {
         if (!gemm256_supported(ws.w, M_pad)) return -2;
-        launch_gemm256(ws.w, dA.as<half_t>(), dB.as<float>(), dR.as<half_t>(), dC.as<half_t>(), M_pad, epilogue, nullptr);
+        if (!launch_gemm256(ws.w, dA.as<half_t>(), dB.as<float>(), dR.as<half_t>(), dC.as<half_t>(), M_pad, epilogue, nullptr)) return -3;
     } else if (impl == 0) launch_gemm_mfma(ws.w, dA.as<half_t>(), dB.as<float>(), dR.as<half_t>(), dC.as<half_t>(), M_pad, epilogue, nullptr);
     else launch_gemm_naive(ws.w, dA.as<half_t>(), dB.as<float>(), dR.as<half_t>(), dC.as<half_t>(), M, epilogue, nullptr);
     CK(hipGetLastError());
@@ -95,13 +95,14 @@ int32_t bert_hip_test_gemm_lnfold(int32_t M, int32_t K1, int32_t H, int32_t N2, 
         if (!gb.upload(v.data(), v.size() * 4, err)) return -1;
         ln.flags |= GemmLnFold::RES; ln.rows_res = dRowsRes.as<float4>(); ln.gb = gb.as<unsigned>();
     }
-    launch_gemm256(w1.w, dA.as<half_t>(), dB1.as<float>(), dR.as<half_t>(), dU.as<half_t>(), M_pad, EPI_BIAS_RESID, nullptr, &ln);
-    launch_ln_rows_finalize(dStats.as<float2>(), P, M_pad, H, dRows.as<float4>(), nullptr);
+    bool ran = launch_gemm256(w1.w, dA.as<half_t>(), dB1.as<float>(), dR.as<half_t>(), dU.as<half_t>(), M_pad, EPI_BIAS_RESID, nullptr, &ln);
+    if (ran) launch_ln_rows_finalize(dStats.as<float2>(), P, M_pad, H, dRows.as<float4>(), nullptr);
     GemmLnFold in;
     in.flags = GemmLnFold::IN; in.rows_in = dRows.as<float4>(); in.waug = waug.as<half_t>();
-    launch_gemm256(w2.w, dU.as<half_t>(), nullptr, nullptr, dOut.as<half_t>(), M_pad, epi2, nullptr, &in);
+    ran = ran && launch_gemm256(w2.w, dU.as<half_t>(), nullptr, nullptr, dOut.as<half_t>(), M_pad, epi2, nullptr, &in);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
+    if (!ran) { fprintf(stderr, "bert_hip_test_gemm_lnfold: launch_gemm256 has no kernel for this LayerNorm-folding form (epilogue %d)\n", epi2); return -3; }
     CK(hipMemcpy(u_out, dU.p, (size_t)M * H * 2, hipMemcpyDeviceToHost));
     CK(hipMemcpy(out2, dOut.p, (size_t)M * N2 * 2, hipMemcpyDeviceToHost));
     CK(hipMemcpy(rows_out, dRows.p, (size_t)M * 16, hipMemcpyDeviceToHost));

@@ -83,7 +83,9 @@ BERT_API int32_t bert_hip_check(struct bert_ctx *ctx);        /* 0 ok, 1 a batch
 
 /* Hidden-state tap for parity tests: one sentence, writes hidden[(n_layer+1)][n_tokens][n_embd]
  * f32 (after the embedding LayerNorm and after every encoder layer, reference bert.cpp:806-901)
- * and the final embedding.  Either output may be NULL.                                          */
+ * and the final embedding.  Either output may be NULL.  The tap needs every layer's normalised states, so it takes neither the
+ * all-layers-in-one-launch kernel nor the folded LayerNorms: at H = 768 with BERT_HIP_LN_FOLD on (the default) its embedding
+ * is that of the un-folded sequence and differs from bert_eval_batch's for the same sentence in the last bits.            */
 BERT_API int32_t bert_hip_eval_hidden(struct bert_ctx *ctx, const bert_vocab_id *tokens, int32_t n_tokens,
                                       float *hidden, float *embedding);
 
@@ -126,7 +128,8 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  *   BERT_HIP_CHUNK_TOKENS  max tokens evaluated per device pass by the host API (default 262144)
  *   BERT_HIP_LN_FOLD       1 (default) | 0 — models on the 256 x 256-tile mat-mul route (H = 768): the LayerNorms folded into the mat-muls around
  *                          them (no LayerNorm launch but the last; roundings differ from the un-folded sequence in the last bits), or a
- *                          LayerNorm kernel per LayerNorm
+ *                          LayerNorm kernel per LayerNorm.  Read at load: 0 builds no folded weight images, and set_option("ln_fold",
+ *                          "1") on such a context is ignored.  bert_hip_eval_hidden always takes the un-folded sequence.
  *   BERT_HIP_QUIET         1 = no progress text on stdout during load, no "unknown token" lines on stderr from bert_tokenize
  * bert_hip_set_option (after load; tests and tuning): "qkv2" / "tail" / "gemm256" / "latency" = "0" | "1" switch single kernels
  * of the fused family, "one_launch" = "0" | "1" (default: all layers in one launch for well-filled windows) | "2" (whenever the

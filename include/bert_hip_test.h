@@ -26,7 +26,8 @@ BERT_API int32_t bert_hip_test_gemm(int32_t M, int32_t N, int32_t K, const uint1
  *         statistics (computed here on the host), written UN-normalised with per-row partial statistics;
  *   out = epi2( LayerNorm(u; g, be) W2[N2][H]^T + b2 ),  epi2 0 = bias, 1 = bias + GELU: reads u itself, gamma folded into W2, one
  *         statistics k-step, rows scaled by 1 / std.
- * u_out [M][H], out2 [M][N2] f16 bits, rows_out [M][4] f32 {rstd, -mean rstd, -mean, std} of u.  Returns 0 on success.          */
+ * u_out [M][H], out2 [M][N2] f16 bits, rows_out [M][4] f32 {rstd, -mean rstd, -mean, std} of u.  Returns 0 on success, -3 when
+ * gemm256 has no kernel for the folded form asked for (any other epi2: the second mat-mul is not launched).                      */
 BERT_API int32_t bert_hip_test_gemm_lnfold(int32_t M, int32_t K1, int32_t H, int32_t N2, const uint16_t *A1, const uint16_t *W1,
                                            const float *b1, const uint16_t *r, const float *rg, const float *rb,
                                            const uint16_t *W2, const float *b2, const float *g, const float *be, int32_t epi2,
