@@ -17,18 +17,13 @@
 // order of S^T (4-key runs interleaved between the two half-waves) is used as-is for P^T and
 // the V^T fragment is gathered with the same permutation (two 8-byte LDS reads).
 // Sequences longer than 128 keys stream over 128-key chunks with an online softmax.
-#include "kernels.h"
-#include "tile_stream.h"      // (the timeline stamps of the tuning builds)
+#include "device.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 namespace bert_hip {
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // In-kernel phase clock of the tuning builds (-DBERT_HIP_TIMELINE): wave 0 and wave 4 of a workgroup (the two waves of one SIMD)
 // add up, over all their items and chunks, the shader cycles between phase boundaries: staging (an item's start to behind its
@@ -145,8 +140,7 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
                 const f16x8 a = __builtin_bit_cast(f16x8, vv[u][0]), b = __builtin_bit_cast(f16x8, vv[u][1]);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-                    *(f16x2v *)(Vt + (c * 8 + e) * vt_ld + 2 * rp) = f16x2v{a[e], b[e]};
+                    *(f16x2 *)(Vt + (c * 8 + e) * vt_ld + 2 * rp) = f16x2{a[e], b[e]};
                 }
             }
         }
@@ -218,14 +212,12 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
         // fragment addresses of the chunk at kc = 0: the swizzle of a K row depends on the row's low bits, i.e. on l31 only,
         // and a V^T row's keys are consecutive, so inside the chunk loop every read is base + compile-time offset and a
         // chunk step is one addition per base (left to the compiler this was ~100 address instructions per chunk)
-        typedef const __attribute__((address_space(3))) char *lds_bytes;       // (typed LDS pointers: generic ones become flat loads)
-        typedef const __attribute__((address_space(3))) half_t *lds_halfs;
-        lds_bytes kbase[D / 16];
+        lds_cptr<char> kbase[D / 16];
 #pragma unroll
-        for (int kk = 0; kk < D / 16; ++kk) kbase[kk] = (lds_bytes)Ks + k_off<D>(l31, kk * 2 + hi);
-        lds_halfs vbase[D / 32];
+        for (int kk = 0; kk < D / 16; ++kk) kbase[kk] = (lds_cptr<char>)Ks + k_off<D>(l31, kk * 2 + hi);
+        lds_cptr<half_t> vbase[D / 32];
 #pragma unroll
-        for (int dv = 0; dv < D / 32; ++dv) vbase[dv] = (lds_halfs)Vt + (dv * 32 + l31) * vt_ld + 4 * hi;
+        for (int dv = 0; dv < D / 32; ++dv) vbase[dv] = (lds_cptr<half_t>)Vt + (dv * 32 + l31) * vt_ld + 4 * hi;
         constexpr int K_ROW = D * 2;                   // bytes per K row
 
         constexpr int KT = CH / 32;                    // key tiles per step
@@ -246,7 +238,7 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
                 // puts every fragment into ONE register set — read, wait out the LDS round trip, MFMA, sixteen times per chunk
                 constexpr int NF = KT * (D / 16);
                 f16x8 kfr[NF];
-                auto rd = [&](int f) __attribute__((always_inline)) { kfr[f] = *(const __attribute__((address_space(3))) f16x8 *)(kbase[f % (D / 16)] + (f / (D / 16)) * 32 * K_ROW); };
+                auto rd = [&](int f) __attribute__((always_inline)) { kfr[f] = *(lds_cptr<f16x8>)(kbase[f % (D / 16)] + (f / (D / 16)) * 32 * K_ROW); };
 #pragma unroll
                 for (int f = 0; f < S_AHEAD; ++f) rd(f);
                 __builtin_amdgcn_sched_group_barrier(0x100, S_AHEAD, 0);
@@ -264,7 +256,7 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
             for (int kt = 0; kt < KT; ++kt) {
 #pragma unroll
                 for (int kk = 0; kk < D / 16; ++kk) {
-                    const f16x8 kf = *(const __attribute__((address_space(3))) f16x8 *)(kbase[kk] + kt * 32 * K_ROW);
+                    const f16x8 kf = *(lds_cptr<f16x8>)(kbase[kk] + kt * 32 * K_ROW);
                     // (the first k-step starts from the constant 0: no zeroing moves)
                     s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], kk == 0 ? (f32x16)0.f : s[kt], 0, 0, 0);
                 }
@@ -292,7 +284,7 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
             // the scale is positive: max(s) * sc is the maximum of the scaled scores, bit for bit
             const float m_new = fmaxf(m_run, mx * sc);      // finite: every step has >= 1 real key
             const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);        // 0 on the first chunk
-            // numerators (softmax_p8, kernels.h; the same function in qkv_attention2.hip: equal bits across the kernels)
+            // numerators (softmax_p8, device.h; the same function in qkv_attention2.hip: equal bits across the kernels)
             float psum = 0.f;
             if constexpr (!MULTI) {
                 // the short-sentence form is ONE chunk: all numerators first (the scores' 64 registers die into 32 of packed P), then
@@ -316,8 +308,8 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
                     for (int st = 0; st < 2; ++st)
 #pragma unroll
                         for (int dv = 0; dv < D / 32; ++dv) {
-                            const lds_halfs vr = vbase[dv] + kt * 32 + 16 * st;
-                            const f16x4 v0 = *(const __attribute__((address_space(3))) f16x4 *)vr, v1 = *(const __attribute__((address_space(3))) f16x4 *)(vr + 8);
+                            const lds_cptr<half_t> vr = vbase[dv] + kt * 32 + 16 * st;
+                            const f16x4 v0 = *(lds_cptr<f16x4>)vr, v1 = *(lds_cptr<f16x4>)(vr + 8);
                             f16x8 vf;
 #pragma unroll
                             for (int e = 0; e < 4; ++e) { vf[e] = v0[e]; vf[4 + e] = v1[e]; }
@@ -348,8 +340,8 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
                     const f16x8 pf = pfr[kt][st];
 #pragma unroll
                     for (int dv = 0; dv < D / 32; ++dv) {
-                        const lds_halfs vr = vbase[dv] + kt * 32 + 16 * st;
-                        const f16x4 v0 = *(const __attribute__((address_space(3))) f16x4 *)vr, v1 = *(const __attribute__((address_space(3))) f16x4 *)(vr + 8);
+                        const lds_cptr<half_t> vr = vbase[dv] + kt * 32 + 16 * st;
+                        const f16x4 v0 = *(lds_cptr<f16x4>)vr, v1 = *(lds_cptr<f16x4>)(vr + 8);
                         f16x8 vf;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) { vf[e] = v0[e]; vf[4 + e] = v1[e]; }

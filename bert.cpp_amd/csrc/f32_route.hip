@@ -12,13 +12,11 @@
 //
 // Replaces, for f32 files: bert.cpp:796-814 (embedding + LayerNorm), :822-839 / :859-865 / :878-891 (mat-muls + bias, GELU,
 // residual), :843-856 (attention), :868-874 / :894-900 (LayerNorm), :904-913 (pooling).
-#include "kernels.h"
+#include "device.h"
 
 #include <algorithm>
 
 namespace bert_hip {
-
-typedef float f32x16r __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float f32_wave_sum(float v) {
 #pragma unroll
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(256) void f32_gemm_kernel(const float *__restrict__
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hi = lane >> 5;
     const int m0 = blockIdx.y * F32_BM, n0 = blockIdx.x * F32_BN;
     const int tb = wave & 1, fb = wave >> 1;
-    f32x16r acc;
+    f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     // staging: thread -> (row = tid / 4, 4 consecutive k = 4 (tid % 4)) of both tiles

@@ -18,20 +18,11 @@
 //     32 weights, tile-contiguous so a tile is one coalesced 4 KiB read); each thread dequantises
 //     one block per reduction tile in registers (v_perm_b32 builds 1024+q half pairs, packed f16
 //     math applies (q-8)*d or q*d+m) and writes four swizzled 16-B chunks into the LDS tile.
-#include "kernels.h"
+#include "device.h"
 
 #include <cstdlib>
 
 namespace bert_hip {
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define AS_GLOBAL(p) ((const __attribute__((address_space(1))) void *)(p))
-#define AS_LDS(p) ((__attribute__((address_space(3))) void *)(p))
 
 struct GemmArgs {
     const half_t *A;        // [M_pad][K]
@@ -46,8 +37,6 @@ struct GemmArgs {
 
 constexpr int TILE_BYTES = 128 * 128;        // 128 rows x 64 halfs
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;  // activation tile + weight tile
-
-__device__ __forceinline__ int lds_off(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 // One wave instruction moves 8 rows x 128 B; a wave moves 32 rows, the workgroup the 128-row tile.
 __device__ __forceinline__ void dma_tile(const half_t *src, int ld, char *tile, int wave, int lane) {
@@ -78,51 +67,10 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-// 4 bytes each holding a nibble value 0..15  ->  two f16x2 = (1024+n0, 1024+n1), (1024+n2, 1024+n3)
-__device__ __forceinline__ void nib4_to_half(unsigned n4, f16x2 &p01, f16x2 &p23) {
-    const unsigned a = __builtin_amdgcn_perm(0x64646464u, n4, 0x04010400u);
-    const unsigned b = __builtin_amdgcn_perm(0x64646464u, n4, 0x04030402u);
-    p01 = __builtin_bit_cast(f16x2, a);
-    p23 = __builtin_bit_cast(f16x2, b);
-}
-
+// q4: this thread's block (row, half kb of the reduction tile) expanded into four swizzled 16-byte chunks of the weight tile
 template <int WT>
-__device__ __forceinline__ void dequant_block_to_lds(const uint4 &q, unsigned scbits, char *tile, int row, int kb) {
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-    f16x2 d2, m2;
-    if (WT == GW_Q4_0) {
-        const _Float16 d = __builtin_bit_cast(_Float16, (unsigned short)(scbits & 0xffffu));
-        d2 = (f16x2){d, d};
-        m2 = (f16x2){(_Float16)0, (_Float16)0};
-    } else {
-        const f16x2 dm = __builtin_bit_cast(f16x2, scbits);
-        d2 = (f16x2){dm[0], dm[0]};
-        m2 = (f16x2){dm[1], dm[1]};
-    }
-    const f16x2 off = WT == GW_Q4_0 ? (f16x2){(_Float16)1032.0f, (_Float16)1032.0f}
-                                     : (f16x2){(_Float16)1024.0f, (_Float16)1024.0f};
-    // chunk j holds block elements 8j..8j+7: j=0,1 low nibbles of bytes 0-7 / 8-15; j=2,3 high nibbles
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        f16x2 h[4];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const unsigned word = w[(j & 1) * 2 + u];
-            const unsigned n4 = (j < 2 ? word : (word >> 4)) & 0x0f0f0f0fu;
-            nib4_to_half(n4, h[2 * u], h[2 * u + 1]);
-        }
-        uint4 out;
-        unsigned o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            f16x2 v = h[e] - off;                       // exact small integer in f16
-            if (WT == GW_Q4_0) v = v * d2;              // (q - 8) * d
-            else v = v * d2 + m2;                       // q * d + m
-            o[e] = __builtin_bit_cast(unsigned, v);
-        }
-        out.x = o[0]; out.y = o[1]; out.z = o[2]; out.w = o[3];
-        *(uint4 *)(tile + lds_off(row, kb * 4 + j)) = out;
-    }
+__device__ __forceinline__ void dequant_block_to_lds(const RawBlock &blk, char *tile, int row, int kb) {
+    q4_expand_block<WT, false>(blk, [&](int c) __attribute__((always_inline)) { return tile + off64(row, kb * 4 + c); });
 }
 
 template <int WT, int EPI>
@@ -149,17 +97,15 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(GemmArgs p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    uint4 qn = {0, 0, 0, 0};
-    unsigned sn = 0;
+    RawBlock qn = {};
 
     // ---- prologue: tile 0 -> stage 0
     dma_tile(Abase, K, smem, wave, lane);
     if (WT == GW_F16) {
         dma_tile(Wbase, K, smem + TILE_BYTES, wave, lane);
     } else {
-        qn = p.qs[qbase + tid];
-        sn = WT == GW_Q4_0 ? (unsigned)((const unsigned short *)p.sc)[qbase + tid] : ((const unsigned *)p.sc)[qbase + tid];
-        dequant_block_to_lds<WT>(qn, sn, smem + TILE_BYTES, tid >> 1, tid & 1);
+        qn = q4_load_block<WT>(p.qs, p.sc, qbase + tid);
+        dequant_block_to_lds<WT>(qn, smem + TILE_BYTES, tid >> 1, tid & 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -173,9 +119,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(GemmArgs p) {
             if (WT == GW_F16) {
                 dma_tile(Wbase + (kt + 1) * GEMM_BK, K, nxt + TILE_BYTES, wave, lane);
             } else {
-                const size_t bi = qbase + (size_t)(kt + 1) * 256 + tid;
-                qn = p.qs[bi];
-                sn = WT == GW_Q4_0 ? (unsigned)((const unsigned short *)p.sc)[bi] : ((const unsigned *)p.sc)[bi];
+                qn = q4_load_block<WT>(p.qs, p.sc, qbase + (size_t)(kt + 1) * 256 + tid);
             }
         }
         const char *At = cur, *Wt = cur + TILE_BYTES;
@@ -185,8 +129,8 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(GemmArgs p) {
             f16x8 a[2], b[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                a[i] = *(const f16x8 *)(Wt + lds_off(wf * 64 + i * 32 + l31, c));
-                b[i] = *(const f16x8 *)(At + lds_off(wt * 64 + i * 32 + l31, c));
+                a[i] = *(const f16x8 *)(Wt + off64(wf * 64 + i * 32 + l31, c));
+                b[i] = *(const f16x8 *)(At + off64(wt * 64 + i * 32 + l31, c));
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -194,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mfma_kernel(GemmArgs p) {
                 for (int j = 0; j < 2; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i], b[j], acc[i][j], 0, 0, 0);
         }
-        if (WT != GW_F16 && more) dequant_block_to_lds<WT>(qn, sn, nxt + TILE_BYTES, tid >> 1, tid & 1);
+        if (WT != GW_F16 && more) dequant_block_to_lds<WT>(qn, nxt + TILE_BYTES, tid >> 1, tid & 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }

@@ -26,21 +26,13 @@
 // Measured (bert-base, 512 x 512 tokens, per reduction tile 1.45 us = 88 % of the matrix rate the board sustains at its
 // power limit; hipBLASLt's 256x256x64 kernel on the same shapes: QKV 836 us, this kernel 960): what is left is the epilogue
 // — 128 store instructions per tile at 31-52 cycles each per CU (tools/ubench/store_issue.hip) with no MFMA beside them.
-#include "tile_stream.h"
+#include "device.h"
 
 #include <type_traits>
 
 namespace bert_hip {
 
 namespace {
-
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define G2_GLOBAL(p) ((const __attribute__((address_space(1))) void *)(p))
-#define G2_LDS(p) ((__attribute__((address_space(3))) void *)(p))
 
 constexpr int G2_BM = 256, G2_BN = 256, G2_BK = 64;
 constexpr int G2_TILE = 256 * 128;               // 256 rows x 64 halfs
@@ -99,14 +91,7 @@ constexpr int g2_piece_at(int step, int m) {
     return -1;
 }
 
-// ---- hand-issued fragment reads (the compiler does not track them: every wait names the registers it releases)
-template <int OFF>
-__device__ __forceinline__ f16x8 g2_read_b128(unsigned addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds offset field is 16 bits");
-    f16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
+// ---- hand-issued fragment reads (lds_read_b128<false, ..>; the compiler does not track them: every wait names the registers it releases)
 struct G2Frag {
     f16x8 a[4], b[2];                                  // weight rows (4 x 32 features), activation rows (2 x 32 tokens) of one k-step
 };
@@ -182,7 +167,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(Gemm256Args p) {
     auto dma_piece = [&](const half_t *src, char *stage_base, auto i_tag) __attribute__((always_inline)) {
         constexpr int i = decltype(i_tag)::value;       // 0..3: activation pieces, 4..7: weight pieces
         if constexpr (Q4 && i >= 4) return;             // (q4: the weight half is expanded from blocks, below)
-        else __builtin_amdgcn_global_load_lds(G2_GLOBAL(src + doff[i & 3]), G2_LDS(stage_base + (i >> 2) * G2_TILE + (wave * 4 + (i & 3)) * 1024), 16, 0, 0);
+        else __builtin_amdgcn_global_load_lds(AS_GLOBAL(src + doff[i & 3]), AS_LDS(stage_base + (i >> 2) * G2_TILE + (wave * 4 + (i & 3)) * 1024), 16, 0, 0);
     };
 
     // ---- fragment addresses of the four k-steps of a reduction tile (stage 0; the other stage is address ^ 64 KiB)
@@ -198,9 +183,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(Gemm256Args p) {
     }
     auto read_frag = [&](G2Frag &f, auto kk_tag) __attribute__((always_inline)) {
         constexpr int kk = decltype(kk_tag)::value;
-        f.a[0] = g2_read_b128<0>(aW[kk]); f.a[1] = g2_read_b128<4096>(aW[kk]);
-        f.a[2] = g2_read_b128<8192>(aW[kk]); f.a[3] = g2_read_b128<12288>(aW[kk]);
-        f.b[0] = g2_read_b128<0>(aA[kk]); f.b[1] = g2_read_b128<4096>(aA[kk]);
+        f.a[0] = lds_read_b128<false, 0>(aW[kk]); f.a[1] = lds_read_b128<false, 4096>(aW[kk]);
+        f.a[2] = lds_read_b128<false, 8192>(aW[kk]); f.a[3] = lds_read_b128<false, 12288>(aW[kk]);
+        f.b[0] = lds_read_b128<false, 0>(aA[kk]); f.b[1] = lds_read_b128<false, 4096>(aA[kk]);
     };
 
     // ---- q4: this thread's block of a weight tile.  A wave owns 32 rows x 2 blocks; its lanes are dealt so that the eight lanes
@@ -212,7 +197,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(Gemm256Args p) {
     // The request is hand-issued (two asm global loads, scalar base + lane offset): a compiler-visible load is retired by the
     // compiler with a vmcnt that also covers the activation pieces issued behind it — a wait for LDS-DMA in front of the first
     // chunk.  Every path from a request to its expansion crosses a reduction-tile barrier (vmcnt(0)), which names these registers.
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 raw_q = {};
     unsigned raw_sc = 0;
     unsigned q_voff = (unsigned)q_lane_idx;
@@ -406,7 +390,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(Gemm256Args p) {
         // accumulator blocks 2 ip, 2 ip + 1 of token block j, converted in place into the first one's registers): left to the
         // allocator the packed halves stay scattered over all eight accumulator tuples, one register in two, and the 64
         // registers that are free hold no 4-register run for the next tile's bias vectors — sixteen of them were spilled.
-        typedef unsigned u32x16 __attribute__((ext_vector_type(16)));
         u32x16 o16[4];
         [[maybe_unused]] float st1[2] = {0.f, 0.f}, st2[2] = {0.f, 0.f};      // LN_STATS: this lane's (sum, sum of squares) per token block
 #pragma unroll
@@ -422,8 +405,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(Gemm256Args p) {
                         f16x4 h;
                         if (EPI == EPI_BIAS_GELU) {
                             // packed f16, as layer_tail.hip evaluates it (the reference reads the GELU from an f16 table)
-                            const f16x2_t g0 = (LN & LN_IN) ? gelu_pk16(a[4 * g] * rs, a[4 * g + 1] * rs) : gelu_pk16(a[4 * g], a[4 * g + 1]);
-                            const f16x2_t g1 = (LN & LN_IN) ? gelu_pk16(a[4 * g + 2] * rs, a[4 * g + 3] * rs) : gelu_pk16(a[4 * g + 2], a[4 * g + 3]);
+                            const f16x2 g0 = (LN & LN_IN) ? gelu_pk16(a[4 * g] * rs, a[4 * g + 1] * rs) : gelu_pk16(a[4 * g], a[4 * g + 1]);
+                            const f16x2 g1 = (LN & LN_IN) ? gelu_pk16(a[4 * g + 2] * rs, a[4 * g + 3] * rs) : gelu_pk16(a[4 * g + 2], a[4 * g + 3]);
                             h[0] = g0[0]; h[1] = g0[1]; h[2] = g1[0]; h[3] = g1[1];
                             if (g % G2_GELU_RUNS == G2_GELU_RUNS - 1) __builtin_amdgcn_sched_barrier(0);   // the GELU temporaries of more runs at a time would spill
                         } else {

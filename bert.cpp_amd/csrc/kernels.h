@@ -1,4 +1,5 @@
-// kernels.h — launch interface of the HIP kernels of the bert_eval hot path (gfx950 only).
+// kernels.h — launch interface of the HIP kernels of the bert_eval hot path (gfx950 only): the weight layouts, the launch_*
+// functions and the launch bookkeeping host code needs.  The device-side building blocks the kernels share are in device.h.
 //
 // Reference ops each kernel replaces are listed in SURVEY.md §2.3; call sites bert.cpp:796-913.
 // Activations are f16 row-major [T_pad][features]; T_pad is T rounded up to GEMM_BM tokens.
@@ -13,166 +14,6 @@
 namespace bert_hip {
 
 typedef _Float16 half_t;
-
-// An f32 value the compiler must materialise: (_Float16)rounded_f32(a * b) is an f32 multiply followed by a conversion,
-// never the fused v_fma_mixlo_f16 (ONE rounding, to f16).  Which of the two forms the compiler picks for (_Float16)(a * b)
-// depends on the surrounding code, and kernels that must agree bit for bit (attention.hip, qkv_attention*.hip) would
-// differ in one result of ~20 000.
-__device__ __forceinline__ float rounded_f32(float v) {
-    asm("" : "+v"(v));
-    return v;
-}
-
-// ---- lane-crossing reductions without the LDS.  __shfl_xor is a ds_bpermute_b32: an LDS round trip (and an lgkmcnt wait) per step.
-// The same PAIRS meet here — so sums and maxima keep their bits — through v_permlane32_swap (lane ^ 32: the two halves of the wave
-// trade places), ds_swizzle (lane ^ 16 / 8 / 4: no address register, no LDS access) and DPP quad_perm on the add itself (lane ^ 2 / 1).
-// tools/ubench/wave_sum.hip checks the six-step sum against the __shfl_xor butterfly bit for bit.
-// xor32_pair: a = this lane's value, b = lane ^ 32's in the low half of the wave and the other way round in the high half — fine for
-// commutative uses (a + b, max(a, b)).  By hand: this compiler's __builtin_amdgcn_permlane32_swap returns its first result twice; the
-// instruction needs two registers (with one as both operands it copies the low half up and loses the high one); the wait states
-// between a VALU write and a lane-crossing read are ours inside an asm.
-__device__ __forceinline__ void xor32_pair(float &a, float &b) {
-    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ float xor32_sum(float v) { float a = v, b = v; xor32_pair(a, b); return a + b; }
-__device__ __forceinline__ float xor32_max(float v) { float a = v, b = v; xor32_pair(a, b); return __builtin_fmaxf(a, b); }
-// v + (lane ^ 32) + ... + (lane ^ 1), the pairs and the order of the __shfl_xor butterfly from 32 down to 1
-__device__ __forceinline__ float wave_sum_f32(float v) {
-    v = xor32_sum(v);
-    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (16 << 10) | 0x1F));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (8 << 10) | 0x1F));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, v), (4 << 10) | 0x1F));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    return v;
-}
-
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-
-// Softmax numerators of EIGHT scores of one query (registers 8 st .. 8 st + 7 of an S^T tile = the B fragment of one P·V MFMA
-// step) — ONE function for all attention bodies (attention.hip, qkv_attention2.hip and with it model_kernel.hip): equal bits
-// across the routes.  Two forms:
-//   BERT_HIP_EXP16 = 0 (default): p = exp2(fma(s, sc, -m)) in f32 (v_fma_f32, v_exp_f32), the row sum an f32 add, P rounded to
-//     f16 for the V mat-mul (v_cvt_pk_f16_f32) — rounds 1-4's arithmetic.
-//   BERT_HIP_EXP16 = 1: the reference's own precision — ggml's soft_max rounds (s - max) to fp16 and reads an fp16 table of exp
-//     (reference bert.cpp:845 -> ggml_soft_max; oracle/bert_oracle.cpp:544): the argument one fma rounded ONCE to f16
-//     (v_fma_mixlo / mixhi_f16 write the two halves of a register), v_exp_f16 on each half (the high one through SDWA with the
-//     low half preserved), the pair IS the MFMA operand, the row sum f32 through v_dot2c_f32_f16 with (1, 1).  21 instructions
-//     per 8 scores against 28 — and SLOWER on this chip (round 5, tools/ubench/valu_cost.hip, profiles/r5_valu_cost.txt):
-//     v_fma_mix* issue at the transcendental rate (7.9 cycles per instance and wave beside MFMAs, 2 waves per SIMD, against 2.5
-//     for v_fma_f32) and v_dot2c shares the matrix pipe (8.6 against 1.9 for v_add_f32): 40 cycles per score pair against 27.
-//     Measured end to end: headline 327.0 k against 330.5 k sentences/s on one box, attention at 512 tokens 9.28 against 8.68 ms
-//     per 12 launches.  Parity-green (395 tests) and kept as a build option; not the default.
-// The trailing s_nop of the fp16 form: gfx940+ needs one wait state between an instruction that writes half a register (SDWA
-// dst_sel) and a reader of that register, and the compiler's hazard pass does not look into an asm block.
-#ifndef BERT_HIP_EXP16
-#define BERT_HIP_EXP16 0
-#endif
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x8_t __attribute__((ext_vector_type(8)));
-// the three steps of softmax_p8 on four score PAIRS, separately callable so that a kernel can put MFMAs between them
-// (attention.hip's software-pipelined chunk loop): arguments (8 VALU), exponentials (8 VALU + the wait state), row sum (4 dot2);
-// softmax_pack: the B fragment of the P·V MFMA step (the exponentials themselves in the fp16 form).
-// -DBERT_HIP_EXP16=0 (tuning builds): the f32 form of rounds 1-4 — fma, v_exp_f32, add, v_cvt_pk_f16_f32.
-#if BERT_HIP_EXP16
-typedef u32x4_t sm_arg_t;
-typedef u32x4_t sm_exp_t;
-__device__ __forceinline__ sm_arg_t softmax_args4(float s0, float s1, float s2, float s3, float s4, float s5, float s6, float s7, float sc, float m) {
-    uint32_t a0, a1, a2, a3;            // (scalar outputs: asm outputs that are elements of a vector come out wrong)
-    asm("v_fma_mixlo_f16 %0, %4, %12, -%13\n\t"
-        "v_fma_mixlo_f16 %1, %6, %12, -%13\n\t"
-        "v_fma_mixlo_f16 %2, %8, %12, -%13\n\t"
-        "v_fma_mixlo_f16 %3, %10, %12, -%13\n\t"
-        "v_fma_mixhi_f16 %0, %5, %12, -%13\n\t"
-        "v_fma_mixhi_f16 %1, %7, %12, -%13\n\t"
-        "v_fma_mixhi_f16 %2, %9, %12, -%13\n\t"
-        "v_fma_mixhi_f16 %3, %11, %12, -%13"
-        : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3)
-        : "v"(s0), "v"(s1), "v"(s2), "v"(s3), "v"(s4), "v"(s5), "v"(s6), "v"(s7), "s"(sc), "v"(m));
-    return u32x4_t{a0, a1, a2, a3};
-}
-__device__ __forceinline__ sm_exp_t softmax_exp4(sm_arg_t a) {
-    uint32_t p0, p1, p2, p3;
-    asm("v_exp_f16_e32 %0, %4\n\t"
-        "v_exp_f16_e32 %1, %5\n\t"
-        "v_exp_f16_e32 %2, %6\n\t"
-        "v_exp_f16_e32 %3, %7\n\t"
-        "v_exp_f16_sdwa %0, %4 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
-        "v_exp_f16_sdwa %1, %5 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
-        "v_exp_f16_sdwa %2, %6 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
-        "v_exp_f16_sdwa %3, %7 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1\n\t"
-        "s_nop 0"
-        : "=&v"(p0), "=&v"(p1), "=&v"(p2), "=&v"(p3)
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]));
-    return u32x4_t{p0, p1, p2, p3};
-}
-__device__ __forceinline__ void softmax_sum4(sm_exp_t p, float &psum) {
-    const f16x2_t one = {(_Float16)1.0f, (_Float16)1.0f};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const uint32_t pe = p[e];       // (a scalar copy: __builtin_bit_cast applied to a vector ELEMENT reads element 0 whatever e is)
-        psum = __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2_t, pe), one, psum, false);
-    }
-}
-__device__ __forceinline__ f16x8_t softmax_pack(sm_exp_t p) { return __builtin_bit_cast(f16x8_t, p); }
-#else
-typedef f32x8_t sm_arg_t;
-typedef f32x8_t sm_exp_t;
-__device__ __forceinline__ sm_arg_t softmax_args4(float s0, float s1, float s2, float s3, float s4, float s5, float s6, float s7, float sc, float m) {
-    const float s[8] = {s0, s1, s2, s3, s4, s5, s6, s7};
-    f32x8_t a;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) a[e] = __builtin_fmaf(s[e], sc, -m);
-    return a;
-}
-__device__ __forceinline__ sm_exp_t softmax_exp4(sm_arg_t a) {
-    f32x8_t p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) p[e] = __builtin_amdgcn_exp2f(a[e]);
-    return p;
-}
-__device__ __forceinline__ void softmax_sum4(sm_exp_t p, float &psum) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) psum += p[e];
-}
-__device__ __forceinline__ f16x8_t softmax_pack(sm_exp_t p) {
-    f16x8_t pf;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) pf[e] = (_Float16)p[e];
-    return pf;
-}
-#endif
-__device__ __forceinline__ f16x8_t softmax_p8(float s0, float s1, float s2, float s3, float s4, float s5, float s6, float s7, float sc,
-                                              float m, float &psum) {
-    const sm_exp_t p = softmax_exp4(softmax_args4(s0, s1, s2, s3, s4, s5, s6, s7, sc, m));
-    softmax_sum4(p, psum);
-    return softmax_pack(p);
-}
-// tanh-form GELU of two values, packed f16: x / (1 + 2^(x (c1 + c2 x^2)))
-__device__ __forceinline__ f16x2_t gelu_pk16h(f16x2_t xh) {
-    const float c1 = -2.0f * 0.79788456080286535588f * 1.44269504088896340736f;
-    const f16x2_t C1 = {(_Float16)c1, (_Float16)c1}, C2 = {(_Float16)(c1 * 0.044715f), (_Float16)(c1 * 0.044715f)};
-    const f16x2_t one = {(_Float16)1.0f, (_Float16)1.0f};
-    const f16x2_t t = (xh * xh * C2 + C1) * xh;
-    const f16x2_t e = {(_Float16)__builtin_exp2f16(t[0]), (_Float16)__builtin_exp2f16(t[1])};
-    const f16x2_t d = e + one;
-    const f16x2_t r = {(_Float16)__builtin_amdgcn_rcph(d[0]), (_Float16)__builtin_amdgcn_rcph(d[1])};
-    return xh * r;
-}
-__device__ __forceinline__ f16x2_t gelu_pk16(float a0, float a1) { return gelu_pk16h(f16x2_t{(_Float16)a0, (_Float16)a1}); }
-
-// LayerNorm statistics (sum, sum of squares over H values) -> (1 / std, -mean / std), eps 1e-5 (ggml's).  Every product and
-// sum is spelled out: with -ffp-contract=fast the compiler picks which a * b + c it fuses by the surrounding code, and kernels
-// that must agree bit for bit (layer_tail.hip and its feature-split mirror skinny.hip) share this function instead.
-// 1 / sqrt = v_rsq_f32 + one Newton step (1 ulp).
-__device__ __forceinline__ void layernorm_scale(float s1, float s2, float inv_h, float &rstd, float &nmr) {
-    const float mean = s1 * inv_h, ex2 = s2 * inv_h;
-    const float t = fmaxf(__builtin_fmaf(-mean, mean, ex2), 0.f) + 1e-5f;
-    const float r = __builtin_amdgcn_rsqf(t);
-    rstd = r * __builtin_fmaf(-0.5f * t, r * r, 1.5f);
-    nmr = -mean * rstd;
-}
 
 constexpr int GEMM_BM = 128;   // token tile
 constexpr int GEMM_BN = 128;   // feature tile

@@ -32,7 +32,7 @@
 // LDS: two rings of 3 x 16 KiB (UP tiles / DOWN tiles; the out-projection uses both), 4 x 2 x 4 KiB GELU'ed chunks,
 // parameters.  Registers (H = 384): U 96 (y) + 64 (two sets of up-projection accumulators) + 48 (fragments) + 16 (chunk
 // being GELU'ed); D 192 + 32 (fragments) + 16 (chunk).
-#include "tile_stream.h"
+#include "device.h"
 
 namespace bert_hip {
 
@@ -60,8 +60,6 @@ constexpr int LT_TILE = 16384;
 #ifndef LT_DPRIO
 #define LT_DPRIO 0
 #endif
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Tuning aid (-DBERT_HIP_TIMELINE, `make timeline`): shader-clock stamps of pair 0 of every workgroup: [0, 128) U behind
 // the barrier of interval i, [128, 256) U in front of it, [256, 384) D in front of it, [384, 512) phases outside the loops
@@ -101,35 +99,16 @@ template <int N>
 __device__ __forceinline__ void wait_lgkm() {
     asm volatile("s_waitcnt lgkmcnt(%0)" : : "n"(N) : "memory");
 }
-// a hand-read register handed to its users (behind the wait that retired the read)
-template <class V>
-__device__ __forceinline__ void landed(V &v) { asm volatile("" : "+v"(v)); }
-// closing barrier of a tile interval: this wave's DMA pieces of the NEXT tile have landed (all but the newest VM), its LDS
-// reads and writes are complete
-template <int VM>
-__device__ __forceinline__ void close_interval() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" : : "n"(VM) : "memory");
-}
+// closing barrier of a tile interval (dma_barrier<VM>, naming the four fragments whose MFMAs follow): this wave's DMA pieces
+// of the NEXT tile have landed (all but the newest VM), its LDS reads and writes are complete
 template <int VM>
 __device__ __forceinline__ void close_interval(f16x8 (&f)[4]) {
     asm volatile("s_waitcnt vmcnt(%4) lgkmcnt(0)\n\ts_barrier" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]) : "n"(VM) : "memory");
 }
 template <int OFF>
-__device__ __forceinline__ f32x2 lds_read_b64_h(unsigned addr) {
-    f32x2 v;
-    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-template <int OFF>
-__device__ __forceinline__ f32x4 lds_read_f32x4_h(unsigned addr) {
-    f32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-template <int OFF>
 __device__ __forceinline__ f16x8 frag_read(unsigned addr) {
     if (LT_ABLATE & 4) { f16x8 z = (f16x8)(_Float16)0.f; asm volatile("" : "+v"(z) : "v"(addr)); return z; }
-    return lds_read_b128_u<OFF>(addr);
+    return lds_read_b128<true, OFF>(addr);
 }
 
 // LDS-DMA by hand (global_load_lds_dwordx4, 1 KiB per wave-instruction): scalar base + 32-bit lane offset, so no 64-bit
@@ -385,7 +364,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
                 else if (role == 1) dma_up(0, p2 - P, up_offset(), ldsU + s2 * LT_TILE);
             }
             pre_close();
-            if (p2 < P || role == 1) close_interval<Q4 ? 63 : 4>(); else close_interval<VMQ>();
+            if (p2 < P || role == 1) dma_barrier<Q4 ? 63 : 4>(); else dma_barrier<VMQ>();
             next_slot();
             return;
         }
@@ -412,7 +391,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
         mm(Fb, 8 * q + 6);
         __builtin_amdgcn_sched_barrier(0);
         pre_close();
-        if (p2 < P || role == 1) close_interval<Q4 ? 63 : 4>(); else close_interval<VMQ>();
+        if (p2 < P || role == 1) dma_barrier<Q4 ? 63 : 4>(); else dma_barrier<VMQ>();
         next_slot();
     });
 
@@ -470,7 +449,6 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
     // ================================ rows -> HBM (both waves of the pair, alternate 1 KiB pieces) ================================
     // (called at the end of EACH role's branch, which then returns: with a common tail behind the branches the register
     // allocator carries U's fragments "through" D's branch — stores in front of D's loop, dead reloads behind it)
-    typedef unsigned store_u32x4 __attribute__((ext_vector_type(4)));
     auto store_rows = [&]() __attribute__((always_inline)) {
         LT_STAMP(tlU, 394);
         const char *S = smem + t * (64 * H);
@@ -493,7 +471,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
             f16x8 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { o[e] = lo[e]; o[4 + e] = hi4[e]; }
-            if constexpr (RAGGED) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(store_u32x4, o), out_rows, (tok * H + c8 * 8) * 2, 0, 0);
+            if constexpr (RAGGED) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), out_rows, (tok * H + c8 * 8) * 2, 0, 0);
             else *(f16x8 *)(ow + (size_t)tok * H + c8 * 8) = o;
         }
 #ifdef BERT_HIP_TIMELINE
@@ -550,7 +528,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
             if constexpr (LT_ABLATE & 2) {
                 o[2 * p] = (_Float16)x0; o[2 * p + 1] = (_Float16)x1;
             } else {
-                const f16x2_t gv = gelu_pk16(x0, x1);
+                const f16x2 gv = gelu_pk16(x0, x1);
                 o[2 * p] = gv[0]; o[2 * p + 1] = gv[1];
             }
             accU[PG][fb][s8 + 2 * p] = p < 2 ? b0[2 * p] : b1[2 * p - 4];
@@ -589,8 +567,8 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
                 const unsigned aBc = aB + (unsigned)(c + 1) * 256u;
                 static_for<nf>([&](auto k_tag) __attribute__((always_inline)) {
                     constexpr int k = decltype(k_tag)::value, jf = f0 + k, off = 4 * (32 * (jf >> 1) + 16 * (jf & 1));
-                    Bv[k][0] = lds_read_f32x4_h<off>(aBc);
-                    Bv[k][1] = lds_read_f32x4_h<off + 32>(aBc);
+                    Bv[k][0] = lds_read_b128<true, off, f32x4>(aBc);
+                    Bv[k][1] = lds_read_b128<true, off + 32, f32x4>(aBc);
                 });
             }
             if constexpr (MMA) { rd(0, Fa); rd(1, Fb); }
@@ -659,7 +637,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
             }
             static_assert(MAXF <= 2, "two GELU batches per interval at most");
             pre_close();
-            if constexpr (MMA) close_interval<VMQ>(Fc); else close_interval<VMQ>();
+            if constexpr (MMA) close_interval<VMQ>(Fc); else dma_barrier<VMQ>();
             next_slot();
         };
         using TT = std::true_type; using FF = std::false_type;
@@ -693,7 +671,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
 #pragma unroll
                     for (int m = 0; m < NYH; ++m) *(f16x8 *)(xu + m * 1024) = Y[8 * (m >> 2) + (m & 3)];
                 }
-                pre_close(); close_interval<VMQ>(); next_slot();
+                pre_close(); dma_barrier<VMQ>(); next_slot();
             }
         });
         static_assert(LAGT > NG, "U needs an idle interval to hand its half of y over");
@@ -766,7 +744,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
             request(TT{}, std::integral_constant<bool, dn>{}, k + 2, k - (LAGT - 2));
             // at the close the pieces of the interval before have landed: all but the newest 4 (+ 4)
             pre_close();
-            close_interval<Q4 ? 63 : (dn ? 8 : 4)>();
+            dma_barrier<Q4 ? 63 : (dn ? 8 : 4)>();
             next_slot();
         });
         // DOWN(c), tile d: acc2[4 d + ob] += W2(row block ob, k-step kk) x g(c)[kk].  UPQ: how many of the chunk's intervals
@@ -786,7 +764,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
                     unsigned a0 = bD ^ (unsigned)(kk << 5);
                     asm volatile("" : "+v"(a0));
                     F[0] = frag_read<0>(a0); F[1] = frag_read<4096>(a0); F[2] = frag_read<8192>(a0); F[3] = frag_read<12288>(a0);
-                    gv = lds_read_b128_u<kk * 1024>(bG);
+                    gv = lds_read_b128<true, kk * 1024>(bG);
                 };
                 auto wait_group = [&](auto n_tag, f16x8 (&F)[4], f16x8 &gv) __attribute__((always_inline)) {
                     asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(F[0]), "+v"(F[1]), "+v"(F[2]), "+v"(F[3]), "+v"(gv) : "n"(decltype(n_tag)::value) : "memory");
@@ -826,7 +804,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
                 wait_group(N0{}, Fb, gb);
                 mm(Fb, gb);
                 pre_close();
-                close_interval<Q4 ? 63 : (up ? 4 : 0) + (dn ? 4 : 0)>();
+                dma_barrier<Q4 ? 63 : (up ? 4 : 0) + (dn ? 4 : 0)>();
                 next_slot();
             });
         };

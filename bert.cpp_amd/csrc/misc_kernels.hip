@@ -1,16 +1,12 @@
 // misc_kernels.hip — the HBM-bound pieces of the forward pass (gfx950): embedding gather-sum +
 // LayerNorm, stand-alone LayerNorm, mean-pool + L2 normalise.  One 64-lane wavefront per token row
 // with __shfl_xor reductions; no LDS needed.
-#include "kernels.h"
-
-#include <algorithm>
+#include "device.h"
 #include "pool_normalize.h"
 
+#include <algorithm>
+
 namespace bert_hip {
-
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float wave_sum(float v) { return wave_sum_f32(v); }      // (kernels.h: the __shfl_xor butterfly's pairs without the LDS)
 
 // Element e of row r of an embedding table stored in the model-file layout,
 // dequantised to f32 exactly as ggml_get_rows does: f16 -> f32, (q-8)*d, q*d+m.
@@ -80,7 +76,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const void *word, const v
             sum += v[j][0] + v[j][1];
         }
     }
-    const float mean = wave_sum(sum) / H;
+    const float mean = wave_sum_f32(sum) / H;
     float sq = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -90,7 +86,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const void *word, const v
             sq += v[j][0] * v[j][0] + v[j][1] * v[j][1];
         }
     }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) / H + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum_f32(sq) / H + 1e-5f);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int e = 2 * lane + 128 * j;
@@ -106,7 +102,6 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const void *word, const v
 // Same operation for f32 / f16 tables with H % 8 == 0 and q4 tables, laid out for bandwidth: the grid is (4-token group, sentence), so
 // a wave knows its sentence and position without searching cu_seqlens; a lane owns 16-byte runs of the row (8
 // features: one 16-byte load per f16 table row, one 16-byte store), NC runs per lane (H <= 512 * NC).
-typedef _Float16 f16x8m __attribute__((ext_vector_type(8)));
 template <int TT>
 __device__ __forceinline__ void table_run8(const void *tab, int H, int r, int e0, float (&v)[8]) {
     if (TT == 0) {
@@ -114,7 +109,7 @@ __device__ __forceinline__ void table_run8(const void *tab, int H, int r, int e0
         const float4 b = *(const float4 *)((const float *)tab + (size_t)r * H + e0 + 4);
         v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
     } else if (TT == 1) {
-        const f16x8m h = *(const f16x8m *)((const half_t *)tab + (size_t)r * H + e0);
+        const f16x8 h = *(const f16x8 *)((const half_t *)tab + (size_t)r * H + e0);
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = (float)h[i];
     } else {
@@ -180,14 +175,14 @@ __global__ __launch_bounds__(256) void embed_ln_rows_kernel(const void *word, co
             for (int i = 0; i < 8; ++i) { v[j][i] = ps[i] + (ty[i] + w[i]); sum += v[j][i]; }
         }
     }
-    const float mean = wave_sum(sum) / H;
+    const float mean = wave_sum_f32(sum) / H;
     float sq = 0.f;
 #pragma unroll
     for (int j = 0; j < NC; ++j)
         if (8 * (lane + 64 * j) < H)
 #pragma unroll
             for (int i = 0; i < 8; ++i) { v[j][i] -= mean; sq += v[j][i] * v[j][i]; }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) / H + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum_f32(sq) / H + 1e-5f);
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
         const int e0 = 8 * (lane + 64 * j);
@@ -196,10 +191,10 @@ __global__ __launch_bounds__(256) void embed_ln_rows_kernel(const void *word, co
             const float4 b0 = *(const float4 *)(beta + e0), b1 = *(const float4 *)(beta + e0 + 4);
             const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
             const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-            f16x8m o;
+            f16x8 o;
 #pragma unroll
             for (int i = 0; i < 8; ++i) o[i] = (_Float16)(gg[i] * (v[j][i] * rstd) + bb[i]);
-            *(f16x8m *)(out + (size_t)t * H + e0) = o;
+            *(f16x8 *)(out + (size_t)t * H + e0) = o;
         }
     }
 }
@@ -250,7 +245,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(half_t *x, const float *
         } else { v[j][0] = 0.f; v[j][1] = 0.f; }
         sum += v[j][0] + v[j][1];
     }
-    const float mean = wave_sum(sum) / H;
+    const float mean = wave_sum_f32(sum) / H;
     float sq = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -260,7 +255,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(half_t *x, const float *
             sq += v[j][0] * v[j][0] + v[j][1] * v[j][1];
         }
     }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) / H + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum_f32(sq) / H + 1e-5f);
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         const int e = 2 * lane + 128 * j;
@@ -283,13 +278,13 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(half_t *x, const fl
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= T) return;
     half_t *row = x + (size_t)t * H;
-    f16x8m h[NC];
+    f16x8 h[NC];
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
         const int e0 = 8 * (lane + 64 * j);
 #pragma unroll
         for (int i = 0; i < 8; ++i) h[j][i] = (_Float16)0.f;
-        if (e0 < H) h[j] = *(const f16x8m *)(row + e0);
+        if (e0 < H) h[j] = *(const f16x8 *)(row + e0);
     }
     float v[NC][8];
     float sum = 0.f;
@@ -297,14 +292,14 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(half_t *x, const fl
     for (int j = 0; j < NC; ++j)
 #pragma unroll
         for (int i = 0; i < 8; ++i) { v[j][i] = (float)h[j][i]; sum += v[j][i]; }
-    const float mean = wave_sum(sum) / H;
+    const float mean = wave_sum_f32(sum) / H;
     float sq = 0.f;
 #pragma unroll
     for (int j = 0; j < NC; ++j)
         if (8 * (lane + 64 * j) < H)
 #pragma unroll
             for (int i = 0; i < 8; ++i) { v[j][i] -= mean; sq += v[j][i] * v[j][i]; }
-    const float rstd = 1.0f / sqrtf(wave_sum(sq) / H + 1e-5f);
+    const float rstd = 1.0f / sqrtf(wave_sum_f32(sq) / H + 1e-5f);
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
         const int e0 = 8 * (lane + 64 * j);
@@ -313,10 +308,10 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(half_t *x, const fl
             const float4 b0 = *(const float4 *)(beta + e0), b1 = *(const float4 *)(beta + e0 + 4);
             const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
             const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-            f16x8m o;
+            f16x8 o;
 #pragma unroll
             for (int i = 0; i < 8; ++i) o[i] = (_Float16)(gg[i] * (v[j][i] * rstd) + bb[i]);
-            *(f16x8m *)(row + e0) = o;
+            *(f16x8 *)(row + e0) = o;
         }
     }
 }

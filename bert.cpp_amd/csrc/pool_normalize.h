@@ -2,15 +2,9 @@
 // pool_normalize_kernel (misc_kernels.hip: a workgroup of 256 threads per sentence) and the epilogue of model_kernel.hip
 // (a workgroup pools its window's sentences itself: threads 0..255 of its 512 work, all of them meet at the barriers).
 #pragma once
-#include <hip/hip_runtime.h>
-#include "kernels.h"
+#include "device.h"
 
 namespace bert_hip {
-
-typedef _Float16 pool_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 pool_f16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float pool_wave_sum(float v) { return wave_sum_f32(v); }
 
 // Sentence b = rows tok0 .. tok0 + n - 1 of x.  Wave w (of four) sums tokens w, w+4, ... over 16-byte (H % 8 == 0) or 4-byte row
 // reads, the four partial rows are combined through LDS: part = [4][H] floats + 4.  Every thread of the workgroup calls this
@@ -35,7 +29,7 @@ __device__ __forceinline__ void pool_normalize_sentence(const half_t *x, int tok
                 float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll 8
                 for (int t = wave; t < n; t += 4) {
-                    const pool_f16x8 v = *(const pool_f16x8 *)(x + (size_t)(tok0 + t) * H + 8 * c);
+                    const f16x8 v = *(const f16x8 *)(x + (size_t)(tok0 + t) * H + 8 * c);
 #pragma unroll
                     for (int i = 0; i < 8; ++i) acc[i] += (float)v[i] * invn;
                 }
@@ -47,7 +41,7 @@ __device__ __forceinline__ void pool_normalize_sentence(const half_t *x, int tok
                 float a0 = 0.f, a1 = 0.f;
 #pragma unroll 8
                 for (int t = wave; t < n; t += 4) {
-                    const pool_f16x2 v = *(const pool_f16x2 *)(x + (size_t)(tok0 + t) * H + e);
+                    const f16x2 v = *(const f16x2 *)(x + (size_t)(tok0 + t) * H + e);
                     a0 += (float)v[0] * invn; a1 += (float)v[1] * invn;
                 }
                 part[wave * H + e] = a0; part[wave * H + e + 1] = a1;
@@ -62,7 +56,7 @@ __device__ __forceinline__ void pool_normalize_sentence(const half_t *x, int tok
             part[e] = a;
             sq += a * a;
         }
-        sq = pool_wave_sum(sq);
+        sq = wave_sum_f32(sq);
     }
     __syncthreads();
     float *red = part + 4 * H;

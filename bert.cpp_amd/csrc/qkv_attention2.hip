@@ -28,7 +28,7 @@
 // of them add exactly nothing, so a sentence gives the same bits in any window, alone or not (tested).  Key tiles
 // that no query of a block needs are skipped, tiles that lie inside the sentence of every query of the block are not
 // masked at all.
-#include "tile_stream.h"
+#include "device.h"
 
 // tuning knobs (A/B builds): the attention waves execute the head's first barrier after step Q2_PM of their 8 steps
 // (0..3 = S^T key tiles, 4..7 = P V key tiles); Q2_PRIO = s_setprio level of the attention waves
@@ -63,13 +63,6 @@ struct Qkv2Args {
 
 __device__ __forceinline__ int q2_off32(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
-template <int OFF>
-__device__ __forceinline__ f16x8 q2_read_b128(unsigned addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds offset field is 16 bits");
-    f16x8 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
 // everything but the newest six hand-issued reads has landed: hands one half's fragments to its MFMAs
 __device__ __forceinline__ void q2_wait6(f16x8 (&f)[2][3]) {
     asm volatile("s_waitcnt lgkmcnt(6)"
@@ -92,19 +85,6 @@ __device__ __forceinline__ void q2_wait0_bias(f16x8 (&f)[2][3], f32x4 (&bq)[4], 
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(f[0][0]), "+v"(f[0][1]), "+v"(f[0][2]), "+v"(f[1][0]), "+v"(f[1][1]), "+v"(f[1][2]),
                    "+v"(bq[0]), "+v"(bq[1]), "+v"(bq[2]), "+v"(bq[3]), "+v"(bk[0]), "+v"(bk[1]), "+v"(bk[2]), "+v"(bk[3]) : : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ f32x4 q2_read_f32x4(unsigned addr) {
-    f32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-// hands over the V bias (an untracked global load older than every DMA piece that is still in flight at the head's first barrier)
-__device__ __forceinline__ void q2_take(float &bv) { asm volatile("" : "+v"(bv)); }
-// end of a head: Q/K/V^T are written, this wave's pieces of the next head's first slab have landed (all but the newest VM)
-template <int VM>
-__device__ __forceinline__ void q2_head_barrier() {
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" : : "n"(VM) : "memory");
 }
 
 }  // namespace
@@ -262,9 +242,9 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
             constexpr int par = decltype(par_tag)::value, tt = decltype(tt_tag)::value, half = decltype(half_tag)::value;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                F[par][i][0] = q2_read_b128<tt * Q2_TILE>(aS[2 * half + i]);
-                F[par][i][1] = q2_read_b128<tt * Q2_TILE + 4096>(aS[2 * half + i]);
-                F[par][i][2] = q2_read_b128<tt * Q2_TILE + 8192>(aS[2 * half + i]);
+                F[par][i][0] = lds_read_b128<false, tt * Q2_TILE>(aS[2 * half + i]);
+                F[par][i][1] = lds_read_b128<false, tt * Q2_TILE + 4096>(aS[2 * half + i]);
+                F[par][i][2] = lds_read_b128<false, tt * Q2_TILE + 8192>(aS[2 * half + i]);
             }
         };
         // x rows and slab 0 have landed (slab 1 may still be in flight)
@@ -334,7 +314,7 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
                     if (h < 8) TL_STAMP_AT(tl_sel, 2 + 6 * h);
                     q2_slab_barrier<Q4 ? 63 : PPS - 1>(F[par]);
                     if (h < 8) TL_STAMP_AT(tl_sel, 2 + 6 * h + 1);
-                    q2_take(bv);
+                    landed(bv);         // (the V bias: an untracked global load older than every DMA piece still in flight here)
                     rslot = rslot == 2 ? 0 : rslot + 1;
                     set_slot();
                 }
@@ -349,9 +329,9 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
                 } else if constexpr (hh == LT0) {
                     // the head's Q / K biases, read by hand behind the last half's fragments: they land under this half's MFMAs
                     const unsigned ab = aBias + (unsigned)h * 128u;
-                    bq[0] = q2_read_f32x4<0>(ab); bq[1] = q2_read_f32x4<32>(ab); bq[2] = q2_read_f32x4<64>(ab); bq[3] = q2_read_f32x4<96>(ab);
-                    bk[0] = q2_read_f32x4<H * 4>(ab); bk[1] = q2_read_f32x4<H * 4 + 32>(ab);
-                    bk[2] = q2_read_f32x4<H * 4 + 64>(ab); bk[3] = q2_read_f32x4<H * 4 + 96>(ab);
+                    bq[0] = lds_read_b128<false, 0, f32x4>(ab); bq[1] = lds_read_b128<false, 32, f32x4>(ab); bq[2] = lds_read_b128<false, 64, f32x4>(ab); bq[3] = lds_read_b128<false, 96, f32x4>(ab);
+                    bk[0] = lds_read_b128<false, H * 4, f32x4>(ab); bk[1] = lds_read_b128<false, H * 4 + 32, f32x4>(ab);
+                    bk[2] = lds_read_b128<false, H * 4 + 64, f32x4>(ab); bk[3] = lds_read_b128<false, H * 4 + 96, f32x4>(ab);
                     q2_wait14(F[par]);
                     static_for<6>([&](auto m_tag) __attribute__((always_inline)) {      // last k-tile, matrix by matrix: Q Q K K V V ...
                         constexpr int m = decltype(m_tag)::value;
@@ -393,7 +373,7 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
             // most: they finished head h-2 before they passed the end of head h-1).  One barrier publishes them and opens the
             // next head's first slab; in flight behind it: this wave's pieces of the next head's second slab
             if (h < 8) TL_STAMP_AT(tl_sel, 2 + 6 * h + 4);
-            q2_head_barrier<Q4 ? 63 : PPS>();
+            dma_barrier<Q4 ? 63 : PPS>();
             if (h < 8) TL_STAMP_AT(tl_sel, 2 + 6 * h + 5);
             rslot = rslot == 2 ? 0 : rslot + 1;
             set_slot();
@@ -484,7 +464,7 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
                 if (FAST || (need & (1u << kt))) {
 #pragma unroll
                     for (int st = 0; st < 2; ++st) {
-                        // (softmax_p8, kernels.h: fp16 argument and exponential like the reference's table, f32 row sum)
+                        // (softmax_p8, device.h: fp16 argument and exponential like the reference's table, f32 row sum)
                         const f16x8 pf = softmax_p8(s[kt][8 * st], s[kt][8 * st + 1], s[kt][8 * st + 2], s[kt][8 * st + 3], s[kt][8 * st + 4],
                                                     s[kt][8 * st + 5], s[kt][8 * st + 6], s[kt][8 * st + 7], sc, mx, psum);
                         const int key0 = kt * 32 + 16 * st + 4 * hi;              // keys key0..+3 and key0+8..+11

@@ -26,7 +26,7 @@
 #include <cstring>
 #include <vector>
 
-#include "kernels.h"
+#include "device.h"
 #include "search.h"
 
 #define HIP_OK(expr, errvar, ret)                                                                       \
@@ -50,8 +50,6 @@ constexpr int SENT_ID = INT_MAX;        // id of an empty list entry (score -inf
 constexpr int TARGET_BLOCKS = 2048;     // score workgroups a search aims for (8 per CU)
 constexpr int MERGE_U = 16;             // candidates per thread and round of the merge
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 // (s, i) ranks before (ts, ti)
 __device__ __forceinline__ bool better(float s, int i, float ts, int ti) { return s > ts || (s == ts && i < ti); }
@@ -84,17 +82,17 @@ template <class T> struct ScoreBlock;
 
 template <> struct ScoreBlock<half_t> {
     // v_mfma_f32_32x32x16_f16: lane l holds A[l & 31][16 s + 8 (l >> 5) + j] and B[..][l & 31] in element j of step s
-    static __device__ __forceinline__ void run(const half_t *qp, const half_t *rp, bool qok, bool rok, int dpad, int h, f32x16_t &acc) {
+    static __device__ __forceinline__ void run(const half_t *qp, const half_t *rp, bool qok, bool rok, int dpad, int h, f32x16 &acc) {
         constexpr int U = 8;
-        const f16x8_t z = {};
+        const f16x8 z = {};
         for (int k0 = 0; k0 < dpad; k0 += 16 * U) {
-            f16x8_t a[U], b[U];
+            f16x8 a[U], b[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const bool in = k0 + 16 * u < dpad;
                 const int kk = k0 + 16 * u + 8 * h;
-                a[u] = qok && in ? *(const f16x8_t *)(qp + kk) : z;
-                b[u] = rok && in ? *(const f16x8_t *)(rp + kk) : z;
+                a[u] = qok && in ? *(const f16x8 *)(qp + kk) : z;
+                b[u] = rok && in ? *(const f16x8 *)(rp + kk) : z;
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -106,17 +104,17 @@ template <> struct ScoreBlock<half_t> {
 template <> struct ScoreBlock<float> {
     // v_mfma_f32_32x32x2_f32 (an exact f32 fma chain): lane l loads the float4 at k = 8 g + 4 (l >> 5) and feeds element e
     // to step (g, e), which covers k = 8 g + e and 8 g + 4 + e
-    static __device__ __forceinline__ void run(const float *qp, const float *rp, bool qok, bool rok, int dpad, int h, f32x16_t &acc) {
+    static __device__ __forceinline__ void run(const float *qp, const float *rp, bool qok, bool rok, int dpad, int h, f32x16 &acc) {
         constexpr int U = 8;
-        const f32x4_t z = {};
+        const f32x4 z = {};
         for (int k0 = 0; k0 < dpad; k0 += 8 * U) {
-            f32x4_t a[U], b[U];
+            f32x4 a[U], b[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const bool in = k0 + 8 * u < dpad;
                 const int kk = k0 + 8 * u + 4 * h;
-                a[u] = qok && in ? *(const f32x4_t *)(qp + kk) : z;
-                b[u] = rok && in ? *(const f32x4_t *)(rp + kk) : z;
+                a[u] = qok && in ? *(const f32x4 *)(qp + kk) : z;
+                b[u] = rok && in ? *(const f32x4 *)(rp + kk) : z;
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -170,7 +168,7 @@ __global__ __launch_bounds__(NT) void index_topk_kernel(TopkArgs a) {
         const int row = base + wave * 32 + col;
         const bool rok = row < r1;
         const T *rp = (const T *)a.rows + (size_t)(rok ? row : r0) * a.dpad;
-        f32x16_t acc = {};
+        f32x16 acc = {};
         ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, acc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {

@@ -17,7 +17,7 @@
 // (x + bo; b1; y + b2 resp. b2 with y added at the end for the features layer_tail's U wave owns), the same packed-f16
 // GELU on the same element pairs, and LayerNorm statistics summed in the order layer_tail's lanes and wave pairs sum them.
 // tests/test_gpu_parity.py::test_latency_route_gives_the_batch_route_s_bits holds the two routes against each other.
-#include "tile_stream.h"
+#include "device.h"
 
 namespace bert_hip {
 
@@ -156,8 +156,8 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const half_t *__restri
                 for (int e = 0; e < 4; ++e) { b[e] = y[n][2 * s][e]; b[4 + e] = y[n][2 * s + 1][e]; }
             } else {                                          // plain k order: k = 16 q + 8 hi .. + 7 = run 2 s + hi of BOTH lane halves
                 const f16x4 send = hi ? y[n][2 * s] : y[n][2 * s + 1];
-                const unsigned s0 = __builtin_bit_cast(unsigned, f16x2_t{send[0], send[1]}), s1 = __builtin_bit_cast(unsigned, f16x2_t{send[2], send[3]});
-                const f16x2_t r0 = __builtin_bit_cast(f16x2_t, (unsigned)__shfl_xor((int)s0, 32)), r1 = __builtin_bit_cast(f16x2_t, (unsigned)__shfl_xor((int)s1, 32));
+                const unsigned s0 = __builtin_bit_cast(unsigned, f16x2{send[0], send[1]}), s1 = __builtin_bit_cast(unsigned, f16x2{send[2], send[3]});
+                const f16x2 r0 = __builtin_bit_cast(f16x2, (unsigned)__shfl_xor((int)s0, 32)), r1 = __builtin_bit_cast(f16x2, (unsigned)__shfl_xor((int)s1, 32));
                 const f16x4 recv = {r0[0], r0[1], r1[0], r1[1]};
                 const f16x4 lo = hi ? recv : y[n][2 * s], up = hi ? y[n][2 * s + 1] : recv;
 #pragma unroll
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(512) void skinny_gemm_kernel(const half_t *__restri
             for (int e = 0; e < 4; ++e) o[e] = (_Float16)(acc[4 * g + e] + bias4[g][e]);
             *(f16x4 *)(p.out16 + (size_t)tok * N + f) = o;
         } else if constexpr (MODE == SK_UP) {                 // packed-f16 GELU of adjacent pairs (layer_tail.hip: gelu_pair)
-            const f16x2_t g0 = gelu_pk16(acc[4 * g], acc[4 * g + 1]), g1 = gelu_pk16(acc[4 * g + 2], acc[4 * g + 3]);
+            const f16x2 g0 = gelu_pk16(acc[4 * g], acc[4 * g + 1]), g1 = gelu_pk16(acc[4 * g + 2], acc[4 * g + 3]);
             const f16x4 o = {g0[0], g0[1], g1[0], g1[1]};
             // stored in FRAGMENT order: inside every group of 16 features the runs sit at [0-3, 8-11, 4-7, 12-15] (w16p's order),
             // so that the down-projection's token fragment is one 16-byte load: run 8 (g & 1) + 4 hi of group g >> 1 goes

@@ -92,14 +92,9 @@ def test_gemm_persistent_workgroups_walk_several_tiles(M, N, K, impl=3):
         assert not bad.any(), (impl, epi, int(bad.sum()), float(err.max()), np.argwhere(bad)[:5].tolist())
 
 
-@pytest.mark.parametrize("wtype", [2, 3], ids=["q4_0", "q4_1"])
-@pytest.mark.parametrize("M,N,K", [(300, 768, 768), (512, 2304, 768), (257, 768, 3072), (20480, 3072, 768), (33000, 768, 3072), (9000, 256, 128)])
-def test_gemm256_q4_tile_load_gives_the_f16_form_s_bits(M, N, K, wtype):
-    """gemm256 with 4-bit-resident weights (SURVEY §8 row g1 at H = 768: q4_0 / q4_1 blocks dequantised in the GEMM's tile
-    load): a thread fetches its 32-weight block two reduction tiles ahead and expands it into the weight tile's LDS image —
-    the image the f16 form loads by LDS-DMA from the matrix expanded at load.  Same image, same MFMA sequence: EQUAL BITS with
-    the f16 form on the expanded matrix, all three epilogues; sizes with one output tile per workgroup, with several
-    (persistent walk, block requests crossing output tiles), and with the minimum of two reduction tiles."""
+def _q4_gives_the_f16_form_s_bits(M, N, K, wtype, impl):
+    """The mat-mul kernel `impl` on q4 blocks against the same kernel on the f16 image of those blocks: equal bits, all three
+    epilogues; and the f16 form itself is right."""
     rng = np.random.default_rng(M + N + K + wtype)
     A = rng.normal(0, 1, (M, K)).astype(np.float16)
     W = (rng.normal(0, 1, (N, K)) / np.sqrt(K)).astype(np.float32)
@@ -111,13 +106,34 @@ def test_gemm256_q4_tile_load_gives_the_f16_form_s_bits(M, N, K, wtype):
     img = _q4_image_f16(q, wtype, (N, K))
     for epi in (0, 1, 2):
         r = resid if epi == 2 else None
-        got = pybert.test_gemm(A, q.reshape(-1), wtype, N, bias, r, epi, 3)
-        want = pybert.test_gemm(A, img.view(np.uint8).reshape(-1), 1, N, bias, r, epi, 3)
+        got = pybert.test_gemm(A, q.reshape(-1), wtype, N, bias, r, epi, impl)
+        want = pybert.test_gemm(A, img.view(np.uint8).reshape(-1), 1, N, bias, r, epi, impl)
         assert np.array_equal(got.view(np.uint16), want.view(np.uint16)), (epi, int((got != want).sum()), np.argwhere(got != want)[:5].tolist())
-    # and the f16 form itself is right (float32 BLAS: the big cases are too large for a float64 product in a test)
+    # (float32 BLAS: the big cases are too large for a float64 product in a test)
     base = A.astype(np.float32) @ img.astype(np.float32).T + bias
     err = np.abs(want.astype(np.float32) - (base + resid.astype(np.float32)))
     assert not (err > 2e-3 * np.abs(base) + 6e-3).any(), float(err.max())
+
+
+@pytest.mark.parametrize("wtype", [2, 3], ids=["q4_0", "q4_1"])
+@pytest.mark.parametrize("M,N,K", [(300, 768, 768), (512, 2304, 768), (257, 768, 3072), (20480, 3072, 768), (33000, 768, 3072), (9000, 256, 128)])
+def test_gemm256_q4_tile_load_gives_the_f16_form_s_bits(M, N, K, wtype):
+    """gemm256 with 4-bit-resident weights (SURVEY §8 row g1 at H = 768: q4_0 / q4_1 blocks dequantised in the GEMM's tile
+    load): a thread fetches its 32-weight block two reduction tiles ahead and expands it into the weight tile's LDS image —
+    the image the f16 form loads by LDS-DMA from the matrix expanded at load.  Same image, same MFMA sequence: EQUAL BITS with
+    the f16 form on the expanded matrix, all three epilogues; sizes with one output tile per workgroup, with several
+    (persistent walk, block requests crossing output tiles), and with the minimum of two reduction tiles."""
+    _q4_gives_the_f16_form_s_bits(M, N, K, wtype, 3)
+
+
+@pytest.mark.parametrize("wtype", [2, 3], ids=["q4_0", "q4_1"])
+@pytest.mark.parametrize("M,N,K", [(200, 192, 128), (130, 64, 64), (256, 256, 64), (384, 384, 1536), (129, 2304, 768), (300, 768, 3072),
+                                   (513, 3072, 768), (9000, 256, 128)])
+def test_gemm_mfma_q4_tile_load_gives_the_f16_form_s_bits(M, N, K, wtype):
+    """gemm.hip's 128 x 128 kernel expands a thread's q4 block per reduction tile into the weight tile's LDS image with the
+    shared block expansion (device.h q4_expand_block): EQUAL BITS with the same kernel on the expanded f16 matrix, all three
+    epilogues; a partial feature tile (N = 64, 192), one reduction tile (K = 64), ragged token tiles."""
+    _q4_gives_the_f16_form_s_bits(M, N, K, wtype, 0)
 
 
 @pytest.mark.parametrize("rebuild", [False, True], ids=["plain-residual", "rebuilt-residual"])
