@@ -18,7 +18,8 @@ public:
     static constexpr int MAX_K = 256, MAX_DIM = 2048;
     static constexpr int QCHUNK = 4096;                  // queries per internal pass (workspace bound)
 
-    // dtype 0: f32 rows, 1: f16 rows (queries rounded to f16 as well)
+    // dtype 0: f32 rows, 1: f16 rows (queries rounded to f16 as well), 2: i8 rows with one f32 scale each (queries quantized
+    // the same way; search.hip)
     static Index *create(Engine *eng, int dim, int dtype, std::string &err);
     ~Index();
 
@@ -54,7 +55,9 @@ private:
     int dim_ = 0, dtype_ = 0, dpad_ = 0, es_ = 4;       // dpad_: elements per stored row, es_: bytes per element
     int n_ = 0, cap_ = 0;
     void *rows_ = nullptr;                              // [cap_][dpad_]
+    float *rscale_ = nullptr;                           // i8: [cap_] row scales
     DevBuf ws_s_, ws_i_, qbuf_;                         // per-(query, slice) lists; the current chunk's queries as stored
+    DevBuf qscale_;                                     // i8: the current chunk's query scales
     DevBuf stage_, out_ids_, out_scores_, scratch_;     // host routes: f32 rows / queries, results; the text routes' embeddings
     hipStream_t stream_ = nullptr;                      // the host routes' stream
     // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event

@@ -3,7 +3,8 @@
 // A search of nq queries over N rows of dim elements is a GEMM (M = queries, N = rows, K = dim) whose epilogue selects:
 //   index_topk_kernel<T>  one workgroup per (query tile of 32, slice of rows).  Each wave scores a 32 x 32 block
 //                         (queries x rows) per step on the matrix cores — f16 rows: v_mfma_f32_32x32x16_f16, f32 rows:
-//                         v_mfma_f32_32x32x2_f32 — and a lane ends the step with one row's scores for 16 queries.  Every score
+//                         v_mfma_f32_32x32x2_f32, i8 rows: v_mfma_i32_32x32x32_i8 and the two scales — and a lane ends the
+//                         step with one row's scores for 16 queries.  Every score
 //                         is compared with its query's threshold (the k-th best of this workgroup so far, kept in registers);
 //                         only the ones that beat it go into the query's candidate queue in LDS (an LDS atomic hands out the
 //                         slot).  When a queue might not take another step's rows, the lists are bitonic-sorted in LDS by
@@ -12,18 +13,26 @@
 //   topk_merge_kernel     one workgroup per query: the same threshold / queue / sort over the slices' lists, then the
 //                         final ids and scores.
 //   index_convert_kernel  f32 rows (added rows, queries) -> the stored form: f32 or f16 (RNE), zero-padded to dpad.
+//   index_quantize_kernel f32 rows (added rows, queries) -> the i8 form: one wave per row, codes zero-padded to dpad and one
+//                         f32 scale per row.
+//
+// The i8 form (dtype 2): a row or query x is stored as scale = amax / 127 (amax = max |x_i|; NaN if any x_i is NaN or +-inf)
+// and codes c_i = clamp(rint(x_i / scale), -127, 127) (all 0 if the scale is 0 or NaN); its score is
+// ((float)dot * qscale) * rscale with dot = sum_i qc_i rc_i an exact int32 (|dot| <= 2048 * 127^2 < 2^31).  A row that held a
+// NaN or an inf scores NaN and is never returned; so does every row for such a query.
 //
 // Order of a result: larger score first, equal scores (==, so +0 equals -0) by smaller id; NaN scores never pass a compare
 // and are never returned; missing entries are id -1, score -inf (inside the kernels: id INT_MAX, which ranks below every row).
-// Determinism: a (query, row) score is one MFMA accumulation chain in a fixed k order that depends on nothing but dpad, and
-// the key order is total over distinct rows, so the set and order of a result do not depend on the slicing, the chunking of
-// the queries, the neighbours in a batch, or k (top-10 is the first 10 of top-100).
+// Determinism: a (query, row) score is one MFMA accumulation chain in a fixed k order that depends on nothing but dpad (i8: an
+// exact integer sum, then two multiplies), and the key order is total over distinct rows, so the set and order of a result do
+// not depend on the slicing, the chunking of the queries, the neighbours in a batch, or k (top-10 is the first 10 of top-100).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "device.h"
@@ -128,16 +137,44 @@ template <> struct ScoreBlock<float> {
     }
 };
 
+template <> struct ScoreBlock<int8_t> {
+    // v_mfma_i32_32x32x32_i8: lane l feeds the 16 bytes at k = 32 s + 16 (l >> 5) of its query and of its row to step s — the
+    // same k map on both sides, and an integer sum is exact in any order
+    static __device__ __forceinline__ void run(const int8_t *qp, const int8_t *rp, bool qok, bool rok, int dpad, int h, i32x16 &acc) {
+        constexpr int U = 8;
+        const i32x4 z = {};
+        for (int k0 = 0; k0 < dpad; k0 += 32 * U) {
+            i32x4 a[U], b[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k0 + 32 * u < dpad;
+                const int kk = k0 + 32 * u + 16 * h;
+                a[u] = qok && in ? *(const i32x4 *)(qp + kk) : z;
+                b[u] = rok && in ? *(const i32x4 *)(rp + kk) : z;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (k0 + 32 * u < dpad) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[u], b[u], acc, 0, 0, 0);
+        }
+    }
+};
+
 struct TopkArgs {
     const void *rows, *queries;          // [n_rows][dpad], [nq][dpad] of T
     float *ws_s;                         // [nq][n_slices][k] per-(query, slice) lists, best first
     int *ws_i;
     int n_rows, dpad, nq, n_qtiles, n_slices, slice_rows, k, L, n_items;
 };
+// (a type of its own: the f16 and f32 kernels keep their argument block, and with it their machine code)
+struct TopkArgsI8 : TopkArgs {
+    const float *qscale, *rscale;        // [nq], [n_rows]
+};
 
 // LDS: float scores [nqv][L], int ids [nqv][L], int count [nqv] — per query the current top-k in [0, k), the queue behind
-template <class T>
-__global__ __launch_bounds__(NT) void index_topk_kernel(TopkArgs a) {
+// (Args: TopkArgsI8 for T = int8_t, TopkArgs otherwise)
+template <class T, class Args>
+__global__ __launch_bounds__(NT) void index_topk_kernel(Args a) {
+    constexpr bool I8 = std::is_same_v<T, int8_t>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // workgroup b runs on XCD b % 8: consecutive items — the query tiles of one slice of rows — go to one XCD, so that
     // they find the slice in that XCD's L2 (the grid is a multiple of 8; items beyond n_items do nothing)
@@ -158,6 +195,15 @@ __global__ __launch_bounds__(NT) void index_topk_kernel(TopkArgs a) {
     int ti[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { ts[r] = -INFINITY; ti[r] = SENT_ID; }
+    // i8: the scales of this lane's 16 queries
+    [[maybe_unused]] float qs[16];
+    if constexpr (I8) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int q = (r & 3) + 8 * (r >> 2) + 4 * h;
+            qs[r] = q < nqv ? a.qscale[q0 + q] : 0.f;
+        }
+    }
     __syncthreads();
 
     const bool qok = col < nqv;
@@ -169,7 +215,16 @@ __global__ __launch_bounds__(NT) void index_topk_kernel(TopkArgs a) {
         const bool rok = row < r1;
         const T *rp = (const T *)a.rows + (size_t)(rok ? row : r0) * a.dpad;
         f32x16 acc = {};
-        ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, acc);
+        if constexpr (I8) {
+            const float rs = a.rscale[rok ? row : r0];
+            i32x16 dot = {};
+            ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, dot);
+            // (two multiplies in this order and no add: nothing the compiler could contract)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = ((float)dot[r] * qs[r]) * rs;
+        } else {
+            ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, acc);
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int q = (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -278,6 +333,45 @@ void launch_convert(const float *src, void *dst, int n, int dim, int dpad, hipSt
     BERT_LAUNCH(index_convert_kernel<T>, dim3(blocks), dim3(256), 0, s, src, (T *)dst, n, dim, dpad);
 }
 
+// f32 rows [n][dim] -> i8 codes [n][dpad] and scales [n] (the i8 form above).  One wave per row: the finite test and the
+// maximum of |x_i| across the wave (a maximum is exact in any lane order), then four codes per lane and 32-bit store.
+// dpad is a multiple of 32; the division is IEEE (correctly rounded), rint rounds to nearest even.
+__global__ __launch_bounds__(256) void index_quantize_kernel(const float *__restrict__ src, int8_t *__restrict__ codes,
+                                                             float *__restrict__ scales, int n, int dim, int dpad) {
+    const int lane = threadIdx.x & 63;
+    const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= (size_t)n) return;                                // (the whole wave)
+    const float *x = src + r * dim;
+    float amax = 0.f;
+    int bad = 0;
+    for (int c = lane; c < dim; c += 64) {
+        const float v = x[c];
+        bad |= !__builtin_isfinite(v);                         // (fmaxf drops a NaN: tested on its own)
+        amax = fmaxf(amax, fabsf(v));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    bad = __any(bad);
+    const float scale = bad ? __builtin_nanf("") : amax / 127.0f;
+    const bool zero = bad || scale == 0.f;
+    if (lane == 0) scales[r] = scale;
+    int8_t *out = codes + r * dpad;
+    for (int c = 4 * lane; c < dpad; c += 256) {
+        uint32_t packed = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float v = c + j < dim ? x[c + j] : 0.f;
+            const float q = zero ? 0.f : fminf(fmaxf(__builtin_rintf(v / scale), -127.f), 127.f);
+            packed |= (uint32_t)(uint8_t)(int8_t)(int)q << (8 * j);
+        }
+        *(uint32_t *)(out + c) = packed;
+    }
+}
+
+void launch_quantize(const float *src, void *codes, float *scales, int n, int dim, int dpad, hipStream_t s) {
+    BERT_LAUNCH(index_quantize_kernel, dim3((n + 3) / 4), dim3(256), 0, s, src, (int8_t *)codes, scales, n, dim, dpad);
+}
+
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int d) {
@@ -319,22 +413,24 @@ size_t Index::ws_entries_bound(int n_rows, int nq, int k) {
 Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
     if (!eng) { err = "no device engine"; return nullptr; }
     if (dim < 1 || dim > MAX_DIM) { err = "dim must be 1 .. 2048"; return nullptr; }
-    if (dtype != 0 && dtype != 1) { err = "dtype must be 0 (f32) or 1 (f16)"; return nullptr; }
+    if (dtype < 0 || dtype > 2) { err = "dtype must be 0 (f32), 1 (f16) or 2 (i8)"; return nullptr; }
     DeviceGuard g(eng->device());
     Index *ix = new Index;
     ix->eng_ = eng;
     ix->dim_ = dim;
     ix->dtype_ = dtype;
-    ix->es_ = dtype == 1 ? 2 : 4;
-    ix->dpad_ = dtype == 1 ? (dim + 15) / 16 * 16 : (dim + 7) / 8 * 8;      // the score kernel's k-step (a 16-byte load per lane)
+    ix->es_ = dtype == 2 ? 1 : dtype == 1 ? 2 : 4;
+    // the score kernel's k-step (a 16-byte load per lane)
+    ix->dpad_ = dtype == 2 ? (dim + 31) / 32 * 32 : dtype == 1 ? (dim + 15) / 16 * 16 : (dim + 7) / 8 * 8;
     const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
     if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
     // (32 queries x 512-entry lists: 128 KiB of LDS, beyond the 64 KiB a launch gets unasked; a launch that still cannot
     // have it fails, and the search reports the launch error)
     const int lds_max = QT * 512 * 8 + QT * 4;
-    (void)hipFuncSetAttribute((const void *)index_topk_kernel<half_t>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-    (void)hipFuncSetAttribute((const void *)index_topk_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<half_t, TopkArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<float, TopkArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<int8_t, TopkArgsI8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     return ix;
 }
 
@@ -343,6 +439,7 @@ Index::~Index() {
     if (busy_) { (void)hipEventSynchronize(busy_); (void)hipEventDestroy(busy_); }
     if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
     if (rows_) (void)hipFree(rows_);
+    if (rscale_) (void)hipFree(rscale_);
 }
 
 bool Index::grow(DevBuf &b, size_t bytes, std::string &err) {
@@ -356,15 +453,27 @@ bool Index::grow_rows(int n_rows, std::string &err) {
     const int cap = (int)std::min<long long>(INT_MAX, std::max<long long>({(long long)n_rows, (long long)cap_ * 3 / 2, 1024}));
     const size_t row_bytes = (size_t)dpad_ * es_;
     void *p = nullptr;
+    float *sc = nullptr;
     HIP_OK(hipEventSynchronize(busy_), err, false);
     HIP_OK(hipMalloc(&p, (size_t)cap * row_bytes), err, false);
-    if (n_ > 0 && hipMemcpy(p, rows_, (size_t)n_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+    if (dtype_ == 2 && hipMalloc(&sc, (size_t)cap * 4) != hipSuccess) {
         (void)hipFree(p);
-        err = "hipMemcpy (index rows) failed";
+        err = "hipMalloc (index row scales) failed";
+        return false;
+    }
+    const char *failed = nullptr;
+    if (n_ > 0 && hipMemcpy(p, rows_, (size_t)n_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) failed = "hipMemcpy (index rows) failed";
+    else if (n_ > 0 && sc && hipMemcpy(sc, rscale_, (size_t)n_ * 4, hipMemcpyDeviceToDevice) != hipSuccess) failed = "hipMemcpy (index row scales) failed";
+    if (failed) {
+        (void)hipFree(p);
+        if (sc) (void)hipFree(sc);
+        err = failed;
         return false;
     }
     if (rows_) (void)hipFree(rows_);
+    if (rscale_) (void)hipFree(rscale_);
     rows_ = p;
+    rscale_ = sc;
     cap_ = cap;
     return true;
 }
@@ -379,7 +488,8 @@ bool Index::reserve(int n_rows, int n_queries, int k, std::string &err) {
     const int rows = std::max(n_rows, n_);
     for (int kk = 1; kk <= k; ++kk)
         for (int t = 1; t <= (nqc + QT - 1) / QT; ++t) ent = std::max(ent, ws_entries_bound(rows, std::min(nqc, t * QT), kk));
-    return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err) && grow(qbuf_, (size_t)nqc * dpad_ * es_, err);
+    return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err) && grow(qbuf_, (size_t)nqc * dpad_ * es_, err) &&
+           (dtype_ != 2 || grow(qscale_, (size_t)nqc * 4, err));
 }
 
 int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &err) {
@@ -390,8 +500,9 @@ int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &er
     if (!grow_rows(n_ + n, err)) return -1;
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     char *dst = (char *)rows_ + (size_t)n_ * dpad_ * es_;
-    eng_->timed_launch(dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
-        if (dtype_ == 1) launch_convert<half_t>(d_rows, dst, n, dim_, dpad_, s);
+    eng_->timed_launch(dtype_ == 2 ? "index_quantize_i8" : dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
+        if (dtype_ == 2) launch_quantize(d_rows, dst, rscale_ + n_, n, dim_, dpad_, s);
+        else if (dtype_ == 1) launch_convert<half_t>(d_rows, dst, n, dim_, dpad_, s);
         else launch_convert<float>(d_rows, dst, n, dim_, dpad_, s);
     });
     HIP_OK(hipGetLastError(), err, -1);
@@ -426,19 +537,24 @@ int Index::add_host(int n, const float *rows, std::string &err) {
 
 void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s) {
     const Plan p = plan(n_, nq, k);
-    eng_->timed_launch(dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
-        if (dtype_ == 1) launch_convert<half_t>(d_q, qbuf_.p, nq, dim_, dpad_, s);
+    eng_->timed_launch(dtype_ == 2 ? "index_quantize_i8" : dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
+        if (dtype_ == 2) launch_quantize(d_q, qbuf_.p, qscale_.as<float>(), nq, dim_, dpad_, s);
+        else if (dtype_ == 1) launch_convert<half_t>(d_q, qbuf_.p, nq, dim_, dpad_, s);
         else launch_convert<float>(d_q, qbuf_.p, nq, dim_, dpad_, s);
     });
     TopkArgs a;
     a.rows = rows_; a.queries = qbuf_.p; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
     a.n_rows = n_; a.dpad = dpad_; a.nq = nq; a.n_qtiles = p.nqt; a.n_slices = p.slices; a.slice_rows = p.slice_rows;
     a.k = k; a.L = p.L; a.n_items = p.nqt * p.slices;
+    TopkArgsI8 a8;
+    static_cast<TopkArgs &>(a8) = a;
+    a8.qscale = qscale_.as<float>(); a8.rscale = rscale_;
     const int grid = (a.n_items + 7) / 8 * 8;
     const double flops = 2.0 * nq * (double)n_ * dim_;
-    eng_->timed_launch(dtype_ == 1 ? "index_topk_f16" : "index_topk_f32", flops, s, [&] {
-        if (dtype_ == 1) BERT_LAUNCH(index_topk_kernel<half_t>, dim3(grid), dim3(NT), p.lds, s, a);
-        else BERT_LAUNCH(index_topk_kernel<float>, dim3(grid), dim3(NT), p.lds, s, a);
+    eng_->timed_launch(dtype_ == 2 ? "index_topk_i8" : dtype_ == 1 ? "index_topk_f16" : "index_topk_f32", flops, s, [&] {
+        if (dtype_ == 2) BERT_LAUNCH((index_topk_kernel<int8_t, TopkArgsI8>), dim3(grid), dim3(NT), p.lds, s, a8);
+        else if (dtype_ == 1) BERT_LAUNCH((index_topk_kernel<half_t, TopkArgs>), dim3(grid), dim3(NT), p.lds, s, a);
+        else BERT_LAUNCH((index_topk_kernel<float, TopkArgs>), dim3(grid), dim3(NT), p.lds, s, a);
     });
     MergeArgs m;
     m.ws_s = a.ws_s; m.ws_i = a.ws_i; m.n_cand = p.slices * k; m.k = k; m.L = merge_L(k); m.ids = d_ids; m.scores = d_scores;
@@ -454,7 +570,9 @@ int Index::search_device(int nq, const float *d_q, int k, int32_t *d_ids, float 
     const int nqc = std::min(nq, QCHUNK);
     // (the last, shorter chunk may be cut into more slices than a full one)
     const size_t ent = std::max(ws_entries_bound(n_, nqc, k), nq % QCHUNK ? ws_entries_bound(n_, nq % QCHUNK, k) : 0);
-    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(qbuf_, (size_t)nqc * dpad_ * es_, err)) return -1;
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(qbuf_, (size_t)nqc * dpad_ * es_, err) ||
+        (dtype_ == 2 && !grow(qscale_, (size_t)nqc * 4, err)))
+        return -1;
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);

@@ -3,8 +3,8 @@
 // then each line read from stdin is a query whose k closest texts are printed in the reference's format.  'q' or the end
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
-//   bert-search -m MODEL -f TEXTS [-k 3] [--f32] [-t THREADS]
-//   (--f32: an f32 index; the default stores the rows as f16)
+//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8] [-t THREADS]
+//   (--f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; the default stores the rows as f16)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,7 +18,7 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32] [-t THREADS]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8] [-t THREADS]\n", argv0);
 }
 
 std::string chomp(std::string s) {
@@ -37,6 +37,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "-k") && has_value) k = atoi(argv[++i]);
         else if ((!strcmp(argv[i], "-t") || !strcmp(argv[i], "--threads")) && has_value) n_threads = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--f32")) dtype = 0;
+        else if (!strcmp(argv[i], "--i8")) dtype = 2;
         else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
     }
     if (!model || !file) { usage(argv[0]); return 2; }

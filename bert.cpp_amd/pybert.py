@@ -399,7 +399,8 @@ class BertModel:
         self.lib.bert_hip_set_option(self.ctx, key.encode(), value.encode())
 
     def index(self, dim: Optional[int] = None, dtype: str = "f16") -> "BertIndex":
-        """An embedding index on the context's first device (bert_hip_index_create): dim None = n_embd, dtype "f16" | "f32"."""
+        """An embedding index on the context's first device (bert_hip_index_create): dim None = n_embd, dtype "f16" | "f32" |
+        "i8" (one int8 code per element and one f32 scale per row)."""
         return BertIndex(self, dim, dtype)
 
 
@@ -409,10 +410,11 @@ class BertIndex:
     data_ptr()) and a stream handle, and return at once."""
 
     def __init__(self, model: BertModel, dim: Optional[int] = None, dtype: str = "f16"):
-        if dtype not in ("f16", "f32"):
-            raise ValueError("dtype must be 'f16' or 'f32'")
+        if dtype not in ("f16", "f32", "i8"):
+            raise ValueError("dtype must be 'f16', 'f32' or 'i8'")
         self.model, self.lib = model, model.lib
-        self.ix = self.lib.bert_hip_index_create(model.ctx, 0 if dim is None else int(dim), 1 if dtype == "f16" else 0)
+        code = {"f16": 1, "i8": 2}.get(dtype, 0)
+        self.ix = self.lib.bert_hip_index_create(model.ctx, 0 if dim is None else int(dim), code)
         if not self.ix:
             raise RuntimeError("bert_hip_index_create failed (see stderr)")
         self.dim = model.n_embd if dim is None else int(dim)

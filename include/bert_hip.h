@@ -143,8 +143,10 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  * An index belongs to the context it was made from: bert_free frees any index the caller left alive.  Like every
  * entry point of a context, the index functions are not re-entrant on one context.
  *   create   dim: 0 = bert_n_embd(ctx), else 1 .. 2048.  dtype: 0 = f32 rows, 1 = f16 rows (rounded to nearest even; the
- *            queries are rounded to f16 the same way).  NULL + a message on stderr on error (tokenizer-only context, no
- *            device, bad arguments).
+ *            queries are rounded to f16 the same way), 2 = int8 rows with one f32 scale per row (the queries quantized the
+ *            same way, on the device; below).  Memory per row: 4 * ceil(dim / 8) * 8 bytes (f32), 2 * ceil(dim / 16) * 16
+ *            (f16), dpad + 4 with dpad = ceil(dim / 32) * 32 (int8).  NULL + a message on stderr on error (tokenizer-only
+ *            context, no device, bad arguments).
  *   add      appends rows [n][dim] (f32); they get ids size, size + 1, ...; returns the first new id, negative on error
  *            (index unchanged).  add_device: the rows in device memory of the index's device, enqueued on `stream`.
  *            add_texts: encodes the texts (dim must equal n_embd) on the context's devices as bert_hip_encode_batch does; on a
@@ -159,6 +161,13 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  *   - score = sum_i q[i] * row[i], accumulated in f32: f32 rows on v_mfma_f32_32x32x2_f32 (an f32 fma chain), f16 rows and
  *     f16-rounded queries on v_mfma_f32_32x32x16_f16 (rows zero-padded to its k-step, which changes no sum).  The engine's
  *     embeddings are L2-normalised: for them the score is the cosine.
+ *   - int8 (dtype 2), all arithmetic f32 unless stated: each row and each query x is quantized on its own, amax = max_i |x_i|,
+ *     scale = amax / 127 (correctly rounded), code_i = clamp(rint(x_i / scale), -127, 127) (rint: nearest even; the division
+ *     correctly rounded), every code 0 if scale == 0; if any x_i is NaN or +-inf the scale is NaN and every code 0.  Codes
+ *     are zero-padded to dpad.  score = ((float)dot * qscale) * rscale in that order (two roundings, no fma), where
+ *     dot = sum_i qcode_i * rcode_i is an exact int32 converted with round-to-nearest-even.  So a row holding a NaN OR an inf
+ *     scores NaN and is never returned (an f32 index can return a row holding an inf); a query holding one returns only
+ *     id -1 / -INFINITY slots; a zero query scores 0 against every finite row.  The same determinism as below holds.
  *   - order: larger score first; equal scores (==, so +0 equals -0) smaller id first.  Rows with a NaN score are never
  *     returned.  Slots beyond the rows that can be returned are id -1, score -INFINITY.  An empty index is valid.
  *   - 1 <= k <= 256, anything else is an error; n_queries == 0 is a successful no-op; large n_queries run in internal chunks.

@@ -6,7 +6,9 @@ bert_hip_index_add.  GPU only: there is no CPU fallback.
 
 Per line: ms per call (device events, after warm-up), queries/s, the algorithmic bytes (the rows once, the queries, the
 results) and FLOPs (2 Q N dim), the share of the binding roofline (HBM 6.3 TB/s achievable; matrix cores 2.5 PF/s f16,
-155 TF/s f32) and its name, torch's ms, and whether the two agree (per query: the same ids up to ties within tolerance).
+155 TF/s f32, 5 PF/s i8) and its name, torch's ms, and whether the two agree (per query: the same ids up to ties within
+tolerance).  i8 rows count dpad + 4 bytes (codes and scale); torch's yardstick for them is the same quantization and score
+restated in torch (f32 mat-mul of the codes, exact at these dims: every partial sum is an integer below 2^24).
 """
 import argparse
 import os
@@ -20,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM = 6.3e12
-PEAK = {"f16": 2.5e15, "f32": 155e12}
+PEAK = {"f16": 2.5e15, "f32": 155e12, "i8": 5.0e15}
 
 
 def agree(ids, scores, t_ids, t_vals, k, tol):
@@ -36,6 +38,14 @@ def agree(ids, scores, t_ids, t_vals, k, tol):
     return True
 
 
+def quantize(x):
+    """the i8 index's quantizer (include/bert_hip.h), restated in torch: codes as f32 and one scale per row"""
+    import torch
+    scale = x.abs().amax(dim=1) / 127
+    codes = torch.clamp(torch.round(x / scale[:, None]), -127, 127)
+    return torch.where(scale[:, None] == 0, torch.zeros_like(codes), codes), scale
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -43,6 +53,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
+    torch.backends.cuda.matmul.allow_tf32 = False
     if not torch.cuda.is_available():
         sys.exit("search_rate.py needs a GPU")
     os.environ.setdefault("BERT_HIP_QUIET", "1")
@@ -71,11 +82,13 @@ def main():
         C /= C.norm(dim=1, keepdim=True)
         Qall = torch.randn(4096, dim, device=dev, generator=g)
         Qall /= Qall.norm(dim=1, keepdim=True)
-        for dtype in ("f16", "f32"):
+        for dtype in ("f16", "f32", "i8"):
             ix = m.index(dim=dim, dtype=dtype)
             ix.reserve(N, 4096, 100)
             ix.add_device(N, C.data_ptr(), sp)
             Ct = C.half() if dtype == "f16" else C
+            if dtype == "i8":
+                Ct, Cs = quantize(C)
             for Q in (1, 16, 256, 4096):
                 q = Qall[:Q].contiguous()
                 for k in (10, 100):
@@ -87,9 +100,13 @@ def main():
 
                     def yard():
                         qt = q.half() if dtype == "f16" else q
+                        if dtype == "i8":
+                            qt, qs = quantize(q)
                         res = []
                         for c0 in range(0, Q, 256):          # (a [256, N] f32 score block at a time: 1 GB)
                             s = (qt[c0:c0 + 256] @ Ct.T).float()
+                            if dtype == "i8":
+                                s = (s * qs[c0:c0 + 256, None]) * Cs[None, :]
                             res.append(torch.topk(s, k, dim=1))
                         return torch.cat([r.values for r in res]), torch.cat([r.indices for r in res])
 
@@ -112,15 +129,17 @@ def main():
                     torch.cuda.synchronize()
                     nq = min(Q, 64)
                     ok = agree(ids[:nq].cpu().numpy(), sc[:nq].cpu().numpy(), ti[:nq].cpu().numpy(), tv[:nq].cpu().numpy(), k, 1e-3)
-                    es = 2 if dtype == "f16" else 4
-                    dpad = (dim + 15) // 16 * 16 if dtype == "f16" else (dim + 7) // 8 * 8
-                    nbytes = N * dpad * es + Q * dim * 4 + Q * k * 8
+                    es = {"f16": 2, "f32": 4, "i8": 1}[dtype]
+                    step = {"f16": 16, "f32": 8, "i8": 32}[dtype]
+                    dpad = (dim + step - 1) // step * step
+                    nbytes = N * (dpad * es + (4 if dtype == "i8" else 0)) + Q * dim * 4 + Q * k * 8
                     flops = 2.0 * Q * N * dim
                     tb, tf = nbytes / HBM, flops / PEAK[dtype]
                     bound, share = ("HBM", tb / (t * 1e-3)) if tb >= tf else ("MFMA", tf / (t * 1e-3))
                     out(f"{dim:5d} {dtype:5s} {Q:5d} {k:4d} | {t:8.3f} {Q / (t * 1e-3):11.0f}  {nbytes:.2e} {flops:.2e} | "
                         f"{bound:5s} {share:6.3f} | {ty:8.3f}  {'yes' if ok else 'NO'}")
             ix.close()
+            del Ct
         del C, Qall
         torch.cuda.empty_cache()
 
