@@ -142,6 +142,16 @@ __device__ __forceinline__ float rounded_f32(float v) {
 __device__ __forceinline__ void xor32_pair(float &a, float &b) {
     asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
 }
+// A 32x32 MFMA RESULT fragment (lane (l31, hi) holds columns 16 q + 4 hi + {0..3} | 16 q + 8 + 4 hi + {0..3} of row l31, rounded to f16)
+// as the OPERAND fragment of k-step q (lane (l31, hi): k = 16 q + 8 hi + {0..7} of the same row): lanes 0..31 give their upper half for
+// the lower half of lanes 32..63 — v_permlane32_swap vdst, src exchanges lanes 32..63 of vdst with lanes 0..31 of src, one dword at a time
+// — and every element already sits in its place.
+__device__ __forceinline__ f16x8 result_to_operand_fragment(const f16x8 &v) {
+    const u32x4 d = __builtin_bit_cast(u32x4, v);
+    uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
+    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\ts_nop 1" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
+    return __builtin_bit_cast(f16x8, u32x4{d0, d1, d2, d3});
+}
 __device__ __forceinline__ float xor32_sum(float v) { float a = v, b = v; xor32_pair(a, b); return a + b; }
 __device__ __forceinline__ float xor32_max(float v) { float a = v, b = v; xor32_pair(a, b); return __builtin_fmaxf(a, b); }
 // v + (lane ^ 32) + ... + (lane ^ 1), the pairs and the order of the __shfl_xor butterfly from 32 down to 1

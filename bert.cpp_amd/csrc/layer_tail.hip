@@ -136,8 +136,14 @@ __device__ __forceinline__ f32x16 mfma16(const f16x8 &a, const f16x8 &b, const f
 // one phase of a launch that carries a window through all layers)
 // RAGGED: the block is rows tok0 .. tok0 + rows - 1 only (a window of whole sentences with fewer than 128 tokens; the rows behind
 // belong to another workgroup): the loads of the missing rows repeat the last one, their stores are skipped.
-template <int NT, int WT, bool RAGGED = false>
-__device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, const int tok0, const int rows, const int tid) {
+// HANDOVER (model_kernel.hip, full windows): the D waves (4..7) also hand out the rows they have just normalised as the operand fragments
+// the next layer's Q|K|V projection starts from — `xnext`, fragment q of lane (l31, hi) = features 16 q + 8 hi .. + 8 of token
+// tok0 + 32 (wave & 3) + l31, what qkv_attention2_body's projection wave `wave` loads from x for its slot 32 (wave & 3) + l31 — in
+// ADDITION to storing them (the next tail's residual, the pooling and the other routes read x).  The U waves leave `xnext` alone.
+template <int NT, int WT, bool RAGGED, bool HANDOVER>
+__device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, const int tok0, const int rows, const int tid,
+                                                [[maybe_unused]] f16x8 (&xnext)[8 * NT]) {
+    static_assert(!(HANDOVER && RAGGED), "a ragged window's rows are packed: its lanes are not the window phase's slots");
     constexpr bool Q4 = WT != GW_F16;
     constexpr int VMQ = Q4 ? 63 : 0;                          // (q4: no LDS-DMA in flight, nothing for a barrier to wait for)
     constexpr int H = 128 * NT, NBH = 2 * NT, NB = 4 * NT, NQ = 8 * NT, NYH = 4 * NT;
@@ -679,6 +685,12 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
         asm volatile("s_barrier" ::: "memory");                                   // [E0] every D wave has taken U's half of y in
         asm volatile("s_barrier" ::: "memory");                                   // [E1] D's rows are staged
         store_rows();
+        // (HANDOVER: the fragments are D's.  Named here as written — by no instruction — or the caller's loop carries whatever they held
+        // a layer ago through this whole branch: 8 NT x 4 registers that U does not have)
+        if constexpr (HANDOVER) {
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) asm volatile("" : "=v"(xnext[q]));
+        }
         return;
     } else {
         // =====================================================================================================
@@ -865,6 +877,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
                         for (int e = 0; e < 4; ++e)
                             o[4 * hq + e] = (_Float16)rounded_f32(__builtin_fmaf(acc2[n][8 * s + 4 * hq + e], gv[2 * s + hq][e] * rstd, __builtin_fmaf(gv[2 * s + hq][e], nmr, bv[2 * s + hq][e])));
                     *(f16x8 *)(S + q * 1024 + ((lane + 2 * q) & 63) * 16) = o;
+                    if constexpr (HANDOVER) xnext[q] = result_to_operand_fragment(o);
                 }
                 asm volatile("" ::: "memory");
             }
@@ -873,6 +886,12 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
         }
         store_rows();
     }
+}
+
+template <int NT, int WT, bool RAGGED = false>
+__device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, const int tok0, const int rows, const int tid) {
+    f16x8 unused[8 * NT];
+    layer_tail_body<NT, WT, RAGGED, false>(a, smem, tok0, rows, tid, unused);
 }
 
 template <int NT, int WT>

@@ -11,7 +11,8 @@
 // the two kernels' bodies unchanged (same arithmetic, same bits: tested) — and nothing ever puts the workgroups back in step.
 // The hand-overs (ctx from the attention waves to the tail, x from the tail to the next layer's projection waves) are plain
 // global stores and loads of the SAME workgroup: 96 KiB each, behind a workgroup-scope fence (one L1 per CU, shared by the
-// workgroup's waves: no invalidate needed outside threadgroup-split mode).  They do NOT stay inside the XCD's L2: 256
+// workgroup's waves: no invalidate needed outside threadgroup-split mode); on full windows x ALSO crosses in registers (the layer
+// loop below), so the next window phase does not wait for its own stores' round trip.  They do NOT stay inside the XCD's L2: 256
 // workgroups x 192 KiB = 48 MiB per layer against 32 MiB of L2, and every store leaves the L2 towards the fabric anyway —
 // measured 313 MB written and 1.06 GB of fabric traffic per launch (profiles/r3_pmc.txt), absorbed by the Infinity Cache at
 // about 1.3 TB/s: far from a limit, but not free.  What the single launch removes is the lockstep, not the bytes.
@@ -30,7 +31,7 @@
 
 namespace bert_hip {
 
-#ifdef BERT_HIP_MODEL_TIMELINE      // (tuning aid: tools/variant.sh tl model_kernel.hip "-DBERT_HIP_MODEL_TIMELINE -fno-slp-vectorize")
+#ifdef BERT_HIP_MODEL_TIMELINE      // (tuning aid: tools/variant.sh tl "-DBERT_HIP_MODEL_TIMELINE")
 // phase boundaries of every workgroup on the constant 100 MHz counter: [0] start, [1 + 2 l] window phase of layer l done, [2 + 2 l] its tail
 // phase done, [1 + 2 L] pooled
 static __device__ unsigned long long g_tl_model[1024 * 32];
@@ -92,32 +93,57 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
     };
     MK_STAMP(0);
     const int n_layer = rows > 0 ? m.n_layer : 0;    // (a window of empty sentences: nothing to compute, NaN rows from the pooling below)
-    for (int l = 0; l < n_layer; ++l) {
-        const ModelLayerArgs &L = m.layer[l];
-        int tid = thread_id();
-        {
-            Qkv2Args q;
-            q.x = m.x; q.w = L.wqkv; q.qs = nullptr; q.sc = nullptr; q.bias = L.bqkv; q.cu = m.cu; q.groups = RAGGED ? m.groups : nullptr; q.n_groups = nullptr;
-            q.out = m.ctx; q.n_head = m.n_head; q.n_sent = m.n_sent; q.spw = 1; q.slot_mask = m.slot_mask;
-            qkv_attention2_body<2 * NT, NT, GW_F16>(q, smem, window, tid);
-        }
-        // ctx is written (attention waves), every LDS access of the phase has returned: hand over to the tail
+    // A phase = the kernel's body on this workgroup's window.  Full windows (!RAGGED) tell the window phase so (FULL: its slots are the
+    // block's tokens, no look at cu) and, from the second layer on, hand it the hidden state in registers (XREGS / HANDOVER below).
+    auto window_phase = [&](const ModelLayerArgs &L, auto xregs_tag, const f16x8 *xf) __attribute__((always_inline)) {
+        const int tid = thread_id();
+        Qkv2Args q;
+        q.x = m.x; q.w = L.wqkv; q.qs = nullptr; q.sc = nullptr; q.bias = L.bqkv; q.cu = m.cu; q.groups = RAGGED ? m.groups : nullptr; q.n_groups = nullptr;
+        q.out = m.ctx; q.n_head = m.n_head; q.n_sent = m.n_sent; q.spw = 1; q.slot_mask = m.slot_mask;
+        qkv_attention2_body<2 * NT, NT, GW_F16, !RAGGED, decltype(xregs_tag)::value>(q, smem, window, tid, xf);
+    };
+    auto tail_phase = [&](const ModelLayerArgs &L, f16x8 (&xf)[8 * NT]) __attribute__((always_inline)) {
+        const int tid = thread_id();
+        TailArgs t;
+        t.ctx = m.ctx; t.x = m.x; t.wo = L.wo; t.w1p = L.w1p; t.w2p = L.w2p;
+        t.wo_qs = t.w1_qs = t.w2_qs = nullptr; t.wo_sc = t.w1_sc = t.w2_sc = nullptr;
+        t.bo = L.bo; t.g1 = L.g1; t.be1 = L.be1; t.b1 = L.b1; t.b2 = L.b2; t.g2 = L.g2; t.be2 = L.be2; t.out = m.x; t.I = m.I;
+        layer_tail_body<NT, GW_F16, RAGGED, !RAGGED>(t, smem, tok0, rows, tid, xf);
+    };
+    // Phase edge: everything the phase stored (ctx by the attention waves; x by all waves) is visible to the workgroup, every LDS access
+    // of the phase has returned (the next phase's first DMA pieces overwrite what the others were reading)
+    auto hand_over = [&]() __attribute__((always_inline)) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        MK_STAMP(1 + 2 * l);
-        tid = thread_id();
-        {
-            TailArgs t;
-            t.ctx = m.ctx; t.x = m.x; t.wo = L.wo; t.w1p = L.w1p; t.w2p = L.w2p;
-            t.wo_qs = t.w1_qs = t.w2_qs = nullptr; t.wo_sc = t.w1_sc = t.w2_sc = nullptr;
-            t.bo = L.bo; t.g1 = L.g1; t.be1 = L.be1; t.b1 = L.b1; t.b2 = L.b2; t.g2 = L.g2; t.be2 = L.be2; t.out = m.x; t.I = m.I;
-            layer_tail_body<NT, GW_F16, RAGGED>(t, smem, tok0, rows, tid);
+    };
+    if constexpr (RAGGED) {
+        for (int l = 0; l < n_layer; ++l) {
+            f16x8 none[8 * NT];                          // (no register hand-over: a ragged window's tail rows are packed, its slots are not)
+            window_phase(m.layer[l], std::false_type{}, nullptr);
+            hand_over();
+            MK_STAMP(1 + 2 * l);
+            tail_phase(m.layer[l], none);
+            hand_over();
+            MK_STAMP(2 + 2 * l);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        MK_STAMP(2 + 2 * l);
+    } else {
+        // Full windows: the tail's D waves 4..7 end with the rows of x they have just normalised in registers, and the same waves, as
+        // the next layer's projection waves, start from those rows — same lanes, same tokens, the f16 values that are stored: LayerNorm 2
+        // hands them over as operand fragments (layer_tail_body's HANDOVER) and the window phases of layers 1 .. L-1 load no x at all
+        // (the stores stay: the next tail's residual and the pooling read x).  The loop is rotated — layer 0's window phase in front,
+        // then tail(l) -> window(l + 1) per turn — so that the fragments are born and consumed inside ONE turn: declared outside, the
+        // U waves' path (which does not write them) would carry 96 registers round the loop and through the tail.
+        if (n_layer > 0) window_phase(m.layer[0], std::false_type{}, nullptr);
+        for (int l = 0; l < n_layer; ++l) {
+            hand_over();
+            MK_STAMP(1 + 2 * l);
+            f16x8 xf[8 * NT];
+            tail_phase(m.layer[l], xf);
+            hand_over();
+            MK_STAMP(2 + 2 * l);
+            if (l + 1 < n_layer) window_phase(m.layer[l + 1], std::true_type{}, xf);
+        }
     }
     // ---- mean-pool + L2 normalise of the window's sentences (pool_normalize.h: the pooling kernel's body and bits), while the
     // other workgroups are still in their layers: the rows were written by this workgroup and sit in the L2

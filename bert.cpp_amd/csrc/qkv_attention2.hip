@@ -94,8 +94,14 @@ __device__ __forceinline__ void q2_wait0_bias(f16x8 (&f)[2][3], f32x4 (&bq)[4], 
 // of expanding them into the ring slot the f16 form fills by LDS-DMA (same tile image, same MFMA sequence, same bits).
 // (the kernel's body as a device function of (arguments, the workgroup's LDS, window index): model_kernel.hip runs it as one
 // phase of a launch that carries a window through all layers)
-template <int KT, int GB, int WT>
-__device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *smem, const int window, const int tid) {
+// FULL (model_kernel.hip's full-window form): the window IS the 128-token block `window` — slot s is token 128 window + s, every key
+// belongs to every query — known without a look at `cu` (the caller vouches for it; `groups`, `spw`, `n_sent`, `slot_mask` are not read).
+// XREGS (with FULL): the projection waves (4..7) do not load their rows of the hidden state, the caller hands them over as the
+// fragments `xf` (layer_tail_body's HANDOVER: same wave, same lanes, same tokens); the other waves' `xf` is not read.
+template <int KT, int GB, int WT, bool FULL = false, bool XREGS = false>
+__device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *smem, const int window, const int tid,
+                                                    [[maybe_unused]] const f16x8 *xf = nullptr) {       // xf: [4 KT]
+    static_assert(FULL || !XREGS, "fragments handed over in registers: full windows only");
     constexpr bool Q4 = WT != GW_F16;
     constexpr int H = 64 * KT, NBAR = KT / GB, SLAB = GB * Q2_TILE, PPS = 3 * GB;   // PPS = DMA pieces per slab and wave
     static_assert(KT == 2 * GB && NBAR == 2, "");
@@ -131,22 +137,26 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
 
     // ---- the window: sentences first .. first+count-1, sentence j at slots [off_j, off_j + n_j)
     int first, count;
-    if (a.groups) {
-        if (a.n_groups && window >= *a.n_groups) {   // beyond the windows the device-side builder produced
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if constexpr (FULL) { first = window; count = 1; }
+    else {
+        if (a.groups) {
+            if (a.n_groups && window >= *a.n_groups) {   // beyond the windows the device-side builder produced
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                return;
+            }
+            const int2 g = a.groups[window];
+            first = g.x; count = g.y;
+        }
+        else { first = window * a.spw; count = min(a.spw, a.n_sent - first); }
+        if (count <= 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (never taken by the launcher's grids) the DMA must not outlive the workgroup
             return;
         }
-        const int2 g = a.groups[window];
-        first = g.x; count = g.y;
-    }
-    else { first = window * a.spw; count = min(a.spw, a.n_sent - first); }
-    if (count <= 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (never taken by the launcher's grids) the DMA must not outlive the workgroup
-        return;
     }
     const int slot = blk * 32 + l31;
     int gtok = -1, k0 = 0, k1 = 0;                            // this lane's slot: global token, key range of its sentence
-    {
+    if constexpr (FULL) { gtok = window * Q2_WIN + slot; k1 = Q2_WIN; }
+    else {
         // (uniform rule, no window list: spw = 128 / round16(max_len) sentences per window.  A sentence longer than the
         // promised max_len is cut to round16(max_len) slots here — it is the one that gets a NaN row from the length guard —
         // instead of pushing its window neighbours past slot 127, where their rows would never be written)
@@ -164,8 +174,11 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
         // rows of the hidden state as MFMA fragments (token = l31, k = 16 ks + 8 hi ..): B operand of the Q / K
         // projections, A operand of the V projection.  Empty slots read the window's first token (finite values).
         f16x8 bf[4 * KT];
-        {
-            const int gt = gtok >= 0 ? gtok : a.cu[first];
+        if constexpr (XREGS) {
+#pragma unroll
+            for (int ks = 0; ks < 4 * KT; ++ks) bf[ks] = xf[ks];
+        } else {
+            const int gt = FULL || gtok >= 0 ? gtok : a.cu[first];
             const half_t *xr = a.x + (size_t)gt * H + 8 * hi;
             // (untracked loads: the first barrier waits for them and for slab 0 only, slab 1 stays in flight)
 #pragma unroll
@@ -247,7 +260,9 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
                 F[par][i][2] = lds_read_b128<false, tt * Q2_TILE + 8192>(aS[2 * half + i]);
             }
         };
-        // x rows and slab 0 have landed (slab 1 may still be in flight)
+        // x rows and slab 0 have landed (slab 1 may still be in flight).  Outstanding, oldest first: slab 0 (PPS pieces), the 4 KT row
+        // loads, slab 1 (PPS pieces).  XREGS: slab 0, slab 1 and nothing between them (the rows came in registers, the caller's barrier
+        // in front of this phase waited for vmcnt(0)): the same count leaves the same slab in flight.
         [[maybe_unused]] const bool tl_sel = tid == 256;
         TL_STAMP_AT(tl_sel, 0);
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" : : "n"(Q4 ? 0 : PPS) : "memory");
@@ -498,21 +513,21 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
                 }
             }
         };
-        const bool fast = need == 0xFu && inner == 0xFu;        // wave-uniform
+        const bool fast = FULL || (need == 0xFu && inner == 0xFu);        // wave-uniform (FULL: known, the masked form is not instantiated)
         // the projection waves' barriers of head 0 (nothing to attend yet), then head h-1 is attended while head h is
         // projected, then the last head
         asm volatile("s_barrier" ::: "memory");
         asm volatile("s_barrier" ::: "memory");
         for (int h = 1; h < n_head; ++h) {
             if (h < 8) TL_STAMP_AT(tl_sel, 128 + 6 * h);
-            if (fast) attend(h - 1, std::true_type{}, std::true_type{}, h);
-            else attend(h - 1, std::true_type{}, std::false_type{}, h);
+            if (FULL || fast) attend(h - 1, std::true_type{}, std::true_type{}, h);
+            else if constexpr (!FULL) attend(h - 1, std::true_type{}, std::false_type{}, h);
             if (h < 8) TL_STAMP_AT(tl_sel, 128 + 6 * h + 5);
             asm volatile("s_barrier" ::: "memory");             // end of head h: it is published
         }
         TL_STAMP_AT(tl_sel, 190);
-        if (fast) attend(n_head - 1, std::false_type{}, std::true_type{}, 0);
-        else attend(n_head - 1, std::false_type{}, std::false_type{}, 0);
+        if (FULL || fast) attend(n_head - 1, std::false_type{}, std::true_type{}, 0);
+        else if constexpr (!FULL) attend(n_head - 1, std::false_type{}, std::false_type{}, 0);
         TL_STAMP_AT(tl_sel, 192);
         TL_STAMP_AT(tl_sel, 252);
         TL_REALTIME_AT(tl_sel, 253);
