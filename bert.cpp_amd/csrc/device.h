@@ -152,6 +152,10 @@ __device__ __forceinline__ f16x8 result_to_operand_fragment(const f16x8 &v) {
     asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\ts_nop 1" : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3));
     return __builtin_bit_cast(f16x8, u32x4{d0, d1, d2, d3});
 }
+// model_kernel.hip's window -> tail edge: where the last two heads' context fragments wait in LDS for the tail's waves (block b: 4 KiB at
+// + 4096 b) — behind the exchange area of the heads before them (nq KiB per block, from 0) and inside what both phases leave alone at the
+// edge: the tail's idle third ring slot / GELU area from 80 KiB on, the window phase's dead ring or dead Q/K/V copy
+constexpr int ctx_edge_offset(int nq) { return nq * 4096 > 80 * 1024 ? nq * 4096 : 80 * 1024; }
 __device__ __forceinline__ float xor32_sum(float v) { float a = v, b = v; xor32_pair(a, b); return a + b; }
 __device__ __forceinline__ float xor32_max(float v) { float a = v, b = v; xor32_pair(a, b); return __builtin_fmaxf(a, b); }
 // v + (lane ^ 32) + ... + (lane ^ 1), the pairs and the order of the __shfl_xor butterfly from 32 down to 1

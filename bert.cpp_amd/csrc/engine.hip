@@ -440,6 +440,16 @@ void Engine::set_option(const std::string &key, const std::string &value) {
     else if (key == "window_slots") set_window_slots(atoi(value.c_str()));      // (process-wide: 16, or 8 — see kernels.h)
     else if (key == "latency_tokens") { const int v = atoi(value.c_str()); if (v >= 32) latency_tokens_ = v; }
     else if (key == "one_launch") one_launch_ = value == "0" ? 0 : value == "2" ? 2 : 1;
+#ifdef BERT_HIP_TEST_ROUTES
+    // (libbert_test.so only) every half of the attention-context workspace becomes a NaN: a pass that still reads what it has not
+    // written itself shows it in its results
+    else if (key == "test_poison_ctx") {
+        (void)hipSetDevice(device());
+        (void)hipDeviceSynchronize();
+        if (ctx_.p) (void)hipMemset(ctx_.p, 0xFF, ctx_.bytes);
+        (void)hipDeviceSynchronize();
+    }
+#endif
     else if (key == "f32") f32_exact_ = value != "f16";       // f32 files: "exact" (f32 arithmetic, default) | "f16" (f16 operands, fused kernels)
     else if (key == "chunk_tokens") { const int v = atoi(value.c_str()); if (v > 0) chunk_tokens_ = v; }
     else if (key == "profile_replay") {

@@ -140,10 +140,13 @@ __device__ __forceinline__ f32x16 mfma16(const f16x8 &a, const f16x8 &b, const f
 // the next layer's Q|K|V projection starts from — `xnext`, fragment q of lane (l31, hi) = features 16 q + 8 hi .. + 8 of token
 // tok0 + 32 (wave & 3) + l31, what qkv_attention2_body's projection wave `wave` loads from x for its slot 32 (wave & 3) + l31 — in
 // ADDITION to storing them (the next tail's residual, the pooling and the other routes read x).  The U waves leave `xnext` alone.
-template <int NT, int WT, bool RAGGED, bool HANDOVER>
+// CTXREGS (model_kernel.hip, full windows): `a.ctx` is not read.  The caller hands the attention context over as the operand fragments
+// `cf` (qkv_attention2_body's CTXREGS: same waves, same lanes, same tokens); the last two heads' four are in LDS at ctx_edge_offset.
+template <int NT, int WT, bool RAGGED, bool HANDOVER, bool CTXREGS = false>
 __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, const int tok0, const int rows, const int tid,
-                                                [[maybe_unused]] f16x8 (&xnext)[8 * NT]) {
+                                                [[maybe_unused]] f16x8 (&xnext)[8 * NT], [[maybe_unused]] const f16x8 *cf = nullptr) {
     static_assert(!(HANDOVER && RAGGED), "a ragged window's rows are packed: its lanes are not the window phase's slots");
+    static_assert(!(CTXREGS && RAGGED), "a ragged window's rows are packed: its lanes are not the attention waves' queries");
     constexpr bool Q4 = WT != GW_F16;
     constexpr int VMQ = Q4 ? 63 : 0;                          // (q4: no LDS-DMA in flight, nothing for a barrier to wait for)
     constexpr int H = 128 * NT, NBH = 2 * NT, NB = 4 * NT, NQ = 8 * NT, NYH = 4 * NT;
@@ -201,7 +204,21 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
     }
     // attention context of the pair's tokens as B fragments, straight into registers (k order as stored)
     f16x8 bf[NQ];
-    {
+    // (CTXREGS) the last two heads' four crossed in LDS.  Where the area lies in G (H = 384), which nothing writes before the feed-forward
+    // loop, they STAY there during the out-projection: each feature block reads them by hand in its last interval, a pair in front of each of
+    // the last two fragment groups, whose waits retire them (CTX_LATE).  Held from here on they are the registers the out-projection does not
+    // have: one fragment went to scratch and came back inside the counted intervals.  In ringD's third slot (H = 256: interval 0 requests
+    // a tile into it) all four are taken here, in front of the first barrier.
+    constexpr bool CTX_LATE = CTXREGS && ctx_edge_offset(NQ) >= 6 * LT_TILE && ctx_edge_offset(NQ) + 16384 <= 6 * LT_TILE + 32768;
+    if constexpr (CTXREGS) {
+        static_assert(ctx_edge_offset(NQ) >= 5 * LT_TILE && ctx_edge_offset(NQ) + 16384 <= 6 * LT_TILE + 32768,
+                      "the edge area: ringD's third slot or G, where the prologue's DMA and parameter writes do not reach");
+#pragma unroll
+        for (int q = 0; q < NQ - 4; ++q) bf[q] = cf[q];
+        const char *const er = smem + ctx_edge_offset(NQ) + t * 4096 + lane * 16;
+#pragma unroll
+        for (int q = 0; q < (CTX_LATE ? 0 : 4); ++q) bf[NQ - 4 + q] = *(const f16x8 *)(er + q * 1024);      // (the first barrier waits for them)
+    } else {
         const half_t *cw = a.ctx + (size_t)row_l * H + 8 * hi;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) bf[q] = *(const f16x8 *)(cw + 16 * q);
@@ -333,6 +350,11 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
         }
 #pragma unroll
     for (int b = 0; b < NBH; ++b) asm volatile("" : "+v"(accp[b]));     // (made here: left alone the compiler keeps x alive and converts it block by block)
+    if constexpr (CTXREGS) {    // (values of this phase from here on: a copy where the window phase's register does not suit, not a spill)
+#pragma unroll
+        for (int q = 0; q < (CTX_LATE ? NQ - 4 : NQ); ++q) asm volatile("" : "+v"(bf[q]));
+    }
+    [[maybe_unused]] const unsigned aEdge = CTX_LATE ? lds_addr(smem) + (unsigned)(ctx_edge_offset(NQ) + t * 4096 + lane * 16) : 0u;
     __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0), visible to the compiler (see the note in U's branch)
     static_for<P>([&](auto p_tag) __attribute__((always_inline)) {
         constexpr int p = decltype(p_tag)::value, n3 = p / NT, q = p % NT, p2 = p + 2;
@@ -384,16 +406,26 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
         wait_frags<4>(Fa);
         mm(Fa, 8 * q + 0);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (CTX_LATE && q == NT - 1) {     // (older than Fa's four reads: the counts below stand)
+            bf[NQ - 4] = lds_read_b128<true, 0>(aEdge);
+            bf[NQ - 3] = lds_read_b128<true, 1024>(aEdge);
+        }
         rd(bB, 0, Fa);
         wait_frags<4>(Fb);
+        if constexpr (CTX_LATE && q == NT - 1) { landed(bf[NQ - 4]); landed(bf[NQ - 3]); }
         mm(Fb, 8 * q + 2);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (CTX_LATE && q == NT - 1) {     // (older than Fb's four reads: the counts below stand)
+            bf[NQ - 2] = lds_read_b128<true, 2048>(aEdge);
+            bf[NQ - 1] = lds_read_b128<true, 3072>(aEdge);
+        }
         rd(bB, 1, Fb);
         if constexpr (Q4) { q4_turn(); __builtin_amdgcn_sched_barrier(0); }
         wait_frags<4 + QW>(Fa);
         mm(Fa, 8 * q + 4);
         __builtin_amdgcn_sched_barrier(0);
         wait_frags<0>(Fb);
+        if constexpr (CTX_LATE && q == NT - 1) { landed(bf[NQ - 2]); landed(bf[NQ - 1]); }
         mm(Fb, 8 * q + 6);
         __builtin_amdgcn_sched_barrier(0);
         pre_close();

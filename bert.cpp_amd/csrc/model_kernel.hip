@@ -11,10 +11,12 @@
 // the two kernels' bodies unchanged (same arithmetic, same bits: tested) — and nothing ever puts the workgroups back in step.
 // The hand-overs (ctx from the attention waves to the tail, x from the tail to the next layer's projection waves) are plain
 // global stores and loads of the SAME workgroup: 96 KiB each, behind a workgroup-scope fence (one L1 per CU, shared by the
-// workgroup's waves: no invalidate needed outside threadgroup-split mode); on full windows x ALSO crosses in registers (the layer
-// loop below), so the next window phase does not wait for its own stores' round trip.  They do NOT stay inside the XCD's L2: 256
+// workgroup's waves: no invalidate needed outside threadgroup-split mode); on full windows x ALSO crosses in registers and ctx crosses
+// ONLY on chip, in registers and through LDS (the layer loop below), so neither phase waits for a round trip of its own data, and no ctx
+// is stored at all.  The global hand-overs (the ragged form's both, the full form's x stores) do NOT stay inside the XCD's L2: 256
 // workgroups x 192 KiB = 48 MiB per layer against 32 MiB of L2, and every store leaves the L2 towards the fabric anyway —
-// measured 313 MB written and 1.06 GB of fabric traffic per launch (profiles/r3_pmc.txt), absorbed by the Infinity Cache at
+// measured 313 MB written and 1.06 GB of fabric traffic per launch with both edges through memory (profiles/r3_pmc.txt), 164 MB and
+// 0.52 GB for the full form as it stands (profiles/traffic.json), absorbed by the Infinity Cache at
 // about 1.3 TB/s: far from a limit, but not free.  What the single launch removes is the lockstep, not the bytes.
 // Full form only: the kernel trusts n_tokens = 128 n_sentences to mean "every sentence is exactly 128 tokens"; that holds
 // whenever the caller's max_len promise (<= 128) does.  A batch that breaks it is flagged by the pooling guard (status word),
@@ -28,6 +30,8 @@
 #include "layer_tail.hip"
 #undef BERT_HIP_PHASES_ONLY
 #include "pool_normalize.h"
+
+#include <cstdlib>
 
 namespace bert_hip {
 
@@ -95,23 +99,26 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
     const int n_layer = rows > 0 ? m.n_layer : 0;    // (a window of empty sentences: nothing to compute, NaN rows from the pooling below)
     // A phase = the kernel's body on this workgroup's window.  Full windows (!RAGGED) tell the window phase so (FULL: its slots are the
     // block's tokens, no look at cu) and, from the second layer on, hand it the hidden state in registers (XREGS / HANDOVER below).
-    auto window_phase = [&](const ModelLayerArgs &L, auto xregs_tag, const f16x8 *xf) __attribute__((always_inline)) {
+    auto window_phase = [&](const ModelLayerArgs &L, auto xregs_tag, const f16x8 *xf, f16x8 *cf) __attribute__((always_inline)) {
         const int tid = thread_id();
         Qkv2Args q;
         q.x = m.x; q.w = L.wqkv; q.qs = nullptr; q.sc = nullptr; q.bias = L.bqkv; q.cu = m.cu; q.groups = RAGGED ? m.groups : nullptr; q.n_groups = nullptr;
         q.out = m.ctx; q.n_head = m.n_head; q.n_sent = m.n_sent; q.spw = 1; q.slot_mask = m.slot_mask;
-        qkv_attention2_body<2 * NT, NT, GW_F16, !RAGGED, decltype(xregs_tag)::value>(q, smem, window, tid, xf);
+        qkv_attention2_body<2 * NT, NT, GW_F16, !RAGGED, decltype(xregs_tag)::value, !RAGGED>(q, smem, window, tid, xf, cf);
     };
-    auto tail_phase = [&](const ModelLayerArgs &L, f16x8 (&xf)[8 * NT]) __attribute__((always_inline)) {
+    auto tail_phase = [&](const ModelLayerArgs &L, f16x8 (&xf)[8 * NT], const f16x8 *cf) __attribute__((always_inline)) {
         const int tid = thread_id();
         TailArgs t;
         t.ctx = m.ctx; t.x = m.x; t.wo = L.wo; t.w1p = L.w1p; t.w2p = L.w2p;
         t.wo_qs = t.w1_qs = t.w2_qs = nullptr; t.wo_sc = t.w1_sc = t.w2_sc = nullptr;
         t.bo = L.bo; t.g1 = L.g1; t.be1 = L.be1; t.b1 = L.b1; t.b2 = L.b2; t.g2 = L.g2; t.be2 = L.be2; t.out = m.x; t.I = m.I;
-        layer_tail_body<NT, GW_F16, RAGGED, !RAGGED>(t, smem, tok0, rows, tid, xf);
+        layer_tail_body<NT, GW_F16, RAGGED, !RAGGED, !RAGGED>(t, smem, tok0, rows, tid, xf, cf);
     };
-    // Phase edge: everything the phase stored (ctx by the attention waves; x by all waves) is visible to the workgroup, every LDS access
-    // of the phase has returned (the next phase's first DMA pieces overwrite what the others were reading)
+    // Phase edge: everything the phase stored (ragged windows: ctx by the attention waves; x by all waves) is visible to the workgroup, every
+    // LDS access of the phase has returned (the next phase's first DMA pieces overwrite what the others were reading).  On full windows
+    // the window -> tail edge has no fresh global store to wait for (ctx crosses on chip, below): there the wait and the barrier order the
+    // attention waves' LDS writes of the last head's fragments before the tail's reads, and the fence keeps the compiler from moving
+    // either across it.
     auto hand_over = [&]() __attribute__((always_inline)) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -120,10 +127,10 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
     if constexpr (RAGGED) {
         for (int l = 0; l < n_layer; ++l) {
             f16x8 none[8 * NT];                          // (no register hand-over: a ragged window's tail rows are packed, its slots are not)
-            window_phase(m.layer[l], std::false_type{}, nullptr);
+            window_phase(m.layer[l], std::false_type{}, nullptr, nullptr);
             hand_over();
             MK_STAMP(1 + 2 * l);
-            tail_phase(m.layer[l], none);
+            tail_phase(m.layer[l], none, nullptr);
             hand_over();
             MK_STAMP(2 + 2 * l);
         }
@@ -134,15 +141,38 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
         // (the stores stay: the next tail's residual and the pooling read x).  The loop is rotated — layer 0's window phase in front,
         // then tail(l) -> window(l + 1) per turn — so that the fragments are born and consumed inside ONE turn: declared outside, the
         // U waves' path (which does not write them) would carry 96 registers round the loop and through the tail.
-        if (n_layer > 0) window_phase(m.layer[0], std::false_type{}, nullptr);
+        //
+        // The other edge, window -> tail, crosses on chip too: no ctx is stored and none is loaded (m.ctx is the ragged form's).  Attention wave a
+        // (0..3) and the tail's U wave of pair a are the same wave with the same tokens: it keeps every head's rounded result as the out-projection's
+        // operand fragments `cf` (qkv_attention2_body's CTXREGS) and the tail starts from them (layer_tail_body's CTXREGS).  The pair's D wave
+        // (4 + a, a projection wave in the window phase) gets the same fragments through LDS.  Map of the edge (KiB; H = 384 | 256):
+        //     window phase          ring [0, 108 | 72)   Q/K/V copy 0 [108, 132.25 | 72, 96.25)   copy 1 (the last head's) behind it
+        //     exchange, older heads [0, 96 | 64): block b at 8 NT b, fragment q of lane l at + q + 16 l bytes.  Written behind the barrier that
+        //                           publishes the last head — the ring is dead, and in this form that barrier waits for the dead prefetches as
+        //                           well — and read by the D waves, idle by then, behind one more barrier [X] while the last head is attended
+        //     last two heads' four  ctx_edge_offset = [96, 112 | 80, 96): block b at + 4 b; dead ring and dead copy 0 | dead copy 0 in the window phase;
+        //                           the tail's GELU area | third slot of ringD, which get their first bytes behind the tail's first barrier.  The
+        //                           attention wave writes them in front of [X] and at the end of the window phase (it has no registers to keep
+        //                           them through the last head's attention); both waves of the pair read them in the tail's prologue
+        //     tail phase prologue   DMA into ringU / ringD slots 0, 1 = [0, 32) and [48, 80), parameters behind 128: all of it behind the
+        //                           edge's barrier, when every D wave holds the exchange area's fragments in registers (its reads are
+        //                           waited for inside the window phase)
+        // `cf` is written by every wave in the window phase and read by every wave in the tail, so it lives across the back edge for what it
+        // is; where no window phase follows it is named as written, or the last tail would carry the fragments it has consumed.
+        f16x8 cf[8 * NT];
+        if (n_layer > 0) window_phase(m.layer[0], std::false_type{}, nullptr, cf);
         for (int l = 0; l < n_layer; ++l) {
             hand_over();
             MK_STAMP(1 + 2 * l);
             f16x8 xf[8 * NT];
-            tail_phase(m.layer[l], xf);
+            tail_phase(m.layer[l], xf, cf);
             hand_over();
             MK_STAMP(2 + 2 * l);
-            if (l + 1 < n_layer) window_phase(m.layer[l + 1], std::true_type{}, xf);
+            if (l + 1 < n_layer) window_phase(m.layer[l + 1], std::true_type{}, xf, cf);
+            else {
+#pragma unroll
+                for (int q = 0; q < 8 * NT; ++q) asm volatile("" : "=v"(cf[q]));
+            }
         }
     }
     // ---- mean-pool + L2 normalise of the window's sentences (pool_normalize.h: the pooling kernel's body and bits), while the
@@ -189,6 +219,8 @@ void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x
     const size_t lds_q = (size_t)3 * GB * Q2_TILE + 2 * (2 * Q2_WIN * 64 + 32 * Q2_VT_LD * 2) + (size_t)2 * H * sizeof(float);
     const size_t lds = std::max(lds_q, layer_tail_lds(H, m.I));
     const bool full = (long long)n_sentences * 128 == n_tokens;      // (with no sentence over 128 tokens: every window is one whole sentence)
+    // (the full form keeps two context fragments per head in a register array sized by H: model_kernel_supported's d_head = 32)
+    if (n_head * 32 != H) { fprintf(stderr, "launch_model_kernel: n_head %d x 32 != H %d\n", n_head, H); abort(); }
     const int grid = full || !groups ? n_sentences : n_groups;
     static DeviceFlags configured[4];
     auto go = [&](auto kernel, int which) {

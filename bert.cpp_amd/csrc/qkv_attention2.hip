@@ -98,10 +98,19 @@ __device__ __forceinline__ void q2_wait0_bias(f16x8 (&f)[2][3], f32x4 (&bq)[4], 
 // belongs to every query — known without a look at `cu` (the caller vouches for it; `groups`, `spw`, `n_sent`, `slot_mask` are not read).
 // XREGS (with FULL): the projection waves (4..7) do not load their rows of the hidden state, the caller hands them over as the
 // fragments `xf` (layer_tail_body's HANDOVER: same wave, same lanes, same tokens); the other waves' `xf` is not read.
-template <int KT, int GB, int WT, bool FULL = false, bool XREGS = false>
+// CTXREGS (with FULL, f16 weights, n_head = 2 KT): the attention context is not stored to `a.out`.  Attention wave `a` keeps the rounded
+// result of every head as the two operand fragments of the out-projection — `cf`, fragment q of lane (l31, hi) = features 16 q + 8 hi .. + 8
+// of token 128 window + 32 a + l31, what layer_tail_body's waves of pair `a` load from ctx — and the projection wave of the same token block
+// (4 + a: the tail's D wave of the pair) ends with the same fragments.  All but the last two heads' four: those wait for both waves in LDS
+// (ctx_edge_offset; the attention wave has no registers for them beside the last head's attention), so every wave leaves with
+// cf[0 .. 4 KT - 5] written (LDS map of the edge: model_kernel.hip).
+template <int KT, int GB, int WT, bool FULL = false, bool XREGS = false, bool CTXREGS = false>
 __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *smem, const int window, const int tid,
-                                                    [[maybe_unused]] const f16x8 *xf = nullptr) {       // xf: [4 KT]
+                                                    [[maybe_unused]] const f16x8 *xf = nullptr,         // xf: [4 KT]
+                                                    [[maybe_unused]] f16x8 *cf = nullptr) {             // cf: [4 KT]
     static_assert(FULL || !XREGS, "fragments handed over in registers: full windows only");
+    static_assert(!CTXREGS || (FULL && WT == GW_F16), "the context in registers: full windows, f16 weights");
+    constexpr int NCF = 4 * KT;                               // context fragments of a token block (two per head); a block's exchange area: NCF KiB
     constexpr bool Q4 = WT != GW_F16;
     constexpr int H = 64 * KT, NBAR = KT / GB, SLAB = GB * Q2_TILE, PPS = 3 * GB;   // PPS = DMA pieces per slab and wave
     static_assert(KT == 2 * GB && NBAR == 2, "");
@@ -114,7 +123,15 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
     const int blk = wave & 3;                                 // token block (projection) / query block (attention)
+    // (CTXREGS: both wave groups count their heads — and with them their barriers — by this one value; that it is 2 KT, which the
+    // fragment indices assume, is d_head = 32: launch_model_kernel checks it)
     const int n_head = a.n_head;
+    if constexpr (CTXREGS) {
+        // the edge's LDS areas inside what this phase has left alone by then: the exchange area in the ring; the last two heads' 16 KiB behind
+        // it, in the dead ring and the dead Q/K/V copy 0 (the last head, an odd one, lives in copy 1)
+        static_assert(NCF * 4096 <= 3 * SLAB && ctx_edge_offset(NCF) >= NCF * 4096 && ctx_edge_offset(NCF) + 16384 <= 3 * SLAB + QKV_BYTES &&
+                      ((2 * KT - 1) & 1) == 1, "the context exchange does not fit the window phase's LDS map");
+    }
     TL_STAMP_AT(tid == 256, 120);
     TL_REALTIME_AT(tid == 256, 121);
     TL_STAMP_AT(tid == 0, 250);
@@ -388,14 +405,36 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
             // most: they finished head h-2 before they passed the end of head h-1).  One barrier publishes them and opens the
             // next head's first slab; in flight behind it: this wave's pieces of the next head's second slab
             if (h < 8) TL_STAMP_AT(tl_sel, 2 + 6 * h + 4);
+            if constexpr (CTXREGS) {
+                // (the last head's barrier also waits for the dead prefetches: behind it the whole ring belongs to the context exchange)
+                if (h + 1 == n_head) dma_barrier<0>(); else dma_barrier<PPS>();
+            } else
             dma_barrier<Q4 ? 63 : PPS>();
             if (h < 8) TL_STAMP_AT(tl_sel, 2 + 6 * h + 5);
+            if constexpr (CTXREGS) {
+                // (no read behind the last head: the attention waves are writing the exchange area there)
+                if (h + 1 < n_head) {
+                    rslot = rslot == 2 ? 0 : rslot + 1;
+                    set_slot();
+                    read_half(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+                }
+            } else {
             rslot = rslot == 2 ? 0 : rslot + 1;
             set_slot();
             read_half(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            }
         }
         TL_STAMP_AT(tl_sel, 60);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the dead prefetches must not outlive the LDS allocation
+        if constexpr (!CTXREGS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the dead prefetches must not outlive the LDS allocation
+        if constexpr (CTXREGS) {
+            // nothing left to project: while the last head is attended, take in the context fragments of the heads before it, which
+            // the attention wave of this token block has put into the ring
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // [X] the exchange area is written
+            const char *const xr = smem + blk * (NCF * 1024) + lane * 16;
+#pragma unroll
+            for (int q = 0; q < NCF - 4; ++q) cf[q] = *(const f16x8 *)(xr + q * 1024);
+            __builtin_amdgcn_s_waitcnt(0xc07f);               // lgkmcnt(0), visible to the compiler (layer_tail.hip: the note in U's branch)
+        }
     } else {
         // =============================== attention wave: query block `blk` ===============================
         // key tiles by class, the same for every head: needed by some query of the block / inside every query's sentence
@@ -417,11 +456,20 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
 
         if constexpr (Q2_PRIO > 0) __builtin_amdgcn_s_setprio(Q2_PRIO);
         [[maybe_unused]] const bool tl_sel = tid == 0;
+        // (CTXREGS: the head loop writes two fragments per turn; named here as written, or the values of a layer ago stay alive up to there)
+        if constexpr (CTXREGS) {
+#pragma unroll
+            for (int q = 0; q < NCF - 4; ++q) asm volatile("" : "=v"(cf[q]));
+        }
         // attention of head hh (copy hh & 1 of Q / K / V^T).  WB: the slab barrier of the head the projection waves work on
         // meanwhile is executed here, after step Q2_PM
         // FAST: every key tile is needed and inside every query's sentence (full windows): straight-line code, no masks
-        auto attend = [&](int hh, auto wb_tag, auto fast_tag, int tb) __attribute__((always_inline)) {
+        // (CTXREGS) TO: where the head's context goes — 0: cf[2 hh], cf[2 hh + 1], hh < 2 KT - 2 (the head loop); 1: pen0, pen1 (the head
+        // before the last: on its way to LDS); 2: the LDS area of the edge (the last head)
+        [[maybe_unused]] f16x8 pen0, pen1;
+        auto attend = [&](int hh, auto wb_tag, auto fast_tag, int tb, [[maybe_unused]] auto to_tag) __attribute__((always_inline)) {
             constexpr bool WB = decltype(wb_tag)::value, FAST = decltype(fast_tag)::value;
+            [[maybe_unused]] constexpr int TO = decltype(to_tag)::value;
             const char *QS = QKV + (hh & 1) * QKV_BYTES, *KS = QS + Q2_WIN * 64;
             const half_t *VT = (const half_t *)(KS + Q2_WIN * 64);
             f32x16 s[4];
@@ -501,6 +549,32 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
             }
             // ---- normalise, store
             psum = xor32_sum(psum);
+            if constexpr (CTXREGS) {
+                // the f16 values the other forms store, as the operand fragments 2 hh, 2 hh + 1 of the out-projection (registers 0..7 /
+                // 8..15 of `o` are result fragments of k-steps 0 / 1 of the head's 32 features).  In the head loop hh is wave-uniform: a
+                // branch per head index around the two fragments' moves, no indexed register access
+                const float inv = 1.0f / psum;
+                f16x8 r0, r1;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { r0[e] = (_Float16)rounded_f32(o[e] * inv); r1[e] = (_Float16)rounded_f32(o[8 + e] * inv); }
+                r0 = result_to_operand_fragment(r0);
+                r1 = result_to_operand_fragment(r1);
+                if constexpr (TO == 0)
+                    static_for<2 * KT - 2>([&](auto i_tag) __attribute__((always_inline)) {
+                        constexpr int i = decltype(i_tag)::value;
+                        if (hh == i) {
+                            cf[2 * i] = r0; cf[2 * i + 1] = r1;
+                            asm volatile("" : "+v"(cf[2 * i]), "+v"(cf[2 * i + 1]));      // (made here: not a select per head index)
+                        }
+                    });
+                else if constexpr (TO == 1) { pen0 = r0; pen1 = r1; }
+                else {
+                    // behind the head before it (below), where the tail phase's prologue writes nothing; the caller's barrier publishes them
+                    char *const ew = smem + ctx_edge_offset(NCF) + blk * 4096 + lane * 16;
+                    *(f16x8 *)(ew + 2048) = r0;
+                    *(f16x8 *)(ew + 3072) = r1;
+                }
+            } else
             if (gtok >= 0) {
                 const float inv = 1.0f / psum;
                 half_t *op = a.out + (size_t)gtok * H + hh * 32;
@@ -518,16 +592,37 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
         // projected, then the last head
         asm volatile("s_barrier" ::: "memory");
         asm volatile("s_barrier" ::: "memory");
-        for (int h = 1; h < n_head; ++h) {
+        using TO0 = std::integral_constant<int, 0>;
+        // (CTXREGS: the loop's last turn apart — its two fragments are not carried round the loop)
+        for (int h = 1; h < (CTXREGS ? n_head - 1 : n_head); ++h) {
             if (h < 8) TL_STAMP_AT(tl_sel, 128 + 6 * h);
-            if (FULL || fast) attend(h - 1, std::true_type{}, std::true_type{}, h);
-            else if constexpr (!FULL) attend(h - 1, std::true_type{}, std::false_type{}, h);
+            if (FULL || fast) attend(h - 1, std::true_type{}, std::true_type{}, h, TO0{});
+            else if constexpr (!FULL) attend(h - 1, std::true_type{}, std::false_type{}, h, TO0{});
             if (h < 8) TL_STAMP_AT(tl_sel, 128 + 6 * h + 5);
             asm volatile("s_barrier" ::: "memory");             // end of head h: it is published
         }
+        if constexpr (CTXREGS) {
+            if (n_head - 1 < 8) TL_STAMP_AT(tl_sel, 128 + 6 * (n_head - 1));
+            attend(n_head - 2, std::true_type{}, std::true_type{}, n_head - 1, std::integral_constant<int, 1>{});
+            if (n_head - 1 < 8) TL_STAMP_AT(tl_sel, 128 + 6 * (n_head - 1) + 5);
+            asm volatile("s_barrier" ::: "memory");             // end of the last head: it is published
+        }
         TL_STAMP_AT(tl_sel, 190);
-        if (FULL || fast) attend(n_head - 1, std::false_type{}, std::true_type{}, 0);
-        else if constexpr (!FULL) attend(n_head - 1, std::false_type{}, std::false_type{}, 0);
+        if constexpr (CTXREGS) {
+            // the ring is dead (the last head's barrier waited for every piece): the heads attended so far go to the projection wave of
+            // this token block through it — block b owns NCF KiB, fragment q of lane l at q KiB + 16 l — which reads them during the last head
+            char *const xw = smem + blk * (NCF * 1024) + lane * 16;
+#pragma unroll
+            for (int q = 0; q < NCF - 4; ++q) *(f16x8 *)(xw + q * 1024) = cf[q];
+            // (the head before the last: to where the last head's will go)
+            char *const ew = smem + ctx_edge_offset(NCF) + blk * 4096 + lane * 16;
+            *(f16x8 *)ew = pen0;
+            *(f16x8 *)(ew + 1024) = pen1;
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");          // [X]
+        }
+        if constexpr (CTXREGS) attend(n_head - 1, std::false_type{}, std::true_type{}, 0, std::integral_constant<int, 2>{});
+        else if (FULL || fast) attend(n_head - 1, std::false_type{}, std::true_type{}, 0, TO0{});
+        else if constexpr (!FULL) attend(n_head - 1, std::false_type{}, std::false_type{}, 0, TO0{});
         TL_STAMP_AT(tl_sel, 192);
         TL_STAMP_AT(tl_sel, 252);
         TL_REALTIME_AT(tl_sel, 253);
