@@ -293,7 +293,7 @@ __device__ __forceinline__ void layernorm_scale(float s1, float s2, float inv_h,
 
 // ---- q4 blocks -> f16 tiles.  A thread expands one block of 32 weights (16 bytes of nibbles: byte j = element j | element
 // j + 16 << 4; f16 d, or f16 {d, m}) into four 16-byte chunks of its row: v_perm_b32 builds (1024 + q) half pairs, packed f16
-// math applies (q - 8) d or q d + m — the values the f16 image holds (engine.hip row_to_f16).
+// math applies (q - 8) d or q d + m — the values the f16 image holds (weights.cpp row_to_f16).
 struct RawBlock { uint4 q; unsigned sc; };
 template <int WT>
 __device__ __forceinline__ RawBlock q4_load_block(const uint4 *qs, const void *sc, size_t index) {
@@ -328,7 +328,7 @@ struct Q4Expansion {
         else asm volatile("s_mov_b32 %0, 0x64006400" : "=s"(offb));                    // 1024, 1024
         off = __builtin_bit_cast(f16x2, offb);
     }
-    // the four weights of the low (high) nibbles of `word`: two f16 pairs.  q4_1: q d + m rounded once (engine.hip row_to_f16).
+    // the four weights of the low (high) nibbles of `word`: two f16 pairs.  q4_1: q d + m rounded once (weights.cpp row_to_f16).
     // Q_FIRST: the operand order of that fma — the same value either way, but each caller's machine code keeps its own order.
     template <bool Q_FIRST>
     __device__ __forceinline__ void four(unsigned word, bool high, unsigned &o0, unsigned &o1) const {

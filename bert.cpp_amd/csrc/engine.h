@@ -1,68 +1,24 @@
 // engine.h — device side of a bert_ctx: HBM-resident weights, workspace, and the launch sequence
 // of the forward pass.  Replaces the reference's ggml arena + per-sentence graph build + execute
-// (reference bert.cpp:730-941, sizing :680-713) with a fixed kernel sequence (2 + 2*L launches on the fused path) over a packed
-// variable-length batch.
+// (reference bert.cpp:730-941, sizing :680-713) with a fixed kernel sequence over a packed variable-length batch: by default
+// one launch for all layers behind the embedding kernel, else two fused launches per layer (plan() in engine.hip picks the route).
+// The weights are weights.h's, the switches options.h's, the per-kernel times profiler.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <functional>
-#include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "kernels.h"
 #include "model_file.h"
+#include "options.h"
+#include "profiler.h"
+#include "weights.h"
 
 namespace bert_hip {
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf();
-    bool alloc(size_t n, std::string &err);                       // zero-filled
-    bool upload(const void *src, size_t n, std::string &err);     // alloc + H2D
-    bool ensure(size_t n, std::string &err);                      // grow only
-    template <class T> T *as() const { return (T *)p; }
-};
-
-// Owns the HBM image of one weight matrix in the layouts kernels.h describes.
-struct GemmWeightStore {
-    GemmWeight w;
-    DevBuf w16, w16p, qs, sc, naive16, w32;
-    bool mfma_ok = false;
-    // rows: list of (file tensor) stacked along N (one entry, or q|k|v).  All share type and K.
-    // want_kperm: also build GemmWeight::w16p (f16 images only); expand_q4: q4_0 / q4_1 tensors become an f16 image at
-    // load (default for the engine) instead of the nibble / scale planes of the fused-dequant kernels
-    // want_f32: f32 tensors also keep their own f32 rows (GemmWeight::w32, the f32 route)
-    bool build(const std::vector<const HostTensor *> &rows, bool want_naive, std::string &err, bool want_kperm = false,
-               bool expand_q4 = false, bool want_f32 = false);
-    // LayerNorm folded into a mat-mul that consumes LayerNorm(u; gamma, beta) (kernels.h GemmLnFold): the f16 image of
-    // W diag(gamma) (this store) and the weight side of the statistics k-step, [N][16] f16: s_hi s_lo s_hi c_hi c_lo c_hi 0..
-    // with s[n] = sum_k W'[n][k], c[n] = sum_k beta[k] W[n][k] + bias[n]
-    bool build_ln_fold(const std::vector<const HostTensor *> &rows, const float *gamma, const float *beta, const float *bias, DevBuf &waug, std::string &err);
-};
-
-struct LayerWeights {
-    GemmWeightStore qkv, o, ffi, ffo;
-    // q4 files with the default BERT_HIP_Q4=expand: the stacked Q | K | V matrix ALSO as 4-bit planes when its f16 image
-    // (3 H x H x 2 bytes) cannot stay in an XCD's 4 MiB L2 beside the activation tiles in flight — gemm256's persistent walk
-    // then re-fetches the f16 image every round (2.40 GB per launch at bert-base dims against 0.81 GB with the planes, which
-    // give the same bits and are 1-3 % faster on that launch: DESIGN.md §3).  Used by the QKV mat-mul of the gemm256 route only.
-    GemmWeightStore qkv_q4;
-    DevBuf qkv_b, o_b, ffi_b, ffo_b, ln_att_w, ln_att_b, ln_out_w, ln_out_b;
-    // LayerNorm folded into the H = 768 mat-muls (kernels.h GemmLnFold): the up-projection with this layer's attention LayerNorm
-    // folded in, the Q|K|V projection with the PREVIOUS layer's output LayerNorm (layers >= 1), their statistics columns, and
-    // the packed (gamma, beta + bias) pairs of the two residual mat-muls (attention output: the previous layer's output LayerNorm)
-    GemmWeightStore ffi_fold, qkv_fold;
-    DevBuf ffi_waug, qkv_waug, o_gb, ffo_gb;
-    bool fold_ok = false;
-};
-
-struct KernelStat { int launches = 0; double ms = 0.0; double flops = 0.0; };
 
 class Engine {
 public:
@@ -93,7 +49,7 @@ public:
     // device-side validation (sentence lengths vs max_len): synchronises, returns and clears the status word
     int check(std::string &err);
     void set_option(const std::string &key, const std::string &value);
-    void profile_enable(bool on);
+    void profile_enable(bool on) { prof_.enable(on); }
     std::string profile_report();
     // a launch of another part of the library (the index kernels of search.hip) under this engine's profiling: listed by
     // profile_report as `name`
@@ -142,13 +98,13 @@ private:
               int epi, std::string &err, const GemmLnFold *ln = nullptr);
     void attention(const Plan &p);
     void tap(const Plan &p, int idx);
-    template <class F> void timed(const char *name, double flops, hipStream_t s, F &&f);
+    template <class F> void timed(const char *name, double flops, hipStream_t s, F &&f) { prof_.timed(name, flops, s, f); }
 
     HParams hp_;
     int device_ = 0;
-    int table_type_ = 0;
-    DevBuf word_emb_, type_emb_, pos_emb_, ln_e_w_, ln_e_b_;
-    std::vector<LayerWeights *> layers_;
+    EngineOptions opt_;
+    std::unique_ptr<ModelWeights> w_;
+    LaunchProfiler prof_;
 
     // workspace (grow-only)
     DevBuf x_, qkv_, ctx_, y_, ff_, v32_, d_tokens_, d_cu_, d_out_, d_hidden_, status_, windows_;
@@ -168,30 +124,6 @@ private:
         DevBuf d_in, d_out;
         hipEvent_t done = nullptr;
     } slot_[2];
-
-    // options
-    bool gemm_naive_ = false, attn_naive_ = false, qkv2_ = true, gemm256_ = true, ln_fold_ = true, tail_ = true, latency_ = true, q4_expand_ = true;
-    bool fold_images_ = false;        // the LayerNorm-folding images were built at load (ln_fold_ was set then)
-    bool f32_file_ = false;           // every matrix and table of the file is f32: the f32 route can take it
-    bool f32_exact_ = true;           // ... and takes it unless BERT_HIP_F32=f16 / set_option("f32", "f16")
-    int one_launch_ = 1;              // all layers in one launch: 0 never, 1 when it pays (well-filled windows), 2 whenever the kernel takes the batch
-    int chunk_tokens_ = 262144;
-    // Calls of at most this many tokens take the latency route (skinny.hip).  A call of T tokens keeps ceil(T / 128) CUs busy on
-    // the fused kernels — 615-685 us for anything from 129 to 3000 tokens of all-MiniLM-L6-v2 — while the route's time grows with T
-    // from 220 us: 252 us at 172 tokens (8 sentences), 330 at 363 (16), 376 at 512, 527 at 716, 606 at 1024 (round 5, same bits).
-    int latency_tokens_ = 768;
-    bool stage_kernel_ = true;        // small staged blocks come in by a kernel that reads the mapped pinned block, not by the copy engine
-
-    // profiling
-    bool profiling_ = false;
-    std::vector<hipEvent_t> ev_pool_;
-    struct Pending { const char *name; hipEvent_t a, b; double flops; int launches; };
-    std::string replay_name_;         // "profile_replay": time K repeats of this kernel between one event pair (engine.hip timed())
-    int replay_k_ = 10;
-    bool replay_done_ = false;
-    std::vector<Pending> pending_;
-    std::map<std::string, KernelStat> stats_;
-    std::map<std::string, int> families_;       // profile: mat-mul launches per kernel family ("family:gemm256_q4" ...)
 };
 
 }  // namespace bert_hip

@@ -11,240 +11,6 @@
 
 namespace bert_hip {
 
-#define HIP_OK(expr, errvar, ret)                                                                       \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess) {                                                                        \
-            errvar = std::string(#expr) + ": " + hipGetErrorString(e__);                                \
-            return ret;                                                                                 \
-        }                                                                                               \
-    } while (0)
-
-// ------------------------------------------------------------------------------------------------
-// DevBuf
-// ------------------------------------------------------------------------------------------------
-DevBuf::~DevBuf() {
-    if (p) (void)hipFree(p);
-}
-bool DevBuf::alloc(size_t n, std::string &err) {
-    if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
-    if (n == 0) n = 16;
-    HIP_OK(hipMalloc(&p, n), err, false);
-    bytes = n;
-    HIP_OK(hipMemset(p, 0, n), err, false);
-    // the fill runs on the null stream and returns early; the engine's streams are non-blocking (not ordered
-    // against it), so a kernel writing this buffer could be overtaken by the fill
-    HIP_OK(hipDeviceSynchronize(), err, false);
-    return true;
-}
-bool DevBuf::upload(const void *src, size_t n, std::string &err) {
-    if (!alloc(n, err)) return false;
-    if (n) HIP_OK(hipMemcpy(p, src, n, hipMemcpyHostToDevice), err, false);
-    return true;
-}
-bool DevBuf::ensure(size_t n, std::string &err) {
-    if (n <= bytes) return true;
-    return alloc(n + n / 8, err);
-}
-
-// ------------------------------------------------------------------------------------------------
-// weight repacking (host) -> HBM layouts of kernels.h
-// ------------------------------------------------------------------------------------------------
-namespace {
-
-inline float h2f(uint16_t bits) { _Float16 h; memcpy(&h, &bits, 2); return (float)h; }
-
-// row `r` of a file tensor dequantised to f16 (exactly representable for f16 files; nearest for f32 / q4)
-void row_to_f16(const HostTensor &t, int64_t r, _Float16 *dst) {
-    const int64_t K = t.ne0;
-    const uint8_t *src = t.data + wtype_row_bytes(t.type, K) * (size_t)r;
-    if (t.type == W_F32) {
-        const float *f = (const float *)src;
-        for (int64_t k = 0; k < K; ++k) dst[k] = (_Float16)f[k];
-    } else if (t.type == W_F16) {
-        memcpy(dst, src, (size_t)K * 2);
-    } else {
-        const int bs = t.type == W_Q4_0 ? 18 : 20;
-        for (int64_t b = 0; b < K / 32; ++b) {
-            const uint8_t *blk = src + b * bs;
-            uint16_t dbits; memcpy(&dbits, blk, 2);
-            const float d = h2f(dbits);
-            float m = 0.f;
-            const uint8_t *qs = blk + 2;
-            if (t.type == W_Q4_1) { uint16_t mb; memcpy(&mb, blk + 2, 2); m = h2f(mb); qs = blk + 4; }
-            for (int j = 0; j < 16; ++j) {
-                const int q0 = qs[j] & 0x0F, q1 = qs[j] >> 4;
-                if (t.type == W_Q4_0) {
-                    dst[b * 32 + j] = (_Float16)((float)(q0 - 8) * d);
-                    dst[b * 32 + j + 16] = (_Float16)((float)(q1 - 8) * d);
-                } else {
-                    dst[b * 32 + j] = (_Float16)((double)q0 * d + m);          // exact in double: one rounding, like an f16 fma
-                    dst[b * 32 + j + 16] = (_Float16)((double)q1 * d + m);
-                }
-            }
-        }
-    }
-}
-
-}  // namespace
-
-bool GemmWeightStore::build(const std::vector<const HostTensor *> &rows, bool want_naive, std::string &err, bool want_kperm,
-                            bool expand_q4, bool want_f32) {
-    const int64_t K = rows[0]->ne0;
-    const int ftype = rows[0]->type;
-    int64_t N = 0;
-    for (auto *t : rows) {
-        if (t->ne0 != K || t->type != ftype) { err = "stacked weights disagree in shape/type"; return false; }
-        N += t->ne1;
-    }
-    w.N = (int)N; w.K = (int)K;
-    w.N_pad = (int)((N + GEMM_BN - 1) / GEMM_BN * GEMM_BN);
-    mfma_ok = (K % GEMM_BK == 0) && (N % 8 == 0);
-    auto src_row = [&](int64_t n, const HostTensor *&t, int64_t &r) {
-        for (auto *c : rows) { if (n < c->ne1) { t = c; r = n; return; } n -= c->ne1; }
-        t = nullptr; r = 0;
-    };
-    // expand_q4: the 4-bit blocks become an f16 image here, once (same values the fused-dequant kernels build in
-    // registers on every tile); the matrix then runs on the f16 kernels
-    const bool quant = (ftype == W_Q4_0 || ftype == W_Q4_1) && !expand_q4;
-    if (mfma_ok && !quant) {
-        w.type = GW_F16;
-        std::vector<_Float16> img((size_t)w.N_pad * K, (_Float16)0);
-        for (int64_t n = 0; n < N; ++n) { const HostTensor *t; int64_t r; src_row(n, t, r); row_to_f16(*t, r, img.data() + (size_t)n * K); }
-        if (!w16.upload(img.data(), img.size() * 2, err)) return false;
-        w.w16 = w16.as<half_t>();
-        if (want_kperm && K % 16 == 0) {
-            std::vector<_Float16> pimg(img.size());
-            for (size_t base = 0; base < img.size(); base += 16)
-                for (int j = 0; j < 16; ++j) {
-                    // stored position j of a group <- k offset: [0-3, 8-11, 4-7, 12-15]
-                    const int src = (j & 3) + ((j >> 2) & 1) * 8 + (j >> 3) * 4;
-                    pimg[base + j] = img[base + src];
-                }
-            if (!w16p.upload(pimg.data(), pimg.size() * 2, err)) return false;
-            w.w16p = w16p.as<half_t>();
-        }
-    } else if (mfma_ok) {
-        w.type = ftype == W_Q4_0 ? GW_Q4_0 : GW_Q4_1;
-        const int bs = ftype == W_Q4_0 ? 18 : 20, scb = ftype == W_Q4_0 ? 2 : 4;
-        const int64_t nkt = K / GEMM_BK, ntn = w.N_pad / GEMM_BN;
-        const size_t nblk = (size_t)ntn * nkt * 256;
-        std::vector<uint8_t> q(nblk * 16, 0), s(nblk * scb, 0);
-        for (int64_t nt = 0; nt < ntn; ++nt)
-            for (int64_t kt = 0; kt < nkt; ++kt)
-                for (int row = 0; row < 128; ++row) {
-                    const int64_t n = nt * 128 + row;
-                    if (n >= N) continue;
-                    const HostTensor *t; int64_t r; src_row(n, t, r);
-                    const uint8_t *rowp = t->data + wtype_row_bytes(ftype, K) * (size_t)r;
-                    for (int kb = 0; kb < 2; ++kb) {
-                        const uint8_t *blk = rowp + (size_t)(kt * 2 + kb) * bs;
-                        const size_t bi = ((size_t)(nt * nkt + kt) * 128 + row) * 2 + kb;
-                        memcpy(s.data() + bi * scb, blk, scb);               // d  or  {d, m}
-                        memcpy(q.data() + bi * 16, blk + scb, 16);           // 32 nibbles
-                    }
-                }
-        if (!qs.upload(q.data(), q.size(), err) || !sc.upload(s.data(), s.size(), err)) return false;
-        w.qs = qs.as<uint4>();
-        w.sc = sc.p;
-    }
-    if (want_f32 && ftype == W_F32) {
-        std::vector<uint8_t> all;
-        for (auto *t : rows) all.insert(all.end(), t->data, t->data + t->nbytes);
-        if (all.size() != (size_t)N * K * 4) { err = "f32 tensor size mismatch"; return false; }
-        if (!w32.upload(all.data(), all.size(), err)) return false;
-        w.w32 = w32.as<float>();
-    }
-    if (!mfma_ok || want_naive) {
-        std::vector<_Float16> img((size_t)N * K);
-        for (int64_t n = 0; n < N; ++n) { const HostTensor *t; int64_t r; src_row(n, t, r); row_to_f16(*t, r, img.data() + (size_t)n * K); }
-        if (!naive16.upload(img.data(), img.size() * 2, err)) return false;
-        w.naive16 = naive16.as<half_t>();
-    }
-    return true;
-}
-
-bool GemmWeightStore::build_ln_fold(const std::vector<const HostTensor *> &rows, const float *gamma, const float *beta, const float *bias,
-                                    DevBuf &waug, std::string &err) {
-    const int64_t K = rows[0]->ne0;
-    int64_t N = 0;
-    for (auto *t : rows) { if (t->ne0 != K) { err = "stacked weights disagree in shape"; return false; } N += t->ne1; }
-    w.N = (int)N; w.K = (int)K; w.N_pad = (int)((N + GEMM_BN - 1) / GEMM_BN * GEMM_BN);
-    mfma_ok = (K % GEMM_BK == 0) && (N % 8 == 0);
-    if (!mfma_ok) return true;                                // (shapes the MFMA kernels do not take are never folded)
-    w.type = GW_F16;
-    std::vector<_Float16> img((size_t)w.N_pad * K, (_Float16)0), row((size_t)K), aug((size_t)N * 16, (_Float16)0);
-    int64_t n = 0;
-    for (auto *t : rows)
-        for (int64_t r = 0; r < t->ne1; ++r, ++n) {
-            row_to_f16(*t, r, row.data());                    // (the values the un-folded f16 image holds)
-            double s = 0.0, c = bias ? (double)bias[n] : 0.0;
-            for (int64_t k = 0; k < K; ++k) {
-                const _Float16 wf = (_Float16)((float)row[k] * gamma[k]);
-                img[(size_t)n * K + k] = wf;
-                s += (double)(float)wf;
-                c += (double)beta[k] * (double)(float)row[k];
-            }
-            const _Float16 s_h = (_Float16)(float)s, s_l = (_Float16)(float)(s - (double)(float)s_h);
-            const _Float16 c_h = (_Float16)(float)c, c_l = (_Float16)(float)(c - (double)(float)c_h);
-            _Float16 *a = aug.data() + (size_t)n * 16;
-            a[0] = s_h; a[1] = s_l; a[2] = s_h; a[3] = c_h; a[4] = c_l; a[5] = c_h;
-        }
-    if (!w16.upload(img.data(), img.size() * 2, err) || !waug.upload(aug.data(), aug.size() * 2, err)) return false;
-    w.w16 = w16.as<half_t>();
-    return true;
-}
-
-// packed (f16 gamma | f16 (beta + bias) << 16) per feature: what a residual mat-mul needs to rebuild LayerNorm(resid) per element
-static bool upload_gamma_beta_bias(DevBuf &b, const float *gamma, const float *beta, const float *bias, int64_t n, std::string &err) {
-    std::vector<uint32_t> v((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        const _Float16 g = (_Float16)gamma[i], bb = (_Float16)(beta[i] + bias[i]);
-        uint16_t gu, bu;
-        memcpy(&gu, &g, 2); memcpy(&bu, &bb, 2);
-        v[(size_t)i] = (uint32_t)gu | ((uint32_t)bu << 16);
-    }
-    return b.upload(v.data(), v.size() * 4, err);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Engine
-// ------------------------------------------------------------------------------------------------
-static bool upload_f32(DevBuf &b, const HostTensor *t, std::string &err) { return b.upload(t->data, t->nbytes, err); }
-
-// an embedding table of a q4 file as f32 values: (q - 8) d / q d + m, the numbers the gather kernel dequantises on the fly
-// (q d is exact in f32, so the host's multiply-add and the device's fma round alike); 6.4x the bytes, but the f32 form is
-// read by the 16-byte-run kernel (embed_ln_rows_kernel) instead of element by element
-static bool upload_table_f32(DevBuf &b, const HostTensor *t, std::string &err) {
-    const int64_t K = t->ne0, N = t->ne1;
-    const int bs = t->type == W_Q4_0 ? 18 : 20;
-    std::vector<float> img((size_t)N * K);
-    for (int64_t r = 0; r < N; ++r) {
-        const uint8_t *src = t->data + wtype_row_bytes(t->type, K) * (size_t)r;
-        float *dst = img.data() + (size_t)r * K;
-        for (int64_t blk_i = 0; blk_i < K / 32; ++blk_i) {
-            const uint8_t *blk = src + blk_i * bs;
-            uint16_t dbits; memcpy(&dbits, blk, 2);
-            const float d = h2f(dbits);
-            float m = 0.f;
-            const uint8_t *qs = blk + 2;
-            if (t->type == W_Q4_1) { uint16_t mb; memcpy(&mb, blk + 2, 2); m = h2f(mb); qs = blk + 4; }
-            for (int j = 0; j < 16; ++j) {
-                const int q0 = qs[j] & 0x0F, q1 = qs[j] >> 4;
-                dst[blk_i * 32 + j] = t->type == W_Q4_0 ? (float)(q0 - 8) * d : (float)q0 * d + m;
-                dst[blk_i * 32 + j + 16] = t->type == W_Q4_0 ? (float)(q1 - 8) * d : (float)q1 * d + m;
-            }
-        }
-    }
-    return b.upload(img.data(), img.size() * sizeof(float), err);
-}
-
-static bool concat_upload(DevBuf &b, std::initializer_list<const HostTensor *> ts, std::string &err) {
-    std::vector<uint8_t> all;
-    for (auto *t : ts) all.insert(all.end(), t->data, t->data + t->nbytes);
-    return b.upload(all.data(), all.size(), err);
-}
-
 Engine *Engine::create(const ModelFile &mf, int device, std::string &err) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -252,142 +18,29 @@ Engine *Engine::create(const ModelFile &mf, int device, std::string &err) {
         return nullptr;
     }
     if (device < 0 || device >= ndev) { err = "HIP device ordinal " + std::to_string(device) + " out of range"; return nullptr; }
-    Engine *e = new Engine;
+    std::unique_ptr<Engine> e(new Engine);
     e->hp_ = mf.hp;
     e->device_ = device;
-    if (hipSetDevice(e->device_) != hipSuccess) { err = "hipSetDevice failed"; delete e; return nullptr; }
+    if (hipSetDevice(e->device_) != hipSuccess) { err = "hipSetDevice failed"; return nullptr; }
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, e->device_) != hipSuccess) { err = "hipGetDeviceProperties failed"; delete e; return nullptr; }
+    if (hipGetDeviceProperties(&prop, e->device_) != hipSuccess) { err = "hipGetDeviceProperties failed"; return nullptr; }
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
         err = std::string("unsupported GPU architecture '") + prop.gcnArchName + "' (kernels are built for gfx950 / MI355X only)";
-        delete e; return nullptr;
+        return nullptr;
     }
-    // BERT_HIP_KERNELS = fused (default) | tiled (GEMM + attention + LayerNorm kernels, Q|K|V and the intermediate through HBM);
-    // finer switches: bert_hip_set_option.  The GENERIC kernels (any shape, row-major f16 images) are what shapes outside the MFMA
-    // kernels' reach fall back to; running a whole model on them is a cross-check for the tests, not a route of the product:
-    // "naive" is understood by libbert_test.so only (this file compiled with -DBERT_HIP_TEST_ROUTES).
-    if (const char *k = getenv("BERT_HIP_KERNELS")) {
-#ifdef BERT_HIP_TEST_ROUTES
-        if (strcmp(k, "naive") == 0) e->gemm_naive_ = e->attn_naive_ = true;
-        else
-#else
-        if (strcmp(k, "naive") == 0) fprintf(stderr, "BERT_HIP_KERNELS=naive: a test cross-check (libbert_test.so), not a route of libbert.so; ignored\n");
-        else
-#endif
-        if (strcmp(k, "tiled") == 0) e->qkv2_ = e->tail_ = e->latency_ = false, e->one_launch_ = 0;
-    }
-    // (the cap of the latency route: measured on H = 384; a window of an H = 128 model costs the fused kernels less than five
-    // launches cost the route, so such models keep the one-window cap)
-    if (mf.hp.n_embd < 256) e->latency_tokens_ = 128;
-    // BERT_HIP_LATENCY: 0 = no latency route; 1 = the default cap; n >= 32: calls of at most n tokens take it
-    if (const char *f = getenv("BERT_HIP_LATENCY")) {
-        e->latency_ = strcmp(f, "0") != 0;
-        if (atoi(f) >= 32) e->latency_tokens_ = atoi(f);
-    }
-    if (const char *f = getenv("BERT_HIP_Q4")) e->q4_expand_ = strcmp(f, "fused") != 0;
-    if (const char *f = getenv("BERT_HIP_LN_FOLD")) e->ln_fold_ = strcmp(f, "0") != 0;        // (tuning: 0 = LayerNorm kernels of their own at H = 768)
-    if (const char *c = getenv("BERT_HIP_CHUNK_TOKENS")) { const int v = atoi(c); if (v > 0) e->chunk_tokens_ = v; }
-    if (const char *c = getenv("BERT_HIP_WINDOW_SLOTS")) set_window_slots(atoi(c));
-    // f32 files: f32 arithmetic like the reference's (f32_route.hip) unless BERT_HIP_F32=f16 asks for f16 operands and the fused kernels
-    if (const char *f = getenv("BERT_HIP_F32")) e->f32_exact_ = strcmp(f, "f16") != 0;
-    if (mf.hp.n_embd % 2 != 0) { err = "n_embd must be even"; delete e; return nullptr; }
-
-    auto T = [&](const std::string &n) { return mf.find(n); };
-    bool ok = true;
-    e->table_type_ = mf.hp.f16;
-    {
-        const HostTensor *tw = T("embeddings.word_embeddings.weight"), *tt = T("embeddings.token_type_embeddings.weight"),
-                         *tp = T("embeddings.position_embeddings.weight");
-        const bool q4_tables = tw && tt && tp && (tw->type == W_Q4_0 || tw->type == W_Q4_1) && tt->type == tw->type && tp->type == tw->type;
-        if (q4_tables && e->q4_expand_ && mf.hp.n_embd % 32 == 0) {
-            e->table_type_ = 0;
-            ok = ok && upload_table_f32(e->word_emb_, tw, err) && upload_table_f32(e->type_emb_, tt, err) && upload_table_f32(e->pos_emb_, tp, err);
-        } else {
-            ok = ok && upload_f32(e->word_emb_, tw, err) && upload_f32(e->type_emb_, tt, err) && upload_f32(e->pos_emb_, tp, err);
-        }
-    }
-    ok = ok && upload_f32(e->ln_e_w_, T("embeddings.LayerNorm.weight"), err);
-    ok = ok && upload_f32(e->ln_e_b_, T("embeddings.LayerNorm.bias"), err);
-    const bool want_naive = e->gemm_naive_;
-    // the f32 route needs every matrix of every layer and the three tables as f32 tensors (a file has one ftype, but check)
-    e->f32_file_ = mf.hp.f16 == 0;
-    for (const char *n : {"embeddings.word_embeddings.weight", "embeddings.token_type_embeddings.weight", "embeddings.position_embeddings.weight"})
-        e->f32_file_ = e->f32_file_ && T(n) && T(n)->type == W_F32;
-    for (int i = 0; e->f32_file_ && i < mf.hp.n_layer; ++i) {
-        const std::string p = "encoder.layer." + std::to_string(i) + ".";
-        for (const char *n : {"attention.self.query.weight", "attention.self.key.weight", "attention.self.value.weight", "attention.output.dense.weight",
-                              "intermediate.dense.weight", "output.dense.weight"})
-            e->f32_file_ = e->f32_file_ && T(p + n) && T(p + n)->type == W_F32;
-    }
-    const bool want_f32 = e->f32_file_;
-    // the k-permuted second image of the FFN weights is only read by layer_tail_kernel (H = 256 / 384)
-    const bool want_kperm = mf.hp.n_embd % 128 == 0 && mf.hp.n_embd >= 256 && mf.hp.n_embd <= 384;
-    for (int i = 0; ok && i < mf.hp.n_layer; ++i) {
-        const std::string p = "encoder.layer." + std::to_string(i) + ".";
-        auto *L = new LayerWeights;
-        e->layers_.push_back(L);
-        ok = ok && L->qkv.build({T(p + "attention.self.query.weight"), T(p + "attention.self.key.weight"),
-                                 T(p + "attention.self.value.weight")}, want_naive, err, false, e->q4_expand_, want_f32);
-        {
-            const HostTensor *tq = T(p + "attention.self.query.weight");
-            const bool q4_file = tq && (tq->type == W_Q4_0 || tq->type == W_Q4_1);
-            if (ok && q4_file && e->q4_expand_ && L->qkv.mfma_ok && (size_t)L->qkv.w.N * L->qkv.w.K * 2 > ((size_t)3 << 20))
-                ok = L->qkv_q4.build({tq, T(p + "attention.self.key.weight"), T(p + "attention.self.value.weight")}, false, err, false, false);
-        }
-        ok = ok && concat_upload(L->qkv_b, {T(p + "attention.self.query.bias"), T(p + "attention.self.key.bias"),
-                                            T(p + "attention.self.value.bias")}, err);
-        ok = ok && L->o.build({T(p + "attention.output.dense.weight")}, want_naive, err, false, e->q4_expand_, want_f32);
-        ok = ok && upload_f32(L->o_b, T(p + "attention.output.dense.bias"), err);
-        ok = ok && upload_f32(L->ln_att_w, T(p + "attention.output.LayerNorm.weight"), err);
-        ok = ok && upload_f32(L->ln_att_b, T(p + "attention.output.LayerNorm.bias"), err);
-        ok = ok && L->ffi.build({T(p + "intermediate.dense.weight")}, want_naive, err, want_kperm, e->q4_expand_, want_f32);
-        ok = ok && upload_f32(L->ffi_b, T(p + "intermediate.dense.bias"), err);
-        ok = ok && L->ffo.build({T(p + "output.dense.weight")}, want_naive, err, want_kperm, e->q4_expand_, want_f32);
-        ok = ok && upload_f32(L->ffo_b, T(p + "output.dense.bias"), err);
-        ok = ok && upload_f32(L->ln_out_w, T(p + "output.LayerNorm.weight"), err);
-        ok = ok && upload_f32(L->ln_out_b, T(p + "output.LayerNorm.bias"), err);
-    }
-    // LayerNorm folding (kernels.h GemmLnFold; the route of models the fused H <= 384 kernels do not take): images for every layer
-    // whose four matrices run on gemm256's f16 form; only when folding is on at load (set_option cannot turn it on without them)
-    e->fold_images_ = e->ln_fold_;
-    auto f16_256 = [](const GemmWeightStore &s) { return s.mfma_ok && s.w.type == GW_F16 && s.w.N % 256 == 0 && s.w.K % 64 == 0 && s.w.K >= 128; };
-    // (1-D f32 tensors, copied out: their bytes in the file buffer have no alignment guarantee; empty: no such tensor)
-    auto F = [&](const std::string &n) { std::vector<float> v(T(n) ? T(n)->nbytes / 4 : 0); if (!v.empty()) memcpy(v.data(), T(n)->data, v.size() * 4); return v; };
-    for (int i = 0; ok && e->fold_images_ && i < mf.hp.n_layer; ++i) {
-        LayerWeights &L = *e->layers_[i];
-        const std::string p = "encoder.layer." + std::to_string(i) + ".";
-        const int H = mf.hp.n_embd;
-        if (!(H > 384 && H % 256 == 0 && f16_256(L.qkv) && f16_256(L.o) && f16_256(L.ffi) && f16_256(L.ffo)) || e->f32_file_) continue;
-        const std::vector<float> g1 = F(p + "attention.output.LayerNorm.weight"), b1 = F(p + "attention.output.LayerNorm.bias"),
-                                 bi = F(p + "intermediate.dense.bias"), bo2 = F(p + "output.dense.bias"), bo = F(p + "attention.output.dense.bias");
-        if (g1.empty() || b1.empty() || bi.empty() || bo2.empty() || bo.empty()) continue;
-        ok = L.ffi_fold.build_ln_fold({T(p + "intermediate.dense.weight")}, g1.data(), b1.data(), bi.data(), L.ffi_waug, err) &&
-             upload_gamma_beta_bias(L.ffo_gb, g1.data(), b1.data(), bo2.data(), H, err);
-        if (ok && i >= 1) {
-            const std::string q = "encoder.layer." + std::to_string(i - 1) + ".";
-            const std::vector<float> g2 = F(q + "output.LayerNorm.weight"), b2 = F(q + "output.LayerNorm.bias");
-            std::vector<float> qb;
-            for (const char *n : {"attention.self.query.bias", "attention.self.key.bias", "attention.self.value.bias"}) { const auto b = F(p + n); qb.insert(qb.end(), b.begin(), b.end()); }
-            if (g2.empty() || b2.empty() || qb.size() != (size_t)3 * H) continue;
-            ok = L.qkv_fold.build_ln_fold({T(p + "attention.self.query.weight"), T(p + "attention.self.key.weight"), T(p + "attention.self.value.weight")},
-                                          g2.data(), b2.data(), qb.data(), L.qkv_waug, err) &&
-                 upload_gamma_beta_bias(L.o_gb, g2.data(), b2.data(), bo.data(), H, err);
-        }
-        L.fold_ok = ok && L.ffi_fold.mfma_ok && (i == 0 || L.qkv_fold.mfma_ok);
-    }
-    ok = ok && e->status_.alloc(16, err);
-    if (ok && hipStreamCreateWithFlags(&e->stream_, hipStreamNonBlocking) != hipSuccess) { err = "hipStreamCreate failed"; ok = false; }
-    if (ok && hipEventCreateWithFlags(&e->busy_, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; ok = false; }
-    if (!ok) { delete e; return nullptr; }
-    return e;
+    e->opt_ = EngineOptions::from_env(mf.hp);
+    LoadOptions lo;
+    lo.naive = e->opt_.gemm_naive; lo.expand_q4 = e->opt_.q4_expand; lo.ln_fold = e->opt_.ln_fold;
+    e->w_ = ModelWeights::load(mf, lo, err);
+    if (!e->w_ || !e->status_.alloc(16, err)) return nullptr;
+    if (hipStreamCreateWithFlags(&e->stream_, hipStreamNonBlocking) != hipSuccess) { err = "hipStreamCreate failed"; return nullptr; }
+    if (hipEventCreateWithFlags(&e->busy_, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return nullptr; }
+    return e.release();
 }
 
 Engine::~Engine() {
     (void)hipSetDevice(device_);
     (void)hipDeviceSynchronize();
-    for (auto *L : layers_) delete L;
-    for (auto ev : ev_pool_) (void)hipEventDestroy(ev);
-    for (auto &p : pending_) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto &sl : slot_) {
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.h_out) (void)hipHostFree(sl.h_out);
@@ -413,58 +66,16 @@ int Engine::check(std::string &err) {
 }
 
 void Engine::set_option(const std::string &key, const std::string &value) {
-#ifndef BERT_HIP_TEST_ROUTES
-    if ((key == "gemm" || key == "attn") && value == "naive") {
-        fprintf(stderr, "bert_hip_set_option: %s=naive is a test cross-check (libbert_test.so), not a route of libbert.so; ignored\n", key.c_str());
-        return;
-    }
-#endif
-    if (key == "gemm") {
-        // the generic kernel reads GemmWeight::naive16, an image that is only built at load time (BERT_HIP_KERNELS=naive) or
-        // for shapes the MFMA kernels cannot take: refuse the switch when a matrix lacks it
-        bool have = true;
-        for (auto *L : layers_)
-            for (GemmWeightStore *w : {&L->qkv, &L->o, &L->ffi, &L->ffo}) have = have && w->w.naive16 != nullptr;
-        if (value == "naive" && !have)
-            fprintf(stderr, "bert_hip_set_option: gemm=naive needs BERT_HIP_KERNELS=naive at load time (the f16 row-major images were not built); ignored\n");
-        else gemm_naive_ = value == "naive";
-    } else if (key == "attn") attn_naive_ = value == "naive";
-    else if (key == "qkv2") qkv2_ = value != "0";
-    else if (key == "gemm256") gemm256_ = value != "0";
-    else if (key == "ln_fold" && value != "0" && !fold_images_)
-        fprintf(stderr, "bert_hip_set_option: ln_fold=1 needs BERT_HIP_LN_FOLD=1 at load time (the folded images were not built); ignored\n");
-    else if (key == "ln_fold") ln_fold_ = value != "0";
-    else if (key == "tail") tail_ = value != "0";
-    else if (key == "latency") latency_ = value != "0";
-    else if (key == "stage_kernel") stage_kernel_ = value != "0";
-    else if (key == "window_slots") set_window_slots(atoi(value.c_str()));      // (process-wide: 16, or 8 — see kernels.h)
-    else if (key == "latency_tokens") { const int v = atoi(value.c_str()); if (v >= 32) latency_tokens_ = v; }
-    else if (key == "one_launch") one_launch_ = value == "0" ? 0 : value == "2" ? 2 : 1;
-#ifdef BERT_HIP_TEST_ROUTES
-    // (libbert_test.so only) every half of the attention-context workspace becomes a NaN: a pass that still reads what it has not
-    // written itself shows it in its results
-    else if (key == "test_poison_ctx") {
-        (void)hipSetDevice(device());
-        (void)hipDeviceSynchronize();
-        if (ctx_.p) (void)hipMemset(ctx_.p, 0xFF, ctx_.bytes);
-        (void)hipDeviceSynchronize();
-    }
-#endif
-    else if (key == "f32") f32_exact_ = value != "f16";       // f32 files: "exact" (f32 arithmetic, default) | "f16" (f16 operands, fused kernels)
-    else if (key == "chunk_tokens") { const int v = atoi(value.c_str()); if (v > 0) chunk_tokens_ = v; }
-    else if (key == "profile_replay") {
-        // "<kernel name>:<K>" (see timed()), "" switches back to an event pair per launch
-        const size_t c = value.rfind(':');
-        replay_name_ = c == std::string::npos ? value : value.substr(0, c);
-        replay_k_ = c == std::string::npos ? 10 : std::max(1, atoi(value.c_str() + c + 1));
-    }
+    if (key == "profile_replay") { prof_.set_replay(value); return; }
+    (void)hipSetDevice(device_);
+    if (!test_poison_option(key, ctx_)) opt_.set(key, value, w_->naive_images(), w_->fold_images);
 }
 
 bool Engine::ensure_workspace(int t_pad, int n_sentences, std::string &err) {
     const size_t H = hp_.n_embd, I = hp_.n_intermediate, tp = (size_t)t_pad;
-    const size_t es = f32_file_ ? 4 : 2;                      // (f32 files: the f32 route's activations are f32)
+    const size_t es = w_->f32_file ? 4 : 2;                      // (f32 files: the f32 route's activations are f32)
     return x_.ensure(tp * H * es, err) && qkv_.ensure(tp * 3 * H * es, err) && ctx_.ensure(tp * H * es, err) &&
-           y_.ensure(tp * H * es, err) && ff_.ensure(tp * I * es, err) && v32_.ensure((size_t)std::max(128, std::min(t_pad, (latency_tokens_ + 255) / 256 * 256)) * H * 4, err) &&
+           y_.ensure(tp * H * es, err) && ff_.ensure(tp * I * es, err) && v32_.ensure((size_t)std::max(128, std::min(t_pad, (opt_.latency_tokens + 255) / 256 * 256)) * H * 4, err) &&
            d_out_.ensure((size_t)n_sentences * H * 4, err) &&
            windows_.ensure((size_t)n_sentences * sizeof(int2), err) &&
            // (LayerNorm folding, H = 768 route: 2 H / 256 partial (sum, sum of squares) pairs and one finalized float4 per row and LayerNorm)
@@ -472,76 +83,12 @@ bool Engine::ensure_workspace(int t_pad, int n_sentences, std::string &err) {
                                            ln_rows1_.ensure(tp * 16, err) && ln_rows2_.ensure(tp * 16, err)));
 }
 
-template <class F>
-void Engine::timed(const char *name, double flops, hipStream_t s, F &&f) {
-    if (!profiling_) { f(); return; }
-    auto get = [&]() {
-        hipEvent_t ev;
-        if (!ev_pool_.empty()) { ev = ev_pool_.back(); ev_pool_.pop_back(); }
-        else (void)hipEventCreate(&ev);
-        return ev;
-    };
-    if (!replay_name_.empty()) {
-        // replay form ("profile_replay" = "<kernel>:<K>"): the pass runs untimed; behind the FIRST launch of the named kernel
-        // the same launch is repeated K times between ONE event pair — the pair's own cost (tens of microseconds around a
-        // sub-millisecond kernel) is spread over K launches, so launches x average cannot exceed the step they belong to.
-        // Kernels that work in place see their own output as input in the repeats: the pass's results are not to be used.
-        f();
-        if (replay_done_ || replay_name_ != name) return;
-        replay_done_ = true;
-        // (in-place kernels run on their own output from here on: this pass's embeddings are NOT results — bench.py restores
-        // its output buffer; say so once for anybody else who turns the option on)
-        static bool warned = false;
-        if (!warned && !getenv("BERT_HIP_QUIET")) { warned = true; fprintf(stderr, "bert_hip: profile_replay is active: the embeddings of profiled passes are not valid results\n"); }
-        Pending p{name, get(), get(), flops * replay_k_, replay_k_};
-        (void)hipEventRecord(p.a, s);
-        for (int k = 0; k < replay_k_; ++k) f();
-        (void)hipEventRecord(p.b, s);
-        pending_.push_back(p);
-        return;
-    }
-    // an event pair attached to the dispatch itself (kernels.h BERT_LAUNCH): an upper bound of the kernel's time in the pass
-    Pending p{name, get(), get(), flops, 1};
-    LaunchTiming lt{p.a, p.b, 0};
-    tl_launch_timing = &lt;
-    f();
-    tl_launch_timing = nullptr;
-    // exactly one launch carries the pair; anything else (a launcher that returned early: stale timestamps of pooled events;
-    // several launches: only the last one measured) is not a sample
-    if (lt.launches == 1) pending_.push_back(p);
-    else { ev_pool_.push_back(p.a); ev_pool_.push_back(p.b); }
-}
-
 void Engine::timed_launch(const char *name, double flops, hipStream_t s, const std::function<void()> &f) { timed(name, flops, s, f); }
-
-void Engine::profile_enable(bool on) { profiling_ = on; }
 
 std::string Engine::profile_report() {
     (void)hipSetDevice(device_);
     (void)hipDeviceSynchronize();
-    for (auto &p : pending_) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-            KernelStat &st = stats_[p.name];
-            st.launches += p.launches; st.ms += ms; st.flops += p.flops;
-        }
-        ev_pool_.push_back(p.a); ev_pool_.push_back(p.b);
-    }
-    pending_.clear();
-    std::string out;
-    char line[256];
-    for (auto &kv : stats_) {
-        snprintf(line, sizeof(line), "%s %d %.6f %.6e\n", kv.first.c_str(), kv.second.launches, kv.second.ms,
-                 kv.second.launches ? kv.second.flops / kv.second.launches : 0.0);
-        out += line;
-    }
-    stats_.clear();
-    for (auto &kv : families_) {
-        snprintf(line, sizeof(line), "%s %d 0 0\n", kv.first.c_str(), kv.second);
-        out += line;
-    }
-    families_.clear();
-    return out;
+    return prof_.report();
 }
 
 void Engine::build_windows(const int32_t *cu, int B, std::vector<int2> &windows, int slot) {
@@ -566,7 +113,7 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     const int slots = slots_in ? slots_in : window_slots();
     HIP_OK(hipSetDevice(device_), err, -1);
     if (!ensure_workspace((T + 255) / 256 * 256, B, err)) return -1;
-    replay_done_ = false;
+    prof_.begin_pass();
     // one forward pass at a time on the shared workspace: wait (on the caller's stream) for the previous pass
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots);
@@ -574,7 +121,7 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     if (p.route == Route::F32) ok = forward_f32(p, err);
     else {
         const int H = hp_.n_embd;
-        timed("embed_ln", 0.0, s, [&] { launch_embed_ln(word_emb_.p, type_emb_.p, pos_emb_.p, table_type_, ln_e_w_.as<float>(), ln_e_b_.as<float>(),
+        timed("embed_ln", 0.0, s, [&] { launch_embed_ln(w_->word_emb.p, w_->type_emb.p, w_->pos_emb.p, w_->table_type, w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(),
                                                         d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, x_.as<half_t>(), s); });
         tap(p, 0);
         if (p.build_windows)
@@ -600,35 +147,35 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
                           float *d_hidden, const int2 *d_windows, int n_windows, int slots) const {
     // (t_pad: whole tiles of every kernel family, 128- and 256-token tiles)
     Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, d_out, d_hidden, s, d_windows, n_windows};
-    if (f32_file_ && f32_exact_) { p.route = Route::F32; return p; }
+    if (w_->f32_file && opt_.f32_exact) { p.route = Route::F32; return p; }
     const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh, Lz = hp_.n_layer;
     auto family = [&](const GemmWeightStore &W) {
-        if (W.mfma_ok && gemm256_ && !gemm_naive_ && gemm256_supported(W.w, p.t_pad)) return Family::GEMM256;
-        return W.mfma_ok && (!gemm_naive_ || !W.w.naive16) ? Family::MFMA : Family::NAIVE;
+        if (W.mfma_ok && opt_.gemm256 && !opt_.gemm_naive && gemm256_supported(W.w, p.t_pad)) return Family::GEMM256;
+        return W.mfma_ok && (!opt_.gemm_naive || !W.w.naive16) ? Family::MFMA : Family::NAIVE;
     };
     // per layer (a file may mix types or shapes from layer to layer): its stages and mat-mul kernels, and whether it can run in the
     // one-launch kernel (which takes all layers' pointers) or with its LayerNorms folded (only models the fused kernels do not take)
     p.layers.resize(Lz);
-    bool qkv2_shape0 = false, one_launch = true, fold = ln_fold_ && H > 384 && H % 256 == 0 && ln_rows2_.p;
+    bool qkv2_shape0 = false, one_launch = true, fold = opt_.ln_fold && H > 384 && H % 256 == 0 && ln_rows2_.p;
     for (int il = 0; il < Lz; ++il) {
-        const LayerWeights &L = *layers_[il];
+        const LayerWeights &L = w_->layers[il];
         LayerPlan &lp = p.layers[il];
         const bool qkv2_shape = qkv_attention2_supported(L.qkv.w, nh, dh, max_len), tail_shape = layer_tail_supported(L.o.w, L.ffi.w, L.ffo.w);
         if (il == 0) qkv2_shape0 = qkv2_shape;
-        lp.qkv2 = qkv2_ && !gemm_naive_ && !attn_naive_ && L.qkv.mfma_ok && qkv2_shape;
-        lp.tail = tail_ && !gemm_naive_ && L.o.mfma_ok && L.ffi.mfma_ok && L.ffo.mfma_ok && tail_shape;
+        lp.qkv2 = opt_.qkv2 && !opt_.gemm_naive && !opt_.attn_naive && L.qkv.mfma_ok && qkv2_shape;
+        lp.tail = opt_.tail && !opt_.gemm_naive && L.o.mfma_ok && L.ffi.mfma_ok && L.ffo.mfma_ok && tail_shape;
         // (q4 files: the 4-bit planes of the stacked matrix where its f16 image overflows an XCD's L2 and gemm256 takes the launch)
         lp.planes = L.qkv_q4.w.qs && family(L.qkv_q4) == Family::GEMM256;
         lp.qkv = family(lp.planes ? L.qkv_q4 : L.qkv), lp.o = family(L.o), lp.ffi = family(L.ffi), lp.ffo = family(L.ffo);
         one_launch = one_launch && L.qkv.mfma_ok && L.o.mfma_ok && L.ffi.mfma_ok && L.ffo.mfma_ok && L.ffi.w.w16p && L.ffo.w.w16p &&
                      model_kernel_supported(L.qkv.w, L.o.w, L.ffi.w, L.ffo.w, Lz, nh, dh, max_len);
         fold = fold && L.fold_ok && (il ? family(L.qkv_fold) : lp.qkv) == Family::GEMM256 && lp.o == Family::GEMM256 &&
-               family(L.ffi_fold) == Family::GEMM256 && lp.ffo == Family::GEMM256 && !(qkv2_ && qkv2_shape) && !(tail_ && tail_shape);
+               family(L.ffi_fold) == Family::GEMM256 && lp.ffo == Family::GEMM256 && !(opt_.qkv2 && qkv2_shape) && !(opt_.tail && tail_shape);
     }
     // a hidden-state tap wants every layer's normalised states: it takes neither the one-launch kernel nor the folded LayerNorms
     if (d_hidden) one_launch = fold = false;
-    const bool fused_windows = p.layers[0].qkv2, latency_call = latency_ && T <= latency_tokens_;
-    one_launch = one_launch && fused_windows && one_launch_ && tail_ && !latency_call;
+    const bool fused_windows = p.layers[0].qkv2, latency_call = opt_.latency && T <= opt_.latency_tokens;
+    one_launch = one_launch && fused_windows && opt_.one_launch && opt_.tail && !latency_call;
     // sentence windows of the fused projection+attention kernel: the caller's (host path), or built on the device from cu_seqlens
     // when packing can pay — sentences on average clearly shorter than max_len; for full-length batches the uniform rule
     // (max_len-sized places) gives the same windows without the extra launch.  (Forced one-launch: the kernel takes a window list
@@ -636,7 +183,7 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
     const bool full_windows = (long long)B * 128 == T;
     const int spw = qkv_attention2_sentences_per_window(max_len, slots);
     if (!d_windows && fused_windows &&
-        (4ll * ((B + spw - 1) / spw) * 128 > 5 * ((long long)T + (long long)(slots / 2) * B) || (one_launch && one_launch_ == 2 && spw > 1 && !full_windows))) {
+        (4ll * ((B + spw - 1) / spw) * 128 > 5 * ((long long)T + (long long)(slots / 2) * B) || (one_launch && opt_.one_launch == 2 && spw > 1 && !full_windows))) {
         p.build_windows = true;
         p.windows = windows_.as<int2>();
         p.n_windows_dev = status_.as<int>() + 1;
@@ -647,10 +194,10 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
     // When the one-launch kernel pays: its layer-tail phase costs a window 128 rows' time however few tokens it holds, the layer-tail
     // KERNEL runs on the packed tokens — 0.32 + 0.68 fill against 0.94 (full windows: +6.7 %): from a fill of 0.91.  The window
     // count is known for the caller's list and for one sentence per window, not for a list built on the device.
-    bool one_launch_pays = full_windows || one_launch_ == 2;
+    bool one_launch_pays = full_windows || opt_.one_launch == 2;
     if (!one_launch_pays && !p.build_windows) one_launch_pays = (d_windows || spw == 1) && 100ll * T >= 95ll * 128 * (d_windows ? n_windows : B);
-    const LayerWeights &L0 = *layers_[0];
-    const bool skinny = latency_call && tail_ && qkv2_ && !gemm_naive_ && !attn_naive_ && max_len <= 128 && (dh == 32 || dh == 64) &&
+    const LayerWeights &L0 = w_->layers[0];
+    const bool skinny = latency_call && opt_.tail && opt_.qkv2 && !opt_.gemm_naive && !opt_.attn_naive && max_len <= 128 && (dh == 32 || dh == 64) &&
                         skinny_layer_supported(L0.qkv.w, L0.o.w, L0.ffi.w, L0.ffo.w) && qkv2_shape0;
     p.route = skinny ? Route::LATENCY : one_launch && one_launch_pays ? Route::ONE_LAUNCH : fold ? Route::FOLDED : Route::LAYERED;
     return p;
@@ -661,8 +208,7 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
 bool Engine::gemm(const Plan &p, const char *name, Family f, const GemmWeightStore &W, const void *A, const float *bias, const void *resid,
                   void *C, int epi, std::string &err, const GemmLnFold *ln) {
     static const char *const kernel[] = {"gemm256", "gemm_mfma", "gemm_naive", "gemm_f32"};
-    if (profiling_ && replay_name_.empty())
-        families_[std::string("family:") + kernel[(int)f] + (f == Family::GEMM256 || f == Family::MFMA ? (W.w.type == GW_F16 ? "_f16" : "_q4") : "")] += 1;
+    prof_.count_family(std::string("family:") + kernel[(int)f] + (f == Family::GEMM256 || f == Family::MFMA ? (W.w.type == GW_F16 ? "_f16" : "_q4") : ""));
     const half_t *a = (const half_t *)A, *r = (const half_t *)resid;
     bool ok = !(ln && ln->flags) || f == Family::GEMM256;
     if (ok)
@@ -681,7 +227,7 @@ void Engine::attention(const Plan &p) {
     const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh;
     half_t *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>();
     timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] {
-        if (attn_naive_ || !launch_attention_mfma(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s)) launch_attention_naive(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s);
+        if (opt_.attn_naive || !launch_attention_mfma(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s)) launch_attention_naive(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s);
     });
 }
 
@@ -699,9 +245,9 @@ void Engine::forward_latency(const Plan &p) {
     half_t *x = x_.as<half_t>(), *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>(), *y = y_.as<half_t>(), *ff = ff_.as<half_t>();
     float *v32 = v32_.as<float>();
     for (int il = 0; il < Lz; ++il) {
-        const LayerWeights &L = *layers_[il];
+        const LayerWeights &L = w_->layers[il];
         // (from the second layer on the QKV kernel LayerNorms the previous layer's output itself and writes x)
-        const LayerWeights *P = il ? layers_[il - 1] : nullptr;
+        const LayerWeights *P = il ? &w_->layers[il - 1] : nullptr;
         timed("skinny_qkv", 2.0 * p.T * 3 * H * H, p.s, [&] {
             launch_skinny_gemm(0, L.qkv.w, x, P ? v32 : nullptr, P ? P->ln_out_w.as<float>() : nullptr, P ? P->ln_out_b.as<float>() : nullptr,
                                x, L.qkv_b.as<float>(), nullptr, qkv, nullptr, tb, p.s);
@@ -728,9 +274,9 @@ void Engine::forward_latency(const Plan &p) {
 // form (every window is one whole sentence, whatever list the caller built).
 void Engine::forward_one_launch(const Plan &p) {
     const int H = hp_.n_embd, I = hp_.n_intermediate;
-    ModelLayerWeights mw[16];
+    ModelLayerWeights mw[MODEL_MAX_LAYERS];          // (plan(): model_kernel_supported refuses more layers)
     for (int il = 0; il < hp_.n_layer; ++il) {
-        const LayerWeights &L = *layers_[il];
+        const LayerWeights &L = w_->layers[il];
         mw[il] = {&L.qkv.w, &L.o.w, &L.ffi.w, &L.ffo.w, L.qkv_b.as<float>(), L.o_b.as<float>(), L.ln_att_w.as<float>(), L.ln_att_b.as<float>(),
                   L.ffi_b.as<float>(), L.ffo_b.as<float>(), L.ln_out_w.as<float>(), L.ln_out_b.as<float>()};
     }
@@ -749,7 +295,7 @@ bool Engine::forward_folded(const Plan &p, std::string &err) {
     float2 *st1 = ln_stats1_.as<float2>(), *st2 = ln_stats2_.as<float2>();
     float4 *rows1 = ln_rows1_.as<float4>(), *rows2 = ln_rows2_.as<float4>();
     for (int il = 0; il < hp_.n_layer; ++il) {
-        const LayerWeights &L = *layers_[il];
+        const LayerWeights &L = w_->layers[il];
         GemmLnFold ln;
         if (il == 0) {
             // x = LayerNorm(embeddings), materialised by the embedding kernel: the plain projection (4-bit planes where the file has them)
@@ -781,7 +327,7 @@ bool Engine::forward_layers(const Plan &p, std::string &err) {
     const int H = hp_.n_embd, I = hp_.n_intermediate;
     half_t *x = x_.as<half_t>(), *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>(), *y = y_.as<half_t>(), *ff = ff_.as<half_t>();
     for (int il = 0; il < hp_.n_layer; ++il) {
-        const LayerWeights &L = *layers_[il];
+        const LayerWeights &L = w_->layers[il];
         const LayerPlan &lp = p.layers[il];
         if (lp.qkv2) {
             // windows of 128 token slots holding whole sentences: Q|K|V never reach HBM whatever the sentence lengths
@@ -817,12 +363,12 @@ bool Engine::forward_f32(const Plan &p, std::string &err) {
     const Family F = Family::F32;
     float *x = x_.as<float>(), *qkv = qkv_.as<float>(), *ctx = ctx_.as<float>(), *y = y_.as<float>(), *ff = ff_.as<float>();
     timed("embed_ln", 0.0, p.s, [&] {
-        launch_f32_embed_ln(word_emb_.as<float>(), type_emb_.as<float>(), pos_emb_.as<float>(), ln_e_w_.as<float>(), ln_e_b_.as<float>(), p.tokens,
+        launch_f32_embed_ln(w_->word_emb.as<float>(), w_->type_emb.as<float>(), w_->pos_emb.as<float>(), w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(), p.tokens,
                             p.cu, p.B, p.T, H, hp_.n_vocab, x, p.s);
     });
     tap(p, 0);
     for (int il = 0; il < hp_.n_layer; ++il) {
-        const LayerWeights &L = *layers_[il];
+        const LayerWeights &L = w_->layers[il];
         if (!gemm(p, "gemm_qkv", F, L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS, err)) return false;
         timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] { launch_f32_attention(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s); });
         if (!gemm(p, "gemm_attn_out", F, L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, err)) return false;
@@ -887,13 +433,13 @@ int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, fl
 #endif
     HIP_OK(hipSetDevice(device_), err, -1);
     const int H = hp_.n_embd;
-    // chunks [b0, b1): at most chunk_tokens_ tokens, at least one sentence
+    // chunks [b0, b1): at most opt_.chunk_tokens tokens, at least one sentence
     struct Chunk { int b0, b1, max_len; };
     std::vector<Chunk> chunks;
     size_t max_T = 0, max_nb = 0;
     for (int b0 = 0; b0 < B;) {
         int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
-        while (b1 < B && cu[b1 + 1] - cu[b0] <= chunk_tokens_) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
+        while (b1 < B && cu[b1 + 1] - cu[b0] <= opt_.chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
         chunks.push_back({b0, b1, max_len});
         max_T = std::max(max_T, (size_t)(cu[b1] - cu[b0]));
         max_nb = std::max(max_nb, (size_t)(b1 - b0));
@@ -952,7 +498,7 @@ int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, fl
         }
         const size_t staged = off_w + (size_t)n_windows * sizeof(int2);
         HOST_LAP("staged", i);
-        if (stage_kernel_ && staged <= ((size_t)256 << 10)) {
+        if (opt_.stage_kernel && staged <= ((size_t)256 << 10)) {
             // (a small block — measured up to the 130 KB of a 256 x 128 batch: a few workgroups read it across the host link, the copy
             // engine's start-up is ~20 us of a 0.8 ms call; full 1 MiB chunks stay with the copy engine, off the compute stream)
             launch_stage_copy(sl.d_in_host, sl.d_in.p, staged, stream_);

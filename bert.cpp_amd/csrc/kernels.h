@@ -77,6 +77,7 @@ void launch_layer_tail(const GemmWeight &Wo, const GemmWeight &W1, const GemmWei
                        const float *g2, const float *be2, half_t *out, int M_pad, hipStream_t stream);
 // All encoder layers of a batch in one launch (model_kernel.hip): a workgroup carries its window (whole sentences, at most 128
 // tokens between them) through every layer — the window kernel's and the layer tail's bodies as phases, same bits.
+constexpr int MODEL_MAX_LAYERS = 12;       // (the layers' pointers travel in the kernel's argument block)
 struct ModelLayerWeights {
     const GemmWeight *Wqkv, *Wo, *W1, *W2;
     const float *bqkv, *bo, *g1, *be1, *b1, *b2, *g2, *be2;
@@ -175,7 +176,7 @@ inline void configure_once(DeviceFlags &seen, F &&opt_in) {
 // dispatch itself (no hipEventRecord barrier packets of their own in the stream).  Measured (round 4): a launch timed alone
 // still reads long — model_kernel 825-866 us against 780 us in rocprofv3's trace of the same steps — whatever the events'
 // fence flags; for kernels of a millisecond and more the two agree within 1 %.  These times feed the per-kernel BREAKDOWN; the
-// roofline's kernel time comes from replay groups (engine.hip timed(), bench.py kernel_roofline).
+// roofline's kernel time comes from replay groups (profiler.h timed(), bench.py kernel_roofline).
 // `launches` counts the launches a timed body issued: the event pair is only meaningful for exactly one (a body that returns
 // without launching leaves stale timestamps in pooled events, a body with two launches measures the last one).
 struct LaunchTiming { hipEvent_t start, stop; int launches; };

@@ -3,7 +3,7 @@
 // Format reader contract: reference bert.cpp:342-669 (magic, 7 x i32 hparams, vocab records,
 // tensor records until EOF with per-tensor ftype, name-keyed lookup, shape and byte-size checks).
 // The reference reads tensors straight into a ggml arena; here they land in host byte buffers
-// that the engine then repacks into its HBM layouts (engine.hip).
+// that the engine then repacks into its HBM layouts (weights.cpp).
 #pragma once
 #include <cstdint>
 #include <map>

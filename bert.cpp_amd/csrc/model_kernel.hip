@@ -46,8 +46,6 @@ static __device__ unsigned long long g_tl_model[1024 * 32];
 
 namespace {
 
-constexpr int MODEL_MAX_LAYERS = 12;
-
 struct ModelLayerArgs {              // what differs from layer to layer
     const half_t *wqkv, *wo, *w1p, *w2p;
     const float *bqkv, *bo, *g1, *be1, *b1, *b2, *g2, *be2;

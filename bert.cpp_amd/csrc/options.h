@@ -1,0 +1,41 @@
+// options.h — the switches of an engine, and their two spellings: the BERT_HIP_* environment (read once, when a model loads)
+// and the keys of bert_hip_set_option.  INTEGRATION.md lists both for users.
+#pragma once
+#include <string>
+
+#include "model_file.h"
+
+namespace bert_hip {
+
+struct DevBuf;
+
+struct EngineOptions {
+    bool gemm_naive = false, attn_naive = false;      // the generic kernels (libbert_test.so only)
+    bool qkv2 = true, gemm256 = true, tail = true;
+    bool ln_fold = true;              // H = 768 route: LayerNorm folded into the mat-muls (needs the images: built at load)
+    bool latency = true;
+    bool q4_expand = true;            // q4 files: f16 images and f32 tables built at load (no key: load time only)
+    bool f32_exact = true;            // f32 files take the f32 route unless BERT_HIP_F32=f16 / "f32" = "f16"
+    int one_launch = 1;               // all layers in one launch: 0 never, 1 when it pays (well-filled windows), 2 whenever the kernel takes the batch
+    int chunk_tokens = 262144;
+    // Calls of at most this many tokens take the latency route (skinny.hip).  A call of T tokens keeps ceil(T / 128) CUs busy on
+    // the fused kernels — 615-685 us for anything from 129 to 3000 tokens of all-MiniLM-L6-v2 — while the route's time grows with T
+    // from 220 us: 252 us at 172 tokens (8 sentences), 330 at 363 (16), 376 at 512, 527 at 716, 606 at 1024 (round 5, same bits).
+    int latency_tokens = 768;
+    bool stage_kernel = true;         // small staged blocks come in by a kernel that reads the mapped pinned block, not by the copy engine
+
+    // the defaults for a model of these dimensions, then the environment
+    static EngineOptions from_env(const HParams &hp);
+    // a key of bert_hip_set_option.  naive_images / fold_images: what was built at load (ModelWeights) — "gemm" = "naive" and
+    // "ln_fold" = "1" are refused, with a line on stderr, without them.  Unknown keys are ignored.
+    void set(const std::string &key, const std::string &value, bool naive_images, bool fold_images);
+
+private:
+    void apply(const std::string &key, const std::string &value);
+};
+
+// "test_poison_ctx" (libbert_test.so only; false, doing nothing, in libbert.so): every half of the attention-context workspace
+// becomes a NaN, so a pass that still reads what it has not written itself shows it in its results
+bool test_poison_option(const std::string &key, const DevBuf &ctx);
+
+}  // namespace bert_hip

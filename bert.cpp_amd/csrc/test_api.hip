@@ -30,7 +30,7 @@ int32_t bert_hip_test_gemm(int32_t M, int32_t N, int32_t K, const uint16_t *A, c
     t.type = wtype; t.n_dims = 2; t.ne0 = K; t.ne1 = N; t.data = (const uint8_t *)W;
     t.nbytes = wtype_row_bytes(wtype, K) * (size_t)N;
     GemmWeightStore ws;
-    if (!ws.build({&t}, impl == 1, err)) { fprintf(stderr, "bert_hip_test_gemm: %s\n", err.c_str()); return -1; }
+    if (!ws.build({&t}, PackOptions{impl == 1}, err)) { fprintf(stderr, "bert_hip_test_gemm: %s\n", err.c_str()); return -1; }
     if (impl != 1 && !ws.mfma_ok) { fprintf(stderr, "bert_hip_test_gemm: shape not supported by the MFMA path\n"); return -2; }
     const int M_pad = impl == 3 ? (M + 255) / 256 * 256 : (M + GEMM_BM - 1) / GEMM_BM * GEMM_BM;
     DevBuf dA, dB, dR, dC;
@@ -66,7 +66,7 @@ int32_t bert_hip_test_gemm_lnfold(int32_t M, int32_t K1, int32_t H, int32_t N2, 
     const HostTensor t1 = tensor(W1, H, K1), t2 = tensor(W2, N2, H);
     GemmWeightStore w1, w2;
     DevBuf waug, gb;
-    if (!w1.build({&t1}, false, err) || !w2.build_ln_fold({&t2}, g, be, b2, waug, err)) { fprintf(stderr, "bert_hip_test_gemm_lnfold: %s\n", err.c_str()); return -1; }
+    if (!w1.build({&t1}, PackOptions(), err) || !w2.build_ln_fold({&t2}, g, be, b2, waug, err)) { fprintf(stderr, "bert_hip_test_gemm_lnfold: %s\n", err.c_str()); return -1; }
     const int M_pad = (M + 255) / 256 * 256, P = 2 * H / 256;
     if (!gemm256_supported(w1.w, M_pad) || !gemm256_supported(w2.w, M_pad) || H % 256) return -2;
     DevBuf dA, dB1, dR, dU, dOut, dStats, dRows, dRowsRes;
@@ -147,7 +147,7 @@ int32_t bert_hip_test_qkv_attention(int32_t n_sentences, const int32_t *cu_seqle
     t.type = wtype; t.n_dims = 2; t.ne0 = H; t.ne1 = 3 * H; t.data = (const uint8_t *)Wqkv;
     t.nbytes = wtype_row_bytes(wtype, H) * (size_t)3 * H;
     GemmWeightStore ws;
-    if (!ws.build({&t}, false, err)) { fprintf(stderr, "bert_hip_test_qkv_attention: %s\n", err.c_str()); return -1; }
+    if (!ws.build({&t}, PackOptions(), err)) { fprintf(stderr, "bert_hip_test_qkv_attention: %s\n", err.c_str()); return -1; }
     if (!ws.mfma_ok) return -2;
     DevBuf dx, dqkv, dcu, db, dout;
     if (!dx.alloc((size_t)T_pad * H * 2, err) || !dqkv.alloc((size_t)T_pad * 3 * H * 2, err) ||
@@ -200,7 +200,9 @@ int32_t bert_hip_test_layer_tail(int32_t M, int32_t H, int32_t I, const uint16_t
     t1.type = wtype; t1.n_dims = 2; t1.ne0 = H; t1.ne1 = I; t1.data = (const uint8_t *)W1; t1.nbytes = wtype_row_bytes(wtype, H) * (size_t)I;
     t2.type = wtype; t2.n_dims = 2; t2.ne0 = I; t2.ne1 = H; t2.data = (const uint8_t *)W2; t2.nbytes = wtype_row_bytes(wtype, I) * (size_t)H;
     GemmWeightStore wo, w1, w2;
-    if (!wo.build({&to}, false, err) || !w1.build({&t1}, false, err, true) || !w2.build({&t2}, false, err, true)) {
+    PackOptions kperm;
+    kperm.kperm = true;
+    if (!wo.build({&to}, PackOptions(), err) || !w1.build({&t1}, kperm, err) || !w2.build({&t2}, kperm, err)) {
         fprintf(stderr, "bert_hip_test_layer_tail: %s\n", err.c_str());
         return -1;
     }
@@ -293,6 +295,52 @@ int32_t bert_hip_test_model_digest(const char *fname, int32_t *legacy_q4, uint64
     *legacy_q4 = mf.legacy_q4 ? 1 : 0;
     *digest = h;
     return (int32_t)mf.tensors.size();
+}
+
+int32_t bert_hip_test_pack_weight(const void *W, int32_t wtype, int32_t N, int32_t K, int32_t form, const float *gamma, const float *beta,
+                                  const float *bias, void *out, int64_t out_cap) {
+    const bool stack3 = (form & BERT_HIP_TEST_PACK_STACK3) != 0;
+    form &= ~BERT_HIP_TEST_PACK_STACK3;
+    const bool q4 = wtype == W_Q4_0 || wtype == W_Q4_1;
+    if (!out || N <= 0 || wtype < W_F32 || wtype > W_Q4_1 || (stack3 && N % 3 != 0)) return -1;
+    if (form != 6 && (!W || K <= 0 || (q4 && K % 32 != 0))) return -1;
+    // W as one tensor, or as three of N / 3 rows each, one behind the other (what a stacked Q | K | V matrix is made of)
+    HostTensor part[3];
+    std::vector<const HostTensor *> rows;
+    const int n_parts = stack3 ? 3 : 1;
+    for (int i = 0; form != 6 && i < n_parts; ++i) {
+        HostTensor &t = part[i];
+        t.type = wtype; t.n_dims = 2; t.ne0 = K; t.ne1 = N / n_parts;
+        t.nbytes = wtype_row_bytes(wtype, K) * (size_t)t.ne1;
+        t.data = (const uint8_t *)W + t.nbytes * i;
+        rows.push_back(&t);
+    }
+    StackedRows s;
+    std::string err;
+    if (form != 6 && !s.stack(rows, err)) return -1;
+    auto give = [&](const auto &v) -> int32_t {
+        const size_t bytes = v.size() * sizeof(v[0]);
+        if ((int64_t)bytes > out_cap) return -2;
+        memcpy(out, v.data(), bytes);
+        return (int32_t)bytes;
+    };
+    switch (form) {
+        case 0: return give(pack_f16_image(s, s.N_pad));
+        case 1: return K % 16 ? -1 : give(permute_k16(pack_f16_image(s, s.N_pad)));
+        case 2: case 3: {
+            if (!q4 || !s.mfma_ok) return -1;
+            const Q4Planes pl = pack_q4_planes(s);
+            return give(form == 2 ? pl.qs : pl.sc);
+        }
+        case 4: case 5: {
+            if (!gamma || !beta) return -1;
+            const LnFoldImage f = pack_ln_fold(s, gamma, beta, bias);
+            return give(form == 4 ? f.img : f.aug);
+        }
+        case 6: return gamma && beta && bias ? give(pack_gamma_beta_bias(gamma, beta, bias, N)) : -1;
+        case 7: return q4 && !stack3 ? give(table_as_f32(part[0])) : -1;
+    }
+    return -1;
 }
 
 void bert_hip_test_shard_bounds(const int32_t *cu_seqlens, int32_t n_sentences, int32_t n_shards, int32_t *bounds) {

@@ -35,7 +35,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_layer_tail", "bert_hip_test_shard_bounds", "bert_hip_test_build_windows",
     "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots",
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
-    "bert_hip_test_model_digest",
+    "bert_hip_test_model_digest", "bert_hip_test_pack_weight",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -141,6 +141,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_pool_normalize.argtypes = [i32, vp, i32p, i32, i32, vp, i32p]
     L.bert_hip_test_model_digest.restype = i32
     L.bert_hip_test_model_digest.argtypes = [C.c_char_p, i32p, C.POINTER(C.c_uint64)]
+    L.bert_hip_test_pack_weight.restype = i32
+    L.bert_hip_test_pack_weight.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, C.c_int64]
     L.bert_hip_test_shard_bounds.restype = None
     L.bert_hip_test_shard_bounds.argtypes = [i32p, i32, i32, i32p]
     L.bert_hip_test_build_windows.restype = i32
@@ -190,6 +192,21 @@ def model_digest(path: str):
     if n < 0:
         raise RuntimeError("model file rejected (see stderr)")
     return n, bool(leg.value), int(dig.value)
+
+
+PACK_FORMS = {"f16": 0, "f16_kperm": 1, "q4_nibbles": 2, "q4_scales": 3, "ln_fold": 4, "ln_fold_stats": 5, "gamma_beta_bias": 6, "table_f32": 7}
+
+
+def pack_weight(W, wtype: int, N: int, K: int, form: str, gamma=None, beta=None, bias=None, stack3: bool = False) -> np.ndarray:
+    """The bytes of one weight image as the engine's host code packs it (no GPU needed): W is the tensor in its file layout."""
+    Wb = np.ascontiguousarray(W)
+    f32 = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (gamma, beta, bias)]
+    out = np.zeros((N + 127) // 128 * 128 * max(K, 16) * 4, dtype=np.uint8)
+    n = test_lib().bert_hip_test_pack_weight(Wb.ctypes.data, wtype, N, K, PACK_FORMS[form] | (0x100 if stack3 else 0),
+                                             *(None if a is None else a.ctypes.data for a in f32), out.ctypes.data, out.nbytes)
+    if n < 0:
+        raise RuntimeError(f"bert_hip_test_pack_weight failed: {n}")
+    return out[:n].copy()
 
 
 def shard_bounds(cu_seqlens: np.ndarray, n_shards: int) -> List[int]:

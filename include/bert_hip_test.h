@@ -71,6 +71,18 @@ BERT_API int32_t bert_hip_test_pool_normalize(int32_t H, const uint16_t *x, cons
  * legacy 20 / 24-byte q4 blocks, and a digest of every tensor's name, type and bytes AFTER conversion to the current layout.   */
 BERT_API int32_t bert_hip_test_model_digest(const char *fname, int32_t *legacy_q4, uint64_t *digest);
 
+/* The host side of the weight packing (no GPU): W [N][K] in the file layout of `wtype` (0 f32, 1 f16, 2 q4_0, 3 q4_1) -> the bytes
+ * of one image as the engine uploads it (kernels.h GemmWeight / GemmLnFold).  form: 0 the f16 image [N_pad][K] (N_pad: N rounded up
+ * to 128, the padding rows zero), 1 the same with k order [0-3, 8-11, 4-7, 12-15] inside every group of 16, 2 the q4 nibble plane,
+ * 3 the q4 scale plane (index ((nt (K/64) + kt) 128 + row) 2 + block; q4 `wtype`, K % 64 == 0, N % 8 == 0), 4 the LayerNorm-fold
+ * image [N_pad][K] = f16(W diag(gamma)), 5 the fold's statistics columns [N][16] f16 (gamma, beta; bias may be NULL), 6 the packed
+ * words [N] f16 gamma | f16 (beta + bias) << 16 (W, wtype and K unused), 7 an embedding table of a q4 file as f32 [N][K].
+ * form | BERT_HIP_TEST_PACK_STACK3: W is three tensors of N / 3 rows, one behind the other, packed as one stacked matrix (forms 0-5).
+ * Returns the bytes written to `out` (capacity out_cap), -1 for a request that makes no sense, -2 when out_cap is too small.      */
+#define BERT_HIP_TEST_PACK_STACK3 0x100
+BERT_API int32_t bert_hip_test_pack_weight(const void *W, int32_t wtype, int32_t N, int32_t K, int32_t form, const float *gamma,
+                                           const float *beta, const float *bias, void *out, int64_t out_cap);
+
 /* Host logic of the multi-GPU layer and of the sentence windows, callable without a GPU:
  * shard bounds [n_shards + 1] of a packed batch (multi_device.h), and the {first, count} windows of 128 token slots
  * (engine.h build_windows; returns their number, `windows` holds 2 ints per window, capacity n_sentences).        */
