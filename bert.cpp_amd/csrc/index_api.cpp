@@ -1,0 +1,180 @@
+// index_api.cpp — the bert_hip_index_* entry points of bert_hip.h: an embedding index (search.h) on a context's first device.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/bert_hip.h"
+#include "abi.h"
+
+using namespace bert_hip;
+
+namespace {
+
+// The frame of an entry point that takes an index: -1 (after a line on stderr) without one, else the body's result; a body
+// that returns -3 has put its message into err, and it is printed here.  -4 for an exception.
+template <class F>
+int32_t index_call(const char *me, bert_hip_index *ix, F &&body) {
+    return guarded(me, [&]() -> int32_t {
+        if (!ix || !ix->ix) { fprintf(stderr, "%s: no index\n", me); return -1; }
+        std::string err;
+        const int32_t r = body(ix->ctx, *ix->ix, err);
+        if (r == -3) fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return r;
+    }, (int32_t)-4);
+}
+
+// Tokenizes and evaluates texts in groups on the context's first device; each group's embeddings [c][n_embd] land in the
+// index's device scratch buffer and are handed to use(i0, c, d_rows).  No host copy of the embeddings.
+template <class F>
+bool encode_groups_device(bert_ctx *ctx, Index &ix, int32_t n_threads, int32_t n, const char **texts, F &&use, std::string &err) {
+    const int32_t H = ctx->hp.n_embd, G = 16384;
+    TokenGroup &g = ctx->texts.group[0];
+    for (int32_t i0 = 0; i0 < n; i0 += G) {
+        const int32_t c = std::min(G, n - i0);
+        g.tokenize(ctx->texts, n_threads, c, texts + i0);
+        if (g.n_ok < c) { err = "input " + std::to_string(i0 + g.n_ok) + " cannot be evaluated"; return false; }
+        float *d = ix.scratch((size_t)c * H, err);
+        if (!d) return false;
+        // (blocking: the rows are in d when it returns)
+        if (ctx->engine()->eval_packed_host(g.packed.get(), g.cu.data(), c, nullptr, err, d) != 0) return false;
+        if (!use(i0, c, d)) return false;
+    }
+    return true;
+}
+
+// the multi-device route of the text entry points: bert_hip_encode_batch into host rows
+bool encode_host(bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts, std::vector<float> &emb, std::string &err) {
+    const size_t H = ctx->hp.n_embd;
+    emb.assign((size_t)n * H, 0.f);
+    std::vector<float *> rows((size_t)n);
+    for (int32_t i = 0; i < n; ++i) rows[i] = emb.data() + i * H;
+    const int32_t done = encode_batch_impl(ctx, n_threads, n, texts, rows.data());
+    if (done != n) { err = "input " + std::to_string(std::max(done, 0)) + " could not be encoded"; return false; }
+    return true;
+}
+
+// (-2 after a line on stderr: the index does not hold this model's embeddings)
+bool dim_ok(const char *me, const bert_ctx *ctx, const Index &x) {
+    if (x.dim() != ctx->hp.n_embd) fprintf(stderr, "%s: the index has dim %d, the model's embeddings %d\n", me, x.dim(), ctx->hp.n_embd);
+    return x.dim() == ctx->hp.n_embd;
+}
+
+}  // namespace
+
+extern "C" {
+
+struct bert_hip_index *bert_hip_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype) {
+    return guarded("bert_hip_index_create", [&]() -> bert_hip_index * {
+        const char *me = "bert_hip_index_create";
+        if (!ctx) { fprintf(stderr, "%s: no context\n", me); return nullptr; }
+        if (!ctx->engine()) { fprintf(stderr, "%s: this context has no device (tokenizer-only): an index lives on the context's device\n", me); return nullptr; }
+        if (dim == 0) dim = ctx->hp.n_embd;
+        std::string err;
+        std::unique_ptr<Index> ix(Index::create(ctx->engine(), dim, dtype, err));
+        if (!ix) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return nullptr; }
+        std::unique_ptr<bert_hip_index> h(new bert_hip_index);
+        h->ctx = ctx;
+        h->ix = std::move(ix);
+        ctx->indexes.push_back(h.get());
+        return h.release();
+    }, (bert_hip_index *)nullptr);
+}
+
+void bert_hip_index_free(struct bert_hip_index *ix) {
+    guarded("bert_hip_index_free", [&] {
+        if (!ix) return;
+        auto &v = ix->ctx->indexes;
+        v.erase(std::remove(v.begin(), v.end(), ix), v.end());
+        delete ix;
+    });
+}
+
+int32_t bert_hip_index_size(struct bert_hip_index *ix) { return ix && ix->ix ? ix->ix->size() : -1; }
+
+int32_t bert_hip_index_reserve(struct bert_hip_index *ix, int32_t n_rows, int32_t n_queries, int32_t k) {
+    return index_call("bert_hip_index_reserve", ix, [&](bert_ctx *, Index &x, std::string &err) { return x.reserve(n_rows, n_queries, k, err) ? 0 : -3; });
+}
+
+int32_t bert_hip_index_add(struct bert_hip_index *ix, int32_t n, const float *rows) {
+    return index_call("bert_hip_index_add", ix, [&](bert_ctx *, Index &x, std::string &err) {
+        const int first = x.add_host(n, rows, err);
+        return first < 0 ? -3 : first;
+    });
+}
+
+int32_t bert_hip_index_add_device(struct bert_hip_index *ix, int32_t n, const float *d_rows, void *stream) {
+    return index_call("bert_hip_index_add_device", ix, [&](bert_ctx *, Index &x, std::string &err) {
+        const int first = x.add_device(n, d_rows, (hipStream_t)stream, err);
+        return first < 0 ? -3 : first;
+    });
+}
+
+int32_t bert_hip_index_add_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n, const char **texts) {
+    const char *me = "bert_hip_index_add_texts";
+    return index_call(me, ix, [&](bert_ctx *ctx, Index &x, std::string &err) -> int32_t {
+        if (!dim_ok(me, ctx, x)) return -2;
+        if (n < 0 || (n > 0 && !texts)) { fprintf(stderr, "%s: n >= 0 and texts required\n", me); return -2; }
+        const int first = x.size();
+        if (n == 0) return first;
+        bool ok;
+        if (ctx->engines.size() > 1) {
+            std::vector<float> emb;
+            ok = encode_host(ctx, n_threads, n, texts, emb, err) && x.add_host(n, emb.data(), err) >= 0;
+        } else {
+            ok = encode_groups_device(ctx, x, n_threads, n, texts, [&](int32_t, int32_t c, const float *d) {
+                return x.add_device(c, d, x.stream(), err) >= 0 && hipStreamSynchronize(x.stream()) == hipSuccess;
+            }, err);
+        }
+        if (ok) return first;
+        x.truncate(first);
+        if (err.empty()) err = "device error";
+        return -3;
+    });
+}
+
+int32_t bert_hip_index_search(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t k, int32_t *ids, float *scores) {
+    return index_call("bert_hip_index_search", ix, [&](bert_ctx *, Index &x, std::string &err) {
+        return x.search_to_host(n_queries, queries, false, k, ids, scores, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t k, int32_t *d_ids,
+                                     float *d_scores, void *stream) {
+    return index_call("bert_hip_index_search_device", ix, [&](bert_ctx *, Index &x, std::string &err) {
+        return x.search_device(n_queries, d_queries, k, d_ids, d_scores, (hipStream_t)stream, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n_queries, const char **texts, int32_t k,
+                                    int32_t *ids, float *scores) {
+    const char *me = "bert_hip_index_search_texts";
+    return index_call(me, ix, [&](bert_ctx *ctx, Index &x, std::string &err) -> int32_t {
+        if (!dim_ok(me, ctx, x)) return -2;
+        if (k < 1 || k > Index::MAX_K) { fprintf(stderr, "%s: k must be 1 .. 256\n", me); return -2; }
+        if (n_queries < 0 || (n_queries > 0 && (!texts || !ids || !scores))) { fprintf(stderr, "%s: n_queries >= 0 and texts / outputs required\n", me); return -2; }
+        if (n_queries == 0) return 0;
+        bool ok;
+        // (results land in a buffer of our own: the caller's outputs stay untouched on an error)
+        std::vector<int32_t> hid((size_t)n_queries * k);
+        std::vector<float> hsc((size_t)n_queries * k);
+        if (ctx->engines.size() > 1) {
+            std::vector<float> emb;
+            ok = encode_host(ctx, n_threads, n_queries, texts, emb, err) && x.search_to_host(n_queries, emb.data(), false, k, hid.data(), hsc.data(), err) == 0;
+        } else {
+            ok = encode_groups_device(ctx, x, n_threads, n_queries, texts, [&](int32_t i0, int32_t c, const float *d) {
+                return x.search_to_host(c, d, true, k, hid.data() + (size_t)i0 * k, hsc.data() + (size_t)i0 * k, err) == 0;
+            }, err);
+        }
+        if (!ok) {
+            if (err.empty()) err = "device error";
+            return -3;
+        }
+        memcpy(ids, hid.data(), hid.size() * 4);
+        memcpy(scores, hsc.data(), hsc.size() * 4);
+        return 0;
+    });
+}
+
+}  // extern "C"

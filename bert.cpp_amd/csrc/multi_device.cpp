@@ -142,6 +142,12 @@ int ShardWorkers::run(const std::vector<int> &bounds, const std::function<int(in
     return 0;
 }
 
+int ShardWorkers::run_each(int n, const std::function<int(int)> &f, std::string *err) {
+    std::vector<int> each((size_t)n + 1);
+    for (int k = 0; k <= n; ++k) each[k] = k;                   // "shard" k = turn k
+    return run(each, [&](int k, int, int) { return f(k); }, err);
+}
+
 // ---- RCCL through dlopen: the handful of entry points the exchange needs (NCCL C API, stable ABI)
 namespace {
 typedef int (*fn_comm_init_all)(void **comms, int ndev, const int *devlist);

@@ -33,6 +33,9 @@ public:
     // receives the message of an exception thrown by eval (result -9).  Calls are serialised by the caller (a bert_ctx is not
     // thread-safe, like the reference's).
     int run(const std::vector<int> &bounds, const std::function<int(int, int, int)> &eval, std::string *err = nullptr);
+    // one turn per thread: f(k) for k = 0 .. n - 1, turn k on worker k - 1, turn 0 (and a turn without a worker) on the caller.
+    // Results as run's.
+    int run_each(int n, const std::function<int(int)> &f, std::string *err = nullptr);
     // threads this process has created for shard work so far (test hook: a thousand calls must not create a thousand threads)
     static long threads_created();
 

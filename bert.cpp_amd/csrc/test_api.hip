@@ -7,8 +7,7 @@
 #include "../../include/bert_hip_test.h"
 #include <stdexcept>
 
-#include "engine.h"
-#include "multi_device.h"
+#include "context.h"
 
 using namespace bert_hip;
 
@@ -394,6 +393,49 @@ int32_t bert_hip_test_dispatch(const bert_vocab_id *tokens, const int32_t *cu_se
         }
         return 0;
     });
+}
+
+int32_t bert_hip_test_parse_devices(const char *list, int32_t n_devices, int32_t current, int32_t *devs, char *err, int32_t err_cap) {
+    std::vector<int> d;
+    std::string e;
+    if (!parse_device_list(list, n_devices, current, d, e)) {
+        snprintf(err, (size_t)err_cap, "%s", e.c_str());
+        return -1;
+    }
+    for (size_t i = 0; i < d.size(); ++i) devs[i] = d[i];
+    return (int32_t)d.size();
+}
+
+int32_t bert_hip_test_gather_runs(const int32_t *cu_seqlens, int32_t n_sentences, int64_t tokens_per_run, int32_t *runs) {
+    std::vector<int> r;
+    gather_runs(cu_seqlens, n_sentences, tokens_per_run, r);
+    for (size_t i = 0; i < r.size(); ++i) runs[i] = r[i];
+    return (int32_t)r.size();
+}
+
+int32_t bert_hip_test_encode_groups(int32_t n_inputs, int32_t *groups, int32_t cap) {
+    int32_t k = 0;
+    for (int32_t left = n_inputs; left > 0; ++k) {
+        const int32_t n = encode_group_size(k, left);
+        if (k < cap) groups[k] = n;
+        left -= n;
+    }
+    return k;
+}
+
+int32_t bert_hip_test_tokenize_pack(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts, const int32_t *counts,
+                                    int32_t *n_tokens, int32_t *cu, bert_vocab_id *packed, int32_t packed_cap) {
+    TokenGroup &g = ctx->texts.group[0];
+    g.tokenize(ctx->texts, n_threads, n, texts);
+    if (counts) {
+        std::copy(counts, counts + n, g.n_tokens.begin());
+        g.pack(ctx->texts.n_max_tokens, n);
+    }
+    if (g.cu[g.n_ok] > packed_cap) return -1;
+    std::copy(g.n_tokens.begin(), g.n_tokens.end(), n_tokens);
+    std::copy(g.cu.begin(), g.cu.begin() + g.n_ok + 1, cu);
+    std::copy(g.packed.get(), g.packed.get() + g.cu[g.n_ok], packed);
+    return g.n_ok;
 }
 
 }  // extern "C"

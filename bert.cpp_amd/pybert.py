@@ -35,7 +35,8 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_layer_tail", "bert_hip_test_shard_bounds", "bert_hip_test_build_windows",
     "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots",
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
-    "bert_hip_test_model_digest", "bert_hip_test_pack_weight",
+    "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
+    "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -157,6 +158,14 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_shard_threads_created.argtypes = []
     L.bert_hip_test_dispatch.restype = i32
     L.bert_hip_test_dispatch.argtypes = [i32p, i32p, i32, i32, i32, C.POINTER(C.c_float)]
+    L.bert_hip_test_parse_devices.restype = i32
+    L.bert_hip_test_parse_devices.argtypes = [C.c_char_p, i32, i32, i32p, C.c_char_p, i32]
+    L.bert_hip_test_gather_runs.restype = i32
+    L.bert_hip_test_gather_runs.argtypes = [i32p, i32, C.c_int64, i32p]
+    L.bert_hip_test_encode_groups.restype = i32
+    L.bert_hip_test_encode_groups.argtypes = [i32, i32p, i32]
+    L.bert_hip_test_tokenize_pack.restype = i32
+    L.bert_hip_test_tokenize_pack.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32p, i32p, i32p, i32p, i32]
     _test_lib = L
     return L
 
@@ -248,6 +257,44 @@ def dispatch_stub(tokens: np.ndarray, cu_seqlens: np.ndarray, n_shards: int, H: 
 
 def shard_threads_created() -> int:
     return int(test_lib().bert_hip_test_shard_threads_created())
+
+
+def parse_devices(spec: Optional[bytes], n_devices: int, current: int = 0):
+    """(devices, None) or (None, message): the device list of BERT_HIP_DEVICES as the context's loader reads it (no GPU needed)."""
+    devs = np.zeros(max(n_devices, 1), dtype=np.int32)
+    err = C.create_string_buffer(512)
+    n = test_lib().bert_hip_test_parse_devices(spec, n_devices, current, _i32p(devs), err, len(err))
+    return (None, err.value.decode()) if n < 0 else (devs[:n].tolist(), None)
+
+
+def gather_runs(cu_seqlens: np.ndarray, tokens_per_run: int) -> List[int]:
+    cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    out = np.zeros(len(cu), dtype=np.int32)
+    n = test_lib().bert_hip_test_gather_runs(_i32p(cu), len(cu) - 1, tokens_per_run, _i32p(out))
+    return out[:n].tolist()
+
+
+def encode_groups(n_inputs: int) -> List[int]:
+    out = np.zeros(1024, dtype=np.int32)
+    n = test_lib().bert_hip_test_encode_groups(n_inputs, _i32p(out), len(out))
+    assert n <= len(out)
+    return out[:n].tolist()
+
+
+def tokenize_pack(model: "BertModel", texts: Sequence[bytes], n_threads: int, counts=None):
+    """(n_ok, counts, cu, packed ids) of the text entry points' tokenize + pack step; `model` must live in libbert_test.so
+    (test_routes=True).  counts: pack with these counts instead of the tokenizer's."""
+    n, N = len(texts), model.n_max_tokens
+    arr = (C.c_char_p * n)(*texts)
+    cnt = np.zeros(n, dtype=np.int32)
+    cu = np.full(n + 1, -1, dtype=np.int32)
+    packed = np.full(n * N, -1, dtype=np.int32)
+    given = None if counts is None else np.ascontiguousarray(counts, dtype=np.int32)
+    n_ok = test_lib().bert_hip_test_tokenize_pack(model.ctx, n_threads, n, arr, None if given is None else _i32p(given), _i32p(cnt),
+                                                  _i32p(cu), _i32p(packed), len(packed))
+    if n_ok < 0:
+        raise RuntimeError("bert_hip_test_tokenize_pack failed")
+    return n_ok, cnt.tolist(), cu[:n_ok + 1].tolist(), packed[:cu[n_ok]].tolist()
 
 
 def _f32p(a: np.ndarray):

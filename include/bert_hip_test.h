@@ -103,6 +103,28 @@ BERT_API int32_t bert_hip_test_dispatch(const bert_vocab_id *tokens, const int32
 /* Threads this process has created for shard work so far (ShardWorkers): repeated calls must not create threads.          */
 BERT_API int64_t bert_hip_test_shard_threads_created(void);
 
+
+/* Host logic of the API layer, callable without a GPU.
+ * The device list of BERT_HIP_DEVICES (context.h parse_device_list) on a box of n_devices devices whose caller's current device
+ * is `current`: returns the number of devices written to devs (capacity n_devices), or -1 with the message in err (err_cap bytes). */
+BERT_API int32_t bert_hip_test_parse_devices(const char *list, int32_t n_devices, int32_t current, int32_t *devs, char *err,
+                                             int32_t err_cap);
+/* The super-batch cut of bert_hip_eval_packed_gather (gather.h gather_runs): returns the number of entries written to runs
+ * (capacity n_sentences + 1).                                                                                                  */
+BERT_API int32_t bert_hip_test_gather_runs(const int32_t *cu_seqlens, int32_t n_sentences, int64_t tokens_per_run, int32_t *runs);
+/* The group sizes bert_encode_batch cuts n_inputs texts into (text_batch.h encode_group_size): returns their number, the first
+ * `cap` of them in groups.                                                                                                      */
+BERT_API int32_t bert_hip_test_encode_groups(int32_t n_inputs, int32_t *groups, int32_t cap);
+/* The tokenize + validate + pack step of the text entry points (text_batch.h TokenGroup) on the context's first group; works on
+ * a tokenizer-only context.  counts == NULL: tokenizes n texts on n_threads threads and packs them.  counts != NULL: the same,
+ * but the pack step runs on these n counts instead of the tokenizer's (how a text that cannot be evaluated is produced: the
+ * tokenizer truncates, so no text gives a count outside 1 .. n_max_tokens).  n_tokens [n] receives the counts packed with,
+ * cu [n + 1] the prefix sums (n_ok + 1 entries are written), packed the ids back to back.  Returns n_ok, the number of texts in
+ * front of the first one that cannot be evaluated, or -1 if packed_cap ids do not hold the result.                             */
+BERT_API int32_t bert_hip_test_tokenize_pack(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts,
+                                             const int32_t *counts, int32_t *n_tokens, int32_t *cu, bert_vocab_id *packed,
+                                             int32_t packed_cap);
+
 #ifdef __cplusplus
 }
 #endif
