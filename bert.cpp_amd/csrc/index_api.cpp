@@ -2,11 +2,15 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include <sys/stat.h>
+
 #include "../../include/bert_hip.h"
 #include "abi.h"
+#include "index_file.h"
 
 using namespace bert_hip;
 
@@ -60,6 +64,17 @@ bool dim_ok(const char *me, const bert_ctx *ctx, const Index &x) {
     if (x.dim() != ctx->hp.n_embd) fprintf(stderr, "%s: the index has dim %d, the model's embeddings %d\n", me, x.dim(), ctx->hp.n_embd);
     return x.dim() == ctx->hp.n_embd;
 }
+
+// an allow-list of n_words words covers the index (-2 after a line on stderr otherwise)
+bool allow_ok(const char *me, const Index &x, const uint32_t *allow, int32_t n_words) {
+    const int64_t need = ((int64_t)x.size() + 31) / 32;
+    if (allow && n_words < need) fprintf(stderr, "%s: the allow-list has %d words, an index of %d rows needs %lld\n", me, n_words, x.size(), (long long)need);
+    return !allow || n_words >= need;
+}
+
+struct FileCloser {
+    void operator()(FILE *f) const { if (f) fclose(f); }
+};
 
 }  // namespace
 
@@ -145,6 +160,69 @@ int32_t bert_hip_index_search_device(struct bert_hip_index *ix, int32_t n_querie
     return index_call("bert_hip_index_search_device", ix, [&](bert_ctx *, Index &x, std::string &err) {
         return x.search_device(n_queries, d_queries, k, d_ids, d_scores, (hipStream_t)stream, err) != 0 ? -3 : 0;
     });
+}
+
+int32_t bert_hip_index_search_filtered(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t k, const uint32_t *allow,
+                                       int32_t n_words, int32_t *ids, float *scores) {
+    const char *me = "bert_hip_index_search_filtered";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!allow_ok(me, x, allow, n_words)) return -2;
+        return x.search_to_host(n_queries, queries, false, k, ids, scores, err, allow) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_filtered_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t k,
+                                              const uint32_t *d_allow, int32_t n_words, int32_t *d_ids, float *d_scores, void *stream) {
+    const char *me = "bert_hip_index_search_filtered_device";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!allow_ok(me, x, d_allow, n_words)) return -2;
+        return x.search_device(n_queries, d_queries, k, d_ids, d_scores, (hipStream_t)stream, err, d_allow) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_remove(struct bert_hip_index *ix, int32_t n, const int32_t *ids) {
+    return index_call("bert_hip_index_remove", ix, [&](bert_ctx *, Index &x, std::string &err) {
+        const int r = x.remove(n, ids, err);
+        return r < 0 ? -3 : r;
+    });
+}
+
+int32_t bert_hip_index_n_live(struct bert_hip_index *ix) { return ix && ix->ix ? ix->ix->n_live() : -1; }
+
+int32_t bert_hip_index_compact(struct bert_hip_index *ix, int32_t *old_ids) {
+    return index_call("bert_hip_index_compact", ix, [&](bert_ctx *, Index &x, std::string &err) {
+        const int r = x.compact(old_ids, err);
+        return r < 0 ? -3 : r;
+    });
+}
+
+int32_t bert_hip_index_save(struct bert_hip_index *ix, const char *path) {
+    return index_call("bert_hip_index_save", ix, [&](bert_ctx *, Index &x, std::string &err) { return x.save(path, err) ? 0 : -3; });
+}
+
+struct bert_hip_index *bert_hip_index_load(struct bert_ctx *ctx, const char *path) {
+    return guarded("bert_hip_index_load", [&]() -> bert_hip_index * {
+        const char *me = "bert_hip_index_load";
+        if (!ctx) { fprintf(stderr, "%s: no context\n", me); return nullptr; }
+        if (!ctx->engine()) { fprintf(stderr, "%s: this context has no device (tokenizer-only): an index lives on the context's device\n", me); return nullptr; }
+        if (!path) { fprintf(stderr, "%s: no path\n", me); return nullptr; }
+        std::unique_ptr<FILE, FileCloser> f(fopen(path, "rb"));
+        struct stat st;
+        if (!f || fstat(fileno(f.get()), &st) != 0 || !S_ISREG(st.st_mode)) { fprintf(stderr, "%s: cannot read '%s'\n", me, path); return nullptr; }
+        // everything the header promises is checked, against the file's length too, before anything is allocated
+        unsigned char hdr[INDEX_HEADER_BYTES];
+        const size_t got = fread(hdr, 1, sizeof hdr, f.get());
+        IndexFileHeader h;
+        std::string err;
+        if (!index_header_check(hdr, got, (uint64_t)st.st_size, h, err)) { fprintf(stderr, "%s: '%s': %s\n", me, path, err.c_str()); return nullptr; }
+        std::unique_ptr<Index> ix(Index::create(ctx->engine(), (int)h.dim, (int)h.dtype, err));
+        if (!ix || !ix->load_rows(f.get(), h, err)) { fprintf(stderr, "%s: '%s': %s\n", me, path, err.c_str()); return nullptr; }
+        std::unique_ptr<bert_hip_index> out(new bert_hip_index);
+        out->ctx = ctx;
+        out->ix = std::move(ix);
+        ctx->indexes.push_back(out.get());
+        return out.release();
+    }, (bert_hip_index *)nullptr);
 }
 
 int32_t bert_hip_index_search_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n_queries, const char **texts, int32_t k,

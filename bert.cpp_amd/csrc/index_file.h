@@ -1,0 +1,32 @@
+// index_file.h — the file form of an embedding index (bert_hip_index_save / _load; the format is stated in include/bert_hip.h).
+// Plain host C++: what a stored row looks like for each dtype, the 64-byte header, and the one check a file passes before
+// anything is allocated for it.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+namespace bert_hip {
+
+constexpr size_t INDEX_HEADER_BYTES = 64;
+constexpr uint32_t INDEX_FILE_VERSION = 1;
+constexpr int INDEX_MAX_DIM = 2048;
+
+// bytes per stored element of dtype 0 (f32), 1 (f16), 2 (i8); 0 for any other dtype
+int index_elem_size(int dtype);
+// elements per stored row: dim rounded up to the score kernel's k-step (8 floats, 16 halves, 32 bytes)
+int index_dpad(int dtype, int dim);
+
+struct IndexFileHeader {
+    uint32_t version = INDEX_FILE_VERSION, dtype = 0, dim = 0, dpad = 0, n_rows = 0, has_live = 0;
+};
+
+// the length of the file this header describes: header, rows, i8 scales, live words
+uint64_t index_file_bytes(const IndexFileHeader &h);
+// the header's 64 bytes, little-endian
+void index_header_write(const IndexFileHeader &h, unsigned char out[INDEX_HEADER_BYTES]);
+// Parses and checks the first buf_len bytes of a file of file_bytes bytes: magic, version, dtype 0 .. 2, dim 1 .. 2048, dpad as
+// index_dpad gives it, reserved bytes zero, has_live 0 or 1, and file_bytes exactly index_file_bytes.  false + err otherwise.
+bool index_header_check(const void *buf, size_t buf_len, uint64_t file_bytes, IndexFileHeader &h, std::string &err);
+
+}  // namespace bert_hip

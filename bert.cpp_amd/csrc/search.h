@@ -3,19 +3,27 @@
 // zero-padded to the k-step of the score kernel's MFMA.  A search is a GEMM (queries x rows x dim) whose epilogue selects
 // instead of storing: index_topk_kernel keeps a top-k per (query, slice of rows) in LDS, topk_merge_kernel merges the
 // slices' lists per query.  The score matrix never reaches HBM.
+//
+// Removed rows: from the first remove() on, the index keeps one bit per row (set = live) in device words [ceil(cap / 32)] and
+// in a host mirror; bits at and beyond size() are zero in the mirror and ignored on the device.  A search then (or with an
+// allow-list, a second bitmap of the same shape from the caller) runs the masked instantiation of index_topk_kernel.  An
+// index that never saw a removal has no bitmap and launches what it always did.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <string>
+#include <vector>
 
 #include "engine.h"
+#include "index_file.h"
 
 namespace bert_hip {
 
 class Index {
 public:
-    static constexpr int MAX_K = 256, MAX_DIM = 2048;
+    static constexpr int MAX_K = 256, MAX_DIM = INDEX_MAX_DIM;
     static constexpr int QCHUNK = 4096;                  // queries per internal pass (workspace bound)
 
     // dtype 0: f32 rows, 1: f16 rows (queries rounded to f16 as well), 2: i8 rows with one f32 scale each (queries quantized
@@ -24,6 +32,7 @@ public:
     ~Index();
 
     int size() const { return n_; }
+    int n_live() const { return n_ - n_removed_; }
     int dim() const { return dim_; }
     int dtype() const { return dtype_; }
     hipStream_t stream() const { return stream_; }
@@ -33,14 +42,27 @@ public:
     // append f32 rows [n][dim]: the first new id, -1 on error (index unchanged)
     int add_device(int n, const float *d_rows, hipStream_t s, std::string &err);     // asynchronous on s
     int add_host(int n, const float *rows, std::string &err);                        // blocking
-    // ids / scores [nq][k], best first; 0 or -1
-    int search_device(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err);
-    // host results (written only on success), queries in host (q_on_device = false) or device memory; blocking
-    int search_to_host(int nq, const float *q, bool q_on_device, int k, int32_t *ids, float *scores, std::string &err);
+    // ids / scores [nq][k], best first; 0 or -1.  d_allow: null, or device words (bit b of word w set = row 32 w + b may be
+    // returned), at least ceil(size / 32) of them
+    int search_device(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err,
+                      const uint32_t *d_allow = nullptr);
+    // host results (written only on success), queries in host (q_on_device = false) or device memory; allow: null or host
+    // words as above; blocking
+    int search_to_host(int nq, const float *q, bool q_on_device, int k, int32_t *ids, float *scores, std::string &err,
+                       const uint32_t *allow = nullptr);
+    // marks rows as removed (ids in [0, size) or -1 with the index unchanged; repeats ignored): the number newly removed; blocking
+    int remove(int n, const int32_t *ids, std::string &err);
+    // drops the removed rows' storage: live rows keep order and bits, ids 0 .. n_live - 1; old_ids (null or [n_live]) the
+    // former ids; the new size or -1; blocking
+    int compact(int32_t *old_ids, std::string &err);
+    // the index as stored to / from a file (index_file.h); load_rows: into an empty index made for the header's dim and dtype,
+    // f positioned behind the header
+    bool save(const char *path, std::string &err);
+    bool load_rows(FILE *f, const IndexFileHeader &h, std::string &err);
     // a device f32 buffer of at least n floats for the text routes (the index's operations that read it are finished)
     float *scratch(size_t n, std::string &err);
     // forget the rows behind the first n (an add of several parts that failed part way)
-    void truncate(int n) { if (n >= 0 && n < n_) n_ = n; }
+    void truncate(int n);
 
 private:
     Index() = default;
@@ -49,7 +71,10 @@ private:
     static size_t ws_entries_bound(int n_rows, int nq, int k);
     bool grow_rows(int n_rows, std::string &err);
     bool grow(DevBuf &b, size_t bytes, std::string &err);
-    void enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s);
+    void enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow);
+    bool make_live(std::string &err);
+    bool upload_live(size_t w0, size_t w1, std::string &err);
+    void drop_live();
 
     Engine *eng_ = nullptr;
     int dim_ = 0, dtype_ = 0, dpad_ = 0, es_ = 4;       // dpad_: elements per stored row, es_: bytes per element
@@ -58,6 +83,11 @@ private:
     float *rscale_ = nullptr;                           // i8: [cap_] row scales
     DevBuf ws_s_, ws_i_, qbuf_;                         // per-(query, slice) lists; the current chunk's queries as stored
     DevBuf qscale_;                                     // i8: the current chunk's query scales
+    // removed rows: device words [ceil(cap_ / 32)] (null until the first remove) and their host mirror of the same length
+    uint32_t *live_ = nullptr;
+    std::vector<uint32_t> live_h_;
+    int n_removed_ = 0;
+    DevBuf allow_;                                      // host route: the caller's allow-list on the device
     DevBuf stage_, out_ids_, out_scores_, scratch_;     // host routes: f32 rows / queries, results; the text routes' embeddings
     hipStream_t stream_ = nullptr;                      // the host routes' stream
     // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event

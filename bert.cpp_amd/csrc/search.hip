@@ -12,6 +12,12 @@
 //                         workgroup writes one sorted top-k list per query to the workspace.
 //   topk_merge_kernel     one workgroup per query: the same threshold / queue / sort over the slices' lists, then the
 //                         final ids and scores.
+//                         The masked instantiations (TopkArgsMasked / TopkArgsI8Masked: an index with removed rows, or a
+//                         search with an allow-list) read one word of each bitmap per wave and step — the wave's block is
+//                         the 32 rows of that word —, score and push only the rows whose bit of live & allow is set, and
+//                         skip the loads and MFMAs of a block whose combined word is zero.
+//   index_gather_kernel   compaction: stored rows (and i8 scales) of the listed old ids into a fresh allocation.
+//   live_set_range_kernel sets the live bits of newly added rows.
 //   index_convert_kernel  f32 rows (added rows, queries) -> the stored form: f32 or f16 (RNE), zero-padded to dpad.
 //   index_quantize_kernel f32 rows (added rows, queries) -> the i8 form: one wave per row, codes zero-padded to dpad and one
 //                         f32 scale per row.
@@ -30,6 +36,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstdio>
 #include <cmath>
 #include <cstring>
 #include <type_traits>
@@ -170,11 +177,21 @@ struct TopkArgsI8 : TopkArgs {
     const float *qscale, *rscale;        // [nq], [n_rows]
 };
 
+// (types of their own again: the three kernels above keep their argument blocks.)  live, allow: words [ceil(n_rows / 32)],
+// bit b of word w set = row 32 w + b is live / may be returned; either may be null = all ones
+struct TopkArgsMasked : TopkArgs {
+    const uint32_t *live, *allow;
+};
+struct TopkArgsI8Masked : TopkArgsI8 {
+    const uint32_t *live, *allow;
+};
+template <class Args> constexpr bool is_masked_v = std::is_same_v<Args, TopkArgsMasked> || std::is_same_v<Args, TopkArgsI8Masked>;
+
 // LDS: float scores [nqv][L], int ids [nqv][L], int count [nqv] — per query the current top-k in [0, k), the queue behind
-// (Args: TopkArgsI8 for T = int8_t, TopkArgs otherwise)
+// (Args: TopkArgsI8 for T = int8_t, TopkArgs otherwise; their masked forms)
 template <class T, class Args>
 __global__ __launch_bounds__(NT) void index_topk_kernel(Args a) {
-    constexpr bool I8 = std::is_same_v<T, int8_t>;
+    constexpr bool I8 = std::is_same_v<T, int8_t>, MASKED = is_masked_v<Args>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // workgroup b runs on XCD b % 8: consecutive items — the query tiles of one slice of rows — go to one XCD, so that
     // they find the slice in that XCD's L2 (the grid is a multiple of 8; items beyond n_items do nothing)
@@ -212,18 +229,34 @@ __global__ __launch_bounds__(NT) void index_topk_kernel(Args a) {
     const int room = L - k - STEP_ROWS;
     for (int base = r0; base < r1; base += STEP_ROWS) {
         const int row = base + wave * 32 + col;
-        const bool rok = row < r1;
-        const T *rp = (const T *)a.rows + (size_t)(rok ? row : r0) * a.dpad;
+        bool rok = row < r1;
+        // masked: r0 and the step are multiples of 128, so the wave's 32 rows are the bits of one word, the same for all
+        // its lanes; a block that starts at or beyond r1 has no word
+        [[maybe_unused]] uint32_t word = 0;
+        if constexpr (MASKED) {
+            const int blk = __builtin_amdgcn_readfirstlane(base + wave * 32);
+            if (blk < r1) {
+                word = ~0u;
+                if (a.live) word &= a.live[blk >> 5];
+                if (a.allow) word &= a.allow[blk >> 5];
+            }
+            word = __builtin_amdgcn_readfirstlane(word);
+            rok = rok && ((word >> col) & 1u);           // (a row that does not qualify is a zero operand and never pushed)
+        }
         f32x16 acc = {};
-        if constexpr (I8) {
-            const float rs = a.rscale[rok ? row : r0];
-            i32x16 dot = {};
-            ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, dot);
-            // (two multiplies in this order and no add: nothing the compiler could contract)
+        // (masked: a block without a qualifying row costs no loads and no MFMAs — wave-uniform, and the barriers are below)
+        if (!MASKED || word != 0) {
+            const T *rp = (const T *)a.rows + (size_t)(rok ? row : r0) * a.dpad;
+            if constexpr (I8) {
+                const float rs = a.rscale[rok ? row : r0];
+                i32x16 dot = {};
+                ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, dot);
+                // (two multiplies in this order and no add: nothing the compiler could contract)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = ((float)dot[r] * qs[r]) * rs;
-        } else {
-            ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, acc);
+                for (int r = 0; r < 16; ++r) acc[r] = ((float)dot[r] * qs[r]) * rs;
+            } else {
+                ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, acc);
+            }
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -372,6 +405,47 @@ void launch_quantize(const float *src, void *codes, float *scales, int n, int di
     BERT_LAUNCH(index_quantize_kernel, dim3((n + 3) / 4), dim3(256), 0, s, src, (int8_t *)codes, scales, n, dim, dpad);
 }
 
+// Compaction: row i of dst (row_bytes, a multiple of 16) = row old_ids[i] of src, and the i8 scale with it (sscale null for
+// the other forms).  One thread per 16-byte piece.
+__global__ __launch_bounds__(256) void index_gather_kernel(const i32x4 *__restrict__ src, i32x4 *__restrict__ dst,
+                                                           const float *__restrict__ sscale, float *__restrict__ dscale,
+                                                           const int32_t *__restrict__ old_ids, int n, int pieces) {
+    const size_t total = (size_t)n * pieces;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / pieces;
+        const int c = (int)(i - r * pieces);
+        const size_t o = (size_t)old_ids[r];
+        dst[i] = src[o * pieces + c];
+        if (sscale && c == 0) dscale[r] = sscale[o];
+    }
+}
+
+// live bits of rows [first, first + n) := 1.  One thread per word of the range, read-modify-write: the index's operations
+// never overlap, and no two threads share a word.
+__global__ __launch_bounds__(256) void live_set_range_kernel(uint32_t *__restrict__ live, int first, int n) {
+    const int w0 = first >> 5, w1 = (int)(((long long)first + n - 1) >> 5);
+    const int w = w0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (w > w1) return;
+    uint32_t m = ~0u;
+    if (w == w0) m &= ~0u << (first & 31);
+    const int last = (int)(((long long)first + n - 1) & 31);
+    if (w == w1 && last < 31) m &= (1u << (last + 1)) - 1u;
+    live[w] |= m;
+}
+
+// the same on the host mirror
+void live_set_range_host(std::vector<uint32_t> &live, int first, int n) {
+    for (long long r = first; r < (long long)first + n;) {
+        const size_t w = (size_t)(r >> 5);
+        const int b = (int)(r & 31);
+        const int c = (int)std::min<long long>(32 - b, (long long)first + n - r);
+        live[w] |= (c == 32 ? ~0u : ((1u << c) - 1u) << b);
+        r += c;
+    }
+}
+
+size_t live_words(long long rows) { return (size_t)((rows + 31) / 32); }
+
 struct DeviceGuard {
     int prev = -1;
     explicit DeviceGuard(int d) {
@@ -419,9 +493,9 @@ Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
     ix->eng_ = eng;
     ix->dim_ = dim;
     ix->dtype_ = dtype;
-    ix->es_ = dtype == 2 ? 1 : dtype == 1 ? 2 : 4;
+    ix->es_ = index_elem_size(dtype);
     // the score kernel's k-step (a 16-byte load per lane)
-    ix->dpad_ = dtype == 2 ? (dim + 31) / 32 * 32 : dtype == 1 ? (dim + 15) / 16 * 16 : (dim + 7) / 8 * 8;
+    ix->dpad_ = index_dpad(dtype, dim);
     const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
     if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
@@ -431,6 +505,9 @@ Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
     (void)hipFuncSetAttribute((const void *)index_topk_kernel<half_t, TopkArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     (void)hipFuncSetAttribute((const void *)index_topk_kernel<float, TopkArgs>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     (void)hipFuncSetAttribute((const void *)index_topk_kernel<int8_t, TopkArgsI8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<half_t, TopkArgsMasked>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<float, TopkArgsMasked>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<int8_t, TopkArgsI8Masked>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     return ix;
 }
 
@@ -440,6 +517,7 @@ Index::~Index() {
     if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
     if (rows_) (void)hipFree(rows_);
     if (rscale_) (void)hipFree(rscale_);
+    if (live_) (void)hipFree(live_);
 }
 
 bool Index::grow(DevBuf &b, size_t bytes, std::string &err) {
@@ -461,19 +539,28 @@ bool Index::grow_rows(int n_rows, std::string &err) {
         err = "hipMalloc (index row scales) failed";
         return false;
     }
+    // (an index with removed rows: the live words grow with the rows, so that an add within the capacity never allocates)
+    uint32_t *lv = nullptr;
+    const size_t lw = live_words(cap);
     const char *failed = nullptr;
-    if (n_ > 0 && hipMemcpy(p, rows_, (size_t)n_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) failed = "hipMemcpy (index rows) failed";
+    if (live_ && hipMalloc(&lv, lw * 4) != hipSuccess) failed = "hipMalloc (index live words) failed";
+    else if (n_ > 0 && hipMemcpy(p, rows_, (size_t)n_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) failed = "hipMemcpy (index rows) failed";
     else if (n_ > 0 && sc && hipMemcpy(sc, rscale_, (size_t)n_ * 4, hipMemcpyDeviceToDevice) != hipSuccess) failed = "hipMemcpy (index row scales) failed";
+    else if (lv && (hipMemset(lv, 0, lw * 4) != hipSuccess ||
+                    hipMemcpy(lv, live_h_.data(), live_words(n_) * 4, hipMemcpyHostToDevice) != hipSuccess)) failed = "hipMemcpy (index live words) failed";
     if (failed) {
         (void)hipFree(p);
         if (sc) (void)hipFree(sc);
+        if (lv) (void)hipFree(lv);
         err = failed;
         return false;
     }
     if (rows_) (void)hipFree(rows_);
     if (rscale_) (void)hipFree(rscale_);
+    if (live_) { (void)hipFree(live_); live_h_.resize(lw, 0u); }
     rows_ = p;
     rscale_ = sc;
+    live_ = lv;
     cap_ = cap;
     return true;
 }
@@ -505,8 +592,14 @@ int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &er
         else if (dtype_ == 1) launch_convert<half_t>(d_rows, dst, n, dim_, dpad_, s);
         else launch_convert<float>(d_rows, dst, n, dim_, dpad_, s);
     });
+    // (rows added after a removal are live: their bits on the same stream, and in the mirror, which is already long enough)
+    if (live_) {
+        const int words = (int)(((long long)n_ + n - 1) >> 5) - (n_ >> 5) + 1;
+        BERT_LAUNCH(live_set_range_kernel, dim3((words + 255) / 256), dim3(256), 0, s, live_, n_, n);
+    }
     HIP_OK(hipGetLastError(), err, -1);
     HIP_OK(hipEventRecord(busy_, s), err, -1);
+    if (live_) live_set_range_host(live_h_, n_, n);
     const int first = n_;
     n_ += n;
     return first;
@@ -528,14 +621,14 @@ int Index::add_host(int n, const float *rows, std::string &err) {
             add_device(c, stage_.as<float>(), stream_, err) < 0 || hipStreamSynchronize(stream_) != hipSuccess) {
             (void)hipStreamSynchronize(stream_);
             if (err.empty()) err = "add: copy to the device failed";
-            n_ = first;
+            truncate(first);
             return -1;
         }
     }
     return first;
 }
 
-void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s) {
+void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow) {
     const Plan p = plan(n_, nq, k);
     eng_->timed_launch(dtype_ == 2 ? "index_quantize_i8" : dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
         if (dtype_ == 2) launch_quantize(d_q, qbuf_.p, qscale_.as<float>(), nq, dim_, dpad_, s);
@@ -551,18 +644,34 @@ void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float
     a8.qscale = qscale_.as<float>(); a8.rscale = rscale_;
     const int grid = (a.n_items + 7) / 8 * 8;
     const double flops = 2.0 * nq * (double)n_ * dim_;
-    eng_->timed_launch(dtype_ == 2 ? "index_topk_i8" : dtype_ == 1 ? "index_topk_f16" : "index_topk_f32", flops, s, [&] {
-        if (dtype_ == 2) BERT_LAUNCH((index_topk_kernel<int8_t, TopkArgsI8>), dim3(grid), dim3(NT), p.lds, s, a8);
-        else if (dtype_ == 1) BERT_LAUNCH((index_topk_kernel<half_t, TopkArgs>), dim3(grid), dim3(NT), p.lds, s, a);
-        else BERT_LAUNCH((index_topk_kernel<float, TopkArgs>), dim3(grid), dim3(NT), p.lds, s, a);
-    });
+    if (!live_ && !d_allow) {
+        eng_->timed_launch(dtype_ == 2 ? "index_topk_i8" : dtype_ == 1 ? "index_topk_f16" : "index_topk_f32", flops, s, [&] {
+            if (dtype_ == 2) BERT_LAUNCH((index_topk_kernel<int8_t, TopkArgsI8>), dim3(grid), dim3(NT), p.lds, s, a8);
+            else if (dtype_ == 1) BERT_LAUNCH((index_topk_kernel<half_t, TopkArgs>), dim3(grid), dim3(NT), p.lds, s, a);
+            else BERT_LAUNCH((index_topk_kernel<float, TopkArgs>), dim3(grid), dim3(NT), p.lds, s, a);
+        });
+    } else {
+        // removed rows or an allow-list: the masked kernels, the same plan and workspace
+        TopkArgsMasked am;
+        static_cast<TopkArgs &>(am) = a;
+        am.live = live_; am.allow = d_allow;
+        TopkArgsI8Masked am8;
+        static_cast<TopkArgsI8 &>(am8) = a8;
+        am8.live = live_; am8.allow = d_allow;
+        eng_->timed_launch(dtype_ == 2 ? "index_topk_i8_masked" : dtype_ == 1 ? "index_topk_f16_masked" : "index_topk_f32_masked", flops, s, [&] {
+            if (dtype_ == 2) BERT_LAUNCH((index_topk_kernel<int8_t, TopkArgsI8Masked>), dim3(grid), dim3(NT), p.lds, s, am8);
+            else if (dtype_ == 1) BERT_LAUNCH((index_topk_kernel<half_t, TopkArgsMasked>), dim3(grid), dim3(NT), p.lds, s, am);
+            else BERT_LAUNCH((index_topk_kernel<float, TopkArgsMasked>), dim3(grid), dim3(NT), p.lds, s, am);
+        });
+    }
     MergeArgs m;
     m.ws_s = a.ws_s; m.ws_i = a.ws_i; m.n_cand = p.slices * k; m.k = k; m.L = merge_L(k); m.ids = d_ids; m.scores = d_scores;
     const size_t lds = (size_t)m.L * 8 + 16;
     eng_->timed_launch("topk_merge", 0.0, s, [&] { BERT_LAUNCH(topk_merge_kernel, dim3(nq), dim3(NT), lds, s, m); });
 }
 
-int Index::search_device(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err) {
+int Index::search_device(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err,
+                         const uint32_t *d_allow) {
     if (k < 1 || k > MAX_K) { err = "search: k must be 1 .. 256"; return -1; }
     if (nq < 0 || (nq > 0 && (!d_q || !d_ids || !d_scores))) { err = "search: n_queries >= 0 and query / result pointers required"; return -1; }
     if (nq == 0) return 0;
@@ -576,20 +685,29 @@ int Index::search_device(int nq, const float *d_q, int k, int32_t *d_ids, float 
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
-        enqueue_chunk(c, d_q + (size_t)c0 * dim_, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
+        enqueue_chunk(c, d_q + (size_t)c0 * dim_, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s, d_allow);
     }
     HIP_OK(hipGetLastError(), err, -1);
     HIP_OK(hipEventRecord(busy_, s), err, -1);
     return 0;
 }
 
-int Index::search_to_host(int nq, const float *q, bool q_on_device, int k, int32_t *ids, float *scores, std::string &err) {
+int Index::search_to_host(int nq, const float *q, bool q_on_device, int k, int32_t *ids, float *scores, std::string &err,
+                          const uint32_t *allow) {
     if (k < 1 || k > MAX_K) { err = "search: k must be 1 .. 256"; return -1; }
     if (nq < 0 || (nq > 0 && (!q || !ids || !scores))) { err = "search: n_queries >= 0 and query / result pointers required"; return -1; }
     if (nq == 0) return 0;
     DeviceGuard g(eng_->device());
     std::vector<int32_t> hid((size_t)nq * k);
     std::vector<float> hsc((size_t)nq * k);
+    const uint32_t *d_allow = nullptr;
+    if (allow && n_ > 0) {
+        // (the first search below waits for this copy: the same stream)
+        if (!grow(allow_, live_words(n_) * 4, err)) return -1;
+        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -1);
+        HIP_OK(hipMemcpyAsync(allow_.p, allow, live_words(n_) * 4, hipMemcpyHostToDevice, stream_), err, -1);
+        d_allow = allow_.as<uint32_t>();
+    }
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         const float *dq = q + (size_t)c0 * dim_;
@@ -599,7 +717,7 @@ int Index::search_to_host(int nq, const float *q, bool q_on_device, int k, int32
             dq = stage_.as<float>();
         }
         if (!grow(out_ids_, (size_t)c * k * 4, err) || !grow(out_scores_, (size_t)c * k * 4, err)) return -1;
-        if (search_device(c, dq, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err) != 0) { (void)hipStreamSynchronize(stream_); return -1; }
+        if (search_device(c, dq, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow) != 0) { (void)hipStreamSynchronize(stream_); return -1; }
         HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
         HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
         HIP_OK(hipStreamSynchronize(stream_), err, -1);
@@ -607,6 +725,207 @@ int Index::search_to_host(int nq, const float *q, bool q_on_device, int k, int32
     memcpy(ids, hid.data(), hid.size() * 4);
     memcpy(scores, hsc.data(), hsc.size() * 4);
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// removed rows, compaction, file form
+// ------------------------------------------------------------------------------------------------
+void Index::truncate(int n) {
+    if (n < 0 || n >= n_) return;
+    // (the mirror keeps its bits at and beyond size zero; the device words of the dropped rows stay as they are: a search
+    // ignores them, and the add that reuses those rows sets them)
+    if (live_) {
+        for (long long r = n; r < n_;) {
+            const int b = (int)(r & 31);
+            live_h_[(size_t)(r >> 5)] &= b ? (1u << b) - 1u : 0u;
+            r += 32 - b;
+        }
+        n_removed_ = n;
+        for (size_t w = 0; w < live_words(n); ++w) n_removed_ -= __builtin_popcount(live_h_[w]);
+    }
+    n_ = n;
+}
+
+// the bitmap of an index that had none: every row live
+bool Index::make_live(std::string &err) {
+    if (live_) return true;
+    const size_t lw = live_words(cap_);
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    HIP_OK(hipMalloc((void **)&live_, std::max<size_t>(lw, 1) * 4), err, false);
+    live_h_.assign(lw, 0u);
+    if (n_ > 0) live_set_range_host(live_h_, 0, n_);
+    n_removed_ = 0;
+    if (hipMemcpy(live_, live_h_.data(), lw * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        drop_live();
+        err = "hipMemcpy (index live words) failed";
+        return false;
+    }
+    return true;
+}
+
+void Index::drop_live() {
+    if (live_) (void)hipFree(live_);
+    live_ = nullptr;
+    live_h_.clear();
+    n_removed_ = 0;
+}
+
+// mirror words [w0, w1) -> device, on the index's stream behind whatever is queued; blocking
+bool Index::upload_live(size_t w0, size_t w1, std::string &err) {
+    if (w1 <= w0) return true;
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
+    HIP_OK(hipMemcpyAsync(live_ + w0, live_h_.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, stream_), err, false);
+    HIP_OK(hipEventRecord(busy_, stream_), err, false);
+    HIP_OK(hipStreamSynchronize(stream_), err, false);
+    return true;
+}
+
+int Index::remove(int n, const int32_t *ids, std::string &err) {
+    if (n < 0 || (n > 0 && !ids)) { err = "remove: n >= 0 and an id pointer required"; return -1; }
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= n_) { err = "remove: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(n_) + ")"; return -1; }
+    if (n == 0) return 0;
+    DeviceGuard g(eng_->device());
+    if (!make_live(err)) return -1;
+    std::vector<int32_t> fresh;                          // the ids this call removes (repeats and removed rows left out)
+    size_t w0 = SIZE_MAX, w1 = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t w = (size_t)ids[i] >> 5;
+        const uint32_t bit = 1u << (ids[i] & 31);
+        if (!(live_h_[w] & bit)) continue;
+        live_h_[w] &= ~bit;
+        fresh.push_back(ids[i]);
+        w0 = std::min(w0, w);
+        w1 = std::max(w1, w + 1);
+    }
+    if (!fresh.empty() && !upload_live(w0, w1, err)) {
+        for (int32_t id : fresh) live_h_[(size_t)id >> 5] |= 1u << (id & 31);      // (the mirror as it was)
+        return -1;
+    }
+    n_removed_ += (int)fresh.size();
+    return (int)fresh.size();
+}
+
+int Index::compact(int32_t *old_ids, std::string &err) {
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipEventSynchronize(busy_), err, -1);
+    if (n_removed_ == 0) {
+        if (old_ids) for (int i = 0; i < n_; ++i) old_ids[i] = i;
+        drop_live();
+        return n_;
+    }
+    const int nl = n_ - n_removed_;
+    std::vector<int32_t> map((size_t)nl);
+    int j = 0;
+    for (int r = 0; r < n_; ++r)
+        if (live_h_[(size_t)r >> 5] >> (r & 31) & 1u) map[(size_t)j++] = r;
+    const size_t row_bytes = (size_t)dpad_ * es_;
+    void *p = nullptr;
+    float *sc = nullptr;
+    int32_t *d_map = nullptr;
+    const char *failed = nullptr;
+    if (nl > 0) {
+        if (hipMalloc(&p, (size_t)nl * row_bytes) != hipSuccess) failed = "hipMalloc (index rows) failed";
+        else if (dtype_ == 2 && hipMalloc((void **)&sc, (size_t)nl * 4) != hipSuccess) failed = "hipMalloc (index row scales) failed";
+        else if (hipMalloc((void **)&d_map, (size_t)nl * 4) != hipSuccess) failed = "hipMalloc (compaction ids) failed";
+        else if (hipMemcpyAsync(d_map, map.data(), (size_t)nl * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) failed = "hipMemcpy (compaction ids) failed";
+        else {
+            const int pieces = (int)(row_bytes / 16);
+            const int blocks = (int)std::min<size_t>(((size_t)nl * pieces + 255) / 256, 16384);
+            eng_->timed_launch("index_gather", 0.0, stream_, [&] {
+                BERT_LAUNCH(index_gather_kernel, dim3(blocks), dim3(256), 0, stream_, (const i32x4 *)rows_, (i32x4 *)p, rscale_, sc, d_map, nl, pieces);
+            });
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) failed = "the gather kernel failed";
+        }
+        if (d_map) (void)hipFree(d_map);
+        if (failed) {
+            if (p) (void)hipFree(p);
+            if (sc) (void)hipFree(sc);
+            err = failed;
+            return -1;
+        }
+    }
+    if (rows_) (void)hipFree(rows_);
+    if (rscale_) (void)hipFree(rscale_);
+    rows_ = p;
+    rscale_ = sc;
+    cap_ = n_ = nl;
+    drop_live();
+    if (old_ids) memcpy(old_ids, map.data(), (size_t)nl * 4);
+    return nl;
+}
+
+namespace {
+
+// device memory <-> file in pieces of at most 64 MiB through a host buffer
+constexpr size_t FILE_PIECE = (size_t)64 << 20;
+
+bool device_to_file(FILE *f, const void *d, size_t bytes, std::vector<char> &buf, std::string &err) {
+    for (size_t o = 0; o < bytes; o += FILE_PIECE) {
+        const size_t c = std::min(FILE_PIECE, bytes - o);
+        if (buf.size() < c) buf.resize(c);
+        HIP_OK(hipMemcpy(buf.data(), (const char *)d + o, c, hipMemcpyDeviceToHost), err, false);
+        if (fwrite(buf.data(), 1, c, f) != c) { err = "write failed"; return false; }
+    }
+    return true;
+}
+
+bool file_to_device(FILE *f, void *d, size_t bytes, std::vector<char> &buf, std::string &err) {
+    for (size_t o = 0; o < bytes; o += FILE_PIECE) {
+        const size_t c = std::min(FILE_PIECE, bytes - o);
+        if (buf.size() < c) buf.resize(c);
+        if (fread(buf.data(), 1, c, f) != c) { err = "read failed"; return false; }
+        HIP_OK(hipMemcpy((char *)d + o, buf.data(), c, hipMemcpyHostToDevice), err, false);
+    }
+    return true;
+}
+
+}  // namespace
+
+bool Index::save(const char *path, std::string &err) {
+    if (!path || !*path) { err = "a path is required"; return false; }
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    IndexFileHeader h;
+    h.dtype = (uint32_t)dtype_; h.dim = (uint32_t)dim_; h.dpad = (uint32_t)dpad_; h.n_rows = (uint32_t)n_; h.has_live = live_ ? 1u : 0u;
+    unsigned char hdr[INDEX_HEADER_BYTES];
+    index_header_write(h, hdr);
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) { err = "cannot write '" + tmp + "'"; return false; }
+    std::vector<char> buf;
+    // (the live words come from the mirror: its bits at and beyond size are zero)
+    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && device_to_file(f, rows_, (size_t)n_ * dpad_ * es_, buf, err) &&
+              (dtype_ != 2 || device_to_file(f, rscale_, (size_t)n_ * 4, buf, err)) &&
+              (!live_ || fwrite(live_h_.data(), 4, live_words(n_), f) == live_words(n_));
+    ok = (fclose(f) == 0) && ok;
+    if (ok && rename(tmp.c_str(), path) != 0) ok = false;
+    if (!ok) {
+        (void)::remove(tmp.c_str());
+        if (err.empty()) err = "cannot write '" + std::string(path) + "'";
+    }
+    return ok;
+}
+
+bool Index::load_rows(FILE *f, const IndexFileHeader &h, std::string &err) {
+    if (n_ != 0 || live_ || (int)h.dtype != dtype_ || (int)h.dim != dim_ || (int)h.dpad != dpad_) { err = "load: the index does not fit the file"; return false; }
+    DeviceGuard g(eng_->device());
+    const int n = (int)h.n_rows;
+    if (!grow_rows(n, err)) return false;
+    std::vector<char> buf;
+    if (!file_to_device(f, rows_, (size_t)n * dpad_ * es_, buf, err)) return false;
+    if (dtype_ == 2 && !file_to_device(f, rscale_, (size_t)n * 4, buf, err)) return false;
+    n_ = n;
+    if (!h.has_live) return true;
+    std::vector<uint32_t> words(live_words(n));
+    if (fread(words.data(), 4, words.size(), f) != words.size()) { n_ = 0; err = "read failed"; return false; }
+    if (n & 31 && !words.empty() && (words.back() >> (n & 31)) != 0) { n_ = 0; err = "live bits beyond the last row"; return false; }
+    if (!make_live(err)) { n_ = 0; return false; }
+    std::copy(words.begin(), words.end(), live_h_.begin());
+    for (uint32_t w : words) n_removed_ += 32 - __builtin_popcount(w);
+    n_removed_ -= (int)(words.size() * 32 - (size_t)n);          // (the last word's bits beyond n are zero, not removed rows)
+    if (!upload_live(0, words.size(), err)) { drop_live(); n_ = 0; return false; }
+    return true;
 }
 
 float *Index::scratch(size_t n, std::string &err) {

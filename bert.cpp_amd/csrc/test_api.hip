@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "context.h"
+#include "index_file.h"
 
 using namespace bert_hip;
 
@@ -436,6 +437,20 @@ int32_t bert_hip_test_tokenize_pack(struct bert_ctx *ctx, int32_t n_threads, int
     std::copy(g.cu.begin(), g.cu.begin() + g.n_ok + 1, cu);
     std::copy(g.packed.get(), g.packed.get() + g.cu[g.n_ok], packed);
     return g.n_ok;
+}
+
+int32_t bert_hip_test_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err, int32_t err_cap) {
+    IndexFileHeader h;
+    std::string e;
+    if (err && err_cap > 0) err[0] = 0;
+    if (buf_len < 0 || file_bytes < 0) e = "negative length";
+    else if (index_header_check(buf, (size_t)buf_len, (uint64_t)file_bytes, h, e)) {
+        const uint32_t f[6] = {h.version, h.dtype, h.dim, h.dpad, h.n_rows, h.has_live};
+        if (fields) std::copy(f, f + 6, fields);
+        return 0;
+    }
+    if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return -1;
 }
 
 }  // extern "C"

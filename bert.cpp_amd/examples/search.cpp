@@ -3,8 +3,10 @@
 // then each line read from stdin is a query whose k closest texts are printed in the reference's format.  'q' or the end
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
-//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8] [-t THREADS]
-//   (--f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; the default stores the rows as f16)
+//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8] [-t THREADS] [--save PATH] [--load PATH]
+//   (--f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; the default stores the rows as f16;
+//   --save: the index goes to PATH (bert_hip_index_save) once it is built; --load: the index comes from PATH instead of being
+//   embedded — TEXTS is still read, for printing, and must have as many lines as the index has rows)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,7 +20,7 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8] [-t THREADS]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
 }
 
 std::string chomp(std::string s) {
@@ -28,7 +30,7 @@ std::string chomp(std::string s) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *model = nullptr, *file = nullptr;
+    const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr;
     int k = 3, n_threads = 6, dtype = 1;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
@@ -36,6 +38,8 @@ int main(int argc, char **argv) {
         else if ((!strcmp(argv[i], "-f") || !strcmp(argv[i], "--file")) && has_value) file = argv[++i];
         else if (!strcmp(argv[i], "-k") && has_value) k = atoi(argv[++i]);
         else if ((!strcmp(argv[i], "-t") || !strcmp(argv[i], "--threads")) && has_value) n_threads = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--save") && has_value) save = argv[++i];
+        else if (!strcmp(argv[i], "--load") && has_value) load = argv[++i];
         else if (!strcmp(argv[i], "--f32")) dtype = 0;
         else if (!strcmp(argv[i], "--i8")) dtype = 2;
         else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
@@ -60,9 +64,29 @@ int main(int argc, char **argv) {
     std::vector<const char *> ptrs;
     for (auto &t : texts) ptrs.push_back(t.c_str());
 
-    bert_hip_index *ix = bert_hip_index_create(ctx, 0, dtype);
-    if (!ix || bert_hip_index_add_texts(ix, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
-        fprintf(stderr, "search: could not build the index\n");
+    bert_hip_index *ix;
+    if (load) {
+        ix = bert_hip_index_load(ctx, load);
+        if (!ix) {
+            fprintf(stderr, "search: could not load the index from '%s'\n", load);
+            bert_free(ctx);
+            return 1;
+        }
+        if ((size_t)bert_hip_index_size(ix) != texts.size()) {
+            fprintf(stderr, "search: '%s' holds %d rows, '%s' has %zu lines\n", load, bert_hip_index_size(ix), file, texts.size());
+            bert_free(ctx);
+            return 1;
+        }
+    } else {
+        ix = bert_hip_index_create(ctx, 0, dtype);
+        if (!ix || bert_hip_index_add_texts(ix, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+            fprintf(stderr, "search: could not build the index\n");
+            bert_free(ctx);
+            return 1;
+        }
+    }
+    if (save && bert_hip_index_save(ix, save) != 0) {
+        fprintf(stderr, "search: could not save the index to '%s'\n", save);
         bert_free(ctx);
         return 1;
     }

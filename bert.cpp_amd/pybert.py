@@ -27,7 +27,8 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_profile_enable", "bert_hip_profile_report", "bert_hip_set_option", "bert_hip_version",
     "bert_hip_index_create", "bert_hip_index_free", "bert_hip_index_size", "bert_hip_index_reserve", "bert_hip_index_add",
     "bert_hip_index_add_device", "bert_hip_index_add_texts", "bert_hip_index_search", "bert_hip_index_search_device",
-    "bert_hip_index_search_texts",
+    "bert_hip_index_search_texts", "bert_hip_index_remove", "bert_hip_index_n_live", "bert_hip_index_search_filtered",
+    "bert_hip_index_search_filtered_device", "bert_hip_index_compact", "bert_hip_index_save", "bert_hip_index_load",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -36,7 +37,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots",
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
-    "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack",
+    "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -98,6 +99,14 @@ def _declare_product_abi(L):
     L.bert_hip_index_search_device.restype = i32; L.bert_hip_index_search_device.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     L.bert_hip_index_search_texts.restype = i32
     L.bert_hip_index_search_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32p, f32p]
+    L.bert_hip_index_remove.restype = i32; L.bert_hip_index_remove.argtypes = [vp, i32, i32p]
+    L.bert_hip_index_n_live.restype = i32; L.bert_hip_index_n_live.argtypes = [vp]
+    L.bert_hip_index_search_filtered.restype = i32; L.bert_hip_index_search_filtered.argtypes = [vp, i32, f32p, i32, vp, i32, i32p, f32p]
+    L.bert_hip_index_search_filtered_device.restype = i32
+    L.bert_hip_index_search_filtered_device.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_index_compact.restype = i32; L.bert_hip_index_compact.argtypes = [vp, i32p]
+    L.bert_hip_index_save.restype = i32; L.bert_hip_index_save.argtypes = [vp, C.c_char_p]
+    L.bert_hip_index_load.restype = vp; L.bert_hip_index_load.argtypes = [vp, C.c_char_p]
 
 
 def lib() -> C.CDLL:
@@ -166,6 +175,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_encode_groups.argtypes = [i32, i32p, i32]
     L.bert_hip_test_tokenize_pack.restype = i32
     L.bert_hip_test_tokenize_pack.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32p, i32p, i32p, i32p, i32]
+    L.bert_hip_test_index_header.restype = i32
+    L.bert_hip_test_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
     _test_lib = L
     return L
 
@@ -467,16 +478,41 @@ class BertModel:
         "i8" (one int8 code per element and one f32 scale per row)."""
         return BertIndex(self, dim, dtype)
 
+    def load_index(self, path: str) -> "BertIndex":
+        """The index a BertIndex.save wrote (bert_hip_index_load), on this context's first device."""
+        return BertIndex(self, _load=path)
+
+
+def allow_words(allow, n_rows: int) -> np.ndarray:
+    """An allow-list as the uint32 words of bert_hip_index_search_filtered: a bool array of n_rows entries is packed (row 32 w + b
+    = bit b of word w), uint32 words pass through."""
+    a = np.asarray(allow)
+    if a.dtype == np.uint32:
+        return np.ascontiguousarray(a).reshape(-1)
+    if a.dtype != np.bool_ or a.shape != (n_rows,):
+        raise ValueError(f"allow must be a bool array of {n_rows} entries or uint32 words")
+    packed = np.packbits(a, bitorder="little").tobytes().ljust((n_rows + 31) // 32 * 4, b"\0")
+    return np.frombuffer(packed, dtype="<u4").astype(np.uint32)
+
 
 class BertIndex:
     """bert_hip_index_*: rows in HBM, exact top-k inner-product search.  search* return (ids [n, k] int32, scores [n, k] f32),
     best first; missing entries are id -1, score -inf.  The *_device forms take device pointers (ints, e.g. torch's
     data_ptr()) and a stream handle, and return at once."""
 
-    def __init__(self, model: BertModel, dim: Optional[int] = None, dtype: str = "f16"):
+    def __init__(self, model: BertModel, dim: Optional[int] = None, dtype: str = "f16", _load: Optional[str] = None):
         if dtype not in ("f16", "f32", "i8"):
             raise ValueError("dtype must be 'f16', 'f32' or 'i8'")
         self.model, self.lib = model, model.lib
+        if _load is not None:
+            # dim and dtype come from the file's header (include/bert_hip.h: u32 dtype at byte 12, u32 dim at 16)
+            self.ix = self.lib.bert_hip_index_load(model.ctx, os.fsencode(_load))
+            if not self.ix:
+                raise RuntimeError("bert_hip_index_load failed (see stderr)")
+            with open(_load, "rb") as f:
+                head = np.frombuffer(f.read(24), dtype="<u4")
+            self.dtype, self.dim = ("f32", "f16", "i8")[int(head[3])], int(head[4])
+            return
         code = {"f16": 1, "i8": 2}.get(dtype, 0)
         self.ix = self.lib.bert_hip_index_create(model.ctx, 0 if dim is None else int(dim), code)
         if not self.ix:
@@ -525,19 +561,58 @@ class BertIndex:
             raise RuntimeError(f"bert_hip_index_add_texts failed: {r}")
         return r
 
-    def search(self, queries, k: int = 10):
+    def search(self, queries, k: int = 10, allow=None):
+        """allow: None, a bool array of len(index) entries (True = the row may be returned), or uint32 words (bit b of word w =
+        row 32 w + b), which are passed through."""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         ids = np.empty((q.shape[0], k), dtype=np.int32)
         scores = np.empty((q.shape[0], k), dtype=np.float32)
-        r = self.lib.bert_hip_index_search(self.ix, q.shape[0], _f32p(q), k, _i32p(ids), _f32p(scores))
+        if allow is None:
+            r = self.lib.bert_hip_index_search(self.ix, q.shape[0], _f32p(q), k, _i32p(ids), _f32p(scores))
+            if r != 0:
+                raise RuntimeError(f"bert_hip_index_search failed: {r}")
+            return ids, scores
+        words = allow_words(allow, len(self))
+        r = self.lib.bert_hip_index_search_filtered(self.ix, q.shape[0], _f32p(q), k, words.ctypes.data, len(words), _i32p(ids), _f32p(scores))
         if r != 0:
-            raise RuntimeError(f"bert_hip_index_search failed: {r}")
+            raise RuntimeError(f"bert_hip_index_search_filtered failed: {r}")
         return ids, scores
 
-    def search_device(self, n_queries: int, d_queries_ptr: int, k: int, d_ids_ptr: int, d_scores_ptr: int, stream: int = 0) -> None:
-        r = self.lib.bert_hip_index_search_device(self.ix, n_queries, d_queries_ptr, k, d_ids_ptr, d_scores_ptr, stream)
+    def search_device(self, n_queries: int, d_queries_ptr: int, k: int, d_ids_ptr: int, d_scores_ptr: int, stream: int = 0,
+                      d_allow_ptr: Optional[int] = None, n_words: int = 0) -> None:
+        if d_allow_ptr is None:
+            r = self.lib.bert_hip_index_search_device(self.ix, n_queries, d_queries_ptr, k, d_ids_ptr, d_scores_ptr, stream)
+            if r != 0:
+                raise RuntimeError(f"bert_hip_index_search_device failed: {r}")
+            return
+        r = self.lib.bert_hip_index_search_filtered_device(self.ix, n_queries, d_queries_ptr, k, d_allow_ptr, n_words, d_ids_ptr, d_scores_ptr, stream)
         if r != 0:
-            raise RuntimeError(f"bert_hip_index_search_device failed: {r}")
+            raise RuntimeError(f"bert_hip_index_search_filtered_device failed: {r}")
+
+    @property
+    def n_live(self) -> int:
+        return int(self.lib.bert_hip_index_n_live(self.ix))
+
+    def remove(self, ids) -> int:
+        """Marks rows as deleted (ids stay stable); returns the number newly removed."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        r = self.lib.bert_hip_index_remove(self.ix, len(ids), _i32p(ids))
+        if r < 0:
+            raise RuntimeError(f"bert_hip_index_remove failed: {r}")
+        return r
+
+    def compact(self) -> np.ndarray:
+        """Drops the removed rows' storage; returns old_ids [n_live] int32: the former id of each new id."""
+        old = np.empty(max(self.n_live, 0), dtype=np.int32)
+        r = self.lib.bert_hip_index_compact(self.ix, _i32p(old))
+        if r < 0:
+            raise RuntimeError(f"bert_hip_index_compact failed: {r}")
+        return old[:r]
+
+    def save(self, path: str) -> None:
+        r = self.lib.bert_hip_index_save(self.ix, os.fsencode(path))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_save failed: {r}")
 
     def search_texts(self, texts: Sequence[str], k: int = 10, n_threads: int = 6):
         n = len(texts)

@@ -174,7 +174,36 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  *   - a row's score for a query has the same bits whatever the other queries of the call, the number of add calls that built
  *     the index, reserved or grown storage, k (top-10 is the first 10 entries of top-100), and host or device entry point.
  *   - *_device calls are asynchronous on the caller's stream; an index has ONE event, so its operations never overlap,
- *     whatever streams they were enqueued on.                                                                            */
+ *     whatever streams they were enqueued on.
+ * Removing rows, filtered search, compaction, files:
+ *   remove   marks rows as deleted.  Ids are stable: the other rows keep theirs, new rows still get size, size + 1, ... (size
+ *            counts removed rows too).  A removed row is never returned by any search (search, search_device, search_texts
+ *            and the filtered forms).  ids out of [0, size): error, index unchanged.  Repeats and already-removed ids are
+ *            ignored.  Returns the number of rows newly removed.  Blocking.  n_live: size minus removed rows; -1 without
+ *            an index.  From the first removal on the index keeps one bit per row on the device (sized with the rows by
+ *            reserve), so add_device stays free of allocations and host copies within the reserved bounds.
+ *   search_filtered   a search with an allow-list shared by all queries of the call: allow[w] bit b set = row 32 w + b may
+ *            be returned.  n_words >= ceil(size / 32) or error (-2); bits at and beyond size are ignored; allow == NULL =
+ *            all rows (then n_words is ignored) and the call is bert_hip_index_search.  Everything the search block above
+ *            promises holds over the rows that are live AND allowed: the same score bits as an unfiltered search, the same
+ *            order rule, -1 / -INFINITY slots when fewer than k rows qualify.  search_filtered_device: queries, allow-list
+ *            and results in device memory, asynchronous on `stream` under the one-event rule; within the bounds of reserve
+ *            it never allocates.  Blocks of 32 rows without a qualifying row cost neither loads nor arithmetic.
+ *   compact  drops the removed rows' storage.  Live rows keep their order and stored bits and get ids 0 .. n_live - 1;
+ *            old_ids (NULL, or room for n_live entries) receives the former id of each new id.  Returns the new size (an
+ *            index without removed rows: a no-op that returns size).  Blocking.
+ *   save / load   the index as stored (format below), so a loaded index answers every search with the bits the saved one
+ *            gave.  save writes path + ".tmp" and renames it; 0 or negative.  load: NULL + a line on stderr for a
+ *            tokenizer-only context, an unreadable, truncated, over-long or inconsistent file; the file is checked against
+ *            its header before anything is allocated.  The loaded index belongs to ctx like a created one; its dim need
+ *            not be bert_n_embd(ctx).
+ * Errors of the functions that take an index: -1 no index, -2 bad arguments (after a line on stderr), -3 an error of the
+ * index or the device (its message on stderr), -4 an exception.  Outputs are untouched on error.
+ * File format (little-endian).  Header, 64 bytes: magic "BHIPIDX1" (8 bytes), u32 version = 1, u32 dtype (0 f32, 1 f16,
+ * 2 i8), u32 dim, u32 dpad (elements per stored row: dim rounded up to 8 (f32), 16 (f16), 32 (i8)), u32 n_rows (= size,
+ * removed rows included), u32 has_live (0 | 1), 32 zero bytes.  Then n_rows * dpad * elem_size bytes of rows exactly as
+ * stored (zero-padded to dpad; elem_size 4, 2, 1); for i8, n_rows f32 row scales; if has_live, ceil(n_rows / 32) u32 words,
+ * bit b of word w set = row 32 w + b is live, the bits at and beyond n_rows zero.  The file is exactly that long.        */
 struct bert_hip_index;
 BERT_API struct bert_hip_index *bert_hip_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype);
 BERT_API void    bert_hip_index_free(struct bert_hip_index *ix);
@@ -189,6 +218,16 @@ BERT_API int32_t bert_hip_index_search_device(struct bert_hip_index *ix, int32_t
                                               int32_t *d_ids, float *d_scores, void *stream);
 BERT_API int32_t bert_hip_index_search_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n_queries, const char **texts,
                                              int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_index_remove(struct bert_hip_index *ix, int32_t n, const int32_t *ids);
+BERT_API int32_t bert_hip_index_n_live(struct bert_hip_index *ix);
+BERT_API int32_t bert_hip_index_search_filtered(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t k,
+                                                const uint32_t *allow, int32_t n_words, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_index_search_filtered_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries,
+                                                       int32_t k, const uint32_t *d_allow, int32_t n_words, int32_t *d_ids,
+                                                       float *d_scores, void *stream);
+BERT_API int32_t bert_hip_index_compact(struct bert_hip_index *ix, int32_t *old_ids);
+BERT_API int32_t bert_hip_index_save(struct bert_hip_index *ix, const char *path);
+BERT_API struct bert_hip_index *bert_hip_index_load(struct bert_ctx *ctx, const char *path);
 
 BERT_API const char *bert_hip_version(void);
 

@@ -124,6 +124,11 @@ BERT_API int32_t bert_hip_test_encode_groups(int32_t n_inputs, int32_t *groups, 
 BERT_API int32_t bert_hip_test_tokenize_pack(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts,
                                              const int32_t *counts, int32_t *n_tokens, int32_t *cu, bert_vocab_id *packed,
                                              int32_t packed_cap);
+/* The check bert_hip_index_load runs on a file's header before it allocates (index_file.h index_header_check; the format is in
+ * bert_hip.h): buf holds the first buf_len bytes of a file of file_bytes bytes.  0 and fields = {version, dtype, dim, dpad,
+ * n_rows, has_live} for a header this build loads; -1 and the reason in err (err_cap bytes) otherwise.                          */
+BERT_API int32_t bert_hip_test_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err,
+                                            int32_t err_cap);
 
 #ifdef __cplusplus
 }

@@ -3,12 +3,19 @@ device and data beside every line as the yardstick, and the rate of bert_hip_ind
 bert_hip_index_add.  GPU only: there is no CPU fallback.
 
     python tools/search_rate.py [--rows 1000000] [--iters 10] [--out profiles/search_rate.txt]
+                                [--sections search,filter,texts] [--dims 384,768] [--dtypes f16,f32,i8] [--no-yardstick]
 
 Per line: ms per call (device events, after warm-up), queries/s, the algorithmic bytes (the rows once, the queries, the
 results) and FLOPs (2 Q N dim), the share of the binding roofline (HBM 6.3 TB/s achievable; matrix cores 2.5 PF/s f16,
 155 TF/s f32, 5 PF/s i8) and its name, torch's ms, and whether the two agree (per query: the same ids up to ties within
 tolerance).  i8 rows count dpad + 4 bytes (codes and scale); torch's yardstick for them is the same quantization and score
 restated in torch (f32 mat-mul of the codes, exact at these dims: every partial sum is an integer below 2^24).
+
+Section "filter" (bert_hip_index_search_filtered_device; f16 and i8 rows, dim 384, k = 10, Q = 1 and 4096): the unfiltered
+call, then allow-lists of density 1.0, 0.1 and 0.01, with the allowed rows drawn at random or in contiguous runs of 4096 rows
+spread evenly over the index.  Per line: ms per call (median, and the smallest and largest of the iterations: the run-to-run
+spread), the ratio to the unfiltered line, and the rows that qualify.  --no-yardstick leaves torch's column out (for a quick
+comparison of two builds).
 """
 import argparse
 import os
@@ -46,11 +53,64 @@ def quantize(x):
     return torch.where(scale[:, None] == 0, torch.zeros_like(codes), codes), scale
 
 
+def filter_section(a, m, N, out, timed, torch, dev, sp):
+    """search_filtered_device against search_device on the same index: what an allow-list costs or saves"""
+    from bert_cpp_amd import pybert
+    dim, k, run = 384, 10, 4096
+    out(f"# search_filtered_device, N = {N} rows, dim {dim}, k = {k}; allow-list of the given density, rows allowed at random or in "
+        f"contiguous runs of {run} rows; ms = median (min .. max) of {a.iters}")
+    out("# dtype     Q  allow-list          qualifying |      ms (min .. max)        x unfiltered")
+    g = torch.Generator(device=dev).manual_seed(dim)
+    C = torch.randn(N, dim, device=dev, generator=g)
+    C /= C.norm(dim=1, keepdim=True)
+    Qall = torch.randn(4096, dim, device=dev, generator=g)
+    Qall /= Qall.norm(dim=1, keepdim=True)
+    rng = np.random.default_rng(1)
+    lists = [("none (search_device)", None)]
+    for density in (1.0, 0.1, 0.01):
+        if density == 1.0:
+            lists.append(("1.0", np.ones(N, bool)))
+            continue
+        lists.append((f"{density} random", rng.random(N) < density))
+        blocks = np.zeros(N, bool)
+        n_runs = max(1, int(round(density * N / run)))
+        for start in np.linspace(0, N - run, n_runs).astype(np.int64) // 128 * 128:
+            blocks[start:start + run] = True
+        lists.append((f"{density} contiguous", blocks))
+    for dtype in ("f16", "i8"):
+        ix = m.index(dim=dim, dtype=dtype)
+        ix.reserve(N, 4096, k)
+        ix.add_device(N, C.data_ptr(), sp)
+        for Q in (1, 4096):
+            q = Qall[:Q].contiguous()
+            ids = torch.empty(Q, k, dtype=torch.int32, device=dev)
+            sc = torch.empty(Q, k, dtype=torch.float32, device=dev)
+            base = None
+            for name, keep in lists:
+                if keep is None:
+                    t, lo, hi = timed(lambda: ix.search_device(Q, q.data_ptr(), k, ids.data_ptr(), sc.data_ptr(), sp))
+                    base, n_q = t, N
+                else:
+                    words = torch.from_numpy(pybert.allow_words(keep, N).view(np.int32)).to(dev)
+                    t, lo, hi = timed(lambda: ix.search_device(Q, q.data_ptr(), k, ids.data_ptr(), sc.data_ptr(), sp,
+                                                               d_allow_ptr=words.data_ptr(), n_words=words.numel()))
+                    n_q = int(keep.sum())
+                    # (every returned row is an allowed one)
+                    got = ids.cpu().numpy()
+                    assert keep[got[got >= 0]].all(), name
+                out(f"{dtype:7s} {Q:5d}  {name:20s} {n_q:9d} | {t:8.3f} ({lo:7.3f} .. {hi:7.3f})  {t / base:6.2f}")
+        ix.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sections", default="search,filter,texts")
+    ap.add_argument("--dims", default="384,768")
+    ap.add_argument("--dtypes", default="f16,f32,i8")
+    ap.add_argument("--no-yardstick", action="store_true")
     a = ap.parse_args()
     import torch
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -74,15 +134,33 @@ def main():
     st = torch.cuda.current_stream()
     sp = st.cuda_stream
     N = a.rows
+    sections = a.sections.split(",")
+    dims = [int(d) for d in a.dims.split(",")] if "search" in sections else []
+    dtypes = a.dtypes.split(",")
+
+    def timed(f):
+        """ms per call: (median, smallest, largest) of a.iters calls after 3 warm-up calls"""
+        for _ in range(3):
+            f()
+        ms = []
+        for _ in range(a.iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            f()
+            e1.record(st)
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms)), float(min(ms)), float(max(ms))
+
     out(f"# search_device, N = {N} rows, {torch.cuda.get_device_name(0)}; ms per call = median of {a.iters} after 3 warm-up calls")
-    out("# dim dtype     Q    k |      ms    queries/s  bytes      FLOPs   | bound  share | torch ms  agree")
-    for dim in (384, 768):
+    out("# dim dtype     Q    k |      ms (min .. max)       queries/s  bytes      FLOPs   | bound  share | torch ms  agree")
+    for dim in dims:
         g = torch.Generator(device=dev).manual_seed(dim)
         C = torch.randn(N, dim, device=dev, generator=g)
         C /= C.norm(dim=1, keepdim=True)
         Qall = torch.randn(4096, dim, device=dev, generator=g)
         Qall /= Qall.norm(dim=1, keepdim=True)
-        for dtype in ("f16", "f32", "i8"):
+        for dtype in dtypes:
             ix = m.index(dim=dim, dtype=dtype)
             ix.reserve(N, 4096, 100)
             ix.add_device(N, C.data_ptr(), sp)
@@ -110,25 +188,14 @@ def main():
                             res.append(torch.topk(s, k, dim=1))
                         return torch.cat([r.values for r in res]), torch.cat([r.indices for r in res])
 
-                    def timed(f):
-                        for _ in range(3):
-                            f()
-                        ms = []
-                        for _ in range(a.iters):
-                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                            e0.record(st)
-                            f()
-                            e1.record(st)
-                            e1.synchronize()
-                            ms.append(e0.elapsed_time(e1))
-                        return float(np.median(ms))
-
-                    t = timed(call)
-                    ty = timed(yard)
-                    tv, ti = yard()
-                    torch.cuda.synchronize()
-                    nq = min(Q, 64)
-                    ok = agree(ids[:nq].cpu().numpy(), sc[:nq].cpu().numpy(), ti[:nq].cpu().numpy(), tv[:nq].cpu().numpy(), k, 1e-3)
+                    t, t_lo, t_hi = timed(call)
+                    ty, ok = float("nan"), None
+                    if not a.no_yardstick:
+                        ty = timed(yard)[0]
+                        tv, ti = yard()
+                        torch.cuda.synchronize()
+                        nq = min(Q, 64)
+                        ok = agree(ids[:nq].cpu().numpy(), sc[:nq].cpu().numpy(), ti[:nq].cpu().numpy(), tv[:nq].cpu().numpy(), k, 1e-3)
                     es = {"f16": 2, "f32": 4, "i8": 1}[dtype]
                     step = {"f16": 16, "f32": 8, "i8": 32}[dtype]
                     dpad = (dim + step - 1) // step * step
@@ -136,31 +203,35 @@ def main():
                     flops = 2.0 * Q * N * dim
                     tb, tf = nbytes / HBM, flops / PEAK[dtype]
                     bound, share = ("HBM", tb / (t * 1e-3)) if tb >= tf else ("MFMA", tf / (t * 1e-3))
-                    out(f"{dim:5d} {dtype:5s} {Q:5d} {k:4d} | {t:8.3f} {Q / (t * 1e-3):11.0f}  {nbytes:.2e} {flops:.2e} | "
-                        f"{bound:5s} {share:6.3f} | {ty:8.3f}  {'yes' if ok else 'NO'}")
+                    out(f"{dim:5d} {dtype:5s} {Q:5d} {k:4d} | {t:8.3f} ({t_lo:7.3f} .. {t_hi:7.3f}) {Q / (t * 1e-3):11.0f}  {nbytes:.2e} {flops:.2e} | "
+                        f"{bound:5s} {share:6.3f} | {ty:8.3f}  {'-' if ok is None else 'yes' if ok else 'NO'}")
             ix.close()
             del Ct
         del C, Qall
         torch.cuda.empty_cache()
 
+    if "filter" in sections:
+        filter_section(a, m, N, out, timed, torch, dev, sp)
+
     # strings in, index rows out: add_texts against encode_batch + add
-    base = [l.rstrip("\n") for l in open(os.path.join(ROOT, "tests", "golden", "sample_client_texts_600.txt"), encoding="utf-8")]
-    texts = [f"{base[i % len(base)]} {i}" for i in range(32768)]
-    rates = {}
-    for name in ("add_texts", "encode_batch+add"):
-        best = 1e9
-        for _ in range(3):
-            ix = m.index(dtype="f16")
-            t0 = time.perf_counter()
-            if name == "add_texts":
-                ix.add_texts(texts, n_threads=16)
-            else:
-                ix.add(m.encode_batch(texts, n_threads=16))
-            best = min(best, time.perf_counter() - t0)
-            ix.close()
-        rates[name] = len(texts) / best
-    out(f"# texts into the index (minilm-l6 synthetic f16, 32768 texts, best of 3): add_texts {rates['add_texts']:.0f} texts/s, "
-        f"encode_batch + add {rates['encode_batch+add']:.0f} texts/s")
+    if "texts" in sections:
+        base = [l.rstrip("\n") for l in open(os.path.join(ROOT, "tests", "golden", "sample_client_texts_600.txt"), encoding="utf-8")]
+        texts = [f"{base[i % len(base)]} {i}" for i in range(32768)]
+        rates = {}
+        for name in ("add_texts", "encode_batch+add"):
+            best = 1e9
+            for _ in range(3):
+                ix = m.index(dtype="f16")
+                t0 = time.perf_counter()
+                if name == "add_texts":
+                    ix.add_texts(texts, n_threads=16)
+                else:
+                    ix.add(m.encode_batch(texts, n_threads=16))
+                best = min(best, time.perf_counter() - t0)
+                ix.close()
+            rates[name] = len(texts) / best
+        out(f"# texts into the index (minilm-l6 synthetic f16, 32768 texts, best of 3): add_texts {rates['add_texts']:.0f} texts/s, "
+            f"encode_batch + add {rates['encode_batch+add']:.0f} texts/s")
     m.close()
     if a.out:
         with open(a.out, "w") as f:
