@@ -194,6 +194,8 @@ int32_t bert_hip_n_vocab(struct bert_ctx *ctx) { return ctx->hp.n_vocab; }
 int32_t bert_hip_ftype(struct bert_ctx *ctx) { return ctx->hp.f16; }
 int32_t bert_hip_device(struct bert_ctx *ctx) { return ctx->engine() ? ctx->engine()->device() : -1; }
 int32_t bert_hip_n_devices(struct bert_ctx *ctx) { return (int32_t)ctx->engines.size(); }
+int32_t bert_hip_pooling(struct bert_ctx *ctx) { return ctx && ctx->engine() ? (int32_t)ctx->engine()->options().pool_cls : -1; }
+int32_t bert_hip_normalize(struct bert_ctx *ctx) { return ctx && ctx->engine() ? (int32_t)ctx->engine()->options().normalize : -1; }
 
 int32_t bert_hip_eval_packed(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens,
                              int32_t n_sentences, float *embeddings) {

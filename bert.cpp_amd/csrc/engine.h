@@ -36,7 +36,8 @@ public:
     // short enough on average for packing to pay, else sentences are placed by the uniform rule of qkv_attention2.hip
     int eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int n_sentences, int n_tokens, int max_len,
                            float *d_out, hipStream_t stream, float *d_hidden, std::string &err,
-                           const int2 *d_windows = nullptr, int n_windows = 0, int window_slots = 0);      // window_slots: the place granularity d_windows was built with (0: read it now)
+                           const int2 *d_windows = nullptr, int n_windows = 0, int window_slots = 0,       // window_slots: the place granularity d_windows was built with (0: read it now)
+                           int pool_mode = -1);                  // kernels.h POOL_*: what the host call read for all its chunks (-1: read the options now)
     // next-fit packing of whole sentences (in order, each starting at a multiple of 16 slots) into windows of 128 token
     // slots: {first sentence, count} per window.  Sentences longer than a window get one of their own (the fused kernel is
     // not used for such batches).
@@ -56,6 +57,7 @@ public:
     void timed_launch(const char *name, double flops, hipStream_t s, const std::function<void()> &f);
 
     const HParams &hparams() const { return hp_; }
+    const EngineOptions &options() const { return opt_; }
     int device() const { return device_; }
     hipStream_t stream() const { return stream_; }
 
@@ -75,7 +77,7 @@ private:
     struct Plan {
         // the call (windows, n_windows: the caller's list, or the one the pass builds on the device)
         const int32_t *tokens, *cu;
-        int B, T, max_len, t_pad, slots;
+        int B, T, max_len, t_pad, slots, pool_mode;
         float *out, *hidden;
         hipStream_t s;
         const int2 *windows;
@@ -87,7 +89,7 @@ private:
         std::vector<LayerPlan> layers;
     };
     Plan plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s, float *d_hidden,
-              const int2 *d_windows, int n_windows, int slots) const;
+              const int2 *d_windows, int n_windows, int slots, int pool_mode) const;
     bool forward_f32(const Plan &p, std::string &err);        // f32 files in f32 arithmetic (f32_route.hip), one launch per operation
     void forward_latency(const Plan &p);
     void forward_one_launch(const Plan &p);

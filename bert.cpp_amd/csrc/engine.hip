@@ -106,17 +106,20 @@ void Engine::build_windows(const int32_t *cu, int B, std::vector<int2> &windows,
 }
 
 int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out,
-                               hipStream_t s, float *d_hidden, std::string &err, const int2 *d_windows, int n_windows, int slots_in) {
+                               hipStream_t s, float *d_hidden, std::string &err, const int2 *d_windows, int n_windows, int slots_in,
+                               int pool_mode_in) {
     if (B <= 0 || T <= 0) return 0;
     // the windows' place granularity, read ONCE per pass (the host path read it when it built its list): the window list, the
     // grid bound and the kernels' place rule must agree whatever another thread or context sets meanwhile
     const int slots = slots_in ? slots_in : window_slots();
+    // (so are "pooling" and "normalize": every launch that ends the pass gets the plan's value)
+    const int pool_mode = pool_mode_in >= 0 ? pool_mode_in : opt_.pool_mode();
     HIP_OK(hipSetDevice(device_), err, -1);
     if (!ensure_workspace((T + 255) / 256 * 256, B, err)) return -1;
     prof_.begin_pass();
     // one forward pass at a time on the shared workspace: wait (on the caller's stream) for the previous pass
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
-    const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots);
+    const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots, pool_mode);
     bool ok = true;
     if (p.route == Route::F32) ok = forward_f32(p, err);
     else {
@@ -134,7 +137,7 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
         }
         // (the one-launch kernel's workgroups pool their sentences themselves)
         if (ok && p.route != Route::ONE_LAUNCH)
-            timed("pool_normalize", 2.0 * T * H, s, [&] { launch_pool_normalize(x_.as<half_t>(), d_cu, B, H, max_len, status_.as<int>(), d_out, s); });
+            timed("pool_normalize", 2.0 * T * H, s, [&] { launch_pool_normalize(x_.as<half_t>(), d_cu, B, H, max_len, status_.as<int>(), d_out, p.pool_mode, s); });
     }
     if (!ok) return -1;
     HIP_OK(hipGetLastError(), err, -1);
@@ -144,9 +147,9 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
 
 // The route of a pass and, per layer, its kernels: every eligibility test of the forward pass, each made here once.  Launches nothing.
 Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s,
-                          float *d_hidden, const int2 *d_windows, int n_windows, int slots) const {
+                          float *d_hidden, const int2 *d_windows, int n_windows, int slots, int pool_mode) const {
     // (t_pad: whole tiles of every kernel family, 128- and 256-token tiles)
-    Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, d_out, d_hidden, s, d_windows, n_windows};
+    Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, pool_mode, d_out, d_hidden, s, d_windows, n_windows};
     if (w_->f32_file && opt_.f32_exact) { p.route = Route::F32; return p; }
     const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh, Lz = hp_.n_layer;
     auto family = [&](const GemmWeightStore &W) {
@@ -282,7 +285,7 @@ void Engine::forward_one_launch(const Plan &p) {
     }
     timed("model_kernel", hp_.n_layer * (2.0 * p.T * 3 * H * H + 4.0 * p.T * p.max_len * H + 2.0 * p.T * H * H + 4.0 * p.T * H * I), p.s, [&] {
         launch_model_kernel(mw, hp_.n_layer, x_.as<half_t>(), ctx_.as<half_t>(), p.cu, p.B, p.T, p.windows, p.n_windows, p.n_windows_dev, hp_.n_head,
-                            p.out, p.max_len, status_.as<int>(), p.slots, p.s);
+                            p.out, p.max_len, status_.as<int>(), p.pool_mode, p.slots, p.s);
     });
 }
 
@@ -378,7 +381,7 @@ bool Engine::forward_f32(const Plan &p, std::string &err) {
         timed("layernorm", 0.0, p.s, [&] { launch_f32_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.T, H, p.s); });
         tap(p, il + 1);
     }
-    timed("pool_normalize", 2.0 * p.T * H, p.s, [&] { launch_f32_pool_normalize(x, p.cu, p.B, H, p.max_len, status_.as<int>(), p.out, p.s); });
+    timed("pool_normalize", 2.0 * p.T * H, p.s, [&] { launch_f32_pool_normalize(x, p.cu, p.B, H, p.max_len, status_.as<int>(), p.out, p.pool_mode, p.s); });
     return true;
 }
 
@@ -483,6 +486,7 @@ int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, fl
     auto fail = [&]() { (void)hipStreamSynchronize(stream_); return -1; };        // nothing may stay queued on the slots
     std::vector<int2> windows;
     const int slots = window_slots();                         // (once per call: the lists below and the kernels that place by them)
+    const int pool_mode = opt_.pool_mode();                   // (once per call as well: every chunk ends by the same rule)
     for (size_t i = 0; i < chunks.size(); ++i) {
         HostSlot &sl = slot_[i & 1];
         const int b0 = chunks[i].b0, nb = chunks[i].b1 - b0, T = cu[chunks[i].b1] - cu[b0];
@@ -510,7 +514,7 @@ int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, fl
         // host destination: the pooling kernel's rows go straight into the pinned block (no D2H copy behind the pass)
         float *out = d_embeddings ? sl.d_out.as<float>() : sl.d_out_host;
         if (eval_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, chunks[i].max_len, out, stream_, nullptr, err,
-                               n_windows ? (const int2 *)(d_in + off_w) : nullptr, n_windows, slots) != 0)
+                               n_windows ? (const int2 *)(d_in + off_w) : nullptr, n_windows, slots, pool_mode) != 0)
             return fail();
         if ((d_embeddings && hipMemcpyAsync(d_embeddings + (size_t)b0 * H, sl.d_out.p, (size_t)nb * H * 4, hipMemcpyDeviceToDevice, stream_) != hipSuccess) ||
             hipEventRecord(sl.done, stream_) != hipSuccess) {

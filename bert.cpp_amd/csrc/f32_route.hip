@@ -185,10 +185,11 @@ __global__ void f32_attention_kernel(const float *qkv, const int32_t *cu_seqlens
 }
 
 // reference bert.cpp:904-913: mean over all N tokens (a mat-vec with a 1/N vector: every term is x * (1/N)), y / ||y||_2 without
-// epsilon.  One workgroup per sentence; a sentence outside [1, max_len] gets a NaN row and raises the status word (the
-// device API's promise, as launch_pool_normalize).
+// epsilon; pool_mode (kernels.h): POOL_CLS the f32 row of the first token instead of the mean, POOL_RAW no division.  One workgroup
+// per sentence; a sentence outside [1, max_len] gets a NaN row and raises the status word (the device API's promise, as
+// launch_pool_normalize).
 __global__ __launch_bounds__(256) void f32_pool_normalize_kernel(const float *x, const int32_t *cu_seqlens, int H, int max_len, int *status,
-                                                                 float *out) {
+                                                                 float *out, int pool_mode) {
     extern __shared__ float part[];          // [H] pooled row, then red[4]
     const int b = blockIdx.x, tid = threadIdx.x;
     const int tok0 = cu_seqlens[b], n = cu_seqlens[b + 1] - tok0;
@@ -197,14 +198,18 @@ __global__ __launch_bounds__(256) void f32_pool_normalize_kernel(const float *x,
         if (tid == 0 && status) atomicOr(status, 1);
         return;
     }
+    const bool cls = (pool_mode & POOL_CLS) != 0, raw = (pool_mode & POOL_RAW) != 0;
     const float invn = 1.0f / (float)n;
     float sq = 0.f;
     for (int e = tid; e < H; e += 256) {
         float a = 0.f;
-        for (int t = 0; t < n; ++t) a += x[(size_t)(tok0 + t) * H + e] * invn;
-        part[e] = a;
-        sq += a * a;
+        if (cls) a = x[(size_t)tok0 * H + e];
+        else
+            for (int t = 0; t < n; ++t) a += x[(size_t)(tok0 + t) * H + e] * invn;
+        if (raw) out[(size_t)b * H + e] = a;
+        else { part[e] = a; sq += a * a; }
     }
+    if (raw) return;
     sq = f32_wave_sum(sq);
     float *red = part + H;
     __syncthreads();
@@ -237,9 +242,10 @@ void launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sen
 }
 
 void launch_f32_pool_normalize(const float *x, const int32_t *cu_seqlens, int n_sentences, int H, int max_len, int *status, float *out,
-                               hipStream_t stream) {
+                               int pool_mode, hipStream_t stream) {
     if (n_sentences <= 0) return;
-    BERT_LAUNCH(f32_pool_normalize_kernel, dim3(n_sentences), dim3(256), (H + 4) * sizeof(float), stream, x, cu_seqlens, H, max_len, status, out);
+    BERT_LAUNCH(f32_pool_normalize_kernel, dim3(n_sentences), dim3(256), (H + 4) * sizeof(float), stream, x, cu_seqlens, H, max_len, status, out,
+                pool_mode);
 }
 
 }  // namespace bert_hip

@@ -87,10 +87,10 @@ bool model_kernel_supported(const GemmWeight &Wqkv, const GemmWeight &Wo, const 
 // x: in = embeddings + LayerNorm, out = the last layer's output; ctx: workspace [T][H].  groups / n_groups / n_groups_dev: the
 // window list as for launch_qkv_attention2 (nullptr: one sentence per window); n_tokens = 128 n_sentences selects the form
 // specialised for full windows.  pooled != nullptr: the workgroups also pool and normalise their sentences (launch_pool_normalize's
-// arguments and bits: [n_sentences][H] f32, max_len, status word).
+// arguments and bits: [n_sentences][H] f32, max_len, status word, pool_mode).
 void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x, half_t *ctx, const int32_t *cu_seqlens, int n_sentences,
                          int n_tokens, const int2 *groups, int n_groups, const int *n_groups_dev, int n_head, float *pooled, int max_len,
-                         int *status, int slots, hipStream_t stream);
+                         int *status, int pool_mode, int slots, hipStream_t stream);
 // The latency route (skinny.hip): the weight mat-muls of a layer split by output features AND token blocks over up to 192
 // one-wave workgroups, for batches of at most 128 tokens; same bits per sentence as qkv_attention2 + layer_tail.
 // mode: 0 QKV projection (-> f16), 1 out-projection (+ x + bo -> f32), 2 up-projection + GELU (-> f16, fragment order),
@@ -141,10 +141,13 @@ int qkv_attention2_max_windows(int n_sentences, int n_tokens, int slots);
 int window_slots();
 void set_window_slots(int slots);
 
-// mean over the sentence's tokens, then L2 normalise; out f32 [n_sentences][H].  A sentence whose length is not in
-// [1, max_len] (the caller of the device API promised max_len) gets a NaN row and sets *status (device word) to 1.
+// How a pass ends (bert_hip.h "pooling" / "normalize"), the bits of every `pool_mode` below: 0 = mean over the sentence's tokens, then
+// L2 normalise (the reference's); POOL_CLS: the row of the sentence's first token instead of the mean; POOL_RAW: no division by the norm.
+constexpr int POOL_CLS = 1, POOL_RAW = 2;
+// the sentences' rows by that rule; out f32 [n_sentences][H].  A sentence whose length is not in [1, max_len] (the caller of the
+// device API promised max_len) gets a NaN row and sets *status (device word) to 1, whatever the mode.
 void launch_pool_normalize(const half_t *x, const int32_t *cu_seqlens, int n_sentences, int H, int max_len, int *status,
-                           float *out, hipStream_t stream);
+                           float *out, int pool_mode, hipStream_t stream);
 
 // The > 64 KiB dynamic-LDS opt-in (hipFuncSetAttribute) is per device: `seen` is the launcher's per-kernel record.  The
 // devices of a context launch from threads of their own, and two contexts may share a device: the record is atomic, and
@@ -200,7 +203,7 @@ void launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sen
                           hipStream_t stream);
 void launch_f32_layernorm(float *x, const float *gamma, const float *beta, int T, int H, hipStream_t stream);
 void launch_f32_pool_normalize(const float *x, const int32_t *cu_seqlens, int n_sentences, int H, int max_len, int *status, float *out,
-                               hipStream_t stream);
+                               int pool_mode, hipStream_t stream);
 
 // bytes (rounded up to 16) from mapped pinned host memory to device memory by a kernel (small staged blocks of the host API)
 void launch_stage_copy(const void *mapped_src, void *dst, size_t bytes, hipStream_t stream);

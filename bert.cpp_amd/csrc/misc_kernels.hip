@@ -354,18 +354,18 @@ void launch_ln_rows_finalize(const float2 *stats, int P, int T, int H, float4 *r
 // reference bert.cpp:904-913: mean over all N tokens (mat-vec with a 1/N vector), then y / ||y||_2.
 // One workgroup per sentence (pool_normalize.h: the body, shared with the epilogue of model_kernel.hip).
 __global__ __launch_bounds__(256) void pool_normalize_kernel(const half_t *x, const int32_t *cu_seqlens, int H,
-                                                             int max_len, int *status, float *out) {
+                                                             int max_len, int *status, float *out, int pool_mode) {
     extern __shared__ float part[];          // [4][H] partial sums, then red[4]
     const int b = blockIdx.x;
     const int tok0 = cu_seqlens[b], n = cu_seqlens[b + 1] - tok0;
-    pool_normalize_sentence(x, tok0, n, b, H, max_len, status, out, part, (int)threadIdx.x, true);
+    pool_normalize_sentence(x, tok0, n, b, H, max_len, status, out, part, (int)threadIdx.x, true, pool_mode);
 }
 
 void launch_pool_normalize(const half_t *x, const int32_t *cu_seqlens, int n_sentences, int H, int max_len, int *status,
-                           float *out, hipStream_t stream) {
+                           float *out, int pool_mode, hipStream_t stream) {
     if (n_sentences <= 0) return;
     BERT_LAUNCH(pool_normalize_kernel, dim3(n_sentences), dim3(256), (4 * H + 4) * sizeof(float), stream, x,
-                       cu_seqlens, H, max_len, status, out);
+                       cu_seqlens, H, max_len, status, out, pool_mode);
 }
 
 // A call's staged block (ids | cu_seqlens | windows) from MAPPED pinned host memory into device memory by a kernel: the copy

@@ -58,7 +58,7 @@ struct ModelArgs {
     int n_layer, n_head, n_sent, I, slot_mask;      // slot_mask: the windows' place granularity - 1 (Qkv2Args)
     float *pooled;                   // [n_sent][H] f32: the sentences' pooled, normalised rows (the workgroup pools its window itself), or nullptr
     int *status;                     // pooling's status word (a sentence outside [1, max_len])
-    int max_len;
+    int max_len, pool_mode;          // pool_mode: kernels.h POOL_CLS | POOL_RAW, read by the epilogue alone (POOL_MODES forms)
     ModelLayerArgs layer[MODEL_MAX_LAYERS];
 };
 
@@ -66,7 +66,11 @@ struct ModelArgs {
 
 // RAGGED: windows of whole sentences with up to 128 tokens between them (the window phase's slots: every sentence starts at a
 // multiple of 16), whose rows of x / ctx are tok0 .. tok0 + rows - 1 of the packed batch: the layer-tail phase runs on those.
-template <int NT, bool RAGGED>
+// POOL_MODES: the epilogue pools as m.pool_mode says; else by the default rule, mean + L2 normalisation, as a constant.  The
+// layer loop is the same text in both, but with a run-time mode in the epilogue the compiler schedules the loop differently and
+// picks other scalar registers in it (no register more, no spill more: profiles/pooling_resources.txt): the default mode keeps a
+// form of its own, whose machine code is the kernel's from before the modes existed.
+template <int NT, bool RAGGED, bool POOL_MODES>
 __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int window = (int)blockIdx.x;              // full windows: = sentence = 128-token block
@@ -173,8 +177,8 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
             }
         }
     }
-    // ---- mean-pool + L2 normalise of the window's sentences (pool_normalize.h: the pooling kernel's body and bits), while the
-    // other workgroups are still in their layers: the rows were written by this workgroup and sit in the L2
+    // ---- mean-pool + L2 normalise (or what m.pool_mode asks for) of the window's sentences (pool_normalize.h: the pooling kernel's
+    // body and bits), while the other workgroups are still in their layers: the rows were written by this workgroup and sit in the L2
     if (m.pooled) {
         const int tid = thread_id();
         for (int j = 0; j < count; ++j) {
@@ -184,7 +188,8 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
             // sum of its lengths — somebody longer than max_len = 128, somebody shorter — a sentence that is not exactly that block
             // gets the NaN row and the status word of the length guard instead of numbers made of its neighbours' tokens)
             if (!RAGGED && (t0 != tok0 || n != 128)) n = -1;
-            pool_normalize_sentence(m.x, t0, n, b, 128 * NT, m.max_len, m.status, m.pooled, (float *)smem, tid, tid < 256);
+            if constexpr (POOL_MODES) pool_normalize_sentence(m.x, t0, n, b, 128 * NT, m.max_len, m.status, m.pooled, (float *)smem, tid, tid < 256, m.pool_mode);
+            else pool_normalize_sentence<false, false>(m.x, t0, n, b, 128 * NT, m.max_len, m.status, m.pooled, (float *)smem, tid, tid < 256);
             __syncthreads();                                  // (the next sentence reuses the partial rows)
         }
     }
@@ -202,9 +207,9 @@ bool model_kernel_supported(const GemmWeight &Wqkv, const GemmWeight &Wo, const 
 
 void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x, half_t *ctx, const int32_t *cu_seqlens, int n_sentences,
                          int n_tokens, const int2 *groups, int n_groups, const int *n_groups_dev, int n_head, float *pooled, int max_len,
-                         int *status, int slots, hipStream_t stream) {
+                         int *status, int pool_mode, int slots, hipStream_t stream) {
     ModelArgs m;
-    m.pooled = pooled; m.status = status; m.max_len = max_len;
+    m.pooled = pooled; m.status = status; m.max_len = max_len; m.pool_mode = pool_mode;
     m.x = x; m.ctx = ctx; m.cu = cu_seqlens; m.groups = groups; m.n_groups = n_groups_dev;
     m.n_layer = n_layer; m.n_head = n_head; m.n_sent = n_sentences; m.I = layers[0].W1->N; m.slot_mask = slots - 1;
     for (int l = 0; l < n_layer; ++l) {
@@ -220,7 +225,7 @@ void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x
     // (the full form keeps two context fragments per head in a register array sized by H: model_kernel_supported's d_head = 32)
     if (n_head * 32 != H) { fprintf(stderr, "launch_model_kernel: n_head %d x 32 != H %d\n", n_head, H); abort(); }
     const int grid = full || !groups ? n_sentences : n_groups;
-    static DeviceFlags configured[4];
+    static DeviceFlags configured[8];
     auto go = [&](auto kernel, int which) {
         configure_once(configured[which], [&] { (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
         BERT_LAUNCH(kernel, dim3(grid), dim3(512), lds, stream, m);
@@ -265,8 +270,13 @@ void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x
         }
 #endif
     };
-    if (full) { if (H == 256) go(model_kernel<2, false>, 0); else go(model_kernel<3, false>, 1); }
-    else { if (H == 256) go(model_kernel<2, true>, 2); else go(model_kernel<3, true>, 3); }
+    if (pool_mode == 0) {
+        if (full) { if (H == 256) go(model_kernel<2, false, false>, 0); else go(model_kernel<3, false, false>, 1); }
+        else { if (H == 256) go(model_kernel<2, true, false>, 2); else go(model_kernel<3, true, false>, 3); }
+    } else {
+        if (full) { if (H == 256) go(model_kernel<2, false, true>, 4); else go(model_kernel<3, false, true>, 5); }
+        else { if (H == 256) go(model_kernel<2, true, true>, 6); else go(model_kernel<3, true, true>, 7); }
+    }
 }
 
 }  // namespace bert_hip

@@ -17,9 +17,19 @@ static constexpr bool TEST_ROUTES = true;
 static constexpr bool TEST_ROUTES = false;
 #endif
 
-// A key and its value, with no questions asked: the parsing the environment and bert_hip_set_option share.
+int EngineOptions::pool_mode() const { return (pool_cls ? POOL_CLS : 0) | (normalize ? 0 : POOL_RAW); }
+
+// A key and its value, with no questions asked (but of the two that change what a context computes: they take the values they
+// name and nothing else): the parsing the environment and bert_hip_set_option share.
 void EngineOptions::apply(const std::string &key, const std::string &value) {
     const int n = atoi(value.c_str());
+    if (key == "pooling" || key == "normalize") {
+        const bool pooling = key == "pooling";
+        const char *const on = pooling ? "cls" : "1", *const off = pooling ? "mean" : "0";
+        if (value == on || value == off) (pooling ? pool_cls : normalize) = value == on;
+        else fprintf(stderr, "bert_hip: %s = \"%s\": expected \"%s\" or \"%s\"; ignored\n", key.c_str(), value.c_str(), off, on);
+        return;
+    }
     if (key == "gemm") gemm_naive = value == "naive";
     else if (key == "attn") attn_naive = value == "naive";
     else if (key == "qkv2") qkv2 = value != "0";
@@ -58,6 +68,7 @@ EngineOptions EngineOptions::from_env(const HParams &hp) {
         {"BERT_HIP_LN_FOLD", "ln_fold"},                      // (tuning: 0 = LayerNorm kernels of their own at H = 768)
         {"BERT_HIP_CHUNK_TOKENS", "chunk_tokens"}, {"BERT_HIP_WINDOW_SLOTS", "window_slots"},
         {"BERT_HIP_F32", "f32"},                              // (f32 files: f32 arithmetic like the reference's unless "f16")
+        {"BERT_HIP_POOLING", "pooling"}, {"BERT_HIP_NORMALIZE", "normalize"},
     };
     for (auto &ek : same_as_key)
         if (const char *v = getenv(ek[0])) o.apply(ek[1], v);

@@ -23,11 +23,16 @@ struct EngineOptions {
     // from 220 us: 252 us at 172 tokens (8 sentences), 330 at 363 (16), 376 at 512, 527 at 716, 606 at 1024 (round 5, same bits).
     int latency_tokens = 768;
     bool stage_kernel = true;         // small staged blocks come in by a kernel that reads the mapped pinned block, not by the copy engine
+    // How a pass ends (bert_hip.h): the mean over a sentence's tokens or the state of its first token ([CLS]), divided by its L2
+    // norm or not.  A pass reads both once, at its start (pool_mode()).
+    bool pool_cls = false, normalize = true;
+    int pool_mode() const;            // kernels.h: POOL_CLS | POOL_RAW
 
     // the defaults for a model of these dimensions, then the environment
     static EngineOptions from_env(const HParams &hp);
     // a key of bert_hip_set_option.  naive_images / fold_images: what was built at load (ModelWeights) — "gemm" = "naive" and
-    // "ln_fold" = "1" are refused, with a line on stderr, without them.  Unknown keys are ignored.
+    // "ln_fold" = "1" are refused, with a line on stderr, without them.  Unknown keys are ignored; so is, with a line on stderr, a value
+    // that "pooling" or "normalize" do not know (from the environment as well).
     void set(const std::string &key, const std::string &value, bool naive_images, bool fold_images);
 
 private:

@@ -263,22 +263,34 @@ int32_t bert_hip_test_embed_ln(int32_t table_type, int32_t H, int32_t n_vocab, i
     return 0;
 }
 
-int32_t bert_hip_test_pool_normalize(int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
-                                     float *out, int32_t *status) {
+// x [T][H] f16 bits -> the sentences' rows by the rule pool_mode names (kernels.h POOL_*), and the status word
+static int32_t test_pool(const char *me, int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
+                         int pool_mode, float *out, int32_t *status) {
     std::string err;
     const int T = cu_seqlens[n_sentences];
     DevBuf dx, dcu, dout, dst;
     if (!dx.upload(x, (size_t)T * H * 2, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
         !dout.alloc((size_t)n_sentences * H * 4, err) || !dst.alloc(16, err)) {
-        fprintf(stderr, "bert_hip_test_pool_normalize: %s\n", err.c_str());
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
         return -1;
     }
-    launch_pool_normalize(dx.as<half_t>(), dcu.as<int32_t>(), n_sentences, H, max_len, dst.as<int>(), dout.as<float>(), nullptr);
+    launch_pool_normalize(dx.as<half_t>(), dcu.as<int32_t>(), n_sentences, H, max_len, dst.as<int>(), dout.as<float>(), pool_mode, nullptr);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(out, dout.p, (size_t)n_sentences * H * 4, hipMemcpyDeviceToHost));
     CK(hipMemcpy(status, dst.p, 4, hipMemcpyDeviceToHost));
     return 0;
+}
+
+int32_t bert_hip_test_pool_normalize(int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
+                                     float *out, int32_t *status) {
+    return test_pool("bert_hip_test_pool_normalize", H, x, cu_seqlens, n_sentences, max_len, 0, out, status);
+}
+
+int32_t bert_hip_test_pool(int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len, int32_t pooling,
+                           int32_t normalize, float *out, int32_t *status) {
+    return test_pool("bert_hip_test_pool", H, x, cu_seqlens, n_sentences, max_len, (pooling ? POOL_CLS : 0) | (normalize ? 0 : POOL_RAW), out,
+                     status);
 }
 
 int32_t bert_hip_test_model_digest(const char *fname, int32_t *legacy_q4, uint64_t *digest) {

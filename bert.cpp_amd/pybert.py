@@ -22,7 +22,7 @@ BERT_H_SYMBOLS = [
 ]
 BERT_HIP_H_SYMBOLS = [
     "bert_hip_load_tokenizer", "bert_hip_tokenize_batch", "bert_hip_n_layer", "bert_hip_n_head", "bert_hip_n_intermediate", "bert_hip_n_vocab",
-    "bert_hip_ftype", "bert_hip_device", "bert_hip_n_devices", "bert_hip_encode_batch", "bert_hip_eval_packed", "bert_hip_eval_packed_gather",
+    "bert_hip_ftype", "bert_hip_device", "bert_hip_n_devices", "bert_hip_pooling", "bert_hip_normalize", "bert_hip_encode_batch", "bert_hip_eval_packed", "bert_hip_eval_packed_gather",
     "bert_hip_eval_packed_device", "bert_hip_reserve", "bert_hip_check", "bert_hip_eval_hidden",
     "bert_hip_profile_enable", "bert_hip_profile_report", "bert_hip_set_option", "bert_hip_version",
     "bert_hip_index_create", "bert_hip_index_free", "bert_hip_index_size", "bert_hip_index_reserve", "bert_hip_index_add",
@@ -36,6 +36,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_layer_tail", "bert_hip_test_shard_bounds", "bert_hip_test_build_windows",
     "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots",
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
+    "bert_hip_test_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
 ]
@@ -61,7 +62,7 @@ def _declare_product_abi(L):
     L.bert_hip_load_tokenizer.restype = vp; L.bert_hip_load_tokenizer.argtypes = [C.c_char_p]
     L.bert_free.restype = None; L.bert_free.argtypes = [vp]
     for fn in ("bert_n_embd", "bert_n_max_tokens", "bert_hip_n_layer", "bert_hip_n_head", "bert_hip_n_intermediate",
-               "bert_hip_n_vocab", "bert_hip_ftype", "bert_hip_device"):
+               "bert_hip_n_vocab", "bert_hip_ftype", "bert_hip_device", "bert_hip_pooling", "bert_hip_normalize"):
         getattr(L, fn).restype = i32; getattr(L, fn).argtypes = [vp]
     L.bert_vocab_id_to_token.restype = C.c_char_p; L.bert_vocab_id_to_token.argtypes = [vp, i32]
     L.bert_tokenize.restype = None; L.bert_tokenize.argtypes = [vp, C.c_char_p, i32p, i32p, i32]
@@ -149,6 +150,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_embed_ln.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32p, i32p, i32, vp]
     L.bert_hip_test_pool_normalize.restype = i32
     L.bert_hip_test_pool_normalize.argtypes = [i32, vp, i32p, i32, i32, vp, i32p]
+    L.bert_hip_test_pool.restype = i32
+    L.bert_hip_test_pool.argtypes = [i32, vp, i32p, i32, i32, i32, i32, vp, i32p]
     L.bert_hip_test_model_digest.restype = i32
     L.bert_hip_test_model_digest.argtypes = [C.c_char_p, i32p, C.POINTER(C.c_uint64)]
     L.bert_hip_test_pack_weight.restype = i32
@@ -201,6 +204,18 @@ def test_pool_normalize(x: np.ndarray, cu_seqlens, max_len: int):
     r = test_lib().bert_hip_test_pool_normalize(x.shape[1], x.ctypes.data, _i32p(cu), len(cu) - 1, max_len, out.ctypes.data, _i32p(st))
     if r != 0:
         raise RuntimeError(f"bert_hip_test_pool_normalize failed: {r}")
+    return out, int(st[0])
+
+
+def test_pool(x: np.ndarray, cu_seqlens, max_len: int, pooling: str = "mean", normalize: bool = True):
+    """The pooling kernel under a context's settings: pooling "mean" | "cls"; returns (rows [n_sentences, H] f32, status word)."""
+    x = np.ascontiguousarray(x, dtype=np.float16); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    out = np.zeros((len(cu) - 1, x.shape[1]), dtype=np.float32)
+    st = np.zeros(1, dtype=np.int32)
+    r = test_lib().bert_hip_test_pool(x.shape[1], x.ctypes.data, _i32p(cu), len(cu) - 1, max_len, {"mean": 0, "cls": 1}[pooling],
+                                      int(bool(normalize)), out.ctypes.data, _i32p(st))
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_pool failed: {r}")
     return out, int(st[0])
 
 
@@ -472,6 +487,14 @@ class BertModel:
 
     def set_option(self, key: str, value: str) -> None:
         self.lib.bert_hip_set_option(self.ctx, key.encode(), value.encode())
+
+    def pooling(self) -> int:
+        """0 mean, 1 cls (set_option "pooling" / BERT_HIP_POOLING); -1 for a tokenizer-only context."""
+        return int(self.lib.bert_hip_pooling(self.ctx))
+
+    def normalize(self) -> int:
+        """1 or 0 (set_option "normalize" / BERT_HIP_NORMALIZE); -1 for a tokenizer-only context."""
+        return int(self.lib.bert_hip_normalize(self.ctx))
 
     def index(self, dim: Optional[int] = None, dtype: str = "f16") -> "BertIndex":
         """An embedding index on the context's first device (bert_hip_index_create): dim None = n_embd, dtype "f16" | "f32" |

@@ -32,6 +32,9 @@ BERT_API int32_t bert_hip_n_vocab(struct bert_ctx *ctx);
 BERT_API int32_t bert_hip_ftype(struct bert_ctx *ctx);        /* 0 f32, 1 f16, 2 q4_0, 3 q4_1 */
 BERT_API int32_t bert_hip_device(struct bert_ctx *ctx);       /* HIP ordinal of the context's first device, -1 if none */
 BERT_API int32_t bert_hip_n_devices(struct bert_ctx *ctx);    /* GPUs the context spreads its batches over */
+/* How the context's passes end ("pooling" / "normalize" below); -1 for a context without a device (tokenizer-only, NULL).       */
+BERT_API int32_t bert_hip_pooling(struct bert_ctx *ctx);      /* 0 mean, 1 cls */
+BERT_API int32_t bert_hip_normalize(struct bert_ctx *ctx);    /* 1 the embedding is divided by its L2 norm, 0 it is not */
 
 /* bert_encode_batch with a result: the number of inputs encoded (all of them, or the inputs in front of the first one
  * that could not be evaluated — later embeddings stay untouched), negative on an internal error.                     */
@@ -102,7 +105,7 @@ BERT_API int32_t bert_hip_eval_hidden(struct bert_ctx *ctx, const bert_vocab_id 
 BERT_API void    bert_hip_profile_enable(struct bert_ctx *ctx, int32_t on);
 BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_t buf_len);
 
-/* Environment, read by bert_load_from_file (eight switches):
+/* Environment, read by bert_load_from_file (eleven switches):
  *   BERT_HIP_DEVICES       "all" or a comma-separated list of HIP ordinals without repeats: the GPUs of the context
  *                          (default: the calling thread's current device — one context, one GPU, unless asked otherwise);
  *                          BERT_HIP_DEVICE=<n>, the spelling of the first builds, is read as a list of one when this is unset
@@ -130,13 +133,26 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  *                          them (no LayerNorm launch but the last; roundings differ from the un-folded sequence in the last bits), or a
  *                          LayerNorm kernel per LayerNorm.  Read at load: 0 builds no folded weight images, and set_option("ln_fold",
  *                          "1") on such a context is ignored.  bert_hip_eval_hidden always takes the un-folded sequence.
+ *   BERT_HIP_POOLING       "mean" (default) | "cls" — what a sentence's embedding is made of: the mean over its tokens' final states (the
+ *                          reference's; the all-MiniLM, e5 and gte families), or the final state of its FIRST token as the caller gave
+ *                          it (the BGE family: bert_tokenize puts [CLS] there, the packed entry points take whatever id comes first)
+ *   BERT_HIP_NORMALIZE     1 (default) | 0 — that row divided by its L2 norm (no epsilon), or as it is.  "cls" with 0 is the stored state
+ *                          exactly (the f16 values converted to f32; the f32 values on the f32 route), "mean" with 0 the sums that 1
+ *                          scales.  Both settings are per context and change nothing else: the same kernels run, the length guard
+ *                          (NaN row, status word) and "the same sentence gives the same bits in any batch, on the latency and the batch
+ *                          route, with one launch or two" hold in every mode, and whatever returns or consumes a context's embeddings
+ *                          follows them — bert_eval[_batch], bert_encode[_batch], bert_hip_eval_packed[_device, _gather], the embedding
+ *                          of bert_hip_eval_hidden, bert_hip_index_add_texts and _search_texts.  Any other value: a line on stderr, the
+ *                          setting stays as it was (the keys below likewise).  A pass reads both once, at its start; a host call cut
+ *                          into chunks or spread over devices uses one value throughout
  *   BERT_HIP_QUIET         1 = no progress text on stdout during load, no "unknown token" lines on stderr from bert_tokenize
  * bert_hip_set_option (after load; tests and tuning): "qkv2" / "tail" / "gemm256" / "latency" = "0" | "1" switch single kernels
  * of the fused family, "one_launch" = "0" | "1" (default: all layers in one launch for well-filled windows) | "2" (whenever the
  * kernel takes the batch), "gemm" / "attn" = "mfma" | "naive" (libbert_test.so), "ln_fold" = "0" | "1", "f32" = "exact" | "f16", "latency_tokens" = n, "window_slots" = "16" | "8" (process-wide default, read once
  * per forward pass), "chunk_tokens" = n, "gather_super_tokens" = n (bert_hip_eval_packed_gather: tokens per device and super-batch, 0 =
  * four device chunks), "stage_kernel" = "0" | "1" (host API: staged blocks of at most 256 KiB travel by a kernel that reads the mapped
- * pinned memory instead of the copy engine), "profile_replay" (above).                                                                 */
+ * pinned memory instead of the copy engine), "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"
+ * (BERT_HIP_POOLING / BERT_HIP_NORMALIZE above; bert_hip_pooling / bert_hip_normalize return what is in force).                       */
 BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const char *value);
 
 /* Embedding index: rows in HBM on the context's FIRST device (bert_hip_device), exact top-k search by inner product.
@@ -159,8 +175,9 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  *            stream capture).  Without it storage and workspace grow on demand.
  * Semantics:
  *   - score = sum_i q[i] * row[i], accumulated in f32: f32 rows on v_mfma_f32_32x32x2_f32 (an f32 fma chain), f16 rows and
- *     f16-rounded queries on v_mfma_f32_32x32x16_f16 (rows zero-padded to its k-step, which changes no sum).  The engine's
- *     embeddings are L2-normalised: for them the score is the cosine.
+ *     f16-rounded queries on v_mfma_f32_32x32x16_f16 (rows zero-padded to its k-step, which changes no sum).  With "normalize" = 1
+ *     (the default) the engine's embeddings are L2-normalised: for them the score is the cosine; with 0 it is the plain inner
+ *     product of what add_texts and search_texts encoded.
  *   - int8 (dtype 2), all arithmetic f32 unless stated: each row and each query x is quantized on its own, amax = max_i |x_i|,
  *     scale = amax / 127 (correctly rounded), code_i = clamp(rint(x_i / scale), -127, 127) (rint: nearest even; the division
  *     correctly rounded), every code 0 if scale == 0; if any x_i is NaN or +-inf the scale is NaN and every code 0.  Codes

@@ -66,6 +66,9 @@ BERT_API int32_t bert_hip_test_embed_ln(int32_t table_type, int32_t H, int32_t n
  * the device status word (1 if a sentence length is outside [1, max_len]: its row is NaN).                              */
 BERT_API int32_t bert_hip_test_pool_normalize(int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences,
                                               int32_t max_len, float *out, int32_t *status);
+/* The same kernel under the settings of a context (bert_hip.h): pooling 0 mean | 1 the sentence's first row, normalize 1 | 0.   */
+BERT_API int32_t bert_hip_test_pool(int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
+                                    int32_t pooling, int32_t normalize, float *out, int32_t *status);
 
 /* Parses a model file (no GPU): returns the number of tensors (negative on error, message on stderr), whether the file uses the
  * legacy 20 / 24-byte q4 blocks, and a digest of every tensor's name, type and bytes AFTER conversion to the current layout.   */
