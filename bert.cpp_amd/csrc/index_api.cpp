@@ -72,6 +72,27 @@ bool allow_ok(const char *me, const Index &x, const uint32_t *allow, int32_t n_w
     return !allow || n_words >= need;
 }
 
+// the shape of a rescore call (-2 after a line on stderr otherwise); have_ptrs: every pointer the call needs is there
+bool rescore_args_ok(const char *me, int32_t n_queries, int32_t n_cand, int32_t k, bool have_ptrs) {
+    const bool ok = k >= 1 && k <= Index::MAX_K && n_cand >= 1 && n_cand <= Index::MAX_CAND && n_queries >= 0 && (n_queries == 0 || have_ptrs);
+    if (!ok) fprintf(stderr, "%s: 1 <= k <= 256, 1 <= n_cand <= 1024, n_queries >= 0 and queries / candidates / outputs required\n", me);
+    return ok;
+}
+
+// what a two-stage search asks of its two indexes and its shape (-2 after a line on stderr otherwise)
+bool two_stage_ok(const char *me, const bert_hip_index *coarse, const bert_hip_index *fine, int32_t n_queries, int32_t n_cand, int32_t k,
+                  bool have_ptrs) {
+    const char *why = nullptr;
+    if (!coarse || !coarse->ix) why = "no coarse index";
+    else if (coarse->ctx != fine->ctx) why = "the two indexes belong to different contexts";
+    else if (coarse->ix->dim() != fine->ix->dim()) why = "the two indexes differ in dim";
+    else if (coarse->ix->size() != fine->ix->size()) why = "the two indexes differ in size";
+    else if (k < 1 || k > n_cand || n_cand > Index::MAX_K) why = "1 <= k <= n_cand <= 256 required";
+    else if (n_queries < 0 || (n_queries > 0 && !have_ptrs)) why = "n_queries >= 0 and queries / outputs required";
+    if (why) fprintf(stderr, "%s: %s\n", me, why);
+    return !why;
+}
+
 struct FileCloser {
     void operator()(FILE *f) const { if (f) fclose(f); }
 };
@@ -177,6 +198,47 @@ int32_t bert_hip_index_search_filtered_device(struct bert_hip_index *ix, int32_t
     return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
         if (!allow_ok(me, x, d_allow, n_words)) return -2;
         return x.search_device(n_queries, d_queries, k, d_ids, d_scores, (hipStream_t)stream, err, d_allow) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_rescore(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t n_cand, const int32_t *cand_ids,
+                               int32_t k, int32_t *ids, float *scores) {
+    const char *me = "bert_hip_index_rescore";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!rescore_args_ok(me, n_queries, n_cand, k, queries && cand_ids && ids && scores)) return -2;
+        for (size_t i = 0; i < (size_t)n_queries * n_cand; ++i)
+            if (cand_ids[i] < -1 || cand_ids[i] >= x.size()) {
+                fprintf(stderr, "%s: candidate id %d is outside [-1, %d)\n", me, cand_ids[i], x.size());
+                return -2;
+            }
+        return x.rescore_to_host(n_queries, queries, n_cand, cand_ids, k, ids, scores, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_rescore_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t n_cand,
+                                      const int32_t *d_cand_ids, int32_t k, int32_t *d_ids, float *d_scores, void *stream) {
+    const char *me = "bert_hip_index_rescore_device";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!rescore_args_ok(me, n_queries, n_cand, k, d_queries && d_cand_ids && d_ids && d_scores)) return -2;
+        return x.rescore_device(n_queries, d_queries, n_cand, d_cand_ids, k, d_ids, d_scores, (hipStream_t)stream, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_rescored(struct bert_hip_index *coarse, struct bert_hip_index *fine, int32_t n_queries, const float *queries,
+                                       int32_t n_cand, int32_t k, int32_t *ids, float *scores) {
+    const char *me = "bert_hip_index_search_rescored";
+    return index_call(me, fine, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!two_stage_ok(me, coarse, fine, n_queries, n_cand, k, queries && ids && scores)) return -2;
+        return x.search_rescored_to_host(*coarse->ix, n_queries, queries, n_cand, k, ids, scores, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_rescored_device(struct bert_hip_index *coarse, struct bert_hip_index *fine, int32_t n_queries,
+                                              const float *d_queries, int32_t n_cand, int32_t k, int32_t *d_ids, float *d_scores, void *stream) {
+    const char *me = "bert_hip_index_search_rescored_device";
+    return index_call(me, fine, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!two_stage_ok(me, coarse, fine, n_queries, n_cand, k, d_queries && d_ids && d_scores)) return -2;
+        return x.search_rescored_device(*coarse->ix, n_queries, d_queries, n_cand, k, d_ids, d_scores, (hipStream_t)stream, err) != 0 ? -3 : 0;
     });
 }
 

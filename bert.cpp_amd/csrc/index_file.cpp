@@ -22,12 +22,16 @@ uint32_t get_u32(const unsigned char *p) {
 int index_elem_size(int dtype) { return dtype == 0 ? 4 : dtype == 1 ? 2 : dtype == 2 ? 1 : 0; }
 
 int index_dpad(int dtype, int dim) {
-    const int step = dtype == 2 ? 32 : dtype == 1 ? 16 : 8;
+    const int step = dtype == 3 ? 128 : dtype == 2 ? 32 : dtype == 1 ? 16 : 8;
     return (dim + step - 1) / step * step;
 }
 
+uint64_t index_row_bytes(int dtype, int dpad) {
+    return dtype == 3 ? (uint64_t)dpad / 8 : (uint64_t)dpad * (uint64_t)index_elem_size(dtype);
+}
+
 uint64_t index_file_bytes(const IndexFileHeader &h) {
-    uint64_t n = INDEX_HEADER_BYTES + (uint64_t)h.n_rows * h.dpad * (uint64_t)index_elem_size((int)h.dtype);
+    uint64_t n = INDEX_HEADER_BYTES + (uint64_t)h.n_rows * index_row_bytes((int)h.dtype, (int)h.dpad);
     if (h.dtype == 2) n += (uint64_t)h.n_rows * 4;
     if (h.has_live) n += ((uint64_t)h.n_rows + 31) / 32 * 4;
     return n;
@@ -48,7 +52,7 @@ bool index_header_check(const void *buf, size_t buf_len, uint64_t file_bytes, In
     g.version = get_u32(p + 8); g.dtype = get_u32(p + 12); g.dim = get_u32(p + 16);
     g.dpad = get_u32(p + 20); g.n_rows = get_u32(p + 24); g.has_live = get_u32(p + 28);
     if (g.version != INDEX_FILE_VERSION) { err = "version " + std::to_string(g.version) + " (this build reads version 1)"; return false; }
-    if (g.dtype > 2) { err = "dtype " + std::to_string(g.dtype) + " (0 f32, 1 f16, 2 i8)"; return false; }
+    if (g.dtype > 3) { err = "dtype " + std::to_string(g.dtype) + " (0 f32, 1 f16, 2 i8, 3 b1)"; return false; }
     if (g.dim < 1 || g.dim > (uint32_t)INDEX_MAX_DIM) { err = "dim " + std::to_string(g.dim) + " (1 .. 2048)"; return false; }
     const uint32_t dpad = (uint32_t)index_dpad((int)g.dtype, (int)g.dim);
     if (g.dpad != dpad) { err = "dpad " + std::to_string(g.dpad) + " where dim " + std::to_string(g.dim) + " is stored in " + std::to_string(dpad); return false; }

@@ -1,6 +1,6 @@
 // search.h — an embedding index in HBM and its exact top-k inner-product search (search.hip; C ABI: bert_hip_index_* in
-// include/bert_hip.h).  Rows live on the device of the engine the index was made from, as f32 or as f16 (RNE), each row
-// zero-padded to the k-step of the score kernel's MFMA.  A search is a GEMM (queries x rows x dim) whose epilogue selects
+// include/bert_hip.h).  Rows live on the device of the engine the index was made from, as f32, as f16 (RNE), as i8 codes with a
+// scale or as one sign bit per element (b1), each row zero-padded to the k-step of the score kernel's MFMA.  A search is a GEMM (queries x rows x dim) whose epilogue selects
 // instead of storing: index_topk_kernel keeps a top-k per (query, slice of rows) in LDS, topk_merge_kernel merges the
 // slices' lists per query.  The score matrix never reaches HBM.
 //
@@ -8,6 +8,11 @@
 // in a host mirror; bits at and beyond size() are zero in the mirror and ignored on the device.  A search then (or with an
 // allow-list, a second bitmap of the same shape from the caller) runs the masked instantiation of index_topk_kernel.  An
 // index that never saw a removal has no bitmap and launches what it always did.
+//
+// Rescoring: index_rescore_kernel scores each query against the rows its own candidate list names (the same ScoreBlock as
+// the search, hence the same score bits) into [nq][n_cand] lists in the workspace, and topk_merge_kernel selects from them.
+// A two-stage search is a search of a coarse index (b1, say) with k' = n_cand whose ids stay on the device and are rescored
+// against a finer index of the same rows.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,9 +30,10 @@ class Index {
 public:
     static constexpr int MAX_K = 256, MAX_DIM = INDEX_MAX_DIM;
     static constexpr int QCHUNK = 4096;                  // queries per internal pass (workspace bound)
+    static constexpr int MAX_CAND = 1024;                // candidates per query of a rescore
 
     // dtype 0: f32 rows, 1: f16 rows (queries rounded to f16 as well), 2: i8 rows with one f32 scale each (queries quantized
-    // the same way; search.hip)
+    // the same way; search.hip), 3: one sign bit per element, no scale (queries quantized to i8 codes and a scale)
     static Index *create(Engine *eng, int dim, int dtype, std::string &err);
     ~Index();
 
@@ -50,6 +56,19 @@ public:
     // words as above; blocking
     int search_to_host(int nq, const float *q, bool q_on_device, int k, int32_t *ids, float *scores, std::string &err,
                        const uint32_t *allow = nullptr);
+    // Rescoring: ids / scores [nq][k] = the best k of each query's own candidates d_cand [nq][n_cand] (ids; < 0, >= size and
+    // removed rows are skipped; repeats count as often as they appear), scored as a search scores them.  1 <= n_cand <=
+    // MAX_CAND, 1 <= k <= MAX_K.  Asynchronous on s; 0 or -1
+    int rescore_device(int nq, const float *d_q, int n_cand, const int32_t *d_cand, int k, int32_t *d_ids, float *d_scores,
+                       hipStream_t s, std::string &err);
+    // host queries, candidates (every id in [-1, size): the caller checks) and results (written only on success); blocking
+    int rescore_to_host(int nq, const float *q, int n_cand, const int32_t *cand, int k, int32_t *ids, float *scores, std::string &err);
+    // Two-stage search: coarse.search_device with k' = n_cand, the ids kept on the device, then this index's rescore_device
+    // with the same f32 queries.  The caller checks that both live on one engine and have equal dim and size, and
+    // 1 <= k <= n_cand <= MAX_K.  Asynchronous on s; 0 or -1
+    int search_rescored_device(Index &coarse, int nq, const float *d_q, int n_cand, int k, int32_t *d_ids, float *d_scores,
+                               hipStream_t s, std::string &err);
+    int search_rescored_to_host(Index &coarse, int nq, const float *q, int n_cand, int k, int32_t *ids, float *scores, std::string &err);
     // marks rows as removed (ids in [0, size) or -1 with the index unchanged; repeats ignored): the number newly removed; blocking
     int remove(int n, const int32_t *ids, std::string &err);
     // drops the removed rows' storage: live rows keep order and bits, ids 0 .. n_live - 1; old_ids (null or [n_live]) the
@@ -72,17 +91,21 @@ private:
     bool grow_rows(int n_rows, std::string &err);
     bool grow(DevBuf &b, size_t bytes, std::string &err);
     void enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow);
+    void enqueue_queries(int nq, const float *d_q, hipStream_t s);
+    bool grow_queries(int nqc, std::string &err);
     bool make_live(std::string &err);
     bool upload_live(size_t w0, size_t w1, std::string &err);
     void drop_live();
 
     Engine *eng_ = nullptr;
-    int dim_ = 0, dtype_ = 0, dpad_ = 0, es_ = 4;       // dpad_: elements per stored row, es_: bytes per element
+    int dim_ = 0, dtype_ = 0, dpad_ = 0;                // dpad_: elements per stored row
+    size_t row_bytes_ = 0, qrow_bytes_ = 0;             // bytes per stored row; per query as the score kernel reads it (b1: i8 codes)
     int n_ = 0, cap_ = 0;
-    void *rows_ = nullptr;                              // [cap_][dpad_]
+    void *rows_ = nullptr;                              // [cap_][row_bytes_]
     float *rscale_ = nullptr;                           // i8: [cap_] row scales
     DevBuf ws_s_, ws_i_, qbuf_;                         // per-(query, slice) lists; the current chunk's queries as stored
-    DevBuf qscale_;                                     // i8: the current chunk's query scales
+    DevBuf qscale_;                                     // i8, b1: the current chunk's query scales
+    DevBuf cand_i_, cand_s_, cand_in_;                  // two-stage search: the coarse stage's lists; host rescore: the caller's ids
     // removed rows: device words [ceil(cap_ / 32)] (null until the first remove) and their host mirror of the same length
     uint32_t *live_ = nullptr;
     std::vector<uint32_t> live_h_;

@@ -3,7 +3,8 @@
 // A search of nq queries over N rows of dim elements is a GEMM (M = queries, N = rows, K = dim) whose epilogue selects:
 //   index_topk_kernel<T>  one workgroup per (query tile of 32, slice of rows).  Each wave scores a 32 x 32 block
 //                         (queries x rows) per step on the matrix cores — f16 rows: v_mfma_f32_32x32x16_f16, f32 rows:
-//                         v_mfma_f32_32x32x2_f32, i8 rows: v_mfma_i32_32x32x32_i8 and the two scales — and a lane ends the
+//                         v_mfma_f32_32x32x2_f32, i8 rows: v_mfma_i32_32x32x32_i8 and the two scales, b1 rows: the same MFMA over
+//                         bits expanded to +1 / -1 bytes in registers and the query's scale — and a lane ends the
 //                         step with one row's scores for 16 queries.  Every score
 //                         is compared with its query's threshold (the k-th best of this workgroup so far, kept in registers);
 //                         only the ones that beat it go into the query's candidate queue in LDS (an LDS atomic hands out the
@@ -12,26 +13,37 @@
 //                         workgroup writes one sorted top-k list per query to the workspace.
 //   topk_merge_kernel     one workgroup per query: the same threshold / queue / sort over the slices' lists, then the
 //                         final ids and scores.
-//                         The masked instantiations (TopkArgsMasked / TopkArgsI8Masked: an index with removed rows, or a
+//                         The masked instantiations (TopkArgsMasked / TopkArgsI8Masked / TopkArgsB1Masked: an index with removed rows, or a
 //                         search with an allow-list) read one word of each bitmap per wave and step — the wave's block is
 //                         the 32 rows of that word —, score and push only the rows whose bit of live & allow is set, and
 //                         skip the loads and MFMAs of a block whose combined word is zero.
+//   index_rescore_kernel<T>  one wave per (query, 32 of its candidates): the rows the ids name against that one query through the
+//                         same ScoreBlock (the same MFMA chain per (query, row), so the same bits as a search), scores and ids
+//                         [nq][n_cand] into the workspace — id INT_MAX, score -inf for an entry that names no live row —, from
+//                         which topk_merge_kernel selects.
 //   index_gather_kernel   compaction: stored rows (and i8 scales) of the listed old ids into a fresh allocation.
 //   live_set_range_kernel sets the live bits of newly added rows.
 //   index_convert_kernel  f32 rows (added rows, queries) -> the stored form: f32 or f16 (RNE), zero-padded to dpad.
 //   index_quantize_kernel f32 rows (added rows, queries) -> the i8 form: one wave per row, codes zero-padded to dpad and one
 //                         f32 scale per row.
+//   index_pack_b1_kernel  f32 rows (added rows) -> the b1 form: one wave per row, 64 sign bits per step from a ballot.
 //
 // The i8 form (dtype 2): a row or query x is stored as scale = amax / 127 (amax = max |x_i|; NaN if any x_i is NaN or +-inf)
 // and codes c_i = clamp(rint(x_i / scale), -127, 127) (all 0 if the scale is 0 or NaN); its score is
 // ((float)dot * qscale) * rscale with dot = sum_i qc_i rc_i an exact int32 (|dot| <= 2048 * 127^2 < 2^31).  A row that held a
 // NaN or an inf scores NaN and is never returned; so does every row for such a query.
 //
+// The b1 form (dtype 3): element i of a row is bit i & 31 of u32 word i >> 5, set iff x_i > 0 (so -0, NaN and -inf give 0, +inf
+// gives 1: a row's non-finite elements are not detected); dpad is a multiple of 128 (rows are whole 16-byte pieces), the padding
+// bits zero, no scale.  Queries are quantized as for i8.  score = (float)dot * qscale with dot = sum_i qc_i (bit_i ? +1 : -1) an
+// exact int32; the padding's -1 meets a zero code.
+//
 // Order of a result: larger score first, equal scores (==, so +0 equals -0) by smaller id; NaN scores never pass a compare
 // and are never returned; missing entries are id -1, score -inf (inside the kernels: id INT_MAX, which ranks below every row).
 // Determinism: a (query, row) score is one MFMA accumulation chain in a fixed k order that depends on nothing but dpad (i8: an
 // exact integer sum, then two multiplies), and the key order is total over distinct rows, so the set and order of a result do
-// not depend on the slicing, the chunking of the queries, the neighbours in a batch, or k (top-10 is the first 10 of top-100).
+// not depend on the slicing, the chunking of the queries, the neighbours in a batch, or k (top-10 is the first 10 of top-100);
+// nor on whether a search or a rescore computed it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -166,8 +178,61 @@ template <> struct ScoreBlock<int8_t> {
     }
 };
 
+// a stored byte of a b1 row: the sign bits of eight elements
+struct b1_t { uint8_t bits; };
+
+template <> struct ScoreBlock<b1_t> {
+    // bit 4 j + b of bits16 in byte b of element j: 0x01 for a set bit, 0xff (-1) for a clear one.  The multiply puts bit b of
+    // a nibble at bit 8 b (four copies 7 bits apart, which do not overlap); the byte permute looks 0 / 1 up in {0xff, 0x01}
+    static __device__ __forceinline__ i32x4 expand(uint32_t bits16) {
+        i32x4 v;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t t = (((bits16 >> (4 * j)) & 0xfu) * 0x00204081u) & 0x01010101u;
+            v[j] = (int)__builtin_amdgcn_perm(0x000001ffu, 0x000001ffu, t);
+        }
+        return v;
+    }
+    // v_mfma_i32_32x32x32_i8, the row operand dequantised in the tile load: lane l feeds step s the query's 16 codes at
+    // k = 32 s + 16 (l >> 5) and the row's bits at the same k — half (l >> 5) of its word s — as sixteen +-1 bytes.  A 16-byte
+    // load of the row serves four steps.  (rok false: the row's scores mean nothing — no caller reads them; the bits are
+    // not loaded.)
+    static __device__ __forceinline__ void run(const int8_t *qp, const b1_t *rp, bool qok, bool rok, int dpad, int h, i32x16 &acc) {
+        constexpr int U = 2;
+        const i32x4 z = {};
+        const u32x4 zw = {};
+        for (int k0 = 0; k0 < dpad; k0 += 128 * U) {
+            i32x4 a[U][4];
+            u32x4 w[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = k0 + 128 * u < dpad;
+                w[u] = rok && in ? *(const u32x4 *)(rp + ((k0 + 128 * u) >> 3)) : zw;
+#pragma unroll
+                for (int t = 0; t < 4; ++t) a[u][t] = qok && in ? *(const i32x4 *)(qp + k0 + 128 * u + 32 * t + 16 * h) : z;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (k0 + 128 * u < dpad) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[u][t], expand((w[u][t] >> (16 * h)) & 0xffffu), acc, 0, 0, 0);
+                }
+        }
+    }
+};
+
+// the element type of a query as the score block reads it, and the bytes of a stored row of dpad elements
+template <class T> struct QueryElem { using type = T; };
+template <> struct QueryElem<b1_t> { using type = int8_t; };
+// stored row `row` of rows of dpad elements (b1: dpad / 8 bytes)
+template <class T> __device__ __forceinline__ const T *row_ptr(const void *rows, size_t row, int dpad) {
+    if constexpr (std::is_same_v<T, b1_t>) return (const T *)rows + row * (dpad >> 3);
+    else return (const T *)rows + row * dpad;
+}
+
 struct TopkArgs {
-    const void *rows, *queries;          // [n_rows][dpad], [nq][dpad] of T
+    const void *rows, *queries;          // [n_rows][dpad], [nq][dpad] of T (b1: rows of dpad bits, queries of dpad i8 codes)
     float *ws_s;                         // [nq][n_slices][k] per-(query, slice) lists, best first
     int *ws_i;
     int n_rows, dpad, nq, n_qtiles, n_slices, slice_rows, k, L, n_items;
@@ -177,7 +242,12 @@ struct TopkArgsI8 : TopkArgs {
     const float *qscale, *rscale;        // [nq], [n_rows]
 };
 
-// (types of their own again: the three kernels above keep their argument blocks.)  live, allow: words [ceil(n_rows / 32)],
+// (b1: a query scale and no row scale)
+struct TopkArgsB1 : TopkArgs {
+    const float *qscale;                 // [nq]
+};
+
+// (types of their own again: the kernels above keep their argument blocks.)  live, allow: words [ceil(n_rows / 32)],
 // bit b of word w set = row 32 w + b is live / may be returned; either may be null = all ones
 struct TopkArgsMasked : TopkArgs {
     const uint32_t *live, *allow;
@@ -185,13 +255,18 @@ struct TopkArgsMasked : TopkArgs {
 struct TopkArgsI8Masked : TopkArgsI8 {
     const uint32_t *live, *allow;
 };
-template <class Args> constexpr bool is_masked_v = std::is_same_v<Args, TopkArgsMasked> || std::is_same_v<Args, TopkArgsI8Masked>;
+struct TopkArgsB1Masked : TopkArgsB1 {
+    const uint32_t *live, *allow;
+};
+template <class Args> constexpr bool is_masked_v = std::is_same_v<Args, TopkArgsMasked> || std::is_same_v<Args, TopkArgsI8Masked> ||
+                                                   std::is_same_v<Args, TopkArgsB1Masked>;
 
 // LDS: float scores [nqv][L], int ids [nqv][L], int count [nqv] — per query the current top-k in [0, k), the queue behind
-// (Args: TopkArgsI8 for T = int8_t, TopkArgs otherwise; their masked forms)
+// (Args: TopkArgsI8 for T = int8_t, TopkArgsB1 for b1_t, TopkArgs otherwise; their masked forms)
 template <class T, class Args>
 __global__ __launch_bounds__(NT) void index_topk_kernel(Args a) {
-    constexpr bool I8 = std::is_same_v<T, int8_t>, MASKED = is_masked_v<Args>;
+    constexpr bool I8 = std::is_same_v<T, int8_t>, B1 = std::is_same_v<T, b1_t>, MASKED = is_masked_v<Args>;
+    using QE = typename QueryElem<T>::type;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // workgroup b runs on XCD b % 8: consecutive items — the query tiles of one slice of rows — go to one XCD, so that
     // they find the slice in that XCD's L2 (the grid is a multiple of 8; items beyond n_items do nothing)
@@ -212,9 +287,9 @@ __global__ __launch_bounds__(NT) void index_topk_kernel(Args a) {
     int ti[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { ts[r] = -INFINITY; ti[r] = SENT_ID; }
-    // i8: the scales of this lane's 16 queries
+    // i8, b1: the scales of this lane's 16 queries
     [[maybe_unused]] float qs[16];
-    if constexpr (I8) {
+    if constexpr (I8 || B1) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int q = (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -224,7 +299,7 @@ __global__ __launch_bounds__(NT) void index_topk_kernel(Args a) {
     __syncthreads();
 
     const bool qok = col < nqv;
-    const T *qp = (const T *)a.queries + (size_t)(q0 + (qok ? col : 0)) * a.dpad;
+    const QE *qp = (const QE *)a.queries + (size_t)(q0 + (qok ? col : 0)) * a.dpad;
     // a step pushes at most STEP_ROWS entries per query: sort before a queue could hold fewer free slots
     const int room = L - k - STEP_ROWS;
     for (int base = r0; base < r1; base += STEP_ROWS) {
@@ -246,8 +321,13 @@ __global__ __launch_bounds__(NT) void index_topk_kernel(Args a) {
         f32x16 acc = {};
         // (masked: a block without a qualifying row costs no loads and no MFMAs — wave-uniform, and the barriers are below)
         if (!MASKED || word != 0) {
-            const T *rp = (const T *)a.rows + (size_t)(rok ? row : r0) * a.dpad;
-            if constexpr (I8) {
+            const T *rp = row_ptr<T>(a.rows, (size_t)(rok ? row : r0), a.dpad);
+            if constexpr (B1) {
+                i32x16 dot = {};
+                ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, dot);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = (float)dot[r] * qs[r];
+            } else if constexpr (I8) {
                 const float rs = a.rscale[rok ? row : r0];
                 i32x16 dot = {};
                 ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, dot);
@@ -349,6 +429,55 @@ __global__ __launch_bounds__(NT) void topk_merge_kernel(MergeArgs a) {
     }
 }
 
+struct RescoreArgs {
+    const void *rows, *queries;          // as TopkArgs
+    const float *qscale, *rscale;        // i8: both, b1: qscale
+    const uint32_t *live;                // null = every row live
+    const int32_t *cand;                 // [nq][n_cand] ids; outside [0, n_rows) = no candidate
+    float *ws_s;                         // [nq][n_cand]
+    int *ws_i;
+    int n_rows, dpad, nq, n_cand, n_blocks;      // n_blocks = ceil(n_cand / 32)
+};
+
+// One wave per (query, block of 32 of its candidates): the block's rows are the MFMA's 32 rows, the query is query 0 of the
+// tile (the other 31 are zero operands), so lane l < 32 ends with acc[0] = its row's score — the accumulation chain of a search.
+template <class T>
+__global__ __launch_bounds__(NT) void index_rescore_kernel(RescoreArgs a) {
+    constexpr bool I8 = std::is_same_v<T, int8_t>, B1 = std::is_same_v<T, b1_t>;
+    using QE = typename QueryElem<T>::type;
+    const int lane = threadIdx.x & 63, col = lane & 31, h = lane >> 5;
+    const int w = (int)blockIdx.x * NWAVE + (int)(threadIdx.x >> 6);
+    if (w >= a.nq * a.n_blocks) return;                        // (the whole wave)
+    const int q = w / a.n_blocks, c = (w - q * a.n_blocks) * 32 + col;
+    const int id = c < a.n_cand ? a.cand[(size_t)q * a.n_cand + c] : -1;
+    bool rok = id >= 0 && id < a.n_rows;
+    if (rok && a.live) rok = (a.live[id >> 5] >> (id & 31)) & 1u;
+    float s = -INFINITY;
+    if (__any(rok)) {                                          // (wave-uniform)
+        const bool qok = col == 0;
+        const QE *qp = (const QE *)a.queries + (size_t)q * a.dpad;
+        const T *rp = row_ptr<T>(a.rows, (size_t)(rok ? id : 0), a.dpad);
+        if constexpr (B1) {
+            i32x16 dot = {};
+            ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, dot);
+            s = (float)dot[0] * a.qscale[q];
+        } else if constexpr (I8) {
+            const float rs = rok ? a.rscale[id] : 0.f;
+            i32x16 dot = {};
+            ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, dot);
+            s = ((float)dot[0] * a.qscale[q]) * rs;            // (the search's two multiplies)
+        } else {
+            f32x16 acc = {};
+            ScoreBlock<T>::run(qp, rp, qok, rok, a.dpad, h, acc);
+            s = acc[0];
+        }
+    }
+    if (h == 0 && c < a.n_cand) {
+        a.ws_s[(size_t)q * a.n_cand + c] = rok ? s : -INFINITY;
+        a.ws_i[(size_t)q * a.n_cand + c] = rok ? id : SENT_ID;
+    }
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void index_convert_kernel(const float *__restrict__ src, T *__restrict__ dst, int n, int dim, int dpad) {
     const size_t total = (size_t)n * dpad;
@@ -403,6 +532,25 @@ __global__ __launch_bounds__(256) void index_quantize_kernel(const float *__rest
 
 void launch_quantize(const float *src, void *codes, float *scales, int n, int dim, int dpad, hipStream_t s) {
     BERT_LAUNCH(index_quantize_kernel, dim3((n + 3) / 4), dim3(256), 0, s, src, (int8_t *)codes, scales, n, dim, dpad);
+}
+
+// f32 rows [n][dim] -> b1 rows [n][dpad / 32] words (the b1 form above).  One wave per row: a ballot of x > 0 is the 64 bits of
+// elements c0 .. c0 + 63, whose two words lanes 0 and 1 store.  dpad is a multiple of 128; elements at and beyond dim are 0.
+__global__ __launch_bounds__(256) void index_pack_b1_kernel(const float *__restrict__ src, uint32_t *__restrict__ dst, int n, int dim, int dpad) {
+    const int lane = threadIdx.x & 63;
+    const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= (size_t)n) return;                                // (the whole wave)
+    const float *x = src + r * dim;
+    uint32_t *out = dst + r * (size_t)(dpad >> 5);
+    for (int c0 = 0; c0 < dpad; c0 += 64) {
+        const float v = c0 + lane < dim ? x[c0 + lane] : 0.f;
+        const unsigned long long m = __ballot(v > 0.f);        // (an IEEE compare: false for -0, NaN, -inf)
+        if (lane < 2) out[(c0 >> 5) + lane] = (uint32_t)(m >> (32 * lane));
+    }
+}
+
+void launch_pack_b1(const float *src, void *dst, int n, int dim, int dpad, hipStream_t s) {
+    BERT_LAUNCH(index_pack_b1_kernel, dim3((n + 3) / 4), dim3(256), 0, s, src, (uint32_t *)dst, n, dim, dpad);
 }
 
 // Compaction: row i of dst (row_bytes, a multiple of 16) = row old_ids[i] of src, and the i8 scale with it (sscale null for
@@ -487,15 +635,16 @@ size_t Index::ws_entries_bound(int n_rows, int nq, int k) {
 Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
     if (!eng) { err = "no device engine"; return nullptr; }
     if (dim < 1 || dim > MAX_DIM) { err = "dim must be 1 .. 2048"; return nullptr; }
-    if (dtype < 0 || dtype > 2) { err = "dtype must be 0 (f32), 1 (f16) or 2 (i8)"; return nullptr; }
+    if (dtype < 0 || dtype > 3) { err = "dtype must be 0 (f32), 1 (f16), 2 (i8) or 3 (b1)"; return nullptr; }
     DeviceGuard g(eng->device());
     Index *ix = new Index;
     ix->eng_ = eng;
     ix->dim_ = dim;
     ix->dtype_ = dtype;
-    ix->es_ = index_elem_size(dtype);
     // the score kernel's k-step (a 16-byte load per lane)
     ix->dpad_ = index_dpad(dtype, dim);
+    ix->row_bytes_ = (size_t)index_row_bytes(dtype, ix->dpad_);
+    ix->qrow_bytes_ = dtype == 3 ? (size_t)ix->dpad_ : ix->row_bytes_;      // (b1: the queries are i8 codes)
     const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
     if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
@@ -508,6 +657,8 @@ Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
     (void)hipFuncSetAttribute((const void *)index_topk_kernel<half_t, TopkArgsMasked>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     (void)hipFuncSetAttribute((const void *)index_topk_kernel<float, TopkArgsMasked>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     (void)hipFuncSetAttribute((const void *)index_topk_kernel<int8_t, TopkArgsI8Masked>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<b1_t, TopkArgsB1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+    (void)hipFuncSetAttribute((const void *)index_topk_kernel<b1_t, TopkArgsB1Masked>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
     return ix;
 }
 
@@ -529,7 +680,7 @@ bool Index::grow(DevBuf &b, size_t bytes, std::string &err) {
 bool Index::grow_rows(int n_rows, std::string &err) {
     if (n_rows <= cap_) return true;
     const int cap = (int)std::min<long long>(INT_MAX, std::max<long long>({(long long)n_rows, (long long)cap_ * 3 / 2, 1024}));
-    const size_t row_bytes = (size_t)dpad_ * es_;
+    const size_t row_bytes = row_bytes_;
     void *p = nullptr;
     float *sc = nullptr;
     HIP_OK(hipEventSynchronize(busy_), err, false);
@@ -575,8 +726,12 @@ bool Index::reserve(int n_rows, int n_queries, int k, std::string &err) {
     const int rows = std::max(n_rows, n_);
     for (int kk = 1; kk <= k; ++kk)
         for (int t = 1; t <= (nqc + QT - 1) / QT; ++t) ent = std::max(ent, ws_entries_bound(rows, std::min(nqc, t * QT), kk));
-    return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err) && grow(qbuf_, (size_t)nqc * dpad_ * es_, err) &&
-           (dtype_ != 2 || grow(qscale_, (size_t)nqc * 4, err));
+    return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err) && grow_queries(nqc, err);
+}
+
+// the stored form of a chunk of nqc queries (i8, b1: codes and scales)
+bool Index::grow_queries(int nqc, std::string &err) {
+    return grow(qbuf_, (size_t)nqc * qrow_bytes_, err) && (dtype_ < 2 || grow(qscale_, (size_t)nqc * 4, err));
 }
 
 int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &err) {
@@ -586,9 +741,10 @@ int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &er
     DeviceGuard g(eng_->device());
     if (!grow_rows(n_ + n, err)) return -1;
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
-    char *dst = (char *)rows_ + (size_t)n_ * dpad_ * es_;
-    eng_->timed_launch(dtype_ == 2 ? "index_quantize_i8" : dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
-        if (dtype_ == 2) launch_quantize(d_rows, dst, rscale_ + n_, n, dim_, dpad_, s);
+    char *dst = (char *)rows_ + (size_t)n_ * row_bytes_;
+    eng_->timed_launch(dtype_ == 3 ? "index_pack_b1" : dtype_ == 2 ? "index_quantize_i8" : dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
+        if (dtype_ == 3) launch_pack_b1(d_rows, dst, n, dim_, dpad_, s);
+        else if (dtype_ == 2) launch_quantize(d_rows, dst, rscale_ + n_, n, dim_, dpad_, s);
         else if (dtype_ == 1) launch_convert<half_t>(d_rows, dst, n, dim_, dpad_, s);
         else launch_convert<float>(d_rows, dst, n, dim_, dpad_, s);
     });
@@ -628,13 +784,18 @@ int Index::add_host(int n, const float *rows, std::string &err) {
     return first;
 }
 
-void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow) {
-    const Plan p = plan(n_, nq, k);
-    eng_->timed_launch(dtype_ == 2 ? "index_quantize_i8" : dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
-        if (dtype_ == 2) launch_quantize(d_q, qbuf_.p, qscale_.as<float>(), nq, dim_, dpad_, s);
+// f32 queries -> qbuf_ (and qscale_) in the form the score block reads (b1: i8 codes padded to this dpad, and their scales)
+void Index::enqueue_queries(int nq, const float *d_q, hipStream_t s) {
+    eng_->timed_launch(dtype_ >= 2 ? "index_quantize_i8" : dtype_ == 1 ? "index_convert_f16" : "index_convert_f32", 0.0, s, [&] {
+        if (dtype_ >= 2) launch_quantize(d_q, qbuf_.p, qscale_.as<float>(), nq, dim_, dpad_, s);
         else if (dtype_ == 1) launch_convert<half_t>(d_q, qbuf_.p, nq, dim_, dpad_, s);
         else launch_convert<float>(d_q, qbuf_.p, nq, dim_, dpad_, s);
     });
+}
+
+void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow) {
+    const Plan p = plan(n_, nq, k);
+    enqueue_queries(nq, d_q, s);
     TopkArgs a;
     a.rows = rows_; a.queries = qbuf_.p; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
     a.n_rows = n_; a.dpad = dpad_; a.nq = nq; a.n_qtiles = p.nqt; a.n_slices = p.slices; a.slice_rows = p.slice_rows;
@@ -642,11 +803,15 @@ void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float
     TopkArgsI8 a8;
     static_cast<TopkArgs &>(a8) = a;
     a8.qscale = qscale_.as<float>(); a8.rscale = rscale_;
+    TopkArgsB1 a1;
+    static_cast<TopkArgs &>(a1) = a;
+    a1.qscale = qscale_.as<float>();
     const int grid = (a.n_items + 7) / 8 * 8;
     const double flops = 2.0 * nq * (double)n_ * dim_;
     if (!live_ && !d_allow) {
-        eng_->timed_launch(dtype_ == 2 ? "index_topk_i8" : dtype_ == 1 ? "index_topk_f16" : "index_topk_f32", flops, s, [&] {
-            if (dtype_ == 2) BERT_LAUNCH((index_topk_kernel<int8_t, TopkArgsI8>), dim3(grid), dim3(NT), p.lds, s, a8);
+        eng_->timed_launch(dtype_ == 3 ? "index_topk_b1" : dtype_ == 2 ? "index_topk_i8" : dtype_ == 1 ? "index_topk_f16" : "index_topk_f32", flops, s, [&] {
+            if (dtype_ == 3) BERT_LAUNCH((index_topk_kernel<b1_t, TopkArgsB1>), dim3(grid), dim3(NT), p.lds, s, a1);
+            else if (dtype_ == 2) BERT_LAUNCH((index_topk_kernel<int8_t, TopkArgsI8>), dim3(grid), dim3(NT), p.lds, s, a8);
             else if (dtype_ == 1) BERT_LAUNCH((index_topk_kernel<half_t, TopkArgs>), dim3(grid), dim3(NT), p.lds, s, a);
             else BERT_LAUNCH((index_topk_kernel<float, TopkArgs>), dim3(grid), dim3(NT), p.lds, s, a);
         });
@@ -658,8 +823,12 @@ void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float
         TopkArgsI8Masked am8;
         static_cast<TopkArgsI8 &>(am8) = a8;
         am8.live = live_; am8.allow = d_allow;
-        eng_->timed_launch(dtype_ == 2 ? "index_topk_i8_masked" : dtype_ == 1 ? "index_topk_f16_masked" : "index_topk_f32_masked", flops, s, [&] {
-            if (dtype_ == 2) BERT_LAUNCH((index_topk_kernel<int8_t, TopkArgsI8Masked>), dim3(grid), dim3(NT), p.lds, s, am8);
+        TopkArgsB1Masked am1;
+        static_cast<TopkArgsB1 &>(am1) = a1;
+        am1.live = live_; am1.allow = d_allow;
+        eng_->timed_launch(dtype_ == 3 ? "index_topk_b1_masked" : dtype_ == 2 ? "index_topk_i8_masked" : dtype_ == 1 ? "index_topk_f16_masked" : "index_topk_f32_masked", flops, s, [&] {
+            if (dtype_ == 3) BERT_LAUNCH((index_topk_kernel<b1_t, TopkArgsB1Masked>), dim3(grid), dim3(NT), p.lds, s, am1);
+            else if (dtype_ == 2) BERT_LAUNCH((index_topk_kernel<int8_t, TopkArgsI8Masked>), dim3(grid), dim3(NT), p.lds, s, am8);
             else if (dtype_ == 1) BERT_LAUNCH((index_topk_kernel<half_t, TopkArgsMasked>), dim3(grid), dim3(NT), p.lds, s, am);
             else BERT_LAUNCH((index_topk_kernel<float, TopkArgsMasked>), dim3(grid), dim3(NT), p.lds, s, am);
         });
@@ -679,9 +848,7 @@ int Index::search_device(int nq, const float *d_q, int k, int32_t *d_ids, float 
     const int nqc = std::min(nq, QCHUNK);
     // (the last, shorter chunk may be cut into more slices than a full one)
     const size_t ent = std::max(ws_entries_bound(n_, nqc, k), nq % QCHUNK ? ws_entries_bound(n_, nq % QCHUNK, k) : 0);
-    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(qbuf_, (size_t)nqc * dpad_ * es_, err) ||
-        (dtype_ == 2 && !grow(qscale_, (size_t)nqc * 4, err)))
-        return -1;
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow_queries(nqc, err)) return -1;
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
@@ -718,6 +885,120 @@ int Index::search_to_host(int nq, const float *q, bool q_on_device, int k, int32
         }
         if (!grow(out_ids_, (size_t)c * k * 4, err) || !grow(out_scores_, (size_t)c * k * 4, err)) return -1;
         if (search_device(c, dq, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow) != 0) { (void)hipStreamSynchronize(stream_); return -1; }
+        HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
+        HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
+        HIP_OK(hipStreamSynchronize(stream_), err, -1);
+    }
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// rescoring, two-stage search
+// ------------------------------------------------------------------------------------------------
+int Index::rescore_device(int nq, const float *d_q, int n_cand, const int32_t *d_cand, int k, int32_t *d_ids, float *d_scores,
+                          hipStream_t s, std::string &err) {
+    if (k < 1 || k > MAX_K) { err = "rescore: k must be 1 .. 256"; return -1; }
+    if (n_cand < 1 || n_cand > MAX_CAND) { err = "rescore: n_cand must be 1 .. 1024"; return -1; }
+    if (nq < 0 || (nq > 0 && (!d_q || !d_cand || !d_ids || !d_scores))) { err = "rescore: n_queries >= 0 and query / candidate / result pointers required"; return -1; }
+    if (nq == 0) return 0;
+    DeviceGuard g(eng_->device());
+    const int nqc = std::min(nq, QCHUNK);
+    const size_t ent = (size_t)nqc * n_cand;
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow_queries(nqc, err)) return -1;
+    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        enqueue_queries(c, d_q + (size_t)c0 * dim_, s);
+        RescoreArgs a;
+        a.rows = rows_; a.queries = qbuf_.p; a.qscale = qscale_.as<float>(); a.rscale = rscale_; a.live = live_;
+        a.cand = d_cand + (size_t)c0 * n_cand; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+        a.n_rows = n_; a.dpad = dpad_; a.nq = c; a.n_cand = n_cand; a.n_blocks = (n_cand + 31) / 32;
+        const int grid = (c * a.n_blocks + NWAVE - 1) / NWAVE;
+        const double flops = 2.0 * c * (double)n_cand * dim_;
+        eng_->timed_launch(dtype_ == 3 ? "index_rescore_b1" : dtype_ == 2 ? "index_rescore_i8" : dtype_ == 1 ? "index_rescore_f16" : "index_rescore_f32", flops, s, [&] {
+            if (dtype_ == 3) BERT_LAUNCH(index_rescore_kernel<b1_t>, dim3(grid), dim3(NT), 0, s, a);
+            else if (dtype_ == 2) BERT_LAUNCH(index_rescore_kernel<int8_t>, dim3(grid), dim3(NT), 0, s, a);
+            else if (dtype_ == 1) BERT_LAUNCH(index_rescore_kernel<half_t>, dim3(grid), dim3(NT), 0, s, a);
+            else BERT_LAUNCH(index_rescore_kernel<float>, dim3(grid), dim3(NT), 0, s, a);
+        });
+        MergeArgs m;
+        m.ws_s = a.ws_s; m.ws_i = a.ws_i; m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
+        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
+        const size_t lds = (size_t)m.L * 8 + 16;
+        eng_->timed_launch("topk_merge", 0.0, s, [&] { BERT_LAUNCH(topk_merge_kernel, dim3(c), dim3(NT), lds, s, m); });
+    }
+    HIP_OK(hipGetLastError(), err, -1);
+    HIP_OK(hipEventRecord(busy_, s), err, -1);
+    return 0;
+}
+
+int Index::rescore_to_host(int nq, const float *q, int n_cand, const int32_t *cand, int k, int32_t *ids, float *scores, std::string &err) {
+    if (k < 1 || k > MAX_K) { err = "rescore: k must be 1 .. 256"; return -1; }
+    if (n_cand < 1 || n_cand > MAX_CAND) { err = "rescore: n_cand must be 1 .. 1024"; return -1; }
+    if (nq < 0 || (nq > 0 && (!q || !cand || !ids || !scores))) { err = "rescore: n_queries >= 0 and query / candidate / result pointers required"; return -1; }
+    if (nq == 0) return 0;
+    DeviceGuard g(eng_->device());
+    std::vector<int32_t> hid((size_t)nq * k);
+    std::vector<float> hsc((size_t)nq * k);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        if (!grow(stage_, (size_t)c * dim_ * 4, err) || !grow(cand_in_, (size_t)c * n_cand * 4, err) ||
+            !grow(out_ids_, (size_t)c * k * 4, err) || !grow(out_scores_, (size_t)c * k * 4, err))
+            return -1;
+        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -1);
+        HIP_OK(hipMemcpyAsync(stage_.p, q + (size_t)c0 * dim_, (size_t)c * dim_ * 4, hipMemcpyHostToDevice, stream_), err, -1);
+        HIP_OK(hipMemcpyAsync(cand_in_.p, cand + (size_t)c0 * n_cand, (size_t)c * n_cand * 4, hipMemcpyHostToDevice, stream_), err, -1);
+        if (rescore_device(c, stage_.as<float>(), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err) != 0) {
+            (void)hipStreamSynchronize(stream_);
+            return -1;
+        }
+        HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
+        HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
+        HIP_OK(hipStreamSynchronize(stream_), err, -1);
+    }
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+int Index::search_rescored_device(Index &coarse, int nq, const float *d_q, int n_cand, int k, int32_t *d_ids, float *d_scores,
+                                  hipStream_t s, std::string &err) {
+    if (n_cand < 1 || n_cand > MAX_K || k < 1 || k > n_cand) { err = "search_rescored: 1 <= k <= n_cand <= 256 required"; return -1; }
+    if (nq < 0 || (nq > 0 && (!d_q || !d_ids || !d_scores))) { err = "search_rescored: n_queries >= 0 and query / result pointers required"; return -1; }
+    if (nq == 0) return 0;
+    DeviceGuard g(eng_->device());
+    const int nqc = std::min(nq, QCHUNK);
+    if (!grow(cand_i_, (size_t)nqc * n_cand * 4, err) || !grow(cand_s_, (size_t)nqc * n_cand * 4, err)) return -1;
+    // (the candidate lists are this index's: the coarse search that fills them waits for whatever still reads them; after
+    // that the two steps of a chunk, and the chunks, follow each other on s)
+    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        const float *dq = d_q + (size_t)c0 * dim_;
+        if (coarse.search_device(c, dq, n_cand, cand_i_.as<int32_t>(), cand_s_.as<float>(), s, err) != 0) return -1;
+        if (rescore_device(c, dq, n_cand, cand_i_.as<int32_t>(), k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s, err) != 0) return -1;
+    }
+    return 0;
+}
+
+int Index::search_rescored_to_host(Index &coarse, int nq, const float *q, int n_cand, int k, int32_t *ids, float *scores, std::string &err) {
+    if (n_cand < 1 || n_cand > MAX_K || k < 1 || k > n_cand) { err = "search_rescored: 1 <= k <= n_cand <= 256 required"; return -1; }
+    if (nq < 0 || (nq > 0 && (!q || !ids || !scores))) { err = "search_rescored: n_queries >= 0 and query / result pointers required"; return -1; }
+    if (nq == 0) return 0;
+    DeviceGuard g(eng_->device());
+    std::vector<int32_t> hid((size_t)nq * k);
+    std::vector<float> hsc((size_t)nq * k);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        if (!grow(stage_, (size_t)c * dim_ * 4, err) || !grow(out_ids_, (size_t)c * k * 4, err) || !grow(out_scores_, (size_t)c * k * 4, err)) return -1;
+        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -1);
+        HIP_OK(hipMemcpyAsync(stage_.p, q + (size_t)c0 * dim_, (size_t)c * dim_ * 4, hipMemcpyHostToDevice, stream_), err, -1);
+        if (search_rescored_device(coarse, c, stage_.as<float>(), n_cand, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err) != 0) {
+            (void)hipStreamSynchronize(stream_);
+            return -1;
+        }
         HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
         HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
         HIP_OK(hipStreamSynchronize(stream_), err, -1);
@@ -819,7 +1100,7 @@ int Index::compact(int32_t *old_ids, std::string &err) {
     int j = 0;
     for (int r = 0; r < n_; ++r)
         if (live_h_[(size_t)r >> 5] >> (r & 31) & 1u) map[(size_t)j++] = r;
-    const size_t row_bytes = (size_t)dpad_ * es_;
+    const size_t row_bytes = row_bytes_;
     void *p = nullptr;
     float *sc = nullptr;
     int32_t *d_map = nullptr;
@@ -895,7 +1176,7 @@ bool Index::save(const char *path, std::string &err) {
     if (!f) { err = "cannot write '" + tmp + "'"; return false; }
     std::vector<char> buf;
     // (the live words come from the mirror: its bits at and beyond size are zero)
-    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && device_to_file(f, rows_, (size_t)n_ * dpad_ * es_, buf, err) &&
+    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && device_to_file(f, rows_, (size_t)n_ * row_bytes_, buf, err) &&
               (dtype_ != 2 || device_to_file(f, rscale_, (size_t)n_ * 4, buf, err)) &&
               (!live_ || fwrite(live_h_.data(), 4, live_words(n_), f) == live_words(n_));
     ok = (fclose(f) == 0) && ok;
@@ -913,7 +1194,7 @@ bool Index::load_rows(FILE *f, const IndexFileHeader &h, std::string &err) {
     const int n = (int)h.n_rows;
     if (!grow_rows(n, err)) return false;
     std::vector<char> buf;
-    if (!file_to_device(f, rows_, (size_t)n * dpad_ * es_, buf, err)) return false;
+    if (!file_to_device(f, rows_, (size_t)n * row_bytes_, buf, err)) return false;
     if (dtype_ == 2 && !file_to_device(f, rscale_, (size_t)n * 4, buf, err)) return false;
     n_ = n;
     if (!h.has_live) return true;

@@ -3,8 +3,10 @@
 // then each line read from stdin is a query whose k closest texts are printed in the reference's format.  'q' or the end
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
-//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8] [-t THREADS] [--save PATH] [--load PATH]
-//   (--f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; the default stores the rows as f16;
+//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [-t THREADS] [--save PATH] [--load PATH]
+//   (--f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; --b1: one sign bit per element; the
+//   default stores the rows as f16; --rescore N: an int8 index of the same texts is kept beside the index, which only picks N
+//   candidates per query, and the answer is the int8 index's best k of them (bert_hip_index_search_rescored; k <= N <= 256);
 //   --save: the index goes to PATH (bert_hip_index_save) once it is built; --load: the index comes from PATH instead of being
 //   embedded — TEXTS is still read, for printing, and must have as many lines as the index has rows)
 #include <cstdio>
@@ -20,7 +22,7 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
 }
 
 std::string chomp(std::string s) {
@@ -31,7 +33,7 @@ std::string chomp(std::string s) {
 
 int main(int argc, char **argv) {
     const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr;
-    int k = 3, n_threads = 6, dtype = 1;
+    int k = 3, n_threads = 6, dtype = 1, n_cand = 0;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
         if ((!strcmp(argv[i], "-m") || !strcmp(argv[i], "--model")) && has_value) model = argv[++i];
@@ -42,10 +44,14 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--load") && has_value) load = argv[++i];
         else if (!strcmp(argv[i], "--f32")) dtype = 0;
         else if (!strcmp(argv[i], "--i8")) dtype = 2;
+        else if (!strcmp(argv[i], "--b1")) dtype = 3;
+        else if (!strcmp(argv[i], "--rescore") && has_value) n_cand = atoi(argv[++i]);
         else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
     }
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
+    const bool two_stage = n_cand != 0;
+    if (two_stage && (n_cand < k || n_cand > 256)) { fprintf(stderr, "search: --rescore must be -k .. 256\n"); return 2; }
 
     bert_ctx *ctx = bert_load_from_file(model);
     if (!ctx) {
@@ -85,6 +91,16 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    // the finer index of a two-stage search: the same texts as int8 rows
+    bert_hip_index *fine = nullptr;
+    if (two_stage) {
+        fine = bert_hip_index_create(ctx, 0, 2);
+        if (!fine || bert_hip_index_add_texts(fine, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+            fprintf(stderr, "search: could not build the int8 index to rescore with\n");
+            bert_free(ctx);
+            return 1;
+        }
+    }
     if (save && bert_hip_index_save(ix, save) != 0) {
         fprintf(stderr, "search: could not save the index to '%s'\n", save);
         bert_free(ctx);
@@ -94,6 +110,7 @@ int main(int argc, char **argv) {
 
     std::vector<int32_t> ids((size_t)k);
     std::vector<float> scores((size_t)k);
+    std::vector<float> emb((size_t)bert_n_embd(ctx));
     for (;;) {
         printf("Enter a text to find similar texts (enter 'q' to quit): ");
         fflush(stdout);
@@ -102,7 +119,15 @@ int main(int argc, char **argv) {
         q = chomp(q);
         if (q == "q") break;
         const char *qp = q.c_str();
-        if (bert_hip_index_search_texts(ix, n_threads, 1, &qp, k, ids.data(), scores.data()) != 0) {
+        int32_t r;
+        if (two_stage) {
+            float *ep = emb.data();
+            r = bert_hip_encode_batch(ctx, n_threads, 1, &qp, &ep) == 1
+                    ? bert_hip_index_search_rescored(ix, fine, 1, emb.data(), n_cand, k, ids.data(), scores.data()) : -1;
+        } else {
+            r = bert_hip_index_search_texts(ix, n_threads, 1, &qp, k, ids.data(), scores.data());
+        }
+        if (r != 0) {
             fprintf(stderr, "search: the search failed\n");
             bert_free(ctx);
             return 1;

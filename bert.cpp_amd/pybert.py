@@ -29,6 +29,7 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_index_add_device", "bert_hip_index_add_texts", "bert_hip_index_search", "bert_hip_index_search_device",
     "bert_hip_index_search_texts", "bert_hip_index_remove", "bert_hip_index_n_live", "bert_hip_index_search_filtered",
     "bert_hip_index_search_filtered_device", "bert_hip_index_compact", "bert_hip_index_save", "bert_hip_index_load",
+    "bert_hip_index_rescore", "bert_hip_index_rescore_device", "bert_hip_index_search_rescored", "bert_hip_index_search_rescored_device",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -108,6 +109,11 @@ def _declare_product_abi(L):
     L.bert_hip_index_compact.restype = i32; L.bert_hip_index_compact.argtypes = [vp, i32p]
     L.bert_hip_index_save.restype = i32; L.bert_hip_index_save.argtypes = [vp, C.c_char_p]
     L.bert_hip_index_load.restype = vp; L.bert_hip_index_load.argtypes = [vp, C.c_char_p]
+    L.bert_hip_index_rescore.restype = i32; L.bert_hip_index_rescore.argtypes = [vp, i32, f32p, i32, i32p, i32, i32p, f32p]
+    L.bert_hip_index_rescore_device.restype = i32; L.bert_hip_index_rescore_device.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_index_search_rescored.restype = i32; L.bert_hip_index_search_rescored.argtypes = [vp, vp, i32, f32p, i32, i32, i32p, f32p]
+    L.bert_hip_index_search_rescored_device.restype = i32
+    L.bert_hip_index_search_rescored_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
 
 
 def lib() -> C.CDLL:
@@ -498,7 +504,8 @@ class BertModel:
 
     def index(self, dim: Optional[int] = None, dtype: str = "f16") -> "BertIndex":
         """An embedding index on the context's first device (bert_hip_index_create): dim None = n_embd, dtype "f16" | "f32" |
-        "i8" (one int8 code per element and one f32 scale per row)."""
+        "i8" (one int8 code per element and one f32 scale per row) | "b1" (one sign bit per element, searched with int8
+        queries: the coarse stage of BertIndex.search_rescored)."""
         return BertIndex(self, dim, dtype)
 
     def load_index(self, path: str) -> "BertIndex":
@@ -524,8 +531,8 @@ class BertIndex:
     data_ptr()) and a stream handle, and return at once."""
 
     def __init__(self, model: BertModel, dim: Optional[int] = None, dtype: str = "f16", _load: Optional[str] = None):
-        if dtype not in ("f16", "f32", "i8"):
-            raise ValueError("dtype must be 'f16', 'f32' or 'i8'")
+        if dtype not in ("f16", "f32", "i8", "b1"):
+            raise ValueError("dtype must be 'f16', 'f32', 'i8' or 'b1'")
         self.model, self.lib = model, model.lib
         if _load is not None:
             # dim and dtype come from the file's header (include/bert_hip.h: u32 dtype at byte 12, u32 dim at 16)
@@ -534,9 +541,9 @@ class BertIndex:
                 raise RuntimeError("bert_hip_index_load failed (see stderr)")
             with open(_load, "rb") as f:
                 head = np.frombuffer(f.read(24), dtype="<u4")
-            self.dtype, self.dim = ("f32", "f16", "i8")[int(head[3])], int(head[4])
+            self.dtype, self.dim = ("f32", "f16", "i8", "b1")[int(head[3])], int(head[4])
             return
-        code = {"f16": 1, "i8": 2}.get(dtype, 0)
+        code = {"f16": 1, "i8": 2, "b1": 3}.get(dtype, 0)
         self.ix = self.lib.bert_hip_index_create(model.ctx, 0 if dim is None else int(dim), code)
         if not self.ix:
             raise RuntimeError("bert_hip_index_create failed (see stderr)")
@@ -611,6 +618,41 @@ class BertIndex:
         r = self.lib.bert_hip_index_search_filtered_device(self.ix, n_queries, d_queries_ptr, k, d_allow_ptr, n_words, d_ids_ptr, d_scores_ptr, stream)
         if r != 0:
             raise RuntimeError(f"bert_hip_index_search_filtered_device failed: {r}")
+
+    def rescore(self, queries, cand_ids, k: int = 10):
+        """bert_hip_index_rescore: the best k of each query's own candidates, cand_ids [n_queries, n_cand] int32 (-1 and removed
+        rows are skipped; ids outside [-1, len(index)) are an error), scored by this index's rule."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        cand = np.ascontiguousarray(cand_ids, dtype=np.int32).reshape(q.shape[0], -1)
+        ids = np.empty((q.shape[0], k), dtype=np.int32)
+        scores = np.empty((q.shape[0], k), dtype=np.float32)
+        r = self.lib.bert_hip_index_rescore(self.ix, q.shape[0], _f32p(q), cand.shape[1], _i32p(cand), k, _i32p(ids), _f32p(scores))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_rescore failed: {r}")
+        return ids, scores
+
+    def rescore_device(self, n_queries: int, d_queries_ptr: int, n_cand: int, d_cand_ptr: int, k: int, d_ids_ptr: int,
+                       d_scores_ptr: int, stream: int = 0) -> None:
+        r = self.lib.bert_hip_index_rescore_device(self.ix, n_queries, d_queries_ptr, n_cand, d_cand_ptr, k, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_rescore_device failed: {r}")
+
+    def search_rescored(self, fine: "BertIndex", queries, k: int = 10, n_cand: int = 100):
+        """Two-stage search (bert_hip_index_search_rescored): this index (a "b1" one, say) picks n_cand candidates per query,
+        `fine` — an index of the same rows — rescores them and returns its best k."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), dtype=np.int32)
+        scores = np.empty((q.shape[0], k), dtype=np.float32)
+        r = self.lib.bert_hip_index_search_rescored(self.ix, fine.ix, q.shape[0], _f32p(q), n_cand, k, _i32p(ids), _f32p(scores))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search_rescored failed: {r}")
+        return ids, scores
+
+    def search_rescored_device(self, fine: "BertIndex", n_queries: int, d_queries_ptr: int, n_cand: int, k: int, d_ids_ptr: int,
+                               d_scores_ptr: int, stream: int = 0) -> None:
+        r = self.lib.bert_hip_index_search_rescored_device(self.ix, fine.ix, n_queries, d_queries_ptr, n_cand, k, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search_rescored_device failed: {r}")
 
     @property
     def n_live(self) -> int:

@@ -160,9 +160,10 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  * entry point of a context, the index functions are not re-entrant on one context.
  *   create   dim: 0 = bert_n_embd(ctx), else 1 .. 2048.  dtype: 0 = f32 rows, 1 = f16 rows (rounded to nearest even; the
  *            queries are rounded to f16 the same way), 2 = int8 rows with one f32 scale per row (the queries quantized the
- *            same way, on the device; below).  Memory per row: 4 * ceil(dim / 8) * 8 bytes (f32), 2 * ceil(dim / 16) * 16
- *            (f16), dpad + 4 with dpad = ceil(dim / 32) * 32 (int8).  NULL + a message on stderr on error (tokenizer-only
- *            context, no device, bad arguments).
+ *            same way, on the device; below), 3 = "b1": one sign bit per element and no scale (the queries quantized to int8;
+ *            below).  Memory per row: 4 * ceil(dim / 8) * 8 bytes (f32), 2 * ceil(dim / 16) * 16
+ *            (f16), dpad + 4 with dpad = ceil(dim / 32) * 32 (int8), dpad / 8 with dpad = ceil(dim / 128) * 128 (b1: 48 bytes
+ *            at dim 384).  NULL + a message on stderr on error (tokenizer-only context, no device, bad arguments).
  *   add      appends rows [n][dim] (f32); they get ids size, size + 1, ...; returns the first new id, negative on error
  *            (index unchanged).  add_device: the rows in device memory of the index's device, enqueued on `stream`.
  *            add_texts: encodes the texts (dim must equal n_embd) on the context's devices as bert_hip_encode_batch does; on a
@@ -185,6 +186,15 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  *     dot = sum_i qcode_i * rcode_i is an exact int32 converted with round-to-nearest-even.  So a row holding a NaN OR an inf
  *     scores NaN and is never returned (an f32 index can return a row holding an inf); a query holding one returns only
  *     id -1 / -INFINITY slots; a zero query scores 0 against every finite row.  The same determinism as below holds.
+ *   - 1-bit (dtype 3, "b1"; asymmetric: bit rows, int8 queries): element i of a row is bit i & 31 of little-endian u32 word
+ *     i >> 5, set iff x_i > 0 as an IEEE f32 comparison — so -0, NaN and -inf give 0 and +inf gives 1.  Unlike int8, non-finite
+ *     elements of a ROW are not detected: such a row is stored and returned like any other.  Rows are padded with zero bits
+ *     to dpad = ceil(dim / 128) * 128 elements (whole 16-byte pieces); there is no row scale.  Queries are quantized exactly as
+ *     for int8 (scale = amax / 127, code_i = clamp(rint(x_i / scale), -127, 127), a NaN scale and zero codes for a non-finite
+ *     element), the codes zero-padded to this dpad.  score = (float)dot * qscale, where dot = sum_i qcode_i * (bit_i ? +1 : -1)
+ *     is an exact int32 (the padding meets zero codes).  A query holding a NaN or an inf returns only id -1 / -INFINITY slots;
+ *     a zero query scores +0 against every row, so the smallest ids win.  Equal scores are common with this form: the order
+ *     rule below decides every one.  The same determinism as below holds.  Meant as the coarse stage of search_rescored.
  *   - order: larger score first; equal scores (==, so +0 equals -0) smaller id first.  Rows with a NaN score are never
  *     returned.  Slots beyond the rows that can be returned are id -1, score -INFINITY.  An empty index is valid.
  *   - 1 <= k <= 256, anything else is an error; n_queries == 0 is a successful no-op; large n_queries run in internal chunks.
@@ -214,12 +224,29 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  *            tokenizer-only context, an unreadable, truncated, over-long or inconsistent file; the file is checked against
  *            its header before anything is allocated.  The loaded index belongs to ctx like a created one; its dim need
  *            not be bert_n_embd(ctx).
+ * Rescoring and two-stage search:
+ *   rescore  scores each query against ITS OWN candidates and returns the best k of them: cand_ids[n_queries][n_cand] are row
+ *            ids; works on any dtype, with the index's own score rule — for distinct ids, query q's result has the ids and
+ *            the score bits of bert_hip_index_search_filtered called with that one query and an allow-list of exactly its
+ *            candidates.  -1 entries and removed rows are skipped.  An id < -1 or >= size is an error (-2, nothing
+ *            written) in the host call; the device call treats it as -1.  An id that appears more than once in a query's
+ *            list counts as that many candidates (it can be returned more than once); lists that come from a search are
+ *            distinct.  1 <= k <= 256, 1 <= n_cand <= 1024, k may exceed n_cand: slots beyond the candidates that remain are
+ *            id -1 / -INFINITY.  rescore_device: queries, candidates and results in device memory, asynchronous on `stream`
+ *            under the one-event rule.  The workspace ([n_queries][n_cand] entries, queries in internal chunks) is not part
+ *            of reserve and grows on demand, which allocates: call once at the largest shape before a stream capture.
+ *   search_rescored   a search of `coarse` with k' = n_cand, then rescore on `fine` with the same f32 queries; the candidates
+ *            stay on the device between the two.  Both indexes must belong to one context and agree in dim and size (they
+ *            are meant to hold the same rows in the same order, removals included: a candidate that `fine` has removed is
+ *            skipped), and 1 <= k <= n_cand <= 256; otherwise -2.  The result equals the two public calls chained by hand.
+ *            search_rescored_device: asynchronous on `stream`; both indexes' events are honoured.  The same advice on
+ *            allocation as for rescore holds (the coarse search's workspace is covered by coarse's reserve with k = n_cand).
  * Errors of the functions that take an index: -1 no index, -2 bad arguments (after a line on stderr), -3 an error of the
  * index or the device (its message on stderr), -4 an exception.  Outputs are untouched on error.
  * File format (little-endian).  Header, 64 bytes: magic "BHIPIDX1" (8 bytes), u32 version = 1, u32 dtype (0 f32, 1 f16,
- * 2 i8), u32 dim, u32 dpad (elements per stored row: dim rounded up to 8 (f32), 16 (f16), 32 (i8)), u32 n_rows (= size,
- * removed rows included), u32 has_live (0 | 1), 32 zero bytes.  Then n_rows * dpad * elem_size bytes of rows exactly as
- * stored (zero-padded to dpad; elem_size 4, 2, 1); for i8, n_rows f32 row scales; if has_live, ceil(n_rows / 32) u32 words,
+ * 2 i8, 3 b1), u32 dim, u32 dpad (elements per stored row: dim rounded up to 8 (f32), 16 (f16), 32 (i8), 128 (b1: bits)), u32
+ * n_rows (= size, removed rows included), u32 has_live (0 | 1), 32 zero bytes.  Then n_rows * dpad * elem_size bytes of rows
+ * exactly as stored (zero-padded to dpad; elem_size 4, 2, 1; b1: n_rows * dpad / 8 bytes); for i8, n_rows f32 row scales; if has_live, ceil(n_rows / 32) u32 words,
  * bit b of word w set = row 32 w + b is live, the bits at and beyond n_rows zero.  The file is exactly that long.        */
 struct bert_hip_index;
 BERT_API struct bert_hip_index *bert_hip_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype);
@@ -241,6 +268,15 @@ BERT_API int32_t bert_hip_index_search_filtered(struct bert_hip_index *ix, int32
                                                 const uint32_t *allow, int32_t n_words, int32_t *ids, float *scores);
 BERT_API int32_t bert_hip_index_search_filtered_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries,
                                                        int32_t k, const uint32_t *d_allow, int32_t n_words, int32_t *d_ids,
+                                                       float *d_scores, void *stream);
+BERT_API int32_t bert_hip_index_rescore(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t n_cand,
+                                        const int32_t *cand_ids, int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_index_rescore_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t n_cand,
+                                               const int32_t *d_cand_ids, int32_t k, int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_index_search_rescored(struct bert_hip_index *coarse, struct bert_hip_index *fine, int32_t n_queries,
+                                                const float *queries, int32_t n_cand, int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_index_search_rescored_device(struct bert_hip_index *coarse, struct bert_hip_index *fine, int32_t n_queries,
+                                                       const float *d_queries, int32_t n_cand, int32_t k, int32_t *d_ids,
                                                        float *d_scores, void *stream);
 BERT_API int32_t bert_hip_index_compact(struct bert_hip_index *ix, int32_t *old_ids);
 BERT_API int32_t bert_hip_index_save(struct bert_hip_index *ix, const char *path);

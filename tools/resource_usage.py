@@ -19,7 +19,7 @@ for line in err.splitlines():
         continue
     k, v = m.groups()
     if k == "Function Name":
-        cur = {"name": subprocess.run(["c++filt", v], capture_output=True, text=True).stdout.strip().split("(")[0]}
+        cur = {"name": subprocess.run(["c++filt", v], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "").split("(")[0]}
     else:
         cur[k.split(" [")[0]] = v
         if k.startswith("LDS"):

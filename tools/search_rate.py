@@ -4,18 +4,25 @@ bert_hip_index_add.  GPU only: there is no CPU fallback.
 
     python tools/search_rate.py [--rows 1000000] [--iters 10] [--out profiles/search_rate.txt]
                                 [--sections search,filter,texts] [--dims 384,768] [--dtypes f16,f32,i8] [--no-yardstick]
+    python tools/search_rate.py --sections rescore --out profiles/search_b1_rate.txt
 
 Per line: ms per call (device events, after warm-up), queries/s, the algorithmic bytes (the rows once, the queries, the
 results) and FLOPs (2 Q N dim), the share of the binding roofline (HBM 6.3 TB/s achievable; matrix cores 2.5 PF/s f16,
 155 TF/s f32, 5 PF/s i8) and its name, torch's ms, and whether the two agree (per query: the same ids up to ties within
 tolerance).  i8 rows count dpad + 4 bytes (codes and scale); torch's yardstick for them is the same quantization and score
-restated in torch (f32 mat-mul of the codes, exact at these dims: every partial sum is an integer below 2^24).
+restated in torch (f32 mat-mul of the codes, exact at these dims: every partial sum is an integer below 2^24).  b1 rows
+(--dtypes ...,b1) count dpad / 8 bytes with dpad = dim rounded up to 128; their yardstick is the int8 query codes against a
++-1 matrix of the rows' sign bits, times the query scale; their matrix-core line is the i8 one.
 
 Section "filter" (bert_hip_index_search_filtered_device; f16 and i8 rows, dim 384, k = 10, Q = 1 and 4096): the unfiltered
 call, then allow-lists of density 1.0, 0.1 and 0.01, with the allowed rows drawn at random or in contiguous runs of 4096 rows
 spread evenly over the index.  Per line: ms per call (median, and the smallest and largest of the iterations: the run-to-run
 spread), the ratio to the unfiltered line, and the rows that qualify.  --no-yardstick leaves torch's column out (for a quick
 comparison of two builds).
+
+Section "rescore" (not part of the default; 10^6 rows, dims 384 and 768, Q = 1 and 4096, k = 10): the b1 search, the two-stage
+search b1(100) -> i8 (bert_hip_index_search_rescored_device) and the plain i8 search, from the same run on the same box, each as
+median (min .. max), and the share of the two-stage answers' ids that the plain i8 search also returns.
 """
 import argparse
 import os
@@ -29,7 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM = 6.3e12
-PEAK = {"f16": 2.5e15, "f32": 155e12, "i8": 5.0e15}
+PEAK = {"f16": 2.5e15, "f32": 155e12, "i8": 5.0e15, "b1": 5.0e15}
 
 
 def agree(ids, scores, t_ids, t_vals, k, tol):
@@ -102,6 +109,41 @@ def filter_section(a, m, N, out, timed, torch, dev, sp):
         ix.close()
 
 
+def rescore_section(a, m, N, out, timed, torch, dev, sp):
+    """the b1 search, b1(100) -> i8 two-stage and the plain i8 search side by side"""
+    k, n_cand = 10, 100
+    out(f"# b1 search, b1({n_cand}) -> i8 two-stage search and i8 search, N = {N} rows, k = {k}; ms = median (min .. max) of {a.iters}")
+    out("#  dim     Q  call                    |      ms (min .. max)        queries/s   ids shared with i8")
+    for dim in (384, 768):
+        g = torch.Generator(device=dev).manual_seed(dim)
+        C = torch.randn(N, dim, device=dev, generator=g)
+        C /= C.norm(dim=1, keepdim=True)
+        Qall = torch.randn(4096, dim, device=dev, generator=g)
+        Qall /= Qall.norm(dim=1, keepdim=True)
+        b1, i8 = m.index(dim=dim, dtype="b1"), m.index(dim=dim, dtype="i8")
+        for ix, kk in ((b1, n_cand), (i8, k)):
+            ix.reserve(N, 4096, kk)
+            ix.add_device(N, C.data_ptr(), sp)
+        for Q in (1, 4096):
+            q = Qall[:Q].contiguous()
+            ids = {name: torch.empty(Q, k, dtype=torch.int32, device=dev) for name in ("b1", "two-stage", "i8")}
+            sc = torch.empty(Q, k, dtype=torch.float32, device=dev)
+            calls = {"b1": lambda: b1.search_device(Q, q.data_ptr(), k, ids["b1"].data_ptr(), sc.data_ptr(), sp),
+                     "two-stage": lambda: b1.search_rescored_device(i8, Q, q.data_ptr(), n_cand, k, ids["two-stage"].data_ptr(), sc.data_ptr(), sp),
+                     "i8": lambda: i8.search_device(Q, q.data_ptr(), k, ids["i8"].data_ptr(), sc.data_ptr(), sp)}
+            times = {name: timed(f) for name, f in calls.items()}
+            want = ids["i8"].cpu().numpy()
+            for name, label in (("b1", "b1 search"), ("two-stage", f"b1({n_cand}) -> i8"), ("i8", "i8 search")):
+                t, lo, hi = times[name]
+                got = ids[name].cpu().numpy()
+                shared = np.mean([len(set(x.tolist()) & set(y.tolist())) / k for x, y in zip(got, want)])
+                out(f"{dim:6d} {Q:5d}  {label:22s} | {t:8.3f} ({lo:7.3f} .. {hi:7.3f}) {Q / (t * 1e-3):11.0f}   {shared:.3f}")
+        b1.close()
+        i8.close()
+        del C, Qall
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -167,6 +209,8 @@ def main():
             Ct = C.half() if dtype == "f16" else C
             if dtype == "i8":
                 Ct, Cs = quantize(C)
+            if dtype == "b1":
+                Ct = torch.where(C > 0, 1.0, -1.0)
             for Q in (1, 16, 256, 4096):
                 q = Qall[:Q].contiguous()
                 for k in (10, 100):
@@ -178,13 +222,15 @@ def main():
 
                     def yard():
                         qt = q.half() if dtype == "f16" else q
-                        if dtype == "i8":
+                        if dtype in ("i8", "b1"):
                             qt, qs = quantize(q)
                         res = []
                         for c0 in range(0, Q, 256):          # (a [256, N] f32 score block at a time: 1 GB)
                             s = (qt[c0:c0 + 256] @ Ct.T).float()
                             if dtype == "i8":
                                 s = (s * qs[c0:c0 + 256, None]) * Cs[None, :]
+                            if dtype == "b1":
+                                s = s * qs[c0:c0 + 256, None]
                             res.append(torch.topk(s, k, dim=1))
                         return torch.cat([r.values for r in res]), torch.cat([r.indices for r in res])
 
@@ -196,10 +242,10 @@ def main():
                         torch.cuda.synchronize()
                         nq = min(Q, 64)
                         ok = agree(ids[:nq].cpu().numpy(), sc[:nq].cpu().numpy(), ti[:nq].cpu().numpy(), tv[:nq].cpu().numpy(), k, 1e-3)
-                    es = {"f16": 2, "f32": 4, "i8": 1}[dtype]
-                    step = {"f16": 16, "f32": 8, "i8": 32}[dtype]
+                    es = {"f16": 2, "f32": 4, "i8": 1, "b1": 0.125}[dtype]
+                    step = {"f16": 16, "f32": 8, "i8": 32, "b1": 128}[dtype]
                     dpad = (dim + step - 1) // step * step
-                    nbytes = N * (dpad * es + (4 if dtype == "i8" else 0)) + Q * dim * 4 + Q * k * 8
+                    nbytes = N * (int(dpad * es) + (4 if dtype == "i8" else 0)) + Q * dim * 4 + Q * k * 8
                     flops = 2.0 * Q * N * dim
                     tb, tf = nbytes / HBM, flops / PEAK[dtype]
                     bound, share = ("HBM", tb / (t * 1e-3)) if tb >= tf else ("MFMA", tf / (t * 1e-3))
@@ -212,6 +258,9 @@ def main():
 
     if "filter" in sections:
         filter_section(a, m, N, out, timed, torch, dev, sp)
+
+    if "rescore" in sections:
+        rescore_section(a, m, N, out, timed, torch, dev, sp)
 
     # strings in, index rows out: add_texts against encode_batch + add
     if "texts" in sections:
