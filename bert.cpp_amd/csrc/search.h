@@ -1,5 +1,5 @@
-// search.h — an embedding index in HBM and its exact top-k inner-product search (search.hip; C ABI: bert_hip_index_* in
-// include/bert_hip.h).  Rows live on the device of the engine the index was made from, as f32, as f16 (RNE), as i8 codes with a
+// search.h — an embedding index in HBM and its exact top-k inner-product search (the class: index.cpp; its kernels: search.hip
+// behind search_kernels.h; C ABI: bert_hip_index_* in include/bert_hip.h).  Rows live on the device of the engine the index was made from, as f32, as f16 (RNE), as i8 codes with a
 // scale or as one sign bit per element (b1), each row zero-padded to the k-step of the score kernel's MFMA.  A search is a GEMM (queries x rows x dim) whose epilogue selects
 // instead of storing: index_topk_kernel keeps a top-k per (query, slice of rows) in LDS, topk_merge_kernel merges the
 // slices' lists per query.  The score matrix never reaches HBM.
@@ -18,6 +18,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -85,13 +86,13 @@ public:
 
 private:
     Index() = default;
-    struct Plan { int nqt, slices, slice_rows, L; size_t lds; };
-    static Plan plan(int n_rows, int nq, int k);
-    static size_t ws_entries_bound(int n_rows, int nq, int k);
     bool grow_rows(int n_rows, std::string &err);
     bool grow(DevBuf &b, size_t bytes, std::string &err);
     void enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow);
     void enqueue_queries(int nq, const float *d_q, hipStream_t s);
+    void enqueue_merge(int nq, int n_cand, int k, int32_t *d_ids, float *d_scores, hipStream_t s);
+    int host_route(int nq, const float *q, bool q_on_device, bool wait, int k, int32_t *ids, float *scores, std::string &err,
+                   const std::function<int(int, int, const float *, int32_t *, float *)> &device_form);
     bool grow_queries(int nqc, std::string &err);
     bool make_live(std::string &err);
     bool upload_live(size_t w0, size_t w1, std::string &err);

@@ -1,0 +1,61 @@
+// search_kernels.h — the device code of the embedding index (search.hip) as its host side (index.cpp) sees it: the argument
+// blocks, the tile constants a search is planned with, and one launcher per kernel.  dtype is the index's: 0 f32, 1 f16, 2 i8,
+// 3 b1 (search.hip states the forms).  A launcher only enqueues: the caller reads hipGetLastError.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+namespace bert_hip {
+
+constexpr int QT = 32;                  // queries per workgroup tile: the M side of one 32 x 32 MFMA block
+constexpr int NWAVE = 4;
+constexpr int NT = 64 * NWAVE;
+constexpr int STEP_ROWS = 32 * NWAVE;   // rows a workgroup scores per step (each wave one 32-row block)
+constexpr int TARGET_BLOCKS = 2048;     // score workgroups a search aims for (8 per CU)
+
+// index_topk_kernel.  LDS (lds bytes of launch_topk): float scores [min(QT, nq)][L], int ids the same, int count [QT]
+struct TopkArgs {
+    const void *rows, *queries;          // [n_rows][dpad], [nq][dpad] of T (b1: rows of dpad bits, queries of dpad i8 codes)
+    float *ws_s;                         // [nq][n_slices][k] per-(query, slice) lists, best first
+    int *ws_i;
+    int n_rows, dpad, nq, n_qtiles, n_slices, slice_rows, k, L, n_items;
+    const float *qscale, *rscale;        // [nq], [n_rows]: i8 both, b1 qscale; null (never read) where the form has none
+    // words [ceil(n_rows / 32)], bit b of word w set = row 32 w + b is live / may be returned; either may be null = all ones
+    const uint32_t *live, *allow;
+};
+
+struct MergeArgs {
+    const float *ws_s;                   // [nq][n_cand]
+    const int *ws_i;
+    int n_cand, k, L;                    // L = merge_L(k)
+    int32_t *ids;                        // [nq][k]
+    float *scores;
+};
+inline int merge_L(int k) { return k + NT <= 256 ? 256 : 512; }
+
+struct RescoreArgs {
+    const void *rows, *queries;          // as TopkArgs
+    const float *qscale, *rscale;
+    const uint32_t *live;                // null = every row live
+    const int32_t *cand;                 // [nq][n_cand] ids; outside [0, n_rows) = no candidate
+    float *ws_s;                         // [nq][n_cand]
+    int *ws_i;
+    int n_rows, dpad, nq, n_cand, n_blocks;      // n_blocks = ceil(n_cand / 32)
+};
+
+// lets every index_topk_kernel instantiation of the current device have the LDS of 32 queries x 512-entry lists
+void search_kernels_init();
+// the masked instantiation if a.live or a.allow is set
+void launch_topk(int dtype, const TopkArgs &a, size_t lds, hipStream_t s);
+void launch_topk_merge(const MergeArgs &a, int nq, hipStream_t s);
+void launch_rescore(int dtype, const RescoreArgs &a, hipStream_t s);
+// f32 rows [n][dim] -> the stored form of dtype, [n][dpad] (scales [n]: i8 only)
+void launch_ingest(int dtype, const float *src, void *dst, float *scales, int n, int dim, int dpad, hipStream_t s);
+// row i of dst (row_bytes, a multiple of 16) = row old_ids[i] of src, and its scale with it (sscale null: the form has none)
+void launch_gather(const void *src, void *dst, const float *sscale, float *dscale, const int32_t *old_ids, int n, size_t row_bytes, hipStream_t s);
+// live bits of rows [first, first + n) := 1
+void launch_live_set_range(uint32_t *live, int first, int n, hipStream_t s);
+
+}  // namespace bert_hip
