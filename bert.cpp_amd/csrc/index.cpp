@@ -1,5 +1,5 @@
-// index.cpp — the host side of the embedding index (search.h): storage and its growth, add, the search, rescore and two-stage
-// routes, the live bits, compaction and the file form.  Every kernel is in search.hip and reached through search_kernels.h.
+// index.cpp — the host side of the embedding index (search.h): storage and its growth, add, the search, rescore, two-stage and
+// probed routes, reading rows back, the live bits, compaction and the file form (the partition itself: index_partition.cpp).  Every kernel is in search.hip and reached through search_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,15 +18,15 @@ namespace {
 // What the host knows of a row form, by dtype (the device's side of it: ScoreBlock<T> in search.hip; the bytes of a stored
 // row: index_file.h).  The names are the profiler's; ingest is the kernel that makes the stored form of f32 rows.
 struct FormInfo {
-    const char *topk[2], *rescore, *ingest;      // topk[1]: the masked instantiation
+    const char *topk[2], *rescore, *probe, *exported, *ingest;      // topk[1]: the masked instantiation
     bool has_rscale;                             // one f32 scale per row beside the rows
     bool quantized_queries;                      // queries are stored as rows of the i8 form (codes and a scale), else of this one
 };
 constexpr FormInfo FORMS[4] = {
-    {{"index_topk_f32", "index_topk_f32_masked"}, "index_rescore_f32", "index_convert_f32", false, false},
-    {{"index_topk_f16", "index_topk_f16_masked"}, "index_rescore_f16", "index_convert_f16", false, false},
-    {{"index_topk_i8", "index_topk_i8_masked"}, "index_rescore_i8", "index_quantize_i8", true, true},
-    {{"index_topk_b1", "index_topk_b1_masked"}, "index_rescore_b1", "index_pack_b1", false, true},
+    {{"index_topk_f32", "index_topk_f32_masked"}, "index_rescore_f32", "index_probe_f32", "index_export_f32", "index_convert_f32", false, false},
+    {{"index_topk_f16", "index_topk_f16_masked"}, "index_rescore_f16", "index_probe_f16", "index_export_f16", "index_convert_f16", false, false},
+    {{"index_topk_i8", "index_topk_i8_masked"}, "index_rescore_i8", "index_probe_i8", "index_export_i8", "index_quantize_i8", true, true},
+    {{"index_topk_b1", "index_topk_b1_masked"}, "index_rescore_b1", "index_probe_b1", "index_export_b1", "index_pack_b1", false, true},
 };
 int query_form(int dtype) { return FORMS[dtype].quantized_queries ? 2 : dtype; }
 
@@ -42,15 +42,6 @@ void live_set_range_host(std::vector<uint32_t> &live, int first, int n) {
 }
 
 size_t live_words(long long rows) { return (size_t)((rows + 31) / 32); }
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(d);
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 // slices of a search: enough workgroups to fill the chip, but each slice long against k (the first k rows of a slice all
 // enter its list, and the merge reads slices x k candidates per query).  Grows with n_rows.
@@ -385,6 +376,74 @@ int Index::search_rescored_to_host(Index &coarse, int nq, const float *q, int n_
 }
 
 // ------------------------------------------------------------------------------------------------
+// probed search (the partition: index_partition.cpp), rows read back
+// ------------------------------------------------------------------------------------------------
+int Index::search_probed_device(int nq, const float *d_q, int nprobe, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err) {
+    if (const int go = check_search(nq, d_q, k, d_ids, d_scores, err); go <= 0) return go;
+    if (!cent_ || nprobe < 1 || nprobe > std::min(n_lists(), MAX_K)) { err = "search_probed: a partition and 1 <= nprobe <= min(n_lists, 256) required"; return -1; }
+    DeviceGuard g(eng_->device());
+    const int nqc = std::min(nq, QCHUNK);
+    // items per query: the probed lists, then the chunks of the tail
+    const int n_items = nprobe + (int)(((long long)n_ - n_part_ + PROBE_CHUNK - 1) / PROBE_CHUNK);
+    const size_t ent = (size_t)nqc * n_items * k;
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow_queries(nqc, err) ||
+        !grow(probe_i_, (size_t)nqc * nprobe * 4, err) || !grow(probe_s_, (size_t)nqc * nprobe * 4, err)) return -1;
+    // (the probe lists are this index's: the centroid search that fills them waits, on s, for whatever still reads them)
+    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        const float *dq = d_q + (size_t)c0 * dim_;
+        if (cent_->search_device(c, dq, nprobe, probe_i_.as<int32_t>(), probe_s_.as<float>(), s, err) != 0) return -1;
+        enqueue_queries(c, dq, s);
+        ProbeArgs a;
+        a.rows = rows_; a.queries = qbuf_.p; a.qscale = qscale_.as<float>(); a.rscale = rscale_; a.live = live_;
+        a.probe = probe_i_.as<int32_t>(); a.offsets = offsets_.as<int32_t>(); a.order = order_.as<int32_t>();
+        a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+        a.n_rows = n_; a.dpad = dpad_; a.nq = c; a.nprobe = nprobe; a.n_lists = n_lists(); a.n_part = n_part_; a.n_items = n_items;
+        a.k = k; a.L = probe_L(k);
+        eng_->timed_launch(FORMS[dtype_].probe, 0.0, s, [&] { launch_probe(dtype_, a, s); });
+        enqueue_merge(c, n_items * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
+    }
+    HIP_OK(hipGetLastError(), err, -1);
+    HIP_OK(hipEventRecord(busy_, s), err, -1);
+    return 0;
+}
+
+int Index::search_probed_to_host(int nq, const float *q, int nprobe, int k, int32_t *ids, float *scores, std::string &err) {
+    if (const int go = check_search(nq, q, k, ids, scores, err); go <= 0) return go;
+    DeviceGuard g(eng_->device());
+    return host_route(nq, q, false, true, k, ids, scores, err, [&](int, int c, const float *d_q, int32_t *d_ids, float *d_scores) {
+        return search_probed_device(c, d_q, nprobe, k, d_ids, d_scores, stream_, err);
+    });
+}
+
+// rows ids[i] (d_ids null: first + i) as f32 into d_out [n][dim]
+void Index::enqueue_export(int first, int n, const int32_t *d_ids, float *d_out, hipStream_t s) {
+    ExportArgs a;
+    a.rows = rows_; a.rscale = rscale_; a.ids = d_ids; a.out = d_out; a.first = first; a.n = n; a.dim = dim_; a.dpad = dpad_;
+    eng_->timed_launch(FORMS[dtype_].exported, 0.0, s, [&] { launch_export(dtype_, a, s); });
+}
+
+int Index::get_rows(int n, const int32_t *ids, float *rows, std::string &err) {
+    if (n <= 0) return 0;
+    DeviceGuard g(eng_->device());
+    // through device buffers of at most 64 MiB, as add_host
+    const int per = (int)std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)dim_ * 4));
+    for (int i0 = 0; i0 < n; i0 += per) {
+        const int c = std::min(per, n - i0);
+        if (!grow(cand_in_, (size_t)c * 4, err) || !grow(export_, (size_t)c * dim_ * 4, err)) return -1;
+        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -1);
+        HIP_OK(hipMemcpyAsync(cand_in_.p, ids + i0, (size_t)c * 4, hipMemcpyHostToDevice, stream_), err, -1);
+        enqueue_export(0, c, cand_in_.as<int32_t>(), export_.as<float>(), stream_);
+        HIP_OK(hipGetLastError(), err, -1);
+        HIP_OK(hipEventRecord(busy_, stream_), err, -1);
+        HIP_OK(hipMemcpyAsync(rows + (size_t)i0 * dim_, export_.p, (size_t)c * dim_ * 4, hipMemcpyDeviceToHost, stream_), err, -1);
+        HIP_OK(hipStreamSynchronize(stream_), err, -1);
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // removed rows, compaction, file form
 // ------------------------------------------------------------------------------------------------
 void Index::truncate(int n) {
@@ -505,6 +564,19 @@ int Index::compact(int32_t *old_ids, std::string &err) {
     cap_ = n_ = nl;
     drop_live();
     if (old_ids) memcpy(old_ids, map.data(), (size_t)nl * 4);
+    if (cent_) {
+        // the partition follows the rows: each keeps its list, and the tail (the old ids from n_part_ on) stays the tail
+        std::vector<int32_t> kept;
+        for (int32_t old : map)
+            if (old < n_part_) kept.push_back(list_of_[(size_t)old]);
+        if (!upload_lists(kept, n_lists(), err)) {
+            drop_partition();
+            err = "the rows are compacted, but the partition was dropped: " + err;
+            return -1;
+        }
+        n_part_ = (int)kept.size();
+        list_of_ = std::move(kept);
+    }
     return nl;
 }
 

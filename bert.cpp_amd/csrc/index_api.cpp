@@ -1,5 +1,6 @@
 // index_api.cpp — the bert_hip_index_* entry points of bert_hip.h: an embedding index (search.h) on a context's first device.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -89,6 +90,29 @@ bool two_stage_ok(const char *me, const bert_hip_index *coarse, const bert_hip_i
     else if (coarse->ix->size() != fine->ix->size()) why = "the two indexes differ in size";
     else if (k < 1 || k > n_cand || n_cand > Index::MAX_K) why = "1 <= k <= n_cand <= 256 required";
     else if (n_queries < 0 || (n_queries > 0 && !have_ptrs)) why = "n_queries >= 0 and queries / outputs required";
+    if (why) fprintf(stderr, "%s: %s\n", me, why);
+    return !why;
+}
+
+// the shape of a probed search (-2 after a line on stderr otherwise)
+bool probed_ok(const char *me, const Index &x, int32_t n_queries, int32_t nprobe, int32_t k, bool have_ptrs) {
+    const char *why = nullptr;
+    if (x.n_lists() == 0) why = "the index has no partition";
+    else if (nprobe < 1 || nprobe > std::min(x.n_lists(), Index::MAX_K)) why = "1 <= nprobe <= min(n_lists, 256) required";
+    else if (k < 1 || k > Index::MAX_K) why = "k must be 1 .. 256";
+    else if (n_queries < 0 || (n_queries > 0 && !have_ptrs)) why = "n_queries >= 0 and queries / outputs required";
+    if (why) fprintf(stderr, "%s: %s\n", me, why);
+    return !why;
+}
+
+// centroids [n_lists][dim] as partition and kmeans take them (-2 after a line on stderr otherwise)
+bool centroids_ok(const char *me, const Index &x, int32_t n_lists, const float *centroids) {
+    const char *why = nullptr;
+    if (n_lists < 1 || n_lists > Index::MAX_LISTS) why = "1 <= n_lists <= 65536 required";
+    else if (!centroids) why = "centroids required";
+    else
+        for (size_t i = 0; i < (size_t)n_lists * x.dim() && !why; ++i)
+            if (!std::isfinite(centroids[i])) why = "a centroid element is not finite";
     if (why) fprintf(stderr, "%s: %s\n", me, why);
     return !why;
 }
@@ -239,6 +263,79 @@ int32_t bert_hip_index_search_rescored_device(struct bert_hip_index *coarse, str
     return index_call(me, fine, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
         if (!two_stage_ok(me, coarse, fine, n_queries, n_cand, k, d_queries && d_ids && d_scores)) return -2;
         return x.search_rescored_device(*coarse->ix, n_queries, d_queries, n_cand, k, d_ids, d_scores, (hipStream_t)stream, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_get_rows(struct bert_hip_index *ix, int32_t n, const int32_t *ids, float *rows) {
+    const char *me = "bert_hip_index_get_rows";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (n < 0 || (n > 0 && (!ids || !rows))) { fprintf(stderr, "%s: n >= 0 and ids / rows required\n", me); return -2; }
+        for (int32_t i = 0; i < n; ++i)
+            if (ids[i] < 0 || ids[i] >= x.size()) { fprintf(stderr, "%s: id %d is outside [0, %d)\n", me, ids[i], x.size()); return -2; }
+        // (into a buffer of our own: the caller's rows stay untouched on an error)
+        std::vector<float> out((size_t)n * x.dim());
+        if (x.get_rows(n, ids, out.data(), err) != 0) return -3;
+        memcpy(rows, out.data(), out.size() * 4);
+        return 0;
+    });
+}
+
+int32_t bert_hip_index_partition(struct bert_hip_index *ix, int32_t n_lists, const float *centroids) {
+    const char *me = "bert_hip_index_partition";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (n_lists != 0 && !centroids_ok(me, x, n_lists, centroids)) return -2;
+        return x.partition(n_lists, centroids, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_n_lists(struct bert_hip_index *ix) { return ix && ix->ix ? ix->ix->n_lists() : -1; }
+
+int32_t bert_hip_index_partition_centroids(struct bert_hip_index *ix, float *centroids) {
+    const char *me = "bert_hip_index_partition_centroids";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &) -> int32_t {
+        if (x.n_lists() == 0 || !centroids) { fprintf(stderr, "%s: a partition and room for its centroids required\n", me); return -2; }
+        memcpy(centroids, x.centroids().data(), x.centroids().size() * 4);
+        return 0;
+    });
+}
+
+int32_t bert_hip_index_partition_lists(struct bert_hip_index *ix, int32_t *list_of_row) {
+    const char *me = "bert_hip_index_partition_lists";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &) -> int32_t {
+        if (x.n_lists() == 0 || (x.size() > 0 && !list_of_row)) { fprintf(stderr, "%s: a partition and room for size entries required\n", me); return -2; }
+        x.partition_lists(list_of_row);
+        return 0;
+    });
+}
+
+int32_t bert_hip_index_kmeans(struct bert_hip_index *ix, int32_t n_lists, int32_t n_iter, float *centroids) {
+    const char *me = "bert_hip_index_kmeans";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!centroids_ok(me, x, n_lists, centroids)) return -2;
+        if (n_iter < 1) { fprintf(stderr, "%s: n_iter >= 1 required\n", me); return -2; }
+        // (refined in a buffer of our own: the caller's centroids stay untouched on an error)
+        std::vector<float> c(centroids, centroids + (size_t)n_lists * x.dim());
+        if (x.kmeans(n_lists, n_iter, c.data(), err) != 0) return -3;
+        memcpy(centroids, c.data(), c.size() * 4);
+        return 0;
+    });
+}
+
+int32_t bert_hip_index_search_probed(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t nprobe, int32_t k,
+                                     int32_t *ids, float *scores) {
+    const char *me = "bert_hip_index_search_probed";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!probed_ok(me, x, n_queries, nprobe, k, queries && ids && scores)) return -2;
+        return x.search_probed_to_host(n_queries, queries, nprobe, k, ids, scores, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_probed_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t nprobe, int32_t k,
+                                            int32_t *d_ids, float *d_scores, void *stream) {
+    const char *me = "bert_hip_index_search_probed_device";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!probed_ok(me, x, n_queries, nprobe, k, d_queries && d_ids && d_scores)) return -2;
+        return x.search_probed_device(n_queries, d_queries, nprobe, k, d_ids, d_scores, (hipStream_t)stream, err) != 0 ? -3 : 0;
     });
 }
 

@@ -13,12 +13,19 @@
 // the search, hence the same score bits) into [nq][n_cand] lists in the workspace, and topk_merge_kernel selects from them.
 // A two-stage search is a search of a coarse index (b1, say) with k' = n_cand whose ids stay on the device and are rescored
 // against a finer index of the same rows.
+//
+// Partition (index_partition.cpp; the list tables: partition.h): centroids, held as an f32 Index of their own, and one list id
+// per row — the id a k = 1 search of that index returns for the row as get_rows gives it.  Storage stays in id order; the lists
+// are a table of row ids sorted by (list, id).  A probed search scores the centroids (a search with k = nprobe), then
+// index_probe_kernel scans the members of each query's lists and the unassigned tail — the rows added since — and selects on
+// chip; topk_merge_kernel merges the items' lists.  kmeans refines centroids with the same assignment and kmeans_update_kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -26,6 +33,16 @@
 #include "index_file.h"
 
 namespace bert_hip {
+
+// the index's device for the length of a call (index.cpp, index_partition.cpp)
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int d) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        (void)hipSetDevice(d);
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
 
 class Index {
 public:
@@ -70,6 +87,22 @@ public:
     int search_rescored_device(Index &coarse, int nq, const float *d_q, int n_cand, int k, int32_t *d_ids, float *d_scores,
                                hipStream_t s, std::string &err);
     int search_rescored_to_host(Index &coarse, int nq, const float *q, int n_cand, int k, int32_t *ids, float *scores, std::string &err);
+    // the stored rows ids [n] (each in [0, size): the caller checks) as f32 [n][dim], removed rows included; blocking
+    int get_rows(int n, const int32_t *ids, float *rows, std::string &err);
+    // Partition.  partition: installs centroids [n_lists][dim] (finite: the caller checks; 1 <= n_lists <= MAX_LISTS) and
+    // assigns every current row; n_lists = 0 drops the partition.  Rows added later are the unassigned tail.  Blocking; 0 or -1
+    static constexpr int MAX_LISTS = 65536;
+    int partition(int n_lists, const float *centroids, std::string &err);
+    int n_lists() const { return cent_ ? cent_->size() : 0; }
+    const std::vector<float> &centroids() const { return cent_h_; }
+    void partition_lists(int32_t *list_of_row) const;               // [size]: -1 for the tail
+    // spherical k-means over the live rows: n_iter times assign as partition does, then each centroid := its members' sum
+    // over that sum's norm (kept for no member, a zero or a non-finite norm).  Leaves the index as it is.  Blocking; 0 or -1
+    int kmeans(int n_lists, int n_iter, float *centroids, std::string &err);
+    // Probed search: as search_device over the rows of each query's nprobe best lists and the tail.  The caller checks that
+    // there is a partition and 1 <= nprobe <= min(n_lists, MAX_K).  Asynchronous on s; 0 or -1
+    int search_probed_device(int nq, const float *d_q, int nprobe, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err);
+    int search_probed_to_host(int nq, const float *q, int nprobe, int k, int32_t *ids, float *scores, std::string &err);
     // marks rows as removed (ids in [0, size) or -1 with the index unchanged; repeats ignored): the number newly removed; blocking
     int remove(int n, const int32_t *ids, std::string &err);
     // drops the removed rows' storage: live rows keep order and bits, ids 0 .. n_live - 1; old_ids (null or [n_live]) the
@@ -94,6 +127,10 @@ private:
     int host_route(int nq, const float *q, bool q_on_device, bool wait, int k, int32_t *ids, float *scores, std::string &err,
                    const std::function<int(int, int, const float *, int32_t *, float *)> &device_form);
     bool grow_queries(int nqc, std::string &err);
+    void enqueue_export(int first, int n, const int32_t *d_ids, float *d_out, hipStream_t s);
+    bool assign_rows(Index &cent, std::vector<int32_t> &list_of, std::string &err);
+    bool upload_lists(const std::vector<int32_t> &list_of, int n_lists, std::string &err);
+    void drop_partition();
     bool make_live(std::string &err);
     bool upload_live(size_t w0, size_t w1, std::string &err);
     void drop_live();
@@ -111,6 +148,13 @@ private:
     uint32_t *live_ = nullptr;
     std::vector<uint32_t> live_h_;
     int n_removed_ = 0;
+    // partition: the centroids as an index (null: none) and on the host; the list of each row below n_part_ (the rows behind
+    // are the tail); the list tables on the device; the probed lists of the current chunk; exported rows and their lists
+    std::unique_ptr<Index> cent_;
+    std::vector<float> cent_h_;
+    std::vector<int32_t> list_of_;
+    int n_part_ = 0;
+    DevBuf offsets_, order_, probe_i_, probe_s_, export_, assign_i_, assign_s_;
     DevBuf allow_;                                      // host route: the caller's allow-list on the device
     DevBuf stage_, out_ids_, out_scores_, scratch_;     // host routes: f32 rows / queries, results; the text routes' embeddings
     hipStream_t stream_ = nullptr;                      // the host routes' stream

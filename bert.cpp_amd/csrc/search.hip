@@ -22,6 +22,15 @@
 //                         same ScoreBlock (the same MFMA chain per (query, row), so the same bits as a search), scores and ids
 //                         [nq][n_cand] into the workspace — id INT_MAX, score -inf for an entry that names no live row —, from
 //                         which topk_merge_kernel selects.
+//   index_probe_kernel<T>  the probed search of a partitioned index: one workgroup per (query, item), an item being one of the
+//                         query's probed lists (its members' ids come from the partition's order table) or a chunk of the
+//                         unassigned tail.  Each wave scores 32 members per step as the rescore kernel does, and the workgroup
+//                         selects in LDS as the top-k kernel does for one query: k entries per item reach the workspace, from
+//                         which topk_merge_kernel selects.
+//   index_export_kernel<T>  stored rows, named by id, back as f32 (ScoreBlock<T>::element): bert_hip_index_get_rows, and the
+//                         queries of the partition's assignment.
+//   kmeans_update_kernel<T>  one workgroup per list: the sum of its members' exported rows in an order fixed by the member
+//                         positions (each wave every fourth member, then a fixed tree over the waves), divided by its norm.
 //   index_gather_kernel   compaction: stored rows (and i8 scales) of the listed old ids into a fresh allocation.
 //   live_set_range_kernel sets the live bits of newly added rows.
 //   index_convert_kernel  f32 rows (added rows, queries) -> the stored form: f32 or f16 (RNE), zero-padded to dpad.
@@ -91,7 +100,8 @@ __device__ void bitonic_sort_lists(float *ls, int *li, int nl, int L, int tid) {
 // accumulation is fixed by dpad alone.
 // ScoreBlock<T> is also everything else a kernel knows of the stored form T: query_t / acc_t, the element of a query as run
 // reads it and run's accumulator; QSCALE / RSCALE, whether a score takes the query's / the row's scale; row_ptr, stored row
-// `row` of rows of dpad elements; finish, one accumulator element -> the score, the one place that arithmetic is written.
+// `row` of rows of dpad elements; finish, one accumulator element -> the score, the one place that arithmetic is written;
+// element, element e of a stored row as f32 (rs: its scale where RSCALE) — what bert_hip_index_get_rows returns.
 template <class T> struct ScoreBlock;
 
 // f16, f32: queries are stored as rows are, and the MFMA's f32 sum is the score
@@ -101,6 +111,7 @@ template <class T> struct FloatForm {
     static constexpr bool QSCALE = false, RSCALE = false;
     static __device__ __forceinline__ const T *row_ptr(const void *rows, size_t row, int dpad) { return (const T *)rows + row * dpad; }
     static __device__ __forceinline__ float finish(float acc, float, float) { return acc; }
+    static __device__ __forceinline__ float element(const T *rp, float, int e) { return (float)rp[e]; }
 };
 
 template <> struct ScoreBlock<half_t> : FloatForm<half_t> {
@@ -158,6 +169,7 @@ template <> struct ScoreBlock<int8_t> {
     static __device__ __forceinline__ const int8_t *row_ptr(const void *rows, size_t row, int dpad) { return (const int8_t *)rows + row * dpad; }
     // (two multiplies in this order and no add: nothing the compiler could contract)
     static __device__ __forceinline__ float finish(int dot, float qs, float rs) { return ((float)dot * qs) * rs; }
+    static __device__ __forceinline__ float element(const int8_t *rp, float rs, int e) { return (float)rp[e] * rs; }
     // v_mfma_i32_32x32x32_i8: lane l feeds the 16 bytes at k = 32 s + 16 (l >> 5) of its query and of its row to step s — the
     // same k map on both sides, and an integer sum is exact in any order
     static __device__ __forceinline__ void run(const int8_t *qp, const int8_t *rp, bool qok, bool rok, int dpad, int h, i32x16 &acc) {
@@ -189,6 +201,7 @@ template <> struct ScoreBlock<b1_t> {
     // (dpad / 8 bytes per row)
     static __device__ __forceinline__ const b1_t *row_ptr(const void *rows, size_t row, int dpad) { return (const b1_t *)rows + row * (dpad >> 3); }
     static __device__ __forceinline__ float finish(int dot, float qs, float) { return (float)dot * qs; }
+    static __device__ __forceinline__ float element(const b1_t *rp, float, int e) { return (rp[e >> 3].bits >> (e & 7)) & 1 ? 1.f : -1.f; }
     // bit 4 j + b of bits16 in byte b of element j: 0x01 for a set bit, 0xff (-1) for a clear one.  The multiply puts bit b of
     // a nibble at bit 8 b (four copies 7 bits apart, which do not overlap); the byte permute looks 0 / 1 up in {0xff, 0x01}
     static __device__ __forceinline__ i32x4 expand(uint32_t bits16) {
@@ -405,6 +418,136 @@ __global__ __launch_bounds__(NT) void index_rescore_kernel(RescoreArgs a) {
     }
 }
 
+// One workgroup per (query, item); the item's members m0 .. m1 - 1 are rows order[m] (a probed list) or m itself (a tail chunk).
+// Scoring is index_rescore_kernel's — the query is query 0 of the tile, lane l < 32 ends with its member's score —, selection
+// index_topk_kernel's with one query: threshold in registers, queue behind the current top-k in LDS, sorted when a step might
+// not fit.  The k entries written for an item that has fewer candidates are (-inf, SENT_ID).
+template <class T>
+__global__ __launch_bounds__(NT) void index_probe_kernel(ProbeArgs a) {
+    using F = ScoreBlock<T>;
+    using QE = typename F::query_t;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int q = (int)blockIdx.x / a.n_items, item = (int)blockIdx.x - q * a.n_items;
+    const int L = a.L, k = a.k, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
+    float *ls = (float *)smem;
+    int *li = (int *)(ls + L);
+    int *cnt = li + L;
+    // (everything up to the loop is uniform over the workgroup)
+    const bool listed = item < a.nprobe;
+    int m0 = 0, m1 = 0;
+    if (listed) {
+        const int l = a.probe[(size_t)q * a.nprobe + item];
+        if (l >= 0 && l < a.n_lists) { m0 = a.offsets[l]; m1 = a.offsets[l + 1]; }
+    } else {
+        // (64-bit: n_part + c * PROBE_CHUNK may pass 2^31 in the last chunk's end)
+        const long long t0 = (long long)a.n_part + (long long)(item - a.nprobe) * PROBE_CHUNK;
+        m0 = (int)min(t0, (long long)a.n_rows);
+        m1 = (int)min(t0 + PROBE_CHUNK, (long long)a.n_rows);
+    }
+    const size_t out = ((size_t)q * a.n_items + item) * k;
+    if (m0 >= m1) {
+        for (int j = tid; j < k; j += NT) { a.ws_s[out + j] = -INFINITY; a.ws_i[out + j] = SENT_ID; }
+        return;
+    }
+    for (int i = tid; i < L; i += NT) { ls[i] = -INFINITY; li[i] = SENT_ID; }
+    if (tid == 0) *cnt = 0;
+    float ts = -INFINITY;
+    int ti = SENT_ID;
+    __syncthreads();
+
+    const QE *qp = (const QE *)a.queries + (size_t)q * a.dpad;
+    const float qs = F::QSCALE ? a.qscale[q] : 0.f;
+    const int room = L - k - STEP_ROWS;          // a step pushes at most STEP_ROWS entries
+    // (the trip count is the workgroup's: the barriers below are met by every wave)
+    for (int base = m0; base < m1; base += STEP_ROWS) {
+        const int m = base + wave * 32 + col;
+        const int id = m < m1 ? (listed ? a.order[m] : m) : -1;
+        bool rok = id >= 0 && id < a.n_rows;
+        if (rok && a.live) rok = (a.live[id >> 5] >> (id & 31)) & 1u;
+        if (__any(rok)) {                                          // (wave-uniform)
+            const T *rp = F::row_ptr(a.rows, (size_t)(rok ? id : 0), a.dpad);
+            const float rs = F::RSCALE && rok ? a.rscale[id] : 0.f;
+            typename F::acc_t dot = {};
+            F::run(qp, rp, col == 0, rok, a.dpad, h, dot);
+            const float s = F::finish(dot[0], qs, rs);
+            if (h == 0 && rok && better(s, id, ts, ti)) {
+                const int p = atomicAdd(cnt, 1);
+                ls[k + p] = s;
+                li[k + p] = id;
+            }
+        }
+        __syncthreads();
+        if (__syncthreads_or(tid == 0 && *cnt > room)) {
+            bitonic_sort_lists(ls, li, 1, L, tid);
+            ts = ls[k - 1];
+            ti = li[k - 1];
+            if (tid == 0) *cnt = 0;
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (__syncthreads_or(tid == 0 && *cnt > 0)) bitonic_sort_lists(ls, li, 1, L, tid);
+    for (int j = tid; j < k; j += NT) { a.ws_s[out + j] = ls[j]; a.ws_i[out + j] = li[j]; }
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void index_export_kernel(ExportArgs a) {
+    using F = ScoreBlock<T>;
+    const size_t total = (size_t)a.n * a.dim;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / a.dim;
+        const int c = (int)(i - r * a.dim);
+        const size_t row = a.ids ? (size_t)a.ids[r] : (size_t)a.first + r;
+        a.out[i] = F::element(F::row_ptr(a.rows, row, a.dpad), F::RSCALE ? a.rscale[row] : 0.f, c);
+    }
+}
+
+// One workgroup per list.  Lane l of a wave owns elements l, l + 64, ... of the sum; wave w adds members w, w + NWAVE, ... of the
+// list in that order, the four partial sums meet as (0 + 1) + (2 + 3), and the squares as each thread's elements in ascending
+// order, then a halving tree over the threads: the bits depend on the member positions alone.  No atomics.
+template <class T>
+__global__ __launch_bounds__(NT) void kmeans_update_kernel(KmeansArgs a) {
+    using F = ScoreBlock<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int EPL = 2048 / 64;               // elements per lane at the largest dim of an index
+    float *part = (float *)smem;                 // [NWAVE][dim], then [dim] the sum
+    float *sq = part + NWAVE * a.dim;            // [NT]
+    const int l = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, dim = a.dim;
+    const int m0 = a.offsets[l], m1 = a.offsets[l + 1];
+    if (m0 >= m1) return;                        // (the whole workgroup)
+    float acc[EPL];
+#pragma unroll
+    for (int j = 0; j < EPL; ++j) acc[j] = 0.f;
+    for (int m = m0 + wave; m < m1; m += NWAVE) {
+        const int row = a.order[m];
+        const T *rp = F::row_ptr(a.rows, (size_t)row, a.dpad);
+        const float rs = F::RSCALE ? a.rscale[row] : 0.f;
+#pragma unroll
+        for (int j = 0; j < EPL; ++j)
+            if (64 * j + lane < dim) acc[j] += F::element(rp, rs, 64 * j + lane);
+    }
+#pragma unroll
+    for (int j = 0; j < EPL; ++j)
+        if (64 * j + lane < dim) part[wave * dim + 64 * j + lane] = acc[j];
+    __syncthreads();
+    float ss = 0.f;
+    for (int e = tid; e < dim; e += NT) {
+        const float v = (part[e] + part[dim + e]) + (part[2 * dim + e] + part[3 * dim + e]);
+        part[e] = v;
+        ss += v * v;
+    }
+    sq[tid] = ss;
+    __syncthreads();
+    for (int o = NT / 2; o > 0; o >>= 1) {
+        if (tid < o) sq[tid] += sq[tid + o];
+        __syncthreads();
+    }
+    const float norm = sqrtf(sq[0]);
+    if (!(norm > 0.f) || !__builtin_isfinite(norm)) return;
+    for (int e = tid; e < dim; e += NT) a.centroids[(size_t)l * dim + e] = part[e] / norm;
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void index_convert_kernel(const float *__restrict__ src, T *__restrict__ dst, int n, int dim, int dpad) {
     const size_t total = (size_t)n * dpad;
@@ -537,6 +680,22 @@ void launch_topk_merge(const MergeArgs &a, int nq, hipStream_t s) {
 void launch_rescore(int dtype, const RescoreArgs &a, hipStream_t s) {
     const int grid = (a.nq * a.n_blocks + NWAVE - 1) / NWAVE;
     dispatch(dtype, [&](auto form) { BERT_LAUNCH(index_rescore_kernel<decltype(row_type(form))>, dim3(grid), dim3(NT), 0, s, a); });
+}
+
+void launch_probe(int dtype, const ProbeArgs &a, hipStream_t s) {
+    dispatch(dtype, [&](auto form) {
+        BERT_LAUNCH(index_probe_kernel<decltype(row_type(form))>, dim3((unsigned)a.nq * a.n_items), dim3(NT), (size_t)a.L * 8 + 16, s, a);
+    });
+}
+
+void launch_export(int dtype, const ExportArgs &a, hipStream_t s) {
+    const int blocks = (int)std::min<size_t>(((size_t)a.n * a.dim + 255) / 256, 8192);
+    dispatch(dtype, [&](auto form) { BERT_LAUNCH(index_export_kernel<decltype(row_type(form))>, dim3(blocks), dim3(256), 0, s, a); });
+}
+
+void launch_kmeans_update(int dtype, const KmeansArgs &a, hipStream_t s) {
+    const size_t lds = ((size_t)NWAVE * a.dim + NT) * 4;
+    dispatch(dtype, [&](auto form) { BERT_LAUNCH(kmeans_update_kernel<decltype(row_type(form))>, dim3(a.n_lists), dim3(NT), lds, s, a); });
 }
 
 void launch_ingest(int dtype, const float *src, void *dst, float *scales, int n, int dim, int dpad, hipStream_t s) {

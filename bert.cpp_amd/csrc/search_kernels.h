@@ -45,12 +45,50 @@ struct RescoreArgs {
     int n_rows, dpad, nq, n_cand, n_blocks;      // n_blocks = ceil(n_cand / 32)
 };
 
+// index_probe_kernel: one workgroup per (query, item).  Items 0 .. nprobe - 1 are the lists probe[q][item] names (-1: none), whose
+// members are order[offsets[l] .. offsets[l + 1]); item nprobe + c is tail chunk c, rows n_part + c * PROBE_CHUNK ... (< n_rows).
+// LDS: float scores [L], int ids [L], int count, L = probe_L(k)
+constexpr int PROBE_CHUNK = 1024;       // rows of a tail chunk
+struct ProbeArgs {
+    const void *rows, *queries;          // as TopkArgs
+    const float *qscale, *rscale;
+    const uint32_t *live;                // null = every row live
+    const int32_t *probe;                // [nq][nprobe] list ids
+    const int32_t *offsets, *order;      // [n_lists + 1], [offsets[n_lists]]
+    float *ws_s;                         // [nq][n_items][k], best first
+    int *ws_i;
+    int n_rows, dpad, nq, nprobe, n_lists, n_part, n_items, k, L;
+};
+inline int probe_L(int k) { return k + STEP_ROWS <= 256 ? 256 : 512; }
+
+// index_export_kernel: out [n][dim] f32 = the stored rows ids[i] (ids null: first + i), as bert_hip_index_get_rows states them
+struct ExportArgs {
+    const void *rows;
+    const float *rscale;
+    const int32_t *ids;
+    float *out;
+    int first, n, dim, dpad;
+};
+
+// kmeans_update_kernel: one workgroup per list; centroid l := the sum of the exported rows order[offsets[l] .. offsets[l + 1])
+// over its L2 norm, left as it is for an empty list or a zero or non-finite norm.  LDS: NWAVE * dim + NT floats
+struct KmeansArgs {
+    const void *rows;
+    const float *rscale;
+    const int32_t *offsets, *order;
+    float *centroids;                    // [n_lists][dim]
+    int n_lists, dim, dpad;
+};
+
 // lets every index_topk_kernel instantiation of the current device have the LDS of 32 queries x 512-entry lists
 void search_kernels_init();
 // the masked instantiation if a.live or a.allow is set
 void launch_topk(int dtype, const TopkArgs &a, size_t lds, hipStream_t s);
 void launch_topk_merge(const MergeArgs &a, int nq, hipStream_t s);
 void launch_rescore(int dtype, const RescoreArgs &a, hipStream_t s);
+void launch_probe(int dtype, const ProbeArgs &a, hipStream_t s);
+void launch_export(int dtype, const ExportArgs &a, hipStream_t s);
+void launch_kmeans_update(int dtype, const KmeansArgs &a, hipStream_t s);
 // f32 rows [n][dim] -> the stored form of dtype, [n][dpad] (scales [n]: i8 only)
 void launch_ingest(int dtype, const float *src, void *dst, float *scales, int n, int dim, int dpad, hipStream_t s);
 // row i of dst (row_bytes, a multiple of 16) = row old_ids[i] of src, and its scale with it (sscale null: the form has none)

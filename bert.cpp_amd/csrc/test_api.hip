@@ -9,6 +9,7 @@
 
 #include "context.h"
 #include "index_file.h"
+#include "partition.h"
 
 using namespace bert_hip;
 
@@ -463,6 +464,15 @@ int32_t bert_hip_test_index_header(const void *buf, int32_t buf_len, int64_t fil
     }
     if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", e.c_str());
     return -1;
+}
+
+int32_t bert_hip_test_build_lists(const int32_t *list_of, int32_t n, int32_t n_lists, int32_t *offsets, int32_t *order) {
+    if (n < 0 || n_lists < 0 || (n > 0 && !list_of) || !offsets || (n > 0 && !order)) return -1;
+    ListTables t;
+    build_lists(list_of, n, n_lists, t);
+    std::copy(t.offsets.begin(), t.offsets.end(), offsets);
+    std::copy(t.order.begin(), t.order.end(), order);
+    return (int32_t)t.order.size();
 }
 
 }  // extern "C"

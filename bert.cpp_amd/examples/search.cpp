@@ -3,10 +3,13 @@
 // then each line read from stdin is a query whose k closest texts are printed in the reference's format.  'q' or the end
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
-//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [-t THREADS] [--save PATH] [--load PATH]
+//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N [--nprobe P]] [-t THREADS] [--save PATH] [--load PATH]
 //   (--f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; --b1: one sign bit per element; the
 //   default stores the rows as f16; --rescore N: an int8 index of the same texts is kept beside the index, which only picks N
 //   candidates per query, and the answer is the int8 index's best k of them (bert_hip_index_search_rescored; k <= N <= 256);
+//   --lists N: once the texts are in, the index is partitioned into N lists (bert_hip_index_kmeans, ten iterations from N evenly
+//   spaced rows, then bert_hip_index_partition); --nprobe P: each query then scans only its P nearest lists
+//   (bert_hip_index_search_probed; 1 <= P <= min(N, 256));
 //   --save: the index goes to PATH (bert_hip_index_save) once it is built; --load: the index comes from PATH instead of being
 //   embedded — TEXTS is still read, for printing, and must have as many lines as the index has rows)
 #include <cstdio>
@@ -22,7 +25,7 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N [--nprobe P]] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
 }
 
 std::string chomp(std::string s) {
@@ -33,7 +36,7 @@ std::string chomp(std::string s) {
 
 int main(int argc, char **argv) {
     const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr;
-    int k = 3, n_threads = 6, dtype = 1, n_cand = 0;
+    int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
         if ((!strcmp(argv[i], "-m") || !strcmp(argv[i], "--model")) && has_value) model = argv[++i];
@@ -46,12 +49,20 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--i8")) dtype = 2;
         else if (!strcmp(argv[i], "--b1")) dtype = 3;
         else if (!strcmp(argv[i], "--rescore") && has_value) n_cand = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--lists") && has_value) n_lists = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--nprobe") && has_value) nprobe = atoi(argv[++i]);
         else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
     }
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
     const bool two_stage = n_cand != 0;
     if (two_stage && (n_cand < k || n_cand > 256)) { fprintf(stderr, "search: --rescore must be -k .. 256\n"); return 2; }
+
+    if (n_lists < 0 || n_lists > 65536) { fprintf(stderr, "search: --lists must be 1 .. 65536\n"); return 2; }
+    if (nprobe != 0 && (two_stage || nprobe < 1 || nprobe > n_lists || nprobe > 256)) {
+        fprintf(stderr, "search: --nprobe must be 1 .. min(--lists, 256), and goes without --rescore\n");
+        return 2;
+    }
 
     bert_ctx *ctx = bert_load_from_file(model);
     if (!ctx) {
@@ -101,6 +112,24 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (n_lists > 0) {
+        // centroids: ten k-means iterations from n_lists evenly spaced rows
+        const int32_t size = bert_hip_index_size(ix);
+        if (n_lists > size) {
+            fprintf(stderr, "search: --lists %d exceeds the %d texts\n", n_lists, size);
+            bert_free(ctx);
+            return 1;
+        }
+        std::vector<int32_t> seeds((size_t)n_lists);
+        for (int i = 0; i < n_lists; ++i) seeds[(size_t)i] = (int32_t)((int64_t)i * size / n_lists);
+        std::vector<float> centroids((size_t)n_lists * bert_n_embd(ctx));
+        if (bert_hip_index_get_rows(ix, n_lists, seeds.data(), centroids.data()) != 0 || bert_hip_index_kmeans(ix, n_lists, 10, centroids.data()) != 0 ||
+            bert_hip_index_partition(ix, n_lists, centroids.data()) != 0) {
+            fprintf(stderr, "search: could not partition the index\n");
+            bert_free(ctx);
+            return 1;
+        }
+    }
     if (save && bert_hip_index_save(ix, save) != 0) {
         fprintf(stderr, "search: could not save the index to '%s'\n", save);
         bert_free(ctx);
@@ -124,6 +153,10 @@ int main(int argc, char **argv) {
             float *ep = emb.data();
             r = bert_hip_encode_batch(ctx, n_threads, 1, &qp, &ep) == 1
                     ? bert_hip_index_search_rescored(ix, fine, 1, emb.data(), n_cand, k, ids.data(), scores.data()) : -1;
+        } else if (nprobe > 0) {
+            float *ep = emb.data();
+            r = bert_hip_encode_batch(ctx, n_threads, 1, &qp, &ep) == 1
+                    ? bert_hip_index_search_probed(ix, 1, emb.data(), nprobe, k, ids.data(), scores.data()) : -1;
         } else {
             r = bert_hip_index_search_texts(ix, n_threads, 1, &qp, k, ids.data(), scores.data());
         }

@@ -30,6 +30,8 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_index_search_texts", "bert_hip_index_remove", "bert_hip_index_n_live", "bert_hip_index_search_filtered",
     "bert_hip_index_search_filtered_device", "bert_hip_index_compact", "bert_hip_index_save", "bert_hip_index_load",
     "bert_hip_index_rescore", "bert_hip_index_rescore_device", "bert_hip_index_search_rescored", "bert_hip_index_search_rescored_device",
+    "bert_hip_index_get_rows", "bert_hip_index_partition", "bert_hip_index_n_lists", "bert_hip_index_partition_centroids",
+    "bert_hip_index_partition_lists", "bert_hip_index_kmeans", "bert_hip_index_search_probed", "bert_hip_index_search_probed_device",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -40,6 +42,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
+    "bert_hip_test_build_lists",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -114,6 +117,14 @@ def _declare_product_abi(L):
     L.bert_hip_index_search_rescored.restype = i32; L.bert_hip_index_search_rescored.argtypes = [vp, vp, i32, f32p, i32, i32, i32p, f32p]
     L.bert_hip_index_search_rescored_device.restype = i32
     L.bert_hip_index_search_rescored_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
+    L.bert_hip_index_get_rows.restype = i32; L.bert_hip_index_get_rows.argtypes = [vp, i32, i32p, f32p]
+    L.bert_hip_index_partition.restype = i32; L.bert_hip_index_partition.argtypes = [vp, i32, f32p]
+    L.bert_hip_index_n_lists.restype = i32; L.bert_hip_index_n_lists.argtypes = [vp]
+    L.bert_hip_index_partition_centroids.restype = i32; L.bert_hip_index_partition_centroids.argtypes = [vp, f32p]
+    L.bert_hip_index_partition_lists.restype = i32; L.bert_hip_index_partition_lists.argtypes = [vp, i32p]
+    L.bert_hip_index_kmeans.restype = i32; L.bert_hip_index_kmeans.argtypes = [vp, i32, i32, f32p]
+    L.bert_hip_index_search_probed.restype = i32; L.bert_hip_index_search_probed.argtypes = [vp, i32, f32p, i32, i32, i32p, f32p]
+    L.bert_hip_index_search_probed_device.restype = i32; L.bert_hip_index_search_probed_device.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
 
 
 def lib() -> C.CDLL:
@@ -186,6 +197,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_tokenize_pack.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32p, i32p, i32p, i32p, i32]
     L.bert_hip_test_index_header.restype = i32
     L.bert_hip_test_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
+    L.bert_hip_test_build_lists.restype = i32
+    L.bert_hip_test_build_lists.argtypes = [i32p, i32, i32, i32p, i32p]
     _test_lib = L
     return L
 
@@ -653,6 +666,88 @@ class BertIndex:
         r = self.lib.bert_hip_index_search_rescored_device(self.ix, fine.ix, n_queries, d_queries_ptr, n_cand, k, d_ids_ptr, d_scores_ptr, stream)
         if r != 0:
             raise RuntimeError(f"bert_hip_index_search_rescored_device failed: {r}")
+
+    def get_rows(self, ids) -> np.ndarray:
+        """bert_hip_index_get_rows: the stored rows `ids` as f32 [n, dim], removed rows included."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        rows = np.empty((len(ids), self.dim), dtype=np.float32)
+        r = self.lib.bert_hip_index_get_rows(self.ix, len(ids), _i32p(ids), _f32p(rows))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_get_rows failed: {r}")
+        return rows
+
+    def kmeans(self, n_lists: int, n_iter: int, centroids) -> np.ndarray:
+        """bert_hip_index_kmeans: n_iter steps of spherical k-means over the live rows from the initial centroids [n_lists, dim];
+        returns the refined centroids.  The index is unchanged."""
+        c = np.array(centroids, dtype=np.float32, order="C").reshape(n_lists, self.dim)
+        r = self.lib.bert_hip_index_kmeans(self.ix, n_lists, n_iter, _f32p(c))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_kmeans failed: {r}")
+        return c
+
+    def partition(self, centroids) -> None:
+        """bert_hip_index_partition: installs centroids [n_lists, dim] and assigns every current row to its nearest one; None or
+        an empty array drops the partition."""
+        c = np.zeros((0, self.dim), np.float32) if centroids is None else np.ascontiguousarray(centroids, dtype=np.float32).reshape(-1, self.dim)
+        r = self.lib.bert_hip_index_partition(self.ix, c.shape[0], _f32p(c))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_partition failed: {r}")
+
+    @property
+    def n_lists(self) -> int:
+        """the number of lists of the partition, 0 without one"""
+        return int(self.lib.bert_hip_index_n_lists(self.ix))
+
+    def centroids(self) -> np.ndarray:
+        """the partition's centroids [n_lists, dim] as installed"""
+        c = np.empty((max(self.n_lists, 0), self.dim), dtype=np.float32)
+        r = self.lib.bert_hip_index_partition_centroids(self.ix, _f32p(c))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_partition_centroids failed: {r}")
+        return c
+
+    def partition_lists(self) -> np.ndarray:
+        """the list of every row [len(index)] int32, -1 for the rows added since partition (the tail)"""
+        lists = np.empty(len(self), dtype=np.int32)
+        r = self.lib.bert_hip_index_partition_lists(self.ix, _i32p(lists))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_partition_lists failed: {r}")
+        return lists
+
+    def live_ids(self) -> np.ndarray:
+        """The ids a search can return, ascending.  With removed rows: found by rescoring every id against a zero query, 256
+        candidates per query (a removed row is skipped, every other finite row scores 0)."""
+        n = len(self)
+        if self.n_live == n:
+            return np.arange(n, dtype=np.int32)
+        cand = np.full((n + 255) // 256 * 256, -1, np.int32)
+        cand[:n] = np.arange(n, dtype=np.int32)
+        ids, _ = self.rescore(np.zeros((len(cand) // 256, self.dim), np.float32), cand.reshape(-1, 256), 256)
+        return np.sort(ids[ids >= 0])
+
+    def train_partition(self, n_lists: int, n_iter: int = 10, seed: int = 0) -> np.ndarray:
+        """Seeds the centroids with get_rows(numpy.random.default_rng(seed).choice(live_ids(), n_lists, replace=False)), refines
+        them with kmeans(n_lists, n_iter) and installs them with partition; returns the centroids."""
+        pick = np.random.default_rng(seed).choice(self.live_ids(), n_lists, replace=False)
+        c = self.kmeans(n_lists, n_iter, self.get_rows(pick))
+        self.partition(c)
+        return c
+
+    def search_probed(self, queries, k: int = 10, nprobe: int = 8):
+        """bert_hip_index_search_probed: the search over the rows of each query's nprobe nearest lists and the tail."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), dtype=np.int32)
+        scores = np.empty((q.shape[0], k), dtype=np.float32)
+        r = self.lib.bert_hip_index_search_probed(self.ix, q.shape[0], _f32p(q), nprobe, k, _i32p(ids), _f32p(scores))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search_probed failed: {r}")
+        return ids, scores
+
+    def search_probed_device(self, n_queries: int, d_queries_ptr: int, nprobe: int, k: int, d_ids_ptr: int, d_scores_ptr: int,
+                             stream: int = 0) -> None:
+        r = self.lib.bert_hip_index_search_probed_device(self.ix, n_queries, d_queries_ptr, nprobe, k, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search_probed_device failed: {r}")
 
     @property
     def n_live(self) -> int:

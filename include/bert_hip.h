@@ -241,6 +241,45 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  *            skipped), and 1 <= k <= n_cand <= 256; otherwise -2.  The result equals the two public calls chained by hand.
  *            search_rescored_device: asynchronous on `stream`; both indexes' events are honoured.  The same advice on
  *            allocation as for rescore holds (the coarse search's workspace is covered by coarse's reserve with k = n_cand).
+ * Reading rows back, cluster partition and probed search:
+ *   get_rows  rows[n][dim] = the stored rows ids[0 .. n) as f32, removed rows included: the bits (f32), the exact conversion
+ *            (f16), (float)code * scale with one rounding (i8; NaN for a row whose scale is NaN), +1.0 or -1.0 per bit (b1).
+ *            An id outside [0, size): -2, nothing written.  Blocking.  This is "the row" of partition and kmeans below.
+ *   partition   installs centroids[n_lists][dim] (host f32, every element finite or -2; 1 <= n_lists <= 65536; n_lists == 0
+ *            drops the partition) and assigns every current row, removed ones included, to one list.  The rule, through
+ *            public calls: the list of row r is the id that bert_hip_index_search returns with k = 1 on an f32 index that
+ *            holds the centroids as rows 0 .. n_lists - 1, queried with get_rows(r) — so equal scores go to the smaller list
+ *            id, by the order rule above; a row whose every score is NaN (the search returns -1) goes to list 0.  Blocking.
+ *            Storage stays in id order: ids, add, remove, save and every other search are untouched, and an index without a
+ *            partition launches what it always did.  n_lists: the number of lists, 0 without a partition, -1 without an
+ *            index.  partition_centroids: the centroids as installed, [n_lists][dim].  partition_lists: list_of_row[size],
+ *            -1 for an unassigned row; both -2 without a partition.
+ *            Rows added after partition (add, add_device, add_texts) are unassigned: they form the TAIL, which every probed
+ *            search scans in full; add_device does nothing for the partition, so it stays free of allocations and legal
+ *            under stream capture.  partition again, with the same or new centroids, assigns everything.  remove changes
+ *            nothing in the partition: the scan reads the live bits.  compact keeps the partition: each live row keeps its
+ *            list under its new id, the tail stays the tail.  The file format holds no partition, and a loaded index has
+ *            none: keep partition_centroids beside the file, and partition after the load restores the same lists, because
+ *            the assignment is a deterministic function of the stored rows and the centroids.
+ *   kmeans   spherical k-means over the LIVE rows as get_rows returns them; centroids[n_lists][dim]: in, the initial centroids
+ *            (finite, or -2; the caller seeds them), out, the refined ones.  Each of the n_iter >= 1 iterations assigns by
+ *            the rule of partition, then replaces each centroid by the f32 sum of its members divided by that sum's L2 norm;
+ *            a list without a live member, or whose sum has a zero or non-finite norm, keeps its centroid.  The sums are
+ *            taken in an order fixed by the members' positions (no atomics): the same input gives the same bits.  The index
+ *            (its rows, its partition) is unchanged.  Blocking.
+ *   search_probed   1 <= nprobe <= min(n_lists, 256), 1 <= k <= 256, no partition: -2; n_queries == 0 is a no-op.  Query q's
+ *            result has the ids and the score bits of bert_hip_index_search_filtered called with that one query and an
+ *            allow-list of exactly: the rows of the nprobe lists that bert_hip_index_search(k = nprobe) returns for q on the
+ *            f32 index of the centroids, plus every tail row.  Removed rows are skipped; slots beyond the qualifying rows are
+ *            -1 / -INFINITY.  A query holding a NaN or an inf probes no list (its centroid search returns only -1); the tail
+ *            is still scanned, as the filtered search would (i8, b1: only empty slots, as always).  With nprobe == n_lists
+ *            and no NaN the result equals bert_hip_index_search.  The determinism promises above hold: a query's result
+ *            depends neither on the other queries, nor on k, nor on the entry point.  search_probed_device: asynchronous on
+ *            `stream` under the one-event rule (the index's event and its centroid index's are both honoured); nothing
+ *            leaves the device between the centroid search, the scan of the lists (only k entries per list reach HBM) and
+ *            the merge.  The workspace ([n_queries][nprobe + ceil(tail / 1024)][k] entries, queries in internal chunks) is
+ *            not part of reserve and grows on demand, which allocates: call once at the largest shape before a stream
+ *            capture.
  * Errors of the functions that take an index: -1 no index, -2 bad arguments (after a line on stderr), -3 an error of the
  * index or the device (its message on stderr), -4 an exception.  Outputs are untouched on error.
  * File format (little-endian).  Header, 64 bytes: magic "BHIPIDX1" (8 bytes), u32 version = 1, u32 dtype (0 f32, 1 f16,
@@ -278,6 +317,16 @@ BERT_API int32_t bert_hip_index_search_rescored(struct bert_hip_index *coarse, s
 BERT_API int32_t bert_hip_index_search_rescored_device(struct bert_hip_index *coarse, struct bert_hip_index *fine, int32_t n_queries,
                                                        const float *d_queries, int32_t n_cand, int32_t k, int32_t *d_ids,
                                                        float *d_scores, void *stream);
+BERT_API int32_t bert_hip_index_get_rows(struct bert_hip_index *ix, int32_t n, const int32_t *ids, float *rows);
+BERT_API int32_t bert_hip_index_partition(struct bert_hip_index *ix, int32_t n_lists, const float *centroids);
+BERT_API int32_t bert_hip_index_n_lists(struct bert_hip_index *ix);
+BERT_API int32_t bert_hip_index_partition_centroids(struct bert_hip_index *ix, float *centroids);
+BERT_API int32_t bert_hip_index_partition_lists(struct bert_hip_index *ix, int32_t *list_of_row);
+BERT_API int32_t bert_hip_index_kmeans(struct bert_hip_index *ix, int32_t n_lists, int32_t n_iter, float *centroids);
+BERT_API int32_t bert_hip_index_search_probed(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t nprobe,
+                                              int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_index_search_probed_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries,
+                                                     int32_t nprobe, int32_t k, int32_t *d_ids, float *d_scores, void *stream);
 BERT_API int32_t bert_hip_index_compact(struct bert_hip_index *ix, int32_t *old_ids);
 BERT_API int32_t bert_hip_index_save(struct bert_hip_index *ix, const char *path);
 BERT_API struct bert_hip_index *bert_hip_index_load(struct bert_ctx *ctx, const char *path);

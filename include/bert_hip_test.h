@@ -133,6 +133,11 @@ BERT_API int32_t bert_hip_test_tokenize_pack(struct bert_ctx *ctx, int32_t n_thr
 BERT_API int32_t bert_hip_test_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err,
                                             int32_t err_cap);
 
+/* The list tables of a partitioned index (partition.h build_lists; bert_hip.h "cluster partition"): offsets[n_lists + 1] and
+ * order[up to n] from list_of[n] by a stable counting sort, entries outside [0, n_lists) in no list.  Returns the number of
+ * entries written to order, -1 for bad arguments.  No device.                                                               */
+BERT_API int32_t bert_hip_test_build_lists(const int32_t *list_of, int32_t n, int32_t n_lists, int32_t *offsets, int32_t *order);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,12 @@ comparison of two builds).
 Section "rescore" (not part of the default; 10^6 rows, dims 384 and 768, Q = 1 and 4096, k = 10): the b1 search, the two-stage
 search b1(100) -> i8 (bert_hip_index_search_rescored_device) and the plain i8 search, from the same run on the same box, each as
 median (min .. max), and the share of the two-stage answers' ids that the plain i8 search also returns.
+
+Section "probe" (not part of the default; a clustered corpus of 10^6 rows — 4096 random centres, unit rows of centre + noise —,
+dim 384, f16 and i8 rows, n_lists = 1024, Q = 1 and 4096, k = 10): the time of BertIndex.train_partition, then the plain search
+and the probed search (bert_hip_index_search_probed_device) with nprobe = 1, 8, 32, 128 from the same run, each as median
+(min .. max) and as a ratio to the plain line, with recall@10 against the plain search's ids beside it.
+    python tools/search_rate.py --sections probe --out profiles/search_probe_rate.txt
 """
 import argparse
 import os
@@ -144,6 +150,47 @@ def rescore_section(a, m, N, out, timed, torch, dev, sp):
         torch.cuda.empty_cache()
 
 
+def probe_section(a, m, N, out, timed, torch, dev, sp):
+    """the plain search and the probed search of a partitioned index side by side, with the recall of the probed one"""
+    dim, k, n_lists, n_centres, sigma = 384, 10, 1024, 4096, 0.04
+    out(f"# search_probed_device against search_device, N = {N} rows in {n_centres} clusters (unit rows of centre + {sigma} * noise), dim {dim}, "
+        f"n_lists = {n_lists}, k = {k}; ms = median (min .. max) of {a.iters}; recall@{k} against the plain search's ids")
+    out("# dtype     Q  call            |      ms (min .. max)        x plain   queries/s   recall")
+    g = torch.Generator(device=dev).manual_seed(dim)
+    centres = torch.randn(n_centres, dim, device=dev, generator=g)
+    centres /= centres.norm(dim=1, keepdim=True)
+
+    def draw(n):
+        x = centres[torch.randint(0, n_centres, (n,), device=dev, generator=g)] + sigma * torch.randn(n, dim, device=dev, generator=g)
+        return x / x.norm(dim=1, keepdim=True)
+
+    C, Qall = draw(N), draw(4096)
+    for dtype in ("f16", "i8"):
+        ix = m.index(dim=dim, dtype=dtype)
+        ix.reserve(N, 4096, k)
+        ix.add_device(N, C.data_ptr(), sp)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ix.train_partition(n_lists, n_iter=10, seed=0)
+        lens = np.bincount(ix.partition_lists(), minlength=n_lists)
+        out(f"# {dtype}: train_partition({n_lists}, n_iter=10) {time.perf_counter() - t0:.2f} s; list lengths min {lens.min()}, "
+            f"median {int(np.median(lens))}, max {lens.max()}")
+        for Q in (1, 4096):
+            q = Qall[:Q].contiguous()
+            ids = torch.empty(Q, k, dtype=torch.int32, device=dev)
+            pid = torch.empty(Q, k, dtype=torch.int32, device=dev)
+            sc = torch.empty(Q, k, dtype=torch.float32, device=dev)
+            base, lo, hi = timed(lambda: ix.search_device(Q, q.data_ptr(), k, ids.data_ptr(), sc.data_ptr(), sp))
+            want = ids.cpu().numpy()
+            out(f"{dtype:7s} {Q:5d}  {'search':15s} | {base:8.3f} ({lo:7.3f} .. {hi:7.3f})  {1.0:6.2f} {Q / (base * 1e-3):11.0f}   1.000")
+            for nprobe in (1, 8, 32, 128):
+                t, lo, hi = timed(lambda: ix.search_probed_device(Q, q.data_ptr(), nprobe, k, pid.data_ptr(), sc.data_ptr(), sp))
+                got = pid.cpu().numpy()
+                recall = np.mean([len(set(x.tolist()) & set(y.tolist())) / k for x, y in zip(got, want)])
+                out(f"{dtype:7s} {Q:5d}  {'nprobe = %d' % nprobe:15s} | {t:8.3f} ({lo:7.3f} .. {hi:7.3f})  {t / base:6.2f} {Q / (t * 1e-3):11.0f}   {recall:.3f}")
+        ix.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -261,6 +308,9 @@ def main():
 
     if "rescore" in sections:
         rescore_section(a, m, N, out, timed, torch, dev, sp)
+
+    if "probe" in sections:
+        probe_section(a, m, N, out, timed, torch, dev, sp)
 
     # strings in, index rows out: add_texts against encode_batch + add
     if "texts" in sections:
