@@ -16,7 +16,8 @@
 // k order inside a group of 16 included: GemmWeight::w16p for the feed-forward), the same initial accumulator values
 // (x + bo; b1; y + b2 resp. b2 with y added at the end for the features layer_tail's U wave owns), the same packed-f16
 // GELU on the same element pairs, and LayerNorm statistics summed in the order layer_tail's lanes and wave pairs sum them.
-// tests/test_gpu_parity.py::test_latency_route_gives_the_batch_route_s_bits holds the two routes against each other.
+// tests/test_gpu_parity.py::test_latency_route_gives_the_batch_route_s_bits holds the two routes against each other; kernel by
+// kernel (every width's pipeline start and end, token-block edges, padding rows, float64) tests/test_gpu_latency_kernels.py does.
 #include "device.h"
 
 namespace bert_hip {
@@ -42,8 +43,9 @@ struct SkinnyArgs {
 
 }  // namespace
 
-// grid = (N / 32 feature tiles, token blocks), block = 128 or 256: ONE wave of the workgroup owns 32 tokens x 32 features (up to
-// 192 workgroups at once for a 128-token sentence), the others only request their share of the LDS-DMA pieces.  The tile's weight rows (32 x K halfs = 24 .. 96 KiB, one contiguous block)
+// grid = (N / 32 feature tiles, token blocks), block = 512 (launch_skinny_gemm): ONE wave of the workgroup owns 32 tokens x 32
+// features (up to 192 workgroups at once for a 128-token sentence), the other seven only request their share of the LDS-DMA pieces.
+// The tile's weight rows (32 x K halfs = 16 .. 160 KiB, one contiguous block)
 // come in by LDS-DMA in one round trip — fully coalesced 1 KiB pieces, the 16-byte chunk of a row XOR-swizzled on the
 // source side so that the fragment reads are conflict-free.  The token operand:
 //   LN == 0: 16-byte fragments straight from HBM / L2 (x in the first layer, ctx, the intermediate in fragment order);

@@ -22,6 +22,52 @@ using namespace bert_hip;
         }                                                                              \
     } while (0)
 
+// skinny_layer_supported judges a whole layer.  An entry that holds only some of its matrices passes stand-ins for the others:
+// `like`'s type and image pointers (that they are there is all the predicate asks of them) under the shape a layer gives them.
+static GemmWeight stand_in(const GemmWeight &like, int N, int K) {
+    GemmWeight w = like;
+    w.N = w.N_pad = N; w.K = K; w.w16p = like.w16;
+    return w;
+}
+static bool skinny_qkv_supported(const GemmWeight &Wqkv) {
+    const int H = Wqkv.K;
+    return skinny_layer_supported(Wqkv, stand_in(Wqkv, H, H), stand_in(Wqkv, 4 * H, H), stand_in(Wqkv, H, 4 * H));
+}
+
+// rows [M][cols] of 16- or 32-bit words -> device rows [M_pad][cols], rows M .. M_pad - 1 filled with `pad` (the kernels compute
+// whole token blocks, and in a reused workspace those rows hold whatever the call before left); src == nullptr: all rows `pad`
+template <class T>
+static bool upload_padded(DevBuf &d, const T *src, int M, int M_pad, int cols, T pad, std::string &err) {
+    std::vector<T> h((size_t)M_pad * cols, pad);
+    if (src) memcpy(h.data(), src, (size_t)M * cols * sizeof(T));
+    return d.upload(h, err);
+}
+
+// the matrices and parameter vectors of a layer tail on the device, from file-layout bytes (W1, W2 also in the k order of w16p)
+struct TailOperands {
+    GemmWeightStore wo, w1, w2;
+    DevBuf bo, g1, be1, b1, b2, g2, be2;
+    // 0; -1 with a line on stderr; -2: a matrix the MFMA kernels do not take
+    int build(const char *me, int H, int I, const void *Wo, const void *W1, const void *W2, int32_t wtype, const float *bo_, const float *g1_,
+              const float *be1_, const float *b1_, const float *b2_, const float *g2_, const float *be2_) {
+        std::string err;
+        HostTensor to, t1, t2;
+        to.type = wtype; to.n_dims = 2; to.ne0 = H; to.ne1 = H; to.data = (const uint8_t *)Wo; to.nbytes = wtype_row_bytes(wtype, H) * (size_t)H;
+        t1.type = wtype; t1.n_dims = 2; t1.ne0 = H; t1.ne1 = I; t1.data = (const uint8_t *)W1; t1.nbytes = wtype_row_bytes(wtype, H) * (size_t)I;
+        t2.type = wtype; t2.n_dims = 2; t2.ne0 = I; t2.ne1 = H; t2.data = (const uint8_t *)W2; t2.nbytes = wtype_row_bytes(wtype, I) * (size_t)H;
+        PackOptions kperm;
+        kperm.kperm = true;
+        if (!wo.build({&to}, PackOptions(), err) || !w1.build({&t1}, kperm, err) || !w2.build({&t2}, kperm, err) ||
+            !bo.upload(bo_, (size_t)H * 4, err) || !g1.upload(g1_, (size_t)H * 4, err) || !be1.upload(be1_, (size_t)H * 4, err) ||
+            !b1.upload(b1_, (size_t)I * 4, err) || !b2.upload(b2_, (size_t)H * 4, err) || !g2.upload(g2_, (size_t)H * 4, err) ||
+            !be2.upload(be2_, (size_t)H * 4, err)) {
+            fprintf(stderr, "%s: %s\n", me, err.c_str());
+            return -1;
+        }
+        return wo.mfma_ok && w1.mfma_ok && w2.mfma_ok ? 0 : -2;
+    }
+};
+
 extern "C" {
 
 int32_t bert_hip_test_gemm(int32_t M, int32_t N, int32_t K, const uint16_t *A, const void *W, int32_t wtype,
@@ -180,6 +226,13 @@ int32_t bert_hip_test_qkv_attention(int32_t n_sentences, const int32_t *cu_seqle
                               window_slots(), dout.as<half_t>(), nullptr);
         CK(hipGetLastError());
         CK(hipDeviceSynchronize());
+    } else if (fused == 5) {
+        // the first half of a latency-route layer as Engine::forward_latency chains it (first layer: x comes as f16 rows)
+        if (!skinny_qkv_supported(ws.w)) return -2;
+        launch_skinny_gemm(0, ws.w, dx.as<half_t>(), nullptr, nullptr, nullptr, dx.as<half_t>(), db.as<float>(), nullptr, dqkv.as<half_t>(), nullptr,
+                           (T + 31) / 32, nullptr);
+        if (!launch_attention_mfma(dqkv.as<half_t>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<half_t>(), nullptr))
+            return -2;
     } else {
         launch_gemm_mfma(ws.w, dx.as<half_t>(), db.as<float>(), nullptr, dqkv.as<half_t>(), T_pad, EPI_BIAS, nullptr);
         if (!launch_attention_mfma(dqkv.as<half_t>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<half_t>(), nullptr))
@@ -196,47 +249,103 @@ int32_t bert_hip_test_layer_tail(int32_t M, int32_t H, int32_t I, const uint16_t
                                  const float *be1, const float *b1, const float *b2, const float *g2, const float *be2,
                                  int32_t impl, uint16_t *out) {
     std::string err;
-    HostTensor to, t1, t2;
-    to.type = wtype; to.n_dims = 2; to.ne0 = H; to.ne1 = H; to.data = (const uint8_t *)Wo; to.nbytes = wtype_row_bytes(wtype, H) * (size_t)H;
-    t1.type = wtype; t1.n_dims = 2; t1.ne0 = H; t1.ne1 = I; t1.data = (const uint8_t *)W1; t1.nbytes = wtype_row_bytes(wtype, H) * (size_t)I;
-    t2.type = wtype; t2.n_dims = 2; t2.ne0 = I; t2.ne1 = H; t2.data = (const uint8_t *)W2; t2.nbytes = wtype_row_bytes(wtype, I) * (size_t)H;
-    GemmWeightStore wo, w1, w2;
-    PackOptions kperm;
-    kperm.kperm = true;
-    if (!wo.build({&to}, PackOptions(), err) || !w1.build({&t1}, kperm, err) || !w2.build({&t2}, kperm, err)) {
-        fprintf(stderr, "bert_hip_test_layer_tail: %s\n", err.c_str());
-        return -1;
-    }
-    if (!wo.mfma_ok || !w1.mfma_ok || !w2.mfma_ok) return -2;
+    TailOperands w;
+    if (const int r = w.build("bert_hip_test_layer_tail", H, I, Wo, W1, W2, wtype, bo, g1, be1, b1, b2, g2, be2)) return r;
     const int M_pad = (M + GEMM_BM - 1) / GEMM_BM * GEMM_BM;
-    DevBuf dc, dx, dy, dout, dbo, dg1, dbe1, db1, db2, dg2, dbe2;
+    DevBuf dc, dx, dy, dout;
     if (!dc.alloc((size_t)M_pad * H * 2, err) || !dx.alloc((size_t)M_pad * H * 2, err) || !dy.alloc((size_t)M_pad * H * 2, err) ||
-        !dout.alloc((size_t)M_pad * H * 2, err) || !dbo.upload(bo, (size_t)H * 4, err) || !dg1.upload(g1, (size_t)H * 4, err) ||
-        !dbe1.upload(be1, (size_t)H * 4, err) || !db1.upload(b1, (size_t)I * 4, err) || !db2.upload(b2, (size_t)H * 4, err) ||
-        !dg2.upload(g2, (size_t)H * 4, err) || !dbe2.upload(be2, (size_t)H * 4, err)) {
+        !dout.alloc((size_t)M_pad * H * 2, err)) {
         fprintf(stderr, "bert_hip_test_layer_tail: %s\n", err.c_str());
         return -1;
     }
     CK(hipMemcpy(dc.p, ctx, (size_t)M * H * 2, hipMemcpyHostToDevice));
     CK(hipMemcpy(dx.p, x, (size_t)M * H * 2, hipMemcpyHostToDevice));
     if (impl == 1) {
-        if (!layer_tail_supported(wo.w, w1.w, w2.w)) return -2;
-        launch_layer_tail(wo.w, w1.w, w2.w, dc.as<half_t>(), dx.as<half_t>(), dbo.as<float>(), dg1.as<float>(), dbe1.as<float>(),
-                          db1.as<float>(), db2.as<float>(), dg2.as<float>(), dbe2.as<float>(), dout.as<half_t>(), M_pad, nullptr);
+        if (!layer_tail_supported(w.wo.w, w.w1.w, w.w2.w)) return -2;
+        launch_layer_tail(w.wo.w, w.w1.w, w.w2.w, dc.as<half_t>(), dx.as<half_t>(), w.bo.as<float>(), w.g1.as<float>(), w.be1.as<float>(),
+                          w.b1.as<float>(), w.b2.as<float>(), w.g2.as<float>(), w.be2.as<float>(), dout.as<half_t>(), M_pad, nullptr);
     } else {
         // three GEMM kernels + two LayerNorm kernels
         DevBuf dff;
         if (!dff.alloc((size_t)M_pad * I * 2, err)) return -1;
-        launch_gemm_mfma(wo.w, dc.as<half_t>(), dbo.as<float>(), dx.as<half_t>(), dy.as<half_t>(), M_pad, EPI_BIAS_RESID, nullptr);
-        launch_layernorm(dy.as<half_t>(), dg1.as<float>(), dbe1.as<float>(), M_pad, H, nullptr);
-        launch_gemm_mfma(w1.w, dy.as<half_t>(), db1.as<float>(), nullptr, dff.as<half_t>(), M_pad, EPI_BIAS_GELU, nullptr);
-        launch_gemm_mfma(w2.w, dff.as<half_t>(), db2.as<float>(), dy.as<half_t>(), dout.as<half_t>(), M_pad, EPI_BIAS_RESID, nullptr);
-        launch_layernorm(dout.as<half_t>(), dg2.as<float>(), dbe2.as<float>(), M_pad, H, nullptr);
+        launch_gemm_mfma(w.wo.w, dc.as<half_t>(), w.bo.as<float>(), dx.as<half_t>(), dy.as<half_t>(), M_pad, EPI_BIAS_RESID, nullptr);
+        launch_layernorm(dy.as<half_t>(), w.g1.as<float>(), w.be1.as<float>(), M_pad, H, nullptr);
+        launch_gemm_mfma(w.w1.w, dy.as<half_t>(), w.b1.as<float>(), nullptr, dff.as<half_t>(), M_pad, EPI_BIAS_GELU, nullptr);
+        launch_gemm_mfma(w.w2.w, dff.as<half_t>(), w.b2.as<float>(), dy.as<half_t>(), dout.as<half_t>(), M_pad, EPI_BIAS_RESID, nullptr);
+        launch_layernorm(dout.as<half_t>(), w.g2.as<float>(), w.be2.as<float>(), M_pad, H, nullptr);
         CK(hipDeviceSynchronize());
     }
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(out, dout.p, (size_t)M * H * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int32_t bert_hip_test_skinny_tail(int32_t M, int32_t H, int32_t I, const uint16_t *ctx, const uint16_t *x, const void *Wo, const void *W1,
+                                  const void *W2, int32_t wtype, const float *bo, const float *g1, const float *be1, const float *b1,
+                                  const float *b2, const float *g2, const float *be2, uint32_t pad, uint16_t *out, float *v_proj,
+                                  uint16_t *y, uint16_t *ff, float *v_down) {
+    std::string err;
+    TailOperands w;
+    if (const int r = w.build("bert_hip_test_skinny_tail", H, I, Wo, W1, W2, wtype, bo, g1, be1, b1, b2, g2, be2)) return r;
+    if (!skinny_layer_supported(stand_in(w.wo.w, 3 * H, H), w.wo.w, w.w1.w, w.w2.w)) return -2;
+    const int M_pad = (M + GEMM_BM - 1) / GEMM_BM * GEMM_BM, tb = (M + 31) / 32;
+    DevBuf dc, dx, dy, dff, dv;
+    if (!upload_padded(dc, ctx, M, M_pad, H, (uint16_t)pad, err) || !upload_padded(dx, x, M, M_pad, H, (uint16_t)pad, err) ||
+        !dy.alloc((size_t)M_pad * H * 2, err) || !dff.alloc((size_t)M_pad * I * 2, err) || !dv.alloc((size_t)M_pad * H * 4, err)) {
+        fprintf(stderr, "bert_hip_test_skinny_tail: %s\n", err.c_str());
+        return -1;
+    }
+    half_t *xd = dx.as<half_t>(), *yd = dy.as<half_t>(), *ffd = dff.as<half_t>();
+    float *v32 = dv.as<float>();
+    // (Engine::forward_latency's launches and arguments; the f32 rows of both residual mat-muls share one buffer there)
+    launch_skinny_gemm(1, w.wo.w, dc.as<half_t>(), nullptr, nullptr, nullptr, nullptr, w.bo.as<float>(), xd, nullptr, v32, tb, nullptr);
+    if (v_proj) {
+        CK(hipGetLastError());
+        CK(hipMemcpy(v_proj, v32, (size_t)M * H * 4, hipMemcpyDeviceToHost));
+    }
+    launch_skinny_gemm(2, w.w1.w, nullptr, v32, w.g1.as<float>(), w.be1.as<float>(), yd, w.b1.as<float>(), nullptr, ffd, nullptr, tb, nullptr);
+    launch_skinny_gemm(3, w.w2.w, ffd, nullptr, nullptr, nullptr, nullptr, w.b2.as<float>(), yd, nullptr, v32, tb, nullptr);
+    if (v_down) {
+        CK(hipGetLastError());
+        CK(hipMemcpy(v_down, v32, (size_t)M * H * 4, hipMemcpyDeviceToHost));
+    }
+    launch_skinny_layernorm(v32, w.g2.as<float>(), w.be2.as<float>(), xd, tb, H, nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, xd, (size_t)M * H * 2, hipMemcpyDeviceToHost));
+    if (y) CK(hipMemcpy(y, yd, (size_t)M * H * 2, hipMemcpyDeviceToHost));
+    if (ff) CK(hipMemcpy(ff, ffd, (size_t)M * I * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int32_t bert_hip_test_skinny_qkv(int32_t M, int32_t H, const uint16_t *x, const float *V, const float *gamma, const float *beta,
+                                 const void *Wqkv, int32_t wtype, const float *bias, uint32_t pad, uint16_t *qkv, uint16_t *ln_out) {
+    std::string err;
+    if ((V == nullptr) == (x == nullptr) || (V && (!gamma || !beta || !ln_out))) return -1;
+    HostTensor t;
+    t.type = wtype; t.n_dims = 2; t.ne0 = H; t.ne1 = 3 * H; t.data = (const uint8_t *)Wqkv;
+    t.nbytes = wtype_row_bytes(wtype, H) * (size_t)3 * H;
+    GemmWeightStore ws;
+    if (!ws.build({&t}, PackOptions(), err)) { fprintf(stderr, "bert_hip_test_skinny_qkv: %s\n", err.c_str()); return -1; }
+    if (!ws.mfma_ok || !skinny_qkv_supported(ws.w)) return -2;
+    const int M_pad = (M + GEMM_BM - 1) / GEMM_BM * GEMM_BM, tb = (M + 31) / 32;
+    DevBuf dx, dv, dg, dbe, db, dqkv;
+    // (the LayerNorm-fused form writes x: the rows are its ln_out, as in the engine)
+    if (!upload_padded(dx, x, M, M_pad, H, (uint16_t)(V ? 0 : pad), err) || !dqkv.alloc((size_t)M_pad * 3 * H * 2, err) ||
+        !db.upload(bias, (size_t)3 * H * 4, err) ||
+        (V && (!upload_padded(dv, (const uint32_t *)V, M, M_pad, H, pad, err) || !dg.upload(gamma, (size_t)H * 4, err) ||
+               !dbe.upload(beta, (size_t)H * 4, err)))) {
+        fprintf(stderr, "bert_hip_test_skinny_qkv: %s\n", err.c_str());
+        return -1;
+    }
+    half_t *xd = dx.as<half_t>();
+    launch_skinny_gemm(0, ws.w, xd, V ? dv.as<float>() : nullptr, V ? dg.as<float>() : nullptr, V ? dbe.as<float>() : nullptr, xd,
+                       db.as<float>(), nullptr, dqkv.as<half_t>(), nullptr, tb, nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(qkv, dqkv.p, (size_t)M * 3 * H * 2, hipMemcpyDeviceToHost));
+    if (V) CK(hipMemcpy(ln_out, xd, (size_t)M * H * 2, hipMemcpyDeviceToHost));
     return 0;
 }
 

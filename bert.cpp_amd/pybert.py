@@ -36,7 +36,7 @@ BERT_HIP_H_SYMBOLS = [
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_gemm", "bert_hip_test_gemm_lnfold", "bert_hip_test_attention", "bert_hip_test_qkv_attention",
-    "bert_hip_test_layer_tail", "bert_hip_test_shard_bounds", "bert_hip_test_build_windows",
+    "bert_hip_test_layer_tail", "bert_hip_test_skinny_tail", "bert_hip_test_skinny_qkv", "bert_hip_test_shard_bounds", "bert_hip_test_build_windows",
     "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots",
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
     "bert_hip_test_pool",
@@ -163,6 +163,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_qkv_attention.argtypes = [i32, i32p, i32, i32, vp, vp, i32, vp, i32, vp]
     L.bert_hip_test_layer_tail.restype = i32
     L.bert_hip_test_layer_tail.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    L.bert_hip_test_skinny_tail.restype = i32
+    L.bert_hip_test_skinny_tail.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.bert_hip_test_skinny_qkv.restype = i32
+    L.bert_hip_test_skinny_qkv.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, vp, C.c_uint32, vp, vp]
     L.bert_hip_test_embed_ln.restype = i32
     L.bert_hip_test_embed_ln.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32p, i32p, i32, vp]
     L.bert_hip_test_pool_normalize.restype = i32
@@ -866,3 +870,46 @@ def test_layer_tail(ctx: np.ndarray, x: np.ndarray, Wo_bytes, W1_bytes, W2_bytes
     if r != 0:
         raise RuntimeError(f"bert_hip_test_layer_tail failed: {r}")
     return out
+
+
+def test_skinny_tail(ctx: np.ndarray, x: np.ndarray, Wo_bytes, W1_bytes, W2_bytes, wtype: int, I: int, bo, g1, be1, b1, b2,
+                     g2, be2, pad: int = 0, parts: bool = False):
+    """test_layer_tail's operation through the latency route's kernels; pad: the 16-bit pattern in the padding rows of ctx and x.
+    parts: returns (out, {"v_proj" f32 [M][H], "y" f16 [M][H], "ff" f16 [M][I] in fragment order, "v_down" f32 [M][H]})."""
+    L = test_lib()
+    ctx = np.ascontiguousarray(ctx, dtype=np.float16)
+    x = np.ascontiguousarray(x, dtype=np.float16)
+    M, H = ctx.shape
+    ws = [np.ascontiguousarray(w) for w in (Wo_bytes, W1_bytes, W2_bytes)]
+    ps = [np.ascontiguousarray(v, dtype=np.float32) for v in (bo, g1, be1, b1, b2, g2, be2)]
+    out = np.zeros((M, H), dtype=np.float16)
+    mid = {"v_proj": np.zeros((M, H), dtype=np.float32), "y": np.zeros((M, H), dtype=np.float16),
+           "ff": np.zeros((M, I), dtype=np.float16), "v_down": np.zeros((M, H), dtype=np.float32)} if parts else {}
+    r = L.bert_hip_test_skinny_tail(M, H, I, ctx.ctypes.data, x.ctypes.data, ws[0].ctypes.data, ws[1].ctypes.data, ws[2].ctypes.data,
+                                    wtype, *[p.ctypes.data for p in ps], pad, out.ctypes.data,
+                                    *[mid[k].ctypes.data if parts else None for k in ("v_proj", "y", "ff", "v_down")])
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_skinny_tail failed: {r}")
+    return (out, mid) if parts else out
+
+
+def test_skinny_qkv(W_bytes: np.ndarray, wtype: int, bias: np.ndarray, x: Optional[np.ndarray] = None, V: Optional[np.ndarray] = None,
+                    gamma=None, beta=None, pad: int = 0):
+    """The latency route's Q|K|V projection of x [M][H] f16 -> qkv [M][3H] f16, or of LayerNorm(V [M][H] f32; gamma, beta), which the
+    kernel computes itself -> (qkv, the normalised rows [M][H] f16).  pad: the 16-bit (x) / 32-bit (V) pattern of the padding rows."""
+    L = test_lib()
+    w = np.ascontiguousarray(W_bytes)
+    bias = np.ascontiguousarray(bias, dtype=np.float32)
+    rows = np.ascontiguousarray(x, dtype=np.float16) if V is None else np.ascontiguousarray(V, dtype=np.float32)
+    M, H = rows.shape
+    qkv = np.zeros((M, 3 * H), dtype=np.float16)
+    if V is None:
+        r = L.bert_hip_test_skinny_qkv(M, H, rows.ctypes.data, None, None, None, w.ctypes.data, wtype, bias.ctypes.data, pad, qkv.ctypes.data, None)
+    else:
+        g = np.ascontiguousarray(gamma, dtype=np.float32); b = np.ascontiguousarray(beta, dtype=np.float32)
+        ln_out = np.zeros((M, H), dtype=np.float16)
+        r = L.bert_hip_test_skinny_qkv(M, H, None, rows.ctypes.data, g.ctypes.data, b.ctypes.data, w.ctypes.data, wtype, bias.ctypes.data, pad,
+                                       qkv.ctypes.data, ln_out.ctypes.data)
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_skinny_qkv failed: {r}")
+    return qkv if V is None else (qkv, ln_out)

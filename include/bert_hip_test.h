@@ -40,7 +40,8 @@ BERT_API int32_t bert_hip_test_attention(int32_t n_sentences, const int32_t *cu_
 /* Q|K|V projection + attention: x[T][H] f16 bits, Wqkv [3H][H] (Q rows, K rows, V rows) in file layout of `wtype`,
  * bias[3H] -> ctx[T][H] f16 bits (reference bert.cpp:822-856).  fused: 0 = GEMM kernel + attention kernel; the window kernel
  * (qkv_attention2.hip; -2 if the shape is not supported) with 2 = next-fit windows built on the host, 3 = the uniform
- * placement rule, 4 = next-fit windows built on the device.                                                               */
+ * placement rule, 4 = next-fit windows built on the device; 5 = the first half of a latency-route layer: the feature-split
+ * projection kernel (skinny.hip, x as f16 rows) + the attention kernel (-2 unless the latency route takes the shape).       */
 BERT_API int32_t bert_hip_test_qkv_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head,
                                              int32_t d_head, const uint16_t *x, const void *Wqkv, int32_t wtype,
                                              const float *bias, int32_t fused, uint16_t *out);
@@ -55,6 +56,26 @@ BERT_API int32_t bert_hip_test_layer_tail(int32_t M, int32_t H, int32_t I, const
                                           const float *bo, const float *g1, const float *be1, const float *b1,
                                           const float *b2, const float *g2, const float *be2, int32_t impl,
                                           uint16_t *out);
+
+/* The same layer tail through the kernels of the latency route (skinny.hip), launched as Engine::forward_latency launches them:
+ * out-projection, up-projection with LayerNorm 1, down-projection, LayerNorm 2, on ceil(M / 32) token blocks.  Inputs as above
+ * (-2 unless skinny_layer_supported takes the matrices).  pad: the 16-bit pattern rows M .. M_pad - 1 of the ctx and x buffers
+ * hold (M_pad: M rounded up to 128; the kernels compute whole blocks of 32 tokens and read those rows).  Besides out [M][H],
+ * each unless NULL: v_proj f32 [M][H] = ctx Wo^T + bo + x, y f16 [M][H] = LayerNorm 1 of it, ff f16 [M][I] = gelu(y W1^T + b1)
+ * in the kernels' fragment order (inside every group of 16 features the runs of 4 sit at [0-3, 8-11, 4-7, 12-15]),
+ * v_down f32 [M][H] = ff W2^T + b2 + y.                                                                                      */
+BERT_API int32_t bert_hip_test_skinny_tail(int32_t M, int32_t H, int32_t I, const uint16_t *ctx, const uint16_t *x, const void *Wo,
+                                           const void *W1, const void *W2, int32_t wtype, const float *bo, const float *g1,
+                                           const float *be1, const float *b1, const float *b2, const float *g2, const float *be2,
+                                           uint32_t pad, uint16_t *out, float *v_proj, uint16_t *y, uint16_t *ff, float *v_down);
+
+/* The Q|K|V projection of the latency route: qkv [M][3H] f16 bits = rows Wqkv^T + bias, Wqkv [3H][H] in file layout of `wtype`.
+ * Exactly one of x and V: the rows are x [M][H] f16 bits (the first layer's form), or LayerNorm(V [M][H] f32; gamma, beta), which
+ * the kernel computes itself and also writes to ln_out [M][H] f16 bits (every later layer's form).  pad: what rows M .. M_pad - 1
+ * of the x or V buffer hold, a 16-bit resp. 32-bit pattern.  -2 unless the latency route takes the shape.                      */
+BERT_API int32_t bert_hip_test_skinny_qkv(int32_t M, int32_t H, const uint16_t *x, const float *V, const float *gamma,
+                                          const float *beta, const void *Wqkv, int32_t wtype, const float *bias, uint32_t pad,
+                                          uint16_t *qkv, uint16_t *ln_out);
 
 /* Embedding gather-sum + LayerNorm (reference bert.cpp:796-814): tables in the file layout of `table_type` (0 f32, 1 f16,
  * 2 q4_0, 3 q4_1), word [n_vocab][H], type [2][H], pos [n_pos][H]; packed sentences; out [T][H] f16 bits.               */

@@ -14,6 +14,7 @@ from bert_cpp_amd import ggml_file as gf
 from bert_cpp_amd import pybert
 from oracle import oracle as orc
 
+import layer_reference
 from conftest import GOLDEN, cosine
 
 pytestmark = pytest.mark.gpu
@@ -199,18 +200,7 @@ def test_layer_tail_kernel(M, H, I, impl=1):
     b1 = rng.normal(0, 0.5, I)
     g1, g2 = 1 + rng.normal(0, 0.1, H), 1 + rng.normal(0, 0.1, H)
     be1, be2 = rng.normal(0, 0.1, H), rng.normal(0, 0.1, H)
-
-    def ln(v, g, b):
-        mu = v.mean(axis=1, keepdims=True)
-        var = ((v - mu) ** 2).mean(axis=1, keepdims=True)
-        return (v - mu) / np.sqrt(var + 1e-5) * g + b
-
-    f8 = lambda a: a.astype(np.float64)
-    y = ln(f8(ctx) @ f8(Wo).T + bo + f8(x), g1, be1)
-    y16 = f8(y.astype(np.float16))                       # the device keeps y in f16 (GEMM input and residual)
-    u = y16 @ f8(W1).T + b1
-    gl = 0.5 * u * (1 + np.tanh(0.7978845608028654 * u * (1 + 0.044715 * u * u)))
-    want = ln(f8(gl.astype(np.float16)) @ f8(W2).T + b2 + y16, g2, be2)
+    want = layer_reference.layer_tail(ctx, x, Wo, W1, W2, bo, g1, be1, b1, b2, g2, be2)
 
     args = (ctx, x, Wo.view(np.uint8), W1.view(np.uint8), W2.view(np.uint8), 1, I, bo, g1, be1, b1, b2, g2, be2)
     base = pybert.test_layer_tail(*args, 0).astype(np.float64)
