@@ -18,15 +18,15 @@ namespace {
 // What the host knows of a row form, by dtype (the device's side of it: ScoreBlock<T> in search.hip; the bytes of a stored
 // row: index_file.h).  The names are the profiler's; ingest is the kernel that makes the stored form of f32 rows.
 struct FormInfo {
-    const char *topk[2], *rescore, *probe, *exported, *ingest;      // topk[1]: the masked instantiation
+    const char *topk[2], *rescore, *probe, *probe_masked, *exported, *ingest;      // topk[1], probe_masked: the masked instantiations
     bool has_rscale;                             // one f32 scale per row beside the rows
     bool quantized_queries;                      // queries are stored as rows of the i8 form (codes and a scale), else of this one
 };
 constexpr FormInfo FORMS[4] = {
-    {{"index_topk_f32", "index_topk_f32_masked"}, "index_rescore_f32", "index_probe_f32", "index_export_f32", "index_convert_f32", false, false},
-    {{"index_topk_f16", "index_topk_f16_masked"}, "index_rescore_f16", "index_probe_f16", "index_export_f16", "index_convert_f16", false, false},
-    {{"index_topk_i8", "index_topk_i8_masked"}, "index_rescore_i8", "index_probe_i8", "index_export_i8", "index_quantize_i8", true, true},
-    {{"index_topk_b1", "index_topk_b1_masked"}, "index_rescore_b1", "index_probe_b1", "index_export_b1", "index_pack_b1", false, true},
+    {{"index_topk_f32", "index_topk_f32_masked"}, "index_rescore_f32", "index_probe_f32", "index_probe_f32_masked", "index_export_f32", "index_convert_f32", false, false},
+    {{"index_topk_f16", "index_topk_f16_masked"}, "index_rescore_f16", "index_probe_f16", "index_probe_f16_masked", "index_export_f16", "index_convert_f16", false, false},
+    {{"index_topk_i8", "index_topk_i8_masked"}, "index_rescore_i8", "index_probe_i8", "index_probe_i8_masked", "index_export_i8", "index_quantize_i8", true, true},
+    {{"index_topk_b1", "index_topk_b1_masked"}, "index_rescore_b1", "index_probe_b1", "index_probe_b1_masked", "index_export_b1", "index_pack_b1", false, true},
 };
 int query_form(int dtype) { return FORMS[dtype].quantized_queries ? 2 : dtype; }
 
@@ -301,16 +301,21 @@ int Index::search_to_host(int nq, const float *q, bool q_on_device, int k, int32
     if (const int go = check_search(nq, q, k, ids, scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
     const uint32_t *d_allow = nullptr;
-    if (allow && n_ > 0) {
-        // (the first search below waits for this copy: the same stream)
-        if (!grow(allow_, live_words(n_) * 4, err)) return -1;
-        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -1);
-        HIP_OK(hipMemcpyAsync(allow_.p, allow, live_words(n_) * 4, hipMemcpyHostToDevice, stream_), err, -1);
-        d_allow = allow_.as<uint32_t>();
-    }
+    if (!upload_allow(allow, stream_, d_allow, err)) return -1;
     return host_route(nq, q, q_on_device, false, k, ids, scores, err, [&](int, int c, const float *d_q, int32_t *d_ids, float *d_scores) {
         return search_device(c, d_q, k, d_ids, d_scores, stream_, err, d_allow);
     });
+}
+
+// a host allow-list (null, or an empty index: d_allow stays null) into allow_, on s behind whatever is queued on the index; the
+// searches that read it follow on s
+bool Index::upload_allow(const uint32_t *allow, hipStream_t s, const uint32_t *&d_allow, std::string &err) {
+    if (!allow || n_ == 0) return true;
+    if (!grow(allow_, live_words(n_) * 4, err)) return false;
+    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, false);
+    HIP_OK(hipMemcpyAsync(allow_.p, allow, live_words(n_) * 4, hipMemcpyHostToDevice, s), err, false);
+    d_allow = allow_.as<uint32_t>();
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -350,7 +355,7 @@ int Index::rescore_to_host(int nq, const float *q, int n_cand, const int32_t *ca
 }
 
 int Index::search_rescored_device(Index &coarse, int nq, const float *d_q, int n_cand, int k, int32_t *d_ids, float *d_scores,
-                                  hipStream_t s, std::string &err) {
+                                  hipStream_t s, std::string &err, int nprobe, const uint32_t *d_allow) {
     if (const int go = check_search_rescored(nq, d_q, n_cand, k, d_ids, d_scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
     const int nqc = std::min(nq, QCHUNK);
@@ -361,24 +366,31 @@ int Index::search_rescored_device(Index &coarse, int nq, const float *d_q, int n
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         const float *dq = d_q + (size_t)c0 * dim_;
-        if (coarse.search_device(c, dq, n_cand, cand_i_.as<int32_t>(), cand_s_.as<float>(), s, err) != 0) return -1;
+        const int r = nprobe > 0 ? coarse.search_probed_device(c, dq, nprobe, n_cand, cand_i_.as<int32_t>(), cand_s_.as<float>(), s, err, d_allow)
+                                 : coarse.search_device(c, dq, n_cand, cand_i_.as<int32_t>(), cand_s_.as<float>(), s, err);
+        if (r != 0) return -1;
         if (rescore_device(c, dq, n_cand, cand_i_.as<int32_t>(), k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s, err) != 0) return -1;
     }
     return 0;
 }
 
-int Index::search_rescored_to_host(Index &coarse, int nq, const float *q, int n_cand, int k, int32_t *ids, float *scores, std::string &err) {
+int Index::search_rescored_to_host(Index &coarse, int nq, const float *q, int n_cand, int k, int32_t *ids, float *scores, std::string &err,
+                                   int nprobe, const uint32_t *allow) {
     if (const int go = check_search_rescored(nq, q, n_cand, k, ids, scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
+    // (the list goes into coarse's buffer on this index's stream, on which coarse's searches follow)
+    const uint32_t *d_allow = nullptr;
+    if (nprobe > 0 && !coarse.upload_allow(allow, stream_, d_allow, err)) return -1;
     return host_route(nq, q, false, true, k, ids, scores, err, [&](int, int c, const float *d_q, int32_t *d_ids, float *d_scores) {
-        return search_rescored_device(coarse, c, d_q, n_cand, k, d_ids, d_scores, stream_, err);
+        return search_rescored_device(coarse, c, d_q, n_cand, k, d_ids, d_scores, stream_, err, nprobe, d_allow);
     });
 }
 
 // ------------------------------------------------------------------------------------------------
 // probed search (the partition: index_partition.cpp), rows read back
 // ------------------------------------------------------------------------------------------------
-int Index::search_probed_device(int nq, const float *d_q, int nprobe, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err) {
+int Index::search_probed_device(int nq, const float *d_q, int nprobe, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err,
+                                const uint32_t *d_allow) {
     if (const int go = check_search(nq, d_q, k, d_ids, d_scores, err); go <= 0) return go;
     if (!cent_ || nprobe < 1 || nprobe > std::min(n_lists(), MAX_K)) { err = "search_probed: a partition and 1 <= nprobe <= min(n_lists, 256) required"; return -1; }
     DeviceGuard g(eng_->device());
@@ -401,7 +413,8 @@ int Index::search_probed_device(int nq, const float *d_q, int nprobe, int k, int
         a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
         a.n_rows = n_; a.dpad = dpad_; a.nq = c; a.nprobe = nprobe; a.n_lists = n_lists(); a.n_part = n_part_; a.n_items = n_items;
         a.k = k; a.L = probe_L(k);
-        eng_->timed_launch(FORMS[dtype_].probe, 0.0, s, [&] { launch_probe(dtype_, a, s); });
+        a.allow = d_allow;                                   // (an allow-list: the masked kernel, the same items and workspace)
+        eng_->timed_launch(d_allow ? FORMS[dtype_].probe_masked : FORMS[dtype_].probe, 0.0, s, [&] { launch_probe(dtype_, a, s); });
         enqueue_merge(c, n_items * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -1);
@@ -409,11 +422,14 @@ int Index::search_probed_device(int nq, const float *d_q, int nprobe, int k, int
     return 0;
 }
 
-int Index::search_probed_to_host(int nq, const float *q, int nprobe, int k, int32_t *ids, float *scores, std::string &err) {
+int Index::search_probed_to_host(int nq, const float *q, int nprobe, int k, int32_t *ids, float *scores, std::string &err,
+                                 const uint32_t *allow) {
     if (const int go = check_search(nq, q, k, ids, scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
+    const uint32_t *d_allow = nullptr;
+    if (!upload_allow(allow, stream_, d_allow, err)) return -1;
     return host_route(nq, q, false, true, k, ids, scores, err, [&](int, int c, const float *d_q, int32_t *d_ids, float *d_scores) {
-        return search_probed_device(c, d_q, nprobe, k, d_ids, d_scores, stream_, err);
+        return search_probed_device(c, d_q, nprobe, k, d_ids, d_scores, stream_, err, d_allow);
     });
 }
 

@@ -94,6 +94,15 @@ bool two_stage_ok(const char *me, const bert_hip_index *coarse, const bert_hip_i
     return !why;
 }
 
+// what a probed two-stage search asks on top of two_stage_ok: coarse's partition and nprobe, and an allow-list that covers coarse
+bool two_stage_probed_ok(const char *me, const Index &coarse, int32_t nprobe, const uint32_t *allow, int32_t n_words) {
+    const char *why = nullptr;
+    if (coarse.n_lists() == 0) why = "the coarse index has no partition";
+    else if (nprobe < 1 || nprobe > std::min(coarse.n_lists(), Index::MAX_K)) why = "1 <= nprobe <= min(n_lists, 256) required";
+    if (why) fprintf(stderr, "%s: %s\n", me, why);
+    return !why && allow_ok(me, coarse, allow, n_words);
+}
+
 // the shape of a probed search (-2 after a line on stderr otherwise)
 bool probed_ok(const char *me, const Index &x, int32_t n_queries, int32_t nprobe, int32_t k, bool have_ptrs) {
     const char *why = nullptr;
@@ -336,6 +345,65 @@ int32_t bert_hip_index_search_probed_device(struct bert_hip_index *ix, int32_t n
     return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
         if (!probed_ok(me, x, n_queries, nprobe, k, d_queries && d_ids && d_scores)) return -2;
         return x.search_probed_device(n_queries, d_queries, nprobe, k, d_ids, d_scores, (hipStream_t)stream, err) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_probed_filtered(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t nprobe, int32_t k,
+                                              const uint32_t *allow, int32_t n_words, int32_t *ids, float *scores) {
+    const char *me = "bert_hip_index_search_probed_filtered";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!probed_ok(me, x, n_queries, nprobe, k, queries && ids && scores) || !allow_ok(me, x, allow, n_words)) return -2;
+        return x.search_probed_to_host(n_queries, queries, nprobe, k, ids, scores, err, allow) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_probed_filtered_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t nprobe,
+                                                     int32_t k, const uint32_t *d_allow, int32_t n_words, int32_t *d_ids, float *d_scores,
+                                                     void *stream) {
+    const char *me = "bert_hip_index_search_probed_filtered_device";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!probed_ok(me, x, n_queries, nprobe, k, d_queries && d_ids && d_scores) || !allow_ok(me, x, d_allow, n_words)) return -2;
+        return x.search_probed_device(n_queries, d_queries, nprobe, k, d_ids, d_scores, (hipStream_t)stream, err, d_allow) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_rescored_probed(struct bert_hip_index *coarse, struct bert_hip_index *fine, int32_t n_queries,
+                                              const float *queries, int32_t nprobe, int32_t n_cand, int32_t k, const uint32_t *allow,
+                                              int32_t n_words, int32_t *ids, float *scores) {
+    const char *me = "bert_hip_index_search_rescored_probed";
+    return index_call(me, fine, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!two_stage_ok(me, coarse, fine, n_queries, n_cand, k, queries && ids && scores) ||
+            !two_stage_probed_ok(me, *coarse->ix, nprobe, allow, n_words)) return -2;
+        return x.search_rescored_to_host(*coarse->ix, n_queries, queries, n_cand, k, ids, scores, err, nprobe, allow) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_search_rescored_probed_device(struct bert_hip_index *coarse, struct bert_hip_index *fine, int32_t n_queries,
+                                                     const float *d_queries, int32_t nprobe, int32_t n_cand, int32_t k,
+                                                     const uint32_t *d_allow, int32_t n_words, int32_t *d_ids, float *d_scores, void *stream) {
+    const char *me = "bert_hip_index_search_rescored_probed_device";
+    return index_call(me, fine, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!two_stage_ok(me, coarse, fine, n_queries, n_cand, k, d_queries && d_ids && d_scores) ||
+            !two_stage_probed_ok(me, *coarse->ix, nprobe, d_allow, n_words)) return -2;
+        return x.search_rescored_device(*coarse->ix, n_queries, d_queries, n_cand, k, d_ids, d_scores, (hipStream_t)stream, err, nprobe, d_allow) != 0 ? -3 : 0;
+    });
+}
+
+int32_t bert_hip_index_partition_save(struct bert_hip_index *ix, const char *path) {
+    const char *me = "bert_hip_index_partition_save";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (x.n_lists() == 0 || !path || !*path) { fprintf(stderr, "%s: a partition and a path required\n", me); return -2; }
+        return x.save_partition(path, err) ? 0 : -3;
+    });
+}
+
+int32_t bert_hip_index_partition_load(struct bert_hip_index *ix, const char *path) {
+    const char *me = "bert_hip_index_partition_load";
+    return index_call(me, ix, [&](bert_ctx *, Index &x, std::string &err) -> int32_t {
+        if (!path || !*path) { fprintf(stderr, "%s: a path required\n", me); return -2; }
+        const int r = x.load_partition(path, err);
+        if (r == -2) fprintf(stderr, "%s: '%s': %s\n", me, path, err.c_str());
+        return r;
     });
 }
 

@@ -1,4 +1,4 @@
-// index_file.cpp — header of an embedding index file (index_file.h): layout, and the check in front of a load.
+// index_file.cpp — headers of an embedding index file and of a partition file (index_file.h): layout, and the check in front of a load.
 #include "index_file.h"
 
 #include <cstring>
@@ -8,6 +8,7 @@ namespace bert_hip {
 namespace {
 
 const char MAGIC[8] = {'B', 'H', 'I', 'P', 'I', 'D', 'X', '1'};
+const char PARTITION_MAGIC[8] = {'B', 'H', 'I', 'P', 'P', 'R', 'T', '1'};
 
 void put_u32(unsigned char *p, uint32_t v) {
     for (int i = 0; i < 4; ++i) p[i] = (unsigned char)(v >> (8 * i));
@@ -61,6 +62,39 @@ bool index_header_check(const void *buf, size_t buf_len, uint64_t file_bytes, In
     for (size_t i = 32; i < INDEX_HEADER_BYTES; ++i)
         if (p[i]) { err = "non-zero reserved header bytes"; return false; }
     const uint64_t want = index_file_bytes(g);
+    if (file_bytes != want) {
+        err = "the file has " + std::to_string(file_bytes) + " bytes, its header describes " + std::to_string(want) +
+              (file_bytes < want ? " (truncated)" : " (over-long)");
+        return false;
+    }
+    h = g;
+    return true;
+}
+
+uint64_t partition_file_bytes(const PartitionFileHeader &h) {
+    return INDEX_HEADER_BYTES + (uint64_t)h.n_lists * (uint64_t)h.dim * 4 + (uint64_t)h.n_part * 4;
+}
+
+void partition_header_write(const PartitionFileHeader &h, unsigned char out[INDEX_HEADER_BYTES]) {
+    memset(out, 0, INDEX_HEADER_BYTES);
+    memcpy(out, PARTITION_MAGIC, 8);
+    const uint32_t f[4] = {h.version, h.dim, h.n_lists, h.n_part};
+    for (int i = 0; i < 4; ++i) put_u32(out + 8 + 4 * i, f[i]);
+}
+
+bool partition_header_check(const void *buf, size_t buf_len, uint64_t file_bytes, PartitionFileHeader &h, std::string &err) {
+    const unsigned char *p = (const unsigned char *)buf;
+    if (!p || buf_len < INDEX_HEADER_BYTES) { err = "shorter than the 64-byte header"; return false; }
+    if (memcmp(p, PARTITION_MAGIC, 8) != 0) { err = "not a partition file (magic BHIPPRT1 expected)"; return false; }
+    PartitionFileHeader g;
+    g.version = get_u32(p + 8); g.dim = get_u32(p + 12); g.n_lists = get_u32(p + 16); g.n_part = get_u32(p + 20);
+    if (g.version != PARTITION_FILE_VERSION) { err = "version " + std::to_string(g.version) + " (this build reads version 1)"; return false; }
+    if (g.dim < 1 || g.dim > (uint32_t)INDEX_MAX_DIM) { err = "dim " + std::to_string(g.dim) + " (1 .. 2048)"; return false; }
+    if (g.n_lists < 1 || g.n_lists > PARTITION_MAX_LISTS) { err = "n_lists " + std::to_string(g.n_lists) + " (1 .. 65536)"; return false; }
+    if (g.n_part > 0x7fffffffu) { err = "more than 2^31 - 1 assigned rows"; return false; }
+    for (size_t i = 24; i < INDEX_HEADER_BYTES; ++i)
+        if (p[i]) { err = "non-zero reserved header bytes"; return false; }
+    const uint64_t want = partition_file_bytes(g);
     if (file_bytes != want) {
         err = "the file has " + std::to_string(file_bytes) + " bytes, its header describes " + std::to_string(want) +
               (file_bytes < want ? " (truncated)" : " (over-long)");

@@ -1,11 +1,16 @@
 // index_partition.cpp — the cluster partition of an embedding index (search.h): the assignment of rows to centroids, the list
-// tables on the device (built by partition.h), and k-means.  The probed search that reads the tables is in index.cpp.
+// tables on the device (built by partition.h), k-means, and the partition file.  The probed search that reads the tables is in
+// index.cpp.
 //
 // The assignment is a public search: the list of a row is the id that a k = 1 search of an f32 index of the centroids returns
 // for the row as get_rows gives it; -1 (every score NaN) becomes list 0.  partition and kmeans share assign_rows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstdio>
+
+#include <sys/stat.h>
 
 #include "partition.h"
 #include "search.h"
@@ -71,15 +76,88 @@ int Index::partition(int n_lists, const float *centroids, std::string &err) {
     std::unique_ptr<Index> cent(Index::create(eng_, dim_, 0, err));
     if (!cent || cent->add_host(n_lists, centroids, err) < 0) return -1;
     std::vector<int32_t> list_of;
-    if (!assign_rows(*cent, list_of, err) || !upload_lists(list_of, n_lists, err)) {
-        if (cent_ && !upload_lists(list_of_, this->n_lists(), err)) drop_partition();    // (the tables of the partition that stays)
-        return -1;
+    if (!assign_rows(*cent, list_of, err)) return -1;
+    return install_partition(std::move(cent), centroids, std::move(list_of), err) ? 0 : -1;
+}
+
+// cent (the centroids as an index), centroids (the same on the host) and the lists of the first list_of.size() rows become the
+// partition; on an error the index keeps the one it had
+bool Index::install_partition(std::unique_ptr<Index> cent, const float *centroids, std::vector<int32_t> &&list_of, std::string &err) {
+    const int n_lists = cent->size();
+    if (!upload_lists(list_of, n_lists, err)) {
+        std::string e2;
+        if (cent_ && !upload_lists(list_of_, this->n_lists(), e2)) drop_partition();    // (the tables of the partition that stays)
+        return false;
     }
     cent_ = std::move(cent);
     cent_h_.assign(centroids, centroids + (size_t)n_lists * dim_);
+    n_part_ = (int)list_of.size();
     list_of_ = std::move(list_of);
-    n_part_ = n_;
-    return 0;
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the partition file (index_file.h)
+// ------------------------------------------------------------------------------------------------
+bool Index::save_partition(const char *path, std::string &err) {
+    if (!path || !*path) { err = "a path is required"; return false; }
+    if (!cent_) { err = "the index has no partition"; return false; }
+    PartitionFileHeader h;
+    h.dim = (uint32_t)dim_; h.n_lists = (uint32_t)n_lists(); h.n_part = (uint32_t)n_part_;
+    unsigned char hdr[INDEX_HEADER_BYTES];
+    partition_header_write(h, hdr);
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) { err = "cannot write '" + tmp + "'"; return false; }
+    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && fwrite(cent_h_.data(), 4, cent_h_.size(), f) == cent_h_.size() &&
+              fwrite(list_of_.data(), 4, (size_t)n_part_, f) == (size_t)n_part_;
+    ok = (fclose(f) == 0) && ok;
+    if (ok && rename(tmp.c_str(), path) != 0) ok = false;
+    if (!ok) {
+        (void)::remove(tmp.c_str());
+        err = "cannot write '" + std::string(path) + "'";
+    }
+    return ok;
+}
+
+int Index::load_partition(const char *path, std::string &err) {
+    if (!path || !*path) { err = "a path is required"; return -2; }
+    FILE *f = fopen(path, "rb");
+    struct stat st;
+    if (!f || fstat(fileno(f), &st) != 0 || !S_ISREG(st.st_mode)) {
+        if (f) fclose(f);
+        err = "cannot read '" + std::string(path) + "'";
+        return -3;
+    }
+    // the header and the file's length first; then the contents, on the host; the device only sees a partition that passed
+    unsigned char hdr[INDEX_HEADER_BYTES];
+    const size_t got = fread(hdr, 1, sizeof hdr, f);
+    PartitionFileHeader h;
+    std::vector<float> cents;
+    std::vector<int32_t> list_of;
+    int r = 0;
+    if (!partition_header_check(hdr, got, (uint64_t)st.st_size, h, err)) r = -2;
+    else if ((int)h.dim != dim_) { err = "the file has dim " + std::to_string(h.dim) + ", the index " + std::to_string(dim_); r = -2; }
+    else if (h.n_part > (uint32_t)n_) { err = "the file assigns " + std::to_string(h.n_part) + " rows, the index holds " + std::to_string(n_); r = -2; }
+    else {
+        cents.resize((size_t)h.n_lists * h.dim);
+        list_of.resize(h.n_part);
+        if (fread(cents.data(), 4, cents.size(), f) != cents.size() || fread(list_of.data(), 4, list_of.size(), f) != list_of.size()) { err = "read failed"; r = -3; }
+    }
+    fclose(f);
+    if (r != 0) return r;
+    for (float c : cents)
+        if (!std::isfinite(c)) { err = "a centroid element is not finite"; return -2; }
+    for (size_t i = 0; i < list_of.size(); ++i)
+        if (list_of[i] < 0 || list_of[i] >= (int32_t)h.n_lists) {
+            err = "row " + std::to_string(i) + " has list id " + std::to_string(list_of[i]) + ", outside [0, " + std::to_string(h.n_lists) + ")";
+            return -2;
+        }
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipEventSynchronize(busy_), err, -3);
+    std::unique_ptr<Index> cent(Index::create(eng_, dim_, 0, err));
+    if (!cent || cent->add_host((int)h.n_lists, cents.data(), err) < 0) return -3;
+    return install_partition(std::move(cent), cents.data(), std::move(list_of), err) ? 0 : -3;
 }
 
 void Index::partition_lists(int32_t *list_of_row) const {

@@ -19,6 +19,8 @@
 // are a table of row ids sorted by (list, id).  A probed search scores the centroids (a search with k = nprobe), then
 // index_probe_kernel scans the members of each query's lists and the unassigned tail — the rows added since — and selects on
 // chip; topk_merge_kernel merges the items' lists.  kmeans refines centroids with the same assignment and kmeans_update_kernel.
+// With an allow-list the scan runs index_probe_kernel's masked instantiation; a two-stage search may take the probed search as its
+// coarse stage; the partition (centroids, list ids, the tail's start) has a file of its own, which a load installs as it is.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -83,10 +85,12 @@ public:
     int rescore_to_host(int nq, const float *q, int n_cand, const int32_t *cand, int k, int32_t *ids, float *scores, std::string &err);
     // Two-stage search: coarse.search_device with k' = n_cand, the ids kept on the device, then this index's rescore_device
     // with the same f32 queries.  The caller checks that both live on one engine and have equal dim and size, and
-    // 1 <= k <= n_cand <= MAX_K.  Asynchronous on s; 0 or -1
+    // 1 <= k <= n_cand <= MAX_K.  Asynchronous on s; 0 or -1.  nprobe > 0: the coarse stage is coarse.search_probed_device with
+    // that nprobe and the allow-list (device / host words covering coarse, or null), under that call's conditions
     int search_rescored_device(Index &coarse, int nq, const float *d_q, int n_cand, int k, int32_t *d_ids, float *d_scores,
-                               hipStream_t s, std::string &err);
-    int search_rescored_to_host(Index &coarse, int nq, const float *q, int n_cand, int k, int32_t *ids, float *scores, std::string &err);
+                               hipStream_t s, std::string &err, int nprobe = 0, const uint32_t *d_allow = nullptr);
+    int search_rescored_to_host(Index &coarse, int nq, const float *q, int n_cand, int k, int32_t *ids, float *scores, std::string &err,
+                                int nprobe = 0, const uint32_t *allow = nullptr);
     // the stored rows ids [n] (each in [0, size): the caller checks) as f32 [n][dim], removed rows included; blocking
     int get_rows(int n, const int32_t *ids, float *rows, std::string &err);
     // Partition.  partition: installs centroids [n_lists][dim] (finite: the caller checks; 1 <= n_lists <= MAX_LISTS) and
@@ -100,9 +104,18 @@ public:
     // over that sum's norm (kept for no member, a zero or a non-finite norm).  Leaves the index as it is.  Blocking; 0 or -1
     int kmeans(int n_lists, int n_iter, float *centroids, std::string &err);
     // Probed search: as search_device over the rows of each query's nprobe best lists and the tail.  The caller checks that
-    // there is a partition and 1 <= nprobe <= min(n_lists, MAX_K).  Asynchronous on s; 0 or -1
-    int search_probed_device(int nq, const float *d_q, int nprobe, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err);
-    int search_probed_to_host(int nq, const float *q, int nprobe, int k, int32_t *ids, float *scores, std::string &err);
+    // there is a partition and 1 <= nprobe <= min(n_lists, MAX_K).  Asynchronous on s; 0 or -1.  d_allow / allow: as search_device's
+    // and search_to_host's — with one, index_probe_kernel's masked instantiation over the same items and workspace
+    int search_probed_device(int nq, const float *d_q, int nprobe, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err,
+                             const uint32_t *d_allow = nullptr);
+    int search_probed_to_host(int nq, const float *q, int nprobe, int k, int32_t *ids, float *scores, std::string &err,
+                              const uint32_t *allow = nullptr);
+    // The partition as a file of its own (index_file.h; the format is stated in include/bert_hip.h).  save_partition: the caller
+    // checks that there is one.  load_partition installs the file's centroids and lists as they are — no assignment runs, the
+    // rows at and beyond its n_part are the tail —: 0, -2 (the file does not fit the index, or holds a non-finite centroid or a
+    // list id outside the lists) or -3, the index keeping the partition it had.  Blocking
+    bool save_partition(const char *path, std::string &err);
+    int load_partition(const char *path, std::string &err);
     // marks rows as removed (ids in [0, size) or -1 with the index unchanged; repeats ignored): the number newly removed; blocking
     int remove(int n, const int32_t *ids, std::string &err);
     // drops the removed rows' storage: live rows keep order and bits, ids 0 .. n_live - 1; old_ids (null or [n_live]) the
@@ -130,6 +143,8 @@ private:
     void enqueue_export(int first, int n, const int32_t *d_ids, float *d_out, hipStream_t s);
     bool assign_rows(Index &cent, std::vector<int32_t> &list_of, std::string &err);
     bool upload_lists(const std::vector<int32_t> &list_of, int n_lists, std::string &err);
+    bool install_partition(std::unique_ptr<Index> cent, const float *centroids, std::vector<int32_t> &&list_of, std::string &err);
+    bool upload_allow(const uint32_t *allow, hipStream_t s, const uint32_t *&d_allow, std::string &err);
     void drop_partition();
     bool make_live(std::string &err);
     bool upload_live(size_t w0, size_t w1, std::string &err);

@@ -26,7 +26,9 @@
 //                         query's probed lists (its members' ids come from the partition's order table) or a chunk of the
 //                         unassigned tail.  Each wave scores 32 members per step as the rescore kernel does, and the workgroup
 //                         selects in LDS as the top-k kernel does for one query: k entries per item reach the workspace, from
-//                         which topk_merge_kernel selects.
+//                         which topk_merge_kernel selects.  The masked instantiation (a probed search with an allow-list)
+//                         scores and pushes only the members whose bit of live & allow is set; a wave whose 32 members hold
+//                         none issues no row loads and no MFMA.
 //   index_export_kernel<T>  stored rows, named by id, back as f32 (ScoreBlock<T>::element): bert_hip_index_get_rows, and the
 //                         queries of the partition's assignment.
 //   kmeans_update_kernel<T>  one workgroup per list: the sum of its members' exported rows in an order fixed by the member
@@ -422,7 +424,11 @@ __global__ __launch_bounds__(NT) void index_rescore_kernel(RescoreArgs a) {
 // Scoring is index_rescore_kernel's — the query is query 0 of the tile, lane l < 32 ends with its member's score —, selection
 // index_topk_kernel's with one query: threshold in registers, queue behind the current top-k in LDS, sorted when a step might
 // not fit.  The k entries written for an item that has fewer candidates are (-inf, SENT_ID).
-template <class T>
+// MASKED (a search with an allow-list): a member is a candidate iff its bit of live & allow is set.  The members of a list are
+// scattered ids, so each lane reads its own member's words; the members of a tail chunk are consecutive ids, so the wave's 32
+// bits come from at most two words read once per wave and step (the tail starts at n_part, any row: the block straddles two
+// words unless it happens to start at a multiple of 32).  A word that holds no row below n_rows is never read.
+template <class T, bool MASKED>
 __global__ __launch_bounds__(NT) void index_probe_kernel(ProbeArgs a) {
     using F = ScoreBlock<T>;
     using QE = typename F::query_t;
@@ -464,7 +470,33 @@ __global__ __launch_bounds__(NT) void index_probe_kernel(ProbeArgs a) {
         const int m = base + wave * 32 + col;
         const int id = m < m1 ? (listed ? a.order[m] : m) : -1;
         bool rok = id >= 0 && id < a.n_rows;
-        if (rok && a.live) rok = (a.live[id >> 5] >> (id & 31)) & 1u;
+        if constexpr (!MASKED) {
+            if (rok && a.live) rok = (a.live[id >> 5] >> (id & 31)) & 1u;
+        } else if (listed) {
+            if (rok) {
+                uint32_t w = a.allow[id >> 5];
+                if (a.live) w &= a.live[id >> 5];
+                rok = (w >> (id & 31)) & 1u;
+            }
+        } else {
+            // the wave's block is rows b0 .. b0 + 31: bit c of `bits` is row b0 + c's, from word b0 >> 5 and, where the block
+            // straddles and the next word still holds a row below m1 (<= n_rows), from that one
+            const int b0 = __builtin_amdgcn_readfirstlane(base + wave * 32);
+            uint32_t bits = 0;
+            if (b0 < m1) {
+                const int w0 = b0 >> 5, sh = b0 & 31;
+                uint32_t lo = a.allow[w0];
+                if (a.live) lo &= a.live[w0];
+                bits = lo >> sh;
+                if (sh != 0 && w0 < ((m1 - 1) >> 5)) {
+                    uint32_t hi = a.allow[w0 + 1];
+                    if (a.live) hi &= a.live[w0 + 1];
+                    bits |= hi << (32 - sh);
+                }
+            }
+            bits = __builtin_amdgcn_readfirstlane(bits);
+            rok = rok && ((bits >> col) & 1u);
+        }
         if (__any(rok)) {                                          // (wave-uniform)
             const T *rp = F::row_ptr(a.rows, (size_t)(rok ? id : 0), a.dpad);
             const float rs = F::RSCALE && rok ? a.rscale[id] : 0.f;
@@ -683,8 +715,12 @@ void launch_rescore(int dtype, const RescoreArgs &a, hipStream_t s) {
 }
 
 void launch_probe(int dtype, const ProbeArgs &a, hipStream_t s) {
+    const dim3 grid((unsigned)a.nq * a.n_items);
+    const size_t lds = (size_t)a.L * 8 + 16;
     dispatch(dtype, [&](auto form) {
-        BERT_LAUNCH(index_probe_kernel<decltype(row_type(form))>, dim3((unsigned)a.nq * a.n_items), dim3(NT), (size_t)a.L * 8 + 16, s, a);
+        using T = decltype(row_type(form));
+        if (a.allow) BERT_LAUNCH((index_probe_kernel<T, true>), grid, dim3(NT), lds, s, a);
+        else BERT_LAUNCH((index_probe_kernel<T, false>), grid, dim3(NT), lds, s, a);
     });
 }
 

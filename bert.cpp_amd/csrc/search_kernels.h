@@ -58,6 +58,9 @@ struct ProbeArgs {
     float *ws_s;                         // [nq][n_items][k], best first
     int *ws_i;
     int n_rows, dpad, nq, nprobe, n_lists, n_part, n_items, k, L;
+    // words shaped like live, bit set = the row may be returned; null = every row (read by the masked instantiation only, and
+    // last in the block: the unmasked one's argument offsets are what they were)
+    const uint32_t *allow;
 };
 inline int probe_L(int k) { return k + STEP_ROWS <= 256 ? 256 : 512; }
 
@@ -86,6 +89,7 @@ void search_kernels_init();
 void launch_topk(int dtype, const TopkArgs &a, size_t lds, hipStream_t s);
 void launch_topk_merge(const MergeArgs &a, int nq, hipStream_t s);
 void launch_rescore(int dtype, const RescoreArgs &a, hipStream_t s);
+// the masked instantiation iff a.allow is set (removed rows alone stay on the unmasked one, which reads a.live per lane)
 void launch_probe(int dtype, const ProbeArgs &a, hipStream_t s);
 void launch_export(int dtype, const ExportArgs &a, hipStream_t s);
 void launch_kmeans_update(int dtype, const KmeansArgs &a, hipStream_t s);

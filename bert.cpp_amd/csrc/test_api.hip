@@ -575,6 +575,20 @@ int32_t bert_hip_test_index_header(const void *buf, int32_t buf_len, int64_t fil
     return -1;
 }
 
+int32_t bert_hip_test_partition_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err, int32_t err_cap) {
+    PartitionFileHeader h;
+    std::string e;
+    if (err && err_cap > 0) err[0] = 0;
+    if (buf_len < 0 || file_bytes < 0) e = "negative length";
+    else if (partition_header_check(buf, (size_t)buf_len, (uint64_t)file_bytes, h, e)) {
+        const uint32_t f[4] = {h.version, h.dim, h.n_lists, h.n_part};
+        if (fields) std::copy(f, f + 4, fields);
+        return 0;
+    }
+    if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return -1;
+}
+
 int32_t bert_hip_test_build_lists(const int32_t *list_of, int32_t n, int32_t n_lists, int32_t *offsets, int32_t *order) {
     if (n < 0 || n_lists < 0 || (n > 0 && !list_of) || !offsets || (n > 0 && !order)) return -1;
     ListTables t;

@@ -3,15 +3,18 @@
 // then each line read from stdin is a query whose k closest texts are printed in the reference's format.  'q' or the end
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
-//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N [--nprobe P]] [-t THREADS] [--save PATH] [--load PATH]
+//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
 //   (--f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; --b1: one sign bit per element; the
 //   default stores the rows as f16; --rescore N: an int8 index of the same texts is kept beside the index, which only picks N
 //   candidates per query, and the answer is the int8 index's best k of them (bert_hip_index_search_rescored; k <= N <= 256);
 //   --lists N: once the texts are in, the index is partitioned into N lists (bert_hip_index_kmeans, ten iterations from N evenly
 //   spaced rows, then bert_hip_index_partition); --nprobe P: each query then scans only its P nearest lists
-//   (bert_hip_index_search_probed; 1 <= P <= min(N, 256));
-//   --save: the index goes to PATH (bert_hip_index_save) once it is built; --load: the index comes from PATH instead of being
-//   embedded — TEXTS is still read, for printing, and must have as many lines as the index has rows)
+//   (bert_hip_index_search_probed; 1 <= P <= min(lists, 256)); with --rescore the partitioned index is the coarse one: it picks
+//   the N candidates among the P lists, which the int8 index rescores (bert_hip_index_search_rescored_probed);
+//   --save: the index goes to PATH (bert_hip_index_save) once it is built, and the partition of a partitioned one to PATH.part
+//   (bert_hip_index_partition_save); --load: the index comes from PATH instead of being embedded — TEXTS is still read, for
+//   printing, and must have as many lines as the index has rows —, and its partition from PATH.part where that file exists
+//   (bert_hip_index_partition_load: --nprobe then needs no --lists))
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,7 +28,7 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N [--nprobe P]] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
 }
 
 std::string chomp(std::string s) {
@@ -59,8 +62,9 @@ int main(int argc, char **argv) {
     if (two_stage && (n_cand < k || n_cand > 256)) { fprintf(stderr, "search: --rescore must be -k .. 256\n"); return 2; }
 
     if (n_lists < 0 || n_lists > 65536) { fprintf(stderr, "search: --lists must be 1 .. 65536\n"); return 2; }
-    if (nprobe != 0 && (two_stage || nprobe < 1 || nprobe > n_lists || nprobe > 256)) {
-        fprintf(stderr, "search: --nprobe must be 1 .. min(--lists, 256), and goes without --rescore\n");
+    // (against the lists themselves once they are there: they may come from --load PATH's PATH.part)
+    if (nprobe != 0 && (nprobe < 1 || nprobe > 256 || (n_lists > 0 && nprobe > n_lists) || (n_lists == 0 && !load))) {
+        fprintf(stderr, "search: --nprobe must be 1 .. min(lists, 256), the lists those of --lists or of --load PATH's PATH.part\n");
         return 2;
     }
 
@@ -91,6 +95,13 @@ int main(int argc, char **argv) {
         }
         if ((size_t)bert_hip_index_size(ix) != texts.size()) {
             fprintf(stderr, "search: '%s' holds %d rows, '%s' has %zu lines\n", load, bert_hip_index_size(ix), file, texts.size());
+            bert_free(ctx);
+            return 1;
+        }
+        // the partition saved beside the index, if there is one
+        const std::string part = std::string(load) + ".part";
+        if (std::ifstream(part).good() && bert_hip_index_partition_load(ix, part.c_str()) != 0) {
+            fprintf(stderr, "search: could not load the partition from '%s'\n", part.c_str());
             bert_free(ctx);
             return 1;
         }
@@ -130,8 +141,18 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    if (nprobe > bert_hip_index_n_lists(ix)) {
+        fprintf(stderr, "search: --nprobe %d exceeds the index's %d lists\n", nprobe, bert_hip_index_n_lists(ix));
+        bert_free(ctx);
+        return 1;
+    }
     if (save && bert_hip_index_save(ix, save) != 0) {
         fprintf(stderr, "search: could not save the index to '%s'\n", save);
+        bert_free(ctx);
+        return 1;
+    }
+    if (save && bert_hip_index_n_lists(ix) > 0 && bert_hip_index_partition_save(ix, (std::string(save) + ".part").c_str()) != 0) {
+        fprintf(stderr, "search: could not save the partition to '%s.part'\n", save);
         bert_free(ctx);
         return 1;
     }
@@ -149,7 +170,11 @@ int main(int argc, char **argv) {
         if (q == "q") break;
         const char *qp = q.c_str();
         int32_t r;
-        if (two_stage) {
+        if (two_stage && nprobe > 0) {
+            float *ep = emb.data();
+            r = bert_hip_encode_batch(ctx, n_threads, 1, &qp, &ep) == 1
+                    ? bert_hip_index_search_rescored_probed(ix, fine, 1, emb.data(), nprobe, n_cand, k, nullptr, 0, ids.data(), scores.data()) : -1;
+        } else if (two_stage) {
             float *ep = emb.data();
             r = bert_hip_encode_batch(ctx, n_threads, 1, &qp, &ep) == 1
                     ? bert_hip_index_search_rescored(ix, fine, 1, emb.data(), n_cand, k, ids.data(), scores.data()) : -1;

@@ -32,6 +32,8 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_index_rescore", "bert_hip_index_rescore_device", "bert_hip_index_search_rescored", "bert_hip_index_search_rescored_device",
     "bert_hip_index_get_rows", "bert_hip_index_partition", "bert_hip_index_n_lists", "bert_hip_index_partition_centroids",
     "bert_hip_index_partition_lists", "bert_hip_index_kmeans", "bert_hip_index_search_probed", "bert_hip_index_search_probed_device",
+    "bert_hip_index_search_probed_filtered", "bert_hip_index_search_probed_filtered_device", "bert_hip_index_search_rescored_probed",
+    "bert_hip_index_search_rescored_probed_device", "bert_hip_index_partition_save", "bert_hip_index_partition_load",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -42,7 +44,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
-    "bert_hip_test_build_lists",
+    "bert_hip_test_build_lists", "bert_hip_test_partition_header",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -125,6 +127,16 @@ def _declare_product_abi(L):
     L.bert_hip_index_kmeans.restype = i32; L.bert_hip_index_kmeans.argtypes = [vp, i32, i32, f32p]
     L.bert_hip_index_search_probed.restype = i32; L.bert_hip_index_search_probed.argtypes = [vp, i32, f32p, i32, i32, i32p, f32p]
     L.bert_hip_index_search_probed_device.restype = i32; L.bert_hip_index_search_probed_device.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
+    L.bert_hip_index_search_probed_filtered.restype = i32
+    L.bert_hip_index_search_probed_filtered.argtypes = [vp, i32, f32p, i32, i32, vp, i32, i32p, f32p]
+    L.bert_hip_index_search_probed_filtered_device.restype = i32
+    L.bert_hip_index_search_probed_filtered_device.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_index_search_rescored_probed.restype = i32
+    L.bert_hip_index_search_rescored_probed.argtypes = [vp, vp, i32, f32p, i32, i32, i32, vp, i32, i32p, f32p]
+    L.bert_hip_index_search_rescored_probed_device.restype = i32
+    L.bert_hip_index_search_rescored_probed_device.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_index_partition_save.restype = i32; L.bert_hip_index_partition_save.argtypes = [vp, C.c_char_p]
+    L.bert_hip_index_partition_load.restype = i32; L.bert_hip_index_partition_load.argtypes = [vp, C.c_char_p]
 
 
 def lib() -> C.CDLL:
@@ -201,6 +213,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_tokenize_pack.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32p, i32p, i32p, i32p, i32]
     L.bert_hip_test_index_header.restype = i32
     L.bert_hip_test_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
+    L.bert_hip_test_partition_header.restype = i32
+    L.bert_hip_test_partition_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
     L.bert_hip_test_build_lists.restype = i32
     L.bert_hip_test_build_lists.argtypes = [i32p, i32, i32, i32p, i32p]
     _test_lib = L
@@ -737,21 +751,68 @@ class BertIndex:
         self.partition(c)
         return c
 
-    def search_probed(self, queries, k: int = 10, nprobe: int = 8):
-        """bert_hip_index_search_probed: the search over the rows of each query's nprobe nearest lists and the tail."""
+    def search_probed(self, queries, k: int = 10, nprobe: int = 8, allow=None):
+        """bert_hip_index_search_probed: the search over the rows of each query's nprobe nearest lists and the tail.  allow: as
+        in search (bert_hip_index_search_probed_filtered)."""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         ids = np.empty((q.shape[0], k), dtype=np.int32)
         scores = np.empty((q.shape[0], k), dtype=np.float32)
-        r = self.lib.bert_hip_index_search_probed(self.ix, q.shape[0], _f32p(q), nprobe, k, _i32p(ids), _f32p(scores))
+        if allow is None:
+            r = self.lib.bert_hip_index_search_probed(self.ix, q.shape[0], _f32p(q), nprobe, k, _i32p(ids), _f32p(scores))
+            if r != 0:
+                raise RuntimeError(f"bert_hip_index_search_probed failed: {r}")
+            return ids, scores
+        words = allow_words(allow, len(self))
+        r = self.lib.bert_hip_index_search_probed_filtered(self.ix, q.shape[0], _f32p(q), nprobe, k, words.ctypes.data, len(words),
+                                                           _i32p(ids), _f32p(scores))
         if r != 0:
-            raise RuntimeError(f"bert_hip_index_search_probed failed: {r}")
+            raise RuntimeError(f"bert_hip_index_search_probed_filtered failed: {r}")
         return ids, scores
 
     def search_probed_device(self, n_queries: int, d_queries_ptr: int, nprobe: int, k: int, d_ids_ptr: int, d_scores_ptr: int,
-                             stream: int = 0) -> None:
-        r = self.lib.bert_hip_index_search_probed_device(self.ix, n_queries, d_queries_ptr, nprobe, k, d_ids_ptr, d_scores_ptr, stream)
+                             stream: int = 0, d_allow_ptr: int = 0, n_words: int = 0) -> None:
+        if not d_allow_ptr:
+            r = self.lib.bert_hip_index_search_probed_device(self.ix, n_queries, d_queries_ptr, nprobe, k, d_ids_ptr, d_scores_ptr, stream)
+            if r != 0:
+                raise RuntimeError(f"bert_hip_index_search_probed_device failed: {r}")
+            return
+        r = self.lib.bert_hip_index_search_probed_filtered_device(self.ix, n_queries, d_queries_ptr, nprobe, k, d_allow_ptr, n_words,
+                                                                  d_ids_ptr, d_scores_ptr, stream)
         if r != 0:
-            raise RuntimeError(f"bert_hip_index_search_probed_device failed: {r}")
+            raise RuntimeError(f"bert_hip_index_search_probed_filtered_device failed: {r}")
+
+    def search_rescored_probed(self, fine: "BertIndex", queries, k: int = 10, n_cand: int = 100, nprobe: int = 8, allow=None):
+        """Two-stage search over a partition (bert_hip_index_search_rescored_probed): this index's search_probed(k = n_cand,
+        nprobe, allow) picks the candidates, which stay on the device; `fine` rescores them and returns its best k."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        ids = np.empty((q.shape[0], k), dtype=np.int32)
+        scores = np.empty((q.shape[0], k), dtype=np.float32)
+        words = None if allow is None else allow_words(allow, len(self))
+        r = self.lib.bert_hip_index_search_rescored_probed(self.ix, fine.ix, q.shape[0], _f32p(q), nprobe, n_cand, k,
+                                                           None if words is None else words.ctypes.data, 0 if words is None else len(words),
+                                                           _i32p(ids), _f32p(scores))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search_rescored_probed failed: {r}")
+        return ids, scores
+
+    def search_rescored_probed_device(self, fine: "BertIndex", n_queries: int, d_queries_ptr: int, nprobe: int, n_cand: int, k: int,
+                                      d_ids_ptr: int, d_scores_ptr: int, stream: int = 0, d_allow_ptr: int = 0, n_words: int = 0) -> None:
+        r = self.lib.bert_hip_index_search_rescored_probed_device(self.ix, fine.ix, n_queries, d_queries_ptr, nprobe, n_cand, k,
+                                                                  d_allow_ptr or None, n_words, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_search_rescored_probed_device failed: {r}")
+
+    def save_partition(self, path: str) -> None:
+        """bert_hip_index_partition_save: centroids, list ids and the tail's start, as a file of its own."""
+        r = self.lib.bert_hip_index_partition_save(self.ix, os.fsencode(path))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_partition_save failed: {r}")
+
+    def load_partition(self, path: str) -> None:
+        """bert_hip_index_partition_load: installs the file's centroids and lists as they are (no assignment runs)."""
+        r = self.lib.bert_hip_index_partition_load(self.ix, os.fsencode(path))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_index_partition_load failed: {r}")
 
     @property
     def n_live(self) -> int:

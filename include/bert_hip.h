@@ -258,9 +258,10 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  *            search scans in full; add_device does nothing for the partition, so it stays free of allocations and legal
  *            under stream capture.  partition again, with the same or new centroids, assigns everything.  remove changes
  *            nothing in the partition: the scan reads the live bits.  compact keeps the partition: each live row keeps its
- *            list under its new id, the tail stays the tail.  The file format holds no partition, and a loaded index has
- *            none: keep partition_centroids beside the file, and partition after the load restores the same lists, because
- *            the assignment is a deterministic function of the stored rows and the centroids.
+ *            list under its new id, the tail stays the tail.  The index file holds no partition, and a loaded index has
+ *            none: partition_save / partition_load below keep it in a file of its own (or keep partition_centroids and
+ *            partition again after the load: the assignment is a deterministic function of the stored rows and the
+ *            centroids, but it assigns the former tail as well).
  *   kmeans   spherical k-means over the LIVE rows as get_rows returns them; centroids[n_lists][dim]: in, the initial centroids
  *            (finite, or -2; the caller seeds them), out, the refined ones.  Each of the n_iter >= 1 iterations assigns by
  *            the rule of partition, then replaces each centroid by the f32 sum of its members divided by that sum's L2 norm;
@@ -280,13 +281,41 @@ BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const c
  *            the merge.  The workspace ([n_queries][nprobe + ceil(tail / 1024)][k] entries, queries in internal chunks) is
  *            not part of reserve and grows on demand, which allocates: call once at the largest shape before a stream
  *            capture.
+ *   search_probed_filtered   search_probed with the allow-list of search_filtered.  Query q's result has the ids and the score
+ *            bits of bert_hip_index_search_filtered called with that one query and an allow-list of exactly: (the rows of the
+ *            nprobe lists that the centroid index returns for q, plus every tail row) AND the caller's list.  allow == NULL
+ *            is search_probed (n_words is ignored); n_words < ceil(size / 32): -2; bits at and beyond size are ignored and
+ *            never read; argument ranges are search_probed's; removed rows, NaN queries and -1 / -INFINITY slots as stated
+ *            for search_filtered and search_probed.  32 consecutive members of a list or of the tail without a qualifying
+ *            row cost neither row loads nor arithmetic.  An index with removed rows but no allow-list launches what
+ *            search_probed always did.  search_probed_filtered_device: queries, allow-list and results in device memory,
+ *            asynchronous on `stream` under the one-event rule; it uses the workspace of search_probed_device and never
+ *            allocates where a search_probed_device of the same shape has run.
+ *   search_rescored_probed   search_rescored whose coarse stage is coarse's search_probed_filtered with k' = n_cand: the
+ *            candidates stay on the device, then `fine` rescores them with the same f32 queries.  The result equals the two
+ *            public calls chained by hand.  `coarse` must have a partition, `fine` needs none; the allow-list (NULL: none;
+ *            n_words as above, against the common size) applies to the coarse stage, so no disallowed row is returned.  The
+ *            conditions of search_rescored (one context, equal dim and size, 1 <= k <= n_cand <= 256) and of search_probed
+ *            (nprobe) hold, otherwise -2.  search_rescored_probed_device: asynchronous on `stream`; both indexes' events
+ *            are honoured; the advice on allocation of rescore and search_probed holds.
+ *   partition_save / partition_load   the partition as a file of its own beside the index file (format below; the index file
+ *            and its version are untouched).  save writes path + ".tmp" and renames it; -2 without a partition.  load checks
+ *            the header against the file's length before anything is read or allocated, then requires dim == the index's
+ *            dim, 1 <= n_lists <= 65536, n_part <= size, every centroid element finite and every list id in [0, n_lists);
+ *            any failure is -2 or -3 after a line on stderr, and the index keeps the partition it had.  On success the
+ *            file's centroids and lists are installed as they are: NO assignment runs (the lists are the file's even where
+ *            an assignment would decide otherwise), rows at and beyond n_part are the tail, and n_lists,
+ *            partition_centroids, partition_lists and every probed search give the bits the saving index gave.  Blocking.
  * Errors of the functions that take an index: -1 no index, -2 bad arguments (after a line on stderr), -3 an error of the
  * index or the device (its message on stderr), -4 an exception.  Outputs are untouched on error.
  * File format (little-endian).  Header, 64 bytes: magic "BHIPIDX1" (8 bytes), u32 version = 1, u32 dtype (0 f32, 1 f16,
  * 2 i8, 3 b1), u32 dim, u32 dpad (elements per stored row: dim rounded up to 8 (f32), 16 (f16), 32 (i8), 128 (b1: bits)), u32
  * n_rows (= size, removed rows included), u32 has_live (0 | 1), 32 zero bytes.  Then n_rows * dpad * elem_size bytes of rows
  * exactly as stored (zero-padded to dpad; elem_size 4, 2, 1; b1: n_rows * dpad / 8 bytes); for i8, n_rows f32 row scales; if has_live, ceil(n_rows / 32) u32 words,
- * bit b of word w set = row 32 w + b is live, the bits at and beyond n_rows zero.  The file is exactly that long.        */
+ * bit b of word w set = row 32 w + b is live, the bits at and beyond n_rows zero.  The file is exactly that long.
+ * Partition file format (little-endian).  Header, 64 bytes: magic "BHIPPRT1" (8 bytes), u32 version = 1, u32 dim, u32 n_lists,
+ * u32 n_part (the number of assigned rows; the rows behind are the tail), 40 zero bytes.  Then n_lists * dim f32 centroids, then
+ * n_part i32 list ids.  The file is exactly that long.                                                                    */
 struct bert_hip_index;
 BERT_API struct bert_hip_index *bert_hip_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype);
 BERT_API void    bert_hip_index_free(struct bert_hip_index *ix);
@@ -327,6 +356,21 @@ BERT_API int32_t bert_hip_index_search_probed(struct bert_hip_index *ix, int32_t
                                               int32_t k, int32_t *ids, float *scores);
 BERT_API int32_t bert_hip_index_search_probed_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries,
                                                      int32_t nprobe, int32_t k, int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_index_search_probed_filtered(struct bert_hip_index *ix, int32_t n_queries, const float *queries,
+                                                       int32_t nprobe, int32_t k, const uint32_t *allow, int32_t n_words,
+                                                       int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_index_search_probed_filtered_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries,
+                                                              int32_t nprobe, int32_t k, const uint32_t *d_allow, int32_t n_words,
+                                                              int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_index_search_rescored_probed(struct bert_hip_index *coarse, struct bert_hip_index *fine, int32_t n_queries,
+                                                       const float *queries, int32_t nprobe, int32_t n_cand, int32_t k,
+                                                       const uint32_t *allow, int32_t n_words, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_index_search_rescored_probed_device(struct bert_hip_index *coarse, struct bert_hip_index *fine,
+                                                              int32_t n_queries, const float *d_queries, int32_t nprobe,
+                                                              int32_t n_cand, int32_t k, const uint32_t *d_allow, int32_t n_words,
+                                                              int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_index_partition_save(struct bert_hip_index *ix, const char *path);
+BERT_API int32_t bert_hip_index_partition_load(struct bert_hip_index *ix, const char *path);
 BERT_API int32_t bert_hip_index_compact(struct bert_hip_index *ix, int32_t *old_ids);
 BERT_API int32_t bert_hip_index_save(struct bert_hip_index *ix, const char *path);
 BERT_API struct bert_hip_index *bert_hip_index_load(struct bert_ctx *ctx, const char *path);

@@ -153,6 +153,10 @@ BERT_API int32_t bert_hip_test_tokenize_pack(struct bert_ctx *ctx, int32_t n_thr
  * n_rows, has_live} for a header this build loads; -1 and the reason in err (err_cap bytes) otherwise.                          */
 BERT_API int32_t bert_hip_test_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err,
                                             int32_t err_cap);
+/* The same for a partition file (index_file.h partition_header_check, in front of bert_hip_index_partition_load): 0 and
+ * fields = {version, dim, n_lists, n_part}; -1 and the reason in err otherwise.                                             */
+BERT_API int32_t bert_hip_test_partition_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err,
+                                                int32_t err_cap);
 
 /* The list tables of a partitioned index (partition.h build_lists; bert_hip.h "cluster partition"): offsets[n_lists + 1] and
  * order[up to n] from list_of[n] by a stable counting sort, entries outside [0, n_lists) in no list.  Returns the number of

@@ -29,6 +29,12 @@ dim 384, f16 and i8 rows, n_lists = 1024, Q = 1 and 4096, k = 10): the time of B
 and the probed search (bert_hip_index_search_probed_device) with nprobe = 1, 8, 32, 128 from the same run, each as median
 (min .. max) and as a ratio to the plain line, with recall@10 against the plain search's ids beside it.
     python tools/search_rate.py --sections probe --out profiles/search_probe_rate.txt
+
+Section "probe_filter" (not part of the default; the corpus and the partition of "probe", f16 and i8 rows, nprobe = 8, Q = 1 and
+4096, k = 10): the probed search without a list (bert_hip_index_search_probed_device), then
+bert_hip_index_search_probed_filtered_device with allow-lists of density 1.0, 0.1 and 0.01 (rows allowed at random), each as
+median (min .. max) and as a ratio to the unfiltered probed line of the same run.
+    python tools/search_rate.py --sections probe_filter --out profiles/search_probe_filter_rate.txt
 """
 import argparse
 import os
@@ -191,6 +197,58 @@ def probe_section(a, m, N, out, timed, torch, dev, sp):
         ix.close()
 
 
+def probe_filter_section(a, m, N, out, timed, torch, dev, sp):
+    """search_probed_filtered_device against search_probed_device on the same partitioned index: what an allow-list costs or saves"""
+    from bert_cpp_amd import pybert
+    dim, k, n_lists, n_centres, sigma, nprobe = 384, 10, 1024, 4096, 0.04, 8
+    out(f"# search_probed_filtered_device against search_probed_device, N = {N} rows in {n_centres} clusters (unit rows of centre + {sigma} * noise), "
+        f"dim {dim}, n_lists = {n_lists}, nprobe = {nprobe}, k = {k}; allow-list of the given density, rows allowed at random; "
+        f"ms = median (min .. max) of {a.iters}")
+    out("# dtype     Q  allow-list                    qualifying |      ms (min .. max)        x unfiltered probed")
+    g = torch.Generator(device=dev).manual_seed(dim)
+    centres = torch.randn(n_centres, dim, device=dev, generator=g)
+    centres /= centres.norm(dim=1, keepdim=True)
+
+    def draw(n):
+        x = centres[torch.randint(0, n_centres, (n,), device=dev, generator=g)] + sigma * torch.randn(n, dim, device=dev, generator=g)
+        return x / x.norm(dim=1, keepdim=True)
+
+    C, Qall = draw(N), draw(4096)
+    rng = np.random.default_rng(1)
+    lists = [("none (search_probed_device)", None)] + [(f"{d}" + ("" if d == 1.0 else " random"), np.ones(N, bool) if d == 1.0 else rng.random(N) < d)
+                                                       for d in (1.0, 0.1, 0.01)]
+    cents = None
+    for dtype in ("f16", "i8"):
+        ix = m.index(dim=dim, dtype=dtype)
+        ix.reserve(N, 4096, k)
+        ix.add_device(N, C.data_ptr(), sp)
+        torch.cuda.synchronize()
+        # (the centroids are trained once, on the f16 rows, and installed into both indexes)
+        if cents is None:
+            cents = ix.train_partition(n_lists, n_iter=10, seed=0)
+        else:
+            ix.partition(cents)
+        for Q in (1, 4096):
+            q = Qall[:Q].contiguous()
+            ids = torch.empty(Q, k, dtype=torch.int32, device=dev)
+            sc = torch.empty(Q, k, dtype=torch.float32, device=dev)
+            base = None
+            for name, keep in lists:
+                if keep is None:
+                    t, lo, hi = timed(lambda: ix.search_probed_device(Q, q.data_ptr(), nprobe, k, ids.data_ptr(), sc.data_ptr(), sp))
+                    base, n_q = t, N
+                else:
+                    words = torch.from_numpy(pybert.allow_words(keep, N).view(np.int32)).to(dev)
+                    t, lo, hi = timed(lambda: ix.search_probed_device(Q, q.data_ptr(), nprobe, k, ids.data_ptr(), sc.data_ptr(), sp,
+                                                                      d_allow_ptr=words.data_ptr(), n_words=words.numel()))
+                    n_q = int(keep.sum())
+                    # (every returned row is an allowed one)
+                    got = ids.cpu().numpy()
+                    assert keep[got[got >= 0]].all(), name
+                out(f"{dtype:7s} {Q:5d}  {name:29s} {n_q:9d} | {t:8.3f} ({lo:7.3f} .. {hi:7.3f})  {t / base:6.2f}")
+        ix.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -311,6 +369,9 @@ def main():
 
     if "probe" in sections:
         probe_section(a, m, N, out, timed, torch, dev, sp)
+
+    if "probe_filter" in sections:
+        probe_filter_section(a, m, N, out, timed, torch, dev, sp)
 
     # strings in, index rows out: add_texts against encode_batch + add
     if "texts" in sections:
