@@ -68,7 +68,7 @@ int Engine::check(std::string &err) {
 void Engine::set_option(const std::string &key, const std::string &value) {
     if (key == "profile_replay") { prof_.set_replay(value); return; }
     (void)hipSetDevice(device_);
-    if (!test_poison_option(key, ctx_)) opt_.set(key, value, w_->naive_images(), w_->fold_images);
+    if (!test_poison_option(key, ctx_, y_)) opt_.set(key, value, w_->naive_images(), w_->fold_images);
 }
 
 bool Engine::ensure_workspace(int t_pad, int n_sentences, std::string &err) {
@@ -274,7 +274,8 @@ void Engine::forward_latency(const Plan &p) {
 
 // All layers in one launch, a workgroup per window (model_kernel.hip) — the two fused kernels' bodies as phases, no kernel boundary
 // to put the workgroups back in step.  Batches of FULL windows (every sentence exactly 128 tokens: T = 128 B) take the specialised
-// form (every window is one whole sentence, whatever list the caller built).
+// form (every window is one whole sentence, whatever list the caller built); between its layers the residual crosses in lane order through
+// the y workspace, which this route uses for nothing else (not through ctx: the full form must not touch that one at all).
 void Engine::forward_one_launch(const Plan &p) {
     const int H = hp_.n_embd, I = hp_.n_intermediate;
     ModelLayerWeights mw[MODEL_MAX_LAYERS];          // (plan(): model_kernel_supported refuses more layers)
@@ -284,7 +285,7 @@ void Engine::forward_one_launch(const Plan &p) {
                   L.ffi_b.as<float>(), L.ffo_b.as<float>(), L.ln_out_w.as<float>(), L.ln_out_b.as<float>()};
     }
     timed("model_kernel", hp_.n_layer * (2.0 * p.T * 3 * H * H + 4.0 * p.T * p.max_len * H + 2.0 * p.T * H * H + 4.0 * p.T * H * I), p.s, [&] {
-        launch_model_kernel(mw, hp_.n_layer, x_.as<half_t>(), ctx_.as<half_t>(), p.cu, p.B, p.T, p.windows, p.n_windows, p.n_windows_dev, hp_.n_head,
+        launch_model_kernel(mw, hp_.n_layer, x_.as<half_t>(), ctx_.as<half_t>(), y_.as<half_t>(), p.cu, p.B, p.T, p.windows, p.n_windows, p.n_windows_dev, hp_.n_head,
                             p.out, p.max_len, status_.as<int>(), p.pool_mode, p.slots, p.s);
     });
 }

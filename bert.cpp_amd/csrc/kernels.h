@@ -84,11 +84,12 @@ struct ModelLayerWeights {
 };
 bool model_kernel_supported(const GemmWeight &Wqkv, const GemmWeight &Wo, const GemmWeight &W1, const GemmWeight &W2, int n_layer,
                             int n_head, int d_head, int max_len);
-// x: in = embeddings + LayerNorm, out = the last layer's output; ctx: workspace [T][H].  groups / n_groups / n_groups_dev: the
+// x: in = embeddings + LayerNorm, out = the last layer's output; ctx: workspace [T][H] (the ragged form's); xres: workspace [T][H] (full
+// windows: the residual between the layers' tails in lane order; no other route's data survives in it).  groups / n_groups / n_groups_dev: the
 // window list as for launch_qkv_attention2 (nullptr: one sentence per window); n_tokens = 128 n_sentences selects the form
 // specialised for full windows.  pooled != nullptr: the workgroups also pool and normalise their sentences (launch_pool_normalize's
 // arguments and bits: [n_sentences][H] f32, max_len, status word, pool_mode).
-void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x, half_t *ctx, const int32_t *cu_seqlens, int n_sentences,
+void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x, half_t *ctx, half_t *xres, const int32_t *cu_seqlens, int n_sentences,
                          int n_tokens, const int2 *groups, int n_groups, const int *n_groups_dev, int n_head, float *pooled, int max_len,
                          int *status, int pool_mode, int slots, hipStream_t stream);
 // The latency route (skinny.hip): the weight mat-muls of a layer split by output features AND token blocks over up to 192

@@ -142,11 +142,23 @@ __device__ __forceinline__ f32x16 mfma16(const f16x8 &a, const f16x8 &b, const f
 // ADDITION to storing them (the next tail's residual, the pooling and the other routes read x).  The U waves leave `xnext` alone.
 // CTXREGS (model_kernel.hip, full windows): `a.ctx` is not read.  The caller hands the attention context over as the operand fragments
 // `cf` (qkv_attention2_body's CTXREGS: same waves, same lanes, same tokens); the last two heads' four are in LDS at ctx_edge_offset.
-template <int NT, int WT, bool RAGGED, bool HANDOVER, bool CTXREGS = false>
+// XRES_IN / XRES_OUT (model_kernel.hip, full windows): the residual x may cross between two tails of the SAME workgroup in LANE ORDER, through
+// the scratch rows `xres` ([T_pad][H] halves, the pair's 32 rows as one 8 NT KiB block) instead of the row-major a.x / a.out: result fragment
+// (n, s) of LayerNorm 2 — D's lane (l31, hi): features 32 n + 16 s + 4 hi + {0..3, 8..11} of token l31 — is 1 KiB, lane l's 16 bytes at
+// ((2 n + s) 64 + l) 16 of the block.  Those are the halves the next tail's prologue wants in the same lane as its residual, for both roles:
+// xv[b][2 s] | xv[b][2 s + 1] of role r = fragment (4 (b >> 1) + 2 r + (b & 1), s).  So D stores its fragments straight from registers (no
+// staging in LDS, no transposition, none of the two barriers around it, no store loop in either role) and the next prologue loads 4 NT
+// fragments where it loaded 8 NT quarter rows: contiguous 1 KiB wave-instructions on both sides.  `lane_in` / `lane_out` (wave-uniform,
+// the same for every wave of the workgroup: both roles drop the same barriers) say which order this call reads and writes; a form
+// compiled without XRES_IN / XRES_OUT ignores them, and a.x / a.out are untouched by a side that runs in lane order.
+template <int NT, int WT, bool RAGGED, bool HANDOVER, bool CTXREGS = false, bool XRES_IN = false, bool XRES_OUT = false>
 __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, const int tok0, const int rows, const int tid,
-                                                [[maybe_unused]] f16x8 (&xnext)[8 * NT], [[maybe_unused]] const f16x8 *cf = nullptr) {
+                                                [[maybe_unused]] f16x8 (&xnext)[8 * NT], [[maybe_unused]] const f16x8 *cf = nullptr,
+                                                [[maybe_unused]] half_t *xres = nullptr, const bool lane_in = false, const bool lane_out = false) {
     static_assert(!(HANDOVER && RAGGED), "a ragged window's rows are packed: its lanes are not the window phase's slots");
     static_assert(!(CTXREGS && RAGGED), "a ragged window's rows are packed: its lanes are not the attention waves' queries");
+    static_assert(!((XRES_IN || XRES_OUT) && (RAGGED || WT != GW_F16)), "lane order: full windows (a pair owns its 32 rows), f16 weights");
+    const bool xres_out = XRES_OUT && lane_out;
     constexpr bool Q4 = WT != GW_F16;
     constexpr int VMQ = Q4 ? 63 : 0;                          // (q4: no LDS-DMA in flight, nothing for a barrier to wait for)
     constexpr int H = 128 * NT, NBH = 2 * NT, NB = 4 * NT, NQ = 8 * NT, NYH = 4 * NT;
@@ -195,7 +207,37 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
     // from LDS behind the first barrier: requesting both from HBM at once needs 144 registers next to the 96 of the context.
     f32x16 accp[NBH];
     f16x4 xv[NBH][4];
-    {
+    if constexpr (XRES_IN) {
+        // Lane order: the fragments D stored a layer ago, own features only.  A call that gets rows (the first layer: the embedding
+        // kernel's) takes them to the scratch itself first — this wave's quarter rows as the fragments this wave loads below, same lanes, so
+        // nobody else's stores are waited for — and then reads them like every other layer: ONE sequence of loads into xv.  (With the two
+        // orders as the arms of a branch that both define xv, model_kernel<3, false> keeps one register too few through the out-projection
+        // and reloads a context fragment from scratch inside two of its intervals.)  One more round trip to the L2 per launch.
+        char *const xb = (char *)(xres + (size_t)tok_w * H);     // (scalar base + the lane's 32-bit offset: no 64-bit address per lane)
+        const unsigned xl = (unsigned)lane * 16u;
+        if (!lane_in) {
+            const half_t *xr = a.x + (size_t)row_l * H + role * 64 + 4 * hi;
+#pragma unroll
+            for (int b = 0; b < NBH; ++b)
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const f16x4 lo = *(const f16x4 *)(xr + (b >> 1) * 128 + (b & 1) * 32 + 16 * s), up = *(const f16x4 *)(xr + (b >> 1) * 128 + (b & 1) * 32 + 16 * s + 8);
+                    f16x8 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { v[e] = lo[e]; v[4 + e] = up[e]; }
+                    *(f16x8 *)(xb + (2 * (4 * (b >> 1) + 2 * role + (b & 1)) + s) * 1024 + xl) = v;
+                }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the loads below: behind this wave's own stores)
+        }
+#pragma unroll
+        for (int b = 0; b < NBH; ++b)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const f16x8 v = *(const f16x8 *)(xb + (2 * (4 * (b >> 1) + 2 * role + (b & 1)) + s) * 1024 + xl);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { xv[b][2 * s][e] = v[e]; xv[b][2 * s + 1][e] = v[4 + e]; }
+            }
+    } else {
         const half_t *xr = a.x + (size_t)row_l * H + role * 64 + 4 * hi;
 #pragma unroll
         for (int b = 0; b < NBH; ++b)
@@ -713,10 +755,12 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
             }
         });
         static_assert(LAGT > NG, "U needs an idle interval to hand its half of y over");
-        // LayerNorm 2 is D's; U stores half of the rows below
-        asm volatile("s_barrier" ::: "memory");                                   // [E0] every D wave has taken U's half of y in
-        asm volatile("s_barrier" ::: "memory");                                   // [E1] D's rows are staged
-        store_rows();
+        // LayerNorm 2 is D's; U stores half of the rows below (lane order out: D stores its fragments itself, nothing is staged, U is done)
+        if (!xres_out) {
+            asm volatile("s_barrier" ::: "memory");                               // [E0] every D wave has taken U's half of y in
+            asm volatile("s_barrier" ::: "memory");                               // [E1] D's rows are staged
+            store_rows();
+        }
         // (HANDOVER: the fragments are D's.  Named here as written — by no instruction — or the caller's loop carries whatever they held
         // a layer ago through this whole branch: 8 NT x 4 registers that U does not have)
         if constexpr (HANDOVER) {
@@ -880,6 +924,44 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
 #pragma unroll
                         for (int e = 0; e < 8; ++e) acc2[4 * n3 + (m >> 1)][8 * (m & 1) + e] += (float)yu[m][e];
                     asm volatile("" ::: "memory");
+                }
+            }
+            // Lane order out: every fragment, as it is, to its KiB of the pair's block of xres, and D is done.  Nothing is staged, so there is
+            // no [E0] / [E1] (U skips them too) and no store loop.  (The text of the rows' loop below, apart from where a fragment goes: kept
+            // apart from it, so that the forms without XRES_OUT keep their machine code.)
+            if constexpr (XRES_OUT) {
+                if (xres_out) {
+                    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                    for (int n = 0; n < NB; ++n)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) { s1 += acc2[n][r]; s2 = __builtin_fmaf(acc2[n][r], acc2[n][r], s2); }
+                    s1 += __shfl_xor(s1, 32);
+                    s2 += __shfl_xor(s2, 32);
+                    float rstd, nmr;
+                    layernorm_scale(s1, s2, 1.0f / H, rstd, nmr);
+                    char *const xb = (char *)(xres + (size_t)tok_w * H);      // (scalar base + the lane's 32-bit offset)
+                    const unsigned xl = (unsigned)lane * 16u;
+#pragma unroll
+                    for (int n = 0; n < NB; ++n) {
+                        f32x4 gv[4], bv[4];
+#pragma unroll
+                        for (int g4 = 0; g4 < 4; ++g4) { gv[g4] = *(const f32x4 *)(cg2 + 32 * n + 8 * g4 + 4 * hi); bv[g4] = *(const f32x4 *)(cbe2 + 32 * n + 8 * g4 + 4 * hi); }
+#pragma unroll
+                        for (int s = 0; s < 2; ++s) {
+                            const int q = 2 * n + s;
+                            f16x8 o;
+#pragma unroll
+                            for (int hq = 0; hq < 2; ++hq)
+#pragma unroll
+                                for (int e = 0; e < 4; ++e)
+                                    o[4 * hq + e] = (_Float16)rounded_f32(__builtin_fmaf(acc2[n][8 * s + 4 * hq + e], gv[2 * s + hq][e] * rstd, __builtin_fmaf(gv[2 * s + hq][e], nmr, bv[2 * s + hq][e])));
+                            *(f16x8 *)(xb + q * 1024 + xl) = o;
+                            if constexpr (HANDOVER) xnext[q] = result_to_operand_fragment(o);
+                        }
+                        asm volatile("" ::: "memory");          // (one block's parameters at a time)
+                    }
+                    return;
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // [E0] the staging below overwrites other pairs' areas

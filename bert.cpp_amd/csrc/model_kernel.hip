@@ -13,10 +13,12 @@
 // global stores and loads of the SAME workgroup: 96 KiB each, behind a workgroup-scope fence (one L1 per CU, shared by the
 // workgroup's waves: no invalidate needed outside threadgroup-split mode); on full windows x ALSO crosses in registers and ctx crosses
 // ONLY on chip, in registers and through LDS (the layer loop below), so neither phase waits for a round trip of its own data, and no ctx
-// is stored at all.  The global hand-overs (the ragged form's both, the full form's x stores) do NOT stay inside the XCD's L2: 256
+// is stored at all; what the next tail needs of x as its residual crosses through a scratch workspace in LANE ORDER (LayerNorm 2's
+// result fragments as they are: the layer loop below), so the full form stores rows of x after its last layer only.  The global
+// hand-overs (the ragged form's both, the full form's residual fragments) do NOT stay inside the XCD's L2: 256
 // workgroups x 192 KiB = 48 MiB per layer against 32 MiB of L2, and every store leaves the L2 towards the fabric anyway —
 // measured 313 MB written and 1.06 GB of fabric traffic per launch with both edges through memory (profiles/r3_pmc.txt), 164 MB and
-// 0.52 GB for the full form as it stands (profiles/traffic.json), absorbed by the Infinity Cache at
+// 0.52 GB for the full form with x stored as rows by every layer (profiles/traffic.json), absorbed by the Infinity Cache at
 // about 1.3 TB/s: far from a limit, but not free.  What the single launch removes is the lockstep, not the bytes.
 // Full form only: the kernel trusts n_tokens = 128 n_sentences to mean "every sentence is exactly 128 tokens"; that holds
 // whenever the caller's max_len promise (<= 128) does.  A batch that breaks it is flagged by the pooling guard (status word),
@@ -60,6 +62,8 @@ struct ModelArgs {
     int *status;                     // pooling's status word (a sentence outside [1, max_len])
     int max_len, pool_mode;          // pool_mode: kernels.h POOL_CLS | POOL_RAW, read by the epilogue alone (POOL_MODES forms)
     ModelLayerArgs layer[MODEL_MAX_LAYERS];
+    half_t *xres;                    // FULL windows: [T][H] scratch, the residual x between two tails in lane order (layer_tail_body's XRES_IN /
+                                     // XRES_OUT); behind everything else: the ragged form, which ignores it, finds its arguments where they were
 };
 
 }  // namespace
@@ -108,13 +112,15 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
         q.out = m.ctx; q.n_head = m.n_head; q.n_sent = m.n_sent; q.spw = 1; q.slot_mask = m.slot_mask;
         qkv_attention2_body<2 * NT, NT, GW_F16, !RAGGED, decltype(xregs_tag)::value, !RAGGED>(q, smem, window, tid, xf, cf);
     };
-    auto tail_phase = [&](const ModelLayerArgs &L, f16x8 (&xf)[8 * NT], const f16x8 *cf) __attribute__((always_inline)) {
+    auto tail_phase = [&](const ModelLayerArgs &L, f16x8 (&xf)[8 * NT], const f16x8 *cf, [[maybe_unused]] const bool lane_in,
+                          [[maybe_unused]] const bool lane_out) __attribute__((always_inline)) {
         const int tid = thread_id();
         TailArgs t;
         t.ctx = m.ctx; t.x = m.x; t.wo = L.wo; t.w1p = L.w1p; t.w2p = L.w2p;
         t.wo_qs = t.w1_qs = t.w2_qs = nullptr; t.wo_sc = t.w1_sc = t.w2_sc = nullptr;
         t.bo = L.bo; t.g1 = L.g1; t.be1 = L.be1; t.b1 = L.b1; t.b2 = L.b2; t.g2 = L.g2; t.be2 = L.be2; t.out = m.x; t.I = m.I;
-        layer_tail_body<NT, GW_F16, RAGGED, !RAGGED, !RAGGED>(t, smem, tok0, rows, tid, xf, cf);
+        if constexpr (RAGGED) layer_tail_body<NT, GW_F16, true, false, false>(t, smem, tok0, rows, tid, xf, cf);
+        else layer_tail_body<NT, GW_F16, false, true, true, true, true>(t, smem, tok0, rows, tid, xf, cf, m.xres, lane_in, lane_out);
     };
     // Phase edge: everything the phase stored (ragged windows: ctx by the attention waves; x by all waves) is visible to the workgroup, every
     // LDS access of the phase has returned (the next phase's first DMA pieces overwrite what the others were reading).  On full windows
@@ -132,7 +138,7 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
             window_phase(m.layer[l], std::false_type{}, nullptr, nullptr);
             hand_over();
             MK_STAMP(1 + 2 * l);
-            tail_phase(m.layer[l], none, nullptr);
+            tail_phase(m.layer[l], none, nullptr, false, false);
             hand_over();
             MK_STAMP(2 + 2 * l);
         }
@@ -140,7 +146,7 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
         // Full windows: the tail's D waves 4..7 end with the rows of x they have just normalised in registers, and the same waves, as
         // the next layer's projection waves, start from those rows — same lanes, same tokens, the f16 values that are stored: LayerNorm 2
         // hands them over as operand fragments (layer_tail_body's HANDOVER) and the window phases of layers 1 .. L-1 load no x at all
-        // (the stores stay: the next tail's residual and the pooling read x).  The loop is rotated — layer 0's window phase in front,
+        // (the residual of the next tail and the pooling still read what is stored: below).  The loop is rotated — layer 0's window phase in front,
         // then tail(l) -> window(l + 1) per turn — so that the fragments are born and consumed inside ONE turn: declared outside, the
         // U waves' path (which does not write them) would carry 96 registers round the loop and through the tail.
         //
@@ -161,13 +167,21 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
         //                           waited for inside the window phase)
         // `cf` is written by every wave in the window phase and read by every wave in the tail, so it lives across the back edge for what it
         // is; where no window phase follows it is named as written, or the last tail would carry the fragments it has consumed.
+        //
+        // The residual x of tail(l + 1) is what LayerNorm 2 of tail(l) wrote, and only this workgroup reads it before the pooling: between two
+        // tails it crosses in LANE ORDER through m.xres (layer_tail_body's XRES_IN / XRES_OUT: D's result fragments as they are, 1 KiB per
+        // wave-instruction on both sides, no staging in LDS, no barriers around it, no row stores), behind the same two phase edges as before.
+        //     layer 0:          rows in (the embedding kernel's m.x), lane order out
+        //     layers 1 .. L-2:  lane order in and out: m.x is neither read nor written
+        //     layer L-1:        lane order in, rows out (the pooling below and the caller read m.x); L = 1: rows in and out
+        // Every fragment a tail loads was stored by the tail before it in the same launch (tests: the scratch poisoned with NaNs).
         f16x8 cf[8 * NT];
         if (n_layer > 0) window_phase(m.layer[0], std::false_type{}, nullptr, cf);
         for (int l = 0; l < n_layer; ++l) {
             hand_over();
             MK_STAMP(1 + 2 * l);
             f16x8 xf[8 * NT];
-            tail_phase(m.layer[l], xf, cf);
+            tail_phase(m.layer[l], xf, cf, l > 0, l + 1 < n_layer);
             hand_over();
             MK_STAMP(2 + 2 * l);
             if (l + 1 < n_layer) window_phase(m.layer[l + 1], std::true_type{}, xf, cf);
@@ -205,12 +219,12 @@ bool model_kernel_supported(const GemmWeight &Wqkv, const GemmWeight &Wo, const 
            Wqkv.type == GW_F16 && Wo.type == GW_F16 && qkv_attention2_supported(Wqkv, n_head, d_head, max_len) && layer_tail_supported(Wo, W1, W2);
 }
 
-void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x, half_t *ctx, const int32_t *cu_seqlens, int n_sentences,
+void launch_model_kernel(const ModelLayerWeights *layers, int n_layer, half_t *x, half_t *ctx, half_t *xres, const int32_t *cu_seqlens, int n_sentences,
                          int n_tokens, const int2 *groups, int n_groups, const int *n_groups_dev, int n_head, float *pooled, int max_len,
                          int *status, int pool_mode, int slots, hipStream_t stream) {
     ModelArgs m;
     m.pooled = pooled; m.status = status; m.max_len = max_len; m.pool_mode = pool_mode;
-    m.x = x; m.ctx = ctx; m.cu = cu_seqlens; m.groups = groups; m.n_groups = n_groups_dev;
+    m.x = x; m.ctx = ctx; m.xres = xres; m.cu = cu_seqlens; m.groups = groups; m.n_groups = n_groups_dev;
     m.n_layer = n_layer; m.n_head = n_head; m.n_sent = n_sentences; m.I = layers[0].W1->N; m.slot_mask = slots - 1;
     for (int l = 0; l < n_layer; ++l) {
         const ModelLayerWeights &s = layers[l];

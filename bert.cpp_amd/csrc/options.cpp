@@ -1,5 +1,5 @@
 // options.cpp — see options.h.  The one translation unit that is compiled twice: libbert_test.so's copy (-DBERT_HIP_TEST_ROUTES)
-// also understands the whole-model "naive" route and "test_poison_ctx".
+// also understands the whole-model "naive" route, "test_poison_ctx" and "test_poison_xres".
 #include "options.h"
 
 #include <cstdio>
@@ -87,10 +87,11 @@ void EngineOptions::set(const std::string &key, const std::string &value, bool n
     else apply(key, value);
 }
 
-bool test_poison_option(const std::string &key, const DevBuf &ctx) {
-    if (!TEST_ROUTES || key != "test_poison_ctx") return false;
+bool test_poison_option(const std::string &key, const DevBuf &ctx, const DevBuf &xres) {
+    if (!TEST_ROUTES || (key != "test_poison_ctx" && key != "test_poison_xres")) return false;
+    const DevBuf &buf = key == "test_poison_ctx" ? ctx : xres;
     (void)hipDeviceSynchronize();
-    if (ctx.p) (void)hipMemset(ctx.p, 0xFF, ctx.bytes);
+    if (buf.p) (void)hipMemset(buf.p, 0xFF, buf.bytes);
     (void)hipDeviceSynchronize();
     return true;
 }

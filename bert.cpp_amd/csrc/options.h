@@ -40,7 +40,8 @@ private:
 };
 
 // "test_poison_ctx" (libbert_test.so only; false, doing nothing, in libbert.so): every half of the attention-context workspace
-// becomes a NaN, so a pass that still reads what it has not written itself shows it in its results
-bool test_poison_option(const std::string &key, const DevBuf &ctx);
+// becomes a NaN, so a pass that still reads what it has not written itself shows it in its results.  "test_poison_xres": the same for the
+// workspace through which the one-launch kernel's full form passes the residual between its layers (the engine's y rows)
+bool test_poison_option(const std::string &key, const DevBuf &ctx, const DevBuf &xres);
 
 }  // namespace bert_hip
