@@ -68,7 +68,7 @@ int Engine::check(std::string &err) {
 void Engine::set_option(const std::string &key, const std::string &value) {
     if (key == "profile_replay") { prof_.set_replay(value); return; }
     (void)hipSetDevice(device_);
-    if (!test_poison_option(key, ctx_, y_)) opt_.set(key, value, w_->naive_images(), w_->fold_images);
+    if (!test_poison_option(key, ctx_, y_, {&x_, &qkv_, &ctx_, &y_, &ff_, &v32_, &ln_stats1_, &ln_stats2_, &ln_rows1_, &ln_rows2_, &d_hidden_})) opt_.set(key, value, w_->naive_images(), w_->fold_images);
 }
 
 bool Engine::ensure_workspace(int t_pad, int n_sentences, std::string &err) {

@@ -1,5 +1,5 @@
 // options.cpp — see options.h.  The one translation unit that is compiled twice: libbert_test.so's copy (-DBERT_HIP_TEST_ROUTES)
-// also understands the whole-model "naive" route, "test_poison_ctx" and "test_poison_xres".
+// also understands the whole-model "naive" route and the "test_poison_*" keys.
 #include "options.h"
 
 #include <cstdio>
@@ -87,11 +87,12 @@ void EngineOptions::set(const std::string &key, const std::string &value, bool n
     else apply(key, value);
 }
 
-bool test_poison_option(const std::string &key, const DevBuf &ctx, const DevBuf &xres) {
-    if (!TEST_ROUTES || (key != "test_poison_ctx" && key != "test_poison_xres")) return false;
-    const DevBuf &buf = key == "test_poison_ctx" ? ctx : xres;
+bool test_poison_option(const std::string &key, const DevBuf &ctx, const DevBuf &xres, std::initializer_list<const DevBuf *> workspace) {
+    if (!TEST_ROUTES || (key != "test_poison_ctx" && key != "test_poison_xres" && key != "test_poison_workspace")) return false;
+    auto poison = [](const DevBuf &buf) { if (buf.p) (void)hipMemset(buf.p, 0xFF, buf.bytes); };
     (void)hipDeviceSynchronize();
-    if (buf.p) (void)hipMemset(buf.p, 0xFF, buf.bytes);
+    if (key == "test_poison_workspace") for (const DevBuf *buf : workspace) poison(*buf);
+    else poison(key == "test_poison_ctx" ? ctx : xres);
     (void)hipDeviceSynchronize();
     return true;
 }

@@ -1,6 +1,7 @@
 // options.h — the switches of an engine, and their two spellings: the BERT_HIP_* environment (read once, when a model loads)
 // and the keys of bert_hip_set_option.  INTEGRATION.md lists both for users.
 #pragma once
+#include <initializer_list>
 #include <string>
 
 #include "model_file.h"
@@ -41,7 +42,14 @@ private:
 
 // "test_poison_ctx" (libbert_test.so only; false, doing nothing, in libbert.so): every half of the attention-context workspace
 // becomes a NaN, so a pass that still reads what it has not written itself shows it in its results.  "test_poison_xres": the same for the
-// workspace through which the one-launch kernel's full form passes the residual between its layers (the engine's y rows)
-bool test_poison_option(const std::string &key, const DevBuf &ctx, const DevBuf &xres);
+// workspace through which the one-launch kernel's full form passes the residual between its layers (the engine's y rows).
+// "test_poison_workspace": the same for every activation scratch buffer of the engine at once (`workspace`: x, qkv, ctx, y, the
+// intermediate, the latency route's f32 rows, the LayerNorm fold's partial statistics and finalized rows, the hidden-state tap's
+// rows; f32 words on the f32 route, where 0xFF bytes are a NaN as well) — a pass may depend on nothing it finds in any of them:
+// not on the rows behind its last token, not on rows a kernel of its own has yet to write.  Left out: the buffers a pass does not
+// compute (token ids, cu_seqlens, the staged input blocks, the window list, the embeddings and the status words).  The engine has no
+// buffer that it fills once and then relies on across passes (DevBuf::ensure zero-fills what it allocates, and no kernel may count on
+// those zeros: the first pass that reaches a row overwrites them), so nothing else is exempt.
+bool test_poison_option(const std::string &key, const DevBuf &ctx, const DevBuf &xres, std::initializer_list<const DevBuf *> workspace);
 
 }  // namespace bert_hip

@@ -43,6 +43,18 @@ static bool upload_padded(DevBuf &d, const T *src, int M, int M_pad, int cols, T
     return d.upload(h, err);
 }
 
+// bert_hip_test_set_pad: what the batch-route entries put where a call writes nothing before the first launch (0, 0: zeros, the
+// state DevBuf::alloc leaves).  The engine's workspaces hold whatever an earlier pass left there.
+static uint16_t g_pad16 = 0;
+static uint32_t g_pad32 = 0;
+// rows [M][cols] of f16 bits (src == nullptr: none) -> device rows [M_pad][cols], the rows behind them holding the 16-bit pattern
+static bool upload_rows16(DevBuf &d, const uint16_t *src, int M, int M_pad, int cols, std::string &err) {
+    return upload_padded(d, src, src ? M : 0, M_pad, cols, g_pad16, err);
+}
+// an output or intermediate buffer of n 16-bit / 32-bit words, every word the pattern
+static bool alloc_pad16(DevBuf &d, size_t n, std::string &err) { return g_pad16 ? upload_padded<uint16_t>(d, nullptr, 0, 1, (int)n, g_pad16, err) : d.alloc(n * 2, err); }
+static bool alloc_pad32(DevBuf &d, size_t n, std::string &err) { return g_pad32 ? upload_padded<uint32_t>(d, nullptr, 0, 1, (int)n, g_pad32, err) : d.alloc(n * 4, err); }
+
 // the matrices and parameter vectors of a layer tail on the device, from file-layout bytes (W1, W2 also in the k order of w16p)
 struct TailOperands {
     GemmWeightStore wo, w1, w2;
@@ -81,14 +93,10 @@ int32_t bert_hip_test_gemm(int32_t M, int32_t N, int32_t K, const uint16_t *A, c
     if (impl != 1 && !ws.mfma_ok) { fprintf(stderr, "bert_hip_test_gemm: shape not supported by the MFMA path\n"); return -2; }
     const int M_pad = impl == 3 ? (M + 255) / 256 * 256 : (M + GEMM_BM - 1) / GEMM_BM * GEMM_BM;
     DevBuf dA, dB, dR, dC;
-    if (!dA.alloc((size_t)M_pad * K * 2, err) || !dC.alloc((size_t)M_pad * N * 2, err) || !dB.upload(bias, (size_t)N * 4, err)) {
+    if (!upload_rows16(dA, A, M, M_pad, K, err) || !alloc_pad16(dC, (size_t)M_pad * N, err) || !dB.upload(bias, (size_t)N * 4, err) ||
+        (resid && !upload_rows16(dR, resid, M, M_pad, N, err))) {
         fprintf(stderr, "bert_hip_test_gemm: %s\n", err.c_str());
         return -1;
-    }
-    CK(hipMemcpy(dA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice));
-    if (resid) {
-        if (!dR.alloc((size_t)M_pad * N * 2, err)) return -1;
-        CK(hipMemcpy(dR.p, resid, (size_t)M * N * 2, hipMemcpyHostToDevice));
     }
     if (impl == 3) {
         if (!gemm256_supported(ws.w, M_pad)) return -2;
@@ -117,22 +125,23 @@ int32_t bert_hip_test_gemm_lnfold(int32_t M, int32_t K1, int32_t H, int32_t N2, 
     const int M_pad = (M + 255) / 256 * 256, P = 2 * H / 256;
     if (!gemm256_supported(w1.w, M_pad) || !gemm256_supported(w2.w, M_pad) || H % 256) return -2;
     DevBuf dA, dB1, dR, dU, dOut, dStats, dRows, dRowsRes;
-    if (!dA.alloc((size_t)M_pad * K1 * 2, err) || !dB1.upload(b1, (size_t)H * 4, err) || !dR.alloc((size_t)M_pad * H * 2, err) || !dU.alloc((size_t)M_pad * H * 2, err) ||
-        !dOut.alloc((size_t)M_pad * N2 * 2, err) || !dStats.alloc((size_t)M_pad * P * 8, err) || !dRows.alloc((size_t)M_pad * 16, err) || !dRowsRes.alloc((size_t)M_pad * 16, err)) return -1;
-    CK(hipMemcpy(dA.p, A1, (size_t)M * K1 * 2, hipMemcpyHostToDevice));
-    CK(hipMemcpy(dR.p, r, (size_t)M * H * 2, hipMemcpyHostToDevice));
+    if (!upload_rows16(dA, A1, M, M_pad, K1, err) || !dB1.upload(b1, (size_t)H * 4, err) || !upload_rows16(dR, r, M, M_pad, H, err) ||
+        !alloc_pad16(dU, (size_t)M_pad * H, err) || !alloc_pad16(dOut, (size_t)M_pad * N2, err) || !alloc_pad32(dStats, (size_t)M_pad * P * 2, err) ||
+        !alloc_pad32(dRows, (size_t)M_pad * 4, err) || (!rg && !alloc_pad32(dRowsRes, (size_t)M_pad * 4, err))) return -1;
     GemmLnFold ln;
     ln.flags = GemmLnFold::STATS; ln.stats = dStats.as<float2>();
     if (rg) {
         // the residual's own row statistics (what the mat-mul that produced r would have left behind), and the packed (gamma, beta + bias)
-        std::vector<float> rows((size_t)M_pad * 4, 0.f);
+        float pad_f;
+        memcpy(&pad_f, &g_pad32, 4);
+        std::vector<float> rows((size_t)M_pad * 4, pad_f);
         for (int t = 0; t < M; ++t) {
             double s1 = 0, s2 = 0;
             for (int f = 0; f < H; ++f) { _Float16 h; memcpy(&h, &r[(size_t)t * H + f], 2); s1 += (double)(float)h; s2 += (double)(float)h * (double)(float)h; }
             const double mean = s1 / H, var = std::max(s2 / H - mean * mean, 0.0) + 1e-5, sd = std::sqrt(var);
             rows[4 * (size_t)t] = (float)(1.0 / sd); rows[4 * (size_t)t + 1] = (float)(-mean / sd); rows[4 * (size_t)t + 2] = (float)-mean; rows[4 * (size_t)t + 3] = (float)sd;
         }
-        CK(hipMemcpy(dRowsRes.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+        if (!dRowsRes.upload(rows, err)) return -1;
         std::vector<uint32_t> v((size_t)H);
         for (int f = 0; f < H; ++f) {
             const _Float16 gg = (_Float16)rg[f], bb = (_Float16)(rb[f] + b1[f]);
@@ -162,9 +171,12 @@ int32_t bert_hip_test_attention(int32_t n_sentences, const int32_t *cu_seqlens, 
     const int T = cu_seqlens[n_sentences], H = n_head * d_head;
     int max_len = 0;
     for (int b = 0; b < n_sentences; ++b) max_len = std::max(max_len, cu_seqlens[b + 1] - cu_seqlens[b]);
+    // (whole token tiles, as in the engine's workspaces, and one key tile more: the kernel pads the LAST sentence's keys to 128 in LDS,
+    // not from memory, and one that loaded them would find the pattern there instead of leaving the buffer)
+    const int T_pad = (T + 255) / 256 * 256 + 128;
     DevBuf dq, dcu, dout;
-    if (!dq.upload(qkv, (size_t)T * 3 * H * 2, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
-        !dout.alloc((size_t)T * H * 2, err)) {
+    if (!upload_rows16(dq, qkv, T, T_pad, 3 * H, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
+        !alloc_pad16(dout, (size_t)T_pad * H, err)) {
         fprintf(stderr, "bert_hip_test_attention: %s\n", err.c_str());
         return -1;
     }
@@ -197,13 +209,14 @@ int32_t bert_hip_test_qkv_attention(int32_t n_sentences, const int32_t *cu_seqle
     if (!ws.build({&t}, PackOptions(), err)) { fprintf(stderr, "bert_hip_test_qkv_attention: %s\n", err.c_str()); return -1; }
     if (!ws.mfma_ok) return -2;
     DevBuf dx, dqkv, dcu, db, dout;
-    if (!dx.alloc((size_t)T_pad * H * 2, err) || !dqkv.alloc((size_t)T_pad * 3 * H * 2, err) ||
+    // (x and qkv: one window more than T_pad rows — the window kernel's empty slots must not read their own rows nor the attention
+    // kernel the keys behind the last sentence, and a kernel that did would find the pattern there instead of leaving the buffer)
+    if (!upload_rows16(dx, x, T, T_pad + 128, H, err) || !alloc_pad16(dqkv, (size_t)(T_pad + 128) * 3 * H, err) ||
         !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) || !db.upload(bias, (size_t)3 * H * 4, err) ||
-        !dout.alloc((size_t)T_pad * H * 2, err)) {
+        !alloc_pad16(dout, (size_t)T_pad * H, err)) {
         fprintf(stderr, "bert_hip_test_qkv_attention: %s\n", err.c_str());
         return -1;
     }
-    CK(hipMemcpy(dx.p, x, (size_t)T * H * 2, hipMemcpyHostToDevice));
     if (fused >= 2 && fused <= 4) {
         // second-generation kernel: 2 = next-fit windows of whole sentences, 3 = the uniform placement rule
         if (!qkv_attention2_supported(ws.w, n_head, d_head, max_len)) return -2;
@@ -253,13 +266,11 @@ int32_t bert_hip_test_layer_tail(int32_t M, int32_t H, int32_t I, const uint16_t
     if (const int r = w.build("bert_hip_test_layer_tail", H, I, Wo, W1, W2, wtype, bo, g1, be1, b1, b2, g2, be2)) return r;
     const int M_pad = (M + GEMM_BM - 1) / GEMM_BM * GEMM_BM;
     DevBuf dc, dx, dy, dout;
-    if (!dc.alloc((size_t)M_pad * H * 2, err) || !dx.alloc((size_t)M_pad * H * 2, err) || !dy.alloc((size_t)M_pad * H * 2, err) ||
-        !dout.alloc((size_t)M_pad * H * 2, err)) {
+    if (!upload_rows16(dc, ctx, M, M_pad, H, err) || !upload_rows16(dx, x, M, M_pad, H, err) || !alloc_pad16(dy, (size_t)M_pad * H, err) ||
+        !alloc_pad16(dout, (size_t)M_pad * H, err)) {
         fprintf(stderr, "bert_hip_test_layer_tail: %s\n", err.c_str());
         return -1;
     }
-    CK(hipMemcpy(dc.p, ctx, (size_t)M * H * 2, hipMemcpyHostToDevice));
-    CK(hipMemcpy(dx.p, x, (size_t)M * H * 2, hipMemcpyHostToDevice));
     if (impl == 1) {
         if (!layer_tail_supported(w.wo.w, w.w1.w, w.w2.w)) return -2;
         launch_layer_tail(w.wo.w, w.w1.w, w.w2.w, dc.as<half_t>(), dx.as<half_t>(), w.bo.as<float>(), w.g1.as<float>(), w.be1.as<float>(),
@@ -267,7 +278,7 @@ int32_t bert_hip_test_layer_tail(int32_t M, int32_t H, int32_t I, const uint16_t
     } else {
         // three GEMM kernels + two LayerNorm kernels
         DevBuf dff;
-        if (!dff.alloc((size_t)M_pad * I * 2, err)) return -1;
+        if (!alloc_pad16(dff, (size_t)M_pad * I, err)) return -1;
         launch_gemm_mfma(w.wo.w, dc.as<half_t>(), w.bo.as<float>(), dx.as<half_t>(), dy.as<half_t>(), M_pad, EPI_BIAS_RESID, nullptr);
         launch_layernorm(dy.as<half_t>(), w.g1.as<float>(), w.be1.as<float>(), M_pad, H, nullptr);
         launch_gemm_mfma(w.w1.w, dy.as<half_t>(), w.b1.as<float>(), nullptr, dff.as<half_t>(), M_pad, EPI_BIAS_GELU, nullptr);
@@ -481,6 +492,8 @@ int32_t bert_hip_test_build_windows(const int32_t *cu_seqlens, int32_t n_sentenc
 int32_t bert_hip_test_max_windows(int32_t n_sentences, int32_t n_tokens) { return qkv_attention2_max_windows(n_sentences, n_tokens, window_slots()); }
 
 int32_t bert_hip_test_set_window_slots(int32_t slots) { set_window_slots(slots); return window_slots(); }
+
+void bert_hip_test_set_pad(uint32_t pattern16, uint32_t pattern32) { g_pad16 = (uint16_t)pattern16; g_pad32 = pattern32; }
 
 int32_t bert_hip_test_build_windows_device(const int32_t *cu_seqlens, int32_t n_sentences, int32_t *windows) {
     std::string err;

@@ -5,6 +5,7 @@ not load, importing/constructing fails loudly.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -39,7 +40,7 @@ BERT_HIP_H_SYMBOLS = [
 BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_gemm", "bert_hip_test_gemm_lnfold", "bert_hip_test_attention", "bert_hip_test_qkv_attention",
     "bert_hip_test_layer_tail", "bert_hip_test_skinny_tail", "bert_hip_test_skinny_qkv", "bert_hip_test_shard_bounds", "bert_hip_test_build_windows",
-    "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots",
+    "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots", "bert_hip_test_set_pad",
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
     "bert_hip_test_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
@@ -197,6 +198,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_max_windows.argtypes = [i32, i32]
     L.bert_hip_test_set_window_slots.restype = i32
     L.bert_hip_test_set_window_slots.argtypes = [i32]
+    L.bert_hip_test_set_pad.restype = None
+    L.bert_hip_test_set_pad.argtypes = [C.c_uint32, C.c_uint32]
     L.bert_hip_test_build_windows_device.restype = i32
     L.bert_hip_test_build_windows_device.argtypes = [i32p, i32, i32p]
     L.bert_hip_test_shard_threads_created.restype = C.c_int64
@@ -302,6 +305,19 @@ def build_windows(cu_seqlens: np.ndarray, device: bool = False) -> List[tuple]:
 def set_window_slots(slots: int) -> int:
     """Place granularity of the windows in libbert_test.so (its own copy of the setting; a context's: set_option "window_slots")."""
     return int(test_lib().bert_hip_test_set_window_slots(slots))
+
+
+@contextlib.contextmanager
+def test_pad(pattern16: int, pattern32: int):
+    """While the block runs, the batch-route op entries (test_gemm, test_gemm_lnfold, test_attention, test_qkv_attention,
+    test_layer_tail) fill their padding rows and every output / intermediate buffer with these bit patterns before they launch
+    (include/bert_hip_test.h bert_hip_test_set_pad); zeros again afterwards."""
+    L = test_lib()
+    L.bert_hip_test_set_pad(pattern16, pattern32)
+    try:
+        yield
+    finally:
+        L.bert_hip_test_set_pad(0, 0)
 
 
 def max_windows(n_sentences: int, n_tokens: int) -> int:

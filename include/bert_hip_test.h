@@ -11,6 +11,19 @@
 extern "C" {
 #endif
 
+/* The batch-route kernels compute whole tiles of 128 or 256 tokens, and in the engine's grow-only workspaces the rows behind a
+ * call's last token (and every row a pass has not written yet) hold what an earlier pass left.  The entries below allocate per
+ * call; this process-wide setting is what they put where the engine would have stale data, BEFORE the first launch:
+ *   - rows M .. M_pad - 1 of every token-row input (A, resid, r and its row statistics, ctx, x; attention: the rows of qkv and of x
+ *     behind the last sentence, to the end of its tile and one tile of 128 more, which no kernel may read) hold pattern16
+ *     (pattern32 in 32-bit buffers);
+ *   - every output and intermediate buffer (C, u, out2, the partial statistics and finalized rows of the LayerNorm fold, qkv
+ *     between projection and attention, y and the intermediate of the five-kernel tail, every out) holds it in ALL its words.
+ * Entries: bert_hip_test_gemm, _gemm_lnfold, _attention, _qkv_attention, _layer_tail (the latency route's entries take a `pad`
+ * argument of their own).  0, 0 (the state at load): zeros, as before.  Quiet NaNs (0x7E00, 0x7FC00000) make any read of such a word
+ * show in the rows a call returns; to the kernels they are data.  Set it under try / finally: it outlives the call.          */
+BERT_API void bert_hip_test_set_pad(uint32_t pattern16, uint32_t pattern32);
+
 /* Standalone kernel entry points for op-level tests (host buffers in, host buffers out).
  * C[M][N] = epilogue(A[M][K] (f16 bits) x W[N][K]^T + bias); W given in file layout of `wtype`
  * (row-major f32 / f16 / block_q4_0 / block_q4_1 bytes).  epilogue: 0 bias, 1 bias+GELU(tanh),

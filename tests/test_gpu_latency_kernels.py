@@ -75,13 +75,6 @@ def _natural_order(ff):
     return np.ascontiguousarray(ff.reshape(M, I // 16, 4, 4)[:, :, [0, 2, 1, 3], :]).reshape(M, I)
 
 
-def _matmul_bound(A, W, bias, resid):
-    """f32 accumulation of exact f16 products, K + 2 terms in any order: (K + 4) 2^-24 S to first order, S the sum of the terms'
-    magnitudes; times 4 for the matrix cores' undocumented internal rounding."""
-    S = np.abs(ref.f8(A)) @ np.abs(ref.f8(W)).T + np.abs(ref.f8(bias)) + np.abs(ref.f8(resid))
-    return 4 * (A.shape[1] + 4) * 2.0 ** -24 * S, S
-
-
 @pytest.mark.parametrize("M,H,I", TAIL_CASES)
 def test_skinny_tail_has_the_one_launch_tail_s_bits_and_float64_parts(M, H, I):
     """PROJ, UP (LayerNorm 1 fused), DOWN, LayerNorm 2 as Engine::forward_latency launches them: the output has the bits of
@@ -101,7 +94,7 @@ def test_skinny_tail_has_the_one_launch_tail_s_bits_and_float64_parts(M, H, I):
     assert err.max() < 2.5e-2 and err.mean() < 2e-3, (float(err.max()), float(err.mean()))
 
     # out-projection: ctx Wo^T + bo + x, f32
-    bound, S = _matmul_bound(d["ctx"], d["Wo"], d["bo"], d["x"])
+    bound, S = ref.matmul_bound(d["ctx"], d["Wo"], d["bo"], d["x"])
     err = np.abs(ref.f8(p["v_proj"]) - (ref.f8(d["ctx"]) @ ref.f8(d["Wo"]).T + ref.f8(d["bo"]) + ref.f8(d["x"])))
     print(f"  v_proj err/S {(err / S).max():.3e} of {4 * (H + 4) * 2.0 ** -24:.3e}")
     assert (err <= bound).all(), ("v_proj", float((err / S).max()), np.argwhere(err > bound)[:5].tolist())
@@ -123,7 +116,7 @@ def test_skinny_tail_has_the_one_launch_tail_s_bits_and_float64_parts(M, H, I):
 
     # down-projection: ff W2^T + b2 + y, f32, on the ff and y the kernels wrote
     want = ref.f8(ff) @ ref.f8(d["W2"]).T + ref.f8(d["b2"]) + ref.f8(p["y"])
-    bound, S = _matmul_bound(ff, d["W2"], d["b2"], p["y"])
+    bound, S = ref.matmul_bound(ff, d["W2"], d["b2"], p["y"])
     err = np.abs(ref.f8(p["v_down"]) - want)
     print(f"  v_down err/S {(err / S).max():.3e} of {4 * (I + 4) * 2.0 ** -24:.3e}")
     assert (err <= bound).all(), ("v_down", float((err / S).max()), np.argwhere(err > bound)[:5].tolist())
@@ -144,19 +137,6 @@ def test_skinny_tail_has_the_one_launch_tail_s_bits_and_float64_parts(M, H, I):
         assert not np.isnan(got).any()
 
 
-def _layernorm_bound(v, g, want):
-    """One f16 ulp of the value for the rounding, and f32 statistics to first order: a sum of H terms in any order is off by at
-    most H 2^-24 sum |v|, so the mean by H 2^-24 mean |v| -- an ABSOLUTE error of every v - mean, which a value that beta all but
-    cancels does not scale down -- and 1 / std by that fraction of itself; twice both for the squares' sum and the arithmetic
-    behind.  (A bound relative to the value alone is not one: with 768 x 384 draws a value of 6e-5 beside a beta of -0.016 comes
-    out 1.1 subnormal ulp away.)"""
-    v = ref.f8(v)
-    mu = v.mean(axis=1, keepdims=True)
-    sd = np.sqrt(((v - mu) ** 2).mean(axis=1, keepdims=True) + 1e-5)
-    stat = 2 * v.shape[1] * 2.0 ** -24 * (np.abs(v).mean(axis=1, keepdims=True) + np.abs(v - mu)) / sd * np.abs(ref.f8(g))
-    return ref.f8(np.spacing(np.abs(want).astype(np.float16))) + stat
-
-
 @pytest.mark.parametrize("H", [256, 384])
 @pytest.mark.parametrize("M", TOKENS + [768])
 def test_skinny_qkv_projection(M, H):
@@ -174,7 +154,7 @@ def test_skinny_qkv_projection(M, H):
     _same_bits(qkv, pybert.test_skinny_qkv(wb, 1, bias, x=ln_out), "fused projection against the plain one on its ln_out")
     want = ref.layernorm(ref.f8(V), ref.f8(g), ref.f8(be))
     err = np.abs(ref.f8(ln_out) - want)
-    bound = _layernorm_bound(V, g, want)
+    bound = ref.layernorm_bound(V, g, want)
     print(f"qkv M={M} H={H}: ln_out err/bound {(err / bound).max():.3f}")
     assert (err <= bound).all(), ("ln_out", float((err / bound).max()), np.argwhere(err > bound)[:5].tolist())
     if M in PAD_TOKENS:
