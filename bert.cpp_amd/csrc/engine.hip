@@ -368,13 +368,20 @@ bool Engine::forward_f32(const Plan &p, std::string &err) {
     float *x = x_.as<float>(), *qkv = qkv_.as<float>(), *ctx = ctx_.as<float>(), *y = y_.as<float>(), *ff = ff_.as<float>();
     timed("embed_ln", 0.0, p.s, [&] {
         launch_f32_embed_ln(w_->word_emb.as<float>(), w_->type_emb.as<float>(), w_->pos_emb.as<float>(), w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(), p.tokens,
-                            p.cu, p.B, p.T, H, hp_.n_vocab, x, p.s);
+                            p.cu, p.B, p.T, H, hp_.n_vocab, p.max_len, x, p.s);
     });
     tap(p, 0);
     for (int il = 0; il < hp_.n_layer; ++il) {
         const LayerWeights &L = w_->layers[il];
         if (!gemm(p, "gemm_qkv", F, L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS, err)) return false;
-        timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] { launch_f32_attention(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s); });
+        bool launched = true;
+        timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] { launched = launch_f32_attention(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s); });
+        if (!launched) {
+            err = "f32 route: the attention kernel keeps the scores of max_len = " + std::to_string(p.max_len) + " keys per wave in LDS, " +
+                  std::to_string(f32_attention_lds_bytes(p.max_len)) + " bytes a workgroup; this device's limit is " +
+                  std::to_string(f32_attention_lds_limit()) + " bytes (set_option \"f32\" = \"f16\" selects the f16 kernels)";
+            return false;
+        }
         if (!gemm(p, "gemm_attn_out", F, L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, err)) return false;
         timed("layernorm", 0.0, p.s, [&] { launch_f32_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), p.T, H, p.s); });
         if (!gemm(p, "gemm_ffn_up", F, L.ffi, y, L.ffi_b.as<float>(), nullptr, ff, EPI_BIAS_GELU, err) ||

@@ -7,8 +7,9 @@
 // activations in HBM, every weight mat-mul on v_mfma_f32_32x32x2_f32 (the matrix cores' f32 form: products and sums are
 // f32 fma chains, 157 TFLOP/s dense), f32 softmax / tanh-GELU / LayerNorm.  It is a precision route, not a benchmark
 // configuration (BASELINE.json's configs are f16 / q4 files): plain LDS-tiled kernels, one launch per operation, any
-// H / d_head / length the file format allows.  `BERT_HIP_F32=f16` (or set_option "f32" = "f16") selects the old behaviour
-// (f16 operands, the fused kernels) for f32 files.
+// H / d_head / length the file format allows -- up to the max_len whose scores fit the LDS of a workgroup (launch_f32_attention:
+// 64 ceil(max_len / 4) bytes against the device's sharedMemPerBlock; 10240 tokens at the MI355X's 160 KiB), beyond which the pass is refused on the
+// host.  `BERT_HIP_F32=f16` (or set_option "f32" = "f16") selects the old behaviour (f16 operands, the fused kernels) for f32 files.
 //
 // Replaces, for f32 files: bert.cpp:796-814 (embedding + LayerNorm), :822-839 / :859-865 / :878-891 (mat-muls + bias, GELU,
 // residual), :843-856 (attention), :868-874 / :894-900 (LayerNorm), :904-913 (pooling).
@@ -37,10 +38,13 @@ __device__ __forceinline__ void f32_layernorm_row(float *row, const float *gamma
 }
 
 // reference bert.cpp:796-814: inpL = word[ids]; inpL = type[0] + inpL; inpL = pos[0..N-1] + inpL; LayerNorm.  One wave per token.
+// max_len (<= the position table's rows: the host refuses a larger one): a token at or behind place max_len of its sentence, which
+// only a sentence longer than the device API's promise has, takes row max_len - 1, so the table is never read past its end; what its
+// row holds does not matter (the pooling kernel gives that sentence a NaN row).
 __global__ __launch_bounds__(256) void f32_embed_ln_kernel(const float *word, const float *type, const float *pos, const float *gamma,
                                                            const float *beta, const int32_t *__restrict__ tokens,
                                                            const int32_t *__restrict__ cu_seqlens, int n_sentences, int T, int H, int n_vocab,
-                                                           float *out) {
+                                                           int max_len, float *out) {
     const int t = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= T) return;
     int lo = 0, hi = n_sentences;                             // sentence of token t: largest b with cu[b] <= t
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(256) void f32_embed_ln_kernel(const float *word, co
         const int mid = (lo + hi) >> 1;
         if (cu_seqlens[mid] <= t) lo = mid; else hi = mid;
     }
-    const int p = t - cu_seqlens[lo];
+    const int p = min(t - cu_seqlens[lo], max_len - 1);
     int id = tokens[t];
     id = id < 0 ? 0 : (id >= n_vocab ? n_vocab - 1 : id);     // ids are validated on the host API; clamp for safety
     float *row = out + (size_t)t * H;
@@ -151,13 +155,15 @@ void launch_f32_gemm(const float *A, const float *W, const float *bias, const fl
 
 // reference bert.cpp:843-856 on f32 Q | K | V rows: one wave per (sentence, head, query); scores of the wave's query in LDS;
 // softmax with the true maximum subtracted, exponentials and sums in f32; no mask (a sentence attends over its own tokens).
-__global__ void f32_attention_kernel(const float *qkv, const int32_t *cu_seqlens, int n_head, int d, float *out) {
+// A wave's stripe of scores holds gridDim.x * 4 >= max_len floats: a sentence longer than max_len (the device API's promise broken)
+// does not fit, and its waves leave before they touch LDS or write a row; the pooling kernel gives it a NaN row and raises the status word.
+__global__ void f32_attention_kernel(const float *qkv, const int32_t *cu_seqlens, int n_head, int d, int max_len, float *out) {
     extern __shared__ float sh[];          // [4 waves][max_len rounded up to 4] scores
     const int b = blockIdx.y, h = blockIdx.z;
     const int tok0 = cu_seqlens[b], n = cu_seqlens[b + 1] - tok0;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + wave;
-    if (q >= n) return;
+    if (q >= n || n > max_len) return;
     const int H = n_head * d, ld = 3 * H;
     float *s = sh + (size_t)wave * gridDim.x * 4;
     const float *qp = qkv + (size_t)(tok0 + q) * ld + h * d;
@@ -220,10 +226,10 @@ __global__ __launch_bounds__(256) void f32_pool_normalize_kernel(const float *x,
 }
 
 void launch_f32_embed_ln(const float *word, const float *type, const float *pos, const float *gamma, const float *beta, const int32_t *tokens,
-                         const int32_t *cu_seqlens, int n_sentences, int T, int H, int n_vocab, float *out, hipStream_t stream) {
+                         const int32_t *cu_seqlens, int n_sentences, int T, int H, int n_vocab, int max_len, float *out, hipStream_t stream) {
     if (T <= 0) return;
     BERT_LAUNCH(f32_embed_ln_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, word, type, pos, gamma, beta, tokens, cu_seqlens, n_sentences, T, H,
-                n_vocab, out);
+                n_vocab, max_len, out);
 }
 
 void launch_f32_layernorm(float *x, const float *gamma, const float *beta, int T, int H, hipStream_t stream) {
@@ -231,14 +237,36 @@ void launch_f32_layernorm(float *x, const float *gamma, const float *beta, int T
     BERT_LAUNCH(f32_layernorm_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, x, gamma, beta, T, H);
 }
 
-void launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head, int max_len, float *out,
+// the dynamic LDS a workgroup of the current device may ask for (its sharedMemPerBlock; 0 if the device does not answer)
+size_t f32_attention_lds_limit() {
+    static size_t limit[MAX_HIP_DEVICES] = {};
+    const int dev = current_device_slot();
+    if (!limit[dev]) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess) limit[dev] = prop.sharedMemPerBlock;
+    }
+    return limit[dev];
+}
+
+size_t f32_attention_lds_bytes(int max_len) { return (size_t)4 * ((max_len + 3) / 4) * 4 * sizeof(float); }
+
+// false, and nothing launched: the scores of max_len keys for four waves do not fit the LDS a workgroup can have on this device
+bool launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head, int max_len, float *out,
                           hipStream_t stream) {
+    if (max_len <= 0) return false;
     const int qblocks = (max_len + 3) / 4;
-    const size_t lds = (size_t)4 * qblocks * 4 * sizeof(float);
+    const size_t lds = f32_attention_lds_bytes(max_len);
+    if (lds > f32_attention_lds_limit()) return false;
+    static DeviceFlags configured;
+    if (lds > 64 * 1024)
+        configure_once(configured, [&] {
+            (void)hipFuncSetAttribute((const void *)f32_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f32_attention_lds_limit());
+        });
     for (int b0 = 0; b0 < n_sentences; b0 += 65535) {          // (a grid dimension holds 65535 sentences)
         const dim3 grid(qblocks, std::min(65535, n_sentences - b0), n_head);
-        BERT_LAUNCH(f32_attention_kernel, grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, out);
+        BERT_LAUNCH(f32_attention_kernel, grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, max_len, out);
     }
+    return true;
 }
 
 void launch_f32_pool_normalize(const float *x, const int32_t *cu_seqlens, int n_sentences, int H, int max_len, int *status, float *out,

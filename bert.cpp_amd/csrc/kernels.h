@@ -197,10 +197,15 @@ inline thread_local LaunchTiming *tl_launch_timing = nullptr;
 // The f32 route (f32_route.hip): the forward pass of f32 model files in f32 arithmetic — f32 activations, mat-muls on
 // v_mfma_f32_32x32x2_f32 (any M, N, K; C = epi(A W^T + bias (+ resid))), f32 softmax / GELU / LayerNorm / pooling.
 void launch_f32_embed_ln(const float *word, const float *type, const float *pos, const float *gamma, const float *beta, const int32_t *tokens,
-                         const int32_t *cu_seqlens, int n_sentences, int T, int H, int n_vocab, float *out, hipStream_t stream);
+                         const int32_t *cu_seqlens, int n_sentences, int T, int H, int n_vocab, int max_len, float *out, hipStream_t stream);
 void launch_f32_gemm(const float *A, const float *W, const float *bias, const float *resid, float *C, int M, int N, int K, int epilogue,
                      hipStream_t stream);
-void launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head, int max_len, float *out,
+// One wave per query keeps its max_len scores in LDS, four waves a workgroup: f32_attention_lds_bytes(max_len) = 64 ceil(max_len / 4)
+// bytes of dynamic LDS.  false, and NO launch, when that exceeds f32_attention_lds_limit(), what the current device's properties give a
+// workgroup (sharedMemPerBlock), or when max_len < 1.
+size_t f32_attention_lds_bytes(int max_len);
+size_t f32_attention_lds_limit();
+bool launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head, int max_len, float *out,
                           hipStream_t stream);
 void launch_f32_layernorm(float *x, const float *gamma, const float *beta, int T, int H, hipStream_t stream);
 void launch_f32_pool_normalize(const float *x, const int32_t *cu_seqlens, int n_sentences, int H, int max_len, int *status, float *out,

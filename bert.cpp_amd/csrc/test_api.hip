@@ -414,6 +414,116 @@ int32_t bert_hip_test_pool(int32_t H, const uint16_t *x, const int32_t *cu_seqle
                      status);
 }
 
+// ---- the f32 route's kernels (f32_route.hip), launched as Engine::forward_f32 launches them ----
+// The engine's workspaces hold whole 256-token tiles: token-row buffers get T_pad rows, the rows behind T holding the 32-bit pattern.
+static int f32_rows_pad(int T) { return (std::max(T, 1) + 255) / 256 * 256; }
+static bool upload_rows32(DevBuf &d, const float *src, int M, int M_pad, int cols, std::string &err) {
+    return upload_padded(d, (const uint32_t *)src, src ? M : 0, M_pad, cols, g_pad32, err);
+}
+// rows [M][cols] of the device buffer to the host; -4 if a word of rows M .. M_pad - 1 no longer holds the pattern (a store behind the
+// last token: in the engine, into another pass's rows)
+static int download_rows32(const char *me, float *dst, const DevBuf &d, int M, int M_pad, int cols) {
+    std::vector<uint32_t> h((size_t)M_pad * cols);
+    CK(hipMemcpy(h.data(), d.p, h.size() * 4, hipMemcpyDeviceToHost));
+    memcpy(dst, h.data(), (size_t)M * cols * 4);
+    for (size_t i = (size_t)M * cols; i < h.size(); ++i)
+        if (h[i] != g_pad32) { fprintf(stderr, "%s: row %zu behind the last token was written\n", me, i / cols); return -4; }
+    return 0;
+}
+
+int32_t bert_hip_test_f32_gemm(int32_t M, int32_t N, int32_t K, const float *A, const float *W, const float *bias, const float *resid,
+                               int32_t epilogue, float *C) {
+    std::string err;
+    if (M <= 0 || N <= 0 || K <= 0 || epilogue < 0 || epilogue > 2 || (epilogue == EPI_BIAS_RESID) != (resid != nullptr)) return -1;
+    const int M_pad = f32_rows_pad(M);
+    DevBuf dA, dW, dB, dR, dC;
+    if (!upload_rows32(dA, A, M, M_pad, K, err) || !dW.upload(W, (size_t)N * K * 4, err) || !dB.upload(bias, (size_t)N * 4, err) ||
+        (resid && !upload_rows32(dR, resid, M, M_pad, N, err)) || !alloc_pad32(dC, (size_t)M_pad * N, err)) {
+        fprintf(stderr, "bert_hip_test_f32_gemm: %s\n", err.c_str());
+        return -1;
+    }
+    launch_f32_gemm(dA.as<float>(), dW.as<float>(), dB.as<float>(), dR.as<float>(), dC.as<float>(), M, N, K, epilogue, nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    return download_rows32("bert_hip_test_f32_gemm", C, dC, M, M_pad, N);
+}
+
+int32_t bert_hip_test_f32_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head, int32_t max_len,
+                                    const float *qkv, float *out) {
+    std::string err;
+    if (n_sentences <= 0 || n_head <= 0 || d_head <= 0) return -1;
+    const int T = cu_seqlens[n_sentences], H = n_head * d_head, T_pad = f32_rows_pad(T);
+    DevBuf dq, dcu, dout;
+    if (!upload_rows32(dq, qkv, T, T_pad, 3 * H, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
+        !alloc_pad32(dout, (size_t)T_pad * H, err)) {
+        fprintf(stderr, "bert_hip_test_f32_attention: %s\n", err.c_str());
+        return -1;
+    }
+    if (!launch_f32_attention(dq.as<float>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<float>(), nullptr)) {
+        fprintf(stderr, "bert_hip_test_f32_attention: max_len = %d needs %zu bytes of LDS a workgroup, the device's limit is %zu\n", max_len,
+                f32_attention_lds_bytes(max_len), f32_attention_lds_limit());
+        return -2;
+    }
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    return download_rows32("bert_hip_test_f32_attention", out, dout, T, T_pad, H);
+}
+
+int32_t bert_hip_test_f32_layernorm(int32_t T, int32_t H, const float *x, const float *gamma, const float *beta, float *out) {
+    std::string err;
+    if (T <= 0 || H <= 0) return -1;
+    const int T_pad = f32_rows_pad(T);
+    DevBuf dx, dg, db;
+    if (!upload_rows32(dx, x, T, T_pad, H, err) || !dg.upload(gamma, (size_t)H * 4, err) || !db.upload(beta, (size_t)H * 4, err)) {
+        fprintf(stderr, "bert_hip_test_f32_layernorm: %s\n", err.c_str());
+        return -1;
+    }
+    launch_f32_layernorm(dx.as<float>(), dg.as<float>(), db.as<float>(), T, H, nullptr);       // (in place, as in the engine)
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    return download_rows32("bert_hip_test_f32_layernorm", out, dx, T, T_pad, H);
+}
+
+int32_t bert_hip_test_f32_embed_ln(int32_t H, int32_t n_vocab, int32_t n_pos, const float *word, const float *type, const float *pos,
+                                   const float *gamma, const float *beta, const bert_vocab_id *tokens, const int32_t *cu_seqlens,
+                                   int32_t n_sentences, int32_t max_len, float *out) {
+    std::string err;
+    if (H <= 0 || n_vocab <= 0 || n_sentences <= 0 || max_len <= 0 || max_len > n_pos) return -1;     // (max_len <= n_max_tokens: bert_hip_eval_packed_device's check)
+    const int T = cu_seqlens[n_sentences], T_pad = f32_rows_pad(T);
+    DevBuf dw, dt, dp, dg, db, dtok, dcu, dout;
+    if (!dw.upload(word, (size_t)n_vocab * H * 4, err) || !dt.upload(type, (size_t)2 * H * 4, err) || !dp.upload(pos, (size_t)n_pos * H * 4, err) ||
+        !dg.upload(gamma, (size_t)H * 4, err) || !db.upload(beta, (size_t)H * 4, err) || !dtok.upload(tokens, (size_t)T * 4, err) ||
+        !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) || !alloc_pad32(dout, (size_t)T_pad * H, err)) {
+        fprintf(stderr, "bert_hip_test_f32_embed_ln: %s\n", err.c_str());
+        return -1;
+    }
+    launch_f32_embed_ln(dw.as<float>(), dt.as<float>(), dp.as<float>(), dg.as<float>(), db.as<float>(), dtok.as<int32_t>(), dcu.as<int32_t>(),
+                        n_sentences, T, H, n_vocab, max_len, dout.as<float>(), nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    return download_rows32("bert_hip_test_f32_embed_ln", out, dout, T, T_pad, H);
+}
+
+int32_t bert_hip_test_f32_pool(int32_t H, const float *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len, int32_t pooling,
+                               int32_t normalize, float *out, int32_t *status) {
+    std::string err;
+    if (H <= 0 || n_sentences <= 0) return -1;
+    const int T = cu_seqlens[n_sentences], T_pad = f32_rows_pad(T);
+    DevBuf dx, dcu, dout, dst;
+    if (!upload_rows32(dx, x, T, T_pad, H, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
+        !alloc_pad32(dout, (size_t)n_sentences * H, err) || !dst.alloc(16, err)) {
+        fprintf(stderr, "bert_hip_test_f32_pool: %s\n", err.c_str());
+        return -1;
+    }
+    launch_f32_pool_normalize(dx.as<float>(), dcu.as<int32_t>(), n_sentences, H, max_len, dst.as<int>(), dout.as<float>(),
+                              (pooling ? POOL_CLS : 0) | (normalize ? 0 : POOL_RAW), nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, (size_t)n_sentences * H * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(status, dst.p, 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int32_t bert_hip_test_model_digest(const char *fname, int32_t *legacy_q4, uint64_t *digest) {
     ModelFile mf;
     std::string err;

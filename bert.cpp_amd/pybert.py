@@ -43,6 +43,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots", "bert_hip_test_set_pad",
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
     "bert_hip_test_pool",
+    "bert_hip_test_f32_gemm", "bert_hip_test_f32_attention", "bert_hip_test_f32_layernorm", "bert_hip_test_f32_embed_ln", "bert_hip_test_f32_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
     "bert_hip_test_build_lists", "bert_hip_test_partition_header",
@@ -186,6 +187,16 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_pool_normalize.argtypes = [i32, vp, i32p, i32, i32, vp, i32p]
     L.bert_hip_test_pool.restype = i32
     L.bert_hip_test_pool.argtypes = [i32, vp, i32p, i32, i32, i32, i32, vp, i32p]
+    L.bert_hip_test_f32_gemm.restype = i32
+    L.bert_hip_test_f32_gemm.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp]
+    L.bert_hip_test_f32_attention.restype = i32
+    L.bert_hip_test_f32_attention.argtypes = [i32, i32p, i32, i32, i32, vp, vp]
+    L.bert_hip_test_f32_layernorm.restype = i32
+    L.bert_hip_test_f32_layernorm.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.bert_hip_test_f32_embed_ln.restype = i32
+    L.bert_hip_test_f32_embed_ln.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, i32p, i32p, i32, i32, vp]
+    L.bert_hip_test_f32_pool.restype = i32
+    L.bert_hip_test_f32_pool.argtypes = [i32, vp, i32p, i32, i32, i32, i32, vp, i32p]
     L.bert_hip_test_model_digest.restype = i32
     L.bert_hip_test_model_digest.argtypes = [C.c_char_p, i32p, C.POINTER(C.c_uint64)]
     L.bert_hip_test_pack_weight.restype = i32
@@ -310,7 +321,7 @@ def set_window_slots(slots: int) -> int:
 @contextlib.contextmanager
 def test_pad(pattern16: int, pattern32: int):
     """While the block runs, the batch-route op entries (test_gemm, test_gemm_lnfold, test_attention, test_qkv_attention,
-    test_layer_tail) fill their padding rows and every output / intermediate buffer with these bit patterns before they launch
+    test_layer_tail) and the f32 route's (test_f32_*) fill their padding rows and every output / intermediate buffer with these bit patterns before they launch
     (include/bert_hip_test.h bert_hip_test_set_pad); zeros again afterwards."""
     L = test_lib()
     L.bert_hip_test_set_pad(pattern16, pattern32)
@@ -990,3 +1001,67 @@ def test_skinny_qkv(W_bytes: np.ndarray, wtype: int, bias: np.ndarray, x: Option
     if r != 0:
         raise RuntimeError(f"bert_hip_test_skinny_qkv failed: {r}")
     return qkv if V is None else (qkv, ln_out)
+
+
+# ---- the f32 route's kernels (include/bert_hip_test.h bert_hip_test_f32_*): f32 arrays in, f32 arrays out ----
+def _f32c(a) -> np.ndarray:
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def test_f32_gemm(A: np.ndarray, W: np.ndarray, bias: np.ndarray, resid: Optional[np.ndarray], epilogue: int) -> np.ndarray:
+    """epilogue(A [M,K] W [N,K]^T + bias): 0 bias, 1 bias + GELU, 2 bias + resid [M,N]."""
+    A, W, bias = _f32c(A), _f32c(W), _f32c(bias)
+    (M, K), N = A.shape, W.shape[0]
+    assert W.shape == (N, K) and bias.shape == (N,)
+    r = None if resid is None else _f32c(resid)
+    assert r is None or r.shape == (M, N)
+    C_ = np.zeros((M, N), dtype=np.float32)
+    rc = test_lib().bert_hip_test_f32_gemm(M, N, K, A.ctypes.data, W.ctypes.data, bias.ctypes.data, None if r is None else r.ctypes.data,
+                                           epilogue, C_.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"bert_hip_test_f32_gemm failed: {rc}")
+    return C_
+
+
+def test_f32_attention(qkv: np.ndarray, cu_seqlens, n_head: int, d_head: int, max_len: int) -> np.ndarray:
+    qkv = _f32c(qkv); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    assert qkv.shape == (int(cu[-1]), 3 * n_head * d_head)
+    out = np.zeros((qkv.shape[0], n_head * d_head), dtype=np.float32)
+    rc = test_lib().bert_hip_test_f32_attention(len(cu) - 1, _i32p(cu), n_head, d_head, max_len, qkv.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"bert_hip_test_f32_attention failed: {rc}")
+    return out
+
+
+def test_f32_layernorm(x: np.ndarray, gamma, beta) -> np.ndarray:
+    x, g, b = _f32c(x), _f32c(gamma), _f32c(beta)
+    out = np.zeros_like(x)
+    rc = test_lib().bert_hip_test_f32_layernorm(x.shape[0], x.shape[1], x.ctypes.data, g.ctypes.data, b.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"bert_hip_test_f32_layernorm failed: {rc}")
+    return out
+
+
+def test_f32_embed_ln(word, type_, pos, gamma, beta, tokens, cu_seqlens, max_len: int) -> np.ndarray:
+    word, type_, pos, g, b = (_f32c(a) for a in (word, type_, pos, gamma, beta))
+    toks = np.ascontiguousarray(tokens, dtype=np.int32); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    H = word.shape[1]
+    assert type_.shape == (2, H) and pos.shape[1] == H and len(toks) == int(cu[-1])
+    out = np.zeros((len(toks), H), dtype=np.float32)
+    rc = test_lib().bert_hip_test_f32_embed_ln(H, word.shape[0], pos.shape[0], word.ctypes.data, type_.ctypes.data, pos.ctypes.data,
+                                               g.ctypes.data, b.ctypes.data, _i32p(toks), _i32p(cu), len(cu) - 1, max_len, out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"bert_hip_test_f32_embed_ln failed: {rc}")
+    return out
+
+
+def test_f32_pool(x: np.ndarray, cu_seqlens, max_len: int, pooling: str = "mean", normalize: bool = True):
+    """test_pool on f32 rows: (rows [n_sentences, H] f32, status word)."""
+    x = _f32c(x); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    out = np.zeros((len(cu) - 1, x.shape[1]), dtype=np.float32)
+    st = np.zeros(1, dtype=np.int32)
+    rc = test_lib().bert_hip_test_f32_pool(x.shape[1], x.ctypes.data, _i32p(cu), len(cu) - 1, max_len, {"mean": 0, "cls": 1}[pooling],
+                                           int(bool(normalize)), out.ctypes.data, _i32p(st))
+    if rc != 0:
+        raise RuntimeError(f"bert_hip_test_f32_pool failed: {rc}")
+    return out, int(st[0])

@@ -19,8 +19,8 @@ extern "C" {
  *     (pattern32 in 32-bit buffers);
  *   - every output and intermediate buffer (C, u, out2, the partial statistics and finalized rows of the LayerNorm fold, qkv
  *     between projection and attention, y and the intermediate of the five-kernel tail, every out) holds it in ALL its words.
- * Entries: bert_hip_test_gemm, _gemm_lnfold, _attention, _qkv_attention, _layer_tail (the latency route's entries take a `pad`
- * argument of their own).  0, 0 (the state at load): zeros, as before.  Quiet NaNs (0x7E00, 0x7FC00000) make any read of such a word
+ * Entries: bert_hip_test_gemm, _gemm_lnfold, _attention, _qkv_attention, _layer_tail and the five _f32_ entries (the latency route's
+ * entries take a `pad` argument of their own).  0, 0 (the state at load): zeros, as before.  Quiet NaNs (0x7E00, 0x7FC00000) make any read of such a word
  * show in the rows a call returns; to the kernels they are data.  Set it under try / finally: it outlives the call.          */
 BERT_API void bert_hip_test_set_pad(uint32_t pattern16, uint32_t pattern32);
 
@@ -103,6 +103,29 @@ BERT_API int32_t bert_hip_test_pool_normalize(int32_t H, const uint16_t *x, cons
 /* The same kernel under the settings of a context (bert_hip.h): pooling 0 mean | 1 the sentence's first row, normalize 1 | 0.   */
 BERT_API int32_t bert_hip_test_pool(int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
                                     int32_t pooling, int32_t normalize, float *out, int32_t *status);
+
+/* The f32 route's kernels (f32_route.hip: what an f32 model file runs on), each launched exactly as Engine::forward_f32 launches it;
+ * everything f32.  Token-row buffers have the engine's workspace shape, whole tiles of 256 rows: under bert_hip_test_set_pad the rows
+ * behind the last token of every input hold pattern32, every output buffer holds it in ALL its words before the launch, and an entry
+ * returns -4 if a word behind the last token's row has changed afterwards.  -1: bad arguments or a HIP error.
+ * C [M][N] = epilogue(A [M][K] W [N][K]^T + bias [N]), epilogue 0 bias, 1 bias + GELU (tanh), 2 bias + resid [M][N] (else resid NULL).  */
+BERT_API int32_t bert_hip_test_f32_gemm(int32_t M, int32_t N, int32_t K, const float *A, const float *W, const float *bias,
+                                        const float *resid, int32_t epilogue, float *C);
+/* qkv [T][3H] (Q | K | V per row), packed sentences -> out [T][H].  max_len is the caller's: it sizes the grid and each wave's stripe
+ * of scores in LDS.  The rows of a sentence longer than max_len are not written (they keep the pattern).  -2, and no launch, when
+ * max_len needs more dynamic LDS than the device gives a workgroup.                                                              */
+BERT_API int32_t bert_hip_test_f32_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head,
+                                             int32_t max_len, const float *qkv, float *out);
+/* out [T][H] = LayerNorm(x [T][H]) gamma + beta, two-pass statistics, eps 1e-5.                                                  */
+BERT_API int32_t bert_hip_test_f32_layernorm(int32_t T, int32_t H, const float *x, const float *gamma, const float *beta, float *out);
+/* Embedding gather-sum + LayerNorm on f32 tables: word [n_vocab][H], type [2][H] (row 0 is used), pos [n_pos][H]; out [T][H].
+ * max_len <= n_pos as bert_hip_eval_packed_device demands (-1 otherwise): no position row at or behind max_len is read.          */
+BERT_API int32_t bert_hip_test_f32_embed_ln(int32_t H, int32_t n_vocab, int32_t n_pos, const float *word, const float *type,
+                                            const float *pos, const float *gamma, const float *beta, const bert_vocab_id *tokens,
+                                            const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len, float *out);
+/* bert_hip_test_pool on f32 rows x [T][H]: out [n_sentences][H], *status the device status word.                                  */
+BERT_API int32_t bert_hip_test_f32_pool(int32_t H, const float *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
+                                        int32_t pooling, int32_t normalize, float *out, int32_t *status);
 
 /* Parses a model file (no GPU): returns the number of tensors (negative on error, message on stderr), whether the file uses the
  * legacy 20 / 24-byte q4 blocks, and a digest of every tensor's name, type and bytes AFTER conversion to the current layout.   */

@@ -68,15 +68,16 @@ def layernorm_stats_bound(v, one_pass=False):
     return 2 * H * U32 * mean_abs, rstd_rel
 
 
-def layernorm_bound(v, g, want, one_pass=False):
+def layernorm_bound(v, g, want, one_pass=False, rounding=None):
     """One f16 ulp of the value for the rounding, and the f32 statistics (layernorm_stats_bound): the mean's error is an ABSOLUTE
     error of every v - mean, which a value that beta all but cancels does not scale down.  (A bound relative to the value alone is
-    not one: with 768 x 384 draws a value of 6e-5 beside a beta of -0.016 comes out 1.1 subnormal ulp away.)"""
+    not one: with 768 x 384 draws a value of 6e-5 beside a beta of -0.016 comes out 1.1 subnormal ulp away.)
+    rounding: what the roundings of the output cost instead, for a kernel that does not store f16 (f32_reference.layernorm_bound)."""
     v = f8(v)
     mu = v.mean(axis=1, keepdims=True)
     sd = np.sqrt(((v - mu) ** 2).mean(axis=1, keepdims=True) + 1e-5)
     mean_err, rstd_rel = layernorm_stats_bound(v, one_pass)
-    return ulp16(want) + (mean_err + np.abs(v - mu) * rstd_rel) / sd * np.abs(f8(g))
+    return (ulp16(want) if rounding is None else rounding) + (mean_err + np.abs(v - mu) * rstd_rel) / sd * np.abs(f8(g))
 
 
 def layernorm_input_term(v, g, dv):
