@@ -495,12 +495,17 @@ __global__ void attention_naive_kernel(const half_t *qkv, const int32_t *cu_seql
     }
 }
 
+// grid.y counts sentences and a grid dimension holds 65535 (kernels.h GRID_YZ_MAX: the limit the code assumes of every device); a
+// chunk of 262 144 tokens has more sentences than that once they average four tokens or fewer, so they go in slices of 65535
+// (cu_seqlens holds absolute token offsets: a slice starts at its own entry of it).
 void launch_attention_naive(const half_t *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head,
                             int max_len, half_t *out, hipStream_t stream) {
     const int qblocks = (max_len + 3) / 4;
-    dim3 grid(qblocks, n_sentences, n_head);
     const size_t lds = (size_t)4 * qblocks * 4 * sizeof(float);
-    BERT_LAUNCH(attention_naive_kernel, grid, dim3(256), lds, stream, qkv, cu_seqlens, n_head, d_head, out);
+    for (int b0 = 0; b0 < n_sentences; b0 += GRID_YZ_MAX) {
+        const dim3 grid(qblocks, std::min(GRID_YZ_MAX, n_sentences - b0), n_head);
+        BERT_LAUNCH(attention_naive_kernel, grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, out);
+    }
 }
 
 }  // namespace bert_hip

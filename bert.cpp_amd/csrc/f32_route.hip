@@ -262,8 +262,8 @@ bool launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sen
         configure_once(configured, [&] {
             (void)hipFuncSetAttribute((const void *)f32_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f32_attention_lds_limit());
         });
-    for (int b0 = 0; b0 < n_sentences; b0 += 65535) {          // (a grid dimension holds 65535 sentences)
-        const dim3 grid(qblocks, std::min(65535, n_sentences - b0), n_head);
+    for (int b0 = 0; b0 < n_sentences; b0 += GRID_YZ_MAX) {    // (a grid dimension holds 65535 sentences)
+        const dim3 grid(qblocks, std::min(GRID_YZ_MAX, n_sentences - b0), n_head);
         BERT_LAUNCH(f32_attention_kernel, grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, max_len, out);
     }
     return true;

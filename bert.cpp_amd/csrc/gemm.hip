@@ -20,6 +20,7 @@
 //     math applies (q-8)*d or q*d+m) and writes four swizzled 16-B chunks into the LDS tile.
 #include "device.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace bert_hip {
@@ -229,13 +230,20 @@ __global__ void gemm_naive_kernel(const half_t *A, const half_t *W, const float 
     C[(size_t)t * N + n] = (_Float16)s;
 }
 
+// grid.y counts groups of 4 token rows and a grid dimension holds 65535 (kernels.h GRID_YZ_MAX: the limit the code assumes of
+// every device): a chunk of 262 144 tokens is 65 536 groups, so the rows go in slices of 4 * 65535.
 void launch_gemm_naive(const GemmWeight &W, const half_t *A, const float *bias, const half_t *resid, half_t *C,
                        int M, int epilogue, hipStream_t stream) {
-    dim3 grid((W.N + 63) / 64, (M + 3) / 4), block(256);
-    switch (epilogue) {
-        case EPI_BIAS: BERT_LAUNCH((gemm_naive_kernel<EPI_BIAS>), grid, block, 0, stream, A, W.naive16, bias, resid, C, M, W.N, W.K); break;
-        case EPI_BIAS_GELU: BERT_LAUNCH((gemm_naive_kernel<EPI_BIAS_GELU>), grid, block, 0, stream, A, W.naive16, bias, resid, C, M, W.N, W.K); break;
-        default: BERT_LAUNCH((gemm_naive_kernel<EPI_BIAS_RESID>), grid, block, 0, stream, A, W.naive16, bias, resid, C, M, W.N, W.K); break;
+    for (int m0 = 0; m0 < M; m0 += 4 * GRID_YZ_MAX) {
+        const int m = std::min(4 * GRID_YZ_MAX, M - m0);
+        const dim3 grid((W.N + 63) / 64, (m + 3) / 4), block(256);
+        const half_t *a = A + (size_t)m0 * W.K, *r = resid ? resid + (size_t)m0 * W.N : nullptr;
+        half_t *c = C + (size_t)m0 * W.N;
+        switch (epilogue) {
+            case EPI_BIAS: BERT_LAUNCH((gemm_naive_kernel<EPI_BIAS>), grid, block, 0, stream, a, W.naive16, bias, r, c, m, W.N, W.K); break;
+            case EPI_BIAS_GELU: BERT_LAUNCH((gemm_naive_kernel<EPI_BIAS_GELU>), grid, block, 0, stream, a, W.naive16, bias, r, c, m, W.N, W.K); break;
+            default: BERT_LAUNCH((gemm_naive_kernel<EPI_BIAS_RESID>), grid, block, 0, stream, a, W.naive16, bias, r, c, m, W.N, W.K); break;
+        }
     }
 }
 

@@ -19,6 +19,10 @@ constexpr int GEMM_BM = 128;   // token tile
 constexpr int GEMM_BN = 128;   // feature tile
 constexpr int GEMM_BK = 64;    // reduction tile (two 32-weight quant blocks)
 
+// What the launches assume grid.y and grid.z hold on every device (the least the programming model promises; DESIGN.md §3 has what
+// the MI355X's runtime reports): a launch whose y or z could exceed it goes in slices.
+constexpr int GRID_YZ_MAX = 65535;
+
 enum Epilogue : int { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESID = 2 };
 enum GemmWType : int { GW_F16 = 0, GW_Q4_0 = 1, GW_Q4_1 = 2 };
 
@@ -109,6 +113,7 @@ void launch_gemm_naive(const GemmWeight &W, const half_t *A, const float *bias, 
                        int M, int epilogue, hipStream_t stream);
 
 // word + token_type(0) + position gather-sum, LayerNorm(eps 1e-5), f16 out.  Tables in file layout.
+// max_len (the device API's promise, <= the position table's rows): chooses the grid form; no position row at or behind it is read.
 void launch_embed_ln(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
                      const float *beta, const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int T,
                      int H, int n_vocab, int max_len, half_t *out, hipStream_t stream);

@@ -41,12 +41,15 @@ __device__ __forceinline__ void table_pair(const void *tab, int type, int H, int
 // reference bert.cpp:796-814: inpL = word[ids]; inpL = type[0] + inpL; inpL = pos[0..N-1] + inpL;
 // LayerNorm (ggml_norm eps 1e-5) then gamma * x + beta.  One wave per token, one pass: the row is
 // held in registers as NJ element pairs per lane (H <= 128 * NJ, H even).
+// max_len (<= the position table's rows: the host refuses a larger one): a token at or behind place max_len of its sentence, which
+// only a sentence longer than the device API's promise has, takes row max_len - 1, so the table is never read past its end; what
+// its row holds does not matter (the pooling kernel gives that sentence a NaN row).  The same in embed_ln_rows_kernel.
 template <int NJ>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const void *word, const void *type, const void *pos,
                                                        int table_type, const float *gamma, const float *beta,
                                                        const int32_t *__restrict__ tokens,
                                                        const int32_t *__restrict__ cu_seqlens, int n_sentences,
-                                                       int T, int H, int n_vocab, half_t *__restrict__ out) {
+                                                       int T, int H, int n_vocab, int max_len, half_t *__restrict__ out) {
     // wave-uniform token index: the sentence search below then runs on scalar loads (constant cache)
     const int t = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= T) return;
@@ -56,7 +59,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const void *word, const v
         const int mid = (lo + hi) >> 1;
         if (cu_seqlens[mid] <= t) lo = mid; else hi = mid;
     }
-    const int p = t - cu_seqlens[lo];
+    const int p = min(t - cu_seqlens[lo], max_len - 1);
     int id = tokens[t];
     id = id < 0 ? 0 : (id >= n_vocab ? n_vocab - 1 : id);   // ids are validated on the host API; clamp for safety
 
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(256) void embed_ln_rows_kernel(const void *word, co
                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
                                                             const int32_t *__restrict__ tokens,
                                                             const int32_t *__restrict__ cu_seqlens, int n_sentences, int T,
-                                                            int H, int n_vocab, half_t *__restrict__ out) {
+                                                            int H, int n_vocab, int max_len, half_t *__restrict__ out) {
     const int lane = threadIdx.x & 63;
     int p = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // position in the sentence / token
     int t;
@@ -157,6 +160,7 @@ __global__ __launch_bounds__(256) void embed_ln_rows_kernel(const void *word, co
         if (p >= n) return;
         t = tok0 + p;
     }
+    p = min(p, max_len - 1);                                  // (the position row; t is settled)
     int id = tokens[t];
     id = id < 0 ? 0 : (id >= n_vocab ? n_vocab - 1 : id);   // ids are validated on the host API; clamp for safety
     float v[NC][8];
@@ -205,13 +209,13 @@ void launch_embed_ln(const void *word, const void *type, const void *pos, int ta
     if (T <= 0) return;
     if ((table_type <= 1 ? H % 8 == 0 : H % 32 == 0) && table_type <= 3 && H <= 1024 && max_len > 0) {
         // (group, sentence) grid while at least two thirds of its workgroups have tokens, else one group per 4 tokens
-        const bool search = n_sentences > 65535 || 2ll * ((max_len + 3) / 4) * n_sentences > 3ll * ((T + 3) / 4);
+        const bool search = n_sentences > GRID_YZ_MAX || 2ll * ((max_len + 3) / 4) * n_sentences > 3ll * ((T + 3) / 4);
         const dim3 g2 = search ? dim3((T + 3) / 4) : dim3((max_len + 3) / 4, n_sentences), b2(256);
 #define EMBR(TT, NC) do { \
             if (search) BERT_LAUNCH((embed_ln_rows_kernel<TT, NC, true>), g2, b2, 0, stream, word, type, pos, gamma, beta, tokens, \
-                                           cu_seqlens, n_sentences, T, H, n_vocab, out); \
+                                           cu_seqlens, n_sentences, T, H, n_vocab, max_len, out); \
             else BERT_LAUNCH((embed_ln_rows_kernel<TT, NC, false>), g2, b2, 0, stream, word, type, pos, gamma, beta, tokens, \
-                                    cu_seqlens, n_sentences, T, H, n_vocab, out); } while (0)
+                                    cu_seqlens, n_sentences, T, H, n_vocab, max_len, out); } while (0)
         if (table_type == 0) { if (H <= 512) EMBR(0, 1); else EMBR(0, 2); }
         else if (table_type == 1) { if (H <= 512) EMBR(1, 1); else EMBR(1, 2); }
         else if (table_type == 2) { if (H <= 512) EMBR(2, 1); else EMBR(2, 2); }
@@ -221,8 +225,9 @@ void launch_embed_ln(const void *word, const void *type, const void *pos, int ta
     }
     const dim3 grid((T + 3) / 4), block(256);
     const int nj = (H + 127) / 128;
+    const int pos_rows = max_len > 0 ? max_len : T;          // (no promise given: a sentence has at most T tokens)
 #define EMB(NJ) BERT_LAUNCH(embed_ln_kernel<NJ>, grid, block, 0, stream, word, type, pos, table_type, gamma, \
-                                   beta, tokens, cu_seqlens, n_sentences, T, H, n_vocab, out)
+                                   beta, tokens, cu_seqlens, n_sentences, T, H, n_vocab, pos_rows, out)
     if (nj <= 1) EMB(1); else if (nj <= 3) EMB(3); else if (nj <= 6) EMB(6); else if (nj <= 8) EMB(8); else EMB(32);
 #undef EMB
 }
@@ -375,6 +380,10 @@ __global__ __launch_bounds__(256) void stage_copy_kernel(const uint4 *__restrict
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n16; i += gridDim.x * 256) dst[i] = src[i];
 }
 
+// Both blocks must hold `bytes` rounded up to 16.  The one caller, Engine::eval_packed_host, sizes its pinned block and its device
+// image at in_bytes + 16, in_bytes being the sum of the three parts of the largest chunk, each rounded up to 16 (so a multiple of
+// 16 itself), and copies off_w + 8 n_windows <= in_bytes bytes (build_windows makes at most one window a sentence): the last whole
+// unit ends at or before in_bytes.
 void launch_stage_copy(const void *mapped_src, void *dst, size_t bytes, hipStream_t stream) {
     const int n16 = (int)((bytes + 15) / 16);
     if (n16 <= 0) return;

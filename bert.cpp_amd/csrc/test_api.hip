@@ -52,8 +52,8 @@ static bool upload_rows16(DevBuf &d, const uint16_t *src, int M, int M_pad, int 
     return upload_padded(d, src, src ? M : 0, M_pad, cols, g_pad16, err);
 }
 // an output or intermediate buffer of n 16-bit / 32-bit words, every word the pattern
-static bool alloc_pad16(DevBuf &d, size_t n, std::string &err) { return g_pad16 ? upload_padded<uint16_t>(d, nullptr, 0, 1, (int)n, g_pad16, err) : d.alloc(n * 2, err); }
-static bool alloc_pad32(DevBuf &d, size_t n, std::string &err) { return g_pad32 ? upload_padded<uint32_t>(d, nullptr, 0, 1, (int)n, g_pad32, err) : d.alloc(n * 4, err); }
+static bool alloc_pad16(DevBuf &d, size_t n, std::string &err) { return g_pad16 ? d.upload(std::vector<uint16_t>(n, g_pad16), err) : d.alloc(n * 2, err); }
+static bool alloc_pad32(DevBuf &d, size_t n, std::string &err) { return g_pad32 ? d.upload(std::vector<uint32_t>(n, g_pad32), err) : d.alloc(n * 4, err); }
 
 // the matrices and parameter vectors of a layer tail on the device, from file-layout bytes (W1, W2 also in the k order of w16p)
 struct TailOperands {
@@ -361,18 +361,34 @@ int32_t bert_hip_test_skinny_qkv(int32_t M, int32_t H, const uint16_t *x, const 
 }
 
 
+// ---- the f16 row kernels of misc_kernels.hip, launched as Engine::forward_layers launches them ----
+// Token-row buffers have the engine's workspace shape, whole tiles of 256 rows, the rows behind T holding the 16-bit pattern.
+static int rows_pad256(int T) { return (std::max(T, 1) + 255) / 256 * 256; }
+// rows [M][cols] of the device buffer to the host; -4 if a word of rows M .. M_pad - 1 no longer holds the pattern (a store behind the
+// last token: in the engine, into another pass's rows)
+static int download_rows16(const char *me, uint16_t *dst, const DevBuf &d, int M, int M_pad, int cols) {
+    std::vector<uint16_t> h((size_t)M_pad * cols);
+    CK(hipMemcpy(h.data(), d.p, h.size() * 2, hipMemcpyDeviceToHost));
+    memcpy(dst, h.data(), (size_t)M * cols * 2);
+    for (size_t i = (size_t)M * cols; i < h.size(); ++i)
+        if (h[i] != g_pad16) { fprintf(stderr, "%s: row %zu behind the last token was written\n", me, i / cols); return -4; }
+    return 0;
+}
+
 int32_t bert_hip_test_embed_ln(int32_t table_type, int32_t H, int32_t n_vocab, int32_t n_pos, const void *word, const void *type,
                                const void *pos, const float *gamma, const float *beta, const bert_vocab_id *tokens,
-                               const int32_t *cu_seqlens, int32_t n_sentences, uint16_t *out) {
+                               const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len, uint16_t *out) {
     std::string err;
-    const int T = cu_seqlens[n_sentences];
-    int max_len = 0;
-    for (int b = 0; b < n_sentences; ++b) max_len = std::max(max_len, cu_seqlens[b + 1] - cu_seqlens[b]);
+    if (H <= 0 || n_vocab <= 0 || n_sentences <= 0 || max_len < 0 || max_len > n_pos) return -1;       // (max_len <= n_max_tokens: bert_hip_eval_packed_device's check)
+    const int T = cu_seqlens[n_sentences], T_pad = rows_pad256(T);
+    if (max_len == 0)
+        for (int b = 0; b < n_sentences; ++b) max_len = std::max(max_len, cu_seqlens[b + 1] - cu_seqlens[b]);
+    if (max_len > n_pos) return -1;
     const size_t rb = wtype_row_bytes(table_type, H);
     DevBuf dw, dt, dp, dg, db, dtok, dcu, dout;
     if (!dw.upload(word, rb * n_vocab, err) || !dt.upload(type, rb * 2, err) || !dp.upload(pos, rb * n_pos, err) ||
         !dg.upload(gamma, (size_t)H * 4, err) || !db.upload(beta, (size_t)H * 4, err) || !dtok.upload(tokens, (size_t)T * 4, err) ||
-        !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) || !dout.alloc((size_t)T * H * 2, err)) {
+        !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) || !alloc_pad16(dout, (size_t)T_pad * H, err)) {
         fprintf(stderr, "bert_hip_test_embed_ln: %s\n", err.c_str());
         return -1;
     }
@@ -380,8 +396,22 @@ int32_t bert_hip_test_embed_ln(int32_t table_type, int32_t H, int32_t n_vocab, i
                     T, H, n_vocab, max_len, dout.as<half_t>(), nullptr);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
-    CK(hipMemcpy(out, dout.p, (size_t)T * H * 2, hipMemcpyDeviceToHost));
-    return 0;
+    return download_rows16("bert_hip_test_embed_ln", out, dout, T, T_pad, H);
+}
+
+int32_t bert_hip_test_layernorm(int32_t T, int32_t H, const uint16_t *x, const float *gamma, const float *beta, uint16_t *out) {
+    std::string err;
+    if (T <= 0 || H <= 0 || H % 2 || H > 4096) return -1;       // (the widths a model file may have: checked at load)
+    const int T_pad = rows_pad256(T);
+    DevBuf dx, dg, db;
+    if (!upload_rows16(dx, x, T, T_pad, H, err) || !dg.upload(gamma, (size_t)H * 4, err) || !db.upload(beta, (size_t)H * 4, err)) {
+        fprintf(stderr, "bert_hip_test_layernorm: %s\n", err.c_str());
+        return -1;
+    }
+    launch_layernorm(dx.as<half_t>(), dg.as<float>(), db.as<float>(), T, H, nullptr);       // (in place, as in the engine)
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    return download_rows16("bert_hip_test_layernorm", out, dx, T, T_pad, H);
 }
 
 // x [T][H] f16 bits -> the sentences' rows by the rule pool_mode names (kernels.h POOL_*), and the status word

@@ -42,7 +42,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_layer_tail", "bert_hip_test_skinny_tail", "bert_hip_test_skinny_qkv", "bert_hip_test_shard_bounds", "bert_hip_test_build_windows",
     "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots", "bert_hip_test_set_pad",
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
-    "bert_hip_test_pool",
+    "bert_hip_test_pool", "bert_hip_test_layernorm",
     "bert_hip_test_f32_gemm", "bert_hip_test_f32_attention", "bert_hip_test_f32_layernorm", "bert_hip_test_f32_embed_ln", "bert_hip_test_f32_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
@@ -182,7 +182,9 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_skinny_qkv.restype = i32
     L.bert_hip_test_skinny_qkv.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, vp, C.c_uint32, vp, vp]
     L.bert_hip_test_embed_ln.restype = i32
-    L.bert_hip_test_embed_ln.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32p, i32p, i32, vp]
+    L.bert_hip_test_embed_ln.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32p, i32p, i32, i32, vp]
+    L.bert_hip_test_layernorm.restype = i32
+    L.bert_hip_test_layernorm.argtypes = [i32, i32, vp, vp, vp, vp]
     L.bert_hip_test_pool_normalize.restype = i32
     L.bert_hip_test_pool_normalize.argtypes = [i32, vp, i32p, i32, i32, vp, i32p]
     L.bert_hip_test_pool.restype = i32
@@ -235,16 +237,31 @@ def test_lib() -> C.CDLL:
     return L
 
 
-def test_embed_ln(table_type: int, word_bytes, type_bytes, pos_bytes, H: int, gamma, beta, tokens, cu_seqlens) -> np.ndarray:
+def test_embed_ln(table_type: int, word_bytes, type_bytes, pos_bytes, H: int, gamma, beta, tokens, cu_seqlens, max_len: int = 0) -> np.ndarray:
+    """Tables as file-layout bytes (the position table has as many rows as pos_bytes holds); max_len: the promise the launch is made
+    under, 0 = the longest sentence.  Returns float16 [T, H]."""
     wb, tb, pb = (np.ascontiguousarray(a) for a in (word_bytes, type_bytes, pos_bytes))
     rb = {0: 4 * H, 1: 2 * H, 2: H // 32 * 18, 3: H // 32 * 20}[table_type]
     g = np.ascontiguousarray(gamma, dtype=np.float32); b = np.ascontiguousarray(beta, dtype=np.float32)
     toks = np.ascontiguousarray(tokens, dtype=np.int32); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    assert len(toks) == int(cu[-1]) and tb.nbytes == 2 * rb and g.shape == (H,) and b.shape == (H,)
     out = np.zeros((len(toks), H), dtype=np.float16)
     r = test_lib().bert_hip_test_embed_ln(table_type, H, wb.nbytes // rb, pb.nbytes // rb, wb.ctypes.data, tb.ctypes.data, pb.ctypes.data,
-                                          g.ctypes.data, b.ctypes.data, _i32p(toks), _i32p(cu), len(cu) - 1, out.ctypes.data)
+                                          g.ctypes.data, b.ctypes.data, _i32p(toks), _i32p(cu), len(cu) - 1, max_len, out.ctypes.data)
     if r != 0:
         raise RuntimeError(f"bert_hip_test_embed_ln failed: {r}")
+    return out
+
+
+def test_layernorm(x: np.ndarray, gamma, beta) -> np.ndarray:
+    """launch_layernorm on f16 rows x [T, H] (in place on the device, as in the engine); returns float16 [T, H]."""
+    x = np.ascontiguousarray(x, dtype=np.float16)
+    g = np.ascontiguousarray(gamma, dtype=np.float32); b = np.ascontiguousarray(beta, dtype=np.float32)
+    assert g.shape == (x.shape[1],) and b.shape == (x.shape[1],)
+    out = np.zeros_like(x)
+    r = test_lib().bert_hip_test_layernorm(x.shape[0], x.shape[1], x.ctypes.data, g.ctypes.data, b.ctypes.data, out.ctypes.data)
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_layernorm failed: {r}")
     return out
 
 
@@ -321,7 +338,7 @@ def set_window_slots(slots: int) -> int:
 @contextlib.contextmanager
 def test_pad(pattern16: int, pattern32: int):
     """While the block runs, the batch-route op entries (test_gemm, test_gemm_lnfold, test_attention, test_qkv_attention,
-    test_layer_tail) and the f32 route's (test_f32_*) fill their padding rows and every output / intermediate buffer with these bit patterns before they launch
+    test_layer_tail, test_embed_ln, test_layernorm) and the f32 route's (test_f32_*) fill their padding rows and every output / intermediate buffer with these bit patterns before they launch
     (include/bert_hip_test.h bert_hip_test_set_pad); zeros again afterwards."""
     L = test_lib()
     L.bert_hip_test_set_pad(pattern16, pattern32)

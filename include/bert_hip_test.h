@@ -19,7 +19,7 @@ extern "C" {
  *     (pattern32 in 32-bit buffers);
  *   - every output and intermediate buffer (C, u, out2, the partial statistics and finalized rows of the LayerNorm fold, qkv
  *     between projection and attention, y and the intermediate of the five-kernel tail, every out) holds it in ALL its words.
- * Entries: bert_hip_test_gemm, _gemm_lnfold, _attention, _qkv_attention, _layer_tail and the five _f32_ entries (the latency route's
+ * Entries: bert_hip_test_gemm, _gemm_lnfold, _attention, _qkv_attention, _layer_tail, _embed_ln, _layernorm and the five _f32_ entries (the latency route's
  * entries take a `pad` argument of their own).  0, 0 (the state at load): zeros, as before.  Quiet NaNs (0x7E00, 0x7FC00000) make any read of such a word
  * show in the rows a call returns; to the kernels they are data.  Set it under try / finally: it outlives the call.          */
 BERT_API void bert_hip_test_set_pad(uint32_t pattern16, uint32_t pattern32);
@@ -90,12 +90,22 @@ BERT_API int32_t bert_hip_test_skinny_qkv(int32_t M, int32_t H, const uint16_t *
                                           const float *beta, const void *Wqkv, int32_t wtype, const float *bias, uint32_t pad,
                                           uint16_t *qkv, uint16_t *ln_out);
 
-/* Embedding gather-sum + LayerNorm (reference bert.cpp:796-814): tables in the file layout of `table_type` (0 f32, 1 f16,
- * 2 q4_0, 3 q4_1), word [n_vocab][H], type [2][H], pos [n_pos][H]; packed sentences; out [T][H] f16 bits.               */
+/* The f16 row kernels of misc_kernels.hip, launched as the engine launches them.  Token-row buffers have the engine's workspace shape,
+ * whole tiles of 256 rows: under bert_hip_test_set_pad the rows behind the last token hold pattern16 (the embedding's output buffer
+ * holds it in ALL its words before the launch), and an entry returns -4 if a word behind the last token's row has changed afterwards.
+ * -1: bad arguments or a HIP error.
+ * Embedding gather-sum + LayerNorm (reference bert.cpp:796-814): tables in the file layout of `table_type` (0 f32, 1 f16,
+ * 2 q4_0, 3 q4_1), word [n_vocab][H], type [2][H] (row 0 is used), pos [n_pos][H]; packed sentences; out [T][H] f16 bits.  Ids outside
+ * [0, n_vocab) take row 0 resp. n_vocab - 1.  max_len is the caller's promise as bert_hip_eval_packed_device takes it (0: the longest
+ * sentence; <= n_pos, -1 otherwise): it chooses the grid form, and no position row at or behind max_len is read.  Rows of a sentence
+ * longer than max_len behind its place round_up(max_len, 4) may keep the pattern.                                                   */
 BERT_API int32_t bert_hip_test_embed_ln(int32_t table_type, int32_t H, int32_t n_vocab, int32_t n_pos, const void *word,
                                         const void *type, const void *pos, const float *gamma, const float *beta,
                                         const bert_vocab_id *tokens, const int32_t *cu_seqlens, int32_t n_sentences,
-                                        uint16_t *out);
+                                        int32_t max_len, uint16_t *out);
+/* out [T][H] = LayerNorm(x [T][H]) gamma + beta on f16 rows, in place on the device as in the engine (launch_layernorm: two-pass
+ * statistics, eps 1e-5); H even, at most 4096.                                                                                      */
+BERT_API int32_t bert_hip_test_layernorm(int32_t T, int32_t H, const uint16_t *x, const float *gamma, const float *beta, uint16_t *out);
 /* Mean-pool + L2 normalise (reference bert.cpp:904-913) of x [T][H] f16 bits -> out [n_sentences][H] f32; *status receives
  * the device status word (1 if a sentence length is outside [1, max_len]: its row is NaN).                              */
 BERT_API int32_t bert_hip_test_pool_normalize(int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences,

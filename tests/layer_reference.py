@@ -160,6 +160,92 @@ def softmax_bound(q, k, v, scale):
     return dw @ np.abs(v) + 8 * (n + 8) * U32 * wv + ulp16(want), want
 
 
+# The generic kernels (gemm_naive_kernel, attention_naive_kernel): one thread an element, plain f32 loops, no matrix cores.
+#
+# __expf(x) is exp2(x log2(e)) on v_exp_f32.  No run has measured it here (f32_reference.py measured the device's tanhf only and
+# takes expf from the OpenCL profile, EXPF_ULP = 3 ulp -- the library function, which this is not); its error is derived:
+#   - log2(e) is an f32 constant (u of it) and the product with x rounds once: the argument of exp2 is off by 2 u |x log2(e)|,
+#     which exp2 turns into the fraction 2 u |x| of the result;
+#   - v_exp_f32 is documented to 1 ulp (2 u of the result); NATIVE_EXP2_ULP allows two;
+#   - a result below 2^-126 is flushed to zero: an absolute 2^-126.
+NATIVE_EXP2_ULP = 2.0
+
+
+def native_expf_rel(x):
+    """the fraction of exp(x) by which the device's __expf(x) may differ from it (besides the flush below 2^-126)"""
+    return 2 * U32 * np.abs(f8(x)) + 2 * NATIVE_EXP2_ULP * U32
+
+
+def generic_matmul_bound(A, W, bias, resid=None):
+    """|gemm_naive_kernel - (A W^T + bias (+ resid))| before the GELU, A and W f16 values, as f32_reference.matmul_bound derives it
+    for an f32 chain, plus the rounding of the result to f16:
+      - the products of two f16 numbers are exact in f32 (22 bits), fused or not; the accumulator is ONE ascending chain of K f32
+        additions: at most g_K S, g_K = K u / (1 - K u), S = sum_k |a_k w_k|;
+      - + bias rounds once: u (|A W^T + bias| + g_K S); with a residual one more addition, u |want|;
+      - g_K (1 + 2 u) <= (K + 1) u while K^2 u <= 1 (K <= 4096); (K + 2) leaves that room twice.  No factor 4: no matrix cores;
+      - the result rounds to f16 once: ulp16(want) (twice what a rounding to nearest costs; the slack covers the rounding boundary
+        the f32 error can push the value across).
+    Returns (bound, want, pre, dpre): pre = A W^T + bias and the most the device's f32 one differs from it."""
+    K = np.shape(A)[1]
+    S = np.abs(f8(A)) @ np.abs(f8(W)).T
+    pre = f8(A) @ f8(W).T + f8(bias)
+    dpre = (K + 2) * U32 * S + U32 * np.abs(pre)
+    want = pre if resid is None else pre + f8(resid)
+    return dpre + (0 if resid is None else U32 * np.abs(want)) + ulp16(want), want, pre, dpre
+
+
+def generic_gemm_bound(A, W, bias, resid, epilogue):
+    """(bound, want) of one call of gemm_naive_kernel under `epilogue` (0 bias, 1 bias + GELU, 2 bias + resid).  GELU: gelu_tanh
+    (gemm.hip) evaluates x / (1 + exp2(t)) in f32; gelu_bound is derived for the same formula evaluated in f16 on the f16-rounded
+    pre-activation and admits every f32 evaluation of it (test_gpu_value_ranges.py holds this kernel to it), and |gelu'| <= 1.13
+    carries the pre-activation's own error."""
+    bound, want, pre, dpre = generic_matmul_bound(A, W, bias, resid if epilogue == 2 else None)
+    if epilogue == 1:
+        return gelu_bound(pre) + 1.13 * dpre, gelu(pre)
+    return bound, want
+
+
+def generic_attention_bound(q, k, v):
+    """|attention_naive_kernel - softmax(q k^T / sqrt(d)) v| for one head (q, k, v [n][d] f16 values), per element, to first order:
+    a two-pass softmax (the TRUE maximum is subtracted, one division at the end), as f32_reference.softmax_bound derives it, with
+    p_j = exp(s_j - max), L = sum p, w = p / L:
+      - s_j = (sum_e k_e q_e) scale: exact products, a chain of d f32 additions, d u sum |k q|; scale = 1 / sqrtf(d), two roundings,
+        and the product a third: (d + 3) u (|q| . |k_j|) scale;
+      - s_j - max rounds once, u |s_j - max|; the maximum's own error multiplies every p by the same factor and cancels in p / L;
+        __expf: native_expf_rel(s_j - max) of p_j, and the flush: 2^-126 on the scale where the largest p is 1;
+      - L is a sum of the n numbers p_j (64 lane chains, then the wave's tree: at most n u), 1 / L rounds once; the output is a chain
+        of n terms v_j p_j, each product rounding once unless it is fused, and its product with 1 / L rounds once: (3 n + 2) u sum w |v|;
+      - the result rounds to f16 once: ulp16(want).
+    |dw_j| <= w_j eps_j + 2^-126 / L + w_j sum_k (w_k eps_k + 2^-126 / L).  Returns (bound, want)."""
+    q, k, v = f8(q), f8(k), f8(v)
+    n, d = q.shape
+    scale = 1 / np.sqrt(d)
+    sc = q @ k.T * scale
+    mx = sc.max(axis=1, keepdims=True)
+    eps = (d + 3) * U32 * (np.abs(q) @ np.abs(k).T) * scale + U32 * (mx - sc) + native_expf_rel(sc - mx)
+    p = np.exp(sc - mx)
+    L = p.sum(axis=1, keepdims=True)
+    w = p / L
+    dw = w * eps + 2.0 ** -126 / L
+    dw = dw + w * dw.sum(axis=1, keepdims=True)
+    want = w @ v
+    return dw @ np.abs(v) + (3 * n + 2) * U32 * (w @ np.abs(v)) + ulp16(want), want
+
+
+def generic_attention_packed(qkv, lens, n_head, d_head):
+    """qkv [T][3H] f16 of packed sentences -> (float64 context rows [T][H], their bounds)"""
+    H = n_head * d_head
+    want, bnd = np.zeros((len(qkv), H)), np.zeros((len(qkv), H))
+    t0 = 0
+    for n in lens:
+        for h in range(n_head):
+            sl = slice(h * d_head, (h + 1) * d_head)
+            q, k, v = (qkv[t0:t0 + n, i * H:(i + 1) * H][:, sl] for i in range(3))
+            bnd[t0:t0 + n, sl], want[t0:t0 + n, sl] = generic_attention_bound(q, k, v)
+        t0 += n
+    return want, bnd
+
+
 # ------------------------------------------------------------------------------------------------
 # NumPy emulations of the device arithmetic the bounds are about
 # ------------------------------------------------------------------------------------------------
@@ -212,6 +298,62 @@ def softmax_online(q, k, v, scale, chunk=128):
             o = o * alpha + (f8(p.astype(np.float16)) @ f8(v[sl])).astype(np.float32)
             m_run = m_new
     return (o * (np.float32(1) / l_run)).astype(np.float16)
+
+
+def gelu_tanh_f32(x):
+    """gemm.hip gelu_tanh in float32: x / (1 + exp2(t)), t = x fma(x x, c2, c1); exp2 and the reciprocal correctly rounded where the
+    device is within one ulp"""
+    x = np.asarray(x, dtype=np.float32)
+    c1 = np.float32(-2.0) * np.float32(0.79788456080286535588) * np.float32(1.44269504088896340736)
+    c2 = c1 * np.float32(0.044715)
+    with np.errstate(over="ignore"):
+        t = x * (f8(x * x) * f8(c2) + f8(c1)).astype(np.float32)
+        return x * (1.0 / f8(np.float32(1) + np.exp2(f8(t)).astype(np.float32))).astype(np.float32)
+
+
+def generic_gemm(A, W, bias, resid, epilogue, k_terms=None):
+    """gemm_naive_kernel: one ascending f32 chain over k of exact products, + bias, the epilogue in f32, one rounding to f16.
+    k_terms: how many of the K terms enter the sum (None: all; K - 1: a loop that ends one short)"""
+    a, w = f8(np.asarray(A).astype(np.float16)), f8(np.asarray(W).astype(np.float16))
+    acc = np.zeros((a.shape[0], w.shape[0]), np.float32)
+    for kk in range(a.shape[1] if k_terms is None else k_terms):
+        acc = (f8(acc) + a[:, kk, None] * w[None, :, kk]).astype(np.float32)
+    acc = acc + np.asarray(bias, dtype=np.float32)[None, :]
+    if epilogue == 1:
+        acc = gelu_tanh_f32(acc)
+    if epilogue == 2:
+        acc = acc + np.asarray(resid).astype(np.float16).astype(np.float32)
+    return acc.astype(np.float16)
+
+
+def generic_attention(q, k, v, lanes=64):
+    """attention_naive_kernel for one head in float32: ascending chains for the scores, the product with 1 / sqrtf(d), the true
+    maximum, exp2 of the rounded product with log2(e) (__expf), lane j % 64 sums its keys in ascending order and the lanes' sums
+    meet in the wave's xor tree, an ascending chain of rounded products v_j p_j, the product with 1 / L, one rounding to f16.
+    lanes: how many of the 64 lanes' sums enter L (64: the kernel)"""
+    q, k, v = (np.asarray(a).astype(np.float16) for a in (q, k, v))
+    n, d = q.shape
+    s = np.zeros((n, n), np.float32)
+    for e in range(d):
+        s = (f8(s) + f8(q[:, e, None]) * f8(k[None, :, e])).astype(np.float32)
+    s = s * (np.float32(1) / np.sqrt(np.float32(d)))
+    x = s - s.max(axis=1, keepdims=True)
+    with np.errstate(under="ignore"):
+        p = np.exp2(f8(x * np.float32(1.44269504088896340736))).astype(np.float32)
+    p[p < np.float32(2.0 ** -126)] = 0
+    part = np.zeros((n, 64), np.float32)
+    for j in range(n):
+        part[:, j % 64] += p[:, j]
+    part[:, lanes:] = 0
+    o = 32
+    while o:
+        part = part + part[:, np.arange(64) ^ o]
+        o >>= 1
+    inv = np.float32(1) / part[:, :1]
+    acc = np.zeros((n, d), np.float32)
+    for j in range(n):
+        acc = acc + v[j].astype(np.float32)[None, :] * p[:, j, None]
+    return (acc * inv).astype(np.float16)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -300,3 +442,21 @@ def softmax_case(case, n, d, seed=0):
         q *= 1.7
         v *= 2.0 ** -17
     return q.astype(np.float16), k.astype(np.float16), v.astype(np.float16)
+
+
+def generic_gemm_inputs(M, N, K, seed=0):
+    """A [M][K] f16, W [N][K] f32 (to be stored in a file type), bias [N] f32, resid [M][N] f16: normal draws, the columns of W
+    growing with k by a factor 2 over the row (a kernel that swaps, repeats or drops a k cannot pass), sums of size 1"""
+    rng = np.random.default_rng(1000003 * M + 1009 * N + K + seed)
+    A = rng.normal(0, 1, (M, K)).astype(np.float16)
+    W = (rng.normal(0, 1, (N, K)) / np.sqrt(K) * (1 + np.arange(K) / K)).astype(np.float32)
+    return A, W, rng.normal(0, 0.5, N).astype(np.float32), rng.normal(0, 1, (M, N)).astype(np.float16)
+
+
+def generic_attention_inputs(lens, n_head, d_head):
+    """qkv [T][3H] f16 for sentences of `lens`: Q a little wide, so that the softmax is neither flat nor one-hot"""
+    rng = np.random.default_rng(sum(lens) * 131 + n_head * 17 + d_head)
+    H = n_head * d_head
+    qkv = rng.normal(0, 1, (sum(lens), 3 * H))
+    qkv[:, :H] *= 1.7
+    return qkv.astype(np.float16)

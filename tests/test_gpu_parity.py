@@ -137,6 +137,33 @@ def test_gemm_mfma_q4_tile_load_gives_the_f16_form_s_bits(M, N, K, wtype):
     _q4_gives_the_f16_form_s_bits(M, N, K, wtype, 0)
 
 
+@pytest.mark.parametrize("K", [64, 192])
+@pytest.mark.parametrize("N", [8, 72, 136, 200])
+def test_gemm_mfma_feature_tile_of_a_multiple_of_8(N, K, M=130):
+    """gemm_mfma_kernel takes every N % 8 == 0 (weights.cpp mfma_ok) -- an intermediate size of 136 gives such an up-projection --
+    but the partial feature tiles above are 64 and 192 wide.  N = 8, 72, 136, 200: the last tile holds 8 features (two 4-feature
+    chunks pass `f0 < N`, the image's rows behind N are zero), ragged tokens, one and three reduction tiles, all three epilogues.  The
+    f16 form against float64 within layer_reference.matmul_bound (and gelu_bound behind it) plus the rounding to f16; the q4 forms
+    give the f16 form's bits on their image.  Measured: worst fraction of the bound 0.48 (bias, residual), 0.17 (GELU)."""
+    ref = layer_reference
+    rng = np.random.default_rng(N + K)
+    A = rng.normal(0, 1, (M, K)).astype(np.float16)
+    W = (rng.normal(0, 1, (N, K)) / np.sqrt(K) * (1 + np.arange(K) / K)).astype(np.float16)
+    bias = rng.normal(0, 0.5, N).astype(np.float32)
+    resid = rng.normal(0, 1, (M, N)).astype(np.float16)
+    pre = ref.f8(A) @ ref.f8(W).T + ref.f8(bias)
+    for epi in (0, 1, 2):
+        got = ref.f8(pybert.test_gemm(A, W.view(np.uint8).reshape(-1), 1, N, bias, resid if epi == 2 else None, epi, 0))
+        dpre, _ = ref.matmul_bound(A, W, bias, resid if epi == 2 else np.zeros((M, N)))
+        want = pre if epi == 0 else ref.gelu(pre) if epi == 1 else pre + ref.f8(resid)
+        bound = ref.gelu_bound(pre) + 1.13 * dpre if epi == 1 else dpre + ref.ulp16(want)
+        frac = float((np.abs(got - want) / bound).max())
+        print(f"gemm_mfma N {N} K {K} epi {epi}: worst err / bound {frac:.3f}")
+        assert frac <= 1, (N, K, epi, frac, np.argwhere(np.abs(got - want) > bound)[:5].tolist())
+    for wtype in (2, 3):
+        _q4_gives_the_f16_form_s_bits(M, N, K, wtype, 0)
+
+
 @pytest.mark.parametrize("rebuild", [False, True], ids=["plain-residual", "rebuilt-residual"])
 @pytest.mark.parametrize("M,K1,H,N2,epi2", [(300, 768, 768, 3072, 1), (1000, 3072, 768, 2304, 0), (20000, 256, 768, 768, 1), (257, 128, 256, 512, 0),
                                              (257, 128, 256, 512, 2)])

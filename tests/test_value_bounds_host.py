@@ -110,3 +110,68 @@ def test_softmax_bound_refuses_a_missing_rescale():
         o = o + p @ ref.f8(v)[c:c + 128]                    # (no o *= alpha)
         m = m_new
     assert (np.abs(o / l - want) > bound).mean() > 0.5
+
+
+# ------------------------------------------------------------------------------------------------
+# the generic kernels (test_gpu_generic_kernels.py holds gemm_naive_kernel and attention_naive_kernel to these bounds on the GPU)
+# ------------------------------------------------------------------------------------------------
+GENERIC_GEMM_SHAPES = [(1, 1, 1), (3, 7, 5), (5, 100, 100), (33, 136, 64), (4, 64, 33), (130, 65, 130), (257, 300, 20)]
+
+
+@pytest.mark.parametrize("M,N,K", GENERIC_GEMM_SHAPES)
+def test_generic_matmul_emulation_stays_inside_its_bound(M, N, K):
+    """One ascending f32 chain, the bias, the epilogue, one rounding to f16: worst fraction of the bound 0.499 under the bias and
+    residual epilogues (the rounding to f16 is half the ulp the bound allows for it) and 0.176 under the GELU; a k loop that ends one
+    term short is outside it on more than half of the elements of every shape (at least 97 % / 83 % / 96 % of them under the three
+    epilogues)."""
+    A, W, bias, resid = ref.generic_gemm_inputs(M, N, K)
+    W16 = W.astype(np.float16)
+    for epi in (0, 1, 2):
+        bound, want = ref.generic_gemm_bound(A, W16, bias, resid, epi)
+        err = np.abs(ref.f8(ref.generic_gemm(A, W16, bias, resid, epi)) - want)
+        assert (err <= bound).all(), (epi, float((err / bound).max()))
+        short = np.abs(ref.f8(ref.generic_gemm(A, W16, bias, resid, epi, k_terms=K - 1)) - want)
+        assert (short > bound).mean() > 0.5, (epi, float((short > bound).mean()))
+
+
+@pytest.mark.parametrize("d", [2, 20, 33, 64, 96])
+def test_generic_attention_emulation_stays_inside_its_bound(d):
+    """The two-pass softmax with exp2(x log2(e)) in float32 on the lengths the GPU test uses: worst fraction of the bound 0.49 (the
+    rounding to f16).  With the sum of 63 of the 64 lanes (lane 63's keys 63 and 127 missing from L) every sentence of 64 keys or
+    more is outside it, on more than a third of its elements (67 % to 94 %); a shorter one does not use the lane."""
+    lens = [1, 2, 3, 4, 5, 63, 64, 65, 130]
+    qkv = ref.generic_attention_inputs(tuple(lens), 1, d)
+    t0 = 0
+    for n in lens:
+        q, k, v = (qkv[t0:t0 + n, i * d:(i + 1) * d] for i in range(3))
+        t0 += n
+        bound, want = ref.generic_attention_bound(q, k, v)
+        err = np.abs(ref.f8(ref.generic_attention(q, k, v)) - want)
+        assert (err <= bound).all(), (n, float((err / bound).max()))
+        short = np.abs(ref.f8(ref.generic_attention(q, k, v, lanes=63)) - want)
+        if n >= 64:
+            assert (short > bound).mean() > 1 / 3, (n, float((short > bound).mean()))
+        else:
+            assert (short <= bound).all()
+
+
+@pytest.mark.parametrize("n", [1, 17, 129])
+def test_generic_attention_bound_on_the_hard_softmax_cases(n, d=20):
+    """layer_reference.SOFTMAX_CASES through the emulation: scores of +-300 (exponentials flushed to zero), one key 40 ahead, |V| up to
+    2^14 and in the subnormals -- all inside the bound (worst 0.498, subnormal-v), nothing NaN; the
+    ahead-* cases are exact."""
+    for case in ref.SOFTMAX_CASES:
+        q, k, v = ref.softmax_case(case, n, d)
+        bound, want = ref.generic_attention_bound(q, k, v)
+        got = ref.generic_attention(q, k, v)
+        err = np.abs(ref.f8(got) - want)
+        assert np.isfinite(got).all() and (err <= bound).all(), (case, float((err / bound).max()))
+
+
+def test_native_expf_bound_admits_the_emulated_exp2():
+    """exp2 of the ROUNDED product x log2(e) against exp(x) on [-87, 0]: inside native_expf_rel with one of its two ulps to spare (worst 0.59
+    of the whole)"""
+    x = -np.random.default_rng(0).uniform(0, 87, 100000).astype(np.float32)
+    got = np.exp2(ref.f8(x * np.float32(1.44269504088896340736))).astype(np.float32)
+    rel = np.abs(ref.f8(got) / np.exp(ref.f8(x)) - 1)
+    assert (rel <= ref.native_expf_rel(x) - 2 * ref.U32).all(), float((rel / ref.native_expf_rel(x)).max())
