@@ -30,4 +30,9 @@ auto guarded(const char *name, F &&body, R on_error = {}) -> decltype(body()) {
 // for a context without a device
 int32_t encode_batch_impl(bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, float **embeddings);
 
+// bert_hip_encode_long_batch: number of inputs encoded, -1 for a context without a device, -2 (outputs untouched) for a bad window or stride
+int32_t encode_long_batch_impl(bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, int32_t window, int32_t stride,
+                               float **embeddings, int32_t *n_windows);
+bool long_args_ok(const char *me, const bert_ctx *ctx, int32_t window, int32_t stride);
+
 }  // namespace bert_hip

@@ -104,6 +104,38 @@ int32_t bert_hip::encode_batch_impl(bert_ctx *ctx, int32_t n_threads, int32_t n_
     });
 }
 
+// window and stride as bert_hip_plan_windows takes them, for this context's model (-2 after a line on stderr otherwise)
+bool bert_hip::long_args_ok(const char *me, const bert_ctx *ctx, int32_t window, int32_t stride) {
+    const bool ok = window >= 3 && window <= ctx->hp.n_max_tokens && stride >= 1 && stride <= window - 2;
+    if (!ok) fprintf(stderr, "%s: 3 <= window <= %d and 1 <= stride <= window - 2 required (window %d, stride %d)\n", me, ctx->hp.n_max_tokens, window, stride);
+    return ok;
+}
+
+// Long texts: tokenized without truncation, cut into windows, every window an ordinary sentence, one pooled row per text
+// (text_batch.h encode_long_groups; the grouped pooling of gather.h).
+int32_t bert_hip::encode_long_batch_impl(bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, int32_t window, int32_t stride,
+                                         float **embeddings, int32_t *n_windows) {
+    const char *me = "bert_hip_encode_long_batch";
+    if (!ctx->engine()) { fprintf(stderr, "%s: this context has no device weights (tokenizer-only)\n", me); return -1; }
+    if (!long_args_ok(me, ctx, window, stride)) return -2;
+    if (n_inputs <= 0) return 0;
+    if (!texts || !embeddings) { fprintf(stderr, "%s: texts and embeddings required\n", me); return -2; }
+    const size_t H = ctx->hp.n_embd;
+    std::vector<float> out;
+    return ctx->texts.encode_long_groups(n_threads, n_inputs, texts, window, stride, n_windows, [&](const LongGroup &g, int32_t i0) -> int32_t {
+        const int32_t G = g.n_texts();
+        out.resize((size_t)G * H);
+        std::string err;
+        if (eval_packed_grouped_all_devices(ctx->engines, ctx->workers.get(), g.packed.data(), g.cu.data(), g.n_windows(), g.group_cu.data(), G,
+                                            out.data(), nullptr, err) != 0) {
+            fprintf(stderr, "%s: %s\n", me, err.c_str());
+            return -1;
+        }
+        for (int32_t i = 0; i < G; ++i) memcpy(embeddings[i0 + i], out.data() + (size_t)i * H, sizeof(float) * H);
+        return G;
+    });
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------
@@ -243,6 +275,76 @@ int32_t bert_hip_eval_packed_device(struct bert_ctx *ctx, const bert_vocab_id *d
         }
         return 0;
     }, (int32_t)-4);
+}
+
+int32_t bert_hip_eval_packed_grouped(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens, int32_t n_sentences,
+                                     const int32_t *group_cu, int32_t n_groups, float *embeddings) {
+    const char *me = "bert_hip_eval_packed_grouped";
+    return guarded(me, [&]() -> int32_t {
+        const int32_t st = packed_batch_status(ctx, me, tokens, cu_seqlens, n_sentences);
+        if (st != 1) return st;
+        // group_cu before anything is launched: from 0 to n_sentences, strictly increasing (no empty group)
+        bool ok = group_cu && embeddings && n_groups >= 1 && n_groups <= n_sentences && group_cu[0] == 0 && group_cu[n_groups] == n_sentences;
+        for (int32_t g = 0; ok && g < n_groups; ++g) ok = group_cu[g + 1] > group_cu[g];
+        if (!ok) {
+            fprintf(stderr, "%s: group_cu must hold n_groups + 1 strictly increasing entries from 0 to n_sentences = %d\n", me, n_sentences);
+            return -2;
+        }
+        std::string err;
+        if (eval_packed_grouped_all_devices(ctx->engines, ctx->workers.get(), tokens, cu_seqlens, n_sentences, group_cu, n_groups, embeddings,
+                                            nullptr, err) != 0) {
+            fprintf(stderr, "%s: %s\n", me, err.c_str());
+            return -3;
+        }
+        return 0;
+    }, (int32_t)-4);
+}
+
+int32_t bert_hip_eval_packed_grouped_device(struct bert_ctx *ctx, const bert_vocab_id *d_tokens, const int32_t *d_cu_seqlens, int32_t n_sentences,
+                                            int32_t n_tokens_total, int32_t max_len, const int32_t *d_group_cu, int32_t n_groups,
+                                            float *d_embeddings, void *stream) {
+    const char *me = "bert_hip_eval_packed_grouped_device";
+    return guarded(me, [&]() -> int32_t {
+        if (!ctx->engine()) { fprintf(stderr, "%s: tokenizer-only context\n", me); return -1; }
+        if (max_len > ctx->hp.n_max_tokens) { fprintf(stderr, "Too many tokens, maximum is %d\n", ctx->hp.n_max_tokens); return -2; }
+        if (max_len <= 0 || n_tokens_total > (long long)n_sentences * max_len) {
+            fprintf(stderr, "%s: max_len = %d cannot hold %d tokens in %d sentences\n", me, max_len, n_tokens_total, n_sentences);
+            return -2;
+        }
+        if (n_groups < 0 || n_groups > n_sentences || (n_groups > 0 && (!d_group_cu || !d_embeddings))) {
+            fprintf(stderr, "%s: 0 <= n_groups <= n_sentences and group_cu / embeddings required\n", me);
+            return -2;
+        }
+        std::string err;
+        if (ctx->engine()->eval_packed_grouped_device(d_tokens, d_cu_seqlens, n_sentences, n_tokens_total, max_len, d_group_cu, n_groups,
+                                                      d_embeddings, (hipStream_t)stream, err) != 0) {
+            fprintf(stderr, "%s: %s\n", me, err.c_str());
+            return -3;
+        }
+        return 0;
+    }, (int32_t)-4);
+}
+
+int32_t bert_hip_tokenize_long(struct bert_ctx *ctx, const char *text, bert_vocab_id *tokens, int32_t cap) {
+    if (!ctx || !text) return -1;
+    return guarded("bert_hip_tokenize_long", [&]() -> int32_t {
+        std::vector<int32_t> ids;
+        ctx->texts.tokenize_long(text, ids);
+        const int32_t n = (int32_t)ids.size();
+        if (tokens && cap >= n) memcpy(tokens, ids.data(), sizeof(int32_t) * (size_t)n);
+        return n;
+    }, (int32_t)-4);
+}
+
+int32_t bert_hip_plan_windows(int32_t n_tokens, int32_t window, int32_t stride, int32_t *starts, int32_t cap) {
+    return plan_windows(n_tokens, window, stride, starts, cap);
+}
+
+int32_t bert_hip_encode_long_batch(struct bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, int32_t window, int32_t stride,
+                                   float **embeddings, int32_t *n_windows) {
+    if (!ctx) return -1;
+    return guarded("bert_hip_encode_long_batch", [&] { return encode_long_batch_impl(ctx, n_threads, n_inputs, texts, window, stride, embeddings, n_windows); },
+                   (int32_t)-4);
 }
 
 int32_t bert_hip_reserve(struct bert_ctx *ctx, int32_t n_tokens, int32_t n_sentences) {

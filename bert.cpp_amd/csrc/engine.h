@@ -28,8 +28,9 @@ public:
 
     // host-resident packed batch (validated by the caller), blocking
     // embeddings: host destination [n_sentences][H]; d_embeddings (optional, instead): destination in this device's memory
+    // pool_mode: as for eval_packed_device below
     int eval_packed_host(const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, float *embeddings,
-                         std::string &err, float *d_embeddings = nullptr);
+                         std::string &err, float *d_embeddings = nullptr, int pool_mode = -1);
     // device-resident, asynchronous on `stream`
     // d_windows / n_windows: optional sentence windows of the fused projection+attention kernel (build_windows), in
     // device memory; without them the same windows are built on the device (launch_build_windows) when the batch is
@@ -43,6 +44,18 @@ public:
     // not used for such batches).
     static void build_windows(const int32_t *cu_seqlens, int n_sentences, std::vector<int2> &windows, int slots);
     int eval_hidden(const int32_t *tokens, int n_tokens, float *hidden, float *embedding, std::string &err);
+
+    // Grouped pooling (bert_hip.h "long texts"): the pass runs with POOL_RAW handed in as an argument (the options stay as they
+    // are), its rows go to raw_rows_ and launch_group_pool makes one row of every group of consecutive sentences, by the context's
+    // "pooling" (token-count or unit weights) and "normalize", both read once per call.  group_cu: n_groups + 1 entries.
+    // Host form, blocking: group_cu validated by the caller; embeddings: host destination [n_groups][H], or d_embeddings: one in this
+    // device's memory.  h_raw_rows (optional): the sentences' POOL_RAW rows [n_sentences][H] in host memory, computed elsewhere (a
+    // multi-device context's sharded pass) under pool_mode: no pass here, they are uploaded and pooled.
+    int eval_packed_grouped_host(const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, const int32_t *group_cu, int n_groups,
+                                 float *embeddings, float *d_embeddings, std::string &err, const float *h_raw_rows = nullptr, int pool_mode = -1);
+    // Device form, asynchronous on `stream`.  raw_rows_ grows on demand like the workspace (eval_packed_device)
+    int eval_packed_grouped_device(const int32_t *d_tokens, const int32_t *d_cu, int n_sentences, int n_tokens, int max_len,
+                                   const int32_t *d_group_cu, int n_groups, float *d_out, hipStream_t stream, std::string &err);
 
     // sizes the workspace for batches of up to n_tokens tokens / n_sentences sentences now, so that later calls of
     // eval_packed_device never allocate (allocation synchronises the device and breaks stream capture)
@@ -100,6 +113,8 @@ private:
               int epi, std::string &err, const GemmLnFold *ln = nullptr);
     void attention(const Plan &p);
     void tap(const Plan &p, int idx);
+    // the grouped-pooling launch ("group_pool" in the profile) behind a pass on s, then busy_ again: the next pass must not write raw_rows_ under it
+    int group_pool(const int32_t *d_cu, int n_sentences, const int32_t *d_group_cu, int n_groups, float *d_out, int pool_mode, hipStream_t s, std::string &err);
     template <class F> void timed(const char *name, double flops, hipStream_t s, F &&f) { prof_.timed(name, flops, s, f); }
 
     HParams hp_;
@@ -110,6 +125,7 @@ private:
 
     // workspace (grow-only)
     DevBuf x_, qkv_, ctx_, y_, ff_, v32_, d_tokens_, d_cu_, d_out_, d_hidden_, status_, windows_;
+    DevBuf raw_rows_, group_in_, group_out_;                  // grouped pooling: the sentences' POOL_RAW rows [n_sentences][H] f32; the host form's cu_seqlens | group_cu and its groups' rows
     DevBuf ln_stats1_, ln_stats2_, ln_rows1_, ln_rows2_;      // LayerNorm folding: per-row partial statistics / finalized rows of the two LayerNorms of a layer
     hipStream_t stream_ = nullptr;
     // the workspace serves ONE forward pass at a time: every pass waits for the previous one's event on its own stream

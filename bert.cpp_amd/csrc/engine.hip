@@ -431,7 +431,7 @@ static void copy_rows_out(float *dst, const float *src, size_t bytes) {
 }
 
 int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, float *embeddings, std::string &err,
-                             float *d_embeddings) {
+                             float *d_embeddings, int pool_mode_in) {
     if (B <= 0) return 0;
 #ifdef BERT_HIP_HOST_TRACE
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -494,7 +494,7 @@ int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, fl
     auto fail = [&]() { (void)hipStreamSynchronize(stream_); return -1; };        // nothing may stay queued on the slots
     std::vector<int2> windows;
     const int slots = window_slots();                         // (once per call: the lists below and the kernels that place by them)
-    const int pool_mode = opt_.pool_mode();                   // (once per call as well: every chunk ends by the same rule)
+    const int pool_mode = pool_mode_in >= 0 ? pool_mode_in : opt_.pool_mode();      // (once per call as well: every chunk ends by the same rule)
     for (size_t i = 0; i < chunks.size(); ++i) {
         HostSlot &sl = slot_[i & 1];
         const int b0 = chunks[i].b0, nb = chunks[i].b1 - b0, T = cu[chunks[i].b1] - cu[b0];
@@ -534,6 +534,58 @@ int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, fl
     }
     if (!unpack(chunks.size() - 1)) return fail();
 #undef HOST_LAP
+    return 0;
+}
+
+int Engine::group_pool(const int32_t *d_cu, int B, const int32_t *d_group_cu, int n_groups, float *d_out, int pool_mode, hipStream_t s, std::string &err) {
+    const int H = hp_.n_embd;
+    // (2 flops per element and sentence; the launch reads B rows and writes n_groups)
+    timed("group_pool", 2.0 * B * H, s, [&] {
+        launch_group_pool(raw_rows_.as<float>(), (pool_mode & POOL_CLS) ? nullptr : d_cu, d_group_cu, B, n_groups, H, (pool_mode & POOL_RAW) != 0,
+                          status_.as<int>(), d_out, s);
+    });
+    HIP_OK(hipGetLastError(), err, -1);
+    HIP_OK(hipEventRecord(busy_, s), err, -1);
+    return 0;
+}
+
+int Engine::eval_packed_grouped_device(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, const int32_t *d_group_cu,
+                                       int n_groups, float *d_out, hipStream_t s, std::string &err) {
+    if (B <= 0 || T <= 0 || n_groups <= 0) return 0;
+    const int pool_mode = opt_.pool_mode();                   // (once per call: the pass and the pooling agree)
+    HIP_OK(hipSetDevice(device_), err, -1);
+    if (!raw_rows_.ensure((size_t)B * hp_.n_embd * 4, err)) return -1;
+    if (eval_packed_device(d_tokens, d_cu, B, T, max_len, raw_rows_.as<float>(), s, nullptr, err, nullptr, 0, 0, pool_mode | POOL_RAW) != 0) return -1;
+    return group_pool(d_cu, B, d_group_cu, n_groups, d_out, pool_mode, s, err);
+}
+
+int Engine::eval_packed_grouped_host(const int32_t *tokens, const int32_t *cu, int B, const int32_t *group_cu, int n_groups, float *embeddings,
+                                     float *d_embeddings, std::string &err, const float *h_raw_rows, int pool_mode_in) {
+    if (B <= 0 || n_groups <= 0) return 0;
+    const int pool_mode = pool_mode_in >= 0 ? pool_mode_in : opt_.pool_mode();
+    const size_t H = hp_.n_embd;
+    HIP_OK(hipSetDevice(device_), err, -1);
+    // cu_seqlens (from 0, whatever window of the caller's prefix sums this is) | group_cu, one upload
+    const size_t n_in = (size_t)B + 1 + n_groups + 1;
+    if (!raw_rows_.ensure((size_t)B * H * 4, err) || !group_in_.ensure(n_in * 4, err) || (!d_embeddings && !group_out_.ensure((size_t)n_groups * H * 4, err))) return -1;
+    std::vector<int32_t> in(n_in);
+    for (int b = 0; b <= B; ++b) in[b] = cu[b] - cu[0];
+    std::copy(group_cu, group_cu + n_groups + 1, in.begin() + B + 1);
+    auto fail = [&](const char *what) { if (what) err = what; (void)hipStreamSynchronize(stream_); return -1; };      // nothing may stay queued on the caller's memory
+    if (h_raw_rows) {
+        // (a device-form call's pooling may still read raw_rows_ on another stream)
+        if (hipStreamWaitEvent(stream_, busy_, 0) != hipSuccess || hipMemcpyAsync(raw_rows_.p, h_raw_rows, (size_t)B * H * 4, hipMemcpyHostToDevice, stream_) != hipSuccess)
+            return fail("hipMemcpyAsync (raw rows) failed");
+    } else if (eval_packed_host(tokens, cu, B, nullptr, err, raw_rows_.as<float>(), pool_mode | POOL_RAW) != 0) {
+        // (blocking, chunk by chunk: the rows are in raw_rows_ when it returns; they never leave the device)
+        return -1;
+    }
+    if (hipMemcpyAsync(group_in_.p, in.data(), n_in * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) return fail("hipMemcpyAsync (groups) failed");
+    float *d_out = d_embeddings ? d_embeddings : group_out_.as<float>();
+    if (group_pool(group_in_.as<int32_t>(), B, group_in_.as<int32_t>() + B + 1, n_groups, d_out, pool_mode, stream_, err) != 0) return fail(nullptr);
+    if (!d_embeddings && hipMemcpyAsync(embeddings, d_out, (size_t)n_groups * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess)
+        return fail("hipMemcpyAsync (embeddings) failed");
+    HIP_OK(hipStreamSynchronize(stream_), err, -1);
     return 0;
 }
 

@@ -8,7 +8,7 @@ namespace bert_hip {
 constexpr long long MIN_SHARD_TOKENS = 2048;
 
 int eval_packed_all_devices(const Engines &engines, ShardWorkers *workers, const int32_t *tokens, const int32_t *cu, int B,
-                            float *embeddings, std::string &err, float *const *d_dst) {
+                            float *embeddings, std::string &err, float *const *d_dst, int pool_mode) {
     const int H = engines[0]->hparams().n_embd;
     int n_dev = (int)engines.size();
     const long long total = (long long)cu[B] - cu[0];
@@ -20,7 +20,7 @@ int eval_packed_all_devices(const Engines &engines, ShardWorkers *workers, const
     auto eval = [&](int r, int b0, int b1) {
         // eval_packed_host takes the global token array and a window of the prefix sums
         return engines[r]->eval_packed_host(tokens, cu + b0, b1 - b0, embeddings ? embeddings + (size_t)b0 * H : nullptr, errs[r],
-                                            d_dst ? d_dst[r] : nullptr);
+                                            d_dst ? d_dst[r] : nullptr, pool_mode);
     };
     int rc;
     if (n_dev == 1 || !workers) {
@@ -34,6 +34,18 @@ int eval_packed_all_devices(const Engines &engines, ShardWorkers *workers, const
         for (auto &e : errs)
             if (!e.empty()) { err = e; break; }
     return rc;
+}
+
+int eval_packed_grouped_all_devices(const Engines &engines, ShardWorkers *workers, const int32_t *tokens, const int32_t *cu, int B,
+                                    const int32_t *group_cu, int n_groups, float *embeddings, float *d_embeddings, std::string &err) {
+    Engine &first = *engines[0];
+    if (engines.size() == 1) return first.eval_packed_grouped_host(tokens, cu, B, group_cu, n_groups, embeddings, d_embeddings, err);
+    // (the first engine's settings, read once: every shard and the pooling end by the same rule)
+    const int pool_mode = first.options().pool_mode();
+    std::vector<float> raw((size_t)B * first.hparams().n_embd);
+    const int rc = eval_packed_all_devices(engines, workers, tokens, cu, B, raw.data(), err, nullptr, pool_mode | POOL_RAW);
+    if (rc != 0) return rc;
+    return first.eval_packed_grouped_host(tokens, cu, B, group_cu, n_groups, embeddings, d_embeddings, err, raw.data(), pool_mode);
 }
 
 void gather_runs(const int32_t *cu, int n_sentences, long long tokens_per_run, std::vector<int> &runs) {

@@ -19,9 +19,17 @@ using Engines = std::vector<std::unique_ptr<Engine>>;
 // One packed batch over the engines: every shard's embeddings written straight into the caller's rows (embeddings), or,
 // d_dst: into the shard's device buffer d_dst[device].  Host-row batches of fewer than 2048 tokens per device use fewer
 // devices (a launch sequence costs ~50 us whatever the size).  workers: the context's threads, or null (one device after the
-// other).  0, or an engine's error code and err; a worker's exception arrives as -9.
+// other).  0, or an engine's error code and err; a worker's exception arrives as -9.  pool_mode: kernels.h POOL_*, what every shard
+// ends by (-1: each engine reads its options).
 int eval_packed_all_devices(const Engines &engines, ShardWorkers *workers, const int32_t *tokens, const int32_t *cu, int B,
-                            float *embeddings, std::string &err, float *const *d_dst = nullptr);
+                            float *embeddings, std::string &err, float *const *d_dst = nullptr, int pool_mode = -1);
+
+// Grouped pooling (bert_hip.h "long texts"; Engine::eval_packed_grouped_host) over the engines: one row per group of consecutive
+// sentences into embeddings (host, [n_groups][H]) or d_embeddings (the FIRST device's memory).  One device: the sentences' raw rows
+// never leave it.  Several: the raw rows come through the sharded host path above into a host buffer, are uploaded to the first
+// device and pooled there — per-group bits do not depend on the number of devices.
+int eval_packed_grouped_all_devices(const Engines &engines, ShardWorkers *workers, const int32_t *tokens, const int32_t *cu, int B,
+                                    const int32_t *group_cu, int n_groups, float *embeddings, float *d_embeddings, std::string &err);
 
 // SUPER-BATCHES ("one gather per super-batch, overlapped with the next super-batch's compute"): a gather call is
 // cut into runs of sentences.  runs[k] .. runs[k + 1]: the sentences of run k (runs[0] = 0, the last entry n_sentences); a run

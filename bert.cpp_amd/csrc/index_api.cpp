@@ -203,6 +203,38 @@ int32_t bert_hip_index_add_texts(struct bert_hip_index *ix, int32_t n_threads, i
     });
 }
 
+int32_t bert_hip_index_add_long_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n, const char **texts, int32_t window, int32_t stride) {
+    const char *me = "bert_hip_index_add_long_texts";
+    return index_call(me, ix, [&](bert_ctx *ctx, Index &x, std::string &err) -> int32_t {
+        if (!dim_ok(me, ctx, x) || !long_args_ok(me, ctx, window, stride)) return -2;
+        if (n < 0 || (n > 0 && !texts)) { fprintf(stderr, "%s: n >= 0 and texts required\n", me); return -2; }
+        const int first = x.size();
+        if (n == 0) return first;
+        const size_t H = ctx->hp.n_embd;
+        bool ok;
+        if (ctx->engines.size() > 1) {
+            // (through the host, as add_texts does)
+            std::vector<float> emb((size_t)n * H);
+            std::vector<float *> rows((size_t)n);
+            for (int32_t i = 0; i < n; ++i) rows[i] = emb.data() + i * H;
+            ok = encode_long_batch_impl(ctx, n_threads, n, texts, window, stride, rows.data(), nullptr) == n && x.add_host(n, emb.data(), err) >= 0;
+            if (!ok && err.empty()) err = "the texts could not be encoded";
+        } else {
+            // every group's pooled rows go from the device buffer straight into the index
+            ok = ctx->texts.encode_long_groups(n_threads, n, texts, window, stride, nullptr, [&](const LongGroup &g, int32_t) -> int32_t {
+                const int32_t G = g.n_texts();
+                float *d = x.scratch((size_t)G * H, err);
+                if (!d || ctx->engine()->eval_packed_grouped_host(g.packed.data(), g.cu.data(), g.n_windows(), g.group_cu.data(), G, nullptr, d, err) != 0) return -1;
+                return x.add_device(G, d, x.stream(), err) >= 0 && hipStreamSynchronize(x.stream()) == hipSuccess ? G : -1;
+            }) == n;
+        }
+        if (ok) return first;
+        x.truncate(first);
+        if (err.empty()) err = "device error";
+        return -3;
+    });
+}
+
 int32_t bert_hip_index_search(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t k, int32_t *ids, float *scores) {
     return index_call("bert_hip_index_search", ix, [&](bert_ctx *, Index &x, std::string &err) {
         return x.search_to_host(n_queries, queries, false, k, ids, scores, err) != 0 ? -3 : 0;

@@ -155,6 +155,14 @@ constexpr int POOL_CLS = 1, POOL_RAW = 2;
 void launch_pool_normalize(const half_t *x, const int32_t *cu_seqlens, int n_sentences, int H, int max_len, int *status,
                            float *out, int pool_mode, hipStream_t stream);
 
+// Grouped pooling (bert_hip.h "long texts"; misc_kernels.hip): rows f32 [n_sentences][H], the sentences' POOL_RAW rows of a pass;
+// group g = sentences group_cu[g] .. group_cu[g + 1] - 1 (device memory, n_groups + 1 entries); out f32 [n_groups][H], not the rows'
+// memory: the weighted mean of the group's rows — weights the sentences' token counts from cu_seqlens, or 1 each when cu_seqlens is
+// null —, divided by its L2 norm unless raw.  A group of one sentence: the bits launch_pool_normalize gives that sentence without
+// POOL_RAW.  A group that is empty, not ascending or outside [0, n_sentences] gets a NaN row and sets *status to 1.  Any H >= 1.
+void launch_group_pool(const float *rows, const int32_t *cu_seqlens, const int32_t *group_cu, int n_sentences, int n_groups, int H,
+                       bool raw, int *status, float *out, hipStream_t stream);
+
 // The > 64 KiB dynamic-LDS opt-in (hipFuncSetAttribute) is per device: `seen` is the launcher's per-kernel record.  The
 // devices of a context launch from threads of their own, and two contexts may share a device: the record is atomic, and
 // the first launcher on a device finishes the opt-in (`mark_configured`) before anybody else launches past it.

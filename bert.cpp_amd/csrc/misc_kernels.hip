@@ -373,6 +373,67 @@ void launch_pool_normalize(const half_t *x, const int32_t *cu_seqlens, int n_sen
                        cu_seqlens, H, max_len, status, out, pool_mode);
 }
 
+// Grouped pooling (bert_hip.h "long texts"): the un-normalised rows of the sentences group_cu[g] .. group_cu[g + 1] - 1 become ONE row,
+// a = (sum_s w_s r_s) / sum_s w_s with w_s = the sentence's token count (cu_seqlens given: the mean over every token state of the
+// group) or 1 (cu_seqlens null), divided by its L2 norm unless RAW.  A workgroup per group; thread tid owns elements tid, tid + 256,
+// ... of the row and walks the sentences in ascending order with one fmaf chain per element, sum w in integers: no atomics, nothing
+// depends on the grid, so a group's bits depend on its own rows and weights alone.  A group of ONE sentence takes its row as it
+// stands, and the norm below restates pool_normalize_sentence's reduction (per-thread squares in ascending element order,
+// wave_sum_f32, the four partials as (0 + 1) + (2 + 3), 1 / sqrtf): such a group's row is, bit for bit, what the pass gives the
+// sentence under the context's own settings.  The un-scaled row waits in `out` itself (a thread reads back only what it wrote), so
+// any H >= 1 fits.  A group that is empty, runs backwards or leaves [0, n_sentences] gets a NaN row and sets *status; a NaN row of a
+// sentence (one that broke the pass's max_len promise) makes its group's row NaN through the chain.
+template <bool RAW>
+__global__ __launch_bounds__(256) void group_pool_kernel(const float *__restrict__ rows, const int32_t *__restrict__ cu_seqlens,
+                                                         const int32_t *__restrict__ group_cu, int n_sentences, int H, int *status,
+                                                         float *out) {
+    __shared__ float red[4];
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int s0 = group_cu[g], s1 = group_cu[g + 1];
+    float *o = out + (size_t)g * H;
+    if (s0 < 0 || s1 <= s0 || s1 > n_sentences) {
+        for (int e = tid; e < H; e += 256) o[e] = __builtin_nanf("");
+        if (tid == 0 && status) atomicOr(status, 1);
+        return;
+    }
+    const bool one = s1 - s0 == 1;                            // (uniform)
+    float inv = 0.f;
+    if (!one) {
+        int wsum = s1 - s0;
+        if (cu_seqlens) wsum = cu_seqlens[s1] - cu_seqlens[s0];
+        inv = 1.0f / (float)wsum;
+    }
+    float sq = 0.f;
+    for (int e = tid; e < H; e += 256) {
+        float a;
+        if (one) a = rows[(size_t)s0 * H + e];
+        else {
+            float acc = 0.f;
+            for (int s = s0; s < s1; ++s) {
+                const int w = cu_seqlens ? cu_seqlens[s + 1] - cu_seqlens[s] : 1;
+                acc = fmaf((float)w, rows[(size_t)s * H + e], acc);
+            }
+            a = acc * inv;
+        }
+        o[e] = a;
+        if constexpr (!RAW) sq += a * a;
+    }
+    if constexpr (!RAW) {
+        sq = wave_sum_f32(sq);
+        if ((tid & 63) == 0) red[tid >> 6] = sq;
+        __syncthreads();
+        const float scale = 1.0f / sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+        for (int e = tid; e < H; e += 256) o[e] = o[e] * scale;
+    }
+}
+
+void launch_group_pool(const float *rows, const int32_t *cu_seqlens, const int32_t *group_cu, int n_sentences, int n_groups, int H,
+                       bool raw, int *status, float *out, hipStream_t stream) {
+    if (n_groups <= 0) return;
+    if (raw) BERT_LAUNCH(group_pool_kernel<true>, dim3(n_groups), dim3(256), 0, stream, rows, cu_seqlens, group_cu, n_sentences, H, status, out);
+    else BERT_LAUNCH(group_pool_kernel<false>, dim3(n_groups), dim3(256), 0, stream, rows, cu_seqlens, group_cu, n_sentences, H, status, out);
+}
+
 // A call's staged block (ids | cu_seqlens | windows) from MAPPED pinned host memory into device memory by a kernel: the copy
 // engine needs about 20 us before the first kernel behind it can start, a few workgroups reading 16 bytes per lane across the host
 // link need 5-8 for the 130 KB of a 256 x 128 batch (engine.hip eval_packed_host; small blocks only).

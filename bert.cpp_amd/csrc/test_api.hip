@@ -444,6 +444,29 @@ int32_t bert_hip_test_pool(int32_t H, const uint16_t *x, const int32_t *cu_seqle
                      status);
 }
 
+int32_t bert_hip_test_group_pool(const float *rows, int32_t n_rows, const int32_t *weights, const int32_t *group_cu, int32_t n_groups, int32_t H,
+                                 int32_t raw, float *out, int32_t *status) {
+    const char *me = "bert_hip_test_group_pool";
+    if (!rows || !group_cu || !out || n_rows < 1 || n_groups < 1 || H < 1) return -1;
+    std::string err;
+    // the weights as the engine has them: prefix sums of the sentences' token counts
+    std::vector<int32_t> cu((size_t)n_rows + 1, 0);
+    if (weights)
+        for (int32_t s = 0; s < n_rows; ++s) cu[s + 1] = cu[s] + weights[s];
+    DevBuf drows, dcu, dg, dout, dst;
+    if (!drows.upload(rows, (size_t)n_rows * H * 4, err) || !dcu.upload(cu, err) || !dg.upload(group_cu, (size_t)(n_groups + 1) * 4, err) ||
+        !dout.upload(out, (size_t)n_groups * H * 4, err) || !dst.alloc(16, err)) {           // (out: what the caller put there stays where the kernel does not write)
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return -1;
+    }
+    launch_group_pool(drows.as<float>(), weights ? dcu.as<int32_t>() : nullptr, dg.as<int32_t>(), n_rows, n_groups, H, raw != 0, dst.as<int>(), dout.as<float>(), nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, (size_t)n_groups * H * 4, hipMemcpyDeviceToHost));
+    if (status) CK(hipMemcpy(status, dst.p, 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---- the f32 route's kernels (f32_route.hip), launched as Engine::forward_f32 launches them ----
 // The engine's workspaces hold whole 256-token tiles: token-row buffers get T_pad rows, the rows behind T holding the 32-bit pattern.
 static int f32_rows_pad(int T) { return (std::max(T, 1) + 255) / 256 * 256; }

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <exception>
 #include <stdexcept>
 #include <string>
@@ -111,6 +112,89 @@ int32_t TextBatcher::encode_groups(int32_t n_threads, int32_t n_inputs, const ch
         i0 += n;
     }
     return total;
+}
+
+void TextBatcher::tokenize_long(const char *text, std::vector<int32_t> &ids) const {
+    const size_t b = strlen(text);
+    if (b > (size_t)INT32_MAX - 2) throw std::length_error("text too long to tokenize");
+    ids.resize(b + 2);
+    int32_t n = 0;
+    tok->tokenize(text, ids.data(), &n, (int32_t)(b + 2));
+    ids.resize((size_t)n);
+}
+
+int32_t LongGroup::append(const std::vector<int32_t> &ids, int32_t window, int32_t stride) {
+    const int32_t n = (int32_t)ids.size(), count = plan_windows(n, window, stride, nullptr, 0);
+    if (count == 1) {
+        packed.insert(packed.end(), ids.begin(), ids.end());
+        cu.push_back((int32_t)packed.size());
+    } else {
+        std::vector<int32_t> starts((size_t)count);
+        plan_windows(n, window, stride, starts.data(), count);
+        for (int32_t i = 0; i < count; ++i) {
+            packed.push_back(ids.front());
+            packed.insert(packed.end(), ids.begin() + 1 + starts[i], ids.begin() + 1 + starts[i] + (window - 2));
+            packed.push_back(ids.back());
+            cu.push_back((int32_t)packed.size());
+        }
+    }
+    group_cu.push_back((int32_t)cu.size() - 1);
+    return count;
+}
+
+int32_t TextBatcher::encode_long_groups(int32_t n_threads, int32_t n_inputs, const char **texts, int32_t window, int32_t stride,
+                                        int32_t *n_windows, const EvalLongGroup &eval) {
+    constexpr int32_t SLAB = 256;                             // texts tokenized at a time (about a quarter of a group at 1000 tokens a text and window 128)
+    std::deque<std::vector<int32_t>> pending;                 // texts next_build .. next_tok - 1, tokenized and not yet in a group
+    std::vector<std::vector<int32_t>> slab;
+    int32_t next_tok = 0, next_build = 0;
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    auto tokenize_slab = [&]() {
+        const int32_t c = std::min(SLAB, n_inputs - next_tok);
+        const char **t = texts + next_tok;
+        slab.resize((size_t)c);
+        const int nt = std::min<int>({n_threads > 0 ? n_threads : 1, (int)hw, (int)c});
+        if (nt <= 1) {
+            for (int32_t i = 0; i < c; ++i) tokenize_long(t[i], slab[i]);
+        } else {
+            std::atomic<int32_t> next{0};
+            auto work = [&](int) {
+                for (int32_t i; (i = next.fetch_add(1)) < c;) tokenize_long(t[i], slab[i]);
+                return 0;
+            };
+            if (!workers || workers_asked < nt - 1) { workers.reset(new ShardWorkers(nt - 1)); workers_asked = nt - 1; }
+            std::string err;
+            if (workers->run_each(nt, work, &err) != 0) throw std::runtime_error("tokenizer worker: " + err);
+        }
+        for (auto &ids : slab) pending.push_back(std::move(ids));
+        next_tok += c;
+    };
+    LongGroup &g = long_group;
+    while (next_build < n_inputs) {
+        const int32_t i0 = next_build;
+        g.clear();
+        for (;;) {
+            if (pending.empty()) {
+                if (next_tok == n_inputs) break;
+                tokenize_slab();
+            }
+            const std::vector<int32_t> &ids = pending.front();
+            const int32_t count = plan_windows((int32_t)ids.size(), window, stride, nullptr, 0);
+            if (g.n_texts() > 0 && (int64_t)g.n_windows() + count > LONG_GROUP_WINDOWS) break;
+            // (the ids of a group are counted in int32, like every packed batch)
+            if ((int64_t)g.packed.size() + (int64_t)count * window > INT32_MAX) {
+                if (g.n_texts() > 0) break;
+                throw std::length_error("a text's windows hold more than 2^31 ids");
+            }
+            g.append(ids, window, stride);
+            pending.pop_front();
+            ++next_build;
+        }
+        if (eval(g, i0) != g.n_texts()) return i0;
+        if (n_windows)
+            for (int32_t i = 0; i < g.n_texts(); ++i) n_windows[i0 + i] = g.group_cu[i + 1] - g.group_cu[i];
+    }
+    return n_inputs;
 }
 
 }  // namespace bert_hip

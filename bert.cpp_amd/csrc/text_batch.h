@@ -9,6 +9,7 @@
 
 #include "multi_device.h"
 #include "tokenizer.h"
+#include "window_plan.h"
 
 namespace bert_hip {
 
@@ -35,6 +36,20 @@ struct TokenGroup {
 // last one.  Tokenizing a group of twice the size still fits under its predecessor's evaluation.
 int32_t encode_group_size(int k, int32_t left);
 
+// A group of LONG texts as the engine takes it (bert_hip.h "long texts"): every window of every text an ordinary sentence, one group
+// of consecutive sentences per text.
+struct LongGroup {
+    std::vector<int32_t> packed, cu, group_cu;          // the windows' ids back to back; [n_windows + 1]; [n_texts + 1]
+    int32_t n_texts() const { return (int32_t)group_cu.size() - 1; }
+    int32_t n_windows() const { return (int32_t)cu.size() - 1; }
+    void clear() { packed.clear(); cu.assign(1, 0); group_cu.assign(1, 0); }
+    // the windows of one text (ids: all of them, [CLS] ... [SEP]; window, stride: legal for plan_windows) as sentences of a new group:
+    // window i is ids[0], the window's inner ids from 1 + starts[i], ids[last].  Returns their number.
+    int32_t append(const std::vector<int32_t> &ids, int32_t window, int32_t stride);
+};
+// windows a group of long texts holds at most (a text's windows never straddle two groups; a text with more is a group of its own)
+constexpr int32_t LONG_GROUP_WINDOWS = 16384;
+
 // The text pipeline of a context.  Not re-entrant, like every entry point of a bert_ctx (context.h).
 struct TextBatcher {
     const Tokenizer *tok = nullptr;                     // the context's, set at load
@@ -57,6 +72,19 @@ struct TextBatcher {
     // stderr) or the first failed eval, later outputs untouched.
     using EvalGroup = std::function<int32_t(const TokenGroup &g, int32_t i0)>;
     int32_t encode_groups(int32_t n_threads, int32_t n_inputs, const char **texts, const EvalGroup &eval);
+
+    // All ids of a text, [CLS] ... [SEP], without truncation: the buffer is sized from the text's byte length (a text of b bytes
+    // yields at most b + 2 ids — every id consumes a byte —, so Tokenizer::tokenize with that cap never truncates).
+    void tokenize_long(const char *text, std::vector<int32_t> &ids) const;
+    // Long texts (bert_hip.h): tokenized without truncation on up to n_threads host threads, a slab of texts at a time, cut into
+    // windows (plan_windows; window and stride validated by the caller) and handed to eval in groups of at most LONG_GROUP_WINDOWS
+    // windows.  eval evaluates the group (texts i0 .. i0 + n_texts - 1) and returns n_texts, or -1.  Tokenizing and evaluating take
+    // turns (no group is tokenized under its predecessor's evaluation).  n_windows (nullable): [n_inputs], written per evaluated
+    // group.  Returns the number of inputs encoded: stops at the first failed eval, later outputs untouched.
+    using EvalLongGroup = std::function<int32_t(const LongGroup &g, int32_t i0)>;
+    int32_t encode_long_groups(int32_t n_threads, int32_t n_inputs, const char **texts, int32_t window, int32_t stride, int32_t *n_windows,
+                               const EvalLongGroup &eval);
+    LongGroup long_group;
 };
 
 }  // namespace bert_hip

@@ -4,7 +4,11 @@
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
-//   (--f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; --b1: one sign bit per element; the
+//               [--long [--window W] [--stride S]]
+//   (--long: a line may be longer than the model's position limit: it is cut into overlapping windows of W ids, S inner ids apart,
+//   and embedded as ONE row (bert_hip_index_add_long_texts; W defaults to 128 or the model's limit if that is less, S to three
+//   quarters of W - 2).  Without --long a line is cut at the model's position limit, like a query;
+//   --f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; --b1: one sign bit per element; the
 //   default stores the rows as f16; --rescore N: an int8 index of the same texts is kept beside the index, which only picks N
 //   candidates per query, and the answer is the int8 index's best k of them (bert_hip_index_search_rescored; k <= N <= 256);
 //   --lists N: once the texts are in, the index is partitioned into N lists (bert_hip_index_kmeans, ten iterations from N evenly
@@ -28,7 +32,9 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]]\n", argv0);
+    fprintf(stderr, "  --long: lines of any length, cut into overlapping windows of W ids, S inner ids apart, one row per line (defaults: W 128 or the\n"
+                    "          model's position limit if that is less, S three quarters of W - 2).  Without --long a line is cut at the model's position limit.\n");
 }
 
 std::string chomp(std::string s) {
@@ -39,7 +45,8 @@ std::string chomp(std::string s) {
 
 int main(int argc, char **argv) {
     const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr;
-    int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0;
+    int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0;
+    bool long_texts = false;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
         if ((!strcmp(argv[i], "-m") || !strcmp(argv[i], "--model")) && has_value) model = argv[++i];
@@ -54,10 +61,14 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--rescore") && has_value) n_cand = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--lists") && has_value) n_lists = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--nprobe") && has_value) nprobe = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--long")) long_texts = true;
+        else if (!strcmp(argv[i], "--window") && has_value) window = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--stride") && has_value) stride = atoi(argv[++i]);
         else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
     }
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
+    if (!long_texts && (window || stride)) { fprintf(stderr, "search: --window and --stride go with --long\n"); return 2; }
     const bool two_stage = n_cand != 0;
     if (two_stage && (n_cand < k || n_cand > 256)) { fprintf(stderr, "search: --rescore must be -k .. 256\n"); return 2; }
 
@@ -84,6 +95,15 @@ int main(int argc, char **argv) {
     for (std::string line; std::getline(in, line);) texts.push_back(chomp(line));
     std::vector<const char *> ptrs;
     for (auto &t : texts) ptrs.push_back(t.c_str());
+    if (long_texts) {
+        if (!window) window = bert_n_max_tokens(ctx) < 128 ? bert_n_max_tokens(ctx) : 128;
+        if (!stride) stride = 3 * (window - 2) / 4 > 1 ? 3 * (window - 2) / 4 : 1;
+    }
+    // the file's lines into an index: cut at the model's position limit, or (--long) whole, as overlapping windows pooled per line
+    auto add_lines = [&](bert_hip_index *to) {
+        return long_texts ? bert_hip_index_add_long_texts(to, n_threads, (int32_t)ptrs.size(), ptrs.data(), window, stride)
+                          : bert_hip_index_add_texts(to, n_threads, (int32_t)ptrs.size(), ptrs.data());
+    };
 
     bert_hip_index *ix;
     if (load) {
@@ -107,7 +127,7 @@ int main(int argc, char **argv) {
         }
     } else {
         ix = bert_hip_index_create(ctx, 0, dtype);
-        if (!ix || bert_hip_index_add_texts(ix, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+        if (!ix || add_lines(ix) < 0) {
             fprintf(stderr, "search: could not build the index\n");
             bert_free(ctx);
             return 1;
@@ -117,7 +137,7 @@ int main(int argc, char **argv) {
     bert_hip_index *fine = nullptr;
     if (two_stage) {
         fine = bert_hip_index_create(ctx, 0, 2);
-        if (!fine || bert_hip_index_add_texts(fine, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+        if (!fine || add_lines(fine) < 0) {
             fprintf(stderr, "search: could not build the int8 index to rescore with\n");
             bert_free(ctx);
             return 1;

@@ -35,6 +35,8 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_index_partition_lists", "bert_hip_index_kmeans", "bert_hip_index_search_probed", "bert_hip_index_search_probed_device",
     "bert_hip_index_search_probed_filtered", "bert_hip_index_search_probed_filtered_device", "bert_hip_index_search_rescored_probed",
     "bert_hip_index_search_rescored_probed_device", "bert_hip_index_partition_save", "bert_hip_index_partition_load",
+    "bert_hip_eval_packed_grouped", "bert_hip_eval_packed_grouped_device", "bert_hip_tokenize_long", "bert_hip_plan_windows",
+    "bert_hip_encode_long_batch", "bert_hip_index_add_long_texts",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -46,7 +48,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_f32_gemm", "bert_hip_test_f32_attention", "bert_hip_test_f32_layernorm", "bert_hip_test_f32_embed_ln", "bert_hip_test_f32_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
-    "bert_hip_test_build_lists", "bert_hip_test_partition_header",
+    "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -139,6 +141,14 @@ def _declare_product_abi(L):
     L.bert_hip_index_search_rescored_probed_device.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]
     L.bert_hip_index_partition_save.restype = i32; L.bert_hip_index_partition_save.argtypes = [vp, C.c_char_p]
     L.bert_hip_index_partition_load.restype = i32; L.bert_hip_index_partition_load.argtypes = [vp, C.c_char_p]
+    L.bert_hip_eval_packed_grouped.restype = i32; L.bert_hip_eval_packed_grouped.argtypes = [vp, i32p, i32p, i32, i32p, i32, f32p]
+    L.bert_hip_eval_packed_grouped_device.restype = i32
+    L.bert_hip_eval_packed_grouped_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]
+    L.bert_hip_tokenize_long.restype = i32; L.bert_hip_tokenize_long.argtypes = [vp, C.c_char_p, i32p, i32]
+    L.bert_hip_plan_windows.restype = i32; L.bert_hip_plan_windows.argtypes = [i32, i32, i32, i32p, i32]
+    L.bert_hip_encode_long_batch.restype = i32
+    L.bert_hip_encode_long_batch.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32, C.POINTER(f32p), i32p]
+    L.bert_hip_index_add_long_texts.restype = i32; L.bert_hip_index_add_long_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32]
 
 
 def lib() -> C.CDLL:
@@ -233,6 +243,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_partition_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
     L.bert_hip_test_build_lists.restype = i32
     L.bert_hip_test_build_lists.argtypes = [i32p, i32, i32, i32p, i32p]
+    L.bert_hip_test_group_pool.restype = i32
+    L.bert_hip_test_group_pool.argtypes = [vp, i32, i32p, i32p, i32, i32, i32, vp, i32p]
     _test_lib = L
     return L
 
@@ -285,6 +297,34 @@ def test_pool(x: np.ndarray, cu_seqlens, max_len: int, pooling: str = "mean", no
     if r != 0:
         raise RuntimeError(f"bert_hip_test_pool failed: {r}")
     return out, int(st[0])
+
+
+def test_group_pool(rows: np.ndarray, weights, group_cu, raw: bool, out: Optional[np.ndarray] = None):
+    """launch_group_pool on chosen rows [n_rows, H] f32 and weights [n_rows] (None: 1 each); group g = rows group_cu[g] .. group_cu[g + 1]
+    - 1 (the rows around the groups are the caller's to poison).  out: the buffer as the kernel finds it, [n_groups, H] f32 (None:
+    NaNs).  Returns (rows [n_groups, H] f32, status word)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32); g = np.ascontiguousarray(group_cu, dtype=np.int32)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.int32)
+    assert rows.ndim == 2 and (w is None or w.shape == (rows.shape[0],))
+    if out is None:
+        out = np.full((len(g) - 1, rows.shape[1]), np.nan, dtype=np.float32)
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(g) - 1, rows.shape[1])
+    st = np.zeros(1, dtype=np.int32)
+    r = test_lib().bert_hip_test_group_pool(rows.ctypes.data, rows.shape[0], None if w is None else _i32p(w), _i32p(g), len(g) - 1, rows.shape[1],
+                                            int(bool(raw)), out.ctypes.data, _i32p(st))
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_group_pool failed: {r}")
+    return out, int(st[0])
+
+
+def plan_windows(n_tokens: int, window: int, stride: int) -> List[int]:
+    """bert_hip_plan_windows: the windows' start offsets among the INNER ids of a text of n_tokens ids (no context, no GPU)."""
+    n = lib().bert_hip_plan_windows(n_tokens, window, stride, None, 0)
+    if n < 0:
+        raise ValueError(f"bert_hip_plan_windows({n_tokens}, {window}, {stride}) = {n}")
+    starts = np.zeros(n, dtype=np.int32)
+    assert lib().bert_hip_plan_windows(n_tokens, window, stride, _i32p(starts), n) == n
+    return starts.tolist()
 
 
 def model_digest(path: str):
@@ -510,6 +550,70 @@ class BertModel:
     def n_devices(self) -> int:
         return self.lib.bert_hip_n_devices(self.ctx)
 
+    # ---- long texts -----------------------------------------------------------------------
+    def tokenize_long(self, text: str | bytes) -> List[int]:
+        """All ids of a text, [CLS] ... [SEP], without truncation (tokenizer-only contexts too)."""
+        data = text if isinstance(text, bytes) else text.encode("utf-8")
+        n = self.lib.bert_hip_tokenize_long(self.ctx, data, None, 0)
+        if n < 0:
+            raise RuntimeError(f"bert_hip_tokenize_long failed: {n}")
+        ids = np.zeros(n, dtype=np.int32)
+        assert self.lib.bert_hip_tokenize_long(self.ctx, data, _i32p(ids), n) == n
+        return ids.tolist()
+
+    def plan_windows(self, n_tokens: int, window: Optional[int] = None, stride: Optional[int] = None) -> List[int]:
+        window, stride = self.long_defaults(window, stride)
+        return plan_windows(n_tokens, window, stride)
+
+    def long_defaults(self, window: Optional[int] = None, stride: Optional[int] = None):
+        """window: 128 ids (one full window of the one-launch kernel) where the model has the positions, else n_max_tokens; stride: three
+        quarters of the window's inner length."""
+        if window is None:
+            window = min(self.n_max_tokens, 128)
+        if stride is None:
+            stride = max(1, 3 * (window - 2) // 4)
+        return int(window), int(stride)
+
+    def eval_packed_grouped(self, tokens: np.ndarray, cu_seqlens: np.ndarray, group_cu: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """One embedding per group of consecutive sentences (bert_hip_eval_packed_grouped); out: the caller's [n_groups, n_embd] rows, NaNs
+        if None.  Raises ValueError for a group_cu the entry refuses (-2: out untouched)."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+        g = np.ascontiguousarray(group_cu, dtype=np.int32)
+        if out is None:
+            out = np.full((len(g) - 1, self.n_embd), np.nan, dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (len(g) - 1, self.n_embd)
+        r = self.lib.bert_hip_eval_packed_grouped(self.ctx, _i32p(tokens), _i32p(cu), len(cu) - 1, _i32p(g), len(g) - 1, _f32p(out))
+        if r == -2:
+            raise ValueError("bert_hip_eval_packed_grouped refused its arguments (see stderr)")
+        if r != 0:
+            raise RuntimeError(f"bert_hip_eval_packed_grouped failed: {r}")
+        return out
+
+    def eval_packed_grouped_device(self, d_tokens_ptr: int, d_cu_ptr: int, n_sentences: int, n_tokens: int, max_len: int, d_group_cu_ptr: int,
+                                   n_groups: int, d_out_ptr: int, stream: int = 0) -> None:
+        r = self.lib.bert_hip_eval_packed_grouped_device(self.ctx, d_tokens_ptr, d_cu_ptr, n_sentences, n_tokens, max_len, d_group_cu_ptr,
+                                                         n_groups, d_out_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_eval_packed_grouped_device failed: {r}")
+
+    def encode_long_batch(self, texts: Sequence[str], window: Optional[int] = None, stride: Optional[int] = None, n_threads: int = 6,
+                          return_windows: bool = False):
+        """One embedding per text of any length (bert_hip_encode_long_batch); return_windows: also the number of windows per text.
+        Raises ValueError for a window or stride the entry refuses."""
+        window, stride = self.long_defaults(window, stride)
+        n = len(texts)
+        out = np.full((n, self.n_embd), np.nan, dtype=np.float32)
+        out_ptrs = (C.POINTER(C.c_float) * n)(*[_f32p(out[i]) for i in range(n)])
+        txt = (C.c_char_p * n)(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        nw = np.full(n, -1, dtype=np.int32)
+        r = self.lib.bert_hip_encode_long_batch(self.ctx, n_threads, n, txt, window, stride, out_ptrs, _i32p(nw))
+        if r == -2:
+            raise ValueError(f"bert_hip_encode_long_batch refused window {window}, stride {stride}")
+        if r != n:
+            raise RuntimeError(f"bert_hip_encode_long_batch encoded {r} of {n} texts")
+        return (out, nw) if return_windows else out
+
     def eval_packed_gather(self, tokens: np.ndarray, cu_seqlens: np.ndarray) -> List[int]:
         """Evaluates on all devices of the context and gathers on every device: returns the device pointers of the
         [n_sentences][n_embd] f32 matrices, one per device (owned by the context)."""
@@ -664,6 +768,19 @@ class BertIndex:
         r = self.lib.bert_hip_index_add_texts(self.ix, n_threads, n, txt)
         if r < 0:
             raise RuntimeError(f"bert_hip_index_add_texts failed: {r}")
+        return r
+
+    def add_long_texts(self, texts: Sequence[str], window: Optional[int] = None, stride: Optional[int] = None, n_threads: int = 6) -> int:
+        """add_texts for texts of any length: one row per text (bert_hip_index_add_long_texts); returns the first new id.  Raises
+        ValueError for a window or stride the entry refuses (the index keeps its size)."""
+        window, stride = self.model.long_defaults(window, stride)
+        n = len(texts)
+        txt = (C.c_char_p * n)(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        r = self.lib.bert_hip_index_add_long_texts(self.ix, n_threads, n, txt, window, stride)
+        if r == -2:
+            raise ValueError(f"bert_hip_index_add_long_texts refused window {window}, stride {stride}")
+        if r < 0:
+            raise RuntimeError(f"bert_hip_index_add_long_texts failed: {r}")
         return r
 
     def search(self, queries, k: int = 10, allow=None):

@@ -155,6 +155,71 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  * (BERT_HIP_POOLING / BERT_HIP_NORMALIZE above; bert_hip_pooling / bert_hip_normalize return what is in force).                       */
 BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const char *value);
 
+/* LONG TEXTS.  bert_tokenize truncates at n_max_tokens (leaving room for one [SEP]), and so does every text entry point above: what
+ * lies behind the cut never reaches the model.  The entry points below embed a text of any length: it is cut into overlapping
+ * windows, every window is evaluated as an ordinary sentence, and the windows' embeddings are combined into ONE row per text on the
+ * device.  Nothing above changes its behaviour or its bits.
+ *
+ * Grouped pooling, the primitive: a packed batch plus a partition of its sentences into consecutive groups gives one embedding per
+ * group.  Sentences group_cu[g] .. group_cu[g + 1] - 1 form group g; group_cu[0] = 0, group_cu[n_groups] = n_sentences, no empty group.
+ *   Definition.  Let the context's settings be "pooling" and "normalize", and r_s sentence s's row as the pass gives it under the
+ *   same "pooling" with "normalize" = 0 (the mean over the sentence's tokens, or its first token's state).  The weight of sentence s
+ *   is w_s = cu[s + 1] - cu[s], its token count, under mean pooling and w_s = 1 under cls pooling.  The group's row is
+ *   a = (sum_s w_s r_s) / sum_s w_s — for mean pooling the mean over every token state of every sentence of the group — and with
+ *   "normalize" = 1 it is divided by its L2 norm (no epsilon).
+ *   Arithmetic.  The ordinary forward pass runs with the raw mode handed in as an argument: the context's options are not touched, a
+ *   later ordinary call and bert_hip_normalize see what they saw before.  The raw rows are f32; one workgroup per group walks its
+ *   sentences in ascending order with one fused multiply-add chain per element, sum w in integers, one multiplication by
+ *   1 / sum w, then the norm in the reduction order of the ordinary pooling.  No atomics: a group's bits depend on its own sentences
+ *   alone — not on the other groups, the number of devices or BERT_HIP_CHUNK_TOKENS.  A group of ONE sentence takes its row
+ *   unchanged, so it is, bit for bit, the embedding bert_hip_eval_packed gives that sentence, in all four modes, on the f16 and
+ *   the f32 route.
+ *   Memory.  The raw rows live in a grow-only [n_sentences][n_embd] f32 buffer of the engine: the first call at a new largest shape
+ *   allocates (synchronises the device, illegal under stream capture) — call once at the largest shape before a capture, as for
+ *   bert_hip_reserve, which does not size this buffer.  On a one-device context the raw rows never leave the device; on a
+ *   multi-device context they come through the sharded host path and are pooled on the first device.
+ *   eval_packed_grouped         host buffers, blocking.  group_cu is checked before anything is launched: -2, a line on stderr and
+ *                               outputs untouched unless it starts at 0, ends at n_sentences and increases strictly.  Otherwise
+ *                               the results and errors of bert_hip_eval_packed.  embeddings: [n_groups][n_embd].
+ *   eval_packed_grouped_device  everything in HBM on the first device, enqueued on `stream`, the rules of
+ *                               bert_hip_eval_packed_device.  group_cu is validated on the device: a group that is empty, not
+ *                               ascending or outside [0, n_sentences] gets a NaN row and sets the status word bert_hip_check
+ *                               returns, as a broken max_len does; a sentence that broke max_len (a NaN row) makes its group's row
+ *                               NaN.  d_embeddings must not overlap the other buffers.
+ *   The launch is listed as "group_pool" by bert_hip_profile_report.                                                             */
+BERT_API int32_t bert_hip_eval_packed_grouped(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens,
+                                              int32_t n_sentences, const int32_t *group_cu, int32_t n_groups, float *embeddings);
+BERT_API int32_t bert_hip_eval_packed_grouped_device(struct bert_ctx *ctx, const bert_vocab_id *d_tokens, const int32_t *d_cu_seqlens,
+                                                     int32_t n_sentences, int32_t n_tokens_total, int32_t max_len,
+                                                     const int32_t *d_group_cu, int32_t n_groups, float *d_embeddings, void *stream);
+
+/* All ids of a text, [CLS] ... [SEP], WITHOUT truncation (host only; tokenizer-only contexts too): returns their number n and writes
+ * them to tokens iff cap >= n (tokens may be NULL with cap 0: a count).  A text of b bytes yields at most b + 2 ids.  For a text that
+ * fits n_max_tokens the ids are bert_tokenize's.  Negative on an error.                                                             */
+BERT_API int32_t bert_hip_tokenize_long(struct bert_ctx *ctx, const char *text, bert_vocab_id *tokens, int32_t cap);
+
+/* The windows of a text of n_tokens ids (pure; no context).  `window` counts ALL ids of a window, its [CLS] and [SEP] included;
+ * `stride` counts inner ids.  Limits: n_tokens >= 2, window >= 3 (the text entry points: <= n_max_tokens), 1 <= stride <= window - 2;
+ * -2 otherwise.  Let m = n_tokens - 2 inner ids and c = window - 2.  n_tokens <= window: one window, the text itself.  Otherwise
+ * windows start at inner offsets 0, stride, 2 stride, ... for as long as start + c < m, and one last window starts at m - c: every
+ * window of a long text has exactly `window` ids, the first starts at the text's start, the last ends at its end, every inner id is
+ * in at least one, and there are 1 + ceil((m - c) / stride) of them.  Window i is the text's first id ([CLS]), the c inner ids from
+ * starts[i] (ids[1 + starts[i]] onwards), then the text's last id ([SEP]).  Returns the number of windows; writes starts[0 .. count)
+ * iff cap >= count (starts may be NULL with cap 0: a count).                                                                      */
+BERT_API int32_t bert_hip_plan_windows(int32_t n_tokens, int32_t window, int32_t stride, int32_t *starts, int32_t cap);
+
+/* bert_hip_encode_batch for texts of any length: per text tokenize_long, plan_windows, every window an ordinary sentence, one group
+ * per text, grouped pooling (above: under mean pooling a text's row is the token-weighted mean over its windows' tokens — tokens
+ * in an overlap count once per window that holds them —, normalised or not as the context says).  A text that fits its window is one
+ * group of one sentence: its embedding is, bit for bit, bert_encode_batch's.  Texts are tokenized on up to n_threads host threads, the
+ * id buffer of a text sized from its byte length; they go to the engine in groups of at most 16384 windows, a text's windows never
+ * in two groups (a text with more windows is a group of its own).  n_windows (nullable): [n_inputs], the number of windows of every
+ * encoded text.  Returns the number of inputs encoded (all of them, or those in front of the first failed group — later embeddings
+ * stay untouched), -1 for a context without a device, -2 with the outputs untouched for a window or stride outside the limits of
+ * bert_hip_plan_windows and 3 <= window <= n_max_tokens.  A row's bits do not depend on the other texts of the call.               */
+BERT_API int32_t bert_hip_encode_long_batch(struct bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, int32_t window,
+                                            int32_t stride, float **embeddings, int32_t *n_windows);
+
 /* Embedding index: rows in HBM on the context's FIRST device (bert_hip_device), exact top-k search by inner product.
  * An index belongs to the context it was made from: bert_free frees any index the caller left alive.  Like every
  * entry point of a context, the index functions are not re-entrant on one context.
@@ -324,6 +389,11 @@ BERT_API int32_t bert_hip_index_reserve(struct bert_hip_index *ix, int32_t n_row
 BERT_API int32_t bert_hip_index_add(struct bert_hip_index *ix, int32_t n, const float *rows);
 BERT_API int32_t bert_hip_index_add_device(struct bert_hip_index *ix, int32_t n, const float *d_rows, void *stream);
 BERT_API int32_t bert_hip_index_add_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n, const char **texts);
+/* add_texts for texts of any length (LONG TEXTS above: bert_hip_encode_long_batch's rows, one per text): returns the first new id, -2
+ * for a bad window or stride, negative on any error with the index at its old size.  Single device: the pooled rows go from the
+ * device buffer straight into the index; several: through the host.                                                            */
+BERT_API int32_t bert_hip_index_add_long_texts(struct bert_hip_index *ix, int32_t n_threads, int32_t n, const char **texts, int32_t window,
+                                               int32_t stride);
 BERT_API int32_t bert_hip_index_search(struct bert_hip_index *ix, int32_t n_queries, const float *queries, int32_t k,
                                        int32_t *ids, float *scores);
 BERT_API int32_t bert_hip_index_search_device(struct bert_hip_index *ix, int32_t n_queries, const float *d_queries, int32_t k,

@@ -114,6 +114,15 @@ BERT_API int32_t bert_hip_test_pool_normalize(int32_t H, const uint16_t *x, cons
 BERT_API int32_t bert_hip_test_pool(int32_t H, const uint16_t *x, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
                                     int32_t pooling, int32_t normalize, float *out, int32_t *status);
 
+/* Grouped pooling (bert_hip.h "long texts"; launch_group_pool) on chosen rows and weights: rows f32 [n_rows][H]; weights [n_rows] > 0
+ * (the sentences' token counts), or NULL: 1 each; group g = rows group_cu[g] .. group_cu[g + 1] - 1 (n_groups + 1 entries; group_cu[0]
+ * may lie behind row 0 and the last entry in front of n_rows: the rows around the groups are the caller's to poison); raw 1: the
+ * weighted means, 0: divided by their L2 norms.  out [n_groups][H]: uploaded as the caller filled it, so a word the kernel does not
+ * write comes back as it was.  *status (nullable) receives the device status word: 1 if a group is empty, not ascending or outside
+ * [0, n_rows] (its row is NaN).  -1: bad arguments or a HIP error.                                                                  */
+BERT_API int32_t bert_hip_test_group_pool(const float *rows, int32_t n_rows, const int32_t *weights, const int32_t *group_cu,
+                                          int32_t n_groups, int32_t H, int32_t raw, float *out, int32_t *status);
+
 /* The f32 route's kernels (f32_route.hip: what an f32 model file runs on), each launched exactly as Engine::forward_f32 launches it;
  * everything f32.  Token-row buffers have the engine's workspace shape, whole tiles of 256 rows: under bert_hip_test_set_pad the rows
  * behind the last token of every input hold pattern32, every output buffer holds it in ALL its words before the launch, and an entry
