@@ -38,7 +38,16 @@ public:
     int eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int n_sentences, int n_tokens, int max_len,
                            float *d_out, hipStream_t stream, float *d_hidden, std::string &err,
                            const int2 *d_windows = nullptr, int n_windows = 0, int window_slots = 0,       // window_slots: the place granularity d_windows was built with (0: read it now)
-                           int pool_mode = -1);                  // kernels.h POOL_*: what the host call read for all its chunks (-1: read the options now)
+                           int pool_mode = -1,                   // kernels.h POOL_*: what the host call read for all its chunks (-1: read the options now)
+                           void *d_token_rows = nullptr, int token_flags = 0);     // token rows (below); d_out may then be null: the embeddings stay in d_out_
+    // Token rows (bert_hip.h "token rows and late interaction"): a pass with one more destination, [n_tokens][H] rows of the final states
+    // (kernels.h launch_token_rows, TOKEN_ROWS_* flags), written by one launch ("token_rows" in the profile) beside the pooling launch.
+    // Such a pass does not take the one-launch kernel (which keeps x on chip between its phases and pools inside the launch: the other
+    // routes leave the final states in x_ in row order); LayerNorm folding stays as planned, so the embeddings are eval_packed's bits.
+    // Host form, blocking, on this engine's device: cut at chunk_tokens between sentences, one plain copy per chunk and direction.
+    // flags: TOKEN_ROWS_NORMALIZE only (rows are f32).  embeddings: nullable.
+    int eval_packed_tokens_host(const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int flags, float *rows, float *embeddings,
+                                std::string &err);
     // next-fit packing of whole sentences (in order, each starting at a multiple of 16 slots) into windows of 128 token
     // slots: {first sentence, count} per window.  Sentences longer than a window get one of their own (the fused kernel is
     // not used for such batches).
@@ -92,6 +101,7 @@ private:
         const int32_t *tokens, *cu;
         int B, T, max_len, t_pad, slots, pool_mode;
         float *out, *hidden;
+        void *token_rows;             // token rows wanted (eval_packed_device): no one-launch kernel
         hipStream_t s;
         const int2 *windows;
         int n_windows;
@@ -102,7 +112,7 @@ private:
         std::vector<LayerPlan> layers;
     };
     Plan plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s, float *d_hidden,
-              const int2 *d_windows, int n_windows, int slots, int pool_mode) const;
+              const int2 *d_windows, int n_windows, int slots, int pool_mode, void *d_token_rows = nullptr) const;
     bool forward_f32(const Plan &p, std::string &err);        // f32 files in f32 arithmetic (f32_route.hip), one launch per operation
     void forward_latency(const Plan &p);
     void forward_one_launch(const Plan &p);
@@ -125,6 +135,7 @@ private:
 
     // workspace (grow-only)
     DevBuf x_, qkv_, ctx_, y_, ff_, v32_, d_tokens_, d_cu_, d_out_, d_hidden_, status_, windows_;
+    DevBuf tok_in_, tok_rows_;                                // the host form of the token rows: a chunk's ids | cu_seqlens, and its rows
     DevBuf raw_rows_, group_in_, group_out_;                  // grouped pooling: the sentences' POOL_RAW rows [n_sentences][H] f32; the host form's cu_seqlens | group_cu and its groups' rows
     DevBuf ln_stats1_, ln_stats2_, ln_rows1_, ln_rows2_;      // LayerNorm folding: per-row partial statistics / finalized rows of the two LayerNorms of a layer
     hipStream_t stream_ = nullptr;

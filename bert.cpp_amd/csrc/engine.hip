@@ -107,7 +107,7 @@ void Engine::build_windows(const int32_t *cu, int B, std::vector<int2> &windows,
 
 int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out,
                                hipStream_t s, float *d_hidden, std::string &err, const int2 *d_windows, int n_windows, int slots_in,
-                               int pool_mode_in) {
+                               int pool_mode_in, void *d_token_rows, int token_flags) {
     if (B <= 0 || T <= 0) return 0;
     // the windows' place granularity, read ONCE per pass (the host path read it when it built its list): the window list, the
     // grid bound and the kernels' place rule must agree whatever another thread or context sets meanwhile
@@ -119,7 +119,8 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     prof_.begin_pass();
     // one forward pass at a time on the shared workspace: wait (on the caller's stream) for the previous pass
     HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
-    const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots, pool_mode);
+    if (!d_out) d_out = d_out_.as<float>();                   // (a token-rows call that wants no embeddings: ensure_workspace sized it)
+    const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots, pool_mode, d_token_rows);
     bool ok = true;
     if (p.route == Route::F32) ok = forward_f32(p, err);
     else {
@@ -140,6 +141,9 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
             timed("pool_normalize", 2.0 * T * H, s, [&] { launch_pool_normalize(x_.as<half_t>(), d_cu, B, H, max_len, status_.as<int>(), d_out, p.pool_mode, s); });
     }
     if (!ok) return -1;
+    // (every route a token-rows pass can take left the final states in x_, [T][H] in row order: f32 on the f32 route, else f16)
+    if (d_token_rows)
+        timed("token_rows", 0.0, s, [&] { launch_token_rows(x_.p, p.route == Route::F32, T, hp_.n_embd, d_cu, B, max_len, token_flags, d_token_rows, s); });
     HIP_OK(hipGetLastError(), err, -1);
     HIP_OK(hipEventRecord(busy_, s), err, -1);
     return 0;
@@ -147,9 +151,9 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
 
 // The route of a pass and, per layer, its kernels: every eligibility test of the forward pass, each made here once.  Launches nothing.
 Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s,
-                          float *d_hidden, const int2 *d_windows, int n_windows, int slots, int pool_mode) const {
+                          float *d_hidden, const int2 *d_windows, int n_windows, int slots, int pool_mode, void *d_token_rows) const {
     // (t_pad: whole tiles of every kernel family, 128- and 256-token tiles)
-    Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, pool_mode, d_out, d_hidden, s, d_windows, n_windows};
+    Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, pool_mode, d_out, d_hidden, d_token_rows, s, d_windows, n_windows};
     if (w_->f32_file && opt_.f32_exact) { p.route = Route::F32; return p; }
     const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh, Lz = hp_.n_layer;
     auto family = [&](const GemmWeightStore &W) {
@@ -177,6 +181,8 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
     }
     // a hidden-state tap wants every layer's normalised states: it takes neither the one-launch kernel nor the folded LayerNorms
     if (d_hidden) one_launch = fold = false;
+    // token rows want the last layer's states in x_ in row order: not the one-launch kernel; the folded LayerNorms stay
+    if (d_token_rows) one_launch = false;
     const bool fused_windows = p.layers[0].qkv2, latency_call = opt_.latency && T <= opt_.latency_tokens;
     one_launch = one_launch && fused_windows && opt_.one_launch && opt_.tail && !latency_call;
     // sentence windows of the fused projection+attention kernel: the caller's (host path), or built on the device from cu_seqlens
@@ -586,6 +592,38 @@ int Engine::eval_packed_grouped_host(const int32_t *tokens, const int32_t *cu, i
     if (!d_embeddings && hipMemcpyAsync(embeddings, d_out, (size_t)n_groups * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess)
         return fail("hipMemcpyAsync (embeddings) failed");
     HIP_OK(hipStreamSynchronize(stream_), err, -1);
+    return 0;
+}
+
+int Engine::eval_packed_tokens_host(const int32_t *tokens, const int32_t *cu, int B, int flags, float *rows, float *embeddings, std::string &err) {
+    if (B <= 0) return 0;
+    HIP_OK(hipSetDevice(device_), err, -1);
+    const size_t H = hp_.n_embd;
+    auto fail = [&](const char *what) { if (what) err = what; (void)hipStreamSynchronize(stream_); return -1; };      // nothing may stay queued on the caller's memory
+    // chunks [b0, b1) by eval_packed_host's rule: at most chunk_tokens tokens, at least one sentence
+    std::vector<int32_t> h_cu;
+    for (int b0 = 0; b0 < B;) {
+        int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
+        while (b1 < B && cu[b1 + 1] - cu[b0] <= opt_.chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
+        const int nb = b1 - b0, T = cu[b1] - cu[b0];
+        const size_t off_cu = ((size_t)T * 4 + 15) & ~(size_t)15;
+        if (!tok_in_.ensure(off_cu + (size_t)(nb + 1) * 4, err) || !tok_rows_.ensure((size_t)T * H * 4, err) || !ensure_workspace((T + 255) / 256 * 256, nb, err)) return fail(nullptr);
+        h_cu.resize(nb + 1);
+        for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
+        char *d_in = tok_in_.as<char>();
+        // (pageable sources: both copies have left the host buffers when they return)
+        if (hipMemcpyAsync(d_in, tokens + cu[b0], (size_t)T * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+            hipMemcpyAsync(d_in + off_cu, h_cu.data(), (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, stream_) != hipSuccess)
+            return fail("hipMemcpyAsync (ids) failed");
+        if (eval_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, nullptr, stream_, nullptr, err, nullptr, 0, 0, -1,
+                               tok_rows_.p, flags & TOKEN_ROWS_NORMALIZE) != 0)
+            return fail(nullptr);
+        if (hipMemcpyAsync(rows + (size_t)cu[b0] * H, tok_rows_.p, (size_t)T * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
+            (embeddings && hipMemcpyAsync(embeddings + (size_t)b0 * H, d_out_.p, (size_t)nb * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess))
+            return fail("hipMemcpyAsync (rows) failed");
+        HIP_OK(hipStreamSynchronize(stream_), err, -1);
+        b0 = b1;
+    }
     return 0;
 }
 

@@ -163,6 +163,30 @@ void launch_pool_normalize(const half_t *x, const int32_t *cu_seqlens, int n_sen
 void launch_group_pool(const float *rows, const int32_t *cu_seqlens, const int32_t *group_cu, int n_sentences, int n_groups, int H,
                        bool raw, int *status, float *out, hipStream_t stream);
 
+// Token rows (bert_hip.h "token rows and late interaction"; misc_kernels.hip): the final states x [T][H] of a pass in row order — f16,
+// or f32 (x_is_f32: the f32 route's) — copied to out [T][H], one wave per row.  flags bit 0 (TOKEN_ROWS_NORMALIZE): every row divided
+// by its own L2 norm (f32 sum of squares, a lane's elements in ascending order, then wave_sum_f32; 1 / sqrtf, no epsilon); bit 1
+// (TOKEN_ROWS_F16): out is f16 (rounded to nearest even), else f32.  Without bit 0 the f32 output is the stored state exactly.  The
+// tokens of a sentence whose length is not in [1, max_len] get NaN rows (the pooling launch sets the status word for it).  Any H >= 1.
+constexpr int TOKEN_ROWS_NORMALIZE = 1, TOKEN_ROWS_F16 = 2;
+void launch_token_rows(const void *x, bool x_is_f32, int T, int H, const int32_t *cu_seqlens, int n_sentences, int max_len, int flags,
+                       void *out, hipStream_t stream);
+
+// MaxSim (maxsim.hip): q [.][H], d [.][H] packed f16 token rows, 16-byte aligned, H % 8 == 0, 8 <= H <= MAXSIM_MAX_H; qcu [n_q + 1],
+// dcu [n_d + 1] cumulative lengths; pairs null: all pairs, scores [n_q][n_d]; else [n_pairs][2] of (a, b), scores [n_pairs].
+// mode bit 0: the mean over the query tokens instead of the sum.  Everything in device memory.
+constexpr int MAXSIM_MAX_H = 1024;
+struct MaxsimArgs {
+    const half_t *q, *d;
+    const int32_t *qcu, *dcu, *pairs;
+    float *scores;
+    int n_q, n_d, H, n_pairs, mode;
+};
+size_t maxsim_lds_bytes(int H);
+void launch_maxsim(const MaxsimArgs &a, hipStream_t stream);
+// n f32 values -> f16, rounded to nearest even (the host form of MaxSim rounds its rows on the device)
+void launch_f32_to_f16(const float *src, half_t *dst, size_t n, hipStream_t stream);
+
 // The > 64 KiB dynamic-LDS opt-in (hipFuncSetAttribute) is per device: `seen` is the launcher's per-kernel record.  The
 // devices of a context launch from threads of their own, and two contexts may share a device: the record is atomic, and
 // the first launcher on a device finishes the opt-in (`mark_configured`) before anybody else launches past it.

@@ -434,6 +434,94 @@ void launch_group_pool(const float *rows, const int32_t *cu_seqlens, const int32
     else BERT_LAUNCH(group_pool_kernel<false>, dim3(n_groups), dim3(256), 0, stream, rows, cu_seqlens, group_cu, n_sentences, H, status, out);
 }
 
+// Token rows (kernels.h launch_token_rows): the final states of a pass, [T][H] in row order, to the caller's buffer.  One wave per token
+// row; a lane owns runs of VW elements (VW = 8 where H % 8 == 0: 16-byte loads of f16 rows; else single elements), run lane + 64 j of the
+// row.  S: the stored type (f16, or f32 on the f32 route), O: the output's.  NORM: the row over its L2 norm — a lane adds the squares of
+// its elements in ascending order in f32, wave_sum_f32 adds the lanes, scale = 1 / sqrtf(sum), no epsilon (the pooling's rule); the row
+// is read a second time (L1 / L2) instead of being kept.  !NORM: the stored value converted, nothing else.  A wave finds its sentence
+// by bisection of cu_seqlens on scalar loads; a token of a sentence whose length is not in [1, max_len], or behind the last
+// sentence, gets a NaN row.
+template <class S, int VW>
+__device__ __forceinline__ void token_run_load(const S *p, float (&v)[VW]) {
+    if constexpr (VW == 1) v[0] = (float)p[0];
+    else if constexpr (std::is_same_v<S, float>) {
+        const float4 a = *(const float4 *)p, b = *(const float4 *)(p + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+        const f16x8 hv = *(const f16x8 *)p;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (float)hv[i];
+    }
+}
+template <class O, int VW>
+__device__ __forceinline__ void token_run_store(O *p, const float (&v)[VW]) {
+    if constexpr (VW == 1) p[0] = (O)v[0];
+    else if constexpr (std::is_same_v<O, float>) {
+        *(float4 *)p = make_float4(v[0], v[1], v[2], v[3]);
+        *(float4 *)(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+        f16x8 hv;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) hv[i] = (_Float16)v[i];
+        *(f16x8 *)p = hv;
+    }
+}
+template <class S, class O, int VW, bool NORM>
+__global__ __launch_bounds__(256) void token_rows_kernel(const S *__restrict__ x, int T, int H, const int32_t *__restrict__ cu_seqlens,
+                                                         int n_sentences, int max_len, O *__restrict__ out) {
+    const int t = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (t >= T) return;
+    int lo = 0, hi = n_sentences;                             // largest b with cu[b] <= t
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (cu_seqlens[mid] <= t) lo = mid; else hi = mid;
+    }
+    const int n = cu_seqlens[lo + 1] - cu_seqlens[lo];
+    const bool bad = n < 1 || n > max_len || t < cu_seqlens[lo] || t >= cu_seqlens[lo + 1];      // (wave-uniform)
+    const S *row = x + (size_t)t * H;
+    O *orow = out + (size_t)t * H;
+    float scale = 1.f;
+    if (NORM && !bad) {
+        float sq = 0.f;
+        for (int e0 = lane * VW; e0 < H; e0 += 64 * VW) {
+            float v[VW];
+            token_run_load<S, VW>(row + e0, v);
+#pragma unroll
+            for (int i = 0; i < VW; ++i) sq += v[i] * v[i];
+        }
+        scale = 1.0f / sqrtf(wave_sum_f32(sq));
+    }
+    for (int e0 = lane * VW; e0 < H; e0 += 64 * VW) {
+        float v[VW];
+        if (bad) {
+#pragma unroll
+            for (int i = 0; i < VW; ++i) v[i] = __builtin_nanf("");
+        } else {
+            token_run_load<S, VW>(row + e0, v);
+            if (NORM) {
+#pragma unroll
+                for (int i = 0; i < VW; ++i) v[i] = v[i] * scale;
+            }
+        }
+        token_run_store<O, VW>(orow + e0, v);
+    }
+}
+
+void launch_token_rows(const void *x, bool x_is_f32, int T, int H, const int32_t *cu_seqlens, int n_sentences, int max_len, int flags,
+                       void *out, hipStream_t stream) {
+    if (T <= 0 || n_sentences <= 0) return;
+    const dim3 grid((T + 3) / 4), block(256);
+    const bool norm = flags & TOKEN_ROWS_NORMALIZE, o16 = flags & TOKEN_ROWS_F16, vec = H % 8 == 0;
+#define TOKR(S, O, VW, NORM) BERT_LAUNCH((token_rows_kernel<S, O, VW, NORM>), grid, block, 0, stream, (const S *)x, T, H, cu_seqlens, n_sentences, max_len, (O *)out)
+#define TOKR_N(S, O, VW) do { if (norm) TOKR(S, O, VW, true); else TOKR(S, O, VW, false); } while (0)
+#define TOKR_V(S, O) do { if (vec) TOKR_N(S, O, 8); else TOKR_N(S, O, 1); } while (0)
+    if (x_is_f32) { if (o16) TOKR_V(float, half_t); else TOKR_V(float, float); }
+    else { if (o16) TOKR_V(half_t, half_t); else TOKR_V(half_t, float); }
+#undef TOKR_V
+#undef TOKR_N
+#undef TOKR
+}
+
 // A call's staged block (ids | cu_seqlens | windows) from MAPPED pinned host memory into device memory by a kernel: the copy
 // engine needs about 20 us before the first kernel behind it can start, a few workgroups reading 16 bytes per lane across the host
 // link need 5-8 for the 130 KB of a 256 x 128 batch (engine.hip eval_packed_host; small blocks only).

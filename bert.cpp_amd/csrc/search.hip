@@ -63,6 +63,7 @@
 #include <cmath>
 
 #include "device.h"
+#include "score_chain.h"
 #include "search_kernels.h"
 
 namespace bert_hip {
@@ -119,21 +120,10 @@ template <class T> struct FloatForm {
 template <> struct ScoreBlock<half_t> : FloatForm<half_t> {
     // v_mfma_f32_32x32x16_f16: lane l holds A[l & 31][16 s + 8 (l >> 5) + j] and B[..][l & 31] in element j of step s
     static __device__ __forceinline__ void run(const half_t *qp, const half_t *rp, bool qok, bool rok, int dpad, int h, f32x16 &acc) {
-        constexpr int U = 8;
+        // (the chain itself: score_chain.h, shared with maxsim.hip)
         const f16x8 z = {};
-        for (int k0 = 0; k0 < dpad; k0 += 16 * U) {
-            f16x8 a[U], b[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const bool in = k0 + 16 * u < dpad;
-                const int kk = k0 + 16 * u + 8 * h;
-                a[u] = qok && in ? *(const f16x8 *)(qp + kk) : z;
-                b[u] = rok && in ? *(const f16x8 *)(rp + kk) : z;
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                if (k0 + 16 * u < dpad) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[u], b[u], acc, 0, 0, 0);
-        }
+        score_chain_f16([&](int k, bool in) __attribute__((always_inline)) { return qok && in ? *(const f16x8 *)(qp + k + 8 * h) : z; },
+                        [&](int k, bool in) __attribute__((always_inline)) { return rok && in ? *(const f16x8 *)(rp + k + 8 * h) : z; }, dpad, acc);
     }
 };
 

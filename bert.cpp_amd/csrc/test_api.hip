@@ -774,4 +774,23 @@ int32_t bert_hip_test_build_lists(const int32_t *list_of, int32_t n, int32_t n_l
     return (int32_t)t.order.size();
 }
 
+int32_t bert_hip_test_token_rows(const void *x, int32_t is_f32, int32_t T, int32_t H, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
+                                 int32_t flags, void *out) {
+    const char *me = "bert_hip_test_token_rows";
+    if (!x || !cu_seqlens || !out || T < 1 || H < 1 || n_sentences < 1 || (flags & ~3)) return -1;
+    std::string err;
+    const int T_pad = (T + GEMM_BM - 1) / GEMM_BM * GEMM_BM;
+    const bool o16 = flags & TOKEN_ROWS_F16;
+    DevBuf dx, dcu, dout;
+    const bool ok = (is_f32 ? upload_padded(dx, (const uint32_t *)x, T, T_pad, H, g_pad32, err) : upload_rows16(dx, (const uint16_t *)x, T, T_pad, H, err)) &&
+                    dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) &&
+                    (o16 ? alloc_pad16(dout, (size_t)T * H, err) : alloc_pad32(dout, (size_t)T * H, err));
+    if (!ok) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return -1; }
+    launch_token_rows(dx.p, is_f32 != 0, T, H, dcu.as<int32_t>(), n_sentences, max_len, flags, dout.p, nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, (size_t)T * H * (o16 ? 2 : 4), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 }  // extern "C"

@@ -4,7 +4,12 @@
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
-//               [--long [--window W] [--stride S]]
+//               [--long [--window W] [--stride S]] [--maxsim N]
+//   (--maxsim N: late-interaction reranking.  The stages above return N candidates per query line instead of k (k <= N <= 256, and
+//   N <= --rescore's); the query and the N candidate lines go through bert_hip_encode_tokens_batch (token rows, each over its L2
+//   norm, lines cut at the model's position limit), bert_hip_maxsim scores the pairs (query, candidate j) — the sum over the query's
+//   tokens of the best cosine among the candidate's tokens —, and the k lines printed are the best by that score, which is shown;
+//   equal scores keep the first stage's order.)
 //   (--long: a line may be longer than the model's position limit: it is cut into overlapping windows of W ids, S inner ids apart,
 //   and embedded as ONE row (bert_hip_index_add_long_texts; W defaults to 128 or the model's limit if that is less, S to three
 //   quarters of W - 2).  Without --long a line is cut at the model's position limit, like a query;
@@ -19,6 +24,7 @@
 //   (bert_hip_index_partition_save); --load: the index comes from PATH instead of being embedded — TEXTS is still read, for
 //   printing, and must have as many lines as the index has rows —, and its partition from PATH.part where that file exists
 //   (bert_hip_index_partition_load: --nprobe then needs no --lists))
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,9 +38,11 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N]\n", argv0);
     fprintf(stderr, "  --long: lines of any length, cut into overlapping windows of W ids, S inner ids apart, one row per line (defaults: W 128 or the\n"
                     "          model's position limit if that is less, S three quarters of W - 2).  Without --long a line is cut at the model's position limit.\n");
+    fprintf(stderr, "  --maxsim N: the search returns N candidates (k <= N <= 256), which are reranked by the MaxSim score of their token rows against the\n"
+                    "          query's (bert_hip_encode_tokens_batch + bert_hip_maxsim); the k best by that score are printed with it.\n");
 }
 
 std::string chomp(std::string s) {
@@ -45,8 +53,8 @@ std::string chomp(std::string s) {
 
 int main(int argc, char **argv) {
     const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr;
-    int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0;
-    bool long_texts = false;
+    int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0;
+    bool long_texts = false, maxsim = false;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
         if ((!strcmp(argv[i], "-m") || !strcmp(argv[i], "--model")) && has_value) model = argv[++i];
@@ -64,13 +72,17 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--long")) long_texts = true;
         else if (!strcmp(argv[i], "--window") && has_value) window = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--stride") && has_value) stride = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--maxsim") && has_value) { maxsim = true; n_maxsim = atoi(argv[++i]); }
         else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
     }
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
     if (!long_texts && (window || stride)) { fprintf(stderr, "search: --window and --stride go with --long\n"); return 2; }
+    if (maxsim && (n_maxsim < k || n_maxsim > 256)) { fprintf(stderr, "search: --maxsim must be -k .. 256\n"); return 2; }
+    const int k_print = k;
+    if (maxsim) k = n_maxsim;                                 // (what the stages below return; k_print lines come out of the reranking)
     const bool two_stage = n_cand != 0;
-    if (two_stage && (n_cand < k || n_cand > 256)) { fprintf(stderr, "search: --rescore must be -k .. 256\n"); return 2; }
+    if (two_stage && (n_cand < k || n_cand > 256)) { fprintf(stderr, "search: --rescore must be %s .. 256\n", maxsim ? "--maxsim's N" : "-k"); return 2; }
 
     if (n_lists < 0 || n_lists > 65536) { fprintf(stderr, "search: --lists must be 1 .. 65536\n"); return 2; }
     // (against the lists themselves once they are there: they may come from --load PATH's PATH.part)
@@ -209,6 +221,35 @@ int main(int argc, char **argv) {
             fprintf(stderr, "search: the search failed\n");
             bert_free(ctx);
             return 1;
+        }
+        if (maxsim) {
+            // token rows of the query and the candidates, then the pairs (query, candidate j)
+            int n_found = 0;
+            while (n_found < k && ids[n_found] >= 0) ++n_found;
+            std::vector<const char *> lines{qp};
+            for (int j = 0; j < n_found; ++j) lines.push_back(texts[ids[j]].c_str());
+            const int32_t n_in = (int32_t)lines.size(), H = bert_n_embd(ctx);
+            std::vector<int32_t> cu((size_t)n_in + 1), pairs;
+            const int64_t total = bert_hip_encode_tokens_batch(ctx, n_threads, n_in, lines.data(), 1, cu.data(), nullptr, 0);
+            std::vector<float> rows(total > 0 ? (size_t)total * H : 0), ms((size_t)n_found);
+            bool ok = total > 0 && bert_hip_encode_tokens_batch(ctx, n_threads, n_in, lines.data(), 1, cu.data(), rows.data(), total) == total;
+            if (ok && n_found > 0) {
+                const int32_t qcu[2] = {0, cu[1]};
+                std::vector<int32_t> dcu((size_t)n_found + 1);
+                for (int j = 0; j <= n_found; ++j) { dcu[j] = cu[j + 1] - cu[1]; if (j < n_found) { pairs.push_back(0); pairs.push_back(j); } }
+                ok = bert_hip_maxsim(ctx, rows.data(), qcu, 1, rows.data() + (size_t)cu[1] * H, dcu.data(), n_found, H, pairs.data(), n_found, 0, ms.data()) == 0;
+            }
+            if (!ok) {
+                fprintf(stderr, "search: the MaxSim reranking failed\n");
+                bert_free(ctx);
+                return 1;
+            }
+            std::vector<int> order((size_t)n_found);
+            for (int j = 0; j < n_found; ++j) order[j] = j;
+            std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return ms[x] > ms[y]; });
+            printf("\nClosest texts:\n");
+            for (int i = 0; i < k_print && i < n_found; ++i) printf("%d. %s\n (MaxSim score: %.4f)\n", i + 1, texts[ids[order[i]]].c_str(), ms[order[i]]);
+            continue;
         }
         printf("\nClosest texts:\n");
         for (int i = 0; i < k && ids[i] >= 0; ++i) printf("%d. %s\n (similarity score: %.4f)\n", i + 1, texts[ids[i]].c_str(), scores[i]);

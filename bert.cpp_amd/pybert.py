@@ -37,6 +37,7 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_index_search_rescored_probed_device", "bert_hip_index_partition_save", "bert_hip_index_partition_load",
     "bert_hip_eval_packed_grouped", "bert_hip_eval_packed_grouped_device", "bert_hip_tokenize_long", "bert_hip_plan_windows",
     "bert_hip_encode_long_batch", "bert_hip_index_add_long_texts",
+    "bert_hip_eval_packed_tokens_device", "bert_hip_eval_packed_tokens", "bert_hip_encode_tokens_batch", "bert_hip_maxsim_device", "bert_hip_maxsim",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -48,7 +49,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_f32_gemm", "bert_hip_test_f32_attention", "bert_hip_test_f32_layernorm", "bert_hip_test_f32_embed_ln", "bert_hip_test_f32_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
-    "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool",
+    "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool", "bert_hip_test_token_rows",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -149,6 +150,13 @@ def _declare_product_abi(L):
     L.bert_hip_encode_long_batch.restype = i32
     L.bert_hip_encode_long_batch.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32, C.POINTER(f32p), i32p]
     L.bert_hip_index_add_long_texts.restype = i32; L.bert_hip_index_add_long_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32]
+    L.bert_hip_eval_packed_tokens_device.restype = i32
+    L.bert_hip_eval_packed_tokens_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.bert_hip_eval_packed_tokens.restype = i32; L.bert_hip_eval_packed_tokens.argtypes = [vp, i32p, i32p, i32, i32, f32p, f32p]
+    L.bert_hip_encode_tokens_batch.restype = C.c_int64
+    L.bert_hip_encode_tokens_batch.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32p, f32p, C.c_int64]
+    L.bert_hip_maxsim_device.restype = i32; L.bert_hip_maxsim_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
+    L.bert_hip_maxsim.restype = i32; L.bert_hip_maxsim.argtypes = [vp, f32p, i32p, i32, f32p, i32p, i32, i32, i32p, i32, i32, f32p]
 
 
 def lib() -> C.CDLL:
@@ -245,6 +253,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_build_lists.argtypes = [i32p, i32, i32, i32p, i32p]
     L.bert_hip_test_group_pool.restype = i32
     L.bert_hip_test_group_pool.argtypes = [vp, i32, i32p, i32p, i32, i32, i32, vp, i32p]
+    L.bert_hip_test_token_rows.restype = i32
+    L.bert_hip_test_token_rows.argtypes = [vp, i32, i32, i32, i32p, i32, i32, i32, vp]
     _test_lib = L
     return L
 
@@ -315,6 +325,19 @@ def test_group_pool(rows: np.ndarray, weights, group_cu, raw: bool, out: Optiona
     if r != 0:
         raise RuntimeError(f"bert_hip_test_group_pool failed: {r}")
     return out, int(st[0])
+
+
+def test_token_rows(x: np.ndarray, cu_seqlens, max_len: int, normalize: bool = True, f16_out: bool = False) -> np.ndarray:
+    """launch_token_rows on final states x [T, H], float16 or float32 (the f32 route's); returns the rows [T, H], float32 or (f16_out)
+    float16.  Under test_pad the device copy's rows behind T and the output beforehand hold the patterns."""
+    assert x.dtype in (np.float16, np.float32) and x.ndim == 2
+    x = np.ascontiguousarray(x); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    out = np.zeros(x.shape, dtype=np.float16 if f16_out else np.float32)
+    r = test_lib().bert_hip_test_token_rows(x.ctypes.data, int(x.dtype == np.float32), x.shape[0], x.shape[1], _i32p(cu), len(cu) - 1, max_len,
+                                            int(bool(normalize)) | 2 * int(bool(f16_out)), out.ctypes.data)
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_token_rows failed: {r}")
+    return out
 
 
 def plan_windows(n_tokens: int, window: int, stride: int) -> List[int]:
@@ -613,6 +636,72 @@ class BertModel:
         if r != n:
             raise RuntimeError(f"bert_hip_encode_long_batch encoded {r} of {n} texts")
         return (out, nw) if return_windows else out
+
+    # ---- token rows and late interaction ---------------------------------------------------
+    def eval_packed_tokens(self, tokens: np.ndarray, cu_seqlens: np.ndarray, normalize: bool = True, with_embeddings: bool = False):
+        """The final state of every token of a packed batch (bert_hip_eval_packed_tokens): rows [n_tokens, n_embd] f32, each over its L2
+        norm if normalize; with_embeddings: (rows, embeddings [n_sentences, n_embd]), the embeddings eval_packed's bits."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+        B = len(cu) - 1
+        rows = np.full((int(cu[-1]), self.n_embd), np.nan, dtype=np.float32)
+        emb = np.full((B, self.n_embd), np.nan, dtype=np.float32) if with_embeddings else None
+        r = self.lib.bert_hip_eval_packed_tokens(self.ctx, _i32p(tokens), _i32p(cu), B, int(bool(normalize)), _f32p(rows),
+                                                 _f32p(emb) if with_embeddings else None)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_eval_packed_tokens failed: {r}")
+        return (rows, emb) if with_embeddings else rows
+
+    def eval_packed_tokens_device(self, d_tokens_ptr: int, d_cu_ptr: int, n_sentences: int, n_tokens: int, max_len: int, d_rows_ptr: int,
+                                  d_embeddings_ptr: Optional[int] = None, normalize: bool = True, f16: bool = False, stream: int = 0) -> None:
+        r = self.lib.bert_hip_eval_packed_tokens_device(self.ctx, d_tokens_ptr, d_cu_ptr, n_sentences, n_tokens, max_len,
+                                                        int(bool(normalize)) | 2 * int(bool(f16)), d_rows_ptr, d_embeddings_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_eval_packed_tokens_device failed: {r}")
+
+    def encode_tokens(self, texts: Sequence[str], normalize: bool = True, n_threads: int = 6):
+        """Token rows of texts (bert_hip_encode_tokens_batch; tokenized and truncated as encode_batch does): (rows [n_tokens, n_embd] f32,
+        cu [n_texts + 1] int32)."""
+        n = len(texts)
+        txt = (C.c_char_p * n)(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        cu = np.zeros(n + 1, dtype=np.int32)
+        flags = int(bool(normalize))
+        total = self.lib.bert_hip_encode_tokens_batch(self.ctx, n_threads, n, txt, flags, _i32p(cu), None, 0)
+        if total < 0:
+            raise RuntimeError(f"bert_hip_encode_tokens_batch failed: {total}")
+        rows = np.full((total, self.n_embd), np.nan, dtype=np.float32)
+        if self.lib.bert_hip_encode_tokens_batch(self.ctx, n_threads, n, txt, flags, _i32p(cu), _f32p(rows), total) != total:
+            raise RuntimeError("bert_hip_encode_tokens_batch failed")
+        return rows, cu
+
+    def maxsim(self, q_rows, q_cu, d_rows, d_cu, pairs=None, mean: bool = False, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """MaxSim of two packed sets of token rows (bert_hip_maxsim: f32 rows, rounded to f16 on the device): scores [n_q, n_d], or
+        [n_pairs] for pairs [n_pairs, 2] of (query sentence, document sentence).  Raises ValueError for arguments the entry refuses
+        (-2: out, if given, untouched)."""
+        q = np.ascontiguousarray(q_rows, dtype=np.float32); d = np.ascontiguousarray(d_rows, dtype=np.float32)
+        qcu = np.ascontiguousarray(q_cu, dtype=np.int32); dcu = np.ascontiguousarray(d_cu, dtype=np.int32)
+        assert q.ndim == 2 and d.ndim == 2 and q.shape[1] == d.shape[1]
+        n_q, n_d = len(qcu) - 1, len(dcu) - 1
+        pr = None if pairs is None else np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if out is None:
+            out = np.full(len(pr) if pr is not None else (n_q, n_d), np.nan, dtype=np.float32)
+        r = self.lib.bert_hip_maxsim(self.ctx, _f32p(q), _i32p(qcu), n_q, _f32p(d), _i32p(dcu), n_d, q.shape[1], None if pr is None else _i32p(pr),
+                                     0 if pr is None else len(pr), int(bool(mean)), _f32p(out))
+        if r == -2:
+            raise ValueError("bert_hip_maxsim refused its arguments (see stderr)")
+        if r != 0:
+            raise RuntimeError(f"bert_hip_maxsim failed: {r}")
+        return out
+
+    def maxsim_device(self, d_q_ptr: int, d_qcu_ptr: int, n_q: int, d_d_ptr: int, d_dcu_ptr: int, n_d: int, H: int, d_pairs_ptr: Optional[int],
+                      n_pairs: int, d_scores_ptr: int, mean: bool = False, stream: int = 0) -> None:
+        """bert_hip_maxsim_device: f16 rows, lengths, pairs (or None) and scores in device memory, enqueued on stream."""
+        r = self.lib.bert_hip_maxsim_device(self.ctx, d_q_ptr, d_qcu_ptr, n_q, d_d_ptr, d_dcu_ptr, n_d, H, d_pairs_ptr, n_pairs, int(bool(mean)),
+                                            d_scores_ptr, stream)
+        if r == -2:
+            raise ValueError("bert_hip_maxsim_device refused its arguments (see stderr)")
+        if r != 0:
+            raise RuntimeError(f"bert_hip_maxsim_device failed: {r}")
 
     def eval_packed_gather(self, tokens: np.ndarray, cu_seqlens: np.ndarray) -> List[int]:
         """Evaluates on all devices of the context and gathers on every device: returns the device pointers of the

@@ -220,6 +220,71 @@ BERT_API int32_t bert_hip_plan_windows(int32_t n_tokens, int32_t window, int32_t
 BERT_API int32_t bert_hip_encode_long_batch(struct bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, int32_t window,
                                             int32_t stride, float **embeddings, int32_t *n_windows);
 
+/* TOKEN ROWS AND LATE INTERACTION.  Everything above returns one row per sentence or per text; the final state of every token is
+ * computed on every pass and then dropped.  The entry points below return those states — per-token embeddings, the input of BERTScore
+ * and of ColBERT-style late-interaction scoring — and score two sets of them by MaxSim on the device.  Nothing above changes its
+ * behaviour or its bits.
+ *
+ * Token rows.  A pass with one more destination: rows[t] is the final state (after the last layer's output LayerNorm) of token t of
+ * the packed batch, n_embd values, in the order of `tokens`.
+ *   Route.  Such a pass does not take the all-layers-in-one-launch kernel (that kernel pools inside the launch and leaves no row-order
+ *   copy of the states); it runs the latency route, the fused two-launches-per-layer route, the folded-LayerNorm route or the f32 route
+ *   as a call without the rows would with "one_launch" = "0".  Unlike bert_hip_eval_hidden, LayerNorm folding stays as planned, so the
+ *   call's embeddings are, bit for bit, bert_hip_eval_packed's, and a sentence's rows have the same bits alone and in any batch.
+ *   flags.  bit 0 (1): every row divided by its own L2 norm — the sum of squares in f32, a lane's elements in ascending order, then the
+ *   lanes in the butterfly order of the pooling's reductions, 1 / sqrt, no epsilon (a zero row gives NaN, as in the pooling).  bit 1
+ *   (2, device form only): rows are f16, rounded to nearest even, instead of f32.  Without bit 0 the f32 rows are the stored states
+ *   exactly: the f16 values converted to f32, or the f32 values on the f32 route.  Under "pooling" = "cls", "normalize" = "0" the
+ *   un-normalised row of a sentence's first token is that sentence's embedding, bit for bit.
+ *   Guard.  The tokens of a sentence that is empty or longer than max_len get NaN rows (and the sentence a NaN embedding and the status
+ *   word of bert_hip_check, as in every device call).
+ *   The copy is one launch behind the pooling launch, listed as "token_rows" by bert_hip_profile_report; it allocates nothing, so a
+ *   context sized by bert_hip_reserve may call the device form under stream capture.
+ *   eval_packed_tokens_device  the rules of bert_hip_eval_packed_device (everything in HBM on the first device, enqueued on `stream`).
+ *                              d_rows: [n_tokens_total][n_embd] f32, or f16 with flags bit 1; d_embeddings: [n_sentences][n_embd] f32 or
+ *                              NULL (the embeddings then stay in the engine's workspace).  The buffers must not overlap.
+ *   eval_packed_tokens         host buffers, blocking, on the context's FIRST device (a multi-device context does not spread it).
+ *                              flags: bit 0 only; rows [cu_seqlens[n_sentences]][n_embd] f32; embeddings [n_sentences][n_embd] or NULL.
+ *                              The batch is cut at BERT_HIP_CHUNK_TOKENS between sentences, one plain copy per chunk and direction (not
+ *                              the pipelined staging of bert_hip_eval_packed); the cut does not show in the bits.  0; -1 without a device;
+ *                              -2 with the outputs untouched after a line on stderr for a sentence that cannot be evaluated; -3 on a device error.
+ *   encode_tokens_batch        texts: tokenized as bert_encode_batch does (same truncation), on up to n_threads host threads.  cu_out
+ *                              [n_inputs + 1] receives the cumulative token counts, always.  Returns the total token count; writes rows
+ *                              [total][n_embd] iff rows != NULL and cap_rows >= that count (rows NULL with cap_rows 0: a count call that
+ *                              only tokenizes).  flags: bit 0 only.  Negative on an error (-1 without a device).
+ *
+ * MaxSim.  Q [nq_tokens][H] and D [nd_tokens][H] are two packed sets of token rows with cumulative lengths qcu [n_q + 1] and dcu
+ * [n_d + 1] (sentence a of Q is rows qcu[a] .. qcu[a + 1] - 1).  For a pair (a, b)
+ *       score(a, b) = sum over the tokens i of a of ( max over the tokens j of b of <Q_i, D_j> ),
+ * divided by (float)len(a) with mode bit 0.  pairs NULL: all pairs, scores [n_q][n_d]; else pairs [n_pairs][2] of (a, b), in any order
+ * and with repeats, scores [n_pairs].  H: a multiple of 8 from 8 to 1024 (rows are whole 16-byte pieces), else -2.
+ *   Arithmetic.  The rows are f16.  Every inner product is the chain of the f16 index (v_mfma_f32_32x32x16_f16, f32 accumulation, k
+ *   ascending; at H % 16 == 8 the last half step is zero-filled in registers).  The max is exact.  The sum runs in one fixed order:
+ *   the query tokens in blocks of 32, a block's 32 maxima (a short last block padded with +0) added in the butterfly order of the
+ *   pooling's wave reduction, the blocks' sums added in ascending order; the mean is one division.  No atomics: a pair's bits depend
+ *   on its own rows alone — not on its place in the output, the other pairs, or the list form against the all-pairs form.
+ *   Masking.  Rows outside a pair's two ranges are never read into its score: a document slot behind len(b) enters the max as -inf
+ *   (a pair whose similarities are all negative scores negative), a query slot behind len(a) adds 0.
+ *   maxsim_device   rows (f16, 16-byte aligned), lengths, pairs and scores in HBM on the first device, enqueued on `stream`; allocates
+ *                   nothing; listed as "maxsim" by bert_hip_profile_report.  The lengths and pairs are checked on the device: a pair
+ *                   whose index lies outside [0, n_q) x [0, n_d), or one of whose sentences is empty, descends in its cu entries or
+ *                   starts below 0, gets a NaN score; its neighbours are untouched.  -2 for a bad H, count or pointer.
+ *   maxsim          host buffers, blocking: f32 rows, uploaded and rounded to f16 (nearest even) on the device, then maxsim_device.
+ *                   Everything is validated first — cu entries strictly ascending from an entry >= 0, every pair in range —: -2 after a
+ *                   line on stderr with the scores untouched.  -1 without a device, -3 on a device error.                          */
+BERT_API int32_t bert_hip_eval_packed_tokens_device(struct bert_ctx *ctx, const bert_vocab_id *d_tokens, const int32_t *d_cu_seqlens,
+                                                    int32_t n_sentences, int32_t n_tokens_total, int32_t max_len, int32_t flags,
+                                                    void *d_rows, float *d_embeddings, void *stream);
+BERT_API int32_t bert_hip_eval_packed_tokens(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens,
+                                             int32_t n_sentences, int32_t flags, float *rows, float *embeddings);
+BERT_API int64_t bert_hip_encode_tokens_batch(struct bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, int32_t flags,
+                                              int32_t *cu_out, float *rows, int64_t cap_rows);
+BERT_API int32_t bert_hip_maxsim_device(struct bert_ctx *ctx, const void *d_q, const int32_t *d_qcu, int32_t n_q, const void *d_d,
+                                        const int32_t *d_dcu, int32_t n_d, int32_t H, const int32_t *d_pairs, int32_t n_pairs, int32_t mode,
+                                        float *d_scores, void *stream);
+BERT_API int32_t bert_hip_maxsim(struct bert_ctx *ctx, const float *q, const int32_t *qcu, int32_t n_q, const float *d, const int32_t *dcu,
+                                 int32_t n_d, int32_t H, const int32_t *pairs, int32_t n_pairs, int32_t mode, float *scores);
+
 /* Embedding index: rows in HBM on the context's FIRST device (bert_hip_device), exact top-k search by inner product.
  * An index belongs to the context it was made from: bert_free frees any index the caller left alive.  Like every
  * entry point of a context, the index functions are not re-entrant on one context.

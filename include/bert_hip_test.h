@@ -218,6 +218,14 @@ BERT_API int32_t bert_hip_test_partition_header(const void *buf, int32_t buf_len
  * entries written to order, -1 for bad arguments.  No device.                                                               */
 BERT_API int32_t bert_hip_test_build_lists(const int32_t *list_of, int32_t n, int32_t n_lists, int32_t *offsets, int32_t *order);
 
+/* launch_token_rows on its own (kernels.h; bert_hip.h "token rows and late interaction"): x [T][H], f16 bits (is_f32 0) or f32 (1), the
+ * final states of a pass; cu_seqlens [n_sentences + 1], max_len and flags as bert_hip_eval_packed_tokens_device takes them; out [T][H],
+ * f16 bits with flags bit 1, else f32.  Host buffers in and out.  The device copy of x has its rows rounded up to whole 128-token
+ * tiles: the rows behind T, and every word of the output before the launch, hold the patterns of bert_hip_test_set_pad.  0, or -1
+ * after a line on stderr.                                                                                                        */
+BERT_API int32_t bert_hip_test_token_rows(const void *x, int32_t is_f32, int32_t T, int32_t H, const int32_t *cu_seqlens, int32_t n_sentences,
+                                          int32_t max_len, int32_t flags, void *out);
+
 #ifdef __cplusplus
 }
 #endif
