@@ -78,6 +78,21 @@ public:
     // profile_report as `name`
     void timed_launch(const char *name, double flops, hipStream_t s, const std::function<void()> &f);
 
+    // The one-event rule and stream capture (bert_hip.h "stream capture and graphs"), in one place for the engine and its indexes.  An
+    // operation that uses this engine's workspace, or the buffers of one of its indexes, starts with op_begin on the caller's stream and
+    // ends with op_end; `busy` is the owner's event (null: the operation shares no buffer, as MaxSim).
+    //   eager:      op_begin makes s wait for busy, op_end records busy on s — operations never overlap, whatever their streams
+    //   capturing:  neither touches busy.  A wait inside a capture for an event recorded on the same stream before it fails
+    //               (hipErrorStreamCaptureIsolation) and invalidates the capture; an event recorded inside a capture belongs to the
+    //               capture, which the blocking paths' hipEventSynchronize (grow, compact, save, the destructor) need not accept; and
+    //               a replay records nothing anyway.  Inside one capture the stream orders the operations; against everything else
+    //               the caller orders the graph launch.
+    //   capturing while the engine profiles: refused (false, a message in err, nothing enqueued) — a timed launch carries an
+    //               event pair that a capture would take over in the same way, and hipEventElapsedTime on them is undefined.
+    struct StreamOp { hipStream_t s = nullptr; hipEvent_t busy = nullptr; bool capturing = false; };
+    bool op_begin(hipStream_t s, hipEvent_t busy, StreamOp &op, std::string &err);
+    bool op_end(const StreamOp &op, std::string &err);
+
     const HParams &hparams() const { return hp_; }
     const EngineOptions &options() const { return opt_; }
     int device() const { return device_; }
@@ -124,7 +139,7 @@ private:
     void attention(const Plan &p);
     void tap(const Plan &p, int idx);
     // the grouped-pooling launch ("group_pool" in the profile) behind a pass on s, then busy_ again: the next pass must not write raw_rows_ under it
-    int group_pool(const int32_t *d_cu, int n_sentences, const int32_t *d_group_cu, int n_groups, float *d_out, int pool_mode, hipStream_t s, std::string &err);
+    int group_pool(const int32_t *d_cu, int n_sentences, const int32_t *d_group_cu, int n_groups, float *d_out, int pool_mode, const StreamOp &op, std::string &err);
     template <class F> void timed(const char *name, double flops, hipStream_t s, F &&f) { prof_.timed(name, flops, s, f); }
 
     HParams hp_;

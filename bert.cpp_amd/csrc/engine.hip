@@ -85,6 +85,25 @@ bool Engine::ensure_workspace(int t_pad, int n_sentences, std::string &err) {
 
 void Engine::timed_launch(const char *name, double flops, hipStream_t s, const std::function<void()> &f) { timed(name, flops, s, f); }
 
+bool Engine::op_begin(hipStream_t s, hipEvent_t busy, StreamOp &op, std::string &err) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(s, &st), err, false);
+    // (only an ACTIVE capture.  A stream whose capture was invalidated — by an allocation, say — takes the eager path: the runtime
+    // refuses the wait or the launches on it itself, and goes on doing so after hipStreamEndCapture: such a stream is to be destroyed)
+    op.s = s; op.busy = busy; op.capturing = st == hipStreamCaptureStatusActive;
+    if (!op.capturing) {
+        if (busy) HIP_OK(hipStreamWaitEvent(s, busy, 0), err, false);
+        return true;
+    }
+    if (prof_.enabled()) { err = "the stream is capturing while the context profiles: a timed launch cannot be captured (bert_hip_profile_enable(ctx, 0) first)"; return false; }
+    return true;
+}
+
+bool Engine::op_end(const StreamOp &op, std::string &err) {
+    if (!op.capturing && op.busy) HIP_OK(hipEventRecord(op.busy, op.s), err, false);
+    return true;
+}
+
 std::string Engine::profile_report() {
     (void)hipSetDevice(device_);
     (void)hipDeviceSynchronize();
@@ -115,10 +134,11 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     // (so are "pooling" and "normalize": every launch that ends the pass gets the plan's value)
     const int pool_mode = pool_mode_in >= 0 ? pool_mode_in : opt_.pool_mode();
     HIP_OK(hipSetDevice(device_), err, -1);
+    // one forward pass at a time on the shared workspace: wait (on the caller's stream) for the previous pass — unless s is capturing
+    StreamOp op;
+    if (!op_begin(s, busy_, op, err)) return -1;
     if (!ensure_workspace((T + 255) / 256 * 256, B, err)) return -1;
     prof_.begin_pass();
-    // one forward pass at a time on the shared workspace: wait (on the caller's stream) for the previous pass
-    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     if (!d_out) d_out = d_out_.as<float>();                   // (a token-rows call that wants no embeddings: ensure_workspace sized it)
     const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots, pool_mode, d_token_rows);
     bool ok = true;
@@ -145,8 +165,7 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     if (d_token_rows)
         timed("token_rows", 0.0, s, [&] { launch_token_rows(x_.p, p.route == Route::F32, T, hp_.n_embd, d_cu, B, max_len, token_flags, d_token_rows, s); });
     HIP_OK(hipGetLastError(), err, -1);
-    HIP_OK(hipEventRecord(busy_, s), err, -1);
-    return 0;
+    return op_end(op, err) ? 0 : -1;
 }
 
 // The route of a pass and, per layer, its kernels: every eligibility test of the forward pass, each made here once.  Launches nothing.
@@ -543,16 +562,16 @@ int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, fl
     return 0;
 }
 
-int Engine::group_pool(const int32_t *d_cu, int B, const int32_t *d_group_cu, int n_groups, float *d_out, int pool_mode, hipStream_t s, std::string &err) {
+int Engine::group_pool(const int32_t *d_cu, int B, const int32_t *d_group_cu, int n_groups, float *d_out, int pool_mode, const StreamOp &op, std::string &err) {
     const int H = hp_.n_embd;
+    const hipStream_t s = op.s;
     // (2 flops per element and sentence; the launch reads B rows and writes n_groups)
     timed("group_pool", 2.0 * B * H, s, [&] {
         launch_group_pool(raw_rows_.as<float>(), (pool_mode & POOL_CLS) ? nullptr : d_cu, d_group_cu, B, n_groups, H, (pool_mode & POOL_RAW) != 0,
                           status_.as<int>(), d_out, s);
     });
     HIP_OK(hipGetLastError(), err, -1);
-    HIP_OK(hipEventRecord(busy_, s), err, -1);
-    return 0;
+    return op_end(op, err) ? 0 : -1;
 }
 
 int Engine::eval_packed_grouped_device(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, const int32_t *d_group_cu,
@@ -560,9 +579,12 @@ int Engine::eval_packed_grouped_device(const int32_t *d_tokens, const int32_t *d
     if (B <= 0 || T <= 0 || n_groups <= 0) return 0;
     const int pool_mode = opt_.pool_mode();                   // (once per call: the pass and the pooling agree)
     HIP_OK(hipSetDevice(device_), err, -1);
+    // (the pooling launch behind the pass is part of the same operation: one answer for both on whether s is capturing)
+    StreamOp op;
+    if (!op_begin(s, busy_, op, err)) return -1;
     if (!raw_rows_.ensure((size_t)B * hp_.n_embd * 4, err)) return -1;
     if (eval_packed_device(d_tokens, d_cu, B, T, max_len, raw_rows_.as<float>(), s, nullptr, err, nullptr, 0, 0, pool_mode | POOL_RAW) != 0) return -1;
-    return group_pool(d_cu, B, d_group_cu, n_groups, d_out, pool_mode, s, err);
+    return group_pool(d_cu, B, d_group_cu, n_groups, d_out, pool_mode, op, err);
 }
 
 int Engine::eval_packed_grouped_host(const int32_t *tokens, const int32_t *cu, int B, const int32_t *group_cu, int n_groups, float *embeddings,
@@ -588,7 +610,7 @@ int Engine::eval_packed_grouped_host(const int32_t *tokens, const int32_t *cu, i
     }
     if (hipMemcpyAsync(group_in_.p, in.data(), n_in * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) return fail("hipMemcpyAsync (groups) failed");
     float *d_out = d_embeddings ? d_embeddings : group_out_.as<float>();
-    if (group_pool(group_in_.as<int32_t>(), B, group_in_.as<int32_t>() + B + 1, n_groups, d_out, pool_mode, stream_, err) != 0) return fail(nullptr);
+    if (group_pool(group_in_.as<int32_t>(), B, group_in_.as<int32_t>() + B + 1, n_groups, d_out, pool_mode, StreamOp{stream_, busy_, false}, err) != 0) return fail(nullptr);
     if (!d_embeddings && hipMemcpyAsync(embeddings, d_out, (size_t)n_groups * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess)
         return fail("hipMemcpyAsync (embeddings) failed");
     HIP_OK(hipStreamSynchronize(stream_), err, -1);

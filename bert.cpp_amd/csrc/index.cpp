@@ -190,14 +190,15 @@ bool Index::grow_queries(int nqc, std::string &err) {
 int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &err) {
     if (const int go = check_add(n, d_rows, n_, err); go <= 0) return go < 0 ? -1 : n_;
     DeviceGuard g(eng_->device());
+    Engine::StreamOp op;                                     // (engine.h: the one-event rule, and what a capturing stream changes)
+    if (!eng_->op_begin(s, busy_, op, err)) return -1;
     if (!grow_rows(n_ + n, err)) return -1;
-    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     char *dst = (char *)rows_ + (size_t)n_ * row_bytes_;
     eng_->timed_launch(FORMS[dtype_].ingest, 0.0, s, [&] { launch_ingest(dtype_, d_rows, dst, rscale_ ? rscale_ + n_ : nullptr, n, dim_, dpad_, s); });
     // (rows added after a removal are live: their bits on the same stream, and in the mirror, which is already long enough)
     if (live_) launch_live_set_range(live_, n_, n, s);
     HIP_OK(hipGetLastError(), err, -1);
-    HIP_OK(hipEventRecord(busy_, s), err, -1);
+    if (!eng_->op_end(op, err)) return -1;
     if (live_) live_set_range_host(live_h_, n_, n);
     const int first = n_;
     n_ += n;
@@ -254,18 +255,18 @@ int Index::search_device(int nq, const float *d_q, int k, int32_t *d_ids, float 
                          const uint32_t *d_allow) {
     if (const int go = check_search(nq, d_q, k, d_ids, d_scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -1;
     const int nqc = std::min(nq, QCHUNK);
     // (the last, shorter chunk may be cut into more slices than a full one)
     const size_t ent = std::max(ws_entries_bound(n_, nqc, k), nq % QCHUNK ? ws_entries_bound(n_, nq % QCHUNK, k) : 0);
     if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow_queries(nqc, err)) return -1;
-    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         enqueue_chunk(c, d_q + (size_t)c0 * dim_, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s, d_allow);
     }
     HIP_OK(hipGetLastError(), err, -1);
-    HIP_OK(hipEventRecord(busy_, s), err, -1);
-    return 0;
+    return eng_->op_end(op, err) ? 0 : -1;
 }
 
 // The loop of the host routes, blocking: per chunk of QCHUNK queries, the queries into stage_ (unless they are on the device;
@@ -325,10 +326,11 @@ int Index::rescore_device(int nq, const float *d_q, int n_cand, const int32_t *d
                           hipStream_t s, std::string &err) {
     if (const int go = check_rescore(nq, d_q, n_cand, d_cand, k, d_ids, d_scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -1;
     const int nqc = std::min(nq, QCHUNK);
     const size_t ent = (size_t)nqc * n_cand;
     if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow_queries(nqc, err)) return -1;
-    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         enqueue_queries(c, d_q + (size_t)c0 * dim_, s);
@@ -340,8 +342,7 @@ int Index::rescore_device(int nq, const float *d_q, int n_cand, const int32_t *d
         enqueue_merge(c, n_cand, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -1);
-    HIP_OK(hipEventRecord(busy_, s), err, -1);
-    return 0;
+    return eng_->op_end(op, err) ? 0 : -1;
 }
 
 int Index::rescore_to_host(int nq, const float *q, int n_cand, const int32_t *cand, int k, int32_t *ids, float *scores, std::string &err) {
@@ -358,11 +359,12 @@ int Index::search_rescored_device(Index &coarse, int nq, const float *d_q, int n
                                   hipStream_t s, std::string &err, int nprobe, const uint32_t *d_allow) {
     if (const int go = check_search_rescored(nq, d_q, n_cand, k, d_ids, d_scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
+    // (the candidate lists are this index's: the coarse search that fills them waits for whatever still reads them; after
+    // that the two steps of a chunk, and the chunks, follow each other on s.  The rescore of each chunk ends the operation.)
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -1;
     const int nqc = std::min(nq, QCHUNK);
     if (!grow(cand_i_, (size_t)nqc * n_cand * 4, err) || !grow(cand_s_, (size_t)nqc * n_cand * 4, err)) return -1;
-    // (the candidate lists are this index's: the coarse search that fills them waits for whatever still reads them; after
-    // that the two steps of a chunk, and the chunks, follow each other on s)
-    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         const float *dq = d_q + (size_t)c0 * dim_;
@@ -394,14 +396,15 @@ int Index::search_probed_device(int nq, const float *d_q, int nprobe, int k, int
     if (const int go = check_search(nq, d_q, k, d_ids, d_scores, err); go <= 0) return go;
     if (!cent_ || nprobe < 1 || nprobe > std::min(n_lists(), MAX_K)) { err = "search_probed: a partition and 1 <= nprobe <= min(n_lists, 256) required"; return -1; }
     DeviceGuard g(eng_->device());
+    // (the probe lists are this index's: the centroid search that fills them waits, on s, for whatever still reads them)
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -1;
     const int nqc = std::min(nq, QCHUNK);
     // items per query: the probed lists, then the chunks of the tail
     const int n_items = nprobe + (int)(((long long)n_ - n_part_ + PROBE_CHUNK - 1) / PROBE_CHUNK);
     const size_t ent = (size_t)nqc * n_items * k;
     if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow_queries(nqc, err) ||
         !grow(probe_i_, (size_t)nqc * nprobe * 4, err) || !grow(probe_s_, (size_t)nqc * nprobe * 4, err)) return -1;
-    // (the probe lists are this index's: the centroid search that fills them waits, on s, for whatever still reads them)
-    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, -1);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         const float *dq = d_q + (size_t)c0 * dim_;
@@ -418,8 +421,7 @@ int Index::search_probed_device(int nq, const float *d_q, int nprobe, int k, int
         enqueue_merge(c, n_items * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -1);
-    HIP_OK(hipEventRecord(busy_, s), err, -1);
-    return 0;
+    return eng_->op_end(op, err) ? 0 : -1;
 }
 
 int Index::search_probed_to_host(int nq, const float *q, int nprobe, int k, int32_t *ids, float *scores, std::string &err,

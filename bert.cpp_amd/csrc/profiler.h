@@ -19,6 +19,7 @@ public:
     ~LaunchProfiler();                                        // (the owner has set the device and drained it)
 
     void enable(bool on) { profiling_ = on; }
+    bool enabled() const { return profiling_; }
     // "<kernel name>:<K>" (see timed()), "" switches back to an event pair per launch
     void set_replay(const std::string &value);
     void begin_pass() { replay_done_ = false; }

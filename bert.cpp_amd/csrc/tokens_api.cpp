@@ -137,6 +137,10 @@ int32_t bert_hip_maxsim_device(struct bert_ctx *ctx, const void *d_q, const int3
         if (hipSetDevice(e->device()) != hipSuccess) { fprintf(stderr, "%s: hipSetDevice failed\n", me); return -3; }
         MaxsimArgs a{(const half_t *)d_q, (const half_t *)d_d, d_qcu, d_dcu, d_pairs, d_scores, n_q, n_d, H, d_pairs ? n_pairs : 0, mode};
         const hipStream_t s = (hipStream_t)stream;
+        // (no workspace, so no event: the call only asks whether s may take the launch — not a capturing stream while the context profiles)
+        Engine::StreamOp op;
+        std::string err;
+        if (!e->op_begin(s, nullptr, op, err)) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return -3; }
         // (flops: unknown without the lengths, which live on the device)
         e->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(a, s); });
         if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: the launch failed\n", me); return -3; }

@@ -65,8 +65,10 @@ BERT_API int32_t bert_hip_eval_packed_gather(struct bert_ctx *ctx, const bert_vo
  * enqueued on `stream` and NOT synchronised (the caller owns the stream).  `max_len` must be >=
  * the longest sentence (it selects and sizes the attention kernels); n_tokens_total = cu[n].
  * Rules of the asynchronous entry point:
- *   - a context has ONE workspace: a forward pass waits (on its own stream, hipStreamWaitEvent) for the previous pass
- *     of the context, whatever stream that ran on — passes never overlap, callers need no extra ordering;
+ *   - a context has ONE workspace: an eagerly enqueued forward pass waits (on its own stream, hipStreamWaitEvent) for the
+ *     previous eagerly enqueued pass of the context, whatever stream that ran on — eager passes never overlap and need no
+ *     extra ordering.  A pass that runs as part of a graph launch is outside this rule: the caller orders it (STREAM CAPTURE
+ *     AND GRAPHS below);
  *   - the workspace grows on demand, and growing allocates (synchronises the device, illegal under stream capture):
  *     call bert_hip_reserve once with the largest batch first;
  *   - lengths are validated on the device: a sentence longer than max_len (or empty) yields a NaN embedding and sets a
@@ -84,6 +86,36 @@ BERT_API int32_t bert_hip_eval_packed_device(struct bert_ctx *ctx, const bert_vo
 BERT_API int32_t bert_hip_reserve(struct bert_ctx *ctx, int32_t n_tokens, int32_t n_sentences);
 BERT_API int32_t bert_hip_check(struct bert_ctx *ctx);        /* 0 ok, 1 a batch broke its max_len promise, < 0 error */
 
+/* STREAM CAPTURE AND GRAPHS.  Every *_device entry point of this header may be called on a stream that is capturing (hipStreamBeginCapture;
+ * a capture on ONE stream), provided the call does not have to allocate: size the context with bert_hip_reserve and an index with
+ * bert_hip_index_reserve, and call once eagerly at the largest shape where an entry says that those two do not cover its buffer (grouped
+ * pooling, rescore, the probed and the two-stage searches).  The captured call returns 0 and runs nothing; the graph holds its launches,
+ * all of them on the caller's stream.
+ *   A graph bakes in what the host knew at capture: n_sentences, n_tokens_total and max_len; the route and every option the pass read
+ *   ("pooling", "normalize", the kernel switches, "window_slots"); n_queries, k, nprobe, n_cand and n_words; the index's row count, its
+ *   partition and its storage pointers; the workspace pointers of the context and of the index.  None of these can change between
+ *   replays.  So whatever grows, moves or frees that memory invalidates the graph, and launching it afterwards reads freed memory:
+ *   bert_hip_reserve or an eager call beyond the reserved size, bert_hip_index_reserve, an add beyond the capacity, compact, partition,
+ *   bert_hip_index_free, bert_free.  An add within the capacity keeps the graph valid, but the graph goes on searching the rows it was
+ *   captured with.
+ *   What may change between replays is the CONTENTS of the caller's device buffers: ids, cu_seqlens and group_cu (the lengths are read on
+ *   the device: any lengths with the same n_sentences and the same sum; the max_len guard and bert_hip_check work as in an eager call),
+ *   queries, allow-list bits, candidate ids, token rows, pairs.  A replay gives the bits of the eager call on the same buffers.
+ *   bert_hip_index_add_device under capture returns the first id and grows size WHEN IT IS CAPTURED, not when the graph runs; every launch
+ *   converts what d_rows holds then into those same rows (a second launch overwrites them, it does not append).  A search captured behind
+ *   it in the same capture sees them; before the first launch those rows are undefined.
+ *   Ordering.  The one-event rule (one pass of a context, one operation of an index at a time, whatever the streams) orders EAGER calls
+ *   only: a captured call neither waits for the event nor records it — an event recorded inside a capture belongs to that capture, and a
+ *   replay would record nothing anyway.  Inside one capture the stream orders the operations.  The caller orders every graph launch against
+ *   every other use of the same context or index: eager calls on other streams, the host entry points (which run on streams of the
+ *   context's own), other graphs.
+ *   Profiling and capture exclude each other: while bert_hip_profile_enable is on, a *_device call on a capturing stream returns -3 after
+ *   one line on stderr and enqueues nothing; the capture stays valid.
+ *   A call that has to allocate under capture fails with -3 (hipMalloc: hipErrorStreamCaptureUnsupported) and the runtime invalidates the
+ *   capture: hipStreamEndCapture returns hipErrorStreamCaptureInvalidated and no graph.  The context and its indexes are unharmed — reserve,
+ *   then capture again —, but on the ROCm 7.2 runtime the stream of the broken capture stays invalidated even after hipStreamEndCapture
+ *   (every later launch on it fails): destroy it and capture on a new one.                                                              */
+
 /* Hidden-state tap for parity tests: one sentence, writes hidden[(n_layer+1)][n_tokens][n_embd]
  * f32 (after the embedding LayerNorm and after every encoder layer, reference bert.cpp:806-901)
  * and the final embedding.  Either output may be NULL.  The tap needs every layer's normalised states, so it takes neither the
@@ -96,7 +128,8 @@ BERT_API int32_t bert_hip_eval_hidden(struct bert_ctx *ctx, const bert_vocab_id 
  * the forward pass carries an event pair (hipExtLaunchKernelGGL start / stop events: a timed launch runs behind system-scope
  * fences and reads up to 8 % long for sub-millisecond kernels, so never enable it inside a throughput measurement).  bert_hip_profile_report writes one line per
  * kernel: "<name> <launches> <total_ms> <flops_per_launch_avg>\n" and returns the number of bytes
- * it needed (excluding NUL); it synchronises the device first and resets the counters.  Behind the kernels it lists which
+ * it needed (excluding NUL); it synchronises the device first and resets the counters.  While enabled, calls on a capturing stream are
+ * refused (STREAM CAPTURE AND GRAPHS above).  Behind the kernels it lists which
  * mat-mul kernel family served the weight GEMMs of the pass: "family:gemm256_f16" / "family:gemm256_q4" (256 x 256 tiles, f16
  * image / 4-bit planes dequantised in the tile load), "family:gemm_mfma_f16" / "_q4" (128 x 128 tiles), "family:gemm_naive",
  * each "<name> <launches> 0 0".  With bert_hip_set_option("profile_replay", "<kernel>:<K>") a pass runs untimed and the
@@ -330,8 +363,8 @@ BERT_API int32_t bert_hip_maxsim(struct bert_ctx *ctx, const float *q, const int
  *   - 1 <= k <= 256, anything else is an error; n_queries == 0 is a successful no-op; large n_queries run in internal chunks.
  *   - a row's score for a query has the same bits whatever the other queries of the call, the number of add calls that built
  *     the index, reserved or grown storage, k (top-10 is the first 10 entries of top-100), and host or device entry point.
- *   - *_device calls are asynchronous on the caller's stream; an index has ONE event, so its operations never overlap,
- *     whatever streams they were enqueued on.
+ *   - *_device calls are asynchronous on the caller's stream; an index has ONE event, so its eagerly enqueued operations never
+ *     overlap, whatever streams they were enqueued on.  Captured calls and graph launches: STREAM CAPTURE AND GRAPHS above.
  * Removing rows, filtered search, compaction, files:
  *   remove   marks rows as deleted.  Ids are stable: the other rows keep theirs, new rows still get size, size + 1, ... (size
  *            counts removed rows too).  A removed row is never returned by any search (search, search_device, search_texts
