@@ -124,6 +124,7 @@ private:
         Route route = Route::LAYERED;
         bool build_windows = false;   // launch_build_windows ahead of the route, its count in n_windows_dev (n_windows: a bound)
         const int *n_windows_dev = nullptr;
+        bool embed_lanes = false;     // ONE_LAUNCH on full windows: the embedding kernel writes y_ in lane order, x_ is not written (model_kernel.hip)
         std::vector<LayerPlan> layers;
     };
     Plan plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s, float *d_hidden,

@@ -145,8 +145,14 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     if (p.route == Route::F32) ok = forward_f32(p, err);
     else {
         const int H = hp_.n_embd;
-        timed("embed_ln", 0.0, s, [&] { launch_embed_ln(w_->word_emb.p, w_->type_emb.p, w_->pos_emb.p, w_->table_type, w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(),
-                                                        d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, x_.as<half_t>(), s); });
+        // (the one-launch kernel's full form: the same values in lane order in y_, no rows — plan() asked the launcher's own rule)
+        if (p.embed_lanes)
+            timed("embed_ln", 0.0, s, [&] { ok = launch_embed_ln_lanes(w_->word_emb.p, w_->type_emb.p, w_->pos_emb.p, w_->table_type, w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(),
+                                                                       d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, y_.as<half_t>(), s); });
+        else
+            timed("embed_ln", 0.0, s, [&] { launch_embed_ln(w_->word_emb.p, w_->type_emb.p, w_->pos_emb.p, w_->table_type, w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(),
+                                                            d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, x_.as<half_t>(), s); });
+        if (!ok) { err = "embed_ln: no lane-order kernel for this shape"; return -1; }
         tap(p, 0);
         if (p.build_windows)
             timed("build_windows", 0.0, s, [&] { launch_build_windows(d_cu, B, windows_.as<int2>(), status_.as<int>() + 1, slots, s); });
@@ -209,6 +215,9 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
     // (max_len-sized places) gives the same windows without the extra launch.  (Forced one-launch: the kernel takes a window list
     // or one sentence per window — its layer-tail phase needs a window's tokens to be at most 128 whatever the sentences' lengths.)
     const bool full_windows = (long long)B * 128 == T;
+    // (the one-launch kernel's full form starts from the embedding in lane order and reads no rows: a batch of that shape whose tables the
+    // lane-order embedding kernel does not take leaves the route)
+    if (full_windows && !embed_ln_lanes_supported(w_->table_type, H, T, max_len)) one_launch = false;
     const int spw = qkv_attention2_sentences_per_window(max_len, slots);
     if (!d_windows && fused_windows &&
         (4ll * ((B + spw - 1) / spw) * 128 > 5 * ((long long)T + (long long)(slots / 2) * B) || (one_launch && opt_.one_launch == 2 && spw > 1 && !full_windows))) {
@@ -228,6 +237,9 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
     const bool skinny = latency_call && opt_.tail && opt_.qkv2 && !opt_.gemm_naive && !opt_.attn_naive && max_len <= 128 && (dh == 32 || dh == 64) &&
                         skinny_layer_supported(L0.qkv.w, L0.o.w, L0.ffi.w, L0.ffo.w) && qkv2_shape0;
     p.route = skinny ? Route::LATENCY : one_launch && one_launch_pays ? Route::ONE_LAUNCH : fold ? Route::FOLDED : Route::LAYERED;
+    // (launch_model_kernel takes its full form by the same rule; neither a tap nor token rows reach this route, nothing else reads x_ on it
+    // before the kernel's last layer has written it)
+    p.embed_lanes = p.route == Route::ONE_LAUNCH && full_windows;
     return p;
 }
 

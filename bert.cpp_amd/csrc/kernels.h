@@ -88,8 +88,9 @@ struct ModelLayerWeights {
 };
 bool model_kernel_supported(const GemmWeight &Wqkv, const GemmWeight &Wo, const GemmWeight &W1, const GemmWeight &W2, int n_layer,
                             int n_head, int d_head, int max_len);
-// x: in = embeddings + LayerNorm, out = the last layer's output; ctx: workspace [T][H] (the ragged form's); xres: workspace [T][H] (full
-// windows: the residual between the layers' tails in lane order; no other route's data survives in it).  groups / n_groups / n_groups_dev: the
+// x: in = embeddings + LayerNorm (the ragged form; the full form reads none), out = the last layer's output; ctx: workspace [T][H] (the
+// ragged form's); xres: workspace [T][H] (full windows: in = embeddings + LayerNorm in lane order, launch_embed_ln_lanes; then the residual
+// between the layers' tails in the same order; no other route's data survives in it).  groups / n_groups / n_groups_dev: the
 // window list as for launch_qkv_attention2 (nullptr: one sentence per window); n_tokens = 128 n_sentences selects the form
 // specialised for full windows.  pooled != nullptr: the workgroups also pool and normalise their sentences (launch_pool_normalize's
 // arguments and bits: [n_sentences][H] f32, max_len, status word, pool_mode).
@@ -117,6 +118,14 @@ void launch_gemm_naive(const GemmWeight &W, const half_t *A, const float *bias, 
 void launch_embed_ln(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
                      const float *beta, const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int T,
                      int H, int n_vocab, int max_len, half_t *out, hipStream_t stream);
+// The same values in LANE ORDER, for launch_model_kernel's full-window form, which starts from them in `xres` and reads no rows: block k
+// (tokens 32 k .. 32 k + 31) is the 32 H halves from 32 k H on, fragment q < H / 16 its KiB q, lane l = 32 hi + l31 owns 16 bytes at 16 l
+// of it: features 16 q + 4 hi + {0..3}, then 16 q + 8 + 4 hi + {0..3} of token 32 k + l31 (layer_tail.hip's XRES layout).  Its shapes:
+// T a positive multiple of 128, H = 256 or 384, table types 0..3, max_len >= 1; any other is refused — false, nothing launched.
+bool embed_ln_lanes_supported(int table_type, int H, int T, int max_len);
+bool launch_embed_ln_lanes(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
+                           const float *beta, const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int T,
+                           int H, int n_vocab, int max_len, half_t *xres, hipStream_t stream);
 
 // In-place LayerNorm over H of f16 rows (eps 1e-5), gamma/beta f32.
 void launch_layernorm(half_t *x, const float *gamma, const float *beta, int T, int H, hipStream_t stream);

@@ -148,13 +148,14 @@ __device__ __forceinline__ f32x16 mfma16(const f16x8 &a, const f16x8 &b, const f
 // ((2 n + s) 64 + l) 16 of the block.  Those are the halves the next tail's prologue wants in the same lane as its residual, for both roles:
 // xv[b][2 s] | xv[b][2 s + 1] of role r = fragment (4 (b >> 1) + 2 r + (b & 1), s).  So D stores its fragments straight from registers (no
 // staging in LDS, no transposition, none of the two barriers around it, no store loop in either role) and the next prologue loads 4 NT
-// fragments where it loaded 8 NT quarter rows: contiguous 1 KiB wave-instructions on both sides.  `lane_in` / `lane_out` (wave-uniform,
-// the same for every wave of the workgroup: both roles drop the same barriers) say which order this call reads and writes; a form
-// compiled without XRES_IN / XRES_OUT ignores them, and a.x / a.out are untouched by a side that runs in lane order.
+// fragments where it loaded 8 NT quarter rows: contiguous 1 KiB wave-instructions on both sides.  XRES_IN reads lane order ALWAYS — the
+// first layer's residual too: the embedding kernel writes `xres` in this order for the route (misc_kernels.hip embed_ln_lanes_kernel) and
+// a.x is not read.  `lane_out` (wave-uniform, the same for every wave of the workgroup: both roles drop the same barriers) says which
+// order this call writes; a form compiled without XRES_OUT ignores it, and a.out is untouched by a call that writes lane order.
 template <int NT, int WT, bool RAGGED, bool HANDOVER, bool CTXREGS = false, bool XRES_IN = false, bool XRES_OUT = false>
 __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, const int tok0, const int rows, const int tid,
                                                 [[maybe_unused]] f16x8 (&xnext)[8 * NT], [[maybe_unused]] const f16x8 *cf = nullptr,
-                                                [[maybe_unused]] half_t *xres = nullptr, const bool lane_in = false, const bool lane_out = false) {
+                                                [[maybe_unused]] half_t *xres = nullptr, const bool lane_out = false) {
     static_assert(!(HANDOVER && RAGGED), "a ragged window's rows are packed: its lanes are not the window phase's slots");
     static_assert(!(CTXREGS && RAGGED), "a ragged window's rows are packed: its lanes are not the attention waves' queries");
     static_assert(!((XRES_IN || XRES_OUT) && (RAGGED || WT != GW_F16)), "lane order: full windows (a pair owns its 32 rows), f16 weights");
@@ -208,27 +209,10 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
     f32x16 accp[NBH];
     f16x4 xv[NBH][4];
     if constexpr (XRES_IN) {
-        // Lane order: the fragments D stored a layer ago, own features only.  A call that gets rows (the first layer: the embedding
-        // kernel's) takes them to the scratch itself first — this wave's quarter rows as the fragments this wave loads below, same lanes, so
-        // nobody else's stores are waited for — and then reads them like every other layer: ONE sequence of loads into xv.  (With the two
-        // orders as the arms of a branch that both define xv, model_kernel<3, false> keeps one register too few through the out-projection
-        // and reloads a context fragment from scratch inside two of its intervals.)  One more round trip to the L2 per launch.
+        // Lane order: own features only of the fragments the tail before stored — or, for the first layer, the embedding kernel
+        // (embed_ln_lanes_kernel writes this order itself): ONE sequence of loads into xv for every layer, 4 NT contiguous KiB per wave.
         char *const xb = (char *)(xres + (size_t)tok_w * H);     // (scalar base + the lane's 32-bit offset: no 64-bit address per lane)
         const unsigned xl = (unsigned)lane * 16u;
-        if (!lane_in) {
-            const half_t *xr = a.x + (size_t)row_l * H + role * 64 + 4 * hi;
-#pragma unroll
-            for (int b = 0; b < NBH; ++b)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const f16x4 lo = *(const f16x4 *)(xr + (b >> 1) * 128 + (b & 1) * 32 + 16 * s), up = *(const f16x4 *)(xr + (b >> 1) * 128 + (b & 1) * 32 + 16 * s + 8);
-                    f16x8 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { v[e] = lo[e]; v[4 + e] = up[e]; }
-                    *(f16x8 *)(xb + (2 * (4 * (b >> 1) + 2 * role + (b & 1)) + s) * 1024 + xl) = v;
-                }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the loads below: behind this wave's own stores)
-        }
 #pragma unroll
         for (int b = 0; b < NBH; ++b)
 #pragma unroll
@@ -400,13 +384,21 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
     __builtin_amdgcn_s_waitcnt(0xc07f);                       // lgkmcnt(0), visible to the compiler (see the note in U's branch)
     static_for<P>([&](auto p_tag) __attribute__((always_inline)) {
         constexpr int p = decltype(p_tag)::value, n3 = p / NT, q = p % NT, p2 = p + 2;
-        const unsigned bA = aR + (unsigned)(slot * LT_TILE + role * 8192), bB = bA + 3 * LT_TILE;
+        // (XRES_IN — model_kernel's full form, which has no register to spare here: ringD's tile through ringU's four lane addresses, its
+        // 48 KiB in the instruction offset, where the other forms keep four addresses of its own)
+        constexpr int OB = XRES_IN ? 3 * LT_TILE : 0;
+        const unsigned bA = aR + (unsigned)(slot * LT_TILE + role * 8192), bB = bA + (3 * LT_TILE - OB);
         f16x8 Fa[4], Fb[4];
         // group = two k-steps x the wave's two row blocks
         auto rd = [&](unsigned base, int g2, f16x8 (&F)[4]) __attribute__((always_inline)) {
             const unsigned a0 = base ^ (unsigned)((2 * g2) << 5), a1 = base ^ (unsigned)((2 * g2 + 1) << 5);
             F[0] = frag_read<0>(a0); F[1] = frag_read<4096>(a0);
             F[2] = frag_read<0>(a1); F[3] = frag_read<4096>(a1);
+        };
+        auto rdB = [&](int g2, f16x8 (&F)[4]) __attribute__((always_inline)) {
+            const unsigned a0 = bB ^ (unsigned)((2 * g2) << 5), a1 = bB ^ (unsigned)((2 * g2 + 1) << 5);
+            F[0] = frag_read<OB>(a0); F[1] = frag_read<OB + 4096>(a0);
+            F[2] = frag_read<OB>(a1); F[3] = frag_read<OB + 4096>(a1);
         };
         auto mm = [&](f16x8 (&F)[4], int ks) __attribute__((always_inline)) {      // ks = first ctx k-step of the group
             accp[n3 * 2 + 0] = mfma16(F[0], bf[ks], accp[n3 * 2 + 0]);
@@ -452,7 +444,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
             bf[NQ - 4] = lds_read_b128<true, 0>(aEdge);
             bf[NQ - 3] = lds_read_b128<true, 1024>(aEdge);
         }
-        rd(bB, 0, Fa);
+        rdB(0, Fa);
         wait_frags<4>(Fb);
         if constexpr (CTX_LATE && q == NT - 1) { landed(bf[NQ - 4]); landed(bf[NQ - 3]); }
         mm(Fb, 8 * q + 2);
@@ -461,7 +453,7 @@ __device__ __forceinline__ void layer_tail_body(const TailArgs &a, char *smem, c
             bf[NQ - 2] = lds_read_b128<true, 2048>(aEdge);
             bf[NQ - 1] = lds_read_b128<true, 3072>(aEdge);
         }
-        rd(bB, 1, Fb);
+        rdB(1, Fb);
         if constexpr (Q4) { q4_turn(); __builtin_amdgcn_sched_barrier(0); }
         wait_frags<4 + QW>(Fa);
         mm(Fa, 8 * q + 4);

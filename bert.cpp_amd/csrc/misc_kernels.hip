@@ -232,6 +232,98 @@ void launch_embed_ln(const void *word, const void *type, const void *pos, int ta
 #undef EMB
 }
 
+// The rows kernel's values in LANE ORDER (kernels.h launch_embed_ln_lanes; layer_tail.hip's XRES layout), for model_kernel's full-window
+// form: H = 128 NT, T a multiple of 128.  Per token nothing differs from embed_ln_rows_kernel<TT, 1, *> — one wave, lane c owns features
+// 8 c .. 8 c + 7, the same sums in the same order, the same clamps: the same bits — but where the 16 bytes go.  A workgroup is a 32-token
+// block (8 waves x 4 tokens).  A lane's run of 8 is the halves of two lanes of fragment c >> 1: features 8 c + {0..3} are bytes
+// 8 (c & 1) .. of lane (l31, 0), features 8 c + 4 + {0..3} the same bytes of lane (l31, 1).  Stored from registers that would be 8-byte
+// scatters; so the block is staged in LDS in fragment order (a KiB + 16 bytes apart: the 8-byte writes of a half wave then fall into
+// 32 different bank pairs) and leaves as whole 1 KiB wave-instructions, 16 bytes per lane.
+// Sentence and position: block k lies in the 128-token block b = k / 4.  Where sentence b IS that block (cu[b] = 128 b, cu[b + 1] =
+// 128 b + 128: every block of a batch of full sentences) the position is t % 128; any other batch of this T — full only by the sum of
+// its lengths — bisects cu_seqlens like the SEARCH form, on scalar loads.
+template <int TT, int NT>
+__global__ __launch_bounds__(512) void embed_ln_lanes_kernel(const void *word, const void *type, const void *pos,
+                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                             const int32_t *__restrict__ tokens,
+                                                             const int32_t *__restrict__ cu_seqlens, int n_sentences, int H,
+                                                             int n_vocab, int max_len, half_t *__restrict__ xres) {
+    constexpr int NQ = 8 * NT, FS = 1024 + 16;                // fragments of a block; bytes from one to the next in LDS
+    __shared__ __attribute__((aligned(16))) char S[NQ * FS];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tok0 = blockIdx.x * 32, b = tok0 >> 7;
+    const bool whole = b < n_sentences && cu_seqlens[b] == 128 * b && cu_seqlens[b + 1] == 128 * b + 128;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int l31 = wave * 4 + i, t = tok0 + l31;
+        int p = t & 127;
+        if (!whole) {
+            int lo = 0, hi = n_sentences;                     // largest b with cu[b] <= t
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (cu_seqlens[mid] <= t) lo = mid; else hi = mid;
+            }
+            p = t - cu_seqlens[lo];
+        }
+        p = min(p, max_len - 1);                              // (the position row; t is settled)
+        int id = tokens[t];
+        id = id < 0 ? 0 : (id >= n_vocab ? n_vocab - 1 : id);   // ids are validated on the host API; clamp for safety
+        const int e0 = 8 * lane;
+        float v[8];
+        float sum = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = 0.f;
+        if (e0 < H) {
+            float w[8], ty[8], ps[8];
+            table_run8<TT>(word, H, id, e0, w);
+            table_run8<TT>(type, H, 0, e0, ty);
+            table_run8<TT>(pos, H, p, e0, ps);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { v[k] = ps[k] + (ty[k] + w[k]); sum += v[k]; }
+        }
+        const float mean = wave_sum_f32(sum) / H;
+        float sq = 0.f;
+        if (e0 < H)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { v[k] -= mean; sq += v[k] * v[k]; }
+        const float rstd = 1.0f / sqrtf(wave_sum_f32(sq) / H + 1e-5f);
+        if (e0 < H) {
+            const float4 g0 = *(const float4 *)(gamma + e0), g1 = *(const float4 *)(gamma + e0 + 4);
+            const float4 b0 = *(const float4 *)(beta + e0), b1 = *(const float4 *)(beta + e0 + 4);
+            const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+            const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+            f16x8 o;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) o[k] = (_Float16)(gg[k] * (v[k] * rstd) + bb[k]);
+            char *const d = S + (lane >> 1) * FS + 8 * (lane & 1) + 16 * l31;
+            *(f16x4 *)d = f16x4{o[0], o[1], o[2], o[3]};
+            *(f16x4 *)(d + 16 * 32) = f16x4{o[4], o[5], o[6], o[7]};
+        }
+    }
+    __syncthreads();
+    char *const out = (char *)(xres + (size_t)tok0 * H);
+#pragma unroll
+    for (int q = wave; q < NQ; q += 8) *(f16x8 *)(out + q * 1024 + lane * 16) = *(const f16x8 *)(S + q * FS + lane * 16);
+}
+
+bool embed_ln_lanes_supported(int table_type, int H, int T, int max_len) {
+    return T > 0 && T % 128 == 0 && (H == 256 || H == 384) && table_type >= 0 && table_type <= 3 && max_len > 0;
+}
+
+bool launch_embed_ln_lanes(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
+                           const float *beta, const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int T,
+                           int H, int n_vocab, int max_len, half_t *xres, hipStream_t stream) {
+    if (!embed_ln_lanes_supported(table_type, H, T, max_len) || n_sentences <= 0) return false;
+#define EMBL(TT) do { \
+        if (H == 256) BERT_LAUNCH((embed_ln_lanes_kernel<TT, 2>), dim3(T / 32), dim3(512), 0, stream, word, type, pos, gamma, beta, tokens, \
+                                  cu_seqlens, n_sentences, H, n_vocab, max_len, xres); \
+        else BERT_LAUNCH((embed_ln_lanes_kernel<TT, 3>), dim3(T / 32), dim3(512), 0, stream, word, type, pos, gamma, beta, tokens, \
+                         cu_seqlens, n_sentences, H, n_vocab, max_len, xres); } while (0)
+    if (table_type == 0) EMBL(0); else if (table_type == 1) EMBL(1); else if (table_type == 2) EMBL(2); else EMBL(3);
+#undef EMBL
+    return true;
+}
+
 // reference bert.cpp:868-874 / :894-900 (ggml_norm + gamma/beta), in place on f16 rows.
 // NJ = pairs per lane held in registers (H <= 128 * NJ).
 template <int NJ>

@@ -14,7 +14,8 @@
 // workgroup's waves: no invalidate needed outside threadgroup-split mode); on full windows x ALSO crosses in registers and ctx crosses
 // ONLY on chip, in registers and through LDS (the layer loop below), so neither phase waits for a round trip of its own data, and no ctx
 // is stored at all; what the next tail needs of x as its residual crosses through a scratch workspace in LANE ORDER (LayerNorm 2's
-// result fragments as they are: the layer loop below), so the full form stores rows of x after its last layer only.  The global
+// result fragments as they are: the layer loop below), so the full form stores rows of x after its last layer only — and loads none
+// before: its embedding kernel writes that workspace in lane order for layer 0 (embed_ln_lanes_kernel, misc_kernels.hip).  The global
 // hand-overs (the ragged form's both, the full form's residual fragments) do NOT stay inside the XCD's L2: 256
 // workgroups x 192 KiB = 48 MiB per layer against 32 MiB of L2, and every store leaves the L2 towards the fabric anyway —
 // measured 313 MB written and 1.06 GB of fabric traffic per launch with both edges through memory (profiles/r3_pmc.txt), 164 MB and
@@ -53,7 +54,7 @@ struct ModelLayerArgs {              // what differs from layer to layer
     const float *bqkv, *bo, *g1, *be1, *b1, *b2, *g2, *be2;
 };
 struct ModelArgs {
-    half_t *x, *ctx;                 // [T][H] hidden state (in: embeddings + LN; out: the last layer's output), attention context
+    half_t *x, *ctx;                 // [T][H] hidden state (RAGGED in: embeddings + LN; out: the last layer's output), attention context
     const int32_t *cu;
     const int2 *groups;              // RAGGED: per window {first sentence, count} (qkv_attention2.hip), or nullptr: one sentence per window
     const int *n_groups;             // RAGGED: device word holding the number of windows (the grid is an upper bound), or nullptr
@@ -62,8 +63,8 @@ struct ModelArgs {
     int *status;                     // pooling's status word (a sentence outside [1, max_len])
     int max_len, pool_mode;          // pool_mode: kernels.h POOL_CLS | POOL_RAW, read by the epilogue alone (POOL_MODES forms)
     ModelLayerArgs layer[MODEL_MAX_LAYERS];
-    half_t *xres;                    // FULL windows: [T][H] scratch, the residual x between two tails in lane order (layer_tail_body's XRES_IN /
-                                     // XRES_OUT); behind everything else: the ragged form, which ignores it, finds its arguments where they were
+    half_t *xres;                    // FULL windows: [T][H] in lane order (layer_tail_body's XRES_IN / XRES_OUT) — in: embeddings + LN, then the
+                                     // residual x between two tails; behind everything else: the ragged form, which ignores it, finds its arguments where they were
 };
 
 }  // namespace
@@ -105,22 +106,24 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
     const int n_layer = rows > 0 ? m.n_layer : 0;    // (a window of empty sentences: nothing to compute, NaN rows from the pooling below)
     // A phase = the kernel's body on this workgroup's window.  Full windows (!RAGGED) tell the window phase so (FULL: its slots are the
     // block's tokens, no look at cu) and, from the second layer on, hand it the hidden state in registers (XREGS / HANDOVER below).
-    auto window_phase = [&](const ModelLayerArgs &L, auto xregs_tag, const f16x8 *xf, f16x8 *cf) __attribute__((always_inline)) {
+    // The first layer has nobody's registers to start from: its window phase takes the same fragments from m.xres, where the embedding kernel
+    // wrote the hidden state in lane order (XLANES: xf == nullptr in the full form).
+    auto window_phase = [&](const ModelLayerArgs &L, auto first_tag, const f16x8 *xf, f16x8 *cf) __attribute__((always_inline)) {
         const int tid = thread_id();
         Qkv2Args q;
         q.x = m.x; q.w = L.wqkv; q.qs = nullptr; q.sc = nullptr; q.bias = L.bqkv; q.cu = m.cu; q.groups = RAGGED ? m.groups : nullptr; q.n_groups = nullptr;
         q.out = m.ctx; q.n_head = m.n_head; q.n_sent = m.n_sent; q.spw = 1; q.slot_mask = m.slot_mask;
-        qkv_attention2_body<2 * NT, NT, GW_F16, !RAGGED, decltype(xregs_tag)::value, !RAGGED>(q, smem, window, tid, xf, cf);
+        constexpr bool FIRST = decltype(first_tag)::value;
+        qkv_attention2_body<2 * NT, NT, GW_F16, !RAGGED, !RAGGED, !RAGGED, !RAGGED && FIRST>(q, smem, window, tid, xf, cf, RAGGED ? nullptr : m.xres);
     };
-    auto tail_phase = [&](const ModelLayerArgs &L, f16x8 (&xf)[8 * NT], const f16x8 *cf, [[maybe_unused]] const bool lane_in,
-                          [[maybe_unused]] const bool lane_out) __attribute__((always_inline)) {
+    auto tail_phase = [&](const ModelLayerArgs &L, f16x8 (&xf)[8 * NT], const f16x8 *cf, [[maybe_unused]] const bool lane_out) __attribute__((always_inline)) {
         const int tid = thread_id();
         TailArgs t;
         t.ctx = m.ctx; t.x = m.x; t.wo = L.wo; t.w1p = L.w1p; t.w2p = L.w2p;
         t.wo_qs = t.w1_qs = t.w2_qs = nullptr; t.wo_sc = t.w1_sc = t.w2_sc = nullptr;
         t.bo = L.bo; t.g1 = L.g1; t.be1 = L.be1; t.b1 = L.b1; t.b2 = L.b2; t.g2 = L.g2; t.be2 = L.be2; t.out = m.x; t.I = m.I;
         if constexpr (RAGGED) layer_tail_body<NT, GW_F16, true, false, false>(t, smem, tok0, rows, tid, xf, cf);
-        else layer_tail_body<NT, GW_F16, false, true, true, true, true>(t, smem, tok0, rows, tid, xf, cf, m.xres, lane_in, lane_out);
+        else layer_tail_body<NT, GW_F16, false, true, true, true, true>(t, smem, tok0, rows, tid, xf, cf, m.xres, lane_out);
     };
     // Phase edge: everything the phase stored (ragged windows: ctx by the attention waves; x by all waves) is visible to the workgroup, every
     // LDS access of the phase has returned (the next phase's first DMA pieces overwrite what the others were reading).  On full windows
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
             window_phase(m.layer[l], std::false_type{}, nullptr, nullptr);
             hand_over();
             MK_STAMP(1 + 2 * l);
-            tail_phase(m.layer[l], none, nullptr, false, false);
+            tail_phase(m.layer[l], none, nullptr, false);
             hand_over();
             MK_STAMP(2 + 2 * l);
         }
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
         // Full windows: the tail's D waves 4..7 end with the rows of x they have just normalised in registers, and the same waves, as
         // the next layer's projection waves, start from those rows — same lanes, same tokens, the f16 values that are stored: LayerNorm 2
         // hands them over as operand fragments (layer_tail_body's HANDOVER) and the window phases of layers 1 .. L-1 load no x at all
-        // (the residual of the next tail and the pooling still read what is stored: below).  The loop is rotated — layer 0's window phase in front,
+        // (the residual of the next tail and the pooling still read what is stored: below; layer 0's load theirs from m.xres).  The loop is rotated — layer 0's window phase in front,
         // then tail(l) -> window(l + 1) per turn — so that the fragments are born and consumed inside ONE turn: declared outside, the
         // U waves' path (which does not write them) would carry 96 registers round the loop and through the tail.
         //
@@ -171,20 +174,23 @@ __global__ __launch_bounds__(512, 2) void model_kernel(ModelArgs m) {
         // The residual x of tail(l + 1) is what LayerNorm 2 of tail(l) wrote, and only this workgroup reads it before the pooling: between two
         // tails it crosses in LANE ORDER through m.xres (layer_tail_body's XRES_IN / XRES_OUT: D's result fragments as they are, 1 KiB per
         // wave-instruction on both sides, no staging in LDS, no barriers around it, no row stores), behind the same two phase edges as before.
-        //     layer 0:          rows in (the embedding kernel's m.x), lane order out
-        //     layers 1 .. L-2:  lane order in and out: m.x is neither read nor written
-        //     layer L-1:        lane order in, rows out (the pooling below and the caller read m.x); L = 1: rows in and out
-        // Every fragment a tail loads was stored by the tail before it in the same launch (tests: the scratch poisoned with NaNs).
+        //     layers 0 .. L-2:  lane order in and out: m.x is neither read nor written
+        //     layer L-1:        lane order in, rows out (the pooling below and the caller read m.x); L = 1 is this line alone
+        // Layer 0 is a layer like the others: the embedding kernel of this route (misc_kernels.hip embed_ln_lanes_kernel) writes the hidden
+        // state into m.xres in lane order and no rows at all, tail 0 loads its residual like every tail, and window phase 0 starts from the
+        // same fragments (qkv_attention2_body's XLANES: 8 NT contiguous KiB per projection wave instead of 8 NT row-major fragments).  So the
+        // full form reads NO m.x before its last tail has written it.  Every fragment a tail loads was stored in the same pass, by the
+        // embedding kernel or by the tail before it in this launch (tests: x, the scratch and everything else poisoned with NaNs).
         f16x8 cf[8 * NT];
-        if (n_layer > 0) window_phase(m.layer[0], std::false_type{}, nullptr, cf);
+        if (n_layer > 0) window_phase(m.layer[0], std::true_type{}, nullptr, cf);
         for (int l = 0; l < n_layer; ++l) {
             hand_over();
             MK_STAMP(1 + 2 * l);
             f16x8 xf[8 * NT];
-            tail_phase(m.layer[l], xf, cf, l > 0, l + 1 < n_layer);
+            tail_phase(m.layer[l], xf, cf, l + 1 < n_layer);
             hand_over();
             MK_STAMP(2 + 2 * l);
-            if (l + 1 < n_layer) window_phase(m.layer[l + 1], std::true_type{}, xf, cf);
+            if (l + 1 < n_layer) window_phase(m.layer[l + 1], std::false_type{}, xf, cf);
             else {
 #pragma unroll
                 for (int q = 0; q < 8 * NT; ++q) asm volatile("" : "=v"(cf[q]));

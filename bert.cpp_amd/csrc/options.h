@@ -42,7 +42,8 @@ private:
 
 // "test_poison_ctx" (libbert_test.so only; false, doing nothing, in libbert.so): every half of the attention-context workspace
 // becomes a NaN, so a pass that still reads what it has not written itself shows it in its results.  "test_poison_xres": the same for the
-// workspace through which the one-launch kernel's full form passes the residual between its layers (the engine's y rows).
+// workspace the one-launch kernel's full form starts from and passes the residual between its layers through (the engine's y rows: the
+// pass's embedding kernel writes them first, in lane order).
 // "test_poison_workspace": the same for every activation scratch buffer of the engine at once (`workspace`: x, qkv, ctx, y, the
 // intermediate, the latency route's f32 rows, the LayerNorm fold's partial statistics and finalized rows, the hidden-state tap's
 // rows; f32 words on the f32 route, where 0xFF bytes are a NaN as well) — a pass may depend on nothing it finds in any of them:

@@ -104,11 +104,18 @@ __device__ __forceinline__ void q2_wait0_bias(f16x8 (&f)[2][3], f32x4 (&bq)[4], 
 // (4 + a: the tail's D wave of the pair) ends with the same fragments.  All but the last two heads' four: those wait for both waves in LDS
 // (ctx_edge_offset; the attention wave has no registers for them beside the last head's attention), so every wave leaves with
 // cf[0 .. 4 KT - 5] written (LDS map of the edge: model_kernel.hip).
-template <int KT, int GB, int WT, bool FULL = false, bool XREGS = false, bool CTXREGS = false>
+// XLANES (with XREGS: the first layer of model_kernel.hip's full form): nobody has the fragments in registers yet.  The projection wave
+// takes them from `xlanes`, the hidden state in LANE ORDER (layer_tail.hip's XRES layout, written by embed_ln_lanes_kernel): its token
+// block's 4 KT result fragments as contiguous 1 KiB loads where the plain form loads 4 KT row-major fragments, queued where that form
+// queues its rows — behind slab 0's request, in front of slab 1's, so the first barrier's count holds — and turned into operand
+// fragments (result_to_operand_fragment: what LayerNorm 2 does to the same fragments for `xf`) behind that barrier.  `a.x`, `xf`: not read.
+template <int KT, int GB, int WT, bool FULL = false, bool XREGS = false, bool CTXREGS = false, bool XLANES = false>
 __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *smem, const int window, const int tid,
                                                     [[maybe_unused]] const f16x8 *xf = nullptr,         // xf: [4 KT]
-                                                    [[maybe_unused]] f16x8 *cf = nullptr) {             // cf: [4 KT]
+                                                    [[maybe_unused]] f16x8 *cf = nullptr,               // cf: [4 KT]
+                                                    [[maybe_unused]] const half_t *xlanes = nullptr) {  // [T][H] in lane order
     static_assert(FULL || !XREGS, "fragments handed over in registers: full windows only");
+    static_assert(XREGS || !XLANES, "lane order in: the register form's body, full windows only");
     static_assert(!CTXREGS || (FULL && WT == GW_F16), "the context in registers: full windows, f16 weights");
     constexpr int NCF = 4 * KT;                               // context fragments of a token block (two per head); a block's exchange area: NCF KiB
     constexpr bool Q4 = WT != GW_F16;
@@ -191,7 +198,15 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
         // rows of the hidden state as MFMA fragments (token = l31, k = 16 ks + 8 hi ..): B operand of the Q / K
         // projections, A operand of the V projection.  Empty slots read the window's first token (finite values).
         f16x8 bf[4 * KT];
-        if constexpr (XREGS) {
+        if constexpr (XLANES) {
+            // (untracked like the rows below, and in their place in the queue; scalar base + the lane's 32-bit offset, four fragments per base:
+            // the instruction offset stops short of 4 KiB)
+            const char *const xb = (const char *)(xlanes + ((size_t)window * Q2_WIN + blk * 32) * H);
+            const unsigned xl = (unsigned)lane * 16u;
+#pragma unroll
+            for (int ks = 0; ks < 4 * KT; ++ks)
+                asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(bf[ks]) : "v"(xl), "s"(xb + (ks >> 2) * 4096), "n"((ks & 3) * 1024));
+        } else if constexpr (XREGS) {
 #pragma unroll
             for (int ks = 0; ks < 4 * KT; ++ks) bf[ks] = xf[ks];
         } else {
@@ -279,12 +294,17 @@ __device__ __forceinline__ void qkv_attention2_body(const Qkv2Args &a, char *sme
         };
         // x rows and slab 0 have landed (slab 1 may still be in flight).  Outstanding, oldest first: slab 0 (PPS pieces), the 4 KT row
         // loads, slab 1 (PPS pieces).  XREGS: slab 0, slab 1 and nothing between them (the rows came in registers, the caller's barrier
-        // in front of this phase waited for vmcnt(0)): the same count leaves the same slab in flight.
+        // in front of this phase waited for vmcnt(0)): the same count leaves the same slab in flight.  XLANES: the plain form's queue, with the
+        // 4 KT lane-order fragments where its rows are.
         [[maybe_unused]] const bool tl_sel = tid == 256;
         TL_STAMP_AT(tl_sel, 0);
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" : : "n"(Q4 ? 0 : PPS) : "memory");
 #pragma unroll
         for (int ks = 0; ks < 4 * KT; ++ks) asm volatile("" : "+v"(bf[ks]));
+        if constexpr (XLANES) {
+#pragma unroll
+            for (int ks = 0; ks < 4 * KT; ++ks) bf[ks] = result_to_operand_fragment(bf[ks]);
+        }
         if constexpr (Q4) {
 #pragma unroll
             for (int i = 0; i < NRAW; ++i) q4_request(min(1, n_head - 1), 0, i);

@@ -399,6 +399,33 @@ int32_t bert_hip_test_embed_ln(int32_t table_type, int32_t H, int32_t n_vocab, i
     return download_rows16("bert_hip_test_embed_ln", out, dout, T, T_pad, H);
 }
 
+// the lane-order form (launch_embed_ln_lanes): `out` gets the [T][H] halves as the kernel stored them; -2, and no launch, for a shape
+// the launcher declines
+int32_t bert_hip_test_embed_ln_lanes(int32_t table_type, int32_t H, int32_t n_vocab, int32_t n_pos, const void *word, const void *type,
+                                     const void *pos, const float *gamma, const float *beta, const bert_vocab_id *tokens,
+                                     const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len, uint16_t *out) {
+    std::string err;
+    if (H <= 0 || n_vocab <= 0 || n_sentences <= 0 || max_len < 0 || max_len > n_pos) return -1;
+    const int T = cu_seqlens[n_sentences], T_pad = rows_pad256(T);
+    if (max_len == 0)
+        for (int b = 0; b < n_sentences; ++b) max_len = std::max(max_len, cu_seqlens[b + 1] - cu_seqlens[b]);
+    if (max_len > n_pos) return -1;
+    if (!embed_ln_lanes_supported(table_type, H, T, max_len)) return -2;
+    const size_t rb = wtype_row_bytes(table_type, H);
+    DevBuf dw, dt, dp, dg, db, dtok, dcu, dout;
+    if (!dw.upload(word, rb * n_vocab, err) || !dt.upload(type, rb * 2, err) || !dp.upload(pos, rb * n_pos, err) ||
+        !dg.upload(gamma, (size_t)H * 4, err) || !db.upload(beta, (size_t)H * 4, err) || !dtok.upload(tokens, (size_t)T * 4, err) ||
+        !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) || !alloc_pad16(dout, (size_t)T_pad * H, err)) {
+        fprintf(stderr, "bert_hip_test_embed_ln_lanes: %s\n", err.c_str());
+        return -1;
+    }
+    if (!launch_embed_ln_lanes(dw.p, dt.p, dp.p, table_type, dg.as<float>(), db.as<float>(), dtok.as<int32_t>(), dcu.as<int32_t>(), n_sentences,
+                               T, H, n_vocab, max_len, dout.as<half_t>(), nullptr)) return -2;
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    return download_rows16("bert_hip_test_embed_ln_lanes", out, dout, T, T_pad, H);
+}
+
 int32_t bert_hip_test_layernorm(int32_t T, int32_t H, const uint16_t *x, const float *gamma, const float *beta, uint16_t *out) {
     std::string err;
     if (T <= 0 || H <= 0 || H % 2 || H > 4096) return -1;       // (the widths a model file may have: checked at load)

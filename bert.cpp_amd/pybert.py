@@ -44,7 +44,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_gemm", "bert_hip_test_gemm_lnfold", "bert_hip_test_attention", "bert_hip_test_qkv_attention",
     "bert_hip_test_layer_tail", "bert_hip_test_skinny_tail", "bert_hip_test_skinny_qkv", "bert_hip_test_shard_bounds", "bert_hip_test_build_windows",
     "bert_hip_test_build_windows_device", "bert_hip_test_max_windows", "bert_hip_test_set_window_slots", "bert_hip_test_set_pad",
-    "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_pool_normalize",
+    "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_embed_ln_lanes", "bert_hip_test_pool_normalize",
     "bert_hip_test_pool", "bert_hip_test_layernorm",
     "bert_hip_test_f32_gemm", "bert_hip_test_f32_attention", "bert_hip_test_f32_layernorm", "bert_hip_test_f32_embed_ln", "bert_hip_test_f32_pool",
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
@@ -201,6 +201,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_skinny_qkv.argtypes = [i32, i32, vp, vp, vp, vp, vp, i32, vp, C.c_uint32, vp, vp]
     L.bert_hip_test_embed_ln.restype = i32
     L.bert_hip_test_embed_ln.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32p, i32p, i32, i32, vp]
+    L.bert_hip_test_embed_ln_lanes.restype = i32
+    L.bert_hip_test_embed_ln_lanes.argtypes = L.bert_hip_test_embed_ln.argtypes
     L.bert_hip_test_layernorm.restype = i32
     L.bert_hip_test_layernorm.argtypes = [i32, i32, vp, vp, vp, vp]
     L.bert_hip_test_pool_normalize.restype = i32
@@ -259,7 +261,7 @@ def test_lib() -> C.CDLL:
     return L
 
 
-def test_embed_ln(table_type: int, word_bytes, type_bytes, pos_bytes, H: int, gamma, beta, tokens, cu_seqlens, max_len: int = 0) -> np.ndarray:
+def test_embed_ln(table_type: int, word_bytes, type_bytes, pos_bytes, H: int, gamma, beta, tokens, cu_seqlens, max_len: int = 0, lanes: bool = False) -> np.ndarray:
     """Tables as file-layout bytes (the position table has as many rows as pos_bytes holds); max_len: the promise the launch is made
     under, 0 = the longest sentence.  Returns float16 [T, H]."""
     wb, tb, pb = (np.ascontiguousarray(a) for a in (word_bytes, type_bytes, pos_bytes))
@@ -268,11 +270,20 @@ def test_embed_ln(table_type: int, word_bytes, type_bytes, pos_bytes, H: int, ga
     toks = np.ascontiguousarray(tokens, dtype=np.int32); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
     assert len(toks) == int(cu[-1]) and tb.nbytes == 2 * rb and g.shape == (H,) and b.shape == (H,)
     out = np.zeros((len(toks), H), dtype=np.float16)
-    r = test_lib().bert_hip_test_embed_ln(table_type, H, wb.nbytes // rb, pb.nbytes // rb, wb.ctypes.data, tb.ctypes.data, pb.ctypes.data,
-                                          g.ctypes.data, b.ctypes.data, _i32p(toks), _i32p(cu), len(cu) - 1, max_len, out.ctypes.data)
+    entry = getattr(test_lib(), "bert_hip_test_embed_ln_lanes" if lanes else "bert_hip_test_embed_ln")
+    r = entry(table_type, H, wb.nbytes // rb, pb.nbytes // rb, wb.ctypes.data, tb.ctypes.data, pb.ctypes.data,
+              g.ctypes.data, b.ctypes.data, _i32p(toks), _i32p(cu), len(cu) - 1, max_len, out.ctypes.data)
+    if lanes and r == -2:
+        return None
     if r != 0:
-        raise RuntimeError(f"bert_hip_test_embed_ln failed: {r}")
+        raise RuntimeError(f"bert_hip_test_embed_ln{'_lanes' if lanes else ''} failed: {r}")
     return out
+
+
+def test_embed_ln_lanes(table_type: int, word_bytes, type_bytes, pos_bytes, H: int, gamma, beta, tokens, cu_seqlens, max_len: int = 0):
+    """The lane-order form (launch_embed_ln_lanes) on test_embed_ln's arguments: the float16 [T, H] halves as the kernel stored them
+    (tests/lane_order.py puts them back into rows), or None where the launcher declines the shape and launches nothing."""
+    return test_embed_ln(table_type, word_bytes, type_bytes, pos_bytes, H, gamma, beta, tokens, cu_seqlens, max_len, lanes=True)
 
 
 def test_layernorm(x: np.ndarray, gamma, beta) -> np.ndarray:

@@ -103,6 +103,14 @@ BERT_API int32_t bert_hip_test_embed_ln(int32_t table_type, int32_t H, int32_t n
                                         const void *type, const void *pos, const float *gamma, const float *beta,
                                         const bert_vocab_id *tokens, const int32_t *cu_seqlens, int32_t n_sentences,
                                         int32_t max_len, uint16_t *out);
+/* The same arguments and values in LANE ORDER (launch_embed_ln_lanes, the one-launch route's embedding on full windows): out gets the
+ * [T][H] f16 bits as stored — 32-token block k at 32 k H, its fragment q at + 512 q, lane l = 32 hi + l31 of it at + 8 l: features
+ * 16 q + 4 hi + {0..3}, 16 q + 8 + 4 hi + {0..3} of token 32 k + l31.  Every token in front of T is written.  -2, and nothing is
+ * launched, for a shape the launcher declines (T no positive multiple of 128, H not 256 or 384, a table type outside 0..3).          */
+BERT_API int32_t bert_hip_test_embed_ln_lanes(int32_t table_type, int32_t H, int32_t n_vocab, int32_t n_pos, const void *word,
+                                              const void *type, const void *pos, const float *gamma, const float *beta,
+                                              const bert_vocab_id *tokens, const int32_t *cu_seqlens, int32_t n_sentences,
+                                              int32_t max_len, uint16_t *out);
 /* out [T][H] = LayerNorm(x [T][H]) gamma + beta on f16 rows, in place on the device as in the engine (launch_layernorm: two-pass
  * statistics, eps 1e-5); H even, at most 4096.                                                                                      */
 BERT_API int32_t bert_hip_test_layernorm(int32_t T, int32_t H, const uint16_t *x, const float *gamma, const float *beta, uint16_t *out);
