@@ -39,7 +39,23 @@ public:
                            float *d_out, hipStream_t stream, float *d_hidden, std::string &err,
                            const int2 *d_windows = nullptr, int n_windows = 0, int window_slots = 0,       // window_slots: the place granularity d_windows was built with (0: read it now)
                            int pool_mode = -1,                   // kernels.h POOL_*: what the host call read for all its chunks (-1: read the options now)
-                           void *d_token_rows = nullptr, int token_flags = 0);     // token rows (below); d_out may then be null: the embeddings stay in d_out_
+                           void *d_token_rows = nullptr, int token_flags = 0,      // token rows (below); d_out may then be null: the embeddings stay in d_out_
+                           const int32_t *d_first_len = nullptr);                  // token types (below); null: type 0 everywhere, the untyped embedding kernels
+    // Sentence pairs and scores (bert_hip.h): a TYPED pass carries d_first_len [n_sentences] — the leading tokens of each sentence that take
+    // token-type row 0, the rest row 1 (kernels.h launch_embed_ln) — and plans like any other pass; only the embedding launch differs.
+    // score_packed_device: a typed pass that ends in POOL_CLS | POOL_RAW rows in d_out_ (the mode handed in as an argument, as the grouped
+    // pass hands in POOL_RAW; the options stay as they are), then the head launch ("cls_head" in the profile; cls_head.hip: the
+    // matrix-core form, or the plain form on the f32 route and for an H the other refuses) -> d_scores f32 [n_sentences][n_labels].
+    // flags: kernels.h CLS_HEAD_SIGMOID.  -2 with a message for a model without a head.  After reserve() it allocates nothing.
+    int n_labels() const { return w_->n_labels; }
+    int score_packed_device(const int32_t *d_tokens, const int32_t *d_cu, const int32_t *d_first_len, int n_sentences, int n_tokens, int max_len,
+                            int flags, float *d_scores, hipStream_t stream, std::string &err,
+                            const int2 *d_windows = nullptr, int n_windows = 0, int window_slots = 0);      // (as eval_packed_device takes them)
+    // Host forms, blocking, on this engine's device: cut at chunk_tokens between sentences, one copy per chunk and direction (ids |
+    // cu_seqlens | first_len in; rows or scores out).  first_len: nullable (all type 0), validated by the caller.  scores == false: the
+    // context's pooling and normalisation, out [n_sentences][H]; true: out [n_sentences][n_labels].
+    int eval_packed_typed_host(const int32_t *tokens, const int32_t *cu_seqlens, const int32_t *first_len, int n_sentences, bool scores, int flags,
+                               float *out, std::string &err);
     // Token rows (bert_hip.h "token rows and late interaction"): a pass with one more destination, [n_tokens][H] rows of the final states
     // (kernels.h launch_token_rows, TOKEN_ROWS_* flags), written by one launch ("token_rows" in the profile) beside the pooling launch.
     // Such a pass does not take the one-launch kernel (which keeps x on chip between its phases and pools inside the launch: the other
@@ -117,6 +133,7 @@ private:
         int B, T, max_len, t_pad, slots, pool_mode;
         float *out, *hidden;
         void *token_rows;             // token rows wanted (eval_packed_device): no one-launch kernel
+        const int32_t *first_len;     // a typed pass (eval_packed_device): the embedding launch's first_len, else null
         hipStream_t s;
         const int2 *windows;
         int n_windows;
@@ -128,7 +145,7 @@ private:
         std::vector<LayerPlan> layers;
     };
     Plan plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s, float *d_hidden,
-              const int2 *d_windows, int n_windows, int slots, int pool_mode, void *d_token_rows = nullptr) const;
+              const int2 *d_windows, int n_windows, int slots, int pool_mode, void *d_token_rows = nullptr, const int32_t *d_first_len = nullptr) const;
     bool forward_f32(const Plan &p, std::string &err);        // f32 files in f32 arithmetic (f32_route.hip), one launch per operation
     void forward_latency(const Plan &p);
     void forward_one_launch(const Plan &p);
@@ -151,6 +168,7 @@ private:
 
     // workspace (grow-only)
     DevBuf x_, qkv_, ctx_, y_, ff_, v32_, d_tokens_, d_cu_, d_out_, d_hidden_, status_, windows_;
+    DevBuf typed_in_, typed_out_;                             // the host forms of the typed pass: a chunk's ids | cu_seqlens | first_len, and its rows or scores
     DevBuf tok_in_, tok_rows_;                                // the host form of the token rows: a chunk's ids | cu_seqlens, and its rows
     DevBuf raw_rows_, group_in_, group_out_;                  // grouped pooling: the sentences' POOL_RAW rows [n_sentences][H] f32; the host form's cu_seqlens | group_cu and its groups' rows
     DevBuf ln_stats1_, ln_stats2_, ln_rows1_, ln_rows2_;      // LayerNorm folding: per-row partial statistics / finalized rows of the two LayerNorms of a layer

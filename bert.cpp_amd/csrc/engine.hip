@@ -126,7 +126,7 @@ void Engine::build_windows(const int32_t *cu, int B, std::vector<int2> &windows,
 
 int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out,
                                hipStream_t s, float *d_hidden, std::string &err, const int2 *d_windows, int n_windows, int slots_in,
-                               int pool_mode_in, void *d_token_rows, int token_flags) {
+                               int pool_mode_in, void *d_token_rows, int token_flags, const int32_t *d_first_len) {
     if (B <= 0 || T <= 0) return 0;
     // the windows' place granularity, read ONCE per pass (the host path read it when it built its list): the window list, the
     // grid bound and the kernels' place rule must agree whatever another thread or context sets meanwhile
@@ -140,7 +140,7 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     if (!ensure_workspace((T + 255) / 256 * 256, B, err)) return -1;
     prof_.begin_pass();
     if (!d_out) d_out = d_out_.as<float>();                   // (a token-rows call that wants no embeddings: ensure_workspace sized it)
-    const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots, pool_mode, d_token_rows);
+    const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots, pool_mode, d_token_rows, d_first_len);
     bool ok = true;
     if (p.route == Route::F32) ok = forward_f32(p, err);
     else {
@@ -148,10 +148,10 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
         // (the one-launch kernel's full form: the same values in lane order in y_, no rows — plan() asked the launcher's own rule)
         if (p.embed_lanes)
             timed("embed_ln", 0.0, s, [&] { ok = launch_embed_ln_lanes(w_->word_emb.p, w_->type_emb.p, w_->pos_emb.p, w_->table_type, w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(),
-                                                                       d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, y_.as<half_t>(), s); });
+                                                                       d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, y_.as<half_t>(), s, d_first_len); });
         else
             timed("embed_ln", 0.0, s, [&] { launch_embed_ln(w_->word_emb.p, w_->type_emb.p, w_->pos_emb.p, w_->table_type, w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(),
-                                                            d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, x_.as<half_t>(), s); });
+                                                            d_tokens, d_cu, B, T, H, hp_.n_vocab, max_len, x_.as<half_t>(), s, d_first_len); });
         if (!ok) { err = "embed_ln: no lane-order kernel for this shape"; return -1; }
         tap(p, 0);
         if (p.build_windows)
@@ -176,9 +176,10 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
 
 // The route of a pass and, per layer, its kernels: every eligibility test of the forward pass, each made here once.  Launches nothing.
 Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s,
-                          float *d_hidden, const int2 *d_windows, int n_windows, int slots, int pool_mode, void *d_token_rows) const {
+                          float *d_hidden, const int2 *d_windows, int n_windows, int slots, int pool_mode, void *d_token_rows,
+                          const int32_t *d_first_len) const {
     // (t_pad: whole tiles of every kernel family, 128- and 256-token tiles)
-    Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, pool_mode, d_out, d_hidden, d_token_rows, s, d_windows, n_windows};
+    Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, pool_mode, d_out, d_hidden, d_token_rows, d_first_len, s, d_windows, n_windows};
     if (w_->f32_file && opt_.f32_exact) { p.route = Route::F32; return p; }
     const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh, Lz = hp_.n_layer;
     auto family = [&](const GemmWeightStore &W) {
@@ -405,7 +406,7 @@ bool Engine::forward_f32(const Plan &p, std::string &err) {
     float *x = x_.as<float>(), *qkv = qkv_.as<float>(), *ctx = ctx_.as<float>(), *y = y_.as<float>(), *ff = ff_.as<float>();
     timed("embed_ln", 0.0, p.s, [&] {
         launch_f32_embed_ln(w_->word_emb.as<float>(), w_->type_emb.as<float>(), w_->pos_emb.as<float>(), w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(), p.tokens,
-                            p.cu, p.B, p.T, H, hp_.n_vocab, p.max_len, x, p.s);
+                            p.cu, p.B, p.T, H, hp_.n_vocab, p.max_len, x, p.s, p.first_len);
     });
     tap(p, 0);
     for (int il = 0; il < hp_.n_layer; ++il) {
@@ -655,6 +656,77 @@ int Engine::eval_packed_tokens_host(const int32_t *tokens, const int32_t *cu, in
         if (hipMemcpyAsync(rows + (size_t)cu[b0] * H, tok_rows_.p, (size_t)T * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
             (embeddings && hipMemcpyAsync(embeddings + (size_t)b0 * H, d_out_.p, (size_t)nb * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess))
             return fail("hipMemcpyAsync (rows) failed");
+        HIP_OK(hipStreamSynchronize(stream_), err, -1);
+        b0 = b1;
+    }
+    return 0;
+}
+
+int Engine::score_packed_device(const int32_t *d_tokens, const int32_t *d_cu, const int32_t *d_first_len, int B, int T, int max_len, int flags,
+                                float *d_scores, hipStream_t s, std::string &err, const int2 *d_windows, int n_windows, int slots) {
+    if (w_->n_labels <= 0) { err = "the model file has no classification head (pooler.dense.*, classifier.*)"; return -2; }
+    if (B <= 0 || T <= 0) return 0;
+    HIP_OK(hipSetDevice(device_), err, -1);
+    // (the head launch behind the pass is part of the same operation: one answer for both on whether s is capturing)
+    StreamOp op;
+    if (!op_begin(s, busy_, op, err)) return -1;
+    // the un-normalised [CLS] rows, in the engine's own d_out_ (ensure_workspace sizes it for the pass)
+    if (eval_packed_device(d_tokens, d_cu, B, T, max_len, nullptr, s, nullptr, err, d_windows, n_windows, slots, POOL_CLS | POOL_RAW, nullptr, 0, d_first_len) != 0) return -1;
+    const int H = hp_.n_embd;
+    const bool f32_route = w_->f32_file && opt_.f32_exact;
+    const ClsHeadArgs a{d_out_.as<float>(), w_->head_wp16.as<half_t>(), f32_route ? w_->head_wp32.as<float>() : nullptr, w_->head_bp.as<float>(),
+                        w_->head_wc.as<float>(), w_->head_bc.as<float>(), d_scores, B, H, w_->n_labels, flags};
+    bool ok = true;
+    timed("cls_head", 2.0 * B * H * (H + w_->n_labels), s, [&] {
+        ok = !f32_route && cls_head_mfma_supported(H) ? launch_cls_head(a, s) : launch_cls_head_f32(a, s);
+    });
+    if (!ok) { err = "cls_head: no kernel for n_embd = " + std::to_string(H); return -1; }
+    HIP_OK(hipGetLastError(), err, -1);
+    return op_end(op, err) ? 0 : -1;
+}
+
+int Engine::eval_packed_typed_host(const int32_t *tokens, const int32_t *cu, const int32_t *first_len, int B, bool scores, int flags, float *out,
+                                   std::string &err) {
+    if (scores && w_->n_labels <= 0) { err = "the model file has no classification head (pooler.dense.*, classifier.*)"; return -2; }
+    if (B <= 0) return 0;
+    HIP_OK(hipSetDevice(device_), err, -1);
+    const size_t W = scores ? (size_t)w_->n_labels : (size_t)hp_.n_embd;      // floats per sentence that leave
+    auto fail = [&](const char *what) { if (what) err = what; (void)hipStreamSynchronize(stream_); return -1; };      // nothing may stay queued on the caller's memory
+    auto pad16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
+    // chunks [b0, b1) by eval_packed_host's rule: at most chunk_tokens tokens, at least one sentence
+    std::vector<char> h_in;
+    std::vector<int2> windows;
+    const int slots = window_slots(), pool_mode = opt_.pool_mode();       // (once per call, as eval_packed_host reads them)
+    for (int b0 = 0; b0 < B;) {
+        int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
+        while (b1 < B && cu[b1 + 1] - cu[b0] <= opt_.chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
+        const int nb = b1 - b0, T = cu[b1] - cu[b0];
+        // (the windows of eval_packed_host, so that a typed call plans as the untyped one does)
+        const size_t off_cu = pad16((size_t)T * 4), off_fl = off_cu + pad16((size_t)(nb + 1) * 4), off_w = off_fl + pad16((size_t)nb * 4),
+                     in_bytes = off_w + (size_t)nb * sizeof(int2);
+        if (!typed_in_.ensure(in_bytes, err) || !typed_out_.ensure((size_t)nb * W * 4, err) || !ensure_workspace((T + 255) / 256 * 256, nb, err)) return fail(nullptr);
+        h_in.assign(in_bytes, 0);
+        memcpy(h_in.data(), tokens + cu[b0], (size_t)T * 4);
+        int32_t *h_cu = (int32_t *)(h_in.data() + off_cu);
+        for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
+        if (first_len) memcpy(h_in.data() + off_fl, first_len + b0, (size_t)nb * 4);
+        int n_windows = 0;
+        if (max_len <= 128) {
+            build_windows(h_cu, nb, windows, slots);
+            n_windows = (int)windows.size();
+            memcpy(h_in.data() + off_w, windows.data(), windows.size() * sizeof(int2));
+        }
+        const int2 *d_w = n_windows ? (const int2 *)(typed_in_.as<char>() + off_w) : nullptr;
+        const char *d_in = typed_in_.as<char>();
+        // (a pageable source: the copy has left the host buffer when it returns)
+        if (hipMemcpyAsync(typed_in_.p, h_in.data(), in_bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) return fail("hipMemcpyAsync (ids) failed");
+        const int32_t *d_fl = first_len ? (const int32_t *)(d_in + off_fl) : nullptr;
+        const int r = scores ? score_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), d_fl, nb, T, max_len, flags, typed_out_.as<float>(), stream_, err,
+                                                   d_w, n_windows, slots)
+                             : eval_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, typed_out_.as<float>(), stream_, nullptr, err,
+                                                  d_w, n_windows, slots, pool_mode, nullptr, 0, d_fl);
+        if (r != 0) return fail(nullptr);
+        if (hipMemcpyAsync(out + (size_t)b0 * W, typed_out_.p, (size_t)nb * W * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess) return fail("hipMemcpyAsync (results) failed");
         HIP_OK(hipStreamSynchronize(stream_), err, -1);
         b0 = b1;
     }

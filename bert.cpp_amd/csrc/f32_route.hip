@@ -41,10 +41,12 @@ __device__ __forceinline__ void f32_layernorm_row(float *row, const float *gamma
 // max_len (<= the position table's rows: the host refuses a larger one): a token at or behind place max_len of its sentence, which
 // only a sentence longer than the device API's promise has, takes row max_len - 1, so the table is never read past its end; what its
 // row holds does not matter (the pooling kernel gives that sentence a NaN row).
+// TYPED: the token-type row by first_len, misc_kernels.hip embed_ln_kernel's rule.
+template <bool TYPED>
 __global__ __launch_bounds__(256) void f32_embed_ln_kernel(const float *word, const float *type, const float *pos, const float *gamma,
                                                            const float *beta, const int32_t *__restrict__ tokens,
                                                            const int32_t *__restrict__ cu_seqlens, int n_sentences, int T, int H, int n_vocab,
-                                                           int max_len, float *out) {
+                                                           int max_len, float *out, const int32_t *__restrict__ first_len) {
     const int t = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= T) return;
     int lo = 0, hi = n_sentences;                             // sentence of token t: largest b with cu[b] <= t
@@ -52,7 +54,8 @@ __global__ __launch_bounds__(256) void f32_embed_ln_kernel(const float *word, co
         const int mid = (lo + hi) >> 1;
         if (cu_seqlens[mid] <= t) lo = mid; else hi = mid;
     }
-    const int p = min(t - cu_seqlens[lo], max_len - 1);
+    const int place = t - cu_seqlens[lo], p = min(place, max_len - 1);
+    if constexpr (TYPED) type += place >= first_len[lo] ? H : 0;
     int id = tokens[t];
     id = id < 0 ? 0 : (id >= n_vocab ? n_vocab - 1 : id);     // ids are validated on the host API; clamp for safety
     float *row = out + (size_t)t * H;
@@ -226,10 +229,13 @@ __global__ __launch_bounds__(256) void f32_pool_normalize_kernel(const float *x,
 }
 
 void launch_f32_embed_ln(const float *word, const float *type, const float *pos, const float *gamma, const float *beta, const int32_t *tokens,
-                         const int32_t *cu_seqlens, int n_sentences, int T, int H, int n_vocab, int max_len, float *out, hipStream_t stream) {
+                         const int32_t *cu_seqlens, int n_sentences, int T, int H, int n_vocab, int max_len, float *out, hipStream_t stream,
+                         const int32_t *first_len) {
     if (T <= 0) return;
-    BERT_LAUNCH(f32_embed_ln_kernel, dim3((T + 3) / 4), dim3(256), 0, stream, word, type, pos, gamma, beta, tokens, cu_seqlens, n_sentences, T, H,
-                n_vocab, max_len, out);
+    if (first_len) BERT_LAUNCH(f32_embed_ln_kernel<true>, dim3((T + 3) / 4), dim3(256), 0, stream, word, type, pos, gamma, beta, tokens, cu_seqlens, n_sentences, T, H,
+                               n_vocab, max_len, out, first_len);
+    else BERT_LAUNCH(f32_embed_ln_kernel<false>, dim3((T + 3) / 4), dim3(256), 0, stream, word, type, pos, gamma, beta, tokens, cu_seqlens, n_sentences, T, H,
+                     n_vocab, max_len, out, first_len);
 }
 
 void launch_f32_layernorm(float *x, const float *gamma, const float *beta, int T, int H, hipStream_t stream) {

@@ -113,11 +113,18 @@ void launch_skinny_layernorm(const float *v, const float *gamma, const float *be
 void launch_gemm_naive(const GemmWeight &W, const half_t *A, const float *bias, const half_t *resid, half_t *C,
                        int M, int epilogue, hipStream_t stream);
 
-// word + token_type(0) + position gather-sum, LayerNorm(eps 1e-5), f16 out.  Tables in file layout.
+// form (the op-level tests pick one; the engine leaves the choice to the launcher): the rows kernel on its (group, sentence) grid or
+// with the bisection, or the generic kernel.  A rows form on a shape the rows kernel does not take launches nothing: false.
+enum : int { EMBED_FORM_AUTO = -1, EMBED_FORM_GRID = 0, EMBED_FORM_SEARCH = 1, EMBED_FORM_GENERIC = 2 };
+// word + token_type + position gather-sum, LayerNorm(eps 1e-5), f16 out.  Tables in file layout.
 // max_len (the device API's promise, <= the position table's rows): chooses the grid form; no position row at or behind it is read.
-void launch_embed_ln(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
+// first_len (all four embedding launchers; device memory, [n_sentences], nullable): the leading tokens of sentence b that take
+// token-type row 0, every token at a place at or behind it row 1 — the place in the sentence, not the clamped position row.  Any value
+// is legal (<= 0: all row 1, >= the length: all row 0).  Null: row 0 for every token, on the kernels' untyped instantiations.
+bool launch_embed_ln(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
                      const float *beta, const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int T,
-                     int H, int n_vocab, int max_len, half_t *out, hipStream_t stream);
+                     int H, int n_vocab, int max_len, half_t *out, hipStream_t stream, const int32_t *first_len = nullptr,
+                     int form = EMBED_FORM_AUTO);
 // The same values in LANE ORDER, for launch_model_kernel's full-window form, which starts from them in `xres` and reads no rows: block k
 // (tokens 32 k .. 32 k + 31) is the 32 H halves from 32 k H on, fragment q < H / 16 its KiB q, lane l = 32 hi + l31 owns 16 bytes at 16 l
 // of it: features 16 q + 4 hi + {0..3}, then 16 q + 8 + 4 hi + {0..3} of token 32 k + l31 (layer_tail.hip's XRES layout).  Its shapes:
@@ -125,7 +132,7 @@ void launch_embed_ln(const void *word, const void *type, const void *pos, int ta
 bool embed_ln_lanes_supported(int table_type, int H, int T, int max_len);
 bool launch_embed_ln_lanes(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
                            const float *beta, const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int T,
-                           int H, int n_vocab, int max_len, half_t *xres, hipStream_t stream);
+                           int H, int n_vocab, int max_len, half_t *xres, hipStream_t stream, const int32_t *first_len = nullptr);
 
 // In-place LayerNorm over H of f16 rows (eps 1e-5), gamma/beta f32.
 void launch_layernorm(half_t *x, const float *gamma, const float *beta, int T, int H, hipStream_t stream);
@@ -192,6 +199,24 @@ struct MaxsimArgs {
     int n_q, n_d, H, n_pairs, mode;
 };
 size_t maxsim_lds_bytes(int H);
+// The classification head (cls_head.hip; bert_hip.h "sentence pairs and scores"): rows f32 [B][H], the sentences' POOL_CLS | POOL_RAW rows
+// of a pass -> out f32 [B][n_labels] = Wc tanh(Wp row + bp) + bc, n_labels in 1 .. CLS_HEAD_MAX_LABELS.  wp16: Wp [H][H] f16 row-major
+// (row = out-feature), 16-byte aligned; wp32: the same as f32 (f32 files).  bp [H], wc [n_labels][H], bc [n_labels]: f32.
+// flags bit 0 (CLS_HEAD_SIGMOID): 1 / (1 + exp(-logit)) per label instead of the logit.
+// launch_cls_head: the matrix-core form (H % 8 == 0, 8 <= H <= CLS_HEAD_MFMA_MAX_H; wp16) — false, nothing launched, for another H.
+// launch_cls_head_f32: one workgroup per sentence, f32 dot products; Wp from wp32 if given, else wp16; false for H > 8192.
+constexpr int CLS_HEAD_MAX_LABELS = 8, CLS_HEAD_MFMA_MAX_H = 1024, CLS_HEAD_SIGMOID = 1;
+struct ClsHeadArgs {
+    const float *rows;
+    const half_t *wp16;
+    const float *wp32, *bp, *wc, *bc;
+    float *out;
+    int B, H, n_labels, flags;
+};
+bool cls_head_mfma_supported(int H);
+size_t cls_head_lds_bytes(int H);
+bool launch_cls_head(const ClsHeadArgs &a, hipStream_t stream);
+bool launch_cls_head_f32(const ClsHeadArgs &a, hipStream_t stream);
 void launch_maxsim(const MaxsimArgs &a, hipStream_t stream);
 // n f32 values -> f16, rounded to nearest even (the host form of MaxSim rounds its rows on the device)
 void launch_f32_to_f16(const float *src, half_t *dst, size_t n, hipStream_t stream);
@@ -243,7 +268,8 @@ inline thread_local LaunchTiming *tl_launch_timing = nullptr;
 // The f32 route (f32_route.hip): the forward pass of f32 model files in f32 arithmetic — f32 activations, mat-muls on
 // v_mfma_f32_32x32x2_f32 (any M, N, K; C = epi(A W^T + bias (+ resid))), f32 softmax / GELU / LayerNorm / pooling.
 void launch_f32_embed_ln(const float *word, const float *type, const float *pos, const float *gamma, const float *beta, const int32_t *tokens,
-                         const int32_t *cu_seqlens, int n_sentences, int T, int H, int n_vocab, int max_len, float *out, hipStream_t stream);
+                         const int32_t *cu_seqlens, int n_sentences, int T, int H, int n_vocab, int max_len, float *out, hipStream_t stream,
+                         const int32_t *first_len = nullptr);
 void launch_f32_gemm(const float *A, const float *W, const float *bias, const float *resid, float *C, int M, int N, int K, int epilogue,
                      hipStream_t stream);
 // One wave per query keeps its max_len scores in LDS, four waves a workgroup: f32_attention_lds_bytes(max_len) = 64 ceil(max_len / 4)

@@ -44,12 +44,17 @@ __device__ __forceinline__ void table_pair(const void *tab, int type, int H, int
 // max_len (<= the position table's rows: the host refuses a larger one): a token at or behind place max_len of its sentence, which
 // only a sentence longer than the device API's promise has, takes row max_len - 1, so the table is never read past its end; what
 // its row holds does not matter (the pooling kernel gives that sentence a NaN row).  The same in embed_ln_rows_kernel.
-template <int NJ>
+// TYPED (every embedding kernel; bert_hip.h "sentence pairs and scores"): first_len[b] = how many leading tokens of sentence b take row 0
+// of the token-type table; a token at a place at or behind it — its place in the sentence, NOT the clamped position row — takes row 1.
+// Any value is legal on the device (<= 0: all row 1; >= the length: all row 0, the untyped bits): the row index is a comparison's
+// result, 0 or 1.  !TYPED never reads first_len and is the kernel as it was.
+template <int NJ, bool TYPED>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const void *word, const void *type, const void *pos,
                                                        int table_type, const float *gamma, const float *beta,
                                                        const int32_t *__restrict__ tokens,
                                                        const int32_t *__restrict__ cu_seqlens, int n_sentences,
-                                                       int T, int H, int n_vocab, int max_len, half_t *__restrict__ out) {
+                                                       int T, int H, int n_vocab, int max_len, half_t *__restrict__ out,
+                                                       const int32_t *__restrict__ first_len) {
     // wave-uniform token index: the sentence search below then runs on scalar loads (constant cache)
     const int t = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (t >= T) return;
@@ -59,7 +64,9 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const void *word, const v
         const int mid = (lo + hi) >> 1;
         if (cu_seqlens[mid] <= t) lo = mid; else hi = mid;
     }
-    const int p = min(t - cu_seqlens[lo], max_len - 1);
+    const int place = t - cu_seqlens[lo], p = min(place, max_len - 1);
+    int tr = 0;
+    if constexpr (TYPED) tr = place >= first_len[lo] ? 1 : 0;
     int id = tokens[t];
     id = id < 0 ? 0 : (id >= n_vocab ? n_vocab - 1 : id);   // ids are validated on the host API; clamp for safety
 
@@ -72,7 +79,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const void *word, const v
         if (e < H) {
             float w0, w1, t0, t1, p0, p1;
             table_pair(word, table_type, H, id, e, w0, w1);
-            table_pair(type, table_type, H, 0, e, t0, t1);
+            table_pair(type, table_type, H, tr, e, t0, t1);
             table_pair(pos, table_type, H, p, e, p0, p1);
             v[j][0] = p0 + (t0 + w0);
             v[j][1] = p1 + (t1 + w1);
@@ -136,15 +143,16 @@ __device__ __forceinline__ void table_run8(const void *tab, int H, int r, int e0
 }
 // SEARCH: the grid is (4-token group of the batch) and a wave finds its sentence by bisection of cu_seqlens on scalar loads
 // — for batches of short sentences, where the (group, sentence) grid would be mostly empty workgroups.
-template <int TT, int NC, bool SEARCH>
+template <int TT, int NC, bool SEARCH, bool TYPED>
 __global__ __launch_bounds__(256) void embed_ln_rows_kernel(const void *word, const void *type, const void *pos,
                                                             const float *__restrict__ gamma, const float *__restrict__ beta,
                                                             const int32_t *__restrict__ tokens,
                                                             const int32_t *__restrict__ cu_seqlens, int n_sentences, int T,
-                                                            int H, int n_vocab, int max_len, half_t *__restrict__ out) {
+                                                            int H, int n_vocab, int max_len, half_t *__restrict__ out,
+                                                            const int32_t *__restrict__ first_len) {
     const int lane = threadIdx.x & 63;
     int p = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // position in the sentence / token
-    int t;
+    int t, tr = 0;                                            // (tr: the token-type row)
     if constexpr (SEARCH) {
         t = p;
         if (t >= T) return;
@@ -154,11 +162,13 @@ __global__ __launch_bounds__(256) void embed_ln_rows_kernel(const void *word, co
             if (cu_seqlens[mid] <= t) lo = mid; else hi = mid;
         }
         p = t - cu_seqlens[lo];
+        if constexpr (TYPED) tr = p >= first_len[lo] ? 1 : 0;
     } else {
         const int b = blockIdx.y;
         const int tok0 = cu_seqlens[b], n = cu_seqlens[b + 1] - tok0;
         if (p >= n) return;
         t = tok0 + p;
+        if constexpr (TYPED) tr = p >= first_len[b] ? 1 : 0;
     }
     p = min(p, max_len - 1);                                  // (the position row; t is settled)
     int id = tokens[t];
@@ -173,7 +183,7 @@ __global__ __launch_bounds__(256) void embed_ln_rows_kernel(const void *word, co
         if (e0 < H) {
             float w[8], ty[8], ps[8];
             table_run8<TT>(word, H, id, e0, w);
-            table_run8<TT>(type, H, 0, e0, ty);
+            table_run8<TT>(type, H, tr, e0, ty);
             table_run8<TT>(pos, H, p, e0, ps);
 #pragma unroll
             for (int i = 0; i < 8; ++i) { v[j][i] = ps[i] + (ty[i] + w[i]); sum += v[j][i]; }
@@ -203,33 +213,39 @@ __global__ __launch_bounds__(256) void embed_ln_rows_kernel(const void *word, co
     }
 }
 
-void launch_embed_ln(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
+bool launch_embed_ln(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
                      const float *beta, const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int T,
-                     int H, int n_vocab, int max_len, half_t *out, hipStream_t stream) {
-    if (T <= 0) return;
-    if ((table_type <= 1 ? H % 8 == 0 : H % 32 == 0) && table_type <= 3 && H <= 1024 && max_len > 0) {
+                     int H, int n_vocab, int max_len, half_t *out, hipStream_t stream, const int32_t *first_len, int form) {
+    if (T <= 0) return true;
+    const bool rows_shape = (table_type <= 1 ? H % 8 == 0 : H % 32 == 0) && table_type <= 3 && H <= 1024 && max_len > 0;
+    if ((form == EMBED_FORM_GRID || form == EMBED_FORM_SEARCH) && !(rows_shape && (form == EMBED_FORM_SEARCH || n_sentences <= GRID_YZ_MAX))) return false;
+    if (rows_shape && form != EMBED_FORM_GENERIC) {
         // (group, sentence) grid while at least two thirds of its workgroups have tokens, else one group per 4 tokens
-        const bool search = n_sentences > GRID_YZ_MAX || 2ll * ((max_len + 3) / 4) * n_sentences > 3ll * ((T + 3) / 4);
+        const bool search = form == EMBED_FORM_AUTO ? n_sentences > GRID_YZ_MAX || 2ll * ((max_len + 3) / 4) * n_sentences > 3ll * ((T + 3) / 4) : form == EMBED_FORM_SEARCH;
         const dim3 g2 = search ? dim3((T + 3) / 4) : dim3((max_len + 3) / 4, n_sentences), b2(256);
+#define EMBR_T(TT, NC, SEARCH, TYPED) BERT_LAUNCH((embed_ln_rows_kernel<TT, NC, SEARCH, TYPED>), g2, b2, 0, stream, word, type, pos, gamma, beta, tokens, \
+                                                 cu_seqlens, n_sentences, T, H, n_vocab, max_len, out, first_len)
 #define EMBR(TT, NC) do { \
-            if (search) BERT_LAUNCH((embed_ln_rows_kernel<TT, NC, true>), g2, b2, 0, stream, word, type, pos, gamma, beta, tokens, \
-                                           cu_seqlens, n_sentences, T, H, n_vocab, max_len, out); \
-            else BERT_LAUNCH((embed_ln_rows_kernel<TT, NC, false>), g2, b2, 0, stream, word, type, pos, gamma, beta, tokens, \
-                                    cu_seqlens, n_sentences, T, H, n_vocab, max_len, out); } while (0)
+            if (search) { if (first_len) EMBR_T(TT, NC, true, true); else EMBR_T(TT, NC, true, false); } \
+            else { if (first_len) EMBR_T(TT, NC, false, true); else EMBR_T(TT, NC, false, false); } } while (0)
         if (table_type == 0) { if (H <= 512) EMBR(0, 1); else EMBR(0, 2); }
         else if (table_type == 1) { if (H <= 512) EMBR(1, 1); else EMBR(1, 2); }
         else if (table_type == 2) { if (H <= 512) EMBR(2, 1); else EMBR(2, 2); }
         else { if (H <= 512) EMBR(3, 1); else EMBR(3, 2); }
 #undef EMBR
-        return;
+#undef EMBR_T
+        return true;
     }
     const dim3 grid((T + 3) / 4), block(256);
     const int nj = (H + 127) / 128;
     const int pos_rows = max_len > 0 ? max_len : T;          // (no promise given: a sentence has at most T tokens)
-#define EMB(NJ) BERT_LAUNCH(embed_ln_kernel<NJ>, grid, block, 0, stream, word, type, pos, table_type, gamma, \
-                                   beta, tokens, cu_seqlens, n_sentences, T, H, n_vocab, pos_rows, out)
+#define EMB_T(NJ, TYPED) BERT_LAUNCH((embed_ln_kernel<NJ, TYPED>), grid, block, 0, stream, word, type, pos, table_type, gamma, \
+                                    beta, tokens, cu_seqlens, n_sentences, T, H, n_vocab, pos_rows, out, first_len)
+#define EMB(NJ) do { if (first_len) EMB_T(NJ, true); else EMB_T(NJ, false); } while (0)
     if (nj <= 1) EMB(1); else if (nj <= 3) EMB(3); else if (nj <= 6) EMB(6); else if (nj <= 8) EMB(8); else EMB(32);
 #undef EMB
+#undef EMB_T
+    return true;
 }
 
 // The rows kernel's values in LANE ORDER (kernels.h launch_embed_ln_lanes; layer_tail.hip's XRES layout), for model_kernel's full-window
@@ -242,12 +258,13 @@ void launch_embed_ln(const void *word, const void *type, const void *pos, int ta
 // Sentence and position: block k lies in the 128-token block b = k / 4.  Where sentence b IS that block (cu[b] = 128 b, cu[b + 1] =
 // 128 b + 128: every block of a batch of full sentences) the position is t % 128; any other batch of this T — full only by the sum of
 // its lengths — bisects cu_seqlens like the SEARCH form, on scalar loads.
-template <int TT, int NT>
+template <int TT, int NT, bool TYPED>
 __global__ __launch_bounds__(512) void embed_ln_lanes_kernel(const void *word, const void *type, const void *pos,
                                                              const float *__restrict__ gamma, const float *__restrict__ beta,
                                                              const int32_t *__restrict__ tokens,
                                                              const int32_t *__restrict__ cu_seqlens, int n_sentences, int H,
-                                                             int n_vocab, int max_len, half_t *__restrict__ xres) {
+                                                             int n_vocab, int max_len, half_t *__restrict__ xres,
+                                                             const int32_t *__restrict__ first_len) {
     constexpr int NQ = 8 * NT, FS = 1024 + 16;                // fragments of a block; bytes from one to the next in LDS
     __shared__ __attribute__((aligned(16))) char S[NQ * FS];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -256,7 +273,7 @@ __global__ __launch_bounds__(512) void embed_ln_lanes_kernel(const void *word, c
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int l31 = wave * 4 + i, t = tok0 + l31;
-        int p = t & 127;
+        int p = t & 127, tr = 0;                              // (tr: the token-type row)
         if (!whole) {
             int lo = 0, hi = n_sentences;                     // largest b with cu[b] <= t
             while (hi - lo > 1) {
@@ -264,7 +281,8 @@ __global__ __launch_bounds__(512) void embed_ln_lanes_kernel(const void *word, c
                 if (cu_seqlens[mid] <= t) lo = mid; else hi = mid;
             }
             p = t - cu_seqlens[lo];
-        }
+            if constexpr (TYPED) tr = p >= first_len[lo] ? 1 : 0;
+        } else if constexpr (TYPED) tr = p >= first_len[b] ? 1 : 0;
         p = min(p, max_len - 1);                              // (the position row; t is settled)
         int id = tokens[t];
         id = id < 0 ? 0 : (id >= n_vocab ? n_vocab - 1 : id);   // ids are validated on the host API; clamp for safety
@@ -276,7 +294,7 @@ __global__ __launch_bounds__(512) void embed_ln_lanes_kernel(const void *word, c
         if (e0 < H) {
             float w[8], ty[8], ps[8];
             table_run8<TT>(word, H, id, e0, w);
-            table_run8<TT>(type, H, 0, e0, ty);
+            table_run8<TT>(type, H, tr, e0, ty);
             table_run8<TT>(pos, H, p, e0, ps);
 #pragma unroll
             for (int k = 0; k < 8; ++k) { v[k] = ps[k] + (ty[k] + w[k]); sum += v[k]; }
@@ -312,15 +330,16 @@ bool embed_ln_lanes_supported(int table_type, int H, int T, int max_len) {
 
 bool launch_embed_ln_lanes(const void *word, const void *type, const void *pos, int table_type, const float *gamma,
                            const float *beta, const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int T,
-                           int H, int n_vocab, int max_len, half_t *xres, hipStream_t stream) {
+                           int H, int n_vocab, int max_len, half_t *xres, hipStream_t stream, const int32_t *first_len) {
     if (!embed_ln_lanes_supported(table_type, H, T, max_len) || n_sentences <= 0) return false;
+#define EMBL_T(TT, NT, TYPED) BERT_LAUNCH((embed_ln_lanes_kernel<TT, NT, TYPED>), dim3(T / 32), dim3(512), 0, stream, word, type, pos, gamma, beta, tokens, \
+                                          cu_seqlens, n_sentences, H, n_vocab, max_len, xres, first_len)
 #define EMBL(TT) do { \
-        if (H == 256) BERT_LAUNCH((embed_ln_lanes_kernel<TT, 2>), dim3(T / 32), dim3(512), 0, stream, word, type, pos, gamma, beta, tokens, \
-                                  cu_seqlens, n_sentences, H, n_vocab, max_len, xres); \
-        else BERT_LAUNCH((embed_ln_lanes_kernel<TT, 3>), dim3(T / 32), dim3(512), 0, stream, word, type, pos, gamma, beta, tokens, \
-                         cu_seqlens, n_sentences, H, n_vocab, max_len, xres); } while (0)
+        if (H == 256) { if (first_len) EMBL_T(TT, 2, true); else EMBL_T(TT, 2, false); } \
+        else { if (first_len) EMBL_T(TT, 3, true); else EMBL_T(TT, 3, false); } } while (0)
     if (table_type == 0) EMBL(0); else if (table_type == 1) EMBL(1); else if (table_type == 2) EMBL(2); else EMBL(3);
 #undef EMBL
+#undef EMBL_T
     return true;
 }
 

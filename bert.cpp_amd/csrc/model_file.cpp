@@ -59,6 +59,19 @@ std::map<std::string, Expect> expected_tensors(const HParams &h) {
     return m;
 }
 
+// The optional classification head (BertForSequenceClassification: pooler + classifier), all four or none, behind the encoder's set.
+// ne1 of the classifier (n_labels, 1 .. HEAD_MAX_LABELS) is read from the file; 0 here stands for it.
+const char *const kHeadNames[4] = {"pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"};
+std::map<std::string, Expect> head_tensors(const HParams &h) {
+    std::map<std::string, Expect> m;
+    const int64_t H = h.n_embd;
+    m[kHeadNames[0]] = {H, H, true};
+    m[kHeadNames[1]] = {H, 1, false};
+    m[kHeadNames[2]] = {H, 0, true};
+    m[kHeadNames[3]] = {0, 1, false};
+    return m;
+}
+
 }  // namespace
 
 bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
@@ -107,12 +120,16 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
         return false;
     }
     const auto expect = expected_tensors(hp);
+    const auto head = head_tensors(hp);
+    n_labels = 0;
     tensors.clear();
     total_tensor_bytes = 0;
     // q4 files exist in two block layouts and the records carry no byte counts: the current one (18-byte q4_0 / 20-byte
     // q4_1 blocks: f16 scales, nibbles j | j+16 per byte) and the one of early-2023 ggml (20 / 24 bytes: f32 scales, nibbles
     // 2j | 2j+1 — the sizes the reference's README prints are these, README.md:105-107).  Every expected tensor appears
     // exactly once, so the length of the tensor section tells the two apart.
+    // (The sums run over the encoder's set only: nothing ever wrote a legacy file with a classification head, so such a file matches
+    // neither length, is read in the current layout, fails to parse and is refused.)
     legacy_q4 = false;
     if (hp.f16 == W_Q4_0 || hp.f16 == W_Q4_1) {
         size_t cur = 0, leg = 0;
@@ -147,12 +164,21 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
         std::string name((const char *)c.p, name_len);
         c.p += name_len;
         auto ex = expect.find(name);
-        if (ex == expect.end()) { err = "unknown tensor '" + name + "' in model file"; return false; }
-        if (ex->second.ne0 * ex->second.ne1 != nel) { err = "tensor '" + name + "' has wrong size in model file"; return false; }
-        if (ex->second.ne0 != ne[0] || ex->second.ne1 != ne[1]) {
+        if (ex == expect.end()) {
+            ex = head.find(name);
+            if (ex == head.end()) { err = "unknown tensor '" + name + "' in model file"; return false; }
+            if (name == kHeadNames[2] && ne[0] == hp.n_embd && (ne[1] < 1 || ne[1] > HEAD_MAX_LABELS)) {
+                err = "tensor '" + name + "': n_labels = " + std::to_string(ne[1]) + " outside 1 .. " + std::to_string(HEAD_MAX_LABELS);
+                return false;
+            }
+        }
+        // (the head's open dimension: whatever the file holds; the pair is checked against each other behind the loop)
+        const Expect want{ex->second.ne0 ? ex->second.ne0 : ne[0], ex->second.ne1 ? ex->second.ne1 : ne[1], ex->second.two_d};
+        if (ex->second.ne0 * ex->second.ne1 != 0 && ex->second.ne0 * ex->second.ne1 != nel) { err = "tensor '" + name + "' has wrong size in model file"; return false; }
+        if (want.ne0 != ne[0] || want.ne1 != ne[1]) {
             err = "tensor '" + name + "' has wrong shape in model file: got [" + std::to_string(ne[0]) + ", " +
-                  std::to_string(ne[1]) + "], expected [" + std::to_string(ex->second.ne0) + ", " +
-                  std::to_string(ex->second.ne1) + "]";
+                  std::to_string(ne[1]) + "], expected [" + std::to_string(want.ne0) + ", " +
+                  std::to_string(want.ne1) + "]";
             return false;
         }
         if (ftype < 0 || ftype > 3) { err = "unknown ftype " + std::to_string(ftype) + " in model file"; return false; }
@@ -207,6 +233,23 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
     // the reference leaves missing tensors uninitialised; fail loudly instead
     for (const auto &kv : expect)
         if (!tensors.count(kv.first)) { err = "tensor '" + kv.first + "' is missing from model file"; return false; }
+    // the head: all four tensors or none, the classifier's two agreeing on n_labels
+    int n_head = 0;
+    for (const char *name : kHeadNames) n_head += (int)tensors.count(name);
+    if (n_head != 0 && n_head != 4) {
+        for (const char *name : kHeadNames)
+            if (!tensors.count(name)) { err = std::string("partial classification head: tensor '") + name + "' is missing from model file"; return false; }
+    }
+    if (n_head == 4) {
+        const HostTensor &wc = tensors[kHeadNames[2]], &bc = tensors[kHeadNames[3]];
+        if (bc.ne0 != wc.ne1) {
+            err = std::string("tensor '") + kHeadNames[3] + "' has wrong shape in model file: got [" + std::to_string(bc.ne0) + ", 1], expected [" +
+                  std::to_string(wc.ne1) + ", 1]";
+            return false;
+        }
+        if (wc.ne1 < 1 || wc.ne1 > HEAD_MAX_LABELS) { err = "n_labels = " + std::to_string(wc.ne1) + " outside 1 .. " + std::to_string(HEAD_MAX_LABELS); return false; }
+        n_labels = (int32_t)wc.ne1;
+    }
     return true;
 }
 

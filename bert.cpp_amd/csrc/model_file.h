@@ -13,6 +13,7 @@
 namespace bert_hip {
 
 enum WType : int32_t { W_F32 = 0, W_F16 = 1, W_Q4_0 = 2, W_Q4_1 = 3 };
+constexpr int HEAD_MAX_LABELS = 8;   // classifier.weight [H, n_labels]: 1 .. 8 labels
 
 struct HParams {             // reference bert.cpp:18-27, file order :361-367
     int32_t n_vocab = 0, n_max_tokens = 0, n_embd = 0, n_intermediate = 0, n_head = 0, n_layer = 0, f16 = 0;
@@ -32,6 +33,8 @@ struct ModelFile {
     std::map<std::string, HostTensor> tensors;
     std::vector<uint8_t> blob;   // whole file; HostTensor::data points into it
     size_t total_tensor_bytes = 0;
+    // the optional classification head (pooler.dense.{weight, bias}, classifier.{weight, bias}: all four or none): its labels, 0 = no head
+    int32_t n_labels = 0;
     bool legacy_q4 = false;                          // the file uses the 20 / 24-byte q4 blocks of early-2023 ggml
     std::vector<std::vector<uint8_t>> converted;     // their tensors, re-blocked into the current layout
 

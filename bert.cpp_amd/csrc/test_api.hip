@@ -820,4 +820,72 @@ int32_t bert_hip_test_token_rows(const void *x, int32_t is_f32, int32_t T, int32
     return 0;
 }
 
+int32_t bert_hip_test_embed_ln_typed(int32_t table_type, int32_t H, int32_t n_vocab, int32_t n_pos, const void *word, const void *type,
+                                     const void *pos, const float *gamma, const float *beta, const bert_vocab_id *tokens,
+                                     const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len, const int32_t *first_len, int32_t form,
+                                     void *out) {
+    const char *me = "bert_hip_test_embed_ln_typed";
+    std::string err;
+    if (H <= 0 || n_vocab <= 0 || n_sentences <= 0 || max_len < 0 || max_len > n_pos || form < 0 || form > 4 || table_type < 0 || table_type > 3) return -1;
+    if (form == 4 && table_type != W_F32) return -2;
+    const int T = cu_seqlens[n_sentences], T_pad = form == 4 ? f32_rows_pad(T) : rows_pad256(T);
+    if (max_len == 0)
+        for (int b = 0; b < n_sentences; ++b) max_len = std::max(max_len, cu_seqlens[b + 1] - cu_seqlens[b]);
+    if (max_len > n_pos || max_len <= 0) return -1;
+    if (form == 3 && !embed_ln_lanes_supported(table_type, H, T, max_len)) return -2;
+    const size_t rb = wtype_row_bytes(table_type, H);
+    DevBuf dw, dt, dp, dg, db, dtok, dcu, dfl, dout;
+    if (!dw.upload(word, rb * n_vocab, err) || !dt.upload(type, rb * 2, err) || !dp.upload(pos, rb * n_pos, err) ||
+        !dg.upload(gamma, (size_t)H * 4, err) || !db.upload(beta, (size_t)H * 4, err) || !dtok.upload(tokens, (size_t)T * 4, err) ||
+        !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) || (first_len && !dfl.upload(first_len, (size_t)n_sentences * 4, err)) ||
+        !(form == 4 ? alloc_pad32(dout, (size_t)T_pad * H, err) : alloc_pad16(dout, (size_t)T_pad * H, err))) {
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return -1;
+    }
+    const int32_t *fl = first_len ? dfl.as<int32_t>() : nullptr;
+    bool launched = true;
+    if (form == 4)
+        launch_f32_embed_ln(dw.as<float>(), dt.as<float>(), dp.as<float>(), dg.as<float>(), db.as<float>(), dtok.as<int32_t>(), dcu.as<int32_t>(), n_sentences, T,
+                            H, n_vocab, max_len, dout.as<float>(), nullptr, fl);
+    else if (form == 3)
+        launched = launch_embed_ln_lanes(dw.p, dt.p, dp.p, table_type, dg.as<float>(), db.as<float>(), dtok.as<int32_t>(), dcu.as<int32_t>(), n_sentences, T, H,
+                                         n_vocab, max_len, dout.as<half_t>(), nullptr, fl);
+    else
+        launched = launch_embed_ln(dw.p, dt.p, dp.p, table_type, dg.as<float>(), db.as<float>(), dtok.as<int32_t>(), dcu.as<int32_t>(), n_sentences, T, H, n_vocab,
+                                   max_len, dout.as<half_t>(), nullptr, fl, form);
+    if (!launched) return -2;
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    return form == 4 ? download_rows32(me, (float *)out, dout, T, T_pad, H) : download_rows16(me, (uint16_t *)out, dout, T, T_pad, H);
+}
+
+int32_t bert_hip_test_cls_head(int32_t B, int32_t H, int32_t n_labels, const float *rows, const void *Wp, int32_t wp_is_f32, const float *bp,
+                               const float *Wc, const float *bc, int32_t flags, int32_t form, float *out) {
+    const char *me = "bert_hip_test_cls_head";
+    if (B < 1 || H < 1 || n_labels < 1 || n_labels > CLS_HEAD_MAX_LABELS || !rows || !Wp || !bp || !Wc || !bc || !out || (flags & ~1) || form < 0 || form > 1) return -1;
+    if (form == 0 && (wp_is_f32 || !cls_head_mfma_supported(H))) return -2;
+    std::string err;
+    // the rows as the engine's d_out_ holds them, one more block of 32 sentences behind the last whole one: those hold the 32-bit pattern,
+    // as every word of the output does before the launch
+    const int B_pad = (B + 31) / 32 * 32 + 32;
+    DevBuf drows, dwp, dbp, dwc, dbc, dout;
+    if (!upload_padded(drows, (const uint32_t *)rows, B, B_pad, H, g_pad32, err) || !dwp.upload(Wp, (size_t)H * H * (wp_is_f32 ? 4 : 2), err) ||
+        !dbp.upload(bp, (size_t)H * 4, err) || !dwc.upload(Wc, (size_t)n_labels * H * 4, err) || !dbc.upload(bc, (size_t)n_labels * 4, err) ||
+        !alloc_pad32(dout, (size_t)B_pad * n_labels, err)) {
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return -1;
+    }
+    const ClsHeadArgs a{drows.as<float>(), wp_is_f32 ? nullptr : dwp.as<half_t>(), wp_is_f32 ? dwp.as<float>() : nullptr, dbp.as<float>(), dwc.as<float>(),
+                        dbc.as<float>(), dout.as<float>(), B, H, n_labels, flags};
+    if (!(form == 0 ? launch_cls_head(a, nullptr) : launch_cls_head_f32(a, nullptr))) return -2;
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    std::vector<uint32_t> h((size_t)B_pad * n_labels);
+    CK(hipMemcpy(h.data(), dout.p, h.size() * 4, hipMemcpyDeviceToHost));
+    memcpy(out, h.data(), (size_t)B * n_labels * 4);
+    for (size_t i = (size_t)B * n_labels; i < h.size(); ++i)
+        if (h[i] != g_pad32) { fprintf(stderr, "%s: a score behind the last sentence was written\n", me); return -4; }
+    return 0;
+}
+
 }  // extern "C"

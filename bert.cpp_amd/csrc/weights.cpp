@@ -90,6 +90,16 @@ std::vector<float> table_as_f32(const HostTensor &t) {
     return img;
 }
 
+std::vector<float> tensor_as_f32(const HostTensor &t) {
+    if (t.type == W_Q4_0 || t.type == W_Q4_1) return table_as_f32(t);
+    const size_t n = (size_t)t.ne0 * t.ne1;
+    std::vector<float> v(n);
+    if (t.type == W_F32) memcpy(v.data(), t.data, n * 4);
+    else
+        for (size_t i = 0; i < n; ++i) { _Float16 h; memcpy(&h, t.data + 2 * i, 2); v[i] = (float)h; }
+    return v;
+}
+
 std::vector<_Float16> pack_f16_image(const StackedRows &s, int64_t n_rows) {
     std::vector<_Float16> img((size_t)n_rows * s.K, (_Float16)0);
     s.for_each_row([&](int64_t n, const uint8_t *src) { row_to_f16(s.type, s.K, src, img.data() + (size_t)n * s.K); });
@@ -342,6 +352,17 @@ std::unique_ptr<ModelWeights> ModelWeights::load(const ModelFile &mf, const Load
                  L.o_gb.upload(pack_gamma_beta_bias(g2.data(), b2.data(), bo.data(), H), err);
         }
         L.fold_ok = ok && L.ffi_fold.mfma_ok && (i == 0 || L.qkv_fold.mfma_ok);
+    }
+    // the classification head (ModelFile::load: all four tensors or none, shapes checked)
+    if (ok && mf.n_labels > 0) {
+        const HostTensor *wp = mf.find("pooler.dense.weight"), *bp = mf.find("pooler.dense.bias"), *wc = mf.find("classifier.weight"),
+                         *bc = mf.find("classifier.bias");
+        if (!wp || !bp || !wc || !bc) { err = "the classification head is incomplete"; return nullptr; }
+        StackedRows s;
+        ok = s.stack({wp}, err) && w->head_wp16.upload(pack_f16_image(s, s.N), err) && upload_tensor(w->head_bp, bp, err) &&
+             w->head_wc.upload(tensor_as_f32(*wc), err) && upload_tensor(w->head_bc, bc, err);
+        if (ok && w->f32_file) ok = upload_tensor(w->head_wp32, wp, err);
+        w->n_labels = mf.n_labels;
     }
     if (!ok) return nullptr;
     return w;

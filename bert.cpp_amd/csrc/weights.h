@@ -83,6 +83,8 @@ LnFoldImage pack_ln_fold(const StackedRows &s, const float *gamma, const float *
 std::vector<uint32_t> pack_gamma_beta_bias(const float *gamma, const float *beta, const float *bias, int64_t n);
 // an embedding table of a q4 file as f32 values, the numbers the gather kernel dequantises on the fly
 std::vector<float> table_as_f32(const HostTensor &t);
+// any file tensor as f32 values [ne1][ne0]: f32 as stored, f16 widened, q4 as table_as_f32
+std::vector<float> tensor_as_f32(const HostTensor &t);
 
 // ------------------------------------------------------------------------------------------------
 // images on the device
@@ -136,6 +138,11 @@ struct ModelWeights {
     bool f32_file = false;                // every matrix and table of the file is f32: the f32 route can take it
     bool fold_images = false;             // the LayerNorm-folding images were built (LoadOptions::ln_fold)
     bool naive_images() const;            // every matrix has GemmWeight::naive16
+    // The classification head of the file, if it has one (model_file.h; cls_head.hip): Wp [H][H] as f16 (the file's f16 bits, or its
+    // f32 / q4 values rounded once: row_to_f16), and for f32 files also its own f32 rows (the f32 route); bp [H], Wc [n_labels][H],
+    // bc [n_labels] as f32 (q4 / f16 classifiers dequantised at load).  n_labels == 0: no head, nothing uploaded.
+    int n_labels = 0;
+    DevBuf head_wp16, head_wp32, head_bp, head_wc, head_bc;
     // uploads to the current device
     static std::unique_ptr<ModelWeights> load(const ModelFile &mf, const LoadOptions &opt, std::string &err);
 };

@@ -4,7 +4,12 @@
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
-//               [--long [--window W] [--stride S]] [--maxsim N]
+//               [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]
+//   (--cross-model PATH --cross N: cross-encoder reranking.  PATH is a second model file, one with a classification head (bert_hip.h
+//   "sentence pairs and scores"), loaded into a context of its own.  The stages above return N candidates per query line instead of k
+//   (k <= N <= 256, and N <= --rescore's); bert_hip_score_pairs scores the pairs (query line, candidate line) — each pair read as one
+//   sentence, cut at the cross-encoder's position limit —, and the k lines printed are the best by the first label's logit, which is
+//   shown; equal scores keep the first stage's order.  Not together with --maxsim.)
 //   (--maxsim N: late-interaction reranking.  The stages above return N candidates per query line instead of k (k <= N <= 256, and
 //   N <= --rescore's); the query and the N candidate lines go through bert_hip_encode_tokens_batch (token rows, each over its L2
 //   norm, lines cut at the model's position limit), bert_hip_maxsim scores the pairs (query, candidate j) — the sum over the query's
@@ -38,11 +43,13 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]\n", argv0);
     fprintf(stderr, "  --long: lines of any length, cut into overlapping windows of W ids, S inner ids apart, one row per line (defaults: W 128 or the\n"
                     "          model's position limit if that is less, S three quarters of W - 2).  Without --long a line is cut at the model's position limit.\n");
     fprintf(stderr, "  --maxsim N: the search returns N candidates (k <= N <= 256), which are reranked by the MaxSim score of their token rows against the\n"
                     "          query's (bert_hip_encode_tokens_batch + bert_hip_maxsim); the k best by that score are printed with it.\n");
+    fprintf(stderr, "  --cross-model PATH --cross N: the search returns N candidates (k <= N <= 256), which a cross-encoder (a model file with a classification\n"
+                    "          head) reranks: bert_hip_score_pairs on (query, candidate); the k best by the first label's logit are printed with it.\n");
 }
 
 std::string chomp(std::string s) {
@@ -52,9 +59,9 @@ std::string chomp(std::string s) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr;
-    int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0;
-    bool long_texts = false, maxsim = false;
+    const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr, *cross_model = nullptr;
+    int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0, n_cross = 0;
+    bool long_texts = false, maxsim = false, cross = false;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
         if ((!strcmp(argv[i], "-m") || !strcmp(argv[i], "--model")) && has_value) model = argv[++i];
@@ -73,16 +80,23 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--window") && has_value) window = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--stride") && has_value) stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--maxsim") && has_value) { maxsim = true; n_maxsim = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--cross-model") && has_value) cross_model = argv[++i];
+        else if (!strcmp(argv[i], "--cross") && has_value) { cross = true; n_cross = atoi(argv[++i]); }
         else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
     }
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
     if (!long_texts && (window || stride)) { fprintf(stderr, "search: --window and --stride go with --long\n"); return 2; }
     if (maxsim && (n_maxsim < k || n_maxsim > 256)) { fprintf(stderr, "search: --maxsim must be -k .. 256\n"); return 2; }
+    if (cross != (cross_model != nullptr)) { fprintf(stderr, "search: --cross-model and --cross go together\n"); return 2; }
+    if (cross && maxsim) { fprintf(stderr, "search: --cross and --maxsim exclude each other\n"); return 2; }
+    if (cross && (n_cross < k || n_cross > 256)) { fprintf(stderr, "search: --cross must be -k .. 256\n"); return 2; }
     const int k_print = k;
     if (maxsim) k = n_maxsim;                                 // (what the stages below return; k_print lines come out of the reranking)
+    if (cross) k = n_cross;
     const bool two_stage = n_cand != 0;
     if (two_stage && (n_cand < k || n_cand > 256)) { fprintf(stderr, "search: --rescore must be %s .. 256\n", maxsim ? "--maxsim's N" : "-k"); return 2; }
+    if (two_stage && cross && n_cand < k) { fprintf(stderr, "search: --rescore must be --cross's N .. 256\n"); return 2; }
 
     if (n_lists < 0 || n_lists > 65536) { fprintf(stderr, "search: --lists must be 1 .. 65536\n"); return 2; }
     // (against the lists themselves once they are there: they may come from --load PATH's PATH.part)
@@ -95,6 +109,17 @@ int main(int argc, char **argv) {
     if (!ctx) {
         fprintf(stderr, "search: failed to load model from '%s'\n", model);
         return 1;
+    }
+    // the cross-encoder: a context of its own (frees: at exit, behind ctx)
+    bert_ctx *cross_ctx = nullptr;
+    if (cross) {
+        cross_ctx = bert_load_from_file(cross_model);
+        if (!cross_ctx || bert_hip_n_labels(cross_ctx) < 1) {
+            fprintf(stderr, "search: '%s' %s\n", cross_model, cross_ctx ? "has no classification head" : "failed to load");
+            if (cross_ctx) bert_free(cross_ctx);
+            bert_free(ctx);
+            return 1;
+        }
     }
     printf("Loading texts from %s...\n", file);
     std::ifstream in(file);
@@ -251,10 +276,31 @@ int main(int argc, char **argv) {
             for (int i = 0; i < k_print && i < n_found; ++i) printf("%d. %s\n (MaxSim score: %.4f)\n", i + 1, texts[ids[order[i]]].c_str(), ms[order[i]]);
             continue;
         }
+        if (cross) {
+            int n_found = 0;
+            while (n_found < k && ids[n_found] >= 0) ++n_found;
+            const int32_t NL = bert_hip_n_labels(cross_ctx);
+            std::vector<const char *> qs((size_t)n_found, qp), ds;
+            for (int j = 0; j < n_found; ++j) ds.push_back(texts[ids[j]].c_str());
+            std::vector<float> cs((size_t)n_found * NL);
+            if (n_found > 0 && bert_hip_score_pairs(cross_ctx, n_threads, n_found, qs.data(), ds.data(), 0, cs.data()) != n_found) {
+                fprintf(stderr, "search: the cross-encoder reranking failed\n");
+                bert_free(cross_ctx);
+                bert_free(ctx);
+                return 1;
+            }
+            std::vector<int> order((size_t)n_found);
+            for (int j = 0; j < n_found; ++j) order[j] = j;
+            std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cs[(size_t)x * NL] > cs[(size_t)y * NL]; });
+            printf("\nClosest texts:\n");
+            for (int i = 0; i < k_print && i < n_found; ++i) printf("%d. %s\n (cross-encoder score: %.4f)\n", i + 1, texts[ids[order[i]]].c_str(), cs[(size_t)order[i] * NL]);
+            continue;
+        }
         printf("\nClosest texts:\n");
         for (int i = 0; i < k && ids[i] >= 0; ++i) printf("%d. %s\n (similarity score: %.4f)\n", i + 1, texts[ids[i]].c_str(), scores[i]);
     }
     printf("\n");
+    if (cross_ctx) bert_free(cross_ctx);
     bert_free(ctx);                                           // (frees the index as well)
     return 0;
 }

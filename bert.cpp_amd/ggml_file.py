@@ -167,6 +167,16 @@ def tensor_names(n_layer: int) -> List[str]:
     return names
 
 
+# The optional classification head (BertForSequenceClassification), written behind the encoder's tensors: all four or none.
+HEAD_NAMES = ["pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"]
+HEAD_MAX_LABELS = 8
+
+
+def head_shapes(hp: BertHParams, n_labels: int) -> Dict[str, Tuple[int, ...]]:
+    H = hp.n_embd
+    return {"pooler.dense.weight": (H, H), "pooler.dense.bias": (H,), "classifier.weight": (n_labels, H), "classifier.bias": (n_labels,)}
+
+
 def tensor_shape(name: str, hp: BertHParams) -> Tuple[int, ...]:
     """numpy (row-major, [out, in]) shape of each tensor."""
     H, I = hp.n_embd, hp.n_intermediate
@@ -187,8 +197,10 @@ def tensor_shape(name: str, hp: BertHParams) -> Tuple[int, ...]:
     return (H,)
 
 
-def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive") -> Dict[str, np.ndarray]:
+def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive", n_labels: int = 0) -> Dict[str, np.ndarray]:
     """Seeded random f32 weights of the BERT architecture.
+
+    n_labels > 0 adds a classification head (HEAD_NAMES), drawn after everything else: a seed gives the same encoder with and without it.
 
     style="sensitive": fan-in scaled matrices with O(1) activations, spread-out attention scores,
     non-trivial biases and LayerNorm affine terms, so that a wrong softmax / bias / LN path moves
@@ -217,6 +229,13 @@ def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive") 
             else:
                 a = rng.normal(0.0, 0.1, shp)
         out[name] = a.astype(np.float32)
+    if n_labels:
+        for name, shp in head_shapes(hp, n_labels).items():
+            if style == "hf":
+                a = rng.normal(0.0, 0.02, shp) if len(shp) == 2 else np.zeros(shp)
+            else:
+                a = rng.normal(0.0, 1.0 / np.sqrt(shp[1]), shp) if len(shp) == 2 else rng.normal(0.0, 0.1, shp)
+            out[name] = a.astype(np.float32)
     return out
 
 
@@ -260,9 +279,16 @@ def write_model(path: str, hp: BertHParams, weights: Dict[str, np.ndarray], ftyp
         for tok in vocab:
             f.write(struct.pack("<I", len(tok)))
             f.write(tok)
-        for name in tensor_names(hp.n_layer):
+        names = tensor_names(hp.n_layer)
+        head = [n for n in HEAD_NAMES if n in weights]
+        if head:
+            assert head == HEAD_NAMES, f"partial classification head: {head}"
+            n_labels = int(np.asarray(weights["classifier.weight"]).shape[0])
+            assert 1 <= n_labels <= HEAD_MAX_LABELS, n_labels
+            names = names + HEAD_NAMES
+        for name in names:
             a = np.asarray(weights[name], dtype=np.float32)
-            assert a.shape == tensor_shape(name, hp), (name, a.shape)
+            assert a.shape == (head_shapes(hp, n_labels)[name] if name in HEAD_NAMES else tensor_shape(name, hp)), (name, a.shape)
             two_d = a.ndim == 2
             t = ftype if two_d else FTYPE_F32
             nm = name.encode()
@@ -327,11 +353,20 @@ def read_model(path: str) -> ModelFile:
 
 
 def make_synthetic_model(path: str, dims: str | BertHParams, ftype: str | int, seed: int = 0,
-                         style: str = "sensitive") -> BertHParams:
+                         style: str = "sensitive", n_labels: int = 0) -> BertHParams:
     hp = MODEL_DIMS[dims] if isinstance(dims, str) else dims
     ft = FTYPE_BY_NAME[ftype] if isinstance(ftype, str) else ftype
-    write_model(path, hp, synthetic_weights(hp, seed, style), ft)
+    write_model(path, hp, synthetic_weights(hp, seed, style, n_labels), ft)
     return hp
+
+
+def hf_classifier_weights(state_dict, n_layer: int) -> Dict[str, np.ndarray]:
+    """The tensors of a HuggingFace BertForSequenceClassification state dict under this format's names ('bert.' stripped; the head's
+    names are HF's own).  Values may be torch tensors or arrays."""
+    def arr(v):
+        return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+    sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in state_dict.items()}
+    return {n: arr(sd[n]) for n in tensor_names(n_layer) + HEAD_NAMES}
 
 
 def synthetic_token_ids(n_sentences: int, seq_len: int, n_vocab: int, seed: int) -> np.ndarray:

@@ -38,6 +38,8 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_eval_packed_grouped", "bert_hip_eval_packed_grouped_device", "bert_hip_tokenize_long", "bert_hip_plan_windows",
     "bert_hip_encode_long_batch", "bert_hip_index_add_long_texts",
     "bert_hip_eval_packed_tokens_device", "bert_hip_eval_packed_tokens", "bert_hip_encode_tokens_batch", "bert_hip_maxsim_device", "bert_hip_maxsim",
+    "bert_hip_n_labels", "bert_hip_tokenize_pair", "bert_hip_eval_packed_typed", "bert_hip_eval_packed_typed_device", "bert_hip_score_packed",
+    "bert_hip_score_packed_device", "bert_hip_score_pairs",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -50,6 +52,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
     "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool", "bert_hip_test_token_rows",
+    "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -157,6 +160,14 @@ def _declare_product_abi(L):
     L.bert_hip_encode_tokens_batch.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32p, f32p, C.c_int64]
     L.bert_hip_maxsim_device.restype = i32; L.bert_hip_maxsim_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
     L.bert_hip_maxsim.restype = i32; L.bert_hip_maxsim.argtypes = [vp, f32p, i32p, i32, f32p, i32p, i32, i32, i32p, i32, i32, f32p]
+    L.bert_hip_n_labels.restype = i32; L.bert_hip_n_labels.argtypes = [vp]
+    L.bert_hip_tokenize_pair.restype = i32; L.bert_hip_tokenize_pair.argtypes = [vp, C.c_char_p, C.c_char_p, i32p, i32p, i32p, i32]
+    L.bert_hip_eval_packed_typed.restype = i32; L.bert_hip_eval_packed_typed.argtypes = [vp, i32p, i32p, i32p, i32, f32p]
+    L.bert_hip_eval_packed_typed_device.restype = i32; L.bert_hip_eval_packed_typed_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.bert_hip_score_packed.restype = i32; L.bert_hip_score_packed.argtypes = [vp, i32p, i32p, i32p, i32, i32, f32p]
+    L.bert_hip_score_packed_device.restype = i32; L.bert_hip_score_packed_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.bert_hip_score_pairs.restype = i32
+    L.bert_hip_score_pairs.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32, f32p]
 
 
 def lib() -> C.CDLL:
@@ -257,6 +268,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_group_pool.argtypes = [vp, i32, i32p, i32p, i32, i32, i32, vp, i32p]
     L.bert_hip_test_token_rows.restype = i32
     L.bert_hip_test_token_rows.argtypes = [vp, i32, i32, i32, i32p, i32, i32, i32, vp]
+    L.bert_hip_test_embed_ln_typed.restype = i32
+    L.bert_hip_test_embed_ln_typed.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32p, i32p, i32, i32, vp, i32, vp]
+    L.bert_hip_test_cls_head.restype = i32
+    L.bert_hip_test_cls_head.argtypes = [i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp]
     _test_lib = L
     return L
 
@@ -284,6 +299,52 @@ def test_embed_ln_lanes(table_type: int, word_bytes, type_bytes, pos_bytes, H: i
     """The lane-order form (launch_embed_ln_lanes) on test_embed_ln's arguments: the float16 [T, H] halves as the kernel stored them
     (tests/lane_order.py puts them back into rows), or None where the launcher declines the shape and launches nothing."""
     return test_embed_ln(table_type, word_bytes, type_bytes, pos_bytes, H, gamma, beta, tokens, cu_seqlens, max_len, lanes=True)
+
+
+EMBED_FORMS = {"grid": 0, "search": 1, "generic": 2, "lanes": 3, "f32": 4}
+
+
+def test_embed_ln_typed(table_type: int, word_bytes, type_bytes, pos_bytes, H: int, gamma, beta, tokens, cu_seqlens, first_len, form: str,
+                        max_len: int = 0):
+    """An embedding kernel with token types (bert_hip_test.h): test_embed_ln's arguments, first_len (int per sentence, or None: the
+    untyped instantiation) and the form, a key of EMBED_FORMS.  float16 [T, H] (float32 for "f32"; "lanes": as the kernel stored them), or
+    None where the form does not take the shape."""
+    wb, tb, pb = (np.ascontiguousarray(a) for a in (word_bytes, type_bytes, pos_bytes))
+    rb = {0: 4 * H, 1: 2 * H, 2: H // 32 * 18, 3: H // 32 * 20}[table_type]
+    g = np.ascontiguousarray(gamma, dtype=np.float32); b = np.ascontiguousarray(beta, dtype=np.float32)
+    toks = np.ascontiguousarray(tokens, dtype=np.int32); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    fl = None if first_len is None else np.ascontiguousarray(first_len, dtype=np.int32)
+    assert len(toks) == int(cu[-1]) and tb.nbytes == 2 * rb and g.shape == (H,) and b.shape == (H,) and (fl is None or len(fl) == len(cu) - 1)
+    out = np.zeros((len(toks), H), dtype=np.float32 if form == "f32" else np.float16)
+    r = test_lib().bert_hip_test_embed_ln_typed(table_type, H, wb.nbytes // rb, pb.nbytes // rb, wb.ctypes.data, tb.ctypes.data, pb.ctypes.data,
+                                                g.ctypes.data, b.ctypes.data, _i32p(toks), _i32p(cu), len(cu) - 1, max_len,
+                                                None if fl is None else fl.ctypes.data, EMBED_FORMS[form], out.ctypes.data)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_embed_ln_typed failed: {r}")
+    return out
+
+
+def test_cls_head(rows, Wp, bp, Wc, bc, flags: int = 0, form: str = "mfma"):
+    """The classification head on its own: rows float32 [B, H]; Wp [H, H] float16 or float32 (its dtype says which image the kernel
+    reads); bp [H], Wc [n_labels, H], bc [n_labels] float32; form "mfma" or "plain".  float32 [B, n_labels], or None where the form does
+    not take the shape."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    Wp = np.ascontiguousarray(Wp)
+    assert Wp.dtype in (np.float16, np.float32)
+    bp, Wc, bc = (np.ascontiguousarray(a, dtype=np.float32) for a in (bp, Wc, bc))
+    B, H = rows.shape
+    NL = Wc.shape[0]
+    assert Wp.shape == (H, H) and bp.shape == (H,) and Wc.shape == (NL, H) and bc.shape == (NL,)
+    out = np.full((B, NL), np.nan, dtype=np.float32)
+    r = test_lib().bert_hip_test_cls_head(B, H, NL, rows.ctypes.data, Wp.ctypes.data, int(Wp.dtype == np.float32), bp.ctypes.data, Wc.ctypes.data,
+                                          bc.ctypes.data, flags, {"mfma": 0, "plain": 1}[form], out.ctypes.data)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_cls_head failed: {r}")
+    return out
 
 
 def test_layernorm(x: np.ndarray, gamma, beta) -> np.ndarray:
@@ -583,6 +644,84 @@ class BertModel:
 
     def n_devices(self) -> int:
         return self.lib.bert_hip_n_devices(self.ctx)
+
+    # ---- sentence pairs and scores --------------------------------------------------------
+    @property
+    def n_labels(self) -> int:
+        """Labels of the model's classification head, 0 without one."""
+        return self.lib.bert_hip_n_labels(self.ctx)
+
+    def tokenize_pair(self, a: str | bytes, b: str | bytes, n_max_tokens: Optional[int] = None):
+        """(ids, first_len) of [CLS] a [SEP] b [SEP], cut to n_max_tokens (tokenizer-only contexts too)."""
+        n_max = n_max_tokens or self.n_max_tokens
+        buf = np.zeros(max(n_max, 4), dtype=np.int32)
+        n, fl = C.c_int32(0), C.c_int32(0)
+        da, db = (t if isinstance(t, bytes) else t.encode("utf-8") for t in (a, b))
+        r = self.lib.bert_hip_tokenize_pair(self.ctx, da, db, _i32p(buf), C.byref(n), C.byref(fl), n_max)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_tokenize_pair failed: {r}")
+        return buf[: n.value].tolist(), fl.value
+
+    def eval_packed_typed(self, tokens: np.ndarray, cu_seqlens: np.ndarray, first_len=None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """eval_packed with token types: first_len[b] leading tokens of sentence b take type 0, the rest type 1 (None: all type 0)."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+        fl = None if first_len is None else np.ascontiguousarray(first_len, dtype=np.int32)
+        B = len(cu) - 1
+        if out is None:
+            out = np.full((B, self.n_embd), np.nan, dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (B, self.n_embd) and (fl is None or len(fl) == B)
+        r = self.lib.bert_hip_eval_packed_typed(self.ctx, _i32p(tokens), _i32p(cu), None if fl is None else _i32p(fl), B, _f32p(out))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_eval_packed_typed failed: {r}")
+        return out
+
+    def eval_packed_typed_device(self, d_tokens_ptr: int, d_cu_ptr: int, d_first_len_ptr: Optional[int], n_sentences: int, n_tokens: int,
+                                 max_len: int, d_out_ptr: int, stream: int = 0) -> None:
+        r = self.lib.bert_hip_eval_packed_typed_device(self.ctx, d_tokens_ptr, d_cu_ptr, d_first_len_ptr, n_sentences, n_tokens, max_len, d_out_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_eval_packed_typed_device failed: {r}")
+
+    def score_packed(self, tokens: np.ndarray, cu_seqlens: np.ndarray, first_len=None, sigmoid: bool = False, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Cross-encoder scores [B, n_labels] of a packed, typed batch: the logits, or 1 / (1 + exp(-logit)) with sigmoid."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+        fl = None if first_len is None else np.ascontiguousarray(first_len, dtype=np.int32)
+        B = len(cu) - 1
+        if out is None:
+            out = np.full((B, max(self.n_labels, 1)), np.nan, dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and (fl is None or len(fl) == B)
+        r = self.lib.bert_hip_score_packed(self.ctx, _i32p(tokens), _i32p(cu), None if fl is None else _i32p(fl), B, int(sigmoid), _f32p(out))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_score_packed failed: {r}")
+        return out
+
+    def score_packed_device(self, d_tokens_ptr: int, d_cu_ptr: int, d_first_len_ptr: Optional[int], n_sentences: int, n_tokens: int, max_len: int,
+                            d_scores_ptr: int, sigmoid: bool = False, stream: int = 0) -> None:
+        r = self.lib.bert_hip_score_packed_device(self.ctx, d_tokens_ptr, d_cu_ptr, d_first_len_ptr, n_sentences, n_tokens, max_len, int(sigmoid),
+                                                  d_scores_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_score_packed_device failed: {r}")
+
+    def score_pairs(self, pairs: Sequence, sigmoid: bool = False, n_threads: int = 6) -> np.ndarray:
+        """Scores [n, n_labels] of (a, b) text pairs: tokenize_pair at the model's n_max_tokens, then score_packed."""
+        n = len(pairs)
+        enc = lambda t: t if isinstance(t, bytes) else t.encode("utf-8")
+        ta = (C.c_char_p * n)(*[enc(p[0]) for p in pairs])
+        tb = (C.c_char_p * n)(*[enc(p[1]) for p in pairs])
+        out = np.full((n, max(self.n_labels, 1)), np.nan, dtype=np.float32)
+        r = self.lib.bert_hip_score_pairs(self.ctx, n_threads, n, ta, tb, int(sigmoid), _f32p(out))
+        if r != n:
+            raise RuntimeError(f"bert_hip_score_pairs scored {r} of {n} pairs")
+        return out
+
+    def rerank(self, query: str | bytes, docs: Sequence, top_k: Optional[int] = None):
+        """(order, scores): the documents' indices by the first label's score, descending, ties by index; the scores in that order."""
+        s = self.score_pairs([(query, d) for d in docs])[:, 0] if len(docs) else np.zeros(0, dtype=np.float32)
+        order = np.argsort(-s, kind="stable")
+        if top_k is not None:
+            order = order[:top_k]
+        return order, s[order]
 
     # ---- long texts -----------------------------------------------------------------------
     def tokenize_long(self, text: str | bytes) -> List[int]:

@@ -318,6 +318,58 @@ BERT_API int32_t bert_hip_maxsim_device(struct bert_ctx *ctx, const void *d_q, c
 BERT_API int32_t bert_hip_maxsim(struct bert_ctx *ctx, const float *q, const int32_t *qcu, int32_t n_q, const float *d, const int32_t *dcu,
                                  int32_t n_d, int32_t H, const int32_t *pairs, int32_t n_pairs, int32_t mode, float *scores);
 
+/* SENTENCE PAIRS AND SCORES.  A cross-encoder reads a query and a document as ONE sentence, [CLS] a [SEP] b [SEP], with token type 0 on
+ * the first segment and 1 on the second, and ends in a classification head: logits = Wc tanh(Wp h_CLS + bp) + bc, h_CLS the
+ * un-normalised final state of [CLS] (HuggingFace BertForSequenceClassification; cross-encoder/ms-marco-MiniLM-L-6-v2 is one, with the
+ * geometry of the MiniLM bi-encoders).  Nothing above changes its behaviour or its bits.
+ *
+ * The model file.  Four optional tensors behind the encoder's set, all or none: pooler.dense.weight [n_embd, n_embd], pooler.dense.bias
+ * [n_embd], classifier.weight [n_embd, n_labels], classifier.bias [n_labels] (ne0 = in-features; 2-D tensors in the file's type, 1-D
+ * in f32; 1 <= n_labels <= 8).  bert_hip_n_labels: the labels of the context's head, 0 without one.
+ *
+ * Token types.  first_len[b] is the number of leading tokens of sentence b that take row 0 of the token-type table; every token at a
+ * place at or behind it takes row 1.  first_len NULL: row 0 everywhere, and then a typed call returns the untyped call's bits.  The
+ * host forms want 0 <= first_len[b] <= the sentence's length (-2 otherwise); the device forms take any value (<= 0: all row 1; >= the
+ * length: all row 0).  A typed pass plans and runs like any other pass; only its embedding launch differs.
+ *   eval_packed_typed[_device]  bert_hip_eval_packed[_device] with types: the context's pooling, normalisation and routes.  For any BERT
+ *                               that was trained with segments.
+ *
+ * Scores.  score_packed[_device] run a typed pass that ends in the [CLS] rows and launch the head on them ("cls_head" in
+ * bert_hip_profile_report): scores [n_sentences][n_labels] f32.  flags 0: the logits; 1: 1 / (1 + exp(-logit)) per label (what
+ * sentence-transformers' CrossEncoder applies for n_labels == 1).  The context's "pooling" / "normalize" do not enter.  The head runs
+ * on the matrix cores for n_embd % 8 == 0, n_embd <= 1024 — the [CLS] rows and Wp rounded to f16, f32 accumulation — and in plain f32
+ * for f32 files on the f32 route and any other n_embd.  Its sums run in one fixed order without atomics: a pair's scores have the same
+ * bits alone, anywhere in a batch and in any batch size.  -2 after a line on stderr, nothing written, for a model without a head.
+ *   *_device   the rules of bert_hip_eval_packed_device: everything in HBM on the first device, enqueued on `stream`; after
+ *              bert_hip_reserve they allocate nothing and may be captured into a graph.
+ *   host forms blocking, on the context's FIRST device (a multi-device context does not spread these calls).  Cut at
+ *              BERT_HIP_CHUNK_TOKENS between sentences, one plain copy per chunk and direction.  0; -1 without a device; -2 with the
+ *              outputs untouched for a sentence that cannot be evaluated or a first_len outside [0, length]; -3 on a device error.
+ *
+ * Pairs of texts.
+ *   tokenize_pair  a is tokenized as bert_tokenize does, [CLS] .. [SEP]; b likewise, losing its [CLS]; tokens = a's ids, then b's;
+ *                  *first_len = the count of a's ids.  When the two exceed n_max_tokens (>= 4; tokens must hold that many), a is cut
+ *                  to at most n_max_tokens / 2 ids and b to the remainder, each cut keeping its [SEP] last.  Works on tokenizer-only
+ *                  contexts.  0, or -2 for a bad argument.
+ *   score_pairs    both sides tokenized on up to n_threads host threads, paired by tokenize_pair's rule at the model's n_max_tokens,
+ *                  packed and scored: scores [n_pairs][n_labels].  Returns the number of pairs scored (bert_hip_encode_batch's
+ *                  conventions: it stops at the first failure, later outputs untouched), -1 without a device, -2 without a head.   */
+BERT_API int32_t bert_hip_n_labels(struct bert_ctx *ctx);
+BERT_API int32_t bert_hip_tokenize_pair(struct bert_ctx *ctx, const char *text_a, const char *text_b, bert_vocab_id *tokens, int32_t *n_tokens,
+                                        int32_t *first_len, int32_t n_max_tokens);
+BERT_API int32_t bert_hip_eval_packed_typed(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens, const int32_t *first_len,
+                                            int32_t n_sentences, float *embeddings);
+BERT_API int32_t bert_hip_eval_packed_typed_device(struct bert_ctx *ctx, const bert_vocab_id *d_tokens, const int32_t *d_cu_seqlens,
+                                                   const int32_t *d_first_len, int32_t n_sentences, int32_t n_tokens_total, int32_t max_len,
+                                                   float *d_embeddings, void *stream);
+BERT_API int32_t bert_hip_score_packed(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens, const int32_t *first_len,
+                                       int32_t n_sentences, int32_t flags, float *scores);
+BERT_API int32_t bert_hip_score_packed_device(struct bert_ctx *ctx, const bert_vocab_id *d_tokens, const int32_t *d_cu_seqlens,
+                                              const int32_t *d_first_len, int32_t n_sentences, int32_t n_tokens_total, int32_t max_len,
+                                              int32_t flags, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_score_pairs(struct bert_ctx *ctx, int32_t n_threads, int32_t n_pairs, const char **texts_a, const char **texts_b,
+                                      int32_t flags, float *scores);
+
 /* Embedding index: rows in HBM on the context's FIRST device (bert_hip_device), exact top-k search by inner product.
  * An index belongs to the context it was made from: bert_free frees any index the caller left alive.  Like every
  * entry point of a context, the index functions are not re-entrant on one context.

@@ -234,6 +234,23 @@ BERT_API int32_t bert_hip_test_build_lists(const int32_t *list_of, int32_t n, in
 BERT_API int32_t bert_hip_test_token_rows(const void *x, int32_t is_f32, int32_t T, int32_t H, const int32_t *cu_seqlens, int32_t n_sentences,
                                           int32_t max_len, int32_t flags, void *out);
 
+/* The embedding kernels with token types (bert_hip.h "sentence pairs and scores"): the arguments of bert_hip_test_embed_ln, _embed_ln_lanes
+ * and _f32_embed_ln, plus first_len [n_sentences] (nullable: the untyped instantiation; any value is legal, type [2][H] has both rows
+ * read) and the form: 0 the rows kernel on its (group, sentence) grid, 1 the rows kernel with the bisection, 2 the generic kernel, 3 the
+ * lane-order kernel (out as _embed_ln_lanes stores it), 4 the f32 route's (table_type 0 only; out [T][H] f32, else f16 bits).  The
+ * padding and the -4 check of those entries apply.  -2, and nothing is launched, for a shape the form does not take.                */
+BERT_API int32_t bert_hip_test_embed_ln_typed(int32_t table_type, int32_t H, int32_t n_vocab, int32_t n_pos, const void *word,
+                                              const void *type, const void *pos, const float *gamma, const float *beta,
+                                              const bert_vocab_id *tokens, const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len,
+                                              const int32_t *first_len, int32_t form, void *out);
+/* The classification head on its own (kernels.h launch_cls_head / launch_cls_head_f32): rows [B][H] f32, Wp [H][H] as f16 bits
+ * (wp_is_f32 0) or f32 (1), bp [H], Wc [n_labels][H], bc [n_labels], flags bit 0 the sigmoid; form 0 the matrix-core kernel (f16 Wp, H % 8
+ * == 0, H <= 1024), 1 the plain one; out [B][n_labels].  The device copy of the rows runs one block of 32 sentences past the last whole
+ * one, holding pattern32 of bert_hip_test_set_pad, as every word of the output does before the launch; -4 if a word behind the last
+ * sentence's scores has changed.  -2, and no launch, for a shape the form does not take.                                            */
+BERT_API int32_t bert_hip_test_cls_head(int32_t B, int32_t H, int32_t n_labels, const float *rows, const void *Wp, int32_t wp_is_f32,
+                                        const float *bp, const float *Wc, const float *bc, int32_t flags, int32_t form, float *out);
+
 #ifdef __cplusplus
 }
 #endif
