@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <functional>
 #include <memory>
@@ -56,6 +57,20 @@ public:
     // context's pooling and normalisation, out [n_sentences][H]; true: out [n_sentences][n_labels].
     int eval_packed_typed_host(const int32_t *tokens, const int32_t *cu_seqlens, const int32_t *first_len, int n_sentences, bool scores, int flags,
                                float *out, std::string &err);
+    // Learned sparse embeddings (bert_hip.h): a pass planned as a token-rows pass — its final states stay in x_ in row order, nothing is
+    // copied (eval_packed_device is handed x_ itself as the rows' destination) —, then the MLM transform t = LayerNorm(gelu(x Wt^T + bt))
+    // into ctx_, free behind the pass ("mlm_transform", "mlm_layernorm" in the profile: launch_gemm_mfma / _naive + launch_layernorm, or
+    // the f32 route's two), then the vocabulary launch on the tied word embeddings (sparse_vocab.hip: "sparse_vocab" + "sparse_finish";
+    // the plain form on the f32 route and for an H the other refuses).  k == 0: d_weights f32 [n_sentences][n_vocab], d_ids unused.
+    // 1 <= k <= SPARSE_MAX_K: the head runs in chunks of sparse_chunk() sentences into sparse_dense_ and "sparse_topk" selects from
+    // each: d_ids i32 [n_sentences][k], d_weights f32 [n_sentences][k].  -2 with a message for a model without the head.  After
+    // reserve() it allocates nothing: reserve fixes the chunk and sizes sparse_dense_ with the workspace.
+    bool has_mlm_head() const { return w_->mlm_head; }
+    int sparse_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int n_sentences, int n_tokens, int max_len, int k, int32_t *d_ids,
+                             float *d_weights, hipStream_t stream, std::string &err);
+    // Host form, blocking, on this engine's device: cut at chunk_tokens between sentences and at the sentences whose results fit 32 MiB,
+    // one plain copy per chunk and direction.  k == 0: weights [n_sentences][n_vocab], ids unused.
+    int sparse_packed_host(const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int k, int32_t *ids, float *weights, std::string &err);
     // Token rows (bert_hip.h "token rows and late interaction"): a pass with one more destination, [n_tokens][H] rows of the final states
     // (kernels.h launch_token_rows, TOKEN_ROWS_* flags), written by one launch ("token_rows" in the profile) beside the pooling launch.
     // Such a pass does not take the one-launch kernel (which keeps x on chip between its phases and pools inside the launch: the other
@@ -117,6 +132,9 @@ public:
 private:
     Engine() = default;
     bool ensure_workspace(int t_pad, int n_sentences, std::string &err);
+    // sentences whose dense rows [n_vocab] f32 fit 32 MiB, at least one: what bounds sparse_dense_ and a host chunk's results
+    int sparse_sentence_cap() const { return std::max(1, (int)(((size_t)32 << 20) / ((size_t)hp_.n_vocab * 4))); }
+    bool ensure_sparse(int n_sentences, std::string &err);    // grows sparse_chunk_ (never past the cap) and sparse_dense_ with it
 
     // The forward pass: plan() decides everything once, before the first launch; a forward_* method per route only launches.
     enum class Route { F32, LATENCY, ONE_LAUNCH, FOLDED, LAYERED };
@@ -169,6 +187,8 @@ private:
     // workspace (grow-only)
     DevBuf x_, qkv_, ctx_, y_, ff_, v32_, d_tokens_, d_cu_, d_out_, d_hidden_, status_, windows_;
     DevBuf typed_in_, typed_out_;                             // the host forms of the typed pass: a chunk's ids | cu_seqlens | first_len, and its rows or scores
+    DevBuf sparse_dense_, sparse_in_, sparse_out_;           // learned sparse embeddings: the top-k form's dense rows [sparse_chunk_][n_vocab] f32; the host form's ids | cu_seqlens and its results
+    int sparse_chunk_ = 0;
     DevBuf tok_in_, tok_rows_;                                // the host form of the token rows: a chunk's ids | cu_seqlens, and its rows
     DevBuf raw_rows_, group_in_, group_out_;                  // grouped pooling: the sentences' POOL_RAW rows [n_sentences][H] f32; the host form's cu_seqlens | group_cu and its groups' rows
     DevBuf ln_stats1_, ln_stats2_, ln_rows1_, ln_rows2_;      // LayerNorm folding: per-row partial statistics / finalized rows of the two LayerNorms of a layer

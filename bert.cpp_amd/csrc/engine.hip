@@ -53,7 +53,7 @@ Engine::~Engine() {
 bool Engine::reserve(int n_tokens, int n_sentences, std::string &err) {
     HIP_OK(hipSetDevice(device_), err, false);
     if (n_tokens <= 0 || n_sentences <= 0) return true;
-    return ensure_workspace((n_tokens + 255) / 256 * 256, n_sentences, err);
+    return ensure_workspace((n_tokens + 255) / 256 * 256, n_sentences, err) && (!w_->mlm_head || ensure_sparse(n_sentences, err));
 }
 
 int Engine::check(std::string &err) {
@@ -168,7 +168,8 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     }
     if (!ok) return -1;
     // (every route a token-rows pass can take left the final states in x_, [T][H] in row order: f32 on the f32 route, else f16)
-    if (d_token_rows)
+    // (a destination that IS x_: the caller wants them where they are — the sparse head —, nothing to copy)
+    if (d_token_rows && d_token_rows != x_.p)
         timed("token_rows", 0.0, s, [&] { launch_token_rows(x_.p, p.route == Route::F32, T, hp_.n_embd, d_cu, B, max_len, token_flags, d_token_rows, s); });
     HIP_OK(hipGetLastError(), err, -1);
     return op_end(op, err) ? 0 : -1;
@@ -727,6 +728,94 @@ int Engine::eval_packed_typed_host(const int32_t *tokens, const int32_t *cu, con
                                                   d_w, n_windows, slots, pool_mode, nullptr, 0, d_fl);
         if (r != 0) return fail(nullptr);
         if (hipMemcpyAsync(out + (size_t)b0 * W, typed_out_.p, (size_t)nb * W * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess) return fail("hipMemcpyAsync (results) failed");
+        HIP_OK(hipStreamSynchronize(stream_), err, -1);
+        b0 = b1;
+    }
+    return 0;
+}
+
+bool Engine::ensure_sparse(int B, std::string &err) {
+    sparse_chunk_ = std::max(sparse_chunk_, std::min(B, sparse_sentence_cap()));
+    return sparse_dense_.ensure((size_t)sparse_chunk_ * hp_.n_vocab * 4, err);
+}
+
+int Engine::sparse_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, int k, int32_t *d_ids, float *d_weights,
+                                 hipStream_t s, std::string &err) {
+    if (!w_->mlm_head) { err = "the model file has no MLM head (cls.predictions.*)"; return -2; }
+    if (B <= 0 || T <= 0) return 0;
+    HIP_OK(hipSetDevice(device_), err, -1);
+    // (the launches behind the pass are part of the same operation: one answer for all on whether s is capturing)
+    StreamOp op;
+    if (!op_begin(s, busy_, op, err)) return -1;
+    const int t_pad = (T + 255) / 256 * 256, H = hp_.n_embd, V = hp_.n_vocab;
+    if (!ensure_workspace(t_pad, B, err) || (k > 0 && !ensure_sparse(B, err))) return -1;
+    // the final states, left in x_ (its address is settled: the pass's own ensure_workspace asks for the same sizes)
+    if (eval_packed_device(d_tokens, d_cu, B, T, max_len, nullptr, s, nullptr, err, nullptr, 0, 0, -1, x_.p, 0) != 0) return -1;
+    const bool f32_route = w_->f32_file && opt_.f32_exact;
+    const GemmWeightStore &Wt = w_->mlm_wt;
+    if (f32_route) {
+        timed("mlm_transform", 2.0 * T * H * H, s, [&] { launch_f32_gemm(x_.as<float>(), Wt.w.w32, w_->mlm_bt.as<float>(), nullptr, ctx_.as<float>(), T, H, H, EPI_BIAS_GELU, s); });
+        timed("mlm_layernorm", 0.0, s, [&] { launch_f32_layernorm(ctx_.as<float>(), w_->mlm_ln_w.as<float>(), w_->mlm_ln_b.as<float>(), T, H, s); });
+    } else {
+        const bool naive = !Wt.mfma_ok || (opt_.gemm_naive && Wt.w.naive16);
+        timed("mlm_transform", 2.0 * T * H * H, s, [&] {
+            if (naive) launch_gemm_naive(Wt.w, x_.as<half_t>(), w_->mlm_bt.as<float>(), nullptr, ctx_.as<half_t>(), T, EPI_BIAS_GELU, s);
+            else launch_gemm_mfma(Wt.w, x_.as<half_t>(), w_->mlm_bt.as<float>(), nullptr, ctx_.as<half_t>(), t_pad, EPI_BIAS_GELU, s);
+        });
+        timed("mlm_layernorm", 0.0, s, [&] { launch_layernorm(ctx_.as<half_t>(), w_->mlm_ln_w.as<float>(), w_->mlm_ln_b.as<float>(), T, H, s); });
+    }
+    const bool mfma = !f32_route && sparse_vocab_mfma_supported(H);
+    SparseVocabArgs a{f32_route ? nullptr : ctx_.as<half_t>(), w_->vocab16, f32_route ? ctx_.as<float>() : nullptr, f32_route ? w_->word_emb.as<float>() : nullptr,
+                      w_->mlm_bias.as<float>(), d_cu, nullptr, 0, 0, T, H, V, max_len};
+    // sentences [s0, s0 + ns) -> out [ns][V]
+    auto head = [&](int s0, int ns, float *out) {
+        a.s0 = s0; a.ns = ns; a.out = out;
+        bool ok = true;
+        timed("sparse_vocab", 2.0 * T * V * H * ns / B, s, [&] { ok = mfma ? launch_sparse_vocab(a, s) : launch_sparse_vocab_f32(a, s); });
+        if (ok && mfma) timed("sparse_finish", 0.0, s, [&] { launch_sparse_finish(out, (size_t)ns * V, s); });
+        if (!ok) err = "sparse_vocab: no kernel for this shape (n_embd = " + std::to_string(H) + ", " + std::to_string(ns) + " sentences)";
+        return ok;
+    };
+    if (k <= 0) {
+        if (!head(0, B, d_weights)) return -1;
+    } else {
+        for (int s0 = 0; s0 < B; s0 += sparse_chunk_) {
+            const int ns = std::min(sparse_chunk_, B - s0);
+            bool ok = head(s0, ns, sparse_dense_.as<float>());
+            if (ok) timed("sparse_topk", 0.0, s, [&] { ok = launch_sparse_topk(sparse_dense_.as<float>(), ns, V, k, d_ids + (size_t)s0 * k, d_weights + (size_t)s0 * k, s); });
+            if (!ok) { if (err.empty()) err = "sparse_topk: no kernel for n_vocab = " + std::to_string(V) + ", k = " + std::to_string(k); return -1; }
+        }
+    }
+    HIP_OK(hipGetLastError(), err, -1);
+    return op_end(op, err) ? 0 : -1;
+}
+
+int Engine::sparse_packed_host(const int32_t *tokens, const int32_t *cu, int B, int k, int32_t *ids, float *weights, std::string &err) {
+    if (!w_->mlm_head) { err = "the model file has no MLM head (cls.predictions.*)"; return -2; }
+    if (B <= 0) return 0;
+    HIP_OK(hipSetDevice(device_), err, -1);
+    const size_t V = hp_.n_vocab, W = k > 0 ? (size_t)k : V;       // results per sentence (top-k: as many ids, then as many weights)
+    const int cap = k > 0 ? std::max(1, (int)(((size_t)32 << 20) / (W * 8))) : sparse_sentence_cap();
+    auto fail = [&](const char *what) { if (what) err = what; (void)hipStreamSynchronize(stream_); return -1; };      // nothing may stay queued on the caller's memory
+    std::vector<int32_t> h_cu;
+    for (int b0 = 0; b0 < B;) {
+        int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
+        while (b1 < B && b1 - b0 < cap && cu[b1 + 1] - cu[b0] <= opt_.chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
+        const int nb = b1 - b0, T = cu[b1] - cu[b0];
+        const size_t off_cu = ((size_t)T * 4 + 15) & ~(size_t)15, off_w = k > 0 ? ((size_t)nb * W * 4 + 15) & ~(size_t)15 : 0;
+        if (!sparse_in_.ensure(off_cu + (size_t)(nb + 1) * 4, err) || !sparse_out_.ensure(off_w + (size_t)nb * W * 4, err)) return fail(nullptr);
+        h_cu.resize(nb + 1);
+        for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
+        char *d_in = sparse_in_.as<char>(), *d_res = sparse_out_.as<char>();
+        // (pageable sources: both copies have left the host buffers when they return)
+        if (hipMemcpyAsync(d_in, tokens + cu[b0], (size_t)T * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+            hipMemcpyAsync(d_in + off_cu, h_cu.data(), (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, stream_) != hipSuccess)
+            return fail("hipMemcpyAsync (ids) failed");
+        if (sparse_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, k, (int32_t *)d_res, (float *)(d_res + off_w), stream_, err) != 0)
+            return fail(nullptr);
+        if ((k > 0 && hipMemcpyAsync(ids + (size_t)b0 * W, d_res, (size_t)nb * W * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess) ||
+            hipMemcpyAsync(weights + (size_t)b0 * W, d_res + off_w, (size_t)nb * W * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess)
+            return fail("hipMemcpyAsync (results) failed");
         HIP_OK(hipStreamSynchronize(stream_), err, -1);
         b0 = b1;
     }

@@ -217,6 +217,35 @@ bool cls_head_mfma_supported(int H);
 size_t cls_head_lds_bytes(int H);
 bool launch_cls_head(const ClsHeadArgs &a, hipStream_t stream);
 bool launch_cls_head_f32(const ClsHeadArgs &a, hipStream_t stream);
+// Learned sparse weights (sparse_vocab.hip; bert_hip.h "learned sparse embeddings"): t [T][H], the MLM transform of a pass's packed token
+// rows; e [V][H], the tied vocabulary matrix, row-major; bias [V] f32; cu [n_sentences + 1] cumulative lengths (device memory), of
+// which sentences s0 .. s0 + ns - 1 are served: out f32 [ns][V],
+//   out[b][v] = z > 0 ? log1pf(z) : +0,  z = (max over the tokens i of sentence s0 + b of <t_i, e_v>) + bias[v].
+// No token row at or behind T and no vocabulary row at or behind V is read.  max_len: the longest sentence the caller promises (it
+// bounds the grid; tokens of a longer sentence behind that bound do not enter).
+// launch_sparse_vocab: the matrix-core form — t16 / e16 f16, 16-byte aligned, H % 8 == 0, 8 <= H <= SPARSE_MFMA_MAX_H; the products are
+// score_chain_f16's.  It zero-fills out itself (hipMemsetAsync), combines the pieces of a sentence that spans token tiles by an integer
+// atomic max on the bits of the non-negative z (exact and commutative: no bit depends on the order of arrival), and applies log1pf in
+// place by a second launch, sparse_finish.  false, nothing enqueued, for another H.
+// launch_sparse_vocab_f32: the plain form, any H — f32 fmaf chains over k = lane, lane + 64, ..., wave_sum_f32; operands t32 / e32
+// (f32) where given, else t16 / e16; one workgroup per (sentence, 64 vocabulary entries), plain stores.
+constexpr int SPARSE_MFMA_MAX_H = 1024;
+struct SparseVocabArgs {
+    const half_t *t16, *e16;
+    const float *t32, *e32, *bias;
+    const int32_t *cu;
+    float *out;
+    int s0, ns, T, H, V, max_len;
+};
+bool sparse_vocab_mfma_supported(int H);
+size_t sparse_vocab_lds_bytes(int H);
+bool launch_sparse_vocab(const SparseVocabArgs &a, hipStream_t stream);       // the vocabulary launch alone (out: the bits of relu(z))
+void launch_sparse_finish(float *out, size_t n, hipStream_t stream);          // log1pf in place
+bool launch_sparse_vocab_f32(const SparseVocabArgs &a, hipStream_t stream);
+// Top-k terms of dense rows w [n][V] (sparse_vocab.hip): per row the k largest POSITIVE weights, larger first, equal weights smaller id
+// first; ids [n][k] (-1 in unused places), weights [n][k] (+0 there).  1 <= k <= SPARSE_MAX_K, V < 2^24.  One workgroup per row.
+constexpr int SPARSE_MAX_K = 256;
+bool launch_sparse_topk(const float *w, int n, int V, int k, int32_t *ids, float *weights, hipStream_t stream);
 void launch_maxsim(const MaxsimArgs &a, hipStream_t stream);
 // n f32 values -> f16, rounded to nearest even (the host form of MaxSim rounds its rows on the device)
 void launch_f32_to_f16(const float *src, half_t *dst, size_t n, hipStream_t stream);

@@ -72,6 +72,21 @@ std::map<std::string, Expect> head_tensors(const HParams &h) {
     return m;
 }
 
+// The optional masked-language-model head (BertForMaskedLM's transform and output bias; the decoder matrix is tied to the word
+// embeddings and not stored), all five or none, behind the encoder's set and the classification head.
+const char *const kMlmNames[5] = {"cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias",
+                                  "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias", "cls.predictions.bias"};
+std::map<std::string, Expect> mlm_tensors(const HParams &h) {
+    std::map<std::string, Expect> m;
+    const int64_t H = h.n_embd;
+    m[kMlmNames[0]] = {H, H, true};
+    m[kMlmNames[1]] = {H, 1, false};
+    m[kMlmNames[2]] = {H, 1, false};
+    m[kMlmNames[3]] = {H, 1, false};
+    m[kMlmNames[4]] = {h.n_vocab, 1, false};
+    return m;
+}
+
 }  // namespace
 
 bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
@@ -121,7 +136,9 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
     }
     const auto expect = expected_tensors(hp);
     const auto head = head_tensors(hp);
+    const auto mlm = mlm_tensors(hp);
     n_labels = 0;
+    mlm_head = false;
     tensors.clear();
     total_tensor_bytes = 0;
     // q4 files exist in two block layouts and the records carry no byte counts: the current one (18-byte q4_0 / 20-byte
@@ -166,7 +183,10 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
         auto ex = expect.find(name);
         if (ex == expect.end()) {
             ex = head.find(name);
-            if (ex == head.end()) { err = "unknown tensor '" + name + "' in model file"; return false; }
+            if (ex == head.end()) {
+                ex = mlm.find(name);
+                if (ex == mlm.end()) { err = "unknown tensor '" + name + "' in model file"; return false; }
+            }
             if (name == kHeadNames[2] && ne[0] == hp.n_embd && (ne[1] < 1 || ne[1] > HEAD_MAX_LABELS)) {
                 err = "tensor '" + name + "': n_labels = " + std::to_string(ne[1]) + " outside 1 .. " + std::to_string(HEAD_MAX_LABELS);
                 return false;
@@ -250,6 +270,14 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
         if (wc.ne1 < 1 || wc.ne1 > HEAD_MAX_LABELS) { err = "n_labels = " + std::to_string(wc.ne1) + " outside 1 .. " + std::to_string(HEAD_MAX_LABELS); return false; }
         n_labels = (int32_t)wc.ne1;
     }
+    // the MLM head: all five tensors or none (their shapes were checked as they were read)
+    int n_mlm = 0;
+    for (const char *name : kMlmNames) n_mlm += (int)tensors.count(name);
+    if (n_mlm != 0 && n_mlm != 5) {
+        for (const char *name : kMlmNames)
+            if (!tensors.count(name)) { err = std::string("partial MLM head: tensor '") + name + "' is missing from model file"; return false; }
+    }
+    mlm_head = n_mlm == 5;
     return true;
 }
 

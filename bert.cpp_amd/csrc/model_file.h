@@ -35,6 +35,9 @@ struct ModelFile {
     size_t total_tensor_bytes = 0;
     // the optional classification head (pooler.dense.{weight, bias}, classifier.{weight, bias}: all four or none): its labels, 0 = no head
     int32_t n_labels = 0;
+    // the optional masked-language-model head (cls.predictions.transform.dense.{weight, bias}, .transform.LayerNorm.{weight, bias},
+    // cls.predictions.bias [n_vocab]: all five or none; the decoder matrix is the word embeddings)
+    bool mlm_head = false;
     bool legacy_q4 = false;                          // the file uses the 20 / 24-byte q4 blocks of early-2023 ggml
     std::vector<std::vector<uint8_t>> converted;     // their tensors, re-blocked into the current layout
 

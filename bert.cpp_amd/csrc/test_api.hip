@@ -888,4 +888,67 @@ int32_t bert_hip_test_cls_head(int32_t B, int32_t H, int32_t n_labels, const flo
     return 0;
 }
 
+int32_t bert_hip_test_sparse_vocab(int32_t form, int32_t H, int32_t V, const void *t, int32_t t_is_f32, const void *e, int32_t e_is_f32,
+                                   const float *bias, const int32_t *cu_seqlens, int32_t n_sentences, int32_t s0, int32_t ns, float *out) {
+    const char *me = "bert_hip_test_sparse_vocab";
+    if (form < 0 || form > 1 || H < 1 || V < 1 || !t || !e || !bias || !cu_seqlens || n_sentences < 1 || s0 < 0 || ns < 1 || s0 + ns > n_sentences || !out) return -1;
+    if (form == 0 && (t_is_f32 || e_is_f32 || !sparse_vocab_mfma_supported(H))) return -2;
+    std::string err;
+    const int T = cu_seqlens[n_sentences], GUARD = 64;
+    int max_len = 1;
+    for (int b = s0; b < s0 + ns; ++b) max_len = std::max(max_len, cu_seqlens[b + 1] - cu_seqlens[b]);
+    if (T < 1) return -1;
+    // NaN rows in front of and behind the token rows and behind the vocabulary image; the output holds negative, NaN and huge bit patterns,
+    // with one row of pattern32 behind it
+    const size_t ts = t_is_f32 ? 4 : 2, es = e_is_f32 ? 4 : 2;
+    std::vector<uint8_t> ht((size_t)(T + 2 * GUARD) * H * ts, 0xFF), he((size_t)(V + GUARD) * H * es, 0xFF);      // (all ones: a NaN in f16 and in f32)
+    memcpy(ht.data() + (size_t)GUARD * H * ts, t, (size_t)T * H * ts);
+    memcpy(he.data(), e, (size_t)V * H * es);
+    static const uint32_t garbage[4] = {0xFFC00001u, 0xBF800000u, 0x7FC00000u, 0x7F7FFFFFu};
+    std::vector<uint32_t> ho((size_t)(ns + 1) * V);
+    for (size_t i = 0; i < ho.size(); ++i) ho[i] = i < (size_t)ns * V ? garbage[i & 3] : g_pad32;
+    DevBuf dt, de, db, dcu, dout;
+    if (!dt.upload(ht, err) || !de.upload(he, err) || !db.upload(bias, (size_t)V * 4, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
+        !dout.upload(ho, err)) {
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return -1;
+    }
+    const char *tp = dt.as<char>() + (size_t)GUARD * H * ts;
+    const SparseVocabArgs a{t_is_f32 ? nullptr : (const half_t *)tp, e_is_f32 ? nullptr : de.as<half_t>(), t_is_f32 ? (const float *)tp : nullptr,
+                            e_is_f32 ? de.as<float>() : nullptr, db.as<float>(), dcu.as<int32_t>(), dout.as<float>(), s0, ns, T, H, V, max_len};
+    if (form == 0) {
+        if (!launch_sparse_vocab(a, nullptr)) return -2;
+        launch_sparse_finish(dout.as<float>(), (size_t)ns * V, nullptr);
+    } else if (!launch_sparse_vocab_f32(a, nullptr)) return -2;
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(ho.data(), dout.p, ho.size() * 4, hipMemcpyDeviceToHost));
+    memcpy(out, ho.data(), (size_t)ns * V * 4);
+    for (size_t i = (size_t)ns * V; i < ho.size(); ++i)
+        if (ho[i] != g_pad32) { fprintf(stderr, "%s: a weight behind the last sentence was written\n", me); return -4; }
+    return 0;
+}
+
+int32_t bert_hip_test_sparse_topk(const float *w, int32_t n, int32_t V, int32_t k, int32_t *ids, float *weights) {
+    const char *me = "bert_hip_test_sparse_topk";
+    if (!w || n < 1 || V < 1 || k < 1 || !ids || !weights) return -1;
+    std::string err;
+    DevBuf dw, di, dv;
+    if (!dw.upload(w, (size_t)n * V * 4, err) || !alloc_pad32(di, (size_t)(n + 1) * k, err) || !alloc_pad32(dv, (size_t)(n + 1) * k, err)) {
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return -1;
+    }
+    if (!launch_sparse_topk(dw.as<float>(), n, V, k, di.as<int32_t>(), dv.as<float>(), nullptr)) return -2;
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    std::vector<uint32_t> hi((size_t)(n + 1) * k), hv(hi.size());
+    CK(hipMemcpy(hi.data(), di.p, hi.size() * 4, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hv.data(), dv.p, hv.size() * 4, hipMemcpyDeviceToHost));
+    memcpy(ids, hi.data(), (size_t)n * k * 4);
+    memcpy(weights, hv.data(), (size_t)n * k * 4);
+    for (size_t i = (size_t)n * k; i < hi.size(); ++i)
+        if (hi[i] != g_pad32 || hv[i] != g_pad32) { fprintf(stderr, "%s: a place behind the last row was written\n", me); return -4; }
+    return 0;
+}
+
 }  // extern "C"

@@ -364,6 +364,22 @@ std::unique_ptr<ModelWeights> ModelWeights::load(const ModelFile &mf, const Load
         if (ok && w->f32_file) ok = upload_tensor(w->head_wp32, wp, err);
         w->n_labels = mf.n_labels;
     }
+    // the MLM head (ModelFile::load: all five tensors or none, shapes checked)
+    if (ok && mf.mlm_head) {
+        const HostTensor *wt = mf.find("cls.predictions.transform.dense.weight"), *bt = mf.find("cls.predictions.transform.dense.bias"),
+                         *lw = mf.find("cls.predictions.transform.LayerNorm.weight"), *lb = mf.find("cls.predictions.transform.LayerNorm.bias"),
+                         *bv = mf.find("cls.predictions.bias");
+        if (!wt || !bt || !lw || !lb || !bv) { err = "the MLM head is incomplete"; return nullptr; }
+        ok = w->mlm_wt.build({wt}, po, err) && upload_tensor(w->mlm_bt, bt, err) && upload_tensor(w->mlm_ln_w, lw, err) &&
+             upload_tensor(w->mlm_ln_b, lb, err) && upload_tensor(w->mlm_bias, bv, err);
+        if (ok && hp.f16 == W_F16) w->vocab16 = w->word_emb.as<half_t>();
+        else if (ok) {
+            StackedRows s;
+            ok = s.stack({t.word}, err) && w->vocab16_own.upload(pack_f16_image(s, s.N), err);
+            w->vocab16 = w->vocab16_own.as<half_t>();
+        }
+        w->mlm_head = ok;
+    }
     if (!ok) return nullptr;
     return w;
 }

@@ -143,6 +143,14 @@ struct ModelWeights {
     // bc [n_labels] as f32 (q4 / f16 classifiers dequantised at load).  n_labels == 0: no head, nothing uploaded.
     int n_labels = 0;
     DevBuf head_wp16, head_wp32, head_bp, head_wc, head_bc;
+    // The masked-language-model head of the file, if it has one (model_file.h; sparse_vocab.hip): the transform matrix as a layer's
+    // matrices are (f32 files also keep its f32 rows), its bias, the transform's LayerNorm and the output bias [n_vocab] as f32, and the
+    // tied vocabulary matrix as an f16 image [n_vocab][H]: for f16 files word_emb itself, no second copy; for q4 and f32 files one
+    // rounding per element (row_to_f16) into vocab16_own, made only when the head is present.
+    bool mlm_head = false;
+    GemmWeightStore mlm_wt;
+    DevBuf mlm_bt, mlm_ln_w, mlm_ln_b, mlm_bias, vocab16_own;
+    const half_t *vocab16 = nullptr;
     // uploads to the current device
     static std::unique_ptr<ModelWeights> load(const ModelFile &mf, const LoadOptions &opt, std::string &err);
 };

@@ -177,6 +177,21 @@ def head_shapes(hp: BertHParams, n_labels: int) -> Dict[str, Tuple[int, ...]]:
     return {"pooler.dense.weight": (H, H), "pooler.dense.bias": (H,), "classifier.weight": (n_labels, H), "classifier.bias": (n_labels,)}
 
 
+# The optional masked-language-model head (BertForMaskedLM), written behind the encoder's tensors and the classification head: all
+# five or none.  The decoder matrix is tied to embeddings.word_embeddings.weight and not stored.
+MLM_HEAD_NAMES = ["cls.predictions.transform.dense.weight", "cls.predictions.transform.dense.bias",
+                  "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias", "cls.predictions.bias"]
+
+
+# how far below zero, in standard deviations of a logit, synthetic_weights draws cls.predictions.bias
+MLM_BIAS_SIGMAS = 1.1
+
+
+def mlm_head_shapes(hp: BertHParams) -> Dict[str, Tuple[int, ...]]:
+    H = hp.n_embd
+    return dict(zip(MLM_HEAD_NAMES, [(H, H), (H,), (H,), (H,), (hp.n_vocab,)]))
+
+
 def tensor_shape(name: str, hp: BertHParams) -> Tuple[int, ...]:
     """numpy (row-major, [out, in]) shape of each tensor."""
     H, I = hp.n_embd, hp.n_intermediate
@@ -197,10 +212,14 @@ def tensor_shape(name: str, hp: BertHParams) -> Tuple[int, ...]:
     return (H,)
 
 
-def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive", n_labels: int = 0) -> Dict[str, np.ndarray]:
+def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive", n_labels: int = 0, mlm_head: bool = False) -> Dict[str, np.ndarray]:
     """Seeded random f32 weights of the BERT architecture.
 
     n_labels > 0 adds a classification head (HEAD_NAMES), drawn after everything else: a seed gives the same encoder with and without it.
+    mlm_head adds a masked-language-model head (MLM_HEAD_NAMES), drawn after that: a seed gives the same encoder and the same
+    classification head with and without it.  Its cls.predictions.bias is negative, about MLM_BIAS_SIGMAS standard deviations of a
+    logit (|t| |E[v]| / sqrt(H) with |t| = sqrt(H) behind the LayerNorm), so that a sentence's max over its tokens is positive for
+    some vocabulary entries and not for others: the sparse vectors are sparse.
 
     style="sensitive": fan-in scaled matrices with O(1) activations, spread-out attention scores,
     non-trivial biases and LayerNorm affine terms, so that a wrong softmax / bias / LN path moves
@@ -235,6 +254,18 @@ def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive", 
                 a = rng.normal(0.0, 0.02, shp) if len(shp) == 2 else np.zeros(shp)
             else:
                 a = rng.normal(0.0, 1.0 / np.sqrt(shp[1]), shp) if len(shp) == 2 else rng.normal(0.0, 0.1, shp)
+            out[name] = a.astype(np.float32)
+    if mlm_head:
+        sigma = (0.02 if style == "hf" else 1.0) * np.sqrt(hp.n_embd)        # a logit's standard deviation under this style
+        for name, shp in mlm_head_shapes(hp).items():
+            if name == "cls.predictions.bias":
+                a = rng.normal(-MLM_BIAS_SIGMAS * sigma, 0.75 * sigma, shp)
+            elif style == "hf":
+                a = rng.normal(0.0, 0.02, shp) if len(shp) == 2 else (np.ones(shp) if name.endswith("LayerNorm.weight") else np.zeros(shp))
+            elif len(shp) == 2:
+                a = rng.normal(0.0, 1.0 / np.sqrt(shp[1]), shp)
+            else:
+                a = rng.normal(1.0 if name.endswith("LayerNorm.weight") else 0.0, 0.1, shp)
             out[name] = a.astype(np.float32)
     return out
 
@@ -286,9 +317,14 @@ def write_model(path: str, hp: BertHParams, weights: Dict[str, np.ndarray], ftyp
             n_labels = int(np.asarray(weights["classifier.weight"]).shape[0])
             assert 1 <= n_labels <= HEAD_MAX_LABELS, n_labels
             names = names + HEAD_NAMES
+        mlm = [n for n in MLM_HEAD_NAMES if n in weights]
+        if mlm:
+            assert mlm == MLM_HEAD_NAMES, f"partial MLM head: {mlm}"
+            names = names + MLM_HEAD_NAMES
         for name in names:
             a = np.asarray(weights[name], dtype=np.float32)
-            assert a.shape == (head_shapes(hp, n_labels)[name] if name in HEAD_NAMES else tensor_shape(name, hp)), (name, a.shape)
+            want = head_shapes(hp, n_labels)[name] if name in HEAD_NAMES else mlm_head_shapes(hp)[name] if name in MLM_HEAD_NAMES else tensor_shape(name, hp)
+            assert a.shape == want, (name, a.shape)
             two_d = a.ndim == 2
             t = ftype if two_d else FTYPE_F32
             nm = name.encode()
@@ -353,10 +389,10 @@ def read_model(path: str) -> ModelFile:
 
 
 def make_synthetic_model(path: str, dims: str | BertHParams, ftype: str | int, seed: int = 0,
-                         style: str = "sensitive", n_labels: int = 0) -> BertHParams:
+                         style: str = "sensitive", n_labels: int = 0, mlm_head: bool = False) -> BertHParams:
     hp = MODEL_DIMS[dims] if isinstance(dims, str) else dims
     ft = FTYPE_BY_NAME[ftype] if isinstance(ftype, str) else ftype
-    write_model(path, hp, synthetic_weights(hp, seed, style, n_labels), ft)
+    write_model(path, hp, synthetic_weights(hp, seed, style, n_labels, mlm_head), ft)
     return hp
 
 
@@ -367,6 +403,16 @@ def hf_classifier_weights(state_dict, n_layer: int) -> Dict[str, np.ndarray]:
         return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
     sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in state_dict.items()}
     return {n: arr(sd[n]) for n in tensor_names(n_layer) + HEAD_NAMES}
+
+
+def hf_mlm_weights(state_dict, n_layer: int) -> Dict[str, np.ndarray]:
+    """The tensors of a HuggingFace BertForMaskedLM state dict (a SPLADE checkpoint is one) under this format's names ('bert.' stripped;
+    the head's names are HF's own; cls.predictions.decoder.* is the tied word-embedding matrix and cls.predictions.bias over again, and
+    is dropped).  Values may be torch tensors or arrays."""
+    def arr(v):
+        return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+    sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in state_dict.items()}
+    return {n: arr(sd[n]) for n in tensor_names(n_layer) + MLM_HEAD_NAMES}
 
 
 def synthetic_token_ids(n_sentences: int, seq_len: int, n_vocab: int, seed: int) -> np.ndarray:

@@ -40,6 +40,8 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_eval_packed_tokens_device", "bert_hip_eval_packed_tokens", "bert_hip_encode_tokens_batch", "bert_hip_maxsim_device", "bert_hip_maxsim",
     "bert_hip_n_labels", "bert_hip_tokenize_pair", "bert_hip_eval_packed_typed", "bert_hip_eval_packed_typed_device", "bert_hip_score_packed",
     "bert_hip_score_packed_device", "bert_hip_score_pairs",
+    "bert_hip_has_mlm_head", "bert_hip_sparse_packed", "bert_hip_sparse_packed_device", "bert_hip_sparse_topk_packed",
+    "bert_hip_sparse_topk_packed_device", "bert_hip_encode_sparse_batch",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -52,7 +54,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
     "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool", "bert_hip_test_token_rows",
-    "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head",
+    "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -168,6 +170,13 @@ def _declare_product_abi(L):
     L.bert_hip_score_packed_device.restype = i32; L.bert_hip_score_packed_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.bert_hip_score_pairs.restype = i32
     L.bert_hip_score_pairs.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), i32, f32p]
+    L.bert_hip_has_mlm_head.restype = i32; L.bert_hip_has_mlm_head.argtypes = [vp]
+    L.bert_hip_sparse_packed.restype = i32; L.bert_hip_sparse_packed.argtypes = [vp, i32p, i32p, i32, f32p]
+    L.bert_hip_sparse_packed_device.restype = i32; L.bert_hip_sparse_packed_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    L.bert_hip_sparse_topk_packed.restype = i32; L.bert_hip_sparse_topk_packed.argtypes = [vp, i32p, i32p, i32, i32, i32p, f32p]
+    L.bert_hip_sparse_topk_packed_device.restype = i32; L.bert_hip_sparse_topk_packed_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.bert_hip_encode_sparse_batch.restype = i32
+    L.bert_hip_encode_sparse_batch.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32p, f32p]
 
 
 def lib() -> C.CDLL:
@@ -272,6 +281,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_embed_ln_typed.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, i32p, i32p, i32, i32, vp, i32, vp]
     L.bert_hip_test_cls_head.restype = i32
     L.bert_hip_test_cls_head.argtypes = [i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp]
+    L.bert_hip_test_sparse_vocab.restype = i32
+    L.bert_hip_test_sparse_vocab.argtypes = [i32, i32, i32, vp, i32, vp, i32, vp, i32p, i32, i32, i32, vp]
+    L.bert_hip_test_sparse_topk.restype = i32
+    L.bert_hip_test_sparse_topk.argtypes = [vp, i32, i32, i32, vp, vp]
     _test_lib = L
     return L
 
@@ -345,6 +358,41 @@ def test_cls_head(rows, Wp, bp, Wc, bc, flags: int = 0, form: str = "mfma"):
     if r != 0:
         raise RuntimeError(f"bert_hip_test_cls_head failed: {r}")
     return out
+
+
+def test_sparse_vocab(t, e, bias, cu_seqlens, form: str = "mfma", s0: int = 0, ns: Optional[int] = None):
+    """The vocabulary launch of the learned sparse embeddings on its own (bert_hip_test.h): t [T, H] token rows and e [V, H] vocabulary
+    rows, float16 or float32 (the dtype says which operand the kernel reads), bias [V]; sentences s0 .. s0 + ns - 1 of cu_seqlens.
+    float32 [ns, V], or None where the form does not take the shape."""
+    t, e = np.ascontiguousarray(t), np.ascontiguousarray(e)
+    assert t.dtype in (np.float16, np.float32) and e.dtype in (np.float16, np.float32)
+    bias = np.ascontiguousarray(bias, dtype=np.float32)
+    cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    (T, H), V, B = t.shape, e.shape[0], len(cu) - 1
+    ns = B - s0 if ns is None else ns
+    assert e.shape == (V, H) and bias.shape == (V,) and int(cu[-1]) == T
+    out = np.full((ns, V), np.nan, dtype=np.float32)
+    r = test_lib().bert_hip_test_sparse_vocab({"mfma": 0, "plain": 1}[form], H, V, t.ctypes.data, int(t.dtype == np.float32), e.ctypes.data,
+                                              int(e.dtype == np.float32), bias.ctypes.data, _i32p(cu), B, s0, ns, out.ctypes.data)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_sparse_vocab failed: {r}")
+    return out
+
+
+def test_sparse_topk(w, k: int):
+    """The top-k launch on its own: w float32 [n, V] -> (ids int32 [n, k], weights float32 [n, k]), or None where it refuses k or V."""
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    n, V = w.shape
+    ids = np.full((n, max(k, 1)), -7, dtype=np.int32)
+    wt = np.full((n, max(k, 1)), np.nan, dtype=np.float32)
+    r = test_lib().bert_hip_test_sparse_topk(w.ctypes.data, n, V, k, ids.ctypes.data, wt.ctypes.data)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_sparse_topk failed: {r}")
+    return ids, wt
 
 
 def test_layernorm(x: np.ndarray, gamma, beta) -> np.ndarray:
@@ -722,6 +770,56 @@ class BertModel:
         if top_k is not None:
             order = order[:top_k]
         return order, s[order]
+
+    # ---- learned sparse embeddings --------------------------------------------------------
+    @property
+    def has_mlm_head(self) -> bool:
+        """Whether the model file carries a masked-language-model head."""
+        return bool(self.lib.bert_hip_has_mlm_head(self.ctx))
+
+    def sparse_packed(self, tokens: np.ndarray, cu_seqlens: np.ndarray, k: Optional[int] = None, out=None):
+        """Learned sparse weights of a packed batch: float32 [B, n_vocab], or with k (ids int32 [B, k], weights float32 [B, k]) — the k
+        largest positive weights, larger first, equal weights smaller id first, unused places id -1 / weight 0.  out: the array(s) to fill."""
+        tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+        cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+        B = len(cu) - 1
+        if k is None:
+            w = np.full((B, self.n_vocab), np.nan, dtype=np.float32) if out is None else out
+            assert w.dtype == np.float32 and w.flags.c_contiguous and w.shape == (B, self.n_vocab)
+            r = self.lib.bert_hip_sparse_packed(self.ctx, _i32p(tokens), _i32p(cu), B, _f32p(w))
+            if r != 0:
+                raise RuntimeError(f"bert_hip_sparse_packed failed: {r}")
+            return w
+        ids, w = (np.full((B, max(k, 1)), -1, dtype=np.int32), np.zeros((B, max(k, 1)), dtype=np.float32)) if out is None else out
+        assert ids.dtype == np.int32 and w.dtype == np.float32 and ids.flags.c_contiguous and w.flags.c_contiguous
+        r = self.lib.bert_hip_sparse_topk_packed(self.ctx, _i32p(tokens), _i32p(cu), B, k, _i32p(ids), _f32p(w))
+        if r != 0:
+            raise RuntimeError(f"bert_hip_sparse_topk_packed failed: {r}")
+        return ids, w
+
+    def sparse_packed_device(self, d_tokens_ptr: int, d_cu_ptr: int, n_sentences: int, n_tokens: int, max_len: int, d_weights_ptr: int,
+                             k: Optional[int] = None, d_ids_ptr: Optional[int] = None, stream: int = 0) -> None:
+        if k is None:
+            r = self.lib.bert_hip_sparse_packed_device(self.ctx, d_tokens_ptr, d_cu_ptr, n_sentences, n_tokens, max_len, d_weights_ptr, stream)
+        else:
+            r = self.lib.bert_hip_sparse_topk_packed_device(self.ctx, d_tokens_ptr, d_cu_ptr, n_sentences, n_tokens, max_len, k, d_ids_ptr, d_weights_ptr, stream)
+        if r != 0:
+            raise RuntimeError(f"bert_hip_sparse{'' if k is None else '_topk'}_packed_device failed: {r}")
+
+    def encode_sparse(self, texts: Sequence, k: Optional[int] = None, n_threads: int = 6):
+        """Learned sparse embeddings of texts: dense float32 [n, n_vocab], or (ids, weights) of the k largest terms when k is given."""
+        n = len(texts)
+        if k is None:
+            toks = self.tokenize_batch(texts, n_threads)
+            cu = np.concatenate([[0], np.cumsum([len(t) for t in toks])]).astype(np.int32)
+            return self.sparse_packed(np.concatenate(toks).astype(np.int32) if n else np.zeros(0, np.int32), cu)
+        arr = (C.c_char_p * n)(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        ids = np.full((n, max(k, 1)), -1, dtype=np.int32)
+        w = np.zeros((n, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_encode_sparse_batch(self.ctx, n_threads, n, arr, k, _i32p(ids), _f32p(w))
+        if r != n:
+            raise RuntimeError(f"bert_hip_encode_sparse_batch encoded {r} of {n} texts")
+        return ids, w
 
     # ---- long texts -----------------------------------------------------------------------
     def tokenize_long(self, text: str | bytes) -> List[int]:

@@ -370,6 +370,51 @@ BERT_API int32_t bert_hip_score_packed_device(struct bert_ctx *ctx, const bert_v
 BERT_API int32_t bert_hip_score_pairs(struct bert_ctx *ctx, int32_t n_threads, int32_t n_pairs, const char **texts_a, const char **texts_b,
                                       int32_t flags, float *scores);
 
+/* LEARNED SPARSE EMBEDDINGS.  A BERT with its masked-language-model head (HuggingFace BertForMaskedLM; the SPLADE family is trained this
+ * way) turns a text into one non-negative weight per vocabulary entry,
+ *     w[v] = max over the text's tokens i of log(1 + relu(logit[i][v])),   logit[i] = E t_i + bias,   t = LayerNorm(gelu(Wt x + bt)),
+ * x the final states of the pass, E the word-embedding matrix (the decoder is tied to it).  [CLS] and [SEP] take part, as under
+ * HuggingFace's attention mask.  Nothing above changes its behaviour or its bits.
+ *
+ * The model file.  Five optional tensors behind the encoder's set and the classification head (the two heads are independent), all or
+ * none: cls.predictions.transform.dense.weight [n_embd, n_embd] (the file's type), cls.predictions.transform.dense.bias,
+ * cls.predictions.transform.LayerNorm.weight, .LayerNorm.bias [n_embd] and cls.predictions.bias [n_vocab] (f32).  The decoder matrix is
+ * not stored.  bert_hip_has_mlm_head: 1 if the context's model has the head, else 0.
+ *
+ * What is computed.  out[b][v] = z > 0 ? log1pf(z) : +0 with z = (max over the tokens of sentence b of <t_i, E_v>) + bias[v]: log1p and
+ * relu are monotone, so the max moves inside and the bias is added once.  For n_embd % 8 == 0, n_embd <= 1024 the products run on the
+ * matrix cores: t and E as f16 (E: the file's f16 bits, or its f32 / q4 values rounded once), f32 accumulation, the index's chain; for
+ * f32 files on the f32 route and any other n_embd in plain f32.  The logits [tokens][n_vocab] never reach memory: the max over a
+ * sentence's tokens is taken in registers and only [n_sentences][n_vocab] leaves the chip.  The max is exact, so a sentence's weights
+ * have the same bits alone, anywhere in a batch, in any batch size and from run to run.  The context's "pooling" / "normalize" do not
+ * enter.  The launches are "mlm_transform", "mlm_layernorm", "sparse_vocab", "sparse_finish" and "sparse_topk" in
+ * bert_hip_profile_report.
+ *   sparse_packed[_device]       weights [n_sentences][n_vocab] f32, dense.
+ *   sparse_topk_packed[_device]  per sentence the k largest POSITIVE weights (1 <= k <= 256) with their vocabulary ids, larger first,
+ *                                equal weights smaller id first: ids [n_sentences][k] i32, weights [n_sentences][k] f32; a sentence with
+ *                                fewer than k positive weights ends in ids of -1 with weights +0.  The dense rows behind it live in a
+ *                                scratch of at most 32 MiB: the head runs in chunks of sentences, the chunk fixed at bert_hip_reserve.
+ *   *_device   the rules of bert_hip_eval_packed_device: everything in HBM on the first device, enqueued on `stream`; after
+ *              bert_hip_reserve (which accounts for the transform's buffer and the scratch) they allocate nothing and may be captured
+ *              into a graph.
+ *   host forms blocking, on the context's FIRST device.  Cut at BERT_HIP_CHUNK_TOKENS between sentences, one plain copy per chunk and
+ *              direction.  0; -1 without a device; -2 after a line on stderr, the outputs untouched, for a model without the head, a k
+ *              outside its range or a sentence that cannot be evaluated; -3 on a device error.
+ *   encode_sparse_batch  texts tokenized on up to n_threads host threads as bert_hip_encode_batch does, packed, top-k: returns the number
+ *              of texts encoded (it stops at the first failure, later outputs untouched), -1 without a device, -2 as above.            */
+BERT_API int32_t bert_hip_has_mlm_head(struct bert_ctx *ctx);
+BERT_API int32_t bert_hip_sparse_packed(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens, int32_t n_sentences,
+                                        float *weights);
+BERT_API int32_t bert_hip_sparse_packed_device(struct bert_ctx *ctx, const bert_vocab_id *d_tokens, const int32_t *d_cu_seqlens,
+                                               int32_t n_sentences, int32_t n_tokens_total, int32_t max_len, float *d_weights, void *stream);
+BERT_API int32_t bert_hip_sparse_topk_packed(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens, int32_t n_sentences,
+                                             int32_t k, int32_t *ids, float *weights);
+BERT_API int32_t bert_hip_sparse_topk_packed_device(struct bert_ctx *ctx, const bert_vocab_id *d_tokens, const int32_t *d_cu_seqlens,
+                                                    int32_t n_sentences, int32_t n_tokens_total, int32_t max_len, int32_t k, int32_t *d_ids,
+                                                    float *d_weights, void *stream);
+BERT_API int32_t bert_hip_encode_sparse_batch(struct bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts, int32_t k, int32_t *ids,
+                                              float *weights);
+
 /* Embedding index: rows in HBM on the context's FIRST device (bert_hip_device), exact top-k search by inner product.
  * An index belongs to the context it was made from: bert_free frees any index the caller left alive.  Like every
  * entry point of a context, the index functions are not re-entrant on one context.

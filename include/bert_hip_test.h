@@ -251,6 +251,18 @@ BERT_API int32_t bert_hip_test_embed_ln_typed(int32_t table_type, int32_t H, int
 BERT_API int32_t bert_hip_test_cls_head(int32_t B, int32_t H, int32_t n_labels, const float *rows, const void *Wp, int32_t wp_is_f32,
                                         const float *bp, const float *Wc, const float *bc, int32_t flags, int32_t form, float *out);
 
+/* The vocabulary launch of the learned sparse embeddings on its own (kernels.h launch_sparse_vocab + launch_sparse_finish, or
+ * launch_sparse_vocab_f32): t [T][H] token rows and e [V][H] vocabulary rows as f16 bits or f32 (*_is_f32), bias [V], cu_seqlens
+ * [n_sentences + 1] with T = its last entry; sentences s0 .. s0 + ns - 1 are served: out [ns][V].  form 0: the matrix-core kernel (both
+ * f16, H % 8 == 0, H <= 1024), 1: the plain one.  On the device 64 NaN rows stand in front of and behind the token rows and behind row V
+ * of the vocabulary image, and the output is pre-filled with negative, NaN and huge bit patterns, one row of pattern32 (bert_hip_test_set_pad)
+ * behind it; -4 if a word of that row has changed.  -2, and no launch, for a shape the form does not take.                          */
+BERT_API int32_t bert_hip_test_sparse_vocab(int32_t form, int32_t H, int32_t V, const void *t, int32_t t_is_f32, const void *e, int32_t e_is_f32,
+                                            const float *bias, const int32_t *cu_seqlens, int32_t n_sentences, int32_t s0, int32_t ns, float *out);
+/* The top-k launch on its own (kernels.h launch_sparse_topk): w [n][V] -> ids [n][k], weights [n][k]; both outputs hold pattern32 before
+ * the launch, one row behind the last included (-4 if that changed).  -2, and no launch, for k outside 1 .. 256 or V >= 2^24.        */
+BERT_API int32_t bert_hip_test_sparse_topk(const float *w, int32_t n, int32_t V, int32_t k, int32_t *ids, float *weights);
+
 #ifdef __cplusplus
 }
 #endif
