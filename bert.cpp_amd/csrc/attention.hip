@@ -407,7 +407,7 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
 }
 
 template <int D>
-static void launch_att(const half_t *qkv, const int32_t *cu, int B, int n_head, int max_len, half_t *out,
+static void launch_att(const half_t *qkv, const int32_t *cu, const AttentionGrid &g, int n_head, int max_len, half_t *out,
                        hipStream_t s) {
     const int n_pad = (max_len + ATT_CHUNK - 1) / ATT_CHUNK * ATT_CHUNK;
     const size_t lds = (size_t)n_pad * D * 2 + (size_t)D * (n_pad + VT_PAD) * 2;
@@ -419,17 +419,8 @@ static void launch_att(const half_t *qkv, const int32_t *cu, int B, int n_head, 
             if (wide) (void)hipFuncSetAttribute((const void *)attention_mfma_kernel<D, 512, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             else (void)hipFuncSetAttribute((const void *)attention_mfma_kernel<D, 256, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         });
-    const int items = B * n_head;
-    // the persistent form: one workgroup per CU (a multiple of 8: a workgroup's items stay on its XCD)
-    static int n_cu[MAX_HIP_DEVICES] = {};
-    const int dev = current_device_slot();
-    if (!n_cu[dev]) {
-        hipDeviceProp_t prop;
-        n_cu[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8 ? prop.multiProcessorCount / 8 * 8 : 256;
-    }
-    const int pgrid = items >= 8 ? std::min(n_cu[dev], items / 8 * 8) : items;
-    if (wide) BERT_LAUNCH((attention_mfma_kernel<D, 512, 128>), dim3(pgrid), dim3(512), lds, s, qkv, cu, n_head, out, items);
-    else BERT_LAUNCH((attention_mfma_kernel<D, 256, 128>), dim3(items), dim3(256), lds, s, qkv, cu, n_head, out, items);
+    if (wide) BERT_LAUNCH((attention_mfma_kernel<D, 512, 128>), dim3(g.grid), dim3(512), lds, s, qkv, cu, n_head, out, g.items);
+    else BERT_LAUNCH((attention_mfma_kernel<D, 256, 128>), dim3(g.grid), dim3(256), lds, s, qkv, cu, n_head, out, g.items);
 #ifdef BERT_HIP_TIMELINE
     {
         static int shots = 0;
@@ -448,14 +439,29 @@ static void launch_att(const half_t *qkv, const int32_t *cu, int B, int n_head, 
 #endif
 }
 
-bool launch_attention_mfma(const half_t *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head,
-                           int max_len, half_t *out, hipStream_t stream) {
+// The choice of form and grid, host arithmetic and the device's CU count alone (kernels.h).
+AttentionGrid attention_mfma_grid(int n_sentences, int n_head, int d_head, int max_len) {
     const int n_pad = (max_len + ATT_CHUNK - 1) / ATT_CHUNK * ATT_CHUNK;
     const size_t lds = (size_t)n_pad * d_head * 2 + (size_t)d_head * (n_pad + VT_PAD) * 2;
-    if (lds > 160 * 1024) return false;
-    if (d_head == 32) launch_att<32>(qkv, cu_seqlens, n_sentences, n_head, max_len, out, stream);
-    else if (d_head == 64) launch_att<64>(qkv, cu_seqlens, n_sentences, n_head, max_len, out, stream);
-    else return false;
+    if (lds > 160 * 1024 || (d_head != 32 && d_head != 64)) return AttentionGrid{0, 0, 0};
+    const int items = n_sentences * n_head;
+    if (n_pad <= 128) return AttentionGrid{256, items, items};
+    // the persistent form: one workgroup per CU (a multiple of 8: a workgroup's items stay on its XCD)
+    static int n_cu[MAX_HIP_DEVICES] = {};
+    const int dev = current_device_slot();
+    if (!n_cu[dev]) {
+        hipDeviceProp_t prop;
+        n_cu[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount >= 8 ? prop.multiProcessorCount / 8 * 8 : 256;
+    }
+    return AttentionGrid{512, items >= 8 ? std::min(n_cu[dev], items / 8 * 8) : items, items};
+}
+
+bool launch_attention_mfma(const half_t *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head,
+                           int max_len, half_t *out, hipStream_t stream) {
+    const AttentionGrid g = attention_mfma_grid(n_sentences, n_head, d_head, max_len);
+    if (!g.threads) return false;
+    if (d_head == 32) launch_att<32>(qkv, cu_seqlens, g, n_head, max_len, out, stream);
+    else launch_att<64>(qkv, cu_seqlens, g, n_head, max_len, out, stream);
     return true;
 }
 

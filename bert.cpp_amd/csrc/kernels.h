@@ -143,6 +143,11 @@ bool launch_attention_mfma(const half_t *qkv, const int32_t *cu_seqlens, int n_s
                            int max_len, half_t *out, hipStream_t stream);
 void launch_attention_naive(const half_t *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head,
                             int max_len, half_t *out, hipStream_t stream);
+// The form and grid launch_attention_mfma launches on the current device: threads per workgroup — 256, one workgroup per (sentence, head)
+// item, up to 128 tokens; 512, the persistent form, beyond: min(CUs / 8 * 8, items / 8 * 8) workgroups (all of fewer than 8 items) that
+// walk the items —, the grid and the items.  All zero where the launcher refuses the shape (d_head, or more LDS than 160 KiB).
+struct AttentionGrid { int threads, grid, items; };
+AttentionGrid attention_mfma_grid(int n_sentences, int n_head, int d_head, int max_len);
 
 // Q|K|V projection + attention in one kernel (qkv_attention2.hip): x [T_pad][H] -> ctx [T_pad][H].  A workgroup owns a window
 // of 128 token slots holding one or several whole sentences (16-slot aligned); f16 or q4 weights, d_head 32, H = 128 / 256 / 384, every sentence <= 128 tokens.
@@ -240,6 +245,11 @@ struct SparseVocabArgs {
 bool sparse_vocab_mfma_supported(int H);
 size_t sparse_vocab_lds_bytes(int H);
 bool launch_sparse_vocab(const SparseVocabArgs &a, hipStream_t stream);       // the vocabulary launch alone (out: the bits of relu(z))
+// The grid launch_sparse_vocab launches for a shape, host arithmetic alone: `tile` token slots per workgroup (128, or 64 above H = 624),
+// n_tiles of them over min(T, ns max_len) tokens (grid.x), vocabulary slabs of slab_blocks 32-entry blocks — a multiple of 8 in 8 .. 64 —
+// and n_slabs of them (grid.y).  false, and zeros, exactly where the launcher refuses the shape.
+struct SparseVocabGeometry { int tile, n_tiles, slab_blocks, n_slabs; };
+bool sparse_vocab_geometry(int H, int V, int T, int ns, int max_len, SparseVocabGeometry &g);
 void launch_sparse_finish(float *out, size_t n, hipStream_t stream);          // log1pf in place
 bool launch_sparse_vocab_f32(const SparseVocabArgs &a, hipStream_t stream);
 // Top-k terms of dense rows w [n][V] (sparse_vocab.hip): per row the k largest POSITIVE weights, larger first, equal weights smaller id

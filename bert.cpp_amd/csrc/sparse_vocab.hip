@@ -228,17 +228,27 @@ bool sparse_vocab_mfma_supported(int H) { return H >= 8 && H % 8 == 0 && H <= SP
 
 size_t sparse_vocab_lds_bytes(int H) { return (size_t)tile_slots(H) * (H + 8) * 2 + (size_t)(tile_slots(H) + 1) * sizeof(int); }
 
-bool launch_sparse_vocab(const SparseVocabArgs &a, hipStream_t s) {
-    if (!common_ok(a) || !a.t16 || !a.e16 || a.max_len <= 0 || !sparse_vocab_mfma_supported(a.H)) return false;
-    const int tile = tile_slots(a.H), nblk = (a.V + 31) / 32;
-    const long long tokens = std::min<long long>(a.T, (long long)a.ns * a.max_len), n_tiles = (tokens + tile - 1) / tile;
+// The launch geometry of the matrix-core form, host arithmetic alone: tokens per tile, token tiles, vocabulary blocks per slab, slabs.
+bool sparse_vocab_geometry(int H, int V, int T, int ns, int max_len, SparseVocabGeometry &g) {
+    g = SparseVocabGeometry{0, 0, 0, 0};
+    if (ns <= 0 || T <= 0 || V <= 0 || max_len <= 0 || !sparse_vocab_mfma_supported(H)) return false;
+    const int tile = tile_slots(H), nblk = (V + 31) / 32;
+    const long long tokens = std::min<long long>(T, (long long)ns * max_len), n_tiles = (tokens + tile - 1) / tile;
     // slabs of whole wave rounds (8 blocks), sized so that a small batch still spreads over the chip: about a thousand workgroups or more
     const long long slabs_wanted = std::max<long long>(1, (1024 + n_tiles - 1) / n_tiles);
     const int slab_blocks = (int)std::min<long long>(64, std::max<long long>(8, ((nblk + slabs_wanted - 1) / slabs_wanted + 7) / 8 * 8));
     const int n_slabs = (nblk + slab_blocks - 1) / slab_blocks;
     if (n_slabs > GRID_YZ_MAX || n_tiles > 0x7FFFFFFF) return false;
+    g = SparseVocabGeometry{tile, (int)n_tiles, slab_blocks, n_slabs};
+    return true;
+}
+
+bool launch_sparse_vocab(const SparseVocabArgs &a, hipStream_t s) {
+    SparseVocabGeometry g;
+    if (!common_ok(a) || !a.t16 || !a.e16 || !sparse_vocab_geometry(a.H, a.V, a.T, a.ns, a.max_len, g)) return false;
+    const int tile = g.tile, slab_blocks = g.slab_blocks;
     if (hipMemsetAsync(a.out, 0, (size_t)a.ns * a.V * sizeof(float), s) != hipSuccess) return false;
-    const dim3 grid((unsigned)n_tiles, (unsigned)n_slabs);
+    const dim3 grid((unsigned)g.n_tiles, (unsigned)g.n_slabs);
     // (past the 64 KiB a kernel gets without asking from H = 248 on: 100 868 bytes at H = 384, 132 356 at H = 1024)
     if (tile == 128) {
         configure_once(g_sparse_configured[0], [] { (void)hipFuncSetAttribute((const void *)sparse_vocab_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sparse_vocab_lds_bytes(624)); });

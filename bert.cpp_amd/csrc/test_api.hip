@@ -951,4 +951,21 @@ int32_t bert_hip_test_sparse_topk(const float *w, int32_t n, int32_t V, int32_t 
     return 0;
 }
 
+int32_t bert_hip_test_sparse_vocab_geometry(int32_t H, int32_t V, int32_t T, int32_t ns, int32_t max_len, int32_t *geometry) {
+    if (!geometry) return -1;
+    SparseVocabGeometry g;
+    const bool ok = sparse_vocab_geometry(H, V, T, ns, max_len, g);
+    geometry[0] = g.tile; geometry[1] = g.n_tiles; geometry[2] = g.slab_blocks; geometry[3] = g.n_slabs;
+    return ok ? 0 : -2;
+}
+
+int32_t bert_hip_test_attention_grid(int32_t n_sentences, int32_t n_head, int32_t d_head, int32_t max_len, int32_t *threads, int32_t *items) {
+    if (n_sentences < 1 || n_head < 1 || max_len < 1 || !threads || !items) return -1;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { fprintf(stderr, "bert_hip_test_attention_grid: no device\n"); return -1; }
+    const AttentionGrid g = attention_mfma_grid(n_sentences, n_head, d_head, max_len);
+    *threads = g.threads; *items = g.items;
+    return g.grid;
+}
+
 }  // extern "C"

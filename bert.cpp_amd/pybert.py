@@ -55,6 +55,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
     "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool", "bert_hip_test_token_rows",
     "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
+    "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -285,6 +286,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_sparse_vocab.argtypes = [i32, i32, i32, vp, i32, vp, i32, vp, i32p, i32, i32, i32, vp]
     L.bert_hip_test_sparse_topk.restype = i32
     L.bert_hip_test_sparse_topk.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.bert_hip_test_sparse_vocab_geometry.restype = i32
+    L.bert_hip_test_sparse_vocab_geometry.argtypes = [i32, i32, i32, i32, i32, i32p]
+    L.bert_hip_test_attention_grid.restype = i32
+    L.bert_hip_test_attention_grid.argtypes = [i32, i32, i32, i32, i32p, i32p]
     _test_lib = L
     return L
 
@@ -379,6 +384,28 @@ def test_sparse_vocab(t, e, bias, cu_seqlens, form: str = "mfma", s0: int = 0, n
     if r != 0:
         raise RuntimeError(f"bert_hip_test_sparse_vocab failed: {r}")
     return out
+
+
+def test_sparse_vocab_geometry(H: int, V: int, T: int, ns: int, max_len: int):
+    """The grid of the matrix-core vocabulary launch (bert_hip_test.h; no GPU): {"tile", "n_tiles", "slab_blocks", "n_slabs"} for T packed
+    tokens of which ns sentences of at most max_len tokens are served, or None where the launcher refuses the shape."""
+    g = (C.c_int32 * 4)()
+    r = test_lib().bert_hip_test_sparse_vocab_geometry(H, V, T, ns, max_len, g)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_sparse_vocab_geometry failed: {r}")
+    return dict(zip(("tile", "n_tiles", "slab_blocks", "n_slabs"), (int(x) for x in g)))
+
+
+def test_attention_grid(n_sentences: int, n_head: int, d_head: int, max_len: int):
+    """(threads, grid, items) of test_attention's matrix-core launch on the current device (bert_hip_test.h): 512 threads are the
+    persistent form, whose workgroups walk items `grid` apart.  (0, 0, 0) for a shape the launcher refuses."""
+    threads, items = C.c_int32(0), C.c_int32(0)
+    grid = test_lib().bert_hip_test_attention_grid(n_sentences, n_head, d_head, max_len, C.byref(threads), C.byref(items))
+    if grid < 0:
+        raise RuntimeError(f"bert_hip_test_attention_grid failed: {grid}")
+    return int(threads.value), int(grid), int(items.value)
 
 
 def test_sparse_topk(w, k: int):

@@ -263,6 +263,19 @@ BERT_API int32_t bert_hip_test_sparse_vocab(int32_t form, int32_t H, int32_t V, 
  * the launch, one row behind the last included (-4 if that changed).  -2, and no launch, for k outside 1 .. 256 or V >= 2^24.        */
 BERT_API int32_t bert_hip_test_sparse_topk(const float *w, int32_t n, int32_t V, int32_t k, int32_t *ids, float *weights);
 
+/* The launch geometry of the kernels whose loops depend on the size of the launch, so that a test can assert the path it reached.
+ * The grid the matrix-core vocabulary launch takes for n_embd H, V vocabulary entries, T packed tokens of which ns sentences of at most
+ * max_len tokens are served (kernels.h sparse_vocab_geometry; no GPU): geometry = {tile, n_tiles, slab_blocks, n_slabs} — token slots per
+ * workgroup, token tiles (grid.x), 32-entry vocabulary blocks per slab (a workgroup's four waves take 8 of them per round, a pair each), slabs
+ * (grid.y).  0; -2 and zeros where the launcher refuses the shape; -1 for a NULL geometry.                                          */
+BERT_API int32_t bert_hip_test_sparse_vocab_geometry(int32_t H, int32_t V, int32_t T, int32_t ns, int32_t max_len, int32_t *geometry);
+/* The form and grid bert_hip_test_attention's matrix-core launch (impl 0) takes on the current device for n_sentences sentences of at
+ * most max_len tokens (kernels.h attention_mfma_grid; reads the device's CU count): returns the grid, *threads 256 (one workgroup per
+ * (sentence, head) item) or 512 (the persistent form: a workgroup walks items grid apart), *items = n_sentences n_head.  0, and zeros,
+ * for a shape the launcher refuses; -1 for bad arguments or no device.                                                            */
+BERT_API int32_t bert_hip_test_attention_grid(int32_t n_sentences, int32_t n_head, int32_t d_head, int32_t max_len, int32_t *threads,
+                                              int32_t *items);
+
 #ifdef __cplusplus
 }
 #endif

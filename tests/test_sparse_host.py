@@ -1,6 +1,6 @@
 """CPU-side tests of the learned sparse embeddings (bert_hip.h "learned sparse embeddings"): the optional MLM head in the model file, the
 float64 reference model against HuggingFace, the weights' error bound against an f32 emulation, the top-k rule, the sparsity of the
-end-to-end batches and the new symbols."""
+end-to-end batches, the new symbols and the launch geometry of the vocabulary kernel."""
 import os
 import re
 import struct
@@ -18,7 +18,7 @@ import sparse_reference as sr
 FTYPES = ["f32", "f16", "q4_0", "q4_1"]
 NEW_SYMBOLS = ["bert_hip_has_mlm_head", "bert_hip_sparse_packed", "bert_hip_sparse_packed_device", "bert_hip_sparse_topk_packed",
                "bert_hip_sparse_topk_packed_device", "bert_hip_encode_sparse_batch"]
-NEW_TEST_SYMBOLS = ["bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk"]
+NEW_TEST_SYMBOLS = ["bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk", "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid"]
 
 
 def _write(path, hp, w, ftype, **kw):
@@ -198,3 +198,81 @@ def test_end_to_end_batches_are_sparse(tmp_path, dims, ftype):
         print(f"{dims} {ftype} {name}: {zero:.3f} of the weights are zero; per sentence {[round(float((r == 0).mean()), 2) for r in w]}")
         assert 0.2 <= zero <= 0.8, (dims, ftype, name, zero)
         assert (w >= 0).all() and np.isfinite(w).all()
+
+
+# ------------------------------------------------------------------------------------------------
+# the launch geometry of the matrix-core vocabulary kernel (kernels.h sparse_vocab_geometry; no GPU)
+# ------------------------------------------------------------------------------------------------
+def _geometry_rule(H, V, T, ns, max_len):
+    """launch_sparse_vocab's grid arithmetic as the kernel's header states it, in Python integers; None where the launcher refuses"""
+    if min(H, V, T, ns, max_len) <= 0 or H < 8 or H % 8 or H > 1024:
+        return None
+    tile = 128 if H <= 624 else 64
+    nblk = -(-V // 32)
+    n_tiles = -(-min(T, ns * max_len) // tile)
+    slabs_wanted = max(1, -(-1024 // n_tiles))
+    slab_blocks = min(64, max(8, -(--(-nblk // slabs_wanted) // 8) * 8))
+    n_slabs = -(-nblk // slab_blocks)
+    if n_slabs > 65535:
+        return None
+    return dict(tile=tile, n_tiles=n_tiles, slab_blocks=slab_blocks, n_slabs=n_slabs)
+
+
+# (H, V, T, ns, max_len) -> geometry: the shapes of test_gpu_launch_geometry.py, of test_gpu_sparse.py (all 8-block slabs) and of
+# profiles/sparse_rate.txt
+GEOMETRY_TABLE = [
+    ((64, 16421, 2048, 40, 128), dict(tile=128, n_tiles=16, slab_blocks=16, n_slabs=33)),
+    ((640, 16421, 1024, 20, 128), dict(tile=64, n_tiles=16, slab_blocks=16, n_slabs=33)),
+    ((64, 20001, 4096, 80, 128), dict(tile=128, n_tiles=32, slab_blocks=24, n_slabs=27)),
+    ((64, 28737, 8192, 150, 128), dict(tile=128, n_tiles=64, slab_blocks=64, n_slabs=15)),
+    ((384, 30522, 32768, 256, 128), dict(tile=128, n_tiles=256, slab_blocks=64, n_slabs=15)),
+    ((384, 30522, 8192, 64, 128), dict(tile=128, n_tiles=64, slab_blocks=64, n_slabs=15)),
+    ((384, 30522, 333, 3, 200), dict(tile=128, n_tiles=3, slab_blocks=8, n_slabs=120)),
+    ((1024, 1000, 513, 1, 513), dict(tile=64, n_tiles=9, slab_blocks=8, n_slabs=4)),
+    ((8, 1, 1, 1, 1), dict(tile=128, n_tiles=1, slab_blocks=8, n_slabs=1)),
+    ((624, 250, 128, 1, 128), dict(tile=128, n_tiles=1, slab_blocks=8, n_slabs=1)),
+    ((632, 250, 128, 1, 128), dict(tile=64, n_tiles=2, slab_blocks=8, n_slabs=1)),
+    ((64, 28737, 8192, 9, 128), dict(tile=128, n_tiles=9, slab_blocks=8, n_slabs=113)),        # (a piece of nine sentences)
+    ((64, 28737, 8192, 10, 128), dict(tile=128, n_tiles=10, slab_blocks=16, n_slabs=57)),
+]
+
+
+@pytest.mark.parametrize("shape,want", GEOMETRY_TABLE, ids=[str(s) for s, _ in GEOMETRY_TABLE])
+def test_vocabulary_geometry_table(shape, want):
+    """The geometry hook on written-out shapes (the values worked by hand from the rule in sparse_vocab.hip), and the Python rule agrees."""
+    assert libbert.test_sparse_vocab_geometry(*shape) == want
+    assert _geometry_rule(*shape) == want
+
+
+def test_vocabulary_geometry_invariants():
+    """Over a sweep of (H, V, T, ns, max_len), V up to 2^24 - 1: slab_blocks is a multiple of 8 in 8 .. 64; the slabs cover the vocabulary
+    blocks and the last one is not empty; the tiles cover the served tokens; the call is refused exactly where the launcher refuses; every
+    value is the rule's."""
+    Hs = [0, 4, 8, 20, 24, 64, 384, 624, 632, 640, 768, 1024, 1032]
+    Vs = [0, 1, 31, 32, 33, 250, 257, 8192, 16421, 20001, 28737, 30522, 250002, (1 << 24) - 1]
+    Ts = [0, 1, 63, 64, 65, 127, 128, 129, 1000, 2048, 8192, 32768, 262144, (1 << 31) - 1]
+    nss = [0, 1, 3, 64, 300, 65535, 1 << 24]
+    max_lens = [0, 1, 33, 128, 512, 1 << 20]
+    seen, n = set(), 0
+    for H in Hs:
+        for V in Vs:
+            for T in Ts:
+                for ns in nss:
+                    for max_len in max_lens:
+                        got = libbert.test_sparse_vocab_geometry(H, V, T, ns, max_len)
+                        refused = min(V, T, ns, max_len) <= 0 or H < 8 or H % 8 != 0 or H > 1024
+                        assert (got is None) == refused, (H, V, T, ns, max_len, got)
+                        assert got == _geometry_rule(H, V, T, ns, max_len), (H, V, T, ns, max_len, got)
+                        if got is None:
+                            continue
+                        n += 1
+                        nblk, sb = (V + 31) // 32, got["slab_blocks"]
+                        assert sb % 8 == 0 and 8 <= sb <= 64
+                        assert got["n_slabs"] * sb >= nblk > (got["n_slabs"] - 1) * sb
+                        assert got["tile"] == (128 if H <= 624 else 64)
+                        assert got["n_tiles"] * got["tile"] >= min(T, ns * max_len) > (got["n_tiles"] - 1) * got["tile"]
+                        seen.add(sb)
+    assert {8, 16, 24, 32, 64} <= seen and n > 10000, (sorted(seen), n)
+    # the one refusal beyond the arguments: more slabs than a grid dimension holds (never below V = 2^24)
+    assert libbert.test_sparse_vocab_geometry(64, 65536 * 64 * 32, 1 << 20, 8192, 128) is None
+    assert libbert.test_sparse_vocab_geometry(64, 65535 * 64 * 32, 1 << 20, 8192, 128) == dict(tile=128, n_tiles=8192, slab_blocks=64, n_slabs=65535)
