@@ -1,0 +1,304 @@
+// sparse_index.cpp — the host side of the sparse index (sparse_index.h): storage and its growth, add, the search and its chunks,
+// reading rows back, the checks of the host forms.  Every kernel is in sparse_index.hip (and the merge in search.hip) and reached
+// through sparse_index_kernels.h / search_kernels.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "search.h"
+#include "sparse_index.h"
+
+namespace bert_hip {
+
+namespace {
+
+int blocks_of(long long rows) { return (int)((rows + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS); }
+
+// the most workspace entries (nq' * slices * k) a chunk of up to nqc queries takes: the slice count falls as the tiles grow
+size_t ws_entries_bound(int dtype, int n_vocab, int n_rows, int nqc, int k, int qb_pref) {
+    size_t ent = 0;
+    SparseScanGeometry g;
+    for (int q = 1; q <= nqc; ++q)
+        if (sparse_scan_geometry(dtype, n_vocab, n_rows, q, k, g, qb_pref)) ent = std::max(ent, (size_t)q * g.max_slices * k);
+    return ent;
+}
+
+// Host rows or queries [n][kk]: every id in [-1, n_vocab), none twice in an entry, every used weight finite — as f16 where the
+// index stores f16 (as_f16).  false + err names the first offender.
+bool check_terms(const char *what, int n, int kk, const int32_t *ids, const float *w, int n_vocab, bool as_f16, std::string &err) {
+    std::vector<int32_t> seen;
+    for (int i = 0; i < n; ++i) {
+        seen.clear();
+        for (int j = 0; j < kk; ++j) {
+            const int32_t id = ids[(size_t)i * kk + j];
+            if (id == -1) continue;
+            if (id < -1 || id >= n_vocab) { err = std::string(what) + " " + std::to_string(i) + ": id " + std::to_string(id) + " outside [-1, " + std::to_string(n_vocab) + ")"; return false; }
+            const float x = w[(size_t)i * kk + j];
+            if (!std::isfinite(as_f16 ? (float)(half_t)x : x)) { err = std::string(what) + " " + std::to_string(i) + ": the weight of id " + std::to_string(id) + " is not finite" + (as_f16 ? " as f16" : ""); return false; }
+            seen.push_back(id);
+        }
+        std::sort(seen.begin(), seen.end());
+        const auto dup = std::adjacent_find(seen.begin(), seen.end());
+        if (dup != seen.end()) { err = std::string(what) + " " + std::to_string(i) + ": id " + std::to_string(*dup) + " appears twice"; return false; }
+    }
+    return true;
+}
+
+// 1 = go on, 0 = nothing to do, -2 = refused
+int check_add(int n, int k_in, const void *ids, const void *w, int width, int size, std::string &err) {
+    if (k_in < 1 || k_in > width) { err = "add: 1 <= k_in <= width (" + std::to_string(width) + ") required"; return -2; }
+    if (n < 0 || (n > 0 && (!ids || !w))) { err = "add: n >= 0 and id / weight pointers required"; return -2; }
+    if ((long long)size + n > INT_MAX - SPARSE_BLOCK_ROWS) { err = "add: an index holds at most 2^31 - 65 rows"; return -2; }
+    return n > 0;
+}
+
+int check_search(int nq, int kq, const void *qi, const void *qw, int k, const void *ids, const void *scores, std::string &err) {
+    if (k < 1 || k > SparseIndex::MAX_K) { err = "search: k must be 1 .. 256"; return -2; }
+    if (kq < 1 || kq > SparseIndex::MAX_TERMS) { err = "search: kq must be 1 .. 256"; return -2; }
+    if (nq < 0 || (nq > 0 && (!qi || !qw || !ids || !scores))) { err = "search: n_queries >= 0 and query / result pointers required"; return -2; }
+    return nq > 0;
+}
+
+}  // namespace
+
+SparseIndex *SparseIndex::create(Engine *eng, int n_vocab, int width, int dtype, std::string &err) {
+    if (!eng) { err = "no device engine"; return nullptr; }
+    if (n_vocab < 1 || n_vocab > MAX_VOCAB) { err = "n_vocab must be 1 .. 262144"; return nullptr; }
+    if (width < 1 || width > MAX_TERMS) { err = "width must be 1 .. 256"; return nullptr; }
+    if (dtype < 0 || dtype > 1) { err = "dtype must be 0 (i32 ids, f32 weights) or 1 (u16 ids, f16 weights)"; return nullptr; }
+    if (dtype == 1 && n_vocab > 65536) { err = "dtype 1 stores u16 ids: n_vocab must be at most 65536"; return nullptr; }
+    DeviceGuard g(eng->device());
+    SparseIndex *ix = new SparseIndex;
+    ix->eng_ = eng;
+    ix->n_vocab_ = n_vocab;
+    ix->width_ = width;
+    ix->dtype_ = dtype;
+    const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
+    if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
+    sparse_index_kernels_init();
+    return ix;
+}
+
+SparseIndex::~SparseIndex() {
+    DeviceGuard g(eng_ ? eng_->device() : 0);
+    if (busy_) { (void)hipEventSynchronize(busy_); (void)hipEventDestroy(busy_); }
+    if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
+    if (sids_) (void)hipFree(sids_);
+    if (sweights_) (void)hipFree(sweights_);
+    if (counts_) (void)hipFree(counts_);
+}
+
+bool SparseIndex::grow(DevBuf &b, size_t bytes, std::string &err) {
+    if (bytes <= b.bytes) return true;
+    HIP_OK(hipEventSynchronize(busy_), err, false);          // (what is queued may still read the old buffer)
+    return b.ensure(bytes, err);
+}
+
+// (whole blocks: a block's layout does not depend on the capacity, so growth is three plain copies)
+bool SparseIndex::grow_rows(int n_rows, std::string &err) {
+    if (n_rows <= cap_) return true;
+    const long long want = std::max<long long>({(long long)n_rows, (long long)cap_ * 3 / 2, 1024});
+    const int cap = (int)std::min<long long>((long long)blocks_of(INT_MAX - SPARSE_BLOCK_ROWS) * SPARSE_BLOCK_ROWS, (long long)blocks_of(want) * SPARSE_BLOCK_ROWS);
+    const size_t ib = sparse_id_bytes(dtype_), block_elems = (size_t)width_ * SPARSE_BLOCK_ROWS;
+    const size_t nb = (size_t)cap / SPARSE_BLOCK_ROWS, used = (size_t)blocks_of(n_);
+    void *pi = nullptr, *pw = nullptr;
+    int32_t *pc = nullptr;
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    const char *failed = nullptr;
+    if (hipMalloc(&pi, nb * block_elems * ib) != hipSuccess || hipMalloc(&pw, nb * block_elems * ib) != hipSuccess ||
+        hipMalloc((void **)&pc, (size_t)cap * 4) != hipSuccess) failed = "hipMalloc (sparse index rows) failed";
+    else if (n_ > 0 && (hipMemcpy(pi, sids_, used * block_elems * ib, hipMemcpyDeviceToDevice) != hipSuccess ||
+                        hipMemcpy(pw, sweights_, used * block_elems * ib, hipMemcpyDeviceToDevice) != hipSuccess ||
+                        hipMemcpy(pc, counts_, (size_t)n_ * 4, hipMemcpyDeviceToDevice) != hipSuccess)) failed = "hipMemcpy (sparse index rows) failed";
+    if (failed) {
+        (void)hipGetLastError();
+        if (pi) (void)hipFree(pi);
+        if (pw) (void)hipFree(pw);
+        if (pc) (void)hipFree(pc);
+        err = failed;
+        return false;
+    }
+    if (sids_) (void)hipFree(sids_);
+    if (sweights_) (void)hipFree(sweights_);
+    if (counts_) (void)hipFree(counts_);
+    sids_ = pi; sweights_ = pw; counts_ = pc;
+    cap_ = cap;
+    return true;
+}
+
+bool SparseIndex::grow_search(int n_rows, int nqc, int k, std::string &err) {
+    const size_t ent = ws_entries_bound(dtype_, n_vocab_, n_rows, nqc, k, eng_->options().sparse_index_qb);
+    return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err) && grow(images_, (size_t)nqc * sparse_image_bytes(n_vocab_), err);
+}
+
+int SparseIndex::reserve(int n_rows, int n_queries, int k, std::string &err) {
+    if (n_rows < 0 || n_queries < 0 || k < 1 || k > MAX_K) { err = "reserve: n_rows, n_queries >= 0 and 1 <= k <= 256 required"; return -2; }
+    DeviceGuard g(eng_->device());
+    if (!grow_rows(n_rows, err)) return -3;
+    const int nqc = std::min(n_queries, QCHUNK);
+    if (nqc == 0) return 0;
+    // (the entries grow with k — the list length, and so the tile, changes at k = 128, the slices only fall with it)
+    size_t ent = 0;
+    for (int kk : {std::min(k, 128), k}) ent = std::max(ent, ws_entries_bound(dtype_, n_vocab_, std::max(n_rows, n_), nqc, kk, eng_->options().sparse_index_qb));
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(images_, (size_t)nqc * sparse_image_bytes(n_vocab_), err)) return -3;
+    return 0;
+}
+
+int SparseIndex::add_device(int n, int k_in, const int32_t *d_ids, const float *d_weights, hipStream_t s, std::string &err) {
+    if (const int go = check_add(n, k_in, d_ids, d_weights, width_, n_, err); go <= 0) return go < 0 ? go : n_;
+    DeviceGuard g(eng_->device());
+    Engine::StreamOp op;                                     // (engine.h: the one-event rule, and what a capturing stream changes)
+    if (!eng_->op_begin(s, busy_, op, err)) return -3;
+    if (!grow_rows(n_ + n, err)) return -3;
+    SparseAddArgs a;
+    a.ids = d_ids; a.weights = d_weights; a.sids = sids_; a.sweights = sweights_; a.counts = counts_;
+    a.first = n_; a.n = n; a.k_in = k_in; a.width = width_; a.n_vocab = n_vocab_;
+    eng_->timed_launch(dtype_ ? "sparse_index_add_f16" : "sparse_index_add_f32", 0.0, s, [&] { launch_sparse_add(dtype_, a, s); });
+    HIP_OK(hipGetLastError(), err, -3);
+    if (!eng_->op_end(op, err)) return -3;
+    const int first = n_;
+    n_ += n;
+    return first;
+}
+
+int SparseIndex::add_host(int n, int k_in, const int32_t *ids, const float *weights, std::string &err) {
+    if (const int go = check_add(n, k_in, ids, weights, width_, n_, err); go <= 0) return go < 0 ? go : n_;
+    if (!check_terms("add: row", n, k_in, ids, weights, n_vocab_, dtype_ == 1, err)) return -2;
+    DeviceGuard g(eng_->device());
+    const int first = n_;
+    if (!grow_rows(n_ + n, err)) return -3;
+    // through a staging buffer of at most 64 MiB (a row's stored form does not depend on the parts it came in)
+    const size_t row_bytes = (size_t)k_in * 4;
+    const int per = (int)std::max<size_t>(1, ((size_t)32 << 20) / row_bytes);
+    for (int i0 = 0; i0 < n; i0 += per) {
+        const int c = std::min(per, n - i0);
+        const size_t half = ((size_t)c * row_bytes + 15) & ~(size_t)15;
+        bool ok = grow(stage_, 2 * half, err);
+        char *d = stage_.as<char>();
+        ok = ok && hipStreamWaitEvent(stream_, busy_, 0) == hipSuccess &&
+             hipMemcpyAsync(d, ids + (size_t)i0 * k_in, (size_t)c * row_bytes, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+             hipMemcpyAsync(d + half, weights + (size_t)i0 * k_in, (size_t)c * row_bytes, hipMemcpyHostToDevice, stream_) == hipSuccess &&
+             add_device(c, k_in, (const int32_t *)d, (const float *)(d + half), stream_, err) >= 0 && hipStreamSynchronize(stream_) == hipSuccess;
+        if (!ok) {
+            (void)hipStreamSynchronize(stream_);
+            if (err.empty()) err = "add: copy to the device failed";
+            truncate(first);
+            return -3;
+        }
+    }
+    return first;
+}
+
+void SparseIndex::enqueue_chunk(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s) {
+    SparseScanGeometry g;
+    sparse_scan_geometry(dtype_, n_vocab_, n_, nq, k, g, eng_->options().sparse_index_qb);     // (create's bounds: never refused)
+    const unsigned img = (unsigned)sparse_image_bytes(n_vocab_);
+    SparseQueryArgs q;
+    q.ids = d_qids; q.weights = d_qw; q.images = images_.as<char>(); q.nq = nq; q.kq = kq; q.n_vocab = n_vocab_;
+    q.words = sparse_image_words(n_vocab_); q.img_bytes = img;
+    eng_->timed_launch("sparse_query", 0.0, s, [&] { launch_sparse_query(q, s); });
+    SparseScanArgs a;
+    a.sids = sids_; a.sweights = sweights_; a.counts = counts_; a.images = images_.as<char>();
+    a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+    a.n_rows = n_; a.width = width_; a.nq = nq; a.qb = g.qb; a.n_qtiles = g.n_qtiles; a.n_slices = g.n_slices; a.slice_rows = g.slice_rows;
+    a.k = k; a.L = g.L; a.n_items = g.n_qtiles * g.n_slices; a.words = q.words; a.img_bytes = img;
+    eng_->timed_launch(dtype_ ? "sparse_index_scan_f16" : "sparse_index_scan_f32", 0.0, s, [&] { launch_sparse_scan(dtype_, a, g.lds, s); });
+    MergeArgs m;
+    m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = g.n_slices * k; m.k = k; m.L = merge_L(k); m.ids = d_ids; m.scores = d_scores;
+    eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, nq, s); });
+}
+
+int SparseIndex::search_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
+                               std::string &err) {
+    if (const int go = check_search(nq, kq, d_qids, d_qw, k, d_ids, d_scores, err); go <= 0) return go;
+    DeviceGuard g(eng_->device());
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -3;
+    if (!grow_search(n_, std::min(nq, QCHUNK), k, err)) return -3;
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        enqueue_chunk(c, kq, d_qids + (size_t)c0 * kq, d_qw + (size_t)c0 * kq, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
+    }
+    HIP_OK(hipGetLastError(), err, -3);
+    return eng_->op_end(op, err) ? 0 : -3;
+}
+
+int SparseIndex::search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err) {
+    std::vector<int32_t> hid((size_t)nq * k);
+    std::vector<float> hsc((size_t)nq * k);
+    if (!grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
+    if (search_device(nq, kq, d_qids, d_qw, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err) != 0) { (void)hipStreamSynchronize(stream_); return -3; }
+    HIP_OK(hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+    HIP_OK(hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+    HIP_OK(hipStreamSynchronize(stream_), err, -3);
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+int SparseIndex::search_host(int nq, int kq, const int32_t *qids, const float *qw, int k, int32_t *ids, float *scores, std::string &err) {
+    if (const int go = check_search(nq, kq, qids, qw, k, ids, scores, err); go <= 0) return go;
+    if (!check_terms("search: query", nq, kq, qids, qw, n_vocab_, false, err)) return -2;
+    DeviceGuard g(eng_->device());
+    std::vector<int32_t> hid((size_t)nq * k);
+    std::vector<float> hsc((size_t)nq * k);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        const size_t half = ((size_t)c * kq * 4 + 15) & ~(size_t)15;
+        if (!grow(stage_, 2 * half, err)) return -3;
+        char *d = stage_.as<char>();
+        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
+        HIP_OK(hipMemcpyAsync(d, qids + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
+        HIP_OK(hipMemcpyAsync(d + half, qw + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
+        if (search_device_to_host(c, kq, (const int32_t *)d, (const float *)(d + half), k, hid.data() + (size_t)c0 * k, hsc.data() + (size_t)c0 * k, err) != 0) return -3;
+    }
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+int SparseIndex::get_rows(int n, const int32_t *row_ids, int32_t *out_ids, float *out_weights, std::string &err) {
+    if (n < 0 || (n > 0 && (!row_ids || !out_ids || !out_weights))) { err = "get_rows: n >= 0 and row id / output pointers required"; return -2; }
+    for (int i = 0; i < n; ++i)
+        if (row_ids[i] < 0 || row_ids[i] >= n_) { err = "get_rows: row id " + std::to_string(row_ids[i]) + " outside [0, " + std::to_string(n_) + ")"; return -2; }
+    if (n == 0) return 0;
+    DeviceGuard g(eng_->device());
+    // in parts whose results fit 32 MiB
+    const int per = (int)std::max<size_t>(1, ((size_t)32 << 20) / ((size_t)width_ * 8));
+    std::vector<int32_t> hid((size_t)std::min(per, n) * width_);
+    std::vector<float> hw(hid.size());
+    for (int i0 = 0; i0 < n; i0 += per) {
+        const int c = std::min(per, n - i0);
+        const size_t m = (size_t)c * width_;
+        if (!grow(stage_, (size_t)c * 4, err) || !grow(out_ids_, m * 4, err) || !grow(out_scores_, m * 4, err)) return -3;
+        Engine::StreamOp op;
+        if (!eng_->op_begin(stream_, busy_, op, err)) return -3;
+        HIP_OK(hipMemcpyAsync(stage_.p, row_ids + i0, (size_t)c * 4, hipMemcpyHostToDevice, stream_), err, -3);
+        SparseExportArgs a;
+        a.sids = sids_; a.sweights = sweights_; a.counts = counts_; a.rows = stage_.as<int32_t>();
+        a.out_ids = out_ids_.as<int32_t>(); a.out_weights = out_scores_.as<float>(); a.n = c; a.width = width_;
+        eng_->timed_launch(dtype_ ? "sparse_index_export_f16" : "sparse_index_export_f32", 0.0, stream_, [&] { launch_sparse_export(dtype_, a, stream_); });
+        HIP_OK(hipGetLastError(), err, -3);
+        HIP_OK(hipMemcpyAsync(hid.data(), out_ids_.p, m * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+        HIP_OK(hipMemcpyAsync(hw.data(), out_scores_.p, m * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+        if (!eng_->op_end(op, err)) return -3;
+        HIP_OK(hipStreamSynchronize(stream_), err, -3);
+        memcpy(out_ids + (size_t)i0 * width_, hid.data(), m * 4);
+        memcpy(out_weights + (size_t)i0 * width_, hw.data(), m * 4);
+    }
+    return 0;
+}
+
+bool SparseIndex::text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err) {
+    if (!grow(text_in_, in_bytes, err) || !grow(text_out_, out_bytes, err)) return false;
+    d_in = text_in_.as<char>();
+    d_out = text_out_.as<char>();
+    return true;
+}
+
+}  // namespace bert_hip

@@ -1,0 +1,75 @@
+// sparse_index.h — a sparse index in HBM and its exact top-k inner-product search (the class: sparse_index.cpp; its kernels:
+// sparse_index.hip behind sparse_index_kernels.h; C ABI: bert_hip_sparse_index_* in include/bert_hip.h).  Rows are sets of
+// (vocabulary id, weight) terms, at most `width` each, on the device of the engine the index was made from, as i32 ids + f32 weights
+// or as u16 ids + f16 weights (RNE), in blocks of 64 rows stored column by column (sliced ELL).  A search turns each query into an
+// image the scan reads from LDS (sparse_query_kernel), scans the blocks with one row per lane and selects on chip
+// (sparse_index_scan_kernel: a top-k per (query, slice of rows) in LDS), and merges the slices' lists per query with the embedding
+// index's topk_merge_kernel.  Shaped like Index (search.h): grow-only storage and workspace, one event, a stream for the host routes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+#include "engine.h"
+#include "sparse_index_kernels.h"
+
+namespace bert_hip {
+
+class SparseIndex {
+public:
+    static constexpr int MAX_K = 256, MAX_TERMS = SPARSE_MAX_TERMS, MAX_VOCAB = SPARSE_MAX_VOCAB;
+    static constexpr int QCHUNK = 4096;                  // queries per internal pass (workspace and image-buffer bound)
+
+    // dtype 0: i32 ids + f32 weights, 1: u16 ids + f16 weights (n_vocab <= 65536)
+    static SparseIndex *create(Engine *eng, int n_vocab, int width, int dtype, std::string &err);
+    ~SparseIndex();
+
+    int size() const { return n_; }
+    int n_vocab() const { return n_vocab_; }
+    int width() const { return width_; }
+    int dtype() const { return dtype_; }
+    hipStream_t stream() const { return stream_; }
+
+    // Results: >= 0, or -2 (an argument the entry refuses; nothing changed) or -3 (a device error), a message in err either way.
+    // storage for n_rows rows and the workspace of searches of up to n_queries queries with any k' <= k, now
+    int reserve(int n_rows, int n_queries, int k, std::string &err);
+    // append rows ids / weights [n][k_in] in device memory, unchecked (sparse_index_kernels.h): the first new id.  Asynchronous on s
+    int add_device(int n, int k_in, const int32_t *d_ids, const float *d_weights, hipStream_t s, std::string &err);
+    // host rows, checked (ids in [-1, n_vocab), no id twice in a row, weights finite as stored); blocking
+    int add_host(int n, int k_in, const int32_t *ids, const float *weights, std::string &err);
+    // ids / scores [nq][k], best first; queries ids / weights [nq][kq] in device memory, unchecked.  Asynchronous on s
+    int search_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err);
+    // host queries, checked as add_host's rows (weights finite as f32), and host results (written only on success); blocking
+    int search_host(int nq, int kq, const int32_t *qids, const float *qw, int k, int32_t *ids, float *scores, std::string &err);
+    // the stored rows row_ids [n] (each in [0, size)) as out_ids / out_weights [n][width]; blocking
+    int get_rows(int n, const int32_t *row_ids, int32_t *out_ids, float *out_weights, std::string &err);
+    // Text routes: device buffers of the index for a group's packed token ids | cu_seqlens (in) and its terms ids | weights [n][k] (out);
+    // the index's operations that read them are finished
+    bool text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err);
+    // the results of a device search of nq queries on stream(), d_ids / d_scores in the index's result buffers -> host; blocking
+    int search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err);
+    // forget the rows behind the first n (an add of several parts that failed part way)
+    void truncate(int n) { if (n < n_) n_ = n; }
+
+private:
+    SparseIndex() = default;
+    bool grow(DevBuf &b, size_t bytes, std::string &err);
+    bool grow_rows(int n_rows, std::string &err);
+    bool grow_search(int n_rows, int nq, int k, std::string &err);
+    void enqueue_chunk(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s);
+
+    Engine *eng_ = nullptr;
+    int n_vocab_ = 0, width_ = 0, dtype_ = 0;
+    int n_ = 0, cap_ = 0;                                // rows; capacity in rows, a multiple of 64
+    void *sids_ = nullptr, *sweights_ = nullptr;        // [cap_ / 64][width_][64]
+    int32_t *counts_ = nullptr;                         // [cap_]
+    DevBuf ws_s_, ws_i_, images_;                       // per-(query, slice) lists; the current chunk's query images
+    DevBuf stage_, out_ids_, out_scores_;               // host routes: rows / queries / row ids in, results out
+    DevBuf text_in_, text_out_;                         // text routes
+    hipStream_t stream_ = nullptr;                      // the host routes' stream
+    // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
+    hipEvent_t busy_ = nullptr;
+};
+
+}  // namespace bert_hip

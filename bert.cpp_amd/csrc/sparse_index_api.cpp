@@ -1,0 +1,187 @@
+// sparse_index_api.cpp — the bert_hip_sparse_index_* entry points of bert_hip.h: a sparse index (sparse_index.h) on a context's first
+// device.  The text routes tokenize and pack as bert_hip_encode_sparse_batch does, run the MLM head's top-k form into the index's device
+// buffers and hand those to add_device / search_device: the terms never reach the host.
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/bert_hip.h"
+#include "abi.h"
+
+using namespace bert_hip;
+
+namespace {
+
+// The frame of an entry point that takes a sparse index: -1 (after a line on stderr) without one, else the body's result; a body
+// that returns -2 or -3 has put its message into err, and it is printed here.  -4 for an exception.
+template <class F>
+int32_t sparse_index_call(const char *me, bert_hip_sparse_index *ix, F &&body) {
+    return guarded(me, [&]() -> int32_t {
+        if (!ix || !ix->ix) { fprintf(stderr, "%s: no index\n", me); return -1; }
+        std::string err;
+        const int32_t r = body(ix->ctx, *ix->ix, err);
+        if ((r == -2 || r == -3) && !err.empty()) fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return r;
+    }, (int32_t)-4);
+}
+
+// what the text routes ask of the model (-2 + err otherwise)
+bool text_model_ok(const bert_ctx *ctx, const SparseIndex &x, std::string &err) {
+    if (!ctx->engine()->has_mlm_head()) { err = "the model file has no MLM head (cls.predictions.*)"; return false; }
+    if (x.n_vocab() != ctx->hp.n_vocab) { err = "the index has n_vocab " + std::to_string(x.n_vocab()) + ", the model's is " + std::to_string(ctx->hp.n_vocab); return false; }
+    return true;
+}
+
+// Tokenizes the texts in groups of 4096, cuts each group at chunk_tokens between sentences and at the sentences whose terms fit
+// 32 MiB, and per chunk: ids | cu_seqlens into the index's device buffer, the MLM head's k largest terms of every text into its other
+// one (ids [nb][k] | weights [nb][k]), then use(i0, nb, d_ids, d_weights) — all on the index's stream.  0, -2 or -3 (+ err).
+template <class F>
+int32_t sparse_text_chunks(bert_ctx *ctx, SparseIndex &x, int32_t n_threads, int32_t n, const char **texts, int32_t k, F &&use, std::string &err) {
+    constexpr int32_t GROUP = 4096;
+    Engine *eng = ctx->engine();
+    TokenGroup &g = ctx->texts.group[0];
+    const int cap = std::max(1, (int)(((size_t)32 << 20) / ((size_t)k * 8)));
+    std::vector<int32_t> h_cu;
+    for (int32_t i0 = 0; i0 < n; i0 += GROUP) {
+        const int32_t m = std::min(GROUP, n - i0);
+        g.tokenize(ctx->texts, n_threads, m, texts + i0);
+        if (g.n_ok < m) { err = "input " + std::to_string(i0 + g.n_ok) + " cannot be evaluated"; return -2; }
+        const int32_t *cu = g.cu.data();
+        for (int b0 = 0; b0 < m;) {
+            int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
+            while (b1 < m && b1 - b0 < cap && cu[b1 + 1] - cu[b0] <= eng->options().chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
+            const int nb = b1 - b0, T = cu[b1] - cu[b0];
+            const size_t off_cu = ((size_t)T * 4 + 15) & ~(size_t)15, off_w = ((size_t)nb * k * 4 + 15) & ~(size_t)15;
+            char *d_in = nullptr, *d_out = nullptr;
+            if (!x.text_buffers(off_cu + (size_t)(nb + 1) * 4, off_w + (size_t)nb * k * 4, d_in, d_out, err)) return -3;
+            h_cu.resize(nb + 1);
+            for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
+            hipStream_t s = x.stream();
+            // (pageable sources: both copies have left the host buffers when they return)
+            if (hipMemcpyAsync(d_in, g.packed.get() + cu[b0], (size_t)T * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
+                hipMemcpyAsync(d_in + off_cu, h_cu.data(), (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
+                (void)hipStreamSynchronize(s);
+                err = "hipMemcpyAsync (ids) failed";
+                return -3;
+            }
+            int32_t r = eng->sparse_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, k, (int32_t *)d_out,
+                                                  (float *)(d_out + off_w), s, err) != 0 ? -3 : 0;
+            if (r == 0) r = use(i0 + b0, nb, (const int32_t *)d_out, (const float *)(d_out + off_w));
+            if (hipStreamSynchronize(s) != hipSuccess && r == 0) { err = "device error"; r = -3; }
+            if (r != 0) return r;
+            b0 = b1;
+        }
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+struct bert_hip_sparse_index *bert_hip_sparse_index_create(struct bert_ctx *ctx, int32_t n_vocab, int32_t width, int32_t dtype) {
+    return guarded("bert_hip_sparse_index_create", [&]() -> bert_hip_sparse_index * {
+        const char *me = "bert_hip_sparse_index_create";
+        if (!ctx) { fprintf(stderr, "%s: no context\n", me); return nullptr; }
+        if (!ctx->engine()) { fprintf(stderr, "%s: this context has no device (tokenizer-only): an index lives on the context's device\n", me); return nullptr; }
+        if (n_vocab == 0) n_vocab = ctx->hp.n_vocab;
+        std::string err;
+        std::unique_ptr<SparseIndex> ix(SparseIndex::create(ctx->engine(), n_vocab, width, dtype, err));
+        if (!ix) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return nullptr; }
+        std::unique_ptr<bert_hip_sparse_index> h(new bert_hip_sparse_index);
+        h->ctx = ctx;
+        h->ix = std::move(ix);
+        ctx->sparse_indexes.push_back(h.get());
+        return h.release();
+    }, (bert_hip_sparse_index *)nullptr);
+}
+
+void bert_hip_sparse_index_free(struct bert_hip_sparse_index *ix) {
+    guarded("bert_hip_sparse_index_free", [&] {
+        if (!ix) return;
+        auto &v = ix->ctx->sparse_indexes;
+        v.erase(std::remove(v.begin(), v.end(), ix), v.end());
+        delete ix;
+    });
+}
+
+int32_t bert_hip_sparse_index_size(struct bert_hip_sparse_index *ix) { return ix && ix->ix ? ix->ix->size() : -1; }
+
+int32_t bert_hip_sparse_index_reserve(struct bert_hip_sparse_index *ix, int32_t n_rows, int32_t n_queries, int32_t k) {
+    return sparse_index_call("bert_hip_sparse_index_reserve", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) { return x.reserve(n_rows, n_queries, k, err); });
+}
+
+int32_t bert_hip_sparse_index_add(struct bert_hip_sparse_index *ix, int32_t n, int32_t k_in, const int32_t *ids, const float *weights) {
+    return sparse_index_call("bert_hip_sparse_index_add", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) { return x.add_host(n, k_in, ids, weights, err); });
+}
+
+int32_t bert_hip_sparse_index_add_device(struct bert_hip_sparse_index *ix, int32_t n, int32_t k_in, const int32_t *d_ids, const float *d_weights,
+                                         void *stream) {
+    return sparse_index_call("bert_hip_sparse_index_add_device", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) {
+        return x.add_device(n, k_in, d_ids, d_weights, (hipStream_t)stream, err);
+    });
+}
+
+int32_t bert_hip_sparse_index_add_texts(struct bert_hip_sparse_index *ix, int32_t n_threads, int32_t n, const char **texts) {
+    const char *me = "bert_hip_sparse_index_add_texts";
+    return sparse_index_call(me, ix, [&](bert_ctx *ctx, SparseIndex &x, std::string &err) -> int32_t {
+        if (!text_model_ok(ctx, x, err)) return -2;
+        if (n < 0 || (n > 0 && !texts)) { err = "n >= 0 and texts required"; return -2; }
+        const int first = x.size();
+        if (n == 0) return first;
+        const int32_t r = sparse_text_chunks(ctx, x, n_threads, n, texts, x.width(), [&](int32_t, int32_t nb, const int32_t *d_ids, const float *d_w) -> int32_t {
+            const int32_t a = x.add_device(nb, x.width(), d_ids, d_w, x.stream(), err);
+            return a < 0 ? a : 0;
+        }, err);
+        if (r == 0) return first;
+        x.truncate(first);
+        if (err.empty()) err = "device error";
+        return r;
+    });
+}
+
+int32_t bert_hip_sparse_index_search(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids, const float *q_weights,
+                                     int32_t k, int32_t *ids, float *scores) {
+    return sparse_index_call("bert_hip_sparse_index_search", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) {
+        return x.search_host(n_queries, kq, q_ids, q_weights, k, ids, scores, err);
+    });
+}
+
+int32_t bert_hip_sparse_index_search_device(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *d_q_ids,
+                                            const float *d_q_weights, int32_t k, int32_t *d_ids, float *d_scores, void *stream) {
+    return sparse_index_call("bert_hip_sparse_index_search_device", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) {
+        return x.search_device(n_queries, kq, d_q_ids, d_q_weights, k, d_ids, d_scores, (hipStream_t)stream, err);
+    });
+}
+
+int32_t bert_hip_sparse_index_search_texts(struct bert_hip_sparse_index *ix, int32_t n_threads, int32_t n_queries, const char **texts, int32_t kq,
+                                           int32_t k, int32_t *ids, float *scores) {
+    const char *me = "bert_hip_sparse_index_search_texts";
+    return sparse_index_call(me, ix, [&](bert_ctx *ctx, SparseIndex &x, std::string &err) -> int32_t {
+        if (!text_model_ok(ctx, x, err)) return -2;
+        if (k < 1 || k > SparseIndex::MAX_K || kq < 1 || kq > SparseIndex::MAX_TERMS) { err = "1 <= k <= 256 and 1 <= kq <= 256 required"; return -2; }
+        if (n_queries < 0 || (n_queries > 0 && (!texts || !ids || !scores))) { err = "n_queries >= 0 and texts / outputs required"; return -2; }
+        if (n_queries == 0) return 0;
+        // (the outputs are written only when every chunk has succeeded)
+        std::vector<int32_t> hid((size_t)n_queries * k);
+        std::vector<float> hsc((size_t)n_queries * k);
+        const int32_t r = sparse_text_chunks(ctx, x, n_threads, n_queries, texts, kq, [&](int32_t i0, int32_t nb, const int32_t *d_ids, const float *d_w) -> int32_t {
+            return x.search_device_to_host(nb, kq, d_ids, d_w, k, hid.data() + (size_t)i0 * k, hsc.data() + (size_t)i0 * k, err);
+        }, err);
+        if (r != 0) { if (err.empty()) err = "device error"; return r; }
+        memcpy(ids, hid.data(), hid.size() * 4);
+        memcpy(scores, hsc.data(), hsc.size() * 4);
+        return 0;
+    });
+}
+
+int32_t bert_hip_sparse_index_get_rows(struct bert_hip_sparse_index *ix, int32_t n, const int32_t *row_ids, int32_t *out_ids, float *out_weights) {
+    return sparse_index_call("bert_hip_sparse_index_get_rows", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) {
+        return x.get_rows(n, row_ids, out_ids, out_weights, err);
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,117 @@
+// sparse_index_kernels.h — the device code of the sparse index (sparse_index.hip) as its host side (sparse_index.cpp) sees it: the
+// stored form, the query image, the plan of a scan, the argument blocks and one launcher per kernel.  dtype is the index's: 0 = i32 ids
+// and f32 weights, 1 = u16 ids and f16 weights.  A launcher only enqueues: the caller reads hipGetLastError.
+//
+// Stored form (sliced ELL).  Rows live in blocks of SPARSE_BLOCK_ROWS = 64, one wavefront per block; inside a block the layout is
+// column-major, ids[block][j][lane] and weights[block][j][lane] for j < width, in two arrays.  A row's terms stand in columns
+// 0 .. count - 1 in ascending id, the columns behind hold id 0 and weight +0; counts[row] is the row's term count.  A wave reads column
+// j of its 64 rows as one coalesced access and every lane owns one row and one fma chain in j order.
+//
+// Query image: what the scan reads from LDS for one query — a bitmap over the vocabulary (words = ceil(n_vocab / 32) u32), one u16
+// count of the set bits below each word, and the weights in rank (ascending id) order, SPARSE_MAX_TERMS f32 — img_bytes each, a
+// multiple of 16.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+#include "search_kernels.h"
+
+namespace bert_hip {
+
+constexpr int SPARSE_BLOCK_ROWS = 64;
+constexpr int SPARSE_MAX_TERMS = 256;                   // terms of a row (width) and of a query (kq), at most
+constexpr int SPARSE_MAX_VOCAB = 262144;
+constexpr int SPARSE_STEP_ROWS = SPARSE_BLOCK_ROWS * NWAVE;     // rows a scan workgroup scores per step (each wave one block)
+// entries of a query's LDS list: the top-k ahead of a queue that takes at least half a step more than one step's rows
+inline int sparse_list_L(int k) { return k <= 128 ? 512 : 1024; }
+constexpr int SPARSE_MIN_SLICE_ROWS = 2048;             // a slice is long against the k entries it hands to the merge
+// the dynamic LDS a scan workgroup may ask for: the CU's 160 KiB less a margin for what the compiler allocates statically (the
+// workgroup reductions behind __syncthreads_or)
+constexpr size_t SPARSE_LDS_MAX = 160 * 1024 - 256;
+constexpr int SPARSE_QB_MAX = 8;                        // the most queries of a tile: a lane keeps an accumulator and a threshold pair for each
+constexpr int SPARSE_QB[2] = {2, 2};                    // queries per tile the scan aims for, by dtype
+
+inline size_t sparse_id_bytes(int dtype) { return dtype == 1 ? 2 : 4; }
+inline int sparse_image_words(int n_vocab) { return (n_vocab + 31) / 32; }
+// the parts of a query image: words u32 | words u16, padded to 4 bytes | SPARSE_MAX_TERMS f32, the whole padded to 16 bytes
+inline size_t sparse_image_bytes(int n_vocab) {
+    const size_t w = (size_t)sparse_image_words(n_vocab);
+    return (w * 4 + ((w * 2 + 3) & ~(size_t)3) + (size_t)SPARSE_MAX_TERMS * 4 + 15) & ~(size_t)15;
+}
+
+// How a chunk of nq queries over n_rows rows is cut into workgroups of sparse_index_scan_kernel: tiles of qb queries times slices of
+// slice_rows rows (a multiple of SPARSE_STEP_ROWS, so every slice starts at a block), and a workgroup's LDS — qb query images, then
+// per query a list of L = sparse_list_L(k) (score, id) entries and a count.  The one place this is decided: the launcher's caller and the
+// test hook both call it.  qb_pref: 0, or the tile to aim for in place of SPARSE_QB (the tuning key "sparse_index_qb").
+// (max_slices: what n_slices never exceeds, and what never falls as n_rows grows — the workspace bound)
+struct SparseScanGeometry { int qb, n_qtiles, n_slices, slice_rows, L, max_slices; size_t lds; };
+inline bool sparse_scan_geometry(int dtype, int n_vocab, int n_rows, int nq, int k, SparseScanGeometry &g, int qb_pref = 0) {
+    g = SparseScanGeometry{0, 0, 0, 0, 0, 0, 0};
+    if (dtype < 0 || dtype > 1 || n_vocab < 1 || n_vocab > SPARSE_MAX_VOCAB || (dtype == 1 && n_vocab > 65536) || n_rows < 0 || nq < 1 ||
+        k < 1 || k > SPARSE_MAX_TERMS)
+        return false;
+    g.L = sparse_list_L(k);
+    const size_t per_query = sparse_image_bytes(n_vocab) + (size_t)g.L * 8 + 4;
+    const int aim = qb_pref >= 1 && qb_pref <= SPARSE_QB_MAX ? qb_pref : SPARSE_QB[dtype];
+    g.qb = (int)std::min<size_t>((size_t)std::min(aim, nq), SPARSE_LDS_MAX / per_query);
+    if (g.qb < 1) return false;
+    g.n_qtiles = (nq + g.qb - 1) / g.qb;
+    const int s = std::max(1, std::min((TARGET_BLOCKS + g.n_qtiles - 1) / g.n_qtiles, n_rows / SPARSE_MIN_SLICE_ROWS));
+    g.max_slices = s;
+    const int per = (int)(((long long)n_rows + s - 1) / s);
+    g.slice_rows = std::max(SPARSE_STEP_ROWS, (per + SPARSE_STEP_ROWS - 1) / SPARSE_STEP_ROWS * SPARSE_STEP_ROWS);
+    g.n_slices = std::max(1, (int)(((long long)n_rows + g.slice_rows - 1) / g.slice_rows));
+    g.lds = (size_t)g.qb * per_query;
+    return true;
+}
+
+// sparse_index_add_kernel: one workgroup per row.  Row first + i takes the entries of ids / weights [n][k_in] whose id is in
+// [0, n_vocab), sorted by id (equal ids in input order), the weights rounded to the stored type; its other columns are zeroed.
+struct SparseAddArgs {
+    const int32_t *ids;
+    const float *weights;
+    void *sids, *sweights;              // the stored arrays
+    int32_t *counts;
+    int first, n, k_in, width, n_vocab;
+};
+
+// sparse_query_kernel: one workgroup per query, ids / weights [nq][kq] -> images [nq][img_bytes].  LDS: the image
+struct SparseQueryArgs {
+    const int32_t *ids;
+    const float *weights;
+    char *images;
+    int nq, kq, n_vocab, words;
+    unsigned img_bytes;
+};
+
+// sparse_index_scan_kernel.  LDS: as sparse_scan_geometry states
+struct SparseScanArgs {
+    const void *sids, *sweights;
+    const int32_t *counts;
+    const char *images;                 // [nq][img_bytes]
+    float *ws_s;                        // [nq][n_slices][k] per-(query, slice) lists, best first
+    int *ws_i;
+    int n_rows, width, nq, qb, n_qtiles, n_slices, slice_rows, k, L, n_items, words;
+    unsigned img_bytes;
+};
+
+// sparse_index_export_kernel: out_ids / out_weights [n][width] = the stored rows rows[i]: ids ascending, then -1 with weight +0
+struct SparseExportArgs {
+    const void *sids, *sweights;
+    const int32_t *counts, *rows;
+    int32_t *out_ids;
+    float *out_weights;
+    int n, width;
+};
+
+// lets the scan kernels of the current device have SPARSE_LDS_MAX of LDS
+void sparse_index_kernels_init();
+void launch_sparse_add(int dtype, const SparseAddArgs &a, hipStream_t s);
+void launch_sparse_query(const SparseQueryArgs &a, hipStream_t s);
+void launch_sparse_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStream_t s);
+void launch_sparse_export(int dtype, const SparseExportArgs &a, hipStream_t s);
+
+}  // namespace bert_hip

@@ -959,6 +959,14 @@ int32_t bert_hip_test_sparse_vocab_geometry(int32_t H, int32_t V, int32_t T, int
     return ok ? 0 : -2;
 }
 
+int32_t bert_hip_test_sparse_scan_geometry(int32_t dtype, int32_t n_vocab, int32_t n_rows, int32_t nq, int32_t k, int64_t *geometry) {
+    if (!geometry) return -1;
+    SparseScanGeometry g;
+    const bool ok = sparse_scan_geometry(dtype, n_vocab, n_rows, nq, k, g);
+    geometry[0] = g.qb; geometry[1] = g.n_qtiles; geometry[2] = g.n_slices; geometry[3] = g.slice_rows; geometry[4] = g.L; geometry[5] = (int64_t)g.lds;
+    return ok ? 0 : -2;
+}
+
 int32_t bert_hip_test_attention_grid(int32_t n_sentences, int32_t n_head, int32_t d_head, int32_t max_len, int32_t *threads, int32_t *items) {
     if (n_sentences < 1 || n_head < 1 || max_len < 1 || !threads || !items) return -1;
     int n_dev = 0;

@@ -5,6 +5,11 @@
 //
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
 //               [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]
+//   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS]
+//   (--sparse [WIDTH]: learned sparse search.  MODEL must carry the MLM head (bert_hip.h "learned sparse embeddings"); every line's WIDTH
+//   largest terms (default 128, 1 .. 256) go into a sparse index (bert_hip_sparse_index_add_texts; --f16: u16 ids and f16 weights),
+//   each query line is searched with its WIDTH largest terms (bert_hip_sparse_index_search_texts), and the output has the dense mode's
+//   shape.  Lines without a term in common with the query score 0 and are not printed.  The dense mode's other options do not apply.)
 //   (--cross-model PATH --cross N: cross-encoder reranking.  PATH is a second model file, one with a classification head (bert_hip.h
 //   "sentence pairs and scores"), loaded into a context of its own.  The stages above return N candidates per query line instead of k
 //   (k <= N <= 256, and N <= --rescore's); bert_hip_score_pairs scores the pairs (query line, candidate line) — each pair read as one
@@ -44,6 +49,9 @@
 namespace {
 void usage(const char *argv0) {
     fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]\n", argv0);
+    fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS]\n", argv0);
+    fprintf(stderr, "  --sparse [WIDTH]: learned sparse search with a model that carries the MLM head: each line's and each query's WIDTH largest terms\n"
+                    "          (default 128, 1 .. 256) through a sparse index (bert_hip_sparse_index_*); --f16 stores u16 ids and f16 weights.\n");
     fprintf(stderr, "  --long: lines of any length, cut into overlapping windows of W ids, S inner ids apart, one row per line (defaults: W 128 or the\n"
                     "          model's position limit if that is less, S three quarters of W - 2).  Without --long a line is cut at the model's position limit.\n");
     fprintf(stderr, "  --maxsim N: the search returns N candidates (k <= N <= 256), which are reranked by the MaxSim score of their token rows against the\n"
@@ -61,7 +69,8 @@ std::string chomp(std::string s) {
 int main(int argc, char **argv) {
     const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr, *cross_model = nullptr;
     int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0, n_cross = 0;
-    bool long_texts = false, maxsim = false, cross = false;
+    bool long_texts = false, maxsim = false, cross = false, sparse = false, sparse_f16 = false;
+    int sparse_width = 128;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
         if ((!strcmp(argv[i], "-m") || !strcmp(argv[i], "--model")) && has_value) model = argv[++i];
@@ -77,6 +86,11 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--lists") && has_value) n_lists = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--nprobe") && has_value) nprobe = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--long")) long_texts = true;
+        else if (!strcmp(argv[i], "--sparse")) {
+            sparse = true;
+            if (has_value && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') sparse_width = atoi(argv[++i]);
+        }
+        else if (!strcmp(argv[i], "--f16")) sparse_f16 = true;
         else if (!strcmp(argv[i], "--window") && has_value) window = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--stride") && has_value) stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--maxsim") && has_value) { maxsim = true; n_maxsim = atoi(argv[++i]); }
@@ -86,6 +100,12 @@ int main(int argc, char **argv) {
     }
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
+    if (sparse && (sparse_width < 1 || sparse_width > 256)) { fprintf(stderr, "search: --sparse takes a width of 1 .. 256\n"); return 2; }
+    if (sparse && (dtype != 1 || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model || save || load)) {
+        fprintf(stderr, "search: --sparse goes with -m, -f, -k, -t and --f16 only\n");
+        return 2;
+    }
+    if (sparse_f16 && !sparse) { fprintf(stderr, "search: --f16 goes with --sparse\n"); return 2; }
     if (!long_texts && (window || stride)) { fprintf(stderr, "search: --window and --stride go with --long\n"); return 2; }
     if (maxsim && (n_maxsim < k || n_maxsim > 256)) { fprintf(stderr, "search: --maxsim must be -k .. 256\n"); return 2; }
     if (cross != (cross_model != nullptr)) { fprintf(stderr, "search: --cross-model and --cross go together\n"); return 2; }
@@ -132,6 +152,43 @@ int main(int argc, char **argv) {
     for (std::string line; std::getline(in, line);) texts.push_back(chomp(line));
     std::vector<const char *> ptrs;
     for (auto &t : texts) ptrs.push_back(t.c_str());
+    if (sparse) {
+        // the learned sparse mode: the lines' terms into a sparse index, each query's terms against it; nothing below applies
+        if (!bert_hip_has_mlm_head(ctx)) {
+            fprintf(stderr, "search: --sparse needs a model with the MLM head, '%s' has none\n", model);
+            bert_free(ctx);
+            return 1;
+        }
+        bert_hip_sparse_index *sx = bert_hip_sparse_index_create(ctx, 0, sparse_width, sparse_f16 ? 1 : 0);
+        if (!sx || bert_hip_sparse_index_add_texts(sx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+            fprintf(stderr, "search: could not build the sparse index\n");
+            bert_free(ctx);
+            return 1;
+        }
+        printf("Loaded %zu lines.\n", texts.size());
+        std::vector<int32_t> sids((size_t)k);
+        std::vector<float> sscores((size_t)k);
+        for (;;) {
+            printf("Enter a text to find similar texts (enter 'q' to quit): ");
+            fflush(stdout);
+            std::string q;
+            if (!std::getline(std::cin, q)) break;
+            q = chomp(q);
+            if (q == "q") break;
+            const char *qp = q.c_str();
+            if (bert_hip_sparse_index_search_texts(sx, n_threads, 1, &qp, sparse_width, k, sids.data(), sscores.data()) != 0) {
+                fprintf(stderr, "search: the search failed\n");
+                bert_free(ctx);
+                return 1;
+            }
+            printf("\nClosest texts:\n");
+            // (a line that shares no term with the query scores 0: not a match)
+            for (int i = 0; i < k && sids[i] >= 0 && sscores[i] > 0.f; ++i) printf("%d. %s\n (similarity score: %.4f)\n", i + 1, texts[sids[i]].c_str(), sscores[i]);
+        }
+        printf("\n");
+        bert_free(ctx);                                       // (frees the sparse index as well)
+        return 0;
+    }
     if (long_texts) {
         if (!window) window = bert_n_max_tokens(ctx) < 128 ? bert_n_max_tokens(ctx) : 128;
         if (!stride) stride = 3 * (window - 2) / 4 > 1 ? 3 * (window - 2) / 4 : 1;

@@ -42,6 +42,9 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_score_packed_device", "bert_hip_score_pairs",
     "bert_hip_has_mlm_head", "bert_hip_sparse_packed", "bert_hip_sparse_packed_device", "bert_hip_sparse_topk_packed",
     "bert_hip_sparse_topk_packed_device", "bert_hip_encode_sparse_batch",
+    "bert_hip_sparse_index_create", "bert_hip_sparse_index_free", "bert_hip_sparse_index_size", "bert_hip_sparse_index_reserve",
+    "bert_hip_sparse_index_add", "bert_hip_sparse_index_add_device", "bert_hip_sparse_index_add_texts", "bert_hip_sparse_index_search",
+    "bert_hip_sparse_index_search_device", "bert_hip_sparse_index_search_texts", "bert_hip_sparse_index_get_rows",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -55,7 +58,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
     "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool", "bert_hip_test_token_rows",
     "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
-    "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid",
+    "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid", "bert_hip_test_sparse_scan_geometry",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -178,6 +181,18 @@ def _declare_product_abi(L):
     L.bert_hip_sparse_topk_packed_device.restype = i32; L.bert_hip_sparse_topk_packed_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.bert_hip_encode_sparse_batch.restype = i32
     L.bert_hip_encode_sparse_batch.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32p, f32p]
+    L.bert_hip_sparse_index_create.restype = vp; L.bert_hip_sparse_index_create.argtypes = [vp, i32, i32, i32]
+    L.bert_hip_sparse_index_free.restype = None; L.bert_hip_sparse_index_free.argtypes = [vp]
+    L.bert_hip_sparse_index_size.restype = i32; L.bert_hip_sparse_index_size.argtypes = [vp]
+    L.bert_hip_sparse_index_reserve.restype = i32; L.bert_hip_sparse_index_reserve.argtypes = [vp, i32, i32, i32]
+    L.bert_hip_sparse_index_add.restype = i32; L.bert_hip_sparse_index_add.argtypes = [vp, i32, i32, vp, vp]
+    L.bert_hip_sparse_index_add_device.restype = i32; L.bert_hip_sparse_index_add_device.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.bert_hip_sparse_index_add_texts.restype = i32; L.bert_hip_sparse_index_add_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p)]
+    L.bert_hip_sparse_index_search.restype = i32; L.bert_hip_sparse_index_search.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp]
+    L.bert_hip_sparse_index_search_device.restype = i32; L.bert_hip_sparse_index_search_device.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp]
+    L.bert_hip_sparse_index_search_texts.restype = i32
+    L.bert_hip_sparse_index_search_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32, vp, vp]
+    L.bert_hip_sparse_index_get_rows.restype = i32; L.bert_hip_sparse_index_get_rows.argtypes = [vp, i32, vp, vp, vp]
 
 
 def lib() -> C.CDLL:
@@ -290,6 +305,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_sparse_vocab_geometry.argtypes = [i32, i32, i32, i32, i32, i32p]
     L.bert_hip_test_attention_grid.restype = i32
     L.bert_hip_test_attention_grid.argtypes = [i32, i32, i32, i32, i32p, i32p]
+    L.bert_hip_test_sparse_scan_geometry.restype = i32
+    L.bert_hip_test_sparse_scan_geometry.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
     _test_lib = L
     return L
 
@@ -396,6 +413,18 @@ def test_sparse_vocab_geometry(H: int, V: int, T: int, ns: int, max_len: int):
     if r != 0:
         raise RuntimeError(f"bert_hip_test_sparse_vocab_geometry failed: {r}")
     return dict(zip(("tile", "n_tiles", "slab_blocks", "n_slabs"), (int(x) for x in g)))
+
+
+def test_sparse_scan_geometry(dtype: int, n_vocab: int, n_rows: int, nq: int, k: int):
+    """How the sparse index's scan cuts a search (bert_hip_test_sparse_scan_geometry; no GPU): a dict of qb, n_qtiles, n_slices, slice_rows,
+    L and lds, or None where the plan refuses."""
+    g = (C.c_int64 * 6)()
+    r = test_lib().bert_hip_test_sparse_scan_geometry(dtype, n_vocab, n_rows, nq, k, g)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_sparse_scan_geometry failed: {r}")
+    return dict(qb=g[0], n_qtiles=g[1], n_slices=g[2], slice_rows=g[3], L=g[4], lds=g[5])
 
 
 def test_attention_grid(n_sentences: int, n_head: int, d_head: int, max_len: int):
@@ -1051,6 +1080,11 @@ class BertModel:
         queries: the coarse stage of BertIndex.search_rescored)."""
         return BertIndex(self, dim, dtype)
 
+    def sparse_index(self, width: int = 128, dtype: str = "f32", n_vocab: Optional[int] = None) -> "BertSparseIndex":
+        """A sparse index on the context's first device (bert_hip_sparse_index_create): rows of at most width (id, weight) terms, dtype
+        "f32" (i32 ids, f32 weights) | "f16" (u16 ids, f16 weights; n_vocab <= 65536); n_vocab None = the model's."""
+        return BertSparseIndex(self, width, dtype, n_vocab)
+
     def load_index(self, path: str) -> "BertIndex":
         """The index a BertIndex.save wrote (bert_hip_index_load), on this context's first device."""
         return BertIndex(self, _load=path)
@@ -1373,6 +1407,115 @@ class BertIndex:
         if r != 0:
             raise RuntimeError(f"bert_hip_index_search_texts failed: {r}")
         return ids, scores
+
+
+class BertSparseIndex:
+    """bert_hip_sparse_index_*: rows of (vocabulary id, weight) terms in HBM, exact top-k inner-product search.  Rows and queries are
+    (ids [n, kk] int32, weights [n, kk] float32) as BertModel.encode_sparse(texts, k) returns them, id -1 = unused place.  search*
+    return (ids [n, k] int32, scores [n, k] f32), best first; missing entries are id -1, score -inf.  A ValueError is an argument the
+    entry refused (-2).  The *_device forms take device pointers (ints) and a stream handle, and return at once."""
+
+    def __init__(self, model: BertModel, width: int = 128, dtype: str = "f32", n_vocab: Optional[int] = None):
+        if dtype not in ("f32", "f16"):
+            raise ValueError("dtype must be 'f32' or 'f16'")
+        self.model, self.lib = model, model.lib
+        self.ix = self.lib.bert_hip_sparse_index_create(model.ctx, 0 if n_vocab is None else int(n_vocab), int(width), 1 if dtype == "f16" else 0)
+        if not self.ix:
+            raise RuntimeError("bert_hip_sparse_index_create failed (see stderr)")
+        self.width, self.dtype = int(width), dtype
+        self.n_vocab = model.n_vocab if n_vocab is None else int(n_vocab)
+
+    def close(self):
+        # (an index the context freed already — bert_free frees its indexes — must not be freed again)
+        if getattr(self, "ix", None) and getattr(self.model, "ctx", None):
+            self.lib.bert_hip_sparse_index_free(self.ix)
+        self.ix = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return int(self.lib.bert_hip_sparse_index_size(self.ix))
+
+    @staticmethod
+    def _fail(name: str, r: int):
+        if r == -2:
+            raise ValueError(f"{name} refused its arguments (see stderr)")
+        raise RuntimeError(f"{name} failed: {r}")
+
+    @staticmethod
+    def _terms(ids, weights):
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        if ids.ndim != 2 or ids.shape != weights.shape:
+            raise ValueError("ids and weights must be 2-d arrays of one shape")
+        return ids, weights
+
+    def reserve(self, n_rows: int, n_queries: int = 0, k: int = 1) -> None:
+        r = self.lib.bert_hip_sparse_index_reserve(self.ix, n_rows, n_queries, k)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_reserve", r)
+
+    def add(self, ids, weights) -> int:
+        """rows (ids [n, k_in], weights [n, k_in]); returns the first new id."""
+        ids, weights = self._terms(ids, weights)
+        r = self.lib.bert_hip_sparse_index_add(self.ix, ids.shape[0], ids.shape[1], ids.ctypes.data, weights.ctypes.data)
+        if r < 0:
+            self._fail("bert_hip_sparse_index_add", r)
+        return r
+
+    def add_device(self, n: int, k_in: int, d_ids_ptr: int, d_weights_ptr: int, stream: int = 0) -> int:
+        r = self.lib.bert_hip_sparse_index_add_device(self.ix, n, k_in, d_ids_ptr, d_weights_ptr, stream)
+        if r < 0:
+            self._fail("bert_hip_sparse_index_add_device", r)
+        return r
+
+    def add_texts(self, texts: Sequence, n_threads: int = 6) -> int:
+        n = len(texts)
+        txt = (C.c_char_p * n)(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        r = self.lib.bert_hip_sparse_index_add_texts(self.ix, n_threads, n, txt)
+        if r < 0:
+            self._fail("bert_hip_sparse_index_add_texts", r)
+        return r
+
+    def search(self, q_ids, q_weights, k: int = 10):
+        q_ids, q_weights = self._terms(q_ids, q_weights)
+        nq = q_ids.shape[0]
+        ids = np.empty((nq, max(k, 1)), dtype=np.int32)
+        scores = np.empty((nq, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_sparse_index_search(self.ix, nq, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data, k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_search", r)
+        return ids, scores
+
+    def search_device(self, n_queries: int, kq: int, d_q_ids_ptr: int, d_q_weights_ptr: int, k: int, d_ids_ptr: int, d_scores_ptr: int,
+                      stream: int = 0) -> None:
+        r = self.lib.bert_hip_sparse_index_search_device(self.ix, n_queries, kq, d_q_ids_ptr, d_q_weights_ptr, k, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_search_device", r)
+
+    def search_texts(self, texts: Sequence, kq: int = 32, k: int = 10, n_threads: int = 6):
+        n = len(texts)
+        txt = (C.c_char_p * n)(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        ids = np.empty((n, max(k, 1)), dtype=np.int32)
+        scores = np.empty((n, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_sparse_index_search_texts(self.ix, n_threads, n, txt, kq, k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_search_texts", r)
+        return ids, scores
+
+    def get_rows(self, row_ids):
+        """The stored rows: (ids [n, width] int32 ascending then -1, weights [n, width] float32, +0 behind the terms)."""
+        row_ids = np.ascontiguousarray(row_ids, dtype=np.int32).reshape(-1)
+        ids = np.empty((len(row_ids), self.width), dtype=np.int32)
+        w = np.empty((len(row_ids), self.width), dtype=np.float32)
+        r = self.lib.bert_hip_sparse_index_get_rows(self.ix, len(row_ids), row_ids.ctypes.data, ids.ctypes.data, w.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_get_rows", r)
+        return ids, w
 
 
 def test_gemm(A: np.ndarray, W_bytes: np.ndarray, wtype: int, N: int, bias: np.ndarray,

@@ -184,7 +184,8 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  * kernel takes the batch), "gemm" / "attn" = "mfma" | "naive" (libbert_test.so), "ln_fold" = "0" | "1", "f32" = "exact" | "f16", "latency_tokens" = n, "window_slots" = "16" | "8" (process-wide default, read once
  * per forward pass), "chunk_tokens" = n, "gather_super_tokens" = n (bert_hip_eval_packed_gather: tokens per device and super-batch, 0 =
  * four device chunks), "stage_kernel" = "0" | "1" (host API: staged blocks of at most 256 KiB travel by a kernel that reads the mapped
- * pinned memory instead of the copy engine), "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"
+ * pinned memory instead of the copy engine), "sparse_index_qb" = n (tuning: queries per workgroup tile of the sparse index's scan, 1 .. 8;
+ * "0" = the built-in choice; a result's bits do not depend on it; set it before bert_hip_sparse_index_reserve), "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"
  * (BERT_HIP_POOLING / BERT_HIP_NORMALIZE above; bert_hip_pooling / bert_hip_normalize return what is in force).                       */
 BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const char *value);
 
@@ -639,6 +640,75 @@ BERT_API int32_t bert_hip_index_partition_load(struct bert_hip_index *ix, const 
 BERT_API int32_t bert_hip_index_compact(struct bert_hip_index *ix, int32_t *old_ids);
 BERT_API int32_t bert_hip_index_save(struct bert_hip_index *ix, const char *path);
 BERT_API struct bert_hip_index *bert_hip_index_load(struct bert_ctx *ctx, const char *path);
+
+/* Sparse index: rows of (vocabulary id, weight) terms in HBM on the context's FIRST device (bert_hip_device), exact top-k search by
+ * inner product — the consumer of bert_hip_sparse_topk_packed[_device] and bert_hip_encode_sparse_batch.  An index belongs to the
+ * context it was made from: bert_free frees any sparse index the caller left alive.  Like every entry point of a context, these
+ * functions are not re-entrant on one context.
+ *   create   n_vocab: 0 = bert_hip_n_vocab(ctx), else 1 .. 262144.  width: 1 .. 256, the most terms a row can hold.  dtype: 0 = i32
+ *            ids + f32 weights (8 bytes per term), 1 = u16 ids + f16 weights (4 bytes per term; the weights rounded to nearest even),
+ *            which needs n_vocab <= 65536.  Memory: 64-row blocks of width terms each, plus 4 bytes per row.  NULL + a line on stderr
+ *            on error (tokenizer-only context, no device, bad arguments, dtype 1 with a larger vocabulary).
+ *   rows and queries   both in the form bert_hip_sparse_topk_packed writes: k_in (rows) or kq (queries) columns per entry, ids [n][k_in]
+ *            i32 and weights [n][k_in] f32, in any order; id -1 marks an unused place, whose weight is ignored.  1 <= k_in <= width,
+ *            1 <= kq <= 256.  So the MLM head's device output feeds add_device and search_device as it is.
+ *   add      appends n rows; they get ids size, size + 1, ...; returns the first new id, negative on error (index unchanged).
+ *            add_device: the rows in device memory of the index's device, enqueued on `stream`.  add_texts: runs the MLM head's
+ *            width largest terms of each text (bert_hip_encode_sparse_batch's tokenizing and packing) into a device buffer and adds
+ *            from there: the rows never reach the host.  Needs a model with the head and n_vocab equal to the model's, else -2.
+ *   search   ids[n_queries][k] and scores[n_queries][k], best first; 0 on success, negative on error (outputs untouched).
+ *            search_device: queries and results in device memory, enqueued on `stream`.  search_texts: the queries are texts, their kq
+ *            largest terms computed like add_texts's rows and searched from the device buffer.
+ *   get_rows the stored rows row_ids[n] (each in [0, size), else -2) as out_ids / out_weights [n][width]: the row's ids ascending,
+ *            then -1 with weight +0; an f16 weight comes back exactly converted.  Blocking.
+ *   reserve  sizes the storage for n_rows rows and the search workspace for up to n_queries queries with any k' <= k and any kq now,
+ *            so that the *_device calls within those bounds never allocate (allocation synchronises the device: illegal under stream
+ *            capture).  Without it storage and workspace grow on demand.
+ * Checks:
+ *   - the host forms (add, search) refuse with -2 after a line on stderr, the index unchanged: an id < -1 or >= n_vocab, an id that
+ *     appears twice in one row or query, a weight that is not finite (rows of dtype 1: after rounding to f16).
+ *   - the device forms do not look: an id outside [0, n_vocab) counts as -1; a repeated id or a non-finite weight leaves that row's or
+ *     that query's scores unspecified; nothing is read or written out of bounds in either case.
+ *   - what is stored: negative weights are legal; a weight of 0 is stored as a term; a row may have no terms.
+ * Semantics:
+ *   - score, all arithmetic f32:  acc = +0; for each stored term (id, w) of the row in ascending id: acc = fmaf(w, q[id], acc), where
+ *     q[id] is the query's weight for that id, or +0 where the query does not have it.  For finite operands the result has the same
+ *     bits whether the absent terms are skipped or multiplied by zero (the kernel skips them; the one exception is an accumulator that
+ *     has underflowed to -0, which a skipped term leaves as it is).  A stored f16 weight enters as its exact f32 value; the queries are
+ *     never rounded.
+ *   - a row without a matching term scores +0 and competes like any other row (with a query of only -1s every row scores +0 and the
+ *     smallest ids win): the caller cuts at score <= 0 if it wants only matches.
+ *   - order: larger score first; equal scores (==, so +0 equals -0) smaller id first.  Rows with a NaN score are never returned.
+ *     Slots beyond the rows are id -1, score -INFINITY.  An empty index is valid.
+ *   - 1 <= k <= 256, anything else is an error; n_queries == 0 is a successful no-op; large n_queries run in internal chunks.
+ *   - a row's score for a query depends on that query and that row alone: it has the same bits whatever the other queries of the call,
+ *     the number of add calls that built the index, reserved or grown storage, k (top-10 is the first 10 entries of top-100), the
+ *     slicing of the rows, and host or device entry point.
+ *   - *_device calls are asynchronous on the caller's stream; an index has ONE event, so its eagerly enqueued operations never
+ *     overlap, whatever streams they were enqueued on.  Within reserve's bounds they never allocate and are legal under stream
+ *     capture: STREAM CAPTURE AND GRAPHS above.
+ * Results: -1 without an index (or, for the text forms, a context without a device); -2 after a line on stderr for an argument the
+ * entry refuses (the checks above, k_in > width, k or kq out of range, a missing pointer, a model without the head); -3 on a device
+ * error; -4 for an exception.  Outputs are untouched on error.
+ * Not covered: removing rows, allow-lists, compaction, files; an inverted (term-major) organisation; several GPUs; rows wider than
+ * 256 terms.                                                                                                                        */
+struct bert_hip_sparse_index;
+BERT_API struct bert_hip_sparse_index *bert_hip_sparse_index_create(struct bert_ctx *ctx, int32_t n_vocab, int32_t width, int32_t dtype);
+BERT_API void    bert_hip_sparse_index_free(struct bert_hip_sparse_index *ix);
+BERT_API int32_t bert_hip_sparse_index_size(struct bert_hip_sparse_index *ix);
+BERT_API int32_t bert_hip_sparse_index_reserve(struct bert_hip_sparse_index *ix, int32_t n_rows, int32_t n_queries, int32_t k);
+BERT_API int32_t bert_hip_sparse_index_add(struct bert_hip_sparse_index *ix, int32_t n, int32_t k_in, const int32_t *ids, const float *weights);
+BERT_API int32_t bert_hip_sparse_index_add_device(struct bert_hip_sparse_index *ix, int32_t n, int32_t k_in, const int32_t *d_ids,
+                                                  const float *d_weights, void *stream);
+BERT_API int32_t bert_hip_sparse_index_add_texts(struct bert_hip_sparse_index *ix, int32_t n_threads, int32_t n, const char **texts);
+BERT_API int32_t bert_hip_sparse_index_search(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids,
+                                              const float *q_weights, int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_sparse_index_search_device(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *d_q_ids,
+                                                     const float *d_q_weights, int32_t k, int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_sparse_index_search_texts(struct bert_hip_sparse_index *ix, int32_t n_threads, int32_t n_queries, const char **texts,
+                                                    int32_t kq, int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_sparse_index_get_rows(struct bert_hip_sparse_index *ix, int32_t n, const int32_t *row_ids, int32_t *out_ids,
+                                                float *out_weights);
 
 BERT_API const char *bert_hip_version(void);
 

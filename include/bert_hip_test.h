@@ -275,6 +275,12 @@ BERT_API int32_t bert_hip_test_sparse_vocab_geometry(int32_t H, int32_t V, int32
  * for a shape the launcher refuses; -1 for bad arguments or no device.                                                            */
 BERT_API int32_t bert_hip_test_attention_grid(int32_t n_sentences, int32_t n_head, int32_t d_head, int32_t max_len, int32_t *threads,
                                               int32_t *items);
+/* How the sparse index's scan cuts a chunk of nq queries with this k over n_rows rows of an index of this dtype and n_vocab
+ * (sparse_index_kernels.h sparse_scan_geometry, the function the search itself calls; no GPU): geometry = {qb, n_qtiles, n_slices,
+ * slice_rows, L, lds} — queries per tile, tiles, slices of rows, rows per slice (the last may be shorter), entries of a query's LDS list,
+ * bytes of LDS per workgroup.  0; -2 and zeros where the plan refuses (dtype outside 0 .. 1, n_vocab outside 1 .. 262144 or, for dtype 1,
+ * beyond 65536, n_rows < 0, nq < 1, k outside 1 .. 256); -1 for a NULL geometry.                                                     */
+BERT_API int32_t bert_hip_test_sparse_scan_geometry(int32_t dtype, int32_t n_vocab, int32_t n_rows, int32_t nq, int32_t k, int64_t *geometry);
 
 #ifdef __cplusplus
 }
