@@ -1,5 +1,5 @@
 // sparse_index.cpp — the host side of the sparse index (sparse_index.h): storage and its growth, add, the search and its chunks,
-// reading rows back, the checks of the host forms.  Every kernel is in sparse_index.hip (and the merge in search.hip) and reached
+// rescoring, reading rows back, the checks of the host forms, the live bits, compaction and the file form.  Every kernel is in sparse_index.hip (and the merge in search.hip) and reached
 // through sparse_index_kernels.h / search_kernels.h.
 #include <hip/hip_runtime.h>
 
@@ -7,7 +7,10 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
+
+#include <sys/types.h>
 
 #include "search.h"
 #include "sparse_index.h"
@@ -17,6 +20,17 @@ namespace bert_hip {
 namespace {
 
 int blocks_of(long long rows) { return (int)((rows + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS); }
+size_t live_words(long long rows) { return (size_t)((rows + 31) / 32); }
+
+// live_set_range_kernel on the host mirror
+void live_set_range_host(std::vector<uint32_t> &live, int first, int n) {
+    for (long long r = first; r < (long long)first + n;) {
+        const size_t w = (size_t)(r >> 5);
+        const int b = (int)(r & 31), c = (int)std::min<long long>(32 - b, (long long)first + n - r);
+        live[w] |= (c == 32 ? ~0u : ((1u << c) - 1u) << b);
+        r += c;
+    }
+}
 
 // the most workspace entries (nq' * slices * k) a chunk of up to nqc queries takes: the slice count falls as the tiles grow
 size_t ws_entries_bound(int dtype, int n_vocab, int n_rows, int nqc, int k, int qb_pref) {
@@ -63,6 +77,14 @@ int check_search(int nq, int kq, const void *qi, const void *qw, int k, const vo
     return nq > 0;
 }
 
+int check_rescore(int nq, int kq, const void *qi, const void *qw, int n_cand, const void *cand, int k, const void *ids, const void *scores, std::string &err) {
+    if (k < 1 || k > SparseIndex::MAX_K) { err = "rescore: k must be 1 .. 256"; return -2; }
+    if (kq < 1 || kq > SparseIndex::MAX_TERMS) { err = "rescore: kq must be 1 .. 256"; return -2; }
+    if (n_cand < 1 || n_cand > SparseIndex::MAX_CAND) { err = "rescore: n_cand must be 1 .. 1024"; return -2; }
+    if (nq < 0 || (nq > 0 && (!qi || !qw || !cand || !ids || !scores))) { err = "rescore: n_queries >= 0 and query / candidate / result pointers required"; return -2; }
+    return nq > 0;
+}
+
 }  // namespace
 
 SparseIndex *SparseIndex::create(Engine *eng, int n_vocab, int width, int dtype, std::string &err) {
@@ -91,6 +113,7 @@ SparseIndex::~SparseIndex() {
     if (sids_) (void)hipFree(sids_);
     if (sweights_) (void)hipFree(sweights_);
     if (counts_) (void)hipFree(counts_);
+    if (live_) (void)hipFree(live_);
 }
 
 bool SparseIndex::grow(DevBuf &b, size_t bytes, std::string &err) {
@@ -110,23 +133,30 @@ bool SparseIndex::grow_rows(int n_rows, std::string &err) {
     int32_t *pc = nullptr;
     HIP_OK(hipEventSynchronize(busy_), err, false);
     const char *failed = nullptr;
+    // (an index with removed rows: the live words grow with the rows, so that an add within the capacity never allocates)
+    uint32_t *lv = nullptr;
+    const size_t lw = live_words(cap);
     if (hipMalloc(&pi, nb * block_elems * ib) != hipSuccess || hipMalloc(&pw, nb * block_elems * ib) != hipSuccess ||
-        hipMalloc((void **)&pc, (size_t)cap * 4) != hipSuccess) failed = "hipMalloc (sparse index rows) failed";
+        hipMalloc((void **)&pc, (size_t)cap * 4) != hipSuccess || (live_ && hipMalloc((void **)&lv, lw * 4) != hipSuccess)) failed = "hipMalloc (sparse index rows) failed";
     else if (n_ > 0 && (hipMemcpy(pi, sids_, used * block_elems * ib, hipMemcpyDeviceToDevice) != hipSuccess ||
                         hipMemcpy(pw, sweights_, used * block_elems * ib, hipMemcpyDeviceToDevice) != hipSuccess ||
                         hipMemcpy(pc, counts_, (size_t)n_ * 4, hipMemcpyDeviceToDevice) != hipSuccess)) failed = "hipMemcpy (sparse index rows) failed";
+    else if (lv && (hipMemset(lv, 0, lw * 4) != hipSuccess ||
+                    hipMemcpy(lv, live_h_.data(), live_words(n_) * 4, hipMemcpyHostToDevice) != hipSuccess)) failed = "hipMemcpy (sparse index live words) failed";
     if (failed) {
         (void)hipGetLastError();
         if (pi) (void)hipFree(pi);
         if (pw) (void)hipFree(pw);
         if (pc) (void)hipFree(pc);
+        if (lv) (void)hipFree(lv);
         err = failed;
         return false;
     }
     if (sids_) (void)hipFree(sids_);
     if (sweights_) (void)hipFree(sweights_);
     if (counts_) (void)hipFree(counts_);
-    sids_ = pi; sweights_ = pw; counts_ = pc;
+    if (live_) { (void)hipFree(live_); live_h_.resize(lw, 0u); }
+    sids_ = pi; sweights_ = pw; counts_ = pc; live_ = lv;
     cap_ = cap;
     return true;
 }
@@ -159,8 +189,11 @@ int SparseIndex::add_device(int n, int k_in, const int32_t *d_ids, const float *
     a.ids = d_ids; a.weights = d_weights; a.sids = sids_; a.sweights = sweights_; a.counts = counts_;
     a.first = n_; a.n = n; a.k_in = k_in; a.width = width_; a.n_vocab = n_vocab_;
     eng_->timed_launch(dtype_ ? "sparse_index_add_f16" : "sparse_index_add_f32", 0.0, s, [&] { launch_sparse_add(dtype_, a, s); });
+    // (rows added after a removal are live: their bits on the same stream, and in the mirror, which is already long enough)
+    if (live_) launch_live_set_range(live_, n_, n, s);
     HIP_OK(hipGetLastError(), err, -3);
     if (!eng_->op_end(op, err)) return -3;
+    if (live_) live_set_range_host(live_h_, n_, n);
     const int first = n_;
     n_ += n;
     return first;
@@ -194,27 +227,36 @@ int SparseIndex::add_host(int n, int k_in, const int32_t *ids, const float *weig
     return first;
 }
 
-void SparseIndex::enqueue_chunk(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s) {
+// the images of a chunk's queries into images_
+void SparseIndex::enqueue_queries(int nq, int kq, const int32_t *d_qids, const float *d_qw, hipStream_t s) {
+    SparseQueryArgs q;
+    q.ids = d_qids; q.weights = d_qw; q.images = images_.as<char>(); q.nq = nq; q.kq = kq; q.n_vocab = n_vocab_;
+    q.words = sparse_image_words(n_vocab_); q.img_bytes = (unsigned)sparse_image_bytes(n_vocab_);
+    eng_->timed_launch("sparse_query", 0.0, s, [&] { launch_sparse_query(q, s); });
+}
+
+void SparseIndex::enqueue_chunk(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
+                                const uint32_t *d_allow) {
     SparseScanGeometry g;
     sparse_scan_geometry(dtype_, n_vocab_, n_, nq, k, g, eng_->options().sparse_index_qb);     // (create's bounds: never refused)
     const unsigned img = (unsigned)sparse_image_bytes(n_vocab_);
-    SparseQueryArgs q;
-    q.ids = d_qids; q.weights = d_qw; q.images = images_.as<char>(); q.nq = nq; q.kq = kq; q.n_vocab = n_vocab_;
-    q.words = sparse_image_words(n_vocab_); q.img_bytes = img;
-    eng_->timed_launch("sparse_query", 0.0, s, [&] { launch_sparse_query(q, s); });
+    enqueue_queries(nq, kq, d_qids, d_qw, s);
+    const bool masked = live_ || d_allow;                    // (removed rows or an allow-list: the masked kernel, the same plan and workspace)
     SparseScanArgs a;
     a.sids = sids_; a.sweights = sweights_; a.counts = counts_; a.images = images_.as<char>();
     a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
     a.n_rows = n_; a.width = width_; a.nq = nq; a.qb = g.qb; a.n_qtiles = g.n_qtiles; a.n_slices = g.n_slices; a.slice_rows = g.slice_rows;
-    a.k = k; a.L = g.L; a.n_items = g.n_qtiles * g.n_slices; a.words = q.words; a.img_bytes = img;
-    eng_->timed_launch(dtype_ ? "sparse_index_scan_f16" : "sparse_index_scan_f32", 0.0, s, [&] { launch_sparse_scan(dtype_, a, g.lds, s); });
+    a.k = k; a.L = g.L; a.n_items = g.n_qtiles * g.n_slices; a.words = sparse_image_words(n_vocab_); a.img_bytes = img;
+    a.live = live_; a.allow = d_allow;
+    static const char *const names[2][2] = {{"sparse_index_scan_f32", "sparse_index_scan_f32_masked"}, {"sparse_index_scan_f16", "sparse_index_scan_f16_masked"}};
+    eng_->timed_launch(names[dtype_][masked], 0.0, s, [&] { launch_sparse_scan(dtype_, a, g.lds, s); });
     MergeArgs m;
     m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = g.n_slices * k; m.k = k; m.L = merge_L(k); m.ids = d_ids; m.scores = d_scores;
     eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, nq, s); });
 }
 
 int SparseIndex::search_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
-                               std::string &err) {
+                               std::string &err, const uint32_t *d_allow) {
     if (const int go = check_search(nq, kq, d_qids, d_qw, k, d_ids, d_scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
@@ -222,17 +264,18 @@ int SparseIndex::search_device(int nq, int kq, const int32_t *d_qids, const floa
     if (!grow_search(n_, std::min(nq, QCHUNK), k, err)) return -3;
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
-        enqueue_chunk(c, kq, d_qids + (size_t)c0 * kq, d_qw + (size_t)c0 * kq, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
+        enqueue_chunk(c, kq, d_qids + (size_t)c0 * kq, d_qw + (size_t)c0 * kq, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s, d_allow);
     }
     HIP_OK(hipGetLastError(), err, -3);
     return eng_->op_end(op, err) ? 0 : -3;
 }
 
-int SparseIndex::search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err) {
+int SparseIndex::search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err,
+                                       const uint32_t *d_allow) {
     std::vector<int32_t> hid((size_t)nq * k);
     std::vector<float> hsc((size_t)nq * k);
     if (!grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
-    if (search_device(nq, kq, d_qids, d_qw, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err) != 0) { (void)hipStreamSynchronize(stream_); return -3; }
+    if (search_device(nq, kq, d_qids, d_qw, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow) != 0) { (void)hipStreamSynchronize(stream_); return -3; }
     HIP_OK(hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
     HIP_OK(hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
     HIP_OK(hipStreamSynchronize(stream_), err, -3);
@@ -241,10 +284,13 @@ int SparseIndex::search_device_to_host(int nq, int kq, const int32_t *d_qids, co
     return 0;
 }
 
-int SparseIndex::search_host(int nq, int kq, const int32_t *qids, const float *qw, int k, int32_t *ids, float *scores, std::string &err) {
+int SparseIndex::search_host(int nq, int kq, const int32_t *qids, const float *qw, int k, int32_t *ids, float *scores, std::string &err,
+                             const uint32_t *allow) {
     if (const int go = check_search(nq, kq, qids, qw, k, ids, scores, err); go <= 0) return go;
     if (!check_terms("search: query", nq, kq, qids, qw, n_vocab_, false, err)) return -2;
     DeviceGuard g(eng_->device());
+    const uint32_t *d_allow = nullptr;
+    if (!upload_allow(allow, d_allow, err)) return -3;
     std::vector<int32_t> hid((size_t)nq * k);
     std::vector<float> hsc((size_t)nq * k);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
@@ -255,7 +301,78 @@ int SparseIndex::search_host(int nq, int kq, const int32_t *qids, const float *q
         HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
         HIP_OK(hipMemcpyAsync(d, qids + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
         HIP_OK(hipMemcpyAsync(d + half, qw + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
-        if (search_device_to_host(c, kq, (const int32_t *)d, (const float *)(d + half), k, hid.data() + (size_t)c0 * k, hsc.data() + (size_t)c0 * k, err) != 0) return -3;
+        if (search_device_to_host(c, kq, (const int32_t *)d, (const float *)(d + half), k, hid.data() + (size_t)c0 * k, hsc.data() + (size_t)c0 * k, err, d_allow) != 0) return -3;
+    }
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+// a host allow-list (null, or an empty index: d_allow stays null) into allow_, on the index's stream behind whatever is queued; the
+// searches that read it follow on that stream
+bool SparseIndex::upload_allow(const uint32_t *allow, const uint32_t *&d_allow, std::string &err) {
+    if (!allow || n_ == 0) return true;
+    if (!grow(allow_, live_words(n_) * 4, err)) return false;
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
+    HIP_OK(hipMemcpyAsync(allow_.p, allow, live_words(n_) * 4, hipMemcpyHostToDevice, stream_), err, false);
+    d_allow = allow_.as<uint32_t>();
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// rescoring
+// ------------------------------------------------------------------------------------------------
+int SparseIndex::rescore_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int n_cand, const int32_t *d_cand, int k, int32_t *d_ids,
+                                float *d_scores, hipStream_t s, std::string &err) {
+    if (const int go = check_rescore(nq, kq, d_qids, d_qw, n_cand, d_cand, k, d_ids, d_scores, err); go <= 0) return go;
+    DeviceGuard g(eng_->device());
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -3;
+    const int nqc = std::min(nq, QCHUNK);
+    const size_t ent = (size_t)nqc * n_cand;
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(images_, (size_t)nqc * sparse_image_bytes(n_vocab_), err)) return -3;
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        enqueue_queries(c, kq, d_qids + (size_t)c0 * kq, d_qw + (size_t)c0 * kq, s);
+        SparseRescoreArgs a;
+        a.sids = sids_; a.sweights = sweights_; a.counts = counts_; a.images = images_.as<char>(); a.live = live_;
+        a.cand = d_cand + (size_t)c0 * n_cand; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+        a.n_rows = n_; a.width = width_; a.nq = c; a.n_cand = n_cand; a.n_chunks = (n_cand + SPARSE_RESCORE_CAND - 1) / SPARSE_RESCORE_CAND;
+        a.words = sparse_image_words(n_vocab_); a.img_bytes = (unsigned)sparse_image_bytes(n_vocab_);
+        eng_->timed_launch(dtype_ ? "sparse_index_rescore_f16" : "sparse_index_rescore_f32", 0.0, s, [&] { launch_sparse_rescore(dtype_, a, s); });
+        MergeArgs m;
+        m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
+        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
+        eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+    }
+    HIP_OK(hipGetLastError(), err, -3);
+    return eng_->op_end(op, err) ? 0 : -3;
+}
+
+int SparseIndex::rescore_to_host(int nq, int kq, const int32_t *qids, const float *qw, int n_cand, const int32_t *cand, int k, int32_t *ids,
+                                 float *scores, std::string &err) {
+    if (const int go = check_rescore(nq, kq, qids, qw, n_cand, cand, k, ids, scores, err); go <= 0) return go;
+    if (!check_terms("rescore: query", nq, kq, qids, qw, n_vocab_, false, err)) return -2;
+    for (size_t i = 0; i < (size_t)nq * n_cand; ++i)
+        if (cand[i] < -1 || cand[i] >= n_) { err = "rescore: candidate id " + std::to_string(cand[i]) + " is outside [-1, " + std::to_string(n_) + ")"; return -2; }
+    DeviceGuard g(eng_->device());
+    std::vector<int32_t> hid((size_t)nq * k);
+    std::vector<float> hsc((size_t)nq * k);
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        const size_t half = ((size_t)c * kq * 4 + 15) & ~(size_t)15;
+        if (!grow(stage_, 2 * half, err) || !grow(cand_in_, (size_t)c * n_cand * 4, err) || !grow(out_ids_, (size_t)c * k * 4, err) ||
+            !grow(out_scores_, (size_t)c * k * 4, err)) return -3;
+        char *d = stage_.as<char>();
+        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
+        HIP_OK(hipMemcpyAsync(d, qids + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
+        HIP_OK(hipMemcpyAsync(d + half, qw + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
+        HIP_OK(hipMemcpyAsync(cand_in_.p, cand + (size_t)c0 * n_cand, (size_t)c * n_cand * 4, hipMemcpyHostToDevice, stream_), err, -3);
+        if (rescore_device(c, kq, (const int32_t *)d, (const float *)(d + half), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
+                           out_scores_.as<float>(), stream_, err) != 0) { (void)hipStreamSynchronize(stream_); return -3; }
+        HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+        HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+        HIP_OK(hipStreamSynchronize(stream_), err, -3);
     }
     memcpy(ids, hid.data(), hid.size() * 4);
     memcpy(scores, hsc.data(), hsc.size() * 4);
@@ -292,6 +409,234 @@ int SparseIndex::get_rows(int n, const int32_t *row_ids, int32_t *out_ids, float
         memcpy(out_weights + (size_t)i0 * width_, hw.data(), m * 4);
     }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// removed rows, compaction, file form
+// ------------------------------------------------------------------------------------------------
+void SparseIndex::truncate(int n) {
+    if (n < 0 || n >= n_) return;
+    // (the mirror keeps its bits at and beyond size zero; the device words of the dropped rows stay as they are: a search ignores
+    // them, and the add that reuses those rows sets them)
+    if (live_) {
+        for (long long r = n; r < n_;) {
+            const int b = (int)(r & 31);
+            live_h_[(size_t)(r >> 5)] &= b ? (1u << b) - 1u : 0u;
+            r += 32 - b;
+        }
+        n_removed_ = n;
+        for (size_t w = 0; w < live_words(n); ++w) n_removed_ -= __builtin_popcount(live_h_[w]);
+    }
+    n_ = n;
+}
+
+// the bitmap of an index that had none: every row live
+bool SparseIndex::make_live(std::string &err) {
+    if (live_) return true;
+    const size_t lw = live_words(cap_);
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    HIP_OK(hipMalloc((void **)&live_, std::max<size_t>(lw, 1) * 4), err, false);
+    live_h_.assign(lw, 0u);
+    if (n_ > 0) live_set_range_host(live_h_, 0, n_);
+    n_removed_ = 0;
+    if (lw > 0 && hipMemcpy(live_, live_h_.data(), lw * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        drop_live();
+        err = "hipMemcpy (sparse index live words) failed";
+        return false;
+    }
+    return true;
+}
+
+void SparseIndex::drop_live() {
+    if (live_) (void)hipFree(live_);
+    live_ = nullptr;
+    live_h_.clear();
+    n_removed_ = 0;
+}
+
+// mirror words [w0, w1) -> device, on the index's stream behind whatever is queued; blocking
+bool SparseIndex::upload_live(size_t w0, size_t w1, std::string &err) {
+    if (w1 <= w0) return true;
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
+    HIP_OK(hipMemcpyAsync(live_ + w0, live_h_.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, stream_), err, false);
+    HIP_OK(hipEventRecord(busy_, stream_), err, false);
+    HIP_OK(hipStreamSynchronize(stream_), err, false);
+    return true;
+}
+
+int SparseIndex::remove(int n, const int32_t *ids, std::string &err) {
+    if (n < 0 || (n > 0 && !ids)) { err = "remove: n >= 0 and an id pointer required"; return -2; }
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= n_) { err = "remove: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(n_) + ")"; return -2; }
+    if (n == 0) return 0;
+    DeviceGuard g(eng_->device());
+    if (!make_live(err)) return -3;
+    std::vector<int32_t> fresh;                          // the ids this call removes (repeats and removed rows left out)
+    size_t w0 = SIZE_MAX, w1 = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t w = (size_t)ids[i] >> 5;
+        const uint32_t bit = 1u << (ids[i] & 31);
+        if (!(live_h_[w] & bit)) continue;
+        live_h_[w] &= ~bit;
+        fresh.push_back(ids[i]);
+        w0 = std::min(w0, w);
+        w1 = std::max(w1, w + 1);
+    }
+    if (!fresh.empty() && !upload_live(w0, w1, err)) {
+        for (int32_t id : fresh) live_h_[(size_t)id >> 5] |= 1u << (id & 31);      // (the mirror as it was)
+        return -3;
+    }
+    n_removed_ += (int)fresh.size();
+    return (int)fresh.size();
+}
+
+int SparseIndex::compact(int32_t *old_ids, std::string &err) {
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipEventSynchronize(busy_), err, -3);
+    if (n_removed_ == 0) {
+        if (old_ids) for (int i = 0; i < n_; ++i) old_ids[i] = i;
+        drop_live();
+        return n_;
+    }
+    const int nl = n_ - n_removed_;
+    std::vector<int32_t> map((size_t)nl);
+    int j = 0;
+    for (int r = 0; r < n_; ++r)
+        if (live_h_[(size_t)r >> 5] >> (r & 31) & 1u) map[(size_t)j++] = r;
+    const size_t arr = (size_t)blocks_of(nl) * width_ * SPARSE_BLOCK_ROWS * sparse_id_bytes(dtype_);
+    const int cap = blocks_of(nl) * SPARSE_BLOCK_ROWS;
+    void *pi = nullptr, *pw = nullptr;
+    int32_t *pc = nullptr, *d_map = nullptr;
+    const char *failed = nullptr;
+    if (nl > 0) {
+        if (hipMalloc(&pi, arr) != hipSuccess || hipMalloc(&pw, arr) != hipSuccess || hipMalloc((void **)&pc, (size_t)cap * 4) != hipSuccess ||
+            hipMalloc((void **)&d_map, (size_t)nl * 4) != hipSuccess) failed = "hipMalloc (sparse index rows) failed";
+        else if (hipMemcpyAsync(d_map, map.data(), (size_t)nl * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) failed = "hipMemcpy (compaction ids) failed";
+        else {
+            SparseGatherArgs a;
+            a.sids = sids_; a.sweights = sweights_; a.counts = counts_; a.old_ids = d_map; a.dids = pi; a.dweights = pw; a.dcounts = pc;
+            a.n = nl; a.width = width_;
+            eng_->timed_launch(dtype_ ? "sparse_index_gather_f16" : "sparse_index_gather_f32", 0.0, stream_, [&] { launch_sparse_gather(dtype_, a, stream_); });
+            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) failed = "the gather kernel failed";
+        }
+        if (d_map) (void)hipFree(d_map);
+        if (failed) {
+            (void)hipGetLastError();
+            if (pi) (void)hipFree(pi);
+            if (pw) (void)hipFree(pw);
+            if (pc) (void)hipFree(pc);
+            err = failed;
+            return -3;
+        }
+    }
+    if (sids_) (void)hipFree(sids_);
+    if (sweights_) (void)hipFree(sweights_);
+    if (counts_) (void)hipFree(counts_);
+    sids_ = pi; sweights_ = pw; counts_ = pc;
+    cap_ = nl > 0 ? cap : 0;
+    n_ = nl;
+    drop_live();
+    if (old_ids) memcpy(old_ids, map.data(), (size_t)nl * 4);
+    return nl;
+}
+
+namespace {
+
+// device memory <-> file in pieces of at most 64 MiB through a host buffer
+constexpr size_t FILE_PIECE = (size_t)64 << 20;
+
+bool device_to_file(FILE *f, const void *d, size_t bytes, std::vector<char> &buf, std::string &err) {
+    for (size_t o = 0; o < bytes; o += FILE_PIECE) {
+        const size_t c = std::min(FILE_PIECE, bytes - o);
+        if (buf.size() < c) buf.resize(c);
+        HIP_OK(hipMemcpy(buf.data(), (const char *)d + o, c, hipMemcpyDeviceToHost), err, false);
+        if (fwrite(buf.data(), 1, c, f) != c) { err = "write failed"; return false; }
+    }
+    return true;
+}
+
+// one of the two block arrays of n rows: the whole blocks as they are, the last, partial one with its rows at and beyond n zeroed
+bool blocks_to_file(FILE *f, const void *d, int n, int width, size_t eb, std::vector<char> &buf, std::string &err) {
+    const size_t block = (size_t)width * SPARSE_BLOCK_ROWS * eb, whole = (size_t)(n / SPARSE_BLOCK_ROWS);
+    if (!device_to_file(f, d, whole * block, buf, err)) return false;
+    const int rest = n % SPARSE_BLOCK_ROWS;
+    if (rest == 0) return true;
+    std::vector<char> last(block);
+    HIP_OK(hipMemcpy(last.data(), (const char *)d + whole * block, block, hipMemcpyDeviceToHost), err, false);
+    for (int j = 0; j < width; ++j) memset(last.data() + ((size_t)j * SPARSE_BLOCK_ROWS + rest) * eb, 0, (size_t)(SPARSE_BLOCK_ROWS - rest) * eb);
+    if (fwrite(last.data(), 1, block, f) != block) { err = "write failed"; return false; }
+    return true;
+}
+
+}  // namespace
+
+bool SparseIndex::save(const char *path, std::string &err) {
+    if (!path || !*path) { err = "a path is required"; return false; }
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    SparseIndexFileHeader h;
+    h.dtype = (uint32_t)dtype_; h.n_vocab = (uint32_t)n_vocab_; h.width = (uint32_t)width_; h.n_rows = (uint32_t)n_; h.has_live = live_ ? 1u : 0u;
+    unsigned char hdr[INDEX_HEADER_BYTES];
+    sparse_index_header_write(h, hdr);
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) { err = "cannot write '" + tmp + "'"; return false; }
+    std::vector<char> buf;
+    const size_t eb = sparse_id_bytes(dtype_);
+    // (the live words come from the mirror: its bits at and beyond size are zero)
+    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && blocks_to_file(f, sids_, n_, width_, eb, buf, err) &&
+              blocks_to_file(f, sweights_, n_, width_, eb, buf, err) && device_to_file(f, counts_, (size_t)n_ * 4, buf, err) &&
+              (!live_ || fwrite(live_h_.data(), 4, live_words(n_), f) == live_words(n_));
+    ok = (fclose(f) == 0) && ok;
+    if (ok && rename(tmp.c_str(), path) != 0) ok = false;
+    if (!ok) {
+        (void)::remove(tmp.c_str());
+        if (err.empty()) err = "cannot write '" + std::string(path) + "'";
+    }
+    return ok;
+}
+
+SparseIndex *SparseIndex::load(Engine *eng, FILE *f, const SparseIndexFileHeader &h, std::string &err) {
+    const int n = (int)h.n_rows;
+    const uint64_t arr = sparse_index_file_array_bytes(h);
+    // the counts stand behind the two arrays: read and checked first, since the id check needs them
+    std::vector<int32_t> counts((size_t)n);
+    if (fseeko(f, (off_t)(INDEX_HEADER_BYTES + 2 * arr), SEEK_SET) != 0 || fread(counts.data(), 4, counts.size(), f) != counts.size()) { err = "read failed"; return nullptr; }
+    if (!sparse_index_counts_check(h, counts.data(), err)) return nullptr;
+    std::vector<uint32_t> words(h.has_live ? live_words(n) : 0);
+    if (fread(words.data(), 4, words.size(), f) != words.size()) { err = "read failed"; return nullptr; }
+    if (!sparse_index_live_check(h, words.data(), err)) return nullptr;
+    // the ids, in pieces of whole blocks, each checked against the counts in front of any allocation
+    const size_t block = (size_t)h.width * SPARSE_BLOCK_ROWS * sparse_id_bytes((int)h.dtype);
+    const size_t per = std::max<size_t>(1, FILE_PIECE / block), nb = (size_t)blocks_of(n);
+    std::vector<char> buf(std::min(per, std::max<size_t>(nb, 1)) * block);
+    if (fseeko(f, (off_t)INDEX_HEADER_BYTES, SEEK_SET) != 0) { err = "read failed"; return nullptr; }
+    for (size_t b0 = 0; b0 < nb; b0 += per) {
+        const size_t c = std::min(per, nb - b0);
+        if (fread(buf.data(), 1, c * block, f) != c * block) { err = "read failed"; return nullptr; }
+        if (!sparse_index_ids_check(h, buf.data(), b0, c, counts.data(), err)) return nullptr;
+    }
+    std::unique_ptr<SparseIndex> ix(create(eng, (int)h.n_vocab, (int)h.width, (int)h.dtype, err));
+    if (!ix) return nullptr;
+    DeviceGuard g(eng->device());
+    if (n == 0) return ix.release();
+    if (!ix->grow_rows(n, err)) return nullptr;
+    if (fseeko(f, (off_t)INDEX_HEADER_BYTES, SEEK_SET) != 0) { err = "read failed"; return nullptr; }
+    for (void *dst : {ix->sids_, ix->sweights_})
+        for (size_t b0 = 0; b0 < nb; b0 += per) {
+            const size_t c = std::min(per, nb - b0);
+            if (fread(buf.data(), 1, c * block, f) != c * block) { err = "read failed"; return nullptr; }
+            HIP_OK(hipMemcpy((char *)dst + b0 * block, buf.data(), c * block, hipMemcpyHostToDevice), err, nullptr);
+        }
+    HIP_OK(hipMemcpy(ix->counts_, counts.data(), (size_t)n * 4, hipMemcpyHostToDevice), err, nullptr);
+    ix->n_ = n;
+    if (!h.has_live) return ix.release();
+    if (!ix->make_live(err)) return nullptr;
+    std::copy(words.begin(), words.end(), ix->live_h_.begin());
+    ix->n_removed_ = n;
+    for (uint32_t w : words) ix->n_removed_ -= __builtin_popcount(w);
+    if (!ix->upload_live(0, words.size(), err)) return nullptr;
+    return ix.release();
 }
 
 bool SparseIndex::text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err) {

@@ -5,20 +5,25 @@
 // image the scan reads from LDS (sparse_query_kernel), scans the blocks with one row per lane and selects on chip
 // (sparse_index_scan_kernel: a top-k per (query, slice of rows) in LDS), and merges the slices' lists per query with the embedding
 // index's topk_merge_kernel.  Shaped like Index (search.h): grow-only storage and workspace, one event, a stream for the host routes.
+// Removed rows are a device bitmap with a host mirror, there from the first remove to the next compact; while it exists, or under an
+// allow-list, a search launches the masked scan.  rescore scores per-query candidate rows (sparse_index_rescore_kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <string>
+#include <vector>
 
 #include "engine.h"
+#include "sparse_index_file.h"
 #include "sparse_index_kernels.h"
 
 namespace bert_hip {
 
 class SparseIndex {
 public:
-    static constexpr int MAX_K = 256, MAX_TERMS = SPARSE_MAX_TERMS, MAX_VOCAB = SPARSE_MAX_VOCAB;
+    static constexpr int MAX_K = 256, MAX_TERMS = SPARSE_MAX_TERMS, MAX_VOCAB = SPARSE_MAX_VOCAB, MAX_CAND = SPARSE_MAX_CAND;
     static constexpr int QCHUNK = 4096;                  // queries per internal pass (workspace and image-buffer bound)
 
     // dtype 0: i32 ids + f32 weights, 1: u16 ids + f16 weights (n_vocab <= 65536)
@@ -26,6 +31,7 @@ public:
     ~SparseIndex();
 
     int size() const { return n_; }
+    int n_live() const { return n_ - n_removed_; }
     int n_vocab() const { return n_vocab_; }
     int width() const { return width_; }
     int dtype() const { return dtype_; }
@@ -39,34 +45,68 @@ public:
     // host rows, checked (ids in [-1, n_vocab), no id twice in a row, weights finite as stored); blocking
     int add_host(int n, int k_in, const int32_t *ids, const float *weights, std::string &err);
     // ids / scores [nq][k], best first; queries ids / weights [nq][kq] in device memory, unchecked.  Asynchronous on s
-    int search_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err);
-    // host queries, checked as add_host's rows (weights finite as f32), and host results (written only on success); blocking
-    int search_host(int nq, int kq, const int32_t *qids, const float *qw, int k, int32_t *ids, float *scores, std::string &err);
+    // d_allow: null, or device words [ceil(size / 32)], bit set = the row may be returned
+    int search_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err,
+                      const uint32_t *d_allow = nullptr);
+    // host queries, checked as add_host's rows (weights finite as f32), and host results (written only on success); blocking.  allow:
+    // null, or host words as d_allow
+    int search_host(int nq, int kq, const int32_t *qids, const float *qw, int k, int32_t *ids, float *scores, std::string &err,
+                    const uint32_t *allow = nullptr);
+    // Per query its n_cand candidate rows d_cand [nq][n_cand] (ids outside [0, size) and removed rows: no candidate) scored with the
+    // search's bits, the best k to d_ids / d_scores [nq][k].  1 <= n_cand <= 1024; the workspace [chunk][n_cand] grows on demand and is
+    // not part of reserve: call once at the largest shape before a capture.  Asynchronous on s
+    int rescore_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int n_cand, const int32_t *d_cand, int k, int32_t *d_ids,
+                       float *d_scores, hipStream_t s, std::string &err);
+    // host queries (checked as search_host's), candidates (each in [-1, size), -2 otherwise) and results; blocking
+    int rescore_to_host(int nq, int kq, const int32_t *qids, const float *qw, int n_cand, const int32_t *cand, int k, int32_t *ids, float *scores,
+                        std::string &err);
+    // Removed rows: the number newly removed (repeats and removed rows are ignored); an id outside [0, size): -2, nothing changed.  Blocking
+    int remove(int n, const int32_t *ids, std::string &err);
+    // Drops the removed rows: the live ones keep their order and bits and get ids 0 .. n_live - 1; old_ids (nullable) [n_live] receives
+    // their former ids.  The new size; the bitmap is gone afterwards.  Blocking
+    int compact(int32_t *old_ids, std::string &err);
+    // the file form (sparse_index_file.h); blocking.  load: from f, positioned behind the header h that sparse_index_header_check passed
+    bool save(const char *path, std::string &err);
+    static SparseIndex *load(Engine *eng, FILE *f, const SparseIndexFileHeader &h, std::string &err);
+    // the live words of the host mirror, [ceil(size / 32)], bits at and beyond size zero; empty without removals
+    const std::vector<uint32_t> &live_words_host() const { return live_h_; }
     // the stored rows row_ids [n] (each in [0, size)) as out_ids / out_weights [n][width]; blocking
     int get_rows(int n, const int32_t *row_ids, int32_t *out_ids, float *out_weights, std::string &err);
     // Text routes: device buffers of the index for a group's packed token ids | cu_seqlens (in) and its terms ids | weights [n][k] (out);
     // the index's operations that read them are finished
     bool text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err);
     // the results of a device search of nq queries on stream(), d_ids / d_scores in the index's result buffers -> host; blocking
-    int search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err);
+    int search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err,
+                              const uint32_t *d_allow = nullptr);
     // forget the rows behind the first n (an add of several parts that failed part way)
-    void truncate(int n) { if (n < n_) n_ = n; }
+    void truncate(int n);
 
 private:
     SparseIndex() = default;
     bool grow(DevBuf &b, size_t bytes, std::string &err);
     bool grow_rows(int n_rows, std::string &err);
     bool grow_search(int n_rows, int nq, int k, std::string &err);
-    void enqueue_chunk(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s);
+    void enqueue_queries(int nq, int kq, const int32_t *d_qids, const float *d_qw, hipStream_t s);
+    void enqueue_chunk(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
+                       const uint32_t *d_allow);
+    bool upload_allow(const uint32_t *allow, const uint32_t *&d_allow, std::string &err);
+    bool make_live(std::string &err);
+    void drop_live();
+    bool upload_live(size_t w0, size_t w1, std::string &err);
 
     Engine *eng_ = nullptr;
     int n_vocab_ = 0, width_ = 0, dtype_ = 0;
     int n_ = 0, cap_ = 0;                                // rows; capacity in rows, a multiple of 64
     void *sids_ = nullptr, *sweights_ = nullptr;        // [cap_ / 64][width_][64]
     int32_t *counts_ = nullptr;                         // [cap_]
+    // removed rows: device words [cap_ / 32] and their host mirror (bits at and beyond n_ zero), both absent until the first remove
+    uint32_t *live_ = nullptr;
+    std::vector<uint32_t> live_h_;
+    int n_removed_ = 0;
     DevBuf ws_s_, ws_i_, images_;                       // per-(query, slice) lists; the current chunk's query images
     DevBuf stage_, out_ids_, out_scores_;               // host routes: rows / queries / row ids in, results out
     DevBuf text_in_, text_out_;                         // text routes
+    DevBuf allow_, cand_in_;                            // host routes: a caller's allow-list and candidate lists
     hipStream_t stream_ = nullptr;                      // the host routes' stream
     // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
     hipEvent_t busy_ = nullptr;

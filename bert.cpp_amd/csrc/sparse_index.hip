@@ -8,7 +8,7 @@
 //                         row's place depends on its id alone, so an add may start and end anywhere inside a block.
 //   sparse_query_kernel   one workgroup per query: sets the bitmap's bits with LDS atomics, scans the per-word counts, lets each term
 //                         compute its own rank and store its weight there — no sort —, and writes the image to the chunk's buffer.
-//   sparse_index_scan_kernel<DTYPE>  one workgroup of four waves per (slice of row blocks, tile of qb queries).  It stages the tile's
+//   sparse_index_scan_kernel<DTYPE, MASKED>  one workgroup of four waves per (slice of row blocks, tile of qb queries).  It stages the tile's
 //                         images in LDS; each wave walks one block per step, column by column: a lane loads its row's (id, w) of the
 //                         column once and, for each query of the tile, tests the id's bit and on a hit runs
 //                         acc[q] = fmaf(w, qw[prefix[id >> 5] + popc(word & below)], acc[q]).  The columns are in ascending id, so a
@@ -16,6 +16,9 @@
 //                         largest count of its 64 rows (a wave maximum), not to width.  Selection is index_topk_kernel's (search.hip):
 //                         thresholds in registers, a queue behind the top-k in LDS, bitonic_sort_lists when a queue might not take
 //                         another step, one sorted list per (query, slice) into the workspace — which topk_merge_kernel merges.
+//                         The MASKED instantiation (removed rows, an allow-list) reads two mask words per block: see the kernel.
+//   sparse_index_rescore_kernel<DTYPE>  per-query candidate rows against that query's image, one row per lane, the scan's chain.
+//   sparse_index_gather_kernel<DTYPE>   compaction: the live rows' columns and counts into a fresh allocation.
 //   sparse_index_export_kernel<DTYPE>  stored rows, named by id, back as (i32 id, f32 weight) columns: bert_hip_sparse_index_get_rows.
 //
 // Bounds: every id that reaches storage or an image is in [0, n_vocab), whatever the caller's arrays hold, so the scan's LDS reads stay
@@ -117,7 +120,11 @@ __global__ __launch_bounds__(256) void sparse_query_kernel(SparseQueryArgs a) {
     for (unsigned i = t; i < a.img_bytes / 16; i += 256) dst[i] = ((const u32x4 *)smem)[i];
 }
 
-template <int DTYPE>
+// MASKED (removed rows or an allow-list): a row qualifies iff its bit of live & allow is set.  A wave's block of 64 rows starts at a
+// multiple of 64 (slices start at multiples of SPARSE_STEP_ROWS), so its mask is two words, the same for all its lanes, loaded
+// through the scalar path; a lane whose bit is clear is a lane past the rows — count 0, no push —, so a block is walked to the largest
+// count of its qualifying rows and one without any issues no column load.  No word at or beyond ceil(n_rows / 32) is read.
+template <int DTYPE, bool MASKED>
 __global__ __launch_bounds__(NT) void sparse_index_scan_kernel(SparseScanArgs a) {
     using id_t = typename Stored<DTYPE>::id_t;
     using w_t = typename Stored<DTYPE>::w_t;
@@ -154,7 +161,26 @@ __global__ __launch_bounds__(NT) void sparse_index_scan_kernel(SparseScanArgs a)
     const int room = L - k - SPARSE_STEP_ROWS;
     for (int base = r0; base < r1; base += SPARSE_STEP_ROWS) {
         const int brow = base + wave * SPARSE_BLOCK_ROWS, row = brow + lane;
-        const bool rok = row < r1;
+        const bool inb = row < r1;
+        bool rok = inb;
+        if constexpr (MASKED) {
+            const int blk = __builtin_amdgcn_readfirstlane(brow);
+            uint32_t m0 = 0, m1 = 0;
+            if (blk < r1) {                                    // (a block at or beyond r1 has no words)
+                const int wi = blk >> 5;
+                m0 = ~0u;
+                if (a.live) m0 &= a.live[wi];
+                if (a.allow) m0 &= a.allow[wi];
+                if (blk + 32 < a.n_rows) {                     // (the second word exists: wi + 1 < ceil(n_rows / 32))
+                    m1 = ~0u;
+                    if (a.live) m1 &= a.live[wi + 1];
+                    if (a.allow) m1 &= a.allow[wi + 1];
+                }
+            }
+            m0 = __builtin_amdgcn_readfirstlane(m0);
+            m1 = __builtin_amdgcn_readfirstlane(m1);
+            rok = rok && (((lane < 32 ? m0 : m1) >> (lane & 31)) & 1u);
+        }
         const int n = rok ? a.counts[row] : 0;
         int nmax = n;
 #pragma unroll
@@ -163,8 +189,8 @@ __global__ __launch_bounds__(NT) void sparse_index_scan_kernel(SparseScanArgs a)
         float acc[QB_MAX];
 #pragma unroll
         for (int q = 0; q < QB_MAX; ++q) acc[q] = 0.f;
-        const id_t *ip = (const id_t *)a.sids + slot(rok ? row : r0, 0, a.width);
-        const w_t *wp = (const w_t *)a.sweights + slot(rok ? row : r0, 0, a.width);
+        const id_t *ip = (const id_t *)a.sids + slot(inb ? row : r0, 0, a.width);
+        const w_t *wp = (const w_t *)a.sweights + slot(inb ? row : r0, 0, a.width);
         // COL_U columns at a time: their loads are issued together — unconditional, as stored (no conversion between them, which
         // would wait for each), from a column the block has: what a lane reads past its count is masked below —, then the columns
         // are consumed in j order (the chain's order)
@@ -241,6 +267,74 @@ __global__ __launch_bounds__(256) void sparse_index_export_kernel(SparseExportAr
     }
 }
 
+// One workgroup per (query, chunk of SPARSE_RESCORE_CAND candidates).  It stages the query's image in LDS; lane t takes one candidate id
+// and walks its own row's columns j < count in ascending j with the scan's expression from +0 — the score bits of a search.  The loads
+// are strided (a row per lane), not coalesced: candidates are few.  The barrier stands in front of the per-lane walk.
+template <int DTYPE>
+__global__ __launch_bounds__(SPARSE_RESCORE_CAND) void sparse_index_rescore_kernel(SparseRescoreArgs a) {
+    using id_t = typename Stored<DTYPE>::id_t;
+    using w_t = typename Stored<DTYPE>::w_t;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int t = threadIdx.x;
+    const int q = (int)blockIdx.x / a.n_chunks, c = ((int)blockIdx.x - q * a.n_chunks) * SPARSE_RESCORE_CAND + t;
+    {
+        const u32x4 *src = (const u32x4 *)(a.images + (size_t)q * a.img_bytes);
+        for (unsigned i = t; i < a.img_bytes / 16; i += SPARSE_RESCORE_CAND) ((u32x4 *)smem)[i] = src[i];
+    }
+    const int row = c < a.n_cand ? a.cand[(size_t)q * a.n_cand + c] : -1;
+    bool rok = row >= 0 && row < a.n_rows;
+    if (rok && a.live) rok = (a.live[row >> 5] >> (row & 31)) & 1u;
+    __syncthreads();
+    const size_t pf_off = (size_t)a.words * 4, qw_off = pf_off + (((size_t)a.words * 2 + 3) & ~(size_t)3);
+    float acc = 0.f;
+    if (rok) {
+        const int n = min(a.counts[row], a.width);
+        const id_t *ip = (const id_t *)a.sids + slot(row, 0, a.width);
+        const w_t *wp = (const w_t *)a.sweights + slot(row, 0, a.width);
+        for (int j = 0; j < n; ++j) {
+            const int id = (int)ip[(size_t)j * SPARSE_BLOCK_ROWS];
+            const float w = (float)wp[(size_t)j * SPARSE_BLOCK_ROWS];
+            const int wi = id >> 5;
+            const uint32_t bit = 1u << (id & 31);
+            const uint32_t word = ((const uint32_t *)smem)[wi];
+            if (word & bit) {
+                const int r = (int)((const uint16_t *)(smem + pf_off))[wi] + __popc(word & (bit - 1u));
+                acc = __builtin_fmaf(w, ((const float *)(smem + qw_off))[r], acc);
+            }
+        }
+    }
+    if (c < a.n_cand) {
+        a.ws_s[(size_t)q * a.n_cand + c] = rok ? acc : -INFINITY;
+        a.ws_i[(size_t)q * a.n_cand + c] = rok ? row : SENT_ID;
+    }
+}
+
+// Compaction: one thread per slot of dst's blocks (sparse_index_kernels.h SparseGatherArgs)
+template <int DTYPE>
+__global__ __launch_bounds__(256) void sparse_index_gather_kernel(SparseGatherArgs a) {
+    using id_t = typename Stored<DTYPE>::id_t;
+    using w_t = typename Stored<DTYPE>::w_t;
+    const size_t per_block = (size_t)a.width * SPARSE_BLOCK_ROWS;
+    const size_t total = (size_t)((a.n + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS) * per_block;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const size_t blk = e / per_block;
+        const int in = (int)(e - blk * per_block), j = in >> 6, row = (int)blk * SPARSE_BLOCK_ROWS + (in & 63);
+        id_t id = (id_t)0;
+        w_t w = (w_t)0.f;
+        if (row < a.n) {
+            const int old = a.old_ids[row], n = a.counts[old];
+            if (j < n) {
+                const size_t o = slot(old, j, a.width);
+                id = ((const id_t *)a.sids)[o];
+                w = ((const w_t *)a.sweights)[o];
+            }
+            if (j == 0) a.dcounts[row] = n;
+        }
+        ((id_t *)a.dids)[e] = id;
+        ((w_t *)a.dweights)[e] = w;
+    }
+}
+
 DeviceFlags g_scan_lds;
 
 }  // namespace
@@ -251,8 +345,10 @@ DeviceFlags g_scan_lds;
 void sparse_index_kernels_init() {
     // (beyond the 64 KiB a launch gets unasked; a launch that still cannot have it fails, and the search reports the launch error)
     configure_once(g_scan_lds, [] {
-        const bool ok = hipFuncSetAttribute((const void *)sparse_index_scan_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPARSE_LDS_MAX) == hipSuccess &&
-                        hipFuncSetAttribute((const void *)sparse_index_scan_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPARSE_LDS_MAX) == hipSuccess;
+        bool ok = true;
+        for (const void *f : {(const void *)sparse_index_scan_kernel<0, false>, (const void *)sparse_index_scan_kernel<1, false>,
+                              (const void *)sparse_index_scan_kernel<0, true>, (const void *)sparse_index_scan_kernel<1, true>})
+            ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPARSE_LDS_MAX) == hipSuccess && ok;
         if (!ok) (void)hipGetLastError();                      // (not left behind for an unrelated call's check)
     });
 }
@@ -268,8 +364,25 @@ void launch_sparse_query(const SparseQueryArgs &a, hipStream_t s) {
 
 void launch_sparse_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStream_t s) {
     const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
-    if (dtype == 1) BERT_LAUNCH(sparse_index_scan_kernel<1>, dim3(grid), dim3(NT), lds, s, a);
-    else BERT_LAUNCH(sparse_index_scan_kernel<0>, dim3(grid), dim3(NT), lds, s, a);
+    const bool masked = a.live || a.allow;
+    if (dtype == 1 && masked) BERT_LAUNCH((sparse_index_scan_kernel<1, true>), dim3(grid), dim3(NT), lds, s, a);
+    else if (dtype == 1) BERT_LAUNCH((sparse_index_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
+    else if (masked) BERT_LAUNCH((sparse_index_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
+    else BERT_LAUNCH((sparse_index_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
+}
+
+// (an image is at most 50 KiB — SPARSE_MAX_VOCAB —: inside the 64 KiB a launch gets unasked)
+void launch_sparse_rescore(int dtype, const SparseRescoreArgs &a, hipStream_t s) {
+    const unsigned grid = (unsigned)a.nq * (unsigned)a.n_chunks;
+    if (dtype == 1) BERT_LAUNCH(sparse_index_rescore_kernel<1>, dim3(grid), dim3(SPARSE_RESCORE_CAND), (size_t)a.img_bytes, s, a);
+    else BERT_LAUNCH(sparse_index_rescore_kernel<0>, dim3(grid), dim3(SPARSE_RESCORE_CAND), (size_t)a.img_bytes, s, a);
+}
+
+void launch_sparse_gather(int dtype, const SparseGatherArgs &a, hipStream_t s) {
+    const size_t total = (size_t)((a.n + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS) * a.width * SPARSE_BLOCK_ROWS;
+    const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+    if (dtype == 1) BERT_LAUNCH(sparse_index_gather_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
+    else BERT_LAUNCH(sparse_index_gather_kernel<0>, dim3(blocks), dim3(256), 0, s, a);
 }
 
 void launch_sparse_export(int dtype, const SparseExportArgs &a, hipStream_t s) {

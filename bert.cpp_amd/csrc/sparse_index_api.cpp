@@ -1,6 +1,7 @@
 // sparse_index_api.cpp — the bert_hip_sparse_index_* entry points of bert_hip.h: a sparse index (sparse_index.h) on a context's first
 // device.  The text routes tokenize and pack as bert_hip_encode_sparse_batch does, run the MLM head's top-k form into the index's device
-// buffers and hand those to add_device / search_device: the terms never reach the host.
+// buffers and hand those to add_device / search_device: the terms never reach the host.  remove, the filtered searches, rescore,
+// compact and save are frames around the class; load checks the file's header (sparse_index_file.h) before it makes the index.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -8,8 +9,11 @@
 #include <string>
 #include <vector>
 
+#include <sys/stat.h>
+
 #include "../../include/bert_hip.h"
 #include "abi.h"
+#include "sparse_index_file.h"
 
 using namespace bert_hip;
 
@@ -34,6 +38,18 @@ bool text_model_ok(const bert_ctx *ctx, const SparseIndex &x, std::string &err) 
     if (x.n_vocab() != ctx->hp.n_vocab) { err = "the index has n_vocab " + std::to_string(x.n_vocab()) + ", the model's is " + std::to_string(ctx->hp.n_vocab); return false; }
     return true;
 }
+
+// an allow-list of n_words words covers the index (-2 + err otherwise)
+bool allow_ok(const SparseIndex &x, const uint32_t *allow, int32_t n_words, std::string &err) {
+    const int64_t need = ((int64_t)x.size() + 31) / 32;
+    if (!allow || n_words >= need) return true;
+    err = "the allow-list has " + std::to_string(n_words) + " words, an index of " + std::to_string(x.size()) + " rows needs " + std::to_string(need);
+    return false;
+}
+
+struct FileCloser {
+    void operator()(FILE *f) const { if (f) fclose(f); }
+};
 
 // Tokenizes the texts in groups of 4096, cuts each group at chunk_tokens between sentences and at the sentences whose terms fit
 // 32 MiB, and per chunk: ids | cu_seqlens into the index's device buffer, the MLM head's k largest terms of every text into its other
@@ -176,6 +192,80 @@ int32_t bert_hip_sparse_index_search_texts(struct bert_hip_sparse_index *ix, int
         memcpy(scores, hsc.data(), hsc.size() * 4);
         return 0;
     });
+}
+
+int32_t bert_hip_sparse_index_search_filtered(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids, const float *q_weights,
+                                              int32_t k, const uint32_t *allow, int32_t n_words, int32_t *ids, float *scores) {
+    return sparse_index_call("bert_hip_sparse_index_search_filtered", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) -> int32_t {
+        if (!allow_ok(x, allow, n_words, err)) return -2;
+        return x.search_host(n_queries, kq, q_ids, q_weights, k, ids, scores, err, allow);
+    });
+}
+
+int32_t bert_hip_sparse_index_search_filtered_device(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *d_q_ids,
+                                                     const float *d_q_weights, int32_t k, const uint32_t *d_allow, int32_t n_words, int32_t *d_ids,
+                                                     float *d_scores, void *stream) {
+    return sparse_index_call("bert_hip_sparse_index_search_filtered_device", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) -> int32_t {
+        if (!allow_ok(x, d_allow, n_words, err)) return -2;
+        return x.search_device(n_queries, kq, d_q_ids, d_q_weights, k, d_ids, d_scores, (hipStream_t)stream, err, d_allow);
+    });
+}
+
+int32_t bert_hip_sparse_index_rescore(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids, const float *q_weights,
+                                      int32_t n_cand, const int32_t *cand_ids, int32_t k, int32_t *ids, float *scores) {
+    return sparse_index_call("bert_hip_sparse_index_rescore", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) {
+        return x.rescore_to_host(n_queries, kq, q_ids, q_weights, n_cand, cand_ids, k, ids, scores, err);
+    });
+}
+
+int32_t bert_hip_sparse_index_rescore_device(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *d_q_ids,
+                                             const float *d_q_weights, int32_t n_cand, const int32_t *d_cand_ids, int32_t k, int32_t *d_ids,
+                                             float *d_scores, void *stream) {
+    return sparse_index_call("bert_hip_sparse_index_rescore_device", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) {
+        return x.rescore_device(n_queries, kq, d_q_ids, d_q_weights, n_cand, d_cand_ids, k, d_ids, d_scores, (hipStream_t)stream, err);
+    });
+}
+
+int32_t bert_hip_sparse_index_remove(struct bert_hip_sparse_index *ix, int32_t n, const int32_t *ids) {
+    return sparse_index_call("bert_hip_sparse_index_remove", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) { return x.remove(n, ids, err); });
+}
+
+int32_t bert_hip_sparse_index_n_live(struct bert_hip_sparse_index *ix) { return ix && ix->ix ? ix->ix->n_live() : -1; }
+
+int32_t bert_hip_sparse_index_compact(struct bert_hip_sparse_index *ix, int32_t *old_ids) {
+    return sparse_index_call("bert_hip_sparse_index_compact", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) { return x.compact(old_ids, err); });
+}
+
+int32_t bert_hip_sparse_index_save(struct bert_hip_sparse_index *ix, const char *path) {
+    return sparse_index_call("bert_hip_sparse_index_save", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) -> int32_t {
+        if (!path || !*path) { err = "a path is required"; return -2; }
+        return x.save(path, err) ? 0 : -3;
+    });
+}
+
+struct bert_hip_sparse_index *bert_hip_sparse_index_load(struct bert_ctx *ctx, const char *path) {
+    return guarded("bert_hip_sparse_index_load", [&]() -> bert_hip_sparse_index * {
+        const char *me = "bert_hip_sparse_index_load";
+        if (!ctx) { fprintf(stderr, "%s: no context\n", me); return nullptr; }
+        if (!ctx->engine()) { fprintf(stderr, "%s: this context has no device (tokenizer-only): an index lives on the context's device\n", me); return nullptr; }
+        if (!path) { fprintf(stderr, "%s: no path\n", me); return nullptr; }
+        std::unique_ptr<FILE, FileCloser> f(fopen(path, "rb"));
+        struct stat st;
+        if (!f || fstat(fileno(f.get()), &st) != 0 || !S_ISREG(st.st_mode)) { fprintf(stderr, "%s: cannot read '%s'\n", me, path); return nullptr; }
+        // everything the header promises is checked, against the file's length too, before anything is allocated
+        unsigned char hdr[INDEX_HEADER_BYTES];
+        const size_t got = fread(hdr, 1, sizeof hdr, f.get());
+        SparseIndexFileHeader h;
+        std::string err;
+        if (!sparse_index_header_check(hdr, got, (uint64_t)st.st_size, h, err)) { fprintf(stderr, "%s: '%s': %s\n", me, path, err.c_str()); return nullptr; }
+        std::unique_ptr<SparseIndex> ix(SparseIndex::load(ctx->engine(), f.get(), h, err));
+        if (!ix) { fprintf(stderr, "%s: '%s': %s\n", me, path, err.c_str()); return nullptr; }
+        std::unique_ptr<bert_hip_sparse_index> out(new bert_hip_sparse_index);
+        out->ctx = ctx;
+        out->ix = std::move(ix);
+        ctx->sparse_indexes.push_back(out.get());
+        return out.release();
+    }, (bert_hip_sparse_index *)nullptr);
 }
 
 int32_t bert_hip_sparse_index_get_rows(struct bert_hip_sparse_index *ix, int32_t n, const int32_t *row_ids, int32_t *out_ids, float *out_weights) {

@@ -96,6 +96,36 @@ struct SparseScanArgs {
     int *ws_i;
     int n_rows, width, nq, qb, n_qtiles, n_slices, slice_rows, k, L, n_items, words;
     unsigned img_bytes;
+    // words [ceil(n_rows / 32)], bit b of word w set = row 32 w + b is live / may be returned; either may be null = all ones (read by
+    // the masked instantiation only, and last in the block: the unmasked one's argument offsets are what they were)
+    const uint32_t *live, *allow;
+};
+
+// sparse_index_rescore_kernel: one workgroup of SPARSE_RESCORE_CAND lanes per (query, chunk of its candidates); lane t scores row
+// cand[q][chunk * SPARSE_RESCORE_CAND + t] against query q's image with the scan's chain and writes (score, id) — or (-inf, INT_MAX)
+// for an id outside [0, n_rows) or a removed row — to ws [nq][n_cand], which topk_merge_kernel selects from.  LDS: one image
+constexpr int SPARSE_RESCORE_CAND = 256;
+constexpr int SPARSE_MAX_CAND = 1024;
+struct SparseRescoreArgs {
+    const void *sids, *sweights;
+    const int32_t *counts;
+    const char *images;                 // [nq][img_bytes]
+    const uint32_t *live;               // null = every row live
+    const int32_t *cand;                // [nq][n_cand]
+    float *ws_s;                        // [nq][n_cand]
+    int *ws_i;
+    int n_rows, width, nq, n_cand, n_chunks, words;      // n_chunks = ceil(n_cand / SPARSE_RESCORE_CAND)
+    unsigned img_bytes;
+};
+
+// sparse_index_gather_kernel (compaction): new row i < n of dst = the column slots in front of its count, and the count, of row
+// old_ids[i] of src; every other slot of dst's ceil(n / 64) blocks — behind a count, or of a row at or beyond n — is zero
+struct SparseGatherArgs {
+    const void *sids, *sweights;
+    const int32_t *counts, *old_ids;
+    void *dids, *dweights;
+    int32_t *dcounts;
+    int n, width;
 };
 
 // sparse_index_export_kernel: out_ids / out_weights [n][width] = the stored rows rows[i]: ids ascending, then -1 with weight +0
@@ -111,7 +141,10 @@ struct SparseExportArgs {
 void sparse_index_kernels_init();
 void launch_sparse_add(int dtype, const SparseAddArgs &a, hipStream_t s);
 void launch_sparse_query(const SparseQueryArgs &a, hipStream_t s);
+// the masked instantiation iff a.live or a.allow is set
 void launch_sparse_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStream_t s);
+void launch_sparse_rescore(int dtype, const SparseRescoreArgs &a, hipStream_t s);
+void launch_sparse_gather(int dtype, const SparseGatherArgs &a, hipStream_t s);
 void launch_sparse_export(int dtype, const SparseExportArgs &a, hipStream_t s);
 
 }  // namespace bert_hip

@@ -9,6 +9,7 @@
 
 #include "context.h"
 #include "index_file.h"
+#include "sparse_index_file.h"
 #include "partition.h"
 
 using namespace bert_hip;
@@ -787,6 +788,36 @@ int32_t bert_hip_test_partition_header(const void *buf, int32_t buf_len, int64_t
         const uint32_t f[4] = {h.version, h.dim, h.n_lists, h.n_part};
         if (fields) std::copy(f, f + 4, fields);
         return 0;
+    }
+    if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return -1;
+}
+
+int32_t bert_hip_test_sparse_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err, int32_t err_cap) {
+    SparseIndexFileHeader h;
+    std::string e;
+    if (err && err_cap > 0) err[0] = 0;
+    if (buf_len < 0 || file_bytes < 0) e = "negative length";
+    else if (sparse_index_header_check(buf, (size_t)buf_len, (uint64_t)file_bytes, h, e)) {
+        const uint32_t f[6] = {h.version, h.dtype, h.n_vocab, h.width, h.n_rows, h.has_live};
+        if (fields) std::copy(f, f + 6, fields);
+        return 0;
+    }
+    if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return -1;
+}
+
+int32_t bert_hip_test_sparse_index_body(const uint32_t *fields, const void *body, int64_t body_len, char *err, int32_t err_cap) {
+    std::string e;
+    if (err && err_cap > 0) err[0] = 0;
+    if (!fields || body_len < 0) e = "fields and a body length >= 0 required";
+    else {
+        // (the fields through the header check itself: a body is only ever checked under a header that passed)
+        SparseIndexFileHeader g, h;
+        g.version = fields[0]; g.dtype = fields[1]; g.n_vocab = fields[2]; g.width = fields[3]; g.n_rows = fields[4]; g.has_live = fields[5];
+        unsigned char hdr[INDEX_HEADER_BYTES];
+        sparse_index_header_write(g, hdr);
+        if (sparse_index_header_check(hdr, sizeof hdr, (uint64_t)body_len + INDEX_HEADER_BYTES, h, e) && sparse_index_body_check(h, body, (uint64_t)body_len, e)) return 0;
     }
     if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", e.c_str());
     return -1;

@@ -5,11 +5,14 @@
 //
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
 //               [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]
-//   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS]
+//   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
 //   (--sparse [WIDTH]: learned sparse search.  MODEL must carry the MLM head (bert_hip.h "learned sparse embeddings"); every line's WIDTH
 //   largest terms (default 128, 1 .. 256) go into a sparse index (bert_hip_sparse_index_add_texts; --f16: u16 ids and f16 weights),
 //   each query line is searched with its WIDTH largest terms (bert_hip_sparse_index_search_texts), and the output has the dense mode's
-//   shape.  Lines without a term in common with the query score 0 and are not printed.  The dense mode's other options do not apply.)
+//   shape.  Lines without a term in common with the query score 0 and are not printed.  --save: the sparse index goes to PATH once it
+//   is built (bert_hip_sparse_index_save); --load: it comes from PATH instead of being encoded (bert_hip_sparse_index_load; its stored
+//   type is the file's) — TEXTS is still read, for printing, and must have as many lines as the index has rows.  The dense mode's other
+//   options do not apply.)
 //   (--cross-model PATH --cross N: cross-encoder reranking.  PATH is a second model file, one with a classification head (bert_hip.h
 //   "sentence pairs and scores"), loaded into a context of its own.  The stages above return N candidates per query line instead of k
 //   (k <= N <= 256, and N <= --rescore's); bert_hip_score_pairs scores the pairs (query line, candidate line) — each pair read as one
@@ -49,9 +52,10 @@
 namespace {
 void usage(const char *argv0) {
     fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]\n", argv0);
-    fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS]\n", argv0);
+    fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
     fprintf(stderr, "  --sparse [WIDTH]: learned sparse search with a model that carries the MLM head: each line's and each query's WIDTH largest terms\n"
-                    "          (default 128, 1 .. 256) through a sparse index (bert_hip_sparse_index_*); --f16 stores u16 ids and f16 weights.\n");
+                    "          (default 128, 1 .. 256) through a sparse index (bert_hip_sparse_index_*); --f16 stores u16 ids and f16 weights;\n"
+                    "          --save PATH writes the sparse index once it is built, --load PATH reads it instead of encoding TEXTS (still read for printing).\n");
     fprintf(stderr, "  --long: lines of any length, cut into overlapping windows of W ids, S inner ids apart, one row per line (defaults: W 128 or the\n"
                     "          model's position limit if that is less, S three quarters of W - 2).  Without --long a line is cut at the model's position limit.\n");
     fprintf(stderr, "  --maxsim N: the search returns N candidates (k <= N <= 256), which are reranked by the MaxSim score of their token rows against the\n"
@@ -101,8 +105,8 @@ int main(int argc, char **argv) {
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
     if (sparse && (sparse_width < 1 || sparse_width > 256)) { fprintf(stderr, "search: --sparse takes a width of 1 .. 256\n"); return 2; }
-    if (sparse && (dtype != 1 || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model || save || load)) {
-        fprintf(stderr, "search: --sparse goes with -m, -f, -k, -t and --f16 only\n");
+    if (sparse && (dtype != 1 || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model)) {
+        fprintf(stderr, "search: --sparse goes with -m, -f, -k, -t, --f16, --save and --load only\n");
         return 2;
     }
     if (sparse_f16 && !sparse) { fprintf(stderr, "search: --f16 goes with --sparse\n"); return 2; }
@@ -159,9 +163,29 @@ int main(int argc, char **argv) {
             bert_free(ctx);
             return 1;
         }
-        bert_hip_sparse_index *sx = bert_hip_sparse_index_create(ctx, 0, sparse_width, sparse_f16 ? 1 : 0);
-        if (!sx || bert_hip_sparse_index_add_texts(sx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
-            fprintf(stderr, "search: could not build the sparse index\n");
+        bert_hip_sparse_index *sx;
+        if (load) {
+            sx = bert_hip_sparse_index_load(ctx, load);
+            if (!sx) {
+                fprintf(stderr, "search: could not load the sparse index from '%s'\n", load);
+                bert_free(ctx);
+                return 1;
+            }
+            if ((size_t)bert_hip_sparse_index_size(sx) != texts.size()) {
+                fprintf(stderr, "search: '%s' holds %d rows, '%s' has %zu lines\n", load, bert_hip_sparse_index_size(sx), file, texts.size());
+                bert_free(ctx);
+                return 1;
+            }
+        } else {
+            sx = bert_hip_sparse_index_create(ctx, 0, sparse_width, sparse_f16 ? 1 : 0);
+            if (!sx || bert_hip_sparse_index_add_texts(sx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+                fprintf(stderr, "search: could not build the sparse index\n");
+                bert_free(ctx);
+                return 1;
+            }
+        }
+        if (save && bert_hip_sparse_index_save(sx, save) != 0) {
+            fprintf(stderr, "search: could not save the sparse index to '%s'\n", save);
             bert_free(ctx);
             return 1;
         }

@@ -45,6 +45,9 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_sparse_index_create", "bert_hip_sparse_index_free", "bert_hip_sparse_index_size", "bert_hip_sparse_index_reserve",
     "bert_hip_sparse_index_add", "bert_hip_sparse_index_add_device", "bert_hip_sparse_index_add_texts", "bert_hip_sparse_index_search",
     "bert_hip_sparse_index_search_device", "bert_hip_sparse_index_search_texts", "bert_hip_sparse_index_get_rows",
+    "bert_hip_sparse_index_remove", "bert_hip_sparse_index_n_live", "bert_hip_sparse_index_search_filtered",
+    "bert_hip_sparse_index_search_filtered_device", "bert_hip_sparse_index_rescore", "bert_hip_sparse_index_rescore_device",
+    "bert_hip_sparse_index_compact", "bert_hip_sparse_index_save", "bert_hip_sparse_index_load",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -59,6 +62,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool", "bert_hip_test_token_rows",
     "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
     "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid", "bert_hip_test_sparse_scan_geometry",
+    "bert_hip_test_sparse_index_header", "bert_hip_test_sparse_index_body",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -193,6 +197,18 @@ def _declare_product_abi(L):
     L.bert_hip_sparse_index_search_texts.restype = i32
     L.bert_hip_sparse_index_search_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32, vp, vp]
     L.bert_hip_sparse_index_get_rows.restype = i32; L.bert_hip_sparse_index_get_rows.argtypes = [vp, i32, vp, vp, vp]
+    L.bert_hip_sparse_index_remove.restype = i32; L.bert_hip_sparse_index_remove.argtypes = [vp, i32, vp]
+    L.bert_hip_sparse_index_n_live.restype = i32; L.bert_hip_sparse_index_n_live.argtypes = [vp]
+    L.bert_hip_sparse_index_search_filtered.restype = i32
+    L.bert_hip_sparse_index_search_filtered.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
+    L.bert_hip_sparse_index_search_filtered_device.restype = i32
+    L.bert_hip_sparse_index_search_filtered_device.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_sparse_index_rescore.restype = i32; L.bert_hip_sparse_index_rescore.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
+    L.bert_hip_sparse_index_rescore_device.restype = i32
+    L.bert_hip_sparse_index_rescore_device.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_sparse_index_compact.restype = i32; L.bert_hip_sparse_index_compact.argtypes = [vp, vp]
+    L.bert_hip_sparse_index_save.restype = i32; L.bert_hip_sparse_index_save.argtypes = [vp, C.c_char_p]
+    L.bert_hip_sparse_index_load.restype = vp; L.bert_hip_sparse_index_load.argtypes = [vp, C.c_char_p]
 
 
 def lib() -> C.CDLL:
@@ -287,6 +303,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
     L.bert_hip_test_partition_header.restype = i32
     L.bert_hip_test_partition_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
+    L.bert_hip_test_sparse_index_header.restype = i32
+    L.bert_hip_test_sparse_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
+    L.bert_hip_test_sparse_index_body.restype = i32
+    L.bert_hip_test_sparse_index_body.argtypes = [C.POINTER(C.c_uint32), C.c_char_p, C.c_int64, C.c_char_p, i32]
     L.bert_hip_test_build_lists.restype = i32
     L.bert_hip_test_build_lists.argtypes = [i32p, i32, i32, i32p, i32p]
     L.bert_hip_test_group_pool.restype = i32
@@ -1089,6 +1109,10 @@ class BertModel:
         """The index a BertIndex.save wrote (bert_hip_index_load), on this context's first device."""
         return BertIndex(self, _load=path)
 
+    def load_sparse_index(self, path: str) -> "BertSparseIndex":
+        """The sparse index a BertSparseIndex.save wrote (bert_hip_sparse_index_load), on this context's first device."""
+        return BertSparseIndex(self, _load=path)
+
 
 def allow_words(allow, n_rows: int) -> np.ndarray:
     """An allow-list as the uint32 words of bert_hip_index_search_filtered: a bool array of n_rows entries is packed (row 32 w + b
@@ -1415,10 +1439,19 @@ class BertSparseIndex:
     return (ids [n, k] int32, scores [n, k] f32), best first; missing entries are id -1, score -inf.  A ValueError is an argument the
     entry refused (-2).  The *_device forms take device pointers (ints) and a stream handle, and return at once."""
 
-    def __init__(self, model: BertModel, width: int = 128, dtype: str = "f32", n_vocab: Optional[int] = None):
+    def __init__(self, model: BertModel, width: int = 128, dtype: str = "f32", n_vocab: Optional[int] = None, _load: Optional[str] = None):
         if dtype not in ("f32", "f16"):
             raise ValueError("dtype must be 'f32' or 'f16'")
         self.model, self.lib = model, model.lib
+        if _load is not None:
+            # dtype, n_vocab and width come from the file's header (include/bert_hip.h: u32 dtype at byte 12, n_vocab at 16, width at 20)
+            self.ix = self.lib.bert_hip_sparse_index_load(model.ctx, os.fsencode(_load))
+            if not self.ix:
+                raise RuntimeError("bert_hip_sparse_index_load failed (see stderr)")
+            with open(_load, "rb") as f:
+                head = np.frombuffer(f.read(24), dtype="<u4")
+            self.dtype, self.n_vocab, self.width = ("f32", "f16")[int(head[3])], int(head[4]), int(head[5])
+            return
         self.ix = self.lib.bert_hip_sparse_index_create(model.ctx, 0 if n_vocab is None else int(n_vocab), int(width), 1 if dtype == "f16" else 0)
         if not self.ix:
             raise RuntimeError("bert_hip_sparse_index_create failed (see stderr)")
@@ -1481,21 +1514,95 @@ class BertSparseIndex:
             self._fail("bert_hip_sparse_index_add_texts", r)
         return r
 
-    def search(self, q_ids, q_weights, k: int = 10):
+    def search(self, q_ids, q_weights, k: int = 10, allow=None):
+        """allow: None, or the rows that may be returned — a bool array of len(index) entries or uint32 words (allow_words):
+        bert_hip_sparse_index_search_filtered."""
         q_ids, q_weights = self._terms(q_ids, q_weights)
         nq = q_ids.shape[0]
         ids = np.empty((nq, max(k, 1)), dtype=np.int32)
         scores = np.empty((nq, max(k, 1)), dtype=np.float32)
-        r = self.lib.bert_hip_sparse_index_search(self.ix, nq, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data, k, ids.ctypes.data, scores.ctypes.data)
+        if allow is None:
+            name = "bert_hip_sparse_index_search"
+            r = self.lib.bert_hip_sparse_index_search(self.ix, nq, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data, k, ids.ctypes.data, scores.ctypes.data)
+        else:
+            name = "bert_hip_sparse_index_search_filtered"
+            words = allow_words(allow, len(self))
+            r = self.lib.bert_hip_sparse_index_search_filtered(self.ix, nq, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data, k,
+                                                               words.ctypes.data, len(words), ids.ctypes.data, scores.ctypes.data)
         if r != 0:
-            self._fail("bert_hip_sparse_index_search", r)
+            self._fail(name, r)
         return ids, scores
 
     def search_device(self, n_queries: int, kq: int, d_q_ids_ptr: int, d_q_weights_ptr: int, k: int, d_ids_ptr: int, d_scores_ptr: int,
-                      stream: int = 0) -> None:
-        r = self.lib.bert_hip_sparse_index_search_device(self.ix, n_queries, kq, d_q_ids_ptr, d_q_weights_ptr, k, d_ids_ptr, d_scores_ptr, stream)
+                      stream: int = 0, d_allow_ptr: int = 0, n_words: int = 0) -> None:
+        """d_allow_ptr: 0, or device uint32 words [n_words] as search's allow (bert_hip_sparse_index_search_filtered_device)."""
+        if d_allow_ptr:
+            name = "bert_hip_sparse_index_search_filtered_device"
+            r = self.lib.bert_hip_sparse_index_search_filtered_device(self.ix, n_queries, kq, d_q_ids_ptr, d_q_weights_ptr, k, d_allow_ptr, n_words,
+                                                                      d_ids_ptr, d_scores_ptr, stream)
+        else:
+            name = "bert_hip_sparse_index_search_device"
+            r = self.lib.bert_hip_sparse_index_search_device(self.ix, n_queries, kq, d_q_ids_ptr, d_q_weights_ptr, k, d_ids_ptr, d_scores_ptr, stream)
         if r != 0:
-            self._fail("bert_hip_sparse_index_search_device", r)
+            self._fail(name, r)
+
+    def rescore(self, q_ids, q_weights, cand_ids, k: int = 10):
+        """bert_hip_sparse_index_rescore: per query its candidate rows cand_ids [n, n_cand] (-1 = none) scored with the search's bits,
+        the best k of them."""
+        q_ids, q_weights = self._terms(q_ids, q_weights)
+        nq = q_ids.shape[0]
+        cand = np.ascontiguousarray(cand_ids, dtype=np.int32).reshape(nq, -1)
+        ids = np.empty((nq, max(k, 1)), dtype=np.int32)
+        scores = np.empty((nq, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_sparse_index_rescore(self.ix, nq, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data, cand.shape[1],
+                                                   cand.ctypes.data, k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_rescore", r)
+        return ids, scores
+
+    def rescore_device(self, n_queries: int, kq: int, d_q_ids_ptr: int, d_q_weights_ptr: int, n_cand: int, d_cand_ptr: int, k: int,
+                       d_ids_ptr: int, d_scores_ptr: int, stream: int = 0) -> None:
+        r = self.lib.bert_hip_sparse_index_rescore_device(self.ix, n_queries, kq, d_q_ids_ptr, d_q_weights_ptr, n_cand, d_cand_ptr, k,
+                                                          d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_rescore_device", r)
+
+    def remove(self, ids) -> int:
+        """bert_hip_sparse_index_remove: the number of rows newly removed."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        r = self.lib.bert_hip_sparse_index_remove(self.ix, len(ids), ids.ctypes.data)
+        if r < 0:
+            self._fail("bert_hip_sparse_index_remove", r)
+        return r
+
+    @property
+    def n_live(self) -> int:
+        return int(self.lib.bert_hip_sparse_index_n_live(self.ix))
+
+    def compact(self) -> np.ndarray:
+        """bert_hip_sparse_index_compact: drops the removed rows; returns the former ids of the rows now at 0 .. len(index) - 1."""
+        old = np.empty(max(self.n_live, 1), dtype=np.int32)
+        r = self.lib.bert_hip_sparse_index_compact(self.ix, old.ctypes.data)
+        if r < 0:
+            self._fail("bert_hip_sparse_index_compact", r)
+        return old[:r]
+
+    def save(self, path: str) -> None:
+        r = self.lib.bert_hip_sparse_index_save(self.ix, os.fsencode(path))
+        if r != 0:
+            self._fail("bert_hip_sparse_index_save", r)
+
+    def live_ids(self) -> np.ndarray:
+        """The ids a search can return, ascending.  With removed rows: found by rescoring every id against an empty query, 256
+        candidates per query (a removed row is skipped, every other row scores +0)."""
+        n = len(self)
+        if self.n_live == n:
+            return np.arange(n, dtype=np.int32)
+        cand = np.full((n + 255) // 256 * 256, -1, np.int32)
+        cand[:n] = np.arange(n, dtype=np.int32)
+        nq = len(cand) // 256
+        ids, _ = self.rescore(np.full((nq, 1), -1, np.int32), np.zeros((nq, 1), np.float32), cand.reshape(-1, 256), 256)
+        return np.sort(ids[ids >= 0])
 
     def search_texts(self, texts: Sequence, kq: int = 32, k: int = 10, n_threads: int = 6):
         n = len(texts)

@@ -690,7 +690,7 @@ BERT_API struct bert_hip_index *bert_hip_index_load(struct bert_ctx *ctx, const 
  * Results: -1 without an index (or, for the text forms, a context without a device); -2 after a line on stderr for an argument the
  * entry refuses (the checks above, k_in > width, k or kq out of range, a missing pointer, a model without the head); -3 on a device
  * error; -4 for an exception.  Outputs are untouched on error.
- * Not covered: removing rows, allow-lists, compaction, files; an inverted (term-major) organisation; several GPUs; rows wider than
+ * Not covered: an inverted (term-major) organisation; a fused dense + sparse (hybrid) search call; several GPUs; rows wider than
  * 256 terms.                                                                                                                        */
 struct bert_hip_sparse_index;
 BERT_API struct bert_hip_sparse_index *bert_hip_sparse_index_create(struct bert_ctx *ctx, int32_t n_vocab, int32_t width, int32_t dtype);
@@ -709,6 +709,65 @@ BERT_API int32_t bert_hip_sparse_index_search_texts(struct bert_hip_sparse_index
                                                     int32_t kq, int32_t k, int32_t *ids, float *scores);
 BERT_API int32_t bert_hip_sparse_index_get_rows(struct bert_hip_sparse_index *ix, int32_t n, const int32_t *row_ids, int32_t *out_ids,
                                                 float *out_weights);
+
+/* Sparse index: removing rows, filtered search, rescoring, compaction, files — worded after the embedding index's ("Removing rows,
+ * filtered search, compaction, files" and "Rescoring" above); the error codes are the sparse index's (-1 / -2 / -3 / -4, outputs
+ * untouched on error).
+ *   remove   marks the rows ids[n] removed and returns how many were newly removed.  A removed row is never returned by search,
+ *            search_device, search_texts, the filtered forms or rescore.  Ids are stable and size still counts removed rows; n_live is
+ *            size less the removed rows; get_rows still returns a removed row.  An id outside [0, size): -2, the index unchanged.
+ *            Repeats and already-removed ids are ignored.  Rows added later are live.  Blocking.
+ *   search_filtered[_device]   allow: words [n_words] (device memory for _device), bit b of word w set = row 32 w + b may be returned.
+ *            allow == NULL is the plain search and n_words is ignored; n_words < ceil(size / 32): -2.  Words at and beyond
+ *            ceil(size / 32) are never read, bits at and beyond size are ignored.  Over the rows that are live AND allowed every promise
+ *            of the search holds: the score bits of the unfiltered search, the order rule, -1 / -INFINITY slots when fewer than k
+ *            qualify, independence from the other queries, k, the slicing, the add history and host or device entry.  The host form
+ *            copies ceil(size / 32) words; the device form reads the caller's words when the search runs.
+ *   rescore[_device]   per query q its n_cand candidate rows cand_ids[q][0 .. n_cand) scored with the search's bits, the best k of them
+ *            to ids / scores [n_queries][k] in the search's order: for distinct ids, the ids and score bits of search_filtered with that
+ *            one query and an allow-list of exactly its candidates.  -1 entries and removed rows are skipped; a repeated id counts as
+ *            often as it appears.  1 <= n_cand <= 1024, 1 <= k <= 256 (k may exceed n_cand: -1 / -INFINITY slots).  The host form
+ *            checks the queries as search does and refuses an id < -1 or >= size (-2); the device form treats such an id as -1.  The
+ *            workspace [n_queries][n_cand] grows on demand and is not part of reserve: call once at the largest shape before a capture.
+ *            Hybrid search from public calls: bert_hip_index_search_device writes d_ids [n_queries][k] on a stream; pass them as
+ *            d_cand_ids of bert_hip_sparse_index_rescore_device on the same stream (and the reverse through bert_hip_index_rescore_device):
+ *            the ids never leave the device.  A fused dense + sparse score is not provided.
+ *   compact  drops the removed rows: the live rows keep their order and stored bits and get ids 0 .. n_live - 1; old_ids (may be NULL)
+ *            [n_live] receives their former ids.  Returns the new size.  On an index without removals a no-op that returns size (old_ids
+ *            the identity).  Afterwards the index keeps no bitmap and launches the unmasked scan again.  Blocking; allocates.
+ *   save     writes path + ".tmp" and renames it to path.  load: a new index of the context from a file, NULL + a line on stderr for
+ *            any failure.  A loaded index answers every search with the saved one's bits; its n_vocab need not be the context's (the
+ *            text routes still refuse a mismatch).
+ * File form (little-endian); the file is exactly this long:
+ *   header, 64 bytes: magic "BHIPSPX1", u32 version = 1, u32 dtype, u32 n_vocab, u32 width, u32 n_rows, u32 has_live, 32 zero bytes;
+ *   ceil(n_rows / 64) blocks of ids exactly as stored, [block][width][64], i32 (dtype 0) or u16 (dtype 1);
+ *   the same blocks of weights, f32 or f16;
+ *   n_rows i32 counts;
+ *   if has_live: ceil(n_rows / 32) u32 live words, the bits at and beyond n_rows zero.
+ * save writes zeros for the rows of the last block at and beyond n_rows (what HBM holds there is unspecified), so a file's bytes are a
+ * function of the index's rows and removals alone.  load checks, in this order: the header against the file's length, before anything
+ * is allocated (version 1, dtype 0 .. 1, n_vocab 1 .. 262144, width 1 .. 256, has_live 0 .. 1, reserved bytes zero); dtype 1 requires
+ * n_vocab <= 65536; every count is in [0, width]; no live bit at or beyond n_rows; every id in a column below its row's count is in
+ * [0, n_vocab) — which is what keeps the scan's reads in bounds.  Nothing else is checked: weights load as they are, as add_device
+ * would have stored them.                                                                                                            */
+BERT_API int32_t bert_hip_sparse_index_remove(struct bert_hip_sparse_index *ix, int32_t n, const int32_t *ids);
+BERT_API int32_t bert_hip_sparse_index_n_live(struct bert_hip_sparse_index *ix);
+BERT_API int32_t bert_hip_sparse_index_search_filtered(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids,
+                                                       const float *q_weights, int32_t k, const uint32_t *allow, int32_t n_words,
+                                                       int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_sparse_index_search_filtered_device(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq,
+                                                              const int32_t *d_q_ids, const float *d_q_weights, int32_t k,
+                                                              const uint32_t *d_allow, int32_t n_words, int32_t *d_ids, float *d_scores,
+                                                              void *stream);
+BERT_API int32_t bert_hip_sparse_index_rescore(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids,
+                                               const float *q_weights, int32_t n_cand, const int32_t *cand_ids, int32_t k, int32_t *ids,
+                                               float *scores);
+BERT_API int32_t bert_hip_sparse_index_rescore_device(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *d_q_ids,
+                                                      const float *d_q_weights, int32_t n_cand, const int32_t *d_cand_ids, int32_t k,
+                                                      int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_sparse_index_compact(struct bert_hip_sparse_index *ix, int32_t *old_ids);
+BERT_API int32_t bert_hip_sparse_index_save(struct bert_hip_sparse_index *ix, const char *path);
+BERT_API struct bert_hip_sparse_index *bert_hip_sparse_index_load(struct bert_ctx *ctx, const char *path);
 
 BERT_API const char *bert_hip_version(void);
 

@@ -281,6 +281,14 @@ BERT_API int32_t bert_hip_test_attention_grid(int32_t n_sentences, int32_t n_hea
  * bytes of LDS per workgroup.  0; -2 and zeros where the plan refuses (dtype outside 0 .. 1, n_vocab outside 1 .. 262144 or, for dtype 1,
  * beyond 65536, n_rows < 0, nq < 1, k outside 1 .. 256); -1 for a NULL geometry.                                                     */
 BERT_API int32_t bert_hip_test_sparse_scan_geometry(int32_t dtype, int32_t n_vocab, int32_t n_rows, int32_t nq, int32_t k, int64_t *geometry);
+/* The checks bert_hip_sparse_index_load runs on a file (sparse_index_file.h; the format is in bert_hip.h), without a device.
+ * _header: buf holds the first buf_len bytes of a file of file_bytes bytes; 0 and fields = {version, dtype, n_vocab, width, n_rows,
+ * has_live} for a header this build loads, -1 and the reason in err (err_cap bytes) otherwise.  _body: fields as _header returned
+ * them and the body_len bytes of the file behind its header; 0 if every count, every used id and the live words pass, -1 and the
+ * reason in err otherwise (a body_len that is not what the fields describe included).                                            */
+BERT_API int32_t bert_hip_test_sparse_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err,
+                                                   int32_t err_cap);
+BERT_API int32_t bert_hip_test_sparse_index_body(const uint32_t *fields, const void *body, int64_t body_len, char *err, int32_t err_cap);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 """Rate of the sparse index's search (bert_hip_sparse_index_search_device) on one GPU: 10^6 synthetic rows of up to 128 terms drawn
 Zipf-like over V = 30 522, queries of up to 32 terms drawn the same way, both dtypes, 1 / 64 / 4096 queries, k = 10 and 100.
 
-    python tools/sparse_index_rate.py [--rows 1000000] [--qb 1,2,4,8] [--out profiles/sparse_index_rate.txt]
+    python tools/sparse_index_rate.py [--rows 1000000] [--qb 1,2,4,8] [--sections search,filtered,rescore] [--out profiles/sparse_index_rate.txt] [--append]
 
 Per cell: the time per call (device events around back-to-back calls on one stream, the median of the rounds); the bytes of stored terms
 the call reads (every query tile walks every row's terms once: ids + weights of the stored terms, 8 or 4 bytes each, times the tiles) over
@@ -10,6 +10,11 @@ that time, as a share of the project's HBM line (4.8 TB/s) — a 
 and the same search by torch: a sparse_csr_tensor [rows, V] of the stored weights times the dense queries [V, nq], then topk — where this
 torch build can run it (the script says so where it cannot).  --qb: the A/B of the scan's tile size (queries per workgroup, the tuning
 key "sparse_index_qb") at 64 and 4096 queries, which sparse_index_kernels.h's SPARSE_QB was chosen from.
+--sections: "search" is the table above (the default); "filtered": search_filtered_device at k = 10 with 1 and 64 queries under
+allow-lists of 100 %, 50 % and 1 % of the rows at random and 1 % in contiguous 64-row blocks, beside the plain search, and the plain
+search again on an index whose rows were removed down to the same 50 % (the masked scan through the live bits); "rescore":
+rescore_device of 1000 candidates per query (distinct random rows) beside a filtered search of one query under an allow-list of exactly
+such candidates.  --append adds to --out instead of replacing it.
 Everything is in device memory; the rows are generated on the device and added with add_device."""
 import argparse
 import os
@@ -29,8 +34,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--qb", default="1,2,4,8")
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--sections", default="search")
+    ap.add_argument("--append", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    sections = set(a.sections.split(","))
     import torch
     if not torch.cuda.is_available():
         sys.exit("sparse_index_rate.py needs a GPU")
@@ -98,7 +106,6 @@ def main():
             assert len(ix) == N
             term_bytes = n_terms * (8 if dtype == "f32" else 4)
             out(f"# dtype {dtype}: {term_bytes / 1e9:.3f} GB of stored terms")
-            out("#   nq    k   qb tiles slices        ms (min .. max)      queries/s   GB read    share   torch csr @ dense + topk")
             d_ids = torch.empty(4096, 100, dtype=torch.int32, device=dev)
             d_sc = torch.empty(4096, 100, dtype=torch.float32, device=dev)
 
@@ -149,12 +156,78 @@ def main():
                 w = r_w if dtype == "f32" else r_w.half().float()
                 return r_ids, w
 
+            def words_of(mask):
+                """a bool [N] device mask as the allow-list's uint32 words (bit b of word w = row 32 w + b), on the device"""
+                pad = torch.zeros((N + 31) // 32 * 32, dtype=torch.int64, device=dev)
+                pad[:N] = mask.to(torch.int64)
+                w = (pad.view(-1, 32) << torch.arange(32, device=dev, dtype=torch.int64)).sum(dim=1)
+                return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32).contiguous()      # (the words' bits as i32)
+
+            def cell(label, f, note=""):
+                ms, lo, hi = timed(f)
+                out(f"  {label:58s} {ms:9.3f} ({lo:.3f} .. {hi:.3f})   {note}")
+                return ms
+
+            if "filtered" in sections:
+                out(f"# dtype {dtype}: search_filtered_device, k = 10; blocks = the share of 64-row blocks with an allowed row; x = time / the plain search's")
+                blocks = N // 64
+                masks = {"100 %": torch.ones(N, dtype=torch.bool, device=dev),
+                         "50 % random": torch.rand(N, device=dev, generator=gen) < 0.5,
+                         "1 % random": torch.rand(N, device=dev, generator=gen) < 0.01}
+                clustered = torch.zeros(N, dtype=torch.bool, device=dev)
+                pick = torch.randperm(blocks, device=dev, generator=gen)[:max(1, blocks // 100)]
+                clustered.view(-1)[:blocks * 64].view(blocks, 64)[pick] = True
+                masks["1 % in contiguous blocks"] = clustered
+                for nq in (1, 64):
+                    base = cell(f"nq {nq:2d}  plain search (the unmasked kernel)", lambda: search(nq, 10))
+                    for name, mask in masks.items():
+                        d_allow = words_of(mask)
+                        share = float(mask[:blocks * 64].view(blocks, 64).any(dim=1).float().mean())
+                        ms = cell(f"nq {nq:2d}  allow {name} ({int(mask.sum())} rows)",
+                                  lambda: ix.search_device(nq, KQ, q_ids.data_ptr(), q_w.data_ptr(), 10, d_ids.data_ptr(), d_sc.data_ptr(), stream,
+                                                           d_allow.data_ptr(), d_allow.numel()))
+                        lines[-1] += f"blocks {share:.3f}  x {ms / base:.2f}"
+                        print(f"      blocks {share:.3f}  x {ms / base:.2f}", flush=True)
+                        torch.cuda.synchronize()
+                        del d_allow
+
+            if "rescore" in sections:
+                out(f"# dtype {dtype}: rescore_device of 1000 candidates a query, k = 10, beside one filtered query under an allow-list of 1000 such rows")
+                n_cand = 1000
+                cand = torch.stack([torch.randperm(N, device=dev, generator=gen)[:n_cand] for _ in range(64)]).to(torch.int32).contiguous()
+                for nq in (1, 64):
+                    cell(f"nq {nq:2d}  rescore_device, n_cand {n_cand}",
+                         lambda: ix.rescore_device(nq, KQ, q_ids.data_ptr(), q_w.data_ptr(), n_cand, cand.data_ptr(), 10, d_ids.data_ptr(), d_sc.data_ptr(), stream))
+                one = torch.zeros(N, dtype=torch.bool, device=dev)
+                one[cand[0].long()] = True
+                d_allow = words_of(one)
+                # the two agree on the first query: the same ids and score bits
+                ix.rescore_device(1, KQ, q_ids.data_ptr(), q_w.data_ptr(), n_cand, cand.data_ptr(), 10, d_ids.data_ptr(), d_sc.data_ptr(), stream)
+                torch.cuda.synchronize()
+                r_i, r_s = d_ids.view(-1)[:10].clone(), d_sc.view(-1)[:10].clone()
+                cell("nq  1  search_filtered_device, the same 1000 rows allowed",
+                     lambda: ix.search_device(1, KQ, q_ids.data_ptr(), q_w.data_ptr(), 10, d_ids.data_ptr(), d_sc.data_ptr(), stream, d_allow.data_ptr(), d_allow.numel()))
+                torch.cuda.synchronize()
+                assert torch.equal(r_i, d_ids.view(-1)[:10]) and torch.equal(r_s.view(torch.int32), d_sc.view(-1)[:10].view(torch.int32))
+
+            def removals():
+                """the masked scan through the live bits.  Last of all: the index is not the same afterwards"""
+                if "filtered" not in sections:
+                    return
+                half = torch.nonzero(~masks["50 % random"]).view(-1).to(torch.int32).cpu().numpy()
+                ix.remove(half)
+                for nq in (1, 64):
+                    cell(f"nq {nq:2d}  plain search after removing {len(half)} rows (masked kernel)", lambda: search(nq, 10))
+
             m_qb = None
-            for nq in (1, 64, 4096):
+            if "search" in sections:
+                out(f"# dtype {dtype}: search_device")
+                out("#   nq    k   qb tiles slices        ms (min .. max)      queries/s   GB read    share   torch csr @ dense + topk")
+            for nq in (1, 64, 4096) if "search" in sections else ():
                 for k in (10, 100):
                     row(nq, k, with_torch=True)
             # the tile size's A/B
-            if a.qb:
+            if a.qb and "search" in sections:
                 out(f"# dtype {dtype}: tile size A/B (set_option sparse_index_qb), k = 10")
                 for nq in (64, 4096):
                     for qb in a.qb.split(","):
@@ -164,15 +237,20 @@ def main():
                 m.set_option("sparse_index_qb", "0")
                 m_qb = None
             # a sanity check of the last result: ids in range, scores descending
+            if "search" not in sections:
+                removals()
+                ix.close()
+                continue
             search(64, 10)
             torch.cuda.synchronize()
             got_i, got_s = d_ids[:64 * 10].view(-1)[:640].view(64, 10), d_sc.view(-1)[:640].view(64, 10)
             assert bool(((got_i >= 0) & (got_i < N)).all()) and bool((got_s[:, 1:] <= got_s[:, :-1]).all())
+            removals()
             ix.close()
             csr = None
         m.close()
     if a.out:
-        with open(a.out, "w") as f:
+        with open(a.out, "a" if a.append else "w") as f:
             f.write("\n".join(lines) + "\n")
 
 
