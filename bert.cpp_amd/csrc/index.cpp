@@ -95,6 +95,11 @@ int check_search_rescored(int nq, const void *q, int n_cand, int k, const void *
 
 }  // namespace
 
+void index_search_plan(int n_rows, int nq, int k, int geometry[4]) {
+    const Plan p = plan(n_rows, nq, k);
+    geometry[0] = p.nqt; geometry[1] = p.slices; geometry[2] = p.slice_rows; geometry[3] = p.L;
+}
+
 Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
     if (!eng) { err = "no device engine"; return nullptr; }
     if (dim < 1 || dim > MAX_DIM) { err = "dim must be 1 .. 2048"; return nullptr; }

@@ -177,4 +177,9 @@ private:
     hipEvent_t busy_ = nullptr;
 };
 
+// How a search cuts a chunk of nq queries with this k over n_rows rows into workgroups of index_topk_kernel — what plan() of
+// index.cpp gives enqueue_chunk —: geometry = {query tiles, slices, rows per slice, entries of a query's LDS list}.  For the test
+// hook bert_hip_test_index_plan; no device.
+void index_search_plan(int n_rows, int nq, int k, int geometry[4]);
+
 }  // namespace bert_hip

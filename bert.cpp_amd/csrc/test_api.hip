@@ -11,6 +11,7 @@
 #include "index_file.h"
 #include "sparse_index_file.h"
 #include "partition.h"
+#include "search.h"
 
 using namespace bert_hip;
 
@@ -996,6 +997,24 @@ int32_t bert_hip_test_sparse_scan_geometry(int32_t dtype, int32_t n_vocab, int32
     const bool ok = sparse_scan_geometry(dtype, n_vocab, n_rows, nq, k, g);
     geometry[0] = g.qb; geometry[1] = g.n_qtiles; geometry[2] = g.n_slices; geometry[3] = g.slice_rows; geometry[4] = g.L; geometry[5] = (int64_t)g.lds;
     return ok ? 0 : -2;
+}
+
+int32_t bert_hip_test_sparse_scan_geometry_qb(int32_t dtype, int32_t n_vocab, int32_t n_rows, int32_t nq, int32_t k, int32_t qb, int64_t *geometry) {
+    if (!geometry) return -1;
+    SparseScanGeometry g;
+    const bool ok = sparse_scan_geometry(dtype, n_vocab, n_rows, nq, k, g, qb);
+    geometry[0] = g.qb; geometry[1] = g.n_qtiles; geometry[2] = g.n_slices; geometry[3] = g.slice_rows; geometry[4] = g.L; geometry[5] = (int64_t)g.lds;
+    return ok ? 0 : -2;
+}
+
+int32_t bert_hip_test_index_plan(int32_t n_rows, int32_t nq, int32_t k, int32_t *geometry) {
+    if (!geometry) return -1;
+    geometry[0] = geometry[1] = geometry[2] = geometry[3] = 0;
+    if (n_rows < 0 || nq < 1 || nq > Index::QCHUNK || k < 1 || k > Index::MAX_K) return -2;
+    int g[4];
+    index_search_plan(n_rows, nq, k, g);
+    for (int i = 0; i < 4; ++i) geometry[i] = g[i];
+    return 0;
 }
 
 int32_t bert_hip_test_attention_grid(int32_t n_sentences, int32_t n_head, int32_t d_head, int32_t max_len, int32_t *threads, int32_t *items) {

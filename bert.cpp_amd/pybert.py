@@ -63,6 +63,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
     "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid", "bert_hip_test_sparse_scan_geometry",
     "bert_hip_test_sparse_index_header", "bert_hip_test_sparse_index_body",
+    "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -327,6 +328,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_attention_grid.argtypes = [i32, i32, i32, i32, i32p, i32p]
     L.bert_hip_test_sparse_scan_geometry.restype = i32
     L.bert_hip_test_sparse_scan_geometry.argtypes = [i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    L.bert_hip_test_sparse_scan_geometry_qb.restype = i32
+    L.bert_hip_test_sparse_scan_geometry_qb.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    L.bert_hip_test_index_plan.restype = i32
+    L.bert_hip_test_index_plan.argtypes = [i32, i32, i32, i32p]
     _test_lib = L
     return L
 
@@ -435,16 +440,32 @@ def test_sparse_vocab_geometry(H: int, V: int, T: int, ns: int, max_len: int):
     return dict(zip(("tile", "n_tiles", "slab_blocks", "n_slabs"), (int(x) for x in g)))
 
 
-def test_sparse_scan_geometry(dtype: int, n_vocab: int, n_rows: int, nq: int, k: int):
+def test_sparse_scan_geometry(dtype: int, n_vocab: int, n_rows: int, nq: int, k: int, qb: Optional[int] = None):
     """How the sparse index's scan cuts a search (bert_hip_test_sparse_scan_geometry; no GPU): a dict of qb, n_qtiles, n_slices, slice_rows,
-    L and lds, or None where the plan refuses."""
+    L and lds, or None where the plan refuses.  qb: the value of the tuning key "sparse_index_qb" the plan is made under
+    (bert_hip_test_sparse_scan_geometry_qb); None = the key unset."""
     g = (C.c_int64 * 6)()
-    r = test_lib().bert_hip_test_sparse_scan_geometry(dtype, n_vocab, n_rows, nq, k, g)
+    if qb is None:
+        r = test_lib().bert_hip_test_sparse_scan_geometry(dtype, n_vocab, n_rows, nq, k, g)
+    else:
+        r = test_lib().bert_hip_test_sparse_scan_geometry_qb(dtype, n_vocab, n_rows, nq, k, qb, g)
     if r == -2:
         return None
     if r != 0:
         raise RuntimeError(f"bert_hip_test_sparse_scan_geometry failed: {r}")
     return dict(qb=g[0], n_qtiles=g[1], n_slices=g[2], slice_rows=g[3], L=g[4], lds=g[5])
+
+
+def test_index_plan(n_rows: int, nq: int, k: int):
+    """How the embedding index's search cuts a chunk of nq queries (bert_hip_test_index_plan; no GPU): a dict of nqt, slices, slice_rows and
+    L, or None where the hook refuses the arguments."""
+    g = (C.c_int32 * 4)()
+    r = test_lib().bert_hip_test_index_plan(n_rows, nq, k, g)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_index_plan failed: {r}")
+    return dict(nqt=g[0], slices=g[1], slice_rows=g[2], L=g[3])
 
 
 def test_attention_grid(n_sentences: int, n_head: int, d_head: int, max_len: int):

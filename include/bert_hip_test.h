@@ -281,6 +281,15 @@ BERT_API int32_t bert_hip_test_attention_grid(int32_t n_sentences, int32_t n_hea
  * bytes of LDS per workgroup.  0; -2 and zeros where the plan refuses (dtype outside 0 .. 1, n_vocab outside 1 .. 262144 or, for dtype 1,
  * beyond 65536, n_rows < 0, nq < 1, k outside 1 .. 256); -1 for a NULL geometry.                                                     */
 BERT_API int32_t bert_hip_test_sparse_scan_geometry(int32_t dtype, int32_t n_vocab, int32_t n_rows, int32_t nq, int32_t k, int64_t *geometry);
+/* The same plan with the tile the tuning key "sparse_index_qb" asks for: qb 1 .. 8 is the tile to aim for, any other value the table's,
+ * as bert_hip_set_option reads the key.  What comes back in geometry[0] is what the scan gets: at most nq, and at most what the LDS takes. */
+BERT_API int32_t bert_hip_test_sparse_scan_geometry_qb(int32_t dtype, int32_t n_vocab, int32_t n_rows, int32_t nq, int32_t k, int32_t qb,
+                                                       int64_t *geometry);
+/* How the embedding index's search cuts a chunk of nq queries (1 .. 4096, the queries of one internal pass) with this k over n_rows rows
+ * (index.cpp plan, the function the search itself calls; no GPU): geometry = {n_qtiles, n_slices, slice_rows, L} — tiles of 32 queries,
+ * slices of rows, rows per slice (a multiple of the 128 rows of a step; the last may be shorter), entries of a query's LDS list.  0; -2 and
+ * zeros for n_rows < 0, nq outside 1 .. 4096 or k outside 1 .. 256; -1 for a NULL geometry.                                        */
+BERT_API int32_t bert_hip_test_index_plan(int32_t n_rows, int32_t nq, int32_t k, int32_t *geometry);
 /* The checks bert_hip_sparse_index_load runs on a file (sparse_index_file.h; the format is in bert_hip.h), without a device.
  * _header: buf holds the first buf_len bytes of a file of file_bytes bytes; 0 and fields = {version, dtype, n_vocab, width, n_rows,
  * has_live} for a header this build loads, -1 and the reason in err (err_cap bytes) otherwise.  _body: fields as _header returned

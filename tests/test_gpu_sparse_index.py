@@ -131,22 +131,28 @@ SEARCH_CASES = [
 _SEARCH = {}
 
 
-def _search_case(model, case):
-    """index, queries and the reference's scores [NQ][rows] of a case, built once"""
+def build_search_case(model, case):
+    """index, queries and the reference's scores [NQ][rows] of a case, on model (other test files build their own: an index goes with
+    its model)"""
     name, V, dtype, width, fill, rows, kq, qfill, skew = case
-    if name not in _SEARCH:
-        rng = np.random.default_rng(len(name) + V)
-        ids, w = _terms(rng, max(rows, 3), width, V, fill, skew)
-        ids, w = ids[-rows:], w[-rows:]                          # (a single row: the full one)
-        q_ids, q_w = _terms(rng, NQ, kq, V, qfill, skew)        # (query 0: only -1s)
-        if rows > 3 and width > 1:
-            ids[3], q_ids[3] = -1, -1                            # the vocabulary's last id, stored and asked for
-            ids[3, :2], q_ids[3, 0] = [V - 1, 0], V - 1
-        ix = model.sparse_index(width, dtype, n_vocab=V)
-        ix.add(ids, w)
-        st = ref.stored_rows(ids, w, width, dtype)
-        _SEARCH[name] = (ix, q_ids, q_w, ref.scores(st[0], st[1], q_ids, q_w, V))
-    return _SEARCH[name]
+    rng = np.random.default_rng(len(name) + V)
+    ids, w = _terms(rng, max(rows, 3), width, V, fill, skew)
+    ids, w = ids[-rows:], w[-rows:]                              # (a single row: the full one)
+    q_ids, q_w = _terms(rng, NQ, kq, V, qfill, skew)            # (query 0: only -1s)
+    if rows > 3 and width > 1:
+        ids[3], q_ids[3] = -1, -1                                # the vocabulary's last id, stored and asked for
+        ids[3, :2], q_ids[3, 0] = [V - 1, 0], V - 1
+    ix = model.sparse_index(width, dtype, n_vocab=V)
+    ix.add(ids, w)
+    st = ref.stored_rows(ids, w, width, dtype)
+    return ix, q_ids, q_w, ref.scores(st[0], st[1], q_ids, q_w, V)
+
+
+def _search_case(model, case):
+    """build_search_case, built once"""
+    if case[0] not in _SEARCH:
+        _SEARCH[case[0]] = build_search_case(model, case)
+    return _SEARCH[case[0]]
 
 
 @pytest.mark.parametrize("case", SEARCH_CASES, ids=[c[0] for c in SEARCH_CASES])

@@ -1,0 +1,322 @@
+"""CPU proof that the fixtures of test_gpu_topk_order.py reach the queue states they are built for (tests/topk_order_reference.py: the
+patterns and the host model of the selecting kernels' queue).  The geometry comes from the hooks the searches themselves plan with
+(bert_hip_test_index_plan, bert_hip_test_sparse_scan_geometry[_qb]); the model never calls the library.  A fixture that stops reaching
+its state — after a change of a list length, a step or a plan — fails here, not silently on the GPU.  Every test prints the reached
+state of its fixtures (pytest -s)."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from bert_cpp_amd import pybert as libbert
+
+import topk_order_reference as tor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOOKS = ["bert_hip_test_index_plan", "bert_hip_test_sparse_scan_geometry_qb"]
+
+
+def same(res, S, ok, k, what):
+    """the model selects what the order rule selects"""
+    want = tor.reference_topk(S, ok, k)
+    assert np.array_equal(res["ids"], want[0]) and np.array_equal(res["scores"].view(np.uint32), want[1].view(np.uint32)), what
+
+
+# ------------------------------------------------------------------------------------------------
+# the hooks, the values, the model on hand-made cases
+# ------------------------------------------------------------------------------------------------
+def test_hooks_are_declared_and_exported_by_the_test_library_only():
+    text = open(os.path.join(ROOT, "include", "bert_hip_test.h")).read()
+    L, T = libbert.lib(), libbert.test_lib()
+    for hook in HOOKS:
+        assert re.search(r"BERT_API int32_t " + hook + r"\(", text) and hook in libbert.BERT_HIP_TEST_H_SYMBOLS
+        assert hasattr(T, hook) and not hasattr(L, hook)
+
+
+@pytest.mark.parametrize("args, want", [
+    # (n_rows, nq, k)
+    ((0, 1, 1), dict(nqt=1, slices=1, slice_rows=128, L=256)),
+    ((2500, 33, 128), dict(nqt=2, slices=1, slice_rows=2560, L=256)),
+    ((2500, 32, 129), dict(nqt=1, slices=1, slice_rows=2560, L=512)),
+    ((17 * 4096, 33, 256), dict(nqt=2, slices=17, slice_rows=4096, L=512)),
+    ((17 * 4096, 1, 10), dict(nqt=1, slices=34, slice_rows=2048, L=256)),
+    ((1000000, 4096, 100), dict(nqt=128, slices=16, slice_rows=62592, L=256)),
+])
+def test_index_plan_table(args, want):
+    assert libbert.test_index_plan(*args) == want
+
+
+def test_index_plan_invariants_and_refusals():
+    for k in (1, 127, 128, 129, 256):
+        for nq in (1, 31, 32, 33, 4096):
+            for n in (0, 1, 127, 128, 129, 2047, 2048, 4097, 2500, 69632, 1000000, 2 ** 31 - 1):
+                g = libbert.test_index_plan(n, nq, k)
+                assert g["nqt"] == -(-nq // 32) and g["L"] == tor.dense_L(k) and g["L"] - k - tor.DENSE_STEP >= 0
+                assert g["slice_rows"] % tor.DENSE_STEP == 0 and g["slices"] >= 1
+                assert g["slices"] * g["slice_rows"] >= n > (g["slices"] - 1) * g["slice_rows"] - (n == 0)
+    P = libbert.test_index_plan
+    assert P(-1, 1, 1) is None and P(10, 0, 1) is None and P(10, 4097, 1) is None and P(10, 1, 0) is None and P(10, 1, 257) is None
+    assert libbert.test_lib().bert_hip_test_index_plan(10, 1, 1, None) == -1
+    assert libbert.test_lib().bert_hip_test_sparse_scan_geometry_qb(0, 100, 10, 1, 1, 0, None) == -1
+
+
+def test_values_are_exact_in_f16_and_ascending():
+    v = tor.VALUES
+    assert v[0] == 0 and (v[:2049] == np.arange(2049)).all() and (np.diff(v) > 0).all() and len(v) > 7000
+    assert np.array_equal(v.astype(np.float16).astype(np.float32), v) and v[-1] == 65504
+
+
+def test_the_model_on_hand_made_queues():
+    # k = 2, L = 8, steps of 4: room = 2
+    s = np.array([[1, 2, 3, 4, 0, 0, 5, 6, 7, 8, 9, 10]], np.float32)
+    w = tor.walk(s, np.arange(12), True, 2, 8, 4)
+    # step 0 pushes 4 > room: sort, threshold (3, 2); step 1 pushes 5, 6: count 2 == room, no sort; step 2 pushes 4: slots up to 2 + 5 = 7
+    assert w["sort_steps"] == [0, 2] and w["max_slot"] == 7 and w["fit_stale"][0] and not w["fit_fresh"][0] and w["pushed_late"][0]
+    assert w["ids"].tolist() == [[11, 10]] and w["scores"].tolist() == [[10.0, 9.0]]
+    # all ties: only the first k rows ever push; a masked row never does
+    w = tor.walk(np.zeros((1, 12), np.float32), np.arange(12), np.arange(12) != 0, 2, 8, 4)
+    assert w["ids"].tolist() == [[1, 2]] and not w["pushed_late"][0] and w["sorts"] == 1 and w["max_slot"] == 4
+    # two queries share the sort: the idle one's count is reset with the busy one's
+    both = np.stack([s[0], -s[0]])
+    w = tor.walk(both, np.arange(12), True, 2, 8, 4)
+    assert w["ids"].tolist() == [[11, 10], [4, 5]] and w["pushed_late"].tolist() == [True, True]
+    # fresh fit: two rows allowed, then a whole step, thresholds still -inf
+    ok = np.ones(12, bool)
+    ok[[1, 3]] = False
+    w = tor.walk(s, np.arange(12), ok, 2, 8, 4)
+    assert w["fit_fresh"][0] and w["max_slot"] == 7 and w["sort_steps"] == [1, 2]
+
+
+def test_fit_schedule_counts():
+    for step, Lf in ((tor.DENSE_STEP, tor.dense_L), (tor.SPARSE_STEP, tor.sparse_L)):
+        for k in (1, 127, 128, 129, 255, 256):
+            L = Lf(k)
+            room = L - k - step
+            push = tor.fit_schedule(20 * step, k, L, step, 0)
+            steps = push.reshape(20, step).sum(axis=1)
+            cyc = (room // step + (room % step > 0) if room else 1) + 1
+            assert steps[:cyc - 1].sum() == room and steps[cyc - 1] == step and (steps[:cyc] == steps[cyc:2 * cyc]).all(), (step, k, steps)
+
+
+# ------------------------------------------------------------------------------------------------
+# index_topk_kernel
+# ------------------------------------------------------------------------------------------------
+def check_near_miss_mask(fx, nq, tile, k, L, step, plan):
+    """the second allow-list of a masked fixture: one row more than fits while the thresholds are still -inf — sorted, then a whole step"""
+    for name, lay in tor.layouts(fx.kinds, fx.busy, fx.idle, nq, tile).items():
+        S = fx.S(lay)
+        res = tor.sliced_search(S, fx.ok1, k, tile, plan[0], plan[1], L, step)
+        same(res, S, fx.ok1, k, (fx.name, "near miss", nq, name))
+        for w in res["wgs"]:
+            kinds = lay[w["q0"]:w["q0"] + tile]
+            if name != "mixed" and name.split(":")[1] == "asc":
+                pos = kinds.index("asc")
+                assert w["near_miss"][pos], (fx.name, "near miss", nq, name)
+
+
+def check_tile_states(fx, name, lay, res, tile, L, k, step, mode, what):
+    """the states a first / last / mixed layout is built for, over the workgroups of res"""
+    room = L - k - step
+    for w in res["wgs"]:
+        q0 = w["q0"]
+        kinds = lay[q0:q0 + tile]
+        if name == "mixed":
+            if room == 0 and "asc" in kinds and fx.ok is None:
+                assert w["sorts"] == w["steps"], (what, "a sort at every step", w["sorts"], w["steps"])
+            continue
+        b = name.split(":")[1]
+        pos = [i for i, kk in enumerate(kinds) if kk == b]
+        idle = [i for i, kk in enumerate(kinds) if kk != b]
+        assert len(pos) == 1 and pos[0] == (0 if name.startswith("first") else len(kinds) - 1)
+        # the idle neighbours never push after their first k rows
+        assert not w["pushed_late"][idle].any(), (what, "idle neighbours")
+        if b in ("asc", "stair"):
+            assert w["pushed_late"][pos[0]], what
+        if b == "stair":
+            assert w["fit_stale"][pos[0]] and w["max_slot"] == L - 1, (what, "exact fit, stale thresholds", w["max_slot"])
+        if b == "over":
+            assert w["near_miss"][pos[0]], (what, "one row more than fits: sorted, then a whole step")
+        if b == "asc" and mode != "plain":
+            assert w["fit_fresh"][pos[0]] and w["max_slot"] == L - 1, (what, "exact fit, thresholds still -inf", w["max_slot"])
+        if b == "asc" and mode == "plain" and room == 0:
+            assert w["sorts"] == w["steps"] and w["max_slot"] == L - 1, (what, "a sort at every step")
+
+
+@pytest.mark.parametrize("mode", tor.MODES)
+@pytest.mark.parametrize("k", tor.DENSE_KS)
+@pytest.mark.parametrize("dtype", tor.DENSE_DTYPES)
+def test_dense_fixtures_reach_their_states(dtype, k, mode):
+    for fx in tor.dense_fixtures(dtype, k, mode):
+        for nq in tor.DENSE_NQS:
+            g = libbert.test_index_plan(fx.n, nq, k)
+            assert g["L"] == tor.dense_L(k) and g["slices"] == 1 and g["nqt"] == -(-nq // tor.QT), g
+            assert 15 <= -(-fx.n // tor.DENSE_STEP) <= 20 and fx.n % tor.DENSE_STEP != 0
+            for name, lay in tor.layouts(fx.kinds, fx.busy, fx.idle, nq, tor.QT).items():
+                S = fx.S(lay)
+                res = tor.sliced_search(S, fx.permitted(), k, tor.QT, g["slices"], g["slice_rows"], g["L"], tor.DENSE_STEP)
+                what = (fx.name, nq, name)
+                same(res, S, fx.permitted(), k, what)
+                check_tile_states(fx, name, lay, res, tor.QT, g["L"], k, tor.DENSE_STEP, mode, what)
+                if nq == 32:
+                    print(tor.describe(f"{fx.name} nq={nq} {name}", res))
+            if mode == "allow":
+                check_near_miss_mask(fx, nq, tor.QT, k, g["L"], tor.DENSE_STEP, (g["slices"], g["slice_rows"]))
+        if mode != "plain":
+            # the mask: some whole 32-row word is empty (k = 128) or not, and the masked kernel is the one launched
+            assert not fx.ok.all() and fx.ok.sum() > 256
+
+
+# ------------------------------------------------------------------------------------------------
+# many slices: the merge
+# ------------------------------------------------------------------------------------------------
+def check_many(res, lay, k, slices_aimed, what):
+    assert res["slices"] >= slices_aimed, what
+    m = res["merge"]
+    if k == 256:
+        assert m["rounds"] >= 2 and m["n_cand"] == res["slices"] * k > tor.MERGE_OUTER, what
+        for q, kind in enumerate(lay):
+            w = m["walks"][q]
+            if kind == "asc":
+                # every slice beats all earlier ones: the merge takes a whole list per round, sorts after each, and fills its queue to the end
+                assert w["sorts"] == res["slices"] and w["max_slot"] == tor.MERGE_L - 1, (what, w["sorts"])
+            else:
+                assert w["sorts"] == 1 and not w["pushed_late"][0], what
+
+
+@pytest.mark.parametrize("k", tor.MANY_KS)
+def test_many_slices_reach_a_second_merge_round(k):
+    n = tor.MANY_DENSE_ROWS
+    sc = tor.many_scores(n)
+    for nq in tor.MANY_NQS:
+        lay = tor.many_layout(nq)
+        S = np.stack([sc[kk] for kk in lay])
+        g = libbert.test_index_plan(n, nq, k)
+        res = tor.sliced_search(S, True, k, tor.QT, g["slices"], g["slice_rows"], g["L"], tor.DENSE_STEP)
+        same(res, S, True, k, ("dense", nq, k))
+        check_many(res, lay, k, 17, ("dense", nq, k))
+        print(tor.describe(f"dense f32 {n} rows nq={nq} k={k}", res), "slices", res["slices"])
+    n = tor.MANY_SPARSE_ROWS
+    sc = tor.many_scores(n)
+    for nq in tor.MANY_NQS:
+        lay = tor.many_layout(nq)
+        S = np.stack([sc[kk] for kk in lay])
+        g = libbert.test_sparse_scan_geometry(0, tor.SPARSE_V, n, nq, k)
+        assert g["L"] == tor.sparse_L(k)
+        res = tor.sliced_search(S, True, k, g["qb"], g["n_slices"], g["slice_rows"], g["L"], tor.SPARSE_STEP)
+        same(res, S, True, k, ("sparse", nq, k))
+        check_many(res, lay, k, 17, ("sparse", nq, k))
+        print(tor.describe(f"sparse f32 {n} rows nq={nq} k={k}", res), "slices", res["slices"])
+
+
+@pytest.mark.parametrize("k", tor.MERGE_KS)
+def test_rescored_candidates_reach_the_merge_s_exact_fit(k):
+    sc = tor.merge_scores(k)
+    S = np.stack([sc[kk] for kk in tor.MERGE_KINDS])
+    m = tor.merge(S, np.tile(np.arange(tor.MERGE_CAND), (len(S), 1)), k)
+    same(m, S, True, k, k)
+    by = dict(zip(tor.MERGE_KINDS, m["walks"]))
+    assert m["n_cand"] == tor.MERGE_CAND and by["stair"]["steps"] == 4
+    assert by["stair"]["fit_stale"][0] and by["stair"]["max_slot"] == tor.MERGE_L - 1 and by["over"]["near_miss"][0]
+    assert not by["const"]["pushed_late"][0]
+    print(f"merge k={k}: " + ", ".join(f"{kk}: sorts {w['sorts']} largest slot {w['max_slot']} of {w['L']} (room {w['room']})" for kk, w in by.items()))
+
+
+# ------------------------------------------------------------------------------------------------
+# index_probe_kernel
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("form", tor.PROBE_FORMS)
+@pytest.mark.parametrize("k", tor.PROBE_KS)
+@pytest.mark.parametrize("dtype", tor.DENSE_DTYPES)
+def test_probe_fixtures_reach_their_states(dtype, k, form):
+    fx = tor.probe_fixture(dtype, k, form)
+    masked = form == "allow"
+    L = tor.dense_L(k)
+    assert len(fx.long_rows) >= 1500 and fx.n - fx.n_part > tor.PROBE_CHUNK and fx.n_part % 32 != 0
+    lay = tor.probe_layout()
+    S = fx.S(lay)
+    res = tor.probed_search(S, fx.permitted(), k, fx.lists, tor.PROBE_LISTS)
+    same(res, S, fx.permitted(), k, fx.name)
+    assert len(res["items"]) == tor.PROBE_LISTS + 2 and res["wgs"][3] is None          # an empty list; two tail chunks
+    long_list = res["wgs"][0]
+    if form == "over":
+        assert long_list["near_miss"][0], fx.name
+    else:
+        assert long_list["max_slot"] == L - 1 and long_list["fit_fresh" if masked else "fit_stale"][0], (fx.name, long_list["max_slot"])
+    assert not long_list["pushed_late"][2]                           # (the constant query)
+    if masked:
+        near = tor.probed_search(S, fx.ok1, k, fx.lists, tor.PROBE_LISTS)
+        same(near, S, fx.ok1, k, (fx.name, "near miss"))
+        assert near["wgs"][0]["near_miss"][0], fx.name
+    if k == 128 and not masked:
+        tail = res["wgs"][tor.PROBE_LISTS]
+        assert tail["sorts"] == tail["steps"] == tor.PROBE_CHUNK // tor.DENSE_STEP         # ascending at room 0: a sort at every step
+    print(tor.describe(fx.name, res))
+
+
+# ------------------------------------------------------------------------------------------------
+# sparse_index_scan_kernel
+# ------------------------------------------------------------------------------------------------
+SPARSE_NQS = (1, 2, 3, 5)
+
+
+@pytest.mark.parametrize("mode", tor.MODES)
+@pytest.mark.parametrize("k", tor.SPARSE_KS)
+@pytest.mark.parametrize("dtype", tor.SPARSE_DTYPES)
+def test_sparse_fixtures_reach_their_states(dtype, k, mode):
+    fx = tor.sparse_fixture(dtype, k, mode)
+    for nq in SPARSE_NQS:
+        g = libbert.test_sparse_scan_geometry(tor.SPARSE_DTYPES.index(dtype), tor.SPARSE_V, fx.n, nq, k)
+        assert g["L"] == tor.sparse_L(k) and g["n_slices"] == 1 and g["qb"] == min(2, nq), g
+        for name, lay in tor.layouts(fx.kinds, fx.busy, fx.idle, nq, g["qb"]).items():
+            S = fx.S(lay)
+            res = tor.sliced_search(S, fx.permitted(), k, g["qb"], 1, g["slice_rows"], g["L"], tor.SPARSE_STEP)
+            what = (fx.name, nq, name)
+            same(res, S, fx.permitted(), k, what)
+            check_tile_states(fx, name, lay, res, g["qb"], g["L"], k, tor.SPARSE_STEP, mode, what)
+            if nq == 2:
+                print(tor.describe(f"{fx.name} nq={nq} {name}", res))
+        if mode == "allow":
+            check_near_miss_mask(fx, nq, g["qb"], k, g["L"], tor.SPARSE_STEP, (1, g["slice_rows"]))
+    if k == 256 and mode == "plain":
+        # room 512: two whole steps behind a sort, unsorted, and a third up to slot 1023
+        st = fx.scores["stair"]
+        lead = tor.staircase_lead(k, 1024, tor.SPARSE_STEP)
+        assert (st[lead * 256:(lead + 3) * 256] > 0).all() and g["L"] - k - tor.SPARSE_STEP == 512
+
+
+TILES = (1, 2, 3, 4, 5, 8)
+
+
+def tile_nqs(n):
+    return sorted({n - 1, n, n + 1, 70} - {0})
+
+
+@pytest.mark.parametrize("mode", ["plain", "allow"])
+@pytest.mark.parametrize("n", TILES)
+def test_sparse_tile_sizes_reach_their_states(n, mode):
+    k = 128
+    fx = tor.sparse_fixture("f32", k, mode)
+    for nq in tile_nqs(n):
+        g = libbert.test_sparse_scan_geometry(0, tor.SPARSE_V, fx.n, nq, k, qb=n)
+        assert g["qb"] == min(n, nq) and g["n_qtiles"] == -(-nq // g["qb"]), g
+        for name, lay in tor.layouts(fx.kinds, fx.busy, fx.idle, nq, g["qb"]).items():
+            S = fx.S(lay)
+            res = tor.sliced_search(S, fx.permitted(), k, g["qb"], g["n_slices"], g["slice_rows"], g["L"], tor.SPARSE_STEP)
+            same(res, S, fx.permitted(), k, (fx.name, n, nq, name))
+            check_tile_states(fx, name, lay, res, g["qb"], g["L"], k, tor.SPARSE_STEP, mode, (fx.name, n, nq, name))
+        print(tor.describe(f"{fx.name} tile {n} nq={nq} {name}", res))
+
+
+def test_sparse_tile_option_values_and_the_lds_clamp():
+    G = libbert.test_sparse_scan_geometry
+    table = G(0, 30522, 5000, 70, 10)
+    for bad in (0, 9, -1):
+        assert G(0, 30522, 5000, 70, 10, qb=bad) == table
+    assert G(0, 30522, 5000, 70, 10, qb=2) == table and table["qb"] == 2
+    for n in TILES:
+        assert G(1, 30522, 5000, 70, 10, qb=n)["qb"] == n
+    # the largest query image: the LDS takes fewer than 8 of them
+    for k, want in ((10, 3), (256, 2)):
+        g = G(0, 262144, 130, 70, k, qb=8)
+        assert 1 <= g["qb"] < 8 and g["qb"] == want and g["lds"] <= 160 * 1024 - 256 < g["lds"] // g["qb"] * (g["qb"] + 1), g

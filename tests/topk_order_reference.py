@@ -1,0 +1,617 @@
+"""Ordered score sequences for the selecting kernels, and a host model of their candidate queue.  Nothing here touches the GPU or
+calls the library: test_topk_order_host.py proves on the CPU that each fixture reaches the queue state it is meant to reach, and
+test_gpu_topk_order.py runs the same fixtures through index_topk_kernel, index_probe_kernel, topk_merge_kernel (search.hip) and
+sparse_index_scan_kernel (sparse_index.hip).
+
+The kernels select alike.  A query's current top-k stands in slots [0, k) of an LDS list of L entries; a (score, id) threshold — the
+k-th best at the last sort, (-inf, INT_MAX) before the first — lives in registers; every row that ranks before the threshold is
+pushed behind slot k; the lists of a workgroup are sorted, and the thresholds refreshed, only when some query's count exceeds
+room = L - k - step, step being the most pushes between two checks.  So k + room + step = L with nothing to spare: a step that
+ends with count == room is not sorted, and the next one may push up to slot L - 1.
+
+Scores.  Every value is a non-negative integer that f16 holds exactly (VALUES: 0 .. 2048, then every 2nd, 4th, ... up to 65504),
+named by its rank: rank 0 is the value 0, a larger rank a larger value.  A row carries one value per pattern, a query selects one
+of them with weight +1 or -1 or selects nothing, so a score is one product by +-1 and sums of zeros: exact in f16 and f32 in every
+accumulation order.  The quantized forms (i8: one nonzero column per row; b1: the first rank bits set, against an all-ones query)
+keep the ORDER of the ranks, and index_reference.exact_scores states their bits."""
+import numpy as np
+
+import index_reference as ixr
+import sparse_index_reference as sref
+
+SENT = 2 ** 31 - 1                      # id of an empty list entry (score -inf)
+QT = 32                                 # queries of a dense tile
+DENSE_STEP, SPARSE_STEP = 128, 256      # rows per step
+MERGE_STEP, MERGE_L, MERGE_OUTER = 256, 512, 4096
+PROBE_CHUNK = 1024                      # rows of a tail chunk of the probed search
+
+
+def dense_L(k):
+    """entries of a list of index_topk_kernel and index_probe_kernel"""
+    return 256 if k <= 128 else 512
+
+
+def sparse_L(k):
+    return 512 if k <= 128 else 1024
+
+
+_ints = np.arange(65505, dtype=np.float32)
+VALUES = _ints[_ints.astype(np.float16).astype(np.float32) == _ints]      # ascending; VALUES[r] == r for r <= 2048
+
+
+def values(ranks):
+    return VALUES[np.asarray(ranks, dtype=np.int64)]
+
+
+# ------------------------------------------------------------------------------------------------
+# patterns: ranks [n] as functions of the row id
+# ------------------------------------------------------------------------------------------------
+def ascending(n, base=0):
+    """every row beats everything before it.  (Descending is the same rows under the negated query, constant the zero query: all
+    ties, only the k smallest ids may come back.)"""
+    return base + 1 + np.arange(n)
+
+
+def sawtooth(n, step):
+    """period 2 * step; the teeth repeat their values, so later teeth tie with earlier ones and lose by id"""
+    return 1 + np.arange(n) % (2 * step)
+
+
+def fit_schedule(n, k, L, step, lead, extra=0):
+    """push [n] bool — the rows that are to enter the queue: `lead` steps of all rows, then cycles of (exactly room = L - k - step rows
+    packed into as few steps as take them, then a whole step).  A queue that was emptied in front of a cycle so ends a step with
+    count == room, is not sorted, and takes a full step behind it: up to slot L - 1.  room == 0: the cycle is (a step of no row, a whole
+    step).  extra = 1: room + 1 rows — one more than fits, so the step must be sorted; a kernel that did not would write slot L."""
+    room = L - k - step
+    assert room >= 0 and lead >= 0
+    out = np.ones((n + step - 1) // step * step + 2 * L + 2 * step, dtype=bool)
+    pos = lead * step
+    room += extra
+    while pos < n:
+        if room == 0:
+            out[pos:pos + step] = False
+            pos += step
+        else:
+            pos += room // step * step
+            p = room % step
+            if p:
+                out[pos:pos + step] = False
+                out[pos + np.arange(p) * step // p] = True         # p rows spread over the step's waves
+                pos += step
+        pos += step
+    return out[:n]
+
+
+def staircase_lead(k, L, step):
+    """the steps of all-pushing rows after which a queue has been sorted for the first time and holds k rows"""
+    lead = (L - k - step) // step + 1
+    assert lead * step >= k
+    return lead
+
+
+def staircase(n, k, L, step, extra=0):
+    """the exact-fit pattern of the unmasked kernels: the rows of fit_schedule that push are ascending, the others have rank 0 — below
+    the threshold that the first sort (at the end of the lead) left in the registers.  extra = 1: the near miss, one row more than fits"""
+    push = fit_schedule(n, k, L, step, staircase_lead(k, L, step), extra)
+    return np.where(push, np.cumsum(push), 0)
+
+
+def fit_mask(n, k, L, step, extra=0):
+    """the exact-fit pattern of the masked kernels, over ascending rows: the rows that are not to push are removed or disallowed, so
+    the first cycle runs while the thresholds are still -inf.  Two rows near the end are masked in any case (k + step == L - step has
+    a schedule of all rows).  extra = 1: the near miss, as staircase's."""
+    ok = fit_schedule(n, k, L, step, 0, extra).copy()
+    ok[[n - 1, max(0, n - 3)]] = False
+    return ok
+
+
+# ------------------------------------------------------------------------------------------------
+# the queue model
+# ------------------------------------------------------------------------------------------------
+def _better(s, i, ts, ti):
+    return (s > ts) | ((s == ts) & (i < ti))
+
+
+def walk(scores, ids, ok, k, L, step):
+    """One workgroup: scores [nq, n] f32 of its nq queries against its n rows in the order it meets them, ids [n], ok [n] or [nq, n]
+    (False: the row is removed, disallowed or an empty entry, and never pushed).  Pushes and sorts only.  Returns
+      steps, sorts (not counting the one behind the last step), sort_steps (the steps that ended in a sort),
+      max_slot (the largest slot written; -1: none), fit_fresh / fit_stale [nq] (a step ended with count == room, unsorted, and the next
+      step pushed `step` rows — before / after the workgroup's first sort), near_miss [nq] (a step ended with count == room + 1, was
+      sorted, and the next step pushed `step` rows), pushed_late [nq] (a push after the first sort),
+      ids / scores [nq, k] (the lists at the end, best first; SENT / -inf where empty)."""
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    nq, n = scores.shape
+    ids = np.asarray(ids, dtype=np.int64)
+    ok = np.ascontiguousarray(np.broadcast_to(np.asarray(ok, dtype=bool), (nq, n)))
+    room = L - k - step
+    assert room >= 0 and ids.shape == (n,)
+    # (equal queries walk alike, and a sort is the workgroup's: on any query's count)
+    seen, first, inverse = {}, [], []
+    for q in range(nq):
+        u = seen.setdefault(scores[q].tobytes() + ok[q].tobytes(), len(first))
+        if u == len(first):
+            first.append(q)
+        inverse.append(u)
+    inverse = np.array(inverse, dtype=np.int64)
+    U = len(first)
+    top_s = [np.empty(0, np.float32) for _ in range(U)]
+    top_i = [np.empty(0, np.int64) for _ in range(U)]
+    que_s = [[] for _ in range(U)]
+    que_i = [[] for _ in range(U)]
+    ts, ti = np.full(U, -np.inf, np.float32), np.full(U, SENT, np.int64)
+    cnt, prev_fit = np.zeros(U, np.int64), np.zeros(U, bool)
+    fit_fresh, fit_stale, late = np.zeros(U, bool), np.zeros(U, bool), np.zeros(U, bool)
+    near, prev_over = np.zeros(U, bool), np.zeros(U, bool)
+    sorts, max_slot, sort_steps = 0, -1, []
+    if room == 0:
+        prev_fit[:] = True                                           # (an empty queue is a full one)
+
+    def sort_all():
+        for u in range(U):
+            s = np.concatenate([top_s[u]] + que_s[u])
+            i = np.concatenate([top_i[u]] + que_i[u])
+            order = np.lexsort((i, -s.astype(np.float64)))[:k]
+            top_s[u], top_i[u] = s[order], i[order]
+            que_s[u], que_i[u] = [], []
+            if len(order) == k:
+                ts[u], ti[u] = top_s[u][-1], top_i[u][-1]
+        cnt[:] = 0
+
+    n_steps = (n + step - 1) // step
+    for t in range(n_steps):
+        sl = slice(t * step, min(n, (t + 1) * step))
+        for u in range(U):
+            s, i = scores[first[u], sl], ids[sl]
+            m = ok[first[u], sl] & _better(s, i, ts[u], ti[u])
+            pushed = int(m.sum())
+            if pushed:
+                que_s[u].append(s[m])
+                que_i[u].append(i[m])
+                cnt[u] += pushed
+                max_slot = max(max_slot, k + int(cnt[u]) - 1)
+                late[u] |= sorts > 0
+            if prev_fit[u] and pushed == step:
+                (fit_stale if sorts > 0 else fit_fresh)[u] = True
+            if prev_over[u] and pushed == step:
+                near[u] = True
+        assert max_slot < L, "the model's own invariant: k + room + step == L"
+        prev_over = cnt == room + 1                                  # (more than fits: sorted below)
+        if (cnt > room).any():
+            sort_all()
+            sorts += 1
+            sort_steps.append(t)
+        prev_fit = cnt == room
+    if cnt.any():
+        sort_all()
+    out_i = np.full((U, k), SENT, np.int64)
+    out_s = np.full((U, k), -np.inf, np.float32)
+    for u in range(U):
+        out_i[u, :len(top_i[u])], out_s[u, :len(top_s[u])] = top_i[u], top_s[u]
+    return dict(steps=n_steps, sorts=sorts, sort_steps=sort_steps, max_slot=max_slot, L=L, room=room,
+                fit_fresh=fit_fresh[inverse], fit_stale=fit_stale[inverse], near_miss=near[inverse], pushed_late=late[inverse],
+                ids=out_i[inverse], scores=out_s[inverse])
+
+
+def merge(list_s, list_i, k):
+    """topk_merge_kernel over the candidates [nq, n_cand] of each query (one workgroup per query): rounds of 256 pushes behind a top-k in
+    a list of 512, outer rounds of 4096 candidates.  Returns the walks (one per query) and the result (ids -1 where empty)."""
+    nq, n_cand = list_s.shape
+    cache, walks = {}, []
+    for q in range(nq):
+        key = list_s[q].tobytes() + list_i[q].tobytes()
+        if key not in cache:
+            cache[key] = walk(list_s[q][None], list_i[q], list_i[q] != SENT, k, MERGE_L, MERGE_STEP)
+        walks.append(cache[key])
+    ids = np.concatenate([w["ids"] for w in walks])
+    sc = np.concatenate([w["scores"] for w in walks])
+    return dict(walks=walks, rounds=(n_cand + MERGE_OUTER - 1) // MERGE_OUTER, n_cand=n_cand,
+                ids=np.where(ids == SENT, -1, ids).astype(np.int32), scores=sc)
+
+
+def sliced_search(S, ok, k, tile, slices, slice_rows, L, step):
+    """index_topk_kernel (tile 32, step 128) or sparse_index_scan_kernel (tile qb, step 256) over S [nq, n], one walk per (slice, tile
+    of queries), then the merge of the slices' lists.  Returns wgs (the walks), merge (as merge()), ids / scores [nq, k]."""
+    S = np.ascontiguousarray(S, dtype=np.float32)
+    nq, n = S.shape
+    ok = np.broadcast_to(np.asarray(ok, dtype=bool), (nq, n))
+    assert (slices - 1) * slice_rows < max(n, 1) <= slices * slice_rows and slice_rows % step == 0
+    list_s = np.full((nq, slices, k), -np.inf, np.float32)
+    list_i = np.full((nq, slices, k), SENT, np.int64)
+    wgs, cache = [], {}
+    for sl in range(slices):
+        r0, r1 = sl * slice_rows, min(n, (sl + 1) * slice_rows)
+        for q0 in range(0, nq, tile):
+            key = (sl, S[q0:q0 + tile, r0:r1].tobytes(), ok[q0:q0 + tile, r0:r1].tobytes())
+            if key not in cache:                                     # (tiles of the same queries walk alike)
+                cache[key] = walk(S[q0:q0 + tile, r0:r1], np.arange(r0, r1), ok[q0:q0 + tile, r0:r1], k, L, step)
+            w = dict(cache[key])
+            w["q0"], w["slice"] = q0, sl
+            wgs.append(w)
+            list_s[q0:q0 + tile, sl], list_i[q0:q0 + tile, sl] = w["scores"], w["ids"]
+    m = merge(list_s.reshape(nq, -1), list_i.reshape(nq, -1), k)
+    return dict(wgs=wgs, merge=m, ids=m["ids"], scores=m["scores"], slices=slices)
+
+
+def probed_search(S, ok, k, lists, n_lists):
+    """index_probe_kernel with every list probed, in list order (the centroid scores of the fixtures tie, so the probe order is the
+    ids'): per query one walk per list — its members in ascending id — and per 1024-row chunk of the tail (lists == -1, the rows behind
+    the partition), then the merge of the items' lists.  Returns as sliced_search, wgs[item] holding the walks of the unique queries."""
+    S = np.ascontiguousarray(S, dtype=np.float32)
+    nq, n = S.shape
+    ok = np.broadcast_to(np.asarray(ok, dtype=bool), (nq, n))
+    lists = np.asarray(lists)
+    n_part = int((lists >= 0).sum())
+    assert (lists[:n_part] >= 0).all() and (lists[n_part:] == -1).all()
+    items = [np.nonzero(lists == l)[0] for l in range(n_lists)]
+    items += [np.arange(t0, min(n, t0 + PROBE_CHUNK)) for t0 in range(n_part, n, PROBE_CHUNK)]
+    L = dense_L(k)
+    list_s = np.full((nq, len(items), k), -np.inf, np.float32)
+    list_i = np.full((nq, len(items), k), SENT, np.int64)
+    wgs = []
+    for it, members in enumerate(items):
+        if len(members) == 0:
+            wgs.append(None)                                         # (an empty list: k empty entries, no walk)
+            continue
+        cache, parts = {}, []
+        for q in range(nq):                                          # one workgroup per (query, item): no sort is shared
+            key = S[q, members].tobytes() + ok[q, members].tobytes()
+            if key not in cache:
+                cache[key] = walk(S[q:q + 1, members], members, ok[q:q + 1, members], k, L, DENSE_STEP)
+            parts.append(cache[key])
+        w = dict(parts[0])
+        for f in ("fit_fresh", "fit_stale", "near_miss", "pushed_late", "ids", "scores"):
+            w[f] = np.concatenate([p[f] for p in parts])
+        for f in ("sorts", "max_slot"):
+            w[f] = max(p[f] for p in parts)
+        wgs.append(w)
+        list_s[:, it], list_i[:, it] = w["scores"], w["ids"]
+    m = merge(list_s.reshape(nq, -1), list_i.reshape(nq, -1), k)
+    return dict(wgs=wgs, merge=m, ids=m["ids"], scores=m["scores"], items=items)
+
+
+def reference_topk(S, ok, k):
+    """the order rule over the permitted rows (index_reference.ref_topk): what every search of S must return"""
+    S = np.array(S, dtype=np.float32)
+    S[~np.broadcast_to(np.asarray(ok, dtype=bool), S.shape)] = np.nan
+    return ixr.ref_topk(S, k)
+
+
+# ------------------------------------------------------------------------------------------------
+# the tiles of a fixture: which query stands where
+# ------------------------------------------------------------------------------------------------
+def layouts(kinds, busy, idle, nq, tile):
+    """name -> [nq] kinds.  "first:b" / "last:b": the first / last query of every tile is the busy kind b (for each of busy) and its
+    neighbours push nothing after their first k rows; "mixed": every kind in turn."""
+    out = {}
+    for b in busy:
+        for name in ("first", "last"):
+            lay = [idle[i % len(idle)] for i in range(nq)]
+            for q0 in range(0, nq, tile):
+                lay[q0 if name == "first" else min(nq, q0 + tile) - 1] = b
+            if lay not in out.values():
+                out[f"{name}:{b}"] = lay
+    lay = [kinds[i % len(kinds)] for i in range(nq)]
+    if lay not in out.values():
+        out["mixed"] = lay
+    return out
+
+
+class Fixture:
+    """One index and its queries by kind.  scores[kind] [n] f32 are the reference's (the stored form's rule), intended[kind] [n] the
+    signed values the pattern means, ok [n] the rows a search may return (None: all), ok1 a second allow-list (the near miss of ok's
+    exact fit; None where ok is), busy / idle the kinds of layouts()."""
+
+    def __init__(self, name, **kw):
+        self.name = name
+        self.__dict__.update(kw)
+
+    def S(self, layout):
+        return np.stack([self.scores[kind] for kind in layout])
+
+    def permitted(self):
+        return np.ones(self.n, dtype=bool) if self.ok is None else self.ok
+
+
+def check_order(scores, intended, what=""):
+    """the reference's scores are a strictly increasing function of the intended values: equal where those are equal, ordered as they
+    are"""
+    order = np.lexsort((np.arange(len(intended)), intended))
+    s, v = scores[order].astype(np.float64), np.asarray(intended, dtype=np.float64)[order]
+    assert not np.isnan(s).any(), what
+    assert ((np.diff(s) > 0) == (np.diff(v) > 0)).all() and (np.diff(s) >= 0).all(), what
+
+
+# ------------------------------------------------------------------------------------------------
+# dense fixtures: index_topk_kernel
+# ------------------------------------------------------------------------------------------------
+DENSE_DTYPES = ixr.DTYPES
+DENSE_KS = (1, 127, 128, 129, 256)
+DENSE_NQS = (1, 31, 32, 33)
+DENSE_ROWS = {"f32": 2500, "f16": 2500, "i8": 2500, "b1": 2040}       # 19 whole steps and 68 rows; b1: 15 and 120 (its ranks end at dim)
+MODES = ("plain", "removed", "allow")
+B1_DIM = 2048
+FLOAT_DIM = 8
+
+
+def dense_rows(dtype, patterns):
+    """rows [n, dim] f32 that carry the rank patterns: a column each (f32, f16), the one pattern in column 0 (i8: one nonzero column
+    per row, so its scale cannot reorder the pattern), or the first rank bits set (b1)"""
+    n = len(patterns[0])
+    if dtype == "b1":
+        assert len(patterns) == 1 and patterns[0].max() <= B1_DIM
+        return np.where(np.arange(B1_DIM)[None, :] < patterns[0][:, None], np.float32(1), np.float32(-1))
+    assert len(patterns) <= FLOAT_DIM and (dtype != "i8" or len(patterns) == 1)
+    rows = np.zeros((n, FLOAT_DIM), np.float32)
+    for c, ranks in enumerate(patterns):
+        rows[:, c] = values(ranks)
+    return rows
+
+
+def dense_query(dtype, col, sign):
+    """+-e_col, or the zero vector (sign 0); b1: +-(all ones) — the only query that orders its rows"""
+    q = np.zeros(B1_DIM if dtype == "b1" else FLOAT_DIM, np.float32)
+    if dtype == "b1":
+        q[:] = sign
+    else:
+        q[col] = sign
+    return q
+
+
+def dense_scores(dtype, queries, rows):
+    """[Q, n] f32 by the reference of the stored form: bit for bit where index_reference restates the integer arithmetic (i8, b1), the
+    float64 score of the stored values otherwise — which the callers assert to be the intended integers, exact in f32"""
+    if dtype in ("i8", "b1"):
+        return ixr.exact_scores(queries, rows, dtype)
+    exact = ixr.FloatScores(queries, rows, dtype).exact
+    assert (exact == exact.astype(np.float32)).all()
+    return exact.astype(np.float32) + np.float32(0)                  # (a zero score is +0: the chain starts at +0)
+
+
+def _dense_fixture(name, dtype, patterns, names, ok, busy):
+    """patterns: rank arrays; names: per pattern (kind of +, kind of -)"""
+    rows = dense_rows(dtype, patterns)
+    n = len(rows)
+    kinds, intended = {"const": dense_query(dtype, 0, 0)}, {"const": np.zeros(n)}
+    for c, (ranks, (pos, neg)) in enumerate(zip(patterns, names)):
+        v = values(ranks).astype(np.float64)
+        if dtype == "b1":
+            v = 2.0 * ranks - B1_DIM                                 # (set bits minus clear bits)
+        kinds[pos], intended[pos] = dense_query(dtype, c, 1), v
+        kinds[neg], intended[neg] = dense_query(dtype, c, -1), -v
+    order = list(kinds)
+    sc = dense_scores(dtype, np.stack([kinds[kk] for kk in order]), rows)
+    scores = {kk: sc[i] for i, kk in enumerate(order)}
+    for kk in order:
+        if dtype in ("f32", "f16"):
+            assert np.array_equal(scores[kk].astype(np.float64), intended[kk]), (name, kk)       # exactly the intended integers
+        else:
+            check_order(scores[kk], intended[kk], (name, kk))
+    if dtype == "f32":
+        chain = ixr.f32_chain_scores(np.stack([kinds[kk] for kk in order]), rows)                 # the documented fma chain agrees
+        assert np.array_equal(chain.view(np.uint32), sc.view(np.uint32)), name
+    idle = [kk for kk in ("const", "desc") if kk in kinds]
+    return Fixture(name, dtype=dtype, rows=rows, n=n, queries=kinds, scores=scores, intended=intended, ok=ok, kinds=order,
+                   busy=busy, idle=idle)
+
+
+def dense_fixtures(dtype, k, mode):
+    """The indexes of one (dtype, k, mode) cell.  plain: ascending, sawtooth, the unmasked exact-fit staircase of this k and its near
+    miss.  removed /
+    allow: ascending and sawtooth under fit_mask(k), the masked exact fit (the ascending rows that must not push are removed or
+    disallowed).  f32 and f16 hold the patterns side by side in one index; i8 and b1 hold one pattern per index."""
+    n, L, step = DENSE_ROWS[dtype], dense_L(k), DENSE_STEP
+    pats = [(ascending(n), ("asc", "desc"), "asc"), (sawtooth(n, step), ("saw", "was"), "saw")]
+    ok = ok1 = None
+    if mode == "plain":
+        pats.append((staircase(n, k, L, step), ("stair", "riats"), "stair"))
+        pats.append((staircase(n, k, L, step, 1), ("over", "revo"), "over"))
+    else:
+        ok, ok1 = fit_mask(n, k, L, step), fit_mask(n, k, L, step, 1)
+    if dtype in ("f32", "f16"):
+        out = [_dense_fixture(f"{dtype} k={k} {mode}", dtype, [p[0] for p in pats], [p[1] for p in pats], ok, ["stair", "over", "asc"] if mode == "plain" else ["asc"])]
+    else:
+        out = [_dense_fixture(f"{dtype} k={k} {mode} {p[2]}", dtype, [p[0]], [p[1]], ok, [p[2]]) for p in pats]
+    for fx in out:
+        fx.ok1 = ok1
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# many slices (f32): the merge's outer rounds and its refill
+# ------------------------------------------------------------------------------------------------
+MANY_DENSE_ROWS = 17 * 4096
+MANY_SPARSE_ROWS = 17 * 2048
+MANY_NQS = (1, 33)
+MANY_KS = (256, 10)
+
+
+def many_scores(n):
+    """kind -> scores [n]: plain integers (exact in f32 up to 2^24) ascending over the whole index — every slice beats all earlier ones,
+    so the merge refills in every round —, descending, constant"""
+    v = (1 + np.arange(n)).astype(np.float32)
+    return {"asc": v, "desc": -v, "const": np.zeros(n, np.float32)}
+
+
+MANY_LAYOUT = ["asc", "desc", "const"]
+
+
+def many_layout(nq):
+    return [MANY_LAYOUT[i % 3] for i in range(nq)]
+
+
+# ------------------------------------------------------------------------------------------------
+# the merge's own exact fit: a rescore hands topk_merge_kernel its candidates in the caller's order
+# ------------------------------------------------------------------------------------------------
+MERGE_CAND = 1024                        # the most candidates of a rescore: four rounds of the merge
+MERGE_KS = DENSE_KS
+MERGE_KINDS = ["stair", "riats", "over", "revo", "const"]
+
+
+def merge_scores(k):
+    """kind -> scores [1024] of rows 0 .. 1023, which a rescore names in this order: the staircase of the merge's geometry (a round of
+    all candidates, then room = 512 - k - 256 of them and a whole round) and its near miss"""
+    st = values(staircase(MERGE_CAND, k, MERGE_L, MERGE_STEP))
+    ov = values(staircase(MERGE_CAND, k, MERGE_L, MERGE_STEP, 1))
+    return {"stair": st, "riats": -st + np.float32(0), "over": ov, "revo": -ov + np.float32(0), "const": np.zeros(MERGE_CAND, np.float32)}
+
+
+MERGE_COLUMN = {"stair": (0, 1.0), "riats": (0, -1.0), "over": (1, 1.0), "revo": (1, -1.0), "const": (-1, 0.0)}
+
+
+# ------------------------------------------------------------------------------------------------
+# probed fixtures: index_probe_kernel
+# ------------------------------------------------------------------------------------------------
+PROBE_LISTS = 4
+PROBE_LONG = 1600                        # members of list 0: 12 whole steps and 64 rows
+PROBE_SHORT = 150                        # members of lists 1 and 2; list 3 is empty
+PROBE_TAIL = 1100                        # rows added after the partition: two chunks
+PROBE_KS = DENSE_KS
+PROBE_BIG = 64.0                         # the list's axis of a row; i8: every pattern value is larger, so a row's scale is its value / 127
+
+
+PROBE_FORMS = ("stair", "over", "allow")
+
+
+def probe_fixture(dtype, k, form):
+    """Centroids on separate axes (e_0 .. e_3); row = big * e_list + value * e_last (b1: the list's bit, and the first rank bits behind
+    the list columns), so list membership is by construction and the query e_last (b1: ones behind the list columns) scores the pattern
+    alone — 0 against every centroid, so with nprobe = n_lists no probe ranking is in question.  The long list holds the unmasked
+    staircase of k ("stair"), its near miss ("over") or ascending rows under fit_mask ("allow") in ascending member order, interleaved in storage with two short lists of
+    sawtooth rows; the tail is ascending.  Returns the Fixture with lists [n] (-1: the tail), centroids, n_part."""
+    L, step, masked = dense_L(k), DENSE_STEP, form == "allow"
+    n_part = PROBE_LONG + 2 * PROBE_SHORT
+    n = n_part + PROBE_TAIL
+    # storage order of the partitioned rows: a short-list row after every 5th or 6th long-list row
+    lists = np.zeros(n_part, np.int64)
+    at = np.linspace(3, n_part - 2, 2 * PROBE_SHORT).astype(np.int64)
+    assert len(np.unique(at)) == len(at)
+    lists[at] = 1 + np.arange(len(at)) % 2
+    lists = np.concatenate([lists, np.full(PROBE_TAIL, -1)])
+    long_rows = np.nonzero(lists == 0)[0]
+    assert len(long_rows) == PROBE_LONG
+    base = 80 if dtype == "i8" else 0                                # i8: values above PROBE_BIG
+    ranks = np.zeros(n, np.int64)
+    ok = ok1 = None
+    if masked:
+        ranks[long_rows] = base + ascending(PROBE_LONG)
+        ok = np.ones(n, dtype=bool)
+        ok1 = ok.copy()
+        ok[long_rows], ok1[long_rows] = fit_mask(PROBE_LONG, k, L, step), fit_mask(PROBE_LONG, k, L, step, 1)
+        for m in (ok, ok1):
+            m[[n - 1, n_part + 5, n_part + 40]] = False              # tail rows too: one word, and a block that straddles two
+    else:
+        st = staircase(PROBE_LONG, k, L, step, int(form == "over"))
+        ranks[long_rows] = np.where(st > 0, base + st, 0)
+    for l in (1, 2):
+        ranks[lists == l] = base + sawtooth(PROBE_SHORT, 16)
+    # the tail goes on ascending above the long list (b1: its ranks end at the dim, so the tail starts over and ties with the list)
+    ranks[n_part:] = (0 if dtype == "b1" else base + PROBE_LONG) + ascending(PROBE_TAIL)
+    if dtype == "b1":
+        dim, P0 = B1_DIM, PROBE_LISTS
+        assert ranks.max() <= dim - P0
+        col = np.arange(dim)[None, :]
+        bits = (col >= P0) & (col < P0 + ranks[:, None])
+        bits |= (col == np.where(lists >= 0, lists, 0)[:, None]) & (lists >= 0)[:, None]
+        rows = np.where(bits, np.float32(1), np.float32(-1))
+        q = np.zeros(dim, np.float32)
+        q[P0:] = 1
+        v = 2.0 * ranks - (dim - P0)
+    else:
+        dim = FLOAT_DIM
+        rows = np.zeros((n, dim), np.float32)
+        rows[:, dim - 1] = values(ranks)
+        part = np.nonzero(lists >= 0)[0]
+        rows[part, lists[part]] = PROBE_BIG
+        q = np.zeros(dim, np.float32)
+        q[dim - 1] = 1
+        v = values(ranks).astype(np.float64)
+    centroids = np.zeros((PROBE_LISTS, dim), np.float32)
+    centroids[np.arange(PROBE_LISTS), np.arange(PROBE_LISTS)] = 1
+    kinds = {"pattern": q, "inverse": -q, "const": np.zeros(dim, np.float32)}
+    intended = {"pattern": v, "inverse": -v, "const": np.zeros(n)}
+    order = list(kinds)
+    sc = dense_scores(dtype, np.stack([kinds[kk] for kk in order]), rows)
+    scores = {kk: sc[i] for i, kk in enumerate(order)}
+    name = f"probe {dtype} k={k} {form}"
+    for kk in order:
+        if dtype in ("f32", "f16"):
+            assert np.array_equal(scores[kk].astype(np.float64), intended[kk]), (name, kk)
+        elif dtype == "b1":
+            check_order(scores[kk], intended[kk], (name, kk))
+        else:
+            # i8: a tail row (one nonzero column) and a list row (two) of one value may differ in the last bit of their scales'
+            # product; the order is asked of the rows of each item, whose rows are built alike
+            for sel in (lists == 0, lists == 1, lists == 2, lists == -1):
+                check_order(scores[kk][sel], intended[kk][sel], (name, kk))
+    return Fixture(name, dtype=dtype, rows=rows, n=n, queries=kinds, scores=scores, intended=intended, ok=ok, kinds=order,
+                   ok1=ok1, busy=["pattern"], idle=["const"], lists=lists, centroids=centroids, n_part=n_part, long_rows=long_rows)
+
+
+def probe_layout(nq=3):
+    return ["pattern", "inverse", "const"][:nq]
+
+
+# ------------------------------------------------------------------------------------------------
+# sparse fixtures: sparse_index_scan_kernel
+# ------------------------------------------------------------------------------------------------
+SPARSE_DTYPES = ["f32", "f16"]
+SPARSE_KS = (1, 127, 128, 129, 255, 256)
+SPARSE_ROWS = 4000                       # 15 whole steps and 160 rows
+SPARSE_V = 1000
+SPARSE_TERMS = {"asc": (0, 1.0), "desc": (0, -1.0), "saw": (1, 1.0), "was": (1, -1.0), "stair": (2, 1.0), "riats": (2, -1.0), "over": (3, 1.0), "revo": (3, -1.0),
+                "const": (-1, 0.0)}
+
+
+def sparse_query(kinds):
+    """(ids [nq, 1], weights [nq, 1]): a query holds the one term id of its pattern with weight +-1, or no term"""
+    ids = np.array([[SPARSE_TERMS[kk][0]] for kk in kinds], np.int32)
+    w = np.array([[SPARSE_TERMS[kk][1]] for kk in kinds], np.float32)
+    return ids, w
+
+
+def sparse_fixture(dtype, k, mode, n=SPARSE_ROWS):
+    """One index: row r holds term p with the value of pattern p's rank — 0 ascending, 1 sawtooth, 2 (plain) the unmasked staircase of
+    k, 3 its near miss —, and a query holds one of the ids with weight +-1: the score is fmaf(w, +-1, +0), the stored weight or its negation.  removed /
+    allow: fit_mask(k)."""
+    L, step = sparse_L(k), SPARSE_STEP
+    pats = [ascending(n), sawtooth(n, step)]
+    ok = ok1 = None
+    if mode == "plain":
+        pats += [staircase(n, k, L, step), staircase(n, k, L, step, 1)]
+    else:
+        ok, ok1 = fit_mask(n, k, L, step), fit_mask(n, k, L, step, 1)
+    ids = np.tile(np.arange(len(pats), dtype=np.int32), (n, 1))
+    w = np.stack([values(p) for p in pats], axis=1).astype(np.float32)
+    st = sref.stored_rows(ids, w, len(pats), dtype)
+    assert np.array_equal(st[1], w)                                  # (f16 holds every value)
+    order = [kk for kk, (t, _) in SPARSE_TERMS.items() if t < len(pats)]
+    sc = sref.scores(st[0], st[1], *sparse_query(order), SPARSE_V)
+    scores = {kk: sc[i] for i, kk in enumerate(order)}
+    name = f"sparse {dtype} k={k} {mode}"
+    for kk in order:
+        t, sign = SPARSE_TERMS[kk]
+        want = np.zeros(n) if t < 0 else sign * w[:, t].astype(np.float64)
+        assert np.array_equal(scores[kk].astype(np.float64), want), (name, kk)
+    return Fixture(name, dtype=dtype, n=n, term_ids=ids, term_w=w, scores=scores, ok=ok, ok1=ok1, kinds=order, width=len(pats),
+                   busy=["stair", "over", "asc"] if mode == "plain" else ["asc"], idle=["const", "desc"])
+
+
+def many_sparse_rows(n=MANY_SPARSE_ROWS):
+    """rows of width 1: term 0 with weight 1 + r (f32)"""
+    return np.zeros((n, 1), np.int32), (1 + np.arange(n)).astype(np.float32)[:, None]
+
+
+# ------------------------------------------------------------------------------------------------
+# what a fixture must reach (asserted on the CPU by test_topk_order_host.py)
+# ------------------------------------------------------------------------------------------------
+def describe(tag, res):
+    """one line per fixture for the log: sorts and the largest slot over the scoring workgroups, slices, merge rounds"""
+    wgs = [w for w in res["wgs"] if w is not None]
+    mw = res["merge"]["walks"]
+    return (f"{tag}: workgroups {len(wgs)}, steps {max(w['steps'] for w in wgs)}, sorts {max(w['sorts'] for w in wgs)}, "
+            f"largest slot {max(w['max_slot'] for w in wgs)} of L {wgs[0]['L']} (room {wgs[0]['room']}), "
+            f"exact fit fresh {int(any(w['fit_fresh'].any() for w in wgs))} stale {int(any(w['fit_stale'].any() for w in wgs))} "
+            f"near miss {int(any(w['near_miss'].any() for w in wgs))}; "
+            f"merge: candidates {res['merge']['n_cand']}, outer rounds {res['merge']['rounds']}, sorts {max(w['sorts'] for w in mw)}, "
+            f"largest slot {max(w['max_slot'] for w in mw)} of {MERGE_L}")
