@@ -12,6 +12,7 @@
 #include "../../include/bert_hip.h"
 #include "abi.h"
 #include "index_file.h"
+#include "text_routes.h"
 
 using namespace bert_hip;
 
@@ -30,35 +31,7 @@ int32_t index_call(const char *me, bert_hip_index *ix, F &&body) {
     }, (int32_t)-4);
 }
 
-// Tokenizes and evaluates texts in groups on the context's first device; each group's embeddings [c][n_embd] land in the
-// index's device scratch buffer and are handed to use(i0, c, d_rows).  No host copy of the embeddings.
-template <class F>
-bool encode_groups_device(bert_ctx *ctx, Index &ix, int32_t n_threads, int32_t n, const char **texts, F &&use, std::string &err) {
-    const int32_t H = ctx->hp.n_embd, G = 16384;
-    TokenGroup &g = ctx->texts.group[0];
-    for (int32_t i0 = 0; i0 < n; i0 += G) {
-        const int32_t c = std::min(G, n - i0);
-        g.tokenize(ctx->texts, n_threads, c, texts + i0);
-        if (g.n_ok < c) { err = "input " + std::to_string(i0 + g.n_ok) + " cannot be evaluated"; return false; }
-        float *d = ix.scratch((size_t)c * H, err);
-        if (!d) return false;
-        // (blocking: the rows are in d when it returns)
-        if (ctx->engine()->eval_packed_host(g.packed.get(), g.cu.data(), c, nullptr, err, d) != 0) return false;
-        if (!use(i0, c, d)) return false;
-    }
-    return true;
-}
-
-// the multi-device route of the text entry points: bert_hip_encode_batch into host rows
-bool encode_host(bert_ctx *ctx, int32_t n_threads, int32_t n, const char **texts, std::vector<float> &emb, std::string &err) {
-    const size_t H = ctx->hp.n_embd;
-    emb.assign((size_t)n * H, 0.f);
-    std::vector<float *> rows((size_t)n);
-    for (int32_t i = 0; i < n; ++i) rows[i] = emb.data() + i * H;
-    const int32_t done = encode_batch_impl(ctx, n_threads, n, texts, rows.data());
-    if (done != n) { err = "input " + std::to_string(std::max(done, 0)) + " could not be encoded"; return false; }
-    return true;
-}
+// (the text routes' way from texts to the index's scratch buffer, encode_groups_device and encode_host: text_routes.h)
 
 // (-2 after a line on stderr: the index does not hold this model's embeddings)
 bool dim_ok(const char *me, const bert_ctx *ctx, const Index &x) {

@@ -24,7 +24,8 @@ struct EngineOptions {
     // from 220 us: 252 us at 172 tokens (8 sentences), 330 at 363 (16), 376 at 512, 527 at 716, 606 at 1024 (round 5, same bits).
     int latency_tokens = 768;
     int sparse_index_qb = 0;          // tuning (a key only): queries per tile of the sparse index's scan, 1 .. 8; 0 = the table of sparse_index_kernels.h
-    bool stage_kernel = true;         // small staged blocks come in by a kernel that reads the mapped pinned block, not by the copy engine
+    int hybrid_chunk_queries = 0;     // tuning (a key only): queries per chunk of a hybrid search, 1 .. 4096; 0 = what the score workspace's bound gives (sparse_index_kernels.h)
+    bool stage_kernel = true;        // small staged blocks come in by a kernel that reads the mapped pinned block, not by the copy engine
     // How a pass ends (bert_hip.h): the mean over a sentence's tokens or the state of its first token ([CLS]), divided by its L2
     // norm or not.  A pass reads both once, at its start (pool_mode()).
     bool pool_cls = false, normalize = true;

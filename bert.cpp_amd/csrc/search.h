@@ -131,6 +131,7 @@ public:
     void truncate(int n);
 
 private:
+    friend struct Hybrid;                               // hybrid.h: a search over this index and a sparse index together
     Index() = default;
     bool grow_rows(int n_rows, std::string &err);
     bool grow(DevBuf &b, size_t bytes, std::string &err);

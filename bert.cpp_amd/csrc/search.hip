@@ -22,6 +22,10 @@
 //                         same ScoreBlock (the same MFMA chain per (query, row), so the same bits as a search), scores and ids
 //                         [nq][n_cand] into the workspace — id INT_MAX, score -inf for an entry that names no live row —, from
 //                         which topk_merge_kernel selects.
+//   index_scores_kernel<T> the dense pass of a hybrid search (hybrid.cpp): index_topk_kernel's workgroups, tiles and ScoreBlock chain
+//                         without the selection — every (query, row) score of the chunk goes to a row-contiguous matrix in HBM,
+//                         which the sparse index's hybrid scan reads.  Masked: only the rows whose bit is set.
+//   mask_and_kernel       the word-wise AND of up to three bitmaps (the two indexes' live words, an allow-list).
 //   index_probe_kernel<T>  the probed search of a partitioned index: one workgroup per (query, item), an item being one of the
 //                         query's probed lists (its members' ids come from the partition's order table) or a chunk of the
 //                         unassigned tail.  Each wave scores 32 members per step as the rescore kernel does, and the workgroup
@@ -387,6 +391,64 @@ __global__ __launch_bounds__(NT) void index_rescore_kernel(RescoreArgs a) {
     }
 }
 
+// index_topk_kernel without the selection: one workgroup of four waves per (tile of QT queries, slice of rows), the same XCD map;
+// each wave scores 32 rows a step through ScoreBlock<T>::run and finish — the search's bits — and stores acc[r] to
+// out[(q0 + q) * ld + row] for the queries q < nqv: per accumulator element the 32 lanes of a half-wave write 32 consecutive floats.
+// No LDS, no barrier: a wave whose block lies beyond the slice, or (MASKED) holds no row whose bit of mask is set, does nothing;
+// a row whose bit is clear is a zero operand and is not written.  No word at or beyond ceil(n_rows / 32) is read.
+template <class T, bool MASKED>
+__global__ __launch_bounds__(NT) void index_scores_kernel(ScoresArgs a) {
+    using F = ScoreBlock<T>;
+    using QE = typename F::query_t;
+    const int item = (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8);
+    if (item >= a.n_items) return;
+    const int slice = item / a.n_qtiles, qt = item - slice * a.n_qtiles;
+    const int q0 = qt * QT, nqv = min(QT, a.nq - q0);
+    const int r0 = slice * a.slice_rows, r1 = min(a.n_rows, r0 + a.slice_rows);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
+    float qs[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int q = (r & 3) + 8 * (r >> 2) + 4 * h;
+        qs[r] = F::QSCALE && q < nqv ? a.qscale[q0 + q] : 0.f;
+    }
+    const bool qok = col < nqv;
+    const QE *qp = (const QE *)a.queries + (size_t)(q0 + (qok ? col : 0)) * a.dpad;
+    for (int base = r0; base < r1; base += STEP_ROWS) {
+        const int blk = __builtin_amdgcn_readfirstlane(base + wave * 32);
+        if (blk >= r1) continue;                               // (the whole wave)
+        const int row = blk + col;
+        bool rok = row < r1;
+        if constexpr (MASKED) {
+            // r0 and the step are multiples of 128: the wave's 32 rows are the bits of one word
+            const uint32_t word = __builtin_amdgcn_readfirstlane(a.mask[blk >> 5]);
+            if (word == 0) continue;
+            rok = rok && ((word >> col) & 1u);
+        }
+        const T *rp = F::row_ptr(a.rows, (size_t)(rok ? row : r0), a.dpad);
+        const float rs = F::RSCALE ? a.rscale[rok ? row : r0] : 0.f;
+        typename F::acc_t dot = {};
+        F::run(qp, rp, qok, rok, a.dpad, h, dot);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int q = (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (rok && q < nqv) a.out[(size_t)(q0 + q) * a.ld + row] = F::finish(dot[r], qs[r], rs);
+        }
+    }
+}
+
+// One thread per word
+__global__ __launch_bounds__(256) void mask_and_kernel(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b,
+                                                       const uint32_t *__restrict__ c, uint32_t *__restrict__ out, int n_words) {
+    const int w = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (w >= n_words) return;
+    uint32_t m = ~0u;
+    if (a) m &= a[w];
+    if (b) m &= b[w];
+    if (c) m &= c[w];
+    out[w] = m;
+}
+
 // One workgroup per (query, item); the item's members m0 .. m1 - 1 are rows order[m] (a probed list) or m itself (a tail chunk).
 // Scoring is index_rescore_kernel's — the query is query 0 of the tile, lane l < 32 ends with its member's score —, selection
 // index_topk_kernel's with one query: threshold in registers, queue behind the current top-k in LDS, sorted when a step might
@@ -679,6 +741,19 @@ void launch_topk_merge(const MergeArgs &a, int nq, hipStream_t s) {
 void launch_rescore(int dtype, const RescoreArgs &a, hipStream_t s) {
     const int grid = (a.nq * a.n_blocks + NWAVE - 1) / NWAVE;
     dispatch(dtype, [&](auto form) { BERT_LAUNCH(index_rescore_kernel<decltype(row_type(form))>, dim3(grid), dim3(NT), 0, s, a); });
+}
+
+void launch_index_scores(int dtype, const ScoresArgs &a, hipStream_t s) {
+    const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
+    dispatch(dtype, [&](auto form) {
+        using T = decltype(row_type(form));
+        if (a.mask) BERT_LAUNCH((index_scores_kernel<T, true>), dim3(grid), dim3(NT), 0, s, a);
+        else BERT_LAUNCH((index_scores_kernel<T, false>), dim3(grid), dim3(NT), 0, s, a);
+    });
+}
+
+void launch_mask_and(const uint32_t *a, const uint32_t *b, const uint32_t *c, uint32_t *out, int n_words, hipStream_t s) {
+    BERT_LAUNCH(mask_and_kernel, dim3((n_words + 255) / 256), dim3(256), 0, s, a, b, c, out, n_words);
 }
 
 void launch_probe(int dtype, const ProbeArgs &a, hipStream_t s) {

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 
@@ -44,6 +45,28 @@ struct RescoreArgs {
     int *ws_i;
     int n_rows, dpad, nq, n_cand, n_blocks;      // n_blocks = ceil(n_cand / 32)
 };
+
+// index_scores_kernel (hybrid search): index_topk_kernel's scores without its selection, out[(q) * ld + row] for every query q of
+// the chunk and every row whose bit of mask is set (mask null: every row); the other places of out are not written.  No LDS
+struct ScoresArgs {
+    const void *rows, *queries;          // as TopkArgs
+    const float *qscale, *rscale;
+    const uint32_t *mask;                // words [ceil(n_rows / 32)], bit set = the row's scores are wanted; null = all ones
+    float *out;                          // [nq][ld]
+    size_t ld;                           // floats per query of out, >= n_rows
+    int n_rows, dpad, nq, n_qtiles, n_slices, slice_rows, n_items;
+};
+// How a chunk of nq queries over n_rows rows is cut into workgroups of index_scores_kernel: tiles of QT queries times slices of
+// slice_rows rows (a multiple of STEP_ROWS), TARGET_BLOCKS workgroups aimed for, no slice shorter than 2048 rows
+inline void index_scores_plan(int n_rows, int nq, ScoresArgs &a) {
+    a.n_rows = n_rows; a.nq = nq;
+    a.n_qtiles = (nq + QT - 1) / QT;
+    const int s = std::max(1, std::min((TARGET_BLOCKS + a.n_qtiles - 1) / a.n_qtiles, n_rows / 2048));
+    const int per = (int)(((long long)n_rows + s - 1) / s);
+    a.slice_rows = std::max(STEP_ROWS, (per + STEP_ROWS - 1) / STEP_ROWS * STEP_ROWS);
+    a.n_slices = std::max(1, (int)(((long long)n_rows + a.slice_rows - 1) / a.slice_rows));
+    a.n_items = a.n_qtiles * a.n_slices;
+}
 
 // index_probe_kernel: one workgroup per (query, item).  Items 0 .. nprobe - 1 are the lists probe[q][item] names (-1: none), whose
 // members are order[offsets[l] .. offsets[l + 1]); item nprobe + c is tail chunk c, rows n_part + c * PROBE_CHUNK ... (< n_rows).
@@ -89,6 +112,10 @@ void search_kernels_init();
 void launch_topk(int dtype, const TopkArgs &a, size_t lds, hipStream_t s);
 void launch_topk_merge(const MergeArgs &a, int nq, hipStream_t s);
 void launch_rescore(int dtype, const RescoreArgs &a, hipStream_t s);
+// the masked instantiation iff a.mask is set
+void launch_index_scores(int dtype, const ScoresArgs &a, hipStream_t s);
+// out[w] = a[w] & b[w] & c[w] for w < n_words, a null pointer counting as all ones
+void launch_mask_and(const uint32_t *a, const uint32_t *b, const uint32_t *c, uint32_t *out, int n_words, hipStream_t s);
 // the masked instantiation iff a.allow is set (removed rows alone stay on the unmasked one, which reads a.live per lane)
 void launch_probe(int dtype, const ProbeArgs &a, hipStream_t s);
 void launch_export(int dtype, const ExportArgs &a, hipStream_t s);

@@ -87,6 +87,10 @@ int check_rescore(int nq, int kq, const void *qi, const void *qw, int n_cand, co
 
 }  // namespace
 
+bool sparse_queries_ok(int nq, int kq, const int32_t *qids, const float *qw, int n_vocab, std::string &err) {
+    return check_terms("search: query", nq, kq, qids, qw, n_vocab, false, err);
+}
+
 SparseIndex *SparseIndex::create(Engine *eng, int n_vocab, int width, int dtype, std::string &err) {
     if (!eng) { err = "no device engine"; return nullptr; }
     if (n_vocab < 1 || n_vocab > MAX_VOCAB) { err = "n_vocab must be 1 .. 262144"; return nullptr; }

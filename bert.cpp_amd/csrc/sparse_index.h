@@ -82,6 +82,7 @@ public:
     void truncate(int n);
 
 private:
+    friend struct Hybrid;                               // hybrid.h: a search over this index and an embedding index together
     SparseIndex() = default;
     bool grow(DevBuf &b, size_t bytes, std::string &err);
     bool grow_rows(int n_rows, std::string &err);
@@ -107,9 +108,14 @@ private:
     DevBuf stage_, out_ids_, out_scores_;               // host routes: rows / queries / row ids in, results out
     DevBuf text_in_, text_out_;                         // text routes
     DevBuf allow_, cand_in_;                            // host routes: a caller's allow-list and candidate lists
+    DevBuf hyb_scores_, hyb_mask_;                      // hybrid search: the current chunk's dense scores [HC][ld]; live & live & allow
     hipStream_t stream_ = nullptr;                      // the host routes' stream
     // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
     hipEvent_t busy_ = nullptr;
 };
+
+// host queries [nq][kq] as search_host checks them: every id in [-1, n_vocab), none twice in a query, every used weight finite;
+// false + err names the first offender
+bool sparse_queries_ok(int nq, int kq, const int32_t *qids, const float *qw, int n_vocab, std::string &err);
 
 }  // namespace bert_hip

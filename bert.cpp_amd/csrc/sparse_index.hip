@@ -17,6 +17,8 @@
 //                         thresholds in registers, a queue behind the top-k in LDS, bitonic_sort_lists when a queue might not take
 //                         another step, one sorted list per (query, slice) into the workspace — which topk_merge_kernel merges.
 //                         The MASKED instantiation (removed rows, an allow-list) reads two mask words per block: see the kernel.
+//   sparse_hybrid_scan_kernel<DTYPE, MASKED>  the same body as the second pass of a hybrid search (hybrid.cpp): the score a row is
+//                         selected by is (w_dense * D) + (w_sparse * S), D read from the matrix index_scores_kernel (search.hip) wrote.
 //   sparse_index_rescore_kernel<DTYPE>  per-query candidate rows against that query's image, one row per lane, the scan's chain.
 //   sparse_index_gather_kernel<DTYPE>   compaction: the live rows' columns and counts into a fresh allocation.
 //   sparse_index_export_kernel<DTYPE>  stored rows, named by id, back as (i32 id, f32 weight) columns: bert_hip_sparse_index_get_rows.
@@ -120,12 +122,27 @@ __global__ __launch_bounds__(256) void sparse_query_kernel(SparseQueryArgs a) {
     for (unsigned i = t; i < a.img_bytes / 16; i += 256) dst[i] = ((const u32x4 *)smem)[i];
 }
 
+// The hybrid score H = (w_dense * D) + (w_sparse * S) of bert_hip.h: two f32 multiplications and one f32 addition, each rounded to
+// nearest even, never an fma (contraction is off for this block, whatever the translation unit's default)
+__device__ __forceinline__ float hybrid_score(float w_dense, float d, float w_sparse, float s) {
+#pragma clang fp contract(off)
+    const float x = w_dense * d;
+    const float y = w_sparse * s;
+    return x + y;
+}
+
+// The scan's body, shared by sparse_index_scan_kernel and sparse_hybrid_scan_kernel.
 // MASKED (removed rows or an allow-list): a row qualifies iff its bit of live & allow is set.  A wave's block of 64 rows starts at a
 // multiple of 64 (slices start at multiples of SPARSE_STEP_ROWS), so its mask is two words, the same for all its lanes, loaded
 // through the scalar path; a lane whose bit is clear is a lane past the rows — count 0, no push —, so a block is walked to the largest
 // count of its qualifying rows and one without any issues no column load.  No word at or beyond ceil(n_rows / 32) is read.
-template <int DTYPE, bool MASKED>
-__global__ __launch_bounds__(NT) void sparse_index_scan_kernel(SparseScanArgs a) {
+//
+// HYBRID (sparse_hybrid_scan_kernel, the second pass of a hybrid search): at the top of a step, before the column walk so that the
+// loads' latency hides under it, a lane whose row qualifies loads its row's dense score of each query of the tile from a.dscores
+// (lane = row: a coalesced 256-byte access per query); a lane whose row does not qualify reads nothing — the dense pass may not
+// have written there.  After the walk the score is hybrid_score(D, S) in place of S; everything behind it is the scan's.
+template <int DTYPE, bool MASKED, bool HYBRID>
+__device__ __forceinline__ void sparse_scan_body(const SparseScanArgs &a) {
     using id_t = typename Stored<DTYPE>::id_t;
     using w_t = typename Stored<DTYPE>::w_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -181,6 +198,11 @@ __global__ __launch_bounds__(NT) void sparse_index_scan_kernel(SparseScanArgs a)
             m1 = __builtin_amdgcn_readfirstlane(m1);
             rok = rok && (((lane < 32 ? m0 : m1) >> (lane & 31)) & 1u);
         }
+        [[maybe_unused]] float dv[QB_MAX];
+        if constexpr (HYBRID) {
+#pragma unroll
+            for (int q = 0; q < QB_MAX; ++q) dv[q] = q < nqv && rok ? a.dscores[(size_t)(q0 + q) * a.ld + row] : 0.f;
+        }
         const int n = rok ? a.counts[row] : 0;
         int nmax = n;
 #pragma unroll
@@ -225,7 +247,8 @@ __global__ __launch_bounds__(NT) void sparse_index_scan_kernel(SparseScanArgs a)
 #pragma unroll
         for (int q = 0; q < QB_MAX; ++q)
             if (q < nqv) {
-                const float s = acc[q];
+                float s = acc[q];
+                if constexpr (HYBRID) s = hybrid_score(a.w_dense, dv[q], a.w_sparse, acc[q]);
                 if (rok && better(s, row, ts[q], ti[q])) {
                     const int p = atomicAdd(&cnt[q], 1);
                     ls[q * L + k + p] = s;
@@ -251,6 +274,12 @@ __global__ __launch_bounds__(NT) void sparse_index_scan_kernel(SparseScanArgs a)
         a.ws_i[o] = li[q * L + j];
     }
 }
+
+template <int DTYPE, bool MASKED>
+__global__ __launch_bounds__(NT) void sparse_index_scan_kernel(SparseScanArgs a) { sparse_scan_body<DTYPE, MASKED, false>(a); }
+
+template <int DTYPE, bool MASKED>
+__global__ __launch_bounds__(NT) void sparse_hybrid_scan_kernel(SparseScanArgs a) { sparse_scan_body<DTYPE, MASKED, true>(a); }
 
 template <int DTYPE>
 __global__ __launch_bounds__(256) void sparse_index_export_kernel(SparseExportArgs a) {
@@ -347,7 +376,9 @@ void sparse_index_kernels_init() {
     configure_once(g_scan_lds, [] {
         bool ok = true;
         for (const void *f : {(const void *)sparse_index_scan_kernel<0, false>, (const void *)sparse_index_scan_kernel<1, false>,
-                              (const void *)sparse_index_scan_kernel<0, true>, (const void *)sparse_index_scan_kernel<1, true>})
+                              (const void *)sparse_index_scan_kernel<0, true>, (const void *)sparse_index_scan_kernel<1, true>,
+                              (const void *)sparse_hybrid_scan_kernel<0, false>, (const void *)sparse_hybrid_scan_kernel<1, false>,
+                              (const void *)sparse_hybrid_scan_kernel<0, true>, (const void *)sparse_hybrid_scan_kernel<1, true>})
             ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPARSE_LDS_MAX) == hipSuccess && ok;
         if (!ok) (void)hipGetLastError();                      // (not left behind for an unrelated call's check)
     });
@@ -369,6 +400,15 @@ void launch_sparse_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStrea
     else if (dtype == 1) BERT_LAUNCH((sparse_index_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
     else if (masked) BERT_LAUNCH((sparse_index_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
     else BERT_LAUNCH((sparse_index_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
+}
+
+void launch_sparse_hybrid_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStream_t s) {
+    const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
+    const bool masked = a.live || a.allow;
+    if (dtype == 1 && masked) BERT_LAUNCH((sparse_hybrid_scan_kernel<1, true>), dim3(grid), dim3(NT), lds, s, a);
+    else if (dtype == 1) BERT_LAUNCH((sparse_hybrid_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
+    else if (masked) BERT_LAUNCH((sparse_hybrid_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
+    else BERT_LAUNCH((sparse_hybrid_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
 }
 
 // (an image is at most 50 KiB — SPARSE_MAX_VOCAB —: inside the 64 KiB a launch gets unasked)

@@ -14,6 +14,7 @@
 #include "../../include/bert_hip.h"
 #include "abi.h"
 #include "sparse_index_file.h"
+#include "text_routes.h"
 
 using namespace bert_hip;
 
@@ -32,13 +33,6 @@ int32_t sparse_index_call(const char *me, bert_hip_sparse_index *ix, F &&body) {
     }, (int32_t)-4);
 }
 
-// what the text routes ask of the model (-2 + err otherwise)
-bool text_model_ok(const bert_ctx *ctx, const SparseIndex &x, std::string &err) {
-    if (!ctx->engine()->has_mlm_head()) { err = "the model file has no MLM head (cls.predictions.*)"; return false; }
-    if (x.n_vocab() != ctx->hp.n_vocab) { err = "the index has n_vocab " + std::to_string(x.n_vocab()) + ", the model's is " + std::to_string(ctx->hp.n_vocab); return false; }
-    return true;
-}
-
 // an allow-list of n_words words covers the index (-2 + err otherwise)
 bool allow_ok(const SparseIndex &x, const uint32_t *allow, int32_t n_words, std::string &err) {
     const int64_t need = ((int64_t)x.size() + 31) / 32;
@@ -51,48 +45,7 @@ struct FileCloser {
     void operator()(FILE *f) const { if (f) fclose(f); }
 };
 
-// Tokenizes the texts in groups of 4096, cuts each group at chunk_tokens between sentences and at the sentences whose terms fit
-// 32 MiB, and per chunk: ids | cu_seqlens into the index's device buffer, the MLM head's k largest terms of every text into its other
-// one (ids [nb][k] | weights [nb][k]), then use(i0, nb, d_ids, d_weights) — all on the index's stream.  0, -2 or -3 (+ err).
-template <class F>
-int32_t sparse_text_chunks(bert_ctx *ctx, SparseIndex &x, int32_t n_threads, int32_t n, const char **texts, int32_t k, F &&use, std::string &err) {
-    constexpr int32_t GROUP = 4096;
-    Engine *eng = ctx->engine();
-    TokenGroup &g = ctx->texts.group[0];
-    const int cap = std::max(1, (int)(((size_t)32 << 20) / ((size_t)k * 8)));
-    std::vector<int32_t> h_cu;
-    for (int32_t i0 = 0; i0 < n; i0 += GROUP) {
-        const int32_t m = std::min(GROUP, n - i0);
-        g.tokenize(ctx->texts, n_threads, m, texts + i0);
-        if (g.n_ok < m) { err = "input " + std::to_string(i0 + g.n_ok) + " cannot be evaluated"; return -2; }
-        const int32_t *cu = g.cu.data();
-        for (int b0 = 0; b0 < m;) {
-            int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
-            while (b1 < m && b1 - b0 < cap && cu[b1 + 1] - cu[b0] <= eng->options().chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
-            const int nb = b1 - b0, T = cu[b1] - cu[b0];
-            const size_t off_cu = ((size_t)T * 4 + 15) & ~(size_t)15, off_w = ((size_t)nb * k * 4 + 15) & ~(size_t)15;
-            char *d_in = nullptr, *d_out = nullptr;
-            if (!x.text_buffers(off_cu + (size_t)(nb + 1) * 4, off_w + (size_t)nb * k * 4, d_in, d_out, err)) return -3;
-            h_cu.resize(nb + 1);
-            for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
-            hipStream_t s = x.stream();
-            // (pageable sources: both copies have left the host buffers when they return)
-            if (hipMemcpyAsync(d_in, g.packed.get() + cu[b0], (size_t)T * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(d_in + off_cu, h_cu.data(), (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
-                (void)hipStreamSynchronize(s);
-                err = "hipMemcpyAsync (ids) failed";
-                return -3;
-            }
-            int32_t r = eng->sparse_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, k, (int32_t *)d_out,
-                                                  (float *)(d_out + off_w), s, err) != 0 ? -3 : 0;
-            if (r == 0) r = use(i0 + b0, nb, (const int32_t *)d_out, (const float *)(d_out + off_w));
-            if (hipStreamSynchronize(s) != hipSuccess && r == 0) { err = "device error"; r = -3; }
-            if (r != 0) return r;
-            b0 = b1;
-        }
-    }
-    return 0;
-}
+// (the text routes' way from texts to the index's device buffers, text_model_ok and sparse_text_chunks: text_routes.h)
 
 }  // namespace
 

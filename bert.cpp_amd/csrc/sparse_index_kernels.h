@@ -99,7 +99,29 @@ struct SparseScanArgs {
     // words [ceil(n_rows / 32)], bit b of word w set = row 32 w + b is live / may be returned; either may be null = all ones (read by
     // the masked instantiation only, and last in the block: the unmasked one's argument offsets are what they were)
     const uint32_t *live, *allow;
+    // the hybrid scan only (sparse_hybrid_scan_kernel, last in the block as live / allow were): the dense scores of the chunk's
+    // queries, [nq][ld] with row r's at column r — read for qualifying rows alone —, and the two weights of
+    // H = (w_dense * D) + (w_sparse * S)
+    const float *dscores = nullptr;
+    size_t ld = 0;
+    float w_dense = 0.f, w_sparse = 0.f;
 };
+
+// Hybrid search (hybrid.cpp): the dense scores of one chunk of queries pass through HBM as a matrix [HC][ld], ld = n_rows rounded up
+// to 64 floats.  HYBRID_SCORES_MAX bounds that workspace; it is a bound, not a tuned number.  hybrid_chunk_queries decides HC, the one
+// place: the search and the test hook both call it.  HC is the most queries whose matrix fits the bound, at most nq and at most 4096
+// (the chunk of both indexes), at least 1 — one query's scores are taken whatever they need —, and a multiple of 32 where it is
+// 32 or more, so that the dense tiles stay full.  pref > 0 (the tuning key "hybrid_chunk_queries"): that chunk size instead, not
+// rounded, under the same bounds.
+constexpr size_t HYBRID_SCORES_MAX = (size_t)256 << 20;
+inline size_t hybrid_ld(int n_rows) { return ((size_t)std::max(n_rows, 0) + 63) / 64 * 64; }
+inline int hybrid_chunk_queries(int n_rows, int nq, int pref) {
+    const size_t fit = HYBRID_SCORES_MAX / (std::max<size_t>(hybrid_ld(n_rows), 64) * 4);
+    int hc = (int)std::min<size_t>(fit, (size_t)std::min(std::max(nq, 1), 4096));
+    if (pref > 0) hc = std::min(hc, pref);
+    else if (hc >= 32) hc = hc / 32 * 32;
+    return std::max(hc, 1);
+}
 
 // sparse_index_rescore_kernel: one workgroup of SPARSE_RESCORE_CAND lanes per (query, chunk of its candidates); lane t scores row
 // cand[q][chunk * SPARSE_RESCORE_CAND + t] against query q's image with the scan's chain and writes (score, id) — or (-inf, INT_MAX)
@@ -143,6 +165,8 @@ void launch_sparse_add(int dtype, const SparseAddArgs &a, hipStream_t s);
 void launch_sparse_query(const SparseQueryArgs &a, hipStream_t s);
 // the masked instantiation iff a.live or a.allow is set
 void launch_sparse_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStream_t s);
+// sparse_hybrid_scan_kernel: the scan with a.dscores, a.ld and the weights; masked iff a.live or a.allow is set
+void launch_sparse_hybrid_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStream_t s);
 void launch_sparse_rescore(int dtype, const SparseRescoreArgs &a, hipStream_t s);
 void launch_sparse_gather(int dtype, const SparseGatherArgs &a, hipStream_t s);
 void launch_sparse_export(int dtype, const SparseExportArgs &a, hipStream_t s);

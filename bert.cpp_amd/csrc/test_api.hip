@@ -1007,6 +1007,15 @@ int32_t bert_hip_test_sparse_scan_geometry_qb(int32_t dtype, int32_t n_vocab, in
     return ok ? 0 : -2;
 }
 
+int32_t bert_hip_test_hybrid_chunk(int32_t n_rows, int32_t nq, int32_t pref, int64_t *out) {
+    if (!out) return -1;
+    out[0] = out[1] = 0;
+    if (n_rows < 0 || nq < 1 || pref < 0) return -2;
+    out[0] = hybrid_chunk_queries(n_rows, nq, pref);
+    out[1] = (int64_t)hybrid_ld(n_rows);
+    return 0;
+}
+
 int32_t bert_hip_test_index_plan(int32_t n_rows, int32_t nq, int32_t k, int32_t *geometry) {
     if (!geometry) return -1;
     geometry[0] = geometry[1] = geometry[2] = geometry[3] = 0;

@@ -6,6 +6,13 @@
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
 //               [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]
 //   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
+//   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]
+//   (--hybrid SPLADE: hybrid search.  SPLADE is a second model file, one with the MLM head, loaded into a context of its own (it may be
+//   the same file as DENSE).  Every line goes into an embedding index of DENSE (bert_hip_index_add_texts; --f32 / --i8 / --b1 as
+//   below) and, with its W largest terms (--sparse-width, default 128, 1 .. 256), into a sparse index of SPLADE
+//   (bert_hip_sparse_index_add_texts; --f16: u16 ids and f16 weights).  Each query line is answered by bert_hip_hybrid_search_texts:
+//   the exact top-k of WD * (dense score) + WS * (sparse score) over all lines (--weights, default 1,1; finite numbers), the query's W
+//   largest terms on the sparse side.  Not together with --sparse, --lists, --nprobe, --rescore, --long, --maxsim, --cross, --save, --load.)
 //   (--sparse [WIDTH]: learned sparse search.  MODEL must carry the MLM head (bert_hip.h "learned sparse embeddings"); every line's WIDTH
 //   largest terms (default 128, 1 .. 256) go into a sparse index (bert_hip_sparse_index_add_texts; --f16: u16 ids and f16 weights),
 //   each query line is searched with its WIDTH largest terms (bert_hip_sparse_index_search_texts), and the output has the dense mode's
@@ -38,6 +45,7 @@
 //   printing, and must have as many lines as the index has rows —, and its partition from PATH.part where that file exists
 //   (bert_hip_index_partition_load: --nprobe then needs no --lists))
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -53,6 +61,10 @@ namespace {
 void usage(const char *argv0) {
     fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
+    fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]\n", argv0);
+    fprintf(stderr, "  --hybrid SPLADE: hybrid search: the lines in an embedding index of DENSE and a sparse index of SPLADE (a model file with the MLM head; W\n"
+                    "          terms a line, default 128), each query answered by bert_hip_hybrid_search_texts: the exact top-k of WD * dense + WS * sparse\n"
+                    "          (default 1,1).  Not with --sparse, --lists, --nprobe, --rescore, --long, --maxsim, --cross, --save, --load.\n");
     fprintf(stderr, "  --sparse [WIDTH]: learned sparse search with a model that carries the MLM head: each line's and each query's WIDTH largest terms\n"
                     "          (default 128, 1 .. 256) through a sparse index (bert_hip_sparse_index_*); --f16 stores u16 ids and f16 weights;\n"
                     "          --save PATH writes the sparse index once it is built, --load PATH reads it instead of encoding TEXTS (still read for printing).\n");
@@ -71,7 +83,9 @@ std::string chomp(std::string s) {
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr, *cross_model = nullptr;
+    const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr, *cross_model = nullptr, *hybrid_model = nullptr;
+    float w_dense = 1.f, w_sparse = 1.f;
+    bool weights_ok = true;
     int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0, n_cross = 0;
     bool long_texts = false, maxsim = false, cross = false, sparse = false, sparse_f16 = false;
     int sparse_width = 128;
@@ -95,6 +109,12 @@ int main(int argc, char **argv) {
             if (has_value && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') sparse_width = atoi(argv[++i]);
         }
         else if (!strcmp(argv[i], "--f16")) sparse_f16 = true;
+        else if (!strcmp(argv[i], "--hybrid") && has_value) hybrid_model = argv[++i];
+        else if (!strcmp(argv[i], "--sparse-width") && has_value) sparse_width = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--weights") && has_value) {
+            char tail = 0;
+            weights_ok = sscanf(argv[++i], "%f,%f%c", &w_dense, &w_sparse, &tail) == 2 && std::isfinite(w_dense) && std::isfinite(w_sparse);
+        }
         else if (!strcmp(argv[i], "--window") && has_value) window = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--stride") && has_value) stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--maxsim") && has_value) { maxsim = true; n_maxsim = atoi(argv[++i]); }
@@ -104,12 +124,19 @@ int main(int argc, char **argv) {
     }
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
+    if (hybrid_model && (sparse || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model || save || load)) {
+        fprintf(stderr, "search: --hybrid goes with -m, -f, -k, -t, --sparse-width, --weights, --f32, --i8, --b1 and --f16 only\n");
+        return 2;
+    }
+    if (hybrid_model && (sparse_width < 1 || sparse_width > 256)) { fprintf(stderr, "search: --hybrid: --sparse-width must be 1 .. 256\n"); return 2; }
+    if (hybrid_model && !weights_ok) { fprintf(stderr, "search: --hybrid: --weights takes two finite numbers, WD,WS\n"); return 2; }
+    if (!hybrid_model && (!weights_ok || w_dense != 1.f || w_sparse != 1.f)) { fprintf(stderr, "search: --weights goes with --hybrid\n"); return 2; }
     if (sparse && (sparse_width < 1 || sparse_width > 256)) { fprintf(stderr, "search: --sparse takes a width of 1 .. 256\n"); return 2; }
     if (sparse && (dtype != 1 || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model)) {
         fprintf(stderr, "search: --sparse goes with -m, -f, -k, -t, --f16, --save and --load only\n");
         return 2;
     }
-    if (sparse_f16 && !sparse) { fprintf(stderr, "search: --f16 goes with --sparse\n"); return 2; }
+    if (sparse_f16 && !sparse && !hybrid_model) { fprintf(stderr, "search: --f16 goes with --sparse\n"); return 2; }
     if (!long_texts && (window || stride)) { fprintf(stderr, "search: --window and --stride go with --long\n"); return 2; }
     if (maxsim && (n_maxsim < k || n_maxsim > 256)) { fprintf(stderr, "search: --maxsim must be -k .. 256\n"); return 2; }
     if (cross != (cross_model != nullptr)) { fprintf(stderr, "search: --cross-model and --cross go together\n"); return 2; }
@@ -156,6 +183,45 @@ int main(int argc, char **argv) {
     for (std::string line; std::getline(in, line);) texts.push_back(chomp(line));
     std::vector<const char *> ptrs;
     for (auto &t : texts) ptrs.push_back(t.c_str());
+    if (hybrid_model) {
+        // the hybrid mode: the lines into an embedding index of this model and a sparse index of the second one, each query against both
+        bert_ctx *sparse_ctx = bert_load_from_file(hybrid_model);
+        if (!sparse_ctx || !bert_hip_has_mlm_head(sparse_ctx)) {
+            fprintf(stderr, "search: '%s' %s\n", hybrid_model, sparse_ctx ? "has no MLM head" : "failed to load");
+            if (sparse_ctx) bert_free(sparse_ctx);
+            bert_free(ctx);
+            return 1;
+        }
+        auto fail = [&](const char *what) {
+            fprintf(stderr, "search: %s\n", what);
+            bert_free(sparse_ctx);
+            bert_free(ctx);
+            return 1;
+        };
+        bert_hip_index *dx = bert_hip_index_create(ctx, 0, dtype);
+        if (!dx || bert_hip_index_add_texts(dx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) return fail("could not build the index");
+        bert_hip_sparse_index *sx = bert_hip_sparse_index_create(sparse_ctx, 0, sparse_width, sparse_f16 ? 1 : 0);
+        if (!sx || bert_hip_sparse_index_add_texts(sx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) return fail("could not build the sparse index");
+        printf("Loaded %zu lines.\n", texts.size());
+        std::vector<int32_t> hids((size_t)k);
+        std::vector<float> hscores((size_t)k);
+        for (;;) {
+            printf("Enter a text to find similar texts (enter 'q' to quit): ");
+            fflush(stdout);
+            std::string q;
+            if (!std::getline(std::cin, q)) break;
+            q = chomp(q);
+            if (q == "q") break;
+            const char *qp = q.c_str();
+            if (bert_hip_hybrid_search_texts(dx, sx, n_threads, 1, &qp, sparse_width, w_dense, w_sparse, k, hids.data(), hscores.data()) != 0) return fail("the search failed");
+            printf("\nClosest texts:\n");
+            for (int i = 0; i < k && hids[i] >= 0; ++i) printf("%d. %s\n (similarity score: %.4f)\n", i + 1, texts[hids[i]].c_str(), hscores[i]);
+        }
+        printf("\n");
+        bert_free(sparse_ctx);                                // (frees the sparse index as well)
+        bert_free(ctx);
+        return 0;
+    }
     if (sparse) {
         // the learned sparse mode: the lines' terms into a sparse index, each query's terms against it; nothing below applies
         if (!bert_hip_has_mlm_head(ctx)) {

@@ -48,6 +48,7 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_sparse_index_remove", "bert_hip_sparse_index_n_live", "bert_hip_sparse_index_search_filtered",
     "bert_hip_sparse_index_search_filtered_device", "bert_hip_sparse_index_rescore", "bert_hip_sparse_index_rescore_device",
     "bert_hip_sparse_index_compact", "bert_hip_sparse_index_save", "bert_hip_sparse_index_load",
+    "bert_hip_hybrid_reserve", "bert_hip_hybrid_search", "bert_hip_hybrid_search_device", "bert_hip_hybrid_search_texts",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -63,7 +64,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
     "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid", "bert_hip_test_sparse_scan_geometry",
     "bert_hip_test_sparse_index_header", "bert_hip_test_sparse_index_body",
-    "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan",
+    "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan", "bert_hip_test_hybrid_chunk",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -210,6 +211,13 @@ def _declare_product_abi(L):
     L.bert_hip_sparse_index_compact.restype = i32; L.bert_hip_sparse_index_compact.argtypes = [vp, vp]
     L.bert_hip_sparse_index_save.restype = i32; L.bert_hip_sparse_index_save.argtypes = [vp, C.c_char_p]
     L.bert_hip_sparse_index_load.restype = vp; L.bert_hip_sparse_index_load.argtypes = [vp, C.c_char_p]
+    f32 = C.c_float
+    L.bert_hip_hybrid_reserve.restype = i32; L.bert_hip_hybrid_reserve.argtypes = [vp, vp, i32, i32, i32]
+    L.bert_hip_hybrid_search.restype = i32; L.bert_hip_hybrid_search.argtypes = [vp, vp, i32, vp, i32, vp, vp, f32, f32, vp, i32, i32, vp, vp]
+    L.bert_hip_hybrid_search_device.restype = i32
+    L.bert_hip_hybrid_search_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, f32, f32, vp, i32, i32, vp, vp, vp]
+    L.bert_hip_hybrid_search_texts.restype = i32
+    L.bert_hip_hybrid_search_texts.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_char_p), i32, f32, f32, i32, vp, vp]
 
 
 def lib() -> C.CDLL:
@@ -332,6 +340,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_sparse_scan_geometry_qb.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
     L.bert_hip_test_index_plan.restype = i32
     L.bert_hip_test_index_plan.argtypes = [i32, i32, i32, i32p]
+    L.bert_hip_test_hybrid_chunk.restype = i32
+    L.bert_hip_test_hybrid_chunk.argtypes = [i32, i32, i32, C.POINTER(C.c_int64)]
     _test_lib = L
     return L
 
@@ -466,6 +476,18 @@ def test_index_plan(n_rows: int, nq: int, k: int):
     if r != 0:
         raise RuntimeError(f"bert_hip_test_index_plan failed: {r}")
     return dict(nqt=g[0], slices=g[1], slice_rows=g[2], L=g[3])
+
+
+def test_hybrid_chunk(n_rows: int, nq: int, pref: int = 0):
+    """How a hybrid search chunks nq queries over n_rows rows (bert_hip_test_hybrid_chunk; no GPU): (HC, ld), or None where the hook
+    refuses.  pref: the value of the tuning key "hybrid_chunk_queries" (0 = unset)."""
+    out = (C.c_int64 * 2)()
+    r = test_lib().bert_hip_test_hybrid_chunk(n_rows, nq, pref, out)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_hybrid_chunk failed: {r}")
+    return int(out[0]), int(out[1])
 
 
 def test_attention_grid(n_sentences: int, n_head: int, d_head: int, max_len: int):
@@ -1451,6 +1473,56 @@ class BertIndex:
         r = self.lib.bert_hip_index_search_texts(self.ix, n_threads, n, txt, k, _i32p(ids), _f32p(scores))
         if r != 0:
             raise RuntimeError(f"bert_hip_index_search_texts failed: {r}")
+        return ids, scores
+
+    # ---- hybrid search (bert_hip_hybrid_*): this index and a sparse index of the same rows, H = (w_dense * D) + (w_sparse * S)
+    @staticmethod
+    def _hybrid_fail(name: str, r: int):
+        if r == -2:
+            raise ValueError(f"{name} refused its arguments (see stderr)")
+        raise RuntimeError(f"{name} failed: {r}")
+
+    def hybrid_reserve(self, sparse: "BertSparseIndex", n_rows: int, n_queries: int = 0, k: int = 1) -> None:
+        r = self.lib.bert_hip_hybrid_reserve(self.ix, sparse.ix, n_rows, n_queries, k)
+        if r != 0:
+            self._hybrid_fail("bert_hip_hybrid_reserve", r)
+
+    def hybrid_search(self, sparse: "BertSparseIndex", queries, q_ids, q_weights, k: int = 10, w_dense: float = 1.0, w_sparse: float = 1.0,
+                      allow=None):
+        """The exact top-k of (w_dense * dense score) + (w_sparse * sparse score) over the rows live in both indexes and allowed:
+        queries [n, dim] f32, (q_ids, q_weights) [n, kq] as BertSparseIndex.search takes them, allow as BertIndex.search's."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        q_ids, q_weights = BertSparseIndex._terms(q_ids, q_weights)
+        if q_ids.shape[0] != q.shape[0]:
+            raise ValueError("the dense and the sparse queries differ in number")
+        nq = q.shape[0]
+        ids = np.empty((nq, max(k, 1)), dtype=np.int32)
+        scores = np.empty((nq, max(k, 1)), dtype=np.float32)
+        words = None if allow is None else allow_words(allow, len(self))
+        r = self.lib.bert_hip_hybrid_search(self.ix, sparse.ix, nq, q.ctypes.data, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data,
+                                            w_dense, w_sparse, None if words is None else words.ctypes.data, 0 if words is None else len(words),
+                                            k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._hybrid_fail("bert_hip_hybrid_search", r)
+        return ids, scores
+
+    def hybrid_search_device(self, sparse: "BertSparseIndex", n_queries: int, d_queries_ptr: int, kq: int, d_q_ids_ptr: int, d_q_weights_ptr: int,
+                             k: int, d_ids_ptr: int, d_scores_ptr: int, w_dense: float = 1.0, w_sparse: float = 1.0, stream: int = 0,
+                             d_allow_ptr: int = 0, n_words: int = 0) -> None:
+        r = self.lib.bert_hip_hybrid_search_device(self.ix, sparse.ix, n_queries, d_queries_ptr, kq, d_q_ids_ptr, d_q_weights_ptr, w_dense, w_sparse,
+                                                   d_allow_ptr or None, n_words, k, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            self._hybrid_fail("bert_hip_hybrid_search_device", r)
+
+    def hybrid_search_texts(self, sparse: "BertSparseIndex", texts: Sequence, kq: int = 32, k: int = 10, w_dense: float = 1.0, w_sparse: float = 1.0,
+                            n_threads: int = 6):
+        n = len(texts)
+        txt = (C.c_char_p * max(n, 1))(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        ids = np.empty((n, max(k, 1)), dtype=np.int32)
+        scores = np.empty((n, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_hybrid_search_texts(self.ix, sparse.ix, n_threads, n, txt, kq, w_dense, w_sparse, k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._hybrid_fail("bert_hip_hybrid_search_texts", r)
         return ids, scores
 
 

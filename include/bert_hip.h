@@ -185,7 +185,9 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  * per forward pass), "chunk_tokens" = n, "gather_super_tokens" = n (bert_hip_eval_packed_gather: tokens per device and super-batch, 0 =
  * four device chunks), "stage_kernel" = "0" | "1" (host API: staged blocks of at most 256 KiB travel by a kernel that reads the mapped
  * pinned memory instead of the copy engine), "sparse_index_qb" = n (tuning: queries per workgroup tile of the sparse index's scan, 1 .. 8;
- * "0" = the built-in choice; a result's bits do not depend on it; set it before bert_hip_sparse_index_reserve), "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"
+ * "0" = the built-in choice; a result's bits do not depend on it; set it before bert_hip_sparse_index_reserve), "hybrid_chunk_queries" = n (tuning: queries
+ * per internal chunk of a hybrid search, 1 .. 4096, never more than the score workspace's bound allows; "0" = what that bound gives; a
+ * result's bits do not depend on it), "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"
  * (BERT_HIP_POOLING / BERT_HIP_NORMALIZE above; bert_hip_pooling / bert_hip_normalize return what is in force).                       */
 BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const char *value);
 
@@ -690,8 +692,8 @@ BERT_API struct bert_hip_index *bert_hip_index_load(struct bert_ctx *ctx, const 
  * Results: -1 without an index (or, for the text forms, a context without a device); -2 after a line on stderr for an argument the
  * entry refuses (the checks above, k_in > width, k or kq out of range, a missing pointer, a model without the head); -3 on a device
  * error; -4 for an exception.  Outputs are untouched on error.
- * Not covered: an inverted (term-major) organisation; a fused dense + sparse (hybrid) search call; several GPUs; rows wider than
- * 256 terms.                                                                                                                        */
+ * Not covered: an inverted (term-major) organisation; several GPUs; rows wider than 256 terms.  (A search over an embedding index
+ * and a sparse index together: "Hybrid search" below.)                                                                                                                      */
 struct bert_hip_sparse_index;
 BERT_API struct bert_hip_sparse_index *bert_hip_sparse_index_create(struct bert_ctx *ctx, int32_t n_vocab, int32_t width, int32_t dtype);
 BERT_API void    bert_hip_sparse_index_free(struct bert_hip_sparse_index *ix);
@@ -731,7 +733,8 @@ BERT_API int32_t bert_hip_sparse_index_get_rows(struct bert_hip_sparse_index *ix
  *            workspace [n_queries][n_cand] grows on demand and is not part of reserve: call once at the largest shape before a capture.
  *            Hybrid search from public calls: bert_hip_index_search_device writes d_ids [n_queries][k] on a stream; pass them as
  *            d_cand_ids of bert_hip_sparse_index_rescore_device on the same stream (and the reverse through bert_hip_index_rescore_device):
- *            the ids never leave the device.  A fused dense + sparse score is not provided.
+ *            the ids never leave the device.  That ranks one side's top-k by the other side; the exact top-k of a weighted sum of
+ *            both scores over all rows is bert_hip_hybrid_search ("Hybrid search" below).
  *   compact  drops the removed rows: the live rows keep their order and stored bits and get ids 0 .. n_live - 1; old_ids (may be NULL)
  *            [n_live] receives their former ids.  Returns the new size.  On an index without removals a no-op that returns size (old_ids
  *            the identity).  Afterwards the index keeps no bitmap and launches the unmasked scan again.  Blocking; allocates.
@@ -768,6 +771,54 @@ BERT_API int32_t bert_hip_sparse_index_rescore_device(struct bert_hip_sparse_ind
 BERT_API int32_t bert_hip_sparse_index_compact(struct bert_hip_sparse_index *ix, int32_t *old_ids);
 BERT_API int32_t bert_hip_sparse_index_save(struct bert_hip_sparse_index *ix, const char *path);
 BERT_API struct bert_hip_sparse_index *bert_hip_sparse_index_load(struct bert_ctx *ctx, const char *path);
+
+/* Hybrid search: the exact top-k, over ALL qualifying rows, of a weighted sum of an embedding index's and a sparse index's scores.
+ * `dense` is a bert_hip_index of any dtype (0 .. 3), `sparse` a bert_hip_sparse_index of either dtype.  They may belong to different
+ * contexts — a bi-encoder and a model with the MLM head — or to the same one; they must live on the same HIP device (bert_hip_device of
+ * their contexts) and have equal size, otherwise -2.  They are meant to hold the same texts in the same order: row id r is the same
+ * text in both.
+ *   Score.  For query q and row r, D is the score bits bert_hip_index_rescore gives the pair on `dense` (the dense search's chain,
+ *     whatever the dtype), S the score bits bert_hip_sparse_index_rescore gives it on `sparse` (the fmaf chain from +0; +0 for a row
+ *     without a matching term).  The hybrid score is  H = (w_dense * D) + (w_sparse * S):  two f32 multiplications and one f32
+ *     addition, each rounded to nearest even, never an fma — NumPy float32 arithmetic reproduces it exactly.  w_dense and w_sparse
+ *     must be finite (any sign, zero included), otherwise -2.  NaN and inf follow IEEE through the rule: an i8 row that held an inf
+ *     has D = NaN, hence H = NaN, and is never returned.
+ *   Qualifying rows.  A row qualifies if it is live in `dense`, live in `sparse` and allowed: allow == NULL means all rows (n_words
+ *     is ignored), else words [n_words] as search_filtered's, n_words >= ceil(size / 32) or -2; words at and beyond ceil(size / 32)
+ *     are never read, bits at and beyond size are ignored.
+ *   Order, slots, limits: the indexes' rules.  A larger H first, equal H (==) by smaller id, NaN never returned, id -1 / score
+ *     -INFINITY in the slots beyond the qualifying rows.  1 <= k <= 256, 1 <= kq <= 256.  n_queries == 0 is a successful no-op; an
+ *     empty pair of indexes is valid.  queries [n_queries][dim of dense], q_ids / q_weights [n_queries][kq].  The host form checks
+ *     its queries as bert_hip_index_search and bert_hip_sparse_index_search check theirs; the device form does not look.
+ *   Determinism.  A (query, row) pair's H has the same bits whatever the other queries of the call, k (top-10 is the first 10 of
+ *     top-100), the internal chunking of the queries, the number of add calls that built either index, reserved or grown storage, and
+ *     host or device entry point.  Hence, with finite D and S, weights (1, 0) return the ids of bert_hip_index_search_filtered and
+ *     numerically equal scores (only the sign of a zero may differ), and (0, 1) those of bert_hip_sparse_index_search_filtered.
+ *   Streams.  search_device is asynchronous on the caller's stream.  The call is ONE operation of both indexes: it waits for both
+ *     indexes' events and leaves both recorded.  Within the bounds of bert_hip_hybrid_reserve — both indexes' reserve for n_rows,
+ *     n_queries, k, and the hybrid workspace: at most 256 MiB of dense scores per internal chunk of queries (one query's scores where
+ *     those alone are more), and one bitmap — it never allocates and is legal under stream capture (STREAM CAPTURE AND GRAPHS above);
+ *     without a reserve everything grows on demand.  The tuning key "hybrid_chunk_queries" (bert_hip_set_option on the SPARSE index's
+ *     context) is read when a search is planned and when reserve sizes the workspace: set it before bert_hip_hybrid_reserve.
+ *   search_texts.  dense's context encodes the texts as bert_hip_index_search_texts does (dim == n_embd required), sparse's context
+ *     runs the MLM head's top-kq as bert_hip_sparse_index_search_texts does and refuses what it refuses (no head, another vocabulary);
+ *     the search then runs on the sparse index's stream.  One context may serve both.  A dense context over several GPUs encodes
+ *     through bert_hip_encode_batch, as bert_hip_index_search_texts does there; the sparse side uses its context's first device.
+ * Results: 0; -1 without one of the indexes; -2 after a line on stderr for an argument the entry refuses; -3 on a device error; -4 for
+ * an exception.  Outputs are untouched on error.
+ * Not covered: reciprocal-rank fusion; a probed (IVF) dense side; several GPUs; a hybrid rescore (the two rescores chained give that).   */
+BERT_API int32_t bert_hip_hybrid_reserve(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse, int32_t n_rows, int32_t n_queries,
+                                         int32_t k);
+BERT_API int32_t bert_hip_hybrid_search(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse, int32_t n_queries, const float *queries,
+                                        int32_t kq, const int32_t *q_ids, const float *q_weights, float w_dense, float w_sparse,
+                                        const uint32_t *allow, int32_t n_words, int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_hybrid_search_device(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse, int32_t n_queries,
+                                               const float *d_queries, int32_t kq, const int32_t *d_q_ids, const float *d_q_weights,
+                                               float w_dense, float w_sparse, const uint32_t *d_allow, int32_t n_words, int32_t k,
+                                               int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_hybrid_search_texts(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse, int32_t n_threads,
+                                              int32_t n_queries, const char **texts, int32_t kq, float w_dense, float w_sparse, int32_t k,
+                                              int32_t *ids, float *scores);
 
 BERT_API const char *bert_hip_version(void);
 

@@ -298,6 +298,11 @@ BERT_API int32_t bert_hip_test_index_plan(int32_t n_rows, int32_t nq, int32_t k,
 BERT_API int32_t bert_hip_test_sparse_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err,
                                                    int32_t err_cap);
 BERT_API int32_t bert_hip_test_sparse_index_body(const uint32_t *fields, const void *body, int64_t body_len, char *err, int32_t err_cap);
+/* How a hybrid search chunks nq queries over indexes of n_rows rows (sparse_index_kernels.h hybrid_chunk_queries, the function the
+ * search itself calls; no GPU): out = {HC, ld} — queries per chunk and floats per query of the dense score matrix (n_rows rounded up to
+ * 64).  pref: the value of the tuning key "hybrid_chunk_queries" (0 = unset).  0; -2 and zeros for n_rows < 0, nq < 1 or pref < 0; -1
+ * for a NULL out.                                                                                                                  */
+BERT_API int32_t bert_hip_test_hybrid_chunk(int32_t n_rows, int32_t nq, int32_t pref, int64_t *out);
 
 #ifdef __cplusplus
 }
