@@ -1,5 +1,5 @@
 // context.h — struct bert_ctx: what a loaded model owns (tokenizer, one engine per GPU, the host threads and buffers of the
-// batch entry points, the embedding gather, the caller's indexes and sparse indexes), and how it is loaded.
+// batch entry points, the embedding gather, the caller's indexes, sparse indexes and token indexes), and how it is loaded.
 //
 // A context is NOT thread-safe, like the reference's: every entry point that takes one may use its worker pools and its
 // grow-only buffers, so calls on one context are serialised by the caller (bert_encode_batch's tokenize-ahead thread is the
@@ -15,6 +15,7 @@
 #include "search.h"
 #include "sparse_index.h"
 #include "text_batch.h"
+#include "token_index.h"
 #include "tokenizer.h"
 
 struct bert_ctx;
@@ -29,6 +30,12 @@ struct bert_hip_index {
 struct bert_hip_sparse_index {
     bert_ctx *ctx = nullptr;
     std::unique_ptr<bert_hip::SparseIndex> ix;
+};
+
+// a token index (token_index.h) and the context it was made from
+struct bert_hip_token_index {
+    bert_ctx *ctx = nullptr;
+    std::unique_ptr<bert_hip::TokenIndex> ix;
 };
 
 struct bert_ctx {
@@ -52,11 +59,14 @@ struct bert_ctx {
     std::vector<bert_hip_index *> indexes;
     // the caller's sparse indexes (bert_hip_sparse_index_create), freed with the context in the same place
     std::vector<bert_hip_sparse_index *> sparse_indexes;
+    // the caller's token indexes (bert_hip_token_index_create), freed with the context in the same place
+    std::vector<bert_hip_token_index *> token_indexes;
 
     bert_hip::Engine *engine() const { return engines.empty() ? nullptr : engines[0].get(); }
     ~bert_ctx() {
         for (bert_hip_index *ix : indexes) delete ix;
         for (bert_hip_sparse_index *ix : sparse_indexes) delete ix;
+        for (bert_hip_token_index *ix : token_indexes) delete ix;
     }
 };
 

@@ -1016,6 +1016,14 @@ int32_t bert_hip_test_hybrid_chunk(int32_t n_rows, int32_t nq, int32_t pref, int
     return 0;
 }
 
+int32_t bert_hip_test_token_index_plan(int32_t n_docs, int32_t nq, int32_t pref, int32_t *plan) {
+    if (!plan) return -1;
+    TokenScanPlan p;
+    const bool ok = token_index_plan(n_docs, nq, pref, p);
+    plan[0] = p.n_slices; plan[1] = p.slice_docs;
+    return ok ? 0 : -2;
+}
+
 int32_t bert_hip_test_index_plan(int32_t n_rows, int32_t nq, int32_t k, int32_t *geometry) {
     if (!geometry) return -1;
     geometry[0] = geometry[1] = geometry[2] = geometry[3] = 0;

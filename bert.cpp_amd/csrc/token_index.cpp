@@ -1,0 +1,371 @@
+// token_index.cpp — the host side of the token index (token_index.h): storage and its growth, the add forms, the search and its
+// chunks, rescoring, reading a document back and the checks of the host forms.  Every kernel is in token_index.hip, maxsim.hip or
+// search.hip (the merge) and reached through token_index_kernels.h / kernels.h / search_kernels.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstring>
+#include <vector>
+
+#include "search.h"
+#include "token_index.h"
+
+namespace bert_hip {
+
+namespace {
+
+// the most workspace entries (nq' * slices * k) a chunk of up to nqc queries takes: the slice count falls as the queries grow
+size_t ws_entries_bound(int n_docs, int nqc, int k, int pref) {
+    size_t ent = 0;
+    TokenScanPlan p;
+    for (int q = 1; q <= nqc; ++q)
+        if (token_index_plan(n_docs, q, pref, p)) ent = std::max(ent, (size_t)q * p.max_slices * k);
+    return ent;
+}
+
+// 1 = go on, 0 = nothing to do, -2 = refused
+int check_add(int n_docs, const int32_t *cu, const void *rows, int size, int64_t n_tok, std::string &err) {
+    if (n_docs < 0 || (n_docs > 0 && (!cu || !rows))) { err = "add: n_docs >= 0, cu and rows required"; return -2; }
+    if (n_docs == 0) return 0;
+    if (!token_cu_ok(cu, n_docs)) { err = "add: cu must ascend strictly from an entry >= 0 (every document has at least one token)"; return -2; }
+    if ((long long)size + n_docs > INT_MAX - 1 || n_tok + ((long long)cu[n_docs] - cu[0]) > INT_MAX) { err = "add: an index holds fewer than 2^31 documents and tokens"; return -2; }
+    return 1;
+}
+
+int check_search(int nq, const void *qcu, const void *q, int k, const void *ids, const void *scores, std::string &err) {
+    if (k < 1 || k > TokenIndex::MAX_K) { err = "search: k must be 1 .. 256"; return -2; }
+    if (nq < 0 || (nq > 0 && (!qcu || !q || !ids || !scores))) { err = "search: n_queries >= 0 and query / result pointers required"; return -2; }
+    return nq > 0;
+}
+
+int check_rescore(int nq, const void *qcu, const void *q, int n_cand, const void *cand, int k, const void *ids, const void *scores, std::string &err) {
+    if (k < 1 || k > TokenIndex::MAX_K) { err = "rescore: k must be 1 .. 256"; return -2; }
+    if (n_cand < 1 || n_cand > TokenIndex::MAX_CAND) { err = "rescore: n_cand must be 1 .. 1024"; return -2; }
+    if (nq < 0 || (nq > 0 && (!qcu || !q || !cand || !ids || !scores))) { err = "rescore: n_queries >= 0 and query / candidate / result pointers required"; return -2; }
+    return nq > 0;
+}
+
+}  // namespace
+
+bool token_cu_ok(const int32_t *cu, int n) {
+    bool ok = cu[0] >= 0;
+    for (int i = 0; ok && i < n; ++i) ok = cu[i + 1] > cu[i];
+    return ok;
+}
+
+TokenIndex *TokenIndex::create(Engine *eng, int dim, std::string &err) {
+    if (!eng) { err = "no device engine"; return nullptr; }
+    if (dim < 8 || dim > MAXSIM_MAX_H || dim % 8) { err = "dim must be a multiple of 8 in 8 .. " + std::to_string(MAXSIM_MAX_H); return nullptr; }
+    DeviceGuard g(eng->device());
+    TokenIndex *ix = new TokenIndex;
+    ix->eng_ = eng;
+    ix->dim_ = dim;
+    ix->cu_h_.assign(1, 0);
+    const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
+                    hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
+    if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
+    // (cu[0] = 0 is there from the start: an empty index is searched like any other)
+    if (!ix->grow_storage(1, 0, err)) { delete ix; return nullptr; }
+    token_index_kernels_init();
+    return ix;
+}
+
+TokenIndex::~TokenIndex() {
+    DeviceGuard g(eng_ ? eng_->device() : 0);
+    if (busy_) { (void)hipEventSynchronize(busy_); (void)hipEventDestroy(busy_); }
+    if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
+    if (rows_) (void)hipFree(rows_);
+    if (cu_) (void)hipFree(cu_);
+}
+
+bool TokenIndex::grow(DevBuf &b, size_t bytes, std::string &err) {
+    if (bytes <= b.bytes) return true;
+    HIP_OK(hipEventSynchronize(busy_), err, false);          // (what is queued may still read the old buffer)
+    return b.ensure(bytes, err);
+}
+
+// (rows and cumulative lengths are plain arrays: growth is a copy each; the host mirror's capacity follows cu_'s, so that its
+// entries never move while a copy from them may be queued)
+bool TokenIndex::grow_storage(long long n_docs, long long n_tokens, std::string &err) {
+    if (n_docs <= cap_docs_ && n_tokens <= cap_tok_) return true;
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    HIP_OK(hipStreamSynchronize(stream_), err, false);
+    if (n_docs > cap_docs_) {
+        const long long cap = std::min<long long>(INT_MAX - 1, std::max<long long>({n_docs, (long long)cap_docs_ * 3 / 2, 1024}));
+        int32_t *pc = nullptr;
+        if (hipMalloc((void **)&pc, (size_t)(cap + 1) * 4) != hipSuccess) { (void)hipGetLastError(); err = "hipMalloc (token index lengths) failed"; return false; }
+        if (hipMemcpy(pc, cu_h_.data(), (size_t)(n_ + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(pc);
+            err = "hipMemcpy (token index lengths) failed";
+            return false;
+        }
+        if (cu_) (void)hipFree(cu_);
+        cu_ = pc;
+        cap_docs_ = (int)cap;
+        cu_h_.reserve((size_t)cap + 1);
+    }
+    if (n_tokens > cap_tok_) {
+        const long long cap = std::min<long long>(INT_MAX, std::max<long long>({n_tokens, (long long)cap_tok_ * 3 / 2, 4096}));
+        half_t *pr = nullptr;
+        const size_t row_bytes = (size_t)dim_ * 2;
+        if (hipMalloc((void **)&pr, (size_t)cap * row_bytes) != hipSuccess) { (void)hipGetLastError(); err = "hipMalloc (token index rows) failed"; return false; }
+        if (n_tok_ > 0 && hipMemcpy(pr, rows_, (size_t)n_tok_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(pr);
+            err = "hipMemcpy (token index rows) failed";
+            return false;
+        }
+        if (rows_) (void)hipFree(rows_);
+        rows_ = pr;
+        cap_tok_ = cap;
+    }
+    return true;
+}
+
+bool TokenIndex::grow_search(int n_docs, int nqc, int k, std::string &err) {
+    const size_t ent = ws_entries_bound(n_docs, nqc, k, eng_->options().token_index_slices);
+    return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err);
+}
+
+int TokenIndex::reserve(int n_docs, int64_t n_tokens, int n_queries, int max_q_len, int k, std::string &err) {
+    if (n_docs < 0 || n_tokens < 0 || n_tokens > INT_MAX || n_queries < 0 || k < 1 || k > MAX_K || max_q_len < 0 || max_q_len > max_query_tokens()) {
+        err = "reserve: n_docs, n_queries >= 0, 0 <= n_tokens < 2^31, 1 <= k <= 256 and 0 <= max_q_len <= " + std::to_string(max_query_tokens()) + " required";
+        return -2;
+    }
+    DeviceGuard g(eng_->device());
+    if (!grow_storage(n_docs, n_tokens, err)) return -3;
+    const int nqc = std::min(n_queries, QCHUNK);
+    if (nqc == 0) return 0;
+    return grow_search(std::max(n_docs, n_), nqc, k, err) ? 0 : -3;
+}
+
+bool TokenIndex::commit(int n_docs, const int32_t *cu, hipStream_t s, std::string &err) {
+    const size_t at = cu_h_.size();                          // == n_ + 1 (the capacity is grow_storage's: no entry moves)
+    for (int i = 1; i <= n_docs; ++i) cu_h_.push_back((int32_t)(n_tok_ + ((long long)cu[i] - cu[0])));
+    if (hipMemcpyAsync(cu_ + at, cu_h_.data() + at, (size_t)n_docs * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
+        (void)hipGetLastError();
+        cu_h_.resize(at);
+        err = "hipMemcpyAsync (token index lengths) failed";
+        return false;
+    }
+    n_ += n_docs;
+    n_tok_ = cu_h_.back();
+    return true;
+}
+
+int TokenIndex::add_device(int n_docs, const int32_t *cu, const half_t *d_rows, hipStream_t s, std::string &err) {
+    if (const int go = check_add(n_docs, cu, d_rows, n_, n_tok_, err); go <= 0) return go < 0 ? go : n_;
+    if ((uintptr_t)d_rows & 15) { err = "add: the rows must be 16-byte aligned"; return -2; }
+    DeviceGuard g(eng_->device());
+    Engine::StreamOp op;                                     // (engine.h: the one-event rule)
+    if (!eng_->op_begin(s, busy_, op, err)) return -3;
+    const long long T = (long long)cu[n_docs] - cu[0];
+    if (!grow_storage((long long)n_ + n_docs, n_tok_ + T, err)) return -3;
+    HIP_OK(hipMemcpyAsync(rows_ + (size_t)n_tok_ * dim_, d_rows + (size_t)cu[0] * dim_, (size_t)T * dim_ * 2, hipMemcpyDeviceToDevice, s), err, -3);
+    const int first = n_;
+    if (!commit(n_docs, cu, s, err)) return -3;
+    if (!eng_->op_end(op, err)) return -3;
+    return first;
+}
+
+int TokenIndex::add_host(int n_docs, const int32_t *cu, const float *rows, std::string &err) {
+    if (const int go = check_add(n_docs, cu, rows, n_, n_tok_, err); go <= 0) return go < 0 ? go : n_;
+    DeviceGuard g(eng_->device());
+    const long long T = (long long)cu[n_docs] - cu[0];
+    if (!grow_storage((long long)n_ + n_docs, n_tok_ + T, err)) return -3;
+    // through a staging buffer of at most 32 MiB (a row's stored bits do not depend on the parts it came in)
+    const long long per = std::max<long long>(1, ((long long)32 << 20) / ((long long)dim_ * 4));
+    if (!grow(stage_, (size_t)std::min(per, T) * dim_ * 4, err)) return -3;
+    Engine::StreamOp op;
+    if (!eng_->op_begin(stream_, busy_, op, err)) return -3;
+    for (long long t0 = 0; t0 < T; t0 += per) {
+        const size_t c = (size_t)std::min(per, T - t0);
+        bool ok = hipMemcpyAsync(stage_.p, rows + (size_t)(cu[0] + t0) * dim_, c * dim_ * 4, hipMemcpyHostToDevice, stream_) == hipSuccess;
+        if (ok) eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), rows_ + (size_t)(n_tok_ + t0) * dim_, c * dim_, stream_); });
+        ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(stream_) == hipSuccess;
+        if (!ok) { (void)hipStreamSynchronize(stream_); err = "add: copy to the device failed"; return -3; }
+    }
+    const int first = n_;
+    if (!commit(n_docs, cu, stream_, err)) return -3;
+    if (!eng_->op_end(op, err)) return -3;
+    HIP_OK(hipStreamSynchronize(stream_), err, -3);
+    return first;
+}
+
+half_t *TokenIndex::append_room(int64_t n_tokens, std::string &err) {
+    if (n_tokens < 0 || n_tok_ + n_tokens > INT_MAX) { err = "add: an index holds fewer than 2^31 tokens"; return nullptr; }
+    if (!grow_storage(n_, n_tok_ + n_tokens, err)) return nullptr;
+    return rows_ + (size_t)n_tok_ * dim_;
+}
+
+int TokenIndex::add_in_place(int n_docs, const int32_t *cu, std::string &err) {
+    if (const int go = check_add(n_docs, cu, rows_, n_, n_tok_, err); go <= 0) return go < 0 ? go : n_;
+    if (cu[0] != 0 || n_tok_ + cu[n_docs] > cap_tok_) { err = "add: the rows in place do not match the room asked for"; return -2; }
+    DeviceGuard g(eng_->device());
+    // (the lengths first: growing them keeps rows_ and what the caller enqueued into it)
+    if (!grow_storage((long long)n_ + n_docs, n_tok_, err)) return -3;
+    Engine::StreamOp op;
+    if (!eng_->op_begin(stream_, busy_, op, err)) return -3;
+    const int first = n_;
+    if (!commit(n_docs, cu, stream_, err)) return -3;
+    if (!eng_->op_end(op, err)) return -3;
+    return first;
+}
+
+void TokenIndex::truncate(int n) {
+    if (n < 0 || n >= n_) return;
+    // (after a failure, behind a synchronised stream: no copy from the mirror is queued)
+    cu_h_.resize((size_t)n + 1);
+    n_ = n;
+    n_tok_ = cu_h_.back();
+}
+
+int TokenIndex::get_doc(int id, float *rows, int cap_tokens, std::string &err) {
+    if (id < 0 || id >= n_) { err = "get_doc: id " + std::to_string(id) + " outside [0, " + std::to_string(n_) + ")"; return -2; }
+    const int len = cu_h_[(size_t)id + 1] - cu_h_[(size_t)id];
+    if (!rows || cap_tokens < len) return len;
+    DeviceGuard g(eng_->device());
+    std::vector<half_t> h((size_t)len * dim_);
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
+    HIP_OK(hipMemcpyAsync(h.data(), rows_ + (size_t)cu_h_[(size_t)id] * dim_, h.size() * 2, hipMemcpyDeviceToHost, stream_), err, -3);
+    HIP_OK(hipStreamSynchronize(stream_), err, -3);
+    for (size_t i = 0; i < h.size(); ++i) rows[i] = (float)h[i];
+    return len;
+}
+
+// ------------------------------------------------------------------------------------------------
+// search
+// ------------------------------------------------------------------------------------------------
+int TokenIndex::search_device(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
+                              std::string &err) {
+    if (const int go = check_search(nq, d_qcu, d_q, k, d_ids, d_scores, err); go <= 0) return go;
+    if (max_q_len < 1 || max_q_len > max_query_tokens()) { err = "search: max_q_len must be 1 .. " + std::to_string(max_query_tokens()) + " at dim " + std::to_string(dim_); return -2; }
+    if ((uintptr_t)d_q & 15) { err = "search: the query rows must be 16-byte aligned"; return -2; }
+    DeviceGuard g(eng_->device());
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -3;
+    if (!grow_search(n_, std::min(nq, QCHUNK), k, err)) return -3;
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        TokenScanPlan p;
+        token_index_plan(n_, c, eng_->options().token_index_slices, p);       // (the key's range is the option's: never refused)
+        TokenScanArgs a;
+        a.rows = rows_; a.cu = cu_; a.q = d_q; a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+        a.n_docs = n_; a.dim = dim_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
+        a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
+        eng_->timed_launch("token_index_scan", 0.0, s, [&] { launch_token_scan(a, s); });
+        MergeArgs m;
+        m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = p.n_slices * k; m.k = k; m.L = merge_L(k);
+        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
+        eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+    }
+    HIP_OK(hipGetLastError(), err, -3);
+    return eng_->op_end(op, err) ? 0 : -3;
+}
+
+int TokenIndex::search_device_to_host(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *ids, float *scores, std::string &err) {
+    std::vector<int32_t> hid((size_t)nq * k);
+    std::vector<float> hsc((size_t)nq * k);
+    if (!grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
+    if (const int r = search_device(nq, d_qcu, d_q, max_q_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err); r != 0) {
+        (void)hipStreamSynchronize(stream_);
+        return r;
+    }
+    HIP_OK(hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+    HIP_OK(hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+    HIP_OK(hipStreamSynchronize(stream_), err, -3);
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+int TokenIndex::stage_queries(const char *what, int nq, const int32_t *qcu, const float *q_rows, int limit, int &max_len, std::string &err) {
+    if (!token_cu_ok(qcu, nq)) { err = std::string(what) + ": qcu must ascend strictly from an entry >= 0 (no empty query)"; return -2; }
+    max_len = 0;
+    for (int i = 0; i < nq; ++i) max_len = std::max(max_len, qcu[i + 1] - qcu[i]);
+    if (limit > 0 && max_len > limit) {
+        err = std::string(what) + ": a query of " + std::to_string(max_len) + " tokens; a search at dim " + std::to_string(dim_) + " takes at most " + std::to_string(limit);
+        return -2;
+    }
+    const size_t T = (size_t)(qcu[nq] - qcu[0]), n = T * dim_;
+    if (!grow(stage_, n * 4, err) || !grow(q16_, n * 2, err) || !grow(qcu_in_, (size_t)(nq + 1) * 4, err)) return -3;
+    // (the previous host call has synchronised stream(): nothing reads the staged lengths any more)
+    qcu_h_.resize((size_t)nq + 1);
+    for (int i = 0; i <= nq; ++i) qcu_h_[i] = qcu[i] - qcu[0];
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
+    HIP_OK(hipMemcpyAsync(stage_.p, q_rows + (size_t)qcu[0] * dim_, n * 4, hipMemcpyHostToDevice, stream_), err, -3);
+    HIP_OK(hipMemcpyAsync(qcu_in_.p, qcu_h_.data(), qcu_h_.size() * 4, hipMemcpyHostToDevice, stream_), err, -3);
+    eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), q16_.as<half_t>(), n, stream_); });
+    HIP_OK(hipGetLastError(), err, -3);
+    return 0;
+}
+
+int TokenIndex::search_host(int nq, const int32_t *qcu, const float *q_rows, int k, int32_t *ids, float *scores, std::string &err) {
+    if (const int go = check_search(nq, qcu, q_rows, k, ids, scores, err); go <= 0) return go;
+    DeviceGuard g(eng_->device());
+    int max_len = 0;
+    if (const int r = stage_queries("search", nq, qcu, q_rows, max_query_tokens(), max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
+    return search_device_to_host(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), max_len, k, ids, scores, err);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rescoring
+// ------------------------------------------------------------------------------------------------
+int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, int n_cand, const int32_t *d_cand, int k, int32_t *d_ids,
+                               float *d_scores, hipStream_t s, std::string &err) {
+    if (const int go = check_rescore(nq, d_qcu, d_q, n_cand, d_cand, k, d_ids, d_scores, err); go <= 0) return go;
+    if ((uintptr_t)d_q & 15) { err = "rescore: the query rows must be 16-byte aligned"; return -2; }
+    DeviceGuard g(eng_->device());
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -3;
+    const size_t ent = (size_t)std::min(nq, QCHUNK) * n_cand;
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(pairs_, ent * 8, err)) return -3;
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        TokenPairsArgs pa{d_cand + (size_t)c0 * n_cand, pairs_.as<int32_t>(), ws_i_.as<int>(), c, n_cand, n_};
+        eng_->timed_launch("token_index_pairs", 0.0, s, [&] { launch_token_pairs(pa, s); });
+        // (the index's own arrays are maxsim's document side; a pair (q, -1) is scored NaN and reads nothing)
+        MaxsimArgs ma{d_q, rows_, d_qcu + c0, cu_, pairs_.as<int32_t>(), ws_s_.as<float>(), c, n_, dim_, c * n_cand, 0};
+        eng_->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(ma, s); });
+        MergeArgs m;
+        m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
+        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
+        eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+    }
+    HIP_OK(hipGetLastError(), err, -3);
+    return eng_->op_end(op, err) ? 0 : -3;
+}
+
+int TokenIndex::rescore_host(int nq, const int32_t *qcu, const float *q_rows, int n_cand, const int32_t *cand, int k, int32_t *ids, float *scores,
+                             std::string &err) {
+    if (const int go = check_rescore(nq, qcu, q_rows, n_cand, cand, k, ids, scores, err); go <= 0) return go;
+    for (size_t i = 0; i < (size_t)nq * n_cand; ++i)
+        if (cand[i] < -1 || cand[i] >= n_) { err = "rescore: candidate id " + std::to_string(cand[i]) + " is outside [-1, " + std::to_string(n_) + ")"; return -2; }
+    DeviceGuard g(eng_->device());
+    std::vector<int32_t> hid((size_t)nq * k);
+    std::vector<float> hsc((size_t)nq * k);
+    if (!grow(cand_in_, (size_t)nq * n_cand * 4, err) || !grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
+    int max_len = 0;
+    if (const int r = stage_queries("rescore", nq, qcu, q_rows, 0, max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
+    auto fail = [&](int r) { (void)hipStreamSynchronize(stream_); return r; };
+    if (hipMemcpyAsync(cand_in_.p, cand, (size_t)nq * n_cand * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { err = "rescore: copy to the device failed"; return fail(-3); }
+    if (const int r = rescore_device(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
+                                     out_scores_.as<float>(), stream_, err); r != 0) return fail(r);
+    if (hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
+        hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
+        hipStreamSynchronize(stream_) != hipSuccess) { err = "rescore: copy of the results failed"; return fail(-3); }
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+bool TokenIndex::text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err) {
+    if (!grow(text_in_, in_bytes, err) || !grow(text_out_, std::max<size_t>(out_bytes, 16), err)) return false;
+    d_in = text_in_.as<char>();
+    d_out = text_out_.as<char>();
+    return true;
+}
+
+}  // namespace bert_hip

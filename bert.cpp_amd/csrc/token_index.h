@@ -1,0 +1,100 @@
+// token_index.h — a token index in HBM and its exact MaxSim top-k search (the class: token_index.cpp; its kernels: token_index.hip
+// behind token_index_kernels.h; C ABI: bert_hip_token_index_* in include/bert_hip.h).  Documents are runs of f16 token rows, packed,
+// with int32 cumulative lengths on the device and in a host mirror, on the device of the engine the index was made from.  A search
+// scans the documents with one (query, slice of documents) per workgroup and selects on chip (token_index_scan_kernel), then merges the
+// slices' lists per query with the embedding index's topk_merge_kernel; a rescore turns per-query candidate ids into maxsim's pair
+// list, scores them with launch_maxsim against the index's own arrays and selects with the same merge.  Shaped like SparseIndex
+// (sparse_index.h): grow-only storage and workspace, one event, a stream for the host routes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "engine.h"
+#include "token_index_kernels.h"
+
+namespace bert_hip {
+
+class TokenIndex {
+public:
+    static constexpr int MAX_K = 256, MAX_CAND = TOKEN_MAX_CAND;
+    static constexpr int QCHUNK = 256;                   // queries per internal pass (workspace bound)
+
+    static TokenIndex *create(Engine *eng, int dim, std::string &err);
+    ~TokenIndex();
+
+    int size() const { return n_; }
+    int64_t n_tokens() const { return n_tok_; }
+    int dim() const { return dim_; }
+    int max_query_tokens() const { return token_max_query_tokens(dim_); }
+    hipStream_t stream() const { return stream_; }
+
+    // Results: >= 0, or -2 (an argument the entry refuses; nothing changed) or -3 (a device error), a message in err either way.
+    // storage for n_docs documents of n_tokens tokens in all, and the workspace of searches of up to n_queries queries of up to
+    // max_q_len tokens with any k' <= k, now
+    int reserve(int n_docs, int64_t n_tokens, int n_queries, int max_q_len, int k, std::string &err);
+    // append n_docs documents: cu [n_docs + 1] in HOST memory (checked), d_rows f16 in device memory indexed by cu: the first new id.
+    // Asynchronous on s; may grow storage (not for stream capture)
+    int add_device(int n_docs, const int32_t *cu, const half_t *d_rows, hipStream_t s, std::string &err);
+    // host rows f32 indexed by cu, rounded to f16 on the device; blocking
+    int add_host(int n_docs, const int32_t *cu, const float *rows, std::string &err);
+    // Text route: room for n_tokens more rows (storage grown, the index's operations that read the old storage finished), the place the
+    // next document's first row goes — the caller writes the rows there on stream() and commits them with add_in_place
+    half_t *append_room(int64_t n_tokens, std::string &err);
+    // the n_docs documents whose rows the caller has enqueued on stream() at append_room's place; cu relative (cu[0] == 0), checked
+    int add_in_place(int n_docs, const int32_t *cu, std::string &err);
+    // forget the documents behind the first n (an add of several parts that failed part way)
+    void truncate(int n);
+    // document id's rows as f32 [len][dim] (the stored f16 values converted exactly): its length; writes iff cap_tokens >= it.  Blocking
+    int get_doc(int id, float *rows, int cap_tokens, std::string &err);
+    // ids / scores [nq][k], best first; queries d_q f16 indexed by d_qcu [nq + 1], both in device memory, unchecked (the kernel's
+    // guards).  max_q_len: the caller's promise, 1 .. max_query_tokens().  Asynchronous on s
+    int search_device(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
+                      std::string &err);
+    // host queries (qcu strictly ascending from an entry >= 0, no query longer than max_query_tokens(); rows f32, rounded to f16 on the
+    // device) and host results (written only on success); blocking
+    int search_host(int nq, const int32_t *qcu, const float *q_rows, int k, int32_t *ids, float *scores, std::string &err);
+    // a device search on stream() and its results -> host; blocking
+    int search_device_to_host(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *ids, float *scores, std::string &err);
+    // Per query its n_cand candidates d_cand [nq][n_cand] (ids outside [0, size): no candidate) scored with the search's bits, the best
+    // k to d_ids / d_scores [nq][k].  The workspace grows on demand and is not part of reserve.  Asynchronous on s
+    int rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, int n_cand, const int32_t *d_cand, int k, int32_t *d_ids, float *d_scores,
+                       hipStream_t s, std::string &err);
+    // host queries (checked as search_host's, of any length), candidates (each in [-1, size), -2 otherwise) and results; blocking
+    int rescore_host(int nq, const int32_t *qcu, const float *q_rows, int n_cand, const int32_t *cand, int k, int32_t *ids, float *scores,
+                     std::string &err);
+    // Text routes: device buffers of the index for a chunk's packed token ids | cu_seqlens (in) and, for queries, its f16 rows (out)
+    bool text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err);
+
+private:
+    TokenIndex() = default;
+    bool grow(DevBuf &b, size_t bytes, std::string &err);
+    bool grow_storage(long long n_docs, long long n_tokens, std::string &err);
+    bool grow_search(int n_docs, int nqc, int k, std::string &err);
+    // cu entries of n_docs new documents (lengths from cu, any base) behind the stored ones, on s; bumps the counts
+    bool commit(int n_docs, const int32_t *cu, hipStream_t s, std::string &err);
+    // queries of a host form: rows -> f16 in q16_, lengths (rebased to 0) -> qcu_in_, on stream(); max_len: the longest
+    int stage_queries(const char *what, int nq, const int32_t *qcu, const float *q_rows, int limit, int &max_len, std::string &err);
+
+    Engine *eng_ = nullptr;
+    int dim_ = 0;
+    int n_ = 0, cap_docs_ = 0;                          // documents; capacity of cu_ in documents
+    int64_t n_tok_ = 0, cap_tok_ = 0;                   // rows; capacity of rows_ in rows
+    half_t *rows_ = nullptr;                            // [cap_tok_][dim_]
+    int32_t *cu_ = nullptr;                             // [cap_docs_ + 1]
+    std::vector<int32_t> cu_h_;                         // the host mirror, [n_ + 1]
+    std::vector<int32_t> qcu_h_;                        // host routes: the current call's query lengths, rebased to 0
+    DevBuf ws_s_, ws_i_, pairs_;                        // per-(query, slice) lists, or a rescore's scores and ids; its pair list
+    DevBuf stage_, q16_, qcu_in_, cand_in_, out_ids_, out_scores_;      // host routes: f32 rows in, queries, candidates, results out
+    DevBuf text_in_, text_out_;                         // text routes
+    hipStream_t stream_ = nullptr;                      // the host routes' stream
+    // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
+    hipEvent_t busy_ = nullptr;
+};
+
+// cu [n + 1] ascends strictly from an entry >= 0 (no empty entry)
+bool token_cu_ok(const int32_t *cu, int n);
+
+}  // namespace bert_hip

@@ -1,0 +1,92 @@
+// token_index_kernels.h — the device code of the token index (token_index.hip) as its host side (token_index.cpp) sees it: the stored
+// form, the plan of a scan, the argument blocks and one launcher per kernel.  A launcher only enqueues: the caller reads
+// hipGetLastError.
+//
+// Stored form.  half_t rows[n_tokens][dim], packed, 16-byte aligned (dim a multiple of 8 in 8 .. MAXSIM_MAX_H), and int32
+// cu[n_docs + 1]: document d is rows cu[d] .. cu[d + 1] - 1, never empty — what maxsim.hip takes as its document side, so a rescore
+// hands the index's own arrays to launch_maxsim.
+//
+// A scan workgroup stages one query in LDS as ceil(n / 32) blocks of 32 rows of dim + 8 halfs (maxsim's padding), then a list of L
+// (score, id) entries and a count: token_scan_lds_bytes.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+#include "kernels.h"
+#include "search_kernels.h"
+
+namespace bert_hip {
+
+constexpr int TOKEN_QB = 32;                            // query tokens of a block: the B side of one 32 x 32 MFMA block
+constexpr int TOKEN_MAX_QUERY = 128;                    // the longest query a search takes at any dim
+constexpr int TOKEN_ROUNDS = 16;                        // documents a wave scores between two looks at the list
+constexpr int TOKEN_STEP_DOCS = NWAVE * TOKEN_ROUNDS;   // the most entries a workgroup pushes between two looks
+// a planned slice is at least four documents per wave: long against the query it stages and the k entries it hands to the merge, short
+// enough that 10^5 documents still make TARGET_BLOCKS workgroups (at 64 they made 1562: one and a half rounds of the 1024 a chip holds)
+constexpr int TOKEN_MIN_SLICE_DOCS = 4 * NWAVE;
+constexpr int TOKEN_MAX_SLICES = 4096;                  // the tuning key's range
+constexpr int TOKEN_MAX_CAND = 1024;
+// the dynamic LDS a scan workgroup may ask for: the CU's 160 KiB less a margin for what the compiler allocates statically
+constexpr size_t TOKEN_LDS_MAX = 160 * 1024 - 256;
+
+// entries of the LDS list: the top-k ahead of a queue that takes a step's pushes
+inline int token_list_L(int k) { return k + TOKEN_STEP_DOCS <= 256 ? 256 : 512; }
+inline int token_query_blocks(int n) { return (n + TOKEN_QB - 1) / TOKEN_QB; }
+// 64 (dim + 8) ceil(n / 32) + 8 L + 16 bytes: the query's blocks, the list, the count
+inline size_t token_scan_lds_bytes(int dim, int max_q_len, int k) {
+    return (size_t)token_query_blocks(max_q_len) * TOKEN_QB * (dim + 8) * 2 + (size_t)token_list_L(k) * 8 + 16;
+}
+// the largest multiple of 32, at most TOKEN_MAX_QUERY, whose blocks fit TOKEN_LDS_MAX beside the longest list (dim <= 384: 128,
+// <= 768: 96, <= 1024: 64)
+inline int token_max_query_tokens(int dim) {
+    const size_t block = (size_t)TOKEN_QB * (dim + 8) * 2, room = TOKEN_LDS_MAX - (size_t)512 * 8 - 16;
+    return (int)std::min<size_t>(TOKEN_MAX_QUERY, room / block * TOKEN_QB);
+}
+
+// How a chunk of nq queries over n_docs documents is cut into workgroups of token_index_scan_kernel: one workgroup per (query, slice
+// of slice_docs consecutive documents), TARGET_BLOCKS workgroups aimed for, equal counts per slice (the last takes what is left), no
+// planned slice shorter than TOKEN_MIN_SLICE_DOCS.  pref (the tuning key "token_index_slices", 1 .. TOKEN_MAX_SLICES; 0 = planned):
+// that many slices instead, never more than documents.  An empty index is one empty slice.  The one place this is decided: the search,
+// reserve and the test hook all call it.  (max_slices: what n_slices never exceeds for these nq and pref however n_docs grows up to
+// the n_docs given — the workspace bound)
+struct TokenScanPlan { int n_slices, slice_docs, max_slices; };
+inline bool token_index_plan(int n_docs, int nq, int pref, TokenScanPlan &p) {
+    p = TokenScanPlan{0, 0, 0};
+    if (n_docs < 0 || nq < 1 || pref < 0 || pref > TOKEN_MAX_SLICES) return false;
+    const int aim = pref > 0 ? std::min(pref, std::max(n_docs, 1))
+                             : std::max(1, std::min((TARGET_BLOCKS + nq - 1) / nq, n_docs / TOKEN_MIN_SLICE_DOCS));
+    p.max_slices = aim;
+    p.slice_docs = std::max(1, (int)(((long long)n_docs + aim - 1) / aim));
+    p.n_slices = std::max(1, (int)(((long long)n_docs + p.slice_docs - 1) / p.slice_docs));
+    return true;
+}
+
+// token_index_scan_kernel.  LDS: token_scan_lds_bytes(dim, max_q_len, k)
+struct TokenScanArgs {
+    const half_t *rows;                 // the index
+    const int32_t *cu;                  // [n_docs + 1]
+    const half_t *q;                    // the queries' rows, indexed by qcu
+    const int32_t *qcu;                 // [nq + 1]
+    float *ws_s;                        // [nq][n_slices][k] per-(query, slice) lists, best first
+    int *ws_i;
+    int n_docs, dim, nq, max_q_len, n_slices, slice_docs, k, L, n_items;
+};
+
+// token_index_pairs_kernel: cand [nq][n_cand] -> maxsim's pair list pairs [nq * n_cand][2] = (q, id), and ws_i [nq][n_cand] = id; an
+// id outside [0, n_docs) becomes the pair (q, -1) — which launch_maxsim scores NaN without reading a row — and the id INT_MAX
+struct TokenPairsArgs {
+    const int32_t *cand;
+    int32_t *pairs;
+    int *ws_i;
+    int nq, n_cand, n_docs;
+};
+
+// lets the scan kernel of the current device have TOKEN_LDS_MAX of LDS
+void token_index_kernels_init();
+void launch_token_scan(const TokenScanArgs &a, hipStream_t s);
+void launch_token_pairs(const TokenPairsArgs &a, hipStream_t s);
+
+}  // namespace bert_hip

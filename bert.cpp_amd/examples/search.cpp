@@ -4,7 +4,8 @@
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
-//               [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]
+//               [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N]
+//   bert-search -m MODEL -f TEXTS --late [-k 3] [-t THREADS]
 //   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
 //   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]
 //   (--hybrid SPLADE: hybrid search.  SPLADE is a second model file, one with the MLM head, loaded into a context of its own (it may be
@@ -29,7 +30,13 @@
 //   N <= --rescore's); the query and the N candidate lines go through bert_hip_encode_tokens_batch (token rows, each over its L2
 //   norm, lines cut at the model's position limit), bert_hip_maxsim scores the pairs (query, candidate j) — the sum over the query's
 //   tokens of the best cosine among the candidate's tokens —, and the k lines printed are the best by that score, which is shown;
-//   equal scores keep the first stage's order.)
+//   equal scores keep the first stage's order.  --token-index: the lines' token rows go into a token index while the dense index is
+//   built (bert_hip_token_index_add_texts), and the N candidates are scored by bert_hip_token_index_rescore from the stored rows
+//   instead of being encoded again: only the query goes through the model.  The printed lines and scores are those of --maxsim N alone.
+//   Not together with --long, --sparse, --hybrid, --cross, --save, --load.)
+//   (--late: late-interaction search without a dense stage.  Every line's token rows go into a token index; each query line is answered
+//   by bert_hip_token_index_search_texts, the exact top-k of the MaxSim score over ALL lines.  A query of more tokens than the index's
+//   bert_hip_token_index_max_query_tokens is refused.  With -m, -f, -k and -t only.)
 //   (--long: a line may be longer than the model's position limit: it is cut into overlapping windows of W ids, S inner ids apart,
 //   and embedded as ONE row (bert_hip_index_add_long_texts; W defaults to 128 or the model's limit if that is less, S to three
 //   quarters of W - 2).  Without --long a line is cut at the model's position limit, like a query;
@@ -59,7 +66,8 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N | --cross-model PATH --cross N]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N]\n", argv0);
+    fprintf(stderr, "       %s -m MODEL -f TEXTS --late [-k 3] [-t THREADS]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
     fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]\n", argv0);
     fprintf(stderr, "  --hybrid SPLADE: hybrid search: the lines in an embedding index of DENSE and a sparse index of SPLADE (a model file with the MLM head; W\n"
@@ -72,6 +80,10 @@ void usage(const char *argv0) {
                     "          model's position limit if that is less, S three quarters of W - 2).  Without --long a line is cut at the model's position limit.\n");
     fprintf(stderr, "  --maxsim N: the search returns N candidates (k <= N <= 256), which are reranked by the MaxSim score of their token rows against the\n"
                     "          query's (bert_hip_encode_tokens_batch + bert_hip_maxsim); the k best by that score are printed with it.\n");
+    fprintf(stderr, "  --token-index: with --maxsim N: the lines' token rows are kept in a token index (bert_hip_token_index_add_texts) and the candidates are\n"
+                    "          scored from it (bert_hip_token_index_rescore) instead of being encoded again; the same lines and scores are printed.\n");
+    fprintf(stderr, "  --late: no dense stage: the lines' token rows in a token index, each query answered by bert_hip_token_index_search_texts, the exact\n"
+                    "          top-k by MaxSim score over all lines.  With -m, -f, -k and -t only.\n");
     fprintf(stderr, "  --cross-model PATH --cross N: the search returns N candidates (k <= N <= 256), which a cross-encoder (a model file with a classification\n"
                     "          head) reranks: bert_hip_score_pairs on (query, candidate); the k best by the first label's logit are printed with it.\n");
 }
@@ -87,7 +99,7 @@ int main(int argc, char **argv) {
     float w_dense = 1.f, w_sparse = 1.f;
     bool weights_ok = true;
     int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0, n_cross = 0;
-    bool long_texts = false, maxsim = false, cross = false, sparse = false, sparse_f16 = false;
+    bool long_texts = false, maxsim = false, cross = false, sparse = false, sparse_f16 = false, token_index = false, late = false;
     int sparse_width = 128;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
@@ -118,12 +130,21 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--window") && has_value) window = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--stride") && has_value) stride = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--maxsim") && has_value) { maxsim = true; n_maxsim = atoi(argv[++i]); }
+        else if (!strcmp(argv[i], "--token-index")) token_index = true;
+        else if (!strcmp(argv[i], "--late")) late = true;
         else if (!strcmp(argv[i], "--cross-model") && has_value) cross_model = argv[++i];
         else if (!strcmp(argv[i], "--cross") && has_value) { cross = true; n_cross = atoi(argv[++i]); }
         else { usage(argv[0]); return strcmp(argv[i], "-h") && strcmp(argv[i], "--help") ? 2 : 0; }
     }
     if (!model || !file) { usage(argv[0]); return 2; }
     if (k < 1 || k > 256) { fprintf(stderr, "search: -k must be 1 .. 256\n"); return 2; }
+    for (const char *flag : {token_index ? "--token-index" : nullptr, late ? "--late" : nullptr})
+        if (flag && (long_texts || sparse || hybrid_model || cross || cross_model || save || load)) {
+            fprintf(stderr, "search: %s does not go with --long, --sparse, --hybrid, --cross, --save or --load\n", flag);
+            return 2;
+        }
+    if (token_index && (!maxsim || late)) { fprintf(stderr, "search: --token-index goes with --maxsim N\n"); return 2; }
+    if (late && (maxsim || dtype != 1 || n_cand || n_lists || nprobe || sparse_f16)) { fprintf(stderr, "search: --late goes with -m, -f, -k and -t only\n"); return 2; }
     if (hybrid_model && (sparse || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model || save || load)) {
         fprintf(stderr, "search: --hybrid goes with -m, -f, -k, -t, --sparse-width, --weights, --f32, --i8, --b1 and --f16 only\n");
         return 2;
@@ -279,6 +300,37 @@ int main(int argc, char **argv) {
         bert_free(ctx);                                       // (frees the sparse index as well)
         return 0;
     }
+    if (late) {
+        // the late-interaction mode: the lines' token rows into a token index, each query's token rows against all of them
+        bert_hip_token_index *tx = bert_hip_token_index_create(ctx, 0);
+        if (!tx || bert_hip_token_index_add_texts(tx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+            fprintf(stderr, "search: could not build the token index\n");
+            bert_free(ctx);
+            return 1;
+        }
+        printf("Loaded %zu lines.\n", texts.size());
+        std::vector<int32_t> tids((size_t)k);
+        std::vector<float> tscores((size_t)k);
+        for (;;) {
+            printf("Enter a text to find similar texts (enter 'q' to quit): ");
+            fflush(stdout);
+            std::string q;
+            if (!std::getline(std::cin, q)) break;
+            q = chomp(q);
+            if (q == "q") break;
+            const char *qp = q.c_str();
+            if (bert_hip_token_index_search_texts(tx, n_threads, 1, &qp, k, tids.data(), tscores.data()) != 0) {
+                fprintf(stderr, "search: the search failed\n");
+                bert_free(ctx);
+                return 1;
+            }
+            printf("\nClosest texts:\n");
+            for (int i = 0; i < k && tids[i] >= 0; ++i) printf("%d. %s\n (MaxSim score: %.4f)\n", i + 1, texts[tids[i]].c_str(), tscores[i]);
+        }
+        printf("\n");
+        bert_free(ctx);                                       // (frees the token index as well)
+        return 0;
+    }
     if (long_texts) {
         if (!window) window = bert_n_max_tokens(ctx) < 128 ? bert_n_max_tokens(ctx) : 128;
         if (!stride) stride = 3 * (window - 2) / 4 > 1 ? 3 * (window - 2) / 4 : 1;
@@ -313,6 +365,16 @@ int main(int argc, char **argv) {
         ix = bert_hip_index_create(ctx, 0, dtype);
         if (!ix || add_lines(ix) < 0) {
             fprintf(stderr, "search: could not build the index\n");
+            bert_free(ctx);
+            return 1;
+        }
+    }
+    // --token-index: the lines' token rows, kept for the reranking
+    bert_hip_token_index *tx = nullptr;
+    if (token_index) {
+        tx = bert_hip_token_index_create(ctx, 0);
+        if (!tx || bert_hip_token_index_add_texts(tx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+            fprintf(stderr, "search: could not build the token index\n");
             bert_free(ctx);
             return 1;
         }
@@ -399,13 +461,23 @@ int main(int argc, char **argv) {
             int n_found = 0;
             while (n_found < k && ids[n_found] >= 0) ++n_found;
             std::vector<const char *> lines{qp};
-            for (int j = 0; j < n_found; ++j) lines.push_back(texts[ids[j]].c_str());
+            for (int j = 0; j < n_found && !tx; ++j) lines.push_back(texts[ids[j]].c_str());
             const int32_t n_in = (int32_t)lines.size(), H = bert_n_embd(ctx);
             std::vector<int32_t> cu((size_t)n_in + 1), pairs;
             const int64_t total = bert_hip_encode_tokens_batch(ctx, n_threads, n_in, lines.data(), 1, cu.data(), nullptr, 0);
             std::vector<float> rows(total > 0 ? (size_t)total * H : 0), ms((size_t)n_found);
             bool ok = total > 0 && bert_hip_encode_tokens_batch(ctx, n_threads, n_in, lines.data(), 1, cu.data(), rows.data(), total) == total;
-            if (ok && n_found > 0) {
+            if (ok && n_found > 0 && tx) {
+                // the candidates' scores from the stored rows, all n_found of them, back in the first stage's order
+                std::vector<int32_t> rid((size_t)n_found);
+                std::vector<float> rsc((size_t)n_found);
+                ok = bert_hip_token_index_rescore(tx, 1, cu.data(), rows.data(), n_found, ids.data(), n_found, rid.data(), rsc.data()) == 0;
+                for (int j = 0; ok && j < n_found; ++j) {
+                    const auto at = std::find(rid.begin(), rid.end(), ids[j]);
+                    ok = at != rid.end();
+                    if (ok) ms[j] = rsc[(size_t)(at - rid.begin())];
+                }
+            } else if (ok && n_found > 0) {
                 const int32_t qcu[2] = {0, cu[1]};
                 std::vector<int32_t> dcu((size_t)n_found + 1);
                 for (int j = 0; j <= n_found; ++j) { dcu[j] = cu[j + 1] - cu[1]; if (j < n_found) { pairs.push_back(0); pairs.push_back(j); } }

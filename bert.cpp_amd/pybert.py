@@ -49,6 +49,10 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_sparse_index_search_filtered_device", "bert_hip_sparse_index_rescore", "bert_hip_sparse_index_rescore_device",
     "bert_hip_sparse_index_compact", "bert_hip_sparse_index_save", "bert_hip_sparse_index_load",
     "bert_hip_hybrid_reserve", "bert_hip_hybrid_search", "bert_hip_hybrid_search_device", "bert_hip_hybrid_search_texts",
+    "bert_hip_token_index_create", "bert_hip_token_index_free", "bert_hip_token_index_size", "bert_hip_token_index_n_tokens",
+    "bert_hip_token_index_max_query_tokens", "bert_hip_token_index_reserve", "bert_hip_token_index_add", "bert_hip_token_index_add_device",
+    "bert_hip_token_index_add_texts", "bert_hip_token_index_get_doc", "bert_hip_token_index_search", "bert_hip_token_index_search_device",
+    "bert_hip_token_index_search_texts", "bert_hip_token_index_rescore", "bert_hip_token_index_rescore_device",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -64,7 +68,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
     "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid", "bert_hip_test_sparse_scan_geometry",
     "bert_hip_test_sparse_index_header", "bert_hip_test_sparse_index_body",
-    "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan", "bert_hip_test_hybrid_chunk",
+    "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan", "bert_hip_test_hybrid_chunk", "bert_hip_test_token_index_plan",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -218,6 +222,24 @@ def _declare_product_abi(L):
     L.bert_hip_hybrid_search_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, f32, f32, vp, i32, i32, vp, vp, vp]
     L.bert_hip_hybrid_search_texts.restype = i32
     L.bert_hip_hybrid_search_texts.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_char_p), i32, f32, f32, i32, vp, vp]
+    i64 = C.c_int64
+    L.bert_hip_token_index_create.restype = vp; L.bert_hip_token_index_create.argtypes = [vp, i32]
+    L.bert_hip_token_index_free.restype = None; L.bert_hip_token_index_free.argtypes = [vp]
+    L.bert_hip_token_index_size.restype = i32; L.bert_hip_token_index_size.argtypes = [vp]
+    L.bert_hip_token_index_n_tokens.restype = i64; L.bert_hip_token_index_n_tokens.argtypes = [vp]
+    L.bert_hip_token_index_max_query_tokens.restype = i32; L.bert_hip_token_index_max_query_tokens.argtypes = [vp]
+    L.bert_hip_token_index_reserve.restype = i32; L.bert_hip_token_index_reserve.argtypes = [vp, i32, i64, i32, i32, i32]
+    L.bert_hip_token_index_add.restype = i32; L.bert_hip_token_index_add.argtypes = [vp, i32, vp, vp]
+    L.bert_hip_token_index_add_device.restype = i32; L.bert_hip_token_index_add_device.argtypes = [vp, i32, vp, vp, vp]
+    L.bert_hip_token_index_add_texts.restype = i32; L.bert_hip_token_index_add_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p)]
+    L.bert_hip_token_index_get_doc.restype = i32; L.bert_hip_token_index_get_doc.argtypes = [vp, i32, vp, i32]
+    L.bert_hip_token_index_search.restype = i32; L.bert_hip_token_index_search.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+    L.bert_hip_token_index_search_device.restype = i32; L.bert_hip_token_index_search_device.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp]
+    L.bert_hip_token_index_search_texts.restype = i32
+    L.bert_hip_token_index_search_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, vp, vp]
+    L.bert_hip_token_index_rescore.restype = i32; L.bert_hip_token_index_rescore.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp]
+    L.bert_hip_token_index_rescore_device.restype = i32
+    L.bert_hip_token_index_rescore_device.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp]
 
 
 def lib() -> C.CDLL:
@@ -342,6 +364,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_index_plan.argtypes = [i32, i32, i32, i32p]
     L.bert_hip_test_hybrid_chunk.restype = i32
     L.bert_hip_test_hybrid_chunk.argtypes = [i32, i32, i32, C.POINTER(C.c_int64)]
+    L.bert_hip_test_token_index_plan.restype = i32
+    L.bert_hip_test_token_index_plan.argtypes = [i32, i32, i32, i32p]
     _test_lib = L
     return L
 
@@ -487,6 +511,18 @@ def test_hybrid_chunk(n_rows: int, nq: int, pref: int = 0):
         return None
     if r != 0:
         raise RuntimeError(f"bert_hip_test_hybrid_chunk failed: {r}")
+    return int(out[0]), int(out[1])
+
+
+def test_token_index_plan(n_docs: int, nq: int, pref: int = 0):
+    """How a token index's scan cuts nq queries over n_docs documents (bert_hip_test_token_index_plan; no GPU): (n_slices, slice_docs),
+    or None where the hook refuses.  pref: the value of the tuning key "token_index_slices" (0 = planned)."""
+    out = (C.c_int32 * 2)()
+    r = test_lib().bert_hip_test_token_index_plan(n_docs, nq, pref, out)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_token_index_plan failed: {r}")
     return int(out[0]), int(out[1])
 
 
@@ -1148,6 +1184,11 @@ class BertModel:
         "f32" (i32 ids, f32 weights) | "f16" (u16 ids, f16 weights; n_vocab <= 65536); n_vocab None = the model's."""
         return BertSparseIndex(self, width, dtype, n_vocab)
 
+    def token_index(self, dim: Optional[int] = None) -> "BertTokenIndex":
+        """A token index on the context's first device (bert_hip_token_index_create): documents' f16 token rows, exact MaxSim top-k
+        search; dim None = n_embd."""
+        return BertTokenIndex(self, dim)
+
     def load_index(self, path: str) -> "BertIndex":
         """The index a BertIndex.save wrote (bert_hip_index_load), on this context's first device."""
         return BertIndex(self, _load=path)
@@ -1716,6 +1757,145 @@ class BertSparseIndex:
         if r != 0:
             self._fail("bert_hip_sparse_index_get_rows", r)
         return ids, w
+
+
+class BertTokenIndex:
+    """bert_hip_token_index_*: documents' f16 token rows in HBM, exact MaxSim top-k search.  Documents and queries are (rows [n_tokens,
+    dim] float32, cu [n + 1] int32) as BertModel.encode_tokens returns them.  search* / rescore* return (ids [n, k] int32, scores
+    [n, k] f32), best first; missing entries are id -1, score -inf.  A ValueError is an argument the entry refused (-2).  The *_device
+    forms take device pointers (ints) and a stream handle; search_device and rescore_device return at once."""
+
+    def __init__(self, model: BertModel, dim: Optional[int] = None):
+        self.model, self.lib = model, model.lib
+        self.ix = self.lib.bert_hip_token_index_create(model.ctx, 0 if dim is None else int(dim))
+        if not self.ix:
+            raise RuntimeError("bert_hip_token_index_create failed (see stderr)")
+        self.dim = model.n_embd if dim is None else int(dim)
+
+    def close(self):
+        # (an index the context freed already — bert_free frees its indexes — must not be freed again)
+        if getattr(self, "ix", None) and getattr(self.model, "ctx", None):
+            self.lib.bert_hip_token_index_free(self.ix)
+        self.ix = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return self.size()
+
+    def size(self) -> int:
+        return int(self.lib.bert_hip_token_index_size(self.ix))
+
+    def n_tokens(self) -> int:
+        return int(self.lib.bert_hip_token_index_n_tokens(self.ix))
+
+    def max_query_tokens(self) -> int:
+        return int(self.lib.bert_hip_token_index_max_query_tokens(self.ix))
+
+    @staticmethod
+    def _fail(name: str, r: int):
+        if r == -2:
+            raise ValueError(f"{name} refused its arguments (see stderr)")
+        raise RuntimeError(f"{name} failed: {r}")
+
+    def _packed(self, rows, cu):
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        cu = np.ascontiguousarray(cu, dtype=np.int32).reshape(-1)
+        if rows.ndim != 2 or rows.shape[1] != self.dim or len(cu) < 1:
+            raise ValueError(f"rows must be [n_tokens, {self.dim}] and cu [n + 1]")
+        if len(cu) > 1 and int(cu.max()) > len(rows):
+            raise ValueError("cu names rows beyond the array")
+        return rows, cu
+
+    def reserve(self, n_docs: int, n_tokens: int, n_queries: int = 0, max_q_len: int = 0, k: int = 1) -> None:
+        r = self.lib.bert_hip_token_index_reserve(self.ix, n_docs, n_tokens, n_queries, max_q_len, k)
+        if r != 0:
+            self._fail("bert_hip_token_index_reserve", r)
+
+    def add(self, rows, cu) -> int:
+        """documents (rows [n_tokens, dim] f32, cu [n_docs + 1]); returns the first new id."""
+        rows, cu = self._packed(rows, cu)
+        r = self.lib.bert_hip_token_index_add(self.ix, len(cu) - 1, cu.ctypes.data, rows.ctypes.data)
+        if r < 0:
+            self._fail("bert_hip_token_index_add", r)
+        return r
+
+    def add_device(self, cu, d_rows_ptr: int, stream: int = 0) -> int:
+        """cu [n_docs + 1] on the HOST, d_rows_ptr f16 rows in device memory indexed by cu."""
+        cu = np.ascontiguousarray(cu, dtype=np.int32).reshape(-1)
+        r = self.lib.bert_hip_token_index_add_device(self.ix, len(cu) - 1, cu.ctypes.data, d_rows_ptr, stream)
+        if r < 0:
+            self._fail("bert_hip_token_index_add_device", r)
+        return r
+
+    def add_texts(self, texts: Sequence, n_threads: int = 6) -> int:
+        n = len(texts)
+        txt = (C.c_char_p * max(n, 1))(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        r = self.lib.bert_hip_token_index_add_texts(self.ix, n_threads, n, txt)
+        if r < 0:
+            self._fail("bert_hip_token_index_add_texts", r)
+        return r
+
+    def get_doc(self, doc_id: int) -> np.ndarray:
+        """The stored rows of a document, [length, dim] float32 (the f16 values converted exactly)."""
+        n = self.lib.bert_hip_token_index_get_doc(self.ix, doc_id, None, 0)
+        if n < 0:
+            self._fail("bert_hip_token_index_get_doc", n)
+        rows = np.full((n, self.dim), np.nan, dtype=np.float32)
+        if self.lib.bert_hip_token_index_get_doc(self.ix, doc_id, rows.ctypes.data, n) != n:
+            raise RuntimeError("bert_hip_token_index_get_doc failed")
+        return rows
+
+    def search(self, q_rows, q_cu, k: int = 10):
+        q, qcu = self._packed(q_rows, q_cu)
+        nq = len(qcu) - 1
+        ids = np.empty((nq, max(k, 1)), dtype=np.int32)
+        scores = np.empty((nq, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_token_index_search(self.ix, nq, qcu.ctypes.data, q.ctypes.data, k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_token_index_search", r)
+        return ids, scores
+
+    def search_device(self, n_queries: int, d_qcu_ptr: int, d_q_ptr: int, max_q_len: int, k: int, d_ids_ptr: int, d_scores_ptr: int,
+                      stream: int = 0) -> None:
+        r = self.lib.bert_hip_token_index_search_device(self.ix, n_queries, d_qcu_ptr, d_q_ptr, max_q_len, k, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            self._fail("bert_hip_token_index_search_device", r)
+
+    def search_texts(self, texts: Sequence, k: int = 10, n_threads: int = 6):
+        n = len(texts)
+        txt = (C.c_char_p * max(n, 1))(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        ids = np.empty((n, max(k, 1)), dtype=np.int32)
+        scores = np.empty((n, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_token_index_search_texts(self.ix, n_threads, n, txt, k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_token_index_search_texts", r)
+        return ids, scores
+
+    def rescore(self, q_rows, q_cu, cand_ids, k: int = 10):
+        """bert_hip_token_index_rescore: per query its candidate documents cand_ids [n, n_cand] (-1 = none) scored with the search's
+        bits, the best k of them."""
+        q, qcu = self._packed(q_rows, q_cu)
+        nq = len(qcu) - 1
+        cand = np.ascontiguousarray(cand_ids, dtype=np.int32).reshape(max(nq, 1), -1)
+        ids = np.empty((nq, max(k, 1)), dtype=np.int32)
+        scores = np.empty((nq, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_token_index_rescore(self.ix, nq, qcu.ctypes.data, q.ctypes.data, cand.shape[1], cand.ctypes.data, k,
+                                                  ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_token_index_rescore", r)
+        return ids, scores
+
+    def rescore_device(self, n_queries: int, d_qcu_ptr: int, d_q_ptr: int, n_cand: int, d_cand_ptr: int, k: int, d_ids_ptr: int,
+                       d_scores_ptr: int, stream: int = 0) -> None:
+        r = self.lib.bert_hip_token_index_rescore_device(self.ix, n_queries, d_qcu_ptr, d_q_ptr, n_cand, d_cand_ptr, k, d_ids_ptr, d_scores_ptr,
+                                                         stream)
+        if r != 0:
+            self._fail("bert_hip_token_index_rescore_device", r)
 
 
 def test_gemm(A: np.ndarray, W_bytes: np.ndarray, wtype: int, N: int, bias: np.ndarray,

@@ -187,7 +187,9 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  * pinned memory instead of the copy engine), "sparse_index_qb" = n (tuning: queries per workgroup tile of the sparse index's scan, 1 .. 8;
  * "0" = the built-in choice; a result's bits do not depend on it; set it before bert_hip_sparse_index_reserve), "hybrid_chunk_queries" = n (tuning: queries
  * per internal chunk of a hybrid search, 1 .. 4096, never more than the score workspace's bound allows; "0" = what that bound gives; a
- * result's bits do not depend on it), "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"
+ * result's bits do not depend on it), "token_index_slices" = n (tuning: slices of documents a token index's scan is cut into, 1 .. 4096,
+ * never more than documents; "0" = planned; a result's bits do not depend on it; set it before bert_hip_token_index_reserve),
+ * "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"
  * (BERT_HIP_POOLING / BERT_HIP_NORMALIZE above; bert_hip_pooling / bert_hip_normalize return what is in force).                       */
 BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const char *value);
 
@@ -819,6 +821,90 @@ BERT_API int32_t bert_hip_hybrid_search_device(struct bert_hip_index *dense, str
 BERT_API int32_t bert_hip_hybrid_search_texts(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse, int32_t n_threads,
                                               int32_t n_queries, const char **texts, int32_t kq, float w_dense, float w_sparse, int32_t k,
                                               int32_t *ids, float *scores);
+
+/* TOKEN INDEX: documents' f16 token rows in HBM on the context's FIRST device (bert_hip_device), exact top-k search by late
+ * interaction — over ALL stored documents d, the k largest  score(q, d) = sum over the query's tokens i of ( max over the document's
+ * tokens j of <Q_i, D_j> )  (ColBERT-style retrieval).  The consumer of bert_hip_eval_packed_tokens[_device] and
+ * bert_hip_encode_tokens_batch, and the index form of bert_hip_maxsim[_device] ("token rows and late interaction" above).  An index
+ * belongs to the context it was made from: bert_free frees any token index the caller left alive.  Like every entry point of a
+ * context, these functions are not re-entrant on one context.
+ *   create   dim: 0 = bert_n_embd(ctx), else a multiple of 8 in 8 .. 1024.  Memory: 2 dim bytes per token and 4 bytes per document.
+ *            NULL + a line on stderr on error (tokenizer-only context, no device, bad dim).
+ *   documents and queries   packed rows [n_tokens][dim] with cumulative lengths cu [n + 1], as bert_hip_encode_tokens_batch writes
+ *            them: entry i is rows cu[i] .. cu[i + 1] - 1.  cu ascends strictly from cu[0] >= 0 (every entry has at least one token);
+ *            the rows in front of cu[0] are not read.  The total token count of an index stays below 2^31.
+ *   add      appends n_docs documents; they get ids size, size + 1, ...; returns the first new id, negative on error.  Everything is
+ *            validated first: -2 leaves the index unchanged.  add: cu and f32 rows in host memory, uploaded and rounded to f16 (nearest
+ *            even) on the device.  add_device: cu in HOST memory, d_rows f16 in device memory (16-byte aligned), indexed by cu, copied
+ *            on `stream`.  add_texts: below.  The add forms take host lengths and may grow storage: they are NOT for stream capture.
+ *   get_doc  returns document id's length in tokens; iff cap_tokens >= it, rows [length][dim] receives the stored f16 values converted
+ *            exactly.  An id outside [0, size): -2.  Blocking.
+ *   search   ids [n_queries][k] and scores [n_queries][k], best first; 0 on success, negative on error (outputs untouched).  search:
+ *            qcu and f32 rows in host memory (rounded to f16 on the device), blocking.  search_device: d_qcu, d_q (f16, 16-byte aligned)
+ *            and the results in device memory, asynchronous on `stream`.
+ *   rescore  per query q its n_cand candidates cand_ids[q][0 .. n_cand) scored with the search's bits, the best k of them in the
+ *            search's order.  1 <= n_cand <= 1024; an id of -1 is skipped; a repeated id counts as that many candidates; k may exceed
+ *            n_cand (-1 / -INFINITY slots).  The host form refuses any id below -1 or at or beyond size (-2); the device form treats
+ *            it as no candidate.  d_cand_ids is exactly what bert_hip_index_search_device writes: pass a dense search's d_ids on the
+ *            same stream and its candidates are rescored without leaving the device.  A query may have any length here (no LDS limit:
+ *            rescore runs bert_hip_maxsim_device's kernel on the index's rows).  The workspace [n_queries][n_cand] grows on demand
+ *            and is not part of reserve: call once at the largest shape before a capture.
+ *   reserve  sizes the storage for n_docs documents of n_tokens tokens in all and the search workspace for up to n_queries queries of up
+ *            to max_q_len tokens with any k' <= k now, so that search_device within those bounds never allocates.
+ *   max_query_tokens   the longest query a SEARCH accepts at this dim (below).
+ * Semantics:
+ *   - Score.  score(q, d) is the value bert_hip_maxsim_device gives the pair in mode 0 (sum) on the same f16 rows: every inner product
+ *     is the f16 chain of the embedding index (f32 accumulation, k ascending, the document block as the A operand); the max is exact;
+ *     the query tokens go in blocks of 32, a block's 32 maxima are added in the fixed butterfly order of a wavefront sum with +0 in the
+ *     unused lanes, and the blocks' sums are added in ascending order from +0.  Equality is == on floats; for every non-zero score it is
+ *     equality of bits; the sign of a zero is not promised.  Masking is maxsim's: a document slot behind the document's end enters
+ *     the max as -inf, a query slot behind the query's end adds +0, rows outside the pair's two ranges are never read.
+ *   - Order and slots: the indexes' rules.  Larger score first, equal scores (==) smaller id first; a NaN score is never returned; slots
+ *     beyond the documents that can be returned are id -1 / score -INFINITY.  1 <= k <= 256; n_queries == 0 is a successful no-op; an
+ *     empty index is valid; large n_queries run in internal chunks.
+ *   - Determinism.  A (query, document) score and a query's result do not depend on the other queries of the call, the number of add
+ *     calls that built the index, reserved or grown storage, how the scan is cut into workgroups (the tuning key "token_index_slices"),
+ *     k (top-10 is the first 10 of top-100), the host or device entry point, or search against rescore.
+ *   - Query length of a search.  The scan stages the whole query in LDS, ceil(n / 32) blocks of 32 (dim + 8) halfs; max_query_tokens
+ *     is the largest multiple of 32, at most 128, whose blocks fit the LDS the kernel allows itself: 128 up to dim 384, 96 up to 768,
+ *     64 up to 1024.  The host forms refuse a longer query (-2).  max_q_len of search_device (1 .. max_query_tokens) is a promise that
+ *     sizes the launch's LDS, as bert_hip_eval_packed_device's max_len is one: a query that is longer than max_q_len, or empty, or
+ *     whose d_qcu entries descend or start below 0, gets k slots of -1 / -INFINITY, its neighbours untouched.
+ *   - Texts.  add_texts and search_texts tokenize as bert_encode_batch does, with the same truncation, and run the token-rows pass
+ *     with flags 1 | 2 (each row over its L2 norm, f16) in chunks of BERT_HIP_CHUNK_TOKENS: add_texts writes straight into the index's
+ *     storage, search_texts a device buffer the scan reads in place.  The stored bits are those of bert_hip_encode_tokens_batch
+ *     (flags = 1) rounded to f16.  dim must equal n_embd (-2 otherwise); a query text of more than max_query_tokens tokens: -2.
+ *   - Streams.  search_device and rescore_device are asynchronous on the caller's stream; an index has ONE event, so its eagerly
+ *     enqueued operations never overlap, whatever streams they were enqueued on.  Within the bounds of reserve (and, for rescore, where
+ *     a call of the same shape has run before) they allocate nothing and may be captured into a graph: STREAM CAPTURE AND GRAPHS above.
+ * Results: -1 without an index; -2 after a line on stderr for an argument the entry refuses; -3 on a device error; -4 for an exception.
+ * Outputs are untouched on error.
+ * Not covered: removing documents, allow-lists, compaction and files; several GPUs; several queries per workgroup sharing document
+ * loads; residual or quantised token rows; a mean mode.                                                                             */
+struct bert_hip_token_index;
+BERT_API struct bert_hip_token_index *bert_hip_token_index_create(struct bert_ctx *ctx, int32_t dim);
+BERT_API void    bert_hip_token_index_free(struct bert_hip_token_index *ix);
+BERT_API int32_t bert_hip_token_index_size(struct bert_hip_token_index *ix);
+BERT_API int64_t bert_hip_token_index_n_tokens(struct bert_hip_token_index *ix);
+BERT_API int32_t bert_hip_token_index_max_query_tokens(struct bert_hip_token_index *ix);
+BERT_API int32_t bert_hip_token_index_reserve(struct bert_hip_token_index *ix, int32_t n_docs, int64_t n_tokens, int32_t n_queries,
+                                              int32_t max_q_len, int32_t k);
+BERT_API int32_t bert_hip_token_index_add(struct bert_hip_token_index *ix, int32_t n_docs, const int32_t *cu, const float *rows);
+BERT_API int32_t bert_hip_token_index_add_device(struct bert_hip_token_index *ix, int32_t n_docs, const int32_t *cu, const void *d_rows,
+                                                 void *stream);
+BERT_API int32_t bert_hip_token_index_add_texts(struct bert_hip_token_index *ix, int32_t n_threads, int32_t n, const char **texts);
+BERT_API int32_t bert_hip_token_index_get_doc(struct bert_hip_token_index *ix, int32_t id, float *rows, int32_t cap_tokens);
+BERT_API int32_t bert_hip_token_index_search(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *qcu, const float *q_rows,
+                                             int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_token_index_search_device(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *d_qcu, const void *d_q,
+                                                    int32_t max_q_len, int32_t k, int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_token_index_search_texts(struct bert_hip_token_index *ix, int32_t n_threads, int32_t n_queries, const char **texts,
+                                                   int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_token_index_rescore(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *qcu, const float *q_rows,
+                                              int32_t n_cand, const int32_t *cand_ids, int32_t k, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_token_index_rescore_device(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *d_qcu, const void *d_q,
+                                                     int32_t n_cand, const int32_t *d_cand_ids, int32_t k, int32_t *d_ids, float *d_scores,
+                                                     void *stream);
 
 BERT_API const char *bert_hip_version(void);
 

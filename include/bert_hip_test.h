@@ -303,6 +303,12 @@ BERT_API int32_t bert_hip_test_sparse_index_body(const uint32_t *fields, const v
  * 64).  pref: the value of the tuning key "hybrid_chunk_queries" (0 = unset).  0; -2 and zeros for n_rows < 0, nq < 1 or pref < 0; -1
  * for a NULL out.                                                                                                                  */
 BERT_API int32_t bert_hip_test_hybrid_chunk(int32_t n_rows, int32_t nq, int32_t pref, int64_t *out);
+/* How a token index's scan cuts a chunk of nq queries over n_docs documents (token_index_kernels.h token_index_plan, the function the
+ * search itself calls; no GPU): plan = {n_slices, slice_docs} — slice s is documents s slice_docs .. min(n_docs, (s + 1) slice_docs) - 1,
+ * one workgroup per (query, slice); an empty index is one empty slice.  pref: the value of the tuning key "token_index_slices" (0 =
+ * planned; 1 .. 4096 = that many slices, never more than documents).  0; -2 and zeros for n_docs < 0, nq < 1 or pref outside 0 .. 4096;
+ * -1 for a NULL plan.                                                                                                              */
+BERT_API int32_t bert_hip_test_token_index_plan(int32_t n_docs, int32_t nq, int32_t pref, int32_t *plan);
 
 #ifdef __cplusplus
 }
