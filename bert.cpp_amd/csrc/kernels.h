@@ -189,19 +189,27 @@ void launch_group_pool(const float *rows, const int32_t *cu_seqlens, const int32
 // by its own L2 norm (f32 sum of squares, a lane's elements in ascending order, then wave_sum_f32; 1 / sqrtf, no epsilon); bit 1
 // (TOKEN_ROWS_F16): out is f16 (rounded to nearest even), else f32.  Without bit 0 the f32 output is the stored state exactly.  The
 // tokens of a sentence whose length is not in [1, max_len] get NaN rows (the pooling launch sets the status word for it).  Any H >= 1.
-constexpr int TOKEN_ROWS_NORMALIZE = 1, TOKEN_ROWS_F16 = 2;
+// One launch of a 256-thread workgroup per four tokens: T <= TOKEN_ROWS_MAX_T keeps it at 2^31 threads (the host forms cut their
+// passes at "chunk_tokens" and tokenized calls hold fewer tokens than that; bert_hip_eval_packed_tokens_device refuses more).
+constexpr int TOKEN_ROWS_NORMALIZE = 1, TOKEN_ROWS_F16 = 2, TOKEN_ROWS_MAX_T = 1 << 25;
 void launch_token_rows(const void *x, bool x_is_f32, int T, int H, const int32_t *cu_seqlens, int n_sentences, int max_len, int flags,
                        void *out, hipStream_t stream);
 
 // MaxSim (maxsim.hip): q [.][H], d [.][H] packed f16 token rows, 16-byte aligned, H % 8 == 0, 8 <= H <= MAXSIM_MAX_H; qcu [n_q + 1],
 // dcu [n_d + 1] cumulative lengths; pairs null: all pairs, scores [n_q][n_d]; else [n_pairs][2] of (a, b), scores [n_pairs].
 // mode bit 0: the mean over the query tokens instead of the sum.  Everything in device memory.
+// One workgroup of 256 threads serves one pair, and a launch of 2^32 threads or more is not run as asked: launch_maxsim cuts the pairs
+// into launches of at most MAXSIM_LAUNCH_PAIRS (256 threads each: 2^31 threads), `first` being a launch's first pair (the launcher's
+// field: callers leave it 0).  launch_pairs (the tuning key "maxsim_launch_pairs"): fewer pairs per launch, 1 .. MAXSIM_LAUNCH_PAIRS;
+// 0 = that bound.  A pair's bits depend on its own rows alone, so no result depends on the cut.
 constexpr int MAXSIM_MAX_H = 1024;
+constexpr int MAXSIM_LAUNCH_PAIRS = 1 << 23;
 struct MaxsimArgs {
     const half_t *q, *d;
     const int32_t *qcu, *dcu, *pairs;
     float *scores;
     int n_q, n_d, H, n_pairs, mode;
+    long long first;
 };
 size_t maxsim_lds_bytes(int H);
 // The classification head (cls_head.hip; bert_hip.h "sentence pairs and scores"): rows f32 [B][H], the sentences' POOL_CLS | POOL_RAW rows
@@ -256,8 +264,10 @@ bool launch_sparse_vocab_f32(const SparseVocabArgs &a, hipStream_t stream);
 // first; ids [n][k] (-1 in unused places), weights [n][k] (+0 there).  1 <= k <= SPARSE_MAX_K, V < 2^24.  One workgroup per row.
 constexpr int SPARSE_MAX_K = 256;
 bool launch_sparse_topk(const float *w, int n, int V, int k, int32_t *ids, float *weights, hipStream_t stream);
-void launch_maxsim(const MaxsimArgs &a, hipStream_t stream);
-// n f32 values -> f16, rounded to nearest even (the host form of MaxSim rounds its rows on the device)
+void launch_maxsim(const MaxsimArgs &a, hipStream_t stream, int launch_pairs = 0);
+// n f32 values -> f16, rounded to nearest even (the host form of MaxSim rounds its rows on the device).  One thread per value in one
+// launch: n <= F32_TO_F16_MAX_N (2^31 threads), which the callers see to
+constexpr size_t F32_TO_F16_MAX_N = (size_t)1 << 31;
 void launch_f32_to_f16(const float *src, half_t *dst, size_t n, hipStream_t stream);
 
 // The > 64 KiB dynamic-LDS opt-in (hipFuncSetAttribute) is per device: `seen` is the launcher's per-kernel record.  The

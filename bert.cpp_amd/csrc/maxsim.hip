@@ -23,6 +23,7 @@
 //   f32_to_f16_kernel  the host form's rows, rounded to nearest even.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 
 #include "device.h"
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(MS_NT) void maxsim_kernel(MaxsimArgs a) {
     half_t *qs = (half_t *)ms_lds;                             // [MS_QB][ldq]
     float *wmax = (float *)(ms_lds + (size_t)MS_QB * ldq * 2); // [MS_WAVES][32]
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, col = lane & 31, h = lane >> 5;
-    const long long p = blockIdx.x;
+    const long long p = a.first + blockIdx.x;
     int pa, pb;
     if (a.pairs) { pa = a.pairs[2 * p]; pb = a.pairs[2 * p + 1]; }
     else { pa = (int)(p / a.n_d); pb = (int)(p - (long long)pa * a.n_d); }
@@ -114,16 +115,20 @@ DeviceFlags g_maxsim_configured;
 
 size_t maxsim_lds_bytes(int H) { return (size_t)MS_QB * (H + 8) * 2 + MS_WAVES * 32 * sizeof(float); }
 
-void launch_maxsim(const MaxsimArgs &a, hipStream_t s) {
+void launch_maxsim(const MaxsimArgs &a, hipStream_t s, int launch_pairs) {
     const long long n = a.pairs ? a.n_pairs : (long long)a.n_q * a.n_d;
     if (n <= 0) return;
+    // (a grid of 2^32 threads or more is not run as asked: at most 2^31 per launch)
+    const long long per = launch_pairs >= 1 && launch_pairs < MAXSIM_LAUNCH_PAIRS ? launch_pairs : MAXSIM_LAUNCH_PAIRS;
     // (H = 1024 needs 66 560 bytes: past the 64 KiB a kernel gets without asking)
     configure_once(g_maxsim_configured, [] { (void)hipFuncSetAttribute((const void *)maxsim_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxsim_lds_bytes(MAXSIM_MAX_H)); });
-    BERT_LAUNCH(maxsim_kernel, dim3((unsigned)n), dim3(MS_NT), maxsim_lds_bytes(a.H), s, a);
+    MaxsimArgs part = a;
+    for (part.first = 0; part.first < n; part.first += per)
+        BERT_LAUNCH(maxsim_kernel, dim3((unsigned)std::min(per, n - part.first)), dim3(MS_NT), maxsim_lds_bytes(a.H), s, part);
 }
 
 void launch_f32_to_f16(const float *src, half_t *dst, size_t n, hipStream_t s) {
-    if (!n) return;
+    if (!n) return;                                            // (n <= F32_TO_F16_MAX_N: kernels.h)
     BERT_LAUNCH(f32_to_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, n);
 }
 

@@ -26,6 +26,7 @@ struct EngineOptions {
     int sparse_index_qb = 0;          // tuning (a key only): queries per tile of the sparse index's scan, 1 .. 8; 0 = the table of sparse_index_kernels.h
     int hybrid_chunk_queries = 0;     // tuning (a key only): queries per chunk of a hybrid search, 1 .. 4096; 0 = what the score workspace's bound gives (sparse_index_kernels.h)
     int token_index_slices = 0;       // tuning (a key only): slices of documents of a token index's scan, 1 .. 4096; 0 = planned (token_index_kernels.h)
+    int maxsim_launch_pairs = 0;      // tuning (a key only): pairs per launch of MaxSim's kernel, 1 .. 2^23 (a larger value is clamped to that bound); 0 = the bound (kernels.h)
     bool stage_kernel = true;       // small staged blocks come in by a kernel that reads the mapped pinned block, not by the copy engine
     // How a pass ends (bert_hip.h): the mean over a sentence's tokens or the state of its first token ([CLS]), divided by its L2
     // norm or not.  A pass reads both once, at its start (pool_mode()).

@@ -175,7 +175,8 @@ int TokenIndex::add_host(int n_docs, const int32_t *cu, const float *rows, std::
     DeviceGuard g(eng_->device());
     const long long T = (long long)cu[n_docs] - cu[0];
     if (!grow_storage((long long)n_ + n_docs, n_tok_ + T, err)) return -3;
-    // through a staging buffer of at most 32 MiB (a row's stored bits do not depend on the parts it came in)
+    // through a staging buffer of at most 32 MiB (a row's stored bits do not depend on the parts it came in; a part is at most 2^23
+    // values or one row: far below F32_TO_F16_MAX_N)
     const long long per = std::max<long long>(1, ((long long)32 << 20) / ((long long)dim_ * 4));
     if (!grow(stage_, (size_t)std::min(per, T) * dim_ * 4, err)) return -3;
     Engine::StreamOp op;
@@ -290,6 +291,7 @@ int TokenIndex::stage_queries(const char *what, int nq, const int32_t *qcu, cons
         return -2;
     }
     const size_t T = (size_t)(qcu[nq] - qcu[0]), n = T * dim_;
+    if (n > F32_TO_F16_MAX_N) { err = std::string(what) + ": more than 2^31 query values (tokens x dim) in one call"; return -2; }
     if (!grow(stage_, n * 4, err) || !grow(q16_, n * 2, err) || !grow(qcu_in_, (size_t)(nq + 1) * 4, err)) return -3;
     // (the previous host call has synchronised stream(): nothing reads the staged lengths any more)
     qcu_h_.resize((size_t)nq + 1);
@@ -327,8 +329,8 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
         TokenPairsArgs pa{d_cand + (size_t)c0 * n_cand, pairs_.as<int32_t>(), ws_i_.as<int>(), c, n_cand, n_};
         eng_->timed_launch("token_index_pairs", 0.0, s, [&] { launch_token_pairs(pa, s); });
         // (the index's own arrays are maxsim's document side; a pair (q, -1) is scored NaN and reads nothing)
-        MaxsimArgs ma{d_q, rows_, d_qcu + c0, cu_, pairs_.as<int32_t>(), ws_s_.as<float>(), c, n_, dim_, c * n_cand, 0};
-        eng_->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(ma, s); });
+        MaxsimArgs ma{d_q, rows_, d_qcu + c0, cu_, pairs_.as<int32_t>(), ws_s_.as<float>(), c, n_, dim_, c * n_cand, 0, 0};
+        eng_->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(ma, s, eng_->options().maxsim_launch_pairs); });
         MergeArgs m;
         m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
         m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;

@@ -160,6 +160,7 @@ void launch_token_scan(const TokenScanArgs &a, hipStream_t s) {
 }
 
 void launch_token_pairs(const TokenPairsArgs &a, hipStream_t s) {
+    // (nq <= TokenIndex::QCHUNK = 256 and n_cand <= TOKEN_MAX_CAND = 1024: at most 2^18 threads)
     const size_t n = (size_t)a.nq * a.n_cand;
     if (!n) return;
     BERT_LAUNCH(token_index_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);

@@ -66,6 +66,8 @@ int32_t bert_hip_eval_packed_tokens_device(struct bert_ctx *ctx, const bert_voca
             fprintf(stderr, "%s: max_len = %d cannot hold %d tokens in %d sentences\n", me, max_len, n_tokens_total, n_sentences);
             return -2;
         }
+        // (launch_token_rows: a workgroup of 256 threads per four tokens in one launch, which holds fewer than 2^32 threads)
+        if (n_tokens_total > TOKEN_ROWS_MAX_T) { fprintf(stderr, "%s: more than 2^25 tokens in one call\n", me); return -2; }
         if ((flags & ~3) || (n_sentences > 0 && n_tokens_total > 0 && (!d_rows || !d_tokens || !d_cu_seqlens))) {
             fprintf(stderr, "%s: flags 0 .. 3 and tokens, cu_seqlens, rows required\n", me);
             return -2;
@@ -135,14 +137,15 @@ int32_t bert_hip_maxsim_device(struct bert_ctx *ctx, const void *d_q, const int3
         if (((uintptr_t)d_q | (uintptr_t)d_d) & 15) { fprintf(stderr, "%s: the rows must be 16-byte aligned\n", me); return -2; }
         Engine *e = ctx->engine();
         if (hipSetDevice(e->device()) != hipSuccess) { fprintf(stderr, "%s: hipSetDevice failed\n", me); return -3; }
-        MaxsimArgs a{(const half_t *)d_q, (const half_t *)d_d, d_qcu, d_dcu, d_pairs, d_scores, n_q, n_d, H, d_pairs ? n_pairs : 0, mode};
+        MaxsimArgs a{(const half_t *)d_q, (const half_t *)d_d, d_qcu, d_dcu, d_pairs, d_scores, n_q, n_d, H, d_pairs ? n_pairs : 0, mode, 0};
         const hipStream_t s = (hipStream_t)stream;
         // (no workspace, so no event: the call only asks whether s may take the launch — not a capturing stream while the context profiles)
         Engine::StreamOp op;
         std::string err;
         if (!e->op_begin(s, nullptr, op, err)) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return -3; }
         // (flops: unknown without the lengths, which live on the device)
-        e->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(a, s); });
+        // (more than MAXSIM_LAUNCH_PAIRS pairs go in several launches, which the profiler does not take as a sample: profiler.h)
+        e->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(a, s, e->options().maxsim_launch_pairs); });
         if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: the launch failed\n", me); return -3; }
         return 0;
     }, (int32_t)-4);
@@ -166,6 +169,8 @@ int32_t bert_hip_maxsim(struct bert_ctx *ctx, const float *q, const int32_t *qcu
         auto fail = [&](const char *what) { fprintf(stderr, "%s: %s\n", me, what ? what : err.c_str()); (void)hipStreamSynchronize(s); return (int32_t)-3; };
         if (hipSetDevice(e->device()) != hipSuccess) return fail("hipSetDevice failed");
         const size_t nqt = (size_t)qcu[n_q], ndt = (size_t)dcu[n_d], n_out = pairs ? (size_t)n_pairs : (size_t)n_q * n_d;
+        // (launch_f32_to_f16 rounds a set in one launch of a thread per value)
+        if (nqt * H > F32_TO_F16_MAX_N || ndt * H > F32_TO_F16_MAX_N) { fprintf(stderr, "%s: a set of more than 2^31 values (tokens x H)\n", me); return -2; }
         DevBuf q32, d32, q16, d16, cu, pr, out;
         // one upload for qcu | dcu | pairs
         std::vector<int32_t> in(qcu, qcu + n_q + 1);

@@ -189,6 +189,8 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  * per internal chunk of a hybrid search, 1 .. 4096, never more than the score workspace's bound allows; "0" = what that bound gives; a
  * result's bits do not depend on it), "token_index_slices" = n (tuning: slices of documents a token index's scan is cut into, 1 .. 4096,
  * never more than documents; "0" = planned; a result's bits do not depend on it; set it before bert_hip_token_index_reserve),
+ * "maxsim_launch_pairs" = n (tuning and tests: pairs per launch of MaxSim's kernel, which bert_hip_maxsim[_device] and a token index's
+ * rescore enqueue, 1 .. 8388608 = 2^23; a larger value is clamped to 2^23, "0" = 2^23; a result's bits do not depend on it),
  * "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"
  * (BERT_HIP_POOLING / BERT_HIP_NORMALIZE above; bert_hip_pooling / bert_hip_normalize return what is in force).                       */
 BERT_API void bert_hip_set_option(struct bert_ctx *ctx, const char *key, const char *value);
@@ -307,6 +309,12 @@ BERT_API int32_t bert_hip_encode_long_batch(struct bert_ctx *ctx, int32_t n_thre
  *                   nothing; listed as "maxsim" by bert_hip_profile_report.  The lengths and pairs are checked on the device: a pair
  *                   whose index lies outside [0, n_q) x [0, n_d), or one of whose sentences is empty, descends in its cu entries or
  *                   starts below 0, gets a NaN score; its neighbours are untouched.  -2 for a bad H, count or pointer.
+ *   Limits.         n_pairs < 2^31 with a pair list, n_q n_d < 2^31 without, and every one of those pairs is scored: one workgroup
+ *                   serves one pair, and a call of more than 2^23 pairs is enqueued as several launches of at most 2^23 (one kernel
+ *                   node each in a captured graph, and no sample of bert_hip_profile_report, which times single launches; the tuning
+ *                   key "maxsim_launch_pairs" lowers that number).  The host form takes sets
+ *                   of at most 2^31 values (tokens x H) each, -2 beyond; bert_hip_eval_packed_tokens_device at most 2^25 tokens, -2
+ *                   beyond.
  *   maxsim          host buffers, blocking: f32 rows, uploaded and rounded to f16 (nearest even) on the device, then maxsim_device.
  *                   Everything is validated first — cu entries strictly ascending from an entry >= 0, every pair in range —: -2 after a
  *                   line on stderr with the scores untouched.  -1 without a device, -3 on a device error.                          */

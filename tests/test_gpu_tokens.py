@@ -309,6 +309,153 @@ def test_maxsim_error_cases(ms_model):
 
 
 # ------------------------------------------------------------------------------------------------
+# MaxSim in several launches: one workgroup per pair, at most 2^23 pairs (2^31 threads) per launch; the tuning key
+# "maxsim_launch_pairs" lowers that, so the launch edges are reached at small shapes.  A pair's bits depend on its own rows alone:
+# every result under the key at 7 equals the one at 0 bit for bit.
+# ------------------------------------------------------------------------------------------------
+LAUNCH_PAIRS = 7
+PREFILL = 0x7FC12345                     # a NaN no kernel writes (maxsim's own NaN is 0x7FC00000)
+
+
+def _launch_sets(H=24):
+    rng = np.random.default_rng(31)
+    q, qcu, _ = mr.packed_set(rng, [1, 31, 33, 32, 130], H)
+    d, dcu, _ = mr.packed_set(rng, [33, 1, 129], H)
+    return q, qcu, d, dcu
+
+
+def _with_key(m, value, fn):
+    m.set_option("maxsim_launch_pairs", str(value))
+    try:
+        return fn()
+    finally:
+        m.set_option("maxsim_launch_pairs", "0")
+
+
+def _device_maxsim_prefilled(m, q16, qcu, d16, dcu, pairs, n_out, extra, mean=False, stream=0, hip=None):
+    """bert_hip_maxsim_device into a buffer of n_out + extra words, all PREFILL before: (the n_out scores, the bits of the words behind)"""
+    from hip_graph import Hip
+    hip = hip or Hip()
+    n_q, n_d = len(qcu) - 1, len(dcu) - 1
+    ptrs = [hip.upload(q16), hip.upload(np.asarray(qcu, np.int32)), hip.upload(d16), hip.upload(np.asarray(dcu, np.int32)),
+            hip.upload(np.full(n_out + extra, PREFILL, np.uint32))]
+    d_pairs = hip.upload(np.asarray(pairs, np.int32)) if pairs is not None else None
+    m.maxsim_device(ptrs[0], ptrs[1], n_q, ptrs[2], ptrs[3], n_d, q16.shape[1], d_pairs, 0 if pairs is None else len(pairs), ptrs[4], mean, stream)
+    out = hip.download(ptrs[4], (n_out + extra,), np.uint32)
+    hip.free(*(ptrs + ([d_pairs] if d_pairs else [])))
+    return out[:n_out].view(np.float32), out[n_out:]
+
+
+def test_maxsim_in_several_launches_all_pairs_and_mean(ms_model):
+    """5 x 3 sets: launches of 7 pairs begin inside rows 2 and 4 of the score matrix"""
+    q, qcu, d, dcu = _launch_sets()
+    q16, d16 = q.astype(np.float16), d.astype(np.float16)
+    for mean in (False, True):
+        whole = ms_model.maxsim(q, qcu, d, dcu, None, mean)
+        want, bound = mr.maxsim_reference(mr.round_f16(q), qcu, mr.round_f16(d), dcu, None, mean)
+        assert whole.shape == (5, 3) and (np.abs(whole - want) <= bound).all()
+        for key in (LAUNCH_PAIRS, 1, 15, 16):
+            cut = _with_key(ms_model, key, lambda: ms_model.maxsim(q, qcu, d, dcu, None, mean))
+            assert np.array_equal(_bits(cut), _bits(whole)), (mean, key)
+        dev, behind = _with_key(ms_model, LAUNCH_PAIRS, lambda: _device_maxsim_prefilled(ms_model, q16, qcu, d16, dcu, None, 15, 9, mean))
+        assert np.array_equal(_bits(dev.reshape(5, 3)), _bits(whole)) and (behind == PREFILL).all(), mean
+    # a value above the bound is the bound, a value below 1 the default
+    for key in (2 ** 23 + 1, 2 ** 31 - 1, -3):
+        cut = _with_key(ms_model, key, lambda: ms_model.maxsim(q, qcu, d, dcu))
+        assert np.array_equal(_bits(cut), _bits(ms_model.maxsim(q, qcu, d, dcu))), key
+
+
+def test_maxsim_in_several_launches_pair_list_with_nan_cases_at_the_edges(ms_model):
+    """20 pairs in launches of 7: an index out of range and an empty sentence on both sides of the edges at 7 and 14; nothing behind
+    the list is written"""
+    q, qcu, d, dcu = _launch_sets()
+    q16, d16 = q.astype(np.float16), d.astype(np.float16)
+    empty_qcu = qcu.copy()
+    empty_qcu[3] = empty_qcu[4]                                          # query 3 is empty; query 2 takes its rows, 0, 1 and 4 are as they were
+    pairs = np.array([(0, 0), (1, 2), (2, 1), (4, 0), (0, 2), (1, 1), (0, 3),          # 6: document out of range
+                      (3, 0), (2, 2), (4, 1), (0, 1), (1, 0), (2, 0), (3, 2),          # 7, 13: the empty query
+                      (5, 1), (4, 2), (0, 0), (-1, 0), (2, 1), (1, 2)], np.int32)      # 14, 17: query out of range
+    nan_at = [6, 7, 13, 14, 17]
+    whole, behind0 = _device_maxsim_prefilled(ms_model, q16, empty_qcu, d16, dcu, pairs, 20, 12)
+    cut, behind = _with_key(ms_model, LAUNCH_PAIRS, lambda: _device_maxsim_prefilled(ms_model, q16, empty_qcu, d16, dcu, pairs, 20, 12))
+    assert np.array_equal(_bits(cut), _bits(whole)) and (behind == PREFILL).all() and (behind0 == PREFILL).all()
+    assert np.isnan(cut[nan_at]).all() and (_bits(cut[nan_at]) != PREFILL).all() and np.isfinite(np.delete(cut, nan_at)).all()
+    good = ms_model.maxsim(q, qcu, d, dcu)
+    keep = [i for i in range(20) if i not in nan_at and pairs[i, 0] != 2]
+    assert np.array_equal(_bits(cut[keep]), _bits(np.array([good[a, b] for a, b in pairs[keep].tolist()], np.float32)))
+
+
+def test_token_index_rescore_with_maxsim_in_several_launches(ms_model):
+    import token_index_reference as tref
+
+    dim = 24
+    rng = np.random.default_rng(32)
+    d, dcu = tref.documents(rng, 60, dim)
+    q, qcu = tref.queries(rng, dim, [1, 33, 31, 64, 128])
+    ix = ms_model.token_index(dim)
+    assert ix.add(d, dcu) == 0
+    cand = rng.integers(-1, 60, (5, 33)).astype(np.int32)               # 165 pairs: 24 launches of 7 (the last of 4)
+    whole = ix.rescore(q, qcu, cand, 10)
+    cut = _with_key(ms_model, LAUNCH_PAIRS, lambda: ix.rescore(q, qcu, cand, 10))
+    assert np.array_equal(cut[0], whole[0]) and np.array_equal(_bits(cut[1]), _bits(whole[1]))
+    assert tref.same_result(whole, tref.rescore_expected(ms_model.maxsim(q, qcu, d, dcu), cand, 10))
+    ix.close()
+
+
+def test_maxsim_in_several_launches_is_captured_and_replayed(ms_model):
+    """a captured bert_hip_maxsim_device call holds one kernel node per launch and replays to the eager bits"""
+    from hip_graph import Hip
+    hip = Hip()
+    q, qcu, d, dcu = _launch_sets()
+    eager = ms_model.maxsim(q, qcu, d, dcu)
+    ptrs = [hip.upload(q.astype(np.float16)), hip.upload(qcu.astype(np.int32)), hip.upload(d.astype(np.float16)), hip.upload(dcu.astype(np.int32)),
+            hip.nans((5, 3), np.float32)]
+    s = hip.stream()
+    for key, nodes in ((LAUNCH_PAIRS, 3), (0, 1)):
+        def body():
+            with hip.capture(s) as cap:
+                ms_model.maxsim_device(ptrs[0], ptrs[1], 5, ptrs[2], ptrs[3], 3, q.shape[1], None, 0, ptrs[4], False, s)
+            return cap
+        cap = _with_key(ms_model, key, body)
+        assert cap.status == 0 and cap.graph and hip.kernel_nodes(cap.graph) == nodes, key
+        ex = hip.instantiate(cap.graph)
+        for _ in range(2):
+            hip.poison(ptrs[4], (5, 3), np.float32)
+            hip.launch(ex, s)
+            assert np.array_equal(_bits(hip.download(ptrs[4], (5, 3), np.float32)), _bits(eager)), key
+        hip.destroy(ex, cap.graph)
+    hip.destroy_stream(s)
+    hip.free(*ptrs)
+
+
+def test_maxsim_of_more_than_two_to_the_24_pairs(ms_model):
+    """4097 x 4096 one-token sets at H = 8, all pairs: 16 781 312 workgroups, which as one launch of 256 threads each would pass 2^32
+    threads.  The rows hold small integers, so q @ d.T in float32 is the exact expected matrix; the output starts as NaN and every
+    element must be equal.  (Wall time of the call and its synchronisation: profiles/launch_geometry_tests.txt.)"""
+    import time
+    from hip_graph import Hip
+    hip = Hip()
+    n_q, n_d, H = 4097, 4096, 8
+    assert n_q * n_d == 16781312 > 2 ** 24
+    rng = np.random.default_rng(33)
+    q = rng.integers(-4, 5, (n_q, H)).astype(np.float32)
+    d = rng.integers(-4, 5, (n_d, H)).astype(np.float32)
+    want = q @ d.T
+    assert want.dtype == np.float32 and np.array_equal(want.astype(np.float64), q.astype(np.float64) @ d.astype(np.float64).T)
+    ptrs = [hip.upload(q.astype(np.float16)), hip.upload(np.arange(n_q + 1, dtype=np.int32)), hip.upload(d.astype(np.float16)),
+            hip.upload(np.arange(n_d + 1, dtype=np.int32)), hip.nans((n_q, n_d), np.float32)]
+    hip.sync()
+    t0 = time.perf_counter()
+    ms_model.maxsim_device(ptrs[0], ptrs[1], n_q, ptrs[2], ptrs[3], n_d, H, None, 0, ptrs[4])
+    hip.sync()
+    print(f"maxsim of {n_q} x {n_d} one-token sets at H = {H}: {1e3 * (time.perf_counter() - t0):.1f} ms")
+    got = hip.download(ptrs[4], (n_q, n_d), np.float32)
+    hip.free(*ptrs)
+    wrong = np.flatnonzero(~(got == want).ravel())
+    assert wrong.size == 0, (wrong.size, "first at pair", int(wrong[0]), "unwritten", int(np.isnan(got).sum()))
+
+
+# ------------------------------------------------------------------------------------------------
 # the example program
 # ------------------------------------------------------------------------------------------------
 def test_bert_search_maxsim(text_model, tmp_path):

@@ -320,3 +320,105 @@ def test_sparse_tile_option_values_and_the_lds_clamp():
     for k, want in ((10, 3), (256, 2)):
         g = G(0, 262144, 130, 70, k, qb=8)
         assert 1 <= g["qb"] < 8 and g["qb"] == want and g["lds"] <= 160 * 1024 - 256 < g["lds"] // g["qb"] * (g["qb"] + 1), g
+
+
+# ------------------------------------------------------------------------------------------------
+# token_index_scan_kernel
+# ------------------------------------------------------------------------------------------------
+def test_staircase_lead_of_the_geometries_that_had_one_is_unchanged():
+    """the generalised lead is, wherever the first sort already sees k rows, the closed form the dense, sparse and merge fixtures were built
+    with; at the token scan's step of 64 it is the step after which a sort has left k rows"""
+    geometries = [(k, tor.dense_L(k), tor.DENSE_STEP) for k in tor.DENSE_KS + tor.PROBE_KS]
+    geometries += [(k, tor.sparse_L(k), tor.SPARSE_STEP) for k in tor.SPARSE_KS]
+    geometries += [(k, tor.MERGE_L, tor.MERGE_STEP) for k in tor.MERGE_KS]
+    for k, L, step in geometries:
+        lead = (L - k - step) // step + 1
+        assert lead * step >= k and tor.staircase_lead(k, L, step) == lead, (k, L, step)
+    want = {1: 3, 64: 3, 128: 2, 129: 3, 191: 3, 192: 3, 193: 4, 255: 4, 256: 4}
+    for k in tor.TOKEN_KS:
+        L = tor.token_L(k)
+        lead = tor.staircase_lead(k, L, tor.TOKEN_STEP)
+        assert lead == want[k], (k, lead)
+        # by the model: all rows push for `lead` steps; the last of them ends in a sort that leaves k rows, the one before does not
+        w = tor.walk(tor.values(tor.ascending(lead * tor.TOKEN_STEP))[None], np.arange(lead * tor.TOKEN_STEP), True, k, L, tor.TOKEN_STEP)
+        assert w["sort_steps"] and w["sort_steps"][-1] == lead - 1 and (w["ids"] != tor.SENT).all(), (k, w["sort_steps"])
+        earlier = [t for t in w["sort_steps"] if t < lead - 1]
+        assert not earlier or (earlier[-1] + 1) * tor.TOKEN_STEP < k, (k, w["sort_steps"])
+
+
+def test_token_list_geometry_matches_the_library():
+    for k in range(1, 257):
+        L = tor.token_L(k)
+        assert L == (256 if k <= 192 else 512) and L - k - tor.TOKEN_STEP >= 0
+    rooms = {k: tor.token_L(k) - k - tor.TOKEN_STEP for k in tor.TOKEN_KS}
+    assert rooms == {1: 191, 64: 128, 128: 64, 129: 63, 191: 1, 192: 0, 193: 255, 255: 193, 256: 192}
+    text = open(os.path.join(ROOT, "bert.cpp_amd", "csrc", "token_index_kernels.h")).read()
+    assert "constexpr int TOKEN_ROUNDS = 16;" in text and "TOKEN_STEP_DOCS = NWAVE * TOKEN_ROUNDS" in text
+    assert "inline int token_list_L(int k) { return k + TOKEN_STEP_DOCS <= 256 ? 256 : 512; }" in text
+    assert tor.MERGE_OUTER == 4096 and tor.TOKEN_STEP == 4 * 16
+
+
+# the largest slot the ascending pattern writes in one slice of TOKEN_DOCS documents (the state the fixture was designed to: a change of
+# the step, the list rule or the document count shows here)
+TOKEN_ASC_SLOT = {1: 192, 64: 255, 128: 255, 129: 192, 191: 254, 192: 255, 193: 448, 255: 510, 256: 511}
+
+
+@pytest.mark.parametrize("k", tor.TOKEN_KS)
+def test_token_fixtures_reach_their_states(k):
+    import token_index_reference as tref
+
+    fx = tor.token_fixture(k)
+    L = tor.token_L(k)
+    room = L - k - tor.TOKEN_STEP
+    assert fx.n == tor.TOKEN_DOCS == 1573 and fx.n % tor.TOKEN_STEP == 37 and fx.n % 4 != 0
+    assert sorted(set(fx.lens.tolist())) == sorted(tor.TOKEN_DOC_LENS) and fx.cu[-1] == len(fx.rows)
+    kinds, lens = tor.token_layout()
+    # the closed-form scores are the definition's, from the rows and the queries themselves, at both query lengths
+    f64 = tor.token_scores_f64(fx, kinds, lens)
+    for i, kk in enumerate(kinds):
+        assert np.array_equal(f64[i], fx.scores[kk].astype(np.float64)), (k, kk, lens[i])
+    assert (fx.scores["desc"] < 0).all() and (fx.scores["was"] < 0).all()          # an unmasked slot (0) would beat every one
+    S = np.stack([fx.scores[kk] for kk in tor.TOKEN_KINDS])
+    # one slice: the long walk
+    res = tor.token_search(S, k, 1, fx.n)
+    same(res, S, True, k, (fx.name, "one slice"))
+    by = {kk: res["wgs"][i] for i, kk in enumerate(tor.TOKEN_KINDS)}
+    for kk, w in by.items():
+        assert w["max_slot"] < L and w["steps"] == 25 and w["room"] == room, (k, kk, w["max_slot"])
+    assert by["stair"]["max_slot"] == L - 1 and by["stair"]["fit_stale"][0], (k, "exact fit, stale threshold", by["stair"]["max_slot"])
+    assert by["over"]["near_miss"][0], (k, "one document more than fits: sorted, then a whole step")
+    assert by["asc"]["max_slot"] == TOKEN_ASC_SLOT[k] and by["asc"]["pushed_late"][0], (k, by["asc"]["max_slot"])
+    # all ties, and every document worse than the one before: the first k ids, and nothing pushes once a sort has left k rows
+    lead = tor.staircase_lead(k, L, tor.TOKEN_STEP)
+    for kk in ("const", "desc"):
+        assert by[kk]["ids"][0].tolist() == list(range(k)) and (not by[kk]["sort_steps"] or by[kk]["sort_steps"][-1] < lead), (k, kk)
+    if room == 0:
+        assert by["asc"]["sorts"] == by["asc"]["steps"] and by["asc"]["sort_steps"] == list(range(25)), (k, "a sort at every step")
+    if k in (64, 128, 256):
+        assert by["asc"]["fit_fresh"][0] and by["asc"]["fit_stale"][0], k
+    print(tor.describe(f"{fx.name} one slice", res))
+    print(f"{fx.name}: " + ", ".join(f"{kk}: sorts {w['sorts']} largest slot {w['max_slot']}" for kk, w in by.items()))
+    # the planned cut: slices that are no whole steps
+    n_slices, slice_docs = libbert.test_token_index_plan(fx.n, len(kinds), 0)
+    assert (n_slices, slice_docs) == tref.plan(fx.n, len(kinds)) and slice_docs % 4 != 0 and n_slices > 17
+    planned = tor.token_search(S, k, n_slices, slice_docs)
+    same(planned, S, True, k, (fx.name, "planned"))
+    assert max(w["max_slot"] for w in planned["wgs"]) < L
+
+
+def test_token_many_slices_reach_a_second_merge_round():
+    k, n = tor.TOKEN_MANY_K, tor.TOKEN_MANY_DOCS
+    fx = tor.token_fixture(k, n)
+    n_slices, slice_docs = libbert.test_token_index_plan(n, 2 * len(tor.TOKEN_KINDS), tor.TOKEN_MANY_SLICES)
+    assert n_slices == tor.TOKEN_MANY_SLICES == 17
+    # slices end inside a step and inside a group of four waves, the last one too
+    last = n - (n_slices - 1) * slice_docs
+    assert slice_docs % tor.TOKEN_STEP != 0 and slice_docs % 4 != 0 and last % tor.TOKEN_STEP != 0 and last % 4 != 0
+    S = np.stack([fx.scores[kk] for kk in tor.TOKEN_KINDS])
+    res = tor.token_search(S, k, n_slices, slice_docs)
+    same(res, S, True, k, fx.name)
+    m = res["merge"]
+    assert m["n_cand"] == 17 * 256 == 4352 > tor.MERGE_OUTER and m["rounds"] == 2
+    asc = m["walks"][tor.TOKEN_KINDS.index("asc")]
+    assert asc["pushed_late"][0] and asc["sorts"] >= 2                 # every slice beats the ones before: the merge refills
+    print(tor.describe(fx.name, res))

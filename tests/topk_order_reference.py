@@ -1,7 +1,8 @@
 """Ordered score sequences for the selecting kernels, and a host model of their candidate queue.  Nothing here touches the GPU or
 calls the library: test_topk_order_host.py proves on the CPU that each fixture reaches the queue state it is meant to reach, and
 test_gpu_topk_order.py runs the same fixtures through index_topk_kernel, index_probe_kernel, topk_merge_kernel (search.hip) and
-sparse_index_scan_kernel (sparse_index.hip).
+sparse_index_scan_kernel (sparse_index.hip), test_gpu_token_index_order.py the token fixtures through token_index_scan_kernel
+(token_index.hip).
 
 The kernels select alike.  A query's current top-k stands in slots [0, k) of an LDS list of L entries; a (score, id) threshold — the
 k-th best at the last sort, (-inf, INT_MAX) before the first — lives in registers; every row that ranks before the threshold is
@@ -22,6 +23,7 @@ import sparse_index_reference as sref
 SENT = 2 ** 31 - 1                      # id of an empty list entry (score -inf)
 QT = 32                                 # queries of a dense tile
 DENSE_STEP, SPARSE_STEP = 128, 256      # rows per step
+TOKEN_STEP = 64                         # documents per step of token_index_scan_kernel: 16 rounds of its four waves
 MERGE_STEP, MERGE_L, MERGE_OUTER = 256, 512, 4096
 PROBE_CHUNK = 1024                      # rows of a tail chunk of the probed search
 
@@ -33,6 +35,11 @@ def dense_L(k):
 
 def sparse_L(k):
     return 512 if k <= 128 else 1024
+
+
+def token_L(k):
+    """entries of the list of token_index_scan_kernel (token_index_kernels.h token_list_L)"""
+    return 256 if k + TOKEN_STEP <= 256 else 512
 
 
 _ints = np.arange(65505, dtype=np.float32)
@@ -83,9 +90,17 @@ def fit_schedule(n, k, L, step, lead, extra=0):
 
 
 def staircase_lead(k, L, step):
-    """the steps of all-pushing rows after which a queue has been sorted for the first time and holds k rows"""
-    lead = (L - k - step) // step + 1
-    assert lead * step >= k
+    """the steps of all-pushing rows after which a sort has left k rows in the list, so that the threshold in the registers is a row's.
+    Where the first sort already sees k rows (room + step >= k: every dense, sparse and merge geometry) that is the first sort,
+    (L - k - step) // step + 1 steps; a short step (the token scan: 64 rows against k up to 256) sorts several times before."""
+    room = L - k - step
+    assert room >= 0
+    held = cnt = lead = 0
+    while held < k:
+        lead += 1
+        cnt += step
+        if cnt > room:
+            held, cnt = min(k, held + cnt), 0
     return lead
 
 
@@ -600,6 +615,99 @@ def sparse_fixture(dtype, k, mode, n=SPARSE_ROWS):
 def many_sparse_rows(n=MANY_SPARSE_ROWS):
     """rows of width 1: term 0 with weight 1 + r (f32)"""
     return np.zeros((n, 1), np.int32), (1 + np.arange(n)).astype(np.float32)[:, None]
+
+
+# ------------------------------------------------------------------------------------------------
+# token fixtures: token_index_scan_kernel (token_index.hip)
+# ------------------------------------------------------------------------------------------------
+TOKEN_KS = (1, 64, 128, 129, 191, 192, 193, 255, 256)
+TOKEN_DOCS = TOKEN_STEP * 24 + 37        # 24 whole steps and a tail that ends inside a step and inside a group of four waves
+TOKEN_DIM = 8
+TOKEN_DOC_LENS = (1, 31, 32, 33, 65)     # by document id: the masked last block of 32 document tokens is in play
+TOKEN_QUERY_LENS = (1, 33)               # the first token selects; zero rows behind it: a second query block that adds +0
+TOKEN_COLUMN = {"asc": (0, 1.0), "desc": (0, -1.0), "saw": (1, 1.0), "was": (1, -1.0), "stair": (2, 1.0), "riats": (2, -1.0), "over": (3, 1.0),
+                "revo": (3, -1.0), "const": (-1, 0.0)}
+TOKEN_KINDS = list(TOKEN_COLUMN)
+TOKEN_MANY_SLICES, TOKEN_MANY_K = 17, 256
+TOKEN_MANY_DOCS = 3301                   # 17 slices of 195 documents (the last: 181): 3 steps and 3 documents, 48 groups of four and 3
+
+
+def token_search(S, k, n_slices, slice_docs):
+    """token_index_scan_kernel over S [nq, n_docs]: one walk per (query, slice of slice_docs consecutive documents; the last takes what
+    is left, and a slice need not be whole steps), steps of TOKEN_STEP documents from the slice's first, then the merge of the slices'
+    lists.  The order of the pushes inside a step — the four waves' atomicAdd — is not modelled: walk() sorts by (score, id) alone.
+    Returns as sliced_search."""
+    S = np.ascontiguousarray(S, dtype=np.float32)
+    nq, n = S.shape
+    assert (n_slices - 1) * slice_docs < max(n, 1) <= n_slices * slice_docs
+    L = token_L(k)
+    list_s = np.full((nq, n_slices, k), -np.inf, np.float32)
+    list_i = np.full((nq, n_slices, k), SENT, np.int64)
+    wgs, cache = [], {}
+    for sl in range(n_slices):
+        r0, r1 = sl * slice_docs, min(n, (sl + 1) * slice_docs)
+        for q in range(nq):
+            key = (sl, S[q, r0:r1].tobytes())
+            if key not in cache:
+                cache[key] = walk(S[q:q + 1, r0:r1], np.arange(r0, r1), True, k, L, TOKEN_STEP)
+            w = dict(cache[key])
+            w["q0"], w["slice"] = q, sl
+            wgs.append(w)
+            list_s[q, sl], list_i[q, sl] = w["scores"][0], w["ids"][0]
+    m = merge(list_s.reshape(nq, -1), list_i.reshape(nq, -1), k)
+    return dict(wgs=wgs, merge=m, ids=m["ids"], scores=m["scores"], slices=n_slices)
+
+
+def token_fixture(k, n=TOKEN_DOCS):
+    """One token index of n documents and its queries by kind.  Document d is TOKEN_DOC_LENS[d % 5] copies of one row that carries the
+    value of pattern p's rank in column p — 0 ascending, 1 sawtooth of period 128, 2 the staircase of (k, token_L(k), 64), 3 its near
+    miss —; a query's first token is +-e_p (or zero), the tokens behind it are zero rows.  A score is so one product by +-1, a max over
+    equal values and sums of zeros: scores[kind] [n] f32 are exact in any order.  An unmasked slot behind a document's end would enter
+    the max as 0 and beat every score of a negated pattern.
+    rows [T, 8] f32, cu [n + 1]; queries(kinds, lens) packs a query set."""
+    L = token_L(k)
+    pats = [ascending(n), sawtooth(n, TOKEN_STEP), staircase(n, k, L, TOKEN_STEP), staircase(n, k, L, TOKEN_STEP, 1)]
+    per_doc = np.zeros((n, TOKEN_DIM), np.float32)
+    for c, ranks in enumerate(pats):
+        per_doc[:, c] = values(ranks)
+    assert np.array_equal(per_doc.astype(np.float16).astype(np.float32), per_doc)                 # (the index stores f16)
+    lens = np.array([TOKEN_DOC_LENS[d % len(TOKEN_DOC_LENS)] for d in range(n)], np.int64)
+    rows = np.repeat(per_doc, lens, axis=0)
+    cu = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    scores = {}
+    for kk, (col, sign) in TOKEN_COLUMN.items():
+        scores[kk] = np.zeros(n, np.float32) if col < 0 else np.float32(sign) * per_doc[:, col] + np.float32(0)
+    return Fixture(f"token k={k} n={n}", n=n, k=k, rows=rows, cu=cu, lens=lens, scores=scores, kinds=TOKEN_KINDS)
+
+
+def token_queries(kinds, lens):
+    """(rows [T, 8] f32, cu int32) of one query per (kind, len) pair: +-e_col, then len - 1 zero rows"""
+    parts = []
+    for kk, ln in zip(kinds, lens):
+        q = np.zeros((ln, TOKEN_DIM), np.float32)
+        col, sign = TOKEN_COLUMN[kk]
+        if col >= 0:
+            q[0, col] = sign
+        parts.append(q)
+    return np.concatenate(parts), np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int32)
+
+
+def token_layout():
+    """every kind at every query length: (kinds, lens)"""
+    kinds = [kk for kk in TOKEN_KINDS for _ in TOKEN_QUERY_LENS]
+    return kinds, [ln for _ in TOKEN_KINDS for ln in TOKEN_QUERY_LENS]
+
+
+def token_scores_f64(fx, kinds, lens):
+    """[nq, n] float64 by the definition, from the rows themselves: sum over the query's tokens of the max over the document's tokens of
+    the dot product (what scores[kind] states in closed form)"""
+    q, qcu = token_queries(kinds, lens)
+    out = np.zeros((len(kinds), fx.n))
+    prod = q.astype(np.float64) @ fx.rows.astype(np.float64).T                                    # [query tokens, document tokens]
+    mx = np.maximum.reduceat(prod, fx.cu[:-1], axis=1)                                            # per document
+    for i in range(len(kinds)):
+        out[i] = mx[qcu[i]:qcu[i + 1]].sum(axis=0)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

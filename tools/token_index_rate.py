@@ -2,8 +2,9 @@
 """Rate of the token index (bert_hip_token_index_search_device / _rescore_device) on one GPU beside two baselines on the same f16 rows:
 
     (a) what a user could do before the index: bert_hip_maxsim_device on all pairs (a pair list for a rescore) plus torch.topk — as many
-        queries per call as keep a launch under 2^32 threads (one workgroup of 256 per pair): a larger all-pairs call returns 0 and leaves
-        the pairs beyond that unwritten (profiles/token_index_rate.txt)
+        queries per call as keep a launch under 2^32 threads (one workgroup of 256 per pair).  That split is no longer needed: the
+        library now cuts a call into launches of at most 2^23 pairs itself (when profiles/token_index_rate.txt was measured, a larger
+        all-pairs call returned 0 and left the pairs beyond that unwritten); it stays so that the table's figures keep their meaning
     (b) torch: einsum + amax + sum + topk, the documents in slabs whose intermediate [nq, docs, lq, ld] stays under 2 GiB
 
     workloads (dim 384, queries of 32 tokens, k = 10; 1, 8 and 64 queries):
@@ -110,7 +111,7 @@ def main():
                 def index_scan():
                     ix.search_device(nq, qcu.data_ptr(), q.data_ptr(), lq, k, ids.data_ptr(), sc.data_ptr(), stream)
 
-                qa = max(1, min(nq, (2 ** 32 - 1) // (256 * n_docs)))       # queries per maxsim call: fewer than 2^32 threads in a launch
+                qa = max(1, min(nq, (2 ** 32 - 1) // (256 * n_docs)))       # queries per maxsim call, as the table was measured (no longer needed: see above)
 
                 def maxsim_topk():
                     for q0 in range(0, nq, qa):
