@@ -26,6 +26,11 @@ auto guarded(const char *name, F &&body, R on_error = {}) -> decltype(body()) {
     if constexpr (!std::is_void_v<decltype(body())>) return on_error;
 }
 
+// closes the file a load entry point opened, on every way out
+struct FileCloser {
+    void operator()(FILE *f) const { if (f) fclose(f); }
+};
+
 // bert_encode_batch / bert_hip_encode_batch: number of inputs encoded (stops at the first failure, later outputs untouched), -1
 // for a context without a device
 int32_t encode_batch_impl(bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, float **embeddings);

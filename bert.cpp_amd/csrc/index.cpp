@@ -30,19 +30,6 @@ constexpr FormInfo FORMS[4] = {
 };
 int query_form(int dtype) { return FORMS[dtype].quantized_queries ? 2 : dtype; }
 
-// live_set_range_kernel on the host mirror
-void live_set_range_host(std::vector<uint32_t> &live, int first, int n) {
-    for (long long r = first; r < (long long)first + n;) {
-        const size_t w = (size_t)(r >> 5);
-        const int b = (int)(r & 31);
-        const int c = (int)std::min<long long>(32 - b, (long long)first + n - r);
-        live[w] |= (c == 32 ? ~0u : ((1u << c) - 1u) << b);
-        r += c;
-    }
-}
-
-size_t live_words(long long rows) { return (size_t)((rows + 31) / 32); }
-
 // slices of a search: enough workgroups to fill the chip, but each slice long against k (the first k rows of a slice all
 // enter its list, and the merge reads slices x k candidates per query).  Grows with n_rows.
 int slice_count(int n_rows, int nq, int k) {

@@ -99,10 +99,6 @@ bool centroids_ok(const char *me, const Index &x, int32_t n_lists, const float *
     return !why;
 }
 
-struct FileCloser {
-    void operator()(FILE *f) const { if (f) fclose(f); }
-};
-
 }  // namespace
 
 extern "C" {

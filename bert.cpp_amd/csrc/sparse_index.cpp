@@ -20,18 +20,6 @@ namespace bert_hip {
 namespace {
 
 int blocks_of(long long rows) { return (int)((rows + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS); }
-size_t live_words(long long rows) { return (size_t)((rows + 31) / 32); }
-
-// live_set_range_kernel on the host mirror
-void live_set_range_host(std::vector<uint32_t> &live, int first, int n) {
-    for (long long r = first; r < (long long)first + n;) {
-        const size_t w = (size_t)(r >> 5);
-        const int b = (int)(r & 31), c = (int)std::min<long long>(32 - b, (long long)first + n - r);
-        live[w] |= (c == 32 ? ~0u : ((1u << c) - 1u) << b);
-        r += c;
-    }
-}
-
 // the most workspace entries (nq' * slices * k) a chunk of up to nqc queries takes: the slice count falls as the tiles grow
 size_t ws_entries_bound(int dtype, int n_vocab, int n_rows, int nqc, int k, int qb_pref) {
     size_t ent = 0;

@@ -41,10 +41,6 @@ bool allow_ok(const SparseIndex &x, const uint32_t *allow, int32_t n_words, std:
     return false;
 }
 
-struct FileCloser {
-    void operator()(FILE *f) const { if (f) fclose(f); }
-};
-
 // (the text routes' way from texts to the index's device buffers, text_model_ok and sparse_text_chunks: text_routes.h)
 
 }  // namespace

@@ -824,6 +824,36 @@ int32_t bert_hip_test_sparse_index_body(const uint32_t *fields, const void *body
     return -1;
 }
 
+int32_t bert_hip_test_late_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err, int32_t err_cap) {
+    TokenIndexFileHeader h;
+    std::string e;
+    if (err && err_cap > 0) err[0] = 0;
+    if (buf_len < 0 || file_bytes < 0) e = "negative length";
+    else if (token_index_header_check(buf, (size_t)buf_len, (uint64_t)file_bytes, h, e)) {
+        const uint32_t f[6] = {h.version, h.dim, h.n_docs, h.has_live, (uint32_t)h.n_tokens, (uint32_t)(h.n_tokens >> 32)};
+        if (fields) std::copy(f, f + 6, fields);
+        return 0;
+    }
+    if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return -1;
+}
+
+int32_t bert_hip_test_late_index_body(const uint32_t *fields, const void *body, int64_t body_len, char *err, int32_t err_cap) {
+    std::string e;
+    if (err && err_cap > 0) err[0] = 0;
+    if (!fields || body_len < 0) e = "fields and a body length >= 0 required";
+    else {
+        // (the fields through the header check itself: a body is only ever checked under a header that passed)
+        TokenIndexFileHeader g, h;
+        g.version = fields[0]; g.dim = fields[1]; g.n_docs = fields[2]; g.has_live = fields[3]; g.n_tokens = (uint64_t)fields[4] | (uint64_t)fields[5] << 32;
+        unsigned char hdr[INDEX_HEADER_BYTES];
+        token_index_header_write(g, hdr);
+        if (token_index_header_check(hdr, sizeof hdr, (uint64_t)body_len + INDEX_HEADER_BYTES, h, e) && token_index_body_check(h, body, (uint64_t)body_len, e)) return 0;
+    }
+    if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "%s", e.c_str());
+    return -1;
+}
+
 int32_t bert_hip_test_build_lists(const int32_t *list_of, int32_t n, int32_t n_lists, int32_t *offsets, int32_t *order) {
     if (n < 0 || n_lists < 0 || (n > 0 && !list_of) || !offsets || (n > 0 && !order)) return -1;
     ListTables t;

@@ -1,12 +1,16 @@
 // token_index.cpp — the host side of the token index (token_index.h): storage and its growth, the add forms, the search and its
-// chunks, rescoring, reading a document back and the checks of the host forms.  Every kernel is in token_index.hip, maxsim.hip or
-// search.hip (the merge) and reached through token_index_kernels.h / kernels.h / search_kernels.h.
+// chunks, rescoring, reading a document back, the checks of the host forms, the live bits, compaction and the file form.  Every kernel
+// is in token_index.hip, maxsim.hip or search.hip (the merge, the live bits of added documents) and reached through
+// token_index_kernels.h / kernels.h / search_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cstring>
+#include <memory>
 #include <vector>
+
+#include <sys/types.h>
 
 #include "search.h"
 #include "token_index.h"
@@ -77,6 +81,7 @@ TokenIndex::~TokenIndex() {
     if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
     if (rows_) (void)hipFree(rows_);
     if (cu_) (void)hipFree(cu_);
+    if (live_) (void)hipFree(live_);
 }
 
 bool TokenIndex::grow(DevBuf &b, size_t bytes, std::string &err) {
@@ -94,15 +99,27 @@ bool TokenIndex::grow_storage(long long n_docs, long long n_tokens, std::string 
     if (n_docs > cap_docs_) {
         const long long cap = std::min<long long>(INT_MAX - 1, std::max<long long>({n_docs, (long long)cap_docs_ * 3 / 2, 1024}));
         int32_t *pc = nullptr;
-        if (hipMalloc((void **)&pc, (size_t)(cap + 1) * 4) != hipSuccess) { (void)hipGetLastError(); err = "hipMalloc (token index lengths) failed"; return false; }
-        if (hipMemcpy(pc, cu_h_.data(), (size_t)(n_ + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        // (an index with removed documents: the live words grow with the lengths, so that an add within the capacity never allocates)
+        uint32_t *lv = nullptr;
+        const size_t lw = live_words(cap);
+        if (hipMalloc((void **)&pc, (size_t)(cap + 1) * 4) != hipSuccess || (live_ && hipMalloc((void **)&lv, lw * 4) != hipSuccess)) {
+            (void)hipGetLastError();
+            if (pc) (void)hipFree(pc);
+            err = "hipMalloc (token index lengths) failed";
+            return false;
+        }
+        if (hipMemcpy(pc, cu_h_.data(), (size_t)(n_ + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            (lv && (hipMemset(lv, 0, lw * 4) != hipSuccess ||
+                    (n_ > 0 && hipMemcpy(lv, live_h_.data(), live_words(n_) * 4, hipMemcpyHostToDevice) != hipSuccess)))) {
             (void)hipGetLastError();
             (void)hipFree(pc);
+            if (lv) (void)hipFree(lv);
             err = "hipMemcpy (token index lengths) failed";
             return false;
         }
         if (cu_) (void)hipFree(cu_);
         cu_ = pc;
+        if (live_) { (void)hipFree(live_); live_ = lv; live_h_.resize(lw, 0u); }
         cap_docs_ = (int)cap;
         cu_h_.reserve((size_t)cap + 1);
     }
@@ -149,6 +166,12 @@ bool TokenIndex::commit(int n_docs, const int32_t *cu, hipStream_t s, std::strin
         cu_h_.resize(at);
         err = "hipMemcpyAsync (token index lengths) failed";
         return false;
+    }
+    // (documents added after a removal are live: their bits on the same stream, and in the mirror, which is as long as the capacity)
+    if (live_) {
+        launch_live_set_range(live_, n_, n_docs, s);
+        if (hipGetLastError() != hipSuccess) { cu_h_.resize(at); err = "the live bits of the new documents could not be set"; return false; }
+        live_set_range_host(live_h_, n_, n_docs);
     }
     n_ += n_docs;
     n_tok_ = cu_h_.back();
@@ -218,6 +241,15 @@ int TokenIndex::add_in_place(int n_docs, const int32_t *cu, std::string &err) {
 void TokenIndex::truncate(int n) {
     if (n < 0 || n >= n_) return;
     // (after a failure, behind a synchronised stream: no copy from the mirror is queued)
+    // (the mirror keeps its bits at and beyond size zero; the device words of the dropped documents stay as they are: a search ignores
+    // them, and the add that reuses those ids sets them)
+    if (live_)
+        for (int d = n; d < n_; ++d) {
+            uint32_t &w = live_h_[(size_t)d >> 5];
+            const uint32_t bit = 1u << (d & 31);
+            if (!(w & bit)) { --n_removed_; tok_removed_ -= cu_h_[(size_t)d + 1] - cu_h_[(size_t)d]; }
+            w &= ~bit;
+        }
     cu_h_.resize((size_t)n + 1);
     n_ = n;
     n_tok_ = cu_h_.back();
@@ -240,7 +272,7 @@ int TokenIndex::get_doc(int id, float *rows, int cap_tokens, std::string &err) {
 // search
 // ------------------------------------------------------------------------------------------------
 int TokenIndex::search_device(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
-                              std::string &err) {
+                              std::string &err, const uint32_t *d_allow) {
     if (const int go = check_search(nq, d_qcu, d_q, k, d_ids, d_scores, err); go <= 0) return go;
     if (max_q_len < 1 || max_q_len > max_query_tokens()) { err = "search: max_q_len must be 1 .. " + std::to_string(max_query_tokens()) + " at dim " + std::to_string(dim_); return -2; }
     if ((uintptr_t)d_q & 15) { err = "search: the query rows must be 16-byte aligned"; return -2; }
@@ -256,7 +288,9 @@ int TokenIndex::search_device(int nq, const int32_t *d_qcu, const half_t *d_q, i
         a.rows = rows_; a.cu = cu_; a.q = d_q; a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
         a.n_docs = n_; a.dim = dim_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
         a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
-        eng_->timed_launch("token_index_scan", 0.0, s, [&] { launch_token_scan(a, s); });
+        // (removed documents or an allow-list: the masked kernel, the same plan and workspace; an empty index has no words to read)
+        if (n_ > 0) { a.live = live_; a.allow = d_allow; }
+        eng_->timed_launch(a.live || a.allow ? "token_index_scan_masked" : "token_index_scan", 0.0, s, [&] { launch_token_scan(a, s); });
         MergeArgs m;
         m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = p.n_slices * k; m.k = k; m.L = merge_L(k);
         m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
@@ -266,11 +300,12 @@ int TokenIndex::search_device(int nq, const int32_t *d_qcu, const half_t *d_q, i
     return eng_->op_end(op, err) ? 0 : -3;
 }
 
-int TokenIndex::search_device_to_host(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *ids, float *scores, std::string &err) {
+int TokenIndex::search_device_to_host(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *ids, float *scores, std::string &err,
+                                      const uint32_t *d_allow) {
     std::vector<int32_t> hid((size_t)nq * k);
     std::vector<float> hsc((size_t)nq * k);
     if (!grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
-    if (const int r = search_device(nq, d_qcu, d_q, max_q_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err); r != 0) {
+    if (const int r = search_device(nq, d_qcu, d_q, max_q_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow); r != 0) {
         (void)hipStreamSynchronize(stream_);
         return r;
     }
@@ -304,12 +339,25 @@ int TokenIndex::stage_queries(const char *what, int nq, const int32_t *qcu, cons
     return 0;
 }
 
-int TokenIndex::search_host(int nq, const int32_t *qcu, const float *q_rows, int k, int32_t *ids, float *scores, std::string &err) {
+int TokenIndex::search_host(int nq, const int32_t *qcu, const float *q_rows, int k, int32_t *ids, float *scores, std::string &err,
+                            const uint32_t *allow) {
     if (const int go = check_search(nq, qcu, q_rows, k, ids, scores, err); go <= 0) return go;
     DeviceGuard g(eng_->device());
     int max_len = 0;
     if (const int r = stage_queries("search", nq, qcu, q_rows, max_query_tokens(), max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
-    return search_device_to_host(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), max_len, k, ids, scores, err);
+    const uint32_t *d_allow = nullptr;
+    if (!upload_allow(allow, d_allow, err)) { (void)hipStreamSynchronize(stream_); return -3; }
+    return search_device_to_host(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), max_len, k, ids, scores, err, d_allow);
+}
+
+// (the host form copies ceil(size / 32) words; behind stage_queries, which made stream() wait for the index's event)
+bool TokenIndex::upload_allow(const uint32_t *allow, const uint32_t *&d_allow, std::string &err) {
+    if (!allow || n_ == 0) return true;
+    if (!grow(allow_, live_words(n_) * 4, err)) return false;
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
+    HIP_OK(hipMemcpyAsync(allow_.p, allow, live_words(n_) * 4, hipMemcpyHostToDevice, stream_), err, false);
+    d_allow = allow_.as<uint32_t>();
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -326,7 +374,7 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
     if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(pairs_, ent * 8, err)) return -3;
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
-        TokenPairsArgs pa{d_cand + (size_t)c0 * n_cand, pairs_.as<int32_t>(), ws_i_.as<int>(), c, n_cand, n_};
+        TokenPairsArgs pa{d_cand + (size_t)c0 * n_cand, pairs_.as<int32_t>(), ws_i_.as<int>(), c, n_cand, n_, live_};
         eng_->timed_launch("token_index_pairs", 0.0, s, [&] { launch_token_pairs(pa, s); });
         // (the index's own arrays are maxsim's document side; a pair (q, -1) is scored NaN and reads nothing)
         MaxsimArgs ma{d_q, rows_, d_qcu + c0, cu_, pairs_.as<int32_t>(), ws_s_.as<float>(), c, n_, dim_, c * n_cand, 0, 0};
@@ -361,6 +409,209 @@ int TokenIndex::rescore_host(int nq, const int32_t *qcu, const float *q_rows, in
     memcpy(ids, hid.data(), hid.size() * 4);
     memcpy(scores, hsc.data(), hsc.size() * 4);
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// removed documents, compaction, file form
+// ------------------------------------------------------------------------------------------------
+// the bitmap of an index that had none: every document live
+bool TokenIndex::make_live(std::string &err) {
+    if (live_) return true;
+    const size_t lw = live_words(cap_docs_);
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    HIP_OK(hipStreamSynchronize(stream_), err, false);
+    HIP_OK(hipMalloc((void **)&live_, std::max<size_t>(lw, 1) * 4), err, false);
+    live_h_.assign(lw, 0u);
+    if (n_ > 0) live_set_range_host(live_h_, 0, n_);
+    n_removed_ = 0;
+    tok_removed_ = 0;
+    if (lw > 0 && hipMemcpy(live_, live_h_.data(), lw * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        drop_live();
+        err = "hipMemcpy (token index live words) failed";
+        return false;
+    }
+    return true;
+}
+
+void TokenIndex::drop_live() {
+    if (live_) (void)hipFree(live_);
+    live_ = nullptr;
+    live_h_.clear();
+    n_removed_ = 0;
+    tok_removed_ = 0;
+}
+
+// mirror words [w0, w1) -> device, on the index's stream behind whatever is queued; blocking
+bool TokenIndex::upload_live(size_t w0, size_t w1, std::string &err) {
+    if (w1 <= w0) return true;
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
+    HIP_OK(hipMemcpyAsync(live_ + w0, live_h_.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, stream_), err, false);
+    HIP_OK(hipEventRecord(busy_, stream_), err, false);
+    HIP_OK(hipStreamSynchronize(stream_), err, false);
+    return true;
+}
+
+int TokenIndex::remove(int n, const int32_t *ids, std::string &err) {
+    if (n < 0 || (n > 0 && !ids)) { err = "remove: n >= 0 and an id pointer required"; return -2; }
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= n_) { err = "remove: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(n_) + ")"; return -2; }
+    if (n == 0) return 0;
+    DeviceGuard g(eng_->device());
+    if (!make_live(err)) return -3;
+    std::vector<int32_t> fresh;                          // the ids this call removes (repeats and removed documents left out)
+    size_t w0 = SIZE_MAX, w1 = 0;
+    for (int i = 0; i < n; ++i) {
+        const size_t w = (size_t)ids[i] >> 5;
+        const uint32_t bit = 1u << (ids[i] & 31);
+        if (!(live_h_[w] & bit)) continue;
+        live_h_[w] &= ~bit;
+        fresh.push_back(ids[i]);
+        w0 = std::min(w0, w);
+        w1 = std::max(w1, w + 1);
+    }
+    if (!fresh.empty() && !upload_live(w0, w1, err)) {
+        for (int32_t id : fresh) live_h_[(size_t)id >> 5] |= 1u << (id & 31);      // (the mirror as it was)
+        return -3;
+    }
+    n_removed_ += (int)fresh.size();
+    for (int32_t id : fresh) tok_removed_ += cu_h_[(size_t)id + 1] - cu_h_[(size_t)id];
+    return (int)fresh.size();
+}
+
+int TokenIndex::compact(int32_t *old_ids, std::string &err) {
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipEventSynchronize(busy_), err, -3);
+    HIP_OK(hipStreamSynchronize(stream_), err, -3);
+    if (n_removed_ == 0) {
+        if (old_ids) for (int i = 0; i < n_; ++i) old_ids[i] = i;
+        drop_live();
+        return n_;
+    }
+    // the kept documents' former ids and their new cumulative lengths, from the mirrors
+    const int nl = n_live();
+    const int64_t ntl = n_live_tokens();
+    std::vector<int32_t> map((size_t)nl), ncu((size_t)nl + 1, 0);
+    int j = 0;
+    for (int d = 0; d < n_; ++d)
+        if (live_h_[(size_t)d >> 5] >> (d & 31) & 1u) {
+            map[(size_t)j] = d;
+            ncu[(size_t)j + 1] = ncu[(size_t)j] + (cu_h_[(size_t)d + 1] - cu_h_[(size_t)d]);
+            ++j;
+        }
+    // everything new is made before anything old is let go: fresh lengths and fresh rows beside the old ones (the peak is old + new)
+    const int cap = std::max(nl, 1024);
+    int32_t *pc = nullptr, *d_map = nullptr;
+    half_t *pr = nullptr;
+    const char *failed = nullptr;
+    if (hipMalloc((void **)&pc, ((size_t)cap + 1) * 4) != hipSuccess || (nl > 0 && hipMalloc((void **)&d_map, (size_t)nl * 4) != hipSuccess) ||
+        (ntl > 0 && hipMalloc((void **)&pr, (size_t)ntl * dim_ * 2) != hipSuccess)) failed = "hipMalloc (token index rows) failed";
+    else if (hipMemcpyAsync(pc, ncu.data(), ncu.size() * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
+             (nl > 0 && hipMemcpyAsync(d_map, map.data(), (size_t)nl * 4, hipMemcpyHostToDevice, stream_) != hipSuccess)) failed = "hipMemcpy (compaction ids) failed";
+    else {
+        if (nl > 0) {
+            TokenGatherArgs a{rows_, pr, cu_, pc, d_map, nl, dim_};
+            eng_->timed_launch("token_index_gather", 0.0, stream_, [&] { launch_token_gather(a, stream_); });
+        }
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) failed = "the gather kernel failed";
+    }
+    if (d_map) (void)hipFree(d_map);
+    if (failed) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(stream_);
+        if (pc) (void)hipFree(pc);
+        if (pr) (void)hipFree(pr);
+        err = failed;
+        return -3;
+    }
+    if (rows_) (void)hipFree(rows_);
+    if (cu_) (void)hipFree(cu_);
+    rows_ = pr; cu_ = pc;
+    cap_tok_ = ntl; cap_docs_ = cap;
+    n_ = nl; n_tok_ = ntl;
+    cu_h_.swap(ncu);
+    cu_h_.reserve((size_t)cap + 1);
+    drop_live();
+    if (old_ids && nl > 0) memcpy(old_ids, map.data(), (size_t)nl * 4);
+    return nl;
+}
+
+namespace {
+
+// rows between HBM and a file in pieces of at most 32 MiB through a host buffer, as add uploads them: never a host copy of the index
+constexpr size_t FILE_PIECE = (size_t)32 << 20;
+
+}  // namespace
+
+bool TokenIndex::save(const char *path, std::string &err) {
+    if (!path || !*path) { err = "a path is required"; return false; }
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipEventSynchronize(busy_), err, false);
+    HIP_OK(hipStreamSynchronize(stream_), err, false);
+    TokenIndexFileHeader h;
+    h.dim = (uint32_t)dim_; h.n_docs = (uint32_t)n_; h.has_live = live_ ? 1u : 0u; h.n_tokens = (uint64_t)n_tok_;
+    unsigned char hdr[INDEX_HEADER_BYTES];
+    token_index_header_write(h, hdr);
+    const std::string tmp = std::string(path) + ".tmp";
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) { err = "cannot write '" + tmp + "'"; return false; }
+    // (the lengths and the live words come from the mirrors; the mirror's bits at and beyond size are zero)
+    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && fwrite(cu_h_.data(), 4, (size_t)n_ + 1, f) == (size_t)n_ + 1;
+    const size_t bytes = (size_t)n_tok_ * dim_ * 2;
+    std::vector<char> buf(std::min(FILE_PIECE, bytes));
+    for (size_t o = 0; ok && o < bytes; o += FILE_PIECE) {
+        const size_t c = std::min(FILE_PIECE, bytes - o);
+        if (hipMemcpy(buf.data(), (const char *)rows_ + o, c, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); err = "hipMemcpy (token index rows) failed"; ok = false; }
+        else ok = fwrite(buf.data(), 1, c, f) == c;
+    }
+    ok = ok && (!live_ || fwrite(live_h_.data(), 4, live_words(n_), f) == live_words(n_));
+    ok = (fclose(f) == 0) && ok;
+    if (ok && rename(tmp.c_str(), path) != 0) ok = false;
+    if (!ok) {
+        (void)::remove(tmp.c_str());
+        if (err.empty()) err = "cannot write '" + std::string(path) + "'";
+    }
+    return ok;
+}
+
+TokenIndex *TokenIndex::load(Engine *eng, FILE *f, const TokenIndexFileHeader &h, std::string &err) {
+    const int n = (int)h.n_docs;
+    // the lengths and the live words stand on both sides of the rows: read and checked first, in front of any allocation on the device
+    std::vector<int32_t> cu((size_t)n + 1);
+    if (fread(cu.data(), 4, cu.size(), f) != cu.size()) { err = "read failed"; return nullptr; }
+    if (!token_index_cu_check(h, cu.data(), err)) return nullptr;
+    std::vector<uint32_t> words(h.has_live ? live_words(n) : 0);
+    const uint64_t rows_at = INDEX_HEADER_BYTES + token_index_file_cu_bytes(h), bytes = token_index_file_row_bytes(h);
+    if (fseeko(f, (off_t)(rows_at + bytes), SEEK_SET) != 0 || fread(words.data(), 4, words.size(), f) != words.size()) { err = "read failed"; return nullptr; }
+    if (!token_index_live_check(h, words.data(), err)) return nullptr;
+    std::unique_ptr<TokenIndex> ix(create(eng, (int)h.dim, err));
+    if (!ix) return nullptr;
+    DeviceGuard g(eng->device());
+    if (n == 0) {
+        // (an empty index that had a bitmap keeps one: the file's bytes come back from a save)
+        if (h.has_live && !ix->make_live(err)) return nullptr;
+        return ix.release();
+    }
+    if (!ix->grow_storage(n, (long long)h.n_tokens, err)) return nullptr;
+    if (fseeko(f, (off_t)rows_at, SEEK_SET) != 0) { err = "read failed"; return nullptr; }
+    std::vector<char> buf((size_t)std::min<uint64_t>(FILE_PIECE, bytes));
+    for (uint64_t o = 0; o < bytes; o += FILE_PIECE) {
+        const size_t c = (size_t)std::min<uint64_t>(FILE_PIECE, bytes - o);
+        if (fread(buf.data(), 1, c, f) != c) { err = "read failed"; return nullptr; }
+        HIP_OK(hipMemcpy((char *)ix->rows_ + o, buf.data(), c, hipMemcpyHostToDevice), err, nullptr);
+    }
+    // (grow_storage reserved the mirror: its entries do not move afterwards)
+    ix->cu_h_.assign(cu.begin(), cu.end());
+    HIP_OK(hipMemcpy(ix->cu_, ix->cu_h_.data(), ix->cu_h_.size() * 4, hipMemcpyHostToDevice), err, nullptr);
+    ix->n_ = n;
+    ix->n_tok_ = (int64_t)h.n_tokens;
+    if (!h.has_live) return ix.release();
+    if (!ix->make_live(err)) return nullptr;
+    std::copy(words.begin(), words.end(), ix->live_h_.begin());
+    for (int d = 0; d < n; ++d)
+        if (!(words[(size_t)d >> 5] >> (d & 31) & 1u)) { ++ix->n_removed_; ix->tok_removed_ += cu[(size_t)d + 1] - cu[(size_t)d]; }
+    if (!ix->upload_live(0, words.size(), err)) return nullptr;
+    return ix.release();
 }
 
 bool TokenIndex::text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err) {

@@ -5,14 +5,19 @@
 // slices' lists per query with the embedding index's topk_merge_kernel; a rescore turns per-query candidate ids into maxsim's pair
 // list, scores them with launch_maxsim against the index's own arrays and selects with the same merge.  Shaped like SparseIndex
 // (sparse_index.h): grow-only storage and workspace, one event, a stream for the host routes.
+// Removed documents are a device bitmap with a host mirror, there from the first remove to the next compact; while it exists, or under
+// an allow-list, a search launches the masked scan and a rescore's pair list leaves the removed ids out.  compact gathers the live
+// documents' rows into a fresh allocation on the device; save / load move the file form (token_index_file.h) in pieces.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <string>
 #include <vector>
 
 #include "engine.h"
+#include "token_index_file.h"
 #include "token_index_kernels.h"
 
 namespace bert_hip {
@@ -27,6 +32,8 @@ public:
 
     int size() const { return n_; }
     int64_t n_tokens() const { return n_tok_; }
+    int n_live() const { return n_ - n_removed_; }
+    int64_t n_live_tokens() const { return n_tok_ - tok_removed_; }
     int dim() const { return dim_; }
     int max_query_tokens() const { return token_max_query_tokens(dim_); }
     hipStream_t stream() const { return stream_; }
@@ -50,15 +57,18 @@ public:
     // document id's rows as f32 [len][dim] (the stored f16 values converted exactly): its length; writes iff cap_tokens >= it.  Blocking
     int get_doc(int id, float *rows, int cap_tokens, std::string &err);
     // ids / scores [nq][k], best first; queries d_q f16 indexed by d_qcu [nq + 1], both in device memory, unchecked (the kernel's
-    // guards).  max_q_len: the caller's promise, 1 .. max_query_tokens().  Asynchronous on s
+    // guards).  max_q_len: the caller's promise, 1 .. max_query_tokens().  Asynchronous on s.  d_allow: null, or device words
+    // [ceil(size / 32)], bit set = the document may be returned
     int search_device(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
-                      std::string &err);
+                      std::string &err, const uint32_t *d_allow = nullptr);
     // host queries (qcu strictly ascending from an entry >= 0, no query longer than max_query_tokens(); rows f32, rounded to f16 on the
-    // device) and host results (written only on success); blocking
-    int search_host(int nq, const int32_t *qcu, const float *q_rows, int k, int32_t *ids, float *scores, std::string &err);
+    // device) and host results (written only on success); blocking.  allow: null, or host words as d_allow
+    int search_host(int nq, const int32_t *qcu, const float *q_rows, int k, int32_t *ids, float *scores, std::string &err,
+                    const uint32_t *allow = nullptr);
     // a device search on stream() and its results -> host; blocking
-    int search_device_to_host(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *ids, float *scores, std::string &err);
-    // Per query its n_cand candidates d_cand [nq][n_cand] (ids outside [0, size): no candidate) scored with the search's bits, the best
+    int search_device_to_host(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *ids, float *scores, std::string &err,
+                              const uint32_t *d_allow = nullptr);
+    // Per query its n_cand candidates d_cand [nq][n_cand] (ids outside [0, size) and removed documents: no candidate) scored with the search's bits, the best
     // k to d_ids / d_scores [nq][k].  The workspace grows on demand and is not part of reserve.  Asynchronous on s
     int rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, int n_cand, const int32_t *d_cand, int k, int32_t *d_ids, float *d_scores,
                        hipStream_t s, std::string &err);
@@ -67,6 +77,17 @@ public:
                      std::string &err);
     // Text routes: device buffers of the index for a chunk's packed token ids | cu_seqlens (in) and, for queries, its f16 rows (out)
     bool text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err);
+    // Removed documents: the number newly removed (repeats and removed documents are ignored); an id outside [0, size): -2, nothing
+    // changed.  The first one allocates the bitmap.  Blocking
+    int remove(int n, const int32_t *ids, std::string &err);
+    // Drops the removed documents: the live ones keep their order and bits and get ids 0 .. n_live - 1; old_ids (nullable) [n_live]
+    // receives their former ids.  The new size; the bitmap is gone afterwards.  Fresh storage for the live rows beside the old (the
+    // peak is old + new); -3 and the index unchanged where that fails.  Blocking
+    int compact(int32_t *old_ids, std::string &err);
+    // the file form (token_index_file.h), rows in pieces of 32 MiB through a host buffer; blocking.  load: from f, positioned behind
+    // the header h that token_index_header_check passed
+    bool save(const char *path, std::string &err);
+    static TokenIndex *load(Engine *eng, FILE *f, const TokenIndexFileHeader &h, std::string &err);
 
 private:
     TokenIndex() = default;
@@ -77,6 +98,11 @@ private:
     bool commit(int n_docs, const int32_t *cu, hipStream_t s, std::string &err);
     // queries of a host form: rows -> f16 in q16_, lengths (rebased to 0) -> qcu_in_, on stream(); max_len: the longest
     int stage_queries(const char *what, int nq, const int32_t *qcu, const float *q_rows, int limit, int &max_len, std::string &err);
+    // a host allow-list -> allow_, on stream() behind whatever is queued (null, or an empty index: d_allow stays null)
+    bool upload_allow(const uint32_t *allow, const uint32_t *&d_allow, std::string &err);
+    bool make_live(std::string &err);
+    void drop_live();
+    bool upload_live(size_t w0, size_t w1, std::string &err);
 
     Engine *eng_ = nullptr;
     int dim_ = 0;
@@ -85,10 +111,17 @@ private:
     half_t *rows_ = nullptr;                            // [cap_tok_][dim_]
     int32_t *cu_ = nullptr;                             // [cap_docs_ + 1]
     std::vector<int32_t> cu_h_;                         // the host mirror, [n_ + 1]
+    // removed documents: device words [ceil(cap_docs_ / 32)] and their host mirror of the same length (bits at and beyond n_ zero),
+    // both absent until the first remove
+    uint32_t *live_ = nullptr;
+    std::vector<uint32_t> live_h_;
+    int n_removed_ = 0;
+    int64_t tok_removed_ = 0;                           // the removed documents' rows
     std::vector<int32_t> qcu_h_;                        // host routes: the current call's query lengths, rebased to 0
     DevBuf ws_s_, ws_i_, pairs_;                        // per-(query, slice) lists, or a rescore's scores and ids; its pair list
     DevBuf stage_, q16_, qcu_in_, cand_in_, out_ids_, out_scores_;      // host routes: f32 rows in, queries, candidates, results out
     DevBuf text_in_, text_out_;                         // text routes
+    DevBuf allow_;                                      // host routes: a caller's allow-list
     hipStream_t stream_ = nullptr;                      // the host routes' stream
     // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
     hipEvent_t busy_ = nullptr;

@@ -22,7 +22,15 @@
 //                   [cu[d], cu[d + 1]) of its document or outside the query's range.
 //   Guards.         A query that is empty, descends, starts below 0 or is longer than the launch's max_q_len gets k entries of
 //                   (-inf, INT_MAX) in every slice — id -1 / -INFINITY after the merge —; nothing else is touched.
-//   token_index_pairs_kernel  a rescore's candidate ids as maxsim's pair list (token_index_kernels.h).
+//   Removed documents and allow-lists.  token_index_scan_kernel<true>: the same body with a 64-bit mask per step of TOKEN_STEP_DOCS
+//                   documents, built from up to three words of live & allow that every wave loads through the scalar path.  A wave
+//                   skips a document whose bit is clear before it reads the document's lengths or rows, INSIDE the round loop, so the
+//                   step's barriers are met by all four waves whatever each of them scored; a step whose mask is zero is skipped by
+//                   the whole workgroup, barriers included (the mask is the workgroup's, and nothing was pushed).  A step still
+//                   pushes at most TOKEN_STEP_DOCS entries: L and the room rule are those of the unmasked kernel, whose instantiation
+//                   <false> contains none of this.
+//   token_index_pairs_kernel  a rescore's candidate ids as maxsim's pair list (token_index_kernels.h); a removed id is no candidate.
+//   token_index_gather_kernel  compaction: the kept documents' rows into a fresh allocation (see the kernel).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -39,6 +47,17 @@ namespace {
 
 constexpr int SENT_ID = INT_MAX;        // id of an empty list entry (score -inf): ranks below every document, as in search.hip
 
+static_assert(TOKEN_STEP_DOCS == 64, "the masked scan keeps a step's mask in one 64-bit word");
+
+// the word of live & allow (a null pointer: all ones) at index wi, the same in every lane
+__device__ __forceinline__ uint32_t token_mask_word(const TokenScanArgs &a, int wi) {
+    uint32_t w = ~0u;
+    if (a.live) w &= a.live[wi];
+    if (a.allow) w &= a.allow[wi];
+    return __builtin_amdgcn_readfirstlane(w);
+}
+
+template <bool MASKED>
 __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ti_lds[];
     // workgroup b runs on XCD b % 8: consecutive items — the queries of one slice — go to one XCD, so that they find the slice's rows
@@ -75,9 +94,29 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
 
     const int room = L - k - TOKEN_STEP_DOCS;                  // a step pushes at most TOKEN_STEP_DOCS entries
     for (int base = r0; base < r1; base += TOKEN_STEP_DOCS) {
+        // MASKED: bit i of m = document base + i qualifies.  The step's documents lie in up to three mask words (a slice starts
+        // anywhere); only words that hold a document below r1 are read, so none at or beyond ceil(n_docs / 32).  Everything here is
+        // computed from the workgroup's values alone, the same in all four waves.
+        [[maybe_unused]] uint64_t m = 0;
+        if constexpr (MASKED) {
+            const int wi = base >> 5, sh = base & 31, we = (min(base + TOKEN_STEP_DOCS, r1) - 1) >> 5;
+            const uint32_t w0 = token_mask_word(a, wi);
+            const uint32_t w1 = wi + 1 <= we ? token_mask_word(a, wi + 1) : 0u;
+            const uint32_t w2 = wi + 2 <= we ? token_mask_word(a, wi + 2) : 0u;
+            m = ((uint64_t)w1 << 32 | w0) >> sh;
+            if (sh) m |= (uint64_t)w2 << (64 - sh);
+            // a step without a qualifying document pushes nothing: the count is what the last look left, so both barriers and the
+            // look can go — for the whole workgroup, since m is the workgroup's
+            if (m == 0) continue;
+        }
         for (int u = 0; u < TOKEN_ROUNDS; ++u) {
             const int d = base + NWAVE * u + wave;             // (wave-uniform)
             if (d >= r1) break;
+            if constexpr (MASKED) {
+                // a document that does not qualify is skipped here, in front of its lengths and rows, inside the round loop: the wave
+                // goes on to its next round and meets the step's barriers like the others, even when it scored nothing at all
+                if (!(m >> (NWAVE * u + wave) & 1)) continue;
+            }
             const int d0 = __builtin_amdgcn_readfirstlane(a.cu[d]), nd = __builtin_amdgcn_readfirstlane(a.cu[d + 1]) - d0;
             float total = 0.f;
             for (int qb = 0; qb < nblk; ++qb) {
@@ -135,10 +174,33 @@ __global__ __launch_bounds__(256) void token_index_pairs_kernel(TokenPairsArgs a
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)a.nq * a.n_cand) return;
     const int id = a.cand[i];
-    const bool ok = id >= 0 && id < a.n_docs;
+    bool ok = id >= 0 && id < a.n_docs;
+    if (ok && a.live) ok = (a.live[id >> 5] >> (id & 31)) & 1u;         // (a removed document: no candidate, as an id out of range)
     a.pairs[2 * i] = (int32_t)(i / a.n_cand);
     a.pairs[2 * i + 1] = ok ? id : -1;
     a.ws_i[i] = ok ? id : SENT_ID;
+}
+
+// Compaction (TokenGatherArgs): one wave per kept document, the documents dealt round over the launch's waves.  A document's rows
+// are contiguous in both arrays, so a wave copies ONE run of len * dim / 8 16-byte pieces, a lane a piece, four pieces in flight per
+// lane; the offsets are the wave's (scalar loads).  Both arrays are 16-byte aligned and dim is a multiple of 8.
+constexpr int GATHER_NT = 256, GATHER_MAX_BLOCKS = 16384;
+
+__global__ __launch_bounds__(GATHER_NT) void token_index_gather_kernel(TokenGatherArgs a) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int waves = (int)gridDim.x * (GATHER_NT / 64), chunks = a.dim >> 3;
+    for (int j = (int)blockIdx.x * (GATHER_NT / 64) + wave; j < a.n; j += waves) {
+        const int t0 = a.dst_cu[j], len = a.dst_cu[j + 1] - t0;
+        const u32x4 *src = (const u32x4 *)a.src + (size_t)a.src_cu[a.old_ids[j]] * chunks;
+        u32x4 *dst = (u32x4 *)a.dst + (size_t)t0 * chunks;
+        const long long n = (long long)len * chunks;
+        long long p = lane;
+        for (; p + 192 < n; p += 256) {
+            const u32x4 v0 = src[p], v1 = src[p + 64], v2 = src[p + 128], v3 = src[p + 192];
+            dst[p] = v0; dst[p + 64] = v1; dst[p + 128] = v2; dst[p + 192] = v3;
+        }
+        for (; p < n; p += 64) dst[p] = src[p];
+    }
 }
 
 DeviceFlags g_token_scan_lds;
@@ -148,15 +210,27 @@ DeviceFlags g_token_scan_lds;
 void token_index_kernels_init() {
     // (beyond the 64 KiB a launch gets unasked; a launch that still cannot have it fails, and the search reports the launch error)
     configure_once(g_token_scan_lds, [] {
-        if (hipFuncSetAttribute((const void *)token_index_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOKEN_LDS_MAX) != hipSuccess)
-            (void)hipGetLastError();                           // (not left behind for an unrelated call's check)
+        bool ok = true;
+        for (const void *f : {(const void *)token_index_scan_kernel<false>, (const void *)token_index_scan_kernel<true>})
+            ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOKEN_LDS_MAX) == hipSuccess && ok;
+        if (!ok) (void)hipGetLastError();                      // (not left behind for an unrelated call's check)
     });
 }
 
 void launch_token_scan(const TokenScanArgs &a, hipStream_t s) {
     if (a.n_items <= 0) return;
     const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
-    BERT_LAUNCH(token_index_scan_kernel, dim3(grid), dim3(NT), token_scan_lds_bytes(a.dim, a.max_q_len, a.k), s, a);
+    const size_t lds = token_scan_lds_bytes(a.dim, a.max_q_len, a.k);
+    if (a.live || a.allow) BERT_LAUNCH(token_index_scan_kernel<true>, dim3(grid), dim3(NT), lds, s, a);
+    else BERT_LAUNCH(token_index_scan_kernel<false>, dim3(grid), dim3(NT), lds, s, a);
+}
+
+void launch_token_gather(const TokenGatherArgs &a, hipStream_t s) {
+    // (a wave per document, at most GATHER_MAX_BLOCKS blocks of four waves — 2^22 threads, far below the 2^32 a launch's thread count
+    // wraps at —; the kernel's loop deals the documents beyond that over the same waves)
+    if (a.n <= 0) return;
+    const int blocks = std::min((a.n + GATHER_NT / 64 - 1) / (GATHER_NT / 64), GATHER_MAX_BLOCKS);
+    BERT_LAUNCH(token_index_gather_kernel, dim3(blocks), dim3(GATHER_NT), 0, s, a);
 }
 
 void launch_token_pairs(const TokenPairsArgs &a, hipStream_t s) {

@@ -1,7 +1,8 @@
 // token_index_api.cpp — the bert_hip_token_index_* entry points of bert_hip.h: a token index (token_index.h) on a context's first
 // device.  The text routes tokenize and pack as bert_hip_encode_tokens_batch does and run the token-rows pass with flags 1 | 2 (each
 // row over its L2 norm, f16) in chunks of chunk_tokens: add_texts straight into the index's storage, search_texts into a device buffer
-// the scan reads in place.  The rows never reach the host.
+// the scan reads in place.  The rows never reach the host.  Behind them the bert_hip_late_index_* entry points: the same index's
+// remove, filtered searches, compact, save and load.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -9,8 +10,11 @@
 #include <string>
 #include <vector>
 
+#include <sys/stat.h>
+
 #include "../../include/bert_hip.h"
 #include "abi.h"
+#include "token_index_file.h"
 
 using namespace bert_hip;
 
@@ -75,6 +79,14 @@ int32_t token_text_chunks(bert_ctx *ctx, TokenIndex &x, int32_t n_threads, int32
         }
     }
     return 0;
+}
+
+// an allow-list of n_words words covers the index (-2 + err otherwise)
+bool allow_ok(const TokenIndex &x, const uint32_t *allow, int32_t n_words, std::string &err) {
+    const int64_t need = ((int64_t)x.size() + 31) / 32;
+    if (!allow || n_words >= need) return true;
+    err = "the allow-list has " + std::to_string(n_words) + " words, an index of " + std::to_string(x.size()) + " documents needs " + std::to_string(need);
+    return false;
 }
 
 // what the text routes ask of the index (false + err otherwise)
@@ -213,6 +225,71 @@ int32_t bert_hip_token_index_rescore_device(struct bert_hip_token_index *ix, int
     return token_index_call("bert_hip_token_index_rescore_device", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t {
         return x.rescore_device(n_queries, d_qcu, (const half_t *)d_q, n_cand, d_cand_ids, k, d_ids, d_scores, (hipStream_t)stream, err);
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// bert_hip_late_index_*: the token index's life cycle (bert_hip.h "LATE INDEX").  Frames around the class; load checks the file's header
+// (token_index_file.h) before it makes the index.
+// ------------------------------------------------------------------------------------------------
+int32_t bert_hip_late_index_remove(struct bert_hip_token_index *ix, int32_t n, const int32_t *ids) {
+    return token_index_call("bert_hip_late_index_remove", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t { return x.remove(n, ids, err); });
+}
+
+int32_t bert_hip_late_index_n_live(struct bert_hip_token_index *ix) { return ix && ix->ix ? ix->ix->n_live() : -1; }
+
+int64_t bert_hip_late_index_n_live_tokens(struct bert_hip_token_index *ix) { return ix && ix->ix ? ix->ix->n_live_tokens() : -1; }
+
+int32_t bert_hip_late_index_search_filtered(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *qcu, const float *q_rows, int32_t k,
+                                            const uint32_t *allow, int32_t n_words, int32_t *ids, float *scores) {
+    return token_index_call("bert_hip_late_index_search_filtered", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t {
+        if (!allow_ok(x, allow, n_words, err)) return -2;
+        return x.search_host(n_queries, qcu, q_rows, k, ids, scores, err, allow);
+    });
+}
+
+int32_t bert_hip_late_index_search_filtered_device(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *d_qcu, const void *d_q,
+                                                   int32_t max_q_len, int32_t k, const uint32_t *d_allow, int32_t n_words, int32_t *d_ids,
+                                                   float *d_scores, void *stream) {
+    return token_index_call("bert_hip_late_index_search_filtered_device", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t {
+        if (!allow_ok(x, d_allow, n_words, err)) return -2;
+        return x.search_device(n_queries, d_qcu, (const half_t *)d_q, max_q_len, k, d_ids, d_scores, (hipStream_t)stream, err, d_allow);
+    });
+}
+
+int32_t bert_hip_late_index_compact(struct bert_hip_token_index *ix, int32_t *old_ids) {
+    return token_index_call("bert_hip_late_index_compact", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t { return x.compact(old_ids, err); });
+}
+
+int32_t bert_hip_late_index_save(struct bert_hip_token_index *ix, const char *path) {
+    return token_index_call("bert_hip_late_index_save", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t {
+        if (!path || !*path) { err = "a path is required"; return -2; }
+        return x.save(path, err) ? 0 : -3;
+    });
+}
+
+struct bert_hip_token_index *bert_hip_late_index_load(struct bert_ctx *ctx, const char *path) {
+    return guarded("bert_hip_late_index_load", [&]() -> bert_hip_token_index * {
+        const char *me = "bert_hip_late_index_load";
+        if (!ctx) { fprintf(stderr, "%s: no context\n", me); return nullptr; }
+        if (!ctx->engine()) { fprintf(stderr, "%s: this context has no device (tokenizer-only): an index lives on the context's device\n", me); return nullptr; }
+        if (!path) { fprintf(stderr, "%s: no path\n", me); return nullptr; }
+        std::unique_ptr<FILE, FileCloser> f(fopen(path, "rb"));
+        struct stat st;
+        if (!f || fstat(fileno(f.get()), &st) != 0 || !S_ISREG(st.st_mode)) { fprintf(stderr, "%s: cannot read '%s'\n", me, path); return nullptr; }
+        // everything the header promises is checked, against the file's length too, before anything is allocated
+        unsigned char hdr[INDEX_HEADER_BYTES];
+        const size_t got = fread(hdr, 1, sizeof hdr, f.get());
+        TokenIndexFileHeader h;
+        std::string err;
+        if (!token_index_header_check(hdr, got, (uint64_t)st.st_size, h, err)) { fprintf(stderr, "%s: '%s': %s\n", me, path, err.c_str()); return nullptr; }
+        std::unique_ptr<TokenIndex> ix(TokenIndex::load(ctx->engine(), f.get(), h, err));
+        if (!ix) { fprintf(stderr, "%s: '%s': %s\n", me, path, err.c_str()); return nullptr; }
+        std::unique_ptr<bert_hip_token_index> out(new bert_hip_token_index);
+        out->ctx = ctx;
+        out->ix = std::move(ix);
+        ctx->token_indexes.push_back(out.get());
+        return out.release();
+    }, (bert_hip_token_index *)nullptr);
 }
 
 }  // extern "C"

@@ -73,20 +73,37 @@ struct TokenScanArgs {
     float *ws_s;                        // [nq][n_slices][k] per-(query, slice) lists, best first
     int *ws_i;
     int n_docs, dim, nq, max_q_len, n_slices, slice_docs, k, L, n_items;
+    // the masked instantiation (either non-null): words [ceil(n_docs / 32)], bit d & 31 of word d >> 5 set = document d is live / may
+    // be returned; a null pointer = all ones.  No word at or beyond ceil(n_docs / 32) is read
+    const uint32_t *live = nullptr;
+    const uint32_t *allow = nullptr;
 };
 
 // token_index_pairs_kernel: cand [nq][n_cand] -> maxsim's pair list pairs [nq * n_cand][2] = (q, id), and ws_i [nq][n_cand] = id; an
-// id outside [0, n_docs) becomes the pair (q, -1) — which launch_maxsim scores NaN without reading a row — and the id INT_MAX
+// id outside [0, n_docs), or one whose bit of live (nullable, as the scan's) is clear, becomes the pair (q, -1) — which launch_maxsim
+// scores NaN without reading a row — and the id INT_MAX
 struct TokenPairsArgs {
     const int32_t *cand;
     int32_t *pairs;
     int *ws_i;
     int nq, n_cand, n_docs;
+    const uint32_t *live = nullptr;
 };
 
-// lets the scan kernel of the current device have TOKEN_LDS_MAX of LDS
+// token_index_gather_kernel (compaction): document j of the n kept ones is document old_ids[j] of src — its rows src_cu[old_ids[j]] ..
+// go to rows dst_cu[j] .. dst_cu[j + 1] - 1 of dst, in 16-byte pieces.  old_ids [n], src_cu (the old lengths) and dst_cu [n + 1] in
+// device memory; the lengths agree (dst_cu is built from src_cu on the host)
+struct TokenGatherArgs {
+    const half_t *src;
+    half_t *dst;
+    const int32_t *src_cu, *dst_cu, *old_ids;
+    int n, dim;
+};
+
+// lets the scan kernels of the current device have TOKEN_LDS_MAX of LDS
 void token_index_kernels_init();
 void launch_token_scan(const TokenScanArgs &a, hipStream_t s);
 void launch_token_pairs(const TokenPairsArgs &a, hipStream_t s);
+void launch_token_gather(const TokenGatherArgs &a, hipStream_t s);
 
 }  // namespace bert_hip

@@ -5,7 +5,7 @@
 //
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
 //               [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N]
-//   bert-search -m MODEL -f TEXTS --late [-k 3] [-t THREADS]
+//   bert-search -m MODEL -f TEXTS --late [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]
 //   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
 //   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]
 //   (--hybrid SPLADE: hybrid search.  SPLADE is a second model file, one with the MLM head, loaded into a context of its own (it may be
@@ -36,7 +36,10 @@
 //   Not together with --long, --sparse, --hybrid, --cross, --save, --load.)
 //   (--late: late-interaction search without a dense stage.  Every line's token rows go into a token index; each query line is answered
 //   by bert_hip_token_index_search_texts, the exact top-k of the MaxSim score over ALL lines.  A query of more tokens than the index's
-//   bert_hip_token_index_max_query_tokens is refused.  With -m, -f, -k and -t only.)
+//   bert_hip_token_index_max_query_tokens is refused.  With -m, -f, -k, -t, --save-tokens and --load-tokens only.)
+//   (--save-tokens PATH / --load-tokens PATH, with --late or with --maxsim N --token-index: the token index goes to PATH once it is built
+//   (bert_hip_late_index_save), or comes from PATH instead of the lines being encoded (bert_hip_late_index_load) — TEXTS is still read,
+//   for printing, and must have as many lines as the index has documents.  --save and --load are the dense index's and stay refused.)
 //   (--long: a line may be longer than the model's position limit: it is cut into overlapping windows of W ids, S inner ids apart,
 //   and embedded as ONE row (bert_hip_index_add_long_texts; W defaults to 128 or the model's limit if that is less, S to three
 //   quarters of W - 2).  Without --long a line is cut at the model's position limit, like a query;
@@ -66,8 +69,8 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N]\n", argv0);
-    fprintf(stderr, "       %s -m MODEL -f TEXTS --late [-k 3] [-t THREADS]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
+    fprintf(stderr, "       %s -m MODEL -f TEXTS --late [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
     fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]\n", argv0);
     fprintf(stderr, "  --hybrid SPLADE: hybrid search: the lines in an embedding index of DENSE and a sparse index of SPLADE (a model file with the MLM head; W\n"
@@ -83,7 +86,9 @@ void usage(const char *argv0) {
     fprintf(stderr, "  --token-index: with --maxsim N: the lines' token rows are kept in a token index (bert_hip_token_index_add_texts) and the candidates are\n"
                     "          scored from it (bert_hip_token_index_rescore) instead of being encoded again; the same lines and scores are printed.\n");
     fprintf(stderr, "  --late: no dense stage: the lines' token rows in a token index, each query answered by bert_hip_token_index_search_texts, the exact\n"
-                    "          top-k by MaxSim score over all lines.  With -m, -f, -k and -t only.\n");
+                    "          top-k by MaxSim score over all lines.  With -m, -f, -k, -t, --save-tokens and --load-tokens only.\n");
+    fprintf(stderr, "  --save-tokens PATH, --load-tokens PATH: with --late or with --maxsim N --token-index: the token index is written to PATH once it is built\n"
+                    "          (bert_hip_late_index_save), or read from PATH instead of encoding TEXTS (bert_hip_late_index_load; TEXTS is still read for printing).\n");
     fprintf(stderr, "  --cross-model PATH --cross N: the search returns N candidates (k <= N <= 256), which a cross-encoder (a model file with a classification\n"
                     "          head) reranks: bert_hip_score_pairs on (query, candidate); the k best by the first label's logit are printed with it.\n");
 }
@@ -96,6 +101,7 @@ std::string chomp(std::string s) {
 
 int main(int argc, char **argv) {
     const char *model = nullptr, *file = nullptr, *save = nullptr, *load = nullptr, *cross_model = nullptr, *hybrid_model = nullptr;
+    const char *save_tokens = nullptr, *load_tokens = nullptr;
     float w_dense = 1.f, w_sparse = 1.f;
     bool weights_ok = true;
     int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0, n_cross = 0;
@@ -109,6 +115,8 @@ int main(int argc, char **argv) {
         else if ((!strcmp(argv[i], "-t") || !strcmp(argv[i], "--threads")) && has_value) n_threads = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--save") && has_value) save = argv[++i];
         else if (!strcmp(argv[i], "--load") && has_value) load = argv[++i];
+        else if (!strcmp(argv[i], "--save-tokens") && has_value) save_tokens = argv[++i];
+        else if (!strcmp(argv[i], "--load-tokens") && has_value) load_tokens = argv[++i];
         else if (!strcmp(argv[i], "--f32")) dtype = 0;
         else if (!strcmp(argv[i], "--i8")) dtype = 2;
         else if (!strcmp(argv[i], "--b1")) dtype = 3;
@@ -144,6 +152,10 @@ int main(int argc, char **argv) {
             return 2;
         }
     if (token_index && (!maxsim || late)) { fprintf(stderr, "search: --token-index goes with --maxsim N\n"); return 2; }
+    if ((save_tokens || load_tokens) && !late && !token_index) {
+        fprintf(stderr, "search: --save-tokens and --load-tokens go with --late or with --maxsim N --token-index\n");
+        return 2;
+    }
     if (late && (maxsim || dtype != 1 || n_cand || n_lists || nprobe || sparse_f16)) { fprintf(stderr, "search: --late goes with -m, -f, -k and -t only\n"); return 2; }
     if (hybrid_model && (sparse || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model || save || load)) {
         fprintf(stderr, "search: --hybrid goes with -m, -f, -k, -t, --sparse-width, --weights, --f32, --i8, --b1 and --f16 only\n");
@@ -300,11 +312,34 @@ int main(int argc, char **argv) {
         bert_free(ctx);                                       // (frees the sparse index as well)
         return 0;
     }
+    // the lines' token rows in a token index: encoded, or (--load-tokens) from a file; written (--save-tokens) once they are there.
+    // NULL after a line on stderr
+    auto token_index_of_lines = [&]() -> bert_hip_token_index * {
+        bert_hip_token_index *t;
+        if (load_tokens) {
+            t = bert_hip_late_index_load(ctx, load_tokens);
+            if (!t) { fprintf(stderr, "search: could not load the token index from '%s'\n", load_tokens); return nullptr; }
+            if ((size_t)bert_hip_token_index_size(t) != texts.size()) {
+                fprintf(stderr, "search: '%s' holds %d documents, '%s' has %zu lines\n", load_tokens, bert_hip_token_index_size(t), file, texts.size());
+                return nullptr;
+            }
+        } else {
+            t = bert_hip_token_index_create(ctx, 0);
+            if (!t || bert_hip_token_index_add_texts(t, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
+                fprintf(stderr, "search: could not build the token index\n");
+                return nullptr;
+            }
+        }
+        if (save_tokens && bert_hip_late_index_save(t, save_tokens) != 0) {
+            fprintf(stderr, "search: could not save the token index to '%s'\n", save_tokens);
+            return nullptr;
+        }
+        return t;
+    };
     if (late) {
         // the late-interaction mode: the lines' token rows into a token index, each query's token rows against all of them
-        bert_hip_token_index *tx = bert_hip_token_index_create(ctx, 0);
-        if (!tx || bert_hip_token_index_add_texts(tx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
-            fprintf(stderr, "search: could not build the token index\n");
+        bert_hip_token_index *tx = token_index_of_lines();
+        if (!tx) {
             bert_free(ctx);
             return 1;
         }
@@ -372,9 +407,8 @@ int main(int argc, char **argv) {
     // --token-index: the lines' token rows, kept for the reranking
     bert_hip_token_index *tx = nullptr;
     if (token_index) {
-        tx = bert_hip_token_index_create(ctx, 0);
-        if (!tx || bert_hip_token_index_add_texts(tx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
-            fprintf(stderr, "search: could not build the token index\n");
+        tx = token_index_of_lines();
+        if (!tx) {
             bert_free(ctx);
             return 1;
         }

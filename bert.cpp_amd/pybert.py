@@ -53,6 +53,8 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_token_index_max_query_tokens", "bert_hip_token_index_reserve", "bert_hip_token_index_add", "bert_hip_token_index_add_device",
     "bert_hip_token_index_add_texts", "bert_hip_token_index_get_doc", "bert_hip_token_index_search", "bert_hip_token_index_search_device",
     "bert_hip_token_index_search_texts", "bert_hip_token_index_rescore", "bert_hip_token_index_rescore_device",
+    "bert_hip_late_index_remove", "bert_hip_late_index_n_live", "bert_hip_late_index_n_live_tokens", "bert_hip_late_index_search_filtered",
+    "bert_hip_late_index_search_filtered_device", "bert_hip_late_index_compact", "bert_hip_late_index_save", "bert_hip_late_index_load",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -69,6 +71,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid", "bert_hip_test_sparse_scan_geometry",
     "bert_hip_test_sparse_index_header", "bert_hip_test_sparse_index_body",
     "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan", "bert_hip_test_hybrid_chunk", "bert_hip_test_token_index_plan",
+    "bert_hip_test_late_index_header", "bert_hip_test_late_index_body",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -240,6 +243,15 @@ def _declare_product_abi(L):
     L.bert_hip_token_index_rescore.restype = i32; L.bert_hip_token_index_rescore.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp]
     L.bert_hip_token_index_rescore_device.restype = i32
     L.bert_hip_token_index_rescore_device.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_late_index_remove.restype = i32; L.bert_hip_late_index_remove.argtypes = [vp, i32, vp]
+    L.bert_hip_late_index_n_live.restype = i32; L.bert_hip_late_index_n_live.argtypes = [vp]
+    L.bert_hip_late_index_n_live_tokens.restype = i64; L.bert_hip_late_index_n_live_tokens.argtypes = [vp]
+    L.bert_hip_late_index_search_filtered.restype = i32; L.bert_hip_late_index_search_filtered.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp]
+    L.bert_hip_late_index_search_filtered_device.restype = i32
+    L.bert_hip_late_index_search_filtered_device.argtypes = [vp, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_late_index_compact.restype = i32; L.bert_hip_late_index_compact.argtypes = [vp, vp]
+    L.bert_hip_late_index_save.restype = i32; L.bert_hip_late_index_save.argtypes = [vp, C.c_char_p]
+    L.bert_hip_late_index_load.restype = vp; L.bert_hip_late_index_load.argtypes = [vp, C.c_char_p]
 
 
 def lib() -> C.CDLL:
@@ -366,6 +378,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_hybrid_chunk.argtypes = [i32, i32, i32, C.POINTER(C.c_int64)]
     L.bert_hip_test_token_index_plan.restype = i32
     L.bert_hip_test_token_index_plan.argtypes = [i32, i32, i32, i32p]
+    L.bert_hip_test_late_index_header.restype = i32
+    L.bert_hip_test_late_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
+    L.bert_hip_test_late_index_body.restype = i32
+    L.bert_hip_test_late_index_body.argtypes = [C.POINTER(C.c_uint32), C.c_char_p, C.c_int64, C.c_char_p, i32]
     _test_lib = L
     return L
 
@@ -1197,6 +1213,10 @@ class BertModel:
         """The sparse index a BertSparseIndex.save wrote (bert_hip_sparse_index_load), on this context's first device."""
         return BertSparseIndex(self, _load=path)
 
+    def load_token_index(self, path: str) -> "BertTokenIndex":
+        """The token index a BertTokenIndex.save wrote (bert_hip_late_index_load), on this context's first device."""
+        return BertTokenIndex(self, _load=path)
+
 
 def allow_words(allow, n_rows: int) -> np.ndarray:
     """An allow-list as the uint32 words of bert_hip_index_search_filtered: a bool array of n_rows entries is packed (row 32 w + b
@@ -1765,8 +1785,16 @@ class BertTokenIndex:
     [n, k] f32), best first; missing entries are id -1, score -inf.  A ValueError is an argument the entry refused (-2).  The *_device
     forms take device pointers (ints) and a stream handle; search_device and rescore_device return at once."""
 
-    def __init__(self, model: BertModel, dim: Optional[int] = None):
+    def __init__(self, model: BertModel, dim: Optional[int] = None, _load: Optional[str] = None):
         self.model, self.lib = model, model.lib
+        if _load is not None:
+            # dim comes from the file's header (include/bert_hip.h "LATE INDEX": u32 dim at byte 12)
+            self.ix = self.lib.bert_hip_late_index_load(model.ctx, os.fsencode(_load))
+            if not self.ix:
+                raise RuntimeError("bert_hip_late_index_load failed (see stderr)")
+            with open(_load, "rb") as f:
+                self.dim = int(np.frombuffer(f.read(16), dtype="<u4")[3])
+            return
         self.ix = self.lib.bert_hip_token_index_create(model.ctx, 0 if dim is None else int(dim))
         if not self.ix:
             raise RuntimeError("bert_hip_token_index_create failed (see stderr)")
@@ -1850,21 +1878,37 @@ class BertTokenIndex:
             raise RuntimeError("bert_hip_token_index_get_doc failed")
         return rows
 
-    def search(self, q_rows, q_cu, k: int = 10):
+    def search(self, q_rows, q_cu, k: int = 10, allow=None):
+        """allow: None, or the documents that may be returned — a bool array of len(index) entries or uint32 words (allow_words):
+        bert_hip_late_index_search_filtered."""
         q, qcu = self._packed(q_rows, q_cu)
         nq = len(qcu) - 1
         ids = np.empty((nq, max(k, 1)), dtype=np.int32)
         scores = np.empty((nq, max(k, 1)), dtype=np.float32)
-        r = self.lib.bert_hip_token_index_search(self.ix, nq, qcu.ctypes.data, q.ctypes.data, k, ids.ctypes.data, scores.ctypes.data)
+        if allow is None:
+            name = "bert_hip_token_index_search"
+            r = self.lib.bert_hip_token_index_search(self.ix, nq, qcu.ctypes.data, q.ctypes.data, k, ids.ctypes.data, scores.ctypes.data)
+        else:
+            name = "bert_hip_late_index_search_filtered"
+            words = allow_words(allow, len(self))
+            r = self.lib.bert_hip_late_index_search_filtered(self.ix, nq, qcu.ctypes.data, q.ctypes.data, k, words.ctypes.data, len(words),
+                                                             ids.ctypes.data, scores.ctypes.data)
         if r != 0:
-            self._fail("bert_hip_token_index_search", r)
+            self._fail(name, r)
         return ids, scores
 
     def search_device(self, n_queries: int, d_qcu_ptr: int, d_q_ptr: int, max_q_len: int, k: int, d_ids_ptr: int, d_scores_ptr: int,
-                      stream: int = 0) -> None:
-        r = self.lib.bert_hip_token_index_search_device(self.ix, n_queries, d_qcu_ptr, d_q_ptr, max_q_len, k, d_ids_ptr, d_scores_ptr, stream)
+                      stream: int = 0, d_allow_ptr: Optional[int] = None, n_words: int = 0) -> None:
+        """d_allow_ptr: None (or 0), or device uint32 words [n_words] as search's allow (bert_hip_late_index_search_filtered_device)."""
+        if d_allow_ptr:
+            name = "bert_hip_late_index_search_filtered_device"
+            r = self.lib.bert_hip_late_index_search_filtered_device(self.ix, n_queries, d_qcu_ptr, d_q_ptr, max_q_len, k, d_allow_ptr, n_words,
+                                                                    d_ids_ptr, d_scores_ptr, stream)
+        else:
+            name = "bert_hip_token_index_search_device"
+            r = self.lib.bert_hip_token_index_search_device(self.ix, n_queries, d_qcu_ptr, d_q_ptr, max_q_len, k, d_ids_ptr, d_scores_ptr, stream)
         if r != 0:
-            self._fail("bert_hip_token_index_search_device", r)
+            self._fail(name, r)
 
     def search_texts(self, texts: Sequence, k: int = 10, n_threads: int = 6):
         n = len(texts)
@@ -1896,6 +1940,45 @@ class BertTokenIndex:
                                                          stream)
         if r != 0:
             self._fail("bert_hip_token_index_rescore_device", r)
+
+    def remove(self, ids) -> int:
+        """bert_hip_late_index_remove: the number of documents newly removed."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        r = self.lib.bert_hip_late_index_remove(self.ix, len(ids), ids.ctypes.data)
+        if r < 0:
+            self._fail("bert_hip_late_index_remove", r)
+        return r
+
+    def n_live(self) -> int:
+        return int(self.lib.bert_hip_late_index_n_live(self.ix))
+
+    def n_live_tokens(self) -> int:
+        return int(self.lib.bert_hip_late_index_n_live_tokens(self.ix))
+
+    def compact(self) -> np.ndarray:
+        """bert_hip_late_index_compact: drops the removed documents; returns the former ids of the documents now at 0 .. len(index) - 1."""
+        old = np.empty(max(self.n_live(), 1), dtype=np.int32)
+        r = self.lib.bert_hip_late_index_compact(self.ix, old.ctypes.data)
+        if r < 0:
+            self._fail("bert_hip_late_index_compact", r)
+        return old[:r]
+
+    def save(self, path: str) -> None:
+        r = self.lib.bert_hip_late_index_save(self.ix, os.fsencode(path))
+        if r != 0:
+            self._fail("bert_hip_late_index_save", r)
+
+    def live_ids(self) -> np.ndarray:
+        """The ids a search can return, ascending.  With removed documents: found by rescoring every id against a one-token query, 256
+        candidates per query (a removed document is skipped; a document whose score is NaN is not found either)."""
+        n = len(self)
+        if self.n_live() == n:
+            return np.arange(n, dtype=np.int32)
+        cand = np.full((n + 255) // 256 * 256, -1, np.int32)
+        cand[:n] = np.arange(n, dtype=np.int32)
+        nq = len(cand) // 256
+        ids, _ = self.rescore(np.zeros((nq, self.dim), np.float32), np.arange(nq + 1, dtype=np.int32), cand.reshape(-1, 256), 256)
+        return np.sort(ids[ids >= 0])
 
 
 def test_gemm(A: np.ndarray, W_bytes: np.ndarray, wtype: int, N: int, bias: np.ndarray,

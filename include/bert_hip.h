@@ -887,8 +887,8 @@ BERT_API int32_t bert_hip_hybrid_search_texts(struct bert_hip_index *dense, stru
  *     a call of the same shape has run before) they allocate nothing and may be captured into a graph: STREAM CAPTURE AND GRAPHS above.
  * Results: -1 without an index; -2 after a line on stderr for an argument the entry refuses; -3 on a device error; -4 for an exception.
  * Outputs are untouched on error.
- * Not covered: removing documents, allow-lists, compaction and files; several GPUs; several queries per workgroup sharing document
- * loads; residual or quantised token rows; a mean mode.                                                                             */
+ * Removing documents, allow-lists, compaction and files: "LATE INDEX" below.
+ * Not covered: several GPUs; several queries per workgroup sharing document loads; residual or quantised token rows; a mean mode.   */
 struct bert_hip_token_index;
 BERT_API struct bert_hip_token_index *bert_hip_token_index_create(struct bert_ctx *ctx, int32_t dim);
 BERT_API void    bert_hip_token_index_free(struct bert_hip_token_index *ix);
@@ -913,6 +913,62 @@ BERT_API int32_t bert_hip_token_index_rescore(struct bert_hip_token_index *ix, i
 BERT_API int32_t bert_hip_token_index_rescore_device(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *d_qcu, const void *d_q,
                                                      int32_t n_cand, const int32_t *d_cand_ids, int32_t k, int32_t *d_ids, float *d_scores,
                                                      void *stream);
+
+/* LATE INDEX: the token index's life cycle — removing documents, filtered search, compaction, files — worded after the sparse index's
+ * ("Sparse index: removing rows, filtered search, rescoring, compaction, files" above).  These functions take the same
+ * struct bert_hip_token_index; they are named bert_hip_late_index_* ("late" as in late interaction, as bert-search --late) because the
+ * set of exported names that contain token_index is closed.  The error codes are the token index's (-1 / -2 / -3 / -4, outputs
+ * untouched on error).
+ *   remove   marks the documents ids[n] removed and returns how many were newly removed.  A removed document is never returned by
+ *            search, search_device, search_texts, the filtered forms or rescore[_device]: in rescore a removed id is no candidate,
+ *            exactly as -1 is.  Ids are stable; size and n_tokens still count removed documents; n_live and n_live_tokens are those
+ *            less the removed documents and their rows; get_doc still returns a removed document.  An id outside [0, size): -2, the
+ *            index unchanged.  Repeats and already-removed ids are ignored.  Documents added later are live.  Blocking.  The first
+ *            remove allocates a bitmap of the document capacity (one bit per document, with a host mirror); afterwards an add within
+ *            reserve's bounds still never allocates.
+ *   search_filtered[_device]   allow: words [n_words] (device memory for _device), bit b of word w set = document 32 w + b may be
+ *            returned.  allow == NULL is the plain search and n_words is ignored; n_words < ceil(size / 32): -2.  Words at and beyond
+ *            ceil(size / 32) are never read, bits at and beyond size are ignored.  Over the documents that are live AND allowed every
+ *            promise of the TOKEN INDEX block holds: the score bits of the unfiltered search (bert_hip_maxsim_device's), the order
+ *            rule, -1 / -INFINITY slots when fewer than k qualify, independence from the other queries, k, the slicing, the add
+ *            history and host or device entry.  A document that does not qualify is skipped before any of its rows is read.  The host
+ *            form copies ceil(size / 32) words; the device form reads the caller's words when the search runs, allocates nothing
+ *            within reserve's bounds and is legal under stream capture.
+ *   compact  drops the removed documents: the live ones keep their order and stored bits and get ids 0 .. n_live - 1; old_ids (may be
+ *            NULL) [n_live] receives their former ids.  Returns the new size; n_tokens becomes n_live_tokens and the cumulative
+ *            lengths are rebuilt.  On an index without removals a no-op that returns size (old_ids the identity).  Afterwards the index
+ *            keeps no bitmap and launches the unmasked scan again.  An index whose documents were all removed compacts to a valid
+ *            empty index.  Blocking.  It allocates FRESH storage for the live rows and gathers them on the device, so the peak is old
+ *            + new; on an allocation failure -3 and the index unchanged.
+ *   save     writes path + ".tmp" and renames it to path.  load: a new index of the context from a file, NULL + a line on stderr for
+ *            any failure.  A loaded index answers every search and rescore with the saved one's ids and bits; its dim need not be the
+ *            context's n_embd (the text routes still refuse a mismatch).  A save with removals keeps the removed documents' rows and
+ *            the bitmap: compact first to drop them.  Rows move between the file and HBM in pieces of 32 MiB: no host copy of the
+ *            whole index is ever held.
+ *   Stream capture.  The bitmap's words are updated in place, so a graph captured while the bitmap exists sees later removes.  The
+ *            first remove (unmasked -> masked kernel, a new pointer), a compact and a growth of the storage change the kernel or the
+ *            pointers a captured search holds: capture the graph again after any of them.
+ * File form (little-endian); the file is exactly this long:
+ *   header, 64 bytes: magic "BHIPTOK1", u32 version = 1, u32 dim, u32 n_docs, u32 has_live, u64 n_tokens, 32 zero bytes;
+ *   n_docs + 1 i32 cumulative lengths, starting at 0;
+ *   n_tokens x dim f16 rows exactly as stored;
+ *   if has_live: ceil(n_docs / 32) u32 live words, the bits at and beyond n_docs zero.
+ * A file's bytes are a function of the documents and removals alone.  load checks, in this order: the header against the file's
+ * length, before anything is allocated (version 1, dim a multiple of 8 in 8 .. 1024, n_tokens < 2^31, n_docs <= n_tokens, has_live
+ * 0 .. 1, reserved bytes zero; the length in 64-bit arithmetic: the largest file needs 42 bits); the cumulative lengths start at 0,
+ * ascend strictly and end at n_tokens — which is what keeps the scan's reads in bounds; no live bit at or beyond n_docs.  Rows load as
+ * they are.                                                                                                                          */
+BERT_API int32_t bert_hip_late_index_remove(struct bert_hip_token_index *ix, int32_t n, const int32_t *ids);
+BERT_API int32_t bert_hip_late_index_n_live(struct bert_hip_token_index *ix);
+BERT_API int64_t bert_hip_late_index_n_live_tokens(struct bert_hip_token_index *ix);
+BERT_API int32_t bert_hip_late_index_search_filtered(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *qcu, const float *q_rows,
+                                                     int32_t k, const uint32_t *allow, int32_t n_words, int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_late_index_search_filtered_device(struct bert_hip_token_index *ix, int32_t n_queries, const int32_t *d_qcu,
+                                                            const void *d_q, int32_t max_q_len, int32_t k, const uint32_t *d_allow,
+                                                            int32_t n_words, int32_t *d_ids, float *d_scores, void *stream);
+BERT_API int32_t bert_hip_late_index_compact(struct bert_hip_token_index *ix, int32_t *old_ids);
+BERT_API int32_t bert_hip_late_index_save(struct bert_hip_token_index *ix, const char *path);
+BERT_API struct bert_hip_token_index *bert_hip_late_index_load(struct bert_ctx *ctx, const char *path);
 
 BERT_API const char *bert_hip_version(void);
 

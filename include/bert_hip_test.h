@@ -309,6 +309,14 @@ BERT_API int32_t bert_hip_test_hybrid_chunk(int32_t n_rows, int32_t nq, int32_t 
  * planned; 1 .. 4096 = that many slices, never more than documents).  0; -2 and zeros for n_docs < 0, nq < 1 or pref outside 0 .. 4096;
  * -1 for a NULL plan.                                                                                                              */
 BERT_API int32_t bert_hip_test_token_index_plan(int32_t n_docs, int32_t nq, int32_t pref, int32_t *plan);
+/* The checks bert_hip_late_index_load runs on a file (token_index_file.h; the format is in bert_hip.h "LATE INDEX"), without a device.
+ * _header: buf holds the first buf_len bytes of a file of file_bytes bytes; 0 and fields = {version, dim, n_docs, has_live, the low
+ * and the high 32 bits of n_tokens} for a header this build loads, -1 and the reason in err (err_cap bytes) otherwise.  _body: fields
+ * as _header returned them and the body_len bytes of the file behind its header; 0 if the cumulative lengths and the live words pass
+ * (the rows are not looked at), -1 and the reason in err otherwise (a body_len that is not what the fields describe included).      */
+BERT_API int32_t bert_hip_test_late_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err,
+                                                 int32_t err_cap);
+BERT_API int32_t bert_hip_test_late_index_body(const uint32_t *fields, const void *body, int64_t body_len, char *err, int32_t err_cap);
 
 #ifdef __cplusplus
 }
