@@ -1,6 +1,6 @@
 // token_index.cpp — the host side of the token index (token_index.h): storage and its growth, the add forms, the search and its
 // chunks, rescoring, reading a document back, the checks of the host forms, the live bits, compaction and the file form.  Every kernel
-// is in token_index.hip, maxsim.hip or search.hip (the merge, the live bits of added documents) and reached through
+// is in token_index.hip, token_index_i8.hip (the int8 form), maxsim.hip or search.hip (the merge, the live bits of added documents) and reached through
 // token_index_kernels.h / kernels.h / search_kernels.h.
 #include <hip/hip_runtime.h>
 
@@ -58,13 +58,16 @@ bool token_cu_ok(const int32_t *cu, int n) {
     return ok;
 }
 
-TokenIndex *TokenIndex::create(Engine *eng, int dim, std::string &err) {
+TokenIndex *TokenIndex::create(Engine *eng, int dim, int dtype, std::string &err) {
     if (!eng) { err = "no device engine"; return nullptr; }
     if (dim < 8 || dim > MAXSIM_MAX_H || dim % 8) { err = "dim must be a multiple of 8 in 8 .. " + std::to_string(MAXSIM_MAX_H); return nullptr; }
+    if (dtype != 1 && dtype != 2) { err = "dtype must be 1 (f16) or 2 (int8)"; return nullptr; }
     DeviceGuard g(eng->device());
     TokenIndex *ix = new TokenIndex;
     ix->eng_ = eng;
     ix->dim_ = dim;
+    ix->dtype_ = dtype;
+    ix->dpad_ = token_i8_dpad(dim);
     ix->cu_h_.assign(1, 0);
     const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
                     hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
@@ -72,6 +75,7 @@ TokenIndex *TokenIndex::create(Engine *eng, int dim, std::string &err) {
     // (cu[0] = 0 is there from the start: an empty index is searched like any other)
     if (!ix->grow_storage(1, 0, err)) { delete ix; return nullptr; }
     token_index_kernels_init();
+    if (dtype == 2) token_i8_kernels_init();
     return ix;
 }
 
@@ -80,6 +84,7 @@ TokenIndex::~TokenIndex() {
     if (busy_) { (void)hipEventSynchronize(busy_); (void)hipEventDestroy(busy_); }
     if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
     if (rows_) (void)hipFree(rows_);
+    if (scales_) (void)hipFree(scales_);
     if (cu_) (void)hipFree(cu_);
     if (live_) (void)hipFree(live_);
 }
@@ -125,17 +130,27 @@ bool TokenIndex::grow_storage(long long n_docs, long long n_tokens, std::string 
     }
     if (n_tokens > cap_tok_) {
         const long long cap = std::min<long long>(INT_MAX, std::max<long long>({n_tokens, (long long)cap_tok_ * 3 / 2, 4096}));
-        half_t *pr = nullptr;
-        const size_t row_bytes = (size_t)dim_ * 2;
-        if (hipMalloc((void **)&pr, (size_t)cap * row_bytes) != hipSuccess) { (void)hipGetLastError(); err = "hipMalloc (token index rows) failed"; return false; }
-        if (n_tok_ > 0 && hipMemcpy(pr, rows_, (size_t)n_tok_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
+        char *pr = nullptr;
+        float *ps = nullptr;                                 // (the int8 form's scales grow with its codes)
+        const size_t row_bytes = this->row_bytes();
+        if (hipMalloc((void **)&pr, (size_t)cap * row_bytes) != hipSuccess || (dtype_ == 2 && hipMalloc((void **)&ps, (size_t)cap * 4) != hipSuccess)) {
+            (void)hipGetLastError();
+            if (pr) (void)hipFree(pr);
+            err = "hipMalloc (token index rows) failed";
+            return false;
+        }
+        if (n_tok_ > 0 && (hipMemcpy(pr, rows_, (size_t)n_tok_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess ||
+                           (ps && hipMemcpy(ps, scales_, (size_t)n_tok_ * 4, hipMemcpyDeviceToDevice) != hipSuccess))) {
             (void)hipGetLastError();
             (void)hipFree(pr);
+            if (ps) (void)hipFree(ps);
             err = "hipMemcpy (token index rows) failed";
             return false;
         }
         if (rows_) (void)hipFree(rows_);
+        if (scales_) (void)hipFree(scales_);
         rows_ = pr;
+        scales_ = ps;
         cap_tok_ = cap;
     }
     return true;
@@ -144,6 +159,16 @@ bool TokenIndex::grow_storage(long long n_docs, long long n_tokens, std::string 
 bool TokenIndex::grow_search(int n_docs, int nqc, int k, std::string &err) {
     const size_t ent = ws_entries_bound(n_docs, nqc, k, eng_->options().token_index_slices);
     return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err);
+}
+
+bool TokenIndex::grow_queries(int nqc, int max_q_len, std::string &err) {
+    const size_t slots = (size_t)nqc * max_q_len;
+    return grow(q_codes_, slots * dpad_, err) && grow(q_scales_, slots * 4, err);
+}
+
+void TokenIndex::quantize_rows(const void *d_src, bool src_f32, long long n, long long at, hipStream_t s) {
+    TokenI8QuantizeArgs qa{d_src, (int8_t *)rows_ + (size_t)at * dpad_, scales_ + at, n, dim_, dpad_};
+    eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, src_f32, s); });
 }
 
 int TokenIndex::reserve(int n_docs, int64_t n_tokens, int n_queries, int max_q_len, int k, std::string &err) {
@@ -155,6 +180,7 @@ int TokenIndex::reserve(int n_docs, int64_t n_tokens, int n_queries, int max_q_l
     if (!grow_storage(n_docs, n_tokens, err)) return -3;
     const int nqc = std::min(n_queries, QCHUNK);
     if (nqc == 0) return 0;
+    if (dtype_ == 2 && !grow_queries(nqc, max_q_len, err)) return -3;
     return grow_search(std::max(n_docs, n_), nqc, k, err) ? 0 : -3;
 }
 
@@ -186,7 +212,12 @@ int TokenIndex::add_device(int n_docs, const int32_t *cu, const half_t *d_rows, 
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
     const long long T = (long long)cu[n_docs] - cu[0];
     if (!grow_storage((long long)n_ + n_docs, n_tok_ + T, err)) return -3;
-    HIP_OK(hipMemcpyAsync(rows_ + (size_t)n_tok_ * dim_, d_rows + (size_t)cu[0] * dim_, (size_t)T * dim_ * 2, hipMemcpyDeviceToDevice, s), err, -3);
+    if (dtype_ == 2) {
+        quantize_rows(d_rows + (size_t)cu[0] * dim_, false, T, n_tok_, s);
+        HIP_OK(hipGetLastError(), err, -3);
+    } else {
+        HIP_OK(hipMemcpyAsync(rows_ + (size_t)n_tok_ * row_bytes(), d_rows + (size_t)cu[0] * dim_, (size_t)T * dim_ * 2, hipMemcpyDeviceToDevice, s), err, -3);
+    }
     const int first = n_;
     if (!commit(n_docs, cu, s, err)) return -3;
     if (!eng_->op_end(op, err)) return -3;
@@ -207,7 +238,8 @@ int TokenIndex::add_host(int n_docs, const int32_t *cu, const float *rows, std::
     for (long long t0 = 0; t0 < T; t0 += per) {
         const size_t c = (size_t)std::min(per, T - t0);
         bool ok = hipMemcpyAsync(stage_.p, rows + (size_t)(cu[0] + t0) * dim_, c * dim_ * 4, hipMemcpyHostToDevice, stream_) == hipSuccess;
-        if (ok) eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), rows_ + (size_t)(n_tok_ + t0) * dim_, c * dim_, stream_); });
+        if (ok && dtype_ == 2) quantize_rows(stage_.p, true, (long long)c, n_tok_ + t0, stream_);
+        else if (ok) eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), (half_t *)rows_ + (size_t)(n_tok_ + t0) * dim_, c * dim_, stream_); });
         ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(stream_) == hipSuccess;
         if (!ok) { (void)hipStreamSynchronize(stream_); err = "add: copy to the device failed"; return -3; }
     }
@@ -221,7 +253,8 @@ int TokenIndex::add_host(int n_docs, const int32_t *cu, const float *rows, std::
 half_t *TokenIndex::append_room(int64_t n_tokens, std::string &err) {
     if (n_tokens < 0 || n_tok_ + n_tokens > INT_MAX) { err = "add: an index holds fewer than 2^31 tokens"; return nullptr; }
     if (!grow_storage(n_, n_tok_ + n_tokens, err)) return nullptr;
-    return rows_ + (size_t)n_tok_ * dim_;
+    if (dtype_ == 2) return grow(text_rows_, std::max<size_t>((size_t)n_tokens * dim_ * 2, 16), err) ? text_rows_.as<half_t>() : nullptr;
+    return (half_t *)rows_ + (size_t)n_tok_ * dim_;
 }
 
 int TokenIndex::add_in_place(int n_docs, const int32_t *cu, std::string &err) {
@@ -232,6 +265,12 @@ int TokenIndex::add_in_place(int n_docs, const int32_t *cu, std::string &err) {
     if (!grow_storage((long long)n_ + n_docs, n_tok_, err)) return -3;
     Engine::StreamOp op;
     if (!eng_->op_begin(stream_, busy_, op, err)) return -3;
+    if (dtype_ == 2) {
+        // (the chunk's f16 rows wait in append_room's buffer, enqueued on stream() in front of this)
+        if ((size_t)cu[n_docs] * dim_ * 2 > text_rows_.bytes) { err = "add: the rows in place do not match the room asked for"; return -2; }
+        quantize_rows(text_rows_.p, false, cu[n_docs], n_tok_, stream_);
+        HIP_OK(hipGetLastError(), err, -3);
+    }
     const int first = n_;
     if (!commit(n_docs, cu, stream_, err)) return -3;
     if (!eng_->op_end(op, err)) return -3;
@@ -260,11 +299,32 @@ int TokenIndex::get_doc(int id, float *rows, int cap_tokens, std::string &err) {
     const int len = cu_h_[(size_t)id + 1] - cu_h_[(size_t)id];
     if (!rows || cap_tokens < len) return len;
     DeviceGuard g(eng_->device());
+    if (dtype_ == 2) {
+        std::vector<int8_t> codes((size_t)len * dpad_);
+        std::vector<float> sc((size_t)len);
+        if (const int r = get_codes(id, codes.data(), sc.data(), len, err); r < 0) return r;
+        for (int t = 0; t < len; ++t)
+            for (int e = 0; e < dim_; ++e) rows[(size_t)t * dim_ + e] = (float)codes[(size_t)t * dpad_ + e] * sc[(size_t)t];
+        return len;
+    }
     std::vector<half_t> h((size_t)len * dim_);
     HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
-    HIP_OK(hipMemcpyAsync(h.data(), rows_ + (size_t)cu_h_[(size_t)id] * dim_, h.size() * 2, hipMemcpyDeviceToHost, stream_), err, -3);
+    HIP_OK(hipMemcpyAsync(h.data(), (const half_t *)rows_ + (size_t)cu_h_[(size_t)id] * dim_, h.size() * 2, hipMemcpyDeviceToHost, stream_), err, -3);
     HIP_OK(hipStreamSynchronize(stream_), err, -3);
     for (size_t i = 0; i < h.size(); ++i) rows[i] = (float)h[i];
+    return len;
+}
+
+int TokenIndex::get_codes(int id, int8_t *codes, float *scales, int cap_tokens, std::string &err) {
+    if (dtype_ != 2) { err = "get_codes: the index holds f16 rows (dtype 1), not int8 codes"; return -2; }
+    if (id < 0 || id >= n_) { err = "get_codes: id " + std::to_string(id) + " outside [0, " + std::to_string(n_) + ")"; return -2; }
+    const int t0 = cu_h_[(size_t)id], len = cu_h_[(size_t)id + 1] - t0;
+    if (!codes || !scales || cap_tokens < len) return len;
+    DeviceGuard g(eng_->device());
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
+    HIP_OK(hipMemcpyAsync(codes, rows_ + (size_t)t0 * dpad_, (size_t)len * dpad_, hipMemcpyDeviceToHost, stream_), err, -3);
+    HIP_OK(hipMemcpyAsync(scales, scales_ + t0, (size_t)len * 4, hipMemcpyDeviceToHost, stream_), err, -3);
+    HIP_OK(hipStreamSynchronize(stream_), err, -3);
     return len;
 }
 
@@ -273,6 +333,11 @@ int TokenIndex::get_doc(int id, float *rows, int cap_tokens, std::string &err) {
 // ------------------------------------------------------------------------------------------------
 int TokenIndex::search_device(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
                               std::string &err, const uint32_t *d_allow) {
+    return search_any(nq, d_qcu, d_q, false, max_q_len, k, d_ids, d_scores, s, err, d_allow);
+}
+
+int TokenIndex::search_any(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *d_ids, float *d_scores,
+                           hipStream_t s, std::string &err, const uint32_t *d_allow) {
     if (const int go = check_search(nq, d_qcu, d_q, k, d_ids, d_scores, err); go <= 0) return go;
     if (max_q_len < 1 || max_q_len > max_query_tokens()) { err = "search: max_q_len must be 1 .. " + std::to_string(max_query_tokens()) + " at dim " + std::to_string(dim_); return -2; }
     if ((uintptr_t)d_q & 15) { err = "search: the query rows must be 16-byte aligned"; return -2; }
@@ -280,17 +345,32 @@ int TokenIndex::search_device(int nq, const int32_t *d_qcu, const half_t *d_q, i
     Engine::StreamOp op;
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
     if (!grow_search(n_, std::min(nq, QCHUNK), k, err)) return -3;
+    if (dtype_ == 2 && !grow_queries(std::min(nq, QCHUNK), max_q_len, err)) return -3;
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         TokenScanPlan p;
         token_index_plan(n_, c, eng_->options().token_index_slices, p);       // (the key's range is the option's: never refused)
-        TokenScanArgs a;
-        a.rows = rows_; a.cu = cu_; a.q = d_q; a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
-        a.n_docs = n_; a.dim = dim_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
-        a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
-        // (removed documents or an allow-list: the masked kernel, the same plan and workspace; an empty index has no words to read)
-        if (n_ > 0) { a.live = live_; a.allow = d_allow; }
-        eng_->timed_launch(a.live || a.allow ? "token_index_scan_masked" : "token_index_scan", 0.0, s, [&] { launch_token_scan(a, s); });
+        if (dtype_ == 2) {
+            // the chunk's queries into the workspace (the kernel applies the scan's guards to d_qcu), then the int8 scan: the f16 scan's
+            // plan, workspace and merge
+            TokenI8QuantizeArgs qa{d_q, q_codes_.as<int8_t>(), q_scales_.as<float>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
+            eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, q_f32, s); });
+            TokenI8ScanArgs a;
+            a.codes = (const int8_t *)rows_; a.scales = scales_; a.cu = cu_; a.q_codes = q_codes_.as<int8_t>(); a.q_scales = q_scales_.as<float>();
+            a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+            a.n_docs = n_; a.dim = dim_; a.dpad = dpad_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
+            a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
+            if (n_ > 0) { a.live = live_; a.allow = d_allow; }
+            eng_->timed_launch(a.live || a.allow ? "token_i8_scan_masked" : "token_i8_scan", 0.0, s, [&] { launch_token_i8_scan(a, s); });
+        } else {
+            TokenScanArgs a;
+            a.rows = (const half_t *)rows_; a.cu = cu_; a.q = (const half_t *)d_q; a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+            a.n_docs = n_; a.dim = dim_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
+            a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
+            // (removed documents or an allow-list: the masked kernel, the same plan and workspace; an empty index has no words to read)
+            if (n_ > 0) { a.live = live_; a.allow = d_allow; }
+            eng_->timed_launch(a.live || a.allow ? "token_index_scan_masked" : "token_index_scan", 0.0, s, [&] { launch_token_scan(a, s); });
+        }
         MergeArgs m;
         m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = p.n_slices * k; m.k = k; m.L = merge_L(k);
         m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
@@ -300,12 +380,12 @@ int TokenIndex::search_device(int nq, const int32_t *d_qcu, const half_t *d_q, i
     return eng_->op_end(op, err) ? 0 : -3;
 }
 
-int TokenIndex::search_device_to_host(int nq, const int32_t *d_qcu, const half_t *d_q, int max_q_len, int k, int32_t *ids, float *scores, std::string &err,
-                                      const uint32_t *d_allow) {
+int TokenIndex::search_to_host(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *ids, float *scores,
+                               std::string &err, const uint32_t *d_allow) {
     std::vector<int32_t> hid((size_t)nq * k);
     std::vector<float> hsc((size_t)nq * k);
     if (!grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
-    if (const int r = search_device(nq, d_qcu, d_q, max_q_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow); r != 0) {
+    if (const int r = search_any(nq, d_qcu, d_q, q_f32, max_q_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow); r != 0) {
         (void)hipStreamSynchronize(stream_);
         return r;
     }
@@ -327,14 +407,15 @@ int TokenIndex::stage_queries(const char *what, int nq, const int32_t *qcu, cons
     }
     const size_t T = (size_t)(qcu[nq] - qcu[0]), n = T * dim_;
     if (n > F32_TO_F16_MAX_N) { err = std::string(what) + ": more than 2^31 query values (tokens x dim) in one call"; return -2; }
-    if (!grow(stage_, n * 4, err) || !grow(q16_, n * 2, err) || !grow(qcu_in_, (size_t)(nq + 1) * 4, err)) return -3;
+    if (!grow(stage_, n * 4, err) || (dtype_ != 2 && !grow(q16_, n * 2, err)) || !grow(qcu_in_, (size_t)(nq + 1) * 4, err)) return -3;
     // (the previous host call has synchronised stream(): nothing reads the staged lengths any more)
     qcu_h_.resize((size_t)nq + 1);
     for (int i = 0; i <= nq; ++i) qcu_h_[i] = qcu[i] - qcu[0];
     HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
     HIP_OK(hipMemcpyAsync(stage_.p, q_rows + (size_t)qcu[0] * dim_, n * 4, hipMemcpyHostToDevice, stream_), err, -3);
     HIP_OK(hipMemcpyAsync(qcu_in_.p, qcu_h_.data(), qcu_h_.size() * 4, hipMemcpyHostToDevice, stream_), err, -3);
-    eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), q16_.as<half_t>(), n, stream_); });
+    // (the int8 form quantises the f32 rows where they are)
+    if (dtype_ != 2) eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), q16_.as<half_t>(), n, stream_); });
     HIP_OK(hipGetLastError(), err, -3);
     return 0;
 }
@@ -347,7 +428,7 @@ int TokenIndex::search_host(int nq, const int32_t *qcu, const float *q_rows, int
     if (const int r = stage_queries("search", nq, qcu, q_rows, max_query_tokens(), max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
     const uint32_t *d_allow = nullptr;
     if (!upload_allow(allow, d_allow, err)) { (void)hipStreamSynchronize(stream_); return -3; }
-    return search_device_to_host(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), max_len, k, ids, scores, err, d_allow);
+    return search_to_host(nq, qcu_in_.as<int32_t>(), dtype_ == 2 ? stage_.p : q16_.p, dtype_ == 2, max_len, k, ids, scores, err, d_allow);
 }
 
 // (the host form copies ceil(size / 32) words; behind stage_queries, which made stream() wait for the index's event)
@@ -367,6 +448,9 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
                                float *d_scores, hipStream_t s, std::string &err) {
     if (const int go = check_rescore(nq, d_qcu, d_q, n_cand, d_cand, k, d_ids, d_scores, err); go <= 0) return go;
     if ((uintptr_t)d_q & 15) { err = "rescore: the query rows must be 16-byte aligned"; return -2; }
+    // (the int8 form: the scan's kernel over the candidate lists; the device form knows no query length, so the launch is sized for the
+    // longest a search takes)
+    if (dtype_ == 2) return rescore_i8(nq, d_qcu, d_q, false, max_query_tokens(), n_cand, d_cand, k, d_ids, d_scores, s, err);
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
@@ -377,10 +461,42 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
         TokenPairsArgs pa{d_cand + (size_t)c0 * n_cand, pairs_.as<int32_t>(), ws_i_.as<int>(), c, n_cand, n_, live_};
         eng_->timed_launch("token_index_pairs", 0.0, s, [&] { launch_token_pairs(pa, s); });
         // (the index's own arrays are maxsim's document side; a pair (q, -1) is scored NaN and reads nothing)
-        MaxsimArgs ma{d_q, rows_, d_qcu + c0, cu_, pairs_.as<int32_t>(), ws_s_.as<float>(), c, n_, dim_, c * n_cand, 0, 0};
+        MaxsimArgs ma{d_q, (const half_t *)rows_, d_qcu + c0, cu_, pairs_.as<int32_t>(), ws_s_.as<float>(), c, n_, dim_, c * n_cand, 0, 0};
         eng_->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(ma, s, eng_->options().maxsim_launch_pairs); });
         MergeArgs m;
         m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
+        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
+        eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+    }
+    HIP_OK(hipGetLastError(), err, -3);
+    return eng_->op_end(op, err) ? 0 : -3;
+}
+
+// The int8 rescore: per chunk the queries into the workspace, token_i8_scan_kernel<false, true> over (query, slice of its candidate list)
+// — the search's plan with n_cand in the documents' place —, the merge of the slices' lists.  The workspace [nq][slices][k] grows on demand
+int TokenIndex::rescore_i8(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int n_cand, const int32_t *d_cand, int k,
+                           int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err) {
+    DeviceGuard g(eng_->device());
+    Engine::StreamOp op;
+    if (!eng_->op_begin(s, busy_, op, err)) return -3;
+    const int nqc = std::min(nq, QCHUNK), pref = eng_->options().token_index_slices;
+    const size_t ent = ws_entries_bound(n_cand, nqc, k, pref);
+    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow_queries(nqc, max_q_len, err)) return -3;
+    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
+        const int c = std::min(QCHUNK, nq - c0);
+        TokenScanPlan p;
+        token_index_plan(n_cand, c, pref, p);
+        TokenI8QuantizeArgs qa{d_q, q_codes_.as<int8_t>(), q_scales_.as<float>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
+        eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, q_f32, s); });
+        TokenI8ScanArgs a;
+        a.codes = (const int8_t *)rows_; a.scales = scales_; a.cu = cu_; a.q_codes = q_codes_.as<int8_t>(); a.q_scales = q_scales_.as<float>();
+        a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+        a.n_docs = n_; a.dim = dim_; a.dpad = dpad_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
+        a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
+        a.live = live_; a.cand = d_cand + (size_t)c0 * n_cand; a.n_cand = n_cand;
+        eng_->timed_launch("token_i8_rescore", 0.0, s, [&] { launch_token_i8_scan(a, s); });
+        MergeArgs m;
+        m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = p.n_slices * k; m.k = k; m.L = merge_L(k);
         m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
         eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
     }
@@ -398,11 +514,13 @@ int TokenIndex::rescore_host(int nq, const int32_t *qcu, const float *q_rows, in
     std::vector<float> hsc((size_t)nq * k);
     if (!grow(cand_in_, (size_t)nq * n_cand * 4, err) || !grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
     int max_len = 0;
-    if (const int r = stage_queries("rescore", nq, qcu, q_rows, 0, max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
+    if (const int r = stage_queries("rescore", nq, qcu, q_rows, dtype_ == 2 ? max_query_tokens() : 0, max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
     auto fail = [&](int r) { (void)hipStreamSynchronize(stream_); return r; };
     if (hipMemcpyAsync(cand_in_.p, cand, (size_t)nq * n_cand * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { err = "rescore: copy to the device failed"; return fail(-3); }
-    if (const int r = rescore_device(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
-                                     out_scores_.as<float>(), stream_, err); r != 0) return fail(r);
+    if (const int r = dtype_ == 2 ? rescore_i8(nq, qcu_in_.as<int32_t>(), stage_.p, true, max_len, n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
+                                               out_scores_.as<float>(), stream_, err)
+                                  : rescore_device(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
+                                                   out_scores_.as<float>(), stream_, err); r != 0) return fail(r);
     if (hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
         hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
         hipStreamSynchronize(stream_) != hipSuccess) { err = "rescore: copy of the results failed"; return fail(-3); }
@@ -480,6 +598,7 @@ int TokenIndex::remove(int n, const int32_t *ids, std::string &err) {
 }
 
 int TokenIndex::compact(int32_t *old_ids, std::string &err) {
+    if (dtype_ == 2) { err = "compact: not available for an int8 token index"; return -2; }
     DeviceGuard g(eng_->device());
     HIP_OK(hipEventSynchronize(busy_), err, -3);
     HIP_OK(hipStreamSynchronize(stream_), err, -3);
@@ -510,7 +629,7 @@ int TokenIndex::compact(int32_t *old_ids, std::string &err) {
              (nl > 0 && hipMemcpyAsync(d_map, map.data(), (size_t)nl * 4, hipMemcpyHostToDevice, stream_) != hipSuccess)) failed = "hipMemcpy (compaction ids) failed";
     else {
         if (nl > 0) {
-            TokenGatherArgs a{rows_, pr, cu_, pc, d_map, nl, dim_};
+            TokenGatherArgs a{(const half_t *)rows_, pr, cu_, pc, d_map, nl, dim_};
             eng_->timed_launch("token_index_gather", 0.0, stream_, [&] { launch_token_gather(a, stream_); });
         }
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) failed = "the gather kernel failed";
@@ -526,7 +645,7 @@ int TokenIndex::compact(int32_t *old_ids, std::string &err) {
     }
     if (rows_) (void)hipFree(rows_);
     if (cu_) (void)hipFree(cu_);
-    rows_ = pr; cu_ = pc;
+    rows_ = (char *)pr; cu_ = pc;
     cap_tok_ = ntl; cap_docs_ = cap;
     n_ = nl; n_tok_ = ntl;
     cu_h_.swap(ncu);

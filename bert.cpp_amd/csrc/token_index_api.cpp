@@ -2,7 +2,8 @@
 // device.  The text routes tokenize and pack as bert_hip_encode_tokens_batch does and run the token-rows pass with flags 1 | 2 (each
 // row over its L2 norm, f16) in chunks of chunk_tokens: add_texts straight into the index's storage, search_texts into a device buffer
 // the scan reads in place.  The rows never reach the host.  Behind them the bert_hip_late_index_* entry points: the same index's
-// remove, filtered searches, compact, save and load.
+// remove, filtered searches, compact, save and load, and the int8 form's create, dtype and get_codes (an int8 index hands add_texts a
+// buffer of its own for the f16 rows and quantises from there: TokenIndex::append_room).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -96,18 +97,14 @@ bool text_dim_ok(const bert_ctx *ctx, const TokenIndex &x, std::string &err) {
     return false;
 }
 
-}  // namespace
-
-extern "C" {
-
-struct bert_hip_token_index *bert_hip_token_index_create(struct bert_ctx *ctx, int32_t dim) {
-    return guarded("bert_hip_token_index_create", [&]() -> bert_hip_token_index * {
-        const char *me = "bert_hip_token_index_create";
+// bert_hip_token_index_create (dtype 1) and bert_hip_late_index_create
+bert_hip_token_index *create_token_index(const char *me, bert_ctx *ctx, int32_t dim, int32_t dtype) {
+    return guarded(me, [&]() -> bert_hip_token_index * {
         if (!ctx) { fprintf(stderr, "%s: no context\n", me); return nullptr; }
         if (!ctx->engine()) { fprintf(stderr, "%s: this context has no device (tokenizer-only): an index lives on the context's device\n", me); return nullptr; }
         if (dim == 0) dim = ctx->hp.n_embd;
         std::string err;
-        std::unique_ptr<TokenIndex> ix(TokenIndex::create(ctx->engine(), dim, err));
+        std::unique_ptr<TokenIndex> ix(TokenIndex::create(ctx->engine(), dim, dtype, err));
         if (!ix) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return nullptr; }
         std::unique_ptr<bert_hip_token_index> h(new bert_hip_token_index);
         h->ctx = ctx;
@@ -115,6 +112,14 @@ struct bert_hip_token_index *bert_hip_token_index_create(struct bert_ctx *ctx, i
         ctx->token_indexes.push_back(h.get());
         return h.release();
     }, (bert_hip_token_index *)nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+struct bert_hip_token_index *bert_hip_token_index_create(struct bert_ctx *ctx, int32_t dim) {
+    return create_token_index("bert_hip_token_index_create", ctx, dim, 1);
 }
 
 void bert_hip_token_index_free(struct bert_hip_token_index *ix) {
@@ -263,6 +268,7 @@ int32_t bert_hip_late_index_compact(struct bert_hip_token_index *ix, int32_t *ol
 int32_t bert_hip_late_index_save(struct bert_hip_token_index *ix, const char *path) {
     return token_index_call("bert_hip_late_index_save", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t {
         if (!path || !*path) { err = "a path is required"; return -2; }
+        if (x.dtype() == 2) { err = "save: not available for an int8 token index"; return -2; }
         return x.save(path, err) ? 0 : -3;
     });
 }
@@ -290,6 +296,21 @@ struct bert_hip_token_index *bert_hip_late_index_load(struct bert_ctx *ctx, cons
         ctx->token_indexes.push_back(out.get());
         return out.release();
     }, (bert_hip_token_index *)nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the int8 form (bert_hip.h "TOKEN INDEX, int8 form"): every entry point above takes such an index as it takes an f16 one
+// ------------------------------------------------------------------------------------------------
+struct bert_hip_token_index *bert_hip_late_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype) {
+    return create_token_index("bert_hip_late_index_create", ctx, dim, dtype);
+}
+
+int32_t bert_hip_late_index_dtype(struct bert_hip_token_index *ix) { return ix && ix->ix ? ix->ix->dtype() : -1; }
+
+int32_t bert_hip_late_index_get_codes(struct bert_hip_token_index *ix, int32_t id, int8_t *codes, float *scales, int32_t cap_tokens) {
+    return token_index_call("bert_hip_late_index_get_codes", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t {
+        return x.get_codes(id, codes, scales, cap_tokens, err);
+    });
 }
 
 }  // extern "C"

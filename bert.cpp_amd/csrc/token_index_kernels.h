@@ -8,6 +8,7 @@
 //
 // A scan workgroup stages one query in LDS as ceil(n / 32) blocks of 32 rows of dim + 8 halfs (maxsim's padding), then a list of L
 // (score, id) entries and a count: token_scan_lds_bytes.
+// The int8 form of the same index (token_index_i8.hip) is stated below, behind the f16 kernels' arguments.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,8 +101,64 @@ struct TokenGatherArgs {
     int n, dim;
 };
 
+// ------------------------------------------------------------------------------------------------
+// The int8 form (token_index_i8.hip; bert_hip.h "TOKEN INDEX, int8 form").  Stored form: int8 codes[n_tokens][dpad] (dpad = dim rounded
+// up to a multiple of 32, the padding zero, rows 16-byte aligned), float scales[n_tokens] and the same cu.  A row x is scale = amax / 127
+// and code_i = clamp(rint(x_i / scale), -127, 127) — search.hip's index_quantize_kernel, word for word: all codes 0 where the scale is 0;
+// scale NaN and codes 0 where an element is NaN or +-inf.  Queries are quantised the same way, per token, into a workspace of
+// [nq][max_q_len] rows (query qi's token t at row qi * max_q_len + t), so the scan finds a query's rows without its neighbours' lengths.
+// ------------------------------------------------------------------------------------------------
+inline int token_i8_dpad(int dim) { return (dim + 31) & ~31; }
+// blocks * 32 * (dpad + 16) bytes of query codes (the padding of 16 bytes is the f16 kernel's + 8 halfs), 512 bytes of query scales,
+// the list, the count
+inline size_t token_i8_scan_lds_bytes(int dim, int max_q_len, int k) {
+    return (size_t)token_query_blocks(max_q_len) * TOKEN_QB * (token_i8_dpad(dim) + 16) + TOKEN_MAX_QUERY * 4 + (size_t)token_list_L(k) * 8 + 16;
+}
+// as token_max_query_tokens; 128 at every dim (dim 1024, 128 tokens, the longest list: 137 744 bytes, below TOKEN_LDS_MAX)
+inline int token_i8_max_query_tokens(int dim) {
+    const size_t block = (size_t)TOKEN_QB * (token_i8_dpad(dim) + 16), room = TOKEN_LDS_MAX - TOKEN_MAX_QUERY * 4 - (size_t)512 * 8 - 16;
+    return (int)std::min<size_t>(TOKEN_MAX_QUERY, room / block * TOKEN_QB);
+}
+
+// token_i8_quantize_kernel: rows of dim values (f32 or f16: f16 is converted exactly) -> codes and scales, one wave per row.
+// qcu == nullptr: rows src[0 .. n) -> rows 0 .. n - 1 of codes / scales.  qcu != nullptr (the queries of a search): n = nq * max_q_len
+// slots; slot qi * max_q_len + t takes row qcu[qi] + t of src where the query passes the scan's guards (not empty, not descending, not
+// starting below 0, at most max_q_len tokens) and t is below its length, and is left alone otherwise: no row outside a query's range is read
+struct TokenI8QuantizeArgs {
+    const void *src;
+    int8_t *codes;
+    float *scales;
+    long long n;
+    int dim, dpad;
+    const int32_t *qcu = nullptr;
+    int max_q_len = 0;
+};
+
+// token_i8_scan_kernel.  LDS: token_i8_scan_lds_bytes(dim, max_q_len, k).  The fields of TokenScanArgs with the int8 arrays; cand
+// non-null (a rescore): the "documents" of a slice are positions of the query's candidate list cand[qi][0 .. n_cand), n_list = n_cand
+// takes n_docs' place in the plan, and live is tested per id (allow is not used)
+struct TokenI8ScanArgs {
+    const int8_t *codes;                // the index
+    const float *scales;
+    const int32_t *cu;                  // [n_docs + 1]
+    const int8_t *q_codes;              // the queries' workspace, [nq][max_q_len][dpad]
+    const float *q_scales;              // [nq][max_q_len]
+    const int32_t *qcu;                 // [nq + 1]
+    float *ws_s;                        // [nq][n_slices][k]
+    int *ws_i;
+    int n_docs, dim, dpad, nq, max_q_len, n_slices, slice_docs, k, L, n_items;
+    const uint32_t *live = nullptr;
+    const uint32_t *allow = nullptr;
+    const int32_t *cand = nullptr;      // [nq][n_cand]
+    int n_cand = 0;
+};
+
 // lets the scan kernels of the current device have TOKEN_LDS_MAX of LDS
 void token_index_kernels_init();
+void token_i8_kernels_init();
+// (src_f32: the rows are f32, else f16; more rows than one launch takes go in several)
+void launch_token_i8_quantize(const TokenI8QuantizeArgs &a, bool src_f32, hipStream_t s);
+void launch_token_i8_scan(const TokenI8ScanArgs &a, hipStream_t s);
 void launch_token_scan(const TokenScanArgs &a, hipStream_t s);
 void launch_token_pairs(const TokenPairsArgs &a, hipStream_t s);
 void launch_token_gather(const TokenGatherArgs &a, hipStream_t s);

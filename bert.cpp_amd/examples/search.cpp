@@ -5,7 +5,7 @@
 //
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
 //               [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N]
-//   bert-search -m MODEL -f TEXTS --late [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]
+//   bert-search -m MODEL -f TEXTS --late [--i8] [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]
 //   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
 //   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]
 //   (--hybrid SPLADE: hybrid search.  SPLADE is a second model file, one with the MLM head, loaded into a context of its own (it may be
@@ -36,7 +36,10 @@
 //   Not together with --long, --sparse, --hybrid, --cross, --save, --load.)
 //   (--late: late-interaction search without a dense stage.  Every line's token rows go into a token index; each query line is answered
 //   by bert_hip_token_index_search_texts, the exact top-k of the MaxSim score over ALL lines.  A query of more tokens than the index's
-//   bert_hip_token_index_max_query_tokens is refused.  With -m, -f, -k, -t, --save-tokens and --load-tokens only.)
+//   bert_hip_token_index_max_query_tokens is refused.  With -m, -f, -k, -t, --i8, --save-tokens and --load-tokens only.)
+//   (--i8 with --late or with --maxsim N --token-index: the token index is an int8 one (bert_hip_late_index_create with dtype 2: int8
+//   codes and a scale per token); with --maxsim N --token-index the dense index is the int8 one too, as --i8 says without a token
+//   index.  Not together with --save-tokens or --load-tokens: an int8 token index has no file form.)
 //   (--save-tokens PATH / --load-tokens PATH, with --late or with --maxsim N --token-index: the token index goes to PATH once it is built
 //   (bert_hip_late_index_save), or comes from PATH instead of the lines being encoded (bert_hip_late_index_load) — TEXTS is still read,
 //   for printing, and must have as many lines as the index has documents.  --save and --load are the dense index's and stay refused.)
@@ -70,7 +73,7 @@
 namespace {
 void usage(const char *argv0) {
     fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
-    fprintf(stderr, "       %s -m MODEL -f TEXTS --late [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
+    fprintf(stderr, "       %s -m MODEL -f TEXTS --late [--i8] [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
     fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]\n", argv0);
     fprintf(stderr, "  --hybrid SPLADE: hybrid search: the lines in an embedding index of DENSE and a sparse index of SPLADE (a model file with the MLM head; W\n"
@@ -86,7 +89,9 @@ void usage(const char *argv0) {
     fprintf(stderr, "  --token-index: with --maxsim N: the lines' token rows are kept in a token index (bert_hip_token_index_add_texts) and the candidates are\n"
                     "          scored from it (bert_hip_token_index_rescore) instead of being encoded again; the same lines and scores are printed.\n");
     fprintf(stderr, "  --late: no dense stage: the lines' token rows in a token index, each query answered by bert_hip_token_index_search_texts, the exact\n"
-                    "          top-k by MaxSim score over all lines.  With -m, -f, -k, -t, --save-tokens and --load-tokens only.\n");
+                    "          top-k by MaxSim score over all lines.  With -m, -f, -k, -t, --i8, --save-tokens and --load-tokens only.\n");
+    fprintf(stderr, "  --i8 with --late or with --maxsim N --token-index: the token index stores int8 codes and a scale per token (bert_hip_late_index_create,\n"
+                    "          dtype 2); not with --save-tokens or --load-tokens: an int8 token index has no file form.\n");
     fprintf(stderr, "  --save-tokens PATH, --load-tokens PATH: with --late or with --maxsim N --token-index: the token index is written to PATH once it is built\n"
                     "          (bert_hip_late_index_save), or read from PATH instead of encoding TEXTS (bert_hip_late_index_load; TEXTS is still read for printing).\n");
     fprintf(stderr, "  --cross-model PATH --cross N: the search returns N candidates (k <= N <= 256), which a cross-encoder (a model file with a classification\n"
@@ -156,7 +161,10 @@ int main(int argc, char **argv) {
         fprintf(stderr, "search: --save-tokens and --load-tokens go with --late or with --maxsim N --token-index\n");
         return 2;
     }
-    if (late && (maxsim || dtype != 1 || n_cand || n_lists || nprobe || sparse_f16)) { fprintf(stderr, "search: --late goes with -m, -f, -k and -t only\n"); return 2; }
+    // (--i8 beside a token index: the token index is an int8 one, which has no file form)
+    const bool token_i8 = dtype == 2 && (late || token_index);
+    if (token_i8 && (save_tokens || load_tokens)) { fprintf(stderr, "search: --i8 with a token index does not go with --save-tokens or --load-tokens\n"); return 2; }
+    if (late && (maxsim || (dtype != 1 && dtype != 2) || n_cand || n_lists || nprobe || sparse_f16)) { fprintf(stderr, "search: --late goes with -m, -f, -k, -t and --i8 only\n"); return 2; }
     if (hybrid_model && (sparse || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model || save || load)) {
         fprintf(stderr, "search: --hybrid goes with -m, -f, -k, -t, --sparse-width, --weights, --f32, --i8, --b1 and --f16 only\n");
         return 2;
@@ -324,7 +332,7 @@ int main(int argc, char **argv) {
                 return nullptr;
             }
         } else {
-            t = bert_hip_token_index_create(ctx, 0);
+            t = token_i8 ? bert_hip_late_index_create(ctx, 0, 2) : bert_hip_token_index_create(ctx, 0);
             if (!t || bert_hip_token_index_add_texts(t, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
                 fprintf(stderr, "search: could not build the token index\n");
                 return nullptr;

@@ -55,6 +55,7 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_token_index_search_texts", "bert_hip_token_index_rescore", "bert_hip_token_index_rescore_device",
     "bert_hip_late_index_remove", "bert_hip_late_index_n_live", "bert_hip_late_index_n_live_tokens", "bert_hip_late_index_search_filtered",
     "bert_hip_late_index_search_filtered_device", "bert_hip_late_index_compact", "bert_hip_late_index_save", "bert_hip_late_index_load",
+    "bert_hip_late_index_create", "bert_hip_late_index_dtype", "bert_hip_late_index_get_codes",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -252,6 +253,9 @@ def _declare_product_abi(L):
     L.bert_hip_late_index_compact.restype = i32; L.bert_hip_late_index_compact.argtypes = [vp, vp]
     L.bert_hip_late_index_save.restype = i32; L.bert_hip_late_index_save.argtypes = [vp, C.c_char_p]
     L.bert_hip_late_index_load.restype = vp; L.bert_hip_late_index_load.argtypes = [vp, C.c_char_p]
+    L.bert_hip_late_index_create.restype = vp; L.bert_hip_late_index_create.argtypes = [vp, i32, i32]
+    L.bert_hip_late_index_dtype.restype = i32; L.bert_hip_late_index_dtype.argtypes = [vp]
+    L.bert_hip_late_index_get_codes.restype = i32; L.bert_hip_late_index_get_codes.argtypes = [vp, i32, vp, vp, i32]
 
 
 def lib() -> C.CDLL:
@@ -1200,10 +1204,10 @@ class BertModel:
         "f32" (i32 ids, f32 weights) | "f16" (u16 ids, f16 weights; n_vocab <= 65536); n_vocab None = the model's."""
         return BertSparseIndex(self, width, dtype, n_vocab)
 
-    def token_index(self, dim: Optional[int] = None) -> "BertTokenIndex":
+    def token_index(self, dim: Optional[int] = None, dtype: str = "f16") -> "BertTokenIndex":
         """A token index on the context's first device (bert_hip_token_index_create): documents' f16 token rows, exact MaxSim top-k
-        search; dim None = n_embd."""
-        return BertTokenIndex(self, dim)
+        search; dim None = n_embd.  dtype "i8": int8 codes with a scale per token (bert_hip_late_index_create)."""
+        return BertTokenIndex(self, dim, dtype=dtype)
 
     def load_index(self, path: str) -> "BertIndex":
         """The index a BertIndex.save wrote (bert_hip_index_load), on this context's first device."""
@@ -1785,8 +1789,13 @@ class BertTokenIndex:
     [n, k] f32), best first; missing entries are id -1, score -inf.  A ValueError is an argument the entry refused (-2).  The *_device
     forms take device pointers (ints) and a stream handle; search_device and rescore_device return at once."""
 
-    def __init__(self, model: BertModel, dim: Optional[int] = None, _load: Optional[str] = None):
+    DTYPES = {"f16": 1, "i8": 2}
+
+    def __init__(self, model: BertModel, dim: Optional[int] = None, _load: Optional[str] = None, dtype: str = "f16"):
         self.model, self.lib = model, model.lib
+        if dtype not in self.DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(self.DTYPES)}")
+        self.dtype = dtype                                   # (a file holds f16 rows)
         if _load is not None:
             # dim comes from the file's header (include/bert_hip.h "LATE INDEX": u32 dim at byte 12)
             self.ix = self.lib.bert_hip_late_index_load(model.ctx, os.fsencode(_load))
@@ -1795,7 +1804,10 @@ class BertTokenIndex:
             with open(_load, "rb") as f:
                 self.dim = int(np.frombuffer(f.read(16), dtype="<u4")[3])
             return
-        self.ix = self.lib.bert_hip_token_index_create(model.ctx, 0 if dim is None else int(dim))
+        if dtype == "f16":
+            self.ix = self.lib.bert_hip_token_index_create(model.ctx, 0 if dim is None else int(dim))
+        else:
+            self.ix = self.lib.bert_hip_late_index_create(model.ctx, 0 if dim is None else int(dim), self.DTYPES[dtype])
         if not self.ix:
             raise RuntimeError("bert_hip_token_index_create failed (see stderr)")
         self.dim = model.n_embd if dim is None else int(dim)
@@ -1877,6 +1889,18 @@ class BertTokenIndex:
         if self.lib.bert_hip_token_index_get_doc(self.ix, doc_id, rows.ctypes.data, n) != n:
             raise RuntimeError("bert_hip_token_index_get_doc failed")
         return rows
+
+    def get_codes(self, doc_id: int):
+        """bert_hip_late_index_get_codes: the stored form of a document of an int8 index, (codes [length, dpad] int8, scales [length]
+        f32); a ValueError on an f16 index."""
+        n = self.lib.bert_hip_late_index_get_codes(self.ix, doc_id, None, None, 0)
+        if n < 0:
+            self._fail("bert_hip_late_index_get_codes", n)
+        codes = np.full((n, (self.dim + 31) // 32 * 32), 99, dtype=np.int8)
+        scales = np.full(n, np.nan, dtype=np.float32)
+        if self.lib.bert_hip_late_index_get_codes(self.ix, doc_id, codes.ctypes.data, scales.ctypes.data, n) != n:
+            raise RuntimeError("bert_hip_late_index_get_codes failed")
+        return codes, scales
 
     def search(self, q_rows, q_cu, k: int = 10, allow=None):
         """allow: None, or the documents that may be returned — a bool array of len(index) entries or uint32 words (allow_words):

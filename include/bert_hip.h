@@ -888,7 +888,8 @@ BERT_API int32_t bert_hip_hybrid_search_texts(struct bert_hip_index *dense, stru
  * Results: -1 without an index; -2 after a line on stderr for an argument the entry refuses; -3 on a device error; -4 for an exception.
  * Outputs are untouched on error.
  * Removing documents, allow-lists, compaction and files: "LATE INDEX" below.
- * Not covered: several GPUs; several queries per workgroup sharing document loads; residual or quantised token rows; a mean mode.   */
+ * Quantised token rows: "TOKEN INDEX, int8 form" below.
+ * Not covered: several GPUs; several queries per workgroup sharing document loads; residual token rows; a mean mode.   */
 struct bert_hip_token_index;
 BERT_API struct bert_hip_token_index *bert_hip_token_index_create(struct bert_ctx *ctx, int32_t dim);
 BERT_API void    bert_hip_token_index_free(struct bert_hip_token_index *ix);
@@ -969,6 +970,47 @@ BERT_API int32_t bert_hip_late_index_search_filtered_device(struct bert_hip_toke
 BERT_API int32_t bert_hip_late_index_compact(struct bert_hip_token_index *ix, int32_t *old_ids);
 BERT_API int32_t bert_hip_late_index_save(struct bert_hip_token_index *ix, const char *path);
 BERT_API struct bert_hip_token_index *bert_hip_late_index_load(struct bert_ctx *ctx, const char *path);
+
+/* TOKEN INDEX, int8 form: the same index with every token row stored as int8 codes and one f32 scale — dpad + 4 bytes per token (dpad:
+ * dim rounded up to a multiple of 32) against 2 dim: 388 against 768 at dim 384, 132 against 256 at dim 128, a ratio of
+ * (dpad + 4) / (2 dim).  The struct and every entry point of the two blocks above are shared: add (f32 host rows), add_device (f16 device
+ * rows), add_texts, get_doc, search, search_device, search_texts, rescore, rescore_device, reserve, size, n_tokens, max_query_tokens,
+ * remove, n_live, n_live_tokens and search_filtered[_device] take an int8 index with the inputs they take today.  The new names are
+ * bert_hip_late_index_* for the reason given under LATE INDEX.
+ *   create   dtype 1: the f16 form — exactly bert_hip_token_index_create(ctx, dim) —; dtype 2: the int8 form (the embedding index's code
+ *            for it); anything else: NULL + a line on stderr.  dim as there.
+ *   dtype    1 or 2; -1 without an index.
+ *   get_codes   returns document id's length in tokens; iff cap_tokens >= it (and both pointers are given), codes [length][dpad] and
+ *            scales [length] receive the stored form.  An f16 index, or an id outside [0, size): -2.  Blocking.
+ * Semantics:
+ *   - Stored rows.  The embedding index's int8 rule, per token: scale = amax / 127 in f32; code_i = clamp(rint(x_i / scale), -127, 127)
+ *     with IEEE division and round to nearest even; every code 0 where the scale is 0; where an element is NaN or +-inf the scale is
+ *     NaN and the codes are 0.  The padding up to dpad is zero.  f16 rows (add_device, the text routes) are converted to f32 exactly
+ *     and follow the same rule; add quantises its f32 rows as they are, without a detour through f16.  get_doc returns
+ *     (float)code * scale.
+ *   - Queries are quantised the same way, per token, on the device, into a workspace that reserve sizes with the search's: a
+ *     search_device within reserve's bounds still allocates nothing and may be captured.  The host forms quantise the f32 rows as
+ *     they are; the device forms and search_texts the f16 rows.
+ *   - Score.  With dot_ij = sum over e of qc_i[e] dc_j[e], an exact int32:  m_i = max over j of ((float)dot_ij * ds_j)  (the
+ *     conversion is exact, |dot| <= 1024 x 127^2 < 2^24; a document slot behind the document's end enters as -inf);  t_i = m_i * qs_i,
+ *     one multiply per query token behind the max;  the t_i are added exactly as the f16 form adds its maxima — blocks of 32 in the
+ *     butterfly order of a wavefront sum with +0 in the unused lanes and behind the query's end, the blocks' sums in ascending order
+ *     from +0.  Every operation is exact or one correctly rounded f32 operation in this order, so the score's bits are a function of
+ *     the two sets of rows alone, and the determinism, order and slot rules of the TOKEN INDEX block hold word for word (slicing, k,
+ *     batch neighbours, add history, growth, host or device entry on the same values, search against rescore).
+ *   - Non-finite rows.  A document that holds a token whose scale is NaN scores NaN and is never returned; a query that holds such a
+ *     token gets k slots of -1 / -INFINITY, its neighbours untouched.
+ *   - Query length.  The query's codes are staged in LDS as rows of dpad + 16 bytes, 512 bytes of scales beside them: 128 tokens fit at
+ *     every dim (dim 1024: 137 744 bytes with the longest list), so max_query_tokens is 128 for every int8 index.
+ *   - rescore runs the search's kernel over the candidate lists (a workgroup per query and slice of its list, a wave per document as
+ *     in the search), not bert_hip_maxsim_device's.  It therefore stages the query as a search does: the host form refuses a query of
+ *     more than max_query_tokens tokens (-2), the device form gives it -1 / -INFINITY — where the f16 form's rescore has no limit.
+ *     The workspace grows on demand and is not part of reserve, as there.
+ * Not covered: compact and save of an int8 index (-2 after a line on stderr, the index unchanged and still searchable), and a file
+ * form: bert_hip_late_index_load keeps refusing anything but a BHIPTOK1 version 1 file, which holds f16 rows.                       */
+BERT_API struct bert_hip_token_index *bert_hip_late_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype);
+BERT_API int32_t bert_hip_late_index_dtype(struct bert_hip_token_index *ix);
+BERT_API int32_t bert_hip_late_index_get_codes(struct bert_hip_token_index *ix, int32_t id, int8_t *codes, float *scales, int32_t cap_tokens);
 
 BERT_API const char *bert_hip_version(void);
 
