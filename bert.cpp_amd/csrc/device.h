@@ -1,6 +1,6 @@
 // device.h — the device-side building blocks that more than one kernel file uses (gfx950): vector types, address-space casts,
 // compile-time loops, the in-kernel timeline stamps of the tuning builds, hand-issued LDS reads and the waits around them, the
-// tile swizzle, lane-crossing reductions, the softmax numerators, packed GELU, LayerNorm statistics, q4 block expansion and the
+// tile swizzle, lane-crossing reductions, the int8 row rule, the softmax numerators, packed GELU, LayerNorm statistics, q4 block expansion and the
 // per-lane LayerNorm of the fused kernels.  Host code includes kernels.h only.
 //
 // The kernels that stream weight tiles through LDS rings (gemm256.hip, layer_tail.hip, qkv_attention2.hip, skinny.hip): 128-row
@@ -167,6 +167,39 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
     return v;
+}
+
+// The int8 row rule of the embedding index (search.hip index_quantize_kernel) and the token index (token_index.hip
+// token_i8_quantize_kernel), the whole wave on one row: x[0 .. dim) (f32, or f16 converted exactly) -> scale = amax / 127 and codes
+// out[0 .. dpad) = clamp(rint(x_i / scale), -127, 127), zero from dim on.  All codes 0 where the scale is 0; scale NaN and codes 0 where an
+// element is NaN or +-inf.  The finite test and the maximum of |x_i| across the wave (a maximum is exact in any lane order), then four
+// codes per lane and 32-bit store.  dpad is a multiple of 32; the division is IEEE (correctly rounded), rint rounds to nearest even.
+template <class T>
+__device__ __forceinline__ void quantize_row_i8(const T *__restrict__ x, int dim, int dpad, int8_t *__restrict__ out, float *__restrict__ scale_out,
+                                                int lane) {
+    float amax = 0.f;
+    int bad = 0;
+    for (int c = lane; c < dim; c += 64) {
+        const float v = (float)x[c];
+        bad |= !__builtin_isfinite(v);                         // (fmaxf drops a NaN: tested on its own)
+        amax = fmaxf(amax, fabsf(v));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+    bad = __any(bad);
+    const float scale = bad ? __builtin_nanf("") : amax / 127.0f;
+    const bool zero = bad || scale == 0.f;
+    if (lane == 0) *scale_out = scale;
+    for (int c = 4 * lane; c < dpad; c += 256) {
+        uint32_t packed = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float v = c + j < dim ? (float)x[c + j] : 0.f;
+            const float q = zero ? 0.f : fminf(fmaxf(__builtin_rintf(v / scale), -127.f), 127.f);
+            packed |= (uint32_t)(uint8_t)(int8_t)(int)q << (8 * j);
+        }
+        *(uint32_t *)(out + c) = packed;
+    }
 }
 
 // Softmax numerators of EIGHT scores of one query (registers 8 st .. 8 st + 7 of an S^T tile = the B fragment of one P·V MFMA

@@ -619,39 +619,13 @@ __global__ __launch_bounds__(256) void index_convert_kernel(const float *__restr
     }
 }
 
-// f32 rows [n][dim] -> i8 codes [n][dpad] and scales [n] (the i8 form above).  One wave per row: the finite test and the
-// maximum of |x_i| across the wave (a maximum is exact in any lane order), then four codes per lane and 32-bit store.
-// dpad is a multiple of 32; the division is IEEE (correctly rounded), rint rounds to nearest even.
+// f32 rows [n][dim] -> i8 codes [n][dpad] and scales [n] (the i8 form above).  One wave per row, by device.h's quantize_row_i8.
 __global__ __launch_bounds__(256) void index_quantize_kernel(const float *__restrict__ src, int8_t *__restrict__ codes,
                                                              float *__restrict__ scales, int n, int dim, int dpad) {
     const int lane = threadIdx.x & 63;
     const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= (size_t)n) return;                                // (the whole wave)
-    const float *x = src + r * dim;
-    float amax = 0.f;
-    int bad = 0;
-    for (int c = lane; c < dim; c += 64) {
-        const float v = x[c];
-        bad |= !__builtin_isfinite(v);                         // (fmaxf drops a NaN: tested on its own)
-        amax = fmaxf(amax, fabsf(v));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
-    bad = __any(bad);
-    const float scale = bad ? __builtin_nanf("") : amax / 127.0f;
-    const bool zero = bad || scale == 0.f;
-    if (lane == 0) scales[r] = scale;
-    int8_t *out = codes + r * dpad;
-    for (int c = 4 * lane; c < dpad; c += 256) {
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float v = c + j < dim ? x[c + j] : 0.f;
-            const float q = zero ? 0.f : fminf(fmaxf(__builtin_rintf(v / scale), -127.f), 127.f);
-            packed |= (uint32_t)(uint8_t)(int8_t)(int)q << (8 * j);
-        }
-        *(uint32_t *)(out + c) = packed;
-    }
+    quantize_row_i8(src + r * dim, dim, dpad, codes + r * dpad, scales + r, lane);
 }
 
 // f32 rows [n][dim] -> b1 rows [n][dpad / 32] words (the b1 form above).  One wave per row: a ballot of x > 0 is the 64 bits of

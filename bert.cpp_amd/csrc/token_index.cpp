@@ -1,6 +1,6 @@
 // token_index.cpp — the host side of the token index (token_index.h): storage and its growth, the add forms, the search and its
 // chunks, rescoring, reading a document back, the checks of the host forms, the live bits, compaction and the file form.  Every kernel
-// is in token_index.hip, token_index_i8.hip (the int8 form), maxsim.hip or search.hip (the merge, the live bits of added documents) and reached through
+// is in token_index.hip (both forms), maxsim.hip or search.hip (the merge, the live bits of added documents) and reached through
 // token_index_kernels.h / kernels.h / search_kernels.h.
 #include <hip/hip_runtime.h>
 
@@ -75,7 +75,6 @@ TokenIndex *TokenIndex::create(Engine *eng, int dim, int dtype, std::string &err
     // (cu[0] = 0 is there from the start: an empty index is searched like any other)
     if (!ix->grow_storage(1, 0, err)) { delete ix; return nullptr; }
     token_index_kernels_init();
-    if (dtype == 2) token_i8_kernels_init();
     return ix;
 }
 
@@ -341,60 +340,80 @@ int TokenIndex::search_any(int nq, const int32_t *d_qcu, const void *d_q, bool q
     if (const int go = check_search(nq, d_qcu, d_q, k, d_ids, d_scores, err); go <= 0) return go;
     if (max_q_len < 1 || max_q_len > max_query_tokens()) { err = "search: max_q_len must be 1 .. " + std::to_string(max_query_tokens()) + " at dim " + std::to_string(dim_); return -2; }
     if ((uintptr_t)d_q & 15) { err = "search: the query rows must be 16-byte aligned"; return -2; }
+    return scan_chunks(nq, d_qcu, d_q, q_f32, max_q_len, k, d_ids, d_scores, s, err, d_allow, nullptr, 0);
+}
+
+// The chunk loop of every search and of the int8 rescore: per chunk of up to QCHUNK queries the plan, the int8 form's queries into the
+// workspace (the kernel applies the scan's guards to d_qcu), the scan and the merge of the slices' lists.  A search (d_cand null) scans
+// the n_ documents under live_ / d_allow; a rescore scans the n_cand positions of each query's candidate list — the search's plan with
+// n_cand in the documents' place — and tests live_ per id.  The workspace [nq][slices][k] grows by the same bound over either count
+int TokenIndex::scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *d_ids, float *d_scores,
+                            hipStream_t s, std::string &err, const uint32_t *d_allow, const int32_t *d_cand, int n_cand) {
+    const bool i8 = dtype_ == 2;
+    const int n_list = d_cand ? n_cand : n_;
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
-    if (!grow_search(n_, std::min(nq, QCHUNK), k, err)) return -3;
-    if (dtype_ == 2 && !grow_queries(std::min(nq, QCHUNK), max_q_len, err)) return -3;
+    const int nqc = std::min(nq, QCHUNK), pref = eng_->options().token_index_slices;
+    if (!grow_search(n_list, nqc, k, err)) return -3;
+    if (i8 && !grow_queries(nqc, max_q_len, err)) return -3;
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         TokenScanPlan p;
-        token_index_plan(n_, c, eng_->options().token_index_slices, p);       // (the key's range is the option's: never refused)
-        if (dtype_ == 2) {
-            // the chunk's queries into the workspace (the kernel applies the scan's guards to d_qcu), then the int8 scan: the f16 scan's
-            // plan, workspace and merge
+        token_index_plan(n_list, c, pref, p);                 // (the key's range is the option's: never refused)
+        TokenScanArgs a;
+        a.rows = rows_; a.cu = cu_; a.q = d_q; a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
+        a.n_docs = n_; a.dim = dim_; a.dpad = dpad_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
+        a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
+        if (i8) {
             TokenI8QuantizeArgs qa{d_q, q_codes_.as<int8_t>(), q_scales_.as<float>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
             eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, q_f32, s); });
-            TokenI8ScanArgs a;
-            a.codes = (const int8_t *)rows_; a.scales = scales_; a.cu = cu_; a.q_codes = q_codes_.as<int8_t>(); a.q_scales = q_scales_.as<float>();
-            a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
-            a.n_docs = n_; a.dim = dim_; a.dpad = dpad_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
-            a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
-            if (n_ > 0) { a.live = live_; a.allow = d_allow; }
-            eng_->timed_launch(a.live || a.allow ? "token_i8_scan_masked" : "token_i8_scan", 0.0, s, [&] { launch_token_i8_scan(a, s); });
-        } else {
-            TokenScanArgs a;
-            a.rows = (const half_t *)rows_; a.cu = cu_; a.q = (const half_t *)d_q; a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
-            a.n_docs = n_; a.dim = dim_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
-            a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
-            // (removed documents or an allow-list: the masked kernel, the same plan and workspace; an empty index has no words to read)
-            if (n_ > 0) { a.live = live_; a.allow = d_allow; }
-            eng_->timed_launch(a.live || a.allow ? "token_index_scan_masked" : "token_index_scan", 0.0, s, [&] { launch_token_scan(a, s); });
+            a.scales = scales_; a.q = q_codes_.p; a.q_scales = q_scales_.as<float>();
         }
-        MergeArgs m;
-        m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = p.n_slices * k; m.k = k; m.L = merge_L(k);
-        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
-        eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+        // (removed documents or an allow-list: the masked kernel, the same plan and workspace; an empty index has no words to read)
+        if (d_cand) { a.live = live_; a.cand = d_cand + (size_t)c0 * n_cand; a.n_cand = n_cand; }
+        else if (n_ > 0) { a.live = live_; a.allow = d_allow; }
+        const bool masked = a.live || a.allow;
+        const char *label = d_cand ? "token_i8_rescore" : i8 ? (masked ? "token_i8_scan_masked" : "token_i8_scan") : (masked ? "token_index_scan_masked" : "token_index_scan");
+        eng_->timed_launch(label, 0.0, s, [&] { launch_token_scan(dtype_, a, s); });
+        merge_lists(c, p.n_slices * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -3);
     return eng_->op_end(op, err) ? 0 : -3;
 }
 
-int TokenIndex::search_to_host(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *ids, float *scores,
-                               std::string &err, const uint32_t *d_allow) {
+// the best k of each of c queries' n_cand workspace entries -> ids / scores [c][k]
+void TokenIndex::merge_lists(int c, int n_cand, int k, int32_t *d_ids, float *d_scores, hipStream_t s) {
+    MergeArgs m;
+    m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
+    m.ids = d_ids; m.scores = d_scores;
+    eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+}
+
+// out_ids_ / out_scores_ [nq][k], which a search or rescore (what) on stream() has filled -> host; the caller's arrays are written only on success
+int TokenIndex::results_to_host(const char *what, int nq, int k, int32_t *ids, float *scores, std::string &err) {
     std::vector<int32_t> hid((size_t)nq * k);
     std::vector<float> hsc((size_t)nq * k);
-    if (!grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
+    if (hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
+        hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
+        hipStreamSynchronize(stream_) != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);
+        err = std::string(what) + ": copy of the results failed";
+        return -3;
+    }
+    memcpy(ids, hid.data(), hid.size() * 4);
+    memcpy(scores, hsc.data(), hsc.size() * 4);
+    return 0;
+}
+
+int TokenIndex::search_to_host(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *ids, float *scores,
+                               std::string &err, const uint32_t *d_allow) {
+    if (!grow(out_ids_, (size_t)nq * k * 4, err) || !grow(out_scores_, (size_t)nq * k * 4, err)) return -3;
     if (const int r = search_any(nq, d_qcu, d_q, q_f32, max_q_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow); r != 0) {
         (void)hipStreamSynchronize(stream_);
         return r;
     }
-    HIP_OK(hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
-    HIP_OK(hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
-    HIP_OK(hipStreamSynchronize(stream_), err, -3);
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
-    return 0;
+    return results_to_host("search", nq, k, ids, scores, err);
 }
 
 int TokenIndex::stage_queries(const char *what, int nq, const int32_t *qcu, const float *q_rows, int limit, int &max_len, std::string &err) {
@@ -450,7 +469,7 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
     if ((uintptr_t)d_q & 15) { err = "rescore: the query rows must be 16-byte aligned"; return -2; }
     // (the int8 form: the scan's kernel over the candidate lists; the device form knows no query length, so the launch is sized for the
     // longest a search takes)
-    if (dtype_ == 2) return rescore_i8(nq, d_qcu, d_q, false, max_query_tokens(), n_cand, d_cand, k, d_ids, d_scores, s, err);
+    if (dtype_ == 2) return scan_chunks(nq, d_qcu, d_q, false, max_query_tokens(), k, d_ids, d_scores, s, err, nullptr, d_cand, n_cand);
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
@@ -463,42 +482,7 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
         // (the index's own arrays are maxsim's document side; a pair (q, -1) is scored NaN and reads nothing)
         MaxsimArgs ma{d_q, (const half_t *)rows_, d_qcu + c0, cu_, pairs_.as<int32_t>(), ws_s_.as<float>(), c, n_, dim_, c * n_cand, 0, 0};
         eng_->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(ma, s, eng_->options().maxsim_launch_pairs); });
-        MergeArgs m;
-        m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
-        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
-        eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
-    }
-    HIP_OK(hipGetLastError(), err, -3);
-    return eng_->op_end(op, err) ? 0 : -3;
-}
-
-// The int8 rescore: per chunk the queries into the workspace, token_i8_scan_kernel<false, true> over (query, slice of its candidate list)
-// — the search's plan with n_cand in the documents' place —, the merge of the slices' lists.  The workspace [nq][slices][k] grows on demand
-int TokenIndex::rescore_i8(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int n_cand, const int32_t *d_cand, int k,
-                           int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err) {
-    DeviceGuard g(eng_->device());
-    Engine::StreamOp op;
-    if (!eng_->op_begin(s, busy_, op, err)) return -3;
-    const int nqc = std::min(nq, QCHUNK), pref = eng_->options().token_index_slices;
-    const size_t ent = ws_entries_bound(n_cand, nqc, k, pref);
-    if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow_queries(nqc, max_q_len, err)) return -3;
-    for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
-        const int c = std::min(QCHUNK, nq - c0);
-        TokenScanPlan p;
-        token_index_plan(n_cand, c, pref, p);
-        TokenI8QuantizeArgs qa{d_q, q_codes_.as<int8_t>(), q_scales_.as<float>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
-        eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, q_f32, s); });
-        TokenI8ScanArgs a;
-        a.codes = (const int8_t *)rows_; a.scales = scales_; a.cu = cu_; a.q_codes = q_codes_.as<int8_t>(); a.q_scales = q_scales_.as<float>();
-        a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
-        a.n_docs = n_; a.dim = dim_; a.dpad = dpad_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
-        a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
-        a.live = live_; a.cand = d_cand + (size_t)c0 * n_cand; a.n_cand = n_cand;
-        eng_->timed_launch("token_i8_rescore", 0.0, s, [&] { launch_token_i8_scan(a, s); });
-        MergeArgs m;
-        m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = p.n_slices * k; m.k = k; m.L = merge_L(k);
-        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
-        eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+        merge_lists(c, n_cand, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -3);
     return eng_->op_end(op, err) ? 0 : -3;
@@ -510,23 +494,16 @@ int TokenIndex::rescore_host(int nq, const int32_t *qcu, const float *q_rows, in
     for (size_t i = 0; i < (size_t)nq * n_cand; ++i)
         if (cand[i] < -1 || cand[i] >= n_) { err = "rescore: candidate id " + std::to_string(cand[i]) + " is outside [-1, " + std::to_string(n_) + ")"; return -2; }
     DeviceGuard g(eng_->device());
-    std::vector<int32_t> hid((size_t)nq * k);
-    std::vector<float> hsc((size_t)nq * k);
-    if (!grow(cand_in_, (size_t)nq * n_cand * 4, err) || !grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
+    if (!grow(cand_in_, (size_t)nq * n_cand * 4, err) || !grow(out_ids_, (size_t)nq * k * 4, err) || !grow(out_scores_, (size_t)nq * k * 4, err)) return -3;
     int max_len = 0;
     if (const int r = stage_queries("rescore", nq, qcu, q_rows, dtype_ == 2 ? max_query_tokens() : 0, max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
     auto fail = [&](int r) { (void)hipStreamSynchronize(stream_); return r; };
     if (hipMemcpyAsync(cand_in_.p, cand, (size_t)nq * n_cand * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { err = "rescore: copy to the device failed"; return fail(-3); }
-    if (const int r = dtype_ == 2 ? rescore_i8(nq, qcu_in_.as<int32_t>(), stage_.p, true, max_len, n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
-                                               out_scores_.as<float>(), stream_, err)
+    if (const int r = dtype_ == 2 ? scan_chunks(nq, qcu_in_.as<int32_t>(), stage_.p, true, max_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err,
+                                                nullptr, cand_in_.as<int32_t>(), n_cand)
                                   : rescore_device(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
                                                    out_scores_.as<float>(), stream_, err); r != 0) return fail(r);
-    if (hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
-        hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
-        hipStreamSynchronize(stream_) != hipSuccess) { err = "rescore: copy of the results failed"; return fail(-3); }
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
-    return 0;
+    return results_to_host("rescore", nq, k, ids, scores, err);
 }
 
 // ------------------------------------------------------------------------------------------------

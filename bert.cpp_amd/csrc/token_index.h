@@ -8,10 +8,10 @@
 // Removed documents are a device bitmap with a host mirror, there from the first remove to the next compact; while it exists, or under
 // an allow-list, a search launches the masked scan and a rescore's pair list leaves the removed ids out.  compact gathers the live
 // documents' rows into a fresh allocation on the device; save / load move the file form (token_index_file.h) in pieces.
-// dtype 2, the int8 form (token_index_kernels.h states it; kernels: token_index_i8.hip): rows are int8 codes of dpad bytes with one f32
-// scale per token, every add quantises on the device, a search quantises its queries into a workspace that reserve sizes and scans
-// with token_i8_scan_kernel, and a rescore is the same kernel over the candidate lists instead of maxsim.  The bitmap, the event, the
-// streams, the chunking, commit and the host mirrors are the f16 form's.  compact, save and load are the f16 form's alone.
+// dtype 2, the int8 form (token_index_kernels.h states it): rows are int8 codes of dpad bytes with one f32 scale per token, every add
+// quantises on the device, a search quantises its queries into a workspace that reserve sizes and scans with token_index_scan_kernel's
+// int8 form, and a rescore is the same kernel over the candidate lists instead of maxsim.  The bitmap, the event, the streams, the
+// chunk loop, commit and the host mirrors are the f16 form's.  compact, save and load are the f16 form's alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,7 +44,7 @@ public:
     int dtype() const { return dtype_; }
     int dpad() const { return dpad_; }                   // int8 form: the bytes of a stored row
     // (the int8 form: 128 at every dim, and the limit of a rescore's queries too)
-    int max_query_tokens() const { return dtype_ == 2 ? token_i8_max_query_tokens(dim_) : token_max_query_tokens(dim_); }
+    int max_query_tokens() const { return token_max_query_tokens(dim_, dtype_); }
     hipStream_t stream() const { return stream_; }
 
     // Results: >= 0, or -2 (an argument the entry refuses; nothing changed) or -3 (a device error), a message in err either way.
@@ -122,8 +122,13 @@ private:
                    std::string &err, const uint32_t *d_allow);
     int search_to_host(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *ids, float *scores, std::string &err,
                        const uint32_t *d_allow);
-    int rescore_i8(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int n_cand, const int32_t *d_cand, int k, int32_t *d_ids,
-                   float *d_scores, hipStream_t s, std::string &err);
+    // the chunk loop behind every search (d_cand null: the documents under live_ / d_allow) and the int8 rescore (d_cand [nq][n_cand])
+    int scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
+                    std::string &err, const uint32_t *d_allow, const int32_t *d_cand, int n_cand);
+    // topk_merge over ws_s_ / ws_i_ [c][n_cand] -> d_ids / d_scores [c][k], on s
+    void merge_lists(int c, int n_cand, int k, int32_t *d_ids, float *d_scores, hipStream_t s);
+    // out_ids_ / out_scores_ [nq][k] -> host behind what stream() holds; blocking
+    int results_to_host(const char *what, int nq, int k, int32_t *ids, float *scores, std::string &err);
     // cu entries of n_docs new documents (lengths from cu, any base) behind the stored ones, on s; bumps the counts
     bool commit(int n_docs, const int32_t *cu, hipStream_t s, std::string &err);
     // queries of a host form: rows -> f16 in q16_ (the int8 form: left as f32 in stage_), lengths (rebased to 0) -> qcu_in_, on

@@ -1,14 +1,19 @@
-// token_index_kernels.h — the device code of the token index (token_index.hip) as its host side (token_index.cpp) sees it: the stored
-// form, the plan of a scan, the argument blocks and one launcher per kernel.  A launcher only enqueues: the caller reads
-// hipGetLastError.
+// token_index_kernels.h — the device code of the token index (token_index.hip) as its host side (token_index.cpp) sees it: the two
+// stored forms, the plan of a scan, the argument blocks and one launcher per kernel.  A launcher only enqueues: the caller reads
+// hipGetLastError.  dtype is the index's: 1 f16, 2 int8.
 //
-// Stored form.  half_t rows[n_tokens][dim], packed, 16-byte aligned (dim a multiple of 8 in 8 .. MAXSIM_MAX_H), and int32
+// Stored form, f16.  half_t rows[n_tokens][dim], packed, 16-byte aligned (dim a multiple of 8 in 8 .. MAXSIM_MAX_H), and int32
 // cu[n_docs + 1]: document d is rows cu[d] .. cu[d + 1] - 1, never empty — what maxsim.hip takes as its document side, so a rescore
 // hands the index's own arrays to launch_maxsim.
 //
-// A scan workgroup stages one query in LDS as ceil(n / 32) blocks of 32 rows of dim + 8 halfs (maxsim's padding), then a list of L
-// (score, id) entries and a count: token_scan_lds_bytes.
-// The int8 form of the same index (token_index_i8.hip) is stated below, behind the f16 kernels' arguments.
+// Stored form, int8 (bert_hip.h "TOKEN INDEX, int8 form").  int8 codes[n_tokens][dpad] (dpad = dim rounded up to a multiple of 32, the
+// padding zero, rows 16-byte aligned), float scales[n_tokens] and the same cu.  A row x is scale = amax / 127 and
+// code_i = clamp(rint(x_i / scale), -127, 127) — device.h's quantize_row_i8, the embedding index's rule: all codes 0 where the scale is 0;
+// scale NaN and codes 0 where an element is NaN or +-inf.  Queries are quantised the same way, per token, into a workspace of
+// [nq][max_q_len] rows (query qi's token t at row qi * max_q_len + t), so the scan finds a query's rows without its neighbours' lengths.
+//
+// A scan workgroup (token_index_scan_kernel, one kernel with a form per dtype) stages one query in LDS as ceil(n / 32) blocks of 32 rows
+// padded by 16 bytes, what else its form keeps beside them, then a list of L (score, id) entries and a count: token_scan_lds_bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,15 +41,20 @@ constexpr size_t TOKEN_LDS_MAX = 160 * 1024 - 256;
 // entries of the LDS list: the top-k ahead of a queue that takes a step's pushes
 inline int token_list_L(int k) { return k + TOKEN_STEP_DOCS <= 256 ? 256 : 512; }
 inline int token_query_blocks(int n) { return (n + TOKEN_QB - 1) / TOKEN_QB; }
-// 64 (dim + 8) ceil(n / 32) + 8 L + 16 bytes: the query's blocks, the list, the count
-inline size_t token_scan_lds_bytes(int dim, int max_q_len, int k) {
-    return (size_t)token_query_blocks(max_q_len) * TOKEN_QB * (dim + 8) * 2 + (size_t)token_list_L(k) * 8 + 16;
+inline int token_i8_dpad(int dim) { return (dim + 31) & ~31; }
+// What a form stages per query.  A block of 32 tokens: rows of dim + 8 halfs (maxsim's padding), or of dpad + 16 bytes of codes (the
+// same 16 bytes).  Beside the blocks: nothing, or the int8 form's 512 bytes of query scales
+inline size_t token_query_block_bytes(int dim, int dtype) { return (size_t)TOKEN_QB * (dtype == 2 ? token_i8_dpad(dim) + 16 : (dim + 8) * 2); }
+inline size_t token_query_extra_bytes(int dtype) { return dtype == 2 ? TOKEN_MAX_QUERY * 4 : 0; }
+// the query's blocks, the form's extra bytes, the list (8 L bytes), the count (16)
+inline size_t token_scan_lds_bytes(int dim, int dtype, int max_q_len, int k) {
+    return (size_t)token_query_blocks(max_q_len) * token_query_block_bytes(dim, dtype) + token_query_extra_bytes(dtype) + (size_t)token_list_L(k) * 8 + 16;
 }
-// the largest multiple of 32, at most TOKEN_MAX_QUERY, whose blocks fit TOKEN_LDS_MAX beside the longest list (dim <= 384: 128,
-// <= 768: 96, <= 1024: 64)
-inline int token_max_query_tokens(int dim) {
-    const size_t block = (size_t)TOKEN_QB * (dim + 8) * 2, room = TOKEN_LDS_MAX - (size_t)512 * 8 - 16;
-    return (int)std::min<size_t>(TOKEN_MAX_QUERY, room / block * TOKEN_QB);
+// the largest multiple of 32, at most TOKEN_MAX_QUERY, whose blocks fit TOKEN_LDS_MAX beside the longest list.  f16: dim <= 384: 128,
+// <= 768: 96, <= 1024: 64.  int8: 128 at every dim (dim 1024, 128 tokens, the longest list: 137 744 bytes)
+inline int token_max_query_tokens(int dim, int dtype) {
+    const size_t room = TOKEN_LDS_MAX - token_query_extra_bytes(dtype) - (size_t)512 * 8 - 16;
+    return (int)std::min<size_t>(TOKEN_MAX_QUERY, room / token_query_block_bytes(dim, dtype) * TOKEN_QB);
 }
 
 // How a chunk of nq queries over n_docs documents is cut into workgroups of token_index_scan_kernel: one workgroup per (query, slice
@@ -65,19 +75,25 @@ inline bool token_index_plan(int n_docs, int nq, int pref, TokenScanPlan &p) {
     return true;
 }
 
-// token_index_scan_kernel.  LDS: token_scan_lds_bytes(dim, max_q_len, k)
+// token_index_scan_kernel, both forms.  LDS: token_scan_lds_bytes(dim, dtype, max_q_len, k)
 struct TokenScanArgs {
-    const half_t *rows;                 // the index
+    const void *rows;                   // the index: half_t [n_tokens][dim], or int8 codes [n_tokens][dpad]
+    const float *scales = nullptr;      // int8: [n_tokens]
     const int32_t *cu;                  // [n_docs + 1]
-    const half_t *q;                    // the queries' rows, indexed by qcu
+    const void *q;                      // f16: the queries' rows, indexed by qcu.  int8: the queries' workspace, codes [nq][max_q_len][dpad]
+    const float *q_scales = nullptr;    // int8: [nq][max_q_len]
     const int32_t *qcu;                 // [nq + 1]
     float *ws_s;                        // [nq][n_slices][k] per-(query, slice) lists, best first
     int *ws_i;
-    int n_docs, dim, nq, max_q_len, n_slices, slice_docs, k, L, n_items;
+    int n_docs, dim, dpad, nq, max_q_len, n_slices, slice_docs, k, L, n_items;
     // the masked instantiation (either non-null): words [ceil(n_docs / 32)], bit d & 31 of word d >> 5 set = document d is live / may
     // be returned; a null pointer = all ones.  No word at or beyond ceil(n_docs / 32) is read
     const uint32_t *live = nullptr;
     const uint32_t *allow = nullptr;
+    // the listed instantiation (cand non-null; int8 only): a rescore.  The "documents" of a slice are positions of the query's candidate
+    // list cand[qi][0 .. n_cand), n_cand takes n_docs' place in the plan, and live is tested per id (allow is not used)
+    const int32_t *cand = nullptr;      // [nq][n_cand]
+    int n_cand = 0;
 };
 
 // token_index_pairs_kernel: cand [nq][n_cand] -> maxsim's pair list pairs [nq * n_cand][2] = (q, id), and ws_i [nq][n_cand] = id; an
@@ -101,25 +117,6 @@ struct TokenGatherArgs {
     int n, dim;
 };
 
-// ------------------------------------------------------------------------------------------------
-// The int8 form (token_index_i8.hip; bert_hip.h "TOKEN INDEX, int8 form").  Stored form: int8 codes[n_tokens][dpad] (dpad = dim rounded
-// up to a multiple of 32, the padding zero, rows 16-byte aligned), float scales[n_tokens] and the same cu.  A row x is scale = amax / 127
-// and code_i = clamp(rint(x_i / scale), -127, 127) — search.hip's index_quantize_kernel, word for word: all codes 0 where the scale is 0;
-// scale NaN and codes 0 where an element is NaN or +-inf.  Queries are quantised the same way, per token, into a workspace of
-// [nq][max_q_len] rows (query qi's token t at row qi * max_q_len + t), so the scan finds a query's rows without its neighbours' lengths.
-// ------------------------------------------------------------------------------------------------
-inline int token_i8_dpad(int dim) { return (dim + 31) & ~31; }
-// blocks * 32 * (dpad + 16) bytes of query codes (the padding of 16 bytes is the f16 kernel's + 8 halfs), 512 bytes of query scales,
-// the list, the count
-inline size_t token_i8_scan_lds_bytes(int dim, int max_q_len, int k) {
-    return (size_t)token_query_blocks(max_q_len) * TOKEN_QB * (token_i8_dpad(dim) + 16) + TOKEN_MAX_QUERY * 4 + (size_t)token_list_L(k) * 8 + 16;
-}
-// as token_max_query_tokens; 128 at every dim (dim 1024, 128 tokens, the longest list: 137 744 bytes, below TOKEN_LDS_MAX)
-inline int token_i8_max_query_tokens(int dim) {
-    const size_t block = (size_t)TOKEN_QB * (token_i8_dpad(dim) + 16), room = TOKEN_LDS_MAX - TOKEN_MAX_QUERY * 4 - (size_t)512 * 8 - 16;
-    return (int)std::min<size_t>(TOKEN_MAX_QUERY, room / block * TOKEN_QB);
-}
-
 // token_i8_quantize_kernel: rows of dim values (f32 or f16: f16 is converted exactly) -> codes and scales, one wave per row.
 // qcu == nullptr: rows src[0 .. n) -> rows 0 .. n - 1 of codes / scales.  qcu != nullptr (the queries of a search): n = nq * max_q_len
 // slots; slot qi * max_q_len + t takes row qcu[qi] + t of src where the query passes the scan's guards (not empty, not descending, not
@@ -134,32 +131,12 @@ struct TokenI8QuantizeArgs {
     int max_q_len = 0;
 };
 
-// token_i8_scan_kernel.  LDS: token_i8_scan_lds_bytes(dim, max_q_len, k).  The fields of TokenScanArgs with the int8 arrays; cand
-// non-null (a rescore): the "documents" of a slice are positions of the query's candidate list cand[qi][0 .. n_cand), n_list = n_cand
-// takes n_docs' place in the plan, and live is tested per id (allow is not used)
-struct TokenI8ScanArgs {
-    const int8_t *codes;                // the index
-    const float *scales;
-    const int32_t *cu;                  // [n_docs + 1]
-    const int8_t *q_codes;              // the queries' workspace, [nq][max_q_len][dpad]
-    const float *q_scales;              // [nq][max_q_len]
-    const int32_t *qcu;                 // [nq + 1]
-    float *ws_s;                        // [nq][n_slices][k]
-    int *ws_i;
-    int n_docs, dim, dpad, nq, max_q_len, n_slices, slice_docs, k, L, n_items;
-    const uint32_t *live = nullptr;
-    const uint32_t *allow = nullptr;
-    const int32_t *cand = nullptr;      // [nq][n_cand]
-    int n_cand = 0;
-};
-
-// lets the scan kernels of the current device have TOKEN_LDS_MAX of LDS
+// lets every scan instantiation of the current device have TOKEN_LDS_MAX of LDS
 void token_index_kernels_init();
-void token_i8_kernels_init();
+// the instantiation of dtype's form: listed if a.cand is set (int8 only), else masked if a.live or a.allow is, else plain
+void launch_token_scan(int dtype, const TokenScanArgs &a, hipStream_t s);
 // (src_f32: the rows are f32, else f16; more rows than one launch takes go in several)
 void launch_token_i8_quantize(const TokenI8QuantizeArgs &a, bool src_f32, hipStream_t s);
-void launch_token_i8_scan(const TokenI8ScanArgs &a, hipStream_t s);
-void launch_token_scan(const TokenScanArgs &a, hipStream_t s);
 void launch_token_pairs(const TokenPairsArgs &a, hipStream_t s);
 void launch_token_gather(const TokenGatherArgs &a, hipStream_t s);
 

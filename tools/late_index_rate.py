@@ -6,7 +6,7 @@ alternating within each round.
 
     workloads: 10^5 documents of 180 tokens (13.8 GB of rows) and 10^6 documents of 25 tokens (19.2 GB), generated on the device
 
-    plain       bert_hip_token_index_search_device on an index without removals: token_index_scan_kernel<false>
+    plain       bert_hip_token_index_search_device on an index without removals: token_index_scan_kernel<F16Form, false, false>
     parent      the same call through ANOTHER build of the library (--parent-lib PATH: the commit before the life cycle), its own context
                 and its own copy of the same rows: the check that the plain path did not change, against the spread the run shows
     masked all  bert_hip_late_index_search_filtered_device with every document allowed: the mask's cost
