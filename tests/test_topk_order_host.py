@@ -1,6 +1,6 @@
-"""CPU proof that the fixtures of test_gpu_topk_order.py reach the queue states they are built for (tests/topk_order_reference.py: the
-patterns and the host model of the selecting kernels' queue).  The geometry comes from the hooks the searches themselves plan with
-(bert_hip_test_index_plan, bert_hip_test_sparse_scan_geometry[_qb]); the model never calls the library.  A fixture that stops reaching
+"""CPU proof that the fixtures of test_gpu_topk_order.py, test_gpu_token_index_order.py and test_gpu_token_scan_forms.py reach the
+queue states they are built for (tests/topk_order_reference.py: the patterns and the host model of the selecting kernels' queue).
+The geometry comes from the hooks the searches themselves plan with (bert_hip_test_index_plan, bert_hip_test_sparse_scan_geometry[_qb]); the model never calls the library.  A fixture that stops reaching
 its state — after a change of a list length, a step or a plan — fails here, not silently on the GPU.  Every test prints the reached
 state of its fixtures (pytest -s)."""
 import os
@@ -422,3 +422,206 @@ def test_token_many_slices_reach_a_second_merge_round():
     asc = m["walks"][tor.TOKEN_KINDS.index("asc")]
     assert asc["pushed_late"][0] and asc["sorts"] >= 2                 # every slice beats the ones before: the merge refills
     print(tor.describe(fx.name, res))
+
+
+# ------------------------------------------------------------------------------------------------
+# token_index_scan_kernel: the int8 form, the masked and the listed instantiations
+# ------------------------------------------------------------------------------------------------
+def _one_slice(fx, kind, k, ok=True):
+    """the single-slice walk of one kind of a token fixture"""
+    return tor.token_search(fx.scores[kind][None], k, 1, fx.n, ok)
+
+
+def test_int8_token_fixtures_keep_the_ranks_order_at_every_sign_and_length():
+    """a quantised row keeps its one nonzero column exactly: score[a] < score[b] iff rank[a] < rank[b], equal iff equal, for every
+    pattern, both signs and both query lengths (asserted when a fixture is made; restated here on the raw scores), the expected bits
+    being token_i8_reference.scores_i8 of the rows"""
+    import token_i8_reference as t8
+
+    for k in tor.TOKEN_KS:
+        for pattern in tor.TOKEN_I8_PATTERNS:
+            fx = tor.token_i8_fixture(pattern, k)
+            assert fx.n == tor.TOKEN_DOCS and sorted(set(fx.lens.tolist())) == sorted(tor.TOKEN_DOC_LENS) and fx.cu[-1] == len(fx.rows)
+            assert (np.count_nonzero(fx.rows, axis=1) <= 1).all() and not fx.rows[:, 1:].any()
+            r = fx.ranks
+            for kk, sign in ((fx.pos, 1), (fx.neg, -1)):
+                s = fx.scores[kk].astype(np.float64) * sign
+                order = np.argsort(r, kind="stable")
+                assert ((np.diff(s[order]) > 0) == (np.diff(r[order]) > 0)).all() and ((np.diff(s[order]) == 0) == (np.diff(r[order]) == 0)).all(), (fx.name, kk)
+            assert (fx.scores[fx.neg][r > 0] < 0).all() and (fx.scores["const"] == 0).all()
+    fx = tor.token_i8_fixture("asc")
+    kinds, lens = tor.token_i8_layout(fx)
+    q, qcu = tor.token_i8_queries(kinds, lens)
+    sc = t8.scores_i8(q, qcu, fx.rows, fx.cu)
+    for i, kk in enumerate(kinds):
+        assert np.array_equal(sc[i].view(np.uint32), fx.scores[kk].view(np.uint32)), (kk, lens[i])
+    # (not relied on: the scores are the integers themselves, but for a few that lie one ulp above — two roundings by the scales)
+    exact = fx.scores["asc"] == tor.values(fx.ranks)
+    assert np.array_equal(np.rint(fx.scores["asc"]), tor.values(fx.ranks))
+    print(f"{fx.name}: {int(exact.sum())} of {fx.n} ascending scores are the integers themselves, the others within {float(np.abs(fx.scores['asc'] - tor.values(fx.ranks)).max()):.1e}")
+
+
+@pytest.mark.parametrize("k", tor.TOKEN_KS)
+def test_int8_token_fixtures_reach_their_states(k):
+    L = tor.token_L(k)
+    room = L - k - tor.TOKEN_STEP
+    by = {}
+    for pattern in tor.TOKEN_I8_PATTERNS:
+        fx = tor.token_i8_fixture(pattern, k)
+        S = np.stack([fx.scores[kk] for kk in fx.kinds])
+        res = tor.token_search(S, k, 1, fx.n)
+        same(res, S, True, k, (fx.name, "one slice"))
+        for kk, w in zip(fx.kinds, res["wgs"]):
+            by[(pattern, kk)] = w
+            assert w["max_slot"] < L and w["steps"] == 25 and w["room"] == room
+        print(tor.describe(f"{fx.name}, one slice at k={k}", res))
+        n_slices, slice_docs = libbert.test_token_index_plan(fx.n, 2 * len(fx.kinds), 0)
+        assert slice_docs == 17 and n_slices > 17
+        same(tor.token_search(S, k, n_slices, slice_docs), S, True, k, (fx.name, "planned"))
+    stair, over, asc = by[("stair", "stair")], by[("over", "over")], by[("asc", "asc")]
+    assert stair["max_slot"] == L - 1 and stair["fit_stale"][0], (k, "exact fit, stale threshold", stair["max_slot"])
+    assert over["near_miss"][0], (k, "one document more than fits: sorted, then a whole step")
+    assert asc["max_slot"] == TOKEN_ASC_SLOT[k] and asc["pushed_late"][0]
+    if room == 0:
+        assert asc["sorts"] == asc["steps"] and asc["sort_steps"] == list(range(25)), (k, "a sort at every step")
+    # all ties (const), and every document worse than the one before (desc): the first k ids
+    for key in [(pattern, "const") for pattern in tor.TOKEN_I8_PATTERNS] + [("asc", "desc")]:
+        assert by[key]["ids"][0].tolist() == list(range(k)), (k, key)
+
+
+def test_int8_token_many_slices_reach_a_second_merge_round():
+    k, n = tor.TOKEN_MANY_K, tor.TOKEN_MANY_DOCS
+    fx = tor.token_i8_fixture("asc", n=n)
+    n_slices, slice_docs = libbert.test_token_index_plan(n, 2 * len(fx.kinds), tor.TOKEN_MANY_SLICES)
+    assert n_slices == 17 and slice_docs % tor.TOKEN_STEP != 0 and slice_docs % 4 != 0
+    S = np.stack([fx.scores[kk] for kk in fx.kinds])
+    res = tor.token_search(S, k, n_slices, slice_docs)
+    same(res, S, True, k, fx.name)
+    m = res["merge"]
+    assert m["n_cand"] == 4352 > tor.MERGE_OUTER and m["rounds"] == 2 and m["walks"][0]["pushed_late"][0] and m["walks"][0]["sorts"] >= 2
+    print(tor.describe(fx.name, res))
+
+
+@pytest.mark.parametrize("k", tor.TOKEN_KS)
+def test_masked_token_fixtures_reach_their_states(k):
+    """fit_mask over the ascending pattern, for the f16 and the int8 fixture alike (both are ascending under "asc"): the exact fit while
+    the threshold is still -inf, the near miss, steps without a qualifying document, slices that start inside a mask word"""
+    L = tor.token_L(k)
+    room = L - k - tor.TOKEN_STEP
+    ok, ok1 = tor.token_masks(k)
+    assert not ok.all() and not ok1.all() and ok.sum() > 256 and not np.array_equal(ok, ok1)
+    for fx in (tor.token_fixture(k), tor.token_i8_fixture("asc")):
+        S = np.stack([fx.scores[kk] for kk in tor.TOKEN_MASK_KINDS])
+        for mask, name in ((ok, "exact fit"), (ok1, "near miss")):
+            res = tor.token_search(S, k, 1, fx.n, mask)
+            same(res, S, mask, k, (fx.name, name, "one slice"))
+            asc = res["wgs"][0]
+            if name == "exact fit":
+                assert asc["max_slot"] == L - 1 and asc["fit_fresh"][0], (fx.name, k, "exact fit, threshold still -inf", asc["max_slot"])
+            else:
+                assert asc["near_miss"][0], (fx.name, k, "one document more than fits")
+            print(tor.describe(f"{fx.name} masked k={k} {name} one slice", res))
+            for slices in (0, 7):
+                n_slices, slice_docs = libbert.test_token_index_plan(fx.n, 2 * len(tor.TOKEN_MASK_KINDS), slices)
+                assert slice_docs == (17 if slices == 0 else 225)
+                # the three-word mask: a slice, and so every step of it, starts inside a word
+                assert any((s * slice_docs) & 31 for s in range(n_slices)), (slices, slice_docs)
+                cut = tor.token_search(S, k, n_slices, slice_docs, mask)
+                same(cut, S, mask, k, (fx.name, name, slices))
+                assert max(w["max_slot"] for w in cut["wgs"]) < L
+    if room == 0:
+        # the kernel's `m == 0` skip: whole 64-aligned steps of the single-slice walk without a qualifying document
+        steps = [ok[b:b + tor.TOKEN_STEP] for b in range(0, len(ok), tor.TOKEN_STEP)]
+        assert sum(not s.any() for s in steps) >= 1 and any(s.all() for s in steps)
+    for mode in tor.TOKEN_MASK_MODES:
+        for mask in (ok, ok1):
+            removed, allow = tor.token_mask_mode(mask, mode)
+            assert (mode == "allow") == (len(removed) == 0) and (mode == "removed") == (allow is None)
+            if mode == "both":
+                assert 0 < len(removed) < (~mask).sum() and not allow.all()
+
+
+def _same_listed(res, S, cand, removed, k):
+    import token_index_reference as tref
+
+    want = tref.rescore_expected(tor.list_scores(S, cand, removed), np.tile(cand, (len(S), 1)), k)
+    return np.array_equal(res["ids"], want[0]) and np.array_equal(res["scores"].view(np.uint32), want[1].view(np.uint32))
+
+
+@pytest.mark.parametrize("k", tor.TOKEN_KS)
+def test_listed_fixtures_reach_their_states(k):
+    """one slice of 1024 positions is 16 steps: the exact fit (fresh through the holes, stale through the staircase of ids) and both near
+    misses for every k; the planned rescore's 64 slices of 16 positions reach the merge's second round at k = 256"""
+    L = tor.token_L(k)
+    fx = tor.listed_fixture()
+    assert fx.n == tor.LIST_DOCS == 1024 and fx.scores["asc"][0] == 0 and (np.diff(fx.scores["asc"]) > 0).all()
+    S = np.stack([fx.scores[kk] for kk in fx.kinds])
+    lists = tor.candidate_lists(k)
+    assert tor.staircase_lead(k, L, tor.TOKEN_STEP) + 5 <= 16
+    state = {}
+    for name, (cand, removed) in lists.items():
+        valid = tor.list_valid(cand, removed)
+        res = tor.listed_search(S, cand, valid, k, 1, len(cand))
+        assert _same_listed(res, S, cand, removed, k), (k, name, "one slice")
+        state[name] = res["wgs"][0]                                                  # (the "asc" query)
+        assert res["wgs"][0]["steps"] == 16
+        print(tor.describe(f"listed k={k} {name} one slice", res))
+        n_slices, slice_pos = libbert.test_token_index_plan(len(cand), len(S), 0)
+        assert (n_slices, slice_pos) == (64, 16)
+        planned = tor.listed_search(S, cand, valid, k, n_slices, slice_pos)
+        assert _same_listed(planned, S, cand, removed, k), (k, name, "planned")
+        assert planned["merge"]["n_cand"] == 64 * k
+        if k == 256:
+            assert planned["merge"]["n_cand"] > tor.MERGE_OUTER and planned["merge"]["rounds"] >= 2
+    assert state["holes"]["max_slot"] == L - 1 and state["holes"]["fit_fresh"][0], (k, state["holes"]["max_slot"])
+    assert state["holes over"]["near_miss"][0], k
+    assert state["repeats"]["max_slot"] == L - 1 and state["repeats"]["fit_stale"][0], (k, state["repeats"]["max_slot"])
+    assert state["repeats over"]["near_miss"][0], k
+    # the holes are of all four kinds, and a removed id is a document that would have been pushed
+    cand, removed = lists["holes"]
+    assert (cand == -1).any() and (cand == tor.LIST_DOCS).any() and (cand == 2 ** 31 - 1).any() and len(removed) > 0 and (cand[removed] == removed).all()
+    # reversed: position order and id order disagree; repeats: document 0 is returned as often as it is named
+    cand, _ = lists["reversed"]
+    assert (np.diff(cand) < 0).all() and (np.diff(fx.scores["desc"][cand]) > 0).all()
+    cand, removed = lists["repeats"]
+    res = tor.listed_search(S, cand, tor.list_valid(cand, removed), k, 1, len(cand))
+    zeros = int((cand == 0).sum())
+    assert zeros > 1 and (res["ids"][1][:min(k, zeros)] == 0).all() and (k <= zeros or res["ids"][1][zeros] == 1)
+
+
+def test_wrong_models_disagree_with_the_order_rule():
+    """sensitivity, on the model alone: each deliberately wrong queue gives another result than the order rule on a new fixture (the
+    right one agrees on all of them, above).  No kernel is made wrong for this."""
+    fx = tor.listed_fixture()
+    S = np.stack([fx.scores[kk] for kk in fx.kinds])
+    found = {"a hole is pushed": [], "sorts only above room + 1": [], "positions for ids": []}
+    for k in tor.TOKEN_KS:
+        lists = tor.candidate_lists(k)
+        n = tor.LIST_DOCS
+        cand, removed = lists["holes"]
+        if not _same_listed(tor.listed_search(S, cand, np.ones(n, bool), k, 1, n), S, cand, removed, k):
+            found["a hole is pushed"].append(k)
+        for name in ("holes over", "repeats over"):
+            cand, removed = lists[name]
+            late = tor.listed_search(S, cand, tor.list_valid(cand, removed), k, 1, n, slack=1)
+            if not _same_listed(late, S, cand, removed, k):
+                found["sorts only above room + 1"].append((k, name))
+        cand, removed = lists["reversed"]
+        if not _same_listed(tor.listed_search(S, cand, tor.list_valid(cand, removed), k, 1, n, positions_for_ids=True), S, cand, removed, k):
+            found["positions for ids"].append(k)
+        # the same queue over documents: the int8 near miss and the masked near miss
+        over = tor.token_i8_fixture("over", k)
+        w = tor.walk(over.scores["over"][None], np.arange(over.n), True, k, tor.token_L(k), tor.TOKEN_STEP, slack=1)
+        want = tor.reference_topk(over.scores["over"][None], True, k)
+        if not np.array_equal(np.where(w["ids"] == tor.SENT, -1, w["ids"]), want[0]):
+            found["sorts only above room + 1"].append((k, "int8 over"))
+        asc, ok1 = tor.token_i8_fixture("asc"), tor.token_masks(k)[1]
+        w = tor.walk(asc.scores["asc"][None], np.arange(asc.n), ok1, k, tor.token_L(k), tor.TOKEN_STEP, slack=1)
+        if not np.array_equal(np.where(w["ids"] == tor.SENT, -1, w["ids"]), tor.reference_topk(asc.scores["asc"][None], ok1, k)[0]):
+            found["sorts only above room + 1"].append((k, "masked near miss"))
+    for what, where in found.items():
+        print(f"{what}: disagrees at {where}")
+        assert where, what
+    assert found["a hole is pushed"] == list(tor.TOKEN_KS) and found["positions for ids"] == list(tor.TOKEN_KS)
+    # (k = 1: the one document the late sort loses is overtaken by a later one of the rising pattern, so the end result cannot show it)
+    assert {k for k, _ in found["sorts only above room + 1"]} >= set(tor.TOKEN_KS) - {1}

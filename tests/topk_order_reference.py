@@ -2,7 +2,8 @@
 calls the library: test_topk_order_host.py proves on the CPU that each fixture reaches the queue state it is meant to reach, and
 test_gpu_topk_order.py runs the same fixtures through index_topk_kernel, index_probe_kernel, topk_merge_kernel (search.hip) and
 sparse_index_scan_kernel (sparse_index.hip), test_gpu_token_index_order.py the token fixtures through token_index_scan_kernel
-(token_index.hip).
+(token_index.hip), test_gpu_token_scan_forms.py the int8, masked and listed token fixtures through that kernel's other four
+instantiations.
 
 The kernels select alike.  A query's current top-k stands in slots [0, k) of an LDS list of L entries; a (score, id) threshold — the
 k-th best at the last sort, (-inf, INT_MAX) before the first — lives in registers; every row that ranks before the threshold is
@@ -127,14 +128,16 @@ def _better(s, i, ts, ti):
     return (s > ts) | ((s == ts) & (i < ti))
 
 
-def walk(scores, ids, ok, k, L, step):
+def walk(scores, ids, ok, k, L, step, slack=0):
     """One workgroup: scores [nq, n] f32 of its nq queries against its n rows in the order it meets them, ids [n], ok [n] or [nq, n]
     (False: the row is removed, disallowed or an empty entry, and never pushed).  Pushes and sorts only.  Returns
       steps, sorts (not counting the one behind the last step), sort_steps (the steps that ended in a sort),
       max_slot (the largest slot written; -1: none), fit_fresh / fit_stale [nq] (a step ended with count == room, unsorted, and the next
       step pushed `step` rows — before / after the workgroup's first sort), near_miss [nq] (a step ended with count == room + 1, was
       sorted, and the next step pushed `step` rows), pushed_late [nq] (a push after the first sort),
-      ids / scores [nq, k] (the lists at the end, best first; SENT / -inf where empty)."""
+      ids / scores [nq, k] (the lists at the end, best first; SENT / -inf where empty).
+    slack is 0 for every kernel.  slack > 0 is a deliberately WRONG queue, for test_topk_order_host.py's sensitivity checks alone: it
+    sorts only when a count exceeds room + slack, and a push behind slot L - 1 — the list has L entries — is lost."""
     scores = np.ascontiguousarray(scores, dtype=np.float32)
     nq, n = scores.shape
     ids = np.asarray(ids, dtype=np.int64)
@@ -180,6 +183,9 @@ def walk(scores, ids, ok, k, L, step):
             s, i = scores[first[u], sl], ids[sl]
             m = ok[first[u], sl] & _better(s, i, ts[u], ti[u])
             pushed = int(m.sum())
+            if slack and pushed > L - k - int(cnt[u]):               # (the wrong queue: what does not fit is lost)
+                m[np.flatnonzero(m)[L - k - int(cnt[u]):]] = False
+                pushed = int(m.sum())
             if pushed:
                 que_s[u].append(s[m])
                 que_i[u].append(i[m])
@@ -192,7 +198,7 @@ def walk(scores, ids, ok, k, L, step):
                 near[u] = True
         assert max_slot < L, "the model's own invariant: k + room + step == L"
         prev_over = cnt == room + 1                                  # (more than fits: sorted below)
-        if (cnt > room).any():
+        if (cnt > room + slack).any():
             sort_all()
             sorts += 1
             sort_steps.append(t)
@@ -632,14 +638,18 @@ TOKEN_MANY_SLICES, TOKEN_MANY_K = 17, 256
 TOKEN_MANY_DOCS = 3301                   # 17 slices of 195 documents (the last: 181): 3 steps and 3 documents, 48 groups of four and 3
 
 
-def token_search(S, k, n_slices, slice_docs):
+def token_search(S, k, n_slices, slice_docs, ok=True):
     """token_index_scan_kernel over S [nq, n_docs]: one walk per (query, slice of slice_docs consecutive documents; the last takes what
     is left, and a slice need not be whole steps), steps of TOKEN_STEP documents from the slice's first, then the merge of the slices'
     lists.  The order of the pushes inside a step — the four waves' atomicAdd — is not modelled: walk() sorts by (score, id) alone.
+    ok [n_docs]: the documents that qualify (live and allowed), the masked instantiations' step mask.  The masked kernel skips its look at
+    the count behind a step without a qualifying document; walk() looks and needs no change for that: nothing was pushed in such a step,
+    so the count is what the last look left, which was <= room (a larger one was sorted and reset), and the look it skips finds nothing.
     Returns as sliced_search."""
     S = np.ascontiguousarray(S, dtype=np.float32)
     nq, n = S.shape
     assert (n_slices - 1) * slice_docs < max(n, 1) <= n_slices * slice_docs
+    ok = np.ascontiguousarray(np.broadcast_to(np.asarray(ok, dtype=bool), (n,)))
     L = token_L(k)
     list_s = np.full((nq, n_slices, k), -np.inf, np.float32)
     list_i = np.full((nq, n_slices, k), SENT, np.int64)
@@ -649,7 +659,7 @@ def token_search(S, k, n_slices, slice_docs):
         for q in range(nq):
             key = (sl, S[q, r0:r1].tobytes())
             if key not in cache:
-                cache[key] = walk(S[q:q + 1, r0:r1], np.arange(r0, r1), True, k, L, TOKEN_STEP)
+                cache[key] = walk(S[q:q + 1, r0:r1], np.arange(r0, r1), ok[r0:r1], k, L, TOKEN_STEP)
             w = dict(cache[key])
             w["q0"], w["slice"] = q, sl
             wgs.append(w)
@@ -708,6 +718,191 @@ def token_scores_f64(fx, kinds, lens):
     for i in range(len(kinds)):
         out[i] = mx[qcu[i]:qcu[i + 1]].sum(axis=0)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# int8 token fixtures: token_index_scan_kernel<I8Form, ...>
+# ------------------------------------------------------------------------------------------------
+TOKEN_I8_SIGN = {"asc": 1.0, "desc": -1.0, "saw": 1.0, "was": -1.0, "stair": 1.0, "riats": -1.0, "over": 1.0, "revo": -1.0, "const": 0.0}
+TOKEN_I8_PATTERNS = {"asc": ("asc", "desc"), "saw": ("saw", "was"), "stair": ("stair", "riats"), "over": ("over", "revo")}
+_I8_FIXTURES = {}
+
+
+def token_i8_queries(kinds, lens):
+    """(rows [T, 8] f32, cu int32) of one query per (kind, len) pair: +-e_0 or a zero row, then len - 1 zero rows"""
+    parts = []
+    for kk, ln in zip(kinds, lens):
+        q = np.zeros((ln, TOKEN_DIM), np.float32)
+        q[0, 0] = TOKEN_I8_SIGN[kk]
+        parts.append(q)
+    return np.concatenate(parts), np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int32)
+
+
+def token_i8_rows(ranks):
+    """(rows [T, 8] f32, cu int32, lens): document d is TOKEN_DOC_LENS[d % 5] copies of value(ranks[d]) * e_0 — one nonzero column, so a
+    token's scale is its value / 127 and its code 127: no other column is there for the scale to round away"""
+    n = len(ranks)
+    per_doc = np.zeros((n, TOKEN_DIM), np.float32)
+    per_doc[:, 0] = values(ranks)
+    lens = np.array([TOKEN_DOC_LENS[d % len(TOKEN_DOC_LENS)] for d in range(n)], np.int64)
+    return np.repeat(per_doc, lens, axis=0), np.concatenate([[0], np.cumsum(lens)]).astype(np.int32), lens
+
+
+def _token_i8_fixture(name, ranks, pos, neg):
+    """One int8 token index over the ranks [n] and its queries by kind (pos: +e_0, neg: -e_0, "const": zero).  scores[kind] [n] f32 are
+    token_i8_reference.scores_i8 of the rows themselves — the bits the index must give —, asserted to be the same at both query lengths
+    (the zero rows behind the first token add +0) and to keep the ranks' order exactly (check_order).  Under neg every score of a positive
+    rank is negative, so an unmasked slot behind a document's end (0) would beat it.  Made once, read-only."""
+    import token_i8_reference as t8
+
+    if name in _I8_FIXTURES:
+        return _I8_FIXTURES[name]
+    ranks = np.asarray(ranks, dtype=np.int64)
+    n = len(ranks)
+    rows, cu, lens = token_i8_rows(ranks)
+    kinds = [pos, neg, "const"]
+    q, qcu = token_i8_queries([kk for kk in kinds for _ in TOKEN_QUERY_LENS], [ln for _ in kinds for ln in TOKEN_QUERY_LENS])
+    sc = t8.scores_i8(q, qcu, rows, cu)
+    v = values(ranks).astype(np.float64)
+    scores, intended = {}, {pos: v, neg: -v, "const": np.zeros(n)}
+    for i, kk in enumerate(kinds):
+        a, b = sc[2 * i], sc[2 * i + 1]
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)) and not np.signbit(a[a == 0]).any(), (name, kk)
+        check_order(a, intended[kk], (name, kk))
+        scores[kk] = a
+    for a in (rows, cu, lens, ranks, *scores.values()):
+        a.setflags(write=False)
+    fx = Fixture(name, n=n, rows=rows, cu=cu, lens=lens, ranks=ranks, scores=scores, intended=intended, kinds=kinds, pos=pos, neg=neg)
+    _I8_FIXTURES[name] = fx
+    return fx
+
+
+def token_i8_fixture(pattern, k=None, n=TOKEN_DOCS):
+    """The int8 index of one pattern: "asc", "saw" (period 128), "stair" (the staircase of (k, token_L(k), 64)) or "over" (its near miss)"""
+    pos, neg = TOKEN_I8_PATTERNS[pattern]
+    if pattern == "asc":
+        return _token_i8_fixture(f"token i8 asc n={n}", ascending(n), pos, neg)
+    if pattern == "saw":
+        return _token_i8_fixture(f"token i8 saw n={n}", sawtooth(n, TOKEN_STEP), pos, neg)
+    return _token_i8_fixture(f"token i8 {pattern} k={k} n={n}", staircase(n, k, token_L(k), TOKEN_STEP, int(pattern == "over")), pos, neg)
+
+
+def token_i8_layout(fx):
+    """every kind of the fixture at every query length: (kinds, lens)"""
+    return [kk for kk in fx.kinds for _ in TOKEN_QUERY_LENS], [ln for _ in fx.kinds for ln in TOKEN_QUERY_LENS]
+
+
+# ------------------------------------------------------------------------------------------------
+# masked token fixtures, both forms: token_index_scan_kernel<Form, true, false>
+# ------------------------------------------------------------------------------------------------
+TOKEN_MASK_MODES = ("allow", "removed", "both")
+TOKEN_MASK_KINDS = ["asc", "desc", "const"]
+TOKEN_MASK_SLICES = (1, 0, 7)            # one slice; the planned cut; 7 slices, which start inside a mask word
+
+
+def token_masks(k, n=TOKEN_DOCS):
+    """(ok, ok1) [n] bool over the ascending pattern: the masked exact fit of this k and its near miss"""
+    L = token_L(k)
+    return fit_mask(n, k, L, TOKEN_STEP), fit_mask(n, k, L, TOKEN_STEP, 1)
+
+
+def token_mask_mode(ok, mode):
+    """(the ids to remove, the allow-list or None) that leave exactly the documents ok: as an allow-list, as removals, or as both — a
+    random half of the others removed, the rest disallowed"""
+    if mode == "allow":
+        return np.zeros(0, np.int32), ok
+    if mode == "removed":
+        return np.flatnonzero(~ok).astype(np.int32), None
+    r = np.random.default_rng(len(ok)).random(len(ok)) < 0.5
+    removed, allow = np.flatnonzero(~(ok | r)).astype(np.int32), ok | ~r
+    live = np.ones(len(ok), dtype=bool)
+    live[removed] = False
+    assert np.array_equal(live & allow, ok)
+    return removed, allow
+
+
+# ------------------------------------------------------------------------------------------------
+# listed fixtures: token_index_scan_kernel<I8Form, false, true>, the int8 rescore
+# ------------------------------------------------------------------------------------------------
+LIST_DOCS = MERGE_CAND                   # document d has rank d: its id is its rank, and document 0 scores 0
+LIST_HOLES = (-1, LIST_DOCS, 2 ** 31 - 1, None)       # what stands at a hole, in turn; None: the position's own id, removed from the index
+
+
+def listed_fixture():
+    return _token_i8_fixture(f"token i8 ids n={LIST_DOCS}", np.arange(LIST_DOCS), "asc", "desc")
+
+
+def candidate_lists(k):
+    """name -> (cand [1024] int64, removed ids): candidate lists that carry a pattern along their POSITIONS.
+      arange        position == id: ascending
+      reversed      the ids descend, so under "desc" the scores ascend along the positions while the ids fall
+      holes         ascending, with a hole wherever fit_mask(k) says "no push": the masked exact fit (thresholds still -inf).  The holes are
+                    LIST_HOLES in turn: -1, n_docs, 2^31 - 1, and ids that are removed from the index
+      holes over    its near miss
+      repeats       the ids are the staircase's ranks: the exact fit behind a stale threshold; every position that is not to push names
+                    document 0, whose score 0 is the best of all under "desc" — as often as it is named
+      repeats over  its near miss"""
+    n, L = LIST_DOCS, token_L(k)
+    none = np.zeros(0, np.int32)
+    out = {"arange": (np.arange(n), none), "reversed": (n - 1 - np.arange(n), none)}
+    for name, extra in (("holes", 0), ("holes over", 1)):
+        cand, removed = np.arange(n), []
+        ok = fit_mask(n, k, L, TOKEN_STEP, extra)
+        ok[[n - 2, n - 4]] = False                                   # (at least four holes, one of each kind, where the schedule is all rows)
+        for j, p in enumerate(np.flatnonzero(~ok)):
+            h = LIST_HOLES[j % len(LIST_HOLES)]
+            if h is None:
+                removed.append(p)
+            else:
+                cand[p] = h
+        out[name] = (cand, np.array(removed, np.int32))
+    for name, extra in (("repeats", 0), ("repeats over", 1)):
+        cand = staircase(n, k, L, TOKEN_STEP, extra).astype(np.int64)
+        cand[[n - 1, n - 2, n - 4]] = 0                              # (document 0 at least three times, where the staircase is all rows)
+        out[name] = (cand, none)
+    return out
+
+
+def list_valid(cand, removed, n_docs=LIST_DOCS):
+    """the positions that hold a candidate: an id in [0, n_docs) that is not removed"""
+    cand = np.asarray(cand, dtype=np.int64)
+    return (cand >= 0) & (cand < n_docs) & ~np.isin(cand, removed)
+
+
+def list_scores(S, cand, removed):
+    """S [nq, n_docs] with NaN in the removed documents' columns: what tref.rescore_expected ranks"""
+    Sm = np.array(S, dtype=np.float32)
+    Sm[:, np.asarray(removed, dtype=np.int64)] = np.nan
+    return Sm
+
+
+def listed_search(S, cand, valid, k, n_slices, slice_pos, positions_for_ids=False, slack=0):
+    """the listed instantiation over S [nq, n_docs] and ONE candidate list cand [n_cand] for all queries: one walk per (query, slice of
+    slice_pos consecutive POSITIONS), whose rows are the documents cand[r0:r1] in list order under their own ids, valid [n_cand] saying
+    which positions hold a candidate; then the merge.  positions_for_ids and slack make deliberately wrong models (the sensitivity
+    checks).  Returns as sliced_search."""
+    S = np.ascontiguousarray(S, dtype=np.float32)
+    cand = np.asarray(cand, dtype=np.int64)
+    nq, n = len(S), len(cand)
+    assert (n_slices - 1) * slice_pos < n <= n_slices * slice_pos
+    L = token_L(k)
+    at = np.where((cand >= 0) & (cand < S.shape[1]), cand, 0)
+    list_s = np.full((nq, n_slices, k), -np.inf, np.float32)
+    list_i = np.full((nq, n_slices, k), SENT, np.int64)
+    wgs, cache = [], {}
+    for sl in range(n_slices):
+        r0, r1 = sl * slice_pos, min(n, (sl + 1) * slice_pos)
+        ids = np.arange(r0, r1) if positions_for_ids else cand[r0:r1]
+        for q in range(nq):
+            key = (sl, S[q, at[r0:r1]].tobytes())
+            if key not in cache:
+                cache[key] = walk(S[q:q + 1, at[r0:r1]], ids, valid[r0:r1], k, L, TOKEN_STEP, slack)
+            w = dict(cache[key])
+            w["q0"], w["slice"] = q, sl
+            wgs.append(w)
+            list_s[q, sl], list_i[q, sl] = w["scores"][0], w["ids"][0]
+    m = merge(list_s.reshape(nq, -1), list_i.reshape(nq, -1), k)
+    return dict(wgs=wgs, merge=m, ids=m["ids"], scores=m["scores"], slices=n_slices)
 
 
 # ------------------------------------------------------------------------------------------------
