@@ -1,6 +1,10 @@
-"""CPU proof that the fixtures of test_gpu_topk_order.py, test_gpu_token_index_order.py and test_gpu_token_scan_forms.py reach the
-queue states they are built for (tests/topk_order_reference.py: the patterns and the host model of the selecting kernels' queue).
-The geometry comes from the hooks the searches themselves plan with (bert_hip_test_index_plan, bert_hip_test_sparse_scan_geometry[_qb]); the model never calls the library.  A fixture that stops reaching
+"""CPU proof that the fixtures of test_gpu_topk_order.py, test_gpu_token_index_order.py, test_gpu_token_scan_forms.py and
+test_gpu_hybrid_order.py reach the queue states they are built for (tests/topk_order_reference.py: the patterns and the host model of
+the selecting kernels' queue).
+The geometry comes from the hooks the searches themselves plan with (bert_hip_test_index_plan, bert_hip_test_sparse_scan_geometry[_qb];
+the hybrid scan, sparse_hybrid_scan_kernel: bert_hip_test_hybrid_chunk for the chunks of a call and the scan's plan for each chunk); the
+model never calls the library.  The hybrid section also proves the split fixtures exact and shows that neither term alone nor the
+weights swapped selects what H selects, and that a reader of the dense scores with a wrong row or query index returns another result.  A fixture that stops reaching
 its state — after a change of a list length, a step or a plan — fails here, not silently on the GPU.  Every test prints the reached
 state of its fixtures (pytest -s)."""
 import os
@@ -625,3 +629,272 @@ def test_wrong_models_disagree_with_the_order_rule():
     assert found["a hole is pushed"] == list(tor.TOKEN_KS) and found["positions for ids"] == list(tor.TOKEN_KS)
     # (k = 1: the one document the late sort loses is overtaken by a later one of the rising pattern, so the end result cannot show it)
     assert {k for k, _ in found["sorts only above room + 1"]} >= set(tor.TOKEN_KS) - {1}
+
+
+# ------------------------------------------------------------------------------------------------
+# sparse_hybrid_scan_kernel: the hybrid search's second pass
+# ------------------------------------------------------------------------------------------------
+_PLANNED = {}
+
+
+def planned_search(H, ok, k, g):
+    """sliced_search under a plan of the hook, made once per (scores, mask, plan): the weight pairs and the two sparse forms of a cell
+    give the same H"""
+    ok = np.ascontiguousarray(np.broadcast_to(np.asarray(ok, dtype=bool), H.shape[1:]))
+    key = (H.tobytes(), ok.tobytes(), k, g["qb"], g["n_slices"], g["slice_rows"], g["L"])
+    if key not in _PLANNED:
+        _PLANNED[key] = tor.sliced_search(H, ok, k, g["qb"], g["n_slices"], g["slice_rows"], g["L"], tor.SPARSE_STEP)
+    return _PLANNED[key]
+
+
+def hybrid_tile(fx, nq, k, pref=0):
+    """the scan's tile of a call's first chunk — every chunk but a last short one has it —, for layouts()"""
+    chunks, _ = tor.hybrid_chunks(fx.n, nq, pref, libbert.test_hybrid_chunk)
+    return libbert.test_sparse_scan_geometry(tor.SPARSE_DTYPES.index(fx.sd), tor.SPARSE_V, fx.n, chunks[0][1], k)["qb"]
+
+
+def hybrid_model(fx, lay, ok, k, pref=0, want=None, what=""):
+    """One call of the hybrid search as the library plans it: the chunks of bert_hip_test_hybrid_chunk, for each the scan's plan of
+    bert_hip_test_sparse_scan_geometry, the model's walk over the reference's H.  Asserts that the model selects what
+    hybrid_reference.search selects, bit for bit.  Returns [(c0, c, plan, walks)]."""
+    chunks, ld = tor.hybrid_chunks(fx.n, len(lay), pref, libbert.test_hybrid_chunk)
+    H = fx.S(lay)
+    parts = []
+    for c0, c in chunks:
+        g = libbert.test_sparse_scan_geometry(tor.SPARSE_DTYPES.index(fx.sd), tor.SPARSE_V, fx.n, c, k)
+        assert g["L"] == tor.sparse_L(k) and g["qb"] == min(2, c) and g["n_qtiles"] == -(-c // g["qb"]), g
+        assert c0 % 2 == 0                                           # a chunk starts at a tile's first query: the layouts hold in every chunk
+        parts.append((c0, c, g, planned_search(H[c0:c0 + c], ok, k, g)))
+    want = tor.of_layout(tor.hybrid_reference(fx, k, ok), lay) if want is None else want
+    ids = np.concatenate([p[3]["ids"] for p in parts])
+    sc = np.concatenate([p[3]["scores"] for p in parts])
+    assert np.array_equal(ids, want[0]) and np.array_equal(sc.view(np.uint32), want[1].view(np.uint32)), what
+    return parts
+
+
+def check_hybrid_states(fx, name, lay, parts, k, near, what):
+    """check_tile_states over every chunk, the kinds named by what H does (a negative weight pair makes "desc" the ascending one), and what
+    the walks of §1's table reach beyond it.  near: the mask is the near miss's (ok1)."""
+    L = tor.sparse_L(k)
+    eff = name if name == "mixed" else name.split(":")[0] + ":" + fx.effective[name.split(":")[1]]
+    for c0, c, g, res in parts:
+        kinds = [fx.effective[kk] for kk in lay[c0:c0 + c]]
+        if near:
+            for w in res["wgs"]:
+                if eff.endswith(":asc"):
+                    pos = kinds[w["q0"]:w["q0"] + g["qb"]].index("asc")
+                    assert w["near_miss"][pos], (what, "one row more than fits while the thresholds are -inf")
+            continue
+        check_tile_states(fx, eff, kinds, res, g["qb"], L, k, tor.SPARSE_STEP, fx.mode, what)
+        if eff == "mixed":
+            continue
+        b = eff.split(":")[1]
+        for w in res["wgs"]:
+            pos = kinds[w["q0"]:w["q0"] + g["qb"]].index(b)
+            assert w["max_slot"] < L
+            if b == "stair":
+                assert w["fit_fresh"][pos] == (k == 256), (what, "k = 256: the lead itself fits exactly, before the first sort")
+            if b == "asc" and fx.mode != "plain":
+                assert w["fit_stale"][pos] == tor.masked_reaches_stale(fx.n, k), (what, "the second exact fit, behind a sort")
+
+
+def hybrid_cell(fx, k, nqs, pref=0, show=None):
+    """every layout of every nq of one index pair: the result, the states, and (allow) the near miss of the same pair"""
+    for nq in nqs:
+        tile = hybrid_tile(fx, nq, k, pref)
+        for name, lay in tor.layouts(fx.kinds, fx.busy, fx.idle, nq, tile).items():
+            what = (fx.name, nq, name)
+            parts = hybrid_model(fx, lay, fx.permitted(), k, pref, what=what)
+            check_hybrid_states(fx, name, lay, parts, k, False, what)
+            if nq == show:
+                print(tor.describe(f"{fx.name} nq={nq} {name}", parts[0][3]))
+            if fx.mode == "allow":
+                parts = hybrid_model(fx, lay, fx.ok1, k, pref, what=(*what, "near miss"))
+                check_hybrid_states(fx, name, lay, parts, k, True, (*what, "near miss"))
+
+
+def test_hybrid_schedules_reach_what_the_walks_of_one_query_reach():
+    """the staircase and fit_mask at step 256 and L = sparse_L(k), one query, one slice, every k at both sizes"""
+    for n in sorted(set(tor.HYBRID_ROWS.values())):
+        for k in tor.HYBRID_KS:
+            L = tor.sparse_L(k)
+            ids = np.arange(n)
+            st = tor.walk(tor.values(tor.staircase(n, k, L, tor.SPARSE_STEP))[None], ids, True, k, L, tor.SPARSE_STEP)
+            assert st["max_slot"] == L - 1 and st["fit_stale"][0] and st["fit_fresh"][0] == (k == 256), (n, k)
+            ov = tor.walk(tor.values(tor.staircase(n, k, L, tor.SPARSE_STEP, 1))[None], ids, True, k, L, tor.SPARSE_STEP)
+            assert ov["near_miss"][0], (n, k)
+            asc = tor.values(tor.ascending(n))[None]
+            mk = tor.walk(asc, ids, tor.fit_mask(n, k, L, tor.SPARSE_STEP), k, L, tor.SPARSE_STEP)
+            assert mk["max_slot"] == L - 1 and mk["fit_fresh"][0] and mk["fit_stale"][0] == tor.masked_reaches_stale(n, k), (n, k)
+            assert tor.walk(asc, ids, tor.fit_mask(n, k, L, tor.SPARSE_STEP, 1), k, L, tor.SPARSE_STEP)["near_miss"][0], (n, k)
+    assert tor.SPARSE_ROWS == 15 * 256 + 160 and tor.HYBRID_ROWS["b1"] == 7 * 256 + 248
+    assert libbert.test_hybrid_chunk(tor.SPARSE_ROWS, 1)[1] == 4032 and 4032 - tor.SPARSE_ROWS < 64          # a partial last block of 64
+
+
+@pytest.mark.parametrize("mode", tor.MODES)
+@pytest.mark.parametrize("k", tor.HYBRID_KS)
+@pytest.mark.parametrize("sd", tor.SPARSE_DTYPES)
+def test_hybrid_split_fixtures_reach_their_states(sd, k, mode):
+    for w in tor.HYBRID_WEIGHTS:
+        fx = tor.hybrid_split_fixture(sd, sd, k, mode, w)
+        assert fx.n == tor.SPARSE_ROWS and fx.busy[-1] == ("asc" if w[0] > 0 else "desc")                    # a negative pair: desc rises
+        hybrid_cell(fx, k, tor.HYBRID_NQS, show=2 if w == (1.0, 1.0) else None)
+        if mode == "removed":
+            for three_ways in (True, False):
+                gone_d, gone_s, allow = tor.hybrid_removed_split(fx.ok, three_ways)
+                assert three_ways == (len(gone_d) > 0) == (allow is not None) and len(gone_s) > 0
+                assert not three_ways or k == 256 or not allow.all()
+
+
+@pytest.mark.parametrize("mode", ["plain", "allow"])
+@pytest.mark.parametrize("k", tor.HYBRID_DENSE_KS)
+@pytest.mark.parametrize("dd", tor.DENSE_DTYPES)
+def test_hybrid_dense_carriers_reach_their_states(dd, k, mode):
+    fxs = tor.hybrid_dense_fixtures(dd, "f32", k, mode)
+    assert len(fxs) == (1 if dd in ("f32", "f16") else 4 if mode == "plain" else 2)
+    assert libbert.test_hybrid_chunk(tor.HYBRID_ROWS[dd], 33) == (32, 4032 if dd != "b1" else 2048)          # 33 queries: chunks of 32 + 1
+    for fx in fxs:
+        assert fx.n == tor.HYBRID_ROWS[dd] and fx.rows.shape == (fx.n, tor.B1_DIM if dd == "b1" else tor.FLOAT_DIM)
+        hybrid_cell(fx, k, tor.HYBRID_DENSE_NQS, show=33)
+
+
+@pytest.mark.parametrize("k", tor.HYBRID_SPARSE_KS)
+@pytest.mark.parametrize("sd", tor.SPARSE_DTYPES)
+@pytest.mark.parametrize("dd", ["f32", "f16"])
+def test_hybrid_sparse_carriers_reach_their_states(dd, sd, k):
+    fx = tor.hybrid_sparse_fixture(dd, sd, k)
+    assert fx.rows.any() and all(not q.any() for q in fx.dense_q.values())                                   # the rows are not zero: the query is
+    hybrid_cell(fx, k, tor.HYBRID_NQS, show=2)
+
+
+@pytest.mark.parametrize("mode", ["plain", "allow"])
+@pytest.mark.parametrize("sd", tor.SPARSE_DTYPES)
+def test_hybrid_chunked_fixtures_reach_their_states(sd, mode):
+    k, nq, pref = tor.HYBRID_CHUNK_K, tor.HYBRID_CHUNK_NQ, tor.HYBRID_CHUNK
+    assert libbert.test_hybrid_chunk(tor.SPARSE_ROWS, nq, pref) == (2, 4032)
+    assert tor.hybrid_chunks(tor.SPARSE_ROWS, nq, pref, libbert.test_hybrid_chunk)[0] == [(0, 2), (2, 2), (4, 1)]
+    for w in tor.HYBRID_WEIGHTS:
+        hybrid_cell(tor.hybrid_split_fixture(sd, sd, k, mode, w), k, (nq,), pref=pref, show=nq if w == (1.0, 1.0) else None)
+
+
+@pytest.mark.parametrize("k", tor.MANY_KS)
+def test_hybrid_many_slices_reach_a_second_merge_round(k):
+    fx = tor.many_hybrid_fixture()
+    assert fx.n == tor.MANY_SPARSE_ROWS and (fx.rows[:, 0] % 64 == 0).all() and fx.term_w.max() == 63
+    for nq in tor.MANY_NQS:
+        lay = tor.many_layout(nq)
+        parts = hybrid_model(fx, lay, True, k, what=(fx.name, nq, k))
+        assert [c for _, c, _, _ in parts] == ([1] if nq == 1 else [32, 1])
+        for c0, c, g, res in parts:
+            assert g["n_slices"] >= 17 and g["n_slices"] * g["slice_rows"] >= fx.n
+            # every slice but the first takes its rows' D from beyond the first slice_rows floats of a query's scores
+            assert (fx.dsc["asc"][g["slice_rows"]:] > 0).all()
+            check_many(res, lay[c0:c0 + c], k, 17, (fx.name, nq, k, c0))
+            print(tor.describe(f"{fx.name} nq={nq} k={k} chunk at {c0}", res), "slices", res["slices"])
+
+
+def _ids(D, S, qual, wd, ws, k):
+    import hybrid_reference as href
+
+    return href.search(D[None], S[None], qual, wd, ws, k)[0][0]
+
+
+@pytest.mark.parametrize("mode", tor.MODES)
+@pytest.mark.parametrize("k", tor.HYBRID_KS)
+def test_hybrid_split_fixtures_are_exact_and_separate_the_orderings(k, mode):
+    """sensitivity of the split carrier, on the references alone.  Exact: asserted where a fixture is made (hybrid_split_fixture), restated
+    here from the stored values.  Separating: for every busy kind — the kinds whose H rises with the pattern; a constant or a falling
+    pattern selects the first k rows whatever is dropped — the top-k by the dense term alone (w_dense * D), by the sparse term alone and
+    by H with the two weights swapped (where they differ: (1, 1) and (-1, -1) swapped are themselves) each differ from the top-k by H in
+    at least half of the k slots, over the fixture's rows and (allow) over its near miss's."""
+    least = {}
+    for sd in tor.SPARSE_DTYPES:
+        for w in tor.HYBRID_WEIGHTS:
+            fx = tor.hybrid_split_fixture(sd, sd, k, mode, w)
+            wd, ws = w
+            for kk in fx.kinds:
+                H = np.float32(wd) * fx.dsc[kk] + np.float32(ws) * fx.ssc[kk]
+                assert np.array_equal(H, fx.scores[kk]) and np.array_equal(H.astype(np.float64), fx.intended[kk]), (fx.name, kk)
+                for a in (fx.dsc[kk], fx.ssc[kk]):
+                    assert np.array_equal(a.astype(np.float16).astype(np.float32), a), (fx.name, kk)
+            if sd != "f32":
+                continue                                             # (the same D, S and H: asserted above)
+            zero = np.zeros(fx.n, np.float32)
+            for qual in [fx.permitted()] + ([fx.ok1] if mode == "allow" else []):
+                for kk in fx.busy:
+                    by_h = _ids(fx.dsc[kk], fx.ssc[kk], qual, wd, ws, k)
+                    others = {"dense term alone": _ids(fx.dsc[kk], zero, qual, wd, ws, k), "sparse term alone": _ids(zero, fx.ssc[kk], qual, wd, ws, k)}
+                    if wd != ws:
+                        others["weights swapped"] = _ids(fx.dsc[kk], fx.ssc[kk], qual, ws, wd, k)
+                    for name, ids in others.items():
+                        differ = int((ids != by_h).sum())
+                        least[name] = min(least.get(name, k), differ)
+                        assert 2 * differ >= k, (fx.name, kk, name, differ, k)
+    print(f"split k={k} {mode}: the fewest of {k} slots that differ from the top-k by H: {least}")
+
+
+def test_wrong_hybrid_models_disagree():
+    """sensitivity, on the model and the references alone: no kernel is made wrong for this.
+    A queue that sorts one entry late (walk's slack = 1) can differ from the right one only where a step ends with count == room + 1 —
+    the near-miss kinds, "over" and the ascending rows under ok1 —, and loses the last row of the whole step behind it, the best so far:
+    on the fixture's rows up to that step it disagrees with the order rule for every k (further rows overtake the lost one, so the whole
+    fixture shows it only where the loss is among the last k rows that push).
+    A reader of the dense scores that takes a slice-local row, or the query's index in the call where the chunk's is meant, returns
+    another result on the many-slices and on the chunked case."""
+    import hybrid_reference as href
+
+    whole = []
+    for k in tor.HYBRID_KS:
+        L = tor.sparse_L(k)
+        plain, masked = tor.hybrid_split_fixture("f32", "f32", k, "plain", (1.0, 1.0)), tor.hybrid_split_fixture("f32", "f32", k, "allow", (-0.5, -4.0))
+        for fx, kind, ok in ((plain, "over", np.ones(plain.n, bool)), (masked, "desc", masked.ok1)):
+            assert fx.effective[kind] in ("over", "asc")
+            H = fx.scores[kind][None]
+            cut = None
+            for end in range(tor.SPARSE_STEP, fx.n + tor.SPARSE_STEP, tor.SPARSE_STEP):
+                if tor.walk(H[:, :end], np.arange(min(end, fx.n)), ok[:end], k, L, tor.SPARSE_STEP)["near_miss"][0]:
+                    cut = min(end, fx.n)
+                    break
+            assert cut is not None, (fx.name, kind)
+            late = tor.walk(H[:, :cut], np.arange(cut), ok[:cut], k, L, tor.SPARSE_STEP, slack=1)
+            want = tor.reference_topk(H[:, :cut], ok[:cut], k)
+            assert not np.array_equal(np.where(late["ids"] == tor.SENT, -1, late["ids"]), want[0]), (fx.name, kind, cut)
+            assert late["ids"][0, 0] != want[0][0, 0], (fx.name, kind, "the best row so far is the one lost")
+            late = tor.walk(H, np.arange(fx.n), ok, k, L, tor.SPARSE_STEP, slack=1)
+            if not np.array_equal(np.where(late["ids"] == tor.SENT, -1, late["ids"]), tor.reference_topk(H, ok, k)[0]):
+                whole.append((k, fx.effective[kind]))
+    print(f"sorts only above room + 1: disagrees on the whole fixture at {whole}")
+    assert {k for k, kind in whole if kind == "over"} >= {127, 128, 255, 256}
+
+    def differs(a, b):
+        return not (np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)))
+
+    # a slice-local row index: row r of slice s reads the dense score of row r - s * slice_rows
+    fx = tor.many_hybrid_fixture()
+    for k in tor.MANY_KS:
+        for nq in tor.MANY_NQS:
+            lay = tor.many_layout(nq)
+            for c0, c in tor.hybrid_chunks(fx.n, nq, 0, libbert.test_hybrid_chunk)[0]:
+                g = libbert.test_sparse_scan_geometry(0, tor.SPARSE_V, fx.n, c, k)
+                local = np.arange(fx.n) % g["slice_rows"]
+                for kind in set(lay[c0:c0 + c]) - {"const"}:
+                    wrong = href.search(fx.dsc[kind][None, local], fx.ssc[kind][None], np.ones(fx.n, bool), 1.0, 1.0, k)
+                    assert differs(wrong, tor.hybrid_reference(fx, k)[kind]), (k, nq, kind)
+    # the query's index in the call: chunk c0 .. c0 + c writes rows 0 .. c of the matrix, and query c0 + q reads row c0 + q — beyond the
+    # first chunk a row that no chunk of this call has written (zeros here)
+    k, nq, pref = tor.HYBRID_CHUNK_K, tor.HYBRID_CHUNK_NQ, tor.HYBRID_CHUNK
+    for mode in ("plain", "allow"):
+        for w in tor.HYBRID_WEIGHTS:
+            fx = tor.hybrid_split_fixture("f32", "f32", k, mode, w)
+            lay = tor.layouts(fx.kinds, fx.busy, fx.idle, nq, 2)["mixed"]
+            D, S = np.stack([fx.dsc[kk] for kk in lay]), np.stack([fx.ssc[kk] for kk in lay])
+            matrix = np.zeros((nq, fx.n), np.float32)
+            read = np.zeros_like(D)
+            for c0, c in tor.hybrid_chunks(fx.n, nq, pref, libbert.test_hybrid_chunk)[0]:
+                matrix[:c] = D[c0:c0 + c]
+                read[c0:c0 + c] = matrix[c0:c0 + c]
+            assert np.array_equal(read[:pref], D[:pref]) and not np.array_equal(read, D)
+            wrong = href.search(read, S, fx.permitted(), *w, k)
+            assert differs(wrong, tor.of_layout(tor.hybrid_reference(fx, k), lay)), (fx.name, "call index")
+            unchunked = href.search(D, S, fx.permitted(), *w, k)
+            assert not differs(unchunked, tor.of_layout(tor.hybrid_reference(fx, k), lay))

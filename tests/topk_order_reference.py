@@ -3,7 +3,8 @@ calls the library: test_topk_order_host.py proves on the CPU that each fixture r
 test_gpu_topk_order.py runs the same fixtures through index_topk_kernel, index_probe_kernel, topk_merge_kernel (search.hip) and
 sparse_index_scan_kernel (sparse_index.hip), test_gpu_token_index_order.py the token fixtures through token_index_scan_kernel
 (token_index.hip), test_gpu_token_scan_forms.py the int8, masked and listed token fixtures through that kernel's other four
-instantiations.
+instantiations, test_gpu_hybrid_order.py the hybrid fixtures — a dense and a sparse index that carry one pattern together or alone —
+through sparse_hybrid_scan_kernel (sparse_index.hip) behind index_scores_kernel and mask_and_kernel (search.hip).
 
 The kernels select alike.  A query's current top-k stands in slots [0, k) of an LDS list of L entries; a (score, id) threshold — the
 k-th best at the last sort, (-inf, INT_MAX) before the first — lives in registers; every row that ranks before the threshold is
@@ -624,9 +625,269 @@ def many_sparse_rows(n=MANY_SPARSE_ROWS):
 
 
 # ------------------------------------------------------------------------------------------------
+# hybrid fixtures: sparse_hybrid_scan_kernel (sparse_index.hip), behind index_scores_kernel and mask_and_kernel (search.hip)
+# ------------------------------------------------------------------------------------------------
+# A hybrid fixture is a dense and a sparse index of equal size and queries by kind (the kinds of SPARSE_TERMS).  The intended hybrid score
+# of row r under a kind is +- values(rank_p(r)), the patterns those of the sparse fixtures: the scan's geometry, steps of 256 rows and
+# sparse_L(k) entries.  scores[kind] is hybrid_reference.combine(D, S, w_dense, w_sparse) of the two stored forms' reference scores D
+# (index_reference) and S (sparse_index_reference).  The carrier says which side holds the pattern:
+#   split   both: lo = B * ((v // B) mod C) with (B, C) = HYBRID_SPLIT — the middle digit of v in the mixed radix (B, C) — under the sparse
+#           term id, hi = v - lo — the top and the bottom digit — in the dense column, each divided by the size of its weight.  All weights
+#           are powers of two, so both products and their sum are exact: H = +-v bit for bit (but for the sign of a zero).  Neither side
+#           alone, nor the weights swapped, orders the rows as H does (test_topk_order_host.py; v mod 64, a dense part that dominates the
+#           sparse one, does not meet that: 7808, the largest value, stands alone in its block of 64, and swapping (-0.5, -4) stretches
+#           the dense part further, which keeps H's order).  A negative pair turns asc into desc without negating a query.
+#   dense   the dense index holds the whole pattern (any of the four dtypes), the sparse query holds no term: S = +0, weights (1, 1)
+#   sparse  the sparse index holds the whole pattern, the dense query is the zero vector: D = +0, weights (1, 1)
+HYBRID_WEIGHTS = ((1.0, 1.0), (2.0, 0.5), (-1.0, -1.0), (-0.5, -4.0))
+HYBRID_SPLIT = (24, 16)
+HYBRID_ROWS = {"f32": SPARSE_ROWS, "f16": SPARSE_ROWS, "i8": SPARSE_ROWS, "b1": 2040}       # b1: 7 whole steps and 248 rows (its ranks end at dim)
+HYBRID_KS = SPARSE_KS
+HYBRID_NQS = (1, 2, 3, 5)
+HYBRID_DENSE_KS = (1, 128, 129, 256)     # the dense carrier's
+HYBRID_DENSE_NQS = (1, 33)               # 33: two dense tiles, the second of one query, and chunks of 32 + 1
+HYBRID_SPARSE_KS = (128, 256)            # the sparse carrier's
+HYBRID_CHUNK = 2                         # the value of "hybrid_chunk_queries" in the chunked case: 5 queries are chunks of 2, 2 and 1
+HYBRID_CHUNK_NQ, HYBRID_CHUNK_K = 5, 128
+HYBRID_PATTERN_KINDS = [("asc", "desc"), ("saw", "was"), ("stair", "riats"), ("over", "revo")]
+OPPOSITE = {a: b for pair in HYBRID_PATTERN_KINDS for a, b in (pair, pair[::-1])}
+OPPOSITE["const"] = "const"
+_HYBRID_FIXTURES = {}
+
+
+def hybrid_patterns(n, k, mode):
+    """(ranks of pattern 0 .. [n] each, ok, ok1) of one (k, mode) cell, as sparse_fixture's: ascending, sawtooth, and (plain) the
+    staircase of (k, sparse_L(k), 256) and its near miss, or (removed / allow) fit_mask and its near miss"""
+    L, step = sparse_L(k), SPARSE_STEP
+    pats = [ascending(n), sawtooth(n, step)]
+    ok = ok1 = None
+    if mode == "plain":
+        pats += [staircase(n, k, L, step), staircase(n, k, L, step, 1)]
+    else:
+        ok, ok1 = fit_mask(n, k, L, step), fit_mask(n, k, L, step, 1)
+    return pats, ok, ok1
+
+
+def masked_reaches_stale(n, k):
+    """whether the masked exact fit over n ascending rows also fits exactly behind a sort (fit_stale), not only before the first one:
+    2040 rows end before the second such cycle at k = 129 and 255 (test_topk_order_host.py walks every k at both sizes)"""
+    return not (n == 2040 and k in (129, 255))
+
+
+def _hybrid_fixture(name, wd, ws, positive, plain, **kw):
+    """the Fixture of one pair of indexes: scores = H under (wd, ws); effective[kind] is the kind whose intended scores H[kind] are —
+    the kind itself, or its opposite where the weights are negative; busy / idle are query kinds by what H does"""
+    import hybrid_reference as href
+
+    fx = Fixture(name, w=(wd, ws), **kw)
+    fx.scores = {kk: href.combine(fx.dsc[kk], fx.ssc[kk], wd, ws) for kk in fx.kinds}
+    fx.effective = {kk: kk if positive else OPPOSITE[kk] for kk in fx.kinds}
+    by = {e: kk for kk, e in fx.effective.items()}
+    fx.busy = [by[e] for e in (("stair", "over", "asc") if plain else ("asc",)) if e in by]
+    fx.idle = [by[e] for e in ("const", "desc") if e in by]
+    for d in (fx.dsc, fx.ssc, fx.scores):
+        for a in d.values():
+            a.setflags(write=False)
+    for a in (fx.rows, fx.term_ids, fx.term_w, fx.ok, fx.ok1):
+        if a is not None:
+            a.setflags(write=False)
+    return fx
+
+
+def hybrid_queries(fx, lay):
+    """(dense queries [nq, dim] f32, q_ids [nq, 1], q_w [nq, 1]) of a layout of kinds"""
+    ids = np.array([[fx.sparse_q[kk][0]] for kk in lay], np.int32)
+    w = np.array([[fx.sparse_q[kk][1]] for kk in lay], np.float32)
+    return np.stack([fx.dense_q[kk] for kk in lay]), ids, w
+
+
+def hybrid_split_fixture(dd, sd, k, mode, weights, n=SPARSE_ROWS, split=None):
+    """The split carrier of one (k, mode) cell under one weight pair (dd in f32, f16).  Asserts what makes it exact: every stored value
+    survives f16, the dense reference's scores are +-hi / |w_dense| exactly (f32: the documented fma chain agrees), the sparse reference's
+    +-lo / |w_sparse|, and (w_dense * D) + (w_sparse * S) == +-v in float32 — equal values, hence equal bits but for the sign of a zero."""
+    split = HYBRID_SPLIT if split is None else split
+    key = ("split", dd, sd, k, mode, weights, n, split)
+    if key in _HYBRID_FIXTURES:
+        return _HYBRID_FIXTURES[key]
+    assert dd in ("f32", "f16")
+    wd, ws = weights
+    assert (wd > 0) == (ws > 0) and wd != 0
+    sgn = 1.0 if wd > 0 else -1.0
+    pats, ok, ok1 = hybrid_patterns(n, k, mode)
+    P = len(pats)
+    v = np.stack([values(p) for p in pats], axis=1).astype(np.float32)                            # [n, P]
+    lo = np.float32(split[0]) * np.mod(np.floor(v / np.float32(split[0])), np.float32(split[1]))
+    hi = v - lo
+    rows = np.zeros((n, FLOAT_DIM), np.float32)
+    rows[:, :P] = hi / np.float32(abs(wd))
+    term_ids = np.tile(np.arange(P, dtype=np.int32), (n, 1))
+    term_w = lo / np.float32(abs(ws))
+    name = f"hybrid split {dd} x {sd} k={k} {mode} w=({wd:g}, {ws:g})"
+    for a in (rows, term_w):
+        assert np.array_equal(a.astype(np.float16).astype(np.float32), a), name                   # (both stored forms hold every value)
+    kinds = [kk for kk, (t, _) in SPARSE_TERMS.items() if t < P]
+    dense_q = {kk: dense_query(dd, max(SPARSE_TERMS[kk][0], 0), SPARSE_TERMS[kk][1]) for kk in kinds}
+    sparse_q = {kk: SPARSE_TERMS[kk] for kk in kinds}
+    dq = np.stack([dense_q[kk] for kk in kinds])
+    Dm = dense_scores(dd, dq, rows)
+    if dd == "f32":
+        assert np.array_equal(ixr.f32_chain_scores(dq, rows).view(np.uint32), Dm.view(np.uint32)), name
+    st = sref.stored_rows(term_ids, term_w, P, sd)
+    assert np.array_equal(st[1], term_w), name
+    Sm = sref.scores(st[0], st[1], *sparse_query(kinds), SPARSE_V)
+    D, S, intended = {}, {}, {}
+    for i, kk in enumerate(kinds):
+        t, sign = SPARSE_TERMS[kk]
+        D[kk], S[kk] = Dm[i], Sm[i]
+        want_d = np.zeros(n) if t < 0 else sign * rows[:, t].astype(np.float64)
+        want_s = np.zeros(n) if t < 0 else sign * term_w[:, t].astype(np.float64)
+        assert np.array_equal(D[kk].astype(np.float64), want_d) and np.array_equal(S[kk].astype(np.float64), want_s), (name, kk)
+        intended[kk] = np.zeros(n) if t < 0 else sgn * sign * v[:, t].astype(np.float64)
+    fx = _hybrid_fixture(name, wd, ws, wd > 0, mode == "plain", carrier="split", dd=dd, sd=sd, k=k, mode=mode, n=n, rows=rows,
+                         term_ids=term_ids, term_w=term_w, width=P, dense_q=dense_q, sparse_q=sparse_q, dsc=D, ssc=S, intended=intended,
+                         ok=ok, ok1=ok1, kinds=kinds, split=split)
+    for kk in kinds:
+        assert np.array_equal(fx.scores[kk].astype(np.float64), intended[kk]), (name, kk)         # H is the intended value itself
+    assert max(np.abs(a).max() for a in fx.scores.values()) == v.max() <= 7808
+    _HYBRID_FIXTURES[key] = fx
+    return fx
+
+
+def hybrid_dense_fixtures(dd, sd, k, mode):
+    """The dense carrier of one (k, mode) cell: the index pairs (f32, f16: one, the patterns side by side; i8, b1: one per pattern) whose
+    dense rows are dense_rows(dd, patterns), whose sparse rows are the sparse fixture's and whose sparse queries hold no term.  D is the
+    exact integers (f32, f16) or index_reference.exact_scores (i8, b1); S = +0; H = D + (+0) under (1, 1)."""
+    key = ("dense", dd, sd, k, mode)
+    if key in _HYBRID_FIXTURES:
+        return _HYBRID_FIXTURES[key]
+    n = HYBRID_ROWS[dd]
+    pats, ok, ok1 = hybrid_patterns(n, k, mode)
+    names = HYBRID_PATTERN_KINDS[:len(pats)]
+    term_ids = np.tile(np.arange(len(pats), dtype=np.int32), (n, 1))
+    term_w = np.stack([values(p) for p in pats], axis=1).astype(np.float32)
+    st = sref.stored_rows(term_ids, term_w, len(pats), sd)
+    groups = [(pats, names)] if dd in ("f32", "f16") else [([p], [nm]) for p, nm in zip(pats, names)]
+    out = []
+    for gp, gn in groups:
+        name = f"hybrid dense {dd} x {sd} k={k} {mode}" + ("" if len(groups) == 1 else f" {gn[0][0]}")
+        base = _dense_fixture(name, dd, gp, gn, ok, [])
+        kinds = base.kinds
+        none = np.full((len(kinds), 1), -1, np.int32), np.zeros((len(kinds), 1), np.float32)
+        Sm = sref.scores(st[0], st[1], *none, SPARSE_V)
+        assert not Sm.any() and not np.signbit(Sm).any(), name
+        fx = _hybrid_fixture(name, 1.0, 1.0, True, mode == "plain", carrier="dense", dd=dd, sd=sd, k=k, mode=mode, n=n, rows=base.rows,
+                             term_ids=term_ids, term_w=term_w, width=len(pats), dense_q=base.queries, sparse_q={kk: (-1, 0.0) for kk in kinds},
+                             dsc=base.scores, ssc={kk: Sm[i] for i, kk in enumerate(kinds)}, intended=base.intended, ok=ok, ok1=ok1, kinds=kinds)
+        for kk in kinds:
+            assert np.array_equal(fx.scores[kk], fx.dsc[kk]), (name, kk)                              # D + (+0) == D
+        out.append(fx)
+    _HYBRID_FIXTURES[key] = out
+    return out
+
+
+def hybrid_sparse_fixture(dd, sd, k, mode="plain"):
+    """The sparse carrier (dd in f32, f16): the sparse index is sparse_fixture's, the dense rows hold the same patterns and every dense
+    query is the zero vector: D = +0, H = (+0) + S under (1, 1)"""
+    key = ("sparse", dd, sd, k, mode)
+    if key in _HYBRID_FIXTURES:
+        return _HYBRID_FIXTURES[key]
+    assert dd in ("f32", "f16")
+    base = sparse_fixture(sd, k, mode)
+    n, kinds = base.n, base.kinds
+    pats, ok, ok1 = hybrid_patterns(n, k, mode)
+    rows = dense_rows(dd, pats)
+    zero = dense_query(dd, 0, 0)
+    name = f"hybrid sparse {dd} x {sd} k={k} {mode}"
+    Dm = dense_scores(dd, np.stack([zero] * len(kinds)), rows)
+    assert not Dm.any() and not np.signbit(Dm).any(), name
+    fx = _hybrid_fixture(name, 1.0, 1.0, True, mode == "plain", carrier="sparse", dd=dd, sd=sd, k=k, mode=mode, n=n, rows=rows,
+                         term_ids=base.term_ids, term_w=base.term_w, width=base.width, dense_q={kk: zero for kk in kinds},
+                         sparse_q={kk: SPARSE_TERMS[kk] for kk in kinds}, dsc={kk: Dm[i] for i, kk in enumerate(kinds)},
+                         ssc=dict(base.scores), intended={kk: base.scores[kk].astype(np.float64) for kk in kinds}, ok=ok, ok1=ok1, kinds=kinds)
+    for kk in kinds:
+        assert np.array_equal(fx.scores[kk], fx.ssc[kk]), (name, kk)                                  # (+0) + S == S
+    _HYBRID_FIXTURES[key] = fx
+    return fx
+
+
+def hybrid_reference(fx, k, ok=None):
+    """kind -> hybrid_reference.search of the fixture's D and S under its weights over the rows that qualify (ok: another set than the
+    fixture's), (ids [1, k], scores [1, k]); made once per (k, set)"""
+    import hybrid_reference as href
+
+    qual = fx.permitted() if ok is None else np.asarray(ok, dtype=bool)
+    cache = fx.__dict__.setdefault("_reference", {})
+    key = (k, qual.tobytes())
+    if key not in cache:
+        cache[key] = {kk: href.search(fx.dsc[kk][None], fx.ssc[kk][None], qual, fx.w[0], fx.w[1], k) for kk in fx.kinds}
+    return cache[key]
+
+
+def of_layout(want, lay):
+    """the per-kind results of a layout of kinds, stacked"""
+    return np.concatenate([want[kk][0] for kk in lay]), np.concatenate([want[kk][1] for kk in lay])
+
+
+def hybrid_removed_split(ok, three_ways):
+    """(ids removed from the dense index, ids removed from the sparse index, the allow-list or None) that leave exactly the rows ok:
+    the others by r % 3 — dense, sparse, disallowed: mask_and_kernel's AND of three inputs — or all of them removed in the sparse
+    index alone"""
+    gone = np.flatnonzero(~ok)
+    if not three_ways:
+        return np.zeros(0, np.int32), gone.astype(np.int32), None
+    allow = np.ones(len(ok), dtype=bool)
+    allow[gone[gone % 3 == 2]] = False
+    parts = gone[gone % 3 == 0].astype(np.int32), gone[gone % 3 == 1].astype(np.int32), allow
+    assert all(len(p) > 0 for p in parts[:2])                        # (k = 256 masks two rows only: the allow-list is then all ones)
+    live = np.ones(len(ok), dtype=bool)
+    live[parts[0]] = False
+    live[parts[1]] = False
+    assert np.array_equal(live & allow, ok)
+    return parts
+
+
+def hybrid_chunks(n, nq, pref, hook):
+    """[(c0, c)] of a call of nq queries, from the library's own rule (hook = pybert.test_hybrid_chunk), and ld"""
+    hc, ld = hook(n, nq, pref)
+    assert ld == (n + 63) // 64 * 64 and hc >= 1
+    return [(c0, min(hc, nq - c0)) for c0 in range(0, nq, hc)], ld
+
+
+def many_hybrid_rows(n=MANY_SPARSE_ROWS):
+    """(dense rows [n, 8] f32, term ids [n, 1], term weights [n, 1]): 1 + r split at 64 between column 0 and term 0 — plain integers,
+    exact in f32, so H = many_scores(n) under (1, 1)"""
+    v = 1 + np.arange(n)
+    rows = np.zeros((n, FLOAT_DIM), np.float32)
+    rows[:, 0] = 64 * (v // 64)
+    return rows, np.zeros((n, 1), np.int32), (v % 64).astype(np.float32)[:, None]
+
+
+def many_hybrid_fixture(n=MANY_SPARSE_ROWS):
+    """the f32 x f32 pair of many slices and its kinds asc / desc / const: D and S by the two references, H == many_scores(n)"""
+    key = ("many", n)
+    if key in _HYBRID_FIXTURES:
+        return _HYBRID_FIXTURES[key]
+    rows, term_ids, term_w = many_hybrid_rows(n)
+    kinds = list(MANY_LAYOUT)
+    dense_q = {kk: dense_query("f32", 0, SPARSE_TERMS[kk][1]) for kk in kinds}
+    sparse_q = {kk: SPARSE_TERMS[kk] for kk in kinds}
+    Dm = dense_scores("f32", np.stack([dense_q[kk] for kk in kinds]), rows)
+    st = sref.stored_rows(term_ids, term_w, 1, "f32")
+    Sm = sref.scores(st[0], st[1], *sparse_query(kinds), SPARSE_V)
+    fx = _hybrid_fixture(f"hybrid many {n}", 1.0, 1.0, True, True, carrier="split", dd="f32", sd="f32", n=n, rows=rows, term_ids=term_ids,
+                         term_w=term_w, width=1, dense_q=dense_q, sparse_q=sparse_q, dsc={kk: Dm[i] for i, kk in enumerate(kinds)},
+                         ssc={kk: Sm[i] for i, kk in enumerate(kinds)}, ok=None, ok1=None, kinds=kinds)
+    sc = many_scores(n)
+    for kk in kinds:
+        assert np.array_equal(fx.scores[kk], sc[kk]), kk
+    _HYBRID_FIXTURES[key] = fx
+    return fx
+
+
+# ------------------------------------------------------------------------------------------------
 # token fixtures: token_index_scan_kernel (token_index.hip)
 # ------------------------------------------------------------------------------------------------
-TOKEN_KS = (1, 64, 128, 129, 191, 192, 193, 255, 256)
+TOKEN_KS =(1, 64, 128, 129, 191, 192, 193, 255, 256)
 TOKEN_DOCS = TOKEN_STEP * 24 + 37        # 24 whole steps and a tail that ends inside a step and inside a group of four waves
 TOKEN_DIM = 8
 TOKEN_DOC_LENS = (1, 31, 32, 33, 65)     # by document id: the masked last block of 32 document tokens is in play
