@@ -50,6 +50,12 @@ __device__ __forceinline__ long long att_clock() {
 constexpr int ATT_CHUNK = 128;      // keys per online-softmax step (4 S^T tiles of 32)
 constexpr int VT_PAD = 4;           // halfs of padding per V^T row: 8-byte skew -> conflict-free ds_read_b64
 
+// the optional trailing kernel arguments of a relative position bias, (const float *rel, int P), or none
+__device__ __forceinline__ const float *rel_table() { return nullptr; }
+__device__ __forceinline__ const float *rel_table(const float *rel, int) { return rel; }
+__device__ __forceinline__ int rel_tokens() { return 0; }
+__device__ __forceinline__ int rel_tokens(const float *, int P) { return P; }
+
 template <int D>
 __device__ __forceinline__ int k_off(int row, int chunk) {
     // 16-byte chunk swizzle of the K tile ([n][D] halfs) for conflict-free ds_read_b128
@@ -82,10 +88,22 @@ __device__ __forceinline__ int k_off(int row, int chunk) {
 // therefore PERSISTENT: a workgroup walks the (sentence, head) items v = blockIdx.x, + gridDim.x, ... and requests the NEXT
 // item's K / V rows into registers (64 per thread) before it computes the current one; at the next turn they only have to be
 // written to LDS.  n_items: the number of items (the grid of the non-persistent form).
-template <int D, int NT, int CH, bool MULTI = (NT > 256)>
+// BIAS: a relative position bias (MPNet): score(i, j) = <q_i, k_j> / sqrt(d) + rel[h][j - i + P - 1], rel [n_head][2 P - 1] f32
+// (weights.h rel_bias_table) holding the bias TIMES sqrt(d), because softmax_p8 scales the sum.  Per item the 2 n - 1 entries a
+// sentence of n tokens can meet, rel[h][P - n .. P + n - 2], are staged into LDS behind V^T (2 n_pad floats: the padded keys of
+// the last chunk read on, into whatever is there, and are masked), requested with the item's Q fragments and written between the
+// two barriers of the K / V hand-over, which every wave meets for every item.  Every S^T accumulator element starts from
+// tbl[key - q + n - 1] instead of 0: a lane's runs of four keys are four consecutive entries, the 32 lanes of a half-wave —
+// consecutive queries, one key — read 32 consecutive dwords.  Without BIAS nothing of this is compiled: the kernels are the ones
+// they were, arguments included: Rel is empty, or (const float *rel, int P) — arguments a kernel never reads would still change
+// its prologue and its scalar registers.
+template <int D, int NT, int CH, bool MULTI, class... Rel>
 __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__restrict__ qkv,
                                                              const int32_t *__restrict__ cu_seqlens, int n_head,
-                                                             half_t *__restrict__ out, int n_items) {
+                                                             half_t *__restrict__ out, int n_items, Rel... rel_args) {
+    constexpr bool BIAS = sizeof...(Rel) != 0;
+    const float *__restrict__ rel = rel_table(rel_args...);
+    const int P = rel_tokens(rel_args...);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr bool PERSIST = MULTI;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -168,10 +186,30 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
 #pragma unroll
         for (int kk = 0; kk < D / 16; ++kk) qf[kk] = *(const f16x8 *)(qp + kk * 16);
     }
+    // BIAS: the item's window of the table, two entries a thread in flight beside the Q fragments (all of a sentence of up to NT tokens)
+    float *tbl = (float *)(smem + (size_t)n_pad * D * 2 + (size_t)D * vt_ld * 2);      // [2 n_pad]; entry i <-> distance i - (n - 1)
+    constexpr int TBL_AHEAD = MULTI ? 2 : 1;
+    float tv[TBL_AHEAD];
+    auto rel_entry = [&](int i) -> float {                 // (a sentence longer than P has no entry for its far distances: 0, not a read outside)
+        const int src = P - n + i;
+        return src >= 0 && src < 2 * P - 1 ? rel[(size_t)h * (2 * P - 1) + src] : 0.f;
+    };
+    if constexpr (BIAS) {
+#pragma unroll
+        for (int u = 0; u < TBL_AHEAD; ++u) tv[u] = tid + u * NT < 2 * n - 1 ? rel_entry(tid + u * NT) : 0.f;
+    }
     {
         const int total = (n_pad / 2) * CPR;
         if (!PERSIST) request(cur, tid);
         if (PERSIST && !first) __syncthreads();            // the previous item's fragment reads are done
+        if constexpr (BIAS) {
+            // (in FRONT of the K / V rows: the entries in hand are dead before the deposit's addresses come alive — behind it they cost
+            // the 8-wave d_head 64 form three spilled registers)
+#pragma unroll
+            for (int u = 0; u < TBL_AHEAD; ++u)
+                if (tid + u * NT < 2 * n - 1) tbl[tid + u * NT] = tv[u];
+            for (int i = tid + TBL_AHEAD * NT; i < 2 * n - 1; i += NT) tbl[i] = rel_entry(i);      // (sentences beyond NT tokens: not prefetched)
+        }
         deposit(Ks, Vt, vt_ld, total, tid);
         for (int base = tid + NT * UNR; base < total; base += NT * UNR) {      // (heads beyond 32 K elements: not prefetched)
             request(cur, base);
@@ -225,6 +263,23 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
         for (int kc = 0; kc < n_steps; kc += CH) {
             // ---- S^T chunk: KT key tiles x 16 regs; reg r of tile kt <-> key kc + kt*32 + (r&3) + 8*(r>>2) + 4*hi
             f32x16 s[KT];
+            if constexpr (BIAS) {
+                // the scores start from their bias, tbl[key - q + n - 1], and the MFMAs accumulate onto it: the add costs no register
+                // beyond the accumulators' own (the 8-wave d_head 64 form has none to give: 256 without a spill) and no VALU
+                // instruction.  q: the lane's query under the Q fragments' clamp (the lanes behind the sentence compute its last
+                // query again); keys kc + kt*32 + (r&3) + 8*(r>>2) + 4*hi as the mask below has them: indices 0 .. n + n_pad - 2 of
+                // the 2 n_pad slots.  (No scheduling barrier behind the reads: the compiler spreads a key tile's reads under the tile
+                // before's MFMAs; with all 64 pinned in front of the chunk the 8-wave d_head 64 form spills a register.)
+                // (the lane's part of the address is made HERE from the thread id, behind a statement the compiler cannot see through:
+                // hoisted out of the chunk loop it is one more register alive across it, and the 8-wave d_head 64 form spills)
+                int t = tid;
+                asm volatile("" : "+v"(t));
+                const lds_cptr<float> tb = (lds_cptr<float>)tbl + (n - 1 - min(qb * 32 + (t & 31), n - 1) + kc + 4 * ((t >> 5) & 1));
+#pragma unroll
+                for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[kt][r] = tb[kt * 32 + (r & 3) + 8 * (r >> 2)];
+            }
             // (key tile outside, k-step inside: an accumulator's MFMAs back to back.  The other nest — four accumulators in turn, no
             // MFMA behind its predecessor's result — is 1.5x SLOWER in this phase: 3.6 k against 2.35 k cycles per chunk in the phase
             // clock of round 5, attention at 512 tokens 11.5 against 8.4 ms per 12 launches.)
@@ -247,7 +302,7 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
                     if (f + S_AHEAD < NF) rd(f + S_AHEAD);
                     const int kt = f / (D / 16), kk = f % (D / 16);
                     // (the first k-step starts from the constant 0: no zeroing moves)
-                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfr[f], qf[kk], kk == 0 ? (f32x16)0.f : s[kt], 0, 0, 0);
+                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfr[f], qf[kk], kk == 0 && !BIAS ? (f32x16)0.f : s[kt], 0, 0, 0);
                     if (f + S_AHEAD < NF) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 }
@@ -258,7 +313,7 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
                 for (int kk = 0; kk < D / 16; ++kk) {
                     const f16x8 kf = *(lds_cptr<f16x8>)(kbase[kk] + kt * 32 * K_ROW);
                     // (the first k-step starts from the constant 0: no zeroing moves)
-                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], kk == 0 ? (f32x16)0.f : s[kt], 0, 0, 0);
+                    s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[kk], kk == 0 && !BIAS ? (f32x16)0.f : s[kt], 0, 0, 0);
                 }
             }
             }
@@ -406,21 +461,32 @@ __global__ __launch_bounds__(NT) void attention_mfma_kernel(const half_t *__rest
 #undef ATT_MARK
 }
 
-template <int D>
+// dynamic LDS of a launch whose longest sentence has n_pad key slots: K, V^T and, with a bias, the table's window
+static size_t att_lds_bytes(int n_pad, int d_head, bool bias) {
+    return (size_t)n_pad * d_head * 2 + (size_t)d_head * (n_pad + VT_PAD) * 2 + (bias ? (size_t)2 * n_pad * sizeof(float) : 0);
+}
+
+template <int D, bool BIAS>
 static void launch_att(const half_t *qkv, const int32_t *cu, const AttentionGrid &g, int n_head, int max_len, half_t *out,
-                       hipStream_t s) {
+                       hipStream_t s, const float *rel, int P) {
     const int n_pad = (max_len + ATT_CHUNK - 1) / ATT_CHUNK * ATT_CHUNK;
-    const size_t lds = (size_t)n_pad * D * 2 + (size_t)D * (n_pad + VT_PAD) * 2;
+    const size_t lds = att_lds_bytes(n_pad, D, BIAS);
     // per device: the opt-in is a per-device attribute; the devices of a context launch from threads of their own
     static DeviceFlags configured[2];
     const bool wide = n_pad > 128;
     if (lds > 64 * 1024)
         configure_once(configured[wide], [&] {                 // (once, for the largest LDS the kernel can be launched with)
-            if (wide) (void)hipFuncSetAttribute((const void *)attention_mfma_kernel<D, 512, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            else (void)hipFuncSetAttribute((const void *)attention_mfma_kernel<D, 256, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            const void *k = BIAS ? (wide ? (const void *)attention_mfma_kernel<D, 512, 128, true, const float *, int> : (const void *)attention_mfma_kernel<D, 256, 128, false, const float *, int>)
+                                 : (wide ? (const void *)attention_mfma_kernel<D, 512, 128, true> : (const void *)attention_mfma_kernel<D, 256, 128, false>);
+            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         });
-    if (wide) BERT_LAUNCH((attention_mfma_kernel<D, 512, 128>), dim3(g.grid), dim3(512), lds, s, qkv, cu, n_head, out, g.items);
-    else BERT_LAUNCH((attention_mfma_kernel<D, 256, 128>), dim3(g.grid), dim3(256), lds, s, qkv, cu, n_head, out, g.items);
+    if constexpr (BIAS) {
+        if (wide) BERT_LAUNCH((attention_mfma_kernel<D, 512, 128, true, const float *, int>), dim3(g.grid), dim3(512), lds, s, qkv, cu, n_head, out, g.items, rel, P);
+        else BERT_LAUNCH((attention_mfma_kernel<D, 256, 128, false, const float *, int>), dim3(g.grid), dim3(256), lds, s, qkv, cu, n_head, out, g.items, rel, P);
+    } else {
+        if (wide) BERT_LAUNCH((attention_mfma_kernel<D, 512, 128, true>), dim3(g.grid), dim3(512), lds, s, qkv, cu, n_head, out, g.items);
+        else BERT_LAUNCH((attention_mfma_kernel<D, 256, 128, false>), dim3(g.grid), dim3(256), lds, s, qkv, cu, n_head, out, g.items);
+    }
 #ifdef BERT_HIP_TIMELINE
     {
         static int shots = 0;
@@ -440,9 +506,9 @@ static void launch_att(const half_t *qkv, const int32_t *cu, const AttentionGrid
 }
 
 // The choice of form and grid, host arithmetic and the device's CU count alone (kernels.h).
-AttentionGrid attention_mfma_grid(int n_sentences, int n_head, int d_head, int max_len) {
+AttentionGrid attention_mfma_grid(int n_sentences, int n_head, int d_head, int max_len, bool bias) {
     const int n_pad = (max_len + ATT_CHUNK - 1) / ATT_CHUNK * ATT_CHUNK;
-    const size_t lds = (size_t)n_pad * d_head * 2 + (size_t)d_head * (n_pad + VT_PAD) * 2;
+    const size_t lds = att_lds_bytes(n_pad, d_head, bias);
     if (lds > 160 * 1024 || (d_head != 32 && d_head != 64)) return AttentionGrid{0, 0, 0};
     const int items = n_sentences * n_head;
     if (n_pad <= 128) return AttentionGrid{256, items, items};
@@ -457,18 +523,26 @@ AttentionGrid attention_mfma_grid(int n_sentences, int n_head, int d_head, int m
 }
 
 bool launch_attention_mfma(const half_t *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head,
-                           int max_len, half_t *out, hipStream_t stream) {
-    const AttentionGrid g = attention_mfma_grid(n_sentences, n_head, d_head, max_len);
+                           int max_len, half_t *out, hipStream_t stream, const float *rel, int P) {
+    const AttentionGrid g = attention_mfma_grid(n_sentences, n_head, d_head, max_len, rel != nullptr);
     if (!g.threads) return false;
-    if (d_head == 32) launch_att<32>(qkv, cu_seqlens, g, n_head, max_len, out, stream);
-    else launch_att<64>(qkv, cu_seqlens, g, n_head, max_len, out, stream);
+    if (rel) {
+        if (d_head == 32) launch_att<32, true>(qkv, cu_seqlens, g, n_head, max_len, out, stream, rel, P);
+        else launch_att<64, true>(qkv, cu_seqlens, g, n_head, max_len, out, stream, rel, P);
+    } else if (d_head == 32) launch_att<32, false>(qkv, cu_seqlens, g, n_head, max_len, out, stream, nullptr, 0);
+    else launch_att<64, false>(qkv, cu_seqlens, g, n_head, max_len, out, stream, nullptr, 0);
     return true;
 }
 
 // ------------------------------------------------------------------------------------------------
 // generic fallback: one wave per (sentence, head, query); any d_head, any length
 // ------------------------------------------------------------------------------------------------
-__global__ void attention_naive_kernel(const half_t *qkv, const int32_t *cu_seqlens, int n_head, int d, half_t *out) {
+// BIAS: rel [n_head][2 P - 1] (weights.h rel_bias_table, the bias itself: this kernel scales the score before the add)
+template <class... Rel>
+__global__ void attention_naive_kernel(const half_t *qkv, const int32_t *cu_seqlens, int n_head, int d, half_t *out, Rel... rel_args) {
+    constexpr bool BIAS = sizeof...(Rel) != 0;
+    const float *rel = rel_table(rel_args...);
+    const int P = rel_tokens(rel_args...);
     extern __shared__ float sh[];          // [4 waves][max_len] scores
     const int b = blockIdx.y, h = blockIdx.z;
     const int tok0 = cu_seqlens[b], n = cu_seqlens[b + 1] - tok0;
@@ -485,6 +559,10 @@ __global__ void attention_naive_kernel(const half_t *qkv, const int32_t *cu_seql
         float a = 0.f;
         for (int e = 0; e < d; ++e) a += (float)kp[e] * (float)qp[e];
         a *= scale;
+        if constexpr (BIAS) {
+            const int di = j - q + P - 1;                     // (a sentence longer than P: no entry, no read outside)
+            if (di >= 0 && di < 2 * P - 1) a += rel[(size_t)h * (2 * P - 1) + di];
+        }
         s[j] = a;
         mx = fmaxf(mx, a);
     }
@@ -505,12 +583,13 @@ __global__ void attention_naive_kernel(const half_t *qkv, const int32_t *cu_seql
 // chunk of 262 144 tokens has more sentences than that once they average four tokens or fewer, so they go in slices of 65535
 // (cu_seqlens holds absolute token offsets: a slice starts at its own entry of it).
 void launch_attention_naive(const half_t *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head,
-                            int max_len, half_t *out, hipStream_t stream) {
+                            int max_len, half_t *out, hipStream_t stream, const float *rel, int P) {
     const int qblocks = (max_len + 3) / 4;
     const size_t lds = (size_t)4 * qblocks * 4 * sizeof(float);
     for (int b0 = 0; b0 < n_sentences; b0 += GRID_YZ_MAX) {
         const dim3 grid(qblocks, std::min(GRID_YZ_MAX, n_sentences - b0), n_head);
-        BERT_LAUNCH(attention_naive_kernel, grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, out);
+        if (rel) BERT_LAUNCH((attention_naive_kernel<const float *, int>), grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, out, rel, P);
+        else BERT_LAUNCH(attention_naive_kernel<>, grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, out);
     }
 }
 

@@ -69,6 +69,17 @@ bert_ctx *load_impl(const char *fname, bool tokenizer_only) {
     ctx->hp = mf.hp;
     ctx->tok.build(std::move(mf.vocab));
     ctx->tok.quiet = quiet;           // BERT_HIP_QUIET also drops the reference's per-byte "unknown token" stderr lines
+    ctx->rel_bias = mf.rel_bias;
+    if (mf.rel_bias) {
+        // an MPNet file: its texts are <s> ... </s>.  (Every BERT file keeps 101 / 102 whatever its vocabulary holds.)
+        ctx->tok.cls_id = ctx->tok.find("<s>");
+        ctx->tok.sep_id = ctx->tok.find("</s>");
+        if (ctx->tok.cls_id < 0 || ctx->tok.sep_id < 0) {
+            fprintf(stderr, ME "the model has a relative position bias (%s) but its vocabulary has no '%s' entry\n", REL_BIAS_NAME,
+                    ctx->tok.cls_id < 0 ? "<s>" : "</s>");
+            return nullptr;
+        }
+    }
     ctx->texts.tok = &ctx->tok;
     ctx->texts.n_max_tokens = mf.hp.n_max_tokens;
     if (tokenizer_only) return ctx.release();

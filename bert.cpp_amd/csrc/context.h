@@ -40,6 +40,8 @@ struct bert_hip_token_index {
 
 struct bert_ctx {
     bert_hip::HParams hp;
+    // the model file holds MPNet's relative position bias (model_file.h): tok wraps a text in <s> ... </s>, the pair routes refuse
+    bool rel_bias = false;
     bert_hip::Tokenizer tok;
     // one engine (weight replica + stream + workspace) per GPU; empty for tokenizer-only contexts.  Devices:
     // BERT_HIP_DEVICES ("all" or a comma-separated list without repeats), else the

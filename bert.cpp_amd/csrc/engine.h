@@ -66,6 +66,7 @@ public:
     // each: d_ids i32 [n_sentences][k], d_weights f32 [n_sentences][k].  -2 with a message for a model without the head.  After
     // reserve() it allocates nothing: reserve fixes the chunk and sizes sparse_dense_ with the workspace.
     bool has_mlm_head() const { return w_->mlm_head; }
+    bool has_rel_bias() const { return w_->rel_bias; }
     int sparse_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int n_sentences, int n_tokens, int max_len, int k, int32_t *d_ids,
                              float *d_weights, hipStream_t stream, std::string &err);
     // Host form, blocking, on this engine's device: cut at chunk_tokens between sentences and at the sentences whose results fit 32 MiB,

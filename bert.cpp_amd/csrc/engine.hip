@@ -191,12 +191,15 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
     // one-launch kernel (which takes all layers' pointers) or with its LayerNorms folded (only models the fused kernels do not take)
     p.layers.resize(Lz);
     bool qkv2_shape0 = false, one_launch = true, fold = opt_.ln_fold && H > 384 && H % 256 == 0 && ln_rows2_.p;
+    // a relative position bias (MPNet files) lives in the attention launch alone: such a model takes none of the kernels that hold an
+    // attention of their own — qkv_attention2, and with it the one-launch kernel, and the latency route, which shares their bits
+    const bool fused_attention = !w_->rel_bias;
     for (int il = 0; il < Lz; ++il) {
         const LayerWeights &L = w_->layers[il];
         LayerPlan &lp = p.layers[il];
         const bool qkv2_shape = qkv_attention2_supported(L.qkv.w, nh, dh, max_len), tail_shape = layer_tail_supported(L.o.w, L.ffi.w, L.ffo.w);
         if (il == 0) qkv2_shape0 = qkv2_shape;
-        lp.qkv2 = opt_.qkv2 && !opt_.gemm_naive && !opt_.attn_naive && L.qkv.mfma_ok && qkv2_shape;
+        lp.qkv2 = fused_attention && opt_.qkv2 && !opt_.gemm_naive && !opt_.attn_naive && L.qkv.mfma_ok && qkv2_shape;
         lp.tail = opt_.tail && !opt_.gemm_naive && L.o.mfma_ok && L.ffi.mfma_ok && L.ffo.mfma_ok && tail_shape;
         // (q4 files: the 4-bit planes of the stacked matrix where its f16 image overflows an XCD's L2 and gemm256 takes the launch)
         lp.planes = L.qkv_q4.w.qs && family(L.qkv_q4) == Family::GEMM256;
@@ -236,7 +239,7 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
     bool one_launch_pays = full_windows || opt_.one_launch == 2;
     if (!one_launch_pays && !p.build_windows) one_launch_pays = (d_windows || spw == 1) && 100ll * T >= 95ll * 128 * (d_windows ? n_windows : B);
     const LayerWeights &L0 = w_->layers[0];
-    const bool skinny = latency_call && opt_.tail && opt_.qkv2 && !opt_.gemm_naive && !opt_.attn_naive && max_len <= 128 && (dh == 32 || dh == 64) &&
+    const bool skinny = fused_attention && latency_call && opt_.tail && opt_.qkv2 && !opt_.gemm_naive && !opt_.attn_naive && max_len <= 128 && (dh == 32 || dh == 64) &&
                         skinny_layer_supported(L0.qkv.w, L0.o.w, L0.ffi.w, L0.ffo.w) && qkv2_shape0;
     p.route = skinny ? Route::LATENCY : one_launch && one_launch_pays ? Route::ONE_LAUNCH : fold ? Route::FOLDED : Route::LAYERED;
     // (launch_model_kernel takes its full form by the same rule; neither a tap nor token rows reach this route, nothing else reads x_ on it
@@ -268,8 +271,11 @@ bool Engine::gemm(const Plan &p, const char *name, Family f, const GemmWeightSto
 void Engine::attention(const Plan &p) {
     const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh;
     half_t *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>();
+    // (the relative position bias of the file, if it has one: null pointers otherwise)
+    const int P = hp_.n_max_tokens;
     timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] {
-        if (opt_.attn_naive || !launch_attention_mfma(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s)) launch_attention_naive(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s);
+        if (opt_.attn_naive || !launch_attention_mfma(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s, w_->rel_scaled.as<float>(), P))
+            launch_attention_naive(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s, w_->rel.as<float>(), P);
     });
 }
 
@@ -414,7 +420,7 @@ bool Engine::forward_f32(const Plan &p, std::string &err) {
         const LayerWeights &L = w_->layers[il];
         if (!gemm(p, "gemm_qkv", F, L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS, err)) return false;
         bool launched = true;
-        timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] { launched = launch_f32_attention(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s); });
+        timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] { launched = launch_f32_attention(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s, w_->rel.as<float>(), hp_.n_max_tokens); });
         if (!launched) {
             err = "f32 route: the attention kernel keeps the scores of max_len = " + std::to_string(p.max_len) + " keys per wave in LDS, " +
                   std::to_string(f32_attention_lds_bytes(p.max_len)) + " bytes a workgroup; this device's limit is " +

@@ -160,7 +160,17 @@ void launch_f32_gemm(const float *A, const float *W, const float *bias, const fl
 // softmax with the true maximum subtracted, exponentials and sums in f32; no mask (a sentence attends over its own tokens).
 // A wave's stripe of scores holds gridDim.x * 4 >= max_len floats: a sentence longer than max_len (the device API's promise broken)
 // does not fit, and its waves leave before they touch LDS or write a row; the pooling kernel gives it a NaN row and raises the status word.
-__global__ void f32_attention_kernel(const float *qkv, const int32_t *cu_seqlens, int n_head, int d, int max_len, float *out) {
+// BIAS: rel [n_head][2 P - 1] (weights.h rel_bias_table, the bias itself) is added to the scaled score, MPNet's relative position bias.
+// (Rel: no arguments, or (const float *rel, int P): the kernel without the bias keeps its argument list)
+__device__ __forceinline__ const float *f32_rel_table() { return nullptr; }
+__device__ __forceinline__ const float *f32_rel_table(const float *rel, int) { return rel; }
+__device__ __forceinline__ int f32_rel_tokens() { return 0; }
+__device__ __forceinline__ int f32_rel_tokens(const float *, int P) { return P; }
+template <class... Rel>
+__global__ void f32_attention_kernel(const float *qkv, const int32_t *cu_seqlens, int n_head, int d, int max_len, float *out, Rel... rel_args) {
+    constexpr bool BIAS = sizeof...(Rel) != 0;
+    const float *rel = f32_rel_table(rel_args...);
+    const int P = f32_rel_tokens(rel_args...);
     extern __shared__ float sh[];          // [4 waves][max_len rounded up to 4] scores
     const int b = blockIdx.y, h = blockIdx.z;
     const int tok0 = cu_seqlens[b], n = cu_seqlens[b + 1] - tok0;
@@ -177,6 +187,10 @@ __global__ void f32_attention_kernel(const float *qkv, const int32_t *cu_seqlens
         float a = 0.f;
         for (int e = 0; e < d; ++e) a = fmaf(kp[e], qp[e], a);
         a *= scale;
+        if constexpr (BIAS) {
+            const int di = j - q + P - 1;                     // (a sentence longer than P: no entry, no read outside)
+            if (di >= 0 && di < 2 * P - 1) a += rel[(size_t)h * (2 * P - 1) + di];
+        }
         s[j] = a;
         mx = fmaxf(mx, a);
     }
@@ -258,7 +272,7 @@ size_t f32_attention_lds_bytes(int max_len) { return (size_t)4 * ((max_len + 3) 
 
 // false, and nothing launched: the scores of max_len keys for four waves do not fit the LDS a workgroup can have on this device
 bool launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head, int max_len, float *out,
-                          hipStream_t stream) {
+                          hipStream_t stream, const float *rel, int P) {
     if (max_len <= 0) return false;
     const int qblocks = (max_len + 3) / 4;
     const size_t lds = f32_attention_lds_bytes(max_len);
@@ -266,11 +280,13 @@ bool launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sen
     static DeviceFlags configured;
     if (lds > 64 * 1024)
         configure_once(configured, [&] {
-            (void)hipFuncSetAttribute((const void *)f32_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f32_attention_lds_limit());
+            (void)hipFuncSetAttribute((const void *)f32_attention_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f32_attention_lds_limit());
+            (void)hipFuncSetAttribute((const void *)f32_attention_kernel<const float *, int>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)f32_attention_lds_limit());
         });
     for (int b0 = 0; b0 < n_sentences; b0 += GRID_YZ_MAX) {    // (a grid dimension holds 65535 sentences)
         const dim3 grid(qblocks, std::min(GRID_YZ_MAX, n_sentences - b0), n_head);
-        BERT_LAUNCH(f32_attention_kernel, grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, max_len, out);
+        if (rel) BERT_LAUNCH((f32_attention_kernel<const float *, int>), grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, max_len, out, rel, P);
+        else BERT_LAUNCH(f32_attention_kernel<>, grid, dim3(256), lds, stream, qkv, cu_seqlens + b0, n_head, d_head, max_len, out);
     }
     return true;
 }

@@ -139,15 +139,19 @@ void launch_layernorm(half_t *x, const float *gamma, const float *beta, int T, i
 
 // qkv [T_pad][3H] (Q | K | V), packed sentences; out ctx [T_pad][H].
 // MFMA path supports d_head in {32, 64}; returns false if the shape needs the naive kernel.
+// rel, P: a relative position bias (MPNet), score(i, j) = <q_i, k_j> / sqrt(d_head) + bias[h][j - i]; rel [n_head][2 P - 1] f32 on the
+// device is weights.h rel_bias_table for sentences of up to P tokens — for the MFMA kernel times sqrt(d_head) (it scales the sum), for
+// the naive kernel the bias itself.  nullptr: no bias, the kernels every pass without one runs.
 bool launch_attention_mfma(const half_t *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head,
-                           int max_len, half_t *out, hipStream_t stream);
+                           int max_len, half_t *out, hipStream_t stream, const float *rel = nullptr, int P = 0);
 void launch_attention_naive(const half_t *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head,
-                            int max_len, half_t *out, hipStream_t stream);
+                            int max_len, half_t *out, hipStream_t stream, const float *rel = nullptr, int P = 0);
 // The form and grid launch_attention_mfma launches on the current device: threads per workgroup — 256, one workgroup per (sentence, head)
 // item, up to 128 tokens; 512, the persistent form, beyond: min(CUs / 8 * 8, items / 8 * 8) workgroups (all of fewer than 8 items) that
-// walk the items —, the grid and the items.  All zero where the launcher refuses the shape (d_head, or more LDS than 160 KiB).
+// walk the items —, the grid and the items.  All zero where the launcher refuses the shape (d_head, or more LDS than 160 KiB; bias: a
+// launch with a relative position bias, which keeps 8 bytes per key slot more).
 struct AttentionGrid { int threads, grid, items; };
-AttentionGrid attention_mfma_grid(int n_sentences, int n_head, int d_head, int max_len);
+AttentionGrid attention_mfma_grid(int n_sentences, int n_head, int d_head, int max_len, bool bias = false);
 
 // Q|K|V projection + attention in one kernel (qkv_attention2.hip): x [T_pad][H] -> ctx [T_pad][H].  A workgroup owns a window
 // of 128 token slots holding one or several whole sentences (16-slot aligned); f16 or q4 weights, d_head 32, H = 128 / 256 / 384, every sentence <= 128 tokens.
@@ -326,8 +330,9 @@ void launch_f32_gemm(const float *A, const float *W, const float *bias, const fl
 // workgroup (sharedMemPerBlock), or when max_len < 1.
 size_t f32_attention_lds_bytes(int max_len);
 size_t f32_attention_lds_limit();
+// rel, P: as launch_attention_naive (the bias itself).
 bool launch_f32_attention(const float *qkv, const int32_t *cu_seqlens, int n_sentences, int n_head, int d_head, int max_len, float *out,
-                          hipStream_t stream);
+                          hipStream_t stream, const float *rel = nullptr, int P = 0);
 void launch_f32_layernorm(float *x, const float *gamma, const float *beta, int T, int H, hipStream_t stream);
 void launch_f32_pool_normalize(const float *x, const int32_t *cu_seqlens, int n_sentences, int H, int max_len, int *status, float *out,
                                int pool_mode, hipStream_t stream);

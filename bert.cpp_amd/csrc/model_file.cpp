@@ -87,6 +87,25 @@ std::map<std::string, Expect> mlm_tensors(const HParams &h) {
     return m;
 }
 
+// vocab_only loads: is REL_BIAS_NAME among the tensor records that start at `off`?  Walks the records' headers, skipping the data
+// (a file that ends with its vocabulary, or whose records do not parse — the legacy q4 layout's other block sizes —, has none).
+bool file_has_rel_bias(const char *fname, long off, long sz) {
+    FILE *f = fopen(fname, "rb");
+    if (!f) return false;
+    bool found = false;
+    while (!found && off + 12 <= sz && fseek(f, off, SEEK_SET) == 0) {
+        int32_t h[3], ne[2] = {1, 1};
+        if (fread(h, 4, 3, f) != 3 || h[0] < 1 || h[0] > 2 || h[1] <= 0 || h[1] > 4096 || h[2] < 0 || h[2] > 3) break;
+        if (fread(ne, 4, (size_t)h[0], f) != (size_t)h[0] || ne[0] <= 0 || ne[1] <= 0) break;
+        std::string name((size_t)h[1], '\0');
+        if (fread(&name[0], 1, name.size(), f) != name.size()) break;
+        found = name == REL_BIAS_NAME;
+        off += 12 + 4 * h[0] + h[1] + (long)(wtype_row_bytes(h[2], ne[0]) * (size_t)ne[1]);
+    }
+    fclose(f);
+    return found;
+}
+
 }  // namespace
 
 bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
@@ -128,7 +147,11 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
         vocab.emplace_back((const char *)c.p, len);
         c.p += len;
     }
-    if (vocab_only) return true;
+    rel_bias = false;
+    if (vocab_only) {
+        rel_bias = file_has_rel_bias(fname, (long)(c.p - blob.data()), sz);
+        return true;
+    }
 
     if (hp.f16 < 0 || hp.f16 > 3) {
         err = std::string("invalid model file '") + fname + "' (bad f16 value " + std::to_string(hp.f16) + ")";
@@ -181,6 +204,29 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
         std::string name((const char *)c.p, name_len);
         c.p += name_len;
         auto ex = expect.find(name);
+        if (name == REL_BIAS_NAME) {
+            // never quantised: f32, or f16 in an f16 file, whatever the file-wide type
+            if (n_dims != 2 || ne[1] != REL_BUCKETS) {
+                err = "tensor '" + name + "': " + std::to_string(n_dims == 2 ? ne[1] : 0) + " relative position buckets, this library takes " +
+                      std::to_string(REL_BUCKETS) + " (MPNet's)";
+                return false;
+            }
+            if (ne[0] != hp.n_head) {
+                err = "tensor '" + name + "' has wrong shape in model file: got [" + std::to_string(ne[0]) + ", " + std::to_string(ne[1]) + "], expected [" +
+                      std::to_string(hp.n_head) + ", " + std::to_string(REL_BUCKETS) + "]";
+                return false;
+            }
+            if (ftype != W_F32 && ftype != W_F16) { err = "tensor '" + name + "' is stored in type " + std::to_string(ftype) + ": f32 or f16 expected"; return false; }
+            const size_t nb = wtype_row_bytes(ftype, ne[0]) * (size_t)ne[1];
+            if ((size_t)(c.end - c.p) < nb) { err = "tensor '" + name + "' is truncated"; return false; }
+            HostTensor t;
+            t.type = ftype; t.n_dims = n_dims; t.ne0 = ne[0]; t.ne1 = ne[1]; t.data = c.p; t.nbytes = nb;
+            tensors[name] = t;
+            total_tensor_bytes += nb;
+            c.p += nb;
+            rel_bias = true;
+            continue;
+        }
         if (ex == expect.end()) {
             ex = head.find(name);
             if (ex == head.end()) {

@@ -14,6 +14,8 @@ namespace bert_hip {
 
 enum WType : int32_t { W_F32 = 0, W_F16 = 1, W_Q4_0 = 2, W_Q4_1 = 3 };
 constexpr int HEAD_MAX_LABELS = 8;   // classifier.weight [H, n_labels]: 1 .. 8 labels
+constexpr int REL_BUCKETS = 32;      // encoder.relative_attention_bias.weight [n_head, 32]: MPNet's relative position buckets
+constexpr const char *REL_BIAS_NAME = "encoder.relative_attention_bias.weight";
 
 struct HParams {             // reference bert.cpp:18-27, file order :361-367
     int32_t n_vocab = 0, n_max_tokens = 0, n_embd = 0, n_intermediate = 0, n_head = 0, n_layer = 0, f16 = 0;
@@ -38,6 +40,10 @@ struct ModelFile {
     // the optional masked-language-model head (cls.predictions.transform.dense.{weight, bias}, .transform.LayerNorm.{weight, bias},
     // cls.predictions.bias [n_vocab]: all five or none; the decoder matrix is the word embeddings)
     bool mlm_head = false;
+    // the optional relative position bias of MPNet (encoder.relative_attention_bias.weight, [REL_BUCKETS][n_head], f32 or f16 whatever
+    // the file-wide type: never quantised; one table shared by all layers), behind the encoder's set; it may coexist with either head.
+    // A vocab_only load finds it by walking the tensor records' headers: the tokenizer's [CLS] / [SEP] ids depend on it.
+    bool rel_bias = false;
     bool legacy_q4 = false;                          // the file uses the 20 / 24-byte q4 blocks of early-2023 ggml
     std::vector<std::vector<uint8_t>> converted;     // their tensors, re-blocked into the current layout
 

@@ -74,6 +74,7 @@ int32_t join_pair(const int32_t *a, int32_t la, const int32_t *b, int32_t lb, in
 
 extern "C" {
 
+int32_t bert_hip_relative_attention(struct bert_ctx *ctx) { return ctx ? (ctx->rel_bias ? 1 : 0) : -1; }
 int32_t bert_hip_n_labels(struct bert_ctx *ctx) { return ctx && ctx->engine() ? ctx->engine()->n_labels() : 0; }
 
 int32_t bert_hip_tokenize_pair(struct bert_ctx *ctx, const char *text_a, const char *text_b, bert_vocab_id *tokens, int32_t *n_tokens,
@@ -170,6 +171,10 @@ int32_t bert_hip_score_pairs(struct bert_ctx *ctx, int32_t n_threads, int32_t n_
         if (!ctx || !ctx->engine()) { fprintf(stderr, "%s: this context has no device weights (tokenizer-only)\n", me); return -1; }
         const int32_t NL = ctx->engine()->n_labels();
         if (NL <= 0) { fprintf(stderr, "%s: the model file has no classification head (pooler.dense.*, classifier.*)\n", me); return -2; }
+        if (ctx->rel_bias) {
+            fprintf(stderr, "%s: the model has a relative position bias (MPNet): its pair layout, <s> a </s></s> b </s>, is not built here; pack the ids and call bert_hip_score_packed\n", me);
+            return -2;
+        }
         if (n_pairs <= 0) return 0;
         if (!texts_a || !texts_b || !scores || (flags & ~1)) { fprintf(stderr, "%s: texts, scores and flags 0 | 1 required\n", me); return -2; }
         const int32_t N = ctx->hp.n_max_tokens;

@@ -82,6 +82,41 @@ struct TailOperands {
     }
 };
 
+// bert_hip_test_attention[_bias]: W [32][n_head] expanded for P tokens (or rel as it is), none for both NULL
+static int32_t test_attention(const char *me, int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head, const uint16_t *qkv,
+                              int32_t impl, uint16_t *out, const float *W, int32_t P, const float *rel) {
+    std::string err;
+    const int T = cu_seqlens[n_sentences], H = n_head * d_head;
+    int max_len = 0;
+    for (int b = 0; b < n_sentences; ++b) max_len = std::max(max_len, cu_seqlens[b + 1] - cu_seqlens[b]);
+    // (whole token tiles, as in the engine's workspaces, and one key tile more: the kernel pads the LAST sentence's keys to 128 in LDS,
+    // not from memory, and one that loaded them would find the pattern there instead of leaving the buffer)
+    const int T_pad = (T + 255) / 256 * 256 + 128;
+    DevBuf dq, dcu, dout, drel;
+    const bool bias = W || rel;
+    if (bias && (P < 1 || max_len > P || n_head < 1)) { fprintf(stderr, "%s: a sentence of %d tokens, the table is for up to %d\n", me, max_len, P); return -1; }
+    if (!upload_rows16(dq, qkv, T, T_pad, 3 * H, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
+        !alloc_pad16(dout, (size_t)T_pad * H, err) ||
+        (bias && !(rel ? drel.upload(rel, (size_t)n_head * (2 * P - 1) * 4, err)
+                       : drel.upload(rel_bias_table(W, n_head, P, impl == 0 ? std::sqrt((double)d_head) : 1.0), err)))) {
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return -1;
+    }
+    const float *dr = bias ? drel.as<float>() : nullptr;
+    if (impl == 0) {
+        if (!launch_attention_mfma(dq.as<half_t>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<half_t>(), nullptr, dr, P)) {
+            fprintf(stderr, "%s: shape not supported by the MFMA path\n", me);
+            return -2;
+        }
+    } else {
+        launch_attention_naive(dq.as<half_t>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<half_t>(), nullptr, dr, P);
+    }
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, (size_t)T * H * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" {
 
 int32_t bert_hip_test_gemm(int32_t M, int32_t N, int32_t K, const uint16_t *A, const void *W, int32_t wtype,
@@ -169,30 +204,19 @@ int32_t bert_hip_test_gemm_lnfold(int32_t M, int32_t K1, int32_t H, int32_t N2, 
 
 int32_t bert_hip_test_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head,
                                 const uint16_t *qkv, int32_t impl, uint16_t *out) {
-    std::string err;
-    const int T = cu_seqlens[n_sentences], H = n_head * d_head;
-    int max_len = 0;
-    for (int b = 0; b < n_sentences; ++b) max_len = std::max(max_len, cu_seqlens[b + 1] - cu_seqlens[b]);
-    // (whole token tiles, as in the engine's workspaces, and one key tile more: the kernel pads the LAST sentence's keys to 128 in LDS,
-    // not from memory, and one that loaded them would find the pattern there instead of leaving the buffer)
-    const int T_pad = (T + 255) / 256 * 256 + 128;
-    DevBuf dq, dcu, dout;
-    if (!upload_rows16(dq, qkv, T, T_pad, 3 * H, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
-        !alloc_pad16(dout, (size_t)T_pad * H, err)) {
-        fprintf(stderr, "bert_hip_test_attention: %s\n", err.c_str());
-        return -1;
-    }
-    if (impl == 0) {
-        if (!launch_attention_mfma(dq.as<half_t>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<half_t>(), nullptr)) {
-            fprintf(stderr, "bert_hip_test_attention: shape not supported by the MFMA path\n");
-            return -2;
-        }
-    } else {
-        launch_attention_naive(dq.as<half_t>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<half_t>(), nullptr);
-    }
-    CK(hipGetLastError());
-    CK(hipDeviceSynchronize());
-    CK(hipMemcpy(out, dout.p, (size_t)T * H * 2, hipMemcpyDeviceToHost));
+    return test_attention("bert_hip_test_attention", n_sentences, cu_seqlens, n_head, d_head, qkv, impl, out, nullptr, 0, nullptr);
+}
+
+int32_t bert_hip_test_attention_bias(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head, const uint16_t *qkv,
+                                     int32_t impl, uint16_t *out, const float *W, int32_t P, const float *rel) {
+    if (!W && !rel) { fprintf(stderr, "bert_hip_test_attention_bias: W or rel required\n"); return -1; }
+    return test_attention("bert_hip_test_attention_bias", n_sentences, cu_seqlens, n_head, d_head, qkv, impl, out, W, P, rel);
+}
+
+int32_t bert_hip_test_rel_bias_table(const float *W, int32_t n_head, int32_t P, float *out) {
+    if (!W || !out || n_head < 1 || P < 1) return -1;
+    const std::vector<float> rel = rel_bias_table(W, n_head, P, 1.0);
+    memcpy(out, rel.data(), rel.size() * 4);
     return 0;
 }
 
@@ -530,18 +554,30 @@ int32_t bert_hip_test_f32_gemm(int32_t M, int32_t N, int32_t K, const float *A, 
     return download_rows32("bert_hip_test_f32_gemm", C, dC, M, M_pad, N);
 }
 
+// bert_hip_test_f32_attention[_bias]: W [32][n_head] expanded for P tokens, NULL: none
+static int32_t test_f32_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head, int32_t max_len,
+                                  const float *qkv, float *out, const float *W, int32_t P);
 int32_t bert_hip_test_f32_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head, int32_t max_len,
                                     const float *qkv, float *out) {
+    return test_f32_attention(n_sentences, cu_seqlens, n_head, d_head, max_len, qkv, out, nullptr, 0);
+}
+int32_t bert_hip_test_f32_attention_bias(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head, int32_t max_len,
+                                         const float *qkv, float *out, const float *W, int32_t P) {
+    if (!W || P < 1 || max_len > P) { fprintf(stderr, "bert_hip_test_f32_attention_bias: W and P >= max_len required\n"); return -1; }
+    return test_f32_attention(n_sentences, cu_seqlens, n_head, d_head, max_len, qkv, out, W, P);
+}
+static int32_t test_f32_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head, int32_t max_len,
+                                  const float *qkv, float *out, const float *W, int32_t P) {
     std::string err;
     if (n_sentences <= 0 || n_head <= 0 || d_head <= 0) return -1;
     const int T = cu_seqlens[n_sentences], H = n_head * d_head, T_pad = f32_rows_pad(T);
-    DevBuf dq, dcu, dout;
+    DevBuf dq, dcu, dout, drel;
     if (!upload_rows32(dq, qkv, T, T_pad, 3 * H, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
-        !alloc_pad32(dout, (size_t)T_pad * H, err)) {
+        !alloc_pad32(dout, (size_t)T_pad * H, err) || (W && !drel.upload(rel_bias_table(W, n_head, P, 1.0), err))) {
         fprintf(stderr, "bert_hip_test_f32_attention: %s\n", err.c_str());
         return -1;
     }
-    if (!launch_f32_attention(dq.as<float>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<float>(), nullptr)) {
+    if (!launch_f32_attention(dq.as<float>(), dcu.as<int32_t>(), n_sentences, n_head, d_head, max_len, dout.as<float>(), nullptr, W ? drel.as<float>() : nullptr, P)) {
         fprintf(stderr, "bert_hip_test_f32_attention: max_len = %d needs %zu bytes of LDS a workgroup, the device's limit is %zu\n", max_len,
                 f32_attention_lds_bytes(max_len), f32_attention_lds_limit());
         return -2;

@@ -104,6 +104,11 @@ void Tokenizer::build(std::vector<std::string> &&words) {
     }
 }
 
+int32_t Tokenizer::find(std::string_view word) const {
+    const auto it = token_to_id_.find(word);
+    return it == token_to_id_.end() ? -1 : it->second;
+}
+
 const char *Tokenizer::id_to_token(int32_t id) const {
     if (id >= 0 && (size_t)id < words_.size() && (has_token_[id] || has_subword_[id])) return words_[id].c_str();
     return "[UNK TOKEN from bert_vocab]";
@@ -116,7 +121,7 @@ void Tokenizer::tokenize(const char *text, int32_t *tokens, int32_t *n_tokens, i
     const size_t n = str.size();
 
     int32_t t = 0;
-    tokens[t++] = 101;   // [CLS]
+    tokens[t++] = cls_id;
 
     size_t p = 0;
     while (p < n) {
@@ -155,7 +160,7 @@ void Tokenizer::tokenize(const char *text, int32_t *tokens, int32_t *n_tokens, i
             max_len = max_subword_len_;
         }
     }
-    tokens[t++] = 102;   // [SEP]
+    tokens[t++] = sep_id;
     *n_tokens = t;
 }
 

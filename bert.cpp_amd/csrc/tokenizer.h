@@ -29,6 +29,11 @@ public:
     const char *id_to_token(int32_t id) const;
 
     size_t size() const { return words_.size(); }
+    // the id of a whole-word vocabulary entry, -1 if there is none
+    int32_t find(std::string_view word) const;
+    // what opens and closes a text: BERT's [CLS] / [SEP] ids; a context whose model has MPNet's relative position bias sets them to the
+    // ids of <s> and </s> in the file's vocabulary (context.cpp)
+    int32_t cls_id = 101, sep_id = 102;
     bool quiet = false;   // suppress the per-byte "unknown token" stderr line of the reference
 
 private:

@@ -1,6 +1,7 @@
 // weights.cpp — see weights.h.
 #include "weights.h"
 
+#include <cmath>
 #include <cstring>
 
 namespace bert_hip {
@@ -98,6 +99,23 @@ std::vector<float> tensor_as_f32(const HostTensor &t) {
     else
         for (size_t i = 0; i < n; ++i) { _Float16 h; memcpy(&h, t.data + 2 * i, 2); v[i] = (float)h; }
     return v;
+}
+
+int rel_bias_bucket(int d) {
+    static const int thr[8] = {8, 12, 16, 23, 32, 46, 64, 91};
+    const int m = d < 0 ? -d : d, base = d > 0 ? REL_BUCKETS / 2 : 0;
+    if (m < 8) return base + m;
+    int t = 0;
+    while (t + 1 < 8 && thr[t + 1] <= m) ++t;
+    return base + 8 + t;
+}
+
+std::vector<float> rel_bias_table(const float *W, int n_head, int P, double scale) {
+    const int L = 2 * P - 1;
+    std::vector<float> rel((size_t)n_head * L);
+    for (int h = 0; h < n_head; ++h)
+        for (int d = -(P - 1); d <= P - 1; ++d) rel[(size_t)h * L + d + P - 1] = (float)((double)W[(size_t)rel_bias_bucket(d) * n_head + h] * scale);
+    return rel;
 }
 
 std::vector<_Float16> pack_f16_image(const StackedRows &s, int64_t n_rows) {
@@ -379,6 +397,15 @@ std::unique_ptr<ModelWeights> ModelWeights::load(const ModelFile &mf, const Load
             w->vocab16 = w->vocab16_own.as<half_t>();
         }
         w->mlm_head = ok;
+    }
+    // the relative position bias (ModelFile::load: [REL_BUCKETS][n_head], f32 or f16)
+    if (ok && mf.rel_bias) {
+        const HostTensor *rb = mf.find(REL_BIAS_NAME);
+        if (!rb) { err = "the relative position bias is missing"; return nullptr; }
+        const std::vector<float> W = tensor_as_f32(*rb);
+        ok = w->rel.upload(rel_bias_table(W.data(), hp.n_head, hp.n_max_tokens, 1.0), err) &&
+             w->rel_scaled.upload(rel_bias_table(W.data(), hp.n_head, hp.n_max_tokens, std::sqrt((double)(H / hp.n_head))), err);
+        w->rel_bias = ok;
     }
     if (!ok) return nullptr;
     return w;

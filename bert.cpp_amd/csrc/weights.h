@@ -85,6 +85,13 @@ std::vector<uint32_t> pack_gamma_beta_bias(const float *gamma, const float *beta
 std::vector<float> table_as_f32(const HostTensor &t);
 // any file tensor as f32 values [ne1][ne0]: f32 as stored, f16 widened, q4 as table_as_f32
 std::vector<float> tensor_as_f32(const HostTensor &t);
+// MPNet's relative position bucket of the distance d = key - query (MPNetEncoder.relative_position_bucket with 32 buckets and
+// max_distance 128, in integers): keys behind the query take buckets 16 .. 31, distances below 8 a bucket each, the larger ones the
+// log-spaced ranges that start at 8, 12, 16, 23, 32, 46, 64 and 91
+int rel_bias_bucket(int d);
+// the bias of every distance a sentence of up to P tokens can hold: W [REL_BUCKETS][n_head] f32 -> rel [n_head][2 P - 1] with
+// rel[h][d + P - 1] = W[rel_bias_bucket(d)][h] * scale, the product rounded once to f32 (scale 1: W's own values)
+std::vector<float> rel_bias_table(const float *W, int n_head, int P, double scale);
 
 // ------------------------------------------------------------------------------------------------
 // images on the device
@@ -151,6 +158,11 @@ struct ModelWeights {
     GemmWeightStore mlm_wt;
     DevBuf mlm_bt, mlm_ln_w, mlm_ln_b, mlm_bias, vocab16_own;
     const half_t *vocab16 = nullptr;
+    // The relative position bias of the file, if it has one (model_file.h; attention.hip, f32_route.hip): rel_bias_table for
+    // P = n_max_tokens, as the kernels that scale a score themselves add it (rel) and times sqrt(d_head) for the matrix-core kernel,
+    // which scales the sum (rel_scaled).  One table for all layers.
+    bool rel_bias = false;
+    DevBuf rel, rel_scaled;
     // uploads to the current device
     static std::unique_ptr<ModelWeights> load(const ModelFile &mf, const LoadOptions &opt, std::string &err);
 };

@@ -183,6 +183,12 @@ MLM_HEAD_NAMES = ["cls.predictions.transform.dense.weight", "cls.predictions.tra
                   "cls.predictions.transform.LayerNorm.weight", "cls.predictions.transform.LayerNorm.bias", "cls.predictions.bias"]
 
 
+# The optional relative position bias of MPNet (HuggingFace's encoder.relative_attention_bias.weight, [REL_BUCKETS][n_head]), written
+# behind the encoder's tensors and the heads.  One table for all layers; never quantised: f32, or f16 in an f16 file.
+REL_BIAS_NAME = "encoder.relative_attention_bias.weight"
+REL_BUCKETS = 32
+
+
 # how far below zero, in standard deviations of a logit, synthetic_weights draws cls.predictions.bias
 MLM_BIAS_SIGMAS = 1.1
 
@@ -212,7 +218,8 @@ def tensor_shape(name: str, hp: BertHParams) -> Tuple[int, ...]:
     return (H,)
 
 
-def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive", n_labels: int = 0, mlm_head: bool = False) -> Dict[str, np.ndarray]:
+def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive", n_labels: int = 0, mlm_head: bool = False,
+                      rel_bias: bool = False) -> Dict[str, np.ndarray]:
     """Seeded random f32 weights of the BERT architecture.
 
     n_labels > 0 adds a classification head (HEAD_NAMES), drawn after everything else: a seed gives the same encoder with and without it.
@@ -220,6 +227,8 @@ def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive", 
     classification head with and without it.  Its cls.predictions.bias is negative, about MLM_BIAS_SIGMAS standard deviations of a
     logit (|t| |E[v]| / sqrt(H) with |t| = sqrt(H) behind the LayerNorm), so that a sentence's max over its tokens is positive for
     some vocabulary entries and not for others: the sparse vectors are sparse.
+    rel_bias adds MPNet's relative position bias (REL_BIAS_NAME), drawn after everything else: a seed gives the same encoder and heads
+    with and without it.  N(0, 2^2) under "sensitive" (one wrong bucket moves a softmax far), N(0, 0.02^2) under "hf".
 
     style="sensitive": fan-in scaled matrices with O(1) activations, spread-out attention scores,
     non-trivial biases and LayerNorm affine terms, so that a wrong softmax / bias / LN path moves
@@ -267,14 +276,19 @@ def synthetic_weights(hp: BertHParams, seed: int = 0, style: str = "sensitive", 
             else:
                 a = rng.normal(1.0 if name.endswith("LayerNorm.weight") else 0.0, 0.1, shp)
             out[name] = a.astype(np.float32)
+    if rel_bias:
+        out[REL_BIAS_NAME] = rng.normal(0.0, 0.02 if style == "hf" else 2.0, (REL_BUCKETS, hp.n_head)).astype(np.float32)
     return out
 
 
-def synthetic_vocab(n_vocab: int) -> List[bytes]:
-    """A vocab whose strings do not matter for eval tests; ids 101/102 keep their BERT meaning."""
+def synthetic_vocab(n_vocab: int, mpnet: bool = False) -> List[bytes]:
+    """A vocab whose strings do not matter for eval tests; ids 101/102 keep their BERT meaning.  mpnet: ids 0 .. 3 are MPNet's
+    <s>, <pad>, </s>, <unk> (a file with the relative position bias does not load without <s> and </s>)."""
     v = [f"[unused{i}]".encode() for i in range(n_vocab)]
     if n_vocab > 103:
         v[0], v[100], v[101], v[102], v[103] = b"[PAD]", b"[UNK]", b"[CLS]", b"[SEP]", b"[MASK]"
+    if mpnet:
+        v[0], v[1], v[2], v[3] = b"<s>", b"<pad>", b"</s>", b"<unk>"
     return v
 
 
@@ -295,13 +309,14 @@ def _encode_2d(a: np.ndarray, ftype: int) -> bytes:
 
 def write_model(path: str, hp: BertHParams, weights: Dict[str, np.ndarray], ftype: int,
                 vocab: Optional[Sequence[bytes]] = None, from_f16: bool = True, legacy_q4: bool = False) -> None:
-    """Write a bert.cpp model file.  2-D tensors named '*weight' take `ftype`; 1-D stay f32.
+    """Write a bert.cpp model file.  2-D tensors named '*weight' take `ftype`; 1-D stay f32.  The relative position bias
+    (REL_BIAS_NAME, if `weights` holds it) is never quantised: it stays f32 in q4 files, as the biases do.
 
     For q4 types the source is first rounded through f16 when `from_f16` (the reference pipeline
     is HF -> f16 file -> quantize tool, models/run_conversions.sh + quantize.cpp:175-181).
     """
     if vocab is None:
-        vocab = synthetic_vocab(hp.n_vocab)
+        vocab = synthetic_vocab(hp.n_vocab, mpnet=REL_BIAS_NAME in weights)
     assert len(vocab) == hp.n_vocab
     with open(path, "wb") as f:
         f.write(struct.pack("<I", MAGIC))
@@ -321,12 +336,17 @@ def write_model(path: str, hp: BertHParams, weights: Dict[str, np.ndarray], ftyp
         if mlm:
             assert mlm == MLM_HEAD_NAMES, f"partial MLM head: {mlm}"
             names = names + MLM_HEAD_NAMES
+        if REL_BIAS_NAME in weights:
+            names = names + [REL_BIAS_NAME]
         for name in names:
             a = np.asarray(weights[name], dtype=np.float32)
             want = head_shapes(hp, n_labels)[name] if name in HEAD_NAMES else mlm_head_shapes(hp)[name] if name in MLM_HEAD_NAMES else tensor_shape(name, hp)
-            assert a.shape == want, (name, a.shape)
+            # (the table's shape is the reader's to judge: a file with another one can be written, and is refused at load)
+            assert a.shape == want or (name == REL_BIAS_NAME and a.ndim == 2), (name, a.shape)
             two_d = a.ndim == 2
             t = ftype if two_d else FTYPE_F32
+            if name == REL_BIAS_NAME and t in (FTYPE_Q4_0, FTYPE_Q4_1):
+                t = FTYPE_F32
             nm = name.encode()
             f.write(struct.pack("<3i", a.ndim, len(nm), t))
             for i in range(a.ndim):
@@ -389,10 +409,10 @@ def read_model(path: str) -> ModelFile:
 
 
 def make_synthetic_model(path: str, dims: str | BertHParams, ftype: str | int, seed: int = 0,
-                         style: str = "sensitive", n_labels: int = 0, mlm_head: bool = False) -> BertHParams:
+                         style: str = "sensitive", n_labels: int = 0, mlm_head: bool = False, rel_bias: bool = False) -> BertHParams:
     hp = MODEL_DIMS[dims] if isinstance(dims, str) else dims
     ft = FTYPE_BY_NAME[ftype] if isinstance(ftype, str) else ftype
-    write_model(path, hp, synthetic_weights(hp, seed, style, n_labels, mlm_head), ft)
+    write_model(path, hp, synthetic_weights(hp, seed, style, n_labels, mlm_head, rel_bias), ft)
     return hp
 
 
@@ -413,6 +433,43 @@ def hf_mlm_weights(state_dict, n_layer: int) -> Dict[str, np.ndarray]:
         return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
     sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in state_dict.items()}
     return {n: arr(sd[n]) for n in tensor_names(n_layer) + MLM_HEAD_NAMES}
+
+
+# HuggingFace MPNet's per-layer names -> this format's (BERT's)
+_MPNET_LAYER_NAMES = {
+    "attention.attn.q": "attention.self.query", "attention.attn.k": "attention.self.key", "attention.attn.v": "attention.self.value",
+    "attention.attn.o": "attention.output.dense", "attention.LayerNorm": "attention.output.LayerNorm",
+    "intermediate.dense": "intermediate.dense", "output.dense": "output.dense", "output.LayerNorm": "output.LayerNorm",
+}
+
+
+def hf_mpnet_weights(state_dict, n_layer: int) -> Dict[str, np.ndarray]:
+    """The tensors of a HuggingFace MPNetModel state dict (sentence-transformers/all-mpnet-base-v2 is one; a leading 'mpnet.' or '0.auto_model.' is
+    stripped) under this format's names: attention.attn.{q,k,v,o} become BERT's query / key / value / output.dense; the position table
+    loses its rows 0 and 1 (MPNet's positions start at padding_idx + 1 = 2), so the file's n_max_tokens is max_position_embeddings - 2;
+    MPNet has no token types: a zero [2][H] table; and the relative position bias.  The pooler, if the checkpoint has one, is dropped.
+    Values may be torch tensors or arrays."""
+    def arr(v):
+        return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+    sd = {}
+    for k, v in state_dict.items():
+        for prefix in ("0.auto_model.", "mpnet."):
+            if k.startswith(prefix):
+                k = k[len(prefix):]
+        sd[k] = v
+    out = {
+        "embeddings.word_embeddings.weight": arr(sd["embeddings.word_embeddings.weight"]),
+        "embeddings.position_embeddings.weight": arr(sd["embeddings.position_embeddings.weight"])[2:].copy(),
+        "embeddings.LayerNorm.weight": arr(sd["embeddings.LayerNorm.weight"]),
+        "embeddings.LayerNorm.bias": arr(sd["embeddings.LayerNorm.bias"]),
+        REL_BIAS_NAME: arr(sd[REL_BIAS_NAME]),
+    }
+    out["embeddings.token_type_embeddings.weight"] = np.zeros((2, out["embeddings.word_embeddings.weight"].shape[1]), dtype=np.float32)
+    for i in range(n_layer):
+        for theirs, ours in _MPNET_LAYER_NAMES.items():
+            for part in ("weight", "bias"):
+                out[f"encoder.layer.{i}.{ours}.{part}"] = arr(sd[f"encoder.layer.{i}.{theirs}.{part}"])
+    return out
 
 
 def synthetic_token_ids(n_sentences: int, seq_len: int, n_vocab: int, seed: int) -> np.ndarray:

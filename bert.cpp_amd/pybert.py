@@ -56,6 +56,7 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_late_index_remove", "bert_hip_late_index_n_live", "bert_hip_late_index_n_live_tokens", "bert_hip_late_index_search_filtered",
     "bert_hip_late_index_search_filtered_device", "bert_hip_late_index_compact", "bert_hip_late_index_save", "bert_hip_late_index_load",
     "bert_hip_late_index_create", "bert_hip_late_index_dtype", "bert_hip_late_index_get_codes",
+    "bert_hip_relative_attention",
 ]
 # include/bert_hip_test.h: the op-level test hooks, exported by libbert_test.so only
 BERT_HIP_TEST_H_SYMBOLS = [
@@ -73,6 +74,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_sparse_index_header", "bert_hip_test_sparse_index_body",
     "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan", "bert_hip_test_hybrid_chunk", "bert_hip_test_token_index_plan",
     "bert_hip_test_late_index_header", "bert_hip_test_late_index_body",
+    "bert_hip_test_attention_bias", "bert_hip_test_f32_attention_bias", "bert_hip_test_rel_bias_table",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -181,6 +183,7 @@ def _declare_product_abi(L):
     L.bert_hip_maxsim_device.restype = i32; L.bert_hip_maxsim_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
     L.bert_hip_maxsim.restype = i32; L.bert_hip_maxsim.argtypes = [vp, f32p, i32p, i32, f32p, i32p, i32, i32, i32p, i32, i32, f32p]
     L.bert_hip_n_labels.restype = i32; L.bert_hip_n_labels.argtypes = [vp]
+    L.bert_hip_relative_attention.restype = i32; L.bert_hip_relative_attention.argtypes = [vp]
     L.bert_hip_tokenize_pair.restype = i32; L.bert_hip_tokenize_pair.argtypes = [vp, C.c_char_p, C.c_char_p, i32p, i32p, i32p, i32]
     L.bert_hip_eval_packed_typed.restype = i32; L.bert_hip_eval_packed_typed.argtypes = [vp, i32p, i32p, i32p, i32, f32p]
     L.bert_hip_eval_packed_typed_device.restype = i32; L.bert_hip_eval_packed_typed_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
@@ -290,6 +293,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_gemm_lnfold.argtypes = [i32, i32, i32, i32] + [vp] * 10 + [i32, vp, vp, vp]
     L.bert_hip_test_attention.restype = i32
     L.bert_hip_test_attention.argtypes = [i32, i32p, i32, i32, vp, i32, vp]
+    L.bert_hip_test_attention_bias.restype = i32
+    L.bert_hip_test_attention_bias.argtypes = [i32, i32p, i32, i32, vp, i32, vp, vp, i32, vp]
+    L.bert_hip_test_rel_bias_table.restype = i32
+    L.bert_hip_test_rel_bias_table.argtypes = [vp, i32, i32, vp]
     L.bert_hip_test_qkv_attention.restype = i32
     L.bert_hip_test_qkv_attention.argtypes = [i32, i32p, i32, i32, vp, vp, i32, vp, i32, vp]
     L.bert_hip_test_layer_tail.restype = i32
@@ -312,6 +319,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_f32_gemm.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp]
     L.bert_hip_test_f32_attention.restype = i32
     L.bert_hip_test_f32_attention.argtypes = [i32, i32p, i32, i32, i32, vp, vp]
+    L.bert_hip_test_f32_attention_bias.restype = i32
+    L.bert_hip_test_f32_attention_bias.argtypes = [i32, i32p, i32, i32, i32, vp, vp, vp, i32]
     L.bert_hip_test_f32_layernorm.restype = i32
     L.bert_hip_test_f32_layernorm.argtypes = [i32, i32, vp, vp, vp, vp]
     L.bert_hip_test_f32_embed_ln.restype = i32
@@ -867,6 +876,11 @@ class BertModel:
 
     def n_devices(self) -> int:
         return self.lib.bert_hip_n_devices(self.ctx)
+
+    @property
+    def relative_attention(self) -> bool:
+        """The model file holds MPNet's relative position bias (encoder.relative_attention_bias.weight); tokenizer-only contexts too."""
+        return self.lib.bert_hip_relative_attention(self.ctx) == 1
 
     # ---- sentence pairs and scores --------------------------------------------------------
     @property
@@ -2054,6 +2068,38 @@ def test_attention(qkv: np.ndarray, cu_seqlens: np.ndarray, n_head: int, d_head:
     return out
 
 
+def test_attention_bias(qkv: np.ndarray, cu_seqlens: np.ndarray, n_head: int, d_head: int, impl: int, W: Optional[np.ndarray], P: int,
+                        rel: Optional[np.ndarray] = None) -> np.ndarray:
+    """test_attention with MPNet's relative position bias W [32][n_head] f32, expanded for sentences of up to P tokens; rel, if given,
+    is a table [n_head][2 P - 1] f32 taken as it is in place of the expansion (impl 0 wants it times sqrt(d_head))."""
+    L = test_lib()
+    qkv = np.ascontiguousarray(qkv, dtype=np.float16)
+    cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    out = np.zeros((qkv.shape[0], n_head * d_head), dtype=np.float16)
+    if W is not None:
+        W = np.ascontiguousarray(W, dtype=np.float32)
+        assert W.shape == (32, n_head)
+    if rel is not None:
+        rel = np.ascontiguousarray(rel, dtype=np.float32)
+        assert rel.shape == (n_head, 2 * P - 1)
+    r = L.bert_hip_test_attention_bias(len(cu) - 1, _i32p(cu), n_head, d_head, qkv.ctypes.data, impl, out.ctypes.data,
+                                       W.ctypes.data if W is not None else None, P, rel.ctypes.data if rel is not None else None)
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_attention_bias failed: {r}")
+    return out
+
+
+def test_rel_bias_table(W: np.ndarray, P: int) -> np.ndarray:
+    """The host expansion of W [32][n_head] f32: rel [n_head][2 P - 1], rel[h][d + P - 1] = W[bucket(d)][h] (no device)."""
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    assert W.ndim == 2 and W.shape[0] == 32
+    out = np.zeros((W.shape[1], 2 * P - 1), dtype=np.float32)
+    r = test_lib().bert_hip_test_rel_bias_table(W.ctypes.data, W.shape[1], P, out.ctypes.data)
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_rel_bias_table failed: {r}")
+    return out
+
+
 def test_qkv_attention(x: np.ndarray, cu_seqlens: np.ndarray, n_head: int, d_head: int, W_bytes: np.ndarray, wtype: int,
                        bias: np.ndarray, fused: bool) -> np.ndarray:
     """x [T][H] f16, Wqkv [3H][H] in file layout of wtype, bias [3H] -> attention context [T][H] f16."""
@@ -2158,6 +2204,17 @@ def test_f32_attention(qkv: np.ndarray, cu_seqlens, n_head: int, d_head: int, ma
     rc = test_lib().bert_hip_test_f32_attention(len(cu) - 1, _i32p(cu), n_head, d_head, max_len, qkv.ctypes.data, out.ctypes.data)
     if rc != 0:
         raise RuntimeError(f"bert_hip_test_f32_attention failed: {rc}")
+    return out
+
+
+def test_f32_attention_bias(qkv: np.ndarray, cu_seqlens, n_head: int, d_head: int, max_len: int, W: np.ndarray, P: int) -> np.ndarray:
+    """test_f32_attention with MPNet's relative position bias W [32][n_head] f32, expanded for sentences of up to P tokens."""
+    qkv = _f32c(qkv); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32); W = _f32c(W)
+    assert qkv.shape == (int(cu[-1]), 3 * n_head * d_head) and W.shape == (32, n_head)
+    out = np.zeros((qkv.shape[0], n_head * d_head), dtype=np.float32)
+    rc = test_lib().bert_hip_test_f32_attention_bias(len(cu) - 1, _i32p(cu), n_head, d_head, max_len, qkv.ctypes.data, out.ctypes.data, W.ctypes.data, P)
+    if rc != 0:
+        raise RuntimeError(f"bert_hip_test_f32_attention_bias failed: {rc}")
     return out
 
 

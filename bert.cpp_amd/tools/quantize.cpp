@@ -169,7 +169,8 @@ bool quantize_model(const char *in_path, const char *out_path, int32_t itype) {
         if (ttype < 0 || ttype > 3) { fprintf(stderr, "bert-quantize: tensor '%s' has unknown type %d\n", name.c_str(), ttype); return false; }
         printf("%48s - [%5d, %5d], type = %6s ", name.c_str(), ne[0], ne[1], type_names[ttype]);
 
-        const bool quantize = n_dims == 2 && ends_with(name, "weight");
+        // (MPNet's relative position bias, [32][n_head], is a 2-D "*weight" the engine never takes quantised: copied as it is)
+        const bool quantize = n_dims == 2 && ends_with(name, "weight") && name != "encoder.relative_attention_bias.weight";
         size_t src_bytes;
         if (ttype == 0) src_bytes = (size_t)n_elem * 4;
         else if (ttype == 1) src_bytes = (size_t)n_elem * 2;

@@ -368,6 +368,19 @@ BERT_API int32_t bert_hip_maxsim(struct bert_ctx *ctx, const float *q, const int
  *                  packed and scored: scores [n_pairs][n_labels].  Returns the number of pairs scored (bert_hip_encode_batch's
  *                  conventions: it stops at the first failure, later outputs untouched), -1 without a device, -2 without a head.   */
 BERT_API int32_t bert_hip_n_labels(struct bert_ctx *ctx);
+/* RELATIVE POSITION BIAS (MPNet: sentence-transformers/all-mpnet-base-v2, multi-qa-mpnet-base-*).  One optional tensor behind the
+ * encoder's set, encoder.relative_attention_bias.weight [n_head, 32] (ne0 = n_head: HuggingFace's [32][n_head]), f32 or f16 and never
+ * quantised; it may stand beside either head.  With it every attention score of every layer is
+ *     <q_i, k_j> / sqrt(d_head) + W[bucket(j - i)][head],
+ * bucket as MPNetEncoder.relative_position_bucket with 32 buckets and max_distance 128.  Any other bucket count fails the load.  Such a
+ * model runs the layered, the LayerNorm-folding or the f32 route (the add lives in the attention launch; the fused projection +
+ * attention kernel, the one-launch kernel and the latency route are not taken); everything behind the encoder serves it unchanged.
+ * Its texts are wrapped in the ids of <s> and </s> of the file's vocabulary instead of 101 / 102 (a load error if either is absent;
+ * a file without the tensor keeps 101 / 102 whatever its vocabulary holds), and bert_hip_score_pairs refuses it with -2: MPNet lays a
+ * pair out differently; the packed and typed entry points take ids as given.  ggml_file.hf_mpnet_weights converts a checkpoint:
+ * position rows from 2 on, a zero token-type table.
+ *   relative_attention  1 if the context's model file has the tensor (tokenizer-only contexts included), 0 if not, -1 without a context. */
+BERT_API int32_t bert_hip_relative_attention(struct bert_ctx *ctx);
 BERT_API int32_t bert_hip_tokenize_pair(struct bert_ctx *ctx, const char *text_a, const char *text_b, bert_vocab_id *tokens, int32_t *n_tokens,
                                         int32_t *first_len, int32_t n_max_tokens);
 BERT_API int32_t bert_hip_eval_packed_typed(struct bert_ctx *ctx, const bert_vocab_id *tokens, const int32_t *cu_seqlens, const int32_t *first_len,

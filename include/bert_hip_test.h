@@ -49,6 +49,15 @@ BERT_API int32_t bert_hip_test_gemm_lnfold(int32_t M, int32_t K1, int32_t H, int
 /* qkv[T][3H] f16 bits (Q | K | V per row), packed sentences -> ctx[T][H] f16 bits.             */
 BERT_API int32_t bert_hip_test_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head,
                                          int32_t d_head, const uint16_t *qkv, int32_t impl, uint16_t *out);
+/* The same with MPNet's relative position bias: W [32][n_head] f32 (HuggingFace's encoder.relative_attention_bias.weight), expanded for
+ * sentences of up to P tokens as the engine expands it at load (bert_hip_test_rel_bias_table; times sqrt(d_head) for impl 0, whose kernel
+ * scales the sum).  impl 0 = the matrix-core kernel, 1 = the naive one.  rel, if not NULL, is a table [n_head][2 P - 1] f32 taken AS IT
+ * IS in place of W's expansion (W may then be NULL): what a test poisons outside a sentence's window.  -1 for a sentence longer than P. */
+BERT_API int32_t bert_hip_test_attention_bias(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head,
+                                              const uint16_t *qkv, int32_t impl, uint16_t *out, const float *W, int32_t P, const float *rel);
+/* The host expansion alone (weights.h rel_bias_table, no device): out [n_head][2 P - 1], out[h][d + P - 1] = W[bucket(d)][h].  0, or -1
+ * for a NULL pointer, n_head < 1 or P < 1.                                                                                          */
+BERT_API int32_t bert_hip_test_rel_bias_table(const float *W, int32_t n_head, int32_t P, float *out);
 
 /* Q|K|V projection + attention: x[T][H] f16 bits, Wqkv [3H][H] (Q rows, K rows, V rows) in file layout of `wtype`,
  * bias[3H] -> ctx[T][H] f16 bits (reference bert.cpp:822-856).  fused: 0 = GEMM kernel + attention kernel; the window kernel
@@ -143,6 +152,9 @@ BERT_API int32_t bert_hip_test_f32_gemm(int32_t M, int32_t N, int32_t K, const f
  * max_len needs more dynamic LDS than the device gives a workgroup.                                                              */
 BERT_API int32_t bert_hip_test_f32_attention(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head,
                                              int32_t max_len, const float *qkv, float *out);
+/* The same with MPNet's relative position bias, W [32][n_head] f32 expanded for sentences of up to P tokens (P >= max_len, -1 otherwise). */
+BERT_API int32_t bert_hip_test_f32_attention_bias(int32_t n_sentences, const int32_t *cu_seqlens, int32_t n_head, int32_t d_head,
+                                                  int32_t max_len, const float *qkv, float *out, const float *W, int32_t P);
 /* out [T][H] = LayerNorm(x [T][H]) gamma + beta, two-pass statistics, eps 1e-5.                                                  */
 BERT_API int32_t bert_hip_test_f32_layernorm(int32_t T, int32_t H, const float *x, const float *gamma, const float *beta, float *out);
 /* Embedding gather-sum + LayerNorm on f32 tables: word [n_vocab][H], type [2][H] (row 0 is used), pos [n_pos][H]; out [T][H].
