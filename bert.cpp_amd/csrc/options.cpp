@@ -44,6 +44,7 @@ void EngineOptions::apply(const std::string &key, const std::string &value) {
     else if (key == "f32") f32_exact = value != "f16";        // f32 files: "exact" (f32 arithmetic, default) | "f16" (f16 operands, fused kernels)
     else if (key == "chunk_tokens") { if (n > 0) chunk_tokens = n; }
     else if (key == "sparse_index_qb") sparse_index_qb = n >= 1 && n <= 8 ? n : 0;
+    else if (key == "sparse_index_segment_rows") sparse_index_segment_rows = n >= 256 && n <= 16384 && n % 256 == 0 ? n : 0;
     else if (key == "hybrid_chunk_queries") hybrid_chunk_queries = n >= 1 && n <= 4096 ? n : 0;
     else if (key == "token_index_slices") token_index_slices = n >= 1 && n <= 4096 ? n : 0;
     else if (key == "maxsim_launch_pairs") maxsim_launch_pairs = n >= 1 ? (n < MAXSIM_LAUNCH_PAIRS ? n : MAXSIM_LAUNCH_PAIRS) : 0;
@@ -55,7 +56,7 @@ void EngineOptions::apply(const std::string &key, const std::string &value) {
 //   BERT_HIP_LATENCY  the keys "latency" and "latency_tokens" in one: 0 = no latency route; 1 = the default cap; n >= 32: calls of
 //                     at most n tokens take it
 //   BERT_HIP_Q4       no key: decides how the weights are packed
-// "qkv2", "gemm256", "tail", "stage_kernel", "one_launch", "sparse_index_qb", "hybrid_chunk_queries", "token_index_slices", "maxsim_launch_pairs" (and the profiler's "profile_replay") are keys only.
+// "qkv2", "gemm256", "tail", "stage_kernel", "one_launch", "sparse_index_qb", "sparse_index_segment_rows", "hybrid_chunk_queries", "token_index_slices", "maxsim_launch_pairs" (and the profiler's "profile_replay") are keys only.
 EngineOptions EngineOptions::from_env(const HParams &hp) {
     EngineOptions o;
     // (the cap of the latency route: measured on H = 384; a window of an H = 128 model costs the fused kernels less than five

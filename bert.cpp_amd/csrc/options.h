@@ -24,6 +24,7 @@ struct EngineOptions {
     // from 220 us: 252 us at 172 tokens (8 sentences), 330 at 363 (16), 376 at 512, 527 at 716, 606 at 1024 (round 5, same bits).
     int latency_tokens = 768;
     int sparse_index_qb = 0;          // tuning (a key only): queries per tile of the sparse index's scan, 1 .. 8; 0 = the table of sparse_index_kernels.h
+    int sparse_index_segment_rows = 0; // tuning (a key only): rows per segment of the sparse index's postings, 256 .. 16384 in multiples of 256, read by invert; 0 = the default of sparse_index_kernels.h
     int hybrid_chunk_queries = 0;     // tuning (a key only): queries per chunk of a hybrid search, 1 .. 4096; 0 = what the score workspace's bound gives (sparse_index_kernels.h)
     int token_index_slices = 0;       // tuning (a key only): slices of documents of a token index's scan, 1 .. 4096; 0 = planned (token_index_kernels.h)
     int maxsim_launch_pairs = 0;      // tuning (a key only): pairs per launch of MaxSim's kernel, 1 .. 2^23 (a larger value is clamped to that bound); 0 = the bound (kernels.h)

@@ -1,6 +1,7 @@
 // sparse_index.cpp — the host side of the sparse index (sparse_index.h): storage and its growth, add, the search and its chunks,
 // rescoring, reading rows back, the checks of the host forms, the live bits, compaction and the file form.  Every kernel is in sparse_index.hip (and the merge in search.hip) and reached
-// through sparse_index_kernels.h / search_kernels.h.
+// through sparse_index_kernels.h / search_kernels.h.  The postings and the launches of the inverted search are sparse_postings.cpp; the
+// searches here take `inverted` and share their checks, chunking and copies with it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -163,11 +164,14 @@ int SparseIndex::reserve(int n_rows, int n_queries, int k, std::string &err) {
     DeviceGuard g(eng_->device());
     if (!grow_rows(n_rows, err)) return -3;
     const int nqc = std::min(n_queries, QCHUNK);
+    res_nq_ = nqc; res_k_ = k;
     if (nqc == 0) return 0;
     // (the entries grow with k — the list length, and so the tile, changes at k = 128, the slices only fall with it)
     size_t ent = 0;
     for (int kk : {std::min(k, 128), k}) ent = std::max(ent, ws_entries_bound(dtype_, n_vocab_, std::max(n_rows, n_), nqc, kk, eng_->options().sparse_index_qb));
     if (!grow(ws_s_, ent * 4, err) || !grow(ws_i_, ent * 4, err) || !grow(images_, (size_t)nqc * sparse_image_bytes(n_vocab_), err)) return -3;
+    // (an index with postings: the inverted plan's workspace over the rows they cover)
+    if (inverted_ && !grow_inverted(inv_rows_, nqc, k, err)) return -3;
     return 0;
 }
 
@@ -248,26 +252,29 @@ void SparseIndex::enqueue_chunk(int nq, int kq, const int32_t *d_qids, const flo
 }
 
 int SparseIndex::search_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
-                               std::string &err, const uint32_t *d_allow) {
+                               std::string &err, const uint32_t *d_allow, bool inverted) {
     if (const int go = check_search(nq, kq, d_qids, d_qw, k, d_ids, d_scores, err); go <= 0) return go;
+    if (inverted && !inverted_ok(err)) return -2;
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
-    if (!grow_search(n_, std::min(nq, QCHUNK), k, err)) return -3;
+    if (!(inverted ? grow_inverted(n_, std::min(nq, QCHUNK), k, err) : grow_search(n_, std::min(nq, QCHUNK), k, err))) return -3;
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
-        enqueue_chunk(c, kq, d_qids + (size_t)c0 * kq, d_qw + (size_t)c0 * kq, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s, d_allow);
+        if (inverted) enqueue_chunk_inverted(c, kq, d_qids + (size_t)c0 * kq, d_qw + (size_t)c0 * kq, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s, d_allow);
+        else enqueue_chunk(c, kq, d_qids + (size_t)c0 * kq, d_qw + (size_t)c0 * kq, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s, d_allow);
     }
     HIP_OK(hipGetLastError(), err, -3);
     return eng_->op_end(op, err) ? 0 : -3;
 }
 
 int SparseIndex::search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err,
-                                       const uint32_t *d_allow) {
+                                       const uint32_t *d_allow, bool inverted) {
+    if (inverted && !inverted_ok(err)) return -2;
     std::vector<int32_t> hid((size_t)nq * k);
     std::vector<float> hsc((size_t)nq * k);
     if (!grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
-    if (search_device(nq, kq, d_qids, d_qw, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow) != 0) { (void)hipStreamSynchronize(stream_); return -3; }
+    if (search_device(nq, kq, d_qids, d_qw, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow, inverted) != 0) { (void)hipStreamSynchronize(stream_); return -3; }
     HIP_OK(hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
     HIP_OK(hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
     HIP_OK(hipStreamSynchronize(stream_), err, -3);
@@ -277,9 +284,10 @@ int SparseIndex::search_device_to_host(int nq, int kq, const int32_t *d_qids, co
 }
 
 int SparseIndex::search_host(int nq, int kq, const int32_t *qids, const float *qw, int k, int32_t *ids, float *scores, std::string &err,
-                             const uint32_t *allow) {
+                             const uint32_t *allow, bool inverted) {
     if (const int go = check_search(nq, kq, qids, qw, k, ids, scores, err); go <= 0) return go;
     if (!check_terms("search: query", nq, kq, qids, qw, n_vocab_, false, err)) return -2;
+    if (inverted && !inverted_ok(err)) return -2;
     DeviceGuard g(eng_->device());
     const uint32_t *d_allow = nullptr;
     if (!upload_allow(allow, d_allow, err)) return -3;
@@ -293,7 +301,7 @@ int SparseIndex::search_host(int nq, int kq, const int32_t *qids, const float *q
         HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
         HIP_OK(hipMemcpyAsync(d, qids + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
         HIP_OK(hipMemcpyAsync(d + half, qw + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
-        if (search_device_to_host(c, kq, (const int32_t *)d, (const float *)(d + half), k, hid.data() + (size_t)c0 * k, hsc.data() + (size_t)c0 * k, err, d_allow) != 0) return -3;
+        if (search_device_to_host(c, kq, (const int32_t *)d, (const float *)(d + half), k, hid.data() + (size_t)c0 * k, hsc.data() + (size_t)c0 * k, err, d_allow, inverted) != 0) return -3;
     }
     memcpy(ids, hid.data(), hid.size() * 4);
     memcpy(scores, hsc.data(), hsc.size() * 4);
@@ -408,6 +416,7 @@ int SparseIndex::get_rows(int n, const int32_t *row_ids, int32_t *out_ids, float
 // ------------------------------------------------------------------------------------------------
 void SparseIndex::truncate(int n) {
     if (n < 0 || n >= n_) return;
+    if (inverted_ && n < inv_rows_) drop_postings();
     // (the mirror keeps its bits at and beyond size zero; the device words of the dropped rows stay as they are: a search ignores
     // them, and the add that reuses those rows sets them)
     if (live_) {
@@ -485,6 +494,7 @@ int SparseIndex::remove(int n, const int32_t *ids, std::string &err) {
 int SparseIndex::compact(int32_t *old_ids, std::string &err) {
     DeviceGuard g(eng_->device());
     HIP_OK(hipEventSynchronize(busy_), err, -3);
+    drop_postings();                                         // (the ids change: invert again)
     if (n_removed_ == 0) {
         if (old_ids) for (int i = 0; i < n_; ++i) old_ids[i] = i;
         drop_live();

@@ -7,6 +7,8 @@
 // index's topk_merge_kernel.  Shaped like Index (search.h): grow-only storage and workspace, one event, a stream for the host routes.
 // Removed rows are a device bitmap with a host mirror, there from the first remove to the next compact; while it exists, or under an
 // allow-list, a search launches the masked scan.  rescore scores per-query candidate rows (sparse_index_rescore_kernel).
+// Postings (sparse_postings.cpp, kernels in sparse_postings.hip): invert builds a term-major image of the rows, and the searches'
+// `inverted` form answers from it with the row-major search's ids and score bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -46,12 +48,14 @@ public:
     int add_host(int n, int k_in, const int32_t *ids, const float *weights, std::string &err);
     // ids / scores [nq][k], best first; queries ids / weights [nq][kq] in device memory, unchecked.  Asynchronous on s
     // d_allow: null, or device words [ceil(size / 32)], bit set = the row may be returned
+    // inverted: answer from the postings (sparse_postings_scan_kernel) — the same ids and score bits; -2 where the postings do not
+    // cover the rows (no invert yet, or rows added since)
     int search_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s, std::string &err,
-                      const uint32_t *d_allow = nullptr);
+                      const uint32_t *d_allow = nullptr, bool inverted = false);
     // host queries, checked as add_host's rows (weights finite as f32), and host results (written only on success); blocking.  allow:
     // null, or host words as d_allow
     int search_host(int nq, int kq, const int32_t *qids, const float *qw, int k, int32_t *ids, float *scores, std::string &err,
-                    const uint32_t *allow = nullptr);
+                    const uint32_t *allow = nullptr, bool inverted = false);
     // Per query its n_cand candidate rows d_cand [nq][n_cand] (ids outside [0, size) and removed rows: no candidate) scored with the
     // search's bits, the best k to d_ids / d_scores [nq][k].  1 <= n_cand <= 1024; the workspace [chunk][n_cand] grows on demand and is
     // not part of reserve: call once at the largest shape before a capture.  Asynchronous on s
@@ -77,9 +81,21 @@ public:
     bool text_buffers(size_t in_bytes, size_t out_bytes, char *&d_in, char *&d_out, std::string &err);
     // the results of a device search of nq queries on stream(), d_ids / d_scores in the index's result buffers -> host; blocking
     int search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err,
-                              const uint32_t *d_allow = nullptr);
+                              const uint32_t *d_allow = nullptr, bool inverted = false);
     // forget the rows behind the first n (an add of several parts that failed part way)
     void truncate(int n);
+    // Postings (sparse_index_kernels.h "Postings and the inverted search"): builds the term-major image of all size() rows from the
+    // stored blocks, in segments of the tuning key "sparse_index_segment_rows" (read here), and grows the search workspace to what
+    // the inverted plan needs for the n_queries and k last given to reserve.  Every call rebuilds all segments.  Returns the rows
+    // covered (= size).  Blocking; allocates
+    int invert(std::string &err);
+    // rows the postings cover: 0 without postings (never built, dropped by compact, a loaded index)
+    int inverted_rows() const { return inverted_ ? inv_rows_ : 0; }
+    bool has_postings() const { return inverted_; }
+    int segment_rows() const { return inv_seg_; }
+    // test hook: segment sg's offsets [n_vocab + 1] and its postings (row number inside the segment, weight as f32 — exact), in slot
+    // order, to the host; the segment's term total, -2 without postings or for a segment they do not have.  Blocking
+    int postings_segment_host(int sg, std::vector<uint32_t> &off, std::vector<uint16_t> &rows, std::vector<float> &weights, std::string &err);
 
 private:
     friend struct Hybrid;                               // hybrid.h: a search over this index and an embedding index together
@@ -94,6 +110,11 @@ private:
     bool make_live(std::string &err);
     void drop_live();
     bool upload_live(size_t w0, size_t w1, std::string &err);
+    void drop_postings();
+    bool grow_inverted(int n_rows, int nqc, int k, std::string &err);
+    bool inverted_ok(std::string &err) const;
+    void enqueue_chunk_inverted(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
+                                const uint32_t *d_allow);
 
     Engine *eng_ = nullptr;
     int n_vocab_ = 0, width_ = 0, dtype_ = 0;
@@ -109,6 +130,12 @@ private:
     DevBuf text_in_, text_out_;                         // text routes
     DevBuf allow_, cand_in_;                            // host routes: a caller's allow-list and candidate lists
     DevBuf hyb_scores_, hyb_mask_;                      // hybrid search: the current chunk's dense scores [HC][ld]; live & live & allow
+    // postings: offsets [segments][n_vocab + 1], row numbers and weights [segments][inv_seg_ * width_]; the rows they cover and the
+    // segment size they were built with; the current chunk's sorted queries (ids | weights [chunk][256], then the counts)
+    DevBuf poff_, prow_, pw_, qterms_;
+    bool inverted_ = false;
+    int inv_rows_ = 0, inv_seg_ = 0;
+    int res_nq_ = 0, res_k_ = 1;                        // what reserve was last given
     hipStream_t stream_ = nullptr;                      // the host routes' stream
     // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
     hipEvent_t busy_ = nullptr;

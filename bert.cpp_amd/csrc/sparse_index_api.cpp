@@ -160,6 +160,52 @@ int32_t bert_hip_sparse_index_search_filtered_device(struct bert_hip_sparse_inde
     });
 }
 
+// Postings and the inverted search: the frames of search_filtered[_device] and search_texts around the class's inverted form
+int32_t bert_hip_sparse_index_invert(struct bert_hip_sparse_index *ix) {
+    return sparse_index_call("bert_hip_sparse_index_invert", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) { return x.invert(err); });
+}
+
+int32_t bert_hip_sparse_index_inverted_rows(struct bert_hip_sparse_index *ix) { return ix && ix->ix ? ix->ix->inverted_rows() : -1; }
+
+int32_t bert_hip_sparse_index_search_inverted(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids, const float *q_weights,
+                                              int32_t k, const uint32_t *allow, int32_t n_words, int32_t *ids, float *scores) {
+    return sparse_index_call("bert_hip_sparse_index_search_inverted", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) -> int32_t {
+        if (!allow_ok(x, allow, n_words, err)) return -2;
+        return x.search_host(n_queries, kq, q_ids, q_weights, k, ids, scores, err, allow, true);
+    });
+}
+
+int32_t bert_hip_sparse_index_search_inverted_device(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *d_q_ids,
+                                                     const float *d_q_weights, int32_t k, const uint32_t *d_allow, int32_t n_words, int32_t *d_ids,
+                                                     float *d_scores, void *stream) {
+    return sparse_index_call("bert_hip_sparse_index_search_inverted_device", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) -> int32_t {
+        if (!allow_ok(x, d_allow, n_words, err)) return -2;
+        return x.search_device(n_queries, kq, d_q_ids, d_q_weights, k, d_ids, d_scores, (hipStream_t)stream, err, d_allow, true);
+    });
+}
+
+int32_t bert_hip_sparse_index_search_inverted_texts(struct bert_hip_sparse_index *ix, int32_t n_threads, int32_t n_queries, const char **texts, int32_t kq,
+                                                    int32_t k, int32_t *ids, float *scores) {
+    const char *me = "bert_hip_sparse_index_search_inverted_texts";
+    return sparse_index_call(me, ix, [&](bert_ctx *ctx, SparseIndex &x, std::string &err) -> int32_t {
+        if (!text_model_ok(ctx, x, err)) return -2;
+        if (k < 1 || k > SparseIndex::MAX_K || kq < 1 || kq > SparseIndex::MAX_TERMS) { err = "1 <= k <= 256 and 1 <= kq <= 256 required"; return -2; }
+        if (n_queries < 0 || (n_queries > 0 && (!texts || !ids || !scores))) { err = "n_queries >= 0 and texts / outputs required"; return -2; }
+        if (n_queries == 0) return 0;
+        // (refused before the model runs: the search itself would refuse each chunk)
+        if (!x.has_postings() || x.inverted_rows() != x.size()) { err = "the postings do not cover the index's rows: call bert_hip_sparse_index_invert"; return -2; }
+        std::vector<int32_t> hid((size_t)n_queries * k);
+        std::vector<float> hsc((size_t)n_queries * k);
+        const int32_t r = sparse_text_chunks(ctx, x, n_threads, n_queries, texts, kq, [&](int32_t i0, int32_t nb, const int32_t *d_ids, const float *d_w) -> int32_t {
+            return x.search_device_to_host(nb, kq, d_ids, d_w, k, hid.data() + (size_t)i0 * k, hsc.data() + (size_t)i0 * k, err, nullptr, true);
+        }, err);
+        if (r != 0) { if (err.empty()) err = "device error"; return r; }
+        memcpy(ids, hid.data(), hid.size() * 4);
+        memcpy(scores, hsc.data(), hsc.size() * 4);
+        return 0;
+    });
+}
+
 int32_t bert_hip_sparse_index_rescore(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids, const float *q_weights,
                                       int32_t n_cand, const int32_t *cand_ids, int32_t k, int32_t *ids, float *scores) {
     return sparse_index_call("bert_hip_sparse_index_rescore", ix, [&](bert_ctx *, SparseIndex &x, std::string &err) {

@@ -171,4 +171,95 @@ void launch_sparse_rescore(int dtype, const SparseRescoreArgs &a, hipStream_t s)
 void launch_sparse_gather(int dtype, const SparseGatherArgs &a, hipStream_t s);
 void launch_sparse_export(int dtype, const SparseExportArgs &a, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------------
+// Postings and the inverted search (sparse_postings.hip; the class side is sparse_postings.cpp)
+// ------------------------------------------------------------------------------------------------
+// Postings: a second, term-major image of the stored rows.  The rows are cut into segments of seg rows (a multiple of
+// SPARSE_STEP_ROWS, so a segment starts on a mask word; at most 16384, so a row number inside a segment is a u16).  Per segment a CSR
+// over the vocabulary: off[segment][n_vocab + 1] u32, and two posting arrays as the rows have two — prow, the row number inside the
+// segment (u16), and pw, the weight exactly as stored (f32 or f16).  Segment s owns the slots [s * seg * width, (s + 1) * seg * width)
+// of both arrays (a segment never holds more terms); list id of segment s is slots s * seg * width + [off[s][id], off[s][id + 1]).
+// The order of the entries inside a list is whatever the fill's atomics gave: every entry of a list belongs to another row.
+constexpr int SPARSE_SEGMENT_ROWS = 2048;               // the default seg (the sweep it comes from)
+constexpr int SPARSE_SEGMENT_ROWS_MAX = 16384;
+constexpr int SPARSE_POSTINGS_QB = NWAVE;               // the most queries of a tile: one wave walks one query's lists
+constexpr int SPARSE_POSTINGS_QB_AIM = 2;               // queries per tile the plan aims for: smaller tiles, more workgroups a CU
+// "sparse_index_segment_rows": 256 .. 16384 in multiples of 256, anything else (0 included) = the default
+inline int sparse_segment_rows(int pref) {
+    return pref >= SPARSE_STEP_ROWS && pref <= SPARSE_SEGMENT_ROWS_MAX && pref % SPARSE_STEP_ROWS == 0 ? pref : SPARSE_SEGMENT_ROWS;
+}
+inline int sparse_segments(int n_rows, int seg) { return (int)(((long long)n_rows + seg - 1) / seg); }
+
+// How a chunk of nq queries over n_rows rows in segments of seg rows is cut into workgroups of sparse_postings_scan_kernel: tiles of
+// qb queries times slices of slice_segs whole segments, and a workgroup's LDS — per query seg f32 accumulators, its sorted terms
+// (SPARSE_MAX_TERMS i32 ids and f32 weights) and a list of L = sparse_list_L(k) (score, id) entries, then a term count and a queue
+// count per query.  The one place this is decided: the search and the test hook both call it.  qb_pref as sparse_scan_geometry's:
+// 0, or the tile to aim for in place of SPARSE_POSTINGS_QB_AIM (values beyond SPARSE_POSTINGS_QB aim for that).  max_slices: what n_slices never exceeds and what never falls as n_rows grows.
+struct SparsePostingsGeometry { int qb, n_qtiles, n_slices, slice_segs, L, max_slices, seg; size_t lds; };
+inline bool sparse_postings_geometry(int dtype, int n_vocab, int n_rows, int nq, int k, int seg, SparsePostingsGeometry &g, int qb_pref = 0) {
+    g = SparsePostingsGeometry{0, 0, 0, 0, 0, 0, 0, 0};
+    if (dtype < 0 || dtype > 1 || n_vocab < 1 || n_vocab > SPARSE_MAX_VOCAB || (dtype == 1 && n_vocab > 65536) || n_rows < 0 || nq < 1 ||
+        k < 1 || k > SPARSE_MAX_TERMS || seg < SPARSE_STEP_ROWS || seg > SPARSE_SEGMENT_ROWS_MAX || seg % SPARSE_STEP_ROWS != 0)
+        return false;
+    g.seg = seg;
+    g.L = sparse_list_L(k);
+    const size_t per_query = (size_t)seg * 4 + (size_t)SPARSE_MAX_TERMS * 8 + (size_t)g.L * 8 + 8;
+    const int aim = qb_pref >= 1 ? std::min(qb_pref, SPARSE_POSTINGS_QB) : SPARSE_POSTINGS_QB_AIM;
+    g.qb = (int)std::min<size_t>((size_t)std::min(aim, nq), SPARSE_LDS_MAX / per_query);
+    if (g.qb < 1) return false;
+    g.n_qtiles = (nq + g.qb - 1) / g.qb;
+    const int n_segs = sparse_segments(n_rows, seg);
+    const int s = std::max(1, std::min((TARGET_BLOCKS + g.n_qtiles - 1) / g.n_qtiles, n_segs));
+    g.max_slices = s;
+    g.slice_segs = std::max(1, (n_segs + s - 1) / s);
+    g.n_slices = std::max(1, (n_segs + g.slice_segs - 1) / g.slice_segs);
+    g.lds = (size_t)g.qb * per_query;
+    return true;
+}
+
+// The three build kernels.  count: one thread per stored term of rows [0, n_rows), off[segment][id] += 1 (off zeroed before).
+// scan: one workgroup per segment, off[segment][0 .. n_vocab] becomes the exclusive prefix sum in place (off[segment][n_vocab] the
+// segment's term total).  fill: one thread per stored term, its place taken from cur — a copy of off that the fill consumes.
+struct SparsePostingsBuildArgs {
+    const void *sids, *sweights;        // the stored rows
+    const int32_t *counts;
+    uint32_t *off, *cur;                // [n_segs][n_vocab + 1]
+    uint16_t *prow;
+    void *pw;
+    int n_rows, width, n_vocab, seg;
+};
+
+// sparse_query_sort_kernel: one workgroup per query, ids / weights [nq][kq] -> the query's terms with an id in [0, n_vocab) in
+// ascending id (equal ids in input order), the weights as they are: tids / tw [nq][SPARSE_MAX_TERMS] and tn [nq]
+struct SparseQuerySortArgs {
+    const int32_t *ids;
+    const float *weights;
+    int32_t *tids;
+    float *tw;
+    int32_t *tn;
+    int nq, kq, n_vocab;
+};
+
+// sparse_postings_scan_kernel.  LDS: as sparse_postings_geometry states
+struct SparsePostingsScanArgs {
+    const uint32_t *off;
+    const uint16_t *prow;
+    const void *pw;
+    const int32_t *tids;                // the chunk's sorted queries (SparseQuerySortArgs)
+    const float *tw;
+    const int32_t *tn;
+    float *ws_s;                        // [nq][n_slices][k] per-(query, slice) lists, best first
+    int *ws_i;
+    int n_rows, width, n_vocab, seg, nq, qb, n_qtiles, n_slices, slice_segs, k, L, n_items;
+    const uint32_t *live, *allow;       // as SparseScanArgs's: read by the masked instantiation only
+};
+
+// lets the postings scan of the current device have SPARSE_LDS_MAX of LDS
+void sparse_postings_kernels_init();
+// count, scan and fill of all segments of a.n_rows rows, in that order on s; a.off zeroed and a.cur = a.off copied in between
+void launch_sparse_postings_build(int dtype, const SparsePostingsBuildArgs &a, hipStream_t s);
+void launch_sparse_query_sort(const SparseQuerySortArgs &a, hipStream_t s);
+// the masked instantiation iff a.live or a.allow is set
+void launch_sparse_postings_scan(int dtype, const SparsePostingsScanArgs &a, size_t lds, hipStream_t s);
+
 }  // namespace bert_hip

@@ -1073,6 +1073,31 @@ int32_t bert_hip_test_sparse_scan_geometry_qb(int32_t dtype, int32_t n_vocab, in
     return ok ? 0 : -2;
 }
 
+int32_t bert_hip_test_sparse_postings_geometry(int32_t dtype, int32_t n_vocab, int32_t n_rows, int32_t nq, int32_t k, int32_t seg, int32_t qb,
+                                               int64_t *geometry) {
+    if (!geometry) return -1;
+    SparsePostingsGeometry g;
+    const bool ok = sparse_postings_geometry(dtype, n_vocab, n_rows, nq, k, seg, g, qb);
+    geometry[0] = g.qb; geometry[1] = g.n_qtiles; geometry[2] = g.n_slices; geometry[3] = g.slice_segs; geometry[4] = g.L; geometry[5] = g.max_slices;
+    geometry[6] = (int64_t)g.lds;
+    return ok ? 0 : -2;
+}
+
+int32_t bert_hip_test_sparse_postings_segment(struct bert_hip_sparse_index *ix, int32_t segment, int32_t cap, uint32_t *off, int32_t *rows,
+                                              float *weights, int32_t *seg_rows) {
+    if (!ix || !ix->ix || !off || !rows || !weights || !seg_rows || cap < 0) return -1;
+    std::vector<uint32_t> o;
+    std::vector<uint16_t> r;
+    std::vector<float> w;
+    std::string err;
+    const int total = ix->ix->postings_segment_host(segment, o, r, w, err);
+    if (total < 0) return total;
+    *seg_rows = ix->ix->segment_rows();
+    memcpy(off, o.data(), o.size() * 4);
+    for (int i = 0; i < std::min(total, cap); ++i) { rows[i] = r[(size_t)i]; weights[i] = w[(size_t)i]; }
+    return total;
+}
+
 int32_t bert_hip_test_hybrid_chunk(int32_t n_rows, int32_t nq, int32_t pref, int64_t *out) {
     if (!out) return -1;
     out[0] = out[1] = 0;

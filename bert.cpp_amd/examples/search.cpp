@@ -6,7 +6,7 @@
 //   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
 //               [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N]
 //   bert-search -m MODEL -f TEXTS --late [--i8] [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]
-//   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
+//   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [--inverted] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
 //   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]
 //   (--hybrid SPLADE: hybrid search.  SPLADE is a second model file, one with the MLM head, loaded into a context of its own (it may be
 //   the same file as DENSE).  Every line goes into an embedding index of DENSE (bert_hip_index_add_texts; --f32 / --i8 / --b1 as
@@ -17,7 +17,9 @@
 //   (--sparse [WIDTH]: learned sparse search.  MODEL must carry the MLM head (bert_hip.h "learned sparse embeddings"); every line's WIDTH
 //   largest terms (default 128, 1 .. 256) go into a sparse index (bert_hip_sparse_index_add_texts; --f16: u16 ids and f16 weights),
 //   each query line is searched with its WIDTH largest terms (bert_hip_sparse_index_search_texts), and the output has the dense mode's
-//   shape.  Lines without a term in common with the query score 0 and are not printed.  --save: the sparse index goes to PATH once it
+//   shape.  --inverted: the postings are built once the lines are in the index (bert_hip_sparse_index_invert) and the queries go through
+//   bert_hip_sparse_index_search_inverted_texts — the same lines, the same scores; not together with --hybrid.
+//   Lines without a term in common with the query score 0 and are not printed.  --save: the sparse index goes to PATH once it
 //   is built (bert_hip_sparse_index_save); --load: it comes from PATH instead of being encoded (bert_hip_sparse_index_load; its stored
 //   type is the file's) — TEXTS is still read, for printing, and must have as many lines as the index has rows.  The dense mode's other
 //   options do not apply.)
@@ -74,14 +76,15 @@ namespace {
 void usage(const char *argv0) {
     fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --late [--i8] [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
-    fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
+    fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [--inverted] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
     fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]\n", argv0);
     fprintf(stderr, "  --hybrid SPLADE: hybrid search: the lines in an embedding index of DENSE and a sparse index of SPLADE (a model file with the MLM head; W\n"
                     "          terms a line, default 128), each query answered by bert_hip_hybrid_search_texts: the exact top-k of WD * dense + WS * sparse\n"
                     "          (default 1,1).  Not with --sparse, --lists, --nprobe, --rescore, --long, --maxsim, --cross, --save, --load.\n");
     fprintf(stderr, "  --sparse [WIDTH]: learned sparse search with a model that carries the MLM head: each line's and each query's WIDTH largest terms\n"
                     "          (default 128, 1 .. 256) through a sparse index (bert_hip_sparse_index_*); --f16 stores u16 ids and f16 weights;\n"
-                    "          --save PATH writes the sparse index once it is built, --load PATH reads it instead of encoding TEXTS (still read for printing).\n");
+                    "          --save PATH writes the sparse index once it is built, --load PATH reads it instead of encoding TEXTS (still read for printing);\n"
+                    "          --inverted builds the postings and answers through the inverted search (the same output; not with --hybrid).\n");
     fprintf(stderr, "  --long: lines of any length, cut into overlapping windows of W ids, S inner ids apart, one row per line (defaults: W 128 or the\n"
                     "          model's position limit if that is less, S three quarters of W - 2).  Without --long a line is cut at the model's position limit.\n");
     fprintf(stderr, "  --maxsim N: the search returns N candidates (k <= N <= 256), which are reranked by the MaxSim score of their token rows against the\n"
@@ -110,7 +113,7 @@ int main(int argc, char **argv) {
     float w_dense = 1.f, w_sparse = 1.f;
     bool weights_ok = true;
     int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0, n_cross = 0;
-    bool long_texts = false, maxsim = false, cross = false, sparse = false, sparse_f16 = false, token_index = false, late = false;
+    bool long_texts = false, maxsim = false, cross = false, sparse = false, sparse_f16 = false, token_index = false, late = false, inverted = false;
     int sparse_width = 128;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
@@ -134,6 +137,7 @@ int main(int argc, char **argv) {
             if (has_value && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') sparse_width = atoi(argv[++i]);
         }
         else if (!strcmp(argv[i], "--f16")) sparse_f16 = true;
+        else if (!strcmp(argv[i], "--inverted")) inverted = true;
         else if (!strcmp(argv[i], "--hybrid") && has_value) hybrid_model = argv[++i];
         else if (!strcmp(argv[i], "--sparse-width") && has_value) sparse_width = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--weights") && has_value) {
@@ -169,6 +173,8 @@ int main(int argc, char **argv) {
         fprintf(stderr, "search: --hybrid goes with -m, -f, -k, -t, --sparse-width, --weights, --f32, --i8, --b1 and --f16 only\n");
         return 2;
     }
+    if (inverted && hybrid_model) { fprintf(stderr, "search: --inverted does not go with --hybrid: a hybrid search reads the rows, not the postings\n"); return 2; }
+    if (inverted && !sparse) { fprintf(stderr, "search: --inverted goes with --sparse\n"); return 2; }
     if (hybrid_model && (sparse_width < 1 || sparse_width > 256)) { fprintf(stderr, "search: --hybrid: --sparse-width must be 1 .. 256\n"); return 2; }
     if (hybrid_model && !weights_ok) { fprintf(stderr, "search: --hybrid: --weights takes two finite numbers, WD,WS\n"); return 2; }
     if (!hybrid_model && (!weights_ok || w_dense != 1.f || w_sparse != 1.f)) { fprintf(stderr, "search: --weights goes with --hybrid\n"); return 2; }
@@ -296,6 +302,11 @@ int main(int argc, char **argv) {
             bert_free(ctx);
             return 1;
         }
+        if (inverted && bert_hip_sparse_index_invert(sx) < 0) {
+            fprintf(stderr, "search: could not build the postings\n");
+            bert_free(ctx);
+            return 1;
+        }
         printf("Loaded %zu lines.\n", texts.size());
         std::vector<int32_t> sids((size_t)k);
         std::vector<float> sscores((size_t)k);
@@ -307,7 +318,8 @@ int main(int argc, char **argv) {
             q = chomp(q);
             if (q == "q") break;
             const char *qp = q.c_str();
-            if (bert_hip_sparse_index_search_texts(sx, n_threads, 1, &qp, sparse_width, k, sids.data(), sscores.data()) != 0) {
+            if ((inverted ? bert_hip_sparse_index_search_inverted_texts(sx, n_threads, 1, &qp, sparse_width, k, sids.data(), sscores.data())
+                          : bert_hip_sparse_index_search_texts(sx, n_threads, 1, &qp, sparse_width, k, sids.data(), sscores.data())) != 0) {
                 fprintf(stderr, "search: the search failed\n");
                 bert_free(ctx);
                 return 1;

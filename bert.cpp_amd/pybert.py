@@ -48,6 +48,8 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_sparse_index_remove", "bert_hip_sparse_index_n_live", "bert_hip_sparse_index_search_filtered",
     "bert_hip_sparse_index_search_filtered_device", "bert_hip_sparse_index_rescore", "bert_hip_sparse_index_rescore_device",
     "bert_hip_sparse_index_compact", "bert_hip_sparse_index_save", "bert_hip_sparse_index_load",
+    "bert_hip_sparse_index_invert", "bert_hip_sparse_index_inverted_rows", "bert_hip_sparse_index_search_inverted",
+    "bert_hip_sparse_index_search_inverted_device", "bert_hip_sparse_index_search_inverted_texts",
     "bert_hip_hybrid_reserve", "bert_hip_hybrid_search", "bert_hip_hybrid_search_device", "bert_hip_hybrid_search_texts",
     "bert_hip_token_index_create", "bert_hip_token_index_free", "bert_hip_token_index_size", "bert_hip_token_index_n_tokens",
     "bert_hip_token_index_max_query_tokens", "bert_hip_token_index_reserve", "bert_hip_token_index_add", "bert_hip_token_index_add_device",
@@ -75,6 +77,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan", "bert_hip_test_hybrid_chunk", "bert_hip_test_token_index_plan",
     "bert_hip_test_late_index_header", "bert_hip_test_late_index_body",
     "bert_hip_test_attention_bias", "bert_hip_test_f32_attention_bias", "bert_hip_test_rel_bias_table",
+    "bert_hip_test_sparse_postings_geometry", "bert_hip_test_sparse_postings_segment",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -222,6 +225,14 @@ def _declare_product_abi(L):
     L.bert_hip_sparse_index_compact.restype = i32; L.bert_hip_sparse_index_compact.argtypes = [vp, vp]
     L.bert_hip_sparse_index_save.restype = i32; L.bert_hip_sparse_index_save.argtypes = [vp, C.c_char_p]
     L.bert_hip_sparse_index_load.restype = vp; L.bert_hip_sparse_index_load.argtypes = [vp, C.c_char_p]
+    L.bert_hip_sparse_index_invert.restype = i32; L.bert_hip_sparse_index_invert.argtypes = [vp]
+    L.bert_hip_sparse_index_inverted_rows.restype = i32; L.bert_hip_sparse_index_inverted_rows.argtypes = [vp]
+    L.bert_hip_sparse_index_search_inverted.restype = i32
+    L.bert_hip_sparse_index_search_inverted.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp]
+    L.bert_hip_sparse_index_search_inverted_device.restype = i32
+    L.bert_hip_sparse_index_search_inverted_device.argtypes = [vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp]
+    L.bert_hip_sparse_index_search_inverted_texts.restype = i32
+    L.bert_hip_sparse_index_search_inverted_texts.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32, vp, vp]
     f32 = C.c_float
     L.bert_hip_hybrid_reserve.restype = i32; L.bert_hip_hybrid_reserve.argtypes = [vp, vp, i32, i32, i32]
     L.bert_hip_hybrid_search.restype = i32; L.bert_hip_hybrid_search.argtypes = [vp, vp, i32, vp, i32, vp, vp, f32, f32, vp, i32, i32, vp, vp]
@@ -359,6 +370,10 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
     L.bert_hip_test_partition_header.restype = i32
     L.bert_hip_test_partition_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
+    L.bert_hip_test_sparse_postings_geometry.restype = i32
+    L.bert_hip_test_sparse_postings_geometry.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int64)]
+    L.bert_hip_test_sparse_postings_segment.restype = i32
+    L.bert_hip_test_sparse_postings_segment.argtypes = [vp, i32, i32, vp, vp, vp, C.POINTER(i32)]
     L.bert_hip_test_sparse_index_header.restype = i32
     L.bert_hip_test_sparse_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
     L.bert_hip_test_sparse_index_body.restype = i32
@@ -517,6 +532,33 @@ def test_sparse_scan_geometry(dtype: int, n_vocab: int, n_rows: int, nq: int, k:
     if r != 0:
         raise RuntimeError(f"bert_hip_test_sparse_scan_geometry failed: {r}")
     return dict(qb=g[0], n_qtiles=g[1], n_slices=g[2], slice_rows=g[3], L=g[4], lds=g[5])
+
+
+def test_sparse_postings_geometry(dtype: int, n_vocab: int, n_rows: int, nq: int, k: int, seg: int, qb: int = 0):
+    """How the sparse index's inverted search cuts a chunk of queries (bert_hip_test_sparse_postings_geometry; no GPU): a dict of qb,
+    n_qtiles, n_slices, slice_segs, L, max_slices and lds, or None where the plan refuses.  seg: rows per segment; qb: the value of the
+    tuning key "sparse_index_qb" (0 = unset)."""
+    g = (C.c_int64 * 7)()
+    r = test_lib().bert_hip_test_sparse_postings_geometry(dtype, n_vocab, n_rows, nq, k, seg, qb, g)
+    if r == -2:
+        return None
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_sparse_postings_geometry failed: {r}")
+    return dict(qb=g[0], n_qtiles=g[1], n_slices=g[2], slice_segs=g[3], L=g[4], max_slices=g[5], lds=g[6])
+
+
+def test_sparse_postings_segment(index: "BertSparseIndex", segment: int):
+    """One segment of an index's postings (bert_hip_test_sparse_postings_segment; the index of a BertModel(test_routes=True)):
+    (off [n_vocab + 1] uint32, rows [total] int32 — row numbers inside the segment —, weights [total] float32, seg_rows)."""
+    off = np.zeros(index.n_vocab + 1, dtype=np.uint32)
+    cap = 16384 * index.width
+    rows = np.zeros(cap, dtype=np.int32)
+    w = np.zeros(cap, dtype=np.float32)
+    seg_rows = C.c_int32(0)
+    r = test_lib().bert_hip_test_sparse_postings_segment(index.ix, segment, cap, off.ctypes.data, rows.ctypes.data, w.ctypes.data, C.byref(seg_rows))
+    if r < 0:
+        raise RuntimeError(f"bert_hip_test_sparse_postings_segment failed: {r}")
+    return off, rows[:r].copy(), w[:r].copy(), int(seg_rows.value)
 
 
 def test_index_plan(n_rows: int, nq: int, k: int):
@@ -1784,6 +1826,49 @@ class BertSparseIndex:
         r = self.lib.bert_hip_sparse_index_search_texts(self.ix, n_threads, n, txt, kq, k, ids.ctypes.data, scores.ctypes.data)
         if r != 0:
             self._fail("bert_hip_sparse_index_search_texts", r)
+        return ids, scores
+
+    def invert(self) -> int:
+        """bert_hip_sparse_index_invert: builds the postings of all rows (the inverted searches read them); the rows covered."""
+        r = self.lib.bert_hip_sparse_index_invert(self.ix)
+        if r < 0:
+            self._fail("bert_hip_sparse_index_invert", r)
+        return r
+
+    @property
+    def inverted_rows(self) -> int:
+        return int(self.lib.bert_hip_sparse_index_inverted_rows(self.ix))
+
+    def search_inverted(self, q_ids, q_weights, k: int = 10, allow=None):
+        """search through the postings (bert_hip_sparse_index_search_inverted): the ids and score bits of search(..., allow).  A
+        ValueError too where the postings do not cover the rows (no invert yet, rows added since, compacted)."""
+        q_ids, q_weights = self._terms(q_ids, q_weights)
+        nq = q_ids.shape[0]
+        ids = np.empty((nq, max(k, 1)), dtype=np.int32)
+        scores = np.empty((nq, max(k, 1)), dtype=np.float32)
+        words = None if allow is None else allow_words(allow, len(self))
+        r = self.lib.bert_hip_sparse_index_search_inverted(self.ix, nq, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data, k,
+                                                           None if words is None else words.ctypes.data, 0 if words is None else len(words),
+                                                           ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_search_inverted", r)
+        return ids, scores
+
+    def search_inverted_device(self, n_queries: int, kq: int, d_q_ids_ptr: int, d_q_weights_ptr: int, k: int, d_ids_ptr: int, d_scores_ptr: int,
+                               stream: int = 0, d_allow_ptr: int = 0, n_words: int = 0) -> None:
+        r = self.lib.bert_hip_sparse_index_search_inverted_device(self.ix, n_queries, kq, d_q_ids_ptr, d_q_weights_ptr, k, d_allow_ptr or None,
+                                                                  n_words, d_ids_ptr, d_scores_ptr, stream)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_search_inverted_device", r)
+
+    def search_texts_inverted(self, texts: Sequence, kq: int = 32, k: int = 10, n_threads: int = 6):
+        n = len(texts)
+        txt = (C.c_char_p * n)(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        ids = np.empty((n, max(k, 1)), dtype=np.int32)
+        scores = np.empty((n, max(k, 1)), dtype=np.float32)
+        r = self.lib.bert_hip_sparse_index_search_inverted_texts(self.ix, n_threads, n, txt, kq, k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._fail("bert_hip_sparse_index_search_inverted_texts", r)
         return ids, scores
 
     def get_rows(self, row_ids):

@@ -185,7 +185,9 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  * per forward pass), "chunk_tokens" = n, "gather_super_tokens" = n (bert_hip_eval_packed_gather: tokens per device and super-batch, 0 =
  * four device chunks), "stage_kernel" = "0" | "1" (host API: staged blocks of at most 256 KiB travel by a kernel that reads the mapped
  * pinned memory instead of the copy engine), "sparse_index_qb" = n (tuning: queries per workgroup tile of the sparse index's scan, 1 .. 8;
- * "0" = the built-in choice; a result's bits do not depend on it; set it before bert_hip_sparse_index_reserve), "hybrid_chunk_queries" = n (tuning: queries
+ * "0" = the built-in choice; a result's bits do not depend on it; set it before bert_hip_sparse_index_reserve), "sparse_index_segment_rows" = n
+ * (tuning: rows per segment of a sparse index's postings, 256 .. 16384 in multiples of 256; "0" = the built-in choice; read by
+ * bert_hip_sparse_index_invert; a result's bits do not depend on it), "hybrid_chunk_queries" = n (tuning: queries
  * per internal chunk of a hybrid search, 1 .. 4096, never more than the score workspace's bound allows; "0" = what that bound gives; a
  * result's bits do not depend on it), "token_index_slices" = n (tuning: slices of documents a token index's scan is cut into, 1 .. 4096,
  * never more than documents; "0" = planned; a result's bits do not depend on it; set it before bert_hip_token_index_reserve),
@@ -715,8 +717,8 @@ BERT_API struct bert_hip_index *bert_hip_index_load(struct bert_ctx *ctx, const 
  * Results: -1 without an index (or, for the text forms, a context without a device); -2 after a line on stderr for an argument the
  * entry refuses (the checks above, k_in > width, k or kq out of range, a missing pointer, a model without the head); -3 on a device
  * error; -4 for an exception.  Outputs are untouched on error.
- * Not covered: an inverted (term-major) organisation; several GPUs; rows wider than 256 terms.  (A search over an embedding index
- * and a sparse index together: "Hybrid search" below.)                                                                                                                      */
+ * Not covered: several GPUs; rows wider than 256 terms.  (A search over an embedding index and a sparse index together: "Hybrid
+ * search" below; a term-major image of the rows and a search over it: "Sparse index: postings and the inverted search" below.)    */
 struct bert_hip_sparse_index;
 BERT_API struct bert_hip_sparse_index *bert_hip_sparse_index_create(struct bert_ctx *ctx, int32_t n_vocab, int32_t width, int32_t dtype);
 BERT_API void    bert_hip_sparse_index_free(struct bert_hip_sparse_index *ix);
@@ -794,6 +796,49 @@ BERT_API int32_t bert_hip_sparse_index_rescore_device(struct bert_hip_sparse_ind
 BERT_API int32_t bert_hip_sparse_index_compact(struct bert_hip_sparse_index *ix, int32_t *old_ids);
 BERT_API int32_t bert_hip_sparse_index_save(struct bert_hip_sparse_index *ix, const char *path);
 BERT_API struct bert_hip_sparse_index *bert_hip_sparse_index_load(struct bert_ctx *ctx, const char *path);
+
+/* Sparse index: postings and the inverted search.  The search above reads every stored term of every row for every tile of queries.
+ * The postings are a second, term-major image of the stored rows, built on the device from the blocks the index already holds; the
+ * inverted search reads only the lists of the terms a query has, keeps one f32 accumulator per row on chip, and selects from those.
+ *   invert   builds the postings of all size rows and returns that number (0 for an empty index, which is valid).  Rows are cut into
+ *            segments of S rows (the tuning key "sparse_index_segment_rows", read here; S = 2048 unless set); per segment a CSR over the
+ *            vocabulary — n_vocab + 1 u32 offsets — and per stored term a u16 row number inside the segment and the weight exactly as
+ *            stored.  Memory: about that of the rows again (ceil(size / S) * S * width slots of 6 bytes for dtype 0, 4 bytes for
+ *            dtype 1) plus ceil(size / S) * (n_vocab + 1) * 4 bytes of offsets, and as many bytes again while invert runs.  Called again
+ *            after adds it rebuilds every segment; later searches equal those of a fresh build either way.  It also grows the search
+ *            workspace to what the inverted search needs for the n_queries and k last given to reserve, so that reserve + invert (in
+ *            either order) make search_inverted_device legal under stream capture within those bounds.  Blocking; allocates.
+ *   inverted_rows   the rows the postings cover; 0 without postings; -1 without an index.
+ *   search_inverted[_device]   for every query exactly what bert_hip_sparse_index_search_filtered[_device] returns on the same index
+ *            with the same arguments: the same ids and the same score bits.  allow == NULL is the plain search.  The score rule is a
+ *            chain in ascending term id; the inverted search walks a query's terms in ascending id and applies the same fmaf steps to
+ *            each row's accumulator, from +0, in the same order; absent terms are skipped in both forms, so the -0 footnote above
+ *            holds unchanged.  Every promise above carries over: a row without a matching term scores +0 and competes; the order rule
+ *            (larger score first, == ties by smaller id, NaN never returned, -1 / -INFINITY slots); 1 <= k <= 256 and 1 <= kq <= 256;
+ *            removed rows and allow-lists are honoured; a score's bits do not depend on the other queries of the call, on k, on how
+ *            the rows are cut into segments and workgroups, on the add history, or on host or device entry; the one-event rule;
+ *            within reserved bounds the device form does not allocate and is legal under stream capture.  Checks, chunking of large
+ *            n_queries and error codes are search_filtered's: the host form checks its queries, the device form does not look — an id
+ *            outside [0, n_vocab) counts as -1, a repeated id in a row or a query leaves only that row's or that query's scores
+ *            unspecified, nothing is read or written out of bounds.
+ *   search_inverted_texts   bert_hip_sparse_index_search_texts through the inverted search.
+ *   stale postings   rows added since the last invert: every inverted search returns -2 after a line on stderr that says to call
+ *            invert (as it does before the first invert); inverted_rows still reports the rows covered.  It never answers over a part
+ *            of the rows.  remove keeps the postings: removed rows are dropped at selection.  compact drops them (the ids change;
+ *            inverted_rows is 0 until the next invert).  A loaded index has no postings: save writes the rows only.
+ * Not covered: a file form of the postings; hybrid search over postings; dynamic pruning (WAND / max-score) — this search is exact and
+ * scores every row that holds a queried term; appending to postings on the device or under capture.                                */
+BERT_API int32_t bert_hip_sparse_index_invert(struct bert_hip_sparse_index *ix);
+BERT_API int32_t bert_hip_sparse_index_inverted_rows(struct bert_hip_sparse_index *ix);
+BERT_API int32_t bert_hip_sparse_index_search_inverted(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq, const int32_t *q_ids,
+                                                       const float *q_weights, int32_t k, const uint32_t *allow, int32_t n_words,
+                                                       int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_sparse_index_search_inverted_device(struct bert_hip_sparse_index *ix, int32_t n_queries, int32_t kq,
+                                                              const int32_t *d_q_ids, const float *d_q_weights, int32_t k,
+                                                              const uint32_t *d_allow, int32_t n_words, int32_t *d_ids, float *d_scores,
+                                                              void *stream);
+BERT_API int32_t bert_hip_sparse_index_search_inverted_texts(struct bert_hip_sparse_index *ix, int32_t n_threads, int32_t n_queries,
+                                                             const char **texts, int32_t kq, int32_t k, int32_t *ids, float *scores);
 
 /* Hybrid search: the exact top-k, over ALL qualifying rows, of a weighted sum of an embedding index's and a sparse index's scores.
  * `dense` is a bert_hip_index of any dtype (0 .. 3), `sparse` a bert_hip_sparse_index of either dtype.  They may belong to different

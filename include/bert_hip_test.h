@@ -329,6 +329,20 @@ BERT_API int32_t bert_hip_test_token_index_plan(int32_t n_docs, int32_t nq, int3
 BERT_API int32_t bert_hip_test_late_index_header(const void *buf, int32_t buf_len, int64_t file_bytes, uint32_t *fields, char *err,
                                                  int32_t err_cap);
 BERT_API int32_t bert_hip_test_late_index_body(const uint32_t *fields, const void *body, int64_t body_len, char *err, int32_t err_cap);
+/* How the sparse index's inverted search cuts a chunk of nq queries with this k over n_rows rows in segments of seg rows
+ * (sparse_index_kernels.h sparse_postings_geometry, the function the search itself calls; no GPU): geometry = {qb, n_qtiles, n_slices,
+ * slice_segs, L, max_slices, lds} — queries per tile, tiles, slices, whole segments per slice (the last slice may have fewer), entries of
+ * a query's LDS list, the workspace's bound on n_slices, bytes of LDS per workgroup.  qb: the value of the tuning key "sparse_index_qb"
+ * (0 = unset).  0; -2 and zeros where the plan refuses (sparse_scan_geometry's reasons, or seg outside 256 .. 16384 or no multiple of
+ * 256); -1 for a NULL geometry.                                                                                                   */
+BERT_API int32_t bert_hip_test_sparse_postings_geometry(int32_t dtype, int32_t n_vocab, int32_t n_rows, int32_t nq, int32_t k, int32_t seg,
+                                                        int32_t qb, int64_t *geometry);
+/* One segment of an index's postings back on the host (an index of a context of libbert_test.so).  off [n_vocab + 1]: the segment's
+ * offsets; rows / weights [cap]: the first min(cap, total) postings in slot order, the row number inside the segment and the weight
+ * (f16 exactly converted); *seg_rows: the segment size the postings were built with.  Returns the segment's term total; -2 without
+ * postings or for a segment they do not have; -1 without an index or for a NULL pointer; -3 on a device error.  Blocking.          */
+BERT_API int32_t bert_hip_test_sparse_postings_segment(struct bert_hip_sparse_index *ix, int32_t segment, int32_t cap, uint32_t *off,
+                                                       int32_t *rows, float *weights, int32_t *seg_rows);
 
 #ifdef __cplusplus
 }

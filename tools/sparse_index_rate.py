@@ -2,7 +2,7 @@
 """Rate of the sparse index's search (bert_hip_sparse_index_search_device) on one GPU: 10^6 synthetic rows of up to 128 terms drawn
 Zipf-like over V = 30 522, queries of up to 32 terms drawn the same way, both dtypes, 1 / 64 / 4096 queries, k = 10 and 100.
 
-    python tools/sparse_index_rate.py [--rows 1000000] [--qb 1,2,4,8] [--sections search,filtered,rescore] [--out profiles/sparse_index_rate.txt] [--append]
+    python tools/sparse_index_rate.py [--rows 1000000] [--qb 1,2,4,8] [--sections search,filtered,rescore,inverted] [--out profiles/sparse_index_rate.txt] [--append]
 
 Per cell: the time per call (device events around back-to-back calls on one stream, the median of the rounds); the bytes of stored terms
 the call reads (every query tile walks every row's terms once: ids + weights of the stored terms, 8 or 4 bytes each, times the tiles) over
@@ -14,7 +14,13 @@ key "sparse_index_qb") at 64 and 4096 queries, which sparse_index_kernels.h's SP
 allow-lists of 100 %, 50 % and 1 % of the rows at random and 1 % in contiguous 64-row blocks, beside the plain search, and the plain
 search again on an index whose rows were removed down to the same 50 % (the masked scan through the live bits); "rescore":
 rescore_device of 1000 candidates per query (distinct random rows) beside a filtered search of one query under an allow-list of exactly
-such candidates.  --append adds to --out instead of replacing it.
+such candidates; "inverted": search_inverted_device beside search_device on the same index in the same process, the runs interleaved
+(one timed run of each per repeat, min .. max of --repeats repeats), at 1 / 64 / 4096 queries and k = 10 and 100, with the time of
+invert and the postings' bytes, on two row distributions — ids = V u^3 (the workload above: some terms are in most rows) and uniformly
+random ids (which flatters an inverted search: every list is short) —, a sweep of the tuning key "sparse_index_segment_rows" over
+--segments at 1, 64 and 4096 queries and the tile size's A/B ("sparse_index_qb" 1 and 4 against the plan's 2; the key is the row-major scan's too) at the default segment size, and per cell the floor of the arithmetic: the postings of the queries' lists read once at the HBM
+line plus one pass over 4 bytes per (row, query) of LDS accumulators at the LDS line.  Both searches' results are compared, ids and
+score bits, before anything is timed.  --append adds to --out instead of replacing it.
 Everything is in device memory; the rows are generated on the device and added with add_device."""
 import argparse
 import os
@@ -35,6 +41,8 @@ def main():
     ap.add_argument("--qb", default="1,2,4,8")
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--sections", default="search")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--segments", default="512,1024,2048,4096,8192,16384")
     ap.add_argument("--append", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -58,9 +66,9 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(1)
 
-    def terms(n, kk):
+    def terms(n, kk, power=3):
         """ids [n, kk] i32 (Zipf-like: V u^3; a repeat within a row becomes -1) and weights [n, kk] f32 in (0, 2)"""
-        ids = (V * torch.rand(n, kk, device=dev, generator=gen) ** 3).to(torch.int32).clamp_(max=V - 1)
+        ids = (V * torch.rand(n, kk, device=dev, generator=gen) ** power).to(torch.int32).clamp_(max=V - 1)
         ids, _ = torch.sort(ids, dim=1)
         ids[:, 1:][ids[:, 1:] == ids[:, :-1]] = -1
         w = torch.rand(n, kk, device=dev, generator=gen) * 2 + 1e-3
@@ -95,6 +103,93 @@ def main():
             f"(min .. max) of {a.rounds} rounds of back-to-back calls between device events")
         out(f"# share = bytes of stored terms read (terms x 8 or 4 bytes x query tiles) / time / {HBM_LINE / 1e12:.1f} TB/s")
         csr = None
+        LDS_LINE = 256 * 128 * 2.4e9                             # bytes/s: 4-byte LDS reads at 128 bytes a clock and CU, 256 CUs, 2.4 GHz
+        uniform = (terms(N, W, 1), terms(4096, KQ, 1)) if "inverted" in sections else None
+
+        def pair_timed(f_inv, f_row):
+            """(min, max) ms of each over --repeats repeats; a repeat times one run of back-to-back calls of each, interleaved"""
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ts = ([], [])
+            iters = []
+            for f in (f_inv, f_row):
+                f()
+                torch.cuda.synchronize()
+                e0.record(); f(); e1.record(); e1.synchronize()
+                iters.append(int(max(1, min(50, 100.0 / max(e0.elapsed_time(e1), 1e-3)))))
+            for _ in range(a.repeats):
+                for f, it, t in zip((f_inv, f_row), iters, ts):
+                    e0.record()
+                    for _ in range(it):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    t.append(e0.elapsed_time(e1) / it)
+            return (min(ts[0]), max(ts[0])), (min(ts[1]), max(ts[1]))
+
+        def inverted_section(dtype, ix_readme, d_ids, d_sc):
+            import time
+            wb = idb = 4 if dtype == "f32" else 2
+            d_ids2, d_sc2 = torch.empty_like(d_ids), torch.empty_like(d_sc)
+            for dist, rows_q in (("ids = V u^3", None), ("uniform ids", uniform)):
+                if rows_q is None:
+                    ixd, rid, qi, qw = ix_readme, r_ids, q_ids, q_w
+                else:
+                    (rid, rw), (qi, qw) = rows_q
+                    ixd = m.sparse_index(W, dtype, n_vocab=V)
+                    ixd.reserve(N, 4096, 100)
+                    for r0 in range(0, N, 100000):
+                        c = min(100000, N - r0)
+                        ixd.add_device(c, W, rid[r0:r0 + c].data_ptr(), rw[r0:r0 + c].data_ptr(), stream)
+                    torch.cuda.synchronize()
+                # the rows that hold each id: the length of its posting list over the whole index
+                df = torch.bincount(rid[rid >= 0].long(), minlength=V)
+                nt = int((rid >= 0).sum())
+
+                def inv(nq, k):
+                    ixd.search_inverted_device(nq, KQ, qi.data_ptr(), qw.data_ptr(), k, d_ids2.data_ptr(), d_sc2.data_ptr(), stream)
+
+                def rowm(nq, k):
+                    ixd.search_device(nq, KQ, qi.data_ptr(), qw.data_ptr(), k, d_ids.data_ptr(), d_sc.data_ptr(), stream)
+
+                def table(seg_label, cells):
+                    for nq, k in cells:
+                        inv(nq, k); rowm(nq, k)
+                        torch.cuda.synchronize()
+                        n = nq * k
+                        assert torch.equal(d_ids.view(-1)[:n], d_ids2.view(-1)[:n]) and torch.equal(d_sc.view(-1)[:n].view(torch.int32), d_sc2.view(-1)[:n].view(torch.int32)), (dist, nq, k)
+                        (ilo, ihi), (rlo, rhi) = pair_timed(lambda: inv(nq, k), lambda: rowm(nq, k))
+                        posts = int(df[qi[:nq][qi[:nq] >= 0].long()].sum())
+                        floor = posts * (2 + wb) / HBM_LINE * 1e3 + nq * N * 4 / LDS_LINE * 1e3
+                        slow = "**" if ilo > rhi else ""
+                        out(f"  {seg_label:>6} {nq:5d} {k:4d}   {slow}{ilo:9.3f} .. {ihi:9.3f}{slow}   {rlo:9.3f} .. {rhi:9.3f}   {rlo / ilo:7.2f}   {posts:12d} {floor:9.4f} {ilo / floor:8.1f}")
+
+                out(f"# dtype {dtype}, {dist}: search_inverted_device beside search_device, ms per call, min .. max of {a.repeats} interleaved repeats; "
+                    f"** = the inverted search is slower (its fastest repeat against the row-major search's slowest)")
+                out("#    seg    nq    k        inverted (min .. max)     row-major (min .. max)   row/inv   postings read  floor ms  inv/floor")
+                segs = [int(x) for x in a.segments.split(",")] if rows_q is None else []
+                for seg in [0] + segs:
+                    m.set_option("sparse_index_segment_rows", str(seg))
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    assert ixd.invert() == N
+                    t_inv = (time.perf_counter() - t0) * 1e3
+                    sg = seg or 2048
+                    n_seg = -(-N // sg)
+                    pbytes = n_seg * sg * W * (2 + wb) + n_seg * (V + 1) * 4
+                    out(f"#   segment rows {sg}{' (the default)' if not seg else ''}: invert {t_inv:.1f} ms (blocking, with its allocations); postings {pbytes / 1e9:.3f} GB "
+                        f"({n_seg * (V + 1) * 4 / 1e6:.1f} MB of them offsets) for {nt * (idb + wb) / 1e9:.3f} GB of stored terms in {-(-N // 64) * 64 * W * (idb + wb) / 1e9:.3f} GB of blocks")
+                    table(str(sg), [(nq, k) for nq in (1, 64, 4096) for k in (10, 100)] if not seg else [(1, 10), (64, 10), (4096, 10)])
+                m.set_option("sparse_index_segment_rows", "0")
+                if rows_q is None:
+                    # the tile's A/B at the default segment size (a tile of qb queries keeps qb of the workgroup's four waves walking)
+                    assert ixd.invert() == N
+                    for qb in (1, 4):
+                        m.set_option("sparse_index_qb", str(qb))
+                        table(f"qb {qb}", [(64, 10), (4096, 10)])
+                    m.set_option("sparse_index_qb", "0")
+                if rows_q is not None:
+                    ixd.close()
+
         for dtype in ("f32", "f16"):
             code = 0 if dtype == "f32" else 1
             ix = m.sparse_index(W, dtype, n_vocab=V)
@@ -218,6 +313,9 @@ def main():
                 ix.remove(half)
                 for nq in (1, 64):
                     cell(f"nq {nq:2d}  plain search after removing {len(half)} rows (masked kernel)", lambda: search(nq, 10))
+
+            if "inverted" in sections:
+                inverted_section(dtype, ix, d_ids, d_sc)
 
             m_qb = None
             if "search" in sections:
