@@ -5,8 +5,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <vector>
 
 #include "hybrid.h"
 #include "search_kernels.h"
@@ -21,8 +19,6 @@ const char *const SCORES_NAMES[4][2] = {{"index_scores_f32", "index_scores_f32_m
                                         {"index_scores_i8", "index_scores_i8_masked"}, {"index_scores_b1", "index_scores_b1_masked"}};
 const char *const SCAN_NAMES[2][2] = {{"sparse_hybrid_scan_f32", "sparse_hybrid_scan_f32_masked"}, {"sparse_hybrid_scan_f16", "sparse_hybrid_scan_f16_masked"}};
 
-size_t mask_words(long long rows) { return (size_t)((rows + 31) / 32); }
-
 }  // namespace
 
 int Hybrid::check(const Index &d, const SparseIndex &sp, int nq, bool have_ptrs, int kq, float w_dense, float w_sparse, const void *allow,
@@ -32,8 +28,8 @@ int Hybrid::check(const Index &d, const SparseIndex &sp, int nq, bool have_ptrs,
     if (k < 1 || k > SparseIndex::MAX_K) { err = "k must be 1 .. 256"; return -2; }
     if (kq < 1 || kq > SparseIndex::MAX_TERMS) { err = "kq must be 1 .. 256"; return -2; }
     if (!std::isfinite(w_dense) || !std::isfinite(w_sparse)) { err = "w_dense and w_sparse must be finite"; return -2; }
-    if (allow && (long long)n_words < (long long)mask_words(sp.size())) {
-        err = "the allow-list has " + std::to_string(n_words) + " words, indexes of " + std::to_string(sp.size()) + " rows need " + std::to_string(mask_words(sp.size()));
+    if (allow && (long long)n_words < (long long)live_words(sp.size())) {
+        err = "the allow-list has " + std::to_string(n_words) + " words, indexes of " + std::to_string(sp.size()) + " rows need " + std::to_string(live_words(sp.size()));
         return -2;
     }
     if (nq < 0 || (nq > 0 && !have_ptrs)) { err = "n_queries >= 0 and query / result pointers required"; return -2; }
@@ -50,7 +46,7 @@ int Hybrid::reserve(Index &d, SparseIndex &sp, int n_rows, int n_queries, int k,
     const size_t ld = hybrid_ld(rows);
     // a chunk's matrix is at most HYBRID_SCORES_MAX, or one query's scores where those alone exceed it; never more than every query's
     const size_t bytes = std::min((size_t)std::min(n_queries, Index::QCHUNK) * ld * 4, std::max(HYBRID_SCORES_MAX, ld * 4));
-    if (!sp.grow(sp.hyb_scores_, bytes, err) || !sp.grow(sp.hyb_mask_, mask_words(rows) * 4, err)) return -3;
+    if (!sp.grow(sp.hyb_scores_, bytes, err) || !sp.grow(sp.hyb_mask_, live_words(rows) * 4, err)) return -3;
     return 0;
 }
 
@@ -63,7 +59,7 @@ int Hybrid::search_device(Index &d, SparseIndex &sp, int nq, const float *d_q, i
     if (!d.eng_->op_begin(s, d.busy_, od, err) || !sp.eng_->op_begin(s, sp.busy_, os, err)) return -3;
     const int n = sp.n_;
     const int hc = hybrid_chunk_queries(n, nq, sp.eng_->options().hybrid_chunk_queries);
-    const size_t ld = hybrid_ld(n), words = mask_words(n);
+    const size_t ld = hybrid_ld(n), words = live_words(n);
     const bool masked = n > 0 && (d.live_ || sp.live_ || d_allow);
     if (!sp.grow_search(n, hc, k, err) || !d.grow_queries(hc, err) || !sp.grow(sp.hyb_scores_, (size_t)hc * ld * 4, err) ||
         (masked && !sp.grow(sp.hyb_mask_, words * 4, err))) return -3;
@@ -98,10 +94,7 @@ int Hybrid::search_device(Index &d, SparseIndex &sp, int nq, const float *d_q, i
         a.live = mask; a.allow = nullptr;
         a.dscores = sp.hyb_scores_.as<float>(); a.ld = ld; a.w_dense = w_dense; a.w_sparse = w_sparse;
         sp.eng_->timed_launch(SCAN_NAMES[sp.dtype_][masked], 0.0, s, [&] { launch_sparse_hybrid_scan(sp.dtype_, a, geo.lds, s); });
-        MergeArgs m;
-        m.ws_s = sp.ws_s_.as<float>(); m.ws_i = sp.ws_i_.as<int>(); m.n_cand = geo.n_slices * k; m.k = k; m.L = merge_L(k);
-        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
-        sp.eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+        sp.enqueue_merge(c, geo.n_slices * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -3);
     return d.eng_->op_end(od, err) && sp.eng_->op_end(os, err) ? 0 : -3;
@@ -112,18 +105,14 @@ int Hybrid::search_device_to_host(Index &d, SparseIndex &sp, int nq, const float
     if (nq <= 0) return 0;
     DeviceGuard g(sp.eng_->device());
     hipStream_t s = sp.stream_;
-    std::vector<int32_t> hid((size_t)nq * k);
-    std::vector<float> hsc((size_t)nq * k);
-    if (!sp.grow(sp.out_ids_, hid.size() * 4, err) || !sp.grow(sp.out_scores_, hsc.size() * 4, err)) return -3;
+    HostResults res((size_t)nq * k);
+    if (!sp.grow(sp.out_ids_, res.ids.size() * 4, err) || !sp.grow(sp.out_scores_, res.scores.size() * 4, err)) return -3;
     if (search_device(d, sp, nq, d_q, kq, d_qids, d_qw, w_dense, w_sparse, nullptr, k, sp.out_ids_.as<int32_t>(), sp.out_scores_.as<float>(), s, err) != 0) {
         (void)hipStreamSynchronize(s);
         return -3;
     }
-    HIP_OK(hipMemcpyAsync(hid.data(), sp.out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, s), err, -3);
-    HIP_OK(hipMemcpyAsync(hsc.data(), sp.out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, s), err, -3);
-    HIP_OK(hipStreamSynchronize(s), err, -3);
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
+    if (!sp.results_to_host(s, 0, res.ids.size(), res, err)) return -3;
+    res.deliver(ids, scores);
     return 0;
 }
 
@@ -135,9 +124,8 @@ int Hybrid::search_host(Index &d, SparseIndex &sp, int nq, const float *q, int k
     hipStream_t s = sp.stream_;
     // (the allow-list goes into the sparse index's buffer on its stream, behind whatever is queued on it)
     const uint32_t *d_allow = nullptr;
-    if (!sp.upload_allow(allow, d_allow, err)) return -3;
-    std::vector<int32_t> hid((size_t)nq * k);
-    std::vector<float> hsc((size_t)nq * k);
+    if (!sp.upload_allow(allow, s, d_allow, err)) return -3;
+    HostResults res((size_t)nq * k);
     const int dim = d.dim_;
     for (int c0 = 0; c0 < nq; c0 += Index::QCHUNK) {
         const int c = std::min(Index::QCHUNK, nq - c0);
@@ -156,12 +144,9 @@ int Hybrid::search_host(Index &d, SparseIndex &sp, int nq, const float *q, int k
             (void)hipStreamSynchronize(s);
             return -3;
         }
-        HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, sp.out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, s), err, -3);
-        HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, sp.out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, s), err, -3);
-        HIP_OK(hipStreamSynchronize(s), err, -3);
+        if (!sp.results_to_host(s, (size_t)c0 * k, (size_t)c * k, res, err)) return -3;
     }
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
+    res.deliver(ids, scores);
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // index.cpp — the host side of the embedding index (search.h): storage and its growth, add, the search, rescore, two-stage and
-// probed routes, reading rows back, the live bits, compaction and the file form (the partition itself: index_partition.cpp).  Every kernel is in search.hip and reached through search_kernels.h.
+// probed routes, reading rows back, compaction, the file form (partition: index_partition.cpp; live bits, remove, stream and event: index_frame.h; file frame: index_io.h).  Kernels: search.hip behind search_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "index_io.h"
 #include "search.h"
 #include "search_kernels.h"
 
@@ -93,33 +94,22 @@ Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
     if (dtype < 0 || dtype > 3) { err = "dtype must be 0 (f32), 1 (f16), 2 (i8) or 3 (b1)"; return nullptr; }
     DeviceGuard g(eng->device());
     Index *ix = new Index;
-    ix->eng_ = eng;
     ix->dim_ = dim;
     ix->dtype_ = dtype;
     // the score kernel's k-step (a 16-byte load per lane)
     ix->dpad_ = index_dpad(dtype, dim);
     ix->row_bytes_ = (size_t)index_row_bytes(dtype, ix->dpad_);
     ix->qrow_bytes_ = (size_t)index_row_bytes(query_form(dtype), ix->dpad_);
-    const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
+    if (!ix->open(eng, "index", err)) { delete ix; return nullptr; }
     search_kernels_init();
     return ix;
 }
 
 Index::~Index() {
     DeviceGuard g(eng_ ? eng_->device() : 0);
-    if (busy_) { (void)hipEventSynchronize(busy_); (void)hipEventDestroy(busy_); }
-    if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
+    close();
     if (rows_) (void)hipFree(rows_);
     if (rscale_) (void)hipFree(rscale_);
-    if (live_) (void)hipFree(live_);
-}
-
-bool Index::grow(DevBuf &b, size_t bytes, std::string &err) {
-    if (bytes <= b.bytes) return true;
-    HIP_OK(hipEventSynchronize(busy_), err, false);          // (what is queued may still read the old buffer)
-    return b.ensure(bytes, err);
 }
 
 bool Index::grow_rows(int n_rows, std::string &err) {
@@ -137,26 +127,20 @@ bool Index::grow_rows(int n_rows, std::string &err) {
     }
     // (an index with removed rows: the live words grow with the rows, so that an add within the capacity never allocates)
     uint32_t *lv = nullptr;
-    const size_t lw = live_words(cap);
-    const char *failed = nullptr;
-    if (live_ && hipMalloc(&lv, lw * 4) != hipSuccess) failed = "hipMalloc (index live words) failed";
-    else if (n_ > 0 && hipMemcpy(p, rows_, (size_t)n_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) failed = "hipMemcpy (index rows) failed";
-    else if (n_ > 0 && sc && hipMemcpy(sc, rscale_, (size_t)n_ * 4, hipMemcpyDeviceToDevice) != hipSuccess) failed = "hipMemcpy (index row scales) failed";
-    else if (lv && (hipMemset(lv, 0, lw * 4) != hipSuccess ||
-                    hipMemcpy(lv, live_h_.data(), live_words(n_) * 4, hipMemcpyHostToDevice) != hipSuccess)) failed = "hipMemcpy (index live words) failed";
-    if (failed) {
+    bool ok = live_for_capacity(cap, lv, err);
+    if (ok && n_ > 0 && hipMemcpy(p, rows_, (size_t)n_ * row_bytes, hipMemcpyDeviceToDevice) != hipSuccess) { err = "hipMemcpy (index rows) failed"; ok = false; }
+    if (ok && n_ > 0 && sc && hipMemcpy(sc, rscale_, (size_t)n_ * 4, hipMemcpyDeviceToDevice) != hipSuccess) { err = "hipMemcpy (index row scales) failed"; ok = false; }
+    if (!ok) {
         (void)hipFree(p);
         if (sc) (void)hipFree(sc);
         if (lv) (void)hipFree(lv);
-        err = failed;
         return false;
     }
     if (rows_) (void)hipFree(rows_);
     if (rscale_) (void)hipFree(rscale_);
-    if (live_) { (void)hipFree(live_); live_h_.resize(lw, 0u); }
+    adopt_live(lv, cap);
     rows_ = p;
     rscale_ = sc;
-    live_ = lv;
     cap_ = cap;
     return true;
 }
@@ -191,7 +175,7 @@ int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &er
     if (live_) launch_live_set_range(live_, n_, n, s);
     HIP_OK(hipGetLastError(), err, -1);
     if (!eng_->op_end(op, err)) return -1;
-    if (live_) live_set_range_host(live_h_, n_, n);
+    if (live_) bits_.set_range(n_, n);
     const int first = n_;
     n_ += n;
     return first;
@@ -222,12 +206,6 @@ int Index::add_host(int n, const float *rows, std::string &err) {
 void Index::enqueue_queries(int nq, const float *d_q, hipStream_t s) {
     const int form = query_form(dtype_);
     eng_->timed_launch(FORMS[form].ingest, 0.0, s, [&] { launch_ingest(form, d_q, qbuf_.p, qscale_.as<float>(), nq, dim_, dpad_, s); });
-}
-
-void Index::enqueue_merge(int nq, int n_cand, int k, int32_t *d_ids, float *d_scores, hipStream_t s) {
-    MergeArgs m;
-    m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k); m.ids = d_ids; m.scores = d_scores;
-    eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, nq, s); });
 }
 
 void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow) {
@@ -267,8 +245,7 @@ int Index::search_device(int nq, const float *d_q, int k, int32_t *d_ids, float 
 // before the error returns; ids and scores are written only on success.
 int Index::host_route(int nq, const float *q, bool q_on_device, bool wait, int k, int32_t *ids, float *scores, std::string &err,
                       const std::function<int(int, int, const float *, int32_t *, float *)> &device_form) {
-    std::vector<int32_t> hid((size_t)nq * k);
-    std::vector<float> hsc((size_t)nq * k);
+    HostResults res((size_t)nq * k);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         const float *dq = q + (size_t)c0 * dim_;
@@ -280,12 +257,9 @@ int Index::host_route(int nq, const float *q, bool q_on_device, bool wait, int k
             dq = stage_.as<float>();
         }
         if (device_form(c0, c, dq, out_ids_.as<int32_t>(), out_scores_.as<float>()) != 0) { (void)hipStreamSynchronize(stream_); return -1; }
-        HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
-        HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -1);
-        HIP_OK(hipStreamSynchronize(stream_), err, -1);
+        if (!results_to_host(stream_, (size_t)c0 * k, (size_t)c * k, res, err)) return -1;
     }
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
+    res.deliver(ids, scores);
     return 0;
 }
 
@@ -298,17 +272,6 @@ int Index::search_to_host(int nq, const float *q, bool q_on_device, int k, int32
     return host_route(nq, q, q_on_device, false, k, ids, scores, err, [&](int, int c, const float *d_q, int32_t *d_ids, float *d_scores) {
         return search_device(c, d_q, k, d_ids, d_scores, stream_, err, d_allow);
     });
-}
-
-// a host allow-list (null, or an empty index: d_allow stays null) into allow_, on s behind whatever is queued on the index; the
-// searches that read it follow on s
-bool Index::upload_allow(const uint32_t *allow, hipStream_t s, const uint32_t *&d_allow, std::string &err) {
-    if (!allow || n_ == 0) return true;
-    if (!grow(allow_, live_words(n_) * 4, err)) return false;
-    HIP_OK(hipStreamWaitEvent(s, busy_, 0), err, false);
-    HIP_OK(hipMemcpyAsync(allow_.p, allow, live_words(n_) * 4, hipMemcpyHostToDevice, s), err, false);
-    d_allow = allow_.as<uint32_t>();
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -458,93 +421,21 @@ int Index::get_rows(int n, const int32_t *ids, float *rows, std::string &err) {
 // ------------------------------------------------------------------------------------------------
 void Index::truncate(int n) {
     if (n < 0 || n >= n_) return;
-    // (the mirror keeps its bits at and beyond size zero; the device words of the dropped rows stay as they are: a search
-    // ignores them, and the add that reuses those rows sets them)
-    if (live_) {
-        for (long long r = n; r < n_;) {
-            const int b = (int)(r & 31);
-            live_h_[(size_t)(r >> 5)] &= b ? (1u << b) - 1u : 0u;
-            r += 32 - b;
-        }
-        n_removed_ = n;
-        for (size_t w = 0; w < live_words(n); ++w) n_removed_ -= __builtin_popcount(live_h_[w]);
-    }
+    if (live_) bits_.truncate(n_, n);                        // (live_bits.h: the mirror's side of the invariant; the device words stay)
     n_ = n;
 }
 
-// the bitmap of an index that had none: every row live
-bool Index::make_live(std::string &err) {
-    if (live_) return true;
-    const size_t lw = live_words(cap_);
-    HIP_OK(hipEventSynchronize(busy_), err, false);
-    HIP_OK(hipMalloc((void **)&live_, std::max<size_t>(lw, 1) * 4), err, false);
-    live_h_.assign(lw, 0u);
-    if (n_ > 0) live_set_range_host(live_h_, 0, n_);
-    n_removed_ = 0;
-    if (hipMemcpy(live_, live_h_.data(), lw * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        drop_live();
-        err = "hipMemcpy (index live words) failed";
-        return false;
-    }
-    return true;
-}
-
-void Index::drop_live() {
-    if (live_) (void)hipFree(live_);
-    live_ = nullptr;
-    live_h_.clear();
-    n_removed_ = 0;
-}
-
-// mirror words [w0, w1) -> device, on the index's stream behind whatever is queued; blocking
-bool Index::upload_live(size_t w0, size_t w1, std::string &err) {
-    if (w1 <= w0) return true;
-    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
-    HIP_OK(hipMemcpyAsync(live_ + w0, live_h_.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, stream_), err, false);
-    HIP_OK(hipEventRecord(busy_, stream_), err, false);
-    HIP_OK(hipStreamSynchronize(stream_), err, false);
-    return true;
-}
-
 int Index::remove(int n, const int32_t *ids, std::string &err) {
-    if (n < 0 || (n > 0 && !ids)) { err = "remove: n >= 0 and an id pointer required"; return -1; }
-    for (int i = 0; i < n; ++i)
-        if (ids[i] < 0 || ids[i] >= n_) { err = "remove: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(n_) + ")"; return -1; }
-    if (n == 0) return 0;
-    DeviceGuard g(eng_->device());
-    if (!make_live(err)) return -1;
     std::vector<int32_t> fresh;                          // the ids this call removes (repeats and removed rows left out)
-    size_t w0 = SIZE_MAX, w1 = 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t w = (size_t)ids[i] >> 5;
-        const uint32_t bit = 1u << (ids[i] & 31);
-        if (!(live_h_[w] & bit)) continue;
-        live_h_[w] &= ~bit;
-        fresh.push_back(ids[i]);
-        w0 = std::min(w0, w);
-        w1 = std::max(w1, w + 1);
-    }
-    if (!fresh.empty() && !upload_live(w0, w1, err)) {
-        for (int32_t id : fresh) live_h_[(size_t)id >> 5] |= 1u << (id & 31);      // (the mirror as it was)
-        return -1;
-    }
-    n_removed_ += (int)fresh.size();
-    return (int)fresh.size();
+    return remove_rows(n, ids, cap_, fresh, err) == Removed::ok ? (int)fresh.size() : -1;
 }
 
 int Index::compact(int32_t *old_ids, std::string &err) {
     DeviceGuard g(eng_->device());
     HIP_OK(hipEventSynchronize(busy_), err, -1);
-    if (n_removed_ == 0) {
-        if (old_ids) for (int i = 0; i < n_; ++i) old_ids[i] = i;
-        drop_live();
-        return n_;
-    }
-    const int nl = n_ - n_removed_;
-    std::vector<int32_t> map((size_t)nl);
-    int j = 0;
-    for (int r = 0; r < n_; ++r)
-        if (live_h_[(size_t)r >> 5] >> (r & 31) & 1u) map[(size_t)j++] = r;
+    if (bits_.n_removed == 0) return compact_nothing(old_ids);
+    const std::vector<int32_t> map = bits_.kept(n_);
+    const int nl = (int)map.size();
     const size_t row_bytes = row_bytes_;
     void *p = nullptr;
     float *sc = nullptr;
@@ -590,32 +481,8 @@ int Index::compact(int32_t *old_ids, std::string &err) {
     return nl;
 }
 
-namespace {
-
-// device memory <-> file in pieces of at most 64 MiB through a host buffer
-constexpr size_t FILE_PIECE = (size_t)64 << 20;
-
-bool device_to_file(FILE *f, const void *d, size_t bytes, std::vector<char> &buf, std::string &err) {
-    for (size_t o = 0; o < bytes; o += FILE_PIECE) {
-        const size_t c = std::min(FILE_PIECE, bytes - o);
-        if (buf.size() < c) buf.resize(c);
-        HIP_OK(hipMemcpy(buf.data(), (const char *)d + o, c, hipMemcpyDeviceToHost), err, false);
-        if (fwrite(buf.data(), 1, c, f) != c) { err = "write failed"; return false; }
-    }
-    return true;
-}
-
-bool file_to_device(FILE *f, void *d, size_t bytes, std::vector<char> &buf, std::string &err) {
-    for (size_t o = 0; o < bytes; o += FILE_PIECE) {
-        const size_t c = std::min(FILE_PIECE, bytes - o);
-        if (buf.size() < c) buf.resize(c);
-        if (fread(buf.data(), 1, c, f) != c) { err = "read failed"; return false; }
-        HIP_OK(hipMemcpy((char *)d + o, buf.data(), c, hipMemcpyHostToDevice), err, false);
-    }
-    return true;
-}
-
-}  // namespace
+// device memory <-> file in pieces of at most 64 MiB through a host buffer (index_io.h)
+static constexpr size_t FILE_PIECE = (size_t)64 << 20;
 
 bool Index::save(const char *path, std::string &err) {
     if (!path || !*path) { err = "a path is required"; return false; }
@@ -625,21 +492,13 @@ bool Index::save(const char *path, std::string &err) {
     h.dtype = (uint32_t)dtype_; h.dim = (uint32_t)dim_; h.dpad = (uint32_t)dpad_; h.n_rows = (uint32_t)n_; h.has_live = live_ ? 1u : 0u;
     unsigned char hdr[INDEX_HEADER_BYTES];
     index_header_write(h, hdr);
-    const std::string tmp = std::string(path) + ".tmp";
-    FILE *f = fopen(tmp.c_str(), "wb");
-    if (!f) { err = "cannot write '" + tmp + "'"; return false; }
-    std::vector<char> buf;
-    // (the live words come from the mirror: its bits at and beyond size are zero)
-    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && device_to_file(f, rows_, (size_t)n_ * row_bytes_, buf, err) &&
-              (!FORMS[dtype_].has_rscale || device_to_file(f, rscale_, (size_t)n_ * 4, buf, err)) &&
-              (!live_ || fwrite(live_h_.data(), 4, live_words(n_), f) == live_words(n_));
-    ok = (fclose(f) == 0) && ok;
-    if (ok && rename(tmp.c_str(), path) != 0) ok = false;
-    if (!ok) {
-        (void)::remove(tmp.c_str());
-        if (err.empty()) err = "cannot write '" + std::string(path) + "'";
-    }
-    return ok;
+    return write_atomically(path, err, [&](FILE *f) {
+        std::vector<char> buf;
+        // (the live words come from the mirror: its bits at and beyond size are zero)
+        return fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && device_to_file(f, rows_, (size_t)n_ * row_bytes_, FILE_PIECE, buf, err) &&
+               (!FORMS[dtype_].has_rscale || device_to_file(f, rscale_, (size_t)n_ * 4, FILE_PIECE, buf, err)) &&
+               (!live_ || fwrite(bits_.words.data(), 4, live_words(n_), f) == live_words(n_));
+    });
 }
 
 bool Index::load_rows(FILE *f, const IndexFileHeader &h, std::string &err) {
@@ -648,18 +507,13 @@ bool Index::load_rows(FILE *f, const IndexFileHeader &h, std::string &err) {
     const int n = (int)h.n_rows;
     if (!grow_rows(n, err)) return false;
     std::vector<char> buf;
-    if (!file_to_device(f, rows_, (size_t)n * row_bytes_, buf, err)) return false;
-    if (FORMS[dtype_].has_rscale && !file_to_device(f, rscale_, (size_t)n * 4, buf, err)) return false;
+    if (!file_to_device(f, rows_, (size_t)n * row_bytes_, FILE_PIECE, buf, err)) return false;
+    if (FORMS[dtype_].has_rscale && !file_to_device(f, rscale_, (size_t)n * 4, FILE_PIECE, buf, err)) return false;
     n_ = n;
     if (!h.has_live) return true;
     std::vector<uint32_t> words(live_words(n));
     if (fread(words.data(), 4, words.size(), f) != words.size()) { n_ = 0; err = "read failed"; return false; }
-    if (n & 31 && !words.empty() && (words.back() >> (n & 31)) != 0) { n_ = 0; err = "live bits beyond the last row"; return false; }
-    if (!make_live(err)) { n_ = 0; return false; }
-    std::copy(words.begin(), words.end(), live_h_.begin());
-    for (uint32_t w : words) n_removed_ += 32 - __builtin_popcount(w);
-    n_removed_ -= (int)(words.size() * 32 - (size_t)n);          // (the last word's bits beyond n are zero, not removed rows)
-    if (!upload_live(0, words.size(), err)) { drop_live(); n_ = 0; return false; }
+    if (!install_live(words.data(), cap_, err)) { n_ = 0; return false; }
     return true;
 }
 

@@ -12,6 +12,7 @@
 
 #include <sys/stat.h>
 
+#include "index_io.h"
 #include "partition.h"
 #include "search.h"
 #include "search_kernels.h"
@@ -106,18 +107,10 @@ bool Index::save_partition(const char *path, std::string &err) {
     h.dim = (uint32_t)dim_; h.n_lists = (uint32_t)n_lists(); h.n_part = (uint32_t)n_part_;
     unsigned char hdr[INDEX_HEADER_BYTES];
     partition_header_write(h, hdr);
-    const std::string tmp = std::string(path) + ".tmp";
-    FILE *f = fopen(tmp.c_str(), "wb");
-    if (!f) { err = "cannot write '" + tmp + "'"; return false; }
-    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && fwrite(cent_h_.data(), 4, cent_h_.size(), f) == cent_h_.size() &&
-              fwrite(list_of_.data(), 4, (size_t)n_part_, f) == (size_t)n_part_;
-    ok = (fclose(f) == 0) && ok;
-    if (ok && rename(tmp.c_str(), path) != 0) ok = false;
-    if (!ok) {
-        (void)::remove(tmp.c_str());
-        err = "cannot write '" + std::string(path) + "'";
-    }
-    return ok;
+    return write_atomically(path, err, [&](FILE *f) {
+        return fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && fwrite(cent_h_.data(), 4, cent_h_.size(), f) == cent_h_.size() &&
+               fwrite(list_of_.data(), 4, (size_t)n_part_, f) == (size_t)n_part_;
+    });
 }
 
 int Index::load_partition(const char *path, std::string &err) {
@@ -181,7 +174,7 @@ int Index::kmeans(int n_lists, int n_iter, float *centroids, std::string &err) {
         if (cent->add_device(n_lists, d_cent.as<float>(), stream_, err) < 0 || !assign_rows(*cent, list_of, err)) return -1;
         if (live_)
             for (int r = 0; r < n_; ++r)
-                if (!(live_h_[(size_t)r >> 5] >> (r & 31) & 1u)) list_of[(size_t)r] = -1;
+                if (!bits_.test(r)) list_of[(size_t)r] = -1;
         if (!upload_tables(list_of, n_lists, offsets, order, err)) return -1;
         KmeansArgs a;
         a.rows = rows_; a.rscale = rscale_; a.offsets = offsets.as<int32_t>(); a.order = order.as<int32_t>();

@@ -4,10 +4,10 @@
 // instead of storing: index_topk_kernel keeps a top-k per (query, slice of rows) in LDS, topk_merge_kernel merges the
 // slices' lists per query.  The score matrix never reaches HBM.
 //
-// Removed rows: from the first remove() on, the index keeps one bit per row (set = live) in device words [ceil(cap / 32)] and
-// in a host mirror; bits at and beyond size() are zero in the mirror and ignored on the device.  A search then (or with an
-// allow-list, a second bitmap of the same shape from the caller) runs the masked instantiation of index_topk_kernel.  An
-// index that never saw a removal has no bitmap and launches what it always did.
+// Removed rows: from the first remove() on, the index keeps one bit per row (set = live) in device words and in a host mirror
+// (index_frame.h; the invariant: live_bits.h).  A search then (or with an allow-list, a second bitmap of the same shape from
+// the caller) runs the masked instantiation of index_topk_kernel.  An index that never saw a removal has no bitmap and
+// launches what it always did.
 //
 // Rescoring: index_rescore_kernel scores each query against the rows its own candidate list names (the same ScoreBlock as
 // the search, hence the same score bits) into [nq][n_cand] lists in the workspace, and topk_merge_kernel selects from them.
@@ -33,20 +33,11 @@
 
 #include "engine.h"
 #include "index_file.h"
+#include "index_frame.h"
 
 namespace bert_hip {
 
-// the index's device for the length of a call (index.cpp, index_partition.cpp)
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        (void)hipSetDevice(d);
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-class Index {
+class Index : private IndexFrame {
 public:
     static constexpr int MAX_K = 256, MAX_DIM = INDEX_MAX_DIM;
     static constexpr int QCHUNK = 4096;                  // queries per internal pass (workspace bound)
@@ -58,7 +49,7 @@ public:
     ~Index();
 
     int size() const { return n_; }
-    int n_live() const { return n_ - n_removed_; }
+    int n_live() const { return n_ - bits_.n_removed; }
     int dim() const { return dim_; }
     int dtype() const { return dtype_; }
     hipStream_t stream() const { return stream_; }
@@ -134,10 +125,8 @@ private:
     friend struct Hybrid;                               // hybrid.h: a search over this index and a sparse index together
     Index() = default;
     bool grow_rows(int n_rows, std::string &err);
-    bool grow(DevBuf &b, size_t bytes, std::string &err);
     void enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow);
     void enqueue_queries(int nq, const float *d_q, hipStream_t s);
-    void enqueue_merge(int nq, int n_cand, int k, int32_t *d_ids, float *d_scores, hipStream_t s);
     int host_route(int nq, const float *q, bool q_on_device, bool wait, int k, int32_t *ids, float *scores, std::string &err,
                    const std::function<int(int, int, const float *, int32_t *, float *)> &device_form);
     bool grow_queries(int nqc, std::string &err);
@@ -145,25 +134,16 @@ private:
     bool assign_rows(Index &cent, std::vector<int32_t> &list_of, std::string &err);
     bool upload_lists(const std::vector<int32_t> &list_of, int n_lists, std::string &err);
     bool install_partition(std::unique_ptr<Index> cent, const float *centroids, std::vector<int32_t> &&list_of, std::string &err);
-    bool upload_allow(const uint32_t *allow, hipStream_t s, const uint32_t *&d_allow, std::string &err);
     void drop_partition();
-    bool make_live(std::string &err);
-    bool upload_live(size_t w0, size_t w1, std::string &err);
-    void drop_live();
 
-    Engine *eng_ = nullptr;
     int dim_ = 0, dtype_ = 0, dpad_ = 0;                // dpad_: elements per stored row
     size_t row_bytes_ = 0, qrow_bytes_ = 0;             // bytes per stored row; per query as the score kernel reads it (b1: i8 codes)
-    int n_ = 0, cap_ = 0;
+    int cap_ = 0;                                       // (the rows themselves, n_, the bitmap, the lists' workspace: index_frame.h)
     void *rows_ = nullptr;                              // [cap_][row_bytes_]
     float *rscale_ = nullptr;                           // i8: [cap_] row scales
-    DevBuf ws_s_, ws_i_, qbuf_;                         // per-(query, slice) lists; the current chunk's queries as stored
+    DevBuf qbuf_;                                       // the current chunk's queries as stored
     DevBuf qscale_;                                     // i8, b1: the current chunk's query scales
     DevBuf cand_i_, cand_s_, cand_in_;                  // two-stage search: the coarse stage's lists; host rescore: the caller's ids
-    // removed rows: device words [ceil(cap_ / 32)] (null until the first remove) and their host mirror of the same length
-    uint32_t *live_ = nullptr;
-    std::vector<uint32_t> live_h_;
-    int n_removed_ = 0;
     // partition: the centroids as an index (null: none) and on the host; the list of each row below n_part_ (the rows behind
     // are the tail); the list tables on the device; the probed lists of the current chunk; exported rows and their lists
     std::unique_ptr<Index> cent_;
@@ -171,11 +151,7 @@ private:
     std::vector<int32_t> list_of_;
     int n_part_ = 0;
     DevBuf offsets_, order_, probe_i_, probe_s_, export_, assign_i_, assign_s_;
-    DevBuf allow_;                                      // host route: the caller's allow-list on the device
-    DevBuf stage_, out_ids_, out_scores_, scratch_;     // host routes: f32 rows / queries, results; the text routes' embeddings
-    hipStream_t stream_ = nullptr;                      // the host routes' stream
-    // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
-    hipEvent_t busy_ = nullptr;
+    DevBuf stage_, scratch_;                            // host routes: f32 rows / queries; the text routes' embeddings
 };
 
 // How a search cuts a chunk of nq queries with this k over n_rows rows into workgroups of index_topk_kernel — what plan() of

@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "live_bits.h"
+
 namespace bert_hip {
 
 constexpr int QT = 32;                  // queries per workgroup tile: the M side of one 32 x 32 MFMA block
@@ -127,15 +129,6 @@ void launch_ingest(int dtype, const float *src, void *dst, float *scales, int n,
 void launch_gather(const void *src, void *dst, const float *sscale, float *dscale, const int32_t *old_ids, int n, size_t row_bytes, hipStream_t s);
 // live bits of rows [first, first + n) := 1
 void launch_live_set_range(uint32_t *live, int first, int n, hipStream_t s);
-// the same on a host mirror of the words, and the words that n rows take: shared by the three indexes that keep such a bitmap
-inline void live_set_range_host(std::vector<uint32_t> &live, int first, int n) {
-    for (long long r = first; r < (long long)first + n;) {
-        const size_t w = (size_t)(r >> 5);
-        const int b = (int)(r & 31), c = (int)std::min<long long>(32 - b, (long long)first + n - r);
-        live[w] |= (c == 32 ? ~0u : ((1u << c) - 1u) << b);
-        r += c;
-    }
-}
-inline size_t live_words(long long rows) { return (size_t)((rows + 31) / 32); }
+// (the same on a host mirror of the words, and the words that n rows take: live_set_range_host and live_words of live_bits.h)
 
 }  // namespace bert_hip

@@ -1,6 +1,6 @@
 // sparse_index.cpp — the host side of the sparse index (sparse_index.h): storage and its growth, add, the search and its chunks,
-// rescoring, reading rows back, the checks of the host forms, the live bits, compaction and the file form.  Every kernel is in sparse_index.hip (and the merge in search.hip) and reached
-// through sparse_index_kernels.h / search_kernels.h.  The postings and the launches of the inverted search are sparse_postings.cpp; the
+// rescoring, reading rows back, the checks of the host forms, compaction and the file form (live bits, remove, stream and event:
+// index_frame.h; file frame: index_io.h).  Kernels: sparse_index.hip behind sparse_index_kernels.h (the merge: search.hip).  The postings and the launches of the inverted search are sparse_postings.cpp; the
 // searches here take `inverted` and share their checks, chunking and copies with it.
 #include <hip/hip_runtime.h>
 
@@ -13,7 +13,8 @@
 
 #include <sys/types.h>
 
-#include "search.h"
+#include "index_io.h"
+#include "search_kernels.h"
 #include "sparse_index.h"
 
 namespace bert_hip {
@@ -88,31 +89,20 @@ SparseIndex *SparseIndex::create(Engine *eng, int n_vocab, int width, int dtype,
     if (dtype == 1 && n_vocab > 65536) { err = "dtype 1 stores u16 ids: n_vocab must be at most 65536"; return nullptr; }
     DeviceGuard g(eng->device());
     SparseIndex *ix = new SparseIndex;
-    ix->eng_ = eng;
     ix->n_vocab_ = n_vocab;
     ix->width_ = width;
     ix->dtype_ = dtype;
-    const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
+    if (!ix->open(eng, "sparse index", err)) { delete ix; return nullptr; }
     sparse_index_kernels_init();
     return ix;
 }
 
 SparseIndex::~SparseIndex() {
     DeviceGuard g(eng_ ? eng_->device() : 0);
-    if (busy_) { (void)hipEventSynchronize(busy_); (void)hipEventDestroy(busy_); }
-    if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
+    close();
     if (sids_) (void)hipFree(sids_);
     if (sweights_) (void)hipFree(sweights_);
     if (counts_) (void)hipFree(counts_);
-    if (live_) (void)hipFree(live_);
-}
-
-bool SparseIndex::grow(DevBuf &b, size_t bytes, std::string &err) {
-    if (bytes <= b.bytes) return true;
-    HIP_OK(hipEventSynchronize(busy_), err, false);          // (what is queued may still read the old buffer)
-    return b.ensure(bytes, err);
 }
 
 // (whole blocks: a block's layout does not depend on the capacity, so growth is three plain copies)
@@ -128,28 +118,24 @@ bool SparseIndex::grow_rows(int n_rows, std::string &err) {
     const char *failed = nullptr;
     // (an index with removed rows: the live words grow with the rows, so that an add within the capacity never allocates)
     uint32_t *lv = nullptr;
-    const size_t lw = live_words(cap);
     if (hipMalloc(&pi, nb * block_elems * ib) != hipSuccess || hipMalloc(&pw, nb * block_elems * ib) != hipSuccess ||
-        hipMalloc((void **)&pc, (size_t)cap * 4) != hipSuccess || (live_ && hipMalloc((void **)&lv, lw * 4) != hipSuccess)) failed = "hipMalloc (sparse index rows) failed";
+        hipMalloc((void **)&pc, (size_t)cap * 4) != hipSuccess) failed = "hipMalloc (sparse index rows) failed";
     else if (n_ > 0 && (hipMemcpy(pi, sids_, used * block_elems * ib, hipMemcpyDeviceToDevice) != hipSuccess ||
                         hipMemcpy(pw, sweights_, used * block_elems * ib, hipMemcpyDeviceToDevice) != hipSuccess ||
                         hipMemcpy(pc, counts_, (size_t)n_ * 4, hipMemcpyDeviceToDevice) != hipSuccess)) failed = "hipMemcpy (sparse index rows) failed";
-    else if (lv && (hipMemset(lv, 0, lw * 4) != hipSuccess ||
-                    hipMemcpy(lv, live_h_.data(), live_words(n_) * 4, hipMemcpyHostToDevice) != hipSuccess)) failed = "hipMemcpy (sparse index live words) failed";
-    if (failed) {
+    if (failed) err = failed;
+    if (failed || !live_for_capacity(cap, lv, err)) {
         (void)hipGetLastError();
         if (pi) (void)hipFree(pi);
         if (pw) (void)hipFree(pw);
         if (pc) (void)hipFree(pc);
-        if (lv) (void)hipFree(lv);
-        err = failed;
         return false;
     }
     if (sids_) (void)hipFree(sids_);
     if (sweights_) (void)hipFree(sweights_);
     if (counts_) (void)hipFree(counts_);
-    if (live_) { (void)hipFree(live_); live_h_.resize(lw, 0u); }
-    sids_ = pi; sweights_ = pw; counts_ = pc; live_ = lv;
+    adopt_live(lv, cap);
+    sids_ = pi; sweights_ = pw; counts_ = pc;
     cap_ = cap;
     return true;
 }
@@ -189,7 +175,7 @@ int SparseIndex::add_device(int n, int k_in, const int32_t *d_ids, const float *
     if (live_) launch_live_set_range(live_, n_, n, s);
     HIP_OK(hipGetLastError(), err, -3);
     if (!eng_->op_end(op, err)) return -3;
-    if (live_) live_set_range_host(live_h_, n_, n);
+    if (live_) bits_.set_range(n_, n);
     const int first = n_;
     n_ += n;
     return first;
@@ -246,9 +232,7 @@ void SparseIndex::enqueue_chunk(int nq, int kq, const int32_t *d_qids, const flo
     a.live = live_; a.allow = d_allow;
     static const char *const names[2][2] = {{"sparse_index_scan_f32", "sparse_index_scan_f32_masked"}, {"sparse_index_scan_f16", "sparse_index_scan_f16_masked"}};
     eng_->timed_launch(names[dtype_][masked], 0.0, s, [&] { launch_sparse_scan(dtype_, a, g.lds, s); });
-    MergeArgs m;
-    m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = g.n_slices * k; m.k = k; m.L = merge_L(k); m.ids = d_ids; m.scores = d_scores;
-    eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, nq, s); });
+    enqueue_merge(nq, g.n_slices * k, k, d_ids, d_scores, s);
 }
 
 int SparseIndex::search_device(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
@@ -271,15 +255,11 @@ int SparseIndex::search_device(int nq, int kq, const int32_t *d_qids, const floa
 int SparseIndex::search_device_to_host(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *ids, float *scores, std::string &err,
                                        const uint32_t *d_allow, bool inverted) {
     if (inverted && !inverted_ok(err)) return -2;
-    std::vector<int32_t> hid((size_t)nq * k);
-    std::vector<float> hsc((size_t)nq * k);
-    if (!grow(out_ids_, hid.size() * 4, err) || !grow(out_scores_, hsc.size() * 4, err)) return -3;
+    HostResults res((size_t)nq * k);
+    if (!grow(out_ids_, res.ids.size() * 4, err) || !grow(out_scores_, res.scores.size() * 4, err)) return -3;
     if (search_device(nq, kq, d_qids, d_qw, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err, d_allow, inverted) != 0) { (void)hipStreamSynchronize(stream_); return -3; }
-    HIP_OK(hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
-    HIP_OK(hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_), err, -3);
-    HIP_OK(hipStreamSynchronize(stream_), err, -3);
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
+    if (!results_to_host(stream_, 0, res.ids.size(), res, err)) return -3;
+    res.deliver(ids, scores);
     return 0;
 }
 
@@ -290,9 +270,8 @@ int SparseIndex::search_host(int nq, int kq, const int32_t *qids, const float *q
     if (inverted && !inverted_ok(err)) return -2;
     DeviceGuard g(eng_->device());
     const uint32_t *d_allow = nullptr;
-    if (!upload_allow(allow, d_allow, err)) return -3;
-    std::vector<int32_t> hid((size_t)nq * k);
-    std::vector<float> hsc((size_t)nq * k);
+    if (!upload_allow(allow, stream_, d_allow, err)) return -3;
+    HostResults res((size_t)nq * k);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         const size_t half = ((size_t)c * kq * 4 + 15) & ~(size_t)15;
@@ -301,22 +280,10 @@ int SparseIndex::search_host(int nq, int kq, const int32_t *qids, const float *q
         HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
         HIP_OK(hipMemcpyAsync(d, qids + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
         HIP_OK(hipMemcpyAsync(d + half, qw + (size_t)c0 * kq, (size_t)c * kq * 4, hipMemcpyHostToDevice, stream_), err, -3);
-        if (search_device_to_host(c, kq, (const int32_t *)d, (const float *)(d + half), k, hid.data() + (size_t)c0 * k, hsc.data() + (size_t)c0 * k, err, d_allow, inverted) != 0) return -3;
+        if (search_device_to_host(c, kq, (const int32_t *)d, (const float *)(d + half), k, res.ids.data() + (size_t)c0 * k, res.scores.data() + (size_t)c0 * k, err, d_allow, inverted) != 0) return -3;
     }
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
+    res.deliver(ids, scores);
     return 0;
-}
-
-// a host allow-list (null, or an empty index: d_allow stays null) into allow_, on the index's stream behind whatever is queued; the
-// searches that read it follow on that stream
-bool SparseIndex::upload_allow(const uint32_t *allow, const uint32_t *&d_allow, std::string &err) {
-    if (!allow || n_ == 0) return true;
-    if (!grow(allow_, live_words(n_) * 4, err)) return false;
-    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
-    HIP_OK(hipMemcpyAsync(allow_.p, allow, live_words(n_) * 4, hipMemcpyHostToDevice, stream_), err, false);
-    d_allow = allow_.as<uint32_t>();
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -340,10 +307,7 @@ int SparseIndex::rescore_device(int nq, int kq, const int32_t *d_qids, const flo
         a.n_rows = n_; a.width = width_; a.nq = c; a.n_cand = n_cand; a.n_chunks = (n_cand + SPARSE_RESCORE_CAND - 1) / SPARSE_RESCORE_CAND;
         a.words = sparse_image_words(n_vocab_); a.img_bytes = (unsigned)sparse_image_bytes(n_vocab_);
         eng_->timed_launch(dtype_ ? "sparse_index_rescore_f16" : "sparse_index_rescore_f32", 0.0, s, [&] { launch_sparse_rescore(dtype_, a, s); });
-        MergeArgs m;
-        m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
-        m.ids = d_ids + (size_t)c0 * k; m.scores = d_scores + (size_t)c0 * k;
-        eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
+        enqueue_merge(c, n_cand, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -3);
     return eng_->op_end(op, err) ? 0 : -3;
@@ -356,8 +320,7 @@ int SparseIndex::rescore_to_host(int nq, int kq, const int32_t *qids, const floa
     for (size_t i = 0; i < (size_t)nq * n_cand; ++i)
         if (cand[i] < -1 || cand[i] >= n_) { err = "rescore: candidate id " + std::to_string(cand[i]) + " is outside [-1, " + std::to_string(n_) + ")"; return -2; }
     DeviceGuard g(eng_->device());
-    std::vector<int32_t> hid((size_t)nq * k);
-    std::vector<float> hsc((size_t)nq * k);
+    HostResults res((size_t)nq * k);
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         const size_t half = ((size_t)c * kq * 4 + 15) & ~(size_t)15;
@@ -370,12 +333,9 @@ int SparseIndex::rescore_to_host(int nq, int kq, const int32_t *qids, const floa
         HIP_OK(hipMemcpyAsync(cand_in_.p, cand + (size_t)c0 * n_cand, (size_t)c * n_cand * 4, hipMemcpyHostToDevice, stream_), err, -3);
         if (rescore_device(c, kq, (const int32_t *)d, (const float *)(d + half), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
                            out_scores_.as<float>(), stream_, err) != 0) { (void)hipStreamSynchronize(stream_); return -3; }
-        HIP_OK(hipMemcpyAsync(hid.data() + (size_t)c0 * k, out_ids_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -3);
-        HIP_OK(hipMemcpyAsync(hsc.data() + (size_t)c0 * k, out_scores_.p, (size_t)c * k * 4, hipMemcpyDeviceToHost, stream_), err, -3);
-        HIP_OK(hipStreamSynchronize(stream_), err, -3);
+        if (!results_to_host(stream_, (size_t)c0 * k, (size_t)c * k, res, err)) return -3;
     }
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
+    res.deliver(ids, scores);
     return 0;
 }
 
@@ -417,94 +377,23 @@ int SparseIndex::get_rows(int n, const int32_t *row_ids, int32_t *out_ids, float
 void SparseIndex::truncate(int n) {
     if (n < 0 || n >= n_) return;
     if (inverted_ && n < inv_rows_) drop_postings();
-    // (the mirror keeps its bits at and beyond size zero; the device words of the dropped rows stay as they are: a search ignores
-    // them, and the add that reuses those rows sets them)
-    if (live_) {
-        for (long long r = n; r < n_;) {
-            const int b = (int)(r & 31);
-            live_h_[(size_t)(r >> 5)] &= b ? (1u << b) - 1u : 0u;
-            r += 32 - b;
-        }
-        n_removed_ = n;
-        for (size_t w = 0; w < live_words(n); ++w) n_removed_ -= __builtin_popcount(live_h_[w]);
-    }
+    if (live_) bits_.truncate(n_, n);                        // (live_bits.h: the mirror's side of the invariant; the device words stay)
     n_ = n;
 }
 
-// the bitmap of an index that had none: every row live
-bool SparseIndex::make_live(std::string &err) {
-    if (live_) return true;
-    const size_t lw = live_words(cap_);
-    HIP_OK(hipEventSynchronize(busy_), err, false);
-    HIP_OK(hipMalloc((void **)&live_, std::max<size_t>(lw, 1) * 4), err, false);
-    live_h_.assign(lw, 0u);
-    if (n_ > 0) live_set_range_host(live_h_, 0, n_);
-    n_removed_ = 0;
-    if (lw > 0 && hipMemcpy(live_, live_h_.data(), lw * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        drop_live();
-        err = "hipMemcpy (sparse index live words) failed";
-        return false;
-    }
-    return true;
-}
-
-void SparseIndex::drop_live() {
-    if (live_) (void)hipFree(live_);
-    live_ = nullptr;
-    live_h_.clear();
-    n_removed_ = 0;
-}
-
-// mirror words [w0, w1) -> device, on the index's stream behind whatever is queued; blocking
-bool SparseIndex::upload_live(size_t w0, size_t w1, std::string &err) {
-    if (w1 <= w0) return true;
-    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
-    HIP_OK(hipMemcpyAsync(live_ + w0, live_h_.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, stream_), err, false);
-    HIP_OK(hipEventRecord(busy_, stream_), err, false);
-    HIP_OK(hipStreamSynchronize(stream_), err, false);
-    return true;
-}
-
 int SparseIndex::remove(int n, const int32_t *ids, std::string &err) {
-    if (n < 0 || (n > 0 && !ids)) { err = "remove: n >= 0 and an id pointer required"; return -2; }
-    for (int i = 0; i < n; ++i)
-        if (ids[i] < 0 || ids[i] >= n_) { err = "remove: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(n_) + ")"; return -2; }
-    if (n == 0) return 0;
-    DeviceGuard g(eng_->device());
-    if (!make_live(err)) return -3;
     std::vector<int32_t> fresh;                          // the ids this call removes (repeats and removed rows left out)
-    size_t w0 = SIZE_MAX, w1 = 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t w = (size_t)ids[i] >> 5;
-        const uint32_t bit = 1u << (ids[i] & 31);
-        if (!(live_h_[w] & bit)) continue;
-        live_h_[w] &= ~bit;
-        fresh.push_back(ids[i]);
-        w0 = std::min(w0, w);
-        w1 = std::max(w1, w + 1);
-    }
-    if (!fresh.empty() && !upload_live(w0, w1, err)) {
-        for (int32_t id : fresh) live_h_[(size_t)id >> 5] |= 1u << (id & 31);      // (the mirror as it was)
-        return -3;
-    }
-    n_removed_ += (int)fresh.size();
-    return (int)fresh.size();
+    const Removed r = remove_rows(n, ids, cap_, fresh, err);
+    return r == Removed::ok ? (int)fresh.size() : r == Removed::refused ? -2 : -3;
 }
 
 int SparseIndex::compact(int32_t *old_ids, std::string &err) {
     DeviceGuard g(eng_->device());
     HIP_OK(hipEventSynchronize(busy_), err, -3);
     drop_postings();                                         // (the ids change: invert again)
-    if (n_removed_ == 0) {
-        if (old_ids) for (int i = 0; i < n_; ++i) old_ids[i] = i;
-        drop_live();
-        return n_;
-    }
-    const int nl = n_ - n_removed_;
-    std::vector<int32_t> map((size_t)nl);
-    int j = 0;
-    for (int r = 0; r < n_; ++r)
-        if (live_h_[(size_t)r >> 5] >> (r & 31) & 1u) map[(size_t)j++] = r;
+    if (bits_.n_removed == 0) return compact_nothing(old_ids);
+    const std::vector<int32_t> map = bits_.kept(n_);
+    const int nl = (int)map.size();
     const size_t arr = (size_t)blocks_of(nl) * width_ * SPARSE_BLOCK_ROWS * sparse_id_bytes(dtype_);
     const int cap = blocks_of(nl) * SPARSE_BLOCK_ROWS;
     void *pi = nullptr, *pw = nullptr;
@@ -544,23 +433,13 @@ int SparseIndex::compact(int32_t *old_ids, std::string &err) {
 
 namespace {
 
-// device memory <-> file in pieces of at most 64 MiB through a host buffer
+// device memory <-> file in pieces of at most 64 MiB through a host buffer (index_io.h)
 constexpr size_t FILE_PIECE = (size_t)64 << 20;
-
-bool device_to_file(FILE *f, const void *d, size_t bytes, std::vector<char> &buf, std::string &err) {
-    for (size_t o = 0; o < bytes; o += FILE_PIECE) {
-        const size_t c = std::min(FILE_PIECE, bytes - o);
-        if (buf.size() < c) buf.resize(c);
-        HIP_OK(hipMemcpy(buf.data(), (const char *)d + o, c, hipMemcpyDeviceToHost), err, false);
-        if (fwrite(buf.data(), 1, c, f) != c) { err = "write failed"; return false; }
-    }
-    return true;
-}
 
 // one of the two block arrays of n rows: the whole blocks as they are, the last, partial one with its rows at and beyond n zeroed
 bool blocks_to_file(FILE *f, const void *d, int n, int width, size_t eb, std::vector<char> &buf, std::string &err) {
     const size_t block = (size_t)width * SPARSE_BLOCK_ROWS * eb, whole = (size_t)(n / SPARSE_BLOCK_ROWS);
-    if (!device_to_file(f, d, whole * block, buf, err)) return false;
+    if (!device_to_file(f, d, whole * block, FILE_PIECE, buf, err)) return false;
     const int rest = n % SPARSE_BLOCK_ROWS;
     if (rest == 0) return true;
     std::vector<char> last(block);
@@ -580,22 +459,14 @@ bool SparseIndex::save(const char *path, std::string &err) {
     h.dtype = (uint32_t)dtype_; h.n_vocab = (uint32_t)n_vocab_; h.width = (uint32_t)width_; h.n_rows = (uint32_t)n_; h.has_live = live_ ? 1u : 0u;
     unsigned char hdr[INDEX_HEADER_BYTES];
     sparse_index_header_write(h, hdr);
-    const std::string tmp = std::string(path) + ".tmp";
-    FILE *f = fopen(tmp.c_str(), "wb");
-    if (!f) { err = "cannot write '" + tmp + "'"; return false; }
-    std::vector<char> buf;
-    const size_t eb = sparse_id_bytes(dtype_);
-    // (the live words come from the mirror: its bits at and beyond size are zero)
-    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && blocks_to_file(f, sids_, n_, width_, eb, buf, err) &&
-              blocks_to_file(f, sweights_, n_, width_, eb, buf, err) && device_to_file(f, counts_, (size_t)n_ * 4, buf, err) &&
-              (!live_ || fwrite(live_h_.data(), 4, live_words(n_), f) == live_words(n_));
-    ok = (fclose(f) == 0) && ok;
-    if (ok && rename(tmp.c_str(), path) != 0) ok = false;
-    if (!ok) {
-        (void)::remove(tmp.c_str());
-        if (err.empty()) err = "cannot write '" + std::string(path) + "'";
-    }
-    return ok;
+    return write_atomically(path, err, [&](FILE *f) {
+        std::vector<char> buf;
+        const size_t eb = sparse_id_bytes(dtype_);
+        // (the live words come from the mirror: its bits at and beyond size are zero)
+        return fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && blocks_to_file(f, sids_, n_, width_, eb, buf, err) &&
+               blocks_to_file(f, sweights_, n_, width_, eb, buf, err) && device_to_file(f, counts_, (size_t)n_ * 4, FILE_PIECE, buf, err) &&
+               (!live_ || fwrite(bits_.words.data(), 4, live_words(n_), f) == live_words(n_));
+    });
 }
 
 SparseIndex *SparseIndex::load(Engine *eng, FILE *f, const SparseIndexFileHeader &h, std::string &err) {
@@ -625,19 +496,11 @@ SparseIndex *SparseIndex::load(Engine *eng, FILE *f, const SparseIndexFileHeader
     if (!ix->grow_rows(n, err)) return nullptr;
     if (fseeko(f, (off_t)INDEX_HEADER_BYTES, SEEK_SET) != 0) { err = "read failed"; return nullptr; }
     for (void *dst : {ix->sids_, ix->sweights_})
-        for (size_t b0 = 0; b0 < nb; b0 += per) {
-            const size_t c = std::min(per, nb - b0);
-            if (fread(buf.data(), 1, c * block, f) != c * block) { err = "read failed"; return nullptr; }
-            HIP_OK(hipMemcpy((char *)dst + b0 * block, buf.data(), c * block, hipMemcpyHostToDevice), err, nullptr);
-        }
+        if (!file_to_device(f, dst, nb * block, per * block, buf, err)) return nullptr;
     HIP_OK(hipMemcpy(ix->counts_, counts.data(), (size_t)n * 4, hipMemcpyHostToDevice), err, nullptr);
     ix->n_ = n;
     if (!h.has_live) return ix.release();
-    if (!ix->make_live(err)) return nullptr;
-    std::copy(words.begin(), words.end(), ix->live_h_.begin());
-    ix->n_removed_ = n;
-    for (uint32_t w : words) ix->n_removed_ -= __builtin_popcount(w);
-    if (!ix->upload_live(0, words.size(), err)) return nullptr;
+    if (!ix->install_live(words.data(), ix->cap_, err)) return nullptr;
     return ix.release();
 }
 

@@ -4,9 +4,9 @@
 // or as u16 ids + f16 weights (RNE), in blocks of 64 rows stored column by column (sliced ELL).  A search turns each query into an
 // image the scan reads from LDS (sparse_query_kernel), scans the blocks with one row per lane and selects on chip
 // (sparse_index_scan_kernel: a top-k per (query, slice of rows) in LDS), and merges the slices' lists per query with the embedding
-// index's topk_merge_kernel.  Shaped like Index (search.h): grow-only storage and workspace, one event, a stream for the host routes.
-// Removed rows are a device bitmap with a host mirror, there from the first remove to the next compact; while it exists, or under an
-// allow-list, a search launches the masked scan.  rescore scores per-query candidate rows (sparse_index_rescore_kernel).
+// index's topk_merge_kernel.  Grow-only storage and workspace; the event, the stream of the host routes and the removed-rows bitmap
+// are the frame's that all three indexes derive from (index_frame.h; the bitmap's invariant: live_bits.h).  The bitmap is there from the
+// first remove to the next compact; while it exists, or under an allow-list, a search launches the masked scan.  rescore scores per-query candidate rows (sparse_index_rescore_kernel).
 // Postings (sparse_postings.cpp, kernels in sparse_postings.hip): invert builds a term-major image of the rows, and the searches'
 // `inverted` form answers from it with the row-major search's ids and score bits.
 #pragma once
@@ -18,12 +18,13 @@
 #include <vector>
 
 #include "engine.h"
+#include "index_frame.h"
 #include "sparse_index_file.h"
 #include "sparse_index_kernels.h"
 
 namespace bert_hip {
 
-class SparseIndex {
+class SparseIndex : private IndexFrame {
 public:
     static constexpr int MAX_K = 256, MAX_TERMS = SPARSE_MAX_TERMS, MAX_VOCAB = SPARSE_MAX_VOCAB, MAX_CAND = SPARSE_MAX_CAND;
     static constexpr int QCHUNK = 4096;                  // queries per internal pass (workspace and image-buffer bound)
@@ -33,7 +34,7 @@ public:
     ~SparseIndex();
 
     int size() const { return n_; }
-    int n_live() const { return n_ - n_removed_; }
+    int n_live() const { return n_ - bits_.n_removed; }
     int n_vocab() const { return n_vocab_; }
     int width() const { return width_; }
     int dtype() const { return dtype_; }
@@ -72,8 +73,8 @@ public:
     // the file form (sparse_index_file.h); blocking.  load: from f, positioned behind the header h that sparse_index_header_check passed
     bool save(const char *path, std::string &err);
     static SparseIndex *load(Engine *eng, FILE *f, const SparseIndexFileHeader &h, std::string &err);
-    // the live words of the host mirror, [ceil(size / 32)], bits at and beyond size zero; empty without removals
-    const std::vector<uint32_t> &live_words_host() const { return live_h_; }
+    // the live words of the host mirror (live_bits.h: as long as the capacity, bits at and beyond size zero); empty without removals
+    const std::vector<uint32_t> &live_words_host() const { return bits_.words; }
     // the stored rows row_ids [n] (each in [0, size)) as out_ids / out_weights [n][width]; blocking
     int get_rows(int n, const int32_t *row_ids, int32_t *out_ids, float *out_weights, std::string &err);
     // Text routes: device buffers of the index for a group's packed token ids | cu_seqlens (in) and its terms ids | weights [n][k] (out);
@@ -100,35 +101,25 @@ public:
 private:
     friend struct Hybrid;                               // hybrid.h: a search over this index and an embedding index together
     SparseIndex() = default;
-    bool grow(DevBuf &b, size_t bytes, std::string &err);
     bool grow_rows(int n_rows, std::string &err);
     bool grow_search(int n_rows, int nq, int k, std::string &err);
     void enqueue_queries(int nq, int kq, const int32_t *d_qids, const float *d_qw, hipStream_t s);
     void enqueue_chunk(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
                        const uint32_t *d_allow);
-    bool upload_allow(const uint32_t *allow, const uint32_t *&d_allow, std::string &err);
-    bool make_live(std::string &err);
-    void drop_live();
-    bool upload_live(size_t w0, size_t w1, std::string &err);
     void drop_postings();
     bool grow_inverted(int n_rows, int nqc, int k, std::string &err);
     bool inverted_ok(std::string &err) const;
     void enqueue_chunk_inverted(int nq, int kq, const int32_t *d_qids, const float *d_qw, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
                                 const uint32_t *d_allow);
 
-    Engine *eng_ = nullptr;
     int n_vocab_ = 0, width_ = 0, dtype_ = 0;
-    int n_ = 0, cap_ = 0;                                // rows; capacity in rows, a multiple of 64
+    int cap_ = 0;                                        // capacity in rows, a multiple of 64 (the rows, n_, and the bitmap: index_frame.h)
     void *sids_ = nullptr, *sweights_ = nullptr;        // [cap_ / 64][width_][64]
     int32_t *counts_ = nullptr;                         // [cap_]
-    // removed rows: device words [cap_ / 32] and their host mirror (bits at and beyond n_ zero), both absent until the first remove
-    uint32_t *live_ = nullptr;
-    std::vector<uint32_t> live_h_;
-    int n_removed_ = 0;
-    DevBuf ws_s_, ws_i_, images_;                       // per-(query, slice) lists; the current chunk's query images
-    DevBuf stage_, out_ids_, out_scores_;               // host routes: rows / queries / row ids in, results out
+    DevBuf images_;                                     // the current chunk's query images
+    DevBuf stage_;                                      // host routes: rows / queries / row ids in
     DevBuf text_in_, text_out_;                         // text routes
-    DevBuf allow_, cand_in_;                            // host routes: a caller's allow-list and candidate lists
+    DevBuf cand_in_;                                    // host routes: a caller's candidate lists
     DevBuf hyb_scores_, hyb_mask_;                      // hybrid search: the current chunk's dense scores [HC][ld]; live & live & allow
     // postings: offsets [segments][n_vocab + 1], row numbers and weights [segments][inv_seg_ * width_]; the rows they cover and the
     // segment size they were built with; the current chunk's sorted queries (ids | weights [chunk][256], then the counts)
@@ -136,9 +127,6 @@ private:
     bool inverted_ = false;
     int inv_rows_ = 0, inv_seg_ = 0;
     int res_nq_ = 0, res_k_ = 1;                        // what reserve was last given
-    hipStream_t stream_ = nullptr;                      // the host routes' stream
-    // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
-    hipEvent_t busy_ = nullptr;
 };
 
 // host queries [nq][kq] as search_host checks them: every id in [-1, n_vocab), none twice in a query, every used weight finite;

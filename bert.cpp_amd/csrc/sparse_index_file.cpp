@@ -3,6 +3,8 @@
 
 #include <cstring>
 
+#include "live_bits.h"
+
 namespace bert_hip {
 
 namespace {
@@ -98,7 +100,7 @@ bool sparse_index_ids_check(const SparseIndexFileHeader &h, const void *ids, uin
 bool sparse_index_live_check(const SparseIndexFileHeader &h, const uint32_t *words, std::string &err) {
     if (!h.has_live || (h.n_rows & 31) == 0) return true;
     const uint32_t last = get_u32((const unsigned char *)words + 4 * (uint64_t)(h.n_rows >> 5));
-    if (last >> (h.n_rows & 31)) { err = "live bits beyond the last row"; return false; }
+    if (!live_tail_clear(last, h.n_rows)) { err = "live bits beyond the last row"; return false; }
     return true;
 }
 

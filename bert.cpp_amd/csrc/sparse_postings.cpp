@@ -6,7 +6,6 @@
 #include <algorithm>
 #include <vector>
 
-#include "search.h"
 #include "sparse_index.h"
 
 namespace bert_hip {
@@ -98,9 +97,7 @@ void SparseIndex::enqueue_chunk_inverted(int nq, int kq, const int32_t *d_qids, 
     a.live = live_; a.allow = d_allow;
     static const char *const names[2][2] = {{"sparse_postings_scan_f32", "sparse_postings_scan_f32_masked"}, {"sparse_postings_scan_f16", "sparse_postings_scan_f16_masked"}};
     eng_->timed_launch(names[dtype_][masked], 0.0, s, [&] { launch_sparse_postings_scan(dtype_, a, g.lds, s); });
-    MergeArgs m;
-    m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = g.n_slices * k; m.k = k; m.L = merge_L(k); m.ids = d_ids; m.scores = d_scores;
-    eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, nq, s); });
+    enqueue_merge(nq, g.n_slices * k, k, d_ids, d_scores, s);
 }
 
 int SparseIndex::postings_segment_host(int sg, std::vector<uint32_t> &off, std::vector<uint16_t> &rows, std::vector<float> &weights, std::string &err) {

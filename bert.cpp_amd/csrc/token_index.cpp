@@ -1,6 +1,6 @@
 // token_index.cpp — the host side of the token index (token_index.h): storage and its growth, the add forms, the search and its
-// chunks, rescoring, reading a document back, the checks of the host forms, the live bits, compaction and the file form.  Every kernel
-// is in token_index.hip (both forms), maxsim.hip or search.hip (the merge, the live bits of added documents) and reached through
+// chunks, rescoring, reading a document back, the checks of the host forms, compaction and the file form (live bits, remove, stream
+// and event: index_frame.h; file frame: index_io.h).  Every kernel is in token_index.hip (both forms), maxsim.hip or search.hip (the merge, the live bits of added documents) and reached through
 // token_index_kernels.h / kernels.h / search_kernels.h.
 #include <hip/hip_runtime.h>
 
@@ -12,7 +12,8 @@
 
 #include <sys/types.h>
 
-#include "search.h"
+#include "index_io.h"
+#include "search_kernels.h"
 #include "token_index.h"
 
 namespace bert_hip {
@@ -64,14 +65,11 @@ TokenIndex *TokenIndex::create(Engine *eng, int dim, int dtype, std::string &err
     if (dtype != 1 && dtype != 2) { err = "dtype must be 1 (f16) or 2 (int8)"; return nullptr; }
     DeviceGuard g(eng->device());
     TokenIndex *ix = new TokenIndex;
-    ix->eng_ = eng;
     ix->dim_ = dim;
     ix->dtype_ = dtype;
     ix->dpad_ = token_i8_dpad(dim);
     ix->cu_h_.assign(1, 0);
-    const bool ok = hipStreamCreateWithFlags(&ix->stream_, hipStreamNonBlocking) == hipSuccess &&
-                    hipEventCreateWithFlags(&ix->busy_, hipEventDisableTiming) == hipSuccess;
-    if (!ok) { err = "hipStreamCreate / hipEventCreate failed"; delete ix; return nullptr; }
+    if (!ix->open(eng, "token index", err)) { delete ix; return nullptr; }
     // (cu[0] = 0 is there from the start: an empty index is searched like any other)
     if (!ix->grow_storage(1, 0, err)) { delete ix; return nullptr; }
     token_index_kernels_init();
@@ -80,18 +78,10 @@ TokenIndex *TokenIndex::create(Engine *eng, int dim, int dtype, std::string &err
 
 TokenIndex::~TokenIndex() {
     DeviceGuard g(eng_ ? eng_->device() : 0);
-    if (busy_) { (void)hipEventSynchronize(busy_); (void)hipEventDestroy(busy_); }
-    if (stream_) { (void)hipStreamSynchronize(stream_); (void)hipStreamDestroy(stream_); }
+    close();
     if (rows_) (void)hipFree(rows_);
     if (scales_) (void)hipFree(scales_);
     if (cu_) (void)hipFree(cu_);
-    if (live_) (void)hipFree(live_);
-}
-
-bool TokenIndex::grow(DevBuf &b, size_t bytes, std::string &err) {
-    if (bytes <= b.bytes) return true;
-    HIP_OK(hipEventSynchronize(busy_), err, false);          // (what is queued may still read the old buffer)
-    return b.ensure(bytes, err);
 }
 
 // (rows and cumulative lengths are plain arrays: growth is a copy each; the host mirror's capacity follows cu_'s, so that its
@@ -105,25 +95,21 @@ bool TokenIndex::grow_storage(long long n_docs, long long n_tokens, std::string 
         int32_t *pc = nullptr;
         // (an index with removed documents: the live words grow with the lengths, so that an add within the capacity never allocates)
         uint32_t *lv = nullptr;
-        const size_t lw = live_words(cap);
-        if (hipMalloc((void **)&pc, (size_t)(cap + 1) * 4) != hipSuccess || (live_ && hipMalloc((void **)&lv, lw * 4) != hipSuccess)) {
+        if (hipMalloc((void **)&pc, (size_t)(cap + 1) * 4) != hipSuccess) {
             (void)hipGetLastError();
-            if (pc) (void)hipFree(pc);
             err = "hipMalloc (token index lengths) failed";
             return false;
         }
-        if (hipMemcpy(pc, cu_h_.data(), (size_t)(n_ + 1) * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            (lv && (hipMemset(lv, 0, lw * 4) != hipSuccess ||
-                    (n_ > 0 && hipMemcpy(lv, live_h_.data(), live_words(n_) * 4, hipMemcpyHostToDevice) != hipSuccess)))) {
+        if (hipMemcpy(pc, cu_h_.data(), (size_t)(n_ + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipGetLastError();
             (void)hipFree(pc);
-            if (lv) (void)hipFree(lv);
             err = "hipMemcpy (token index lengths) failed";
             return false;
         }
+        if (!live_for_capacity(cap, lv, err)) { (void)hipFree(pc); return false; }
         if (cu_) (void)hipFree(cu_);
         cu_ = pc;
-        if (live_) { (void)hipFree(live_); live_ = lv; live_h_.resize(lw, 0u); }
+        adopt_live(lv, cap);
         cap_docs_ = (int)cap;
         cu_h_.reserve((size_t)cap + 1);
     }
@@ -196,7 +182,7 @@ bool TokenIndex::commit(int n_docs, const int32_t *cu, hipStream_t s, std::strin
     if (live_) {
         launch_live_set_range(live_, n_, n_docs, s);
         if (hipGetLastError() != hipSuccess) { cu_h_.resize(at); err = "the live bits of the new documents could not be set"; return false; }
-        live_set_range_host(live_h_, n_, n_docs);
+        bits_.set_range(n_, n_docs);
     }
     n_ += n_docs;
     n_tok_ = cu_h_.back();
@@ -279,15 +265,8 @@ int TokenIndex::add_in_place(int n_docs, const int32_t *cu, std::string &err) {
 void TokenIndex::truncate(int n) {
     if (n < 0 || n >= n_) return;
     // (after a failure, behind a synchronised stream: no copy from the mirror is queued)
-    // (the mirror keeps its bits at and beyond size zero; the device words of the dropped documents stay as they are: a search ignores
-    // them, and the add that reuses those ids sets them)
-    if (live_)
-        for (int d = n; d < n_; ++d) {
-            uint32_t &w = live_h_[(size_t)d >> 5];
-            const uint32_t bit = 1u << (d & 31);
-            if (!(w & bit)) { --n_removed_; tok_removed_ -= cu_h_[(size_t)d + 1] - cu_h_[(size_t)d]; }
-            w &= ~bit;
-        }
+    // (live_bits.h: the mirror's side of the invariant; the device words stay)
+    if (live_) bits_.truncate(n_, n, [&](int d) { tok_removed_ -= cu_h_[(size_t)d + 1] - cu_h_[(size_t)d]; });
     cu_h_.resize((size_t)n + 1);
     n_ = n;
     n_tok_ = cu_h_.back();
@@ -376,33 +355,17 @@ int TokenIndex::scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool 
         const bool masked = a.live || a.allow;
         const char *label = d_cand ? "token_i8_rescore" : i8 ? (masked ? "token_i8_scan_masked" : "token_i8_scan") : (masked ? "token_index_scan_masked" : "token_index_scan");
         eng_->timed_launch(label, 0.0, s, [&] { launch_token_scan(dtype_, a, s); });
-        merge_lists(c, p.n_slices * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
+        enqueue_merge(c, p.n_slices * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -3);
     return eng_->op_end(op, err) ? 0 : -3;
 }
 
-// the best k of each of c queries' n_cand workspace entries -> ids / scores [c][k]
-void TokenIndex::merge_lists(int c, int n_cand, int k, int32_t *d_ids, float *d_scores, hipStream_t s) {
-    MergeArgs m;
-    m.ws_s = ws_s_.as<float>(); m.ws_i = ws_i_.as<int>(); m.n_cand = n_cand; m.k = k; m.L = merge_L(k);
-    m.ids = d_ids; m.scores = d_scores;
-    eng_->timed_launch("topk_merge", 0.0, s, [&] { launch_topk_merge(m, c, s); });
-}
-
 // out_ids_ / out_scores_ [nq][k], which a search or rescore (what) on stream() has filled -> host; the caller's arrays are written only on success
-int TokenIndex::results_to_host(const char *what, int nq, int k, int32_t *ids, float *scores, std::string &err) {
-    std::vector<int32_t> hid((size_t)nq * k);
-    std::vector<float> hsc((size_t)nq * k);
-    if (hipMemcpyAsync(hid.data(), out_ids_.p, hid.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
-        hipMemcpyAsync(hsc.data(), out_scores_.p, hsc.size() * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
-        hipStreamSynchronize(stream_) != hipSuccess) {
-        (void)hipStreamSynchronize(stream_);
-        err = std::string(what) + ": copy of the results failed";
-        return -3;
-    }
-    memcpy(ids, hid.data(), hid.size() * 4);
-    memcpy(scores, hsc.data(), hsc.size() * 4);
+int TokenIndex::deliver_results(const char *what, int nq, int k, int32_t *ids, float *scores, std::string &err) {
+    HostResults res((size_t)nq * k);
+    if (!results_to_host(stream_, 0, res.ids.size(), res, err)) { err = std::string(what) + ": " + err; return -3; }
+    res.deliver(ids, scores);
     return 0;
 }
 
@@ -413,7 +376,7 @@ int TokenIndex::search_to_host(int nq, const int32_t *d_qcu, const void *d_q, bo
         (void)hipStreamSynchronize(stream_);
         return r;
     }
-    return results_to_host("search", nq, k, ids, scores, err);
+    return deliver_results("search", nq, k, ids, scores, err);
 }
 
 int TokenIndex::stage_queries(const char *what, int nq, const int32_t *qcu, const float *q_rows, int limit, int &max_len, std::string &err) {
@@ -446,18 +409,8 @@ int TokenIndex::search_host(int nq, const int32_t *qcu, const float *q_rows, int
     int max_len = 0;
     if (const int r = stage_queries("search", nq, qcu, q_rows, max_query_tokens(), max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
     const uint32_t *d_allow = nullptr;
-    if (!upload_allow(allow, d_allow, err)) { (void)hipStreamSynchronize(stream_); return -3; }
+    if (!upload_allow(allow, stream_, d_allow, err)) { (void)hipStreamSynchronize(stream_); return -3; }
     return search_to_host(nq, qcu_in_.as<int32_t>(), dtype_ == 2 ? stage_.p : q16_.p, dtype_ == 2, max_len, k, ids, scores, err, d_allow);
-}
-
-// (the host form copies ceil(size / 32) words; behind stage_queries, which made stream() wait for the index's event)
-bool TokenIndex::upload_allow(const uint32_t *allow, const uint32_t *&d_allow, std::string &err) {
-    if (!allow || n_ == 0) return true;
-    if (!grow(allow_, live_words(n_) * 4, err)) return false;
-    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
-    HIP_OK(hipMemcpyAsync(allow_.p, allow, live_words(n_) * 4, hipMemcpyHostToDevice, stream_), err, false);
-    d_allow = allow_.as<uint32_t>();
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -482,7 +435,7 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
         // (the index's own arrays are maxsim's document side; a pair (q, -1) is scored NaN and reads nothing)
         MaxsimArgs ma{d_q, (const half_t *)rows_, d_qcu + c0, cu_, pairs_.as<int32_t>(), ws_s_.as<float>(), c, n_, dim_, c * n_cand, 0, 0};
         eng_->timed_launch("maxsim", 0.0, s, [&] { launch_maxsim(ma, s, eng_->options().maxsim_launch_pairs); });
-        merge_lists(c, n_cand, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
+        enqueue_merge(c, n_cand, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -3);
     return eng_->op_end(op, err) ? 0 : -3;
@@ -503,73 +456,16 @@ int TokenIndex::rescore_host(int nq, const int32_t *qcu, const float *q_rows, in
                                                 nullptr, cand_in_.as<int32_t>(), n_cand)
                                   : rescore_device(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
                                                    out_scores_.as<float>(), stream_, err); r != 0) return fail(r);
-    return results_to_host("rescore", nq, k, ids, scores, err);
+    return deliver_results("rescore", nq, k, ids, scores, err);
 }
 
 // ------------------------------------------------------------------------------------------------
 // removed documents, compaction, file form
 // ------------------------------------------------------------------------------------------------
-// the bitmap of an index that had none: every document live
-bool TokenIndex::make_live(std::string &err) {
-    if (live_) return true;
-    const size_t lw = live_words(cap_docs_);
-    HIP_OK(hipEventSynchronize(busy_), err, false);
-    HIP_OK(hipStreamSynchronize(stream_), err, false);
-    HIP_OK(hipMalloc((void **)&live_, std::max<size_t>(lw, 1) * 4), err, false);
-    live_h_.assign(lw, 0u);
-    if (n_ > 0) live_set_range_host(live_h_, 0, n_);
-    n_removed_ = 0;
-    tok_removed_ = 0;
-    if (lw > 0 && hipMemcpy(live_, live_h_.data(), lw * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipGetLastError();
-        drop_live();
-        err = "hipMemcpy (token index live words) failed";
-        return false;
-    }
-    return true;
-}
-
-void TokenIndex::drop_live() {
-    if (live_) (void)hipFree(live_);
-    live_ = nullptr;
-    live_h_.clear();
-    n_removed_ = 0;
-    tok_removed_ = 0;
-}
-
-// mirror words [w0, w1) -> device, on the index's stream behind whatever is queued; blocking
-bool TokenIndex::upload_live(size_t w0, size_t w1, std::string &err) {
-    if (w1 <= w0) return true;
-    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
-    HIP_OK(hipMemcpyAsync(live_ + w0, live_h_.data() + w0, (w1 - w0) * 4, hipMemcpyHostToDevice, stream_), err, false);
-    HIP_OK(hipEventRecord(busy_, stream_), err, false);
-    HIP_OK(hipStreamSynchronize(stream_), err, false);
-    return true;
-}
-
 int TokenIndex::remove(int n, const int32_t *ids, std::string &err) {
-    if (n < 0 || (n > 0 && !ids)) { err = "remove: n >= 0 and an id pointer required"; return -2; }
-    for (int i = 0; i < n; ++i)
-        if (ids[i] < 0 || ids[i] >= n_) { err = "remove: id " + std::to_string(ids[i]) + " is outside [0, " + std::to_string(n_) + ")"; return -2; }
-    if (n == 0) return 0;
-    DeviceGuard g(eng_->device());
-    if (!make_live(err)) return -3;
     std::vector<int32_t> fresh;                          // the ids this call removes (repeats and removed documents left out)
-    size_t w0 = SIZE_MAX, w1 = 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t w = (size_t)ids[i] >> 5;
-        const uint32_t bit = 1u << (ids[i] & 31);
-        if (!(live_h_[w] & bit)) continue;
-        live_h_[w] &= ~bit;
-        fresh.push_back(ids[i]);
-        w0 = std::min(w0, w);
-        w1 = std::max(w1, w + 1);
-    }
-    if (!fresh.empty() && !upload_live(w0, w1, err)) {
-        for (int32_t id : fresh) live_h_[(size_t)id >> 5] |= 1u << (id & 31);      // (the mirror as it was)
-        return -3;
-    }
-    n_removed_ += (int)fresh.size();
+    const Removed r = remove_rows(n, ids, cap_docs_, fresh, err);
+    if (r != Removed::ok) return r == Removed::refused ? -2 : -3;
     for (int32_t id : fresh) tok_removed_ += cu_h_[(size_t)id + 1] - cu_h_[(size_t)id];
     return (int)fresh.size();
 }
@@ -579,22 +475,13 @@ int TokenIndex::compact(int32_t *old_ids, std::string &err) {
     DeviceGuard g(eng_->device());
     HIP_OK(hipEventSynchronize(busy_), err, -3);
     HIP_OK(hipStreamSynchronize(stream_), err, -3);
-    if (n_removed_ == 0) {
-        if (old_ids) for (int i = 0; i < n_; ++i) old_ids[i] = i;
-        drop_live();
-        return n_;
-    }
+    if (bits_.n_removed == 0) return compact_nothing(old_ids);
     // the kept documents' former ids and their new cumulative lengths, from the mirrors
     const int nl = n_live();
     const int64_t ntl = n_live_tokens();
-    std::vector<int32_t> map((size_t)nl), ncu((size_t)nl + 1, 0);
-    int j = 0;
-    for (int d = 0; d < n_; ++d)
-        if (live_h_[(size_t)d >> 5] >> (d & 31) & 1u) {
-            map[(size_t)j] = d;
-            ncu[(size_t)j + 1] = ncu[(size_t)j] + (cu_h_[(size_t)d + 1] - cu_h_[(size_t)d]);
-            ++j;
-        }
+    const std::vector<int32_t> map = bits_.kept(n_);
+    std::vector<int32_t> ncu((size_t)nl + 1, 0);
+    for (int j = 0; j < nl; ++j) ncu[(size_t)j + 1] = ncu[(size_t)j] + (cu_h_[(size_t)map[(size_t)j] + 1] - cu_h_[(size_t)map[(size_t)j]]);
     // everything new is made before anything old is let go: fresh lengths and fresh rows beside the old ones (the peak is old + new)
     const int cap = std::max(nl, 1024);
     int32_t *pc = nullptr, *d_map = nullptr;
@@ -628,13 +515,15 @@ int TokenIndex::compact(int32_t *old_ids, std::string &err) {
     cu_h_.swap(ncu);
     cu_h_.reserve((size_t)cap + 1);
     drop_live();
+    tok_removed_ = 0;
     if (old_ids && nl > 0) memcpy(old_ids, map.data(), (size_t)nl * 4);
     return nl;
 }
 
 namespace {
 
-// rows between HBM and a file in pieces of at most 32 MiB through a host buffer, as add uploads them: never a host copy of the index
+// rows between HBM and a file in pieces of at most 32 MiB through a host buffer (index_io.h), as add uploads them: never a host copy of
+// the index
 constexpr size_t FILE_PIECE = (size_t)32 << 20;
 
 }  // namespace
@@ -648,26 +537,13 @@ bool TokenIndex::save(const char *path, std::string &err) {
     h.dim = (uint32_t)dim_; h.n_docs = (uint32_t)n_; h.has_live = live_ ? 1u : 0u; h.n_tokens = (uint64_t)n_tok_;
     unsigned char hdr[INDEX_HEADER_BYTES];
     token_index_header_write(h, hdr);
-    const std::string tmp = std::string(path) + ".tmp";
-    FILE *f = fopen(tmp.c_str(), "wb");
-    if (!f) { err = "cannot write '" + tmp + "'"; return false; }
-    // (the lengths and the live words come from the mirrors; the mirror's bits at and beyond size are zero)
-    bool ok = fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && fwrite(cu_h_.data(), 4, (size_t)n_ + 1, f) == (size_t)n_ + 1;
-    const size_t bytes = (size_t)n_tok_ * dim_ * 2;
-    std::vector<char> buf(std::min(FILE_PIECE, bytes));
-    for (size_t o = 0; ok && o < bytes; o += FILE_PIECE) {
-        const size_t c = std::min(FILE_PIECE, bytes - o);
-        if (hipMemcpy(buf.data(), (const char *)rows_ + o, c, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); err = "hipMemcpy (token index rows) failed"; ok = false; }
-        else ok = fwrite(buf.data(), 1, c, f) == c;
-    }
-    ok = ok && (!live_ || fwrite(live_h_.data(), 4, live_words(n_), f) == live_words(n_));
-    ok = (fclose(f) == 0) && ok;
-    if (ok && rename(tmp.c_str(), path) != 0) ok = false;
-    if (!ok) {
-        (void)::remove(tmp.c_str());
-        if (err.empty()) err = "cannot write '" + std::string(path) + "'";
-    }
-    return ok;
+    return write_atomically(path, err, [&](FILE *f) {
+        std::vector<char> buf;
+        // (the lengths and the live words come from the mirrors; the mirror's bits at and beyond size are zero)
+        return fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && fwrite(cu_h_.data(), 4, (size_t)n_ + 1, f) == (size_t)n_ + 1 &&
+               device_to_file(f, rows_, (size_t)n_tok_ * dim_ * 2, FILE_PIECE, buf, err) &&
+               (!live_ || fwrite(bits_.words.data(), 4, live_words(n_), f) == live_words(n_));
+    });
 }
 
 TokenIndex *TokenIndex::load(Engine *eng, FILE *f, const TokenIndexFileHeader &h, std::string &err) {
@@ -685,28 +561,22 @@ TokenIndex *TokenIndex::load(Engine *eng, FILE *f, const TokenIndexFileHeader &h
     DeviceGuard g(eng->device());
     if (n == 0) {
         // (an empty index that had a bitmap keeps one: the file's bytes come back from a save)
-        if (h.has_live && !ix->make_live(err)) return nullptr;
+        if (h.has_live && !ix->make_live(ix->cap_docs_, err)) return nullptr;
         return ix.release();
     }
     if (!ix->grow_storage(n, (long long)h.n_tokens, err)) return nullptr;
     if (fseeko(f, (off_t)rows_at, SEEK_SET) != 0) { err = "read failed"; return nullptr; }
-    std::vector<char> buf((size_t)std::min<uint64_t>(FILE_PIECE, bytes));
-    for (uint64_t o = 0; o < bytes; o += FILE_PIECE) {
-        const size_t c = (size_t)std::min<uint64_t>(FILE_PIECE, bytes - o);
-        if (fread(buf.data(), 1, c, f) != c) { err = "read failed"; return nullptr; }
-        HIP_OK(hipMemcpy((char *)ix->rows_ + o, buf.data(), c, hipMemcpyHostToDevice), err, nullptr);
-    }
+    std::vector<char> buf;
+    if (!file_to_device(f, ix->rows_, (size_t)bytes, FILE_PIECE, buf, err)) return nullptr;
     // (grow_storage reserved the mirror: its entries do not move afterwards)
     ix->cu_h_.assign(cu.begin(), cu.end());
     HIP_OK(hipMemcpy(ix->cu_, ix->cu_h_.data(), ix->cu_h_.size() * 4, hipMemcpyHostToDevice), err, nullptr);
     ix->n_ = n;
     ix->n_tok_ = (int64_t)h.n_tokens;
     if (!h.has_live) return ix.release();
-    if (!ix->make_live(err)) return nullptr;
-    std::copy(words.begin(), words.end(), ix->live_h_.begin());
+    if (!ix->install_live(words.data(), ix->cap_docs_, err)) return nullptr;
     for (int d = 0; d < n; ++d)
-        if (!(words[(size_t)d >> 5] >> (d & 31) & 1u)) { ++ix->n_removed_; ix->tok_removed_ += cu[(size_t)d + 1] - cu[(size_t)d]; }
-    if (!ix->upload_live(0, words.size(), err)) return nullptr;
+        if (!ix->bits_.test(d)) ix->tok_removed_ += cu[(size_t)d + 1] - cu[(size_t)d];
     return ix.release();
 }
 

@@ -3,9 +3,9 @@
 // with int32 cumulative lengths on the device and in a host mirror, on the device of the engine the index was made from.  A search
 // scans the documents with one (query, slice of documents) per workgroup and selects on chip (token_index_scan_kernel), then merges the
 // slices' lists per query with the embedding index's topk_merge_kernel; a rescore turns per-query candidate ids into maxsim's pair
-// list, scores them with launch_maxsim against the index's own arrays and selects with the same merge.  Shaped like SparseIndex
-// (sparse_index.h): grow-only storage and workspace, one event, a stream for the host routes.
-// Removed documents are a device bitmap with a host mirror, there from the first remove to the next compact; while it exists, or under
+// list, scores them with launch_maxsim against the index's own arrays and selects with the same merge.  Grow-only storage and
+// workspace; the event, the stream of the host routes and the removed-documents bitmap are the frame's that all three indexes derive
+// from (index_frame.h; the bitmap's invariant: live_bits.h).  The bitmap is there from the first remove to the next compact; while it exists, or under
 // an allow-list, a search launches the masked scan and a rescore's pair list leaves the removed ids out.  compact gathers the live
 // documents' rows into a fresh allocation on the device; save / load move the file form (token_index_file.h) in pieces.
 // dtype 2, the int8 form (token_index_kernels.h states it): rows are int8 codes of dpad bytes with one f32 scale per token, every add
@@ -21,12 +21,13 @@
 #include <vector>
 
 #include "engine.h"
+#include "index_frame.h"
 #include "token_index_file.h"
 #include "token_index_kernels.h"
 
 namespace bert_hip {
 
-class TokenIndex {
+class TokenIndex : private IndexFrame {
 public:
     static constexpr int MAX_K = 256, MAX_CAND = TOKEN_MAX_CAND;
     static constexpr int QCHUNK = 256;                   // queries per internal pass (workspace bound)
@@ -38,7 +39,7 @@ public:
 
     int size() const { return n_; }
     int64_t n_tokens() const { return n_tok_; }
-    int n_live() const { return n_ - n_removed_; }
+    int n_live() const { return n_ - bits_.n_removed; }
     int64_t n_live_tokens() const { return n_tok_ - tok_removed_; }
     int dim() const { return dim_; }
     int dtype() const { return dtype_; }
@@ -109,7 +110,6 @@ public:
 
 private:
     TokenIndex() = default;
-    bool grow(DevBuf &b, size_t bytes, std::string &err);
     bool grow_storage(long long n_docs, long long n_tokens, std::string &err);
     bool grow_search(int n_docs, int nqc, int k, std::string &err);
     // int8 form: the queries' codes and scales, [nqc][max_q_len] rows
@@ -125,45 +125,28 @@ private:
     // the chunk loop behind every search (d_cand null: the documents under live_ / d_allow) and the int8 rescore (d_cand [nq][n_cand])
     int scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
                     std::string &err, const uint32_t *d_allow, const int32_t *d_cand, int n_cand);
-    // topk_merge over ws_s_ / ws_i_ [c][n_cand] -> d_ids / d_scores [c][k], on s
-    void merge_lists(int c, int n_cand, int k, int32_t *d_ids, float *d_scores, hipStream_t s);
-    // out_ids_ / out_scores_ [nq][k] -> host behind what stream() holds; blocking
-    int results_to_host(const char *what, int nq, int k, int32_t *ids, float *scores, std::string &err);
+    // out_ids_ / out_scores_ [nq][k] -> the caller's arrays behind what stream() holds; blocking
+    int deliver_results(const char *what, int nq, int k, int32_t *ids, float *scores, std::string &err);
     // cu entries of n_docs new documents (lengths from cu, any base) behind the stored ones, on s; bumps the counts
     bool commit(int n_docs, const int32_t *cu, hipStream_t s, std::string &err);
     // queries of a host form: rows -> f16 in q16_ (the int8 form: left as f32 in stage_), lengths (rebased to 0) -> qcu_in_, on
     // stream(); max_len: the longest
     int stage_queries(const char *what, int nq, const int32_t *qcu, const float *q_rows, int limit, int &max_len, std::string &err);
-    // a host allow-list -> allow_, on stream() behind whatever is queued (null, or an empty index: d_allow stays null)
-    bool upload_allow(const uint32_t *allow, const uint32_t *&d_allow, std::string &err);
-    bool make_live(std::string &err);
-    void drop_live();
-    bool upload_live(size_t w0, size_t w1, std::string &err);
 
-    Engine *eng_ = nullptr;
     int dim_ = 0, dtype_ = 1, dpad_ = 0;
-    int n_ = 0, cap_docs_ = 0;                          // documents; capacity of cu_ in documents
+    int cap_docs_ = 0;                                  // capacity of cu_ in documents (the documents, n_, and the bitmap: index_frame.h)
     int64_t n_tok_ = 0, cap_tok_ = 0;                   // rows; capacity of rows_ in rows
     char *rows_ = nullptr;                              // [cap_tok_][row_bytes()]: f16 rows, or int8 codes
     float *scales_ = nullptr;                           // int8 form: [cap_tok_]
     int32_t *cu_ = nullptr;                             // [cap_docs_ + 1]
     std::vector<int32_t> cu_h_;                         // the host mirror, [n_ + 1]
-    // removed documents: device words [ceil(cap_docs_ / 32)] and their host mirror of the same length (bits at and beyond n_ zero),
-    // both absent until the first remove
-    uint32_t *live_ = nullptr;
-    std::vector<uint32_t> live_h_;
-    int n_removed_ = 0;
-    int64_t tok_removed_ = 0;                           // the removed documents' rows
+    int64_t tok_removed_ = 0;                           // the removed documents' rows (0 without a bitmap)
     std::vector<int32_t> qcu_h_;                        // host routes: the current call's query lengths, rebased to 0
-    DevBuf ws_s_, ws_i_, pairs_;                        // per-(query, slice) lists, or a rescore's scores and ids; its pair list
-    DevBuf stage_, q16_, qcu_in_, cand_in_, out_ids_, out_scores_;      // host routes: f32 rows in, queries, candidates, results out
+    DevBuf pairs_;                                      // a rescore's pair list
+    DevBuf stage_, q16_, qcu_in_, cand_in_;             // host routes: f32 rows in, queries, candidates
     DevBuf text_in_, text_out_;                         // text routes
     DevBuf text_rows_;                                  // int8 form: the f16 rows of an add_texts chunk (append_room)
     DevBuf q_codes_, q_scales_;                         // int8 form: the quantised queries of a search or rescore
-    DevBuf allow_;                                      // host routes: a caller's allow-list
-    hipStream_t stream_ = nullptr;                      // the host routes' stream
-    // the index's buffers serve ONE operation at a time: each waits (on its own stream) for the previous one's event
-    hipEvent_t busy_ = nullptr;
 };
 
 // cu [n + 1] ascends strictly from an entry >= 0 (no empty entry)

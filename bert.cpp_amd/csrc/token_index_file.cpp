@@ -3,6 +3,8 @@
 
 #include <cstring>
 
+#include "live_bits.h"
+
 namespace bert_hip {
 
 namespace {
@@ -75,7 +77,7 @@ bool token_index_cu_check(const TokenIndexFileHeader &h, const int32_t *cu, std:
 bool token_index_live_check(const TokenIndexFileHeader &h, const uint32_t *words, std::string &err) {
     if (!h.has_live || (h.n_docs & 31) == 0) return true;
     const uint32_t last = get_u32((const unsigned char *)words + 4 * (uint64_t)(h.n_docs >> 5));
-    if (last >> (h.n_docs & 31)) { err = "live bits beyond the last document"; return false; }
+    if (!live_tail_clear(last, h.n_docs)) { err = "live bits beyond the last document"; return false; }
     return true;
 }
 

@@ -229,6 +229,34 @@ def test_remove_counts_refuses_and_rescore_skips_removed_ids(model):
     ix.close()
 
 
+def test_removals_at_the_ends_of_a_word_in_seventy_documents(model):
+    """the first and last bit of word 0, the first of word 1 and the index's last document, in the smallest index that has them"""
+    rng = np.random.default_rng(7070)
+    n, dim, k, gone = 70, 8, 8, [0, 31, 32, 69]
+    d, dcu = tref.documents(rng, n, dim, lens=[2, 3, 4, 5])
+    q, qcu = tref.queries(rng, dim, lens=[1, 3, 5])
+    # what is about to go leads every answer: documents 0 and 32 (2 tokens) start with query 0's token, 69 (3 tokens) is query 1, 31 (5) query 2
+    d = np.array(d)
+    d[dcu[0]] = d[dcu[32]] = q[0]
+    d[dcu[69]:dcu[70]] = q[qcu[1]:qcu[2]]
+    d[dcu[31]:dcu[32]] = q[qcu[2]:qcu[3]]
+    S = model.maxsim(q, qcu, d, dcu)
+    assert S.shape == (3, n) and np.isfinite(S).all()
+    ix = model.token_index(dim)
+    assert ix.add(d, dcu) == 0
+    first = ix.search(q, qcu, 2)[0]
+    assert sorted(first[0].tolist()) == [0, 32] and first[1:, 0].tolist() == [69, 31]
+    assert ix.remove(gone) == 4 and len(ix) == n and ix.n_live() == n - 4
+    assert ix.n_live_tokens() == int(dcu[-1]) - int(np.diff(dcu)[gone].sum())
+    live = np.ones(n, bool)
+    live[gone] = False
+    got = ix.search(q, qcu, k)
+    assert not np.isin(got[0], gone).any() and (got[0] >= 0).all()
+    assert tref.same_result(got, _expected(S, live, k))
+    assert np.array_equal(ix.live_ids(), np.flatnonzero(live))
+    ix.close()
+
+
 def test_a_dense_searchs_ids_rescored_after_a_remove_never_show_the_removed_document(model):
     c = _case(model, 64, 65)
     q, qcu, n = c["q"], c["qcu"], c["n"]

@@ -260,6 +260,74 @@ def test_remove_rules_and_rows_added_afterwards(model, dtype, capfd):
     ix.close()
 
 
+# ---- the bitmap's own edges at the smallest sizes that have them: the ends of a word, the first capacity step, stray allow bits
+
+@pytest.mark.parametrize("dtype", ["f32", "f16", "i8"])
+def test_removals_at_the_ends_of_a_word_in_seventy_rows(model, dtype):
+    rng = np.random.default_rng(70)
+    N, dim, k = 70, 32, 8
+    rows = unit_rows(rng, N, dim)
+    gone = [0, 31, 32, N - 1]
+    queries = rows[[0, 32, N - 1]]                          # each asks for a row that is about to go
+    ix = model.index(dim=dim, dtype=dtype)
+    ix.add(rows)
+    assert ix.search(queries, 1)[0][:, 0].tolist() == [0, 32, N - 1]
+    assert ix.remove(gone) == 4 and (len(ix), ix.n_live) == (N, N - 4)
+    keep = np.ones(N, bool)
+    keep[gone] = False
+    got = ix.search(queries, k)
+    assert not np.isin(got[0], gone).any() and (got[0] >= 0).all()
+    assert_same(got, plain_on_qualifying(model, dtype, rows, keep, queries, k), "the ends of a word")
+    ix.close()
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f16", "i8"])
+def test_rows_added_across_the_first_capacity_after_removals(model, dtype):
+    rng = np.random.default_rng(71)
+    N, n_new, dim, k = 1000, 100, 32, 8                     # 1000 rows fit the first capacity (1024), 1100 do not: the rows and the
+    rows, new = unit_rows(rng, N, dim), unit_rows(rng, n_new, dim)      # bitmap move to a new allocation
+    gone = [0, 31, N - 1]
+    ix = model.index(dim=dim, dtype=dtype)
+    ix.add(rows)
+    assert ix.remove(gone) == 3
+    assert ix.add(new) == N and (len(ix), ix.n_live) == (N + n_new, N + n_new - 3)
+    every = np.concatenate([rows, new])
+    keep = np.ones(N + n_new, bool)
+    keep[gone] = False
+    queries = every[[0, N, N + n_new - 1]]                  # a removed row, the first and the last new one
+    got = ix.search(queries, k)
+    assert not np.isin(got[0], gone).any() and got[0][1:, 0].tolist() == [N, N + n_new - 1]
+    assert_same(got, plain_on_qualifying(model, dtype, every, keep, queries, k), "across the first capacity")
+    # the rows in front of the move are still removable, the ones behind it too
+    assert ix.remove([1, N + 1, 0]) == 2
+    keep[[1, N + 1]] = False
+    assert_same(ix.search(queries, k), plain_on_qualifying(model, dtype, every, keep, queries, k), "removed after the move")
+    ix.close()
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f16", "i8"])
+def test_allow_bits_beyond_the_last_row_are_ignored(model, dtype):
+    rng = np.random.default_rng(72)
+    N, dim, k = 70, 32, 8
+    rows, queries = unit_rows(rng, N, dim), unit_rows(rng, 3, dim)
+    keep = rng.random(N) < 0.5
+    keep[N - 1] = True
+    words = pybert.allow_words(keep, N).copy()
+    assert len(words) == 3
+    stray = words.copy()
+    stray[-1] |= np.uint32((0xFFFFFFFF << (N % 32)) & 0xFFFFFFFF)
+    assert stray[-1] != words[-1]
+    ix = model.index(dim=dim, dtype=dtype)
+    ix.add(rows)
+    want = plain_on_qualifying(model, dtype, rows, keep, queries, k)
+    assert_same(ix.search(queries, k, allow=words), want, "clear")
+    assert_same(ix.search(queries, k, allow=stray), want, "stray bits")
+    ix.remove([0])                                          # and with the index's own bitmap beside the list
+    keep[0] = False
+    assert_same(ix.search(queries, k, allow=stray), plain_on_qualifying(model, dtype, rows, keep, queries, k), "stray bits, a removal")
+    ix.close()
+
+
 def test_short_allow_list_is_an_error_and_leaves_the_outputs(model, capfd):
     rng = np.random.default_rng(4)
     N, dim, k = 100, 16, 3

@@ -580,6 +580,78 @@ def test_a_files_bytes_depend_on_rows_and_removals_alone(model, tmp_path, dtype)
     b.close()
 
 
+# ------------------------------------------------------------------------------------------------
+# 5b. the bitmap's own edges at the smallest sizes that have them: the ends of a word, the first capacity step, a file written twice
+# ------------------------------------------------------------------------------------------------
+_EDGE = {}
+_MARKED = [0, 31, 32, 69, 999, 1000, 1099]
+
+
+def _edge_data(dtype):
+    """1100 rows of width 8 over 512 ids and three queries, with the reference's scores, computed once.  The rows _MARKED hold the one
+    term (511, 20000 + 32 j) — exact in f16 — and query 0 asks for id 511 alone: its answer is the marked rows, the last first."""
+    if dtype not in _EDGE:
+        rng = np.random.default_rng(812)
+        ids, w = _terms(rng, 1100, 8, 512, 8, False)
+        q_ids, q_w = _terms(rng, 3, 8, 512, 8, False)
+        for j, r in enumerate(_MARKED):
+            ids[r], w[r] = -1, 1.0
+            ids[r, 0], w[r, 0] = 511, 20000.0 + 32 * j
+        q_ids[0], q_w[0] = -1, 1.0
+        q_ids[0, 0] = 511
+        st = ref.stored_rows(ids, w, 8, dtype)
+        sc = ref.scores(st[0], st[1], q_ids, q_w, 512)
+        for a in (ids, w, q_ids, q_w, sc):
+            a.setflags(write=False)
+        _EDGE[dtype] = (ids, w, q_ids, q_w, sc)
+    return _EDGE[dtype]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_removals_at_the_ends_of_a_word_in_seventy_rows(model, tmp_path, dtype):
+    ids, w, q_ids, q_w, sc = _edge_data(dtype)
+    n, k, gone = 70, 8, [0, 31, 32, 69]
+    ix = model.sparse_index(8, dtype, n_vocab=512)
+    assert ix.add(ids[:n], w[:n]) == 0
+    assert ix.search(q_ids, q_w, k)[0][0, :4].tolist() == [69, 32, 31, 0]          # what is about to go is what query 0 finds
+    assert ix.remove(gone) == 4 and len(ix) == n and ix.n_live == n - 4
+    live = np.ones(n, bool)
+    live[gone] = False
+    got = ix.search(q_ids, q_w, k)
+    assert not np.isin(got[0], gone).any()
+    assert _same(got, _want(sc[:, :n], live, k))
+    # remove -> save -> load: size, live rows and answers are the saved index's, and a second save gives the first one's bytes
+    p1, p2 = str(tmp_path / "a.spx"), str(tmp_path / "b.spx")
+    ix.save(p1)
+    back = model.load_sparse_index(p1)
+    assert len(back) == n and back.n_live == n - 4
+    assert _same(back.search(q_ids, q_w, k), got)
+    back.save(p2)
+    assert open(p1, "rb").read() == open(p2, "rb").read()
+    ix.close()
+    back.close()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_rows_added_across_the_first_capacity_after_removals(model, dtype):
+    ids, w, q_ids, q_w, sc = _edge_data(dtype)
+    n, n_new, k, gone = 1000, 100, 8, [0, 31, 999]          # 1000 rows fit the first capacity (1024), 1100 do not: the blocks and the
+    ix = model.sparse_index(8, dtype, n_vocab=512)          # bitmap move to a new allocation
+    assert ix.add(ids[:n], w[:n]) == 0 and ix.remove(gone) == 3
+    assert ix.add(ids[n:], w[n:]) == n and len(ix) == n + n_new and ix.n_live == n + n_new - 3
+    live = np.ones(n + n_new, bool)
+    live[gone] = False
+    got = ix.search(q_ids, q_w, k)
+    assert got[0][0, :4].tolist() == [1099, 1000, 69, 32]                           # the new rows are found, the removed ones are not
+    assert not np.isin(got[0], gone).any()
+    assert _same(got, _want(sc, live, k))
+    # rows in front of the move and behind it are removable afterwards
+    assert ix.remove([1000, 32, 0]) == 2
+    live[[1000, 32]] = False
+    assert _same(ix.search(q_ids, q_w, k), _want(sc, live, k))
+    ix.close()
+
+
 def _damaged(data, dtype_code, width, n):
     """(name, bytes) of every damaged form of a good file of n rows with live words"""
     arr = sf.array_bytes(dtype_code, width, n)

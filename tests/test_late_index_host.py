@@ -261,8 +261,9 @@ def test_the_python_writer_and_parser_agree():
 def test_make_check_host_passes():
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "bert.cpp_amd"), "check-host"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert r.stdout.count("0 failure(s)") == 3 and "FAIL" not in r.stdout
+    assert r.stdout.count("0 failure(s)") == 4 and "FAIL" not in r.stdout       # the three file programs and live_bits_cases
     assert "body: a live bit at n_docs" in r.stdout and "good, past 2^41 bytes" in r.stdout
+    assert "install rejects a stray bit beyond the last row at 33" in r.stdout and "undo restores the words and the count at 1025" in r.stdout
 
 
 def test_bert_search_names_the_new_flags_and_refuses_them_without_a_token_index(tmp_path):
