@@ -201,9 +201,30 @@ __global__ void f32_attention_kernel(const float *qkv, const int32_t *cu_seqlens
     const float inv = 1.0f / sum;
     __builtin_amdgcn_wave_barrier();
     for (int e = lane; e < d; e += 64) {
-        float a = 0.f;
-        for (int j = 0; j < n; ++j) a = fmaf(qkv[(size_t)(tok0 + j) * ld + 2 * H + h * d + e], s[j], a);
-        out[(size_t)(tok0 + q) * H + h * d + e] = a * inv;
+        const float *vp = qkv + (size_t)tok0 * ld + 2 * H + h * d + e;
+        if constexpr (BIAS) {
+            // Four partial sums over the keys j = 0, 1, 2, 3 mod 4.  ONE chain of n fused multiply-adds rounds n times on a running
+            // value: at 1152 tokens with a table of N(0, 2^2) that chain alone left 2.5e-06 of a row's largest element in the hidden
+            // states of a two-layer model (NumPy float32 with the same chain; the kernel 3.0e-06), four chains of n / 4 leave
+            // 1.2e-06 — what a blocked float32 mat-mul leaves (tests/test_gpu_rel_bias_edges.py, h64-p1152-f32).  Only with a bias:
+            // the kernel without one keeps its order, and a BERT file its bits.
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+            int j = 0;
+            for (; j + 3 < n; j += 4) {
+                a0 = fmaf(vp[(size_t)j * ld], s[j], a0);
+                a1 = fmaf(vp[(size_t)(j + 1) * ld], s[j + 1], a1);
+                a2 = fmaf(vp[(size_t)(j + 2) * ld], s[j + 2], a2);
+                a3 = fmaf(vp[(size_t)(j + 3) * ld], s[j + 3], a3);
+            }
+            if (j < n) a0 = fmaf(vp[(size_t)j * ld], s[j], a0);
+            if (j + 1 < n) a1 = fmaf(vp[(size_t)(j + 1) * ld], s[j + 1], a1);
+            if (j + 2 < n) a2 = fmaf(vp[(size_t)(j + 2) * ld], s[j + 2], a2);
+            out[(size_t)(tok0 + q) * H + h * d + e] = ((a0 + a1) + (a2 + a3)) * inv;
+        } else {
+            float a = 0.f;
+            for (int j = 0; j < n; ++j) a = fmaf(qkv[(size_t)(tok0 + j) * ld + 2 * H + h * d + e], s[j], a);
+            out[(size_t)(tok0 + q) * H + h * d + e] = a * inv;
+        }
     }
 }
 

@@ -18,6 +18,7 @@ from bert_cpp_amd import pybert
 
 import layer_reference as ref
 import sparse_reference as sr
+from attention_walk import _item_of, _walks          # noqa: F401  (the walk order, shared with the relative-position-bias tests)
 from test_gpu_parity import _attention_ref
 from test_gpu_sparse import _model_file, _op_inputs
 
@@ -166,19 +167,6 @@ def test_sparse_end_to_end_at_the_slab_cap(model_dir):
 # ------------------------------------------------------------------------------------------------
 # 3c, 3d. attention: the persistent walk and long keys
 # ------------------------------------------------------------------------------------------------
-def _item_of(v, items):
-    """attention_mfma_kernel's item_of: the logical item (sentence n_head + head) that place v of the walk order takes"""
-    q8, r8, xcd = items >> 3, items & 7, v & 7
-    return (xcd * (q8 + 1) if xcd < r8 else r8 * (q8 + 1) + (xcd - r8) * q8) + (v >> 3)
-
-
-def _walks(grid, items):
-    """per workgroup the items it walks, in order"""
-    walks = [[_item_of(v, items) for v in range(g, items, grid)] for g in range(grid)]
-    assert sorted(i for w in walks for i in w) == list(range(items))
-    return walks
-
-
 def _qkv(lens, n_head, d_head, seed):
     """test_attention_kernel's values: Q times 1.7, a dominant last key per sentence"""
     rng = np.random.default_rng(seed)

@@ -34,13 +34,13 @@ def test_bucket_edges():
 def test_bucket_matches_transformers():
     torch = pytest.importorskip("torch")
     mpnet = pytest.importorskip("transformers.models.mpnet.modeling_mpnet")
-    P = rb.P_OP
+    P = rb.P_LONG                                    # (+-1151: the longest table the matrix-core launcher can serve)
     d = np.arange(-(P - 1), P)
     got = mpnet.MPNetEncoder.relative_position_bucket(torch.tensor(d), num_buckets=32, max_distance=128).numpy()
     assert np.array_equal(got, rb.bucket(d))
 
 
-@pytest.mark.parametrize("n_head,P", [(1, 1), (2, 7), (12, 512), (3, 514)])
+@pytest.mark.parametrize("n_head,P", [(1, 1), (2, 7), (12, 512), (3, 514), (2, 128), (2, 1152)])
 def test_host_expansion_is_the_table(n_head, P):
     W = rb.draw_W(n_head, seed=n_head)
     got = pybert.test_rel_bias_table(W, P)

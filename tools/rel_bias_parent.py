@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""What tests/test_gpu_rel_bias.py holds the relative position bias to, measured on the PARENT commit's library: the error of a model
-WITHOUT the tensor against the float64 model with W = 0 (the test allows a model with the tensor twice that), and the digests of
-eval_packed on two BERT files (the test demands the same bits).  Needs an MI355X.
+"""What tests/test_gpu_rel_bias.py and tests/test_gpu_rel_bias_edges.py hold the relative position bias to, measured on the PARENT
+commit's library: the error of a model WITHOUT the tensor against the float64 model with W = 0 (the tests allow a model with the tensor
+twice that) for rel_bias_reference.E2E_MODELS and E2E_EDGE_MODELS, and the digests of eval_packed on two BERT files (the test demands
+the same bits).  Needs an MI355X.
 
     python tools/rel_bias_parent.py --parent DIR
 
@@ -23,6 +24,7 @@ os.environ.setdefault("BERT_HIP_LATENCY", "128")          # (as tests/conftest.p
 
 import rel_bias_reference as rb          # noqa: E402
 import test_gpu_rel_bias as T            # noqa: E402
+import test_gpu_rel_bias_edges as TE     # noqa: E402
 
 
 def main():
@@ -48,6 +50,14 @@ def main():
             hidden[name] = max(per)
             print(f"{name}: pooled {pooled[name]:.3e}; hidden per length " + " ".join(f"{len(s)}:{e:.2e}" for s, e in zip(sents, per)))
             m.close()
+        edge_pooled, edge_hidden = {}, {}
+        for name in rb.E2E_EDGE_MODELS:
+            path = TE.edge_file(d, name, rel_bias=False)
+            m = pb.BertModel(path)
+            edge_pooled[name], per, _ = TE.edge_errors(m, rb.Model(path, use_bias=False), rb.edge_calls(name))
+            edge_hidden[name] = float(np.max(list(per.values())))
+            print(f"{name}: pooled {edge_pooled[name]:.3e}; hidden per length " + " ".join(f"{n}:{e:.2e}" for n, e in per.items()))
+            m.close()
         for which in T.PARENT_BITS:
             path, toks, cu = T.bits_case(d, which)
             m = pb.BertModel(path)
@@ -62,6 +72,9 @@ def main():
     print("PARENT_POOLED_ERROR =", fmt(pooled))
     print("PARENT_HIDDEN_ERROR =", fmt(hidden))
     print("PARENT_BITS =", bits)
+    print("tests/test_gpu_rel_bias_edges.py:")
+    print("PARENT_POOLED_ERROR =", fmt(edge_pooled))
+    print("PARENT_HIDDEN_ERROR =", fmt(edge_hidden))
 
 
 if __name__ == "__main__":
