@@ -1,5 +1,6 @@
 """The search cases of the sparse index's inverted search (bert_hip.h "Sparse index: postings and the inverted search"), shared by
-tests/test_sparse_inverted_host.py (the reference-only guard) and tests/test_gpu_sparse_inverted.py.  Rows and queries come from the
+tests/test_sparse_inverted_host.py (the reference-only guard), tests/test_gpu_sparse_inverted.py and, for case "a" at ROWS_SLICED rows,
+tests/test_gpu_sparse_inverted_order.py and tests/test_sparse_inverted_order_host.py.  Rows and queries come from the
 generators of tests/test_gpu_sparse_index.py; the reference (tests/sparse_index_reference.py) is computed once per (case, dtype, rows)
 and never changed.  No GPU, no library."""
 import numpy as np
@@ -12,6 +13,10 @@ SEG_TEST = 256          # "sparse_index_segment_rows" of the tests: 700 rows are
 SEG_DEFAULT = 2048      # the built-in segment size (sparse_index_kernels.h SPARSE_SEGMENT_ROWS)
 ROWS = 700
 ABSENT = (7, 11)        # ids no row of a case holds: query 4 asks for exactly these
+# case "a" enlarged (tests/test_gpu_sparse_inverted_order.py): 11 segments of SEG_TEST rows, the last of 130, and the NQ queries TILING
+# times over — 525 tiles of two, for which the plan cuts slices of 3, 3, 3 and 2 segments (test_sparse_inverted_order_host.py)
+ROWS_SLICED = 2690
+TILING = 15
 
 # name: (V, dtypes, width, row fill, rows, kq, query fill, skew)
 CASES = {

@@ -4,7 +4,9 @@ test_gpu_topk_order.py runs the same fixtures through index_topk_kernel, index_p
 sparse_index_scan_kernel (sparse_index.hip), test_gpu_token_index_order.py the token fixtures through token_index_scan_kernel
 (token_index.hip), test_gpu_token_scan_forms.py the int8, masked and listed token fixtures through that kernel's other four
 instantiations, test_gpu_hybrid_order.py the hybrid fixtures — a dense and a sparse index that carry one pattern together or alone —
-through sparse_hybrid_scan_kernel (sparse_index.hip) behind index_scores_kernel and mask_and_kernel (search.hip).
+through sparse_hybrid_scan_kernel (sparse_index.hip) behind index_scores_kernel and mask_and_kernel (search.hip),
+test_gpu_sparse_inverted_order.py the sparse fixtures through sparse_postings_scan_kernel (sparse_postings.hip) under the geometries of
+INVERTED_CELLS, which test_sparse_inverted_order_host.py proves on the CPU.
 
 The kernels select alike.  A query's current top-k stands in slots [0, k) of an LDS list of L entries; a (score, id) threshold — the
 k-th best at the last sort, (-inf, INT_MAX) before the first — lives in registers; every row that ranks before the threshold is
@@ -129,7 +131,7 @@ def _better(s, i, ts, ti):
     return (s > ts) | ((s == ts) & (i < ti))
 
 
-def walk(scores, ids, ok, k, L, step, slack=0):
+def walk(scores, ids, ok, k, L, step, slack=0, forget=0):
     """One workgroup: scores [nq, n] f32 of its nq queries against its n rows in the order it meets them, ids [n], ok [n] or [nq, n]
     (False: the row is removed, disallowed or an empty entry, and never pushed).  Pushes and sorts only.  Returns
       steps, sorts (not counting the one behind the last step), sort_steps (the steps that ended in a sort),
@@ -138,7 +140,9 @@ def walk(scores, ids, ok, k, L, step, slack=0):
       sorted, and the next step pushed `step` rows), pushed_late [nq] (a push after the first sort),
       ids / scores [nq, k] (the lists at the end, best first; SENT / -inf where empty).
     slack is 0 for every kernel.  slack > 0 is a deliberately WRONG queue, for test_topk_order_host.py's sensitivity checks alone: it
-    sorts only when a count exceeds room + slack, and a push behind slot L - 1 — the list has L entries — is lost."""
+    sorts only when a count exceeds room + slack, and a push behind slot L - 1 — the list has L entries — is lost.  forget > 0 is
+    another WRONG queue, for test_sparse_inverted_order_host.py's: at the start of every forget-th step — a segment edge of
+    sparse_postings_scan_kernel — the counts go back to 0 unsorted, and what stood behind the top-k is lost."""
     scores = np.ascontiguousarray(scores, dtype=np.float32)
     nq, n = scores.shape
     ids = np.asarray(ids, dtype=np.int64)
@@ -180,6 +184,10 @@ def walk(scores, ids, ok, k, L, step, slack=0):
     n_steps = (n + step - 1) // step
     for t in range(n_steps):
         sl = slice(t * step, min(n, (t + 1) * step))
+        if forget and t and t % forget == 0:                         # (the wrong queue: the edge forgets what was not sorted)
+            que_s, que_i = [[] for _ in range(U)], [[] for _ in range(U)]
+            cnt[:] = 0
+            prev_fit[:] = room == 0
         for u in range(U):
             s, i = scores[first[u], sl], ids[sl]
             m = ok[first[u], sl] & _better(s, i, ts[u], ti[u])
@@ -232,8 +240,9 @@ def merge(list_s, list_i, k):
 
 
 def sliced_search(S, ok, k, tile, slices, slice_rows, L, step):
-    """index_topk_kernel (tile 32, step 128) or sparse_index_scan_kernel (tile qb, step 256) over S [nq, n], one walk per (slice, tile
-    of queries), then the merge of the slices' lists.  Returns wgs (the walks), merge (as merge()), ids / scores [nq, k]."""
+    """index_topk_kernel (tile 32, step 128), sparse_index_scan_kernel or sparse_hybrid_scan_kernel (tile qb, step 256), or
+    sparse_postings_scan_kernel (tile qb, step 256, slice_rows = slice_segs * seg: postings_search below) over S [nq, n]: one walk per
+    (slice, tile of queries), then the merge of the slices' lists.  Returns wgs (the walks), merge (as merge()), ids / scores [nq, k]."""
     S = np.ascontiguousarray(S, dtype=np.float32)
     nq, n = S.shape
     ok = np.broadcast_to(np.asarray(ok, dtype=bool), (nq, n))
@@ -1164,6 +1173,135 @@ def listed_search(S, cand, valid, k, n_slices, slice_pos, positions_for_ids=Fals
             list_s[q, sl], list_i[q, sl] = w["scores"][0], w["ids"][0]
     m = merge(list_s.reshape(nq, -1), list_i.reshape(nq, -1), k)
     return dict(wgs=wgs, merge=m, ids=m["ids"], scores=m["scores"], slices=n_slices)
+
+
+# ------------------------------------------------------------------------------------------------
+# inverted fixtures: sparse_postings_scan_kernel (sparse_postings.hip)
+# ------------------------------------------------------------------------------------------------
+# The inverted scan selects with the row-major scan's constants (steps of 256 rows, sparse_L(k) entries, the same sort trigger), but its
+# workgroup walks a slice of whole SEGMENTS and carries the thresholds, the counts and the queue over every segment edge, with the
+# accumulators zeroed in between.  Its fixtures are the sparse ones (sparse_fixture, many_sparse_rows); what is new is the geometry they
+# run under: the segment size ("sparse_index_segment_rows", read by invert), the number of queries (which decides how many segments a
+# workgroup walks) and the tile ("sparse_index_qb").  INVERTED_CELLS lists every (seg, nq, tile key, k, mode) that
+# test_gpu_sparse_inverted_order.py runs with what the cell is there to reach; test_sparse_inverted_order_host.py proves each claim
+# with the plan's hook and the model.
+INVERTED_QCHUNK = 4096                   # queries per internal pass (sparse_index.h SparseIndex::QCHUNK)
+INVERTED_LDS_STATIC = 65536              # what a kernel gets without hipFuncSetAttribute
+INVERTED_ONE_SEG = 4096                  # the 4000-row fixtures are one (partial) segment
+INVERTED_NQS = (1, 2, 3, 5)
+INVERTED_WALKED = ((256, 4096), (1024, 4096), (256, 4097), (1024, 4097), (256, 600))          # (seg, nq)
+INVERTED_WALKED_KS = (1, 128, 129, 256)
+INVERTED_TILES = (1, 2, 3, 4, 8)
+INVERTED_TILE_SEGS = (256, 4096)
+INVERTED_TILE_K = 128
+INVERTED_BIG_ROWS = 16384 + 300          # two segments of 16384 rows, three of 8192
+INVERTED_BIG = ((16384, 10, 2), (16384, 256, 2), (8192, 10, 4), (8192, 256, 3))               # (seg, k, the tile under the key 4)
+INVERTED_BIG_QB = 4
+INVERTED_BIG_NQS = (1, 5, 8)
+INVERTED_BIG_GONE = np.arange(16384 - 100, 16384 + 100)                                     # the rows removed around the segment edge
+
+
+class InvertedCell:
+    """One launch geometry of the GPU file.  section: "one" (a single segment), "walked" (a workgroup walks several segments), "tiles".
+    reach: the states the cell is there for, each asserted by test_sparse_inverted_order_host.py —
+      one_segment      one slice of one segment
+      walks_all        the first chunk is ONE slice of all (> 1) segments: every step of seg 256 is a segment edge
+      second_chunk     a second chunk of one query, cut into one slice per segment
+      several          slice_segs > 1 and n_slices > 1
+      short_last       the last slice has fewer segments than the others
+      partial_segment  the last segment is partial
+      fit              every one-slice workgroup of a busy query ends a step with count == room, unsorted, and pushes a whole step
+                       (fresh for the masked modes, stale for plain), up to slot L - 1; the near miss is sorted
+      tile=N           the tile the plan gives"""
+
+    def __init__(self, section, seg, nq, qb, k, mode, reach):
+        self.section, self.seg, self.nq, self.qb, self.k, self.mode, self.reach = section, seg, nq, qb, k, mode, frozenset(reach)
+
+    def __repr__(self):
+        return f"{self.section} seg={self.seg} nq={self.nq} qb={self.qb} k={self.k} {self.mode}"
+
+
+def _inverted_cells():
+    out = []
+    for mode in MODES:
+        for k in SPARSE_KS:
+            for nq in INVERTED_NQS:
+                out.append(InvertedCell("one", INVERTED_ONE_SEG, nq, 0, k, mode, {"one_segment", "partial_segment", "fit", f"tile={min(2, nq)}"}))
+        for k in INVERTED_WALKED_KS:
+            for seg, nq in INVERTED_WALKED:
+                reach = {"partial_segment", "tile=2"}
+                reach |= {"several", "short_last"} if nq < INVERTED_QCHUNK else {"walks_all", "fit"}
+                if nq > INVERTED_QCHUNK:
+                    reach |= {"second_chunk"}
+                out.append(InvertedCell("walked", seg, nq, 0, k, mode, reach))
+    for mode in ("plain", "allow"):
+        for seg in INVERTED_TILE_SEGS:
+            for n in INVERTED_TILES:
+                for nq in sorted({n - 1, n, n + 1, 70} - {0}):
+                    reach = {"partial_segment", f"tile={min(n, 4, nq)}"} | ({"one_segment", "fit"} if seg == INVERTED_ONE_SEG else set())
+                    out.append(InvertedCell("tiles", seg, nq, n, INVERTED_TILE_K, mode, reach))
+    return out
+
+
+INVERTED_CELLS = _inverted_cells()
+
+
+def inverted_cells(section, **match):
+    return [c for c in INVERTED_CELLS if c.section == section and all(getattr(c, a) == v for a, v in match.items())]
+
+
+def postings_plan(hook, dtype, n_rows, nq, k, seg, qb=0, n_vocab=SPARSE_V):
+    """[(c0, c, g)]: the chunks of a call of nq queries (SparseIndex::QCHUNK) and each chunk's geometry from the library's own plan
+    (hook = pybert.test_sparse_postings_geometry), with seg, n_segs and slice_rows added"""
+    out = []
+    for c0 in range(0, nq, INVERTED_QCHUNK):
+        c = min(INVERTED_QCHUNK, nq - c0)
+        g = dict(hook(dtype, n_vocab, n_rows, c, k, seg, qb))
+        assert g["L"] == sparse_L(k) and seg % SPARSE_STEP == 0
+        g["seg"], g["n_segs"], g["slice_rows"] = seg, -(-n_rows // seg), g["slice_segs"] * seg
+        out.append((c0, c, g))
+    return out
+
+
+def postings_search(S, ok, k, g):
+    """sparse_postings_scan_kernel and the merge over S [nq, n], the queries of ONE chunk under its geometry g (postings_plan): sliced_search
+    with the tile, the slices of slice_segs whole segments and the row-major scan's step and list.  A segment is whole steps, so the steps
+    of a slice are those of its rows, and a workgroup's thresholds, counts and queue live on over the segment edges."""
+    return sliced_search(S, ok, k, g["qb"], g["n_slices"], g["slice_rows"], g["L"], SPARSE_STEP)
+
+
+def inverted_period(kinds, tile):
+    """queries after which the tiles of any layouts() list repeat: a multiple of the tile, of the kinds (mixed) and of the two idle kinds"""
+    return tile * len(kinds) * 2
+
+
+def check_inverted_geometry(cell, n_rows, plan):
+    """the geometric claims of a cell on its chunks' geometries"""
+    g = plan[0][2]
+    n_segs, reach = g["n_segs"], cell.reach
+    tile = [int(r.split("=")[1]) for r in reach if r.startswith("tile=")]
+    assert len(tile) == 1 and g["qb"] == tile[0] and g["n_qtiles"] == -(-plan[0][1] // tile[0]), (cell, g)
+    assert ("one_segment" in reach) == (n_segs == 1) and ("partial_segment" in reach) == (n_rows % cell.seg != 0), (cell, g)
+    assert ("walks_all" in reach) == (n_segs > 1 and g["n_slices"] == 1 and g["slice_segs"] == n_segs), (cell, g)
+    assert ("several" in reach) == (g["slice_segs"] > 1 and g["n_slices"] > 1), (cell, g)
+    assert ("short_last" in reach) == (g["n_slices"] > 1 and n_segs % g["slice_segs"] != 0), (cell, g)
+    assert ("second_chunk" in reach) == (len(plan) == 2), (cell, plan)
+    if len(plan) == 2:
+        c0, c, g1 = plan[1]
+        assert (c0, c) == (INVERTED_QCHUNK, 1) and g1["qb"] == 1 and g1["slice_segs"] == 1 and g1["n_slices"] == n_segs > 1, (cell, g1)
+    for _, _, gg in plan:
+        assert gg["lds"] <= 160 * 1024 - 256 and gg["n_slices"] <= gg["max_slices"], (cell, gg)
+
+
+def big_inverted_rows(dtype, n=INVERTED_BIG_ROWS):
+    """(term ids [n, 1], weights [n, 1], scores by kind) of the large-segment index: term 0 with weight 1 + r (f32: many_sparse_rows) or the
+    value of rank 1 + r // 3 (f16: rising in ties of three, inside VALUES); asc / desc / const as many_scores"""
+    ids, w = many_sparse_rows(n)
+    if dtype == "f16":
+        w = values(1 + np.arange(n) // 3)[:, None].astype(np.float32)
+        assert np.array_equal(w.astype(np.float16).astype(np.float32), w)
+    v = w[:, 0]
+    return ids, w, {"asc": v, "desc": -v, "const": np.zeros(n, np.float32)}
 
 
 # ------------------------------------------------------------------------------------------------
