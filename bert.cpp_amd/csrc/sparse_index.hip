@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "device.h"
+#include "hybrid_score.h"
 #include "kernels.h"
 #include "sparse_index_kernels.h"
 #include "topk_select.h"
@@ -120,15 +121,6 @@ __global__ __launch_bounds__(256) void sparse_query_kernel(SparseQueryArgs a) {
     __syncthreads();
     u32x4 *dst = (u32x4 *)(a.images + (size_t)q * a.img_bytes);
     for (unsigned i = t; i < a.img_bytes / 16; i += 256) dst[i] = ((const u32x4 *)smem)[i];
-}
-
-// The hybrid score H = (w_dense * D) + (w_sparse * S) of bert_hip.h: two f32 multiplications and one f32 addition, each rounded to
-// nearest even, never an fma (contraction is off for this block, whatever the translation unit's default)
-__device__ __forceinline__ float hybrid_score(float w_dense, float d, float w_sparse, float s) {
-#pragma clang fp contract(off)
-    const float x = w_dense * d;
-    const float y = w_sparse * s;
-    return x + y;
 }
 
 // The scan's body, shared by sparse_index_scan_kernel and sparse_hybrid_scan_kernel.

@@ -252,14 +252,22 @@ struct SparsePostingsScanArgs {
     int *ws_i;
     int n_rows, width, n_vocab, seg, nq, qb, n_qtiles, n_slices, slice_segs, k, L, n_items;
     const uint32_t *live, *allow;       // as SparseScanArgs's: read by the masked instantiation only
+    // the hybrid scan only (sparse_postings_hybrid_scan_kernel), as SparseScanArgs's and last in the block as there: the dense scores
+    // of the chunk's queries, [nq][ld] with GLOBAL row r's at column r — read for qualifying rows alone —, and the two weights
+    const float *dscores = nullptr;
+    size_t ld = 0;
+    float w_dense = 0.f, w_sparse = 0.f;
 };
 
-// lets the postings scan of the current device have SPARSE_LDS_MAX of LDS
+// lets the postings scans of the current device have SPARSE_LDS_MAX of LDS
 void sparse_postings_kernels_init();
 // count, scan and fill of all segments of a.n_rows rows, in that order on s; a.off zeroed and a.cur = a.off copied in between
 void launch_sparse_postings_build(int dtype, const SparsePostingsBuildArgs &a, hipStream_t s);
 void launch_sparse_query_sort(const SparseQuerySortArgs &a, hipStream_t s);
 // the masked instantiation iff a.live or a.allow is set
 void launch_sparse_postings_scan(int dtype, const SparsePostingsScanArgs &a, size_t lds, hipStream_t s);
+// sparse_postings_hybrid_scan_kernel: the same plan and LDS, selecting by hybrid_score(a.dscores, accumulator); masked iff a.live or
+// a.allow is set
+void launch_sparse_postings_hybrid_scan(int dtype, const SparsePostingsScanArgs &a, size_t lds, hipStream_t s);
 
 }  // namespace bert_hip

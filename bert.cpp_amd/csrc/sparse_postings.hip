@@ -14,6 +14,9 @@
 //                         together, one per lane, then term after term the wave reads that list coalesced and runs
 //                         acc[row] = fmaf(w, qw, acc[row]) in LDS —; then all lanes walk the segment's rows, 256 per step, and select
 //                         with the row-major scan's code: thresholds in registers, a queue behind the top-k, bitonic_sort_lists.
+//   sparse_postings_hybrid_scan_kernel<DTYPE, MASKED>   the same body as the second pass of a hybrid search over the postings
+//                         (hybrid.cpp): a row is selected by hybrid_score(D, accumulator), D read from the matrix index_scores_kernel
+//                         (search.hip) wrote, at [query inside the chunk][global row], a step ahead of its use.
 //
 // The one rule: all updates of one accumulator happen in ascending term id, so a row's chain is the score rule of bert_hip.h and its
 // bits are the row-major search's.  Inside one list every entry is another row, so the lanes of one instruction, and the passes over
@@ -31,6 +34,7 @@
 #include <type_traits>
 
 #include "device.h"
+#include "hybrid_score.h"
 #include "kernels.h"
 #include "sparse_index_kernels.h"
 #include "topk_select.h"
@@ -124,8 +128,22 @@ __global__ __launch_bounds__(256) void sparse_query_sort_kernel(SparseQuerySortA
     if (t == 0) a.tn[q] = count;
 }
 
-template <int DTYPE, bool MASKED>
-__global__ __launch_bounds__(NT) void sparse_postings_scan_kernel(SparsePostingsScanArgs a) {
+// When the hybrid scan asks for a step's dense scores: 1 = one step ahead — the first step's before the segment's term walk, each
+// later step's at the top of the step before it —, 0 = at the top of the step that uses them (the A/B of DESIGN.md §15.1)
+#ifndef SPARSE_POSTINGS_D_AHEAD
+#define SPARSE_POSTINGS_D_AHEAD 1
+#endif
+
+// The scan's body, shared by sparse_postings_scan_kernel and sparse_postings_hybrid_scan_kernel.
+// HYBRID (the second pass of a hybrid search over the postings, hybrid.cpp): in the row walk a lane whose row qualifies holds its
+// row's dense score of each query of the tile, read from a.dscores at [query inside the chunk][GLOBAL row] (lane = row: one coalesced
+// 1 KiB access per query and step), and the score the row is selected by is hybrid_score(D, accumulator) in place of the
+// accumulator.  A lane whose row does not qualify, or lies at or beyond n_rows, reads nothing — the dense pass may not have written
+// there.  The loads are issued a step ahead, into registers: the first step's before the term walk, whose length hides them (and
+// which the waves without a query of their own only wait for), each later step's at the top of the step before it, so that no
+// step waits for the HBM.  No LDS beyond the plain scan's: sparse_postings_geometry is the plan of both.
+template <int DTYPE, bool MASKED, bool HYBRID>
+__device__ __forceinline__ void sparse_postings_scan_body(const SparsePostingsScanArgs &a) {
     using w_t = typename Stored<DTYPE>::w_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // (the row-major scan's XCD map: the query tiles of one slice go to one XCD and find the slice's postings in its L2)
@@ -162,8 +180,40 @@ __global__ __launch_bounds__(NT) void sparse_postings_scan_kernel(SparsePostings
 
     // a step pushes at most SPARSE_STEP_ROWS entries per query: sort before a queue could hold fewer free slots
     const int room = L - k - SPARSE_STEP_ROWS;
+    // does row r0 + lrow of a segment of nrow rows qualify (lrow < seg: a step never leaves the segment)
+    auto qualifies = [&](int lrow, int row, int nrow) -> bool {
+        bool ok = lrow < nrow;
+        if constexpr (MASKED) {
+            if (ok) {
+                uint32_t m = ~0u;
+                if (a.live) m &= a.live[row >> 5];
+                if (a.allow) m &= a.allow[row >> 5];
+                ok = (m >> (row & 31)) & 1u;
+            }
+        }
+        return ok;
+    };
+    // HYBRID: the dense scores of a qualifying row, one per query of the tile.  One branch around all of them and none between them —
+    // a place behind the tile's last query reads that query's score again (inside the matrix, and never used) —, so that the loads
+    // go out together: behind a branch of its own each load would be waited for before the next is issued
+    auto load_dense = [&](bool ok, int row, float (&d)[QB_MAX]) {
+#pragma unroll
+        for (int q = 0; q < QB_MAX; ++q) d[q] = 0.f;
+        if (ok) {
+            const float *p = a.dscores + (size_t)q0 * a.ld + row;
+#pragma unroll
+            for (int q = 0; q < QB_MAX; ++q) d[q] = p[(size_t)min(q, nqv - 1) * a.ld];
+        }
+    };
     for (int sg = s0; sg < s1; ++sg) {
         const int r0 = sg * seg, nrow = min(seg, a.n_rows - r0);
+        // HYBRID: the first step's row state and dense scores, asked for ahead of the walk
+        [[maybe_unused]] float dv[QB_MAX];
+        [[maybe_unused]] bool dok = false;
+        if constexpr (HYBRID && SPARSE_POSTINGS_D_AHEAD) {
+            dok = qualifies(tid, r0 + tid, nrow);
+            load_dense(dok, r0 + tid, dv);
+        }
         // 1. zero the accumulators (the barrier that ends the previous segment's last step stands in front)
         for (int i = tid * 4; i < nqv * seg; i += NT * 4) *(f32x4 *)(acc + i) = f32x4{0.f, 0.f, 0.f, 0.f};
         __syncthreads();
@@ -204,19 +254,23 @@ __global__ __launch_bounds__(NT) void sparse_postings_scan_kernel(SparsePostings
         // 3. all lanes walk the segment's rows
         for (int b0 = 0; b0 < nrow; b0 += SPARSE_STEP_ROWS) {
             const int lrow = b0 + tid, row = r0 + lrow;        // (lrow < seg: b0 and seg are multiples of the step)
-            bool rok = lrow < nrow;
-            if constexpr (MASKED) {
-                if (rok) {
-                    uint32_t m = ~0u;
-                    if (a.live) m &= a.live[row >> 5];
-                    if (a.allow) m &= a.allow[row >> 5];
-                    rok = (m >> (row & 31)) & 1u;
-                }
+            bool rok;
+            [[maybe_unused]] float dn[QB_MAX];
+            [[maybe_unused]] bool nok = false;
+            if constexpr (HYBRID && SPARSE_POSTINGS_D_AHEAD) {
+                rok = dok;
+                // the next step's, before this step's selection (a step behind the segment's last has no rows: nothing is asked for)
+                nok = b0 + SPARSE_STEP_ROWS < nrow && qualifies(lrow + SPARSE_STEP_ROWS, row + SPARSE_STEP_ROWS, nrow);
+                load_dense(nok, row + SPARSE_STEP_ROWS, dn);
+            } else {
+                rok = qualifies(lrow, row, nrow);
+                if constexpr (HYBRID) load_dense(rok, row, dv);
             }
 #pragma unroll
             for (int q = 0; q < QB_MAX; ++q)
                 if (q < nqv) {
-                    const float s = acc[q * seg + lrow];
+                    float s = acc[q * seg + lrow];
+                    if constexpr (HYBRID) s = hybrid_score(a.w_dense, dv[q], a.w_sparse, s);
                     if (rok && better(s, row, ts[q], ti[q])) {
                         const int p = atomicAdd(&cnt[q], 1);
                         ls[q * L + k + p] = s;
@@ -232,6 +286,11 @@ __global__ __launch_bounds__(NT) void sparse_postings_scan_kernel(SparsePostings
                     if (q < nqv) { ts[q] = ls[q * L + k - 1]; ti[q] = li[q * L + k - 1]; }
                 __syncthreads();
             }
+            if constexpr (HYBRID && SPARSE_POSTINGS_D_AHEAD) {
+                dok = nok;
+#pragma unroll
+                for (int q = 0; q < QB_MAX; ++q) dv[q] = dn[q];
+            }
         }
     }
     __syncthreads();
@@ -244,6 +303,12 @@ __global__ __launch_bounds__(NT) void sparse_postings_scan_kernel(SparsePostings
     }
 }
 
+template <int DTYPE, bool MASKED>
+__global__ __launch_bounds__(NT) void sparse_postings_scan_kernel(SparsePostingsScanArgs a) { sparse_postings_scan_body<DTYPE, MASKED, false>(a); }
+
+template <int DTYPE, bool MASKED>
+__global__ __launch_bounds__(NT) void sparse_postings_hybrid_scan_kernel(SparsePostingsScanArgs a) { sparse_postings_scan_body<DTYPE, MASKED, true>(a); }
+
 DeviceFlags g_postings_lds;
 
 }  // namespace
@@ -255,7 +320,9 @@ void sparse_postings_kernels_init() {
     configure_once(g_postings_lds, [] {
         bool ok = true;
         for (const void *f : {(const void *)sparse_postings_scan_kernel<0, false>, (const void *)sparse_postings_scan_kernel<1, false>,
-                              (const void *)sparse_postings_scan_kernel<0, true>, (const void *)sparse_postings_scan_kernel<1, true>})
+                              (const void *)sparse_postings_scan_kernel<0, true>, (const void *)sparse_postings_scan_kernel<1, true>,
+                              (const void *)sparse_postings_hybrid_scan_kernel<0, false>, (const void *)sparse_postings_hybrid_scan_kernel<1, false>,
+                              (const void *)sparse_postings_hybrid_scan_kernel<0, true>, (const void *)sparse_postings_hybrid_scan_kernel<1, true>})
             ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPARSE_LDS_MAX) == hipSuccess && ok;
         if (!ok) (void)hipGetLastError();                      // (a launch that cannot have its LDS fails, and the search reports it)
     });
@@ -287,6 +354,15 @@ void launch_sparse_postings_scan(int dtype, const SparsePostingsScanArgs &a, siz
     else if (dtype == 1) BERT_LAUNCH((sparse_postings_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
     else if (masked) BERT_LAUNCH((sparse_postings_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
     else BERT_LAUNCH((sparse_postings_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
+}
+
+void launch_sparse_postings_hybrid_scan(int dtype, const SparsePostingsScanArgs &a, size_t lds, hipStream_t s) {
+    const int grid = (a.n_items + 7) / 8 * 8;
+    const bool masked = a.live || a.allow;
+    if (dtype == 1 && masked) BERT_LAUNCH((sparse_postings_hybrid_scan_kernel<1, true>), dim3(grid), dim3(NT), lds, s, a);
+    else if (dtype == 1) BERT_LAUNCH((sparse_postings_hybrid_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
+    else if (masked) BERT_LAUNCH((sparse_postings_hybrid_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
+    else BERT_LAUNCH((sparse_postings_hybrid_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
 }
 
 }  // namespace bert_hip

@@ -7,13 +7,15 @@
 //               [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N]
 //   bert-search -m MODEL -f TEXTS --late [--i8] [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]
 //   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [--inverted] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
-//   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]
+//   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--postings] [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]
 //   (--hybrid SPLADE: hybrid search.  SPLADE is a second model file, one with the MLM head, loaded into a context of its own (it may be
 //   the same file as DENSE).  Every line goes into an embedding index of DENSE (bert_hip_index_add_texts; --f32 / --i8 / --b1 as
 //   below) and, with its W largest terms (--sparse-width, default 128, 1 .. 256), into a sparse index of SPLADE
 //   (bert_hip_sparse_index_add_texts; --f16: u16 ids and f16 weights).  Each query line is answered by bert_hip_hybrid_search_texts:
 //   the exact top-k of WD * (dense score) + WS * (sparse score) over all lines (--weights, default 1,1; finite numbers), the query's W
-//   largest terms on the sparse side.  Not together with --sparse, --lists, --nprobe, --rescore, --long, --maxsim, --cross, --save, --load.)
+//   largest terms on the sparse side.  --postings: the sparse index's postings are built once the lines are in
+//   (bert_hip_sparse_index_invert) and each query goes through bert_hip_dense_sparse_search_inverted_texts — the same lines, the same
+//   scores; it goes with --hybrid only (the sparse mode's own switch is --inverted).  Not together with --sparse, --lists, --nprobe, --rescore, --long, --maxsim, --cross, --save, --load.)
 //   (--sparse [WIDTH]: learned sparse search.  MODEL must carry the MLM head (bert_hip.h "learned sparse embeddings"); every line's WIDTH
 //   largest terms (default 128, 1 .. 256) go into a sparse index (bert_hip_sparse_index_add_texts; --f16: u16 ids and f16 weights),
 //   each query line is searched with its WIDTH largest terms (bert_hip_sparse_index_search_texts), and the output has the dense mode's
@@ -77,10 +79,11 @@ void usage(const char *argv0) {
     fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --late [--i8] [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [--inverted] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
-    fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]\n", argv0);
+    fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--postings] [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]\n", argv0);
     fprintf(stderr, "  --hybrid SPLADE: hybrid search: the lines in an embedding index of DENSE and a sparse index of SPLADE (a model file with the MLM head; W\n"
                     "          terms a line, default 128), each query answered by bert_hip_hybrid_search_texts: the exact top-k of WD * dense + WS * sparse\n"
-                    "          (default 1,1).  Not with --sparse, --lists, --nprobe, --rescore, --long, --maxsim, --cross, --save, --load.\n");
+                    "          (default 1,1).  --postings builds the sparse index's postings and answers through them (the same output).\n"
+                    "          Not with --sparse, --lists, --nprobe, --rescore, --long, --maxsim, --cross, --save, --load.\n");
     fprintf(stderr, "  --sparse [WIDTH]: learned sparse search with a model that carries the MLM head: each line's and each query's WIDTH largest terms\n"
                     "          (default 128, 1 .. 256) through a sparse index (bert_hip_sparse_index_*); --f16 stores u16 ids and f16 weights;\n"
                     "          --save PATH writes the sparse index once it is built, --load PATH reads it instead of encoding TEXTS (still read for printing);\n"
@@ -113,7 +116,7 @@ int main(int argc, char **argv) {
     float w_dense = 1.f, w_sparse = 1.f;
     bool weights_ok = true;
     int k = 3, n_threads = 6, dtype = 1, n_cand = 0, n_lists = 0, nprobe = 0, window = 0, stride = 0, n_maxsim = 0, n_cross = 0;
-    bool long_texts = false, maxsim = false, cross = false, sparse = false, sparse_f16 = false, token_index = false, late = false, inverted = false;
+    bool long_texts = false, maxsim = false, cross = false, sparse = false, sparse_f16 = false, token_index = false, late = false, inverted = false, postings = false;
     int sparse_width = 128;
     for (int i = 1; i < argc; ++i) {
         const bool has_value = i + 1 < argc;
@@ -138,6 +141,7 @@ int main(int argc, char **argv) {
         }
         else if (!strcmp(argv[i], "--f16")) sparse_f16 = true;
         else if (!strcmp(argv[i], "--inverted")) inverted = true;
+        else if (!strcmp(argv[i], "--postings")) postings = true;
         else if (!strcmp(argv[i], "--hybrid") && has_value) hybrid_model = argv[++i];
         else if (!strcmp(argv[i], "--sparse-width") && has_value) sparse_width = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--weights") && has_value) {
@@ -173,7 +177,8 @@ int main(int argc, char **argv) {
         fprintf(stderr, "search: --hybrid goes with -m, -f, -k, -t, --sparse-width, --weights, --f32, --i8, --b1 and --f16 only\n");
         return 2;
     }
-    if (inverted && hybrid_model) { fprintf(stderr, "search: --inverted does not go with --hybrid: a hybrid search reads the rows, not the postings\n"); return 2; }
+    if (inverted && hybrid_model) { fprintf(stderr, "search: --inverted does not go with --hybrid: a hybrid search over the postings is --hybrid SPLADE --postings\n"); return 2; }
+    if (postings && !hybrid_model) { fprintf(stderr, "search: --postings goes with --hybrid (the sparse mode's switch is --inverted)\n"); return 2; }
     if (inverted && !sparse) { fprintf(stderr, "search: --inverted goes with --sparse\n"); return 2; }
     if (hybrid_model && (sparse_width < 1 || sparse_width > 256)) { fprintf(stderr, "search: --hybrid: --sparse-width must be 1 .. 256\n"); return 2; }
     if (hybrid_model && !weights_ok) { fprintf(stderr, "search: --hybrid: --weights takes two finite numbers, WD,WS\n"); return 2; }
@@ -249,6 +254,7 @@ int main(int argc, char **argv) {
         if (!dx || bert_hip_index_add_texts(dx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) return fail("could not build the index");
         bert_hip_sparse_index *sx = bert_hip_sparse_index_create(sparse_ctx, 0, sparse_width, sparse_f16 ? 1 : 0);
         if (!sx || bert_hip_sparse_index_add_texts(sx, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) return fail("could not build the sparse index");
+        if (postings && bert_hip_sparse_index_invert(sx) < 0) return fail("could not build the postings");
         printf("Loaded %zu lines.\n", texts.size());
         std::vector<int32_t> hids((size_t)k);
         std::vector<float> hscores((size_t)k);
@@ -260,7 +266,9 @@ int main(int argc, char **argv) {
             q = chomp(q);
             if (q == "q") break;
             const char *qp = q.c_str();
-            if (bert_hip_hybrid_search_texts(dx, sx, n_threads, 1, &qp, sparse_width, w_dense, w_sparse, k, hids.data(), hscores.data()) != 0) return fail("the search failed");
+            if ((postings ? bert_hip_dense_sparse_search_inverted_texts(dx, sx, n_threads, 1, &qp, sparse_width, w_dense, w_sparse, k, hids.data(), hscores.data())
+                          : bert_hip_hybrid_search_texts(dx, sx, n_threads, 1, &qp, sparse_width, w_dense, w_sparse, k, hids.data(), hscores.data())) != 0)
+                return fail("the search failed");
             printf("\nClosest texts:\n");
             for (int i = 0; i < k && hids[i] >= 0; ++i) printf("%d. %s\n (similarity score: %.4f)\n", i + 1, texts[hids[i]].c_str(), hscores[i]);
         }

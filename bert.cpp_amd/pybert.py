@@ -51,6 +51,7 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_sparse_index_invert", "bert_hip_sparse_index_inverted_rows", "bert_hip_sparse_index_search_inverted",
     "bert_hip_sparse_index_search_inverted_device", "bert_hip_sparse_index_search_inverted_texts",
     "bert_hip_hybrid_reserve", "bert_hip_hybrid_search", "bert_hip_hybrid_search_device", "bert_hip_hybrid_search_texts",
+    "bert_hip_dense_sparse_search_inverted", "bert_hip_dense_sparse_search_inverted_device", "bert_hip_dense_sparse_search_inverted_texts",
     "bert_hip_token_index_create", "bert_hip_token_index_free", "bert_hip_token_index_size", "bert_hip_token_index_n_tokens",
     "bert_hip_token_index_max_query_tokens", "bert_hip_token_index_reserve", "bert_hip_token_index_add", "bert_hip_token_index_add_device",
     "bert_hip_token_index_add_texts", "bert_hip_token_index_get_doc", "bert_hip_token_index_search", "bert_hip_token_index_search_device",
@@ -240,6 +241,13 @@ def _declare_product_abi(L):
     L.bert_hip_hybrid_search_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, f32, f32, vp, i32, i32, vp, vp, vp]
     L.bert_hip_hybrid_search_texts.restype = i32
     L.bert_hip_hybrid_search_texts.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_char_p), i32, f32, f32, i32, vp, vp]
+    # (the same searches over the sparse index's postings: the argument lists of the three above)
+    L.bert_hip_dense_sparse_search_inverted.restype = i32
+    L.bert_hip_dense_sparse_search_inverted.argtypes = list(L.bert_hip_hybrid_search.argtypes)
+    L.bert_hip_dense_sparse_search_inverted_device.restype = i32
+    L.bert_hip_dense_sparse_search_inverted_device.argtypes = list(L.bert_hip_hybrid_search_device.argtypes)
+    L.bert_hip_dense_sparse_search_inverted_texts.restype = i32
+    L.bert_hip_dense_sparse_search_inverted_texts.argtypes = list(L.bert_hip_hybrid_search_texts.argtypes)
     i64 = C.c_int64
     L.bert_hip_token_index_create.restype = vp; L.bert_hip_token_index_create.argtypes = [vp, i32]
     L.bert_hip_token_index_free.restype = None; L.bert_hip_token_index_free.argtypes = [vp]
@@ -1608,10 +1616,7 @@ class BertIndex:
         if r != 0:
             self._hybrid_fail("bert_hip_hybrid_reserve", r)
 
-    def hybrid_search(self, sparse: "BertSparseIndex", queries, q_ids, q_weights, k: int = 10, w_dense: float = 1.0, w_sparse: float = 1.0,
-                      allow=None):
-        """The exact top-k of (w_dense * dense score) + (w_sparse * sparse score) over the rows live in both indexes and allowed:
-        queries [n, dim] f32, (q_ids, q_weights) [n, kq] as BertSparseIndex.search takes them, allow as BertIndex.search's."""
+    def _hybrid_search(self, entry: str, sparse: "BertSparseIndex", queries, q_ids, q_weights, k, w_dense, w_sparse, allow):
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         q_ids, q_weights = BertSparseIndex._terms(q_ids, q_weights)
         if q_ids.shape[0] != q.shape[0]:
@@ -1620,12 +1625,28 @@ class BertIndex:
         ids = np.empty((nq, max(k, 1)), dtype=np.int32)
         scores = np.empty((nq, max(k, 1)), dtype=np.float32)
         words = None if allow is None else allow_words(allow, len(self))
-        r = self.lib.bert_hip_hybrid_search(self.ix, sparse.ix, nq, q.ctypes.data, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data,
-                                            w_dense, w_sparse, None if words is None else words.ctypes.data, 0 if words is None else len(words),
-                                            k, ids.ctypes.data, scores.ctypes.data)
+        r = getattr(self.lib, entry)(self.ix, sparse.ix, nq, q.ctypes.data, q_ids.shape[1], q_ids.ctypes.data, q_weights.ctypes.data,
+                                     w_dense, w_sparse, None if words is None else words.ctypes.data, 0 if words is None else len(words),
+                                     k, ids.ctypes.data, scores.ctypes.data)
         if r != 0:
-            self._hybrid_fail("bert_hip_hybrid_search", r)
+            self._hybrid_fail(entry, r)
         return ids, scores
+
+    def _hybrid_search_texts(self, entry: str, sparse: "BertSparseIndex", texts: Sequence, kq, k, w_dense, w_sparse, n_threads):
+        n = len(texts)
+        txt = (C.c_char_p * max(n, 1))(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
+        ids = np.empty((n, max(k, 1)), dtype=np.int32)
+        scores = np.empty((n, max(k, 1)), dtype=np.float32)
+        r = getattr(self.lib, entry)(self.ix, sparse.ix, n_threads, n, txt, kq, w_dense, w_sparse, k, ids.ctypes.data, scores.ctypes.data)
+        if r != 0:
+            self._hybrid_fail(entry, r)
+        return ids, scores
+
+    def hybrid_search(self, sparse: "BertSparseIndex", queries, q_ids, q_weights, k: int = 10, w_dense: float = 1.0, w_sparse: float = 1.0,
+                      allow=None):
+        """The exact top-k of (w_dense * dense score) + (w_sparse * sparse score) over the rows live in both indexes and allowed:
+        queries [n, dim] f32, (q_ids, q_weights) [n, kq] as BertSparseIndex.search takes them, allow as BertIndex.search's."""
+        return self._hybrid_search("bert_hip_hybrid_search", sparse, queries, q_ids, q_weights, k, w_dense, w_sparse, allow)
 
     def hybrid_search_device(self, sparse: "BertSparseIndex", n_queries: int, d_queries_ptr: int, kq: int, d_q_ids_ptr: int, d_q_weights_ptr: int,
                              k: int, d_ids_ptr: int, d_scores_ptr: int, w_dense: float = 1.0, w_sparse: float = 1.0, stream: int = 0,
@@ -1637,14 +1658,26 @@ class BertIndex:
 
     def hybrid_search_texts(self, sparse: "BertSparseIndex", texts: Sequence, kq: int = 32, k: int = 10, w_dense: float = 1.0, w_sparse: float = 1.0,
                             n_threads: int = 6):
-        n = len(texts)
-        txt = (C.c_char_p * max(n, 1))(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
-        ids = np.empty((n, max(k, 1)), dtype=np.int32)
-        scores = np.empty((n, max(k, 1)), dtype=np.float32)
-        r = self.lib.bert_hip_hybrid_search_texts(self.ix, sparse.ix, n_threads, n, txt, kq, w_dense, w_sparse, k, ids.ctypes.data, scores.ctypes.data)
+        return self._hybrid_search_texts("bert_hip_hybrid_search_texts", sparse, texts, kq, k, w_dense, w_sparse, n_threads)
+
+    # ---- the same searches over the sparse index's postings (bert_hip_dense_sparse_search_inverted*): the ids and score bits of the
+    # three above; sparse.invert() must have covered every row, else a ValueError (-2)
+    def hybrid_search_inverted(self, sparse: "BertSparseIndex", queries, q_ids, q_weights, k: int = 10, w_dense: float = 1.0,
+                               w_sparse: float = 1.0, allow=None):
+        """hybrid_search through the sparse index's postings: the same ids and score bits."""
+        return self._hybrid_search("bert_hip_dense_sparse_search_inverted", sparse, queries, q_ids, q_weights, k, w_dense, w_sparse, allow)
+
+    def hybrid_search_inverted_device(self, sparse: "BertSparseIndex", n_queries: int, d_queries_ptr: int, kq: int, d_q_ids_ptr: int,
+                                      d_q_weights_ptr: int, k: int, d_ids_ptr: int, d_scores_ptr: int, w_dense: float = 1.0, w_sparse: float = 1.0,
+                                      stream: int = 0, d_allow_ptr: int = 0, n_words: int = 0) -> None:
+        r = self.lib.bert_hip_dense_sparse_search_inverted_device(self.ix, sparse.ix, n_queries, d_queries_ptr, kq, d_q_ids_ptr, d_q_weights_ptr,
+                                                                  w_dense, w_sparse, d_allow_ptr or None, n_words, k, d_ids_ptr, d_scores_ptr, stream)
         if r != 0:
-            self._hybrid_fail("bert_hip_hybrid_search_texts", r)
-        return ids, scores
+            self._hybrid_fail("bert_hip_dense_sparse_search_inverted_device", r)
+
+    def hybrid_search_inverted_texts(self, sparse: "BertSparseIndex", texts: Sequence, kq: int = 32, k: int = 10, w_dense: float = 1.0,
+                                     w_sparse: float = 1.0, n_threads: int = 6):
+        return self._hybrid_search_texts("bert_hip_dense_sparse_search_inverted_texts", sparse, texts, kq, k, w_dense, w_sparse, n_threads)
 
 
 class BertSparseIndex:

@@ -826,7 +826,8 @@ BERT_API struct bert_hip_sparse_index *bert_hip_sparse_index_load(struct bert_ct
  *            invert (as it does before the first invert); inverted_rows still reports the rows covered.  It never answers over a part
  *            of the rows.  remove keeps the postings: removed rows are dropped at selection.  compact drops them (the ids change;
  *            inverted_rows is 0 until the next invert).  A loaded index has no postings: save writes the rows only.
- * Not covered: a file form of the postings; hybrid search over postings; dynamic pruning (WAND / max-score) — this search is exact and
+ * (A hybrid search over the postings: bert_hip_dense_sparse_search_inverted, under "Hybrid search" below.)
+ * Not covered: a file form of the postings; dynamic pruning (WAND / max-score) — this search is exact and
  * scores every row that holds a queried term; appending to postings on the device or under capture.                                */
 BERT_API int32_t bert_hip_sparse_index_invert(struct bert_hip_sparse_index *ix);
 BERT_API int32_t bert_hip_sparse_index_inverted_rows(struct bert_hip_sparse_index *ix);
@@ -872,6 +873,16 @@ BERT_API int32_t bert_hip_sparse_index_search_inverted_texts(struct bert_hip_spa
  *     runs the MLM head's top-kq as bert_hip_sparse_index_search_texts does and refuses what it refuses (no head, another vocabulary);
  *     the search then runs on the sparse index's stream.  One context may serve both.  A dense context over several GPUs encodes
  *     through bert_hip_encode_batch, as bert_hip_index_search_texts does there; the sparse side uses its context's first device.
+ *   Over the postings.  bert_hip_dense_sparse_search_inverted, _inverted_device and _inverted_texts take the arguments of
+ *     bert_hip_hybrid_search, _search_device and _search_texts and return, for every query, exactly their ids and score bits on the
+ *     same pair of indexes: the same D (the same dense pass), the same S (the inverted search's chain, which is the row-major one:
+ *     "postings and the inverted search" above) and the same three rounded operations.  Every rule of this section holds for them
+ *     unchanged — score, qualifying rows, order and slots, limits, determinism, the one operation of both indexes, the error codes.
+ *     They read the sparse index's postings where the hybrid entries read its rows, and cost less (README, "Hybrid search").  The
+ *     postings must cover every row: without them, or with stale ones (rows added since bert_hip_sparse_index_invert, or the index
+ *     compacted or loaded), each of the three returns -2 after a line on stderr that says to call bert_hip_sparse_index_invert; it
+ *     never answers over a part of the rows.  remove on either index keeps the postings valid.  Within bert_hip_hybrid_reserve and
+ *     bert_hip_sparse_index_invert, called in either order, the device form never allocates and is legal under stream capture.
  * Results: 0; -1 without one of the indexes; -2 after a line on stderr for an argument the entry refuses; -3 on a device error; -4 for
  * an exception.  Outputs are untouched on error.
  * Not covered: reciprocal-rank fusion; a probed (IVF) dense side; several GPUs; a hybrid rescore (the two rescores chained give that).   */
@@ -887,6 +898,18 @@ BERT_API int32_t bert_hip_hybrid_search_device(struct bert_hip_index *dense, str
 BERT_API int32_t bert_hip_hybrid_search_texts(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse, int32_t n_threads,
                                               int32_t n_queries, const char **texts, int32_t kq, float w_dense, float w_sparse, int32_t k,
                                               int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_dense_sparse_search_inverted(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse, int32_t n_queries,
+                                                       const float *queries, int32_t kq, const int32_t *q_ids, const float *q_weights,
+                                                       float w_dense, float w_sparse, const uint32_t *allow, int32_t n_words, int32_t k,
+                                                       int32_t *ids, float *scores);
+BERT_API int32_t bert_hip_dense_sparse_search_inverted_device(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse,
+                                                              int32_t n_queries, const float *d_queries, int32_t kq, const int32_t *d_q_ids,
+                                                              const float *d_q_weights, float w_dense, float w_sparse,
+                                                              const uint32_t *d_allow, int32_t n_words, int32_t k, int32_t *d_ids,
+                                                              float *d_scores, void *stream);
+BERT_API int32_t bert_hip_dense_sparse_search_inverted_texts(struct bert_hip_index *dense, struct bert_hip_sparse_index *sparse,
+                                                             int32_t n_threads, int32_t n_queries, const char **texts, int32_t kq,
+                                                             float w_dense, float w_sparse, int32_t k, int32_t *ids, float *scores);
 
 /* TOKEN INDEX: documents' f16 token rows in HBM on the context's FIRST device (bert_hip_device), exact top-k search by late
  * interaction — over ALL stored documents d, the k largest  score(q, d) = sum over the query's tokens i of ( max over the document's

@@ -11,7 +11,15 @@ bert_hip_sparse_index_search_device on the same indexes (device events around ba
 rounds, the three measured in turn within each round), the hybrid call over the sum of the two, the time one write and one read of the
 score matrix take at the project's HBM line (8 bytes x queries x rows over 4.8 TB/s), and — from a second, profiled
 call, never the timed one — the per-kernel split of the hybrid call by the engine's profiler.  --chunks: the A/B of the tuning key
-"hybrid_chunk_queries" at 4096 queries.  Everything is in device memory; the rows are generated on the device."""
+"hybrid_chunk_queries" at 4096 queries.  Everything is in device memory; the rows are generated on the device.
+
+    python tools/hybrid_rate.py --section inverted [--out profiles/hybrid_inverted_rate.txt]
+
+The hybrid search over the postings (bert_hip_dense_sparse_search_inverted_device) beside bert_hip_hybrid_search_device on the same
+indexes in the same process: per cell both calls' ids and score bits are compared, then the two are timed in turn, the fastest of five
+rounds and the slowest beside it; the per-kernel split of both for the f16 x f32 cells; the time of invert, once per sparse index.
+The load-placement A/B of DESIGN.md §15.1 is this section under two libraries built by tools/variant.sh
+(-DSPARSE_POSTINGS_D_AHEAD=1 and =0), chosen by BERT_HIP_LIB, in one job."""
 import argparse
 import os
 import sys
@@ -35,6 +43,8 @@ def main():
     ap.add_argument("--sparse", default="f32,f16")
     ap.add_argument("--queries", default="1,64,4096")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--section", default="hybrid", choices=["hybrid", "inverted"],
+                    help="inverted: bert_hip_dense_sparse_search_inverted_device beside bert_hip_hybrid_search_device, cell by cell")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -127,6 +137,60 @@ def main():
             rep = m.profile_report()
             m.profile(False)
             return {name: (v["launches"], v["total_ms"]) for name, v in rep.items() if isinstance(v, dict) and v.get("launches")}
+
+        def fastest_in_turn(fs, rounds=5, budget_ms=300.0, max_iters=50):
+            """the calls of fs interleaved, `rounds` rounds: per call (fastest, slowest) ms of a round's mean"""
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            iters = []
+            for f in fs:
+                f()
+                torch.cuda.synchronize()
+                e0.record(); f(); e1.record(); e1.synchronize()
+                iters.append(int(max(1, min(max_iters, budget_ms / max(e0.elapsed_time(e1), 1e-3)))))
+            ts = [[] for _ in fs]
+            for _ in range(rounds):
+                for i, f in enumerate(fs):
+                    e0.record()
+                    for _ in range(iters[i]):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    ts[i].append(e0.elapsed_time(e1) / iters[i])
+            return [(min(t), max(t)) for t in ts]
+
+        if a.section == "inverted":
+            # the hybrid search over the postings beside the one over the rows: the same indexes, the same process, the runs interleaved
+            import time
+            out("# section inverted: bert_hip_dense_sparse_search_inverted_device (new) beside bert_hip_hybrid_search_device (rows), the same "
+                "indexes and queries; ms per call = the fastest of 5 interleaved rounds (slowest in brackets); ids and score bits of the two "
+                "calls compared in every cell before it is timed")
+            for sd, six in sparse.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                six.invert()
+                torch.cuda.synchronize()
+                out(f"# sparse {sd}: bert_hip_sparse_index_invert of {N} rows, once: {(time.perf_counter() - t0) * 1e3:.1f} ms (blocking, wall clock)")
+            a_i, a_s = torch.empty_like(d_ids), torch.empty_like(d_sc)
+            for dd, dix in dense.items():
+                for sd, six in sparse.items():
+                    dix.hybrid_reserve(six, N, max(NQ), K)
+                    out(f"# dense {dd} x sparse {sd}")
+                    out("#   nq    HC     rows ms (slowest)    postings ms (slowest)   postings/rows   bits")
+                    for nq in NQ:
+                        hc = pybert.test_hybrid_chunk(N, nq, 0)[0]
+                        rows_call = lambda: dix.hybrid_search_device(six, nq, q.data_ptr(), KQ, q_ids.data_ptr(), q_w.data_ptr(), K, d_ids.data_ptr(), d_sc.data_ptr(), 0.5, 0.5, stream)
+                        post_call = lambda: dix.hybrid_search_inverted_device(six, nq, q.data_ptr(), KQ, q_ids.data_ptr(), q_w.data_ptr(), K, a_i.data_ptr(), a_s.data_ptr(), 0.5, 0.5, stream)
+                        rows_call(); post_call()
+                        torch.cuda.synchronize()
+                        equal = bool((d_ids[:nq] == a_i[:nq]).all()) and bool((d_sc[:nq].view(torch.int32) == a_s[:nq].view(torch.int32)).all())
+                        (r, rhi), (p, phi) = fastest_in_turn([rows_call, post_call])
+                        out(f"  {nq:5d} {hc:5d} {r:10.3f} ({rhi:.3f}) {p:14.3f} ({phi:.3f}) {p / r:15.3f}   {'equal' if equal else 'DIFFERENT'}")
+                        if (dd, sd) == ("f16", "f32"):
+                            for tag, f in (("rows", rows_call), ("postings", post_call)):
+                                sp = split(f)
+                                out(f"#         {tag:8s} split: " + ", ".join(f"{name} {n} x {ms / n:.3f}" for name, (n, ms) in sorted(sp.items(), key=lambda kv: -kv[1][1])))
+                        assert equal, (dd, sd, nq)
+            dense.clear()
 
         for dd, dix in dense.items():
             for sd, six in sparse.items():
