@@ -47,10 +47,9 @@ Plan plan(int n_rows, int nq, int k) {
     Plan p;
     p.nqt = (nq + QT - 1) / QT;
     const int s = slice_count(n_rows, nq, k);
-    const int per = (int)(((long long)n_rows + s - 1) / s);
-    p.slice_rows = std::max(STEP_ROWS, (per + STEP_ROWS - 1) / STEP_ROWS * STEP_ROWS);
-    p.slices = std::max(1, (int)(((long long)n_rows + p.slice_rows - 1) / p.slice_rows));
-    p.L = k + STEP_ROWS <= 256 ? 256 : 512;
+    const SliceCut c = slice_cut(n_rows, s, STEP_ROWS);
+    p.slice_rows = c.rows; p.slices = c.n_slices;
+    p.L = index_topk_L(k);
     p.lds = (size_t)std::min(QT, nq) * p.L * 8 + QT * 4;
     return p;
 }

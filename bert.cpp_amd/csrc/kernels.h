@@ -318,6 +318,12 @@ inline thread_local LaunchTiming *tl_launch_timing = nullptr;
         } else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                             \
     } while (0)
 
+// The XCD item map of the kernels whose consecutive items share data (the query tiles of one slice of rows): workgroup b runs on
+// XCD b % 8, so item (b % 8) * (grid / 8) + b / 8 sends consecutive items to one XCD, where they find the slice in that XCD's L2.
+// The grid is a multiple of 8 — xcd_grid, the launch side — and a workgroup whose item is at or beyond n_items does nothing.
+__device__ __forceinline__ int xcd_item() { return (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8); }
+inline int xcd_grid(int n_items) { return (n_items + 7) / 8 * 8; }
+
 // The f32 route (f32_route.hip): the forward pass of f32 model files in f32 arithmetic — f32 activations, mat-muls on
 // v_mfma_f32_32x32x2_f32 (any M, N, K; C = epi(A W^T + bias (+ resid))), f32 softmax / GELU / LayerNorm / pooling.
 void launch_f32_embed_ln(const float *word, const float *type, const float *pos, const float *gamma, const float *beta, const int32_t *tokens,

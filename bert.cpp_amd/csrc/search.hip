@@ -8,11 +8,10 @@
 //                         bits expanded to +1 / -1 bytes in registers and the query's scale — and a lane ends the
 //                         step with one row's scores for 16 queries.  Every score
 //                         is compared with its query's threshold (the k-th best of this workgroup so far, kept in registers);
-//                         only the ones that beat it go into the query's candidate queue in LDS (an LDS atomic hands out the
-//                         slot).  When a queue might not take another step's rows, the lists are bitonic-sorted in LDS by
-//                         (score, id) keys, the first k kept and the thresholds raised.  At the end of its slice the
-//                         workgroup writes one sorted top-k list per query to the workspace.
-//   topk_merge_kernel     one workgroup per query: the same threshold / queue / sort over the slices' lists, then the
+//                         only the ones that beat it are pushed.  The selection — the lists and queues in LDS, the look after
+//                         a step, the sort, the write of one sorted top-k list per query to the workspace — is the protocol
+//                         topk_select.h states once for every selecting kernel (written out in this one: see the kernel).
+//   topk_merge_kernel     one workgroup per query: the same selection (one list) over the slices' lists, then the
 //                         final ids and scores.
 //                         The masked instantiations (MASKED: an index with removed rows, or a search with an
 //                         allow-list) read one word of each bitmap per wave and step — the wave's block is
@@ -29,7 +28,7 @@
 //   index_probe_kernel<T>  the probed search of a partitioned index: one workgroup per (query, item), an item being one of the
 //                         query's probed lists (its members' ids come from the partition's order table) or a chunk of the
 //                         unassigned tail.  Each wave scores 32 members per step as the rescore kernel does, and the workgroup
-//                         selects in LDS as the top-k kernel does for one query: k entries per item reach the workspace, from
+//                         selects with topk_select.h's queue, one list: k entries per item reach the workspace, from
 //                         which topk_merge_kernel selects.  The masked instantiation (a probed search with an allow-list)
 //                         scores and pushes only the members whose bit of live & allow is set; a wave whose 32 members hold
 //                         none issues no row loads and no MFMA.
@@ -75,7 +74,6 @@ namespace bert_hip {
 
 namespace {
 
-constexpr int SENT_ID = INT_MAX;        // id of an empty list entry (score -inf): ranks below every row
 constexpr int MERGE_U = 16;             // candidates per thread and round of the merge
 
 
@@ -216,14 +214,14 @@ template <> struct ScoreBlock<b1_t> {
 };
 
 // LDS: float scores [nqv][L], int ids [nqv][L], int count [nqv] — per query the current top-k in [0, k), the queue behind
+// The selection is written out here, not taken from topk_select.h's helpers: with them this kernel measured slower.
+// The protocol and its barrier contract are the ones stated there.
 template <class T, bool MASKED>
 __global__ __launch_bounds__(NT) void index_topk_kernel(TopkArgs a) {
     using F = ScoreBlock<T>;
     using QE = typename F::query_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // workgroup b runs on XCD b % 8: consecutive items — the query tiles of one slice of rows — go to one XCD, so that
-    // they find the slice in that XCD's L2 (the grid is a multiple of 8; items beyond n_items do nothing)
-    const int item = (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8);
+    const int item = xcd_item();                 // (kernels.h: the query tiles of one slice of rows go to one XCD)
     if (item >= a.n_items) return;
     const int slice = item / a.n_qtiles, qt = item - slice * a.n_qtiles;
     const int q0 = qt * QT, nqv = min(QT, a.nq - q0);
@@ -317,15 +315,13 @@ __global__ __launch_bounds__(NT) void topk_merge_kernel(MergeArgs a) {
     const int L = a.L, k = a.k, tid = threadIdx.x;
     float *ls = (float *)smem;
     int *li = (int *)(ls + L);
-    int *cnt = li + L;
+    const SelectLists sel{ls, li, li + L, L, k, L - k - NT};       // a look follows at most NT pushes
     const float *cs = a.ws_s + (size_t)blockIdx.x * a.n_cand;
     const int *ci = a.ws_i + (size_t)blockIdx.x * a.n_cand;
-    for (int i = tid; i < L; i += NT) { ls[i] = -INFINITY; li[i] = SENT_ID; }
-    if (tid == 0) *cnt = 0;
+    select_init(sel, 1, tid);
     float ts = -INFINITY;
     int ti = SENT_ID;
     __syncthreads();
-    const int room = L - k - NT;                 // a round pushes at most NT entries
     for (int base = 0; base < a.n_cand; base += NT * MERGE_U) {
         float s[MERGE_U];
         int id[MERGE_U];
@@ -337,24 +333,15 @@ __global__ __launch_bounds__(NT) void topk_merge_kernel(MergeArgs a) {
         }
 #pragma unroll
         for (int u = 0; u < MERGE_U; ++u) {
-            if (better(s[u], id[u], ts, ti)) {
-                const int p = atomicAdd(cnt, 1);
-                ls[k + p] = s[u];
-                li[k + p] = id[u];
-            }
-            __syncthreads();
-            // (one thread reads the count between the two barriers: the next round's pushes come after the second)
-            if (__syncthreads_or(tid == 0 && *cnt > room)) {
-                bitonic_sort_lists(ls, li, 1, L, tid);
-                ts = ls[k - 1];
-                ti = li[k - 1];
-                if (tid == 0) *cnt = 0;
-                __syncthreads();
+            if (better(s[u], id[u], ts, ti)) select_push(sel, 0, s[u], id[u]);
+            // (a look per u, not per round: a round's MERGE_U * NT candidates would not fit behind the top-k)
+            if (select_step_end(sel, 1, tid)) {
+                select_threshold(sel, 0, ts, ti);
+                select_resume(sel, 1, tid);
             }
         }
     }
-    __syncthreads();
-    if (__syncthreads_or(tid == 0 && *cnt > 0)) bitonic_sort_lists(ls, li, 1, L, tid);
+    select_finish(sel, 1, tid);
     for (int j = tid; j < k; j += NT) {
         const int id = li[j];
         a.ids[(size_t)blockIdx.x * k + j] = id == SENT_ID ? -1 : id;
@@ -391,7 +378,7 @@ __global__ __launch_bounds__(NT) void index_rescore_kernel(RescoreArgs a) {
     }
 }
 
-// index_topk_kernel without the selection: one workgroup of four waves per (tile of QT queries, slice of rows), the same XCD map;
+// index_topk_kernel without the selection: one workgroup of four waves per (tile of QT queries, slice of rows), the same item map;
 // each wave scores 32 rows a step through ScoreBlock<T>::run and finish — the search's bits — and stores acc[r] to
 // out[(q0 + q) * ld + row] for the queries q < nqv: per accumulator element the 32 lanes of a half-wave write 32 consecutive floats.
 // No LDS, no barrier: a wave whose block lies beyond the slice, or (MASKED) holds no row whose bit of mask is set, does nothing;
@@ -400,7 +387,7 @@ template <class T, bool MASKED>
 __global__ __launch_bounds__(NT) void index_scores_kernel(ScoresArgs a) {
     using F = ScoreBlock<T>;
     using QE = typename F::query_t;
-    const int item = (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8);
+    const int item = xcd_item();
     if (item >= a.n_items) return;
     const int slice = item / a.n_qtiles, qt = item - slice * a.n_qtiles;
     const int q0 = qt * QT, nqv = min(QT, a.nq - q0);
@@ -451,8 +438,7 @@ __global__ __launch_bounds__(256) void mask_and_kernel(const uint32_t *__restric
 
 // One workgroup per (query, item); the item's members m0 .. m1 - 1 are rows order[m] (a probed list) or m itself (a tail chunk).
 // Scoring is index_rescore_kernel's — the query is query 0 of the tile, lane l < 32 ends with its member's score —, selection
-// index_topk_kernel's with one query: threshold in registers, queue behind the current top-k in LDS, sorted when a step might
-// not fit.  The k entries written for an item that has fewer candidates are (-inf, SENT_ID).
+// topk_select.h's with one list.  The k entries written for an item that has fewer candidates are (-inf, SENT_ID).
 // MASKED (a search with an allow-list): a member is a candidate iff its bit of live & allow is set.  The members of a list are
 // scattered ids, so each lane reads its own member's words; the members of a tail chunk are consecutive ids, so the wave's 32
 // bits come from at most two words read once per wave and step (the tail starts at n_part, any row: the block straddles two
@@ -467,7 +453,7 @@ __global__ __launch_bounds__(NT) void index_probe_kernel(ProbeArgs a) {
     const int lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
     float *ls = (float *)smem;
     int *li = (int *)(ls + L);
-    int *cnt = li + L;
+    const SelectLists sel{ls, li, li + L, L, k, L - k - STEP_ROWS};        // a step pushes at most STEP_ROWS entries
     // (everything up to the loop is uniform over the workgroup)
     const bool listed = item < a.nprobe;
     int m0 = 0, m1 = 0;
@@ -482,18 +468,16 @@ __global__ __launch_bounds__(NT) void index_probe_kernel(ProbeArgs a) {
     }
     const size_t out = ((size_t)q * a.n_items + item) * k;
     if (m0 >= m1) {
-        for (int j = tid; j < k; j += NT) { a.ws_s[out + j] = -INFINITY; a.ws_i[out + j] = SENT_ID; }
+        select_store_empty(a.ws_s, a.ws_i, out, k, tid);
         return;
     }
-    for (int i = tid; i < L; i += NT) { ls[i] = -INFINITY; li[i] = SENT_ID; }
-    if (tid == 0) *cnt = 0;
+    const QE *qp = (const QE *)a.queries + (size_t)q * a.dpad;
+    const float qs = F::QSCALE ? a.qscale[q] : 0.f;
+    select_init(sel, 1, tid);
     float ts = -INFINITY;
     int ti = SENT_ID;
     __syncthreads();
 
-    const QE *qp = (const QE *)a.queries + (size_t)q * a.dpad;
-    const float qs = F::QSCALE ? a.qscale[q] : 0.f;
-    const int room = L - k - STEP_ROWS;          // a step pushes at most STEP_ROWS entries
     // (the trip count is the workgroup's: the barriers below are met by every wave)
     for (int base = m0; base < m1; base += STEP_ROWS) {
         const int m = base + wave * 32 + col;
@@ -532,23 +516,14 @@ __global__ __launch_bounds__(NT) void index_probe_kernel(ProbeArgs a) {
             typename F::acc_t dot = {};
             F::run(qp, rp, col == 0, rok, a.dpad, h, dot);
             const float s = F::finish(dot[0], qs, rs);
-            if (h == 0 && rok && better(s, id, ts, ti)) {
-                const int p = atomicAdd(cnt, 1);
-                ls[k + p] = s;
-                li[k + p] = id;
-            }
+            if (h == 0 && rok && better(s, id, ts, ti)) select_push(sel, 0, s, id);
         }
-        __syncthreads();
-        if (__syncthreads_or(tid == 0 && *cnt > room)) {
-            bitonic_sort_lists(ls, li, 1, L, tid);
-            ts = ls[k - 1];
-            ti = li[k - 1];
-            if (tid == 0) *cnt = 0;
-            __syncthreads();
+        if (select_step_end(sel, 1, tid)) {
+            select_threshold(sel, 0, ts, ti);
+            select_resume(sel, 1, tid);
         }
     }
-    __syncthreads();
-    if (__syncthreads_or(tid == 0 && *cnt > 0)) bitonic_sort_lists(ls, li, 1, L, tid);
+    select_finish(sel, 1, tid);
     for (int j = tid; j < k; j += NT) { a.ws_s[out + j] = ls[j]; a.ws_i[out + j] = li[j]; }
 }
 
@@ -700,7 +675,7 @@ void search_kernels_init() {
 }
 
 void launch_topk(int dtype, const TopkArgs &a, size_t lds, hipStream_t s) {
-    const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
+    const int grid = xcd_grid(a.n_items);
     dispatch(dtype, [&](auto form) {
         using T = decltype(row_type(form));
         if (a.live || a.allow) BERT_LAUNCH((index_topk_kernel<T, true>), dim3(grid), dim3(NT), lds, s, a);
@@ -718,7 +693,7 @@ void launch_rescore(int dtype, const RescoreArgs &a, hipStream_t s) {
 }
 
 void launch_index_scores(int dtype, const ScoresArgs &a, hipStream_t s) {
-    const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
+    const int grid = xcd_grid(a.n_items);
     dispatch(dtype, [&](auto form) {
         using T = decltype(row_type(form));
         if (a.mask) BERT_LAUNCH((index_scores_kernel<T, true>), dim3(grid), dim3(NT), 0, s, a);

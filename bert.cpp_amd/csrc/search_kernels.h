@@ -19,7 +19,16 @@ constexpr int NT = 64 * NWAVE;
 constexpr int STEP_ROWS = 32 * NWAVE;   // rows a workgroup scores per step (each wave one 32-row block)
 constexpr int TARGET_BLOCKS = 2048;     // score workgroups a search aims for (8 per CU)
 
-// index_topk_kernel.  LDS (lds bytes of launch_topk): float scores [min(QT, nq)][L], int ids the same, int count [QT]
+// The slice cut: n rows in s near-equal slices of whole steps (at least one): the rows of a slice, and how many slices that makes
+struct SliceCut { int rows, n_slices; };
+inline SliceCut slice_cut(int n, int s, int step) {
+    const int per = (int)(((long long)n + s - 1) / s);
+    const int rows = std::max(step, (per + step - 1) / step * step);
+    return {rows, std::max(1, (int)(((long long)n + rows - 1) / rows))};
+}
+
+// index_topk_kernel.  LDS (lds bytes of launch_topk): float scores [min(QT, nq)][L], int ids the same, int count [QT]; L = index_topk_L(k)
+inline int index_topk_L(int k) { return k + STEP_ROWS <= 256 ? 256 : 512; }
 struct TopkArgs {
     const void *rows, *queries;          // [n_rows][dpad], [nq][dpad] of T (b1: rows of dpad bits, queries of dpad i8 codes)
     float *ws_s;                         // [nq][n_slices][k] per-(query, slice) lists, best first
@@ -65,9 +74,8 @@ inline void index_scores_plan(int n_rows, int nq, ScoresArgs &a) {
     a.n_rows = n_rows; a.nq = nq;
     a.n_qtiles = (nq + QT - 1) / QT;
     const int s = std::max(1, std::min((TARGET_BLOCKS + a.n_qtiles - 1) / a.n_qtiles, n_rows / 2048));
-    const int per = (int)(((long long)n_rows + s - 1) / s);
-    a.slice_rows = std::max(STEP_ROWS, (per + STEP_ROWS - 1) / STEP_ROWS * STEP_ROWS);
-    a.n_slices = std::max(1, (int)(((long long)n_rows + a.slice_rows - 1) / a.slice_rows));
+    const SliceCut c = slice_cut(n_rows, s, STEP_ROWS);
+    a.slice_rows = c.rows; a.n_slices = c.n_slices;
     a.n_items = a.n_qtiles * a.n_slices;
 }
 

@@ -3,7 +3,7 @@
 // the SparseIndex class that plans and orders them is sparse_index.cpp (sparse_index.h).
 //
 //   sparse_index_add_kernel<DTYPE>   one workgroup per row: drops the entries whose id is outside [0, n_vocab), ranks the others by id
-//                         (a count over the row's at most 256 keys in LDS; equal ids keep their input order), rounds the weights to the
+//                         (rank_terms, sparse_device.h: a count over the row's keys in LDS; equal ids keep their input order), rounds the weights to the
 //                         stored type and writes the row's column slots in its block of 64, zeros behind its terms, and its count.  A
 //                         row's place depends on its id alone, so an add may start and end anywhere inside a block.
 //   sparse_query_kernel   one workgroup per query: sets the bitmap's bits with LDS atomics, scans the per-word counts, lets each term
@@ -13,9 +13,9 @@
 //                         column once and, for each query of the tile, tests the id's bit and on a hit runs
 //                         acc[q] = fmaf(w, qw[prefix[id >> 5] + popc(word & below)], acc[q]).  The columns are in ascending id, so a
 //                         lane's chain IS the score rule of bert_hip.h; there is no cross-lane reduction.  A block is walked to the
-//                         largest count of its 64 rows (a wave maximum), not to width.  Selection is index_topk_kernel's (search.hip):
-//                         thresholds in registers, a queue behind the top-k in LDS, bitonic_sort_lists when a queue might not take
-//                         another step, one sorted list per (query, slice) into the workspace — which topk_merge_kernel merges.
+//                         largest count of its 64 rows (a wave maximum), not to width.  Selection is topk_select.h's protocol (written
+//                         out in the body: see there), one list per query of the tile and a threshold pair per query in
+//                         registers: one sorted list per (query, slice) into the workspace — which topk_merge_kernel merges.
 //                         The MASKED instantiation (removed rows, an allow-list) reads two mask words per block: see the kernel.
 //   sparse_hybrid_scan_kernel<DTYPE, MASKED>  the same body as the second pass of a hybrid search (hybrid.cpp): the score a row is
 //                         selected by is (w_dense * D) + (w_sparse * S), D read from the matrix index_scores_kernel (search.hip) wrote.
@@ -28,34 +28,20 @@
 // is past its count, reads nothing and uses id 0.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
-#include <type_traits>
 
 #include "device.h"
 #include "hybrid_score.h"
-#include "kernels.h"
-#include "sparse_index_kernels.h"
+#include "sparse_device.h"
 #include "topk_select.h"
 
 namespace bert_hip {
 
 namespace {
 
-constexpr int SENT_ID = INT_MAX;        // id of an empty list entry (score -inf): ranks below every row, as in search.hip
 constexpr int QB_MAX = SPARSE_QB_MAX;   // the most queries of a tile (registers: one accumulator and one threshold pair each)
 constexpr int COL_U = 8;                // columns of a block whose loads are in flight together
 static_assert(SPARSE_QB[0] <= QB_MAX && SPARSE_QB[1] <= QB_MAX, "a tile's accumulators are registers");
-
-template <int DTYPE> struct Stored {
-    using id_t = std::conditional_t<DTYPE == 1, uint16_t, int32_t>;
-    using w_t = std::conditional_t<DTYPE == 1, half_t, float>;
-};
-
-// element (row, column j) of a stored array of rows `width` columns wide
-__device__ __forceinline__ size_t slot(int row, int j, int width) {
-    return ((size_t)(row >> 6) * width + j) * SPARSE_BLOCK_ROWS + (row & 63);
-}
 
 template <int DTYPE>
 __global__ __launch_bounds__(256) void sparse_index_add_kernel(SparseAddArgs a) {
@@ -64,29 +50,16 @@ __global__ __launch_bounds__(256) void sparse_index_add_kernel(SparseAddArgs a) 
     __shared__ int keys[SPARSE_MAX_TERMS], skeys[SPARSE_MAX_TERMS];
     __shared__ float vals[SPARSE_MAX_TERMS];
     const int t = threadIdx.x, i = blockIdx.x, row = a.first + i;
-    int key = INT_MAX;
-    float w = 0.f;
-    if (t < a.k_in) {
-        const int id = a.ids[(size_t)i * a.k_in + t];
-        if (id >= 0 && id < a.n_vocab) { key = id; w = a.weights[(size_t)i * a.k_in + t]; }
-    }
-    keys[t] = key;
-    const int count = __syncthreads_count(key != INT_MAX);
-    int rank = 0;
-    if (key != INT_MAX)
-        for (int u = 0; u < a.k_in; ++u) {
-            const int ku = keys[u];
-            rank += (ku < key || (ku == key && u < t)) ? 1 : 0;
-        }
-    // (every valid entry has a rank of its own below count <= k_in <= width)
-    if (key != INT_MAX) { skeys[rank] = key; vals[rank] = w; }
+    const RankedTerm r = rank_terms(a.ids, a.weights, (size_t)i * a.k_in, a.k_in, a.n_vocab, keys, t);
+    // (count <= k_in <= width)
+    if (r.key != INT_MAX) { skeys[r.rank] = r.key; vals[r.rank] = r.w; }
     __syncthreads();
     if (t < a.width) {
         const size_t o = slot(row, t, a.width);
-        ((id_t *)a.sids)[o] = t < count ? (id_t)skeys[t] : (id_t)0;
-        ((w_t *)a.sweights)[o] = t < count ? (w_t)vals[t] : (w_t)0.f;       // (f16: round to nearest even)
+        ((id_t *)a.sids)[o] = t < r.count ? (id_t)skeys[t] : (id_t)0;
+        ((w_t *)a.sweights)[o] = t < r.count ? (w_t)vals[t] : (w_t)0.f;     // (f16: round to nearest even)
     }
-    if (t == 0) a.counts[row] = count;
+    if (t == 0) a.counts[row] = r.count;
 }
 
 __global__ __launch_bounds__(256) void sparse_query_kernel(SparseQueryArgs a) {
@@ -133,14 +106,15 @@ __global__ __launch_bounds__(256) void sparse_query_kernel(SparseQueryArgs a) {
 // loads' latency hides under it, a lane whose row qualifies loads its row's dense score of each query of the tile from a.dscores
 // (lane = row: a coalesced 256-byte access per query); a lane whose row does not qualify reads nothing — the dense pass may not
 // have written there.  After the walk the score is hybrid_score(D, S) in place of S; everything behind it is the scan's.
+//
+// The selection is written out here, not taken from topk_select.h's helpers: with them this scan measured slower.
+// The protocol and its barrier contract are the ones stated there.
 template <int DTYPE, bool MASKED, bool HYBRID>
 __device__ __forceinline__ void sparse_scan_body(const SparseScanArgs &a) {
     using id_t = typename Stored<DTYPE>::id_t;
     using w_t = typename Stored<DTYPE>::w_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // workgroup b runs on XCD b % 8: consecutive items — the query tiles of one slice of rows — go to one XCD, so that they find
-    // the slice in that XCD's L2 (the grid is a multiple of 8; items beyond n_items do nothing)
-    const int item = (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8);
+    const int item = xcd_item();                 // (kernels.h: the query tiles of one slice of rows go to one XCD)
     if (item >= a.n_items) return;
     const int slice = item / a.n_qtiles, qt = item - slice * a.n_qtiles;
     const int q0 = qt * a.qb, nqv = min(a.qb, a.nq - q0);
@@ -335,11 +309,10 @@ template <int DTYPE>
 __global__ __launch_bounds__(256) void sparse_index_gather_kernel(SparseGatherArgs a) {
     using id_t = typename Stored<DTYPE>::id_t;
     using w_t = typename Stored<DTYPE>::w_t;
-    const size_t per_block = (size_t)a.width * SPARSE_BLOCK_ROWS;
-    const size_t total = (size_t)((a.n + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS) * per_block;
+    const size_t total = block_slots(a.n, a.width);
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const size_t blk = e / per_block;
-        const int in = (int)(e - blk * per_block), j = in >> 6, row = (int)blk * SPARSE_BLOCK_ROWS + (in & 63);
+        int row, j;
+        slot_decode(e, a.width, row, j);
         id_t id = (id_t)0;
         w_t w = (w_t)0.f;
         if (row < a.n) {
@@ -364,16 +337,7 @@ DeviceFlags g_scan_lds;
 // launchers (sparse_index_kernels.h)
 // ------------------------------------------------------------------------------------------------
 void sparse_index_kernels_init() {
-    // (beyond the 64 KiB a launch gets unasked; a launch that still cannot have it fails, and the search reports the launch error)
-    configure_once(g_scan_lds, [] {
-        bool ok = true;
-        for (const void *f : {(const void *)sparse_index_scan_kernel<0, false>, (const void *)sparse_index_scan_kernel<1, false>,
-                              (const void *)sparse_index_scan_kernel<0, true>, (const void *)sparse_index_scan_kernel<1, true>,
-                              (const void *)sparse_hybrid_scan_kernel<0, false>, (const void *)sparse_hybrid_scan_kernel<1, false>,
-                              (const void *)sparse_hybrid_scan_kernel<0, true>, (const void *)sparse_hybrid_scan_kernel<1, true>})
-            ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPARSE_LDS_MAX) == hipSuccess && ok;
-        if (!ok) (void)hipGetLastError();                      // (not left behind for an unrelated call's check)
-    });
+    scan_lds_opt_in(g_scan_lds, {SPARSE_SCAN_FAMILY(sparse_index_scan_kernel), SPARSE_SCAN_FAMILY(sparse_hybrid_scan_kernel)});
 }
 
 void launch_sparse_add(int dtype, const SparseAddArgs &a, hipStream_t s) {
@@ -386,21 +350,11 @@ void launch_sparse_query(const SparseQueryArgs &a, hipStream_t s) {
 }
 
 void launch_sparse_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStream_t s) {
-    const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
-    const bool masked = a.live || a.allow;
-    if (dtype == 1 && masked) BERT_LAUNCH((sparse_index_scan_kernel<1, true>), dim3(grid), dim3(NT), lds, s, a);
-    else if (dtype == 1) BERT_LAUNCH((sparse_index_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
-    else if (masked) BERT_LAUNCH((sparse_index_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
-    else BERT_LAUNCH((sparse_index_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
+    SPARSE_SCAN_LAUNCH(sparse_index_scan_kernel, dtype, a, lds, s);
 }
 
 void launch_sparse_hybrid_scan(int dtype, const SparseScanArgs &a, size_t lds, hipStream_t s) {
-    const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
-    const bool masked = a.live || a.allow;
-    if (dtype == 1 && masked) BERT_LAUNCH((sparse_hybrid_scan_kernel<1, true>), dim3(grid), dim3(NT), lds, s, a);
-    else if (dtype == 1) BERT_LAUNCH((sparse_hybrid_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
-    else if (masked) BERT_LAUNCH((sparse_hybrid_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
-    else BERT_LAUNCH((sparse_hybrid_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
+    SPARSE_SCAN_LAUNCH(sparse_hybrid_scan_kernel, dtype, a, lds, s);
 }
 
 // (an image is at most 50 KiB — SPARSE_MAX_VOCAB —: inside the 64 KiB a launch gets unasked)
@@ -411,8 +365,7 @@ void launch_sparse_rescore(int dtype, const SparseRescoreArgs &a, hipStream_t s)
 }
 
 void launch_sparse_gather(int dtype, const SparseGatherArgs &a, hipStream_t s) {
-    const size_t total = (size_t)((a.n + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS) * a.width * SPARSE_BLOCK_ROWS;
-    const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+    const int blocks = (int)std::min<size_t>((block_slots(a.n, a.width) + 255) / 256, 8192);
     if (dtype == 1) BERT_LAUNCH(sparse_index_gather_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
     else BERT_LAUNCH(sparse_index_gather_kernel<0>, dim3(blocks), dim3(256), 0, s, a);
 }

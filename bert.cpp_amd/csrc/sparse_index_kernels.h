@@ -61,9 +61,8 @@ inline bool sparse_scan_geometry(int dtype, int n_vocab, int n_rows, int nq, int
     g.n_qtiles = (nq + g.qb - 1) / g.qb;
     const int s = std::max(1, std::min((TARGET_BLOCKS + g.n_qtiles - 1) / g.n_qtiles, n_rows / SPARSE_MIN_SLICE_ROWS));
     g.max_slices = s;
-    const int per = (int)(((long long)n_rows + s - 1) / s);
-    g.slice_rows = std::max(SPARSE_STEP_ROWS, (per + SPARSE_STEP_ROWS - 1) / SPARSE_STEP_ROWS * SPARSE_STEP_ROWS);
-    g.n_slices = std::max(1, (int)(((long long)n_rows + g.slice_rows - 1) / g.slice_rows));
+    const SliceCut c = slice_cut(n_rows, s, SPARSE_STEP_ROWS);
+    g.slice_rows = c.rows; g.n_slices = c.n_slices;
     g.lds = (size_t)g.qb * per_query;
     return true;
 }

@@ -6,14 +6,14 @@
 //                         integer atomics, an exclusive prefix sum per segment in place, and the fill — every stored term takes the
 //                         next free slot of its list from a copy of the offsets and writes its row number inside the segment and its
 //                         weight as stored.  The order inside a list is the atomics' and differs from build to build.
-//   sparse_query_sort_kernel   one workgroup per query: the add kernel's rank-by-count turns the query into its terms in ascending id,
+//   sparse_query_sort_kernel   one workgroup per query: rank-by-count (sparse_device.h) turns the query into its terms in ascending id,
 //                         ids in [0, n_vocab), weights unrounded, and a count.
 //   sparse_postings_scan_kernel<DTYPE, MASKED>   one workgroup of four waves per (slice of whole segments, tile of qb <= 4 queries, 2 unless asked otherwise).
 //                         LDS holds per query seg f32 accumulators, the sorted terms and the scan's list.  Per segment: all lanes zero
 //                         the accumulators; wave q walks query q's terms alone, in ascending id — the offsets of 64 terms are loaded
 //                         together, one per lane, then term after term the wave reads that list coalesced and runs
 //                         acc[row] = fmaf(w, qw, acc[row]) in LDS —; then all lanes walk the segment's rows, 256 per step, and select
-//                         with the row-major scan's code: thresholds in registers, a queue behind the top-k, bitonic_sort_lists.
+//                         with topk_select.h's queue: one list per query of the tile, a threshold pair per query in registers.
 //   sparse_postings_hybrid_scan_kernel<DTYPE, MASKED>   the same body as the second pass of a hybrid search over the postings
 //                         (hybrid.cpp): a row is selected by hybrid_score(D, accumulator), D read from the matrix index_scores_kernel
 //                         (search.hip) wrote, at [query inside the chunk][global row], a step ahead of its use.
@@ -29,38 +29,27 @@
 // selected and no mask word at or beyond ceil(n_rows / 32) is read.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cmath>
-#include <type_traits>
 
 #include "device.h"
 #include "hybrid_score.h"
-#include "kernels.h"
-#include "sparse_index_kernels.h"
+#include "sparse_device.h"
 #include "topk_select.h"
 
 namespace bert_hip {
 
 namespace {
 
-constexpr int SENT_ID = INT_MAX;        // id of an empty list entry (score -inf): ranks below every row, as in sparse_index.hip
 constexpr int QB_MAX = SPARSE_POSTINGS_QB;
 
-template <int DTYPE> struct Stored {
-    using id_t = std::conditional_t<DTYPE == 1, uint16_t, int32_t>;
-    using w_t = std::conditional_t<DTYPE == 1, half_t, float>;
-};
-
-// Both passes over the stored rows visit the slots of the blocks in storage order: slot e is column (e / 64) % width of row
-// (e / (64 * width)) * 64 + e % 64
+// Both passes over the stored rows visit the slots of the blocks in storage order (slot_decode)
 template <int DTYPE>
 __global__ __launch_bounds__(256) void sparse_postings_count_kernel(SparsePostingsBuildArgs a) {
     using id_t = typename Stored<DTYPE>::id_t;
-    const size_t per_block = (size_t)a.width * SPARSE_BLOCK_ROWS;
-    const size_t total = (size_t)((a.n_rows + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS) * per_block;
+    const size_t total = block_slots(a.n_rows, a.width);
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const size_t blk = e / per_block;
-        const int in = (int)(e - blk * per_block), j = in >> 6, row = (int)blk * SPARSE_BLOCK_ROWS + (in & 63);
+        int row, j;
+        slot_decode(e, a.width, row, j);
         if (row >= a.n_rows || j >= a.counts[row]) continue;
         const int id = (int)((const id_t *)a.sids)[e];
         if (id < 0 || id >= a.n_vocab) continue;               // (never stored: add and load see to it)
@@ -87,11 +76,10 @@ template <int DTYPE>
 __global__ __launch_bounds__(256) void sparse_postings_fill_kernel(SparsePostingsBuildArgs a) {
     using id_t = typename Stored<DTYPE>::id_t;
     using w_t = typename Stored<DTYPE>::w_t;
-    const size_t per_block = (size_t)a.width * SPARSE_BLOCK_ROWS, per_seg = (size_t)a.seg * a.width;
-    const size_t total = (size_t)((a.n_rows + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS) * per_block;
+    const size_t per_seg = (size_t)a.seg * a.width, total = block_slots(a.n_rows, a.width);
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const size_t blk = e / per_block;
-        const int in = (int)(e - blk * per_block), j = in >> 6, row = (int)blk * SPARSE_BLOCK_ROWS + (in & 63);
+        int row, j;
+        slot_decode(e, a.width, row, j);
         if (row >= a.n_rows || j >= a.counts[row]) continue;
         const int id = (int)((const id_t *)a.sids)[e];
         if (id < 0 || id >= a.n_vocab) continue;
@@ -106,26 +94,13 @@ __global__ __launch_bounds__(256) void sparse_postings_fill_kernel(SparsePosting
 __global__ __launch_bounds__(256) void sparse_query_sort_kernel(SparseQuerySortArgs a) {
     __shared__ int keys[SPARSE_MAX_TERMS];
     const int t = threadIdx.x, q = blockIdx.x;
-    int key = INT_MAX;
-    float w = 0.f;
-    if (t < a.kq) {
-        const int id = a.ids[(size_t)q * a.kq + t];
-        if (id >= 0 && id < a.n_vocab) { key = id; w = a.weights[(size_t)q * a.kq + t]; }
+    const RankedTerm r = rank_terms(a.ids, a.weights, (size_t)q * a.kq, a.kq, a.n_vocab, keys, t);
+    // (count <= kq <= 256; the places behind count are never read)
+    if (r.key != INT_MAX) {
+        a.tids[(size_t)q * SPARSE_MAX_TERMS + r.rank] = r.key;
+        a.tw[(size_t)q * SPARSE_MAX_TERMS + r.rank] = r.w;
     }
-    keys[t] = key;
-    const int count = __syncthreads_count(key != INT_MAX);
-    int rank = 0;
-    if (key != INT_MAX)
-        for (int u = 0; u < a.kq; ++u) {
-            const int ku = keys[u];
-            rank += (ku < key || (ku == key && u < t)) ? 1 : 0;
-        }
-    // (every valid entry has a rank of its own below count <= kq <= 256; the places behind count are never read)
-    if (key != INT_MAX) {
-        a.tids[(size_t)q * SPARSE_MAX_TERMS + rank] = key;
-        a.tw[(size_t)q * SPARSE_MAX_TERMS + rank] = w;
-    }
-    if (t == 0) a.tn[q] = count;
+    if (t == 0) a.tn[q] = r.count;
 }
 
 // When the hybrid scan asks for a step's dense scores: 1 = one step ahead — the first step's before the segment's term walk, each
@@ -146,8 +121,7 @@ template <int DTYPE, bool MASKED, bool HYBRID>
 __device__ __forceinline__ void sparse_postings_scan_body(const SparsePostingsScanArgs &a) {
     using w_t = typename Stored<DTYPE>::w_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // (the row-major scan's XCD map: the query tiles of one slice go to one XCD and find the slice's postings in its L2)
-    const int item = (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8);
+    const int item = xcd_item();                 // (kernels.h: the query tiles of one slice go to one XCD and find its postings in that L2)
     if (item >= a.n_items) return;
     const int slice = item / a.n_qtiles, qt = item - slice * a.n_qtiles;
     const int q0 = qt * a.qb, nqv = min(a.qb, a.nq - q0);
@@ -159,12 +133,13 @@ __device__ __forceinline__ void sparse_postings_scan_body(const SparsePostingsSc
     float *tw = (float *)(tids + a.qb * SPARSE_MAX_TERMS);
     float *ls = tw + a.qb * SPARSE_MAX_TERMS;                  // [qb][L]
     int *li = (int *)(ls + a.qb * L);
-    int *tn = li + a.qb * L;                                   // [qb]
-    int *cnt = tn + a.qb;
+    int *tn = li + a.qb * L;                                   // [qb], the counts [qb] behind
+    // a step pushes at most SPARSE_STEP_ROWS entries per query
+    const SelectLists sel{ls, li, tn + a.qb, L, k, L - k - SPARSE_STEP_ROWS};
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    if (tid < nqv) { cnt[tid] = 0; tn[tid] = min(max(a.tn[q0 + tid], 0), SPARSE_MAX_TERMS); }
-    for (int i = tid; i < nqv * L; i += NT) { ls[i] = -INFINITY; li[i] = SENT_ID; }
+    select_init(sel, nqv, tid);
+    if (tid < nqv) tn[tid] = min(max(a.tn[q0 + tid], 0), SPARSE_MAX_TERMS);
     __syncthreads();
     // (only the terms in front of a query's count were written by the sort)
     for (int i = tid; i < nqv * SPARSE_MAX_TERMS; i += NT) {
@@ -178,8 +153,6 @@ __device__ __forceinline__ void sparse_postings_scan_body(const SparsePostingsSc
     for (int q = 0; q < QB_MAX; ++q) { ts[q] = -INFINITY; ti[q] = SENT_ID; }
     __syncthreads();
 
-    // a step pushes at most SPARSE_STEP_ROWS entries per query: sort before a queue could hold fewer free slots
-    const int room = L - k - SPARSE_STEP_ROWS;
     // does row r0 + lrow of a segment of nrow rows qualify (lrow < seg: a step never leaves the segment)
     auto qualifies = [&](int lrow, int row, int nrow) -> bool {
         bool ok = lrow < nrow;
@@ -271,20 +244,13 @@ __device__ __forceinline__ void sparse_postings_scan_body(const SparsePostingsSc
                 if (q < nqv) {
                     float s = acc[q * seg + lrow];
                     if constexpr (HYBRID) s = hybrid_score(a.w_dense, dv[q], a.w_sparse, s);
-                    if (rok && better(s, row, ts[q], ti[q])) {
-                        const int p = atomicAdd(&cnt[q], 1);
-                        ls[q * L + k + p] = s;
-                        li[q * L + k + p] = row;
-                    }
+                    if (rok && better(s, row, ts[q], ti[q])) select_push(sel, q, s, row);
                 }
-            __syncthreads();
-            if (__syncthreads_or(tid < nqv && cnt[tid] > room)) {
-                bitonic_sort_lists(ls, li, nqv, L, tid);
-                if (tid < nqv) cnt[tid] = 0;
+            if (select_step_end(sel, nqv, tid)) {
 #pragma unroll
                 for (int q = 0; q < QB_MAX; ++q)
-                    if (q < nqv) { ts[q] = ls[q * L + k - 1]; ti[q] = li[q * L + k - 1]; }
-                __syncthreads();
+                    if (q < nqv) select_threshold(sel, q, ts[q], ti[q]);
+                select_resume(sel, nqv, tid);
             }
             if constexpr (HYBRID && SPARSE_POSTINGS_D_AHEAD) {
                 dok = nok;
@@ -293,14 +259,8 @@ __device__ __forceinline__ void sparse_postings_scan_body(const SparsePostingsSc
             }
         }
     }
-    __syncthreads();
-    if (__syncthreads_or(tid < nqv && cnt[tid] > 0)) bitonic_sort_lists(ls, li, nqv, L, tid);
-    for (int i = tid; i < nqv * k; i += NT) {
-        const int q = i / k, j = i - q * k;
-        const size_t o = ((size_t)(q0 + q) * a.n_slices + slice) * k + j;
-        a.ws_s[o] = ls[q * L + j];
-        a.ws_i[o] = li[q * L + j];
-    }
+    select_finish(sel, nqv, tid);
+    select_store(sel, nqv, a.ws_s, a.ws_i, q0, a.n_slices, slice, tid);
 }
 
 template <int DTYPE, bool MASKED>
@@ -317,23 +277,14 @@ DeviceFlags g_postings_lds;
 // launchers (sparse_index_kernels.h)
 // ------------------------------------------------------------------------------------------------
 void sparse_postings_kernels_init() {
-    configure_once(g_postings_lds, [] {
-        bool ok = true;
-        for (const void *f : {(const void *)sparse_postings_scan_kernel<0, false>, (const void *)sparse_postings_scan_kernel<1, false>,
-                              (const void *)sparse_postings_scan_kernel<0, true>, (const void *)sparse_postings_scan_kernel<1, true>,
-                              (const void *)sparse_postings_hybrid_scan_kernel<0, false>, (const void *)sparse_postings_hybrid_scan_kernel<1, false>,
-                              (const void *)sparse_postings_hybrid_scan_kernel<0, true>, (const void *)sparse_postings_hybrid_scan_kernel<1, true>})
-            ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SPARSE_LDS_MAX) == hipSuccess && ok;
-        if (!ok) (void)hipGetLastError();                      // (a launch that cannot have its LDS fails, and the search reports it)
-    });
+    scan_lds_opt_in(g_postings_lds, {SPARSE_SCAN_FAMILY(sparse_postings_scan_kernel), SPARSE_SCAN_FAMILY(sparse_postings_hybrid_scan_kernel)});
 }
 
 void launch_sparse_postings_build(int dtype, const SparsePostingsBuildArgs &a, hipStream_t s) {
     if (a.n_rows <= 0) return;
     const int n_segs = sparse_segments(a.n_rows, a.seg);
     const size_t off_bytes = (size_t)n_segs * (a.n_vocab + 1) * 4;
-    const size_t total = (size_t)((a.n_rows + SPARSE_BLOCK_ROWS - 1) / SPARSE_BLOCK_ROWS) * a.width * SPARSE_BLOCK_ROWS;
-    const int blocks = (int)std::min<size_t>((total + 255) / 256, 16384);
+    const int blocks = (int)std::min<size_t>((block_slots(a.n_rows, a.width) + 255) / 256, 16384);
     (void)hipMemsetAsync(a.off, 0, off_bytes, s);
     if (dtype == 1) BERT_LAUNCH(sparse_postings_count_kernel<1>, dim3(blocks), dim3(256), 0, s, a);
     else BERT_LAUNCH(sparse_postings_count_kernel<0>, dim3(blocks), dim3(256), 0, s, a);
@@ -348,21 +299,11 @@ void launch_sparse_query_sort(const SparseQuerySortArgs &a, hipStream_t s) {
 }
 
 void launch_sparse_postings_scan(int dtype, const SparsePostingsScanArgs &a, size_t lds, hipStream_t s) {
-    const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
-    const bool masked = a.live || a.allow;
-    if (dtype == 1 && masked) BERT_LAUNCH((sparse_postings_scan_kernel<1, true>), dim3(grid), dim3(NT), lds, s, a);
-    else if (dtype == 1) BERT_LAUNCH((sparse_postings_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
-    else if (masked) BERT_LAUNCH((sparse_postings_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
-    else BERT_LAUNCH((sparse_postings_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
+    SPARSE_SCAN_LAUNCH(sparse_postings_scan_kernel, dtype, a, lds, s);
 }
 
 void launch_sparse_postings_hybrid_scan(int dtype, const SparsePostingsScanArgs &a, size_t lds, hipStream_t s) {
-    const int grid = (a.n_items + 7) / 8 * 8;
-    const bool masked = a.live || a.allow;
-    if (dtype == 1 && masked) BERT_LAUNCH((sparse_postings_hybrid_scan_kernel<1, true>), dim3(grid), dim3(NT), lds, s, a);
-    else if (dtype == 1) BERT_LAUNCH((sparse_postings_hybrid_scan_kernel<1, false>), dim3(grid), dim3(NT), lds, s, a);
-    else if (masked) BERT_LAUNCH((sparse_postings_hybrid_scan_kernel<0, true>), dim3(grid), dim3(NT), lds, s, a);
-    else BERT_LAUNCH((sparse_postings_hybrid_scan_kernel<0, false>), dim3(grid), dim3(NT), lds, s, a);
+    SPARSE_SCAN_LAUNCH(sparse_postings_hybrid_scan_kernel, dtype, a, lds, s);
 }
 
 }  // namespace bert_hip

@@ -10,9 +10,8 @@
 //                   of 32 tokens in LDS once (Form::stage).  Then each wave takes whole documents of the slice — first + wave,
 //                   first + wave + 4, ... — and scores each alone (Form::score).  No LDS exchange between waves: a document belongs to
 //                   one wave, a short one costs one chain and one reduction.
-//   Selection.      index_probe_kernel's for one query: a list of L (score, id) entries in LDS, the threshold in registers; lane 0
-//                   of a wave pushes a document that beats the threshold; every TOKEN_ROUNDS documents per wave the workgroup looks
-//                   at the count and sorts (bitonic_sort_lists) when the room left cannot hold another step's pushes.  The trip
+//   Selection.      topk_select.h's queue with one list, the threshold in registers; lane 0 of a wave pushes a document that beats
+//                   the threshold; every TOKEN_ROUNDS documents per wave the workgroup looks at the count (select_step_end).  The trip
 //                   counts are the workgroup's — a wave without a document in a round scores nothing —, so every barrier is met by all
 //                   four waves.  k entries per (query, slice) reach the workspace, which topk_merge_kernel merges; the scores never
 //                   reach HBM.
@@ -71,8 +70,6 @@
 namespace bert_hip {
 
 namespace {
-
-constexpr int SENT_ID = INT_MAX;        // id of an empty list entry (score -inf): ranks below every document, as in search.hip
 
 static_assert(TOKEN_STEP_DOCS == 64, "the masked scan keeps a step's mask in one 64-bit word");
 
@@ -266,13 +263,11 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
     static_assert(!(MASKED && LISTED), "a rescore tests live per id");
     static_assert(!LISTED || Form::LISTABLE, "the f16 form's rescore is token_index_pairs_kernel + maxsim_kernel");
     extern __shared__ __attribute__((aligned(16))) unsigned char ti_lds[];
-    // workgroup b runs on XCD b % 8: consecutive items — the queries of one slice — go to one XCD, so that they find the slice's rows
-    // in that XCD's L2 (the grid is a multiple of 8; items beyond n_items do nothing)
-    const int item = (int)(blockIdx.x % 8) * (int)(gridDim.x / 8) + (int)(blockIdx.x / 8);
+    const int item = xcd_item();                 // (kernels.h: the queries of one slice go to one XCD and find its rows in that L2)
     if (item >= a.n_items) return;
     const int slice = item / a.nq, qi = item - slice * a.nq;
     const int k = a.k, L = a.L;
-    // Code placement (DESIGN §16.3 "Measured").  With the same instructions in the same order the scan's time moves by 0.2 .. 1.3 % with the
+    // Code placement (DESIGN §16.3 "Measured"; §8.1: the shared selection kept both offsets).  With the same instructions in the same order the scan's time moves by 0.2 .. 1.3 % with the
     // byte offset of the round loop's code inside the kernel.  The plain instantiations therefore start with Form::PLAIN_PAD s_nop, once per
     // workgroup: their loops lie at the offsets they were measured at.  The numbers belong to this compiler's output for this source: a change
     // in front of the round loop drops them or derives them again from a measurement, it does not inherit them
@@ -281,7 +276,7 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
     Form f;
     float *ls = (float *)f.init(a, ti_lds);                    // behind the staged query: the list and the count
     int *li = (int *)(ls + L);
-    int *cnt = li + L;
+    const SelectLists sel{ls, li, li + L, L, k, L - k - TOKEN_STEP_DOCS};    // a step pushes at most TOKEN_STEP_DOCS entries
     // (everything up to the loop is uniform over the workgroup)
     const int q0 = a.qcu[qi], nq = a.qcu[qi + 1] - q0;
     const int n_list = LISTED ? a.n_cand : a.n_docs;           // what the slices cut: candidate positions, or documents
@@ -289,26 +284,24 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
     const int r1 = (int)min((long long)r0 + a.slice_docs, (long long)n_list);
     const size_t out = ((size_t)qi * a.n_slices + slice) * k;
     if (nq <= 0 || q0 < 0 || nq > a.max_q_len || r0 >= r1) {
-        for (int j = tid; j < k; j += NT) { a.ws_s[out + j] = -INFINITY; a.ws_i[out + j] = SENT_ID; }
+        select_store_empty(a.ws_s, a.ws_i, out, k, tid);
         return;
     }
     const int nblk = (nq + TOKEN_QB - 1) / TOKEN_QB;
     [[maybe_unused]] const bool qbad = f.stage(a, qi, q0, nq, nblk, tid);
-    for (int i = tid; i < L; i += NT) { ls[i] = -INFINITY; li[i] = SENT_ID; }
-    if (tid == 0) *cnt = 0;
+    select_init(sel, 1, tid);
     float ts = -INFINITY;
     int ti = SENT_ID;
     // (the staging's barrier; a query its form calls bad: the guards' lists)
     if constexpr (Form::BAD_QUERIES) {
         if (__syncthreads_or(qbad)) {
-            for (int j = tid; j < k; j += NT) { a.ws_s[out + j] = -INFINITY; a.ws_i[out + j] = SENT_ID; }
+            select_store_empty(a.ws_s, a.ws_i, out, k, tid);
             return;
         }
     } else {
         __syncthreads();
     }
 
-    const int room = L - k - TOKEN_STEP_DOCS;                  // a step pushes at most TOKEN_STEP_DOCS entries
     for (int base = r0; base < r1; base += TOKEN_STEP_DOCS) {
         // MASKED: bit i of m = document base + i qualifies.  The step's documents lie in up to three mask words (a slice starts
         // anywhere); only words that hold a document below r1 are read, so none at or beyond ceil(n_docs / 32).  Everything here is
@@ -321,8 +314,8 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
             const uint32_t w2 = wi + 2 <= we ? token_mask_word(a, wi + 2) : 0u;
             m = ((uint64_t)w1 << 32 | w0) >> sh;
             if (sh) m |= (uint64_t)w2 << (64 - sh);
-            // a step without a qualifying document pushes nothing: the count is what the last look left, so both barriers and the
-            // look can go — for the whole workgroup, since m is the workgroup's
+            // a step without a qualifying document pushes nothing: the count is what the last look left, so select_step_end — both
+            // barriers and the look — can go, for the whole workgroup, since m is the workgroup's
             if (m == 0) continue;
         }
         for (int u = 0; u < TOKEN_ROUNDS; ++u) {
@@ -343,24 +336,14 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
             const int d0 = __builtin_amdgcn_readfirstlane(a.cu[d]), nd = __builtin_amdgcn_readfirstlane(a.cu[d + 1]) - d0;
             bool dbad;
             const float total = f.score(a, d0, nd, nq, nblk, lane, dbad);
-            if (lane == 0 && !dbad && better(total, d, ts, ti)) {
-                const int p = atomicAdd(cnt, 1);
-                ls[k + p] = total;
-                li[k + p] = d;
-            }
+            if (lane == 0 && !dbad && better(total, d, ts, ti)) select_push(sel, 0, total, d);
         }
-        __syncthreads();
-        // (one thread reads the count between the two barriers: the next step's pushes come after the second)
-        if (__syncthreads_or(tid == 0 && *cnt > room)) {
-            bitonic_sort_lists(ls, li, 1, L, tid);
-            ts = ls[k - 1];
-            ti = li[k - 1];
-            if (tid == 0) *cnt = 0;
-            __syncthreads();
+        if (select_step_end(sel, 1, tid)) {
+            select_threshold(sel, 0, ts, ti);
+            select_resume(sel, 1, tid);
         }
     }
-    __syncthreads();
-    if (__syncthreads_or(tid == 0 && *cnt > 0)) bitonic_sort_lists(ls, li, 1, L, tid);
+    select_finish(sel, 1, tid);
     for (int j = tid; j < k; j += NT) { a.ws_s[out + j] = ls[j]; a.ws_i[out + j] = li[j]; }
 }
 
@@ -434,7 +417,7 @@ void token_index_kernels_init() {
 
 void launch_token_scan(int dtype, const TokenScanArgs &a, hipStream_t s) {
     if (a.n_items <= 0) return;
-    const int grid = (a.n_items + 7) / 8 * 8;                  // (the kernel's XCD map)
+    const int grid = xcd_grid(a.n_items);
     const size_t lds = token_scan_lds_bytes(a.dim, dtype, a.max_q_len, a.k);
     const bool masked = a.live || a.allow;
     if (dtype == 2) {
