@@ -370,7 +370,9 @@ def test_b1_memory_per_row(model):
     ix.reserve(2_000_000, 1, 1)
     used = before - hip.free_bytes()
     ix.close()
-    assert 2_000_000 * 48 <= used <= 2_000_000 * 48 + (16 << 20), used     # dpad / 8 = 48 bytes per row
+    # dpad / 8 = 48 bytes per row.  (A driver may report free memory as whole free 2 MiB pages: an allocation that begins and ends
+    # in pages already in part taken then shows as up to two pages less than its bytes.)
+    assert 2_000_000 * 48 - 2 * (2 << 20) < used <= 2_000_000 * 48 + (16 << 20), used
 
 
 def test_b1_profile_names(make_model):

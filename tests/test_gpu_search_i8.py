@@ -299,7 +299,9 @@ def test_i8_memory_per_row(model):
         return used
 
     f16, i8 = taken("f16"), taken("i8")
-    assert f16 >= 2_000_000 * 384 * 2, f16
+    # (a driver may report free memory as whole free 2 MiB pages: an allocation that begins and ends in pages already in part
+    # taken then shows as up to two pages less than its bytes)
+    assert f16 > 2_000_000 * 384 * 2 - 2 * (2 << 20), f16
     assert i8 <= 0.55 * f16, (i8, f16, i8 / f16)
 
 
