@@ -2,6 +2,7 @@
 // of the forward pass.  Replaces the reference's ggml arena + per-sentence graph build + execute
 // (reference bert.cpp:730-941, sizing :680-713) with a fixed kernel sequence over a packed variable-length batch: by default
 // one launch for all layers behind the embedding kernel, else two fused launches per layer (plan() in engine.hip picks the route).
+// engine.hip holds creation, the workspace, plan(), the routes and the device forms; engine_host.cpp the forms that take host memory.
 // The weights are weights.h's, the switches options.h's, the per-kernel times profiler.h's.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,21 +28,30 @@ public:
     static Engine *create(const ModelFile &mf, int device, std::string &err);
     ~Engine();
 
-    // host-resident packed batch (validated by the caller), blocking
+    // host-resident packed batch (validated by the caller), blocking; cut by the chunk rule (host_chunks.h) and pipelined through two
+    // pinned slots.  This and the other host forms below: engine_host.cpp
     // embeddings: host destination [n_sentences][H]; d_embeddings (optional, instead): destination in this device's memory
-    // pool_mode: as for eval_packed_device below
+    // pool_mode: as Pass::pool_mode below
     int eval_packed_host(const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, float *embeddings,
                          std::string &err, float *d_embeddings = nullptr, int pool_mode = -1);
-    // device-resident, asynchronous on `stream`
-    // d_windows / n_windows: optional sentence windows of the fused projection+attention kernel (build_windows), in
-    // device memory; without them the same windows are built on the device (launch_build_windows) when the batch is
-    // short enough on average for packing to pay, else sentences are placed by the uniform rule of qkv_attention2.hip
-    int eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int n_sentences, int n_tokens, int max_len,
-                           float *d_out, hipStream_t stream, float *d_hidden, std::string &err,
-                           const int2 *d_windows = nullptr, int n_windows = 0, int window_slots = 0,       // window_slots: the place granularity d_windows was built with (0: read it now)
-                           int pool_mode = -1,                   // kernels.h POOL_*: what the host call read for all its chunks (-1: read the options now)
-                           void *d_token_rows = nullptr, int token_flags = 0,      // token rows (below); d_out may then be null: the embeddings stay in d_out_
-                           const int32_t *d_first_len = nullptr);                  // token types (below); null: type 0 everywhere, the untyped embedding kernels
+    // A pass on device-resident ids, asynchronous on `stream`: everything a caller says about it.  A caller names the fields it sets.
+    struct Pass {
+        const int32_t *d_tokens = nullptr, *d_cu = nullptr;
+        int n_sentences = 0, n_tokens = 0, max_len = 0;
+        hipStream_t stream = nullptr;
+        float *d_out = nullptr;                // the embeddings [n_sentences][H]; null: they stay in d_out_ (a token-rows or a score pass)
+        float *d_hidden = nullptr;             // eval_hidden's tap: the states after the embedding LayerNorm and after every layer
+        // d_windows / n_windows: optional sentence windows of the fused projection+attention kernel (build_windows), in
+        // device memory; without them the same windows are built on the device (launch_build_windows) when the batch is
+        // short enough on average for packing to pay, else sentences are placed by the uniform rule of qkv_attention2.hip
+        const int2 *d_windows = nullptr;
+        int n_windows = 0, window_slots = 0;   // window_slots: the place granularity d_windows was built with (0: read it now)
+        int pool_mode = -1;                    // kernels.h POOL_*: what the host call read for all its chunks (-1: read the options now)
+        void *d_token_rows = nullptr;          // token rows (below), written under token_flags
+        int token_flags = 0;
+        const int32_t *d_first_len = nullptr;  // token types (below); null: type 0 everywhere, the untyped embedding kernels
+    };
+    int eval_packed_device(const Pass &pass, std::string &err);
     // Sentence pairs and scores (bert_hip.h): a TYPED pass carries d_first_len [n_sentences] — the leading tokens of each sentence that take
     // token-type row 0, the rest row 1 (kernels.h launch_embed_ln) — and plans like any other pass; only the embedding launch differs.
     // score_packed_device: a typed pass that ends in POOL_CLS | POOL_RAW rows in d_out_ (the mode handed in as an argument, as the grouped
@@ -52,8 +62,8 @@ public:
     int score_packed_device(const int32_t *d_tokens, const int32_t *d_cu, const int32_t *d_first_len, int n_sentences, int n_tokens, int max_len,
                             int flags, float *d_scores, hipStream_t stream, std::string &err,
                             const int2 *d_windows = nullptr, int n_windows = 0, int window_slots = 0);      // (as eval_packed_device takes them)
-    // Host forms, blocking, on this engine's device: cut at chunk_tokens between sentences, one copy per chunk and direction (ids |
-    // cu_seqlens | first_len in; rows or scores out).  first_len: nullable (all type 0), validated by the caller.  scores == false: the
+    // Host forms, blocking, on this engine's device: cut by the chunk rule (host_chunks.h), one copy per chunk and direction (the
+    // staging block in; rows or scores out).  first_len: nullable (all type 0), validated by the caller.  scores == false: the
     // context's pooling and normalisation, out [n_sentences][H]; true: out [n_sentences][n_labels].
     int eval_packed_typed_host(const int32_t *tokens, const int32_t *cu_seqlens, const int32_t *first_len, int n_sentences, bool scores, int flags,
                                float *out, std::string &err);
@@ -69,14 +79,14 @@ public:
     bool has_rel_bias() const { return w_->rel_bias; }
     int sparse_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int n_sentences, int n_tokens, int max_len, int k, int32_t *d_ids,
                              float *d_weights, hipStream_t stream, std::string &err);
-    // Host form, blocking, on this engine's device: cut at chunk_tokens between sentences and at the sentences whose results fit 32 MiB,
-    // one plain copy per chunk and direction.  k == 0: weights [n_sentences][n_vocab], ids unused.
+    // Host form, blocking, on this engine's device: cut by the chunk rule, capped at the sentences whose results fit 32 MiB, one copy
+    // per chunk and direction.  k == 0: weights [n_sentences][n_vocab], ids unused.
     int sparse_packed_host(const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int k, int32_t *ids, float *weights, std::string &err);
     // Token rows (bert_hip.h "token rows and late interaction"): a pass with one more destination, [n_tokens][H] rows of the final states
     // (kernels.h launch_token_rows, TOKEN_ROWS_* flags), written by one launch ("token_rows" in the profile) beside the pooling launch.
     // Such a pass does not take the one-launch kernel (which keeps x on chip between its phases and pools inside the launch: the other
     // routes leave the final states in x_ in row order); LayerNorm folding stays as planned, so the embeddings are eval_packed's bits.
-    // Host form, blocking, on this engine's device: cut at chunk_tokens between sentences, one plain copy per chunk and direction.
+    // Host form, blocking, on this engine's device: cut by the chunk rule, one copy in and one per result out for every chunk.
     // flags: TOKEN_ROWS_NORMALIZE only (rows are f32).  embeddings: nullable.
     int eval_packed_tokens_host(const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int flags, float *rows, float *embeddings,
                                 std::string &err);
@@ -136,6 +146,9 @@ private:
     // sentences whose dense rows [n_vocab] f32 fit 32 MiB, at least one: what bounds sparse_dense_ and a host chunk's results
     int sparse_sentence_cap() const { return std::max(1, (int)(((size_t)32 << 20) / ((size_t)hp_.n_vocab * 4))); }
     bool ensure_sparse(int n_sentences, std::string &err);    // grows sparse_chunk_ (never past the cap) and sparse_dense_ with it
+    template <class OutBytes, class Queue>                    // (engine_host.cpp)
+    int blocking_host_chunks(const int32_t *tokens, const int32_t *cu_seqlens, const int32_t *first_len, int n_sentences, int max_sentences, int slots,
+                             OutBytes &&out_bytes, Queue &&queue, std::string &err);
 
     // The forward pass: plan() decides everything once, before the first launch; a forward_* method per route only launches.
     enum class Route { F32, LATENCY, ONE_LAUNCH, FOLDED, LAYERED };
@@ -147,13 +160,11 @@ private:
         Family qkv = Family::NAIVE, o = Family::NAIVE, ffi = Family::NAIVE, ffo = Family::NAIVE;
     };
     struct Plan {
-        // the call (windows, n_windows: the caller's list, or the one the pass builds on the device)
-        const int32_t *tokens, *cu;
-        int B, T, max_len, t_pad, slots, pool_mode;
-        float *out, *hidden;
-        void *token_rows;             // token rows wanted (eval_packed_device): no one-launch kernel
-        const int32_t *first_len;     // a typed pass (eval_packed_device): the embedding launch's first_len, else null
-        hipStream_t s;
+        Pass pass;                    // the call
+        // what the pass resolved once: whole tiles of tokens, the place granularity and pooling mode read once per call, the
+        // embeddings' destination (the caller's or d_out_), and the windows (the caller's list, or the one the pass builds on the device)
+        int t_pad, slots, pool_mode;
+        float *out;
         const int2 *windows;
         int n_windows;
         // the decisions
@@ -163,8 +174,7 @@ private:
         bool embed_lanes = false;     // ONE_LAUNCH on full windows: the embedding kernel writes y_ in lane order, x_ is not written (model_kernel.hip)
         std::vector<LayerPlan> layers;
     };
-    Plan plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s, float *d_hidden,
-              const int2 *d_windows, int n_windows, int slots, int pool_mode, void *d_token_rows = nullptr, const int32_t *d_first_len = nullptr) const;
+    Plan plan(const Pass &pass, int slots, int pool_mode, float *d_out) const;
     bool forward_f32(const Plan &p, std::string &err);        // f32 files in f32 arithmetic (f32_route.hip), one launch per operation
     void forward_latency(const Plan &p);
     void forward_one_launch(const Plan &p);
@@ -187,11 +197,13 @@ private:
 
     // workspace (grow-only)
     DevBuf x_, qkv_, ctx_, y_, ff_, v32_, d_tokens_, d_cu_, d_out_, d_hidden_, status_, windows_;
-    DevBuf typed_in_, typed_out_;                             // the host forms of the typed pass: a chunk's ids | cu_seqlens | first_len, and its rows or scores
-    DevBuf sparse_dense_, sparse_in_, sparse_out_;           // learned sparse embeddings: the top-k form's dense rows [sparse_chunk_][n_vocab] f32; the host form's ids | cu_seqlens and its results
+    // the blocking host forms (typed, token rows, sparse, grouped): what a chunk sends and what comes back.  ONE pair: a context serves
+    // one call at a time and each of these forms drains stream_ behind every chunk and on every failure, so no two are live at once
+    DevBuf host_in_, host_out_;
+    std::vector<char> host_block_;                            // the pageable host image of host_in_ (blocking_host_chunks)
+    DevBuf sparse_dense_;                                     // learned sparse embeddings: the top-k form's dense rows [sparse_chunk_][n_vocab] f32
     int sparse_chunk_ = 0;
-    DevBuf tok_in_, tok_rows_;                                // the host form of the token rows: a chunk's ids | cu_seqlens, and its rows
-    DevBuf raw_rows_, group_in_, group_out_;                  // grouped pooling: the sentences' POOL_RAW rows [n_sentences][H] f32; the host form's cu_seqlens | group_cu and its groups' rows
+    DevBuf raw_rows_;                                         // grouped pooling: the sentences' POOL_RAW rows [n_sentences][H] f32 (the device form writes it under busy_)
     DevBuf ln_stats1_, ln_stats2_, ln_rows1_, ln_rows2_;      // LayerNorm folding: per-row partial statistics / finalized rows of the two LayerNorms of a layer
     hipStream_t stream_ = nullptr;
     // the workspace serves ONE forward pass at a time: every pass waits for the previous one's event on its own stream
@@ -199,8 +211,7 @@ private:
     // host path: two sets of pinned staging + device id / embedding buffers, so that the host stages chunk i+1 and
     // unpacks chunk i-1 while the GPU computes chunk i (eval_packed_host)
     struct HostSlot {
-        // ONE pinned staging block per chunk — ids | cu_seqlens | windows, each part 16-byte aligned — and one device image of
-        // it: a single H2D copy per chunk.  The embeddings come back without a copy: the pooling kernel writes them straight
+        // ONE pinned staging block per chunk (host_chunks.h StagingLayout) and one device image of it: a single H2D copy per chunk.  The embeddings come back without a copy: the pooling kernel writes them straight
         // into h_out (pinned, mapped into the device's address space as d_out_host).
         char *h_in = nullptr, *d_in_host = nullptr;          // (d_in_host: h_in as the device sees it)
         float *h_out = nullptr, *d_out_host = nullptr;

@@ -1,13 +1,10 @@
-// engine.hip — see engine.h.
+// engine.hip — see engine.h: creation, the workspace, plan(), the routes and the device forms (the host forms: engine_host.cpp).
 #include "engine.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <chrono>
 #include <cstring>
-#include <system_error>
-#include <thread>
 
 namespace bert_hip {
 
@@ -124,23 +121,25 @@ void Engine::build_windows(const int32_t *cu, int B, std::vector<int2> &windows,
     if (B > first) windows.push_back(make_int2(first, B - first));
 }
 
-int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out,
-                               hipStream_t s, float *d_hidden, std::string &err, const int2 *d_windows, int n_windows, int slots_in,
-                               int pool_mode_in, void *d_token_rows, int token_flags, const int32_t *d_first_len) {
+int Engine::eval_packed_device(const Pass &pass, std::string &err) {
+    const int B = pass.n_sentences, T = pass.n_tokens, max_len = pass.max_len;
+    const int32_t *d_tokens = pass.d_tokens, *d_cu = pass.d_cu, *d_first_len = pass.d_first_len;
+    const hipStream_t s = pass.stream;
     if (B <= 0 || T <= 0) return 0;
     // the windows' place granularity, read ONCE per pass (the host path read it when it built its list): the window list, the
     // grid bound and the kernels' place rule must agree whatever another thread or context sets meanwhile
-    const int slots = slots_in ? slots_in : window_slots();
+    const int slots = pass.window_slots ? pass.window_slots : window_slots();
     // (so are "pooling" and "normalize": every launch that ends the pass gets the plan's value)
-    const int pool_mode = pool_mode_in >= 0 ? pool_mode_in : opt_.pool_mode();
+    const int pool_mode = pass.pool_mode >= 0 ? pass.pool_mode : opt_.pool_mode();
     HIP_OK(hipSetDevice(device_), err, -1);
     // one forward pass at a time on the shared workspace: wait (on the caller's stream) for the previous pass — unless s is capturing
     StreamOp op;
     if (!op_begin(s, busy_, op, err)) return -1;
     if (!ensure_workspace((T + 255) / 256 * 256, B, err)) return -1;
     prof_.begin_pass();
-    if (!d_out) d_out = d_out_.as<float>();                   // (a token-rows call that wants no embeddings: ensure_workspace sized it)
-    const Plan p = plan(d_tokens, d_cu, B, T, max_len, d_out, s, d_hidden, d_windows, n_windows, slots, pool_mode, d_token_rows, d_first_len);
+    // (a token-rows call that wants no embeddings: ensure_workspace sized d_out_)
+    float *d_out = pass.d_out ? pass.d_out : d_out_.as<float>();
+    const Plan p = plan(pass, slots, pool_mode, d_out);
     bool ok = true;
     if (p.route == Route::F32) ok = forward_f32(p, err);
     else {
@@ -169,18 +168,18 @@ int Engine::eval_packed_device(const int32_t *d_tokens, const int32_t *d_cu, int
     if (!ok) return -1;
     // (every route a token-rows pass can take left the final states in x_, [T][H] in row order: f32 on the f32 route, else f16)
     // (a destination that IS x_: the caller wants them where they are — the sparse head —, nothing to copy)
-    if (d_token_rows && d_token_rows != x_.p)
-        timed("token_rows", 0.0, s, [&] { launch_token_rows(x_.p, p.route == Route::F32, T, hp_.n_embd, d_cu, B, max_len, token_flags, d_token_rows, s); });
+    if (pass.d_token_rows && pass.d_token_rows != x_.p)
+        timed("token_rows", 0.0, s, [&] { launch_token_rows(x_.p, p.route == Route::F32, T, hp_.n_embd, d_cu, B, max_len, pass.token_flags, pass.d_token_rows, s); });
     HIP_OK(hipGetLastError(), err, -1);
     return op_end(op, err) ? 0 : -1;
 }
 
 // The route of a pass and, per layer, its kernels: every eligibility test of the forward pass, each made here once.  Launches nothing.
-Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, int T, int max_len, float *d_out, hipStream_t s,
-                          float *d_hidden, const int2 *d_windows, int n_windows, int slots, int pool_mode, void *d_token_rows,
-                          const int32_t *d_first_len) const {
+Engine::Plan Engine::plan(const Pass &pass, int slots, int pool_mode, float *d_out) const {
+    const int B = pass.n_sentences, T = pass.n_tokens, max_len = pass.max_len, n_windows = pass.n_windows;
+    const int2 *d_windows = pass.d_windows;
     // (t_pad: whole tiles of every kernel family, 128- and 256-token tiles)
-    Plan p{d_tokens, d_cu, B, T, max_len, (T + 255) / 256 * 256, slots, pool_mode, d_out, d_hidden, d_token_rows, d_first_len, s, d_windows, n_windows};
+    Plan p{pass, (T + 255) / 256 * 256, slots, pool_mode, d_out, d_windows, n_windows};
     if (w_->f32_file && opt_.f32_exact) { p.route = Route::F32; return p; }
     const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh, Lz = hp_.n_layer;
     auto family = [&](const GemmWeightStore &W) {
@@ -210,9 +209,9 @@ Engine::Plan Engine::plan(const int32_t *d_tokens, const int32_t *d_cu, int B, i
                family(L.ffi_fold) == Family::GEMM256 && lp.ffo == Family::GEMM256 && !(opt_.qkv2 && qkv2_shape) && !(opt_.tail && tail_shape);
     }
     // a hidden-state tap wants every layer's normalised states: it takes neither the one-launch kernel nor the folded LayerNorms
-    if (d_hidden) one_launch = fold = false;
+    if (pass.d_hidden) one_launch = fold = false;
     // token rows want the last layer's states in x_ in row order: not the one-launch kernel; the folded LayerNorms stay
-    if (d_token_rows) one_launch = false;
+    if (pass.d_token_rows) one_launch = false;
     const bool fused_windows = p.layers[0].qkv2, latency_call = opt_.latency && T <= opt_.latency_tokens;
     one_launch = one_launch && fused_windows && opt_.one_launch && opt_.tail && !latency_call;
     // sentence windows of the fused projection+attention kernel: the caller's (host path), or built on the device from cu_seqlens
@@ -257,11 +256,11 @@ bool Engine::gemm(const Plan &p, const char *name, Family f, const GemmWeightSto
     const half_t *a = (const half_t *)A, *r = (const half_t *)resid;
     bool ok = !(ln && ln->flags) || f == Family::GEMM256;
     if (ok)
-        timed(name, 2.0 * p.T * W.w.N * W.w.K, p.s, [&] {
-            if (f == Family::F32) launch_f32_gemm((const float *)A, W.w.w32, bias, (const float *)resid, (float *)C, p.T, W.w.N, W.w.K, epi, p.s);
-            else if (f == Family::GEMM256) ok = launch_gemm256(W.w, a, bias, r, (half_t *)C, p.t_pad, epi, p.s, ln);
-            else if (f == Family::MFMA) launch_gemm_mfma(W.w, a, bias, r, (half_t *)C, p.t_pad, epi, p.s);
-            else launch_gemm_naive(W.w, a, bias, r, (half_t *)C, p.T, epi, p.s);
+        timed(name, 2.0 * p.pass.n_tokens * W.w.N * W.w.K, p.pass.stream, [&] {
+            if (f == Family::F32) launch_f32_gemm((const float *)A, W.w.w32, bias, (const float *)resid, (float *)C, p.pass.n_tokens, W.w.N, W.w.K, epi, p.pass.stream);
+            else if (f == Family::GEMM256) ok = launch_gemm256(W.w, a, bias, r, (half_t *)C, p.t_pad, epi, p.pass.stream, ln);
+            else if (f == Family::MFMA) launch_gemm_mfma(W.w, a, bias, r, (half_t *)C, p.t_pad, epi, p.pass.stream);
+            else launch_gemm_naive(W.w, a, bias, r, (half_t *)C, p.pass.n_tokens, epi, p.pass.stream);
         });
     if (!ok) err = std::string(name) + ": no " + kernel[(int)f] + " kernel for LayerNorm-folding flags " + std::to_string(ln->flags) + ", epilogue " + std::to_string(epi);
     return ok;
@@ -273,46 +272,46 @@ void Engine::attention(const Plan &p) {
     half_t *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>();
     // (the relative position bias of the file, if it has one: null pointers otherwise)
     const int P = hp_.n_max_tokens;
-    timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] {
-        if (opt_.attn_naive || !launch_attention_mfma(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s, w_->rel_scaled.as<float>(), P))
-            launch_attention_naive(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s, w_->rel.as<float>(), P);
+    timed("attention", 4.0 * p.pass.n_tokens * p.pass.max_len * H, p.pass.stream, [&] {
+        if (opt_.attn_naive || !launch_attention_mfma(qkv, p.pass.d_cu, p.pass.n_sentences, nh, dh, p.pass.max_len, ctx, p.pass.stream, w_->rel_scaled.as<float>(), P))
+            launch_attention_naive(qkv, p.pass.d_cu, p.pass.n_sentences, nh, dh, p.pass.max_len, ctx, p.pass.stream, w_->rel.as<float>(), P);
     });
 }
 
 // the layer states of eval_hidden as f32: x after the embedding LayerNorm (idx 0) and after every layer
 void Engine::tap(const Plan &p, int idx) {
-    const size_t n = (size_t)p.T * hp_.n_embd;
-    if (p.hidden && p.route == Route::F32) (void)hipMemcpyAsync(p.hidden + idx * n, x_.p, n * 4, hipMemcpyDeviceToDevice, p.s);
-    else if (p.hidden) launch_f16_to_f32(x_.as<half_t>(), p.hidden + idx * n, n, p.s);
+    const size_t n = (size_t)p.pass.n_tokens * hp_.n_embd;
+    if (p.pass.d_hidden && p.route == Route::F32) (void)hipMemcpyAsync(p.pass.d_hidden + idx * n, x_.p, n * 4, hipMemcpyDeviceToDevice, p.pass.stream);
+    else if (p.pass.d_hidden) launch_f16_to_f32(x_.as<half_t>(), p.pass.d_hidden + idx * n, n, p.pass.stream);
 }
 
 // The latency route (skinny.hip): a call of a few windows would keep as many CUs of 256 busy on the fused kernels.  Same bits per
 // sentence (the route must not show in the results), seven short launches per layer.
 void Engine::forward_latency(const Plan &p) {
-    const int H = hp_.n_embd, I = hp_.n_intermediate, tb = (p.T + 31) / 32, Lz = hp_.n_layer;
+    const int H = hp_.n_embd, I = hp_.n_intermediate, tb = (p.pass.n_tokens + 31) / 32, Lz = hp_.n_layer;
     half_t *x = x_.as<half_t>(), *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>(), *y = y_.as<half_t>(), *ff = ff_.as<half_t>();
     float *v32 = v32_.as<float>();
     for (int il = 0; il < Lz; ++il) {
         const LayerWeights &L = w_->layers[il];
         // (from the second layer on the QKV kernel LayerNorms the previous layer's output itself and writes x)
         const LayerWeights *P = il ? &w_->layers[il - 1] : nullptr;
-        timed("skinny_qkv", 2.0 * p.T * 3 * H * H, p.s, [&] {
+        timed("skinny_qkv", 2.0 * p.pass.n_tokens * 3 * H * H, p.pass.stream, [&] {
             launch_skinny_gemm(0, L.qkv.w, x, P ? v32 : nullptr, P ? P->ln_out_w.as<float>() : nullptr, P ? P->ln_out_b.as<float>() : nullptr,
-                               x, L.qkv_b.as<float>(), nullptr, qkv, nullptr, tb, p.s);
+                               x, L.qkv_b.as<float>(), nullptr, qkv, nullptr, tb, p.pass.stream);
         });
         attention(p);
-        timed("skinny_proj", 2.0 * p.T * H * H, p.s, [&] {
-            launch_skinny_gemm(1, L.o.w, ctx, nullptr, nullptr, nullptr, nullptr, L.o_b.as<float>(), x, nullptr, v32, tb, p.s);
+        timed("skinny_proj", 2.0 * p.pass.n_tokens * H * H, p.pass.stream, [&] {
+            launch_skinny_gemm(1, L.o.w, ctx, nullptr, nullptr, nullptr, nullptr, L.o_b.as<float>(), x, nullptr, v32, tb, p.pass.stream);
         });
-        timed("skinny_ffn_up", 2.0 * p.T * H * I, p.s, [&] {
-            launch_skinny_gemm(2, L.ffi.w, nullptr, v32, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), y, L.ffi_b.as<float>(), nullptr, ff, nullptr, tb, p.s);
+        timed("skinny_ffn_up", 2.0 * p.pass.n_tokens * H * I, p.pass.stream, [&] {
+            launch_skinny_gemm(2, L.ffi.w, nullptr, v32, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), y, L.ffi_b.as<float>(), nullptr, ff, nullptr, tb, p.pass.stream);
         });
-        timed("skinny_ffn_down", 2.0 * p.T * H * I, p.s, [&] {
-            launch_skinny_gemm(3, L.ffo.w, ff, nullptr, nullptr, nullptr, nullptr, L.ffo_b.as<float>(), y, nullptr, v32, tb, p.s);
+        timed("skinny_ffn_down", 2.0 * p.pass.n_tokens * H * I, p.pass.stream, [&] {
+            launch_skinny_gemm(3, L.ffo.w, ff, nullptr, nullptr, nullptr, nullptr, L.ffo_b.as<float>(), y, nullptr, v32, tb, p.pass.stream);
         });
         // (the last layer, or a hidden-state tap: somebody has to materialise x now; the next QKV kernel writes the same bits again)
-        if (il + 1 == Lz || p.hidden)
-            timed("skinny_layernorm", 0.0, p.s, [&] { launch_skinny_layernorm(v32, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), x, tb, H, p.s); });
+        if (il + 1 == Lz || p.pass.d_hidden)
+            timed("skinny_layernorm", 0.0, p.pass.stream, [&] { launch_skinny_layernorm(v32, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), x, tb, H, p.pass.stream); });
         tap(p, il + 1);
     }
 }
@@ -329,9 +328,9 @@ void Engine::forward_one_launch(const Plan &p) {
         mw[il] = {&L.qkv.w, &L.o.w, &L.ffi.w, &L.ffo.w, L.qkv_b.as<float>(), L.o_b.as<float>(), L.ln_att_w.as<float>(), L.ln_att_b.as<float>(),
                   L.ffi_b.as<float>(), L.ffo_b.as<float>(), L.ln_out_w.as<float>(), L.ln_out_b.as<float>()};
     }
-    timed("model_kernel", hp_.n_layer * (2.0 * p.T * 3 * H * H + 4.0 * p.T * p.max_len * H + 2.0 * p.T * H * H + 4.0 * p.T * H * I), p.s, [&] {
-        launch_model_kernel(mw, hp_.n_layer, x_.as<half_t>(), ctx_.as<half_t>(), y_.as<half_t>(), p.cu, p.B, p.T, p.windows, p.n_windows, p.n_windows_dev, hp_.n_head,
-                            p.out, p.max_len, status_.as<int>(), p.pool_mode, p.slots, p.s);
+    timed("model_kernel", hp_.n_layer * (2.0 * p.pass.n_tokens * 3 * H * H + 4.0 * p.pass.n_tokens * p.pass.max_len * H + 2.0 * p.pass.n_tokens * H * H + 4.0 * p.pass.n_tokens * H * I), p.pass.stream, [&] {
+        launch_model_kernel(mw, hp_.n_layer, x_.as<half_t>(), ctx_.as<half_t>(), y_.as<half_t>(), p.pass.d_cu, p.pass.n_sentences, p.pass.n_tokens, p.windows, p.n_windows, p.n_windows_dev, hp_.n_head,
+                            p.out, p.pass.max_len, status_.as<int>(), p.pool_mode, p.slots, p.pass.stream);
     });
 }
 
@@ -358,15 +357,15 @@ bool Engine::forward_folded(const Plan &p, std::string &err) {
         // u1 = ctx Wo^T + bo + (x | LayerNorm(u2 of the layer before)) -> y, with its rows' partial statistics
         ln = GemmLnFold(); ln.flags = GemmLnFold::STATS | (il ? GemmLnFold::RES : 0); ln.stats = st1; ln.rows_res = rows2; ln.gb = L.o_gb.as<unsigned>();
         if (!gemm(p, "gemm_attn_out", G, L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, err, &ln)) return false;
-        timed("ln_rows_finalize", 0.0, p.s, [&] { launch_ln_rows_finalize(st1, P, p.t_pad, H, rows1, p.s); });
+        timed("ln_rows_finalize", 0.0, p.pass.stream, [&] { launch_ln_rows_finalize(st1, P, p.t_pad, H, rows1, p.pass.stream); });
         ln = GemmLnFold(); ln.flags = GemmLnFold::IN; ln.rows_in = rows1; ln.waug = L.ffi_waug.as<half_t>();
         if (!gemm(p, "gemm_ffn_up", G, L.ffi_fold, y, nullptr, nullptr, ff, EPI_BIAS_GELU, err, &ln)) return false;
         // u2 = ff W2^T + b2 + LayerNorm(u1) -> x
         ln = GemmLnFold(); ln.flags = GemmLnFold::STATS | GemmLnFold::RES; ln.stats = st2; ln.rows_res = rows1; ln.gb = L.ffo_gb.as<unsigned>();
         if (!gemm(p, "gemm_ffn_down", G, L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID, err, &ln)) return false;
-        timed("ln_rows_finalize", 0.0, p.s, [&] { launch_ln_rows_finalize(st2, P, p.t_pad, H, rows2, p.s); });
+        timed("ln_rows_finalize", 0.0, p.pass.stream, [&] { launch_ln_rows_finalize(st2, P, p.t_pad, H, rows2, p.pass.stream); });
         if (il + 1 == hp_.n_layer)     // (the pooling reads normalised rows: the one LayerNorm launch of the pass)
-            timed("layernorm", 0.0, p.s, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.T, H, p.s); });
+            timed("layernorm", 0.0, p.pass.stream, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.pass.n_tokens, H, p.pass.stream); });
     }
     return true;
 }
@@ -380,8 +379,8 @@ bool Engine::forward_layers(const Plan &p, std::string &err) {
         const LayerPlan &lp = p.layers[il];
         if (lp.qkv2) {
             // windows of 128 token slots holding whole sentences: Q|K|V never reach HBM whatever the sentence lengths
-            timed("qkv_attention2", 2.0 * p.T * L.qkv.w.N * L.qkv.w.K + 4.0 * p.T * p.max_len * H, p.s, [&] {
-                launch_qkv_attention2(L.qkv.w, x, L.qkv_b.as<float>(), p.cu, p.B, p.windows, p.n_windows, p.n_windows_dev, p.max_len, hp_.n_head, p.slots, ctx, p.s);
+            timed("qkv_attention2", 2.0 * p.pass.n_tokens * L.qkv.w.N * L.qkv.w.K + 4.0 * p.pass.n_tokens * p.pass.max_len * H, p.pass.stream, [&] {
+                launch_qkv_attention2(L.qkv.w, x, L.qkv_b.as<float>(), p.pass.d_cu, p.pass.n_sentences, p.windows, p.n_windows, p.n_windows_dev, p.pass.max_len, hp_.n_head, p.slots, ctx, p.pass.stream);
             });
         } else {
             if (!gemm(p, "gemm_qkv", lp.qkv, lp.planes ? L.qkv_q4 : L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS, err)) return false;
@@ -389,16 +388,16 @@ bool Engine::forward_layers(const Plan &p, std::string &err) {
         }
         if (lp.tail) {
             // out-projection + LN + FFN + LN in one launch, a pair of specialist waves per 32 tokens: y and the intermediate never leave the chip
-            timed("layer_tail", 2.0 * p.T * H * H + 4.0 * p.T * H * I, p.s, [&] {
+            timed("layer_tail", 2.0 * p.pass.n_tokens * H * H + 4.0 * p.pass.n_tokens * H * I, p.pass.stream, [&] {
                 launch_layer_tail(L.o.w, L.ffi.w, L.ffo.w, ctx, x, L.o_b.as<float>(), L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), L.ffi_b.as<float>(),
-                                  L.ffo_b.as<float>(), L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), x, p.t_pad, p.s);
+                                  L.ffo_b.as<float>(), L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), x, p.t_pad, p.pass.stream);
             });
         } else {
             if (!gemm(p, "gemm_attn_out", lp.o, L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, err)) return false;
-            timed("layernorm", 0.0, p.s, [&] { launch_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), p.T, H, p.s); });
+            timed("layernorm", 0.0, p.pass.stream, [&] { launch_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), p.pass.n_tokens, H, p.pass.stream); });
             if (!gemm(p, "gemm_ffn_up", lp.ffi, L.ffi, y, L.ffi_b.as<float>(), nullptr, ff, EPI_BIAS_GELU, err) ||
                 !gemm(p, "gemm_ffn_down", lp.ffo, L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID, err)) return false;
-            timed("layernorm", 0.0, p.s, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.T, H, p.s); });
+            timed("layernorm", 0.0, p.pass.stream, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.pass.n_tokens, H, p.pass.stream); });
         }
         tap(p, il + 1);
     }
@@ -411,175 +410,31 @@ bool Engine::forward_f32(const Plan &p, std::string &err) {
     const int H = hp_.n_embd, nh = hp_.n_head, dh = H / nh;
     const Family F = Family::F32;
     float *x = x_.as<float>(), *qkv = qkv_.as<float>(), *ctx = ctx_.as<float>(), *y = y_.as<float>(), *ff = ff_.as<float>();
-    timed("embed_ln", 0.0, p.s, [&] {
-        launch_f32_embed_ln(w_->word_emb.as<float>(), w_->type_emb.as<float>(), w_->pos_emb.as<float>(), w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(), p.tokens,
-                            p.cu, p.B, p.T, H, hp_.n_vocab, p.max_len, x, p.s, p.first_len);
+    timed("embed_ln", 0.0, p.pass.stream, [&] {
+        launch_f32_embed_ln(w_->word_emb.as<float>(), w_->type_emb.as<float>(), w_->pos_emb.as<float>(), w_->ln_e_w.as<float>(), w_->ln_e_b.as<float>(), p.pass.d_tokens,
+                            p.pass.d_cu, p.pass.n_sentences, p.pass.n_tokens, H, hp_.n_vocab, p.pass.max_len, x, p.pass.stream, p.pass.d_first_len);
     });
     tap(p, 0);
     for (int il = 0; il < hp_.n_layer; ++il) {
         const LayerWeights &L = w_->layers[il];
         if (!gemm(p, "gemm_qkv", F, L.qkv, x, L.qkv_b.as<float>(), nullptr, qkv, EPI_BIAS, err)) return false;
         bool launched = true;
-        timed("attention", 4.0 * p.T * p.max_len * H, p.s, [&] { launched = launch_f32_attention(qkv, p.cu, p.B, nh, dh, p.max_len, ctx, p.s, w_->rel.as<float>(), hp_.n_max_tokens); });
+        timed("attention", 4.0 * p.pass.n_tokens * p.pass.max_len * H, p.pass.stream, [&] { launched = launch_f32_attention(qkv, p.pass.d_cu, p.pass.n_sentences, nh, dh, p.pass.max_len, ctx, p.pass.stream, w_->rel.as<float>(), hp_.n_max_tokens); });
         if (!launched) {
-            err = "f32 route: the attention kernel keeps the scores of max_len = " + std::to_string(p.max_len) + " keys per wave in LDS, " +
-                  std::to_string(f32_attention_lds_bytes(p.max_len)) + " bytes a workgroup; this device's limit is " +
+            err = "f32 route: the attention kernel keeps the scores of max_len = " + std::to_string(p.pass.max_len) + " keys per wave in LDS, " +
+                  std::to_string(f32_attention_lds_bytes(p.pass.max_len)) + " bytes a workgroup; this device's limit is " +
                   std::to_string(f32_attention_lds_limit()) + " bytes (set_option \"f32\" = \"f16\" selects the f16 kernels)";
             return false;
         }
         if (!gemm(p, "gemm_attn_out", F, L.o, ctx, L.o_b.as<float>(), x, y, EPI_BIAS_RESID, err)) return false;
-        timed("layernorm", 0.0, p.s, [&] { launch_f32_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), p.T, H, p.s); });
+        timed("layernorm", 0.0, p.pass.stream, [&] { launch_f32_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), p.pass.n_tokens, H, p.pass.stream); });
         if (!gemm(p, "gemm_ffn_up", F, L.ffi, y, L.ffi_b.as<float>(), nullptr, ff, EPI_BIAS_GELU, err) ||
             !gemm(p, "gemm_ffn_down", F, L.ffo, ff, L.ffo_b.as<float>(), y, x, EPI_BIAS_RESID, err)) return false;
-        timed("layernorm", 0.0, p.s, [&] { launch_f32_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.T, H, p.s); });
+        timed("layernorm", 0.0, p.pass.stream, [&] { launch_f32_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.pass.n_tokens, H, p.pass.stream); });
         tap(p, il + 1);
     }
-    timed("pool_normalize", 2.0 * p.T * H, p.s, [&] { launch_f32_pool_normalize(x, p.cu, p.B, H, p.max_len, status_.as<int>(), p.out, p.pool_mode, p.s); });
+    timed("pool_normalize", 2.0 * p.pass.n_tokens * H, p.pass.stream, [&] { launch_f32_pool_normalize(x, p.pass.d_cu, p.pass.n_sentences, H, p.pass.max_len, status_.as<int>(), p.out, p.pool_mode, p.pass.stream); });
     return true;
-}
-
-static bool ensure_pinned(void **p, size_t *cap, size_t need, std::string &err) {
-    if (need <= *cap) return true;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr; *cap = 0;
-    need += need / 4;
-    HIP_OK(hipHostMalloc(p, need, hipHostMallocDefault), err, false);
-    *cap = need;
-    return true;
-}
-
-// The rows of a call's LAST chunk leave the pinned block with nothing to hide the copy behind (earlier chunks are copied out under
-// the next one's forward pass): a large block goes out on four threads (one core moves ~10 GB/s: 0.9 ms for the 9 MB of 6000
-// MiniLM rows).  A thread that cannot be started is not an error: the caller copies its part.
-static void copy_rows_out(float *dst, const float *src, size_t bytes) {
-    constexpr size_t PART_MIN = (size_t)1 << 20;
-    constexpr int MAX_PARTS = 4;
-    const int parts = (int)std::min<size_t>(MAX_PARTS, bytes / PART_MIN);
-    if (parts <= 1) { memcpy(dst, src, bytes); return; }
-    const size_t each = (bytes / parts + 4095) & ~(size_t)4095;
-    std::thread helpers[MAX_PARTS - 1];
-    size_t inline_from = each;                         // [0, each) is the caller's; [inline_from, bytes) too when a start fails
-    for (int k = 1; k < parts; ++k) {
-        const size_t off = (size_t)k * each, n = std::min(each, bytes - std::min(bytes, off));
-        if (n == 0) break;
-        try {
-            helpers[k - 1] = std::thread([=] { memcpy((char *)dst + off, (const char *)src + off, n); });
-            inline_from = off + n;
-        } catch (const std::system_error &) {
-            break;
-        }
-    }
-    memcpy(dst, src, std::min(each, bytes));
-    if (inline_from < bytes) memcpy((char *)dst + inline_from, (const char *)src + inline_from, bytes - inline_from);
-    for (auto &h : helpers)
-        if (h.joinable()) h.join();
-}
-
-int Engine::eval_packed_host(const int32_t *tokens, const int32_t *cu, int B, float *embeddings, std::string &err,
-                             float *d_embeddings, int pool_mode_in) {
-    if (B <= 0) return 0;
-#ifdef BERT_HIP_HOST_TRACE
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_call = now();
-    double t_mark = t_call;
-    auto lap = [&](const char *what, size_t i) { const double t = now(); fprintf(stderr, "[host] chunk %zu %-10s %.3f ms\n", i, what, t - t_mark); t_mark = t; };
-#define HOST_LAP(what, i) lap(what, i)
-#else
-#define HOST_LAP(what, i) do { } while (0)
-#endif
-    HIP_OK(hipSetDevice(device_), err, -1);
-    const int H = hp_.n_embd;
-    // chunks [b0, b1): at most opt_.chunk_tokens tokens, at least one sentence
-    struct Chunk { int b0, b1, max_len; };
-    std::vector<Chunk> chunks;
-    size_t max_T = 0, max_nb = 0;
-    for (int b0 = 0; b0 < B;) {
-        int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
-        while (b1 < B && cu[b1 + 1] - cu[b0] <= opt_.chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
-        chunks.push_back({b0, b1, max_len});
-        max_T = std::max(max_T, (size_t)(cu[b1] - cu[b0]));
-        max_nb = std::max(max_nb, (size_t)(b1 - b0));
-        b0 = b1;
-    }
-    // every buffer is sized for the largest chunk BEFORE anything is queued: growing one later would free memory that
-    // a queued chunk still uses
-    const int n_slots = chunks.size() > 1 ? 2 : 1;
-    auto pad16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
-    const size_t in_bytes = pad16(max_T * 4) + pad16((max_nb + 1) * 4) + pad16(max_nb * sizeof(int2));
-    for (int i = 0; i < n_slots; ++i) {
-        HostSlot &sl = slot_[i];
-        const size_t in_cap = sl.h_in_cap;
-        // (16 spare bytes: the staging kernel copies whole 16-byte units)
-        if (!ensure_pinned((void **)&sl.h_in, &sl.h_in_cap, in_bytes + 16, err)) return -1;
-        if (sl.h_in_cap != in_cap || !sl.d_in_host) HIP_OK(hipHostGetDevicePointer((void **)&sl.d_in_host, sl.h_in, 0), err, -1);
-        const size_t out_cap = sl.h_out_cap;
-        if (!ensure_pinned((void **)&sl.h_out, &sl.h_out_cap, max_nb * H * 4, err)) return -1;
-        if (sl.h_out_cap != out_cap || !sl.d_out_host)
-            HIP_OK(hipHostGetDevicePointer((void **)&sl.d_out_host, sl.h_out, 0), err, -1);
-        if (!sl.d_in.ensure(in_bytes + 16, err) || (d_embeddings && !sl.d_out.ensure(max_nb * H * 4, err))) return -1;
-        if (!sl.done) HIP_OK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), err, -1);
-    }
-    if (!ensure_workspace((int)((max_T + 255) / 256 * 256), (int)max_nb, err)) return -1;
-    HOST_LAP("prepared", (size_t)0);
-
-    // The stream executes H2D, forward, D2H of chunk after chunk; the host runs one chunk ahead: it stages chunk i
-    // into slot i & 1 and queues it, then unpacks chunk i-1 while chunk i computes.
-    auto unpack = [&](size_t i) -> bool {
-        HostSlot &sl = slot_[i & 1];
-        if (hipEventSynchronize(sl.done) != hipSuccess) { err = "hipEventSynchronize failed"; return false; }
-        HOST_LAP("wait", i);
-        if (!d_embeddings) {
-            const size_t bytes = (size_t)(chunks[i].b1 - chunks[i].b0) * H * 4;
-            if (i + 1 == chunks.size()) copy_rows_out(embeddings + (size_t)chunks[i].b0 * H, sl.h_out, bytes);
-            else memcpy(embeddings + (size_t)chunks[i].b0 * H, sl.h_out, bytes);
-        }
-        HOST_LAP("copy-out", i);
-        return true;
-    };
-    auto fail = [&]() { (void)hipStreamSynchronize(stream_); return -1; };        // nothing may stay queued on the slots
-    std::vector<int2> windows;
-    const int slots = window_slots();                         // (once per call: the lists below and the kernels that place by them)
-    const int pool_mode = pool_mode_in >= 0 ? pool_mode_in : opt_.pool_mode();      // (once per call as well: every chunk ends by the same rule)
-    for (size_t i = 0; i < chunks.size(); ++i) {
-        HostSlot &sl = slot_[i & 1];
-        const int b0 = chunks[i].b0, nb = chunks[i].b1 - b0, T = cu[chunks[i].b1] - cu[b0];
-        const size_t off_cu = pad16((size_t)T * 4), off_w = off_cu + pad16((size_t)(nb + 1) * 4);
-        int32_t *h_cu = (int32_t *)(sl.h_in + off_cu);
-        memcpy(sl.h_in, tokens + cu[b0], (size_t)T * 4);
-        for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
-        int n_windows = 0;
-        if (chunks[i].max_len <= 128) {
-            build_windows(h_cu, nb, windows, slots);
-            n_windows = (int)windows.size();
-            memcpy(sl.h_in + off_w, windows.data(), windows.size() * sizeof(int2));
-        }
-        const size_t staged = off_w + (size_t)n_windows * sizeof(int2);
-        HOST_LAP("staged", i);
-        if (opt_.stage_kernel && staged <= ((size_t)256 << 10)) {
-            // (a small block — measured up to the 130 KB of a 256 x 128 batch: a few workgroups read it across the host link, the copy
-            // engine's start-up is ~20 us of a 0.8 ms call; full 1 MiB chunks stay with the copy engine, off the compute stream)
-            launch_stage_copy(sl.d_in_host, sl.d_in.p, staged, stream_);
-        } else if (hipMemcpyAsync(sl.d_in.p, sl.h_in, staged, hipMemcpyHostToDevice, stream_) != hipSuccess) {
-            err = "hipMemcpyAsync (ids) failed";
-            return fail();
-        }
-        const char *d_in = (const char *)sl.d_in.p;
-        // host destination: the pooling kernel's rows go straight into the pinned block (no D2H copy behind the pass)
-        float *out = d_embeddings ? sl.d_out.as<float>() : sl.d_out_host;
-        if (eval_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, chunks[i].max_len, out, stream_, nullptr, err,
-                               n_windows ? (const int2 *)(d_in + off_w) : nullptr, n_windows, slots, pool_mode) != 0)
-            return fail();
-        if ((d_embeddings && hipMemcpyAsync(d_embeddings + (size_t)b0 * H, sl.d_out.p, (size_t)nb * H * 4, hipMemcpyDeviceToDevice, stream_) != hipSuccess) ||
-            hipEventRecord(sl.done, stream_) != hipSuccess) {
-            err = "hipMemcpyAsync (embeddings) failed";
-            return fail();
-        }
-        HOST_LAP("queued", i);
-        if (i >= 1 && !unpack(i - 1)) return fail();           // while chunk i computes; frees the slot chunk i+1 stages into
-    }
-    if (!unpack(chunks.size() - 1)) return fail();
-#undef HOST_LAP
-    return 0;
 }
 
 int Engine::group_pool(const int32_t *d_cu, int B, const int32_t *d_group_cu, int n_groups, float *d_out, int pool_mode, const StreamOp &op, std::string &err) {
@@ -603,70 +458,12 @@ int Engine::eval_packed_grouped_device(const int32_t *d_tokens, const int32_t *d
     StreamOp op;
     if (!op_begin(s, busy_, op, err)) return -1;
     if (!raw_rows_.ensure((size_t)B * hp_.n_embd * 4, err)) return -1;
-    if (eval_packed_device(d_tokens, d_cu, B, T, max_len, raw_rows_.as<float>(), s, nullptr, err, nullptr, 0, 0, pool_mode | POOL_RAW) != 0) return -1;
+    Pass pass;
+    pass.d_tokens = d_tokens; pass.d_cu = d_cu; pass.n_sentences = B; pass.n_tokens = T; pass.max_len = max_len; pass.stream = s;
+    pass.d_out = raw_rows_.as<float>();
+    pass.pool_mode = pool_mode | POOL_RAW;
+    if (eval_packed_device(pass, err) != 0) return -1;
     return group_pool(d_cu, B, d_group_cu, n_groups, d_out, pool_mode, op, err);
-}
-
-int Engine::eval_packed_grouped_host(const int32_t *tokens, const int32_t *cu, int B, const int32_t *group_cu, int n_groups, float *embeddings,
-                                     float *d_embeddings, std::string &err, const float *h_raw_rows, int pool_mode_in) {
-    if (B <= 0 || n_groups <= 0) return 0;
-    const int pool_mode = pool_mode_in >= 0 ? pool_mode_in : opt_.pool_mode();
-    const size_t H = hp_.n_embd;
-    HIP_OK(hipSetDevice(device_), err, -1);
-    // cu_seqlens (from 0, whatever window of the caller's prefix sums this is) | group_cu, one upload
-    const size_t n_in = (size_t)B + 1 + n_groups + 1;
-    if (!raw_rows_.ensure((size_t)B * H * 4, err) || !group_in_.ensure(n_in * 4, err) || (!d_embeddings && !group_out_.ensure((size_t)n_groups * H * 4, err))) return -1;
-    std::vector<int32_t> in(n_in);
-    for (int b = 0; b <= B; ++b) in[b] = cu[b] - cu[0];
-    std::copy(group_cu, group_cu + n_groups + 1, in.begin() + B + 1);
-    auto fail = [&](const char *what) { if (what) err = what; (void)hipStreamSynchronize(stream_); return -1; };      // nothing may stay queued on the caller's memory
-    if (h_raw_rows) {
-        // (a device-form call's pooling may still read raw_rows_ on another stream)
-        if (hipStreamWaitEvent(stream_, busy_, 0) != hipSuccess || hipMemcpyAsync(raw_rows_.p, h_raw_rows, (size_t)B * H * 4, hipMemcpyHostToDevice, stream_) != hipSuccess)
-            return fail("hipMemcpyAsync (raw rows) failed");
-    } else if (eval_packed_host(tokens, cu, B, nullptr, err, raw_rows_.as<float>(), pool_mode | POOL_RAW) != 0) {
-        // (blocking, chunk by chunk: the rows are in raw_rows_ when it returns; they never leave the device)
-        return -1;
-    }
-    if (hipMemcpyAsync(group_in_.p, in.data(), n_in * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) return fail("hipMemcpyAsync (groups) failed");
-    float *d_out = d_embeddings ? d_embeddings : group_out_.as<float>();
-    if (group_pool(group_in_.as<int32_t>(), B, group_in_.as<int32_t>() + B + 1, n_groups, d_out, pool_mode, StreamOp{stream_, busy_, false}, err) != 0) return fail(nullptr);
-    if (!d_embeddings && hipMemcpyAsync(embeddings, d_out, (size_t)n_groups * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess)
-        return fail("hipMemcpyAsync (embeddings) failed");
-    HIP_OK(hipStreamSynchronize(stream_), err, -1);
-    return 0;
-}
-
-int Engine::eval_packed_tokens_host(const int32_t *tokens, const int32_t *cu, int B, int flags, float *rows, float *embeddings, std::string &err) {
-    if (B <= 0) return 0;
-    HIP_OK(hipSetDevice(device_), err, -1);
-    const size_t H = hp_.n_embd;
-    auto fail = [&](const char *what) { if (what) err = what; (void)hipStreamSynchronize(stream_); return -1; };      // nothing may stay queued on the caller's memory
-    // chunks [b0, b1) by eval_packed_host's rule: at most chunk_tokens tokens, at least one sentence
-    std::vector<int32_t> h_cu;
-    for (int b0 = 0; b0 < B;) {
-        int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
-        while (b1 < B && cu[b1 + 1] - cu[b0] <= opt_.chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
-        const int nb = b1 - b0, T = cu[b1] - cu[b0];
-        const size_t off_cu = ((size_t)T * 4 + 15) & ~(size_t)15;
-        if (!tok_in_.ensure(off_cu + (size_t)(nb + 1) * 4, err) || !tok_rows_.ensure((size_t)T * H * 4, err) || !ensure_workspace((T + 255) / 256 * 256, nb, err)) return fail(nullptr);
-        h_cu.resize(nb + 1);
-        for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
-        char *d_in = tok_in_.as<char>();
-        // (pageable sources: both copies have left the host buffers when they return)
-        if (hipMemcpyAsync(d_in, tokens + cu[b0], (size_t)T * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-            hipMemcpyAsync(d_in + off_cu, h_cu.data(), (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, stream_) != hipSuccess)
-            return fail("hipMemcpyAsync (ids) failed");
-        if (eval_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, nullptr, stream_, nullptr, err, nullptr, 0, 0, -1,
-                               tok_rows_.p, flags & TOKEN_ROWS_NORMALIZE) != 0)
-            return fail(nullptr);
-        if (hipMemcpyAsync(rows + (size_t)cu[b0] * H, tok_rows_.p, (size_t)T * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess ||
-            (embeddings && hipMemcpyAsync(embeddings + (size_t)b0 * H, d_out_.p, (size_t)nb * H * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess))
-            return fail("hipMemcpyAsync (rows) failed");
-        HIP_OK(hipStreamSynchronize(stream_), err, -1);
-        b0 = b1;
-    }
-    return 0;
 }
 
 int Engine::score_packed_device(const int32_t *d_tokens, const int32_t *d_cu, const int32_t *d_first_len, int B, int T, int max_len, int flags,
@@ -678,7 +475,12 @@ int Engine::score_packed_device(const int32_t *d_tokens, const int32_t *d_cu, co
     StreamOp op;
     if (!op_begin(s, busy_, op, err)) return -1;
     // the un-normalised [CLS] rows, in the engine's own d_out_ (ensure_workspace sizes it for the pass)
-    if (eval_packed_device(d_tokens, d_cu, B, T, max_len, nullptr, s, nullptr, err, d_windows, n_windows, slots, POOL_CLS | POOL_RAW, nullptr, 0, d_first_len) != 0) return -1;
+    Pass pass;
+    pass.d_tokens = d_tokens; pass.d_cu = d_cu; pass.n_sentences = B; pass.n_tokens = T; pass.max_len = max_len; pass.stream = s;
+    pass.d_windows = d_windows; pass.n_windows = n_windows; pass.window_slots = slots;
+    pass.pool_mode = POOL_CLS | POOL_RAW;
+    pass.d_first_len = d_first_len;
+    if (eval_packed_device(pass, err) != 0) return -1;
     const int H = hp_.n_embd;
     const bool f32_route = w_->f32_file && opt_.f32_exact;
     const ClsHeadArgs a{d_out_.as<float>(), w_->head_wp16.as<half_t>(), f32_route ? w_->head_wp32.as<float>() : nullptr, w_->head_bp.as<float>(),
@@ -690,54 +492,6 @@ int Engine::score_packed_device(const int32_t *d_tokens, const int32_t *d_cu, co
     if (!ok) { err = "cls_head: no kernel for n_embd = " + std::to_string(H); return -1; }
     HIP_OK(hipGetLastError(), err, -1);
     return op_end(op, err) ? 0 : -1;
-}
-
-int Engine::eval_packed_typed_host(const int32_t *tokens, const int32_t *cu, const int32_t *first_len, int B, bool scores, int flags, float *out,
-                                   std::string &err) {
-    if (scores && w_->n_labels <= 0) { err = "the model file has no classification head (pooler.dense.*, classifier.*)"; return -2; }
-    if (B <= 0) return 0;
-    HIP_OK(hipSetDevice(device_), err, -1);
-    const size_t W = scores ? (size_t)w_->n_labels : (size_t)hp_.n_embd;      // floats per sentence that leave
-    auto fail = [&](const char *what) { if (what) err = what; (void)hipStreamSynchronize(stream_); return -1; };      // nothing may stay queued on the caller's memory
-    auto pad16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
-    // chunks [b0, b1) by eval_packed_host's rule: at most chunk_tokens tokens, at least one sentence
-    std::vector<char> h_in;
-    std::vector<int2> windows;
-    const int slots = window_slots(), pool_mode = opt_.pool_mode();       // (once per call, as eval_packed_host reads them)
-    for (int b0 = 0; b0 < B;) {
-        int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
-        while (b1 < B && cu[b1 + 1] - cu[b0] <= opt_.chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
-        const int nb = b1 - b0, T = cu[b1] - cu[b0];
-        // (the windows of eval_packed_host, so that a typed call plans as the untyped one does)
-        const size_t off_cu = pad16((size_t)T * 4), off_fl = off_cu + pad16((size_t)(nb + 1) * 4), off_w = off_fl + pad16((size_t)nb * 4),
-                     in_bytes = off_w + (size_t)nb * sizeof(int2);
-        if (!typed_in_.ensure(in_bytes, err) || !typed_out_.ensure((size_t)nb * W * 4, err) || !ensure_workspace((T + 255) / 256 * 256, nb, err)) return fail(nullptr);
-        h_in.assign(in_bytes, 0);
-        memcpy(h_in.data(), tokens + cu[b0], (size_t)T * 4);
-        int32_t *h_cu = (int32_t *)(h_in.data() + off_cu);
-        for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
-        if (first_len) memcpy(h_in.data() + off_fl, first_len + b0, (size_t)nb * 4);
-        int n_windows = 0;
-        if (max_len <= 128) {
-            build_windows(h_cu, nb, windows, slots);
-            n_windows = (int)windows.size();
-            memcpy(h_in.data() + off_w, windows.data(), windows.size() * sizeof(int2));
-        }
-        const int2 *d_w = n_windows ? (const int2 *)(typed_in_.as<char>() + off_w) : nullptr;
-        const char *d_in = typed_in_.as<char>();
-        // (a pageable source: the copy has left the host buffer when it returns)
-        if (hipMemcpyAsync(typed_in_.p, h_in.data(), in_bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) return fail("hipMemcpyAsync (ids) failed");
-        const int32_t *d_fl = first_len ? (const int32_t *)(d_in + off_fl) : nullptr;
-        const int r = scores ? score_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), d_fl, nb, T, max_len, flags, typed_out_.as<float>(), stream_, err,
-                                                   d_w, n_windows, slots)
-                             : eval_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, typed_out_.as<float>(), stream_, nullptr, err,
-                                                  d_w, n_windows, slots, pool_mode, nullptr, 0, d_fl);
-        if (r != 0) return fail(nullptr);
-        if (hipMemcpyAsync(out + (size_t)b0 * W, typed_out_.p, (size_t)nb * W * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess) return fail("hipMemcpyAsync (results) failed");
-        HIP_OK(hipStreamSynchronize(stream_), err, -1);
-        b0 = b1;
-    }
-    return 0;
 }
 
 bool Engine::ensure_sparse(int B, std::string &err) {
@@ -756,7 +510,10 @@ int Engine::sparse_packed_device(const int32_t *d_tokens, const int32_t *d_cu, i
     const int t_pad = (T + 255) / 256 * 256, H = hp_.n_embd, V = hp_.n_vocab;
     if (!ensure_workspace(t_pad, B, err) || (k > 0 && !ensure_sparse(B, err))) return -1;
     // the final states, left in x_ (its address is settled: the pass's own ensure_workspace asks for the same sizes)
-    if (eval_packed_device(d_tokens, d_cu, B, T, max_len, nullptr, s, nullptr, err, nullptr, 0, 0, -1, x_.p, 0) != 0) return -1;
+    Pass pass;
+    pass.d_tokens = d_tokens; pass.d_cu = d_cu; pass.n_sentences = B; pass.n_tokens = T; pass.max_len = max_len; pass.stream = s;
+    pass.d_token_rows = x_.p;
+    if (eval_packed_device(pass, err) != 0) return -1;
     const bool f32_route = w_->f32_file && opt_.f32_exact;
     const GemmWeightStore &Wt = w_->mlm_wt;
     if (f32_route) {
@@ -794,57 +551,6 @@ int Engine::sparse_packed_device(const int32_t *d_tokens, const int32_t *d_cu, i
     }
     HIP_OK(hipGetLastError(), err, -1);
     return op_end(op, err) ? 0 : -1;
-}
-
-int Engine::sparse_packed_host(const int32_t *tokens, const int32_t *cu, int B, int k, int32_t *ids, float *weights, std::string &err) {
-    if (!w_->mlm_head) { err = "the model file has no MLM head (cls.predictions.*)"; return -2; }
-    if (B <= 0) return 0;
-    HIP_OK(hipSetDevice(device_), err, -1);
-    const size_t V = hp_.n_vocab, W = k > 0 ? (size_t)k : V;       // results per sentence (top-k: as many ids, then as many weights)
-    const int cap = k > 0 ? std::max(1, (int)(((size_t)32 << 20) / (W * 8))) : sparse_sentence_cap();
-    auto fail = [&](const char *what) { if (what) err = what; (void)hipStreamSynchronize(stream_); return -1; };      // nothing may stay queued on the caller's memory
-    std::vector<int32_t> h_cu;
-    for (int b0 = 0; b0 < B;) {
-        int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
-        while (b1 < B && b1 - b0 < cap && cu[b1 + 1] - cu[b0] <= opt_.chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
-        const int nb = b1 - b0, T = cu[b1] - cu[b0];
-        const size_t off_cu = ((size_t)T * 4 + 15) & ~(size_t)15, off_w = k > 0 ? ((size_t)nb * W * 4 + 15) & ~(size_t)15 : 0;
-        if (!sparse_in_.ensure(off_cu + (size_t)(nb + 1) * 4, err) || !sparse_out_.ensure(off_w + (size_t)nb * W * 4, err)) return fail(nullptr);
-        h_cu.resize(nb + 1);
-        for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
-        char *d_in = sparse_in_.as<char>(), *d_res = sparse_out_.as<char>();
-        // (pageable sources: both copies have left the host buffers when they return)
-        if (hipMemcpyAsync(d_in, tokens + cu[b0], (size_t)T * 4, hipMemcpyHostToDevice, stream_) != hipSuccess ||
-            hipMemcpyAsync(d_in + off_cu, h_cu.data(), (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, stream_) != hipSuccess)
-            return fail("hipMemcpyAsync (ids) failed");
-        if (sparse_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, k, (int32_t *)d_res, (float *)(d_res + off_w), stream_, err) != 0)
-            return fail(nullptr);
-        if ((k > 0 && hipMemcpyAsync(ids + (size_t)b0 * W, d_res, (size_t)nb * W * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess) ||
-            hipMemcpyAsync(weights + (size_t)b0 * W, d_res + off_w, (size_t)nb * W * 4, hipMemcpyDeviceToHost, stream_) != hipSuccess)
-            return fail("hipMemcpyAsync (results) failed");
-        HIP_OK(hipStreamSynchronize(stream_), err, -1);
-        b0 = b1;
-    }
-    return 0;
-}
-
-int Engine::eval_hidden(const int32_t *tokens, int N, float *hidden, float *embedding, std::string &err) {
-    HIP_OK(hipSetDevice(device_), err, -1);
-    const int H = hp_.n_embd, L = hp_.n_layer;
-    int32_t cu[2] = {0, N};
-    if (!d_tokens_.ensure((size_t)N * 4, err) || !d_cu_.ensure(8, err)) return -1;
-    if (!d_hidden_.ensure((size_t)(L + 1) * N * H * 4, err)) return -1;
-    const int t_pad = (N + 255) / 256 * 256;
-    if (!ensure_workspace(t_pad, 1, err)) return -1;
-    HIP_OK(hipMemcpy(d_tokens_.p, tokens, (size_t)N * 4, hipMemcpyHostToDevice), err, -1);
-    HIP_OK(hipMemcpy(d_cu_.p, cu, 8, hipMemcpyHostToDevice), err, -1);
-    if (eval_packed_device(d_tokens_.as<int32_t>(), d_cu_.as<int32_t>(), 1, N, N, d_out_.as<float>(), stream_,
-                           d_hidden_.as<float>(), err) != 0)
-        return -1;
-    HIP_OK(hipStreamSynchronize(stream_), err, -1);
-    if (hidden) HIP_OK(hipMemcpy(hidden, d_hidden_.p, (size_t)(L + 1) * N * H * 4, hipMemcpyDeviceToHost), err, -1);
-    if (embedding) HIP_OK(hipMemcpy(embedding, d_out_.p, (size_t)H * 4, hipMemcpyDeviceToHost), err, -1);
-    return 0;
 }
 
 }  // namespace bert_hip

@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "context.h"
+#include "host_chunks.h"
 #include "index_file.h"
 #include "sparse_index_file.h"
 #include "partition.h"
@@ -768,6 +769,16 @@ int32_t bert_hip_test_parse_devices(const char *list, int32_t n_devices, int32_t
     }
     for (size_t i = 0; i < d.size(); ++i) devs[i] = d[i];
     return (int32_t)d.size();
+}
+
+int32_t bert_hip_test_host_chunks(const int32_t *cu_seqlens, int32_t n_sentences, int32_t chunk_tokens, int32_t max_sentences, int32_t *out) {
+    int32_t n = 0;
+    for (int b0 = 0; b0 < n_sentences; ++n) {
+        const HostChunk c = next_host_chunk(cu_seqlens, n_sentences, b0, chunk_tokens, max_sentences);
+        out[3 * n] = c.b0; out[3 * n + 1] = c.b1; out[3 * n + 2] = c.max_len;
+        b0 = c.b1;
+    }
+    return n;
 }
 
 int32_t bert_hip_test_gather_runs(const int32_t *cu_seqlens, int32_t n_sentences, int64_t tokens_per_run, int32_t *runs) {

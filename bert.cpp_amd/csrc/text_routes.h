@@ -1,6 +1,6 @@
 // text_routes.h — how the text entry points of the two indexes (index_api.cpp, sparse_index_api.cpp) and of the hybrid search
 // (hybrid_api.cpp) get from texts to device buffers: the embeddings of a group of texts into the embedding index's scratch buffer,
-// the MLM head's largest terms of a chunk of texts into the sparse index's text buffers.
+// the chunks of a list of texts into an index's text buffers (text_chunks), for the sparse index the MLM head's largest terms of each.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "abi.h"
+#include "host_chunks.h"
 
 namespace bert_hip {
 
@@ -48,47 +49,60 @@ inline bool text_model_ok(const bert_ctx *ctx, const SparseIndex &x, std::string
     return true;
 }
 
-// Tokenizes the texts in groups of 4096, cuts each group at chunk_tokens between sentences and at the sentences whose terms fit
-// 32 MiB, and per chunk: ids | cu_seqlens into the index's device buffer, the MLM head's k largest terms of every text into its other
-// one (ids [nb][k] | weights [nb][k]), then use(i0, nb, d_ids, d_weights) — all on the index's stream.  0, -2 or -3 (+ err).
-template <class F>
-int32_t sparse_text_chunks(bert_ctx *ctx, SparseIndex &x, int32_t n_threads, int32_t n, const char **texts, int32_t k, F &&use, std::string &err) {
+// The way from texts to chunks in an index's device buffers, for the sparse index (below) and the token index (token_index_api.cpp).
+// Tokenizes the texts in groups of 4096, hands every group to pre(i0, m, cu) — nonzero: returned at once —, cuts it by the chunk rule
+// (host_chunks.h; max_sentences: its cap, 0 for none), and per chunk of nb sentences and T tokens: the staging block (ids | cu_seqlens)
+// into the index's device buffer by one copy, out_bytes(nb, T) bytes of room in its other one, then
+// use(i0, nb, T, max_len, h_cu, d_ids, d_cu, d_out) — i0: the chunk's first text; h_cu: the chunk's cu_seqlens from 0, host; d_ids / d_cu:
+// the same on the device — all on the index's stream, which is synchronised behind every chunk.  0, or what pre or use returned, or
+// -2 / -3 (+ err).
+template <class Ix, class Pre, class OutBytes, class F>
+int32_t text_chunks(bert_ctx *ctx, Ix &x, int32_t n_threads, int32_t n, const char **texts, int max_sentences, Pre &&pre, OutBytes &&out_bytes, F &&use,
+                    std::string &err) {
     constexpr int32_t GROUP = 4096;
-    Engine *eng = ctx->engine();
     TokenGroup &g = ctx->texts.group[0];
-    const int cap = std::max(1, (int)(((size_t)32 << 20) / ((size_t)k * 8)));
-    std::vector<int32_t> h_cu;
+    std::vector<char> block;
     for (int32_t i0 = 0; i0 < n; i0 += GROUP) {
         const int32_t m = std::min(GROUP, n - i0);
         g.tokenize(ctx->texts, n_threads, m, texts + i0);
         if (g.n_ok < m) { err = "input " + std::to_string(i0 + g.n_ok) + " cannot be evaluated"; return -2; }
         const int32_t *cu = g.cu.data();
+        if (const int32_t r = pre(i0, m, cu)) return r;
         for (int b0 = 0; b0 < m;) {
-            int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
-            while (b1 < m && b1 - b0 < cap && cu[b1 + 1] - cu[b0] <= eng->options().chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
-            const int nb = b1 - b0, T = cu[b1] - cu[b0];
-            const size_t off_cu = ((size_t)T * 4 + 15) & ~(size_t)15, off_w = ((size_t)nb * k * 4 + 15) & ~(size_t)15;
+            const HostChunk c = next_host_chunk(cu, m, b0, ctx->engine()->options().chunk_tokens, max_sentences);
+            const int nb = c.b1 - b0, T = cu[c.b1] - cu[b0];
+            const StagingLayout L(T, nb, false, 0);
             char *d_in = nullptr, *d_out = nullptr;
-            if (!x.text_buffers(off_cu + (size_t)(nb + 1) * 4, off_w + (size_t)nb * k * 4, d_in, d_out, err)) return -3;
-            h_cu.resize(nb + 1);
-            for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
+            if (!x.text_buffers(L.bytes, out_bytes(nb, T), d_in, d_out, err)) return -3;
+            block.resize(std::max(block.size(), L.bytes));
+            const int32_t *h_cu = fill_staging(block.data(), L, g.packed.get(), cu, c, nullptr, nullptr, 0);
             hipStream_t s = x.stream();
-            // (pageable sources: both copies have left the host buffers when they return)
-            if (hipMemcpyAsync(d_in, g.packed.get() + cu[b0], (size_t)T * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(d_in + off_cu, h_cu.data(), (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
+            // (a pageable source: the copy has left the block when it returns)
+            if (hipMemcpyAsync(d_in, block.data(), L.bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
                 (void)hipStreamSynchronize(s);
                 err = "hipMemcpyAsync (ids) failed";
                 return -3;
             }
-            int32_t r = eng->sparse_packed_device((const int32_t *)d_in, (const int32_t *)(d_in + off_cu), nb, T, max_len, k, (int32_t *)d_out,
-                                                  (float *)(d_out + off_w), s, err) != 0 ? -3 : 0;
-            if (r == 0) r = use(i0 + b0, nb, (const int32_t *)d_out, (const float *)(d_out + off_w));
+            int32_t r = use(i0 + b0, nb, T, c.max_len, h_cu, (const int32_t *)d_in, (const int32_t *)(d_in + L.off_cu), d_out);
             if (hipStreamSynchronize(s) != hipSuccess && r == 0) { err = "device error"; r = -3; }
             if (r != 0) return r;
-            b0 = b1;
+            b0 = c.b1;
         }
     }
     return 0;
+}
+
+// The sparse text route: chunks capped at the sentences whose terms fit 32 MiB; per chunk the MLM head's k largest terms of every text
+// into the index's output buffer (ids [nb][k] | weights [nb][k]), then use(i0, nb, d_ids, d_weights).  0, -2 or -3 (+ err).
+template <class F>
+int32_t sparse_text_chunks(bert_ctx *ctx, SparseIndex &x, int32_t n_threads, int32_t n, const char **texts, int32_t k, F &&use, std::string &err) {
+    auto off_w = [k](int nb) { return ((size_t)nb * k * 4 + 15) & ~(size_t)15; };
+    return text_chunks(ctx, x, n_threads, n, texts, std::max(1, (int)(((size_t)32 << 20) / ((size_t)k * 8))),
+        [](int32_t, int32_t, const int32_t *) { return 0; }, [&](int nb, int) { return off_w(nb) + (size_t)nb * k * 4; },
+        [&](int32_t i0, int nb, int T, int max_len, const int32_t *, const int32_t *d_ids, const int32_t *d_cu, char *d_out) -> int32_t {
+            if (ctx->engine()->sparse_packed_device(d_ids, d_cu, nb, T, max_len, k, (int32_t *)d_out, (float *)(d_out + off_w(nb)), x.stream(), err) != 0) return -3;
+            return use(i0, nb, (const int32_t *)d_out, (const float *)(d_out + off_w(nb)));
+        }, err);
 }
 
 }  // namespace bert_hip

@@ -15,6 +15,7 @@
 
 #include "../../include/bert_hip.h"
 #include "abi.h"
+#include "text_routes.h"
 #include "token_index_file.h"
 
 using namespace bert_hip;
@@ -34,52 +35,28 @@ R token_index_call(const char *me, bert_hip_token_index *ix, F &&body) {
     }, (R)-4);
 }
 
-// Tokenizes the texts in groups of 4096 and cuts each group at chunk_tokens between sentences; per chunk: ids | cu_seqlens into the
-// index's device buffer, then use(i0, nb, T, max_len, h_cu, d_ids, d_cu) — h_cu: the chunk's lengths from 0, host; d_ids / d_cu: the
-// same on the device — all on the index's stream, which is synchronised behind every chunk.  limit > 0: a text of more tokens is
-// refused (-2).  0, -2 or -3 (+ err).
+// The token text route: text_routes.h's text_chunks without a sentence cap, T * out_row_bytes of room for a chunk's rows.  limit > 0: a
+// text of more tokens is refused (-2) before its group's first chunk.  use(i0, nb, T, max_len, h_cu, d_ids, d_cu, d_out).  0, -2 or -3 (+ err).
 template <class F>
 int32_t token_text_chunks(bert_ctx *ctx, TokenIndex &x, int32_t n_threads, int32_t n, const char **texts, int limit, size_t out_row_bytes, F &&use,
                           std::string &err) {
-    constexpr int32_t GROUP = 4096;
-    Engine *eng = ctx->engine();
-    TokenGroup &g = ctx->texts.group[0];
-    std::vector<int32_t> h_cu;
-    for (int32_t i0 = 0; i0 < n; i0 += GROUP) {
-        const int32_t m = std::min(GROUP, n - i0);
-        g.tokenize(ctx->texts, n_threads, m, texts + i0);
-        if (g.n_ok < m) { err = "input " + std::to_string(i0 + g.n_ok) + " cannot be evaluated"; return -2; }
-        const int32_t *cu = g.cu.data();
-        if (limit > 0)
-            for (int b = 0; b < m; ++b)
+    return text_chunks(ctx, x, n_threads, n, texts, 0,
+        [&](int32_t i0, int32_t m, const int32_t *cu) -> int32_t {
+            for (int b = 0; limit > 0 && b < m; ++b)
                 if (cu[b + 1] - cu[b] > limit) {
                     err = "query " + std::to_string(i0 + b) + " has " + std::to_string(cu[b + 1] - cu[b]) + " tokens; a search at this dim takes at most " + std::to_string(limit);
                     return -2;
                 }
-        for (int b0 = 0; b0 < m;) {
-            int b1 = b0 + 1, max_len = cu[b0 + 1] - cu[b0];
-            while (b1 < m && cu[b1 + 1] - cu[b0] <= eng->options().chunk_tokens) { max_len = std::max(max_len, cu[b1 + 1] - cu[b1]); ++b1; }
-            const int nb = b1 - b0, T = cu[b1] - cu[b0];
-            const size_t off_cu = ((size_t)T * 4 + 15) & ~(size_t)15;
-            char *d_in = nullptr, *d_out = nullptr;
-            if (!x.text_buffers(off_cu + (size_t)(nb + 1) * 4, (size_t)T * out_row_bytes, d_in, d_out, err)) return -3;
-            h_cu.resize(nb + 1);
-            for (int j = 0; j <= nb; ++j) h_cu[j] = cu[b0 + j] - cu[b0];
-            hipStream_t s = x.stream();
-            // (pageable sources: both copies have left the host buffers when they return)
-            if (hipMemcpyAsync(d_in, g.packed.get() + cu[b0], (size_t)T * 4, hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(d_in + off_cu, h_cu.data(), (size_t)(nb + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
-                (void)hipStreamSynchronize(s);
-                err = "hipMemcpyAsync (ids) failed";
-                return -3;
-            }
-            int32_t r = use(i0 + b0, nb, T, max_len, h_cu.data(), (const int32_t *)d_in, (const int32_t *)(d_in + off_cu), d_out);
-            if (hipStreamSynchronize(s) != hipSuccess && r == 0) { err = "device error"; r = -3; }
-            if (r != 0) return r;
-            b0 = b1;
-        }
-    }
-    return 0;
+            return 0;
+        }, [&](int, int T) { return (size_t)T * out_row_bytes; }, use, err);
+}
+
+// the pass of both text routes: each token's row over its L2 norm, f16, into d_rows; the embeddings stay in the engine
+Engine::Pass rows_pass(const int32_t *d_ids, const int32_t *d_cu, int nb, int T, int max_len, hipStream_t s, void *d_rows) {
+    Engine::Pass pass;
+    pass.d_tokens = d_ids; pass.d_cu = d_cu; pass.n_sentences = nb; pass.n_tokens = T; pass.max_len = max_len; pass.stream = s;
+    pass.d_token_rows = d_rows; pass.token_flags = TOKEN_ROWS_NORMALIZE | TOKEN_ROWS_F16;
+    return pass;
 }
 
 // an allow-list of n_words words covers the index (-2 + err otherwise)
@@ -164,8 +141,7 @@ int32_t bert_hip_token_index_add_texts(struct bert_hip_token_index *ix, int32_t 
             [&](int32_t, int32_t nb, int32_t T, int32_t max_len, const int32_t *h_cu, const int32_t *d_ids, const int32_t *d_cu, char *) -> int32_t {
                 half_t *dst = x.append_room(T, err);
                 if (!dst) return err.rfind("add:", 0) == 0 ? -2 : -3;
-                if (eng->eval_packed_device(d_ids, d_cu, nb, T, max_len, nullptr, x.stream(), nullptr, err, nullptr, 0, 0, -1, dst,
-                                            TOKEN_ROWS_NORMALIZE | TOKEN_ROWS_F16) != 0) return -3;
+                if (eng->eval_packed_device(rows_pass(d_ids, d_cu, nb, T, max_len, x.stream(), dst), err) != 0) return -3;
                 const int32_t a = x.add_in_place(nb, h_cu, err);
                 return a < 0 ? a : 0;
             }, err);
@@ -207,8 +183,7 @@ int32_t bert_hip_token_index_search_texts(struct bert_hip_token_index *ix, int32
         std::vector<float> hsc((size_t)n_queries * k);
         const int32_t r = token_text_chunks(ctx, x, n_threads, n_queries, texts, x.max_query_tokens(), (size_t)x.dim() * 2,
             [&](int32_t i0, int32_t nb, int32_t T, int32_t max_len, const int32_t *, const int32_t *d_ids, const int32_t *d_cu, char *d_out) -> int32_t {
-                if (eng->eval_packed_device(d_ids, d_cu, nb, T, max_len, nullptr, x.stream(), nullptr, err, nullptr, 0, 0, -1, d_out,
-                                            TOKEN_ROWS_NORMALIZE | TOKEN_ROWS_F16) != 0) return -3;
+                if (eng->eval_packed_device(rows_pass(d_ids, d_cu, nb, T, max_len, x.stream(), d_out), err) != 0) return -3;
                 return x.search_device_to_host(nb, d_cu, (const half_t *)d_out, max_len, k, hid.data() + (size_t)i0 * k, hsc.data() + (size_t)i0 * k, err);
             }, err);
         if (r != 0) { if (err.empty()) err = "device error"; return r; }

@@ -73,8 +73,11 @@ int32_t bert_hip_eval_packed_tokens_device(struct bert_ctx *ctx, const bert_voca
             return -2;
         }
         std::string err;
-        if (ctx->engine()->eval_packed_device(d_tokens, d_cu_seqlens, n_sentences, n_tokens_total, max_len, d_embeddings, (hipStream_t)stream, nullptr, err,
-                                              nullptr, 0, 0, -1, d_rows, flags) != 0) {
+        Engine::Pass pass;
+        pass.d_tokens = d_tokens; pass.d_cu = d_cu_seqlens; pass.n_sentences = n_sentences; pass.n_tokens = n_tokens_total; pass.max_len = max_len; pass.stream = (hipStream_t)stream;
+        pass.d_out = d_embeddings;
+        pass.d_token_rows = d_rows; pass.token_flags = flags;
+        if (ctx->engine()->eval_packed_device(pass, err) != 0) {
             fprintf(stderr, "%s: %s\n", me, err.c_str());
             return -3;
         }

@@ -9,7 +9,7 @@ import contextlib
 import ctypes as C
 import os
 import subprocess
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -69,7 +69,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_dispatch", "bert_hip_test_shard_threads_created", "bert_hip_test_embed_ln", "bert_hip_test_embed_ln_lanes", "bert_hip_test_pool_normalize",
     "bert_hip_test_pool", "bert_hip_test_layernorm",
     "bert_hip_test_f32_gemm", "bert_hip_test_f32_attention", "bert_hip_test_f32_layernorm", "bert_hip_test_f32_embed_ln", "bert_hip_test_f32_pool",
-    "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs",
+    "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs", "bert_hip_test_host_chunks",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
     "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool", "bert_hip_test_token_rows",
     "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
@@ -370,6 +370,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_parse_devices.argtypes = [C.c_char_p, i32, i32, i32p, C.c_char_p, i32]
     L.bert_hip_test_gather_runs.restype = i32
     L.bert_hip_test_gather_runs.argtypes = [i32p, i32, C.c_int64, i32p]
+    L.bert_hip_test_host_chunks.restype = i32
+    L.bert_hip_test_host_chunks.argtypes = [i32p, i32, i32, i32, i32p]
     L.bert_hip_test_encode_groups.restype = i32
     L.bert_hip_test_encode_groups.argtypes = [i32, i32p, i32]
     L.bert_hip_test_tokenize_pack.restype = i32
@@ -789,6 +791,14 @@ def parse_devices(spec: Optional[bytes], n_devices: int, current: int = 0):
     err = C.create_string_buffer(512)
     n = test_lib().bert_hip_test_parse_devices(spec, n_devices, current, _i32p(devs), err, len(err))
     return (None, err.value.decode()) if n < 0 else (devs[:n].tolist(), None)
+
+
+def host_chunks(cu_seqlens: np.ndarray, chunk_tokens: int, max_sentences: int = 0) -> List[Tuple[int, int, int]]:
+    """the chunks (b0, b1, max_len) the host forms and the text routes cut a batch into"""
+    cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    out = np.zeros(3 * (len(cu) - 1), dtype=np.int32)
+    n = test_lib().bert_hip_test_host_chunks(_i32p(cu), len(cu) - 1, chunk_tokens, max_sentences, _i32p(out))
+    return [tuple(c) for c in out[:3 * n].reshape(-1, 3).tolist()]
 
 
 def gather_runs(cu_seqlens: np.ndarray, tokens_per_run: int) -> List[int]:

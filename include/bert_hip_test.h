@@ -211,6 +211,9 @@ BERT_API int32_t bert_hip_test_parse_devices(const char *list, int32_t n_devices
 /* The super-batch cut of bert_hip_eval_packed_gather (gather.h gather_runs): returns the number of entries written to runs
  * (capacity n_sentences + 1).                                                                                                  */
 BERT_API int32_t bert_hip_test_gather_runs(const int32_t *cu_seqlens, int32_t n_sentences, int64_t tokens_per_run, int32_t *runs);
+/* The chunk rule of the host forms and the text routes (host_chunks.h next_host_chunk), walked over the whole batch: returns the number
+ * of chunks, each as {b0, b1, max_len} in out (capacity 3 * n_sentences).  max_sentences 0: no cap.                              */
+BERT_API int32_t bert_hip_test_host_chunks(const int32_t *cu_seqlens, int32_t n_sentences, int32_t chunk_tokens, int32_t max_sentences, int32_t *out);
 /* The group sizes bert_encode_batch cuts n_inputs texts into (text_batch.h encode_group_size): returns their number, the first
  * `cap` of them in groups.                                                                                                      */
 BERT_API int32_t bert_hip_test_encode_groups(int32_t n_inputs, int32_t *groups, int32_t cap);

@@ -1,6 +1,6 @@
 """Host logic of the API layer (csrc/context.cpp, gather.cpp, text_batch.cpp) through the test library, each against a Python
-restatement — no GPU needed: the BERT_HIP_DEVICES parser, the super-batch cut of the gather, the group schedule of
-bert_encode_batch and the tokenize + validate + pack step the text entry points share."""
+restatement — no GPU needed: the BERT_HIP_DEVICES parser, the super-batch cut of the gather, the chunk rule of the host forms and the
+text routes (csrc/host_chunks.h), the group schedule of bert_encode_batch and the tokenize + validate + pack step the text entry points share."""
 import random
 
 import numpy as np
@@ -110,6 +110,44 @@ def test_gather_runs_against_restatement_and_properties():
             if b < n:
                 assert int(cu[b + 1]) - int(cu[a]) > per_run                   # the run could not have taken the next sentence
     assert pybert.gather_runs(_cu([128] * 1024), 128 * 256) == [0, 256, 512, 768, 1024]
+
+
+# ------------------------------------------------------------------------------------------------ host chunks
+def _host_chunks(cu, chunk_tokens, cap):
+    B, chunks, b0 = len(cu) - 1, [], 0
+    while b0 < B:
+        b1 = b0 + 1
+        while b1 < B and (cap == 0 or b1 - b0 < cap) and int(cu[b1 + 1]) - int(cu[b0]) <= chunk_tokens:
+            b1 += 1
+        chunks.append((b0, b1, int(np.diff(cu[b0:b1 + 1]).max())))
+        b0 = b1
+    return chunks
+
+
+def test_host_chunks_against_restatement_and_properties():
+    """The one chunk rule of the host forms and the text routes: the chunks tile [0, B) in order; only a single sentence exceeds
+    chunk_tokens; the sentence cap holds; every cut is greedy; max_len is the chunk's longest sentence."""
+    rng = np.random.default_rng(4)
+    lists = [[7], [300], [1, 300, 1], [300, 300], [30, 40], [40, 30, 1], [30, 41], [10, 20, 10], [10, 20, 11], [54, 65, 48, 64], [1] * 9]
+    for _ in range(60):
+        n = int(rng.integers(1, 200))
+        lists.append((rng.integers(1, 513, n) if rng.integers(2) else np.clip(np.round(rng.lognormal(np.log(21.0), 0.7, n)), 1, 128).astype(int)).tolist())
+    for lens in lists:
+        cu = _cu(lens, first=int(rng.integers(0, 2)) * 1000)                  # (the cut depends on differences only)
+        B = len(lens)
+        for chunk_tokens in (1, 40, 70, 262144):
+            for cap in (0, 1, 3):
+                chunks = pybert.host_chunks(cu, chunk_tokens, cap)
+                assert chunks == _host_chunks(cu, chunk_tokens, cap), (lens[:8], chunk_tokens, cap)
+                assert chunks[0][0] == 0 and chunks[-1][1] == B and all(a[1] == b[0] for a, b in zip(chunks, chunks[1:]))
+                for b0, b1, max_len in chunks:
+                    assert b1 > b0 and max_len == max(lens[b0:b1])
+                    assert sum(lens[b0:b1]) <= chunk_tokens or b1 - b0 == 1     # only a single sentence exceeds a chunk
+                    assert cap == 0 or b1 - b0 <= cap
+                    if b1 < B:                                                  # greedy: the next sentence would not have fitted
+                        assert sum(lens[b0:b1 + 1]) > chunk_tokens or b1 - b0 == cap
+    assert pybert.host_chunks(_cu([30, 40]), 70) == [(0, 2, 40)] and pybert.host_chunks(_cu([30, 41]), 70) == [(0, 1, 30), (1, 2, 41)]
+    assert pybert.host_chunks(_cu([300]), 70) == [(0, 1, 300)] and pybert.host_chunks(_cu([1] * 7), 262144, 3) == [(0, 3, 1), (3, 6, 1), (6, 7, 1)]
 
 
 # ------------------------------------------------------------------------------------------------ group schedule

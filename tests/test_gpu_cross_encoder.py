@@ -244,6 +244,28 @@ def test_typed_pass_and_scores_match_float64(model_dir, dims, ftype):
     m.close()
 
 
+@pytest.mark.parametrize("chunk_tokens", [70, 40])
+def test_host_forms_cut_into_chunks_keep_the_bits(model_dir, chunk_tokens):
+    """54 | 65 | 48 | 64 tokens with mixed first_len under chunk_tokens 70 (cut three times) and 40 (every sentence longer than a chunk: each
+    a chunk of its own): eval_packed_typed and score_packed return the uncut call's bits, and the head is launched once per chunk."""
+    m = pybert.BertModel(_model_file(model_dir, "tiny", "f16", 3))
+    toks, cu, fl, _ = cer.batch(np.random.default_rng(12), DIMS["tiny"], [(54, 20), (65, 65), (48, 1), (64, 33)])
+    want_rows, want_scores = m.eval_packed_typed(toks, cu, fl), m.score_packed(toks, cu, fl)
+    assert np.isfinite(want_rows).all() and np.isfinite(want_scores).all()
+    m.set_option("chunk_tokens", str(chunk_tokens))
+    try:
+        rows = m.eval_packed_typed(toks, cu, fl)
+        m.profile(True)
+        scores = m.score_packed(toks, cu, fl)
+        assert m.profile_report()["cls_head"]["launches"] == 4
+        m.profile(False)
+        assert _same(rows, want_rows) and _same(scores, want_scores)
+    finally:
+        m.set_option("chunk_tokens", "262144")
+    assert _same(m.score_packed(toks, cu, fl), want_scores)
+    m.close()
+
+
 # ------------------------------------------------------------------------------------------------
 # 5. text level, 6. errors
 # ------------------------------------------------------------------------------------------------

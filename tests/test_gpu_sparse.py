@@ -252,6 +252,28 @@ def test_existing_entry_points_keep_their_bits(model_dir, dims, ftype):
     plain.close(); both.close()
 
 
+@pytest.mark.parametrize("chunk_tokens", [70, 40])
+def test_host_form_cut_into_chunks_keeps_the_bits(model_dir, chunk_tokens):
+    """54 | 65 | 48 | 64 tokens under chunk_tokens 70 (cut three times) and 40 (every sentence longer than a chunk: each a chunk of its own):
+    sparse_packed, dense and top-k, returns the uncut call's bits; the dense form launches the vocabulary kernel once per chunk."""
+    m = pybert.BertModel(_model_file(model_dir, "tiny", "f16"))
+    toks, cu, _ = sr.batch(np.random.default_rng(12), DIMS["tiny"], [54, 65, 48, 64])
+    want, (want_ids, want_w) = m.sparse_packed(toks, cu), m.sparse_packed(toks, cu, 10)
+    assert np.isfinite(want).all() and (want > 0).any()
+    m.set_option("chunk_tokens", str(chunk_tokens))
+    try:
+        m.profile(True)
+        dense = m.sparse_packed(toks, cu)
+        assert m.profile_report()["sparse_vocab"]["launches"] == 4
+        m.profile(False)
+        ids, wt = m.sparse_packed(toks, cu, 10)
+        assert _same(dense, want) and np.array_equal(ids, want_ids) and _same(wt, want_w)
+    finally:
+        m.set_option("chunk_tokens", "262144")
+    assert _same(m.sparse_packed(toks, cu), want)
+    m.close()
+
+
 @pytest.fixture(scope="module")
 def text_model(model_dir, tok_golden):
     """tiny dims over the golden tokenizer's vocabulary, with the MLM head"""

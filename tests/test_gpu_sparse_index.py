@@ -429,6 +429,29 @@ def test_text_routes_are_encode_sparse_fed_to_the_index(text_model, dtype):
     m.close()
 
 
+def test_add_texts_cut_into_chunks_stores_the_same_rows(text_model):
+    """Four short lines under chunk_tokens 70: the text route cuts them into several chunks and stores the rows the uncut call stores."""
+    path, _, words = text_model
+    m = pybert.BertModel(path)
+    rng = np.random.default_rng(6)
+    texts = [" ".join(rng.choice(words, size=n)) for n in (34, 36, 33, 35)]
+    lens = [len(i) for i in m.tokenize_batch(texts)]
+    assert max(lens) <= 70 < min(a + b for a, b in zip(lens, lens[1:])), lens     # every line fits a chunk, no two neighbours do
+    uncut = m.sparse_index(48, "f16")
+    assert uncut.add_texts(texts) == 0
+    want = uncut.get_rows(np.arange(4))
+    m.set_option("chunk_tokens", "70")
+    try:
+        ix = m.sparse_index(48, "f16")
+        assert ix.add_texts(texts) == 0 and len(ix) == 4
+        assert _same(ix.get_rows(np.arange(4)), want)
+        ix.close()
+    finally:
+        m.set_option("chunk_tokens", "262144")
+    uncut.close()
+    m.close()
+
+
 def test_text_routes_refuse_a_model_without_the_head_or_another_vocabulary(text_model, capfd):
     with_head, without, _ = text_model
     out_i, out_s = np.full((1, 4), 7, np.int32), np.full((1, 4), 7.0, np.float32)
