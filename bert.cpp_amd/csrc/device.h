@@ -168,6 +168,12 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
     return v;
 }
+// the maximum over the four lanes of a quad (lane ^ 2, then lane ^ 1: wave_sum_f32's last two steps; a maximum is exact in any order)
+__device__ __forceinline__ float quad_max_f32(float v) {
+    v = __builtin_fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)));
+    v = __builtin_fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));
+    return v;
+}
 
 // The int8 row rule of the embedding index (search.hip index_quantize_kernel) and the token index (token_index.hip
 // token_i8_quantize_kernel), the whole wave on one row: x[0 .. dim) (f32, or f16 converted exactly) -> scale = amax / 127 and codes

@@ -16,8 +16,9 @@ namespace bert_hip {
 namespace {
 
 // the profiler's names, by the dense index's dtype / the sparse index's dtype, plain and masked
-const char *const SCORES_NAMES[4][2] = {{"index_scores_f32", "index_scores_f32_masked"}, {"index_scores_f16", "index_scores_f16_masked"},
-                                        {"index_scores_i8", "index_scores_i8_masked"}, {"index_scores_b1", "index_scores_b1_masked"}};
+const char *const SCORES_NAMES[5][2] = {{"index_scores_f32", "index_scores_f32_masked"}, {"index_scores_f16", "index_scores_f16_masked"},
+                                        {"index_scores_i8", "index_scores_i8_masked"}, {"index_scores_b1", "index_scores_b1_masked"},
+                                        {"index_scores_mxfp4", "index_scores_mxfp4_masked"}};
 const char *const SCAN_NAMES[2][2] = {{"sparse_hybrid_scan_f32", "sparse_hybrid_scan_f32_masked"}, {"sparse_hybrid_scan_f16", "sparse_hybrid_scan_f16_masked"}};
 const char *const POSTINGS_SCAN_NAMES[2][2] = {{"sparse_postings_hybrid_scan_f32", "sparse_postings_hybrid_scan_f32_masked"},
                                                {"sparse_postings_hybrid_scan_f16", "sparse_postings_hybrid_scan_f16_masked"}};

@@ -21,15 +21,20 @@ namespace {
 struct FormInfo {
     const char *topk[2], *rescore, *probe, *probe_masked, *exported, *ingest;      // topk[1], probe_masked: the masked instantiations
     bool has_rscale;                             // one f32 scale per row beside the rows
-    bool quantized_queries;                      // queries are stored as rows of the i8 form (codes and a scale), else of this one
+    int query_form;                              // the form the queries take: this one, the i8 form (2: codes and a scale) or QFORM_MXFP8
 };
-constexpr FormInfo FORMS[4] = {
-    {{"index_topk_f32", "index_topk_f32_masked"}, "index_rescore_f32", "index_probe_f32", "index_probe_f32_masked", "index_export_f32", "index_convert_f32", false, false},
-    {{"index_topk_f16", "index_topk_f16_masked"}, "index_rescore_f16", "index_probe_f16", "index_probe_f16_masked", "index_export_f16", "index_convert_f16", false, false},
-    {{"index_topk_i8", "index_topk_i8_masked"}, "index_rescore_i8", "index_probe_i8", "index_probe_i8_masked", "index_export_i8", "index_quantize_i8", true, true},
-    {{"index_topk_b1", "index_topk_b1_masked"}, "index_rescore_b1", "index_probe_b1", "index_probe_b1_masked", "index_export_b1", "index_pack_b1", false, true},
+constexpr FormInfo FORMS[5] = {
+    {{"index_topk_f32", "index_topk_f32_masked"}, "index_rescore_f32", "index_probe_f32", "index_probe_f32_masked", "index_export_f32", "index_convert_f32", false, 0},
+    {{"index_topk_f16", "index_topk_f16_masked"}, "index_rescore_f16", "index_probe_f16", "index_probe_f16_masked", "index_export_f16", "index_convert_f16", false, 1},
+    {{"index_topk_i8", "index_topk_i8_masked"}, "index_rescore_i8", "index_probe_i8", "index_probe_i8_masked", "index_export_i8", "index_quantize_i8", true, 2},
+    {{"index_topk_b1", "index_topk_b1_masked"}, "index_rescore_b1", "index_probe_b1", "index_probe_b1_masked", "index_export_b1", "index_pack_b1", false, 2},
+    {{"index_topk_mxfp4", "index_topk_mxfp4_masked"}, "index_rescore_mxfp4", "index_probe_mxfp4", "index_probe_mxfp4_masked", "index_export_mxfp4", "index_quantize_mxfp4", false, QFORM_MXFP8},
 };
-int query_form(int dtype) { return FORMS[dtype].quantized_queries ? 2 : dtype; }
+int query_form(int dtype) { return FORMS[dtype].query_form; }
+// the profiler's name of the kernel that makes that form of f32 queries
+const char *query_ingest(int form) { return form == QFORM_MXFP8 ? "index_quantize_mxfp8" : FORMS[form].ingest; }
+// whether the queries carry one f32 scale each (the i8 form)
+bool query_scales(int dtype) { return query_form(dtype) == 2; }
 
 // slices of a search: enough workgroups to fill the chip, but each slice long against k (the first k rows of a slice all
 // enter its list, and the merge reads slices x k candidates per query).  Grows with n_rows.
@@ -90,7 +95,7 @@ void index_search_plan(int n_rows, int nq, int k, int geometry[4]) {
 Index *Index::create(Engine *eng, int dim, int dtype, std::string &err) {
     if (!eng) { err = "no device engine"; return nullptr; }
     if (dim < 1 || dim > MAX_DIM) { err = "dim must be 1 .. 2048"; return nullptr; }
-    if (dtype < 0 || dtype > 3) { err = "dtype must be 0 (f32), 1 (f16), 2 (i8) or 3 (b1)"; return nullptr; }
+    if (dtype < 0 || dtype > 4) { err = "dtype must be 0 (f32), 1 (f16), 2 (i8), 3 (b1) or 4 (mxfp4)"; return nullptr; }
     DeviceGuard g(eng->device());
     Index *ix = new Index;
     ix->dim_ = dim;
@@ -159,7 +164,7 @@ bool Index::reserve(int n_rows, int n_queries, int k, std::string &err) {
 
 // the stored form of a chunk of nqc queries (quantized: codes and scales)
 bool Index::grow_queries(int nqc, std::string &err) {
-    return grow(qbuf_, (size_t)nqc * qrow_bytes_, err) && (!FORMS[dtype_].quantized_queries || grow(qscale_, (size_t)nqc * 4, err));
+    return grow(qbuf_, (size_t)nqc * qrow_bytes_, err) && (!query_scales(dtype_) || grow(qscale_, (size_t)nqc * 4, err));
 }
 
 int Index::add_device(int n, const float *d_rows, hipStream_t s, std::string &err) {
@@ -201,10 +206,10 @@ int Index::add_host(int n, const float *rows, std::string &err) {
     return first;
 }
 
-// f32 queries -> qbuf_ (and qscale_) in the form the score block reads: the rows', or i8 codes padded to this dpad and their scales
+// f32 queries -> qbuf_ (and qscale_) in the form the score block reads: the rows', i8 codes padded to this dpad and their scales, or MXFP8
 void Index::enqueue_queries(int nq, const float *d_q, hipStream_t s) {
     const int form = query_form(dtype_);
-    eng_->timed_launch(FORMS[form].ingest, 0.0, s, [&] { launch_ingest(form, d_q, qbuf_.p, qscale_.as<float>(), nq, dim_, dpad_, s); });
+    eng_->timed_launch(query_ingest(form), 0.0, s, [&] { launch_ingest(form, d_q, qbuf_.p, qscale_.as<float>(), nq, dim_, dpad_, s); });
 }
 
 void Index::enqueue_chunk(int nq, const float *d_q, int k, int32_t *d_ids, float *d_scores, hipStream_t s, const uint32_t *d_allow) {
@@ -485,6 +490,7 @@ static constexpr size_t FILE_PIECE = (size_t)64 << 20;
 
 bool Index::save(const char *path, std::string &err) {
     if (!path || !*path) { err = "a path is required"; return false; }
+    if (dtype_ == 4) { err = "save: the mxfp4 form (dtype 4) has no file form yet"; return false; }
     DeviceGuard g(eng_->device());
     HIP_OK(hipEventSynchronize(busy_), err, false);
     IndexFileHeader h;

@@ -23,11 +23,12 @@ uint32_t get_u32(const unsigned char *p) {
 int index_elem_size(int dtype) { return dtype == 0 ? 4 : dtype == 1 ? 2 : dtype == 2 ? 1 : 0; }
 
 int index_dpad(int dtype, int dim) {
-    const int step = dtype == 3 ? 128 : dtype == 2 ? 32 : dtype == 1 ? 16 : 8;
+    const int step = dtype == 4 || dtype == QFORM_MXFP8 ? 64 : dtype == 3 ? 128 : dtype == 2 ? 32 : dtype == 1 ? 16 : 8;
     return (dim + step - 1) / step * step;
 }
 
 uint64_t index_row_bytes(int dtype, int dpad) {
+    if (dtype == 4 || dtype == QFORM_MXFP8) return ((uint64_t)(dtype == 4 ? dpad / 2 : dpad) + (uint64_t)dpad / 32 + 15) / 16 * 16;
     return dtype == 3 ? (uint64_t)dpad / 8 : (uint64_t)dpad * (uint64_t)index_elem_size(dtype);
 }
 

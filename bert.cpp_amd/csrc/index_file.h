@@ -13,12 +13,19 @@ constexpr size_t INDEX_HEADER_BYTES = 64;
 constexpr uint32_t INDEX_FILE_VERSION = 1;
 constexpr int INDEX_MAX_DIM = 2048;
 
-// bytes per stored element of dtype 0 (f32), 1 (f16), 2 (i8); 0 for any other dtype (3, b1, stores an eighth of a byte)
+// The form an mxfp4 index (dtype 4) keeps its queries in, MXFP8: a code for index_dpad, index_row_bytes and the ingest launch
+// beside the dtypes, not the dtype of any index (and of no file: an mxfp4 index has no file form, and index_header_check goes
+// on refusing dtype 4)
+constexpr int QFORM_MXFP8 = 5;
+
+// bytes per stored element of dtype 0 (f32), 1 (f16), 2 (i8); 0 for any other dtype (3, b1, stores an eighth of a byte; 4,
+// mxfp4, half a byte and scale bytes)
 int index_elem_size(int dtype);
-// elements per stored row: dim rounded up to the score kernel's k-step (8 floats, 16 halves, 32 bytes) or, for dtype 3 (b1),
-// to the 128 bits of a 16-byte piece
+// elements per stored row: dim rounded up to the score kernel's k-step (8 floats, 16 halves, 32 bytes; 64 elements for dtype 4
+// and its queries) or, for dtype 3 (b1), to the 128 bits of a 16-byte piece
 int index_dpad(int dtype, int dim);
-// bytes per stored row of dpad elements: dpad * index_elem_size, dpad / 8 for dtype 3 (one bit per element)
+// bytes per stored row of dpad elements: dpad * index_elem_size, dpad / 8 for dtype 3 (one bit per element); dtype 4: dpad / 2
+// code bytes and dpad / 32 scale bytes, QFORM_MXFP8: dpad code bytes and dpad / 32 scale bytes, both padded to a multiple of 16
 uint64_t index_row_bytes(int dtype, int dpad);
 
 struct IndexFileHeader {

@@ -44,7 +44,8 @@ public:
     static constexpr int MAX_CAND = 1024;                // candidates per query of a rescore
 
     // dtype 0: f32 rows, 1: f16 rows (queries rounded to f16 as well), 2: i8 rows with one f32 scale each (queries quantized
-    // the same way; search.hip), 3: one sign bit per element, no scale (queries quantized to i8 codes and a scale)
+    // the same way; search.hip), 3: one sign bit per element, no scale (queries quantized to i8 codes and a scale), 4: mxfp4, e2m1
+    // codes with one E8M0 scale per 32 elements inside the row (queries quantized to MXFP8, e4m3 codes and the same scales)
     static Index *create(Engine *eng, int dim, int dtype, std::string &err);
     ~Index();
 
@@ -137,7 +138,7 @@ private:
     void drop_partition();
 
     int dim_ = 0, dtype_ = 0, dpad_ = 0;                // dpad_: elements per stored row
-    size_t row_bytes_ = 0, qrow_bytes_ = 0;             // bytes per stored row; per query as the score kernel reads it (b1: i8 codes)
+    size_t row_bytes_ = 0, qrow_bytes_ = 0;             // bytes per stored row; per query as the score kernel reads it (b1: i8 codes; mxfp4: MXFP8)
     int cap_ = 0;                                       // (the rows themselves, n_, the bitmap, the lists' workspace: index_frame.h)
     void *rows_ = nullptr;                              // [cap_][row_bytes_]
     float *rscale_ = nullptr;                           // i8: [cap_] row scales

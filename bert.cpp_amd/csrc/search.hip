@@ -53,6 +53,11 @@
 // bits zero, no scale.  Queries are quantized as for i8.  score = (float)dot * qscale with dot = sum_i qc_i (bit_i ? +1 : -1) an
 // exact int32; the padding's -1 meets a zero code.
 //
+// The mxfp4 form (dtype 4): OCP MXFP4 rows — dpad / 2 bytes of e2m1 codes, dpad / 32 E8M0 scale bytes (one per 32 elements),
+// zero bytes to a multiple of 16; dpad a multiple of 64 — against MXFP8 queries (dpad e4m3 bytes and the same scale bytes), both
+// made by index_quantize_mx_kernel as include/bert_hip.h states them and scored by v_mfma_scale_f32_32x32x64_f8f6f4
+// (ScoreBlock<mxfp4_t>).  No scale array beside the rows.  Non-finite input: 0xFF scale bytes, NaN scores, never returned.
+//
 // Order of a result: larger score first, equal scores (==, so +0 equals -0) by smaller id; NaN scores never pass a compare
 // and are never returned; missing entries are id -1, score -inf (inside the kernels: id INT_MAX, which ranks below every row).
 // Determinism: a (query, row) score is one MFMA accumulation chain in a fixed k order that depends on nothing but dpad (i8: an
@@ -82,7 +87,8 @@ constexpr int MERGE_U = 16;             // candidates per thread and round of th
 // accumulation is fixed by dpad alone.
 // ScoreBlock<T> is also everything else a kernel knows of the stored form T: query_t / acc_t, the element of a query as run
 // reads it and run's accumulator; QSCALE / RSCALE, whether a score takes the query's / the row's scale; row_ptr, stored row
-// `row` of rows of dpad elements; finish, one accumulator element -> the score, the one place that arithmetic is written;
+// `row` of rows of dpad elements, and query_ptr, the same for the queries as stored for this form; finish, one accumulator
+// element -> the score, the one place that arithmetic is written;
 // element, element e of a stored row as f32 (rs: its scale where RSCALE) — what bert_hip_index_get_rows returns.
 template <class T> struct ScoreBlock;
 
@@ -92,8 +98,9 @@ template <class T> struct FloatForm {
     using acc_t = f32x16;
     static constexpr bool QSCALE = false, RSCALE = false;
     static __device__ __forceinline__ const T *row_ptr(const void *rows, size_t row, int dpad) { return (const T *)rows + row * dpad; }
+    static __device__ __forceinline__ const T *query_ptr(const void *queries, size_t q, int dpad) { return (const T *)queries + q * dpad; }
     static __device__ __forceinline__ float finish(float acc, float, float) { return acc; }
-    static __device__ __forceinline__ float element(const T *rp, float, int e) { return (float)rp[e]; }
+    static __device__ __forceinline__ float element(const T *rp, float, int e, int) { return (float)rp[e]; }
 };
 
 template <> struct ScoreBlock<half_t> : FloatForm<half_t> {
@@ -138,9 +145,10 @@ template <> struct ScoreBlock<int8_t> {
     using acc_t = i32x16;
     static constexpr bool QSCALE = true, RSCALE = true;
     static __device__ __forceinline__ const int8_t *row_ptr(const void *rows, size_t row, int dpad) { return (const int8_t *)rows + row * dpad; }
+    static __device__ __forceinline__ const int8_t *query_ptr(const void *queries, size_t q, int dpad) { return (const int8_t *)queries + q * dpad; }
     // (two multiplies in this order and no add: nothing the compiler could contract)
     static __device__ __forceinline__ float finish(int dot, float qs, float rs) { return ((float)dot * qs) * rs; }
-    static __device__ __forceinline__ float element(const int8_t *rp, float rs, int e) { return (float)rp[e] * rs; }
+    static __device__ __forceinline__ float element(const int8_t *rp, float rs, int e, int) { return (float)rp[e] * rs; }
     // v_mfma_i32_32x32x32_i8: lane l feeds the 16 bytes at k = 32 s + 16 (l >> 5) of its query and of its row to step s — the
     // same k map on both sides, and an integer sum is exact in any order
     static __device__ __forceinline__ void run(const int8_t *qp, const int8_t *rp, bool qok, bool rok, int dpad, int h, i32x16 &acc) {
@@ -171,8 +179,9 @@ template <> struct ScoreBlock<b1_t> {
     static constexpr bool QSCALE = true, RSCALE = false;
     // (dpad / 8 bytes per row)
     static __device__ __forceinline__ const b1_t *row_ptr(const void *rows, size_t row, int dpad) { return (const b1_t *)rows + row * (dpad >> 3); }
+    static __device__ __forceinline__ const int8_t *query_ptr(const void *queries, size_t q, int dpad) { return (const int8_t *)queries + q * dpad; }
     static __device__ __forceinline__ float finish(int dot, float qs, float) { return (float)dot * qs; }
-    static __device__ __forceinline__ float element(const b1_t *rp, float, int e) { return (rp[e >> 3].bits >> (e & 7)) & 1 ? 1.f : -1.f; }
+    static __device__ __forceinline__ float element(const b1_t *rp, float, int e, int) { return (rp[e >> 3].bits >> (e & 7)) & 1 ? 1.f : -1.f; }
     // bit 4 j + b of bits16 in byte b of element j: 0x01 for a set bit, 0xff (-1) for a clear one.  The multiply puts bit b of
     // a nibble at bit 8 b (four copies 7 bits apart, which do not overlap); the byte permute looks 0 / 1 up in {0xff, 0x01}
     static __device__ __forceinline__ i32x4 expand(uint32_t bits16) {
@@ -213,6 +222,93 @@ template <> struct ScoreBlock<b1_t> {
     }
 };
 
+// a stored byte of an mxfp4 row (two e2m1 codes, or one E8M0 scale) / of an mxfp8 query (one e4m3 code, or one scale)
+struct mxfp4_t { uint8_t byte; };
+struct mxfp8_t { uint8_t byte; };
+typedef int32_t i32x8 __attribute__((ext_vector_type(8)));
+
+// bytes of a stored row of `bytes` code bytes and one scale byte per 32 of dpad elements, padded to whole 16-byte pieces
+__host__ __device__ constexpr size_t mx_row_bytes(int code_bytes, int dpad) { return ((size_t)code_bytes + (dpad >> 5) + 15) & ~(size_t)15; }
+
+// the value of an e2m1 code's three magnitude bits: {0, 0.5, 1, 1.5, 2, 3, 4, 6}
+__device__ __forceinline__ float e2m1_value(uint32_t m) {
+    const uint32_t ex = m >> 1, mant = m & 1u;
+    return ex == 0 ? 0.5f * (float)mant : __builtin_ldexpf(1.f + 0.5f * (float)mant, (int)ex - 1);
+}
+
+template <> struct ScoreBlock<mxfp4_t> {
+    using query_t = mxfp8_t;
+    using acc_t = f32x16;
+    static constexpr bool QSCALE = false, RSCALE = false;
+    // (dpad / 2 code bytes, dpad / 32 scale bytes, padded to 16; a query: dpad code bytes, the same scale bytes, padded to 16)
+    static __device__ __forceinline__ const mxfp4_t *row_ptr(const void *rows, size_t row, int dpad) { return (const mxfp4_t *)rows + row * mx_row_bytes(dpad >> 1, dpad); }
+    static __device__ __forceinline__ const mxfp8_t *query_ptr(const void *queries, size_t q, int dpad) { return (const mxfp8_t *)queries + q * mx_row_bytes(dpad, dpad); }
+    static __device__ __forceinline__ float finish(float acc, float, float) { return acc; }
+    // value(code) * 2^(scale byte - 127), exact in f32 (6 * 2^125 at the most, 0.5 * 2^-127 at the least); NaN for the scale byte
+    // 0xFF of a row that held a non-finite element
+    static __device__ __forceinline__ float element(const mxfp4_t *rp, float, int e, int dpad) {
+        const uint32_t code = (rp[e >> 1].byte >> (4 * (e & 1))) & 0xfu, sc = rp[(dpad >> 1) + (e >> 5)].byte;
+        const float v = e2m1_value(code & 7u);
+        return sc == 0xffu ? __builtin_nanf("") : __builtin_ldexpf(code & 8u ? -v : v, (int)sc - 127);
+    }
+    // v_mfma_scale_f32_32x32x64_f8f6f4, A = the query's e4m3 codes, B = the row's e2m1 codes (blgp 4).  Lane l = (col, h) feeds
+    // step s as B the 16 row bytes at 32 s + 16 h: the 32 codes of block 2 s + h, k = 32 h .. 32 h + 31 of the step.  An 8-bit
+    // operand is two 16-byte chunks, each split over the half-waves: as A the lane feeds the query's 16 bytes at 64 s + 16 h
+    // (registers 0 .. 3: k = 16 h ..) and the 16 at 64 s + 32 + 16 h (registers 4 .. 7: k = 32 + 16 h ..).  The scales go by
+    // k-block, not by the lane's registers: the byte lane (col, h) names with its opsel, for either operand, scales
+    // k = 32 h .. 32 h + 31.  The exact-fit test of tests/test_gpu_search_mxfp4.py checks this map on the hardware.
+    // A lane reads its scale bytes as dwords ahead of the chain (dword j: blocks 4 j .. 4 j + 3, steps 2 j and 2 j + 1) and
+    // shifts them by 8 h once: byte 0 is then block 4 j + h, step 2 j's, and byte 2 block 4 j + 2 + h, step 2 j + 1's —
+    // opsel 0 and 2 for every lane.  One chain of dpad / 64 MFMAs in ascending k from a zero accumulator, U = 4 steps of loads
+    // in flight; the chain is unrolled to the 32 steps of dim 2048 behind wave-uniform tests of dpad, since the scale dwords live in
+    // registers.
+    // Non-finite input: the quantizer wrote 0xFF into every scale byte of such a row or query (a finite one holds no 0xFF: the
+    // largest is 127 + 125).  The scores are made NaN here, from the dwords held, whatever the MFMA makes of that scale: the row's
+    // is this lane's own, the 32 queries' tests meet in a ballot whose bit q is query q's.
+    static __device__ __forceinline__ void run(const mxfp8_t *qp, const mxfp4_t *rp, bool qok, bool rok, int dpad, int h, f32x16 &acc) {
+        constexpr int U = 4, MAX_SC = 2048 / 128;
+        const uint32_t *qsp = (const uint32_t *)(qp + dpad), *rsp = (const uint32_t *)(rp + (dpad >> 1));
+        uint32_t qs[MAX_SC], rs[MAX_SC];
+#pragma unroll
+        for (int j = 0; j < MAX_SC; ++j) {
+            const bool in = 128 * j < dpad;
+            qs[j] = qok && in ? qsp[j] : 0u;
+            rs[j] = rok && in ? rsp[j] : 0u;
+        }
+        const bool rbad = (rs[0] & 0xffu) == 0xffu;
+        const uint32_t qbad = (uint32_t)__ballot(h == 0 && (qs[0] & 0xffu) == 0xffu);  // (bit col: lane (col, 0)'s query)
+#pragma unroll
+        for (int j = 0; j < MAX_SC; ++j) { qs[j] >>= 8 * h; rs[j] >>= 8 * h; }
+        const i32x4 z = {};
+#pragma unroll
+        for (int g = 0; g < MAX_SC / 2; ++g) {
+            if (256 * g >= dpad) break;                          // (wave-uniform)
+            i32x4 a[U][2], b[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const bool in = 256 * g + 64 * u < dpad;
+                const mxfp8_t *qk = qp + 256 * g + 64 * u + 16 * h;
+                a[u][0] = qok && in ? *(const i32x4 *)qk : z;
+                a[u][1] = qok && in ? *(const i32x4 *)(qk + 32) : z;
+                b[u] = rok && in ? *(const i32x4 *)(rp + 128 * g + 32 * u + 16 * h) : z;
+            }
+            // (the opsel is an immediate of the instruction: a compile-time loop)
+            static_for<U>([&](auto uc) __attribute__((always_inline)) {
+                constexpr int u = decltype(uc)::value;
+                if (256 * g + 64 * u < dpad) {
+                    const i32x8 av = {a[u][0][0], a[u][0][1], a[u][0][2], a[u][0][3], a[u][1][0], a[u][1][1], a[u][1][2], a[u][1][3]};
+                    const i32x8 bv = {b[u][0], b[u][1], b[u][2], b[u][3], 0, 0, 0, 0};
+                    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 0, 4, 2 * (u & 1), (int)qs[2 * g + (u >> 1)],
+                                                                          2 * (u & 1), (int)rs[2 * g + (u >> 1)]);
+                }
+            });
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (rbad || ((qbad >> ((r & 3) + 8 * (r >> 2) + 4 * h)) & 1u)) acc[r] = __builtin_nanf("");
+    }
+};
+
 // LDS: float scores [nqv][L], int ids [nqv][L], int count [nqv] — per query the current top-k in [0, k), the queue behind
 // The selection is written out here, not taken from topk_select.h's helpers: with them this kernel measured slower.
 // The protocol and its barrier contract are the ones stated there.
@@ -248,7 +344,7 @@ __global__ __launch_bounds__(NT) void index_topk_kernel(TopkArgs a) {
     __syncthreads();
 
     const bool qok = col < nqv;
-    const QE *qp = (const QE *)a.queries + (size_t)(q0 + (qok ? col : 0)) * a.dpad;
+    const QE *qp = F::query_ptr(a.queries, (size_t)(q0 + (qok ? col : 0)), a.dpad);
     // a step pushes at most STEP_ROWS entries per query: sort before a queue could hold fewer free slots
     const int room = L - k - STEP_ROWS;
     for (int base = r0; base < r1; base += STEP_ROWS) {
@@ -365,7 +461,7 @@ __global__ __launch_bounds__(NT) void index_rescore_kernel(RescoreArgs a) {
     float s = -INFINITY;
     if (__any(rok)) {                                          // (wave-uniform)
         const bool qok = col == 0;
-        const QE *qp = (const QE *)a.queries + (size_t)q * a.dpad;
+        const QE *qp = F::query_ptr(a.queries, (size_t)q, a.dpad);
         const T *rp = F::row_ptr(a.rows, (size_t)(rok ? id : 0), a.dpad);
         const float rs = F::RSCALE && rok ? a.rscale[id] : 0.f;
         typename F::acc_t dot = {};
@@ -400,7 +496,7 @@ __global__ __launch_bounds__(NT) void index_scores_kernel(ScoresArgs a) {
         qs[r] = F::QSCALE && q < nqv ? a.qscale[q0 + q] : 0.f;
     }
     const bool qok = col < nqv;
-    const QE *qp = (const QE *)a.queries + (size_t)(q0 + (qok ? col : 0)) * a.dpad;
+    const QE *qp = F::query_ptr(a.queries, (size_t)(q0 + (qok ? col : 0)), a.dpad);
     for (int base = r0; base < r1; base += STEP_ROWS) {
         const int blk = __builtin_amdgcn_readfirstlane(base + wave * 32);
         if (blk >= r1) continue;                               // (the whole wave)
@@ -471,7 +567,7 @@ __global__ __launch_bounds__(NT) void index_probe_kernel(ProbeArgs a) {
         select_store_empty(a.ws_s, a.ws_i, out, k, tid);
         return;
     }
-    const QE *qp = (const QE *)a.queries + (size_t)q * a.dpad;
+    const QE *qp = F::query_ptr(a.queries, (size_t)q, a.dpad);
     const float qs = F::QSCALE ? a.qscale[q] : 0.f;
     select_init(sel, 1, tid);
     float ts = -INFINITY;
@@ -535,7 +631,7 @@ __global__ __launch_bounds__(256) void index_export_kernel(ExportArgs a) {
         const size_t r = i / a.dim;
         const int c = (int)(i - r * a.dim);
         const size_t row = a.ids ? (size_t)a.ids[r] : (size_t)a.first + r;
-        a.out[i] = F::element(F::row_ptr(a.rows, row, a.dpad), F::RSCALE ? a.rscale[row] : 0.f, c);
+        a.out[i] = F::element(F::row_ptr(a.rows, row, a.dpad), F::RSCALE ? a.rscale[row] : 0.f, c, a.dpad);
     }
 }
 
@@ -561,7 +657,7 @@ __global__ __launch_bounds__(NT) void kmeans_update_kernel(KmeansArgs a) {
         const float rs = F::RSCALE ? a.rscale[row] : 0.f;
 #pragma unroll
         for (int j = 0; j < EPL; ++j)
-            if (64 * j + lane < dim) acc[j] += F::element(rp, rs, 64 * j + lane);
+            if (64 * j + lane < dim) acc[j] += F::element(rp, rs, 64 * j + lane, a.dpad);
     }
 #pragma unroll
     for (int j = 0; j < EPL; ++j)
@@ -618,6 +714,75 @@ __global__ __launch_bounds__(256) void index_pack_b1_kernel(const float *__restr
     }
 }
 
+// The magnitude bits of the e2m1 / e4m3 code nearest to a >= 0, ties to the even code, clamped to the largest (6 / 448): plain
+// compares against the seven midpoints of e2m1's grid; for e4m3 the f32's mantissa rounded to three bits in integers (a carry
+// runs into the exponent, as it should), and below the least normal 2^-6 the multiples of 2^-9 (8 of them is that normal's code).
+__device__ __forceinline__ uint32_t e2m1_code(float a) {
+    return (uint32_t)(a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) + (a >= 3.5f) + (a > 5.f);
+}
+__device__ __forceinline__ uint32_t e4m3_code(float a) {
+    if (a < 0x1p-6f) return (uint32_t)__builtin_rintf(a * 512.f);
+    uint32_t b = __builtin_bit_cast(uint32_t, a);
+    b += 0x7ffffu + ((b >> 20) & 1u);
+    return min((b >> 20) - ((127u - 7u) << 3), 0x7eu);
+}
+
+// f32 rows [n][dim] -> the mxfp4 form (FP8 false: added rows) or the mxfp8 form (queries), both stated in include/bert_hip.h.
+// One wave per row, a lane the 8 consecutive elements from 512 p + 8 lane of pass p (four passes reach dim 2048; the row stays in
+// registers between the finite test and the codes).  Four lanes are one block of 32: its amax meets in two DPP steps, and with
+// E the amax's f32 exponent field, e = max(E - 127 - EMAX, -127) (E = 0, a subnormal amax, ends at -127 as floor(log2) would; no
+// amax reaches +127), 0 for a zero block.  x * 2^-e is exact in f32 unless it falls below 2^-126, far under the first midpoint.  A lane
+// writes one dword of e2m1 codes or two of e4m3 codes, the block's first lane the scale byte, and the row's last lanes its padding.
+template <bool FP8>
+__global__ __launch_bounds__(256) void index_quantize_mx_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, int n, int dim, int dpad) {
+    constexpr int EMAX = FP8 ? 8 : 2, PASSES = 2048 / 512;
+    const int lane = threadIdx.x & 63;
+    const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= (size_t)n) return;                                // (the whole wave)
+    const float *x = src + r * dim;
+    const int code_bytes = FP8 ? dpad : dpad >> 1;
+    const size_t row_bytes = mx_row_bytes(code_bytes, dpad);
+    uint8_t *out = dst + r * row_bytes;
+    float v[PASSES][8];
+    int bad = 0;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = 512 * p + 8 * lane + j;
+            v[p][j] = c < dim ? x[c] : 0.f;
+            bad |= !__builtin_isfinite(v[p][j]);
+        }
+    bad = __any(bad);
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        if (512 * p >= dpad) break;                            // (wave-uniform)
+        const int c0 = 512 * p + 8 * lane;
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[p][j]));
+        amax = quad_max_f32(amax);                             // (lanes 4 b .. 4 b + 3: block b of the pass, whole or beyond dpad)
+        const int E = (int)(__builtin_bit_cast(uint32_t, amax) >> 23);
+        const int e = amax == 0.f ? 0 : max(E - 127 - EMAX, -127);
+        const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);      // 2^-e, a normal: e is -127 .. 125
+        uint32_t w[2] = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float y = v[p][j] * inv;
+            const uint32_t sign = __builtin_bit_cast(uint32_t, y) >> 31;
+            if constexpr (FP8) w[j >> 2] |= (sign << 7 | e4m3_code(fabsf(y))) << (8 * (j & 3));
+            else w[0] |= (sign << 3 | e2m1_code(fabsf(y))) << (4 * j);
+        }
+        if (bad) w[0] = w[1] = 0u;
+        if (c0 < dpad) {
+            if constexpr (FP8) *(uint2 *)(out + c0) = make_uint2(w[0], w[1]);
+            else *(uint32_t *)(out + (c0 >> 1)) = w[0];
+            if ((lane & 3) == 0) out[code_bytes + (c0 >> 5)] = bad ? (uint8_t)0xff : (uint8_t)(e + 127);
+        }
+    }
+    for (size_t i = (size_t)code_bytes + (dpad >> 5) + lane; i < row_bytes; i += 64) out[i] = 0;
+}
+
 // Compaction: row i of dst (row_bytes, a multiple of 16) = row old_ids[i] of src, and the i8 scale with it (sscale null for
 // the other forms).  One thread per 16-byte piece.
 __global__ __launch_bounds__(256) void index_gather_kernel(const i32x4 *__restrict__ src, i32x4 *__restrict__ dst,
@@ -649,6 +814,7 @@ __global__ __launch_bounds__(256) void live_set_range_kernel(uint32_t *__restric
 // f(ScoreBlock<T>{}) for the T of dtype
 template <class Fn> void dispatch(int dtype, Fn &&f) {
     switch (dtype) {
+    case 4: return f(ScoreBlock<mxfp4_t>{});
     case 3: return f(ScoreBlock<b1_t>{});
     case 2: return f(ScoreBlock<int8_t>{});
     case 1: return f(ScoreBlock<half_t>{});
@@ -666,7 +832,7 @@ void search_kernels_init() {
     // (128 KiB of LDS, beyond the 64 KiB a launch gets unasked; a launch that still cannot have it fails, and the search
     // reports the launch error)
     const int lds_max = QT * 512 * 8 + QT * 4;
-    for (int dtype = 0; dtype < 4; ++dtype)
+    for (int dtype = 0; dtype < 5; ++dtype)
         dispatch(dtype, [&](auto form) {
             using T = decltype(row_type(form));
             (void)hipFuncSetAttribute((const void *)index_topk_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
@@ -728,6 +894,8 @@ void launch_kmeans_update(int dtype, const KmeansArgs &a, hipStream_t s) {
 void launch_ingest(int dtype, const float *src, void *dst, float *scales, int n, int dim, int dpad, hipStream_t s) {
     const int blocks = (int)std::min<size_t>(((size_t)n * dpad + 255) / 256, 8192);
     switch (dtype) {
+    case QFORM_MXFP8: BERT_LAUNCH(index_quantize_mx_kernel<true>, dim3((n + 3) / 4), dim3(256), 0, s, src, (uint8_t *)dst, n, dim, dpad); break;
+    case 4: BERT_LAUNCH(index_quantize_mx_kernel<false>, dim3((n + 3) / 4), dim3(256), 0, s, src, (uint8_t *)dst, n, dim, dpad); break;
     case 3: BERT_LAUNCH(index_pack_b1_kernel, dim3((n + 3) / 4), dim3(256), 0, s, src, (uint32_t *)dst, n, dim, dpad); break;
     case 2: BERT_LAUNCH(index_quantize_kernel, dim3((n + 3) / 4), dim3(256), 0, s, src, (int8_t *)dst, scales, n, dim, dpad); break;
     case 1: BERT_LAUNCH(index_convert_kernel<half_t>, dim3(blocks), dim3(256), 0, s, src, (half_t *)dst, n, dim, dpad); break;

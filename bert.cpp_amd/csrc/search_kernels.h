@@ -1,6 +1,6 @@
 // search_kernels.h — the device code of the embedding index (search.hip) as its host side (index.cpp) sees it: the argument
 // blocks, the tile constants a search is planned with, and one launcher per kernel.  dtype is the index's: 0 f32, 1 f16, 2 i8,
-// 3 b1 (search.hip states the forms).  A launcher only enqueues: the caller reads hipGetLastError.
+// 3 b1, 4 mxfp4 (search.hip states the forms).  A launcher only enqueues: the caller reads hipGetLastError.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "index_file.h"
 #include "live_bits.h"
 
 namespace bert_hip {
@@ -30,7 +31,8 @@ inline SliceCut slice_cut(int n, int s, int step) {
 // index_topk_kernel.  LDS (lds bytes of launch_topk): float scores [min(QT, nq)][L], int ids the same, int count [QT]; L = index_topk_L(k)
 inline int index_topk_L(int k) { return k + STEP_ROWS <= 256 ? 256 : 512; }
 struct TopkArgs {
-    const void *rows, *queries;          // [n_rows][dpad], [nq][dpad] of T (b1: rows of dpad bits, queries of dpad i8 codes)
+    const void *rows, *queries;          // [n_rows][dpad], [nq][dpad] of T (b1: rows of dpad bits, queries of dpad i8 codes;
+                                         // mxfp4: rows and queries of index_row_bytes(4 / QFORM_MXFP8, dpad) bytes)
     float *ws_s;                         // [nq][n_slices][k] per-(query, slice) lists, best first
     int *ws_i;
     int n_rows, dpad, nq, n_qtiles, n_slices, slice_rows, k, L, n_items;
@@ -131,7 +133,7 @@ void launch_mask_and(const uint32_t *a, const uint32_t *b, const uint32_t *c, ui
 void launch_probe(int dtype, const ProbeArgs &a, hipStream_t s);
 void launch_export(int dtype, const ExportArgs &a, hipStream_t s);
 void launch_kmeans_update(int dtype, const KmeansArgs &a, hipStream_t s);
-// f32 rows [n][dim] -> the stored form of dtype, [n][dpad] (scales [n]: i8 only)
+// f32 rows [n][dim] -> the stored form of dtype, [n][dpad] (scales [n]: i8 only); dtype QFORM_MXFP8: the queries of an mxfp4 index
 void launch_ingest(int dtype, const float *src, void *dst, float *scales, int n, int dim, int dpad, hipStream_t s);
 // row i of dst (row_bytes, a multiple of 16) = row old_ids[i] of src, and its scale with it (sscale null: the form has none)
 void launch_gather(const void *src, void *dst, const float *sscale, float *dscale, const int32_t *old_ids, int n, size_t row_bytes, hipStream_t s);

@@ -3,13 +3,13 @@
 // then each line read from stdin is a query whose k closest texts are printed in the reference's format.  'q' or the end
 // of the input quits.  Public C API of include/bert.h + include/bert_hip.h only.
 //
-//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
+//   bert-search -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--mxfp4] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH]
 //               [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N]
 //   bert-search -m MODEL -f TEXTS --late [--i8] [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]
 //   bert-search -m MODEL -f TEXTS --sparse [WIDTH] [--inverted] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]
-//   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--postings] [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]
+//   bert-search -m DENSE -f TEXTS --hybrid SPLADE [--postings] [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--mxfp4] [--f16] [-t THREADS]
 //   (--hybrid SPLADE: hybrid search.  SPLADE is a second model file, one with the MLM head, loaded into a context of its own (it may be
-//   the same file as DENSE).  Every line goes into an embedding index of DENSE (bert_hip_index_add_texts; --f32 / --i8 / --b1 as
+//   the same file as DENSE).  Every line goes into an embedding index of DENSE (bert_hip_index_add_texts; --f32 / --i8 / --b1 / --mxfp4 as
 //   below) and, with its W largest terms (--sparse-width, default 128, 1 .. 256), into a sparse index of SPLADE
 //   (bert_hip_sparse_index_add_texts; --f16: u16 ids and f16 weights).  Each query line is answered by bert_hip_hybrid_search_texts:
 //   the exact top-k of WD * (dense score) + WS * (sparse score) over all lines (--weights, default 1,1; finite numbers), the query's W
@@ -50,7 +50,8 @@
 //   (--long: a line may be longer than the model's position limit: it is cut into overlapping windows of W ids, S inner ids apart,
 //   and embedded as ONE row (bert_hip_index_add_long_texts; W defaults to 128 or the model's limit if that is less, S to three
 //   quarters of W - 2).  Without --long a line is cut at the model's position limit, like a query;
-//   --f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; --b1: one sign bit per element; the
+//   --f32: an f32 index; --i8: an int8 index, one code per element and one scale per row; --b1: one sign bit per element; --mxfp4:
+//   4-bit e2m1 codes and one power-of-two scale per 32 elements (not with --save: the form has no file yet); the
 //   default stores the rows as f16; --rescore N: an int8 index of the same texts is kept beside the index, which only picks N
 //   candidates per query, and the answer is the int8 index's best k of them (bert_hip_index_search_rescored; k <= N <= 256);
 //   --lists N: once the texts are in, the index is partitioned into N lists (bert_hip_index_kmeans, ten iterations from N evenly
@@ -76,10 +77,10 @@
 
 namespace {
 void usage(const char *argv0) {
-    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
+    fprintf(stderr, "usage: %s -m MODEL -f TEXTS [-k 3] [--f32 | --i8 | --b1] [--mxfp4] [--rescore N] [--lists N] [--nprobe P] [-t THREADS] [--save PATH] [--load PATH] [--long [--window W] [--stride S]] [--maxsim N [--token-index] | --cross-model PATH --cross N] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --late [--i8] [-k 3] [-t THREADS] [--save-tokens PATH] [--load-tokens PATH]\n", argv0);
     fprintf(stderr, "       %s -m MODEL -f TEXTS --sparse [WIDTH] [--inverted] [-k 3] [--f16] [-t THREADS] [--save PATH] [--load PATH]\n", argv0);
-    fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--postings] [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--f16] [-t THREADS]\n", argv0);
+    fprintf(stderr, "       %s -m DENSE -f TEXTS --hybrid SPLADE [--postings] [--sparse-width W] [--weights WD,WS] [-k 3] [--f32 | --i8 | --b1] [--mxfp4] [--f16] [-t THREADS]\n", argv0);
     fprintf(stderr, "  --hybrid SPLADE: hybrid search: the lines in an embedding index of DENSE and a sparse index of SPLADE (a model file with the MLM head; W\n"
                     "          terms a line, default 128), each query answered by bert_hip_hybrid_search_texts: the exact top-k of WD * dense + WS * sparse\n"
                     "          (default 1,1).  --postings builds the sparse index's postings and answers through them (the same output).\n"
@@ -131,6 +132,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--f32")) dtype = 0;
         else if (!strcmp(argv[i], "--i8")) dtype = 2;
         else if (!strcmp(argv[i], "--b1")) dtype = 3;
+        else if (!strcmp(argv[i], "--mxfp4")) dtype = 4;
         else if (!strcmp(argv[i], "--rescore") && has_value) n_cand = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--lists") && has_value) n_lists = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--nprobe") && has_value) nprobe = atoi(argv[++i]);
@@ -174,7 +176,7 @@ int main(int argc, char **argv) {
     if (token_i8 && (save_tokens || load_tokens)) { fprintf(stderr, "search: --i8 with a token index does not go with --save-tokens or --load-tokens\n"); return 2; }
     if (late && (maxsim || (dtype != 1 && dtype != 2) || n_cand || n_lists || nprobe || sparse_f16)) { fprintf(stderr, "search: --late goes with -m, -f, -k, -t and --i8 only\n"); return 2; }
     if (hybrid_model && (sparse || n_cand || n_lists || nprobe || long_texts || maxsim || cross || cross_model || save || load)) {
-        fprintf(stderr, "search: --hybrid goes with -m, -f, -k, -t, --sparse-width, --weights, --f32, --i8, --b1 and --f16 only\n");
+        fprintf(stderr, "search: --hybrid goes with -m, -f, -k, -t, --sparse-width, --weights, --f32, --i8, --b1, --mxfp4 and --f16 only\n");
         return 2;
     }
     if (inverted && hybrid_model) { fprintf(stderr, "search: --inverted does not go with --hybrid: a hybrid search over the postings is --hybrid SPLADE --postings\n"); return 2; }
@@ -194,6 +196,7 @@ int main(int argc, char **argv) {
     if (cross != (cross_model != nullptr)) { fprintf(stderr, "search: --cross-model and --cross go together\n"); return 2; }
     if (cross && maxsim) { fprintf(stderr, "search: --cross and --maxsim exclude each other\n"); return 2; }
     if (cross && (n_cross < k || n_cross > 256)) { fprintf(stderr, "search: --cross must be -k .. 256\n"); return 2; }
+    if (dtype == 4 && (save || late || sparse)) { fprintf(stderr, "search: --mxfp4 does not go with --save (the form has no file yet), --late or --sparse\n"); return 2; }
     const int k_print = k;
     if (maxsim) k = n_maxsim;                                 // (what the stages below return; k_print lines come out of the reranking)
     if (cross) k = n_cross;

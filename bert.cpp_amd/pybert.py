@@ -1270,7 +1270,9 @@ class BertModel:
     def index(self, dim: Optional[int] = None, dtype: str = "f16") -> "BertIndex":
         """An embedding index on the context's first device (bert_hip_index_create): dim None = n_embd, dtype "f16" | "f32" |
         "i8" (one int8 code per element and one f32 scale per row) | "b1" (one sign bit per element, searched with int8
-        queries: the coarse stage of BertIndex.search_rescored)."""
+        queries: the coarse stage of BertIndex.search_rescored) | "mxfp4" (OCP MXFP4: 4-bit e2m1 codes and one power-of-two
+        scale per 32 elements, searched with MXFP8 queries on the block-scaled MFMA; a coarse stage that needs tens of
+        candidates where "b1" needs hundreds, or an index of its own; it has no file form yet: save raises)."""
         return BertIndex(self, dim, dtype)
 
     def sparse_index(self, width: int = 128, dtype: str = "f32", n_vocab: Optional[int] = None) -> "BertSparseIndex":
@@ -1314,8 +1316,8 @@ class BertIndex:
     data_ptr()) and a stream handle, and return at once."""
 
     def __init__(self, model: BertModel, dim: Optional[int] = None, dtype: str = "f16", _load: Optional[str] = None):
-        if dtype not in ("f16", "f32", "i8", "b1"):
-            raise ValueError("dtype must be 'f16', 'f32', 'i8' or 'b1'")
+        if dtype not in ("f16", "f32", "i8", "b1", "mxfp4"):
+            raise ValueError("dtype must be 'f16', 'f32', 'i8', 'b1' or 'mxfp4'")
         self.model, self.lib = model, model.lib
         if _load is not None:
             # dim and dtype come from the file's header (include/bert_hip.h: u32 dtype at byte 12, u32 dim at 16)
@@ -1324,9 +1326,10 @@ class BertIndex:
                 raise RuntimeError("bert_hip_index_load failed (see stderr)")
             with open(_load, "rb") as f:
                 head = np.frombuffer(f.read(24), dtype="<u4")
-            self.dtype, self.dim = ("f32", "f16", "i8", "b1")[int(head[3])], int(head[4])
+            # (no file holds an mxfp4 index yet: bert_hip_index_load has refused dtype 4 before this line)
+            self.dtype, self.dim = ("f32", "f16", "i8", "b1", "mxfp4")[int(head[3])], int(head[4])
             return
-        code = {"f16": 1, "i8": 2, "b1": 3}.get(dtype, 0)
+        code = {"f16": 1, "i8": 2, "b1": 3, "mxfp4": 4}.get(dtype, 0)
         self.ix = self.lib.bert_hip_index_create(model.ctx, 0 if dim is None else int(dim), code)
         if not self.ix:
             raise RuntimeError("bert_hip_index_create failed (see stderr)")

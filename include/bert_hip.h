@@ -449,9 +449,10 @@ BERT_API int32_t bert_hip_encode_sparse_batch(struct bert_ctx *ctx, int32_t n_th
  *   create   dim: 0 = bert_n_embd(ctx), else 1 .. 2048.  dtype: 0 = f32 rows, 1 = f16 rows (rounded to nearest even; the
  *            queries are rounded to f16 the same way), 2 = int8 rows with one f32 scale per row (the queries quantized the
  *            same way, on the device; below), 3 = "b1": one sign bit per element and no scale (the queries quantized to int8;
- *            below).  Memory per row: 4 * ceil(dim / 8) * 8 bytes (f32), 2 * ceil(dim / 16) * 16
+ *            below), 4 = "mxfp4": 4-bit e2m1 codes with one power-of-two scale per 32 elements (the queries quantized to MXFP8;
+ *            below; no file form yet).  Memory per row: 4 * ceil(dim / 8) * 8 bytes (f32), 2 * ceil(dim / 16) * 16
  *            (f16), dpad + 4 with dpad = ceil(dim / 32) * 32 (int8), dpad / 8 with dpad = ceil(dim / 128) * 128 (b1: 48 bytes
- *            at dim 384).  NULL + a message on stderr on error (tokenizer-only context, no device, bad arguments).
+ *            at dim 384), dpad / 2 + dpad / 32 rounded up to 16 with dpad = ceil(dim / 64) * 64 (mxfp4: 208 bytes at dim 384).  NULL + a message on stderr on error (tokenizer-only context, no device, bad arguments).
  *   add      appends rows [n][dim] (f32); they get ids size, size + 1, ...; returns the first new id, negative on error
  *            (index unchanged).  add_device: the rows in device memory of the index's device, enqueued on `stream`.
  *            add_texts: encodes the texts (dim must equal n_embd) on the context's devices as bert_hip_encode_batch does; on a
@@ -483,6 +484,22 @@ BERT_API int32_t bert_hip_encode_sparse_batch(struct bert_ctx *ctx, int32_t n_th
  *     is an exact int32 (the padding meets zero codes).  A query holding a NaN or an inf returns only id -1 / -INFINITY slots;
  *     a zero query scores +0 against every row, so the smallest ids win.  Equal scores are common with this form: the order
  *     rule below decides every one.  The same determinism as below holds.  Meant as the coarse stage of search_rescored.
+ *   - MXFP4 (dtype 4, "mxfp4"; asymmetric: OCP MXFP4 rows, MXFP8 queries, scored by v_mfma_scale_f32_32x32x64_f8f6f4): dpad =
+ *     ceil(dim / 64) * 64, the padding elements zero.  A stored row is dpad / 2 code bytes — element i in the low (even i) or high
+ *     (odd i) nibble of byte i >> 1, a code being sign << 3 | e2m1 magnitude —, then dpad / 32 E8M0 scale bytes, one per block of
+ *     32 elements, then zero bytes up to a multiple of 16 (208 bytes at dim 384, 1088 at dim 2048).  Per block: amax = max |x_i|;
+ *     amax == 0: scale byte 127; otherwise e = clamp(floor(log2(amax)) - 2, -127, 127), scale byte e + 127; code_i = x_i * 2^-e
+ *     rounded to the nearest of {0, 0.5, 1, 1.5, 2, 3, 4, 6} (ties to the even code: 0.25 -> 0, 2.5 -> 2, 3.5 -> 4, 5 -> 4), clamped
+ *     to 6, with x_i's sign bit.  A query is quantized per call in the same way to MXFP8: dpad code bytes, sign << 7 | OCP e4m3
+ *     (bias 7, subnormals, largest 448, never a NaN code), e = clamp(floor(log2(amax)) - 8, -127, 127), rounded to nearest even
+ *     and clamped to 448; then dpad / 32 scale bytes, padded to 16.  A row or query holding a NaN or an inf gets zero codes and
+ *     0xFF in every scale byte (no finite input produces that byte): such a row is never returned, such a query returns only
+ *     id -1 / -INFINITY slots — the int8 form's promise.  score = sum over the blocks of 2^(qe + re) * sum_i qcode_i * rcode_i,
+ *     one chain of dpad / 64 scaled MFMAs in ascending k from a zero accumulator; there is no per-row f32 scale.  The products
+ *     are exact; the instruction's sum over its 64 products is narrower than an f32 chain (measured: within 4.5e-5 of
+ *     sum_i |q_i r_i|, 2e-7 on average).  The same determinism as below holds.  Meant as a coarse stage that needs tens of
+ *     candidates, or as an index of its own.  It has NO FILE FORM yet: save returns -3 with a line on stderr and writes nothing,
+ *     the file version and its header check (dtype 0 .. 3) are unchanged, so load never sees such a file.
  *   - order: larger score first; equal scores (==, so +0 equals -0) smaller id first.  Rows with a NaN score are never
  *     returned.  Slots beyond the rows that can be returned are id -1, score -INFINITY.  An empty index is valid.
  *   - 1 <= k <= 256, anything else is an error; n_queries == 0 is a successful no-op; large n_queries run in internal chunks.
@@ -531,7 +548,8 @@ BERT_API int32_t bert_hip_encode_sparse_batch(struct bert_ctx *ctx, int32_t n_th
  *            allocation as for rescore holds (the coarse search's workspace is covered by coarse's reserve with k = n_cand).
  * Reading rows back, cluster partition and probed search:
  *   get_rows  rows[n][dim] = the stored rows ids[0 .. n) as f32, removed rows included: the bits (f32), the exact conversion
- *            (f16), (float)code * scale with one rounding (i8; NaN for a row whose scale is NaN), +1.0 or -1.0 per bit (b1).
+ *            (f16), (float)code * scale with one rounding (i8; NaN for a row whose scale is NaN), +1.0 or -1.0 per bit (b1),
+ *            value(code) * 2^(scale byte - 127), exact in f32 (mxfp4; NaN for a row whose scale bytes are 0xFF).
  *            An id outside [0, size): -2, nothing written.  Blocking.  This is "the row" of partition and kmeans below.
  *   partition   installs centroids[n_lists][dim] (host f32, every element finite or -2; 1 <= n_lists <= 65536; n_lists == 0
  *            drops the partition) and assigns every current row, removed ones included, to one list.  The rule, through

@@ -35,6 +35,14 @@ Section "probe_filter" (not part of the default; the corpus and the partition of
 bert_hip_index_search_probed_filtered_device with allow-lists of density 1.0, 0.1 and 0.01 (rows allowed at random), each as
 median (min .. max) and as a ratio to the unfiltered probed line of the same run.
     python tools/search_rate.py --sections probe_filter --out profiles/search_probe_filter_rate.txt
+
+Section "mxfp4" (not part of the default; 10^6 rows, dims 384 and 768, Q = 1, 64 and 4096, k = 10): the mxfp4, i8 and b1 searches
+and the two-stage searches mxfp4(50) -> f16 and b1(256) -> f16 (256: the most candidates a two-stage search takes) from the same
+run, each as median (min .. max), with the bytes of the rows and the share of the two-stage answers' ids that the plain f16 search
+also returns; then the largest |score - exact| / sum_i |q_i r_i| of an mxfp4 search over 4500 random unit rows and 100 queries
+per dim of tests/test_gpu_search_mxfp4.py, exact being float64 over the decoded operands of tests/mxfp4_reference.py.  mxfp4 rows
+(--dtypes ...,mxfp4 in "search") count dpad / 2 + dpad / 32 bytes padded to 16, dpad = dim rounded up to 64; they have no yardstick.
+    python tools/search_rate.py --sections mxfp4 --out profiles/search_mxfp4_rate.txt
 """
 import argparse
 import os
@@ -48,7 +56,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM = 6.3e12
-PEAK = {"f16": 2.5e15, "f32": 155e12, "i8": 5.0e15, "b1": 5.0e15}
+PEAK = {"f16": 2.5e15, "f32": 155e12, "i8": 5.0e15, "b1": 5.0e15, "mxfp4": 5.0e15}       # (mxfp4: fp8 x fp4 runs at the fp8 rate)
 
 
 def agree(ids, scores, t_ids, t_vals, k, tol):
@@ -154,6 +162,57 @@ def rescore_section(a, m, N, out, timed, torch, dev, sp):
         i8.close()
         del C, Qall
         torch.cuda.empty_cache()
+
+
+def mxfp4_section(a, m, N, out, timed, torch, dev, sp):
+    """the mxfp4 search beside i8 and b1, the two-stage searches into f16 rows, and the scaled MFMA's error ratio"""
+    k = 10
+    out(f"# mxfp4, i8 and b1 searches, mxfp4(50) -> f16 and b1(256) -> f16 two-stage searches, N = {N} rows, k = {k}; ms = median (min .. max) of {a.iters}")
+    out("#  dim     Q  call                    row bytes |      ms (min .. max)        queries/s   ids shared with f16")
+    for dim in (384, 768):
+        g = torch.Generator(device=dev).manual_seed(dim)
+        C = torch.randn(N, dim, device=dev, generator=g)
+        C /= C.norm(dim=1, keepdim=True)
+        Qall = torch.randn(4096, dim, device=dev, generator=g)
+        Qall /= Qall.norm(dim=1, keepdim=True)
+        ixs = {d: m.index(dim=dim, dtype=d) for d in ("mxfp4", "i8", "b1", "f16")}
+        for ix in ixs.values():
+            ix.reserve(N, 4096, 256)
+            ix.add_device(N, C.data_ptr(), sp)
+        nbytes = {"mxfp4": ((dim + 63) // 64 * 64 * 17 // 32 + 15) // 16 * 16, "i8": (dim + 31) // 32 * 32 + 4, "b1": (dim + 127) // 128 * 16}
+        for Q in (1, 64, 4096):
+            q = Qall[:Q].contiguous()
+            ids, sc = torch.empty(Q, k, dtype=torch.int32, device=dev), torch.empty(Q, k, dtype=torch.float32, device=dev)
+            ixs["f16"].search_device(Q, q.data_ptr(), k, ids.data_ptr(), sc.data_ptr(), sp)
+            want = ids.cpu().numpy()
+            calls = [(d + " search", nbytes[d], lambda d=d: ixs[d].search_device(Q, q.data_ptr(), k, ids.data_ptr(), sc.data_ptr(), sp)) for d in ("mxfp4", "i8", "b1")]
+            calls += [(f"{d}({n}) -> f16", nbytes[d], lambda d=d, n=n: ixs[d].search_rescored_device(ixs["f16"], Q, q.data_ptr(), n, k, ids.data_ptr(), sc.data_ptr(), sp))
+                      for d, n in (("mxfp4", 50), ("b1", 256))]
+            for label, nb, f in calls:
+                t, lo, hi = timed(f)
+                got = ids.cpu().numpy()
+                shared = np.mean([len(set(x.tolist()) & set(y.tolist())) / k for x, y in zip(got, want)])
+                out(f"{dim:6d} {Q:5d}  {label:22s} {nb:9d} | {t:8.3f} ({lo:7.3f} .. {hi:7.3f}) {Q / (t * 1e-3):11.0f}   {shared:.3f}")
+        for ix in ixs.values():
+            ix.close()
+        del C, Qall
+        torch.cuda.empty_cache()
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from mxfp4_reference import mxfp4_rows, mxfp8_queries
+    worst = 0.0
+    for dim in (1, 31, 33, 64, 65, 384, 2048):
+        rng = np.random.default_rng(dim)
+        rows, q = (x / np.linalg.norm(x, axis=1, keepdims=True) for x in (rng.standard_normal((4500, dim), dtype=np.float32), rng.standard_normal((100, dim), dtype=np.float32)))
+        ix = m.index(dim=dim, dtype="mxfp4")
+        ix.add(rows)
+        ids, sc = ix.search(q, 100)
+        ix.close()
+        R, Qd = mxfp4_rows(rows).astype(np.float64), mxfp8_queries(q).astype(np.float64)
+        prod = Qd[:, None, :] * R[ids]                                   # [Q, k, dim]
+        ratio = np.abs(sc - prod.sum(axis=2)) / np.maximum(np.abs(prod).sum(axis=2), 1e-300)
+        out(f"# mxfp4 dim {dim:4d}: largest |score - exact| / sum |q_i r_i| over 100 queries x top-100 of 4500 rows: {ratio.max():.3e}")
+        worst = max(worst, float(ratio.max()))
+    out(f"# mxfp4: largest error ratio over the dims: {worst:.3e} (an f32 chain of exact products stays within 2e-6)")
 
 
 def probe_section(a, m, N, out, timed, torch, dev, sp):
@@ -341,16 +400,17 @@ def main():
 
                     t, t_lo, t_hi = timed(call)
                     ty, ok = float("nan"), None
-                    if not a.no_yardstick:
+                    if not a.no_yardstick and dtype != "mxfp4":
                         ty = timed(yard)[0]
                         tv, ti = yard()
                         torch.cuda.synchronize()
                         nq = min(Q, 64)
                         ok = agree(ids[:nq].cpu().numpy(), sc[:nq].cpu().numpy(), ti[:nq].cpu().numpy(), tv[:nq].cpu().numpy(), k, 1e-3)
-                    es = {"f16": 2, "f32": 4, "i8": 1, "b1": 0.125}[dtype]
-                    step = {"f16": 16, "f32": 8, "i8": 32, "b1": 128}[dtype]
+                    es = {"f16": 2, "f32": 4, "i8": 1, "b1": 0.125, "mxfp4": 0}[dtype]               # (mxfp4: row_bytes below)
+                    step = {"f16": 16, "f32": 8, "i8": 32, "b1": 128, "mxfp4": 64}[dtype]
                     dpad = (dim + step - 1) // step * step
-                    nbytes = N * (int(dpad * es) + (4 if dtype == "i8" else 0)) + Q * dim * 4 + Q * k * 8
+                    row_bytes = (dpad * 17 // 32 + 15) // 16 * 16 if dtype == "mxfp4" else int(dpad * es) + (4 if dtype == "i8" else 0)
+                    nbytes = N * row_bytes + Q * dim * 4 + Q * k * 8
                     flops = 2.0 * Q * N * dim
                     tb, tf = nbytes / HBM, flops / PEAK[dtype]
                     bound, share = ("HBM", tb / (t * 1e-3)) if tb >= tf else ("MFMA", tf / (t * 1e-3))
@@ -366,6 +426,9 @@ def main():
 
     if "rescore" in sections:
         rescore_section(a, m, N, out, timed, torch, dev, sp)
+
+    if "mxfp4" in sections:
+        mxfp4_section(a, m, N, out, timed, torch, dev, sp)
 
     if "probe" in sections:
         probe_section(a, m, N, out, timed, torch, dev, sp)
