@@ -1,6 +1,6 @@
 // device.h — the device-side building blocks that more than one kernel file uses (gfx950): vector types, address-space casts,
 // compile-time loops, the in-kernel timeline stamps of the tuning builds, hand-issued LDS reads and the waits around them, the
-// tile swizzle, lane-crossing reductions, the int8 row rule, the softmax numerators, packed GELU, LayerNorm statistics, q4 block expansion and the
+// tile swizzle, lane-crossing reductions, the int8 and MX row rules, the softmax numerators, packed GELU, LayerNorm statistics, q4 block expansion and the
 // per-lane LayerNorm of the fused kernels.  Host code includes kernels.h only.
 //
 // The kernels that stream weight tiles through LDS rings (gemm256.hip, layer_tail.hip, qkv_attention2.hip, skinny.hip): 128-row
@@ -26,6 +26,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t i32x8 __attribute__((ext_vector_type(8)));
 typedef int32_t i32x16 __attribute__((ext_vector_type(16)));
 
 // compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N-1>{})
@@ -206,6 +207,73 @@ __device__ __forceinline__ void quantize_row_i8(const T *__restrict__ x, int dim
         }
         *(uint32_t *)(out + c) = packed;
     }
+}
+
+// The magnitude bits of the e2m1 / e4m3 code nearest to a >= 0, ties to the even code, clamped to the largest (6 / 448): plain
+// compares against the seven midpoints of e2m1's grid; for e4m3 the f32's mantissa rounded to three bits in integers (a carry
+// runs into the exponent, as it should), and below the least normal 2^-6 the multiples of 2^-9 (8 of them is that normal's code).
+__device__ __forceinline__ uint32_t e2m1_code(float a) {
+    return (uint32_t)(a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) + (a >= 3.5f) + (a > 5.f);
+}
+__device__ __forceinline__ uint32_t e4m3_code(float a) {
+    if (a < 0x1p-6f) return (uint32_t)__builtin_rintf(a * 512.f);
+    uint32_t b = __builtin_bit_cast(uint32_t, a);
+    b += 0x7ffffu + ((b >> 20) & 1u);
+    return min((b >> 20) - ((127u - 7u) << 3), 0x7eu);
+}
+
+// The MX row rule of the embedding index (search.hip index_quantize_mx_kernel) and the token index (token_index.hip
+// token_mx_quantize_kernel), the whole wave on one row: x[0 .. dim) (f32, or f16 converted exactly) -> the mxfp4 form (FP8 false:
+// stored rows) or the mxfp8 form (queries) at out, mx_row_bytes(code bytes, dpad) bytes, both stated in include/bert_hip.h.
+// A lane holds the 8 consecutive elements from 512 p + 8 lane of pass p (PASSES passes reach dim 512 PASSES; the row stays in
+// registers between the finite test and the codes).  Four lanes are one block of 32: its amax meets in two DPP steps, and with
+// E the amax's f32 exponent field, e = max(E - 127 - EMAX, -127) (E = 0, a subnormal amax, ends at -127 as floor(log2) would; no
+// amax reaches +127), 0 for a zero block.  x * 2^-e is exact in f32 unless it falls below 2^-126, far under the first midpoint.  A lane
+// writes one dword of e2m1 codes or two of e4m3 codes, the block's first lane the scale byte, and the row's last lanes its padding.
+// A row with a NaN or +-inf: every code 0, every scale byte 0xFF.
+template <bool FP8, int PASSES, class T>
+__device__ __forceinline__ void quantize_row_mx(const T *__restrict__ x, int dim, int dpad, uint8_t *__restrict__ out, int lane) {
+    constexpr int EMAX = FP8 ? 8 : 2;
+    const int code_bytes = FP8 ? dpad : dpad >> 1;
+    const size_t row_bytes = mx_row_bytes(code_bytes, dpad);
+    float v[PASSES][8];
+    int bad = 0;
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = 512 * p + 8 * lane + j;
+            v[p][j] = c < dim ? (float)x[c] : 0.f;
+            bad |= !__builtin_isfinite(v[p][j]);
+        }
+    bad = __any(bad);
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        if (512 * p >= dpad) break;                            // (wave-uniform)
+        const int c0 = 512 * p + 8 * lane;
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[p][j]));
+        amax = quad_max_f32(amax);                             // (lanes 4 b .. 4 b + 3: block b of the pass, whole or beyond dpad)
+        const int E = (int)(__builtin_bit_cast(uint32_t, amax) >> 23);
+        const int e = amax == 0.f ? 0 : max(E - 127 - EMAX, -127);
+        const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);      // 2^-e, a normal: e is -127 .. 125
+        uint32_t w[2] = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float y = v[p][j] * inv;
+            const uint32_t sign = __builtin_bit_cast(uint32_t, y) >> 31;
+            if constexpr (FP8) w[j >> 2] |= (sign << 7 | e4m3_code(fabsf(y))) << (8 * (j & 3));
+            else w[0] |= (sign << 3 | e2m1_code(fabsf(y))) << (4 * j);
+        }
+        if (bad) w[0] = w[1] = 0u;
+        if (c0 < dpad) {
+            if constexpr (FP8) *(uint2 *)(out + c0) = make_uint2(w[0], w[1]);
+            else *(uint32_t *)(out + (c0 >> 1)) = w[0];
+            if ((lane & 3) == 0) out[code_bytes + (c0 >> 5)] = bad ? (uint8_t)0xff : (uint8_t)(e + 127);
+        }
+    }
+    for (size_t i = (size_t)code_bytes + (dpad >> 5) + lane; i < row_bytes; i += 64) out[i] = 0;
 }
 
 // Softmax numerators of EIGHT scores of one query (registers 8 st .. 8 st + 7 of an S^T tile = the B fragment of one P·V MFMA

@@ -208,6 +208,10 @@ void launch_token_rows(const void *x, bool x_is_f32, int T, int H, const int32_t
 // 0 = that bound.  A pair's bits depend on its own rows alone, so no result depends on the cut.
 constexpr int MAXSIM_MAX_H = 1024;
 constexpr int MAXSIM_LAUNCH_PAIRS = 1 << 23;
+// The MX row of the embedding index's mxfp4 form and the token index's (device.h quantize_row_mx writes it): `code_bytes` code bytes
+// (dpad / 2 of e2m1, dpad of e4m3), one E8M0 scale byte per 32 of dpad elements, zero bytes to whole 16-byte pieces.  Here, not in
+// device.h beside the rule, because the host sides size storage by it.
+__host__ __device__ constexpr size_t mx_row_bytes(int code_bytes, int dpad) { return ((size_t)code_bytes + (dpad >> 5) + 15) & ~(size_t)15; }
 struct MaxsimArgs {
     const half_t *q, *d;
     const int32_t *qcu, *dcu, *pairs;

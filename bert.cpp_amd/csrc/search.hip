@@ -225,11 +225,8 @@ template <> struct ScoreBlock<b1_t> {
 // a stored byte of an mxfp4 row (two e2m1 codes, or one E8M0 scale) / of an mxfp8 query (one e4m3 code, or one scale)
 struct mxfp4_t { uint8_t byte; };
 struct mxfp8_t { uint8_t byte; };
-typedef int32_t i32x8 __attribute__((ext_vector_type(8)));
 
-// bytes of a stored row of `bytes` code bytes and one scale byte per 32 of dpad elements, padded to whole 16-byte pieces
-__host__ __device__ constexpr size_t mx_row_bytes(int code_bytes, int dpad) { return ((size_t)code_bytes + (dpad >> 5) + 15) & ~(size_t)15; }
-
+// (bytes of a stored row: kernels.h mx_row_bytes)
 // the value of an e2m1 code's three magnitude bits: {0, 0.5, 1, 1.5, 2, 3, 4, 6}
 __device__ __forceinline__ float e2m1_value(uint32_t m) {
     const uint32_t ex = m >> 1, mant = m & 1u;
@@ -714,73 +711,15 @@ __global__ __launch_bounds__(256) void index_pack_b1_kernel(const float *__restr
     }
 }
 
-// The magnitude bits of the e2m1 / e4m3 code nearest to a >= 0, ties to the even code, clamped to the largest (6 / 448): plain
-// compares against the seven midpoints of e2m1's grid; for e4m3 the f32's mantissa rounded to three bits in integers (a carry
-// runs into the exponent, as it should), and below the least normal 2^-6 the multiples of 2^-9 (8 of them is that normal's code).
-__device__ __forceinline__ uint32_t e2m1_code(float a) {
-    return (uint32_t)(a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) + (a >= 3.5f) + (a > 5.f);
-}
-__device__ __forceinline__ uint32_t e4m3_code(float a) {
-    if (a < 0x1p-6f) return (uint32_t)__builtin_rintf(a * 512.f);
-    uint32_t b = __builtin_bit_cast(uint32_t, a);
-    b += 0x7ffffu + ((b >> 20) & 1u);
-    return min((b >> 20) - ((127u - 7u) << 3), 0x7eu);
-}
-
 // f32 rows [n][dim] -> the mxfp4 form (FP8 false: added rows) or the mxfp8 form (queries), both stated in include/bert_hip.h.
-// One wave per row, a lane the 8 consecutive elements from 512 p + 8 lane of pass p (four passes reach dim 2048; the row stays in
-// registers between the finite test and the codes).  Four lanes are one block of 32: its amax meets in two DPP steps, and with
-// E the amax's f32 exponent field, e = max(E - 127 - EMAX, -127) (E = 0, a subnormal amax, ends at -127 as floor(log2) would; no
-// amax reaches +127), 0 for a zero block.  x * 2^-e is exact in f32 unless it falls below 2^-126, far under the first midpoint.  A lane
-// writes one dword of e2m1 codes or two of e4m3 codes, the block's first lane the scale byte, and the row's last lanes its padding.
+// One wave per row by device.h's quantize_row_mx, four passes (dim up to 2048) — the rule, the code functions and the lane map are
+// stated there once, for this index and the token index.
 template <bool FP8>
 __global__ __launch_bounds__(256) void index_quantize_mx_kernel(const float *__restrict__ src, uint8_t *__restrict__ dst, int n, int dim, int dpad) {
-    constexpr int EMAX = FP8 ? 8 : 2, PASSES = 2048 / 512;
     const int lane = threadIdx.x & 63;
     const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= (size_t)n) return;                                // (the whole wave)
-    const float *x = src + r * dim;
-    const int code_bytes = FP8 ? dpad : dpad >> 1;
-    const size_t row_bytes = mx_row_bytes(code_bytes, dpad);
-    uint8_t *out = dst + r * row_bytes;
-    float v[PASSES][8];
-    int bad = 0;
-#pragma unroll
-    for (int p = 0; p < PASSES; ++p)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int c = 512 * p + 8 * lane + j;
-            v[p][j] = c < dim ? x[c] : 0.f;
-            bad |= !__builtin_isfinite(v[p][j]);
-        }
-    bad = __any(bad);
-#pragma unroll
-    for (int p = 0; p < PASSES; ++p) {
-        if (512 * p >= dpad) break;                            // (wave-uniform)
-        const int c0 = 512 * p + 8 * lane;
-        float amax = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[p][j]));
-        amax = quad_max_f32(amax);                             // (lanes 4 b .. 4 b + 3: block b of the pass, whole or beyond dpad)
-        const int E = (int)(__builtin_bit_cast(uint32_t, amax) >> 23);
-        const int e = amax == 0.f ? 0 : max(E - 127 - EMAX, -127);
-        const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);      // 2^-e, a normal: e is -127 .. 125
-        uint32_t w[2] = {0u, 0u};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float y = v[p][j] * inv;
-            const uint32_t sign = __builtin_bit_cast(uint32_t, y) >> 31;
-            if constexpr (FP8) w[j >> 2] |= (sign << 7 | e4m3_code(fabsf(y))) << (8 * (j & 3));
-            else w[0] |= (sign << 3 | e2m1_code(fabsf(y))) << (4 * j);
-        }
-        if (bad) w[0] = w[1] = 0u;
-        if (c0 < dpad) {
-            if constexpr (FP8) *(uint2 *)(out + c0) = make_uint2(w[0], w[1]);
-            else *(uint32_t *)(out + (c0 >> 1)) = w[0];
-            if ((lane & 3) == 0) out[code_bytes + (c0 >> 5)] = bad ? (uint8_t)0xff : (uint8_t)(e + 127);
-        }
-    }
-    for (size_t i = (size_t)code_bytes + (dpad >> 5) + lane; i < row_bytes; i += 64) out[i] = 0;
+    quantize_row_mx<FP8, 2048 / 512>(src + r * dim, dim, dpad, dst + r * mx_row_bytes(FP8 ? dpad : dpad >> 1, dpad), lane);
 }
 
 // Compaction: row i of dst (row_bytes, a multiple of 16) = row old_ids[i] of src, and the i8 scale with it (sscale null for

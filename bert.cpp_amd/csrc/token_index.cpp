@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -62,12 +63,12 @@ bool token_cu_ok(const int32_t *cu, int n) {
 TokenIndex *TokenIndex::create(Engine *eng, int dim, int dtype, std::string &err) {
     if (!eng) { err = "no device engine"; return nullptr; }
     if (dim < 8 || dim > MAXSIM_MAX_H || dim % 8) { err = "dim must be a multiple of 8 in 8 .. " + std::to_string(MAXSIM_MAX_H); return nullptr; }
-    if (dtype != 1 && dtype != 2) { err = "dtype must be 1 (f16) or 2 (int8)"; return nullptr; }
+    if (dtype != 1 && dtype != 2 && dtype != 4) { err = "dtype must be 1 (f16), 2 (int8) or 4 (mxfp4)"; return nullptr; }
     DeviceGuard g(eng->device());
     TokenIndex *ix = new TokenIndex;
     ix->dim_ = dim;
     ix->dtype_ = dtype;
-    ix->dpad_ = token_i8_dpad(dim);
+    ix->dpad_ = dtype == 4 ? token_mx_dpad(dim) : token_i8_dpad(dim);
     ix->cu_h_.assign(1, 0);
     if (!ix->open(eng, "token index", err)) { delete ix; return nullptr; }
     // (cu[0] = 0 is there from the start: an empty index is searched like any other)
@@ -148,10 +149,16 @@ bool TokenIndex::grow_search(int n_docs, int nqc, int k, std::string &err) {
 
 bool TokenIndex::grow_queries(int nqc, int max_q_len, std::string &err) {
     const size_t slots = (size_t)nqc * max_q_len;
+    if (dtype_ == 4) return grow(q_codes_, slots * token_mx_query_bytes(dim_), err);
     return grow(q_codes_, slots * dpad_, err) && grow(q_scales_, slots * 4, err);
 }
 
 void TokenIndex::quantize_rows(const void *d_src, bool src_f32, long long n, long long at, hipStream_t s) {
+    if (dtype_ == 4) {
+        TokenMxQuantizeArgs qa{d_src, (uint8_t *)rows_ + (size_t)at * row_bytes(), n, dim_, dpad_};
+        eng_->timed_launch("token_mx_quantize", 0.0, s, [&] { launch_token_mx_quantize(qa, src_f32, false, s); });
+        return;
+    }
     TokenI8QuantizeArgs qa{d_src, (int8_t *)rows_ + (size_t)at * dpad_, scales_ + at, n, dim_, dpad_};
     eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, src_f32, s); });
 }
@@ -165,7 +172,7 @@ int TokenIndex::reserve(int n_docs, int64_t n_tokens, int n_queries, int max_q_l
     if (!grow_storage(n_docs, n_tokens, err)) return -3;
     const int nqc = std::min(n_queries, QCHUNK);
     if (nqc == 0) return 0;
-    if (dtype_ == 2 && !grow_queries(nqc, max_q_len, err)) return -3;
+    if (quantised() && !grow_queries(nqc, max_q_len, err)) return -3;
     return grow_search(std::max(n_docs, n_), nqc, k, err) ? 0 : -3;
 }
 
@@ -197,7 +204,7 @@ int TokenIndex::add_device(int n_docs, const int32_t *cu, const half_t *d_rows, 
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
     const long long T = (long long)cu[n_docs] - cu[0];
     if (!grow_storage((long long)n_ + n_docs, n_tok_ + T, err)) return -3;
-    if (dtype_ == 2) {
+    if (quantised()) {
         quantize_rows(d_rows + (size_t)cu[0] * dim_, false, T, n_tok_, s);
         HIP_OK(hipGetLastError(), err, -3);
     } else {
@@ -223,7 +230,7 @@ int TokenIndex::add_host(int n_docs, const int32_t *cu, const float *rows, std::
     for (long long t0 = 0; t0 < T; t0 += per) {
         const size_t c = (size_t)std::min(per, T - t0);
         bool ok = hipMemcpyAsync(stage_.p, rows + (size_t)(cu[0] + t0) * dim_, c * dim_ * 4, hipMemcpyHostToDevice, stream_) == hipSuccess;
-        if (ok && dtype_ == 2) quantize_rows(stage_.p, true, (long long)c, n_tok_ + t0, stream_);
+        if (ok && quantised()) quantize_rows(stage_.p, true, (long long)c, n_tok_ + t0, stream_);
         else if (ok) eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), (half_t *)rows_ + (size_t)(n_tok_ + t0) * dim_, c * dim_, stream_); });
         ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(stream_) == hipSuccess;
         if (!ok) { (void)hipStreamSynchronize(stream_); err = "add: copy to the device failed"; return -3; }
@@ -238,7 +245,7 @@ int TokenIndex::add_host(int n_docs, const int32_t *cu, const float *rows, std::
 half_t *TokenIndex::append_room(int64_t n_tokens, std::string &err) {
     if (n_tokens < 0 || n_tok_ + n_tokens > INT_MAX) { err = "add: an index holds fewer than 2^31 tokens"; return nullptr; }
     if (!grow_storage(n_, n_tok_ + n_tokens, err)) return nullptr;
-    if (dtype_ == 2) return grow(text_rows_, std::max<size_t>((size_t)n_tokens * dim_ * 2, 16), err) ? text_rows_.as<half_t>() : nullptr;
+    if (quantised()) return grow(text_rows_, std::max<size_t>((size_t)n_tokens * dim_ * 2, 16), err) ? text_rows_.as<half_t>() : nullptr;
     return (half_t *)rows_ + (size_t)n_tok_ * dim_;
 }
 
@@ -250,7 +257,7 @@ int TokenIndex::add_in_place(int n_docs, const int32_t *cu, std::string &err) {
     if (!grow_storage((long long)n_ + n_docs, n_tok_, err)) return -3;
     Engine::StreamOp op;
     if (!eng_->op_begin(stream_, busy_, op, err)) return -3;
-    if (dtype_ == 2) {
+    if (quantised()) {
         // (the chunk's f16 rows wait in append_room's buffer, enqueued on stream() in front of this)
         if ((size_t)cu[n_docs] * dim_ * 2 > text_rows_.bytes) { err = "add: the rows in place do not match the room asked for"; return -2; }
         quantize_rows(text_rows_.p, false, cu[n_docs], n_tok_, stream_);
@@ -285,6 +292,24 @@ int TokenIndex::get_doc(int id, float *rows, int cap_tokens, std::string &err) {
             for (int e = 0; e < dim_; ++e) rows[(size_t)t * dim_ + e] = (float)codes[(size_t)t * dpad_ + e] * sc[(size_t)t];
         return len;
     }
+    if (dtype_ == 4) {
+        // value(code) * 2^(scale byte - 127), exact in f32; NaN for a token whose scale bytes are 0xFF
+        static const float E2M1[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
+        const size_t rb = row_bytes();
+        std::vector<uint8_t> b((size_t)len * rb);
+        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
+        HIP_OK(hipMemcpyAsync(b.data(), rows_ + (size_t)cu_h_[(size_t)id] * rb, b.size(), hipMemcpyDeviceToHost, stream_), err, -3);
+        HIP_OK(hipStreamSynchronize(stream_), err, -3);
+        for (int t = 0; t < len; ++t) {
+            const uint8_t *r = b.data() + (size_t)t * rb;
+            for (int e = 0; e < dim_; ++e) {
+                const unsigned code = (r[e >> 1] >> (4 * (e & 1))) & 0xfu, sc = r[(dpad_ >> 1) + (e >> 5)];
+                const float v = std::ldexp(E2M1[code & 7u], (int)sc - 127);
+                rows[(size_t)t * dim_ + e] = sc == 0xffu ? std::nanf("") : code & 8u ? -v : v;
+            }
+        }
+        return len;
+    }
     std::vector<half_t> h((size_t)len * dim_);
     HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
     HIP_OK(hipMemcpyAsync(h.data(), (const half_t *)rows_ + (size_t)cu_h_[(size_t)id] * dim_, h.size() * 2, hipMemcpyDeviceToHost, stream_), err, -3);
@@ -294,6 +319,7 @@ int TokenIndex::get_doc(int id, float *rows, int cap_tokens, std::string &err) {
 }
 
 int TokenIndex::get_codes(int id, int8_t *codes, float *scales, int cap_tokens, std::string &err) {
+    if (dtype_ == 4) { err = "get_codes: the index holds mxfp4 rows (dtype 4), not int8 codes"; return -2; }
     if (dtype_ != 2) { err = "get_codes: the index holds f16 rows (dtype 1), not int8 codes"; return -2; }
     if (id < 0 || id >= n_) { err = "get_codes: id " + std::to_string(id) + " outside [0, " + std::to_string(n_) + ")"; return -2; }
     const int t0 = cu_h_[(size_t)id], len = cu_h_[(size_t)id + 1] - t0;
@@ -328,14 +354,14 @@ int TokenIndex::search_any(int nq, const int32_t *d_qcu, const void *d_q, bool q
 // n_cand in the documents' place — and tests live_ per id.  The workspace [nq][slices][k] grows by the same bound over either count
 int TokenIndex::scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *d_ids, float *d_scores,
                             hipStream_t s, std::string &err, const uint32_t *d_allow, const int32_t *d_cand, int n_cand) {
-    const bool i8 = dtype_ == 2;
+    const bool i8 = dtype_ == 2, mx = dtype_ == 4;
     const int n_list = d_cand ? n_cand : n_;
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
     const int nqc = std::min(nq, QCHUNK), pref = eng_->options().token_index_slices;
     if (!grow_search(n_list, nqc, k, err)) return -3;
-    if (i8 && !grow_queries(nqc, max_q_len, err)) return -3;
+    if (quantised() && !grow_queries(nqc, max_q_len, err)) return -3;
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
         TokenScanPlan p;
@@ -349,11 +375,17 @@ int TokenIndex::scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool 
             eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, q_f32, s); });
             a.scales = scales_; a.q = q_codes_.p; a.q_scales = q_scales_.as<float>();
         }
+        if (mx) {
+            TokenMxQuantizeArgs qa{d_q, q_codes_.as<uint8_t>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
+            eng_->timed_launch("token_mx_quantize", 0.0, s, [&] { launch_token_mx_quantize(qa, q_f32, true, s); });
+            a.q = q_codes_.p;
+        }
         // (removed documents or an allow-list: the masked kernel, the same plan and workspace; an empty index has no words to read)
         if (d_cand) { a.live = live_; a.cand = d_cand + (size_t)c0 * n_cand; a.n_cand = n_cand; }
         else if (n_ > 0) { a.live = live_; a.allow = d_allow; }
         const bool masked = a.live || a.allow;
-        const char *label = d_cand ? "token_i8_rescore" : i8 ? (masked ? "token_i8_scan_masked" : "token_i8_scan") : (masked ? "token_index_scan_masked" : "token_index_scan");
+        const char *label = mx ? (d_cand ? "token_mxfp4_rescore" : masked ? "token_mxfp4_scan_masked" : "token_mxfp4_scan")
+                            : d_cand ? "token_i8_rescore" : i8 ? (masked ? "token_i8_scan_masked" : "token_i8_scan") : (masked ? "token_index_scan_masked" : "token_index_scan");
         eng_->timed_launch(label, 0.0, s, [&] { launch_token_scan(dtype_, a, s); });
         enqueue_merge(c, p.n_slices * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
@@ -389,15 +421,15 @@ int TokenIndex::stage_queries(const char *what, int nq, const int32_t *qcu, cons
     }
     const size_t T = (size_t)(qcu[nq] - qcu[0]), n = T * dim_;
     if (n > F32_TO_F16_MAX_N) { err = std::string(what) + ": more than 2^31 query values (tokens x dim) in one call"; return -2; }
-    if (!grow(stage_, n * 4, err) || (dtype_ != 2 && !grow(q16_, n * 2, err)) || !grow(qcu_in_, (size_t)(nq + 1) * 4, err)) return -3;
+    if (!grow(stage_, n * 4, err) || (!quantised() && !grow(q16_, n * 2, err)) || !grow(qcu_in_, (size_t)(nq + 1) * 4, err)) return -3;
     // (the previous host call has synchronised stream(): nothing reads the staged lengths any more)
     qcu_h_.resize((size_t)nq + 1);
     for (int i = 0; i <= nq; ++i) qcu_h_[i] = qcu[i] - qcu[0];
     HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
     HIP_OK(hipMemcpyAsync(stage_.p, q_rows + (size_t)qcu[0] * dim_, n * 4, hipMemcpyHostToDevice, stream_), err, -3);
     HIP_OK(hipMemcpyAsync(qcu_in_.p, qcu_h_.data(), qcu_h_.size() * 4, hipMemcpyHostToDevice, stream_), err, -3);
-    // (the int8 form quantises the f32 rows where they are)
-    if (dtype_ != 2) eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), q16_.as<half_t>(), n, stream_); });
+    // (the int8 and mxfp4 forms quantise the f32 rows where they are)
+    if (!quantised()) eng_->timed_launch("f32_to_f16", 0.0, stream_, [&] { launch_f32_to_f16(stage_.as<float>(), q16_.as<half_t>(), n, stream_); });
     HIP_OK(hipGetLastError(), err, -3);
     return 0;
 }
@@ -410,7 +442,7 @@ int TokenIndex::search_host(int nq, const int32_t *qcu, const float *q_rows, int
     if (const int r = stage_queries("search", nq, qcu, q_rows, max_query_tokens(), max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
     const uint32_t *d_allow = nullptr;
     if (!upload_allow(allow, stream_, d_allow, err)) { (void)hipStreamSynchronize(stream_); return -3; }
-    return search_to_host(nq, qcu_in_.as<int32_t>(), dtype_ == 2 ? stage_.p : q16_.p, dtype_ == 2, max_len, k, ids, scores, err, d_allow);
+    return search_to_host(nq, qcu_in_.as<int32_t>(), quantised() ? stage_.p : q16_.p, quantised(), max_len, k, ids, scores, err, d_allow);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -422,7 +454,7 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
     if ((uintptr_t)d_q & 15) { err = "rescore: the query rows must be 16-byte aligned"; return -2; }
     // (the int8 form: the scan's kernel over the candidate lists; the device form knows no query length, so the launch is sized for the
     // longest a search takes)
-    if (dtype_ == 2) return scan_chunks(nq, d_qcu, d_q, false, max_query_tokens(), k, d_ids, d_scores, s, err, nullptr, d_cand, n_cand);
+    if (quantised()) return scan_chunks(nq, d_qcu, d_q, false, max_query_tokens(), k, d_ids, d_scores, s, err, nullptr, d_cand, n_cand);
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
@@ -449,10 +481,10 @@ int TokenIndex::rescore_host(int nq, const int32_t *qcu, const float *q_rows, in
     DeviceGuard g(eng_->device());
     if (!grow(cand_in_, (size_t)nq * n_cand * 4, err) || !grow(out_ids_, (size_t)nq * k * 4, err) || !grow(out_scores_, (size_t)nq * k * 4, err)) return -3;
     int max_len = 0;
-    if (const int r = stage_queries("rescore", nq, qcu, q_rows, dtype_ == 2 ? max_query_tokens() : 0, max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
+    if (const int r = stage_queries("rescore", nq, qcu, q_rows, quantised() ? max_query_tokens() : 0, max_len, err); r != 0) { (void)hipStreamSynchronize(stream_); return r; }
     auto fail = [&](int r) { (void)hipStreamSynchronize(stream_); return r; };
     if (hipMemcpyAsync(cand_in_.p, cand, (size_t)nq * n_cand * 4, hipMemcpyHostToDevice, stream_) != hipSuccess) { err = "rescore: copy to the device failed"; return fail(-3); }
-    if (const int r = dtype_ == 2 ? scan_chunks(nq, qcu_in_.as<int32_t>(), stage_.p, true, max_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err,
+    if (const int r = quantised() ? scan_chunks(nq, qcu_in_.as<int32_t>(), stage_.p, true, max_len, k, out_ids_.as<int32_t>(), out_scores_.as<float>(), stream_, err,
                                                 nullptr, cand_in_.as<int32_t>(), n_cand)
                                   : rescore_device(nq, qcu_in_.as<int32_t>(), q16_.as<half_t>(), n_cand, cand_in_.as<int32_t>(), k, out_ids_.as<int32_t>(),
                                                    out_scores_.as<float>(), stream_, err); r != 0) return fail(r);
@@ -472,6 +504,7 @@ int TokenIndex::remove(int n, const int32_t *ids, std::string &err) {
 
 int TokenIndex::compact(int32_t *old_ids, std::string &err) {
     if (dtype_ == 2) { err = "compact: not available for an int8 token index"; return -2; }
+    if (dtype_ == 4) { err = "compact: not available for an mxfp4 token index"; return -2; }
     DeviceGuard g(eng_->device());
     HIP_OK(hipEventSynchronize(busy_), err, -3);
     HIP_OK(hipStreamSynchronize(stream_), err, -3);

@@ -12,6 +12,9 @@
 // quantises on the device, a search quantises its queries into a workspace that reserve sizes and scans with token_index_scan_kernel's
 // int8 form, and a rescore is the same kernel over the candidate lists instead of maxsim.  The bitmap, the event, the streams, the
 // chunk loop, commit and the host mirrors are the f16 form's.  compact, save and load are the f16 form's alone.
+// dtype 4, the mxfp4 form (token_index_kernels.h states it): rows are the embedding index's mxfp4 rows, per token, scales inside; the
+// adds, the queries' workspace (MXFP8 rows) and the rescore go the int8 form's ways through token_mx_quantize_kernel and the scan's
+// mxfp4 form.  No scale array.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,7 +36,7 @@ public:
     static constexpr int QCHUNK = 256;                   // queries per internal pass (workspace bound)
 
     static TokenIndex *create(Engine *eng, int dim, std::string &err) { return create(eng, dim, 1, err); }
-    // dtype: 1 = f16 rows, 2 = int8 codes with per-token scales
+    // dtype: 1 = f16 rows, 2 = int8 codes with per-token scales, 4 = mxfp4 rows (e2m1 codes, an E8M0 scale per 32 elements)
     static TokenIndex *create(Engine *eng, int dim, int dtype, std::string &err);
     ~TokenIndex();
 
@@ -43,8 +46,8 @@ public:
     int64_t n_live_tokens() const { return n_tok_ - tok_removed_; }
     int dim() const { return dim_; }
     int dtype() const { return dtype_; }
-    int dpad() const { return dpad_; }                   // int8 form: the bytes of a stored row
-    // (the int8 form: 128 at every dim, and the limit of a rescore's queries too)
+    int dpad() const { return dpad_; }                   // int8 form: the bytes of a stored row; mxfp4 form: the elements of one
+    // (the int8 and mxfp4 forms: 128 at every dim, and the limit of a rescore's queries too)
     int max_query_tokens() const { return token_max_query_tokens(dim_, dtype_); }
     hipStream_t stream() const { return stream_; }
 
@@ -66,7 +69,7 @@ public:
     // forget the documents behind the first n (an add of several parts that failed part way)
     void truncate(int n);
     // document id's rows as f32 [len][dim] (the stored f16 values converted exactly): its length; writes iff cap_tokens >= it.  Blocking
-    // (the int8 form: (float)code * scale)
+    // (the int8 form: (float)code * scale; the mxfp4 form: value(code) * 2^(scale byte - 127), NaN for a token whose scale bytes are 0xFF)
     int get_doc(int id, float *rows, int cap_tokens, std::string &err);
     // int8 form: the document's codes [len][dpad] and scales [len] as stored: its length; writes iff cap_tokens >= it.  f16 form: -2
     int get_codes(int id, int8_t *codes, float *scales, int cap_tokens, std::string &err);
@@ -112,17 +115,18 @@ private:
     TokenIndex() = default;
     bool grow_storage(long long n_docs, long long n_tokens, std::string &err);
     bool grow_search(int n_docs, int nqc, int k, std::string &err);
-    // int8 form: the queries' codes and scales, [nqc][max_q_len] rows
+    // int8 form: the queries' codes and scales, [nqc][max_q_len] rows; mxfp4 form: their MXFP8 rows
     bool grow_queries(int nqc, int max_q_len, std::string &err);
-    size_t row_bytes() const { return dtype_ == 2 ? (size_t)dpad_ : (size_t)dim_ * 2; }
-    // int8 form: n rows (f32 or f16, device memory) -> codes and scales from stored row `at` on, on s
+    size_t row_bytes() const { return dtype_ == 4 ? token_mx_row_bytes(dim_) : dtype_ == 2 ? (size_t)dpad_ : (size_t)dim_ * 2; }
+    bool quantised() const { return dtype_ != 1; }       // the int8 and mxfp4 forms: adds, queries and rescores through a quantiser
+    // int8 and mxfp4 forms: n rows (f32 or f16, device memory) -> the stored form from stored row `at` on, on s
     void quantize_rows(const void *d_src, bool src_f32, long long n, long long at, hipStream_t s);
     // the searches and rescores behind the public forms: the queries d_q are f16, or (q_f32: the host forms of the int8 index) f32
     int search_any(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
                    std::string &err, const uint32_t *d_allow);
     int search_to_host(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *ids, float *scores, std::string &err,
                        const uint32_t *d_allow);
-    // the chunk loop behind every search (d_cand null: the documents under live_ / d_allow) and the int8 rescore (d_cand [nq][n_cand])
+    // the chunk loop behind every search (d_cand null: the documents under live_ / d_allow) and the int8 / mxfp4 rescore (d_cand [nq][n_cand])
     int scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *d_ids, float *d_scores, hipStream_t s,
                     std::string &err, const uint32_t *d_allow, const int32_t *d_cand, int n_cand);
     // out_ids_ / out_scores_ [nq][k] -> the caller's arrays behind what stream() holds; blocking
@@ -136,7 +140,7 @@ private:
     int dim_ = 0, dtype_ = 1, dpad_ = 0;
     int cap_docs_ = 0;                                  // capacity of cu_ in documents (the documents, n_, and the bitmap: index_frame.h)
     int64_t n_tok_ = 0, cap_tok_ = 0;                   // rows; capacity of rows_ in rows
-    char *rows_ = nullptr;                              // [cap_tok_][row_bytes()]: f16 rows, or int8 codes
+    char *rows_ = nullptr;                              // [cap_tok_][row_bytes()]: f16 rows, int8 codes, or mxfp4 rows
     float *scales_ = nullptr;                           // int8 form: [cap_tok_]
     int32_t *cu_ = nullptr;                             // [cap_docs_ + 1]
     std::vector<int32_t> cu_h_;                         // the host mirror, [n_ + 1]
@@ -145,8 +149,8 @@ private:
     DevBuf pairs_;                                      // a rescore's pair list
     DevBuf stage_, q16_, qcu_in_, cand_in_;             // host routes: f32 rows in, queries, candidates
     DevBuf text_in_, text_out_;                         // text routes
-    DevBuf text_rows_;                                  // int8 form: the f16 rows of an add_texts chunk (append_room)
-    DevBuf q_codes_, q_scales_;                         // int8 form: the quantised queries of a search or rescore
+    DevBuf text_rows_;                                  // int8 and mxfp4 forms: the f16 rows of an add_texts chunk (append_room)
+    DevBuf q_codes_, q_scales_;                         // the quantised queries of a search or rescore (int8: codes, scales; mxfp4: MXFP8 rows)
 };
 
 // cu [n + 1] ascends strictly from an entry >= 0 (no empty entry)

@@ -1,11 +1,12 @@
-// token_index.hip — the device code of the token index (gfx950; bert_hip.h "TOKEN INDEX" and "TOKEN INDEX, int8 form"): documents'
-// token rows in HBM — f16 rows, or int8 codes with one f32 scale per token — and their exact MaxSim top-k search.  The kernels and their
-// launchers (token_index_kernels.h, which states both stored forms); the TokenIndex class that plans and orders them is token_index.cpp
+// token_index.hip — the device code of the token index (gfx950; bert_hip.h "TOKEN INDEX", "TOKEN INDEX, int8 form" and "TOKEN INDEX,
+// MXFP4 form"): documents' token rows in HBM — f16 rows, int8 codes with one f32 scale per token, or MXFP4 rows with their scales inside —
+// and their exact MaxSim top-k search.  The kernels and their launchers (token_index_kernels.h, which states the stored forms); the TokenIndex class that plans and orders them is token_index.cpp
 // (token_index.h).
 //
 //   token_index_scan_kernel<Form, MASKED, LISTED>  ONE skeleton — the work map, the guards, the list, the step mask, the round loop and
-//                   its barriers, the selection, the write-out — stated once; a Form (F16Form, I8Form) holds only how a query is staged in
-//                   LDS and how one document is scored.  Five instantiations: f16 plain and masked; int8 plain, masked and listed.
+//                   its barriers, the selection, the write-out — stated once; a Form (F16Form, I8Form, Mxfp4Form) holds only how a query
+//                   is staged in LDS and how one document is scored.  Eight instantiations: f16 plain and masked; int8 and mxfp4 plain,
+//                   masked and listed.
 //   Skeleton.       One workgroup of four waves per (query, slice of consecutive documents).  The workgroup stages ALL the query's blocks
 //                   of 32 tokens in LDS once (Form::stage).  Then each wave takes whole documents of the slice — first + wave,
 //                   first + wave + 4, ... — and scores each alone (Form::score).  No LDS exchange between waves: a document belongs to
@@ -24,7 +25,7 @@
 //                   all four waves whatever each of them scored; a step whose mask is zero is skipped by the whole workgroup, barriers
 //                   included (the mask is the workgroup's, and nothing was pushed).  A step still pushes at most TOKEN_STEP_DOCS
 //                   entries: L and the room rule are those of the unmasked instantiation, which contains none of this.
-//   LISTED.         A rescore (int8 form only; the f16 form's is maxsim_kernel behind token_index_pairs_kernel): a slice is a range of
+//   LISTED.         A rescore (int8 and mxfp4 forms; the f16 form's is maxsim_kernel behind token_index_pairs_kernel): a slice is a range of
 //                   positions of the query's candidate list, a wave's document id comes from the list; an id outside [0, n_docs) or a
 //                   removed one is no candidate, a repeated id is pushed each time.  One wave still sees a whole document: the search's
 //                   bits by construction.
@@ -52,6 +53,25 @@
 //                   sums in ascending order from +0.
 //     Non-finite.   fmaxf drops a NaN, so a NaN scale is looked for on its own: a document with one (the unsigned maximum of the scales'
 //                   bits is above +inf's) scores nothing and is never pushed; a query with one gets the guards' lists.
+//   Mxfp4Form.      v_mfma_scale_f32_32x32x64_f8f6f4: dpad / 64 instructions per (query block, document block), every scale inside the chain.
+//     Query.        MXFP8 rows (dpad e4m3 codes, dpad / 32 E8M0 scale bytes, zero to a multiple of 16) staged once, codes and scale bytes
+//                   in one LDS row of token_mx_ldq bytes: an ODD number of 16-byte slots (one slot added where the row's count is even), so
+//                   the 32 rows a ds_read_b128 step touches lie on distinct slots of the bank row — the int8 form's argument.
+//     Score.        The document block is the A operand as e2m1 (cbsz 4, four registers): lane (col, h) feeds step s the 16 row bytes
+//                   at 32 s + 16 h of token j0 + col — the 32 codes of block 2 s + h — straight from global memory / L2.  The query block
+//                   is the B operand as e4m3 (blgp 0, eight registers): the 16 bytes at 64 s + 16 h and at 64 s + 32 + 16 h of query token
+//                   col.  ScoreBlock<mxfp4_t>::run (search.hip) states the map with the roles the other way round; the scales go by
+//                   k-block for either operand, so a lane reads each scale dword once, shifts it by 8 h, and opsel 0 / 2 serve every lane
+//                   (the query's dwords once per query block, outside the document's loop).  tests/test_gpu_late_mxfp4.py's exact-fit
+//                   test holds this map on the hardware.  U = 4 steps of loads in flight behind wave-uniform tests of dpad, the chain
+//                   unrolled to the 16 steps of dim 1024.  acc[r] is document token j0 + (r & 3) + 8 (r >> 2) + 4 h against query token
+//                   col — the f16 form's layout —, so the block's epilogue is the f16 form's 16 maxima and nothing else, and the max,
+//                   the last block's -inf, xor32_max and wave_sum_f32 are its lines.
+//     Non-finite.   The quantiser writes 0xFF into every scale byte of such a token and nothing else writes that byte.  stage looks at
+//                   the first scale byte of every query token (a query with one: the guards' lists); score at the first scale byte of
+//                   every document token, from the dwords it holds (such a document is never pushed) — not at what the MFMA makes of it.
+//   token_mx_quantize_kernel  f32 or f16 rows -> MXFP4 rows (adds) or MXFP8 rows (queries), one wave per row by device.h's quantize_row_mx —
+//                   the embedding index's rule, stated there once — with token_i8_quantize_kernel's row addressing and guards.
 //   token_i8_quantize_kernel  f32 or f16 rows (f16 is converted exactly) -> codes and scales, one wave per row by device.h's
 //                   quantize_row_i8 — the embedding index's rule, stated there once.  Serves the adds and, with qcu, the queries of every
 //                   search and rescore.
@@ -258,6 +278,108 @@ struct I8Form {
     }
 };
 
+// v_mfma_scale_f32_32x32x64_f8f6f4 with the roles of ScoreBlock<mxfp4_t>::run (search.hip) the other way round, so that the maximum over
+// a document's tokens stays in registers: A = the document block's e2m1 codes (cbsz 4), B = the staged query block's e4m3 codes (blgp 0).
+struct Mxfp4Form {
+    static constexpr bool LISTABLE = true;
+    static constexpr bool BAD_QUERIES = true;           // (a query with a non-finite token: 0xFF scale bytes)
+    static constexpr int PLAIN_PAD = 0;                 // (no placement was measured for this form)
+    static constexpr int U = 4, MAX_SC = MAXSIM_MAX_H / 128;      // steps of loads in flight; scale dwords of a row (16 steps)
+    uint8_t *qs;                                        // [blocks of the launch][32][ldq]
+    int P, ldq, qbytes, rb;                             // qbytes: a query's MXFP8 row in the workspace; rb: a stored row
+
+    __device__ __forceinline__ unsigned char *init(const TokenScanArgs &a, unsigned char *lds) {
+        P = a.dpad; ldq = token_mx_ldq(a.dim); qbytes = (int)token_mx_query_bytes(a.dim); rb = (int)token_mx_row_bytes(a.dim);
+        qs = lds;
+        return lds + (size_t)((a.max_q_len + TOKEN_QB - 1) / TOKEN_QB) * TOKEN_QB * ldq;
+    }
+    __device__ __forceinline__ bool stage(const TokenScanArgs &a, int qi, int, int nq, int nblk, int tid) const {
+        const int chunks = qbytes >> 4, sc = P >> 4;    // (chunks: 16-byte pieces of a row; piece sc starts with the first scale byte)
+        const i32x4 z = {};
+        const uint8_t *qsrc = (const uint8_t *)a.q + (size_t)qi * a.max_q_len * qbytes;
+        bool qbad = false;
+        for (int i = tid; i < nblk * TOKEN_QB * chunks; i += NT) {
+            const int r = i / chunks, c = i - r * chunks;
+            const i32x4 v = r < nq ? *(const i32x4 *)(qsrc + (size_t)r * qbytes + 16 * c) : z;
+            *(i32x4 *)(qs + r * ldq + 16 * c) = v;
+            qbad |= c == sc && (v[0] & 0xff) == 0xff;
+        }
+        return qbad;
+    }
+    __device__ __forceinline__ float score(const TokenScanArgs &a, int d0, int nd, int nq, int nblk, int lane, bool &bad) const {
+        const int col = lane & 31, h = lane >> 5;
+        const uint8_t *rows = (const uint8_t *)a.rows;
+        const i32x4 z = {};
+        float total = 0.f;
+        bool dbad = false;
+        for (int qb = 0; qb < nblk; ++qb) {
+            const bool qok = qb * TOKEN_QB + col < nq;
+            // (a staged slot behind the query's end is zero-filled: codes 0 under the scale 2^-127, every product +0)
+            const uint8_t *qrow = qs + (qb * TOKEN_QB + col) * ldq;
+            // the query token's scale dwords, the same for every block of the document: dword j holds blocks 4 j .. 4 j + 3, steps
+            // 2 j and 2 j + 1; shifted by 8 h, byte 0 is block 4 j + h (step 2 j, opsel 0) and byte 2 block 4 j + 2 + h (step 2 j + 1, opsel 2)
+            uint32_t qsc[MAX_SC];
+#pragma unroll
+            for (int j = 0; j < MAX_SC; ++j) qsc[j] = 128 * j < P ? *(const uint32_t *)(qrow + P + 4 * j) >> (8 * h) : 0u;
+            f32x16 m;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) m[r] = -INFINITY;
+            for (int j0 = 0; j0 < nd; j0 += 32) {
+                const bool dok = j0 + col < nd;            // this lane's row of the A operand: document token j0 + col
+                const uint8_t *drow = rows + (size_t)(d0 + (dok ? j0 + col : 0)) * rb;
+                uint32_t dsc[MAX_SC];
+#pragma unroll
+                for (int j = 0; j < MAX_SC; ++j) dsc[j] = dok && 128 * j < P ? *(const uint32_t *)(drow + (P >> 1) + 4 * j) : 0u;
+                // (a finite row holds no 0xFF scale byte, a non-finite one nothing else; the columns of the blocks are all the tokens)
+                dbad |= (dsc[0] & 0xffu) == 0xffu;
+#pragma unroll
+                for (int j = 0; j < MAX_SC; ++j) dsc[j] >>= 8 * h;
+                f32x16 acc = {};
+#pragma unroll
+                for (int g = 0; g < MAX_SC / 2; ++g) {
+                    if (256 * g >= P) break;               // (wave-uniform)
+                    i32x4 av[U], bv[U][2];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const bool in = 256 * g + 64 * u < P;
+                        const uint8_t *qk = qrow + 256 * g + 64 * u + 16 * h;
+                        av[u] = dok && in ? *(const i32x4 *)(drow + 128 * g + 32 * u + 16 * h) : z;
+                        bv[u][0] = in ? *(const i32x4 *)qk : z;
+                        bv[u][1] = in ? *(const i32x4 *)(qk + 32) : z;
+                    }
+                    // (the opsel is an immediate of the instruction: a compile-time loop)
+                    static_for<U>([&](auto uc) __attribute__((always_inline)) {
+                        constexpr int u = decltype(uc)::value;
+                        if (256 * g + 64 * u < P) {
+                            const i32x8 a8 = {av[u][0], av[u][1], av[u][2], av[u][3], 0, 0, 0, 0};
+                            const i32x8 b8 = {bv[u][0][0], bv[u][0][1], bv[u][0][2], bv[u][0][3], bv[u][1][0], bv[u][1][1], bv[u][1][2], bv[u][1][3]};
+                            acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc, 4, 0, 2 * (u & 1), (int)dsc[2 * g + (u >> 1)],
+                                                                                  2 * (u & 1), (int)qsc[2 * g + (u >> 1)]);
+                        }
+                    });
+                }
+                if (j0 + 32 <= nd) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) m[r] = __builtin_fmaxf(m[r], acc[r]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                        m[r] = __builtin_fmaxf(m[r], j < nd ? acc[r] : -INFINITY);
+                    }
+                }
+            }
+            float v = m[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) v = __builtin_fmaxf(v, m[r]);
+            v = xor32_max(v);
+            total += wave_sum_f32(h == 0 && qok ? v : 0.f);
+        }
+        bad = __any(dbad);
+        return total;
+    }
+};
+
 template <class Form, bool MASKED, bool LISTED>
 __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
     static_assert(!(MASKED && LISTED), "a rescore tests live per id");
@@ -271,7 +393,7 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
     // byte offset of the round loop's code inside the kernel.  The plain instantiations therefore start with Form::PLAIN_PAD s_nop, once per
     // workgroup: their loops lie at the offsets they were measured at.  The numbers belong to this compiler's output for this source: a change
     // in front of the round loop drops them or derives them again from a measurement, it does not inherit them
-    if constexpr (!MASKED && !LISTED) asm volatile(".rept %0\n\ts_nop 0\n\t.endr" ::"n"(Form::PLAIN_PAD));
+    if constexpr (!MASKED && !LISTED && Form::PLAIN_PAD > 0) asm volatile(".rept %0\n\ts_nop 0\n\t.endr" ::"n"(Form::PLAIN_PAD));
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     Form f;
     float *ls = (float *)f.init(a, ti_lds);                    // behind the staged query: the list and the count
@@ -363,6 +485,23 @@ __global__ __launch_bounds__(256) void token_i8_quantize_kernel(TokenI8QuantizeA
     quantize_row_i8((const T *)a.src + row * a.dim, a.dim, a.dpad, a.codes + w * a.dpad, a.scales + w, lane);
 }
 
+// One wave per row (device.h quantize_row_mx, two passes: dim <= MAXSIM_MAX_H); the row addressing and the guards are
+// token_i8_quantize_kernel's (TokenMxQuantizeArgs, token_index_kernels.h)
+template <class T, bool FP8>
+__global__ __launch_bounds__(256) void token_mx_quantize_kernel(TokenMxQuantizeArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= a.n) return;                                      // (the whole wave)
+    long long row = w;
+    if (a.qcu) {
+        const int qi = (int)(w / a.max_q_len), t = (int)(w - (long long)qi * a.max_q_len);
+        const int q0 = a.qcu[qi], len = a.qcu[qi + 1] - q0;
+        if (len <= 0 || q0 < 0 || len > a.max_q_len || t >= len) return;
+        row = (long long)q0 + t;
+    }
+    quantize_row_mx<FP8, MAXSIM_MAX_H / 512>((const T *)a.src + row * a.dim, a.dim, a.dpad, a.dst + w * mx_row_bytes(FP8 ? a.dpad : a.dpad >> 1, a.dpad), lane);
+}
+
 __global__ __launch_bounds__(256) void token_index_pairs_kernel(TokenPairsArgs a) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)a.nq * a.n_cand) return;
@@ -409,7 +548,8 @@ void token_index_kernels_init() {
         bool ok = true;
         for (const void *f : {(const void *)token_index_scan_kernel<F16Form, false, false>, (const void *)token_index_scan_kernel<F16Form, true, false>,
                               (const void *)token_index_scan_kernel<I8Form, false, false>, (const void *)token_index_scan_kernel<I8Form, true, false>,
-                              (const void *)token_index_scan_kernel<I8Form, false, true>})
+                              (const void *)token_index_scan_kernel<I8Form, false, true>, (const void *)token_index_scan_kernel<Mxfp4Form, false, false>,
+                              (const void *)token_index_scan_kernel<Mxfp4Form, true, false>, (const void *)token_index_scan_kernel<Mxfp4Form, false, true>})
             ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOKEN_LDS_MAX) == hipSuccess && ok;
         if (!ok) (void)hipGetLastError();                      // (not left behind for an unrelated call's check)
     });
@@ -420,7 +560,11 @@ void launch_token_scan(int dtype, const TokenScanArgs &a, hipStream_t s) {
     const int grid = xcd_grid(a.n_items);
     const size_t lds = token_scan_lds_bytes(a.dim, dtype, a.max_q_len, a.k);
     const bool masked = a.live || a.allow;
-    if (dtype == 2) {
+    if (dtype == 4) {
+        if (a.cand) BERT_LAUNCH((token_index_scan_kernel<Mxfp4Form, false, true>), dim3(grid), dim3(NT), lds, s, a);
+        else if (masked) BERT_LAUNCH((token_index_scan_kernel<Mxfp4Form, true, false>), dim3(grid), dim3(NT), lds, s, a);
+        else BERT_LAUNCH((token_index_scan_kernel<Mxfp4Form, false, false>), dim3(grid), dim3(NT), lds, s, a);
+    } else if (dtype == 2) {
         if (a.cand) BERT_LAUNCH((token_index_scan_kernel<I8Form, false, true>), dim3(grid), dim3(NT), lds, s, a);
         else if (masked) BERT_LAUNCH((token_index_scan_kernel<I8Form, true, false>), dim3(grid), dim3(NT), lds, s, a);
         else BERT_LAUNCH((token_index_scan_kernel<I8Form, false, false>), dim3(grid), dim3(NT), lds, s, a);
@@ -444,6 +588,25 @@ void launch_token_i8_quantize(const TokenI8QuantizeArgs &a, bool src_f32, hipStr
         const dim3 grid((unsigned)((p.n + 3) / 4));
         if (src_f32) BERT_LAUNCH(token_i8_quantize_kernel<float>, grid, dim3(256), 0, s, p);
         else BERT_LAUNCH(token_i8_quantize_kernel<half_t>, grid, dim3(256), 0, s, p);
+        if (a.qcu) break;
+    }
+}
+
+void launch_token_mx_quantize(const TokenMxQuantizeArgs &a, bool src_f32, bool fp8, hipStream_t s) {
+    // (the pieces of launch_token_i8_quantize)
+    const size_t rb = mx_row_bytes(fp8 ? a.dpad : a.dpad >> 1, a.dpad);
+    for (long long r0 = 0; r0 < a.n; r0 += QUANT_MAX_ROWS) {
+        TokenMxQuantizeArgs p = a;
+        p.n = std::min(QUANT_MAX_ROWS, a.n - r0);
+        if (!a.qcu) {
+            p.src = (const char *)a.src + (size_t)r0 * a.dim * (src_f32 ? 4 : 2);
+            p.dst = a.dst + (size_t)r0 * rb;
+        }
+        const dim3 grid((unsigned)((p.n + 3) / 4));
+        if (src_f32 && fp8) BERT_LAUNCH((token_mx_quantize_kernel<float, true>), grid, dim3(256), 0, s, p);
+        else if (src_f32) BERT_LAUNCH((token_mx_quantize_kernel<float, false>), grid, dim3(256), 0, s, p);
+        else if (fp8) BERT_LAUNCH((token_mx_quantize_kernel<half_t, true>), grid, dim3(256), 0, s, p);
+        else BERT_LAUNCH((token_mx_quantize_kernel<half_t, false>), grid, dim3(256), 0, s, p);
         if (a.qcu) break;
     }
 }

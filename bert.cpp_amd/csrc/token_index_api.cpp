@@ -2,8 +2,8 @@
 // device.  The text routes tokenize and pack as bert_hip_encode_tokens_batch does and run the token-rows pass with flags 1 | 2 (each
 // row over its L2 norm, f16) in chunks of chunk_tokens: add_texts straight into the index's storage, search_texts into a device buffer
 // the scan reads in place.  The rows never reach the host.  Behind them the bert_hip_late_index_* entry points: the same index's
-// remove, filtered searches, compact, save and load, and the int8 form's create, dtype and get_codes (an int8 index hands add_texts a
-// buffer of its own for the f16 rows and quantises from there: TokenIndex::append_room).
+// remove, filtered searches, compact, save and load, and the int8 and mxfp4 forms' create, dtype and get_codes (such an index hands
+// add_texts a buffer of its own for the f16 rows and quantises from there: TokenIndex::append_room).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -244,6 +244,7 @@ int32_t bert_hip_late_index_save(struct bert_hip_token_index *ix, const char *pa
     return token_index_call("bert_hip_late_index_save", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t {
         if (!path || !*path) { err = "a path is required"; return -2; }
         if (x.dtype() == 2) { err = "save: not available for an int8 token index"; return -2; }
+        if (x.dtype() == 4) { err = "save: not available for an mxfp4 token index"; return -2; }
         return x.save(path, err) ? 0 : -3;
     });
 }

@@ -1,6 +1,6 @@
 // token_index_kernels.h — the device code of the token index (token_index.hip) as its host side (token_index.cpp) sees it: the two
 // stored forms, the plan of a scan, the argument blocks and one launcher per kernel.  A launcher only enqueues: the caller reads
-// hipGetLastError.  dtype is the index's: 1 f16, 2 int8.
+// hipGetLastError.  dtype is the index's: 1 f16, 2 int8, 4 mxfp4.
 //
 // Stored form, f16.  half_t rows[n_tokens][dim], packed, 16-byte aligned (dim a multiple of 8 in 8 .. MAXSIM_MAX_H), and int32
 // cu[n_docs + 1]: document d is rows cu[d] .. cu[d + 1] - 1, never empty — what maxsim.hip takes as its document side, so a rescore
@@ -11,6 +11,12 @@
 // code_i = clamp(rint(x_i / scale), -127, 127) — device.h's quantize_row_i8, the embedding index's rule: all codes 0 where the scale is 0;
 // scale NaN and codes 0 where an element is NaN or +-inf.  Queries are quantised the same way, per token, into a workspace of
 // [nq][max_q_len] rows (query qi's token t at row qi * max_q_len + t), so the scan finds a query's rows without its neighbours' lengths.
+//
+// Stored form, mxfp4 (bert_hip.h "TOKEN INDEX, MXFP4 form").  uint8 rows[n_tokens][token_mx_row_bytes(dim)] and the same cu: per token
+// the embedding index's mxfp4 row — dpad / 2 bytes of e2m1 codes (dpad = dim rounded up to a multiple of 64, the padding zero), dpad / 32
+// E8M0 scale bytes (one per 32 elements), zero bytes to a multiple of 16 — by device.h's quantize_row_mx; no array beside the rows.
+// Queries are quantised per token to MXFP8 rows of token_mx_query_bytes(dim) bytes (dpad e4m3 codes, the same scale bytes, padded to
+// 16) into the same [nq][max_q_len] workspace.  A row or query token with a NaN or +-inf: codes 0, every scale byte 0xFF.
 //
 // A scan workgroup (token_index_scan_kernel, one kernel with a form per dtype) stages one query in LDS as ceil(n / 32) blocks of 32 rows
 // padded by 16 bytes, what else its form keeps beside them, then a list of L (score, id) entries and a count: token_scan_lds_bytes.
@@ -42,16 +48,26 @@ constexpr size_t TOKEN_LDS_MAX = 160 * 1024 - 256;
 inline int token_list_L(int k) { return k + TOKEN_STEP_DOCS <= 256 ? 256 : 512; }
 inline int token_query_blocks(int n) { return (n + TOKEN_QB - 1) / TOKEN_QB; }
 inline int token_i8_dpad(int dim) { return (dim + 31) & ~31; }
+__host__ __device__ inline int token_mx_dpad(int dim) { return (dim + 63) & ~63; }
+__host__ __device__ inline size_t token_mx_row_bytes(int dim) { return mx_row_bytes(token_mx_dpad(dim) >> 1, token_mx_dpad(dim)); }
+__host__ __device__ inline size_t token_mx_query_bytes(int dim) { return mx_row_bytes(token_mx_dpad(dim), token_mx_dpad(dim)); }
+// the mxfp4 form's staged query row: the MXFP8 row, and one more 16-byte slot where its slots come out even (an odd count of slots
+// puts the 32 rows of a ds_read_b128 step on distinct slots of the bank row: 9 at dim 128, 25 at 384, 50 + 1 at 768, 66 + 1 at 1024)
+__host__ __device__ inline int token_mx_ldq(int dim) { const int slots = (int)(token_mx_query_bytes(dim) >> 4); return 16 * (slots | 1); }
 // What a form stages per query.  A block of 32 tokens: rows of dim + 8 halfs (maxsim's padding), or of dpad + 16 bytes of codes (the
-// same 16 bytes).  Beside the blocks: nothing, or the int8 form's 512 bytes of query scales
-inline size_t token_query_block_bytes(int dim, int dtype) { return (size_t)TOKEN_QB * (dtype == 2 ? token_i8_dpad(dim) + 16 : (dim + 8) * 2); }
+// same 16 bytes), or of token_mx_ldq bytes (the mxfp4 form: codes and scale bytes in one row).  Beside the blocks: nothing, or the
+// int8 form's 512 bytes of query scales
+inline size_t token_query_block_bytes(int dim, int dtype) {
+    return (size_t)TOKEN_QB * (dtype == 4 ? token_mx_ldq(dim) : dtype == 2 ? token_i8_dpad(dim) + 16 : (dim + 8) * 2);
+}
 inline size_t token_query_extra_bytes(int dtype) { return dtype == 2 ? TOKEN_MAX_QUERY * 4 : 0; }
 // the query's blocks, the form's extra bytes, the list (8 L bytes), the count (16)
 inline size_t token_scan_lds_bytes(int dim, int dtype, int max_q_len, int k) {
     return (size_t)token_query_blocks(max_q_len) * token_query_block_bytes(dim, dtype) + token_query_extra_bytes(dtype) + (size_t)token_list_L(k) * 8 + 16;
 }
 // the largest multiple of 32, at most TOKEN_MAX_QUERY, whose blocks fit TOKEN_LDS_MAX beside the longest list.  f16: dim <= 384: 128,
-// <= 768: 96, <= 1024: 64.  int8: 128 at every dim (dim 1024, 128 tokens, the longest list: 137 744 bytes)
+// <= 768: 96, <= 1024: 64.  int8: 128 at every dim (dim 1024, 128 tokens, the longest list: 137 744 bytes).  mxfp4: 128 at every dim
+// (dim 1024: rows of 1072 bytes, 141 328 bytes with the longest list)
 inline int token_max_query_tokens(int dim, int dtype) {
     const size_t room = TOKEN_LDS_MAX - token_query_extra_bytes(dtype) - (size_t)512 * 8 - 16;
     return (int)std::min<size_t>(TOKEN_MAX_QUERY, room / token_query_block_bytes(dim, dtype) * TOKEN_QB);
@@ -75,12 +91,13 @@ inline bool token_index_plan(int n_docs, int nq, int pref, TokenScanPlan &p) {
     return true;
 }
 
-// token_index_scan_kernel, both forms.  LDS: token_scan_lds_bytes(dim, dtype, max_q_len, k)
+// token_index_scan_kernel, every form.  LDS: token_scan_lds_bytes(dim, dtype, max_q_len, k)
 struct TokenScanArgs {
-    const void *rows;                   // the index: half_t [n_tokens][dim], or int8 codes [n_tokens][dpad]
+    const void *rows;                   // the index: half_t [n_tokens][dim], int8 codes [n_tokens][dpad], or mxfp4 rows [n_tokens][token_mx_row_bytes]
     const float *scales = nullptr;      // int8: [n_tokens]
     const int32_t *cu;                  // [n_docs + 1]
     const void *q;                      // f16: the queries' rows, indexed by qcu.  int8: the queries' workspace, codes [nq][max_q_len][dpad]
+                                        // mxfp4: the workspace of MXFP8 rows [nq][max_q_len][token_mx_query_bytes]
     const float *q_scales = nullptr;    // int8: [nq][max_q_len]
     const int32_t *qcu;                 // [nq + 1]
     float *ws_s;                        // [nq][n_slices][k] per-(query, slice) lists, best first
@@ -90,7 +107,7 @@ struct TokenScanArgs {
     // be returned; a null pointer = all ones.  No word at or beyond ceil(n_docs / 32) is read
     const uint32_t *live = nullptr;
     const uint32_t *allow = nullptr;
-    // the listed instantiation (cand non-null; int8 only): a rescore.  The "documents" of a slice are positions of the query's candidate
+    // the listed instantiation (cand non-null; int8 and mxfp4): a rescore.  The "documents" of a slice are positions of the query's candidate
     // list cand[qi][0 .. n_cand), n_cand takes n_docs' place in the plan, and live is tested per id (allow is not used)
     const int32_t *cand = nullptr;      // [nq][n_cand]
     int n_cand = 0;
@@ -131,12 +148,25 @@ struct TokenI8QuantizeArgs {
     int max_q_len = 0;
 };
 
+// token_mx_quantize_kernel: rows of dim values (f32 or f16) -> MX rows by device.h's quantize_row_mx, one wave per row: the mxfp4
+// form (fp8 false: stored rows of token_mx_row_bytes) or the mxfp8 form (queries, token_mx_query_bytes).  n, qcu and max_q_len as
+// TokenI8QuantizeArgs': the same slot addressing and the same guards
+struct TokenMxQuantizeArgs {
+    const void *src;
+    uint8_t *dst;
+    long long n;
+    int dim, dpad;
+    const int32_t *qcu = nullptr;
+    int max_q_len = 0;
+};
+
 // lets every scan instantiation of the current device have TOKEN_LDS_MAX of LDS
 void token_index_kernels_init();
-// the instantiation of dtype's form: listed if a.cand is set (int8 only), else masked if a.live or a.allow is, else plain
+// the instantiation of dtype's form: listed if a.cand is set (int8 and mxfp4), else masked if a.live or a.allow is, else plain
 void launch_token_scan(int dtype, const TokenScanArgs &a, hipStream_t s);
 // (src_f32: the rows are f32, else f16; more rows than one launch takes go in several)
 void launch_token_i8_quantize(const TokenI8QuantizeArgs &a, bool src_f32, hipStream_t s);
+void launch_token_mx_quantize(const TokenMxQuantizeArgs &a, bool src_f32, bool fp8, hipStream_t s);
 void launch_token_pairs(const TokenPairsArgs &a, hipStream_t s);
 void launch_token_gather(const TokenGatherArgs &a, hipStream_t s);
 

@@ -1282,7 +1282,8 @@ class BertModel:
 
     def token_index(self, dim: Optional[int] = None, dtype: str = "f16") -> "BertTokenIndex":
         """A token index on the context's first device (bert_hip_token_index_create): documents' f16 token rows, exact MaxSim top-k
-        search; dim None = n_embd.  dtype "i8": int8 codes with a scale per token (bert_hip_late_index_create)."""
+        search; dim None = n_embd.  dtype "i8": int8 codes with a scale per token; "mxfp4": e2m1 codes with a power-of-two scale per 32
+        elements, scanned on the block-scaled MFMA (both bert_hip_late_index_create)."""
         return BertTokenIndex(self, dim, dtype=dtype)
 
     def load_index(self, path: str) -> "BertIndex":
@@ -1934,7 +1935,7 @@ class BertTokenIndex:
     [n, k] f32), best first; missing entries are id -1, score -inf.  A ValueError is an argument the entry refused (-2).  The *_device
     forms take device pointers (ints) and a stream handle; search_device and rescore_device return at once."""
 
-    DTYPES = {"f16": 1, "i8": 2}
+    DTYPES = {"f16": 1, "i8": 2, "mxfp4": 4}
 
     def __init__(self, model: BertModel, dim: Optional[int] = None, _load: Optional[str] = None, dtype: str = "f16"):
         self.model, self.lib = model, model.lib
@@ -2026,7 +2027,8 @@ class BertTokenIndex:
         return r
 
     def get_doc(self, doc_id: int) -> np.ndarray:
-        """The stored rows of a document, [length, dim] float32 (the f16 values converted exactly)."""
+        """The stored rows of a document, [length, dim] float32 (the f16 values converted exactly; the int8 and mxfp4 forms decoded,
+        a non-finite token of the mxfp4 form all NaN)."""
         n = self.lib.bert_hip_token_index_get_doc(self.ix, doc_id, None, 0)
         if n < 0:
             self._fail("bert_hip_token_index_get_doc", n)

@@ -987,7 +987,7 @@ BERT_API int32_t bert_hip_dense_sparse_search_inverted_texts(struct bert_hip_ind
  * Results: -1 without an index; -2 after a line on stderr for an argument the entry refuses; -3 on a device error; -4 for an exception.
  * Outputs are untouched on error.
  * Removing documents, allow-lists, compaction and files: "LATE INDEX" below.
- * Quantised token rows: "TOKEN INDEX, int8 form" below.
+ * Quantised token rows: "TOKEN INDEX, int8 form" and "TOKEN INDEX, MXFP4 form" below.
  * Not covered: several GPUs; several queries per workgroup sharing document loads; residual token rows; a mean mode.   */
 struct bert_hip_token_index;
 BERT_API struct bert_hip_token_index *bert_hip_token_index_create(struct bert_ctx *ctx, int32_t dim);
@@ -1077,8 +1077,8 @@ BERT_API struct bert_hip_token_index *bert_hip_late_index_load(struct bert_ctx *
  * remove, n_live, n_live_tokens and search_filtered[_device] take an int8 index with the inputs they take today.  The new names are
  * bert_hip_late_index_* for the reason given under LATE INDEX.
  *   create   dtype 1: the f16 form — exactly bert_hip_token_index_create(ctx, dim) —; dtype 2: the int8 form (the embedding index's code
- *            for it); anything else: NULL + a line on stderr.  dim as there.
- *   dtype    1 or 2; -1 without an index.
+ *            for it); dtype 4: the MXFP4 form (the block below); anything else: NULL + a line on stderr.  dim as there.
+ *   dtype    1, 2 or 4; -1 without an index.
  *   get_codes   returns document id's length in tokens; iff cap_tokens >= it (and both pointers are given), codes [length][dpad] and
  *            scales [length] receive the stored form.  An f16 index, or an id outside [0, size): -2.  Blocking.
  * Semantics:
@@ -1110,6 +1110,36 @@ BERT_API struct bert_hip_token_index *bert_hip_late_index_load(struct bert_ctx *
 BERT_API struct bert_hip_token_index *bert_hip_late_index_create(struct bert_ctx *ctx, int32_t dim, int32_t dtype);
 BERT_API int32_t bert_hip_late_index_dtype(struct bert_hip_token_index *ix);
 BERT_API int32_t bert_hip_late_index_get_codes(struct bert_hip_token_index *ix, int32_t id, int8_t *codes, float *scales, int32_t cap_tokens);
+
+/* TOKEN INDEX, MXFP4 form: bert_hip_late_index_create(ctx, dim, 4) — the embedding index's mxfp4 row (EMBEDDING INDEX, dtype 4), per
+ * token, scanned on v_mfma_scale_f32_32x32x64_f8f6f4.  No new entry point: add (f32 host rows), add_device (f16 device rows), add_texts,
+ * get_doc, search, search_device, search_texts, search_filtered[_device], rescore, rescore_device, reserve, size, n_tokens,
+ * max_query_tokens, remove, n_live, n_live_tokens and dtype (4) take such an index with the inputs they take for an int8 one.
+ *   - Stored rows.  Per token dpad / 2 bytes of e2m1 codes (dpad: dim rounded up to a multiple of 64, the padding zero; element e in
+ *     the low nibble of byte e / 2 for even e), then dpad / 32 E8M0 scale bytes, one per 32 elements, then zero bytes to a multiple of
+ *     16: 208 bytes at dim 384 against 388 (int8) and 768 (f16), 80 at dim 128 against 132 and 256.  A block's exponent is
+ *     floor(log2 amax) - 2 (0 for a zero block), its codes the nearest of {0, 0.5, 1, 1.5, 2, 3, 4, 6} x 2^exponent, ties to the even
+ *     code; every scale byte of a token that holds a NaN or +-inf is 0xFF and its codes are 0.  f16 rows are converted to f32 exactly
+ *     and follow the same rule.  No array beside the rows.  get_doc returns value(code) * 2^(scale byte - 127), NaN for every element
+ *     of a 0xFF token; get_codes stays the int8 form's (-2).
+ *   - Queries are quantised per token on the device to MXFP8 — e4m3 codes, the same scale rule with - 8 — into a workspace of
+ *     [n_queries][max_q_len] rows that reserve sizes: a search_device within reserve's bounds allocates nothing and may be captured.
+ *   - Score.  sum over query tokens i of max over document tokens j of dot_ij, where dot_ij is the block-scaled MFMA's chain over the
+ *     stored values, dpad / 64 instructions in ascending k from a zero accumulator.  The maxima are added as the f16 form adds them:
+ *     blocks of 32 in the butterfly order of a wavefront sum with +0 in the unused lanes and behind the query's end, the blocks' sums in
+ *     ascending order from +0.  The chain's accumulate is narrower than f32, so against arithmetic the promise is a bound:
+ *     |score - exact| <= 8.9e-5 x sum_i max_j (|q_i| . |d_j|) over the decoded values plus the f32 sum's rounding (measured: 1.1e-6).
+ *     Where every product and partial sum is exactly representable the score is exact.
+ *   - Determinism.  The TOKEN INDEX block's promises hold word for word: a (query, document) score has the same bits alone or in a
+ *     batch, for any k, however the scan is sliced, from the host or the device entry on the same values, with or without removals
+ *     and allow-lists, from a search or a rescore, for an index built in one add or in several.  Order (larger first, ties by id),
+ *     -1 / -INFINITY slots and k <= 256 as there.
+ *   - Non-finite rows.  A document with a 0xFF token is never returned; a query with one gets k slots of -1 / -INFINITY, its
+ *     neighbours untouched.  The kernel decides both from the scale bytes, not from what the instruction makes of them.
+ *   - Query length.  A query is staged in LDS as MXFP8 rows of an odd number of 16-byte pieces (dim 1024: 1072 bytes): 128 tokens fit
+ *     at every dim (141 328 bytes with the longest list), so max_query_tokens is 128.  rescore is the search's kernel over the
+ *     candidate lists, with the int8 form's rules for a longer query (host: -2; device: -1 / -INFINITY).
+ * Not covered: compact and save (-2 after a line on stderr, the index unchanged and still searchable) and a file form.             */
 
 BERT_API const char *bert_hip_version(void);
 
