@@ -27,6 +27,7 @@ struct EngineOptions {
     int sparse_index_segment_rows = 0; // tuning (a key only): rows per segment of the sparse index's postings, 256 .. 16384 in multiples of 256, read by invert; 0 = the default of sparse_index_kernels.h
     int hybrid_chunk_queries = 0;     // tuning (a key only): queries per chunk of a hybrid search, 1 .. 4096; 0 = what the score workspace's bound gives (sparse_index_kernels.h)
     int token_index_slices = 0;       // tuning (a key only): slices of documents of a token index's scan, 1 .. 4096; 0 = planned (token_index_kernels.h)
+    int token_index_query_group = 0;  // tuning (a key only): queries per workgroup of an f16 token index's scan, 1 = never group, 2 .. 4 = at most that many; 0 = planned (token_index_kernels.h)
     int maxsim_launch_pairs = 0;      // tuning (a key only): pairs per launch of MaxSim's kernel, 1 .. 2^23 (a larger value is clamped to that bound); 0 = the bound (kernels.h)
     bool stage_kernel = true;       // small staged blocks come in by a kernel that reads the mapped pinned block, not by the copy engine
     // How a pass ends (bert_hip.h): the mean over a sentence's tokens or the state of its first token ([CLS]), divided by its L2

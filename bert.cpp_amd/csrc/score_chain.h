@@ -52,4 +52,32 @@ __device__ __forceinline__ void score_chain_f16_grid(LoadA &&load_a, LoadB &&loa
     }
 }
 
+// The same chain with ONE A operand shared by NB operands B (token_index_grouped.hip: a document block from global memory against the
+// staged query blocks of a group in LDS): acc[b] is the block of A against B operand b.  The roles are the single-block statement's —
+// the grid form above shares its operands the other way round, which would transpose the accumulator —, and every accumulator sees the k
+// sequence of score_chain_f16: steps of 16 ascending from a zeroed or running acc[b], the same `in` rule, nothing of its neighbours.  So
+// a (row, row) product keeps the bits of the single-block statement.  load_a(k, in) as above, loaded a group of U steps AHEAD: the
+// elements of the group behind the one being multiplied are requested in front of its MFMAs (next(k): the loader of the group that
+// starts at k >= dpad — the caller's next A block, or zeros —, so the request crosses the end of this chain); a holds this chain's
+// first group on entry and the next chain's on exit.  load_b(b, k): as it is used (LDS).  on(b): operand b takes part (wave-uniform).
+template <int NB, int U, class LoadA, class NextA, class LoadB, class On>
+__device__ __forceinline__ void score_chain_f16_shared_a(LoadA &&load_a, NextA &&next_a, LoadB &&load_b, On &&on, int dpad, f16x8 (&a)[U],
+                                                         f32x16 (&acc)[NB]) {
+    for (int k0 = 0; k0 < dpad; k0 += 16 * U) {
+        f16x8 n[U];
+        const int k1 = k0 + 16 * U;
+#pragma unroll
+        for (int u = 0; u < U; ++u) n[u] = k1 < dpad ? load_a(k1 + 16 * u, k1 + 16 * u < dpad) : next_a(16 * u);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (k0 + 16 * u < dpad) {
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+                    if (on(b)) acc[b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[u], load_b(b, k0 + 16 * u), acc[b], 0, 0, 0);
+            }
+#pragma unroll
+        for (int u = 0; u < U; ++u) a[u] = n[u];
+    }
+}
+
 }  // namespace bert_hip

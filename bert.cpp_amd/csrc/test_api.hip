@@ -1126,6 +1126,12 @@ int32_t bert_hip_test_token_index_plan(int32_t n_docs, int32_t nq, int32_t pref,
     return ok ? 0 : -2;
 }
 
+int32_t bert_hip_test_late_index_query_group(int32_t dim, int32_t dtype, int32_t max_q_len, int32_t nq, int32_t k, int32_t key) {
+    if (dim < 8 || dim > MAXSIM_MAX_H || dim % 8 || (dtype != 1 && dtype != 2 && dtype != 4) || nq < 1 || k < 1 || k > TokenIndex::MAX_K || key < 0 ||
+        key > TOKEN_MAX_GROUP || max_q_len < 1 || max_q_len > token_max_query_tokens(dim, dtype)) return -2;
+    return token_query_group(dim, dtype, max_q_len, nq, k, key);
+}
+
 int32_t bert_hip_test_index_plan(int32_t n_rows, int32_t nq, int32_t k, int32_t *geometry) {
     if (!geometry) return -1;
     geometry[0] = geometry[1] = geometry[2] = geometry[3] = 0;

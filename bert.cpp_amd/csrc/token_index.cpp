@@ -21,12 +21,15 @@ namespace bert_hip {
 
 namespace {
 
-// the most workspace entries (nq' * slices * k) a chunk of up to nqc queries takes: the slice count falls as the queries grow
-size_t ws_entries_bound(int n_docs, int nqc, int k, int pref) {
+// the most workspace entries (nq' * slices * k) a chunk of up to nqc queries takes: the slice count falls as the queries grow, and
+// rises with the group a later search may take (up to gcap queries a workgroup: the plan is made for the groups, the workspace holds
+// a list per query and slice)
+size_t ws_entries_bound(int n_docs, int nqc, int k, int pref, int gcap) {
     size_t ent = 0;
     TokenScanPlan p;
-    for (int q = 1; q <= nqc; ++q)
-        if (token_index_plan(n_docs, q, pref, p)) ent = std::max(ent, (size_t)q * p.max_slices * k);
+    for (int g = 1; g <= gcap; ++g)
+        for (int q = 1; q <= nqc; ++q)
+            if (token_index_plan(n_docs, (q + g - 1) / g, pref, p)) ent = std::max(ent, (size_t)q * p.max_slices * k);
     return ent;
 }
 
@@ -143,7 +146,7 @@ bool TokenIndex::grow_storage(long long n_docs, long long n_tokens, std::string 
 }
 
 bool TokenIndex::grow_search(int n_docs, int nqc, int k, std::string &err) {
-    const size_t ent = ws_entries_bound(n_docs, nqc, k, eng_->options().token_index_slices);
+    const size_t ent = ws_entries_bound(n_docs, nqc, k, eng_->options().token_index_slices, token_group_cap(dtype_, eng_->options().token_index_query_group));
     return grow(ws_s_, ent * 4, err) && grow(ws_i_, ent * 4, err);
 }
 
@@ -364,12 +367,16 @@ int TokenIndex::scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool 
     if (quantised() && !grow_queries(nqc, max_q_len, err)) return -3;
     for (int c0 = 0; c0 < nq; c0 += QCHUNK) {
         const int c = std::min(QCHUNK, nq - c0);
+        // (a search of f16 rows: G consecutive queries a workgroup, the plan made for the groups — fewer groups aim for more slices;
+        // G == 1: the ungrouped kernel and the plan of the queries, as every rescore and every other form)
+        const int G = d_cand ? 1 : token_query_group(dim_, dtype_, max_q_len, c, k, eng_->options().token_index_query_group);
+        const int n_groups = (c + G - 1) / G;
         TokenScanPlan p;
-        token_index_plan(n_list, c, pref, p);                 // (the key's range is the option's: never refused)
-        TokenScanArgs a;
+        token_index_plan(n_list, n_groups, pref, p);          // (the key's range is the option's: never refused)
+        TokenGroupScanArgs a;
         a.rows = rows_; a.cu = cu_; a.q = d_q; a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
         a.n_docs = n_; a.dim = dim_; a.dpad = dpad_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
-        a.k = k; a.L = token_list_L(k); a.n_items = c * p.n_slices;
+        a.k = k; a.L = token_list_L(k); a.n_items = n_groups * p.n_slices; a.group = G; a.n_groups = n_groups;
         if (i8) {
             TokenI8QuantizeArgs qa{d_q, q_codes_.as<int8_t>(), q_scales_.as<float>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
             eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, q_f32, s); });
@@ -386,7 +393,8 @@ int TokenIndex::scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool 
         const bool masked = a.live || a.allow;
         const char *label = mx ? (d_cand ? "token_mxfp4_rescore" : masked ? "token_mxfp4_scan_masked" : "token_mxfp4_scan")
                             : d_cand ? "token_i8_rescore" : i8 ? (masked ? "token_i8_scan_masked" : "token_i8_scan") : (masked ? "token_index_scan_masked" : "token_index_scan");
-        eng_->timed_launch(label, 0.0, s, [&] { launch_token_scan(dtype_, a, s); });
+        if (G >= 2) eng_->timed_launch(masked ? "token_index_scan_grouped_masked" : "token_index_scan_grouped", 0.0, s, [&] { launch_token_scan_grouped(a, s); });
+        else eng_->timed_launch(label, 0.0, s, [&] { launch_token_scan(dtype_, a, s); });
         enqueue_merge(c, p.n_slices * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -3);

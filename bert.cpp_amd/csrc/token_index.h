@@ -8,6 +8,8 @@
 // from (index_frame.h; the bitmap's invariant: live_bits.h).  The bitmap is there from the first remove to the next compact; while it exists, or under
 // an allow-list, a search launches the masked scan and a rescore's pair list leaves the removed ids out.  compact gathers the live
 // documents' rows into a fresh allocation on the device; save / load move the file form (token_index_file.h) in pieces.
+// A chunk of several queries over f16 rows may be scanned in groups: token_index_scan_grouped_kernel (token_index_grouped.hip), one
+// workgroup per (G consecutive queries, slice), G by token_query_group and the tuning key "token_index_query_group"; the same bits.
 // dtype 2, the int8 form (token_index_kernels.h states it): rows are int8 codes of dpad bytes with one f32 scale per token, every add
 // quantises on the device, a search quantises its queries into a workspace that reserve sizes and scans with token_index_scan_kernel's
 // int8 form, and a rescore is the same kernel over the candidate lists instead of maxsim.  The bitmap, the event, the streams, the

@@ -85,21 +85,12 @@
 #include "device.h"
 #include "score_chain.h"
 #include "token_index_kernels.h"
+#include "token_scan_mask.h"
 #include "topk_select.h"
 
 namespace bert_hip {
 
 namespace {
-
-static_assert(TOKEN_STEP_DOCS == 64, "the masked scan keeps a step's mask in one 64-bit word");
-
-// the word of live & allow (a null pointer: all ones) at index wi, the same in every lane
-__device__ __forceinline__ uint32_t token_mask_word(const TokenScanArgs &a, int wi) {
-    uint32_t w = ~0u;
-    if (a.live) w &= a.live[wi];
-    if (a.allow) w &= a.allow[wi];
-    return __builtin_amdgcn_readfirstlane(w);
-}
 
 // A Form of token_index_scan_kernel: how the query is staged and how one document is scored.  Its members are a few pointers and a
 // row stride, held in registers.
@@ -425,17 +416,10 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
     }
 
     for (int base = r0; base < r1; base += TOKEN_STEP_DOCS) {
-        // MASKED: bit i of m = document base + i qualifies.  The step's documents lie in up to three mask words (a slice starts
-        // anywhere); only words that hold a document below r1 are read, so none at or beyond ceil(n_docs / 32).  Everything here is
-        // computed from the workgroup's values alone, the same in all four waves.
+        // MASKED: bit i of m = document base + i qualifies (token_scan_mask.h), the same in all four waves
         [[maybe_unused]] uint64_t m = 0;
         if constexpr (MASKED) {
-            const int wi = base >> 5, sh = base & 31, we = (min(base + TOKEN_STEP_DOCS, r1) - 1) >> 5;
-            const uint32_t w0 = token_mask_word(a, wi);
-            const uint32_t w1 = wi + 1 <= we ? token_mask_word(a, wi + 1) : 0u;
-            const uint32_t w2 = wi + 2 <= we ? token_mask_word(a, wi + 2) : 0u;
-            m = ((uint64_t)w1 << 32 | w0) >> sh;
-            if (sh) m |= (uint64_t)w2 << (64 - sh);
+            m = token_step_mask(a, base, r1);
             // a step without a qualifying document pushes nothing: the count is what the last look left, so select_step_end — both
             // barriers and the look — can go, for the whole workgroup, since m is the workgroup's
             if (m == 0) continue;
@@ -553,6 +537,7 @@ void token_index_kernels_init() {
             ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOKEN_LDS_MAX) == hipSuccess && ok;
         if (!ok) (void)hipGetLastError();                      // (not left behind for an unrelated call's check)
     });
+    token_index_grouped_kernels_init();
 }
 
 void launch_token_scan(int dtype, const TokenScanArgs &a, hipStream_t s) {

@@ -91,6 +91,34 @@ inline bool token_index_plan(int n_docs, int nq, int pref, TokenScanPlan &p) {
     return true;
 }
 
+// The grouped scan of the f16 form (token_index_grouped.hip): one workgroup serves G consecutive queries over one slice and loads every
+// document block once for all of them.  Every query of a group gets ceil(max_q_len / 32) block slots (the host knows the launch's
+// max_q_len, not the lengths), then G lists of L entries and their counts
+constexpr int TOKEN_MAX_GROUP = 4;
+inline size_t token_group_lds_bytes(int dim, int max_q_len, int k, int g) {
+    return (size_t)g * (token_query_blocks(max_q_len) * token_query_block_bytes(dim, 1) + (size_t)token_list_L(k) * 8) + 16;
+}
+// The planned G (the key at 0), from profiles/token_group_rate.txt (tools/token_group_rate.py: 10^6 x 25 and 10^5 x 180 tokens, dim 384 and
+// 128, 32-token queries, 1 / 8 / 64 queries): a cell's fastest arm where it beat key 1 by more than the cell's min .. max spread, else 1.
+// dim 384: key 3 in all four cells of 8 and 64 queries (0.95, 0.78, 0.61, 0.52 of key 1's time; key 4, one workgroup a CU, behind it).
+// dim 128: key 4 over the long documents (0.62, 0.63) but key 1 over the short ones (key 4: 1.11, 1.09 of its time), and the plan does
+// not know the documents' lengths: 1.  One query: 1.  Not measured: 2 .. 7 queries (1), dims between the two (1) and above 384 (3, which
+// the LDS cuts to 2 at dim 1024: their rows are longer still)
+inline int token_group_planned(int dim, int nq) { return dim >= 384 && nq >= 8 ? 3 : 1; }
+// G of a chunk of nq queries: the largest value that is at most TOKEN_MAX_GROUP, at most nq, at most the tuning key
+// "token_index_query_group" (key: 1 = never group, 2 .. 4 = at most that many; 0 = token_group_planned) and whose LDS fits
+// TOKEN_LDS_MAX.  1 = the ungrouped kernel, which every other dtype launches whatever the key.  With 32-token queries the LDS allows 4 at
+// dim <= 384, 3 at 768, 2 at 1024; with 128-token queries at dim 384: 1.  The one place this is decided: the search and the test hook
+// call it, reserve bounds it by token_group_cap
+inline int token_query_group(int dim, int dtype, int max_q_len, int nq, int k, int key) {
+    if (dtype != 1 || nq < 2 || key == 1) return 1;
+    int g = std::min({TOKEN_MAX_GROUP, nq, key >= 2 ? key : token_group_planned(dim, nq)});
+    while (g > 1 && token_group_lds_bytes(dim, max_q_len, k, g) > TOKEN_LDS_MAX) --g;
+    return g;
+}
+// the most queries a group of any later search may hold under this key (reserve's workspace bound: max_q_len and k may be smaller then)
+inline int token_group_cap(int dtype, int key) { return dtype != 1 || key == 1 ? 1 : key >= 2 ? std::min(key, TOKEN_MAX_GROUP) : TOKEN_MAX_GROUP; }
+
 // token_index_scan_kernel, every form.  LDS: token_scan_lds_bytes(dim, dtype, max_q_len, k)
 struct TokenScanArgs {
     const void *rows;                   // the index: half_t [n_tokens][dim], int8 codes [n_tokens][dpad], or mxfp4 rows [n_tokens][token_mx_row_bytes]
@@ -111,6 +139,13 @@ struct TokenScanArgs {
     // list cand[qi][0 .. n_cand), n_cand takes n_docs' place in the plan, and live is tested per id (allow is not used)
     const int32_t *cand = nullptr;      // [nq][n_cand]
     int n_cand = 0;
+};
+
+// token_index_scan_grouped_kernel (f16 form; cand, n_cand, scales and q_scales are not used): the scan's arguments with nq queries in
+// n_groups groups of `group` consecutive queries (the last group holds what is left), n_items = n_slices * n_groups, item = slice *
+// n_groups + group index.  The workspace is the ungrouped scan's, [nq][n_slices][k].  LDS: token_group_lds_bytes(dim, max_q_len, k, group)
+struct TokenGroupScanArgs : TokenScanArgs {
+    int group = 1, n_groups = 0;
 };
 
 // token_index_pairs_kernel: cand [nq][n_cand] -> maxsim's pair list pairs [nq * n_cand][2] = (q, id), and ws_i [nq][n_cand] = id; an
@@ -162,8 +197,11 @@ struct TokenMxQuantizeArgs {
 
 // lets every scan instantiation of the current device have TOKEN_LDS_MAX of LDS
 void token_index_kernels_init();
+void token_index_grouped_kernels_init();                // (token_index_grouped.hip's part of it)
 // the instantiation of dtype's form: listed if a.cand is set (int8 and mxfp4), else masked if a.live or a.allow is, else plain
 void launch_token_scan(int dtype, const TokenScanArgs &a, hipStream_t s);
+// the grouped scan of the f16 form: masked if a.live or a.allow is set, else plain; a.group in 2 .. TOKEN_MAX_GROUP
+void launch_token_scan_grouped(const TokenGroupScanArgs &a, hipStream_t s);
 // (src_f32: the rows are f32, else f16; more rows than one launch takes go in several)
 void launch_token_i8_quantize(const TokenI8QuantizeArgs &a, bool src_f32, hipStream_t s);
 void launch_token_mx_quantize(const TokenMxQuantizeArgs &a, bool src_f32, bool fp8, hipStream_t s);

@@ -76,7 +76,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid", "bert_hip_test_sparse_scan_geometry",
     "bert_hip_test_sparse_index_header", "bert_hip_test_sparse_index_body",
     "bert_hip_test_sparse_scan_geometry_qb", "bert_hip_test_index_plan", "bert_hip_test_hybrid_chunk", "bert_hip_test_token_index_plan",
-    "bert_hip_test_late_index_header", "bert_hip_test_late_index_body",
+    "bert_hip_test_late_index_header", "bert_hip_test_late_index_body", "bert_hip_test_late_index_query_group",
     "bert_hip_test_attention_bias", "bert_hip_test_f32_attention_bias", "bert_hip_test_rel_bias_table",
     "bert_hip_test_sparse_postings_geometry", "bert_hip_test_sparse_postings_segment",
 ]
@@ -416,6 +416,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_hybrid_chunk.argtypes = [i32, i32, i32, C.POINTER(C.c_int64)]
     L.bert_hip_test_token_index_plan.restype = i32
     L.bert_hip_test_token_index_plan.argtypes = [i32, i32, i32, i32p]
+    L.bert_hip_test_late_index_query_group.restype = i32
+    L.bert_hip_test_late_index_query_group.argtypes = [i32, i32, i32, i32, i32, i32]
     L.bert_hip_test_late_index_header.restype = i32
     L.bert_hip_test_late_index_header.argtypes = [C.c_char_p, i32, C.c_int64, C.POINTER(C.c_uint32), C.c_char_p, i32]
     L.bert_hip_test_late_index_body.restype = i32
@@ -605,6 +607,13 @@ def test_token_index_plan(n_docs: int, nq: int, pref: int = 0):
     if r != 0:
         raise RuntimeError(f"bert_hip_test_token_index_plan failed: {r}")
     return int(out[0]), int(out[1])
+
+
+def test_late_index_query_group(dim: int, dtype: int, max_q_len: int, nq: int, k: int, key: int = 0):
+    """How many consecutive queries a workgroup of a token index's scan serves (bert_hip_test_late_index_query_group; no GPU): 1 = the
+    ungrouped kernel; None where the hook refuses.  key: the value of the tuning key "token_index_query_group" (0 = planned)."""
+    r = test_lib().bert_hip_test_late_index_query_group(dim, dtype, max_q_len, nq, k, key)
+    return None if r == -2 else int(r)
 
 
 def test_attention_grid(n_sentences: int, n_head: int, d_head: int, max_len: int):

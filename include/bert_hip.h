@@ -191,6 +191,9 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  * per internal chunk of a hybrid search, 1 .. 4096, never more than the score workspace's bound allows; "0" = what that bound gives; a
  * result's bits do not depend on it), "token_index_slices" = n (tuning: slices of documents a token index's scan is cut into, 1 .. 4096,
  * never more than documents; "0" = planned; a result's bits do not depend on it; set it before bert_hip_token_index_reserve),
+ * "token_index_query_group" = n (tuning: consecutive queries one workgroup of an f16 token index's scan serves with one read of the
+ * documents, "1" = never group, "2" .. "4" = at most that many, never more than the staged queries' LDS allows; "0" = planned; int8 and
+ * MXFP4 indexes and rescores ignore it; a result's bits do not depend on it; set it before bert_hip_token_index_reserve),
  * "maxsim_launch_pairs" = n (tuning and tests: pairs per launch of MaxSim's kernel, which bert_hip_maxsim[_device] and a token index's
  * rescore enqueue, 1 .. 8388608 = 2^23; a larger value is clamped to 2^23, "0" = 2^23; a result's bits do not depend on it),
  * "profile_replay" (above), "pooling" = "mean" | "cls", "normalize" = "1" | "0"

@@ -324,6 +324,11 @@ BERT_API int32_t bert_hip_test_hybrid_chunk(int32_t n_rows, int32_t nq, int32_t 
  * planned; 1 .. 4096 = that many slices, never more than documents).  0; -2 and zeros for n_docs < 0, nq < 1 or pref outside 0 .. 4096;
  * -1 for a NULL plan.                                                                                                              */
 BERT_API int32_t bert_hip_test_token_index_plan(int32_t n_docs, int32_t nq, int32_t pref, int32_t *plan);
+/* How many consecutive queries one workgroup of a token index's scan serves in a chunk of nq queries of at most max_q_len tokens with
+ * this k (token_index_kernels.h token_query_group, the function the search itself calls; no GPU): 1 = the ungrouped kernel, 2 .. 4 = the
+ * grouped one.  key: the value of the tuning key "token_index_query_group" (0 = planned).  dtype 2 and 4: always 1.  -2 for a dim, dtype,
+ * max_q_len or k a search refuses, nq < 1 or key outside 0 .. 4.                                                                   */
+BERT_API int32_t bert_hip_test_late_index_query_group(int32_t dim, int32_t dtype, int32_t max_q_len, int32_t nq, int32_t k, int32_t key);
 /* The checks bert_hip_late_index_load runs on a file (token_index_file.h; the format is in bert_hip.h "LATE INDEX"), without a device.
  * _header: buf holds the first buf_len bytes of a file of file_bytes bytes; 0 and fields = {version, dim, n_docs, has_live, the low
  * and the high 32 bits of n_tokens} for a header this build loads, -1 and the reason in err (err_cap bytes) otherwise.  _body: fields
