@@ -1,7 +1,9 @@
 // token_index.cpp — the host side of the token index (token_index.h): storage and its growth, the add forms, the search and its
 // chunks, rescoring, reading a document back, the checks of the host forms, compaction and the file form (live bits, remove, stream
-// and event: index_frame.h; file frame: index_io.h).  Every kernel is in token_index.hip (both forms), maxsim.hip or search.hip (the merge, the live bits of added documents) and reached through
-// token_index_kernels.h / kernels.h / search_kernels.h.
+// and event: index_frame.h; file frame: index_io.h).  What differs between the three stored forms is read from TOKEN_FORMS
+// (token_index_kernels.h).  Every kernel is in token_index.hip (the scan of all three forms, the quantisers, pairs, gather),
+// token_index_grouped.hip (the grouped f16 scan), maxsim.hip or search.hip (the merge, the live bits of added documents) and reached
+// through token_index_kernels.h / kernels.h / search_kernels.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,12 +68,14 @@ bool token_cu_ok(const int32_t *cu, int n) {
 TokenIndex *TokenIndex::create(Engine *eng, int dim, int dtype, std::string &err) {
     if (!eng) { err = "no device engine"; return nullptr; }
     if (dim < 8 || dim > MAXSIM_MAX_H || dim % 8) { err = "dim must be a multiple of 8 in 8 .. " + std::to_string(MAXSIM_MAX_H); return nullptr; }
-    if (dtype != 1 && dtype != 2 && dtype != 4) { err = "dtype must be 1 (f16), 2 (int8) or 4 (mxfp4)"; return nullptr; }
+    const TokenForm *form = token_form(dtype);
+    if (!form) { err = "dtype must be 1 (f16), 2 (int8) or 4 (mxfp4)"; return nullptr; }
     DeviceGuard g(eng->device());
     TokenIndex *ix = new TokenIndex;
     ix->dim_ = dim;
     ix->dtype_ = dtype;
-    ix->dpad_ = dtype == 4 ? token_mx_dpad(dim) : token_i8_dpad(dim);
+    ix->form_ = form;
+    ix->dpad_ = token_dpad(*form, dim);
     ix->cu_h_.assign(1, 0);
     if (!ix->open(eng, "token index", err)) { delete ix; return nullptr; }
     // (cu[0] = 0 is there from the start: an empty index is searched like any other)
@@ -120,9 +124,10 @@ bool TokenIndex::grow_storage(long long n_docs, long long n_tokens, std::string 
     if (n_tokens > cap_tok_) {
         const long long cap = std::min<long long>(INT_MAX, std::max<long long>({n_tokens, (long long)cap_tok_ * 3 / 2, 4096}));
         char *pr = nullptr;
-        float *ps = nullptr;                                 // (the int8 form's scales grow with its codes)
+        float *ps = nullptr;                                 // (a form with scales beside its rows: they grow with the rows)
         const size_t row_bytes = this->row_bytes();
-        if (hipMalloc((void **)&pr, (size_t)cap * row_bytes) != hipSuccess || (dtype_ == 2 && hipMalloc((void **)&ps, (size_t)cap * 4) != hipSuccess)) {
+        const bool scales = token_quant_scales(form_->rows);
+        if (hipMalloc((void **)&pr, (size_t)cap * row_bytes) != hipSuccess || (scales && hipMalloc((void **)&ps, (size_t)cap * 4) != hipSuccess)) {
             (void)hipGetLastError();
             if (pr) (void)hipFree(pr);
             err = "hipMalloc (token index rows) failed";
@@ -152,18 +157,12 @@ bool TokenIndex::grow_search(int n_docs, int nqc, int k, std::string &err) {
 
 bool TokenIndex::grow_queries(int nqc, int max_q_len, std::string &err) {
     const size_t slots = (size_t)nqc * max_q_len;
-    if (dtype_ == 4) return grow(q_codes_, slots * token_mx_query_bytes(dim_), err);
-    return grow(q_codes_, slots * dpad_, err) && grow(q_scales_, slots * 4, err);
+    return grow(q_codes_, slots * TOKEN_QUANT_ROW_BYTES[form_->queries](dim_), err) && (!token_quant_scales(form_->queries) || grow(q_scales_, slots * 4, err));
 }
 
 void TokenIndex::quantize_rows(const void *d_src, bool src_f32, long long n, long long at, hipStream_t s) {
-    if (dtype_ == 4) {
-        TokenMxQuantizeArgs qa{d_src, (uint8_t *)rows_ + (size_t)at * row_bytes(), n, dim_, dpad_};
-        eng_->timed_launch("token_mx_quantize", 0.0, s, [&] { launch_token_mx_quantize(qa, src_f32, false, s); });
-        return;
-    }
-    TokenI8QuantizeArgs qa{d_src, (int8_t *)rows_ + (size_t)at * dpad_, scales_ + at, n, dim_, dpad_};
-    eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, src_f32, s); });
+    const TokenQuantizeArgs qa{d_src, rows_ + (size_t)at * row_bytes(), scales_ ? scales_ + at : nullptr, n, dim_, dpad_};
+    eng_->timed_launch(form_->quantize, 0.0, s, [&] { launch_token_quantize(form_->rows, qa, src_f32, s); });
 }
 
 int TokenIndex::reserve(int n_docs, int64_t n_tokens, int n_queries, int max_q_len, int k, std::string &err) {
@@ -282,27 +281,32 @@ void TokenIndex::truncate(int n) {
     n_tok_ = cu_h_.back();
 }
 
+bool TokenIndex::read_rows(int64_t t0, int len, void *rows, float *scales, std::string &err) {
+    const size_t rb = row_bytes();
+    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, false);
+    HIP_OK(hipMemcpyAsync(rows, rows_ + (size_t)t0 * rb, (size_t)len * rb, hipMemcpyDeviceToHost, stream_), err, false);
+    if (scales_) HIP_OK(hipMemcpyAsync(scales, scales_ + t0, (size_t)len * 4, hipMemcpyDeviceToHost, stream_), err, false);
+    HIP_OK(hipStreamSynchronize(stream_), err, false);
+    return true;
+}
+
 int TokenIndex::get_doc(int id, float *rows, int cap_tokens, std::string &err) {
     if (id < 0 || id >= n_) { err = "get_doc: id " + std::to_string(id) + " outside [0, " + std::to_string(n_) + ")"; return -2; }
-    const int len = cu_h_[(size_t)id + 1] - cu_h_[(size_t)id];
+    const int t0 = cu_h_[(size_t)id], len = cu_h_[(size_t)id + 1] - t0;
     if (!rows || cap_tokens < len) return len;
     DeviceGuard g(eng_->device());
+    const size_t rb = row_bytes();
+    std::vector<uint8_t> b((size_t)len * rb);
+    std::vector<float> scales(scales_ ? (size_t)len : 0);
+    if (!read_rows(t0, len, b.data(), scales.data(), err)) return -3;
+    // (the comparisons of dtype_ below: the one place a form's stored bits are interpreted on the host)
     if (dtype_ == 2) {
-        std::vector<int8_t> codes((size_t)len * dpad_);
-        std::vector<float> sc((size_t)len);
-        if (const int r = get_codes(id, codes.data(), sc.data(), len, err); r < 0) return r;
+        const int8_t *codes = (const int8_t *)b.data();
         for (int t = 0; t < len; ++t)
-            for (int e = 0; e < dim_; ++e) rows[(size_t)t * dim_ + e] = (float)codes[(size_t)t * dpad_ + e] * sc[(size_t)t];
-        return len;
-    }
-    if (dtype_ == 4) {
+            for (int e = 0; e < dim_; ++e) rows[(size_t)t * dim_ + e] = (float)codes[(size_t)t * dpad_ + e] * scales[(size_t)t];
+    } else if (dtype_ == 4) {
         // value(code) * 2^(scale byte - 127), exact in f32; NaN for a token whose scale bytes are 0xFF
         static const float E2M1[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
-        const size_t rb = row_bytes();
-        std::vector<uint8_t> b((size_t)len * rb);
-        HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
-        HIP_OK(hipMemcpyAsync(b.data(), rows_ + (size_t)cu_h_[(size_t)id] * rb, b.size(), hipMemcpyDeviceToHost, stream_), err, -3);
-        HIP_OK(hipStreamSynchronize(stream_), err, -3);
         for (int t = 0; t < len; ++t) {
             const uint8_t *r = b.data() + (size_t)t * rb;
             for (int e = 0; e < dim_; ++e) {
@@ -311,28 +315,21 @@ int TokenIndex::get_doc(int id, float *rows, int cap_tokens, std::string &err) {
                 rows[(size_t)t * dim_ + e] = sc == 0xffu ? std::nanf("") : code & 8u ? -v : v;
             }
         }
-        return len;
+    } else {
+        const half_t *h = (const half_t *)b.data();
+        for (size_t i = 0; i < (size_t)len * dim_; ++i) rows[i] = (float)h[i];
     }
-    std::vector<half_t> h((size_t)len * dim_);
-    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
-    HIP_OK(hipMemcpyAsync(h.data(), (const half_t *)rows_ + (size_t)cu_h_[(size_t)id] * dim_, h.size() * 2, hipMemcpyDeviceToHost, stream_), err, -3);
-    HIP_OK(hipStreamSynchronize(stream_), err, -3);
-    for (size_t i = 0; i < h.size(); ++i) rows[i] = (float)h[i];
     return len;
 }
 
 int TokenIndex::get_codes(int id, int8_t *codes, float *scales, int cap_tokens, std::string &err) {
-    if (dtype_ == 4) { err = "get_codes: the index holds mxfp4 rows (dtype 4), not int8 codes"; return -2; }
-    if (dtype_ != 2) { err = "get_codes: the index holds f16 rows (dtype 1), not int8 codes"; return -2; }
+    // (an int8-only entry point by contract: the comparison of dtype_ is its refusal of every other form)
+    if (dtype_ != 2) { err = std::string("get_codes: the index holds ") + form_->name + " rows (dtype " + std::to_string(dtype_) + "), not int8 codes"; return -2; }
     if (id < 0 || id >= n_) { err = "get_codes: id " + std::to_string(id) + " outside [0, " + std::to_string(n_) + ")"; return -2; }
     const int t0 = cu_h_[(size_t)id], len = cu_h_[(size_t)id + 1] - t0;
     if (!codes || !scales || cap_tokens < len) return len;
     DeviceGuard g(eng_->device());
-    HIP_OK(hipStreamWaitEvent(stream_, busy_, 0), err, -3);
-    HIP_OK(hipMemcpyAsync(codes, rows_ + (size_t)t0 * dpad_, (size_t)len * dpad_, hipMemcpyDeviceToHost, stream_), err, -3);
-    HIP_OK(hipMemcpyAsync(scales, scales_ + t0, (size_t)len * 4, hipMemcpyDeviceToHost, stream_), err, -3);
-    HIP_OK(hipStreamSynchronize(stream_), err, -3);
-    return len;
+    return read_rows(t0, len, codes, scales, err) ? len : -3;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -351,13 +348,12 @@ int TokenIndex::search_any(int nq, const int32_t *d_qcu, const void *d_q, bool q
     return scan_chunks(nq, d_qcu, d_q, q_f32, max_q_len, k, d_ids, d_scores, s, err, d_allow, nullptr, 0);
 }
 
-// The chunk loop of every search and of the int8 rescore: per chunk of up to QCHUNK queries the plan, the int8 form's queries into the
-// workspace (the kernel applies the scan's guards to d_qcu), the scan and the merge of the slices' lists.  A search (d_cand null) scans
+// The chunk loop of every search and of the LISTED rescore: per chunk of up to QCHUNK queries the plan, a quantised form's queries into
+// the workspace (the kernel applies the scan's guards to d_qcu), the scan and the merge of the slices' lists.  A search (d_cand null) scans
 // the n_ documents under live_ / d_allow; a rescore scans the n_cand positions of each query's candidate list — the search's plan with
 // n_cand in the documents' place — and tests live_ per id.  The workspace [nq][slices][k] grows by the same bound over either count
 int TokenIndex::scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool q_f32, int max_q_len, int k, int32_t *d_ids, float *d_scores,
                             hipStream_t s, std::string &err, const uint32_t *d_allow, const int32_t *d_cand, int n_cand) {
-    const bool i8 = dtype_ == 2, mx = dtype_ == 4;
     const int n_list = d_cand ? n_cand : n_;
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
@@ -377,24 +373,16 @@ int TokenIndex::scan_chunks(int nq, const int32_t *d_qcu, const void *d_q, bool 
         a.rows = rows_; a.cu = cu_; a.q = d_q; a.qcu = d_qcu + c0; a.ws_s = ws_s_.as<float>(); a.ws_i = ws_i_.as<int>();
         a.n_docs = n_; a.dim = dim_; a.dpad = dpad_; a.nq = c; a.max_q_len = max_q_len; a.n_slices = p.n_slices; a.slice_docs = p.slice_docs;
         a.k = k; a.L = token_list_L(k); a.n_items = n_groups * p.n_slices; a.group = G; a.n_groups = n_groups;
-        if (i8) {
-            TokenI8QuantizeArgs qa{d_q, q_codes_.as<int8_t>(), q_scales_.as<float>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
-            eng_->timed_launch("token_i8_quantize", 0.0, s, [&] { launch_token_i8_quantize(qa, q_f32, s); });
+        if (quantised()) {
+            // (q_scales_ is null where the queries' form has no scales)
+            const TokenQuantizeArgs qa{d_q, q_codes_.p, q_scales_.as<float>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
+            eng_->timed_launch(form_->quantize, 0.0, s, [&] { launch_token_quantize(form_->queries, qa, q_f32, s); });
             a.scales = scales_; a.q = q_codes_.p; a.q_scales = q_scales_.as<float>();
-        }
-        if (mx) {
-            TokenMxQuantizeArgs qa{d_q, q_codes_.as<uint8_t>(), (long long)c * max_q_len, dim_, dpad_, d_qcu + c0, max_q_len};
-            eng_->timed_launch("token_mx_quantize", 0.0, s, [&] { launch_token_mx_quantize(qa, q_f32, true, s); });
-            a.q = q_codes_.p;
         }
         // (removed documents or an allow-list: the masked kernel, the same plan and workspace; an empty index has no words to read)
         if (d_cand) { a.live = live_; a.cand = d_cand + (size_t)c0 * n_cand; a.n_cand = n_cand; }
         else if (n_ > 0) { a.live = live_; a.allow = d_allow; }
-        const bool masked = a.live || a.allow;
-        const char *label = mx ? (d_cand ? "token_mxfp4_rescore" : masked ? "token_mxfp4_scan_masked" : "token_mxfp4_scan")
-                            : d_cand ? "token_i8_rescore" : i8 ? (masked ? "token_i8_scan_masked" : "token_i8_scan") : (masked ? "token_index_scan_masked" : "token_index_scan");
-        if (G >= 2) eng_->timed_launch(masked ? "token_index_scan_grouped_masked" : "token_index_scan_grouped", 0.0, s, [&] { launch_token_scan_grouped(a, s); });
-        else eng_->timed_launch(label, 0.0, s, [&] { launch_token_scan(dtype_, a, s); });
+        eng_->timed_launch(token_scan_label(dtype_, a), 0.0, s, [&] { launch_token_scan(dtype_, a, s); });
         enqueue_merge(c, p.n_slices * k, k, d_ids + (size_t)c0 * k, d_scores + (size_t)c0 * k, s);
     }
     HIP_OK(hipGetLastError(), err, -3);
@@ -460,9 +448,9 @@ int TokenIndex::rescore_device(int nq, const int32_t *d_qcu, const half_t *d_q, 
                                float *d_scores, hipStream_t s, std::string &err) {
     if (const int go = check_rescore(nq, d_qcu, d_q, n_cand, d_cand, k, d_ids, d_scores, err); go <= 0) return go;
     if ((uintptr_t)d_q & 15) { err = "rescore: the query rows must be 16-byte aligned"; return -2; }
-    // (the int8 form: the scan's kernel over the candidate lists; the device form knows no query length, so the launch is sized for the
-    // longest a search takes)
-    if (quantised()) return scan_chunks(nq, d_qcu, d_q, false, max_query_tokens(), k, d_ids, d_scores, s, err, nullptr, d_cand, n_cand);
+    // (the int8 and mxfp4 forms: the scan's kernel over the candidate lists; the device form knows no query length, so the launch is
+    // sized for the longest a search takes)
+    if (form_->rescore) return scan_chunks(nq, d_qcu, d_q, false, max_query_tokens(), k, d_ids, d_scores, s, err, nullptr, d_cand, n_cand);
     DeviceGuard g(eng_->device());
     Engine::StreamOp op;
     if (!eng_->op_begin(s, busy_, op, err)) return -3;
@@ -510,9 +498,13 @@ int TokenIndex::remove(int n, const int32_t *ids, std::string &err) {
     return (int)fresh.size();
 }
 
+bool TokenIndex::has_file_form(const char *what, std::string &err) const {
+    if (!form_->has_file) err = std::string(what) + ": not available for an " + form_->name + " token index";
+    return form_->has_file;
+}
+
 int TokenIndex::compact(int32_t *old_ids, std::string &err) {
-    if (dtype_ == 2) { err = "compact: not available for an int8 token index"; return -2; }
-    if (dtype_ == 4) { err = "compact: not available for an mxfp4 token index"; return -2; }
+    if (!has_file_form("compact", err)) return -2;
     DeviceGuard g(eng_->device());
     HIP_OK(hipEventSynchronize(busy_), err, -3);
     HIP_OK(hipStreamSynchronize(stream_), err, -3);
@@ -569,22 +561,24 @@ constexpr size_t FILE_PIECE = (size_t)32 << 20;
 
 }  // namespace
 
-bool TokenIndex::save(const char *path, std::string &err) {
-    if (!path || !*path) { err = "a path is required"; return false; }
+int TokenIndex::save(const char *path, std::string &err) {
+    if (!path || !*path) { err = "a path is required"; return -2; }
+    if (!has_file_form("save", err)) return -2;
     DeviceGuard g(eng_->device());
-    HIP_OK(hipEventSynchronize(busy_), err, false);
-    HIP_OK(hipStreamSynchronize(stream_), err, false);
+    HIP_OK(hipEventSynchronize(busy_), err, -3);
+    HIP_OK(hipStreamSynchronize(stream_), err, -3);
     TokenIndexFileHeader h;
     h.dim = (uint32_t)dim_; h.n_docs = (uint32_t)n_; h.has_live = live_ ? 1u : 0u; h.n_tokens = (uint64_t)n_tok_;
     unsigned char hdr[INDEX_HEADER_BYTES];
     token_index_header_write(h, hdr);
-    return write_atomically(path, err, [&](FILE *f) {
+    const bool ok = write_atomically(path, err, [&](FILE *f) {
         std::vector<char> buf;
         // (the lengths and the live words come from the mirrors; the mirror's bits at and beyond size are zero)
         return fwrite(hdr, 1, sizeof hdr, f) == sizeof hdr && fwrite(cu_h_.data(), 4, (size_t)n_ + 1, f) == (size_t)n_ + 1 &&
                device_to_file(f, rows_, (size_t)n_tok_ * dim_ * 2, FILE_PIECE, buf, err) &&
                (!live_ || fwrite(bits_.words.data(), 4, live_words(n_), f) == live_words(n_));
     });
+    return ok ? 0 : -3;
 }
 
 TokenIndex *TokenIndex::load(Engine *eng, FILE *f, const TokenIndexFileHeader &h, std::string &err) {

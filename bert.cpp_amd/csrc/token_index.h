@@ -10,13 +10,15 @@
 // documents' rows into a fresh allocation on the device; save / load move the file form (token_index_file.h) in pieces.
 // A chunk of several queries over f16 rows may be scanned in groups: token_index_scan_grouped_kernel (token_index_grouped.hip), one
 // workgroup per (G consecutive queries, slice), G by token_query_group and the tuning key "token_index_query_group"; the same bits.
-// dtype 2, the int8 form (token_index_kernels.h states it): rows are int8 codes of dpad bytes with one f32 scale per token, every add
-// quantises on the device, a search quantises its queries into a workspace that reserve sizes and scans with token_index_scan_kernel's
-// int8 form, and a rescore is the same kernel over the candidate lists instead of maxsim.  The bitmap, the event, the streams, the
-// chunk loop, commit and the host mirrors are the f16 form's.  compact, save and load are the f16 form's alone.
-// dtype 4, the mxfp4 form (token_index_kernels.h states it): rows are the embedding index's mxfp4 rows, per token, scales inside; the
-// adds, the queries' workspace (MXFP8 rows) and the rescore go the int8 form's ways through token_mx_quantize_kernel and the scan's
-// mxfp4 form.  No scale array.
+// Three stored forms, one row each of token_index_kernels.h's TOKEN_FORMS, which is all this class asks about its dtype: what a row
+// and its dpad are, whether scales stand beside the rows, what the adds and the queries are quantised to, whether a rescore is the
+// LISTED scan, whether chunks are grouped, whether compact and the file form exist, and the profiler's names.
+// dtype 2, the int8 form: rows are int8 codes of dpad bytes with one f32 scale per token, every add quantises on the device, a search
+// quantises its queries into a workspace that reserve sizes and scans with token_index_scan_kernel's int8 form, and a rescore is the
+// same kernel over the candidate lists instead of maxsim.  The bitmap, the event, the streams, the chunk loop, commit and the host
+// mirrors are the f16 form's.  compact, save and load are the f16 form's alone.
+// dtype 4, the mxfp4 form: rows are the embedding index's mxfp4 rows, per token, scales inside; the adds, the queries' workspace
+// (MXFP8 rows) and the rescore go the int8 form's ways through token_mx_quantize_kernel and the scan's mxfp4 form.  No scale array.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -73,7 +75,7 @@ public:
     // document id's rows as f32 [len][dim] (the stored f16 values converted exactly): its length; writes iff cap_tokens >= it.  Blocking
     // (the int8 form: (float)code * scale; the mxfp4 form: value(code) * 2^(scale byte - 127), NaN for a token whose scale bytes are 0xFF)
     int get_doc(int id, float *rows, int cap_tokens, std::string &err);
-    // int8 form: the document's codes [len][dpad] and scales [len] as stored: its length; writes iff cap_tokens >= it.  f16 form: -2
+    // int8 form: the document's codes [len][dpad] and scales [len] as stored: its length; writes iff cap_tokens >= it.  Every other form: -2
     int get_codes(int id, int8_t *codes, float *scales, int cap_tokens, std::string &err);
     // ids / scores [nq][k], best first; queries d_q f16 indexed by d_qcu [nq + 1], both in device memory, unchecked (the kernel's
     // guards).  max_q_len: the caller's promise, 1 .. max_query_tokens().  Asynchronous on s.  d_allow: null, or device words
@@ -105,12 +107,12 @@ public:
     int remove(int n, const int32_t *ids, std::string &err);
     // Drops the removed documents: the live ones keep their order and bits and get ids 0 .. n_live - 1; old_ids (nullable) [n_live]
     // receives their former ids.  The new size; the bitmap is gone afterwards.  Fresh storage for the live rows beside the old (the
-    // peak is old + new); -3 and the index unchanged where that fails.  Blocking.  The int8 form: -2, the index unchanged
+    // peak is old + new); -3 and the index unchanged where that fails.  Blocking.  The int8 and mxfp4 forms: -2, the index unchanged
     int compact(int32_t *old_ids, std::string &err);
-    // the file form (token_index_file.h), rows in pieces of 32 MiB through a host buffer; blocking.  load: from f, positioned behind
-    // the header h that token_index_header_check passed
-    // (f16 form only: the C ABI refuses an int8 index with -2 in front of this)
-    bool save(const char *path, std::string &err);
+    // the file form (token_index_file.h), rows in pieces of 32 MiB through a host buffer; blocking.  save: 0, -2 (no path; the int8
+    // and mxfp4 forms, which have no file form: nothing written) or -3.  load: from f, positioned behind the header h that
+    // token_index_header_check passed
+    int save(const char *path, std::string &err);
     static TokenIndex *load(Engine *eng, FILE *f, const TokenIndexFileHeader &h, std::string &err);
 
 private:
@@ -119,8 +121,12 @@ private:
     bool grow_search(int n_docs, int nqc, int k, std::string &err);
     // int8 form: the queries' codes and scales, [nqc][max_q_len] rows; mxfp4 form: their MXFP8 rows
     bool grow_queries(int nqc, int max_q_len, std::string &err);
-    size_t row_bytes() const { return dtype_ == 4 ? token_mx_row_bytes(dim_) : dtype_ == 2 ? (size_t)dpad_ : (size_t)dim_ * 2; }
-    bool quantised() const { return dtype_ != 1; }       // the int8 and mxfp4 forms: adds, queries and rescores through a quantiser
+    size_t row_bytes() const { return form_->row_bytes(dim_); }
+    bool quantised() const { return form_->rows != TOKEN_QUANT_NONE; }   // the int8 and mxfp4 forms: adds, queries and rescores through a quantiser
+    // stored rows t0 .. t0 + len - 1 -> rows, and where the form has scales theirs -> scales, behind what the index has queued; blocking
+    bool read_rows(int64_t t0, int len, void *rows, float *scales, std::string &err);
+    // compact and save: the form has no compact / file form -> false and "<what>: not available for an <form> token index"
+    bool has_file_form(const char *what, std::string &err) const;
     // int8 and mxfp4 forms: n rows (f32 or f16, device memory) -> the stored form from stored row `at` on, on s
     void quantize_rows(const void *d_src, bool src_f32, long long n, long long at, hipStream_t s);
     // the searches and rescores behind the public forms: the queries d_q are f16, or (q_f32: the host forms of the int8 index) f32
@@ -140,6 +146,7 @@ private:
     int stage_queries(const char *what, int nq, const int32_t *qcu, const float *q_rows, int limit, int &max_len, std::string &err);
 
     int dim_ = 0, dtype_ = 1, dpad_ = 0;
+    const TokenForm *form_ = nullptr;                   // dtype_'s row of TOKEN_FORMS
     int cap_docs_ = 0;                                  // capacity of cu_ in documents (the documents, n_, and the bitmap: index_frame.h)
     int64_t n_tok_ = 0, cap_tok_ = 0;                   // rows; capacity of rows_ in rows
     char *rows_ = nullptr;                              // [cap_tok_][row_bytes()]: f16 rows, int8 codes, or mxfp4 rows

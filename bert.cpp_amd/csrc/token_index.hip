@@ -1,7 +1,9 @@
 // token_index.hip — the device code of the token index (gfx950; bert_hip.h "TOKEN INDEX", "TOKEN INDEX, int8 form" and "TOKEN INDEX,
 // MXFP4 form"): documents' token rows in HBM — f16 rows, int8 codes with one f32 scale per token, or MXFP4 rows with their scales inside —
-// and their exact MaxSim top-k search.  The kernels and their launchers (token_index_kernels.h, which states the stored forms); the TokenIndex class that plans and orders them is token_index.cpp
-// (token_index.h).
+// and their exact MaxSim top-k search.  The kernels and their launchers (token_index_kernels.h, which states the three stored forms
+// and their table); the TokenIndex class that plans and orders them is token_index.cpp (token_index.h).  The second scan kernel, the
+// grouped scan of the f16 form, is token_index_grouped.hip; its two instantiations are launched and opted into the LDS from here
+// (TOKEN_SCANS, launch_token_scan: the ten scan instantiations stated once).
 //
 //   token_index_scan_kernel<Form, MASKED, LISTED>  ONE skeleton — the work map, the guards, the list, the step mask, the round loop and
 //                   its barriers, the selection, the write-out — stated once; a Form (F16Form, I8Form, Mxfp4Form) holds only how a query
@@ -71,10 +73,11 @@
 //                   the first scale byte of every query token (a query with one: the guards' lists); score at the first scale byte of
 //                   every document token, from the dwords it holds (such a document is never pushed) — not at what the MFMA makes of it.
 //   token_mx_quantize_kernel  f32 or f16 rows -> MXFP4 rows (adds) or MXFP8 rows (queries), one wave per row by device.h's quantize_row_mx —
-//                   the embedding index's rule, stated there once — with token_i8_quantize_kernel's row addressing and guards.
+//                   the embedding index's rule, stated there once.
 //   token_i8_quantize_kernel  f32 or f16 rows (f16 is converted exactly) -> codes and scales, one wave per row by device.h's
-//                   quantize_row_i8 — the embedding index's rule, stated there once.  Serves the adds and, with qcu, the queries of every
-//                   search and rescore.
+//                   quantize_row_i8 — the embedding index's rule, stated there once.
+//                   Both take TokenQuantizeArgs and share token_quantize_src_row, the slot addressing and the guards: they serve the
+//                   adds and, with qcu, the queries of every search and rescore, through one launcher (launch_token_quantize).
 //   token_index_pairs_kernel  an f16 rescore's candidate ids as maxsim's pair list (token_index_kernels.h); a removed id is no candidate.
 //   token_index_gather_kernel  compaction: the kept documents' rows into a fresh allocation (see the kernel).
 #include <hip/hip_runtime.h>
@@ -453,37 +456,35 @@ __global__ __launch_bounds__(NT) void token_index_scan_kernel(TokenScanArgs a) {
     for (int j = tid; j < k; j += NT) { a.ws_s[out + j] = ls[j]; a.ws_i[out + j] = li[j]; }
 }
 
-// One wave per row (device.h quantize_row_i8); the row addressing is TokenI8QuantizeArgs' (token_index_kernels.h)
-template <class T>
-__global__ __launch_bounds__(256) void token_i8_quantize_kernel(TokenI8QuantizeArgs a) {
-    const int lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= a.n) return;                                      // (the whole wave)
-    long long row = w;
-    if (a.qcu) {
-        const int qi = (int)(w / a.max_q_len), t = (int)(w - (long long)qi * a.max_q_len);
-        const int q0 = a.qcu[qi], len = a.qcu[qi + 1] - q0;
-        if (len <= 0 || q0 < 0 || len > a.max_q_len || t >= len) return;
-        row = (long long)q0 + t;
-    }
-    quantize_row_i8((const T *)a.src + row * a.dim, a.dim, a.dpad, a.codes + w * a.dpad, a.scales + w, lane);
+// The slot addressing and the guards of both quantisers (TokenQuantizeArgs, token_index_kernels.h): the row of src that slot w
+// takes, or -1: the slot is left alone
+__device__ __forceinline__ long long token_quantize_src_row(long long w, const int32_t *qcu, int max_q_len) {
+    if (!qcu) return w;
+    const int qi = (int)(w / max_q_len), t = (int)(w - (long long)qi * max_q_len);
+    const int q0 = qcu[qi], len = qcu[qi + 1] - q0;
+    return len <= 0 || q0 < 0 || len > max_q_len || t >= len ? -1 : (long long)q0 + t;
 }
 
-// One wave per row (device.h quantize_row_mx, two passes: dim <= MAXSIM_MAX_H); the row addressing and the guards are
-// token_i8_quantize_kernel's (TokenMxQuantizeArgs, token_index_kernels.h)
-template <class T, bool FP8>
-__global__ __launch_bounds__(256) void token_mx_quantize_kernel(TokenMxQuantizeArgs a) {
+// One wave per row (device.h quantize_row_i8)
+template <class T>
+__global__ __launch_bounds__(256) void token_i8_quantize_kernel(TokenQuantizeArgs a) {
     const int lane = threadIdx.x & 63;
     const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= a.n) return;                                      // (the whole wave)
-    long long row = w;
-    if (a.qcu) {
-        const int qi = (int)(w / a.max_q_len), t = (int)(w - (long long)qi * a.max_q_len);
-        const int q0 = a.qcu[qi], len = a.qcu[qi + 1] - q0;
-        if (len <= 0 || q0 < 0 || len > a.max_q_len || t >= len) return;
-        row = (long long)q0 + t;
-    }
-    quantize_row_mx<FP8, MAXSIM_MAX_H / 512>((const T *)a.src + row * a.dim, a.dim, a.dpad, a.dst + w * mx_row_bytes(FP8 ? a.dpad : a.dpad >> 1, a.dpad), lane);
+    const long long row = token_quantize_src_row(w, a.qcu, a.max_q_len);
+    if (row < 0) return;
+    quantize_row_i8((const T *)a.src + row * a.dim, a.dim, a.dpad, (int8_t *)a.dst + w * a.dpad, a.scales + w, lane);
+}
+
+// One wave per row (device.h quantize_row_mx, two passes: dim <= MAXSIM_MAX_H)
+template <class T, bool FP8>
+__global__ __launch_bounds__(256) void token_mx_quantize_kernel(TokenQuantizeArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= a.n) return;                                      // (the whole wave)
+    const long long row = token_quantize_src_row(w, a.qcu, a.max_q_len);
+    if (row < 0) return;
+    quantize_row_mx<FP8, MAXSIM_MAX_H / 512>((const T *)a.src + row * a.dim, a.dim, a.dpad, (uint8_t *)a.dst + w * mx_row_bytes(FP8 ? a.dpad : a.dpad >> 1, a.dpad), lane);
 }
 
 __global__ __launch_bounds__(256) void token_index_pairs_kernel(TokenPairsArgs a) {
@@ -521,6 +522,15 @@ __global__ __launch_bounds__(GATHER_NT) void token_index_gather_kernel(TokenGath
 
 DeviceFlags g_token_scan_lds;
 
+// The instantiations of token_index_scan_kernel, stated once: [the form's row of TOKEN_FORMS][plain, masked, listed] (null: the f16
+// form's rescore is maxsim's).  token_scan_grouped_kernels() (token_index_grouped.hip) holds the other two of the ten
+using TokenScanKernel = void (*)(TokenScanArgs);
+constexpr TokenScanKernel TOKEN_SCANS[3][3] = {
+    {token_index_scan_kernel<F16Form, false, false>, token_index_scan_kernel<F16Form, true, false>, nullptr},
+    {token_index_scan_kernel<I8Form, false, false>, token_index_scan_kernel<I8Form, true, false>, token_index_scan_kernel<I8Form, false, true>},
+    {token_index_scan_kernel<Mxfp4Form, false, false>, token_index_scan_kernel<Mxfp4Form, true, false>, token_index_scan_kernel<Mxfp4Form, false, true>},
+};
+
 // rows per launch of the quantisation: 2^22 waves of 64 threads, far below the 2^32 a launch's thread count wraps at
 constexpr long long QUANT_MAX_ROWS = 1ll << 22;
 
@@ -530,68 +540,51 @@ void token_index_kernels_init() {
     // (beyond the 64 KiB a launch gets unasked; a launch that still cannot have it fails, and the search reports the launch error)
     configure_once(g_token_scan_lds, [] {
         bool ok = true;
-        for (const void *f : {(const void *)token_index_scan_kernel<F16Form, false, false>, (const void *)token_index_scan_kernel<F16Form, true, false>,
-                              (const void *)token_index_scan_kernel<I8Form, false, false>, (const void *)token_index_scan_kernel<I8Form, true, false>,
-                              (const void *)token_index_scan_kernel<I8Form, false, true>, (const void *)token_index_scan_kernel<Mxfp4Form, false, false>,
-                              (const void *)token_index_scan_kernel<Mxfp4Form, true, false>, (const void *)token_index_scan_kernel<Mxfp4Form, false, true>})
-            ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOKEN_LDS_MAX) == hipSuccess && ok;
+        auto opt_in = [&](const void *f) { ok = (!f || hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOKEN_LDS_MAX) == hipSuccess) && ok; };
+        for (const auto &form : TOKEN_SCANS)
+            for (const TokenScanKernel f : form) opt_in((const void *)f);
+        for (int m = 0; m < 2; ++m) opt_in((const void *)token_scan_grouped_kernels()[m]);
         if (!ok) (void)hipGetLastError();                      // (not left behind for an unrelated call's check)
     });
-    token_index_grouped_kernels_init();
 }
 
-void launch_token_scan(int dtype, const TokenScanArgs &a, hipStream_t s) {
+const char *token_scan_label(int dtype, const TokenGroupScanArgs &a) {
+    const TokenForm &f = *token_form(dtype);
+    const bool masked = a.live || a.allow;
+    return a.group >= 2 ? f.grouped[masked] : a.cand ? f.rescore : f.scan[masked];
+}
+
+void launch_token_scan(int dtype, const TokenGroupScanArgs &a, hipStream_t s) {
     if (a.n_items <= 0) return;
     const int grid = xcd_grid(a.n_items);
-    const size_t lds = token_scan_lds_bytes(a.dim, dtype, a.max_q_len, a.k);
     const bool masked = a.live || a.allow;
-    if (dtype == 4) {
-        if (a.cand) BERT_LAUNCH((token_index_scan_kernel<Mxfp4Form, false, true>), dim3(grid), dim3(NT), lds, s, a);
-        else if (masked) BERT_LAUNCH((token_index_scan_kernel<Mxfp4Form, true, false>), dim3(grid), dim3(NT), lds, s, a);
-        else BERT_LAUNCH((token_index_scan_kernel<Mxfp4Form, false, false>), dim3(grid), dim3(NT), lds, s, a);
-    } else if (dtype == 2) {
-        if (a.cand) BERT_LAUNCH((token_index_scan_kernel<I8Form, false, true>), dim3(grid), dim3(NT), lds, s, a);
-        else if (masked) BERT_LAUNCH((token_index_scan_kernel<I8Form, true, false>), dim3(grid), dim3(NT), lds, s, a);
-        else BERT_LAUNCH((token_index_scan_kernel<I8Form, false, false>), dim3(grid), dim3(NT), lds, s, a);
-    } else {
-        // (cand is the int8 form's: TokenIndex scores an f16 rescore with maxsim)
-        if (masked) BERT_LAUNCH((token_index_scan_kernel<F16Form, true, false>), dim3(grid), dim3(NT), lds, s, a);
-        else BERT_LAUNCH((token_index_scan_kernel<F16Form, false, false>), dim3(grid), dim3(NT), lds, s, a);
+    if (a.group >= 2) {
+        const TokenGroupScanKernel f = token_scan_grouped_kernels()[masked];
+        BERT_LAUNCH(f, dim3(grid), dim3(NT), token_group_lds_bytes(a.dim, a.max_q_len, a.k, a.group), s, a);
+        return;
     }
+    // (a.cand: the LISTED instantiation, which the f16 form has none of: TokenIndex scores its rescore with maxsim)
+    const TokenScanKernel f = TOKEN_SCANS[token_form(dtype) - TOKEN_FORMS][a.cand ? 2 : masked];
+    BERT_LAUNCH(f, dim3(grid), dim3(NT), token_scan_lds_bytes(a.dim, dtype, a.max_q_len, a.k), s, (const TokenScanArgs &)a);
 }
 
-void launch_token_i8_quantize(const TokenI8QuantizeArgs &a, bool src_f32, hipStream_t s) {
+void launch_token_quantize(TokenQuant target, const TokenQuantizeArgs &a, bool src_f32, hipStream_t s) {
+    using Kernel = void (*)(TokenQuantizeArgs);
+    static constexpr Kernel KERNELS[3][2] = {{token_i8_quantize_kernel<half_t>, token_i8_quantize_kernel<float>},
+                                             {token_mx_quantize_kernel<half_t, false>, token_mx_quantize_kernel<float, false>},
+                                             {token_mx_quantize_kernel<half_t, true>, token_mx_quantize_kernel<float, true>}};
+    const size_t rb = TOKEN_QUANT_ROW_BYTES[target](a.dim);
     // (the queries' form is one launch: at most TokenIndex::QCHUNK * TOKEN_MAX_QUERY slots)
     for (long long r0 = 0; r0 < a.n; r0 += QUANT_MAX_ROWS) {
-        TokenI8QuantizeArgs p = a;
+        TokenQuantizeArgs p = a;
         p.n = std::min(QUANT_MAX_ROWS, a.n - r0);
         if (!a.qcu) {
             p.src = (const char *)a.src + (size_t)r0 * a.dim * (src_f32 ? 4 : 2);
-            p.codes = a.codes + (size_t)r0 * a.dpad;
-            p.scales = a.scales + r0;
+            p.dst = (char *)a.dst + (size_t)r0 * rb;
+            if (a.scales) p.scales = a.scales + r0;
         }
-        const dim3 grid((unsigned)((p.n + 3) / 4));
-        if (src_f32) BERT_LAUNCH(token_i8_quantize_kernel<float>, grid, dim3(256), 0, s, p);
-        else BERT_LAUNCH(token_i8_quantize_kernel<half_t>, grid, dim3(256), 0, s, p);
-        if (a.qcu) break;
-    }
-}
-
-void launch_token_mx_quantize(const TokenMxQuantizeArgs &a, bool src_f32, bool fp8, hipStream_t s) {
-    // (the pieces of launch_token_i8_quantize)
-    const size_t rb = mx_row_bytes(fp8 ? a.dpad : a.dpad >> 1, a.dpad);
-    for (long long r0 = 0; r0 < a.n; r0 += QUANT_MAX_ROWS) {
-        TokenMxQuantizeArgs p = a;
-        p.n = std::min(QUANT_MAX_ROWS, a.n - r0);
-        if (!a.qcu) {
-            p.src = (const char *)a.src + (size_t)r0 * a.dim * (src_f32 ? 4 : 2);
-            p.dst = a.dst + (size_t)r0 * rb;
-        }
-        const dim3 grid((unsigned)((p.n + 3) / 4));
-        if (src_f32 && fp8) BERT_LAUNCH((token_mx_quantize_kernel<float, true>), grid, dim3(256), 0, s, p);
-        else if (src_f32) BERT_LAUNCH((token_mx_quantize_kernel<float, false>), grid, dim3(256), 0, s, p);
-        else if (fp8) BERT_LAUNCH((token_mx_quantize_kernel<half_t, true>), grid, dim3(256), 0, s, p);
-        else BERT_LAUNCH((token_mx_quantize_kernel<half_t, false>), grid, dim3(256), 0, s, p);
+        const Kernel f = KERNELS[target][src_f32];
+        BERT_LAUNCH(f, dim3((unsigned)((p.n + 3) / 4)), dim3(256), 0, s, p);
         if (a.qcu) break;
     }
 }

@@ -242,10 +242,7 @@ int32_t bert_hip_late_index_compact(struct bert_hip_token_index *ix, int32_t *ol
 
 int32_t bert_hip_late_index_save(struct bert_hip_token_index *ix, const char *path) {
     return token_index_call("bert_hip_late_index_save", ix, [&](bert_ctx *, TokenIndex &x, std::string &err) -> int32_t {
-        if (!path || !*path) { err = "a path is required"; return -2; }
-        if (x.dtype() == 2) { err = "save: not available for an int8 token index"; return -2; }
-        if (x.dtype() == 4) { err = "save: not available for an mxfp4 token index"; return -2; }
-        return x.save(path, err) ? 0 : -3;
+        return x.save(path, err);
     });
 }
 

@@ -228,25 +228,11 @@ __global__ __launch_bounds__(NT, 2) void token_index_scan_grouped_kernel(TokenGr
     select_store(sel, gq, a.ws_s, a.ws_i, qf, a.n_slices, slice, tid);
 }
 
-DeviceFlags g_token_group_lds;
-
 }  // namespace
 
-void token_index_grouped_kernels_init() {
-    configure_once(g_token_group_lds, [] {
-        bool ok = true;
-        for (const void *f : {(const void *)token_index_scan_grouped_kernel<false>, (const void *)token_index_scan_grouped_kernel<true>})
-            ok = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TOKEN_LDS_MAX) == hipSuccess && ok;
-        if (!ok) (void)hipGetLastError();                      // (not left behind for an unrelated call's check)
-    });
-}
-
-void launch_token_scan_grouped(const TokenGroupScanArgs &a, hipStream_t s) {
-    if (a.n_items <= 0) return;
-    const int grid = xcd_grid(a.n_items);
-    const size_t lds = token_group_lds_bytes(a.dim, a.max_q_len, a.k, a.group);
-    if (a.live || a.allow) BERT_LAUNCH((token_index_scan_grouped_kernel<true>), dim3(grid), dim3(NT), lds, s, a);
-    else BERT_LAUNCH((token_index_scan_grouped_kernel<false>), dim3(grid), dim3(NT), lds, s, a);
+const TokenGroupScanKernel *token_scan_grouped_kernels() {
+    static constexpr TokenGroupScanKernel KERNELS[2] = {token_index_scan_grouped_kernel<false>, token_index_scan_grouped_kernel<true>};
+    return KERNELS;
 }
 
 }  // namespace bert_hip

@@ -1,6 +1,7 @@
-// token_index_kernels.h — the device code of the token index (token_index.hip) as its host side (token_index.cpp) sees it: the two
-// stored forms, the plan of a scan, the argument blocks and one launcher per kernel.  A launcher only enqueues: the caller reads
-// hipGetLastError.  dtype is the index's: 1 f16, 2 int8, 4 mxfp4.
+// token_index_kernels.h — the device code of the token index (token_index.hip, token_index_grouped.hip) as its host side
+// (token_index.cpp) sees it: the three stored forms and the table that states them (TOKEN_FORMS), the plan of a scan, the argument
+// blocks and the launchers — one for the ten instantiations of the two scan kernels, one for the quantisers, one each for the pairs
+// and the gather kernel.  A launcher only enqueues: the caller reads hipGetLastError.  dtype is the index's: 1 f16, 2 int8, 4 mxfp4.
 //
 // Stored form, f16.  half_t rows[n_tokens][dim], packed, 16-byte aligned (dim a multiple of 8 in 8 .. MAXSIM_MAX_H), and int32
 // cu[n_docs + 1]: document d is rows cu[d] .. cu[d + 1] - 1, never empty — what maxsim.hip takes as its document side, so a rescore
@@ -20,6 +21,7 @@
 //
 // A scan workgroup (token_index_scan_kernel, one kernel with a form per dtype) stages one query in LDS as ceil(n / 32) blocks of 32 rows
 // padded by 16 bytes, what else its form keeps beside them, then a list of L (score, id) entries and a count: token_scan_lds_bytes.
+// The grouped scan of the f16 form (token_index_scan_grouped_kernel) stages up to four queries that way: token_group_lds_bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -54,13 +56,57 @@ __host__ __device__ inline size_t token_mx_query_bytes(int dim) { return mx_row_
 // the mxfp4 form's staged query row: the MXFP8 row, and one more 16-byte slot where its slots come out even (an odd count of slots
 // puts the 32 rows of a ds_read_b128 step on distinct slots of the bank row: 9 at dim 128, 25 at 384, 50 + 1 at 768, 66 + 1 at 1024)
 __host__ __device__ inline int token_mx_ldq(int dim) { const int slots = (int)(token_mx_query_bytes(dim) >> 4); return 16 * (slots | 1); }
-// What a form stages per query.  A block of 32 tokens: rows of dim + 8 halfs (maxsim's padding), or of dpad + 16 bytes of codes (the
-// same 16 bytes), or of token_mx_ldq bytes (the mxfp4 form: codes and scale bytes in one row).  Beside the blocks: nothing, or the
-// int8 form's 512 bytes of query scales
-inline size_t token_query_block_bytes(int dim, int dtype) {
-    return (size_t)TOKEN_QB * (dtype == 4 ? token_mx_ldq(dim) : dtype == 2 ? token_i8_dpad(dim) + 16 : (dim + 8) * 2);
+inline size_t token_f16_row_bytes(int dim) { return (size_t)dim * 2; }
+inline size_t token_i8_row_bytes(int dim) { return (size_t)token_i8_dpad(dim); }
+// What a form stages per query token: a row of dim + 8 halfs (maxsim's padding), of dpad + 16 bytes of codes (the same 16 bytes), or
+// of token_mx_ldq bytes (the mxfp4 form: codes and scale bytes in one row)
+inline size_t token_f16_lds_row_bytes(int dim) { return (size_t)(dim + 8) * 2; }
+inline size_t token_i8_lds_row_bytes(int dim) { return (size_t)token_i8_dpad(dim) + 16; }
+inline size_t token_mx_lds_row_bytes(int dim) { return (size_t)token_mx_ldq(dim); }
+
+// What the quantisers write (launch_token_quantize): the int8 form's codes and scales — stored rows and queries alike —, the mxfp4
+// form's stored rows, or the MXFP8 rows its queries take
+enum TokenQuant { TOKEN_QUANT_NONE = -1, TOKEN_QUANT_I8, TOKEN_QUANT_MXFP4, TOKEN_QUANT_MXFP8 };
+// bytes of a row of such a target, and whether one f32 scale per row goes into an array beside the rows
+constexpr size_t (*TOKEN_QUANT_ROW_BYTES[3])(int dim) = {token_i8_row_bytes, token_mx_row_bytes, token_mx_query_bytes};
+inline bool token_quant_scales(TokenQuant t) { return t == TOKEN_QUANT_I8; }
+
+// Everything the host knows of a stored form, one row per dtype: the place a new form starts.  The device side of a form is its Form
+// in token_index.hip and its entries in that file's list of scan instantiations
+struct TokenForm {
+    int dtype;
+    const char *name;                           // for messages
+    int dpad_step;                              // dpad = dim rounded up to a multiple of this (f16: no kernel reads it; the int8 form's)
+    size_t (*row_bytes)(int dim);               // a stored row
+    // what an add quantises to (its scales beside the rows) and what a search's queries become in the workspace; NONE, both: the rows
+    // are stored as they come and the scan reads the caller's
+    TokenQuant rows, queries;
+    size_t (*lds_row_bytes)(int dim);           // a query token staged in LDS
+    size_t lds_extra;                           // LDS beside the query's blocks (int8: the query's scales)
+    bool has_file;                              // compact and the file form exist
+    // the profiler's names: the scan plain and masked; the grouped scan likewise (null: chunks of this form are never grouped); the
+    // LISTED scan as a rescore (null: a rescore is token_index_pairs_kernel and maxsim); the quantiser (null: none)
+    const char *scan[2], *grouped[2], *rescore, *quantize;
+};
+constexpr TokenForm TOKEN_FORMS[3] = {
+    {1, "f16", 32, token_f16_row_bytes, TOKEN_QUANT_NONE, TOKEN_QUANT_NONE, token_f16_lds_row_bytes, 0, true,
+     {"token_index_scan", "token_index_scan_masked"}, {"token_index_scan_grouped", "token_index_scan_grouped_masked"}, nullptr, nullptr},
+    {2, "int8", 32, token_i8_row_bytes, TOKEN_QUANT_I8, TOKEN_QUANT_I8, token_i8_lds_row_bytes, TOKEN_MAX_QUERY * 4, false,
+     {"token_i8_scan", "token_i8_scan_masked"}, {nullptr, nullptr}, "token_i8_rescore", "token_i8_quantize"},
+    {4, "mxfp4", 64, token_mx_row_bytes, TOKEN_QUANT_MXFP4, TOKEN_QUANT_MXFP8, token_mx_lds_row_bytes, 0, false,
+     {"token_mxfp4_scan", "token_mxfp4_scan_masked"}, {nullptr, nullptr}, "token_mxfp4_rescore", "token_mx_quantize"},
+};
+// the row of dtype, null for a dtype that is no form
+inline const TokenForm *token_form(int dtype) {
+    for (const TokenForm &f : TOKEN_FORMS)
+        if (f.dtype == dtype) return &f;
+    return nullptr;
 }
-inline size_t token_query_extra_bytes(int dtype) { return dtype == 2 ? TOKEN_MAX_QUERY * 4 : 0; }
+inline int token_dpad(const TokenForm &f, int dim) { return (dim + f.dpad_step - 1) / f.dpad_step * f.dpad_step; }
+
+// a staged block of 32 tokens, and what the form keeps beside the blocks
+inline size_t token_query_block_bytes(int dim, int dtype) { return (size_t)TOKEN_QB * token_form(dtype)->lds_row_bytes(dim); }
+inline size_t token_query_extra_bytes(int dtype) { return token_form(dtype)->lds_extra; }
 // the query's blocks, the form's extra bytes, the list (8 L bytes), the count (16)
 inline size_t token_scan_lds_bytes(int dim, int dtype, int max_q_len, int k) {
     return (size_t)token_query_blocks(max_q_len) * token_query_block_bytes(dim, dtype) + token_query_extra_bytes(dtype) + (size_t)token_list_L(k) * 8 + 16;
@@ -107,17 +153,17 @@ inline size_t token_group_lds_bytes(int dim, int max_q_len, int k, int g) {
 inline int token_group_planned(int dim, int nq) { return dim >= 384 && nq >= 8 ? 3 : 1; }
 // G of a chunk of nq queries: the largest value that is at most TOKEN_MAX_GROUP, at most nq, at most the tuning key
 // "token_index_query_group" (key: 1 = never group, 2 .. 4 = at most that many; 0 = token_group_planned) and whose LDS fits
-// TOKEN_LDS_MAX.  1 = the ungrouped kernel, which every other dtype launches whatever the key.  With 32-token queries the LDS allows 4 at
+// TOKEN_LDS_MAX.  1 = the ungrouped kernel, which a form without a grouped scan launches whatever the key.  With 32-token queries the LDS allows 4 at
 // dim <= 384, 3 at 768, 2 at 1024; with 128-token queries at dim 384: 1.  The one place this is decided: the search and the test hook
 // call it, reserve bounds it by token_group_cap
 inline int token_query_group(int dim, int dtype, int max_q_len, int nq, int k, int key) {
-    if (dtype != 1 || nq < 2 || key == 1) return 1;
+    if (!token_form(dtype)->grouped[0] || nq < 2 || key == 1) return 1;
     int g = std::min({TOKEN_MAX_GROUP, nq, key >= 2 ? key : token_group_planned(dim, nq)});
     while (g > 1 && token_group_lds_bytes(dim, max_q_len, k, g) > TOKEN_LDS_MAX) --g;
     return g;
 }
 // the most queries a group of any later search may hold under this key (reserve's workspace bound: max_q_len and k may be smaller then)
-inline int token_group_cap(int dtype, int key) { return dtype != 1 || key == 1 ? 1 : key >= 2 ? std::min(key, TOKEN_MAX_GROUP) : TOKEN_MAX_GROUP; }
+inline int token_group_cap(int dtype, int key) { return !token_form(dtype)->grouped[0] || key == 1 ? 1 : key >= 2 ? std::min(key, TOKEN_MAX_GROUP) : TOKEN_MAX_GROUP; }
 
 // token_index_scan_kernel, every form.  LDS: token_scan_lds_bytes(dim, dtype, max_q_len, k)
 struct TokenScanArgs {
@@ -169,13 +215,14 @@ struct TokenGatherArgs {
     int n, dim;
 };
 
-// token_i8_quantize_kernel: rows of dim values (f32 or f16: f16 is converted exactly) -> codes and scales, one wave per row.
-// qcu == nullptr: rows src[0 .. n) -> rows 0 .. n - 1 of codes / scales.  qcu != nullptr (the queries of a search): n = nq * max_q_len
+// token_i8_quantize_kernel and token_mx_quantize_kernel: rows of dim values (f32 or f16: f16 is converted exactly) -> a TokenQuant's
+// rows, one wave per row, by device.h's quantize_row_i8 (codes to dst, scales beside them) or quantize_row_mx (scales null).
+// qcu == nullptr: rows src[0 .. n) -> rows 0 .. n - 1 of dst / scales.  qcu != nullptr (the queries of a search): n = nq * max_q_len
 // slots; slot qi * max_q_len + t takes row qcu[qi] + t of src where the query passes the scan's guards (not empty, not descending, not
 // starting below 0, at most max_q_len tokens) and t is below its length, and is left alone otherwise: no row outside a query's range is read
-struct TokenI8QuantizeArgs {
+struct TokenQuantizeArgs {
     const void *src;
-    int8_t *codes;
+    void *dst;
     float *scales;
     long long n;
     int dim, dpad;
@@ -183,28 +230,17 @@ struct TokenI8QuantizeArgs {
     int max_q_len = 0;
 };
 
-// token_mx_quantize_kernel: rows of dim values (f32 or f16) -> MX rows by device.h's quantize_row_mx, one wave per row: the mxfp4
-// form (fp8 false: stored rows of token_mx_row_bytes) or the mxfp8 form (queries, token_mx_query_bytes).  n, qcu and max_q_len as
-// TokenI8QuantizeArgs': the same slot addressing and the same guards
-struct TokenMxQuantizeArgs {
-    const void *src;
-    uint8_t *dst;
-    long long n;
-    int dim, dpad;
-    const int32_t *qcu = nullptr;
-    int max_q_len = 0;
-};
-
+// token_index_grouped.hip's entries of token_index.hip's list of scan instantiations: its kernel plain [0] and masked [1]
+using TokenGroupScanKernel = void (*)(TokenGroupScanArgs);
+const TokenGroupScanKernel *token_scan_grouped_kernels();
 // lets every scan instantiation of the current device have TOKEN_LDS_MAX of LDS
 void token_index_kernels_init();
-void token_index_grouped_kernels_init();                // (token_index_grouped.hip's part of it)
-// the instantiation of dtype's form: listed if a.cand is set (int8 and mxfp4), else masked if a.live or a.allow is, else plain
-void launch_token_scan(int dtype, const TokenScanArgs &a, hipStream_t s);
-// the grouped scan of the f16 form: masked if a.live or a.allow is set, else plain; a.group in 2 .. TOKEN_MAX_GROUP
-void launch_token_scan_grouped(const TokenGroupScanArgs &a, hipStream_t s);
-// (src_f32: the rows are f32, else f16; more rows than one launch takes go in several)
-void launch_token_i8_quantize(const TokenI8QuantizeArgs &a, bool src_f32, hipStream_t s);
-void launch_token_mx_quantize(const TokenMxQuantizeArgs &a, bool src_f32, bool fp8, hipStream_t s);
+// One scan of dtype's form: the grouped kernel where a.group >= 2 (f16, a search), else token_index_scan_kernel — listed if a.cand is
+// set (int8 and mxfp4), else masked if a.live or a.allow is, else plain.  token_scan_label: the profiler's name of that launch
+const char *token_scan_label(int dtype, const TokenGroupScanArgs &a);
+void launch_token_scan(int dtype, const TokenGroupScanArgs &a, hipStream_t s);
+// (target: not NONE; src_f32: the rows are f32, else f16; more rows than one launch takes go in several)
+void launch_token_quantize(TokenQuant target, const TokenQuantizeArgs &a, bool src_f32, hipStream_t s);
 void launch_token_pairs(const TokenPairsArgs &a, hipStream_t s);
 void launch_token_gather(const TokenGatherArgs &a, hipStream_t s);
 

@@ -192,15 +192,18 @@ def test_edges_of_the_surface(make_model, tmp_path, capfd):
         ids, sc = dev.download(d_i, (2, 4), np.int32), dev.download(d_s, (2, 4), np.float32)
         assert (ids[0] == -1).all() and np.isneginf(sc[0]).all() and (ids[1] >= 0).all()
         dev.free(d_q, d_qcu, d_c, d_i, d_s)
+    q, qcu = unit_rows(rng, 40, 1024), [0, 7, 40]
+    before = ix.search(q, qcu, 10)
     capfd.readouterr()
     for call, line in ((lambda: ix.get_codes(0), "mxfp4 rows"), (ix.compact, "compact: not available for an mxfp4 token index"),
                        (lambda: ix.save(str(tmp_path / "no.tok")), "save: not available for an mxfp4 token index")):
         with pytest.raises(ValueError):
             call()
         assert line in capfd.readouterr().err
+    # a refusal writes no file and leaves the index as it was
     assert not list(tmp_path.iterdir())
-    q, qcu = unit_rows(rng, 40, 1024), [0, 7, 40]
     got = ix.search(q, qcu, 10)
+    assert_same(got, before, "after the refusals")
     assert ix.remove([1]) == 1 and ix.search(q, qcu, 10) and ix.rescore(q, qcu, got[0], 5)
     rep = m.profile_report()
     for name in ("token_mx_quantize", "token_mxfp4_scan", "token_mxfp4_scan_masked", "token_mxfp4_rescore"):
