@@ -83,6 +83,7 @@ bert_ctx *load_impl(const char *fname, bool tokenizer_only) {
     ctx->texts.tok = &ctx->tok;
     ctx->texts.n_max_tokens = mf.hp.n_max_tokens;
     if (tokenizer_only) return ctx.release();
+    (void)mx_from_env(true);                                  // (a value of BERT_HIP_MX nobody knows: said once per load)
     std::vector<int> devs;
     if (!context_devices(devs, err)) {
         fprintf(stderr, ME "%s\n", err.c_str());

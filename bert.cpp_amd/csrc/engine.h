@@ -152,7 +152,7 @@ private:
 
     // The forward pass: plan() decides everything once, before the first launch; a forward_* method per route only launches.
     enum class Route { F32, LATENCY, ONE_LAUNCH, FOLDED, LAYERED };
-    enum class Family { GEMM256, MFMA, NAIVE, F32 };         // the kernel that serves a weight mat-mul
+    enum class Family { GEMM256, MFMA, NAIVE, F32, MX };     // the kernel that serves a weight mat-mul
     struct LayerPlan {                                       // (LAYERED; FOLDED reads layer 0's planes)
         bool qkv2 = false;            // qkv_attention2, else the Q|K|V mat-mul + attention
         bool tail = false;            // layer_tail, else the mat-muls + LayerNorms
@@ -183,6 +183,11 @@ private:
     // A, resid, C: f32 for Family::F32, else f16
     bool gemm(const Plan &p, const char *name, Family f, const GemmWeightStore &W, const void *A, const float *bias, const void *resid, void *C,
               int epi, std::string &err, const GemmLnFold *ln = nullptr);
+    // The MXFP8 route (gemm_mx.hip; the plan gave all four families of a layer Family::MX): f16 rows [n_tokens][K] -> MX rows
+    // ("mx_quantize" in the profile), and a mat-mul from MX rows into f16 rows (C16) or MX rows (Cmx)
+    void mx_quantize(const Plan &p, const half_t *x, int K, const MxRows &out);
+    void gemm_mx(const Plan &p, const char *name, const GemmWeightStore &W, const MxRows &A, const float *bias, const half_t *resid, half_t *C16, MxRows *Cmx, int epi);
+    void forward_layer_mx(const Plan &p, const LayerWeights &L);
     void attention(const Plan &p);
     void tap(const Plan &p, int idx);
     // the grouped-pooling launch ("group_pool" in the profile) behind a pass on s, then busy_ again: the next pass must not write raw_rows_ under it
@@ -205,6 +210,7 @@ private:
     int sparse_chunk_ = 0;
     DevBuf raw_rows_;                                         // grouped pooling: the sentences' POOL_RAW rows [n_sentences][H] f32 (the device form writes it under busy_)
     DevBuf ln_stats1_, ln_stats2_, ln_rows1_, ln_rows2_;      // LayerNorm folding: per-row partial statistics / finalized rows of the two LayerNorms of a layer
+    DevBuf mx_a_, mx_b_;                                      // the MXFP8 route: two MX activations of t_pad x max(H, I) (only with the images)
     hipStream_t stream_ = nullptr;
     // the workspace serves ONE forward pass at a time: every pass waits for the previous one's event on its own stream
     hipEvent_t busy_ = nullptr;

@@ -27,9 +27,10 @@ Engine *Engine::create(const ModelFile &mf, int device, std::string &err) {
     }
     e->opt_ = EngineOptions::from_env(mf.hp);
     LoadOptions lo;
-    lo.naive = e->opt_.gemm_naive; lo.expand_q4 = e->opt_.q4_expand; lo.ln_fold = e->opt_.ln_fold;
+    lo.naive = e->opt_.gemm_naive; lo.expand_q4 = e->opt_.q4_expand; lo.ln_fold = e->opt_.ln_fold; lo.mx = e->opt_.mx_load;
     e->w_ = ModelWeights::load(mf, lo, err);
     if (!e->w_ || !e->status_.alloc(16, err)) return nullptr;
+    e->opt_.mx = e->w_->mx_images();                          // (the route is the default of a load that built its images)
     if (hipStreamCreateWithFlags(&e->stream_, hipStreamNonBlocking) != hipSuccess) { err = "hipStreamCreate failed"; return nullptr; }
     if (hipEventCreateWithFlags(&e->busy_, hipEventDisableTiming) != hipSuccess) { err = "hipEventCreate failed"; return nullptr; }
     return e.release();
@@ -65,7 +66,7 @@ int Engine::check(std::string &err) {
 void Engine::set_option(const std::string &key, const std::string &value) {
     if (key == "profile_replay") { prof_.set_replay(value); return; }
     (void)hipSetDevice(device_);
-    if (!test_poison_option(key, ctx_, y_, {&x_, &qkv_, &ctx_, &y_, &ff_, &v32_, &ln_stats1_, &ln_stats2_, &ln_rows1_, &ln_rows2_, &d_hidden_})) opt_.set(key, value, w_->naive_images(), w_->fold_images);
+    if (!test_poison_option(key, ctx_, y_, {&x_, &qkv_, &ctx_, &y_, &ff_, &v32_, &ln_stats1_, &ln_stats2_, &ln_rows1_, &ln_rows2_, &d_hidden_, &mx_a_, &mx_b_})) opt_.set(key, value, w_->naive_images(), w_->fold_images, w_->mx_images());
 }
 
 bool Engine::ensure_workspace(int t_pad, int n_sentences, std::string &err) {
@@ -75,6 +76,7 @@ bool Engine::ensure_workspace(int t_pad, int n_sentences, std::string &err) {
            y_.ensure(tp * H * es, err) && ff_.ensure(tp * I * es, err) && v32_.ensure((size_t)std::max(128, std::min(t_pad, (opt_.latency_tokens + 255) / 256 * 256)) * H * 4, err) &&
            d_out_.ensure((size_t)n_sentences * H * 4, err) &&
            windows_.ensure((size_t)n_sentences * sizeof(int2), err) &&
+           (!w_->mx_images() || (mx_a_.ensure(MxRows::bytes(t_pad, (int)std::max(H, I)), err) && mx_b_.ensure(MxRows::bytes(t_pad, (int)std::max(H, I)), err))) &&
            // (LayerNorm folding, H = 768 route: 2 H / 256 partial (sum, sum of squares) pairs and one finalized float4 per row and LayerNorm)
            (!(H > 384 && H % 256 == 0) || (ln_stats1_.ensure(tp * (2 * H / 256) * 8, err) && ln_stats2_.ensure(tp * (2 * H / 256) * 8, err) &&
                                            ln_rows1_.ensure(tp * 16, err) && ln_rows2_.ensure(tp * 16, err)));
@@ -208,6 +210,18 @@ Engine::Plan Engine::plan(const Pass &pass, int slots, int pool_mode, float *d_o
         fold = fold && L.fold_ok && (il ? family(L.qkv_fold) : lp.qkv) == Family::GEMM256 && lp.o == Family::GEMM256 &&
                family(L.ffi_fold) == Family::GEMM256 && lp.ffo == Family::GEMM256 && !(opt_.qkv2 && qkv2_shape) && !(opt_.tail && tail_shape);
     }
+    // The MXFP8 route, where the load built the images and "mx" is on: every layer as mat-muls of gemm_mx.hip around the attention and
+    // LayerNorm launches — x materialised after every layer, so taps and token rows are served —, ahead of every other f16 route
+    bool mx = opt_.mx && mx_a_.p && mx_b_.p;
+    for (int il = 0; mx && il < Lz; ++il) {
+        const LayerWeights &L = w_->layers[il];
+        mx = gemm_mx_supported(L.qkv.w, p.t_pad) && gemm_mx_supported(L.o.w, p.t_pad) && gemm_mx_supported(L.ffi.w, p.t_pad) && gemm_mx_supported(L.ffo.w, p.t_pad);
+    }
+    if (mx) {
+        for (LayerPlan &lp : p.layers) { lp = LayerPlan(); lp.qkv = lp.o = lp.ffi = lp.ffo = Family::MX; }
+        p.route = Route::LAYERED;
+        return p;
+    }
     // a hidden-state tap wants every layer's normalised states: it takes neither the one-launch kernel nor the folded LayerNorms
     if (pass.d_hidden) one_launch = fold = false;
     // token rows want the last layer's states in x_ in row order: not the one-launch kernel; the folded LayerNorms stay
@@ -264,6 +278,35 @@ bool Engine::gemm(const Plan &p, const char *name, Family f, const GemmWeightSto
         });
     if (!ok) err = std::string(name) + ": no " + kernel[(int)f] + " kernel for LayerNorm-folding flags " + std::to_string(ln->flags) + ", epilogue " + std::to_string(epi);
     return ok;
+}
+
+void Engine::mx_quantize(const Plan &p, const half_t *x, int K, const MxRows &out) {
+    timed("mx_quantize", 0.0, p.pass.stream, [&] { launch_mx_quantize_rows(x, p.pass.n_tokens, p.t_pad, K, out, p.pass.stream); });
+}
+
+void Engine::gemm_mx(const Plan &p, const char *name, const GemmWeightStore &W, const MxRows &A, const float *bias, const half_t *resid, half_t *C16,
+                     MxRows *Cmx, int epi) {
+    prof_.count_family("family:gemm_mx");
+    timed(name, 2.0 * p.pass.n_tokens * W.w.N * W.w.K, p.pass.stream, [&] { launch_gemm_mx(W.w, A, bias, resid, C16, Cmx, p.t_pad, epi, p.pass.stream); });
+}
+
+// A layer of the MXFP8 route: every mat-mul reads MX rows.  The inputs other kernels produce (x, the attention context, LayerNorm's y)
+// pass the row quantiser; the up-projection writes its GELU output as MX rows itself, so the intermediate never exists in f16.
+void Engine::forward_layer_mx(const Plan &p, const LayerWeights &L) {
+    const int H = hp_.n_embd, I = hp_.n_intermediate;
+    half_t *x = x_.as<half_t>(), *qkv = qkv_.as<half_t>(), *ctx = ctx_.as<half_t>(), *y = y_.as<half_t>();
+    const MxRows a{mx_a_.as<uint8_t>(), p.t_pad, H};
+    MxRows ff{mx_b_.as<uint8_t>(), p.t_pad, I};
+    mx_quantize(p, x, H, a);
+    gemm_mx(p, "gemm_qkv", L.qkv, a, L.qkv_b.as<float>(), nullptr, qkv, nullptr, EPI_BIAS);
+    attention(p);
+    mx_quantize(p, ctx, H, a);
+    gemm_mx(p, "gemm_attn_out", L.o, a, L.o_b.as<float>(), x, y, nullptr, EPI_BIAS_RESID);
+    timed("layernorm", 0.0, p.pass.stream, [&] { launch_layernorm(y, L.ln_att_w.as<float>(), L.ln_att_b.as<float>(), p.pass.n_tokens, H, p.pass.stream); });
+    mx_quantize(p, y, H, a);
+    gemm_mx(p, "gemm_ffn_up", L.ffi, a, L.ffi_b.as<float>(), nullptr, nullptr, &ff, EPI_BIAS_GELU);
+    gemm_mx(p, "gemm_ffn_down", L.ffo, ff, L.ffo_b.as<float>(), y, x, nullptr, EPI_BIAS_RESID);
+    timed("layernorm", 0.0, p.pass.stream, [&] { launch_layernorm(x, L.ln_out_w.as<float>(), L.ln_out_b.as<float>(), p.pass.n_tokens, H, p.pass.stream); });
 }
 
 // (attention FLOPs: 4 * sum_b N_b^2 * H; only T and max_len are known here -> upper bound T * max_len)
@@ -377,6 +420,11 @@ bool Engine::forward_layers(const Plan &p, std::string &err) {
     for (int il = 0; il < hp_.n_layer; ++il) {
         const LayerWeights &L = w_->layers[il];
         const LayerPlan &lp = p.layers[il];
+        if (lp.qkv == Family::MX) {
+            forward_layer_mx(p, L);
+            tap(p, il + 1);
+            continue;
+        }
         if (lp.qkv2) {
             // windows of 128 token slots holding whole sentences: Q|K|V never reach HBM whatever the sentence lengths
             timed("qkv_attention2", 2.0 * p.pass.n_tokens * L.qkv.w.N * L.qkv.w.K + 4.0 * p.pass.n_tokens * p.pass.max_len * H, p.pass.stream, [&] {

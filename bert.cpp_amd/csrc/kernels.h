@@ -44,7 +44,36 @@ struct GemmWeight {
     const half_t *w16p = nullptr;
     // f32 files (ftype 0) with the f32 route (f32_route.hip): the file's own f32 rows, [N][K] row-major
     const float *w32 = nullptr;
+    // optional MXFP8 image (gemm_mx.hip; BERT_HIP_MX=fp8, N % 128 == 0, K % 64 == 0): MX rows (below) of the f16 image's values, one
+    // 128-row tile after another: tile (nt, kt) — rows 128 nt .., k 128 kt .. — is the MX_ROW_BYTES * 128 bytes from
+    // (nt * mx_k_tiles(K) + kt) * 128 * MX_ROW_BYTES on, what the kernel streams into LDS as it lies
+    const uint8_t *mx = nullptr;
 };
+
+// MX rows: a matrix [rows][K] as MXFP8 — e4m3 codes, one E8M0 scale byte per 32 consecutive k, by the rule include/bert_hip.h states for the
+// mxfp4 index's queries (scale exponent floor(log2(amax)) - 8, 0 for a zero block; codes to nearest even, clamped at 448) — cut into
+// k-tiles of 128.  ONE row layout for the weight image and the activations: a row of a k-tile is MX_ROW_BYTES = 144 bytes, 128 codes,
+// the 4 scale bytes of its 4 blocks, 12 zero bytes — nine 16-byte slots, an odd number, so the fragment reads of eight consecutive rows
+// hit eight different slots of LDS when a tile has come in as it lies in memory.  k from K to the end of the last tile: zero codes under
+// scale byte 127.  A block that holds a NaN or an inf: zero codes under scale byte 0xFF (the products with it are NaN).
+// An activation (MxRows) is k-tile major: row t of k-tile kt at (kt * M_pad + t) * MX_ROW_BYTES, so the 256 token rows of a tile are
+// contiguous.  Rows from the last token to M_pad hold zero codes under scale byte 127 when the row quantiser wrote them.
+constexpr int MX_K_TILE = 128, MX_ROW_BYTES = 144;
+__host__ __device__ constexpr int mx_k_tiles(int K) { return (K + MX_K_TILE - 1) / MX_K_TILE; }
+struct MxRows {
+    uint8_t *p = nullptr;
+    int M_pad = 0, K = 0;
+    static size_t bytes(int M_pad, int K) { return (size_t)mx_k_tiles(K) * M_pad * MX_ROW_BYTES; }
+};
+// f16 rows x [T][K] (K % 32 == 0) -> MX rows; rows T .. T_pad - 1 (T_pad = out.M_pad) are written as zero codes under scale byte 127,
+// whatever x holds there.  Four lanes per block of 32, a wave per row and 512 k.
+void launch_mx_quantize_rows(const half_t *x, int T, int T_pad, int K, MxRows out, hipStream_t stream);
+// gemm_mx.hip: C[t][n] = epi( sum_k Aq[t][k] Wq[n][k] + bias[n] (+ resid[t][n]) ) on v_mfma_scale_f32_32x32x64_f8f6f4, both operands
+// MXFP8 (W.mx and A), 128 features x 256 tokens per workgroup of 8 waves.  C16 (f16 rows [M_pad][N]) and / or Cmx (MX rows of those same
+// f16 values, K = N: the row quantiser fused into the epilogue) — a launch per form asked for.  No row < M depends on a row >= M.
+bool gemm_mx_supported(const GemmWeight &W, int M_pad);
+void launch_gemm_mx(const GemmWeight &W, const MxRows &A, const float *bias, const half_t *resid, half_t *C16, MxRows *Cmx, int M_pad,
+                    int epilogue, hipStream_t stream);
 
 // C[t][n] = epi( sum_k A[t][k] * W[n][k] + bias[n] (+ resid[t][n]) ), t < M_pad (multiple of 128)
 // lda = K, ldc = ldr = N.  MFMA path requires K % 64 == 0.

@@ -35,6 +35,7 @@ void EngineOptions::apply(const std::string &key, const std::string &value) {
     else if (key == "qkv2") qkv2 = value != "0";
     else if (key == "gemm256") gemm256 = value != "0";
     else if (key == "ln_fold") ln_fold = value != "0";
+    else if (key == "mx") mx = value != "0";
     else if (key == "tail") tail = value != "0";
     else if (key == "latency") latency = value != "0";
     else if (key == "stage_kernel") stage_kernel = value != "0";
@@ -57,6 +58,7 @@ void EngineOptions::apply(const std::string &key, const std::string &value) {
 //   BERT_HIP_LATENCY  the keys "latency" and "latency_tokens" in one: 0 = no latency route; 1 = the default cap; n >= 32: calls of
 //                     at most n tokens take it
 //   BERT_HIP_Q4       no key: decides how the weights are packed
+//   BERT_HIP_MX       no key: "fp8" builds the MXFP8 images at load; the key "mx" then switches the route, on by default with them
 // "qkv2", "gemm256", "tail", "stage_kernel", "one_launch", "sparse_index_qb", "sparse_index_segment_rows", "hybrid_chunk_queries", "token_index_slices", "token_index_query_group", "maxsim_launch_pairs" (and the profiler's "profile_replay") are keys only.
 EngineOptions EngineOptions::from_env(const HParams &hp) {
     EngineOptions o;
@@ -69,6 +71,7 @@ EngineOptions EngineOptions::from_env(const HParams &hp) {
     else if (kernels == "naive") fprintf(stderr, "BERT_HIP_KERNELS=naive: a test cross-check (libbert_test.so), not a route of libbert.so; ignored\n");
     else if (kernels == "tiled") o.qkv2 = o.tail = o.latency = false, o.one_launch = 0;
     if (const char *v = getenv("BERT_HIP_Q4")) o.q4_expand = std::string(v) != "fused";
+    o.mx_load = mx_from_env(false);
     static const char *const same_as_key[][2] = {
         {"BERT_HIP_LATENCY", "latency"}, {"BERT_HIP_LATENCY", "latency_tokens"},
         {"BERT_HIP_LN_FOLD", "ln_fold"},                      // (tuning: 0 = LayerNorm kernels of their own at H = 768)
@@ -81,7 +84,15 @@ EngineOptions EngineOptions::from_env(const HParams &hp) {
     return o;
 }
 
-void EngineOptions::set(const std::string &key, const std::string &value, bool naive_images, bool fold_images) {
+bool mx_from_env(bool report) {
+    const char *v = getenv("BERT_HIP_MX");
+    if (!v || !*v) return false;
+    if (std::string(v) == "fp8") return true;
+    if (report) fprintf(stderr, "bert_hip: BERT_HIP_MX = \"%s\": expected \"fp8\"; ignored\n", v);
+    return false;
+}
+
+void EngineOptions::set(const std::string &key, const std::string &value, bool naive_images, bool fold_images, bool mx_images) {
     if (!TEST_ROUTES && (key == "gemm" || key == "attn") && value == "naive")
         fprintf(stderr, "bert_hip_set_option: %s=naive is a test cross-check (libbert_test.so), not a route of libbert.so; ignored\n", key.c_str());
     // the generic kernel reads GemmWeight::naive16, an image that is only built at load time (BERT_HIP_KERNELS=naive) or
@@ -90,6 +101,8 @@ void EngineOptions::set(const std::string &key, const std::string &value, bool n
         fprintf(stderr, "bert_hip_set_option: gemm=naive needs BERT_HIP_KERNELS=naive at load time (the f16 row-major images were not built); ignored\n");
     else if (key == "ln_fold" && value != "0" && !fold_images)
         fprintf(stderr, "bert_hip_set_option: ln_fold=1 needs BERT_HIP_LN_FOLD=1 at load time (the folded images were not built); ignored\n");
+    else if (key == "mx" && value != "0" && !mx_images)
+        fprintf(stderr, "bert_hip_set_option: mx=1 needs BERT_HIP_MX=fp8 at load time (the MXFP8 images were not built); ignored\n");
     else apply(key, value);
 }
 

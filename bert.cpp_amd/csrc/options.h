@@ -15,6 +15,8 @@ struct EngineOptions {
     bool qkv2 = true, gemm256 = true, tail = true;
     bool ln_fold = true;              // H = 768 route: LayerNorm folded into the mat-muls (needs the images: built at load)
     bool latency = true;
+    bool mx = false;                  // the MXFP8 route (gemm_mx.hip): on when the images were built at load, and only with them
+    bool mx_load = false;             // BERT_HIP_MX=fp8: build the MXFP8 images (no key: load time only)
     bool q4_expand = true;            // q4 files: f16 images and f32 tables built at load (no key: load time only)
     bool f32_exact = true;            // f32 files take the f32 route unless BERT_HIP_F32=f16 / "f32" = "f16"
     int one_launch = 1;               // all layers in one launch: 0 never, 1 when it pays (well-filled windows), 2 whenever the kernel takes the batch
@@ -37,14 +39,18 @@ struct EngineOptions {
 
     // the defaults for a model of these dimensions, then the environment
     static EngineOptions from_env(const HParams &hp);
-    // a key of bert_hip_set_option.  naive_images / fold_images: what was built at load (ModelWeights) — "gemm" = "naive" and
-    // "ln_fold" = "1" are refused, with a line on stderr, without them.  Unknown keys are ignored; so is, with a line on stderr, a value
+    // a key of bert_hip_set_option.  naive_images / fold_images / mx_images: what was built at load (ModelWeights) — "gemm" = "naive",
+    // "ln_fold" = "1" and "mx" = "1" are refused, with a line on stderr, without them.  Unknown keys are ignored; so is, with a line on stderr, a value
     // that "pooling" or "normalize" do not know (from the environment as well).
-    void set(const std::string &key, const std::string &value, bool naive_images, bool fold_images);
+    void set(const std::string &key, const std::string &value, bool naive_images, bool fold_images, bool mx_images);
 
 private:
     void apply(const std::string &key, const std::string &value);
 };
+
+// BERT_HIP_MX: true for "fp8"; unset or empty: false; any other value: false, and with `report` a line on stderr saying that it is
+// ignored (a load reports once, before it looks for a device; the engines of the load read the value silently)
+bool mx_from_env(bool report);
 
 // "test_poison_ctx" (libbert_test.so only; false, doing nothing, in libbert.so): every half of the attention-context workspace
 // becomes a NaN, so a pass that still reads what it has not written itself shows it in its results.  "test_poison_xres": the same for the

@@ -147,6 +147,63 @@ int32_t bert_hip_test_gemm(int32_t M, int32_t N, int32_t K, const uint16_t *A, c
     return 0;
 }
 
+// MX rows (kernels.h) of `rows` rows and K elements, as they lie in memory (tile_rows 0: an activation, k-tile major over M_pad rows;
+// 128: the weight image's 128-row tiles) -> codes [rows][K], scales [rows][K / 32]
+static void mx_untile(const uint8_t *mx, int rows, int M_pad, int K, int tile_rows, uint8_t *codes, uint8_t *scales) {
+    const int KT = mx_k_tiles(K);
+    for (int r = 0; r < rows; ++r)
+        for (int kt = 0; kt < KT; ++kt) {
+            const size_t row = tile_rows ? ((size_t)(r / tile_rows) * KT + kt) * tile_rows + r % tile_rows : (size_t)kt * M_pad + r;
+            const uint8_t *src = mx + row * MX_ROW_BYTES;
+            const int nk = std::min(MX_K_TILE, K - kt * MX_K_TILE);
+            memcpy(codes + (size_t)r * K + kt * MX_K_TILE, src, (size_t)nk);
+            memcpy(scales + (size_t)r * (K / 32) + kt * 4, src + MX_K_TILE, (size_t)nk / 32);
+        }
+}
+
+int32_t bert_hip_test_pack_mx(int32_t N, int32_t K, const uint16_t *W, uint8_t *codes, uint8_t *scales) {
+    if (N <= 0 || K <= 0 || N % 128 != 0 || K % 64 != 0) return -1;
+    const std::vector<uint8_t> img = pack_mx_image((const _Float16 *)W, N, K);
+    mx_untile(img.data(), N, 0, K, 128, codes, scales);
+    return 0;
+}
+
+int32_t bert_hip_test_gemm_mx(int32_t M, int32_t N, int32_t K, const uint16_t *A, const uint16_t *W, const float *bias, const uint16_t *resid,
+                              int32_t epilogue, uint16_t *C16, uint8_t *Cq_codes, uint8_t *Cq_scales, uint8_t *Aq_codes, uint8_t *Aq_scales) {
+    const char *me = "bert_hip_test_gemm_mx";
+    std::string err;
+    if (M <= 0 || epilogue < 0 || epilogue > 2 || (epilogue == EPI_BIAS_RESID) != (resid != nullptr)) return -1;
+    HostTensor t;
+    t.type = W_F16; t.n_dims = 2; t.ne0 = K; t.ne1 = N; t.data = (const uint8_t *)W; t.nbytes = (size_t)N * K * 2;
+    PackOptions po;
+    po.mx = true;
+    GemmWeightStore ws;
+    if (!ws.build({&t}, po, err)) { fprintf(stderr, "%s: %s\n", me, err.c_str()); return -1; }
+    const int M_pad = (M + 255) / 256 * 256;
+    if (!gemm_mx_supported(ws.w, M_pad)) return -2;
+    // (the MX buffers as 32-bit words of the pattern: whole rows of 144 bytes)
+    DevBuf dA, dB, dR, dC, dAq, dCq;
+    if (!upload_rows16(dA, A, M, M_pad, K, err) || !alloc_pad16(dC, (size_t)M_pad * N, err) || !dB.upload(bias, (size_t)N * 4, err) ||
+        (resid && !upload_rows16(dR, resid, M, M_pad, N, err)) || !alloc_pad32(dAq, MxRows::bytes(M_pad, K) / 4, err) ||
+        !alloc_pad32(dCq, MxRows::bytes(M_pad, N) / 4, err)) {
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return -1;
+    }
+    const MxRows aq{dAq.as<uint8_t>(), M_pad, K};
+    MxRows cq{dCq.as<uint8_t>(), M_pad, N};
+    launch_mx_quantize_rows(dA.as<half_t>(), M, M_pad, K, aq, nullptr);
+    launch_gemm_mx(ws.w, aq, dB.as<float>(), dR.as<half_t>(), dC.as<half_t>(), &cq, M_pad, epilogue, nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    std::vector<uint8_t> haq(MxRows::bytes(M_pad, K)), hcq(MxRows::bytes(M_pad, N));
+    CK(hipMemcpy(C16, dC.p, (size_t)M * N * 2, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(haq.data(), dAq.p, haq.size(), hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hcq.data(), dCq.p, hcq.size(), hipMemcpyDeviceToHost));
+    mx_untile(haq.data(), M, M_pad, K, 0, Aq_codes, Aq_scales);
+    mx_untile(hcq.data(), M, M_pad, N, 0, Cq_codes, Cq_scales);
+    return 0;
+}
+
 int32_t bert_hip_test_gemm_lnfold(int32_t M, int32_t K1, int32_t H, int32_t N2, const uint16_t *A1, const uint16_t *W1, const float *b1,
                                   const uint16_t *r, const float *rg, const float *rb, const uint16_t *W2, const float *b2, const float *g,
                                   const float *be, int32_t epi2, uint16_t *u_out, uint16_t *out2, float *rows_out) {

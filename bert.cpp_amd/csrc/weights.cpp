@@ -1,6 +1,7 @@
 // weights.cpp — see weights.h.
 #include "weights.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -173,6 +174,43 @@ LnFoldImage pack_ln_fold(const StackedRows &s, const float *gamma, const float *
     return f;
 }
 
+// device.h e4m3_code on the host: the magnitude bits of the e4m3 code nearest to a >= 0, ties to even, clamped to 448
+static uint32_t e4m3_code_host(float a) {
+    if (a < 0x1p-6f) return (uint32_t)std::rint(a * 512.f);
+    uint32_t b;
+    memcpy(&b, &a, 4);
+    b += 0x7ffffu + ((b >> 20) & 1u);
+    return std::min((b >> 20) - ((127u - 7u) << 3), 0x7eu);
+}
+
+std::vector<uint8_t> pack_mx_image(const _Float16 *img, int64_t N, int64_t K) {
+    const int64_t KT = mx_k_tiles((int)K);
+    std::vector<uint8_t> out((size_t)(N / 128) * KT * 128 * MX_ROW_BYTES, 0);
+    for (int64_t n = 0; n < N; ++n)
+        for (int64_t kt = 0; kt < KT; ++kt) {
+            uint8_t *row = out.data() + (size_t)(((n / 128) * KT + kt) * 128 + n % 128) * MX_ROW_BYTES;
+            for (int b = 0; b < 4; ++b) {
+                float v[32];
+                uint32_t amax = 0;                               // as bits: NaN > inf > every finite value
+                for (int j = 0; j < 32; ++j) {
+                    const int64_t k = kt * MX_K_TILE + b * 32 + j;
+                    v[j] = k < K ? (float)img[(size_t)n * K + k] : 0.f;
+                    uint32_t u;
+                    memcpy(&u, &v[j], 4);
+                    amax = std::max(amax, u & 0x7fffffffu);
+                }
+                const int E = (int)(amax >> 23), e = amax == 0 ? 0 : std::max(E - 127 - 8, -127);
+                const bool bad = E == 255;
+                row[MX_K_TILE + b] = bad ? 0xff : (uint8_t)(e + 127);
+                for (int j = 0; j < 32 && !bad; ++j) {
+                    const float y = std::ldexp(v[j], -e);        // exact
+                    row[b * 32 + j] = (uint8_t)((std::signbit(y) ? 0x80u : 0u) | e4m3_code_host(std::fabs(y)));
+                }
+            }
+        }
+    return out;
+}
+
 std::vector<uint32_t> pack_gamma_beta_bias(const float *gamma, const float *beta, const float *bias, int64_t n) {
     std::vector<uint32_t> v((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
@@ -207,6 +245,10 @@ bool GemmWeightStore::build(const std::vector<const HostTensor *> &rows, const P
         if (opt.kperm && s.K % 16 == 0) {
             if (!w16p.upload(permute_k16(img), err)) return false;
             w.w16p = w16p.as<half_t>();
+        }
+        if (opt.mx && s.N % 128 == 0 && s.K % 64 == 0) {
+            if (!mx.upload(pack_mx_image(img.data(), s.N, s.K), err)) return false;
+            w.mx = mx.as<uint8_t>();
         }
     } else if (mfma_ok) {
         w.type = s.type == W_Q4_0 ? GW_Q4_0 : GW_Q4_1;
@@ -309,6 +351,13 @@ bool ModelWeights::naive_images() const {
     return true;
 }
 
+bool ModelWeights::mx_images() const {
+    for (const LayerWeights &L : layers)
+        for (const GemmWeightStore *g : {&L.qkv, &L.o, &L.ffi, &L.ffo})
+            if (!g->w.mx) return false;
+    return !layers.empty();
+}
+
 std::unique_ptr<ModelWeights> ModelWeights::load(const ModelFile &mf, const LoadOptions &opt, std::string &err) {
     const HParams &hp = mf.hp;
     const int H = hp.n_embd;
@@ -332,6 +381,8 @@ std::unique_ptr<ModelWeights> ModelWeights::load(const ModelFile &mf, const Load
 
     PackOptions po;
     po.naive = opt.naive; po.expand_q4 = opt.expand_q4; po.f32 = w->f32_file;
+    const PackOptions po_head = po;                           // (the MLM head's transform: no MX image)
+    po.mx = opt.mx;
     PackOptions po_ffn = po;
     // the k-permuted second image of the FFN weights is only read by layer_tail_kernel (H = 256 / 384)
     po_ffn.kperm = H % 128 == 0 && H >= 256 && H <= 384;
@@ -388,7 +439,7 @@ std::unique_ptr<ModelWeights> ModelWeights::load(const ModelFile &mf, const Load
                          *lw = mf.find("cls.predictions.transform.LayerNorm.weight"), *lb = mf.find("cls.predictions.transform.LayerNorm.bias"),
                          *bv = mf.find("cls.predictions.bias");
         if (!wt || !bt || !lw || !lb || !bv) { err = "the MLM head is incomplete"; return nullptr; }
-        ok = w->mlm_wt.build({wt}, po, err) && upload_tensor(w->mlm_bt, bt, err) && upload_tensor(w->mlm_ln_w, lw, err) &&
+        ok = w->mlm_wt.build({wt}, po_head, err) && upload_tensor(w->mlm_bt, bt, err) && upload_tensor(w->mlm_ln_w, lw, err) &&
              upload_tensor(w->mlm_ln_b, lb, err) && upload_tensor(w->mlm_bias, bv, err);
         if (ok && hp.f16 == W_F16) w->vocab16 = w->word_emb.as<half_t>();
         else if (ok) {

@@ -81,6 +81,9 @@ struct LnFoldImage { std::vector<_Float16> img, aug; };
 LnFoldImage pack_ln_fold(const StackedRows &s, const float *gamma, const float *beta, const float *bias);
 // (f16 gamma | f16 (beta + bias) << 16) per feature: what a residual mat-mul needs to rebuild LayerNorm(resid) per element
 std::vector<uint32_t> pack_gamma_beta_bias(const float *gamma, const float *beta, const float *bias, int64_t n);
+// GemmWeight::mx: the MXFP8 image of an f16 image img [N][K] (N % 128 == 0), kernels.h's MX rows in 128-row tiles — the rule the row
+// quantiser of gemm_mx.hip applies to activations, in plain C++
+std::vector<uint8_t> pack_mx_image(const _Float16 *img, int64_t N, int64_t K);
 // an embedding table of a q4 file as f32 values, the numbers the gather kernel dequantises on the fly
 std::vector<float> table_as_f32(const HostTensor &t);
 // any file tensor as f32 values [ne1][ne0]: f32 as stored, f16 widened, q4 as table_as_f32
@@ -102,12 +105,13 @@ struct PackOptions {
     bool expand_q4 = false;    // q4_0 / q4_1 tensors become an f16 image at load (the engine's default) instead of the nibble /
                                // scale planes of the fused-dequant kernels
     bool f32 = false;          // f32 tensors also keep their own f32 rows (GemmWeight::w32, the f32 route)
+    bool mx = false;           // also GemmWeight::mx, beside an f16 image of N % 128 == 0, K % 64 == 0
 };
 
 // Owns the HBM image of one weight matrix in the layouts kernels.h describes.
 struct GemmWeightStore {
     GemmWeight w;
-    DevBuf w16, w16p, qs, sc, naive16, w32;
+    DevBuf w16, w16p, qs, sc, naive16, w32, mx;
     bool mfma_ok = false;
     // rows: file tensors stacked along N (StackedRows)
     bool build(const std::vector<const HostTensor *> &rows, const PackOptions &opt, std::string &err);
@@ -136,6 +140,7 @@ struct LoadOptions {
     bool naive = false;        // the f16 row-major images of the generic kernels for every matrix
     bool expand_q4 = true;     // q4 files: f16 images and f32 tables, else the 4-bit planes and the file's own tables
     bool ln_fold = true;       // the LayerNorm-folding images of models the fused H <= 384 kernels do not take
+    bool mx = false;           // BERT_HIP_MX=fp8: the MXFP8 images of the layers' matrices beside their f16 images
 };
 
 struct ModelWeights {
@@ -145,6 +150,7 @@ struct ModelWeights {
     bool f32_file = false;                // every matrix and table of the file is f32: the f32 route can take it
     bool fold_images = false;             // the LayerNorm-folding images were built (LoadOptions::ln_fold)
     bool naive_images() const;            // every matrix has GemmWeight::naive16
+    bool mx_images() const;               // every matrix has GemmWeight::mx (LoadOptions::mx, and every shape qualified)
     // The classification head of the file, if it has one (model_file.h; cls_head.hip): Wp [H][H] as f16 (the file's f16 bits, or its
     // f32 / q4 values rounded once: row_to_f16), and for f32 files also its own f32 rows (the f32 route); bp [H], Wc [n_labels][H],
     // bc [n_labels] as f32 (q4 / f16 classifiers dequantised at load).  n_labels == 0: no head, nothing uploaded.

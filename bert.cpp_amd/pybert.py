@@ -79,6 +79,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_late_index_header", "bert_hip_test_late_index_body", "bert_hip_test_late_index_query_group",
     "bert_hip_test_attention_bias", "bert_hip_test_f32_attention_bias", "bert_hip_test_rel_bias_table",
     "bert_hip_test_sparse_postings_geometry", "bert_hip_test_sparse_postings_segment",
+    "bert_hip_test_pack_mx", "bert_hip_test_gemm_mx",
 ]
 TEST_LIB_PATH = LIB_PATH[:-3] + "_test.so"
 
@@ -308,6 +309,10 @@ def test_lib() -> C.CDLL:
     vp, i32, i32p = C.c_void_p, C.c_int32, C.POINTER(C.c_int32)
     L.bert_hip_test_gemm.restype = i32
     L.bert_hip_test_gemm.argtypes = [i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp]
+    L.bert_hip_test_pack_mx.restype = i32
+    L.bert_hip_test_pack_mx.argtypes = [i32, i32, vp, vp, vp]
+    L.bert_hip_test_gemm_mx.restype = i32
+    L.bert_hip_test_gemm_mx.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.bert_hip_test_gemm_lnfold.restype = i32
     L.bert_hip_test_gemm_lnfold.argtypes = [i32, i32, i32, i32] + [vp] * 10 + [i32, vp, vp, vp]
     L.bert_hip_test_attention.restype = i32
@@ -2179,6 +2184,47 @@ def test_gemm(A: np.ndarray, W_bytes: np.ndarray, wtype: int, N: int, bias: np.n
     if r != 0:
         raise RuntimeError(f"bert_hip_test_gemm failed: {r}")
     return out
+
+
+def mx_decode(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """MX rows (e4m3 code bytes [n, K], E8M0 scale bytes [n, K / 32]) as the float32 values they stand for; a block under the scale
+    byte 0xFF is NaN."""
+    c = codes.astype(np.int32)
+    ex, man = (c >> 3) & 15, c & 7
+    mag = np.where(ex == 0, np.ldexp(man.astype(np.float64), -9), np.ldexp(8.0 + man, ex - 10))
+    sc = np.repeat(scales.astype(np.int32), 32, axis=1)
+    v = np.ldexp(np.where(c & 128, -mag, mag), sc - 127)
+    return np.where(sc == 255, np.nan, v).astype(np.float32)
+
+
+def test_pack_mx(W: np.ndarray):
+    """The host packer of the MXFP8 weight image (include/bert_hip_test.h), no GPU: W float16 [N, K] -> (codes uint8 [N, K], scales uint8 [N, K / 32])."""
+    L = test_lib()
+    W = np.ascontiguousarray(W, dtype=np.float16)
+    N, K = W.shape
+    codes, scales = np.zeros((N, K), np.uint8), np.zeros((N, K // 32), np.uint8)
+    r = L.bert_hip_test_pack_mx(N, K, W.ctypes.data, codes.ctypes.data, scales.ctypes.data)
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_pack_mx failed: {r}")
+    return codes, scales
+
+
+def test_gemm_mx(A: np.ndarray, W: np.ndarray, bias: np.ndarray, resid: Optional[np.ndarray], epilogue: int):
+    """Row quantiser + MX mat-mul in both output forms (include/bert_hip_test.h): A float16 [M, K], W float16 [N, K] ->
+    (C16 float16 [M, N], (Cq codes, Cq scales), (Aq codes, Aq scales))."""
+    L = test_lib()
+    A = np.ascontiguousarray(A, dtype=np.float16); W = np.ascontiguousarray(W, dtype=np.float16)
+    bias = np.ascontiguousarray(bias, dtype=np.float32)
+    resid = None if resid is None else np.ascontiguousarray(resid, dtype=np.float16)
+    (M, K), N = A.shape, W.shape[0]
+    c16 = np.zeros((M, N), np.float16)
+    cq = np.zeros((M, N), np.uint8), np.zeros((M, N // 32), np.uint8)
+    aq = np.zeros((M, K), np.uint8), np.zeros((M, K // 32), np.uint8)
+    r = L.bert_hip_test_gemm_mx(M, N, K, A.ctypes.data, W.ctypes.data, bias.ctypes.data, None if resid is None else resid.ctypes.data, epilogue,
+                                c16.ctypes.data, cq[0].ctypes.data, cq[1].ctypes.data, aq[0].ctypes.data, aq[1].ctypes.data)
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_gemm_mx failed: {r}")
+    return c16, cq, aq
 
 
 def test_gemm_lnfold(A1, W1, b1, r, rg, rb, W2, b2, g, be, epi2):

@@ -138,7 +138,7 @@ BERT_API int32_t bert_hip_eval_hidden(struct bert_ctx *ctx, const bert_vocab_id 
 BERT_API void    bert_hip_profile_enable(struct bert_ctx *ctx, int32_t on);
 BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_t buf_len);
 
-/* Environment, read by bert_load_from_file (eleven switches):
+/* Environment, read by bert_load_from_file (twelve switches):
  *   BERT_HIP_DEVICES       "all" or a comma-separated list of HIP ordinals without repeats: the GPUs of the context
  *                          (default: the calling thread's current device — one context, one GPU, unless asked otherwise);
  *                          BERT_HIP_DEVICE=<n>, the spelling of the first builds, is read as a list of one when this is unset
@@ -166,6 +166,13 @@ BERT_API int32_t bert_hip_profile_report(struct bert_ctx *ctx, char *buf, int32_
  *                          them (no LayerNorm launch but the last; roundings differ from the un-folded sequence in the last bits), or a
  *                          LayerNorm kernel per LayerNorm.  Read at load: 0 builds no folded weight images, and set_option("ln_fold",
  *                          "1") on such a context is ignored.  bert_hip_eval_hidden always takes the un-folded sequence.
+ *   BERT_HIP_MX            unset (default) | "fp8" — also pack every layer's four weight matrices as MXFP8 (e4m3 codes, one power-of-two
+ *                          scale per 32 inputs: the rule stated below for the mxfp4 index's queries) beside their f16 images, where
+ *                          every shape allows it (inputs % 64 == 0, outputs % 128 == 0).  A context loaded so runs its weight mat-muls on
+ *                          the block-scaled FP8 matrix instruction, activations quantised on the way (gemm_mx.hip); set_option("mx",
+ *                          "0" | "1") switches between that route and the f16 routes in the same context.  Read at load: without it
+ *                          "mx" = "1" is ignored with a line on stderr.  Any other value: a line on stderr, ignored.  The embeddings move
+ *                          (cosine 0.99 against the f16 route on synthetic weights); no default, result or rate changes without it.
  *   BERT_HIP_POOLING       "mean" (default) | "cls" — what a sentence's embedding is made of: the mean over its tokens' final states (the
  *                          reference's; the all-MiniLM, e5 and gte families), or the final state of its FIRST token as the caller gave
  *                          it (the BGE family: bert_tokenize puts [CLS] there, the packed entry points take whatever id comes first)

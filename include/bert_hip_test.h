@@ -33,6 +33,19 @@ BERT_API int32_t bert_hip_test_gemm(int32_t M, int32_t N, int32_t K, const uint1
                                     int32_t wtype, const float *bias, const uint16_t *resid,
                                     int32_t epilogue, int32_t impl, uint16_t *C);
 
+/* The MXFP8 forward route's pieces (kernels.h "MX rows"; gemm_mx.hip).  W [N][K] f16 bits, N % 128 == 0, K % 64 == 0.
+ * bert_hip_test_pack_mx: the host packer of the weight image alone, no device: codes [N][K] (e4m3 bytes) and scales [N][K / 32] (E8M0
+ * bytes), row-major, un-tiled.  -1 for another shape.
+ * bert_hip_test_gemm_mx: A [M][K] f16 bits -> the row quantiser -> the MX mat-mul in BOTH output forms.  epilogue as bert_hip_test_gemm's
+ * (resid [M][N] f16 bits with 2, else NULL).  C16 [M][N] f16 bits; Cq_codes [M][N] / Cq_scales [M][N / 32]: the MX output form; Aq_codes
+ * [M][K] / Aq_scales [M][K / 32]: what the quantiser made of A.  Token rows are rounded up to 256; under bert_hip_test_set_pad rows
+ * M .. M_pad - 1 of A and resid hold pattern16 and every output and intermediate buffer (the MX ones as 32-bit words of pattern32) holds
+ * the pattern in all its words before the first launch.  -2, and no launch, for a shape the kernel does not take.                     */
+BERT_API int32_t bert_hip_test_pack_mx(int32_t N, int32_t K, const uint16_t *W, uint8_t *codes, uint8_t *scales);
+BERT_API int32_t bert_hip_test_gemm_mx(int32_t M, int32_t N, int32_t K, const uint16_t *A, const uint16_t *W, const float *bias,
+                                       const uint16_t *resid, int32_t epilogue, uint16_t *C16, uint8_t *Cq_codes, uint8_t *Cq_scales,
+                                       uint8_t *Aq_codes, uint8_t *Aq_scales);
+
 /* LayerNorm folded into the mat-muls around it (kernels.h GemmLnFold; gemm256.hip, f16 weights, H and N2 multiples of 256, M is
  * padded to 256): the pair a layer runs —
  *   u   = A1[M][K1] W1[H][K1]^T + b1 + R,   R = r[M][H] itself (rg == NULL) or LayerNorm(r; rg, rb) rebuilt per element from r's row
