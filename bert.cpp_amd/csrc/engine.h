@@ -87,7 +87,12 @@ public:
     // Such a pass does not take the one-launch kernel (which keeps x on chip between its phases and pools inside the launch: the other
     // routes leave the final states in x_ in row order); LayerNorm folding stays as planned, so the embeddings are eval_packed's bits.
     // Host form, blocking, on this engine's device: cut by the chunk rule, one copy in and one per result out for every chunk.
-    // flags: TOKEN_ROWS_NORMALIZE only (rows are f32).  embeddings: nullable.
+    // flags: TOKEN_ROWS_NORMALIZE and TOKEN_ROWS_PROJECT (rows are f32).  embeddings: nullable.
+    // With TOKEN_ROWS_PROJECT the launch is the projection head's instead ("token_project" in the profile; token_proj.hip): rows of
+    // token_dim() values, normalised AFTER the projection.  token_rows_project_ok(): the model has the head and the pass is not the f32
+    // route's (an f32 file without "f32" = "f16"), whose states are f32 — the callers refuse the flag otherwise.
+    int token_dim() const { return w_->token_dim; }
+    bool token_rows_project_ok() const { return w_->token_dim > 0 && !(w_->f32_file && opt_.f32_exact) && hp_.n_embd % 8 == 0; }
     int eval_packed_tokens_host(const int32_t *tokens, const int32_t *cu_seqlens, int n_sentences, int flags, float *rows, float *embeddings,
                                 std::string &err);
     // next-fit packing of whole sentences (in order, each starting at a multiple of 16 slots) into windows of 128 token

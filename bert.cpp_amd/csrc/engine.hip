@@ -170,7 +170,11 @@ int Engine::eval_packed_device(const Pass &pass, std::string &err) {
     if (!ok) return -1;
     // (every route a token-rows pass can take left the final states in x_, [T][H] in row order: f32 on the f32 route, else f16)
     // (a destination that IS x_: the caller wants them where they are — the sparse head —, nothing to copy)
-    if (pass.d_token_rows && pass.d_token_rows != x_.p)
+    // (the projection head in token_rows' place: the same states, [T][token_dim] rows; the callers refused the f32 route and a file without a head)
+    if (pass.d_token_rows && (pass.token_flags & TOKEN_ROWS_PROJECT)) {
+        if (p.route == Route::F32 || w_->token_dim <= 0 || !token_project_supported(hp_.n_embd, w_->token_dim)) { err = "token_project: no projection head, or the f32 route"; return -1; }
+        timed("token_project", 2.0 * T * hp_.n_embd * w_->token_dim, s, [&] { launch_token_project(x_.as<half_t>(), w_->token_proj.as<half_t>(), T, hp_.n_embd, w_->token_dim, d_cu, B, max_len, pass.token_flags, pass.d_token_rows, s); });
+    } else if (pass.d_token_rows && pass.d_token_rows != x_.p)
         timed("token_rows", 0.0, s, [&] { launch_token_rows(x_.p, p.route == Route::F32, T, hp_.n_embd, d_cu, B, max_len, pass.token_flags, pass.d_token_rows, s); });
     HIP_OK(hipGetLastError(), err, -1);
     return op_end(op, err) ? 0 : -1;

@@ -217,11 +217,12 @@ int Engine::eval_packed_grouped_host(const int32_t *tokens, const int32_t *cu, i
 
 int Engine::eval_packed_tokens_host(const int32_t *tokens, const int32_t *cu, int B, int flags, float *rows, float *embeddings, std::string &err) {
     if (B <= 0) return 0;
-    const size_t H = hp_.n_embd;
-    return blocking_host_chunks(tokens, cu, nullptr, B, 0, 0, [&](int, int T) { return (size_t)T * H * 4; }, [&](const HostChunk &c, Pass &pass) {
-        pass.d_token_rows = host_out_.p; pass.token_flags = flags & TOKEN_ROWS_NORMALIZE;
+    // (W: values per row — the projection head's under TOKEN_ROWS_PROJECT; H: per embedding)
+    const size_t H = hp_.n_embd, W = flags & TOKEN_ROWS_PROJECT ? (size_t)w_->token_dim : H;
+    return blocking_host_chunks(tokens, cu, nullptr, B, 0, 0, [&](int, int T) { return (size_t)T * W * 4; }, [&](const HostChunk &c, Pass &pass) {
+        pass.d_token_rows = host_out_.p; pass.token_flags = flags & (TOKEN_ROWS_NORMALIZE | TOKEN_ROWS_PROJECT);
         if (eval_packed_device(pass, err) != 0) return false;
-        if (hipMemcpyAsync(rows + (size_t)cu[c.b0] * H, host_out_.p, (size_t)pass.n_tokens * H * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
+        if (hipMemcpyAsync(rows + (size_t)cu[c.b0] * W, host_out_.p, (size_t)pass.n_tokens * W * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess &&
             (!embeddings || hipMemcpyAsync(embeddings + (size_t)c.b0 * H, d_out_.p, (size_t)pass.n_sentences * H * 4, hipMemcpyDeviceToHost, stream_) == hipSuccess))
             return true;
         err = "hipMemcpyAsync (rows) failed";

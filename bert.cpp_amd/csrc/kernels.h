@@ -228,6 +228,17 @@ constexpr int TOKEN_ROWS_NORMALIZE = 1, TOKEN_ROWS_F16 = 2, TOKEN_ROWS_MAX_T = 1
 void launch_token_rows(const void *x, bool x_is_f32, int T, int H, const int32_t *cu_seqlens, int n_sentences, int max_len, int flags,
                        void *out, hipStream_t stream);
 
+// The projection head of a ColBERT checkpoint over token rows (token_proj.hip): x [T][H] f16 (the final states of a pass), wp [P][H] f16
+// (ModelWeights::token_proj) -> out [T][P], out[t] = Wp x[t].  flags as launch_token_rows: bit 0 divides every row by its own L2 norm
+// AFTER the projection (a lane's squares in ascending feature order, the two lanes of a token added, 1 / sqrtf, no epsilon: the file's
+// head comment has the order), bit 1 rounds to f16.  The same guard: the tokens of a sentence whose length is not in [1, max_len] get
+// NaN rows.  H % 8 == 0, P a multiple of 32 in 32 .. TOKEN_PROJ_MAX_P (token_project_supported; otherwise nothing is launched); x, wp
+// and out 16-byte aligned.  128 tokens a workgroup; rows of x at or beyond T are never read.  Only enqueues, allocates nothing.
+constexpr int TOKEN_ROWS_PROJECT = 4, TOKEN_PROJ_MAX_P = 256;
+bool token_project_supported(int H, int P);
+void launch_token_project(const half_t *x, const half_t *wp, int T, int H, int P, const int32_t *cu_seqlens, int n_sentences, int max_len,
+                          int flags, void *out, hipStream_t stream);
+
 // MaxSim (maxsim.hip): q [.][H], d [.][H] packed f16 token rows, 16-byte aligned, H % 8 == 0, 8 <= H <= MAXSIM_MAX_H; qcu [n_q + 1],
 // dcu [n_d + 1] cumulative lengths; pairs null: all pairs, scores [n_q][n_d]; else [n_pairs][2] of (a, b), scores [n_pairs].
 // mode bit 0: the mean over the query tokens instead of the sum.  Everything in device memory.

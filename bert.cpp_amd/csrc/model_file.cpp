@@ -148,6 +148,7 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
         c.p += len;
     }
     rel_bias = false;
+    token_dim = 0;
     if (vocab_only) {
         rel_bias = file_has_rel_bias(fname, (long)(c.p - blob.data()), sz);
         return true;
@@ -225,6 +226,29 @@ bool ModelFile::load(const char *fname, bool vocab_only, std::string &err) {
             total_tensor_bytes += nb;
             c.p += nb;
             rel_bias = true;
+            continue;
+        }
+        if (name == TOKEN_PROJ_NAME) {
+            // never quantised, like the relative position bias: f32 or f16 whatever the file-wide type
+            if (n_dims != 2 || ne[0] != hp.n_embd) {
+                err = "tensor '" + name + "' has wrong shape in model file: got [" + std::to_string(ne[0]) + ", " + std::to_string(ne[1]) + "], expected [" +
+                      std::to_string(hp.n_embd) + ", P]";
+                return false;
+            }
+            if (ne[1] < 32 || ne[1] > TOKEN_PROJ_MAX_DIM || ne[1] % 32 != 0) {
+                err = "tensor '" + name + "': a projection to " + std::to_string(ne[1]) + " dims, this library takes a multiple of 32 from 32 to " +
+                      std::to_string(TOKEN_PROJ_MAX_DIM);
+                return false;
+            }
+            if (ftype != W_F32 && ftype != W_F16) { err = "tensor '" + name + "' is stored in type " + std::to_string(ftype) + ": f32 or f16 expected"; return false; }
+            const size_t nb = wtype_row_bytes(ftype, ne[0]) * (size_t)ne[1];
+            if ((size_t)(c.end - c.p) < nb) { err = "tensor '" + name + "' is truncated"; return false; }
+            HostTensor t;
+            t.type = ftype; t.n_dims = n_dims; t.ne0 = ne[0]; t.ne1 = ne[1]; t.data = c.p; t.nbytes = nb;
+            tensors[name] = t;
+            total_tensor_bytes += nb;
+            c.p += nb;
+            token_dim = (int32_t)ne[1];
             continue;
         }
         if (ex == expect.end()) {

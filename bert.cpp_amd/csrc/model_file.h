@@ -16,6 +16,8 @@ enum WType : int32_t { W_F32 = 0, W_F16 = 1, W_Q4_0 = 2, W_Q4_1 = 3 };
 constexpr int HEAD_MAX_LABELS = 8;   // classifier.weight [H, n_labels]: 1 .. 8 labels
 constexpr int REL_BUCKETS = 32;      // encoder.relative_attention_bias.weight [n_head, 32]: MPNet's relative position buckets
 constexpr const char *REL_BIAS_NAME = "encoder.relative_attention_bias.weight";
+constexpr const char *TOKEN_PROJ_NAME = "linear.weight";   // a ColBERT checkpoint's projection head [P][n_embd], no bias
+constexpr int TOKEN_PROJ_MAX_DIM = 256;                    // P: a multiple of 32 in 32 .. 256 (token_proj.hip's accumulator blocks)
 
 struct HParams {             // reference bert.cpp:18-27, file order :361-367
     int32_t n_vocab = 0, n_max_tokens = 0, n_embd = 0, n_intermediate = 0, n_head = 0, n_layer = 0, f16 = 0;
@@ -44,6 +46,9 @@ struct ModelFile {
     // the file-wide type: never quantised; one table shared by all layers), behind the encoder's set; it may coexist with either head.
     // A vocab_only load finds it by walking the tensor records' headers: the tokenizer's [CLS] / [SEP] ids depend on it.
     bool rel_bias = false;
+    // the optional projection head of a ColBERT checkpoint (linear.weight [P][n_embd], f32 or f16 whatever the file-wide type: never
+    // quantised), behind the encoder's set; it may coexist with anything else.  token_dim: P, 0 = no head.  A vocab_only load ignores it.
+    int32_t token_dim = 0;
     bool legacy_q4 = false;                          // the file uses the 20 / 24-byte q4 blocks of early-2023 ggml
     std::vector<std::vector<uint8_t>> converted;     // their tensors, re-blocked into the current layout
 

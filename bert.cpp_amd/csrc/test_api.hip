@@ -986,6 +986,27 @@ int32_t bert_hip_test_token_rows(const void *x, int32_t is_f32, int32_t T, int32
     return 0;
 }
 
+int32_t bert_hip_test_token_project(const uint16_t *x, int32_t T, int32_t H, const uint16_t *wp, int32_t P, const int32_t *cu_seqlens, int32_t n_sentences,
+                                    int32_t max_len, int32_t flags, void *out) {
+    const char *me = "bert_hip_test_token_project";
+    if (!x || !wp || !cu_seqlens || !out || T < 1 || n_sentences < 1 || (flags & ~3)) return -1;
+    if (!token_project_supported(H, P)) return -2;
+    std::string err;
+    const int T_pad = (T + GEMM_BM - 1) / GEMM_BM * GEMM_BM;
+    const bool o16 = flags & TOKEN_ROWS_F16;
+    DevBuf dx, dw, dcu, dout;
+    if (!upload_rows16(dx, x, T, T_pad, H, err) || !dw.upload(wp, (size_t)P * H * 2, err) || !dcu.upload(cu_seqlens, (size_t)(n_sentences + 1) * 4, err) ||
+        !(o16 ? alloc_pad16(dout, (size_t)T * P, err) : alloc_pad32(dout, (size_t)T * P, err))) {
+        fprintf(stderr, "%s: %s\n", me, err.c_str());
+        return -1;
+    }
+    launch_token_project(dx.as<half_t>(), dw.as<half_t>(), T, H, P, dcu.as<int32_t>(), n_sentences, max_len, flags, dout.p, nullptr);
+    CK(hipGetLastError());
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(out, dout.p, (size_t)T * P * (o16 ? 2 : 4), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int32_t bert_hip_test_embed_ln_typed(int32_t table_type, int32_t H, int32_t n_vocab, int32_t n_pos, const void *word, const void *type,
                                      const void *pos, const float *gamma, const float *beta, const bert_vocab_id *tokens,
                                      const int32_t *cu_seqlens, int32_t n_sentences, int32_t max_len, const int32_t *first_len, int32_t form,

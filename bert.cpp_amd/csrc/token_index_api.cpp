@@ -52,10 +52,11 @@ int32_t token_text_chunks(bert_ctx *ctx, TokenIndex &x, int32_t n_threads, int32
 }
 
 // the pass of both text routes: each token's row over its L2 norm, f16, into d_rows; the embeddings stay in the engine
-Engine::Pass rows_pass(const int32_t *d_ids, const int32_t *d_cu, int nb, int T, int max_len, hipStream_t s, void *d_rows) {
+// (project: through the model's projection head — an index at the head's dim)
+Engine::Pass rows_pass(const int32_t *d_ids, const int32_t *d_cu, int nb, int T, int max_len, hipStream_t s, void *d_rows, bool project) {
     Engine::Pass pass;
     pass.d_tokens = d_ids; pass.d_cu = d_cu; pass.n_sentences = nb; pass.n_tokens = T; pass.max_len = max_len; pass.stream = s;
-    pass.d_token_rows = d_rows; pass.token_flags = TOKEN_ROWS_NORMALIZE | TOKEN_ROWS_F16;
+    pass.d_token_rows = d_rows; pass.token_flags = TOKEN_ROWS_NORMALIZE | TOKEN_ROWS_F16 | (project ? TOKEN_ROWS_PROJECT : 0);
     return pass;
 }
 
@@ -67,10 +68,15 @@ bool allow_ok(const TokenIndex &x, const uint32_t *allow, int32_t n_words, std::
     return false;
 }
 
-// what the text routes ask of the index (false + err otherwise)
-bool text_dim_ok(const bert_ctx *ctx, const TokenIndex &x, std::string &err) {
+// what the text routes ask of the index (false + err otherwise): the model's n_embd — the final states themselves —, or the dim of its
+// projection head (project: the pass goes through the head)
+bool text_dim_ok(const bert_ctx *ctx, const TokenIndex &x, bool &project, std::string &err) {
+    const Engine *e = ctx->engine();
+    project = false;
     if (x.dim() == ctx->hp.n_embd) return true;
+    if (e->token_dim() == x.dim() && e->token_rows_project_ok()) { project = true; return true; }
     err = "the index has dim " + std::to_string(x.dim()) + ", the model's n_embd is " + std::to_string(ctx->hp.n_embd);
+    if (e->token_dim() > 0) err += " and its projection head's " + std::to_string(e->token_dim()) + (e->token_dim() == x.dim() ? " (not on the f32 route)" : "");
     return false;
 }
 
@@ -132,7 +138,8 @@ int32_t bert_hip_token_index_add_device(struct bert_hip_token_index *ix, int32_t
 
 int32_t bert_hip_token_index_add_texts(struct bert_hip_token_index *ix, int32_t n_threads, int32_t n, const char **texts) {
     return token_index_call("bert_hip_token_index_add_texts", ix, [&](bert_ctx *ctx, TokenIndex &x, std::string &err) -> int32_t {
-        if (!text_dim_ok(ctx, x, err)) return -2;
+        bool project;
+        if (!text_dim_ok(ctx, x, project, err)) return -2;
         if (n < 0 || (n > 0 && !texts)) { err = "n >= 0 and texts required"; return -2; }
         const int first = x.size();
         if (n == 0) return first;
@@ -141,7 +148,7 @@ int32_t bert_hip_token_index_add_texts(struct bert_hip_token_index *ix, int32_t 
             [&](int32_t, int32_t nb, int32_t T, int32_t max_len, const int32_t *h_cu, const int32_t *d_ids, const int32_t *d_cu, char *) -> int32_t {
                 half_t *dst = x.append_room(T, err);
                 if (!dst) return err.rfind("add:", 0) == 0 ? -2 : -3;
-                if (eng->eval_packed_device(rows_pass(d_ids, d_cu, nb, T, max_len, x.stream(), dst), err) != 0) return -3;
+                if (eng->eval_packed_device(rows_pass(d_ids, d_cu, nb, T, max_len, x.stream(), dst, project), err) != 0) return -3;
                 const int32_t a = x.add_in_place(nb, h_cu, err);
                 return a < 0 ? a : 0;
             }, err);
@@ -173,7 +180,8 @@ int32_t bert_hip_token_index_search_device(struct bert_hip_token_index *ix, int3
 int32_t bert_hip_token_index_search_texts(struct bert_hip_token_index *ix, int32_t n_threads, int32_t n_queries, const char **texts, int32_t k, int32_t *ids,
                                           float *scores) {
     return token_index_call("bert_hip_token_index_search_texts", ix, [&](bert_ctx *ctx, TokenIndex &x, std::string &err) -> int32_t {
-        if (!text_dim_ok(ctx, x, err)) return -2;
+        bool project;
+        if (!text_dim_ok(ctx, x, project, err)) return -2;
         if (k < 1 || k > TokenIndex::MAX_K) { err = "1 <= k <= 256 required"; return -2; }
         if (n_queries < 0 || (n_queries > 0 && (!texts || !ids || !scores))) { err = "n_queries >= 0 and texts / outputs required"; return -2; }
         if (n_queries == 0) return 0;
@@ -183,7 +191,7 @@ int32_t bert_hip_token_index_search_texts(struct bert_hip_token_index *ix, int32
         std::vector<float> hsc((size_t)n_queries * k);
         const int32_t r = token_text_chunks(ctx, x, n_threads, n_queries, texts, x.max_query_tokens(), (size_t)x.dim() * 2,
             [&](int32_t i0, int32_t nb, int32_t T, int32_t max_len, const int32_t *, const int32_t *d_ids, const int32_t *d_cu, char *d_out) -> int32_t {
-                if (eng->eval_packed_device(rows_pass(d_ids, d_cu, nb, T, max_len, x.stream(), d_out), err) != 0) return -3;
+                if (eng->eval_packed_device(rows_pass(d_ids, d_cu, nb, T, max_len, x.stream(), d_out, project), err) != 0) return -3;
                 return x.search_device_to_host(nb, d_cu, (const half_t *)d_out, max_len, k, hid.data() + (size_t)i0 * k, hsc.data() + (size_t)i0 * k, err);
             }, err);
         if (r != 0) { if (err.empty()) err = "device error"; return r; }

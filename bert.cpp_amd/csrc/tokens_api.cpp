@@ -45,6 +45,19 @@ bool maxsim_shape_ok(const char *me, const void *q, const void *qcu, int32_t n_q
     return true;
 }
 
+// flags beyond `plain`, or the projection bit where the context cannot serve it: a line on stderr and false.  (A context without a head
+// refuses bit 2 as it refuses an unknown bit; the f32-exact route, whose states are f32, says why.)
+bool token_flags_ok(const bert_ctx *ctx, const char *me, int32_t flags, int32_t plain) {
+    const Engine *e = ctx->engine();
+    const int32_t known = plain | (e->token_dim() > 0 ? TOKEN_ROWS_PROJECT : 0);
+    if (flags & ~known) { fprintf(stderr, "%s: flags beyond %d\n", me, known); return false; }
+    if ((flags & TOKEN_ROWS_PROJECT) && !e->token_rows_project_ok()) {
+        fprintf(stderr, "%s: the projection head does not run on the f32 route (an f32 file without \"f32\" = \"f16\")\n", me);
+        return false;
+    }
+    return true;
+}
+
 // cu: n + 1 strictly ascending entries from 0 on (no empty sentence)
 bool cu_ok(const int32_t *cu, int32_t n) {
     bool ok = cu[0] >= 0;
@@ -68,10 +81,12 @@ int32_t bert_hip_eval_packed_tokens_device(struct bert_ctx *ctx, const bert_voca
         }
         // (launch_token_rows: a workgroup of 256 threads per four tokens in one launch, which holds fewer than 2^32 threads)
         if (n_tokens_total > TOKEN_ROWS_MAX_T) { fprintf(stderr, "%s: more than 2^25 tokens in one call\n", me); return -2; }
-        if ((flags & ~3) || (n_sentences > 0 && n_tokens_total > 0 && (!d_rows || !d_tokens || !d_cu_seqlens))) {
-            fprintf(stderr, "%s: flags 0 .. 3 and tokens, cu_seqlens, rows required\n", me);
+        if (!token_flags_ok(ctx, me, flags, 3)) return -2;
+        if (n_sentences > 0 && n_tokens_total > 0 && (!d_rows || !d_tokens || !d_cu_seqlens)) {
+            fprintf(stderr, "%s: tokens, cu_seqlens, rows required\n", me);
             return -2;
         }
+        if ((flags & TOKEN_ROWS_PROJECT) && ((uintptr_t)d_rows & 15)) { fprintf(stderr, "%s: projected rows must be 16-byte aligned\n", me); return -2; }
         std::string err;
         Engine::Pass pass;
         pass.d_tokens = d_tokens; pass.d_cu = d_cu_seqlens; pass.n_sentences = n_sentences; pass.n_tokens = n_tokens_total; pass.max_len = max_len; pass.stream = (hipStream_t)stream;
@@ -92,7 +107,8 @@ int32_t bert_hip_eval_packed_tokens(struct bert_ctx *ctx, const bert_vocab_id *t
         if (!ctx) return -1;
         const int32_t st = token_batch_status(ctx, me, tokens, cu_seqlens, n_sentences);
         if (st != 1) return st;
-        if ((flags & ~1) || !rows) { fprintf(stderr, "%s: flags 0 | 1 and rows required\n", me); return -2; }
+        if (!token_flags_ok(ctx, me, flags, 1)) return -2;
+        if (!rows) { fprintf(stderr, "%s: rows required\n", me); return -2; }
         std::string err;
         if (ctx->engine()->eval_packed_tokens_host(tokens, cu_seqlens, n_sentences, flags, rows, embeddings, err) != 0) {
             fprintf(stderr, "%s: %s\n", me, err.c_str());
@@ -107,7 +123,8 @@ int64_t bert_hip_encode_tokens_batch(struct bert_ctx *ctx, int32_t n_threads, in
     const char *me = "bert_hip_encode_tokens_batch";
     return guarded(me, [&]() -> int64_t {
         if (!ctx || !ctx->engine()) { fprintf(stderr, "%s: tokenizer-only context\n", me); return -1; }
-        if (n_inputs < 0 || (n_inputs > 0 && (!texts || !cu_out)) || (flags & ~1)) { fprintf(stderr, "%s: texts, cu_out and flags 0 | 1 required\n", me); return -2; }
+        if (n_inputs < 0 || (n_inputs > 0 && (!texts || !cu_out))) { fprintf(stderr, "%s: texts and cu_out required\n", me); return -2; }
+        if (!token_flags_ok(ctx, me, flags, 1)) return -2;
         if (cu_out) cu_out[0] = 0;
         if (n_inputs == 0) return 0;
         const size_t N = ctx->hp.n_max_tokens;
@@ -192,5 +209,7 @@ int32_t bert_hip_maxsim(struct bert_ctx *ctx, const float *q, const int32_t *qcu
         return 0;
     }, (int32_t)-4);
 }
+
+int32_t bert_hip_token_dim(struct bert_ctx *ctx) { return !ctx ? -1 : ctx->engine() ? ctx->engine()->token_dim() : 0; }
 
 }  // extern "C"

@@ -102,6 +102,12 @@ std::vector<float> tensor_as_f32(const HostTensor &t) {
     return v;
 }
 
+std::vector<_Float16> pack_token_proj_image(const HostTensor &t) {
+    std::vector<_Float16> img((size_t)t.ne0 * t.ne1);
+    for (int64_t r = 0; r < t.ne1; ++r) row_to_f16(t.type, t.ne0, t.data + wtype_row_bytes(t.type, t.ne0) * (size_t)r, img.data() + (size_t)r * t.ne0);
+    return img;
+}
+
 int rel_bias_bucket(int d) {
     static const int thr[8] = {8, 12, 16, 23, 32, 46, 64, 91};
     const int m = d < 0 ? -d : d, base = d > 0 ? REL_BUCKETS / 2 : 0;
@@ -457,6 +463,13 @@ std::unique_ptr<ModelWeights> ModelWeights::load(const ModelFile &mf, const Load
         ok = w->rel.upload(rel_bias_table(W.data(), hp.n_head, hp.n_max_tokens, 1.0), err) &&
              w->rel_scaled.upload(rel_bias_table(W.data(), hp.n_head, hp.n_max_tokens, std::sqrt((double)(H / hp.n_head))), err);
         w->rel_bias = ok;
+    }
+    // the projection head (ModelFile::load: [P][H], f32 or f16, P checked)
+    if (ok && mf.token_dim > 0) {
+        const HostTensor *wp = mf.find(TOKEN_PROJ_NAME);
+        if (!wp) { err = "the projection head is missing"; return nullptr; }
+        ok = w->token_proj.upload(pack_token_proj_image(*wp), err);
+        if (ok) w->token_dim = mf.token_dim;
     }
     if (!ok) return nullptr;
     return w;

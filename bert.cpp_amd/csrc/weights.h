@@ -88,6 +88,9 @@ std::vector<uint8_t> pack_mx_image(const _Float16 *img, int64_t N, int64_t K);
 std::vector<float> table_as_f32(const HostTensor &t);
 // any file tensor as f32 values [ne1][ne0]: f32 as stored, f16 widened, q4 as table_as_f32
 std::vector<float> tensor_as_f32(const HostTensor &t);
+// ModelWeights::token_proj: a ColBERT projection head (model_file.h TOKEN_PROJ_NAME, f32 or f16 in the file) as the f16 image [P][H]
+// token_proj.hip streams: the file's f16 bits, or its f32 values rounded once to nearest even
+std::vector<_Float16> pack_token_proj_image(const HostTensor &t);
 // MPNet's relative position bucket of the distance d = key - query (MPNetEncoder.relative_position_bucket with 32 buckets and
 // max_distance 128, in integers): keys behind the query take buckets 16 .. 31, distances below 8 a bucket each, the larger ones the
 // log-spaced ranges that start at 8, 12, 16, 23, 32, 46, 64 and 91
@@ -169,6 +172,10 @@ struct ModelWeights {
     // which scales the sum (rel_scaled).  One table for all layers.
     bool rel_bias = false;
     DevBuf rel, rel_scaled;
+    // The projection head of a ColBERT checkpoint, if the file has one (model_file.h; token_proj.hip): pack_token_proj_image, f16
+    // [token_dim][H].  token_dim == 0: no head, nothing uploaded.
+    int token_dim = 0;
+    DevBuf token_proj;
     // uploads to the current device
     static std::unique_ptr<ModelWeights> load(const ModelFile &mf, const LoadOptions &opt, std::string &err);
 };

@@ -41,6 +41,8 @@
 //   (--late: late-interaction search without a dense stage.  Every line's token rows go into a token index; each query line is answered
 //   by bert_hip_token_index_search_texts, the exact top-k of the MaxSim score over ALL lines.  A query of more tokens than the index's
 //   bert_hip_token_index_max_query_tokens is refused.  With -m, -f, -k, -t, --i8, --mxfp4, --save-tokens and --load-tokens only.)
+//   (a model with a projection head — a ColBERT checkpoint, bert_hip_token_dim > 0 —: the token index of --late and of --maxsim N
+//   --token-index is created at the head's dim and holds projected rows; the queries go through the head too.)
 //   (--i8 with --late or with --maxsim N --token-index: the token index is an int8 one (bert_hip_late_index_create with dtype 2: int8
 //   codes and a scale per token); --mxfp4 there: MXFP4 token rows, dtype 4; with --maxsim N --token-index the dense index is the int8 / mxfp4 one too, as --i8 says without a token
 //   index.  Not together with --save-tokens or --load-tokens: an int8 token index has no file form.)
@@ -360,7 +362,10 @@ int main(int argc, char **argv) {
                 return nullptr;
             }
         } else {
-            t = token_i8 || token_mx ? bert_hip_late_index_create(ctx, 0, dtype) : bert_hip_token_index_create(ctx, 0);
+            // (a model with a projection head — a ColBERT checkpoint — stores its projected rows: the index is created at the head's dim,
+            // and add_texts / search_texts run the pass through the head; 0: n_embd)
+            const int32_t tdim = bert_hip_token_dim(ctx) > 0 ? bert_hip_token_dim(ctx) : 0;
+            t = token_i8 || token_mx ? bert_hip_late_index_create(ctx, tdim, dtype) : bert_hip_token_index_create(ctx, tdim);
             if (!t || bert_hip_token_index_add_texts(t, n_threads, (int32_t)ptrs.size(), ptrs.data()) < 0) {
                 fprintf(stderr, "search: could not build the token index\n");
                 return nullptr;
@@ -532,11 +537,13 @@ int main(int argc, char **argv) {
             while (n_found < k && ids[n_found] >= 0) ++n_found;
             std::vector<const char *> lines{qp};
             for (int j = 0; j < n_found && !tx; ++j) lines.push_back(texts[ids[j]].c_str());
-            const int32_t n_in = (int32_t)lines.size(), H = bert_n_embd(ctx);
+            // (against a token index of projected rows the query goes through the head too: flags bit 2, rows of the head's dim)
+            const bool project = tx && bert_hip_token_dim(ctx) > 0;
+            const int32_t n_in = (int32_t)lines.size(), H = project ? bert_hip_token_dim(ctx) : bert_n_embd(ctx), tflags = project ? 1 | 4 : 1;
             std::vector<int32_t> cu((size_t)n_in + 1), pairs;
-            const int64_t total = bert_hip_encode_tokens_batch(ctx, n_threads, n_in, lines.data(), 1, cu.data(), nullptr, 0);
+            const int64_t total = bert_hip_encode_tokens_batch(ctx, n_threads, n_in, lines.data(), tflags, cu.data(), nullptr, 0);
             std::vector<float> rows(total > 0 ? (size_t)total * H : 0), ms((size_t)n_found);
-            bool ok = total > 0 && bert_hip_encode_tokens_batch(ctx, n_threads, n_in, lines.data(), 1, cu.data(), rows.data(), total) == total;
+            bool ok = total > 0 && bert_hip_encode_tokens_batch(ctx, n_threads, n_in, lines.data(), tflags, cu.data(), rows.data(), total) == total;
             if (ok && n_found > 0 && tx) {
                 // the candidates' scores from the stored rows, all n_found of them, back in the first stage's order
                 std::vector<int32_t> rid((size_t)n_found);

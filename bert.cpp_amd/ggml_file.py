@@ -189,6 +189,11 @@ REL_BIAS_NAME = "encoder.relative_attention_bias.weight"
 REL_BUCKETS = 32
 
 
+# The optional projection head of a ColBERT checkpoint (its linear.weight, [P][H], no bias), written behind everything else.  Never
+# quantised: it takes the file's type in f32 and f16 files and stays f16 in q4 files.  P: a multiple of 32 from 32 to 256.
+TOKEN_PROJ_NAME = "linear.weight"
+
+
 # how far below zero, in standard deviations of a logit, synthetic_weights draws cls.predictions.bias
 MLM_BIAS_SIGMAS = 1.1
 
@@ -310,7 +315,8 @@ def _encode_2d(a: np.ndarray, ftype: int) -> bytes:
 def write_model(path: str, hp: BertHParams, weights: Dict[str, np.ndarray], ftype: int,
                 vocab: Optional[Sequence[bytes]] = None, from_f16: bool = True, legacy_q4: bool = False) -> None:
     """Write a bert.cpp model file.  2-D tensors named '*weight' take `ftype`; 1-D stay f32.  The relative position bias
-    (REL_BIAS_NAME, if `weights` holds it) is never quantised: it stays f32 in q4 files, as the biases do.
+    (REL_BIAS_NAME, if `weights` holds it) is never quantised: it stays f32 in q4 files, as the biases do.  Nor is a ColBERT
+    projection head (TOKEN_PROJ_NAME, [P][H]): it is f16 in q4 files.
 
     For q4 types the source is first rounded through f16 when `from_f16` (the reference pipeline
     is HF -> f16 file -> quantize tool, models/run_conversions.sh + quantize.cpp:175-181).
@@ -338,15 +344,19 @@ def write_model(path: str, hp: BertHParams, weights: Dict[str, np.ndarray], ftyp
             names = names + MLM_HEAD_NAMES
         if REL_BIAS_NAME in weights:
             names = names + [REL_BIAS_NAME]
+        if TOKEN_PROJ_NAME in weights:
+            names = names + [TOKEN_PROJ_NAME]
         for name in names:
             a = np.asarray(weights[name], dtype=np.float32)
             want = head_shapes(hp, n_labels)[name] if name in HEAD_NAMES else mlm_head_shapes(hp)[name] if name in MLM_HEAD_NAMES else tensor_shape(name, hp)
             # (the table's shape is the reader's to judge: a file with another one can be written, and is refused at load)
-            assert a.shape == want or (name == REL_BIAS_NAME and a.ndim == 2), (name, a.shape)
+            assert a.shape == want or (name in (REL_BIAS_NAME, TOKEN_PROJ_NAME) and a.ndim == 2), (name, a.shape)
             two_d = a.ndim == 2
             t = ftype if two_d else FTYPE_F32
             if name == REL_BIAS_NAME and t in (FTYPE_Q4_0, FTYPE_Q4_1):
                 t = FTYPE_F32
+            if name == TOKEN_PROJ_NAME and t in (FTYPE_Q4_0, FTYPE_Q4_1):
+                t = FTYPE_F16
             nm = name.encode()
             f.write(struct.pack("<3i", a.ndim, len(nm), t))
             for i in range(a.ndim):
@@ -433,6 +443,18 @@ def hf_mlm_weights(state_dict, n_layer: int) -> Dict[str, np.ndarray]:
         return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
     sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in state_dict.items()}
     return {n: arr(sd[n]) for n in tensor_names(n_layer) + MLM_HEAD_NAMES}
+
+
+def hf_colbert_weights(state_dict) -> Dict[str, np.ndarray]:
+    """The tensors of a ColBERT checkpoint's state dict (colbert-ir/colbertv2.0 is one: a BERT encoder under 'bert.' and the bias-free
+    projection 'linear.weight' [P, H]) under this format's names: 'bert.' stripped, the projection under its own name
+    (TOKEN_PROJ_NAME); the pooler and position ids, if present, are dropped.  The layers are counted from the names.  Values may be torch
+    tensors or arrays."""
+    def arr(v):
+        return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+    sd = {(k[5:] if k.startswith("bert.") else k): v for k, v in state_dict.items()}
+    n_layer = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("encoder.layer."))
+    return {n: arr(sd[n]) for n in tensor_names(n_layer) + [TOKEN_PROJ_NAME]}
 
 
 # HuggingFace MPNet's per-layer names -> this format's (BERT's)

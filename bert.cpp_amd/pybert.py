@@ -38,6 +38,7 @@ BERT_HIP_H_SYMBOLS = [
     "bert_hip_eval_packed_grouped", "bert_hip_eval_packed_grouped_device", "bert_hip_tokenize_long", "bert_hip_plan_windows",
     "bert_hip_encode_long_batch", "bert_hip_index_add_long_texts",
     "bert_hip_eval_packed_tokens_device", "bert_hip_eval_packed_tokens", "bert_hip_encode_tokens_batch", "bert_hip_maxsim_device", "bert_hip_maxsim",
+    "bert_hip_token_dim",
     "bert_hip_n_labels", "bert_hip_tokenize_pair", "bert_hip_eval_packed_typed", "bert_hip_eval_packed_typed_device", "bert_hip_score_packed",
     "bert_hip_score_packed_device", "bert_hip_score_pairs",
     "bert_hip_has_mlm_head", "bert_hip_sparse_packed", "bert_hip_sparse_packed_device", "bert_hip_sparse_topk_packed",
@@ -72,6 +73,7 @@ BERT_HIP_TEST_H_SYMBOLS = [
     "bert_hip_test_model_digest", "bert_hip_test_pack_weight", "bert_hip_test_parse_devices", "bert_hip_test_gather_runs", "bert_hip_test_host_chunks",
     "bert_hip_test_encode_groups", "bert_hip_test_tokenize_pack", "bert_hip_test_index_header",
     "bert_hip_test_build_lists", "bert_hip_test_partition_header", "bert_hip_test_group_pool", "bert_hip_test_token_rows",
+    "bert_hip_test_token_project",
     "bert_hip_test_embed_ln_typed", "bert_hip_test_cls_head", "bert_hip_test_sparse_vocab", "bert_hip_test_sparse_topk",
     "bert_hip_test_sparse_vocab_geometry", "bert_hip_test_attention_grid", "bert_hip_test_sparse_scan_geometry",
     "bert_hip_test_sparse_index_header", "bert_hip_test_sparse_index_body",
@@ -187,6 +189,7 @@ def _declare_product_abi(L):
     L.bert_hip_encode_tokens_batch.argtypes = [vp, i32, i32, C.POINTER(C.c_char_p), i32, i32p, f32p, C.c_int64]
     L.bert_hip_maxsim_device.restype = i32; L.bert_hip_maxsim_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, i32, i32, vp, vp]
     L.bert_hip_maxsim.restype = i32; L.bert_hip_maxsim.argtypes = [vp, f32p, i32p, i32, f32p, i32p, i32, i32, i32p, i32, i32, f32p]
+    L.bert_hip_token_dim.restype = i32; L.bert_hip_token_dim.argtypes = [vp]
     L.bert_hip_n_labels.restype = i32; L.bert_hip_n_labels.argtypes = [vp]
     L.bert_hip_relative_attention.restype = i32; L.bert_hip_relative_attention.argtypes = [vp]
     L.bert_hip_tokenize_pair.restype = i32; L.bert_hip_tokenize_pair.argtypes = [vp, C.c_char_p, C.c_char_p, i32p, i32p, i32p, i32]
@@ -397,6 +400,8 @@ def test_lib() -> C.CDLL:
     L.bert_hip_test_build_lists.argtypes = [i32p, i32, i32, i32p, i32p]
     L.bert_hip_test_group_pool.restype = i32
     L.bert_hip_test_group_pool.argtypes = [vp, i32, i32p, i32p, i32, i32, i32, vp, i32p]
+    L.bert_hip_test_token_project.restype = i32
+    L.bert_hip_test_token_project.argtypes = [vp, i32, i32, vp, i32, i32p, i32, i32, i32, vp]
     L.bert_hip_test_token_rows.restype = i32
     L.bert_hip_test_token_rows.argtypes = [vp, i32, i32, i32, i32p, i32, i32, i32, vp]
     L.bert_hip_test_embed_ln_typed.restype = i32
@@ -695,6 +700,19 @@ def test_group_pool(rows: np.ndarray, weights, group_cu, raw: bool, out: Optiona
     if r != 0:
         raise RuntimeError(f"bert_hip_test_group_pool failed: {r}")
     return out, int(st[0])
+
+
+def test_token_project(x: np.ndarray, wp: np.ndarray, cu_seqlens, max_len: int, normalize: bool = True, f16_out: bool = False) -> np.ndarray:
+    """launch_token_project on final states x [T, H] float16 and a projection head wp [P, H] float16; returns the rows [T, P], float32
+    or (f16_out) float16.  Under test_pad the device copy's rows behind T and the output beforehand hold the patterns."""
+    assert x.dtype == np.float16 and wp.dtype == np.float16 and x.ndim == 2 and wp.ndim == 2 and x.shape[1] == wp.shape[1]
+    x = np.ascontiguousarray(x); wp = np.ascontiguousarray(wp); cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
+    out = np.zeros((x.shape[0], wp.shape[0]), dtype=np.float16 if f16_out else np.float32)
+    r = test_lib().bert_hip_test_token_project(x.ctypes.data, x.shape[0], x.shape[1], wp.ctypes.data, wp.shape[0], _i32p(cu), len(cu) - 1, max_len,
+                                               int(bool(normalize)) | 2 * int(bool(f16_out)), out.ctypes.data)
+    if r != 0:
+        raise RuntimeError(f"bert_hip_test_token_project failed: {r}")
+    return out
 
 
 def test_token_rows(x: np.ndarray, cu_seqlens, max_len: int, normalize: bool = True, f16_out: bool = False) -> np.ndarray:
@@ -1149,38 +1167,48 @@ class BertModel:
         return (out, nw) if return_windows else out
 
     # ---- token rows and late interaction ---------------------------------------------------
-    def eval_packed_tokens(self, tokens: np.ndarray, cu_seqlens: np.ndarray, normalize: bool = True, with_embeddings: bool = False):
+    @property
+    def token_dim(self) -> int:
+        """The dims of the model's projection head (a ColBERT checkpoint's linear.weight), 0 without one."""
+        return self.lib.bert_hip_token_dim(self.ctx)
+
+    def eval_packed_tokens(self, tokens: np.ndarray, cu_seqlens: np.ndarray, normalize: bool = True, with_embeddings: bool = False,
+                           project: bool = False):
         """The final state of every token of a packed batch (bert_hip_eval_packed_tokens): rows [n_tokens, n_embd] f32, each over its L2
-        norm if normalize; with_embeddings: (rows, embeddings [n_sentences, n_embd]), the embeddings eval_packed's bits."""
+        norm if normalize; with_embeddings: (rows, embeddings [n_sentences, n_embd]), the embeddings eval_packed's bits.  project: the
+        rows through the model's projection head, [n_tokens, token_dim], normalised behind it."""
         tokens = np.ascontiguousarray(tokens, dtype=np.int32)
         cu = np.ascontiguousarray(cu_seqlens, dtype=np.int32)
         B = len(cu) - 1
-        rows = np.full((int(cu[-1]), self.n_embd), np.nan, dtype=np.float32)
+        rows = np.full((int(cu[-1]), max(self.token_dim, 1) if project else self.n_embd), np.nan, dtype=np.float32)
         emb = np.full((B, self.n_embd), np.nan, dtype=np.float32) if with_embeddings else None
-        r = self.lib.bert_hip_eval_packed_tokens(self.ctx, _i32p(tokens), _i32p(cu), B, int(bool(normalize)), _f32p(rows),
+        r = self.lib.bert_hip_eval_packed_tokens(self.ctx, _i32p(tokens), _i32p(cu), B, int(bool(normalize)) | 4 * int(bool(project)), _f32p(rows),
                                                  _f32p(emb) if with_embeddings else None)
         if r != 0:
             raise RuntimeError(f"bert_hip_eval_packed_tokens failed: {r}")
         return (rows, emb) if with_embeddings else rows
 
     def eval_packed_tokens_device(self, d_tokens_ptr: int, d_cu_ptr: int, n_sentences: int, n_tokens: int, max_len: int, d_rows_ptr: int,
-                                  d_embeddings_ptr: Optional[int] = None, normalize: bool = True, f16: bool = False, stream: int = 0) -> None:
+                                  d_embeddings_ptr: Optional[int] = None, normalize: bool = True, f16: bool = False, stream: int = 0,
+                                  project: bool = False) -> None:
+        """project: rows of token_dim values through the projection head (flags bit 2) instead of n_embd."""
         r = self.lib.bert_hip_eval_packed_tokens_device(self.ctx, d_tokens_ptr, d_cu_ptr, n_sentences, n_tokens, max_len,
-                                                        int(bool(normalize)) | 2 * int(bool(f16)), d_rows_ptr, d_embeddings_ptr, stream)
+                                                        int(bool(normalize)) | 2 * int(bool(f16)) | 4 * int(bool(project)), d_rows_ptr,
+                                                        d_embeddings_ptr, stream)
         if r != 0:
             raise RuntimeError(f"bert_hip_eval_packed_tokens_device failed: {r}")
 
-    def encode_tokens(self, texts: Sequence[str], normalize: bool = True, n_threads: int = 6):
+    def encode_tokens(self, texts: Sequence[str], normalize: bool = True, n_threads: int = 6, project: bool = False):
         """Token rows of texts (bert_hip_encode_tokens_batch; tokenized and truncated as encode_batch does): (rows [n_tokens, n_embd] f32,
-        cu [n_texts + 1] int32)."""
+        cu [n_texts + 1] int32).  project: rows [n_tokens, token_dim] through the model's projection head."""
         n = len(texts)
         txt = (C.c_char_p * n)(*[t if isinstance(t, bytes) else t.encode("utf-8") for t in texts])
         cu = np.zeros(n + 1, dtype=np.int32)
-        flags = int(bool(normalize))
+        flags = int(bool(normalize)) | 4 * int(bool(project))
         total = self.lib.bert_hip_encode_tokens_batch(self.ctx, n_threads, n, txt, flags, _i32p(cu), None, 0)
         if total < 0:
             raise RuntimeError(f"bert_hip_encode_tokens_batch failed: {total}")
-        rows = np.full((total, self.n_embd), np.nan, dtype=np.float32)
+        rows = np.full((total, self.token_dim if project else self.n_embd), np.nan, dtype=np.float32)
         if self.lib.bert_hip_encode_tokens_batch(self.ctx, n_threads, n, txt, flags, _i32p(cu), _f32p(rows), total) != total:
             raise RuntimeError("bert_hip_encode_tokens_batch failed")
         return rows, cu

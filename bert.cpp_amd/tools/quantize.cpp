@@ -170,7 +170,8 @@ bool quantize_model(const char *in_path, const char *out_path, int32_t itype) {
         printf("%48s - [%5d, %5d], type = %6s ", name.c_str(), ne[0], ne[1], type_names[ttype]);
 
         // (MPNet's relative position bias, [32][n_head], is a 2-D "*weight" the engine never takes quantised: copied as it is)
-        const bool quantize = n_dims == 2 && ends_with(name, "weight") && name != "encoder.relative_attention_bias.weight";
+        // (so is a ColBERT checkpoint's projection head, linear.weight [P][H]: the f16 of the f16 file this tool is fed)
+        const bool quantize = n_dims == 2 && ends_with(name, "weight") && name != "encoder.relative_attention_bias.weight" && name != "linear.weight";
         size_t src_bytes;
         if (ttype == 0) src_bytes = (size_t)n_elem * 4;
         else if (ttype == 1) src_bytes = (size_t)n_elem * 2;

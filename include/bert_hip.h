@@ -305,6 +305,24 @@ BERT_API int32_t bert_hip_encode_long_batch(struct bert_ctx *ctx, int32_t n_thre
  *                              [total][n_embd] iff rows != NULL and cap_rows >= that count (rows NULL with cap_rows 0: a count call that
  *                              only tokenizes).  flags: bit 0 only.  Negative on an error (-1 without a device).
  *
+ * Projection head.  A ColBERT checkpoint is a BERT encoder followed by one bias-free linear layer that maps every token state to P
+ * dims, each row then divided by its L2 norm (colbertv2.0: 768 -> 128; answerai-colbert-small: 384 -> 96; mxbai-colbert-large: 1024 ->
+ * 128).  Model file: one optional tensor behind the encoder's set, linear.weight [P][n_embd] (ne0 = n_embd), f32 or f16 whatever the
+ * file-wide type — never q4; bert-quantize leaves it f16 —, P a multiple of 32 from 32 to 256 (another P: the load fails and says so).  It
+ * is kept in HBM as an f16 image (f32 values rounded once to nearest even).  A tokenizer-only context ignores it.  bert_hip_token_dim: P,
+ * 0 for a model without the head or a tokenizer-only context, -1 without a context.
+ *   flags bit 2 (4), all three entry points: rows[t] = Wp state[t], bert_hip_token_dim values instead of n_embd, in one launch that takes
+ *   the place of "token_rows" behind the pooling launch and reads the same states ("token_project" in bert_hip_profile_report; it
+ *   allocates nothing either).  f16 operands on v_mfma_f32_32x32x16_f16, f32 accumulation, k ascending in steps of 16 (k beyond n_embd
+ *   zero-filled).  Bit 0 normalises AFTER the projection: the row's 32 j + 8 g + 4 h + e-th values, h = 0 and h = 1, are two sums of
+ *   squares in f32 (each square rounded, ascending feature order), the h = 0 sum plus the h = 1 sum, 1 / sqrt, no epsilon (a zero row
+ *   gives NaN).  Bit 1 as above (device form: d_rows [n_tokens_total][P], 16-byte aligned).  The guard is the same.  The call's embeddings
+ *   stay bert_hip_eval_packed's bits, and a sentence's projected rows are the same alone and in any batch.
+ *   A context without the head refuses bit 2 as it refuses an unknown bit (-2, outputs untouched).  Not covered: the f32-exact route (an
+ *   f32 file without "f32" = "f16"), whose states are f32: bit 2 returns -2 there after a line on stderr.
+ *   Not built: ColBERT's query augmentation ([Q] / [D] marker tokens, [MASK] padding to 32 tokens) and its punctuation skip-list act on
+ *   token ids; the packed-id entry points let a caller apply them.
+ *
  * MaxSim.  Q [nq_tokens][H] and D [nd_tokens][H] are two packed sets of token rows with cumulative lengths qcu [n_q + 1] and dcu
  * [n_d + 1] (sentence a of Q is rows qcu[a] .. qcu[a + 1] - 1).  For a pair (a, b)
  *       score(a, b) = sum over the tokens i of a of ( max over the tokens j of b of <Q_i, D_j> ),
@@ -337,6 +355,7 @@ BERT_API int32_t bert_hip_eval_packed_tokens(struct bert_ctx *ctx, const bert_vo
                                              int32_t n_sentences, int32_t flags, float *rows, float *embeddings);
 BERT_API int64_t bert_hip_encode_tokens_batch(struct bert_ctx *ctx, int32_t n_threads, int32_t n_inputs, const char **texts, int32_t flags,
                                               int32_t *cu_out, float *rows, int64_t cap_rows);
+BERT_API int32_t bert_hip_token_dim(struct bert_ctx *ctx);
 BERT_API int32_t bert_hip_maxsim_device(struct bert_ctx *ctx, const void *d_q, const int32_t *d_qcu, int32_t n_q, const void *d_d,
                                         const int32_t *d_dcu, int32_t n_d, int32_t H, const int32_t *d_pairs, int32_t n_pairs, int32_t mode,
                                         float *d_scores, void *stream);
@@ -990,7 +1009,9 @@ BERT_API int32_t bert_hip_dense_sparse_search_inverted_texts(struct bert_hip_ind
  *   - Texts.  add_texts and search_texts tokenize as bert_encode_batch does, with the same truncation, and run the token-rows pass
  *     with flags 1 | 2 (each row over its L2 norm, f16) in chunks of BERT_HIP_CHUNK_TOKENS: add_texts writes straight into the index's
  *     storage, search_texts a device buffer the scan reads in place.  The stored bits are those of bert_hip_encode_tokens_batch
- *     (flags = 1) rounded to f16.  dim must equal n_embd (-2 otherwise); a query text of more than max_query_tokens tokens: -2.
+ *     (flags = 1) rounded to f16.  dim must equal n_embd, or, on a model with a projection head ("Projection head" above),
+ *     bert_hip_token_dim: the pass then runs with flags 1 | 2 | 4 and the projected rows go straight into the index's storage, its
+ *     quantiser or the query buffer (-2 for any other dim); a query text of more than max_query_tokens tokens: -2.
  *   - Streams.  search_device and rescore_device are asynchronous on the caller's stream; an index has ONE event, so its eagerly
  *     enqueued operations never overlap, whatever streams they were enqueued on.  Within the bounds of reserve (and, for rescore, where
  *     a call of the same shape has run before) they allocate nothing and may be captured into a graph: STREAM CAPTURE AND GRAPHS above.

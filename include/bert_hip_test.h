@@ -262,6 +262,14 @@ BERT_API int32_t bert_hip_test_build_lists(const int32_t *list_of, int32_t n, in
 BERT_API int32_t bert_hip_test_token_rows(const void *x, int32_t is_f32, int32_t T, int32_t H, const int32_t *cu_seqlens, int32_t n_sentences,
                                           int32_t max_len, int32_t flags, void *out);
 
+/* launch_token_project on its own (kernels.h; bert_hip.h "Projection head"): x [T][H] f16 bits, the final states of a pass; wp [P][H] f16
+ * bits, the head's image; cu_seqlens, max_len as above; flags bits 0 and 1 (the projection itself is what the entry does); out [T][P],
+ * f16 bits with flags bit 1, else f32.  Host buffers in and out.  The device copy of x has its rows rounded up to whole 128-token
+ * tiles: the rows behind T, and every word of the output before the launch, hold the patterns of bert_hip_test_set_pad.  0; -1 after a
+ * line on stderr; -2 for an (H, P) the kernel does not take (H % 8 == 0, P a multiple of 32 in 32 .. 256).                          */
+BERT_API int32_t bert_hip_test_token_project(const uint16_t *x, int32_t T, int32_t H, const uint16_t *wp, int32_t P, const int32_t *cu_seqlens,
+                                             int32_t n_sentences, int32_t max_len, int32_t flags, void *out);
+
 /* The embedding kernels with token types (bert_hip.h "sentence pairs and scores"): the arguments of bert_hip_test_embed_ln, _embed_ln_lanes
  * and _f32_embed_ln, plus first_len [n_sentences] (nullable: the untyped instantiation; any value is legal, type [2][H] has both rows
  * read) and the form: 0 the rows kernel on its (group, sentence) grid, 1 the rows kernel with the bisection, 2 the generic kernel, 3 the
